@@ -285,6 +285,36 @@ def free_batches(torch, *batches):
                 m.close()
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6
+
+
+def dump_outputs(torch, out_dir, planes, seed=0xD0D0):
+    """--dump-outputs: the planes the timed path hands its caller after its last step, as float32 .npy files in out_dir, so that two builds
+    can be compared output for output.  Per plane `name` of the (frames, rows, cols) batch: <name>_frame.npy, the whole plane of one frame
+    picked by the seed, and <name>_sample.npy, the samples at seeded flat indices over the whole batch (sorted, drawn with replacement),
+    the plane's share of what is left of DUMP_LIMIT_BYTES.  The picks depend only on the seed and the shapes.  Returns what the result line
+    records about the dump."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(seed)
+    frame = int(rng.integers(0, planes[0][1].shape[0]))
+    frame_bytes = sum(4 * t[frame].numel() for _, t in planes)
+    total = sum(t.numel() for _, t in planes)
+    per_elem = (DUMP_LIMIT_BYTES - frame_bytes - 2 * 4096 * len(planes)) / 4 / total
+    assert per_elem > 0, "one frame of the output does not fit the dump"
+    written = 0
+    for name, t in planes:
+        k = min(t.numel(), int(per_elem * t.numel()))
+        idx = np.sort(rng.integers(0, t.numel(), k))
+        sample = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        for suffix, a in (("frame", t[frame].cpu().numpy()), ("sample", sample)):
+            path = os.path.join(out_dir, "%s_%s.npy" % (name, suffix))
+            np.save(path, a.astype(np.float32))
+            written += os.path.getsize(path)
+    assert written <= DUMP_LIMIT_BYTES, written
+    return {"dir": out_dir, "bytes": written, "frame": frame, "seed": seed}
+
+
 def place_best(torch, make, measure, free, tries, good_ms):
     """Where a buffer lies in HBM decides between two speeds for the same launch on this part (nv12 -> 4K: 0.58 and 0.63 - 0.67 of the peak; which
     physical pages an allocation gets, not its virtual address: profiles/r06_alloc_vmm_sweep_*.txt, r06_arena_offset_sweep.txt).  A resident
@@ -1204,7 +1234,7 @@ def h264_intra_formats_leg(torch, dev, ev, h264):
 def h264_picture_leg(torch, dev, ev):
     """the picture layer: synthetic 1080p P-pictures (tools/h264_synth.py) through ffhip_h264_picture_flush — MC,
     residual add and the in-loop filter in decoder order.  A lone picture is a chain of latency-bound kernels; 16 pictures in flight,
-    each on its own stream and host thread, fill the hardware queues (GPU_MAX_HW_QUEUES, see main())."""
+    each on its own stream and host thread, share the process's hardware queues (GPU_MAX_HW_QUEUES, from the environment)."""
     import threading
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
     from h264_synth import record_p_picture
@@ -1269,7 +1299,7 @@ def h264_picture_leg(torch, dev, ev):
                                            "pictures_per_s_16_in_flight": round(1e3 * npic / res[npic], 1),
                                            "ms_per_batched_flush_of_16": round(res["batch"], 3),
                                            "pictures_per_s_batched_flush_of_16": round(1e3 * npic / res["batch"], 1),
-                                           "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)"),
+                                           "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default"),
                                            "note": "P-pictures: qpel + chroma MC, idct_add on ~half of the blocks, deblocking in decoder order; one stream and host thread per picture"}}
 
 
@@ -1470,6 +1500,9 @@ def single_process(args, torch, S, _lib):
     [t.join() for t in ths]
     sync_all()
     assert all(float(st_[2][0][:1].to(torch.float64).sum().item()) > 0 for st_ in state)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(torch, args.dump_outputs, [("y", state[0][2][0]), ("uv", state[0][2][1])])
 
     # strong leg: `n` frames on member 0, scattered over xGMI, converted on every member, gathered back
     strong = None
@@ -1533,6 +1566,8 @@ def single_process(args, torch, S, _lib):
     }
     if strong is not None:
         line["strong"] = strong
+    if dumped is not None:
+        line["dump"] = dumped
     print(json.dumps(line), flush=True)
     for st_ in state:
         st_[0].close()
@@ -1567,13 +1602,13 @@ def main():
     ap.add_argument("--single-process", action="store_true",
                     help="ONE process drives --gpus N devices through the C ABI (one host thread + FFHipDeviceSet member per GPU) "
                          "instead of one torchrun rank per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0 / member 0: one whole frame and a seeded sample of "
+                         "the batch, per plane) as float32 .npy files under DIR, at most 60 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
-    # one rank, many streams (the picture-layer leg of the extras): the HIP runtime folds all streams of a process onto
-    # GPU_MAX_HW_QUEUES hardware queues, 4 by default; 16 is the measured optimum there.  Read at runtime
-    # initialisation, hence before torch is imported; the timed headline runs on one stream and does not depend on it.
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     import torch
     import torch.distributed as dist
     from ffmpeg_amd import swscale as S, _lib
@@ -1675,6 +1710,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(torch, args.dump_outputs, [("y", dst[0]), ("uv", dst[1])])
     # (3) SUSTAINED: back-to-back launches for >= sustain_ms right after, one event pair around each block of 64 (rank 0 reports its own)
     sust_ms, sust_n, sust_wall = None, 0, 0.0
     if args.sustain_ms > 0:
@@ -1853,6 +1891,8 @@ def main():
         if cpu is not None:
             line["cpu_baseline"] = cpu
         line["roofline"] = roof
+        if dumped is not None:
+            line["dump"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -5,7 +5,9 @@
   The product library is bound in ffmpeg_amd/_lib.py, never here.
 """
 import ctypes as C
+import hashlib
 import os
+import zlib
 
 import numpy as np
 
@@ -260,13 +262,53 @@ def oracle():
     return _oracle
 
 
+PINS_NPZ = os.path.join(ROOT, "tests", "golden", "pins.npz")
+PIN_RECORD = None       # tools/make_pins.py: a dict that collects the digests instead of checking them
+_pins = None
+
+
+def stable_seed(*key):
+    """a seed from a parameter tuple that is the same in every process (hash() of a str is not)"""
+    return zlib.crc32(repr(key).encode()) & 0xFFFFFF
+
+
+class Pin:
+    """sha256 over the outputs a reference-backed test compares, against the digest tests/golden/pins.npz holds for the case.  Where
+    oracle/_ref is not built the test pins the oracle's outputs; where it is, the reference's (which the test also holds equal to the
+    oracle's), so a digest that does not describe the reference's outputs fails wherever the reference is built."""
+
+    def __init__(self, key):
+        self.key, self.h = key, hashlib.sha256()
+
+    def add(self, *arrays):
+        for a in arrays:
+            a = np.ascontiguousarray(a)
+            self.h.update(("%s%s" % (a.dtype.str, a.shape)).encode())
+            self.h.update(a.tobytes())
+
+    def check(self):
+        global _pins
+        d = self.h.hexdigest()
+        if PIN_RECORD is not None:
+            PIN_RECORD[self.key] = d
+            return
+        if _pins is None:
+            z = np.load(PINS_NPZ)
+            _pins = dict(zip(z["keys"].tolist(), z["digests"].tolist()))
+        assert self.key in _pins, "no digest recorded for " + self.key
+        assert d == _pins[self.key], self.key + ": the outputs differ from the recorded ones"
+
+
 def have_ref():
     return os.path.exists(REF_SO)
 
 
 def ref():
+    """The reference library, or None where it is not built (it needs the reference's source tree at build time)."""
     global _ref
     if _ref is None:
+        if not have_ref():
+            return None
         L = C.CDLL(REF_SO)
         L.ffref_sws_create.argtypes = [C.c_int] * 8
         L.ffref_sws_create.restype = C.c_void_p

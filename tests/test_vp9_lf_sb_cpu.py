@@ -37,11 +37,13 @@ CASES = [(bd, ss, kind, seed) for bd in (8, 10, 12) for ss in (1, 0) for kind in
 
 @pytest.mark.parametrize("bd,ss,kind,seed", CASES)
 def test_oracle_vs_reference(bd, ss, kind, seed):
+    """the oracle == the reference where oracle/_ref is built; everywhere, the samples hash to the case's digest in tests/golden/pins.npz"""
     R = ffi.ref()
-    if R is None or not hasattr(R, "ffref_vp9_loopfilter_sb"):
-        pytest.skip("oracle/_ref not built")
+    if R is not None and not hasattr(R, "ffref_vp9_loopfilter_sb"):
+        pytest.skip("oracle/_ref predates ff_vp9_loopfilter_sb")
     O = ffi.oracle()
-    rng = np.random.default_rng(hash((bd, ss, kind, seed)) & 0xFFFFFF)
+    pin = ffi.Pin("vp9_lf_sb/%d-%d-%s-%d" % (bd, ss, kind, seed))
+    rng = np.random.default_rng(ffi.stable_seed(bd, ss, kind, seed))
     lim, mblim = G.filter_lut(int(rng.integers(0, 8)))
     for row, col in ((0, 0), (0, 8), (8, 0), (8, 8)):
         f = G.structured(rng, row // 8, col // 8, 24 - int(rng.integers(0, 3)), 24 - int(rng.integers(0, 3)), ss, ss) if kind == "structured" \
@@ -55,10 +57,13 @@ def test_oracle_vs_reference(bd, ss, kind, seed):
         args = (bd, ss, ss, ptr(level, u8p), ptr(mask, u8p), row, col)
         O.ffo_vp9_loopfilter_sb(*args, *(C.cast(_at(p, k, k), u8p) for p, k in zip(a, (64, m, m))), a[0].strides[0], a[1].strides[0],
                                 ptr(lim, u8p), ptr(mblim, u8p))
-        R.ffref_vp9_loopfilter_sb(*args, *(C.cast(_at(p, k, k), u8p) for p, k in zip(b, (64, m, m))), b[0].strides[0], b[1].strides[0],
-                                  ptr(lim, u8p), ptr(mblim, u8p))
-        for p, q in zip(a, b):
-            assert np.array_equal(p, q)
+        if R is not None:
+            R.ffref_vp9_loopfilter_sb(*args, *(C.cast(_at(p, k, k), u8p) for p, k in zip(b, (64, m, m))), b[0].strides[0], b[1].strides[0],
+                                      ptr(lim, u8p), ptr(mblim, u8p))
+            for p, q in zip(a, b):
+                assert np.array_equal(p, q)
+        pin.add(*a)
+    pin.check()
 
 
 @pytest.mark.parametrize("bd,kind,seed", [(bd, kind, seed) for bd in (8, 10) for kind in ("structured", "bits0", "bits1", "bits2") for seed in range(4)])
@@ -117,11 +122,12 @@ def test_422_440_oracle_reference_and_ctables(bd, ss, kind, seed):
     from ffmpeg_amd import _lib
     L = _lib.lib()
     R = ffi.ref()
-    if R is None or not hasattr(R, "ffref_vp9_loopfilter_sb"):
-        pytest.skip("oracle/_ref not built")
+    if R is not None and not hasattr(R, "ffref_vp9_loopfilter_sb"):
+        pytest.skip("oracle/_ref predates ff_vp9_loopfilter_sb")
     O = ffi.oracle()
     ss_h, ss_v = ss
-    rng = np.random.default_rng(hash((bd, ss, kind, seed, 11)) & 0xFFFFFF)
+    pin = ffi.Pin("vp9_lf_sb_422_440/%d-%d%d-%s-%d" % (bd, ss_h, ss_v, kind, seed))
+    rng = np.random.default_rng(ffi.stable_seed(bd, ss, kind, seed, 11))
     lim, mblim = G.filter_lut(int(rng.integers(0, 8)))
     dt = np.uint8 if bd == 8 else np.uint16
     cw, chh = 64 >> ss_h, 64 >> ss_v
@@ -139,10 +145,12 @@ def test_422_440_oracle_reference_and_ctables(bd, ss, kind, seed):
         pos = ((64, 64), (chh, cw), (chh, cw))
         O.ffo_vp9_loopfilter_sb(*args, *(C.cast(_at(p, r, k), u8p) for p, (r, k) in zip(a, pos)), a[0].strides[0], a[1].strides[0], ptr(lim, u8p),
                                 ptr(mblim, u8p))
-        R.ffref_vp9_loopfilter_sb(*args, *(C.cast(_at(p, r, k), u8p) for p, (r, k) in zip(b, pos)), b[0].strides[0], b[1].strides[0], ptr(lim, u8p),
-                                  ptr(mblim, u8p))
-        for p, q in zip(a, b):
-            assert np.array_equal(p, q)
+        if R is not None:
+            R.ffref_vp9_loopfilter_sb(*args, *(C.cast(_at(p, r, k), u8p) for p, (r, k) in zip(b, pos)), b[0].strides[0], b[1].strides[0],
+                                      ptr(lim, u8p), ptr(mblim, u8p))
+            for p, q in zip(a, b):
+                assert np.array_equal(p, q)
+        pin.add(*a)
         tab, ctab = np.zeros(320, np.uint32), np.zeros(128, np.uint32)
         rt = L.ffhip_vp9_lf_sb_tables(tab.ctypes.data, f.ctypes.data if hasattr(f, "ctypes") else np.ascontiguousarray(f).ctypes.data, row, col, ss_h,
                                       ss_v, lim.ctypes.data, mblim.ctypes.data)
@@ -157,3 +165,4 @@ def test_422_440_oracle_reference_and_ctables(bd, ss, kind, seed):
             assert np.array_equal(p, q)
         changed += sum(int((p != q).sum()) for p, q in zip(a[1:], before[1:]))
     assert changed > 0 or kind != "structured"
+    pin.check()

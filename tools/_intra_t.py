@@ -1,6 +1,6 @@
 import ctypes as C, subprocess, sys, os, runpy
 sys.argv = ["run_intra_batch.py", "1", "1"]
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ffmpeg_amd import _lib
 L = _lib.lib()
 runpy.run_path("tools/run_intra_batch.py", run_name="__main__")

@@ -1,5 +1,5 @@
 import json, os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ffmpeg_amd import _lib as _fflib  # noqa: E402
 _fflib.select("measure")  # the FFHIP_* knobs this tool sets exist only in libffhip_measure.so

@@ -3,7 +3,7 @@ experiments through FFHIP_DEBLOCK_FAULT (2: no picture stores, 4: no filters, 8:
 measurement only) and FFHIP_DEBLOCK_BAND (rows per workgroup; 0 = the launcher's own choice), 4K luma planes."""
 import json, os, sys
 import numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ffmpeg_amd import _lib as _fflib  # noqa: E402
 _fflib.select("measure")  # the FFHIP_* knobs this tool sets exist only in libffhip_measure.so

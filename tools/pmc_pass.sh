@@ -3,7 +3,7 @@
 # Instruction mix of the kernels whose name contains the substring: rocprofv3 PMC pass (counters only, with the kernel trace), summed
 # over the launches of the command and divided by their number.  Run on the GPU box (gpurun); the summary goes to <out-file>.
 pat="$1"; out="$2"; shift 3
-root="${GRAFT_REPO_ROOT:-/root/repo}"
+root="$(cd "$(dirname "$0")/.." && pwd)"
 dir="$root/gpurun_out/pmc_insts"
 rm -rf "$dir"; mkdir -p "$dir"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --pmc $COUNTERS \

@@ -1,6 +1,5 @@
 import os, sys, json
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 dev = torch.device("cuda", 0)
 ev = lambda: torch.cuda.Event(enable_timing=True)
