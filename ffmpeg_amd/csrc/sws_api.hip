@@ -6,15 +6,121 @@
  *   SwsFunc c->convert_unscaled / whole-frame scale -> ffhip_sws_scale() (swscale_internal.h:99-101, swscale.c:1185)
  *   batched device-resident frames        -> ffhip_sws_scale_batch_dev() (no reference equivalent)
  */
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <stdlib.h>
 #include <string.h>
+#include <utility>
 #include <vector>
 
 #include "kernels/common.h"
 #include "kernels/sws_kernels.h"
 #include "kernels/shim_arena.h"
+
+/* device memory a context owns: one hipMalloc, freed with its holder */
+struct DevBlock {
+    void *p = nullptr;
+    DevBlock() = default;
+    DevBlock(const DevBlock &) = delete;
+    DevBlock &operator=(const DevBlock &) = delete;
+    DevBlock(DevBlock &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBlock &operator=(DevBlock &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~DevBlock() { if (p) (void)hipFree(p); }
+};
+
+/* a buffer that grows on demand: one too small is replaced once the device work that may still read it has finished */
+static hipError_t grow(DevBlock &b, size_t &sz, size_t need)
+{
+    if (need <= sz)
+        return hipSuccess;
+    if (b.p) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            return e;
+    }
+    b = DevBlock();
+    sz = 0;
+    const hipError_t e = hipMalloc(&b.p, need);
+    if (e == hipSuccess)
+        sz = need;
+    return e;
+}
+
+struct HostPart { const void *p; size_t bytes; };
+template <class T> static HostPart part(const std::vector<T> &v) { return { v.data(), v.size() * sizeof(T) }; }
+
+/* banks to the device: the parts in one block, each at an offset rounded up to `align` (the block ends on it too, then `tail` bytes more:
+ * some kernels read ahead past a bank); at[k] is part k's device address.  False, and `blk` as it was, when the block cannot be had. */
+static bool upload(DevBlock &blk, const HostPart *parts, int n, size_t align, void **at, size_t tail = 0)
+{
+    size_t end = 0;
+    for (int k = 0; k < n; k++)
+        end = ((end + align - 1) & ~(align - 1)) + parts[k].bytes;
+    DevBlock b;
+    if (hipMalloc(&b.p, ((end + align - 1) & ~(align - 1)) + tail) != hipSuccess)
+        return false;
+    size_t off = 0;
+    for (int k = 0; k < n; k++) {
+        off = (off + align - 1) & ~(align - 1);
+        at[k] = static_cast<uint8_t *>(b.p) + off;
+        if (parts[k].bytes && hipMemcpy(at[k], parts[k].p, parts[k].bytes, hipMemcpyHostToDevice) != hipSuccess)
+            return false;
+        off += parts[k].bytes;
+    }
+    blk = std::move(b);
+    return true;
+}
+static bool upload(DevBlock &blk, std::initializer_list<HostPart> parts, size_t align, void **at, size_t tail = 0)
+{
+    return upload(blk, parts.begin(), (int)parts.size(), align, at, tail);
+}
+
+/* four banks (filter, positions) as eight parts, each padded to `align`: the device view in d[] */
+static bool upload_banks(DevBlock &blk, const std::vector<int16_t> f[4], const std::vector<int32_t> p[4], size_t align, FFHipDevFilter d[4])
+{
+    HostPart parts[8];
+    void *at[8];
+    for (int i = 0; i < 4; i++) {
+        parts[2 * i] = part(f[i]);
+        parts[2 * i + 1] = part(p[i]);
+    }
+    if (!upload(blk, parts, 8, align, at))
+        return false;
+    for (int i = 0; i < 4; i++) {
+        d[i].filter = static_cast<const int16_t *>(at[2 * i]);
+        d[i].pos = static_cast<const int32_t *>(at[2 * i + 1]);
+    }
+    return true;
+}
+
+/* a per-context intermediate, one batch in flight: acquire() locks it, makes the caller's stream wait for the last launch that read it
+ * (whatever its stream) and grows it; the lease records, when it ends, the stream of the last consumer launch as the new last reader */
+struct Scratch {
+    DevBlock buf;
+    size_t sz = 0;
+    std::mutex mu;
+    hipEvent_t done = nullptr;
+    ~Scratch() { if (done) (void)hipEventDestroy(done); }
+};
+struct ScratchLease {
+    Scratch *s = nullptr;
+    hipStream_t stream = nullptr;
+    std::unique_lock<std::mutex> lk;
+    ~ScratchLease() { if (s) (void)hipEventRecord(s->done, stream); }
+};
+static hipError_t acquire(Scratch &s, ScratchLease &l, size_t need, hipStream_t stream)
+{
+    l.lk = std::unique_lock<std::mutex>(s.mu);
+    hipError_t e = s.done ? hipStreamWaitEvent(stream, s.done, 0) : hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
+    if (e == hipSuccess)
+        e = grow(s.buf, s.sz, need);
+    if (e == hipSuccess) {
+        l.s = &s;
+        l.stream = stream;
+    }
+    return e;
+}
 
 /* a packed 8-bit RGB source (round 6, kernels/sws_rgbin.hip): the context is that of the 14-bit planar source its converter lines make */
 struct FFHipSwsRgbIn {
@@ -22,14 +128,12 @@ struct FFHipSwsRgbIn {
     int half = 0;           /* the chroma converters average pixel pairs (4:2:2 lines) */
     int direct_c = 0;       /* ... the chroma banks the identity as well (a planar 4:2:2 / 4:4:4 target at the source's size): one elementwise pass */
     int fused420 = 0;       /* ... and the chroma too: RGB -> yuv420p / NV12 at the source's size in one kernel (k_sws_rgb420); vfv: its vertical chroma bank on the device */
-    uint32_t *vfv = nullptr;
+    DevBlock vfv;
     int y_direct = 0;       /* identity luma banks into an 8-bit plane on the walker: the converter pass writes the target's luma, the walker the chroma */
     int fmt = 0;            /* the caller's source format */
     int ofs[3] = { 0, 0, 0 };
     int32_t table[9] = {};
-    void *planes = nullptr; /* device: the converter lines of the batch in flight (Y, U, V, uint16) */
-    size_t planes_sz = 0;
-    void *stage = nullptr;  /* device: the host face's packed source rows */
+    DevBlock stage;         /* device: the host face's packed source rows */
     size_t stage_sz = 0;
 };
 static void rgb_in_plan_luma(struct FFHipSwsContext *c);
@@ -40,8 +144,8 @@ struct FFHipSwsContext {
     FFHipSwsRgbIn rgb_in;
     int hrgb_seed0 = 0;  /* a deeper source into packed RGB whose rows all take yuv2rgb_2 (two-tap vertical banks): no rounding term in the sums */
     int widen8 = 0;      /* an 8-bit source into a 9..14-bit target on the 16-bit walker: its planes are widened to 16-bit samples first (k_sws_widen8) */
-    void *widen_tmp = nullptr;
-    size_t widen_tmp_sz = 0;
+    Scratch widen_tmp;
+    Scratch rgb_in_planes; /* an RGB source: the converter lines of the batch in flight (Y, U, V, uint16) */
     bool rgb_in_luma_done = false; /* the call in flight (under mu): the converter pass wrote the target's luma plane, the walker skips its luma job */
     int flat_dither = 0; /* an 8-bit target's dither entries are all 64 (an RGB source is not dithered: swscale.c:291 looks at the source format) */
     int hbd_sw = 320, hbd_rows = 96; /* LDS shape the banks need: samples per staged source row, source rows per 32-row tile */
@@ -49,7 +153,7 @@ struct FFHipSwsContext {
     FFHipSwsTables t;
     std::vector<int16_t> f[4];
     std::vector<int32_t> p[4];
-    void *dev_tables = nullptr;
+    DevBlock dev_tables;
     FFHipDevFilter d[4];
     int unscaled_yuv2rgb = 0;
     FFHipYuv2RgbK k;
@@ -59,7 +163,7 @@ struct FFHipSwsContext {
     /* banks as the fast path sees them: sizes 1..3 zero-padded to 4 taps (same sums, positions kept in range) */
     std::vector<int16_t> nf[4];
     std::vector<int32_t> np[4];
-    void *dev_ntables = nullptr;
+    DevBlock dev_ntables;
     FFHipDevFilter dn[4];
     int cw_ok = 0; /* both bank pairs fit the column-walking fast path (sws_colwalk.hip) */
     int cw_opt = 0; /* ... and no horizontal sum can wrap int16: the hand-scheduled variant applies */
@@ -70,18 +174,17 @@ struct FFHipSwsContext {
     int lw_ok = 0, lw_ht = 0, lw_vt = 0;
     std::vector<int16_t> wf[4];
     std::vector<int32_t> wp[4];
-    void *dev_wtables = nullptr;
+    DevBlock dev_wtables;
     FFHipDevFilter dw[4];
     /* exact-2x fast path (sws_up2.hip): virtual banks (regular windows of the edge-replicated rows) on the device */
     /* the column walker above 8 bits (sws_walk16.hip): banks padded to w16_ht x w16_vt taps on the device */
     int w16_ok = 0, w16_ht = 0, w16_vt = 0;
-    void *w16_dev = nullptr;
+    DevBlock w16_dev;
     int w16_span[2][3] = {};           /* [luma, chroma][a plane job (256 columns), a pair job on planes (128), a pair job on an interleaved plane] */
-    const int16_t *w16_f[4] = { nullptr, nullptr, nullptr, nullptr };
-    const int32_t *w16_p[4] = { nullptr, nullptr, nullptr, nullptr };
+    FFHipDevFilter w16[4] = {};        /* (filter and positions only) */
     int up2_ok = 0;
     int up2_rc = 0; /* a range-converting context: the exact-2x kernel with the range stage is its only fast kernel */
-    void *up2_dev = nullptr;
+    DevBlock up2_dev;
     const uint32_t *up2_h[2] = { nullptr, nullptr }, *up2_v[2] = { nullptr, nullptr };
     /* launch tuner of the table converter (round 6): which workgroup numbering of k_yuv420p_rgb24_t is faster is a property of the BOX
      * (profiles/r06_arena_offset_sweep.txt, r06_xcd_numbering_sweep.txt: eighth-per-XCD +1 .. +8 % on some, -4 % on others, whatever the
@@ -92,18 +195,15 @@ struct FFHipSwsContext {
     int up2_hco_ok[2] = { 0, 0 };
     /* 4:2:0 into packed RGB at the source's size through the scaler (sws_eqrgb.hip): the virtual vertical chroma bank on the device */
     int eqr_ok = 0;
-    void *eqr_dev = nullptr;
+    DevBlock eqr_dev;
     /* a scaled packed-RGB target in two stages (lw_ok on an RGB context; sws_lwalk.hip with an int16 luma plane, then sws_y16rgb.hip):
      * the intermediate planes, grown on demand — a context is used by one caller at a time, as an SwsContext is */
-    void *rgb2_tmp = nullptr;
-    size_t rgb2_tmp_sz = 0;
-    hipEvent_t rgb2_done = nullptr; /* the last launch that read the intermediate: the next use waits for it, whatever its stream */
-    std::mutex rgb2_mu;             /* (its own lock: the host face reaches this path holding `mu`) */
+    Scratch rgb2_tmp;               /* (its own lock: the host face reaches this path holding `mu`) */
     hipStream_t rgb2_aux = nullptr; /* exact 2:1: the luma job (k_sws_down2) runs beside the chroma jobs (k_sws_lwalk), forked and joined with events */
     hipEvent_t rgb2_fork = nullptr, rgb2_join = nullptr;
     /* exact 2x of 4:2:0 (yuv420p, NV12, NV21) into packed RGB (sws_up2rgb.hip): virtual banks of all four axes, the vertical ones merged row by row */
     int u2r_ok = 0;
-    void *u2r_dev = nullptr;
+    DevBlock u2r_dev;
     const uint32_t *u2r_hco = nullptr, *u2r_vt = nullptr;
     /* exact-2:1 fast path (sws_down2.hip): the same for banks of up to 8 taps on the windows 2x - 3 .. 2x + 4 */
     int dn2_ok = 0;
@@ -112,32 +212,42 @@ struct FFHipSwsContext {
     int c420_ok = 0;  /* 4:2:0 between planar and semi-planar layouts at the same size, no range change: a copy (sws_copy420.hip) */
     int f444_ok = 0;  /* planar 4:4:4 into packed RGB at the source's size: four one-tap banks, the full-chroma writer (sws_full444.hip) */
     int dn2_luma = 0; /* an RGB context's luma banks alone (its first stage's luma job on k_sws_down2, the chroma on the wide walker); 2: the chroma planes there as well (no vertical filter: FFHipDn2Job.v1) */
-    void *dn2_dev = nullptr;
+    DevBlock dn2_dev;
     int d32_ok = 0;   /* exact 3:2 down in both directions: the static-schedule kernel of sws_down32.hip */
-    void *d32_dev = nullptr;
+    DevBlock d32_dev;
     int u32_ok = 0;   /* exact 3:2 (1) or 4:3 (2) UP between 9..14-bit formats laid out alike: the static-schedule kernel of sws_up32.hip */
-    void *u32_dev = nullptr;
+    DevBlock u32_dev;
     const uint32_t *u32_h[2] = { nullptr, nullptr }, *u32_v[2] = { nullptr, nullptr };
     const uint32_t *d32_h[2] = { nullptr, nullptr }, *d32_v[2] = { nullptr, nullptr };
     const uint32_t *dn2_h[2] = { nullptr, nullptr }, *dn2_v[2] = { nullptr, nullptr };
     /* MFMA-horizontal variant (k_sws_mfma): tile records + window-start index tables on the device */
     int mf_ok = 0, mf_chr_pair = 0, mf_ntiles[2] = { 0, 0 };
-    void *mf_dev = nullptr;
+    DevBlock mf_dev;
     const uint8_t *mf_tiles[2] = { nullptr, nullptr };
     const int32_t *mf_ys[2] = { nullptr, nullptr };
     /* staging for the host-pointer face */
-    void *stage = nullptr;
+    DevBlock stage;
     size_t stage_sz = 0;
     bool luma_pass = false;        /* the alpha pass is running: the planners enumerate the luma job only */
     int slice_next = 0;   /* scaled contexts fed in slices: the next source line expected */
     std::mutex mu;
+    /* (the device blocks free themselves after this, once the aux stream has drained) */
+    ~FFHipSwsContext()
+    {
+        for (hipEvent_t e : tune_ev)
+            if (e)
+                (void)hipEventDestroy(e);
+        if (rgb2_aux) {
+            (void)hipStreamSynchronize(rgb2_aux);
+            (void)hipStreamDestroy(rgb2_aux);
+        }
+        if (rgb2_fork)
+            (void)hipEventDestroy(rgb2_fork);
+        if (rgb2_join)
+            (void)hipEventDestroy(rgb2_join);
+    }
 };
 
-static bool em_forced()
-{
-    const char *em = FFHIP_KNOB("FFHIP_SWS_MFMA");
-    return em && em[0] == '1';
-}
 static bool fmt_hbd(int f) { return ffhip_pixfmt_hbd(f, nullptr, nullptr, nullptr, nullptr) != 0; }
 static bool fmt_yuv(int f)
 {
@@ -198,6 +308,17 @@ static int make_k(const FFHipSwsTables &t, FFHipYuv2RgbK *k)
     k->off_b = t.yuv2rgb_yoffs - (int)(t.yuv2rgb_cbu >> 9);
     k->off_g = t.yuv2rgb_yoffs - (int)(t.yuv2rgb_cgu >> 9) - (int)(t.yuv2rgb_cgv >> 9);
     return 0;
+}
+
+/* bank i (hLum, hChr, vLum, vChr) is one tap of unit weight on the sample itself in every row (16384 across, 4096 down); n rows when n >= 0 */
+static bool bank_is_identity(const FFHipSwsContext *c, int i, int n = -1)
+{
+    if (c->d[i].size != 1 || (n >= 0 && c->d[i].n != n))
+        return false;
+    for (int x = 0; x < c->d[i].n; x++)
+        if (c->p[i][x] != x || c->f[i][x] != (i < 2 ? 16384 : 4096))
+            return false;
+    return true;
 }
 
 /*
@@ -277,22 +398,7 @@ static bool build_fast_view(FFHipSwsContext *c, const int limits[4], bool packed
         c->dn[i] = c->d[i];
         c->dn[i].size = 4;
     }
-    if (padded) {
-        size_t noff[4][2], ntot = 0;
-        for (int i = 0; i < 4; i++) {
-            noff[i][0] = ntot; ntot += (c->nf[i].size() * 2 + 15) & ~(size_t)15;
-            noff[i][1] = ntot; ntot += (c->np[i].size() * 4 + 15) & ~(size_t)15;
-        }
-        ok = hipMalloc(&c->dev_ntables, ntot) == hipSuccess;
-        for (int i = 0; i < 4 && ok; i++) {
-            uint8_t *nb = static_cast<uint8_t *>(c->dev_ntables);
-            ok = hipMemcpy(nb + noff[i][0], c->nf[i].data(), c->nf[i].size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(nb + noff[i][1], c->np[i].data(), c->np[i].size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-            c->dn[i].filter = reinterpret_cast<const int16_t *>(nb + noff[i][0]);
-            c->dn[i].pos = reinterpret_cast<const int32_t *>(nb + noff[i][1]);
-        }
-    }
-    return ok;
+    return !padded || upload_banks(c->dev_ntables, c->nf, c->np, 16, c->dn);
 }
 
 /*
@@ -328,24 +434,9 @@ static bool build_wide_view(FFHipSwsContext *c, const int limits[4], int min_ht 
                 c->wf[i][(size_t)x * P + (pos - npos) + k] = (i >= 2 && fs == 1) ? 4096 : c->f[i][(size_t)x * fs + k];
         }
     }
-    size_t off[4][2], tot = 0;
-    for (int i = 0; i < 4; i++) {
-        off[i][0] = tot; tot += (c->wf[i].size() * 2 + 15) & ~(size_t)15;
-        off[i][1] = tot; tot += (c->wp[i].size() * 4 + 15) & ~(size_t)15;
-    }
-    if (c->dev_wtables) { /* a second try with wider padding */
-        (void)hipFree(c->dev_wtables);
-        c->dev_wtables = nullptr;
-    }
-    if (hipMalloc(&c->dev_wtables, tot) != hipSuccess)
+    if (!upload_banks(c->dev_wtables, c->wf, c->wp, 16, c->dw)) /* (a second try with wider padding replaces the first's block) */
         return false;
-    uint8_t *b = static_cast<uint8_t *>(c->dev_wtables);
     for (int i = 0; i < 4; i++) {
-        if (hipMemcpy(b + off[i][0], c->wf[i].data(), c->wf[i].size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(b + off[i][1], c->wp[i].data(), c->wp[i].size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-        c->dw[i].filter = reinterpret_cast<const int16_t *>(b + off[i][0]);
-        c->dw[i].pos = reinterpret_cast<const int32_t *>(b + off[i][1]);
         c->dw[i].size = i < 2 ? 4 * ht : 2 * vt;
         c->dw[i].n = c->d[i].n;
     }
@@ -377,6 +468,19 @@ static bool wide_setup(FFHipSwsContext *c, const int limits[4], bool chroma_pair
     return false;
 }
 
+/* the virtual banks of a static-schedule kernel (horizontal luma, chroma, vertical luma, chroma), each part on 256 bytes */
+static bool upload_hv(DevBlock &blk, const std::vector<uint32_t> vb[4], void *at[4])
+{
+    return upload(blk, { part(vb[0]), part(vb[1]), part(vb[2]), part(vb[3]) }, 256, at);
+}
+static void set_hv(void *const at[4], const uint32_t *h[2], const uint32_t *v[2])
+{
+    for (int i = 0; i < 2; i++) {
+        h[i] = static_cast<const uint32_t *>(at[i]);
+        v[i] = static_cast<const uint32_t *>(at[2 + i]);
+    }
+}
+
 /* exact 2x: the 4-tap views (c->nf / c->np) as virtual banks on the regular windows of the edge-replicated rows, on the device;
  * sets c->up2_ok when every bank row is of that shape (sws_up2.hip) */
 /* chroma_only: the chroma banks alone (the luma plane is the source's: FFHipSwsContext.mix_up2) */
@@ -397,26 +501,14 @@ static void up2_build(FFHipSwsContext *c, const int nsrc[4], bool chroma_only = 
         memcpy(pv.data() + 2, vb[i].data(), vb[i].size() * 4);
         vb[i].swap(pv);
     }
-    size_t uo[4], ut = 0;
-    for (int i = 0; i < 4; i++) {
-        uo[i] = ut;
-        ut += (vb[i].size() * 4 + 255) & ~(size_t)255;
-    }
-    if (hipMalloc(&c->up2_dev, ut) != hipSuccess)
+    void *at[4];
+    if (!upload_hv(c->up2_dev, vb, at))
         return;
-    uint8_t *b = static_cast<uint8_t *>(c->up2_dev);
-    for (int i = 0; i < 4 && ok; i++)
-        ok = hipMemcpy(b + uo[i], vb[i].data(), vb[i].size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
-        c->up2_h[0] = reinterpret_cast<const uint32_t *>(b + uo[0]);
-        c->up2_h[1] = reinterpret_cast<const uint32_t *>(b + uo[1]);
-        c->up2_v[0] = reinterpret_cast<const uint32_t *>(b + uo[2]);
-        c->up2_v[1] = reinterpret_cast<const uint32_t *>(b + uo[3]);
-        if (chroma_only)
-            c->mix_up2 = 1;
-        else
-            c->up2_ok = 1;
-    }
+    set_hv(at, c->up2_h, c->up2_v);
+    if (chroma_only)
+        c->mix_up2 = 1;
+    else
+        c->up2_ok = 1;
 }
 
 /* exact 2x of 4:2:0 into packed RGB: luma 2x both ways, chroma 2x horizontally and 4x vertically (a packed target has a
@@ -444,14 +536,11 @@ static void up2rgb_build(FFHipSwsContext *c, int srcW, int srcH, int dstW, int d
         uint32_t *r = vt.data() + (size_t)(y + 1) * 4;
         r[0] = vl[2 * (size_t)y]; r[1] = vl[2 * (size_t)y + 1]; r[2] = vc[2 * (size_t)y]; r[3] = vc[2 * (size_t)y + 1];
     }
-    if (hipMalloc(&c->u2r_dev, 256 + vt.size() * 4) != hipSuccess)
+    void *at[2];
+    if (!upload(c->u2r_dev, { { hco, sizeof(hco) }, part(vt) }, 256, at))
         return;
-    uint8_t *b = static_cast<uint8_t *>(c->u2r_dev);
-    if (hipMemcpy(b, hco, sizeof(hco), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b + 256, vt.data(), vt.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return;
-    c->u2r_hco = reinterpret_cast<const uint32_t *>(b);
-    c->u2r_vt = reinterpret_cast<const uint32_t *>(b + 256);
+    c->u2r_hco = static_cast<const uint32_t *>(at[0]);
+    c->u2r_vt = static_cast<const uint32_t *>(at[1]);
     c->u2r_ok = 1;
 }
 
@@ -461,26 +550,15 @@ static void eqrgb_build(FFHipSwsContext *c, int srcW, int srcH, int chrW, int ch
 {
     if ((srcW & 7) || (srcH & 1) || chrH < 4 || 2 * chrH != srcH || 2 * chrW != srcW || c->cw_vround != 1 << 18)
         return;
-    const int unit[3] = { 1 << 14, 1 << 14, 1 << 12 }, want_n[3] = { srcW, chrW, srcH };
-    for (int i = 0; i < 3; i++) {
-        if (c->d[i].size != 1 || c->d[i].n != want_n[i])
-            return;
-        for (int x = 0; x < c->d[i].n; x++)
-            if (c->f[i][x] != unit[i] || c->p[i][x] != x)
-                return;
-    }
-    if (c->d[3].n != srcH)
+    if (!bank_is_identity(c, 0, srcW) || !bank_is_identity(c, 1, chrW) || !bank_is_identity(c, 2, srcH) || c->d[3].n != srcH)
         return;
     std::vector<uint32_t> vc;
     if (!ffhip_up2_virtual_bank(c->nf[3].data(), c->np[3].data(), srcH, chrH, &vc))
         return;
     std::vector<uint32_t> vt((size_t)(srcH + 6) * 2, 0);
     memcpy(vt.data() + 2, vc.data(), vc.size() * 4);
-    if (hipMalloc(&c->eqr_dev, vt.size() * 4) != hipSuccess)
-        return;
-    if (hipMemcpy(c->eqr_dev, vt.data(), vt.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return;
-    c->eqr_ok = 1;
+    void *at[1];
+    c->eqr_ok = upload(c->eqr_dev, { part(vt) }, 4, at);
 }
 
 /* exact 2:1: the banks (up to 8 taps) as virtual banks on the windows 2x - 3 .. 2x + 4 of the edge-replicated rows, on the device;
@@ -495,23 +573,11 @@ static void dn2_build(FFHipSwsContext *c, const int nsrc[4])
         return;
     for (int i = 2; i < 4; i++)
         vb[i].resize((size_t)(c->d[i].n + 8) * 4, 0); /* the row loop reads four rows of coefficients at a time */
-    size_t uo[4], ut = 0;
-    for (int i = 0; i < 4; i++) {
-        uo[i] = ut;
-        ut += (vb[i].size() * 4 + 255) & ~(size_t)255;
-    }
-    if (hipMalloc(&c->dn2_dev, ut) != hipSuccess)
+    void *at[4];
+    if (!upload_hv(c->dn2_dev, vb, at))
         return;
-    uint8_t *b = static_cast<uint8_t *>(c->dn2_dev);
-    for (int i = 0; i < 4 && ok; i++)
-        ok = hipMemcpy(b + uo[i], vb[i].data(), vb[i].size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
-        c->dn2_h[0] = reinterpret_cast<const uint32_t *>(b + uo[0]);
-        c->dn2_h[1] = reinterpret_cast<const uint32_t *>(b + uo[1]);
-        c->dn2_v[0] = reinterpret_cast<const uint32_t *>(b + uo[2]);
-        c->dn2_v[1] = reinterpret_cast<const uint32_t *>(b + uo[3]);
-        c->dn2_ok = 1;
-    }
+    set_hv(at, c->dn2_h, c->dn2_v);
+    c->dn2_ok = 1;
 }
 
 /* exact 3:2: the banks (up to 6 taps) as virtual banks on the windows 3 (x >> 1) - 2 + (x & 1) .. + 5 of the edge-replicated rows, on the
@@ -522,21 +588,10 @@ static void d32_build(FFHipSwsContext *c, const int nsrc[4], int pin = 3, int po
     for (int i = 0; i < 4; i++)
         if (!ffhip_d32_virtual_bank(c->f[i].data(), c->p[i].data(), c->d[i].size, c->d[i].n, nsrc[i], i < 2 ? 3 : 4, &vb[i], pin, pout))
             return;
-    size_t uo[4], ut = 0;
-    for (int i = 0; i < 4; i++) {
-        uo[i] = ut;
-        ut += (vb[i].size() * 4 + 255) & ~(size_t)255;
-    }
-    if (hipMalloc(&c->d32_dev, ut) != hipSuccess)
+    void *at[4];
+    if (!upload_hv(c->d32_dev, vb, at))
         return;
-    uint8_t *b = static_cast<uint8_t *>(c->d32_dev);
-    for (int i = 0; i < 4; i++)
-        if (hipMemcpy(b + uo[i], vb[i].data(), vb[i].size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return;
-    c->d32_h[0] = reinterpret_cast<const uint32_t *>(b + uo[0]);
-    c->d32_h[1] = reinterpret_cast<const uint32_t *>(b + uo[1]);
-    c->d32_v[0] = reinterpret_cast<const uint32_t *>(b + uo[2]);
-    c->d32_v[1] = reinterpret_cast<const uint32_t *>(b + uo[3]);
+    set_hv(at, c->d32_h, c->d32_v);
     c->d32_ok = pin == 3 ? 1 : 2;
 }
 
@@ -548,21 +603,10 @@ static void u32_build(FFHipSwsContext *c, const int nsrc[4], int pin, int pout)
     for (int i = 0; i < 4; i++)
         if (!ffhip_u32_virtual_bank(c->f[i].data(), c->p[i].data(), c->d[i].size, c->d[i].n, nsrc[i], pin, pout, &vb[i]))
             return;
-    size_t uo[4], ut = 0;
-    for (int i = 0; i < 4; i++) {
-        uo[i] = ut;
-        ut += (vb[i].size() * 4 + 255) & ~(size_t)255;
-    }
-    if (hipMalloc(&c->u32_dev, ut) != hipSuccess)
+    void *at[4];
+    if (!upload_hv(c->u32_dev, vb, at))
         return;
-    uint8_t *b = static_cast<uint8_t *>(c->u32_dev);
-    for (int i = 0; i < 4; i++)
-        if (hipMemcpy(b + uo[i], vb[i].data(), vb[i].size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return;
-    c->u32_h[0] = reinterpret_cast<const uint32_t *>(b + uo[0]);
-    c->u32_h[1] = reinterpret_cast<const uint32_t *>(b + uo[1]);
-    c->u32_v[0] = reinterpret_cast<const uint32_t *>(b + uo[2]);
-    c->u32_v[1] = reinterpret_cast<const uint32_t *>(b + uo[3]);
+    set_hv(at, c->u32_h, c->u32_v);
     c->u32_ok = pin == 2 ? 1 : 2;
 }
 
@@ -585,17 +629,14 @@ static void dn2_build_luma(FFHipSwsContext *c, int srcW, int srcH)
         }
     chr = chr && ffhip_cw_bank_nowrap(c->f[1].data(), c->d[1].size, c->d[1].n) &&
           ffhip_down2_virtual_bank(c->f[1].data(), c->p[1].data(), c->d[1].size, c->d[1].n, c->chrSrcW, &vb[2]) != 0;
-    const size_t o1 = (vb[0].size() * 4 + 255) & ~(size_t)255, o2 = o1 + ((vb[1].size() * 4 + 255) & ~(size_t)255);
-    if (hipMalloc(&c->dn2_dev, o2 + (chr ? vb[2].size() * 4 : 0)) != hipSuccess)
+    if (!chr)
+        vb[2].clear();
+    void *at[3];
+    if (!upload(c->dn2_dev, { part(vb[0]), part(vb[1]), part(vb[2]) }, 256, at)) /* (vb[2] is empty without the chroma) */
         return;
-    uint8_t *b = static_cast<uint8_t *>(c->dn2_dev);
-    if (hipMemcpy(b, vb[0].data(), vb[0].size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b + o1, vb[1].data(), vb[1].size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (chr && hipMemcpy(b + o2, vb[2].data(), vb[2].size() * 4, hipMemcpyHostToDevice) != hipSuccess))
-        return;
-    c->dn2_h[0] = reinterpret_cast<const uint32_t *>(b);
-    c->dn2_v[0] = reinterpret_cast<const uint32_t *>(b + o1);
-    c->dn2_h[1] = chr ? reinterpret_cast<const uint32_t *>(b + o2) : nullptr;
+    c->dn2_h[0] = static_cast<const uint32_t *>(at[0]);
+    c->dn2_v[0] = static_cast<const uint32_t *>(at[1]);
+    c->dn2_h[1] = chr ? static_cast<const uint32_t *>(at[2]) : nullptr;
     c->dn2_luma = 1 + (chr ? 1 : 0);
 }
 
@@ -665,7 +706,6 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
     /* copy the banks (with the reference's 3 entries of over-read padding when present is not assumed) */
     const FFHipSwsFilter *in[4] = { &t->hLum, &t->hChr, &t->vLum, &t->vChr };
     FFHipSwsFilter *own[4] = { &c->t.hLum, &c->t.hChr, &c->t.vLum, &c->t.vChr };
-    size_t off[4][2], total = 0;
     /* the reference builds no banks for a context that got a special converter (ff_sws_init_single_context() returns before
      * initFilter(), libswscale/utils.c:1625-1637): the table converter takes none, the context keeps one-tap identities */
     std::vector<int16_t> idf[4];
@@ -692,26 +732,13 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
         c->p[i].assign(in[i]->pos, in[i]->pos + in[i]->n);
         own[i]->filter = c->f[i].data();
         own[i]->pos = c->p[i].data();
-        off[i][0] = total; total += (c->f[i].size() * 2 + 15) & ~(size_t)15;
-        off[i][1] = total; total += (c->p[i].size() * 4 + 15) & ~(size_t)15;
-    }
-    if (hipMalloc(&c->dev_tables, total) != hipSuccess) {
-        ffhip_set_error("ffhip_sws: hipMalloc(%zu) for filter banks failed", total);
-        delete c;
-        return nullptr;
-    }
-    for (int i = 0; i < 4; i++) {
-        uint8_t *base = static_cast<uint8_t *>(c->dev_tables);
-        if (hipMemcpy(base + off[i][0], c->f[i].data(), c->f[i].size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(base + off[i][1], c->p[i].data(), c->p[i].size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            ffhip_set_error("ffhip_sws: filter bank upload failed");
-            ffhip_sws_freeContext(c);
-            return nullptr;
-        }
-        c->d[i].filter = reinterpret_cast<const int16_t *>(base + off[i][0]);
-        c->d[i].pos = reinterpret_cast<const int32_t *>(base + off[i][1]);
         c->d[i].size = in[i]->size;
         c->d[i].n = in[i]->n;
+    }
+    if (!upload_banks(c->dev_tables, c->f, c->p, 16, c->d)) {
+        ffhip_set_error("ffhip_sws: filter bank upload failed");
+        ffhip_sws_freeContext(c);
+        return nullptr;
     }
 
     if (c->unscaled_yuv2rgb)
@@ -774,6 +801,8 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
             (void)ffhip_pixfmt_hbd(t->srcFormat, &sd, &sl, nullptr, nullptr);
             (void)ffhip_pixfmt_hbd(t->dstFormat, &dd, &dl, nullptr, nullptr);
             const int cw = c->chrSrcW, chh = c->chrSrcH;
+            /* no horizontal sum of the banks as they are wraps int16 at the source's depth (the static-schedule kernels and the walker) */
+            const bool nowrap = bank_nowrap_depth(c->f[0].data(), c->d[0].n, sd, c->d[0].size) && bank_nowrap_depth(c->f[1].data(), c->d[1].n, sd, c->d[1].size);
             const int limits[4] = { t->srcW, cw, t->srcH, chh };
             /* (round 6: from an 8-bit source too — planar into planar, NV12 into P01x — on planes widened to 16-bit samples: `widen8`) */
             const bool w8 = sd == 8 && dd > 8 && dd <= 14 && !c->flat_dither && t->srcFormat != FFHIP_PIX_FMT_NV21 &&
@@ -792,8 +821,7 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
             const bool dn8 = dd == 8 && !hrgb && !c->flat_dither /* (k_sws_down2 has the ordered dither only) */ && (sl == 1 ? t->dstFormat == FFHIP_PIX_FMT_NV12 : !fmt_nv(t->dstFormat));
             if (sd > 8 && sd <= 14 && ((dd > 8 && dd <= 14 && sl == dl) || dn8) && sl != 2 && t->src_range == t->dst_range &&
                 t->srcW == 2 * t->dstW && t->srcH == 2 * t->dstH && cw == 2 * cdw && chh == 2 * cdh &&
-                !(t->dstW & 3) && t->dstW >= 12 && (sl ? !(cdw & 1) && cdw >= 6 : !(cdw & 3) && cdw >= 12) &&
-                bank_nowrap_depth(c->f[0].data(), c->d[0].n, sd, c->d[0].size) && bank_nowrap_depth(c->f[1].data(), c->d[1].n, sd, c->d[1].size))
+                !(t->dstW & 3) && t->dstW >= 12 && (sl ? !(cdw & 1) && cdw >= 6 : !(cdw & 3) && cdw >= 12) && nowrap)
                 dn2_build(c, limits);
             /* exact 3:2 up (720p -> 1080p ...) between formats of 9..14 bits laid out alike, or from an 8-bit source widened to words as for the
              * walker below (planar into planar, NV12 into P01x): sws_up32.hip; the walker is set up beside it for planes it cannot take */
@@ -803,15 +831,13 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
                 if (((sd > 8 && sd <= 14 && sl == dl && sl != 2) || w8u) && dd > 8 && dd <= 14 && !hrgb && !c->flat_dither && t->src_range == t->dst_range &&
                     2 * t->dstW == 3 * t->srcW && 2 * t->dstH == 3 * t->srcH && 2 * c->d[1].n == 3 * cw && 2 * c->d[3].n == 3 * chh &&
                     !(t->srcW & 3) && t->srcW >= 12 && !(t->srcH & 1) && !(chh & 1) &&
-                    ((sl || fmt_nv(t->srcFormat)) ? !(cw & 1) && cw >= 6 : !(cw & 3) && cw >= 12) &&
-                    bank_nowrap_depth(c->f[0].data(), c->d[0].n, sd, c->d[0].size) && bank_nowrap_depth(c->f[1].data(), c->d[1].n, sd, c->d[1].size))
+                    ((sl || fmt_nv(t->srcFormat)) ? !(cw & 1) && cw >= 6 : !(cw & 3) && cw >= 12) && nowrap)
                     u32_build(c, limits, 2, 3);
                 /* ... and exact 4:3 (1080p -> 1440p): period (3 in, 4 out) of the same kernel */
                 if (((sd > 8 && sd <= 14 && sl == dl && sl != 2) || w8u) && dd > 8 && dd <= 14 && !hrgb && !c->flat_dither && t->src_range == t->dst_range &&
                     3 * t->dstW == 4 * t->srcW && 3 * t->dstH == 4 * t->srcH && 3 * c->d[1].n == 4 * cw && 3 * c->d[3].n == 4 * chh &&
                     !(t->srcW % 6) && t->srcW >= 18 && !(t->srcH % 3) && !(chh % 3) &&
-                    ((sl || fmt_nv(t->srcFormat)) ? !(cw % 3) && cw >= 9 : !(cw % 6) && cw >= 18) &&
-                    bank_nowrap_depth(c->f[0].data(), c->d[0].n, sd, c->d[0].size) && bank_nowrap_depth(c->f[1].data(), c->d[1].n, sd, c->d[1].size))
+                    ((sl || fmt_nv(t->srcFormat)) ? !(cw % 3) && cw >= 9 : !(cw % 6) && cw >= 18) && nowrap)
                     u32_build(c, limits, 3, 4);
                 if (c->u32_ok && w8u)
                     c->widen8 = 1;
@@ -820,14 +846,12 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
             /* (also into an 8-bit target laid out alike — P01x -> NV12, planar -> planar — with the ordered dither on the way out, as `dn8` above) */
             if (sd > 8 && sd <= 14 && ((dd > 8 && dd <= 14 && sl == dl) || dn8) && sl != 2 && !hrgb && !c->flat_dither && t->src_range == t->dst_range &&
                 2 * t->srcW == 3 * t->dstW && 2 * t->srcH == 3 * t->dstH && 2 * cw == 3 * cdw && 2 * chh == 3 * cdh &&
-                !(t->dstW & 3) && t->dstW >= 12 && !(t->dstH & 1) && !(cdh & 1) && (sl ? !(cdw & 1) && cdw >= 6 : !(cdw & 3) && cdw >= 12) &&
-                bank_nowrap_depth(c->f[0].data(), c->d[0].n, sd, c->d[0].size) && bank_nowrap_depth(c->f[1].data(), c->d[1].n, sd, c->d[1].size))
+                !(t->dstW & 3) && t->dstW >= 12 && !(t->dstH & 1) && !(cdh & 1) && (sl ? !(cdw & 1) && cdw >= 6 : !(cdw & 3) && cdw >= 12) && nowrap)
                 d32_build(c, limits);
             /* ... and exact 4:3 down (1440p -> 1080p): the twin's second period */
             if (!c->d32_ok && sd > 8 && sd <= 14 && dd > 8 && dd <= 14 && sl == dl && sl != 2 && !hrgb && !c->flat_dither && t->src_range == t->dst_range &&
                 3 * t->srcW == 4 * t->dstW && 3 * t->srcH == 4 * t->dstH && 3 * cw == 4 * cdw && 3 * chh == 4 * cdh &&
-                !(t->dstW % 6) && t->dstW >= 18 && !(t->dstH % 3) && !(cdh % 3) && (sl ? !(cdw % 3) && cdw >= 9 : !(cdw % 6) && cdw >= 18) &&
-                bank_nowrap_depth(c->f[0].data(), c->d[0].n, sd, c->d[0].size) && bank_nowrap_depth(c->f[1].data(), c->d[1].n, sd, c->d[1].size))
+                !(t->dstW % 6) && t->dstW >= 18 && !(t->dstH % 3) && !(cdh % 3) && (sl ? !(cdw % 3) && cdw >= 9 : !(cdw % 6) && cdw >= 18) && nowrap)
                 d32_build(c, limits, 4, 3);
             /* every other ratio between 9..14-bit formats whose banks have at most 8 taps: the 16-bit column walker (sws_walk16.hip);
              * no range change (it carries no range stage), no 8-bit side */
@@ -839,8 +863,7 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
             const bool widen = sd == 8 && dd > 8 && dd <= 14 && t->srcFormat != FFHIP_PIX_FMT_NV21 && !c->flat_dither;
             if (!c->up2_ok && !c->dn2_ok && ((sd > 8 && sd <= 14) || widen) && ((dd > 8 && dd <= 14) || to8) && (sl != 2 || widen) && dl != 2 &&
                 (t->src_range == t->dst_range || hrgb /* (the source's range lives in the yuv2rgb tables) */) &&
-                c->d[0].size <= 16 && c->d[1].size <= 16 && c->d[2].size <= 16 && c->d[3].size <= 16 &&
-                bank_nowrap_depth(c->f[0].data(), c->d[0].n, sd, c->d[0].size) && bank_nowrap_depth(c->f[1].data(), c->d[1].n, sd, c->d[1].size)) {
+                c->d[0].size <= 16 && c->d[1].size <= 16 && c->d[2].size <= 16 && c->d[3].size <= 16 && nowrap) {
                 const int hmax = c->d[0].size > c->d[1].size ? c->d[0].size : c->d[1].size, vmax = c->d[2].size > c->d[3].size ? c->d[2].size : c->d[3].size;
                 int ht = hmax <= 4 ? 4 : hmax <= 8 ? 8 : 16, vt = vmax <= 4 ? 4 : vmax <= 8 ? 8 : 16;
                 if (ht == 16 && vt == 4) vt = 8;   /* (the instantiated pairs: 4x4 .. 8x8, 16x8, 8x16, 16x16) */
@@ -851,30 +874,15 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
                 bool ok = true;
                 for (int i = 0; i < 4 && ok; i++)
                     ok = ffhip_w16_pad_bank(c->f[i].data(), c->p[i].data(), c->d[i].size, c->d[i].n, limits[i], T[i], &pf[i], &pp[i]);
-                size_t off[8], tot = 0;
-                for (int i = 0; i < 4; i++) {
-                    off[2 * i] = tot;     tot += (pf[i].size() * 2 + 255) & ~(size_t)255;
-                    off[2 * i + 1] = tot; tot += (pp[i].size() * 4 + 255) & ~(size_t)255;
-                }
-                if (ok && hipMalloc(&c->w16_dev, tot) == hipSuccess) {
-                    uint8_t *b = static_cast<uint8_t *>(c->w16_dev);
-                    for (int i = 0; i < 4 && ok; i++)
-                        ok = hipMemcpy(b + off[2 * i], pf[i].data(), pf[i].size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
-                             hipMemcpy(b + off[2 * i + 1], pp[i].data(), pp[i].size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-                    if (ok) {
-                        for (int i = 0; i < 4; i++) {
-                            c->w16_f[i] = reinterpret_cast<const int16_t *>(b + off[2 * i]);
-                            c->w16_p[i] = reinterpret_cast<const int32_t *>(b + off[2 * i + 1]);
-                        }
-                        c->w16_ht = ht;
-                        c->w16_vt = vt;
-                        c->w16_ok = 1;
-                        c->widen8 = widen;
-                        for (int i = 0; i < 2; i++) {
-                            c->w16_span[i][0] = ffhip_w16_span(pp[i].data(), c->d[i].n, 256, 2, ht);
-                            c->w16_span[i][1] = ffhip_w16_span(pp[i].data(), c->d[i].n, 128, 2, ht);
-                            c->w16_span[i][2] = ffhip_w16_span(pp[i].data(), c->d[i].n, 128, 4, ht);
-                        }
+                if (ok && upload_banks(c->w16_dev, pf, pp, 256, c->w16)) {
+                    c->w16_ht = ht;
+                    c->w16_vt = vt;
+                    c->w16_ok = 1;
+                    c->widen8 = widen;
+                    for (int i = 0; i < 2; i++) {
+                        c->w16_span[i][0] = ffhip_w16_span(pp[i].data(), c->d[i].n, 256, 2, ht);
+                        c->w16_span[i][1] = ffhip_w16_span(pp[i].data(), c->d[i].n, 128, 2, ht);
+                        c->w16_span[i][2] = ffhip_w16_span(pp[i].data(), c->d[i].n, 128, 4, ht);
                     }
                 }
             }
@@ -927,15 +935,9 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
         r = ffhip_plan_scale_rgb(&a, c->p[0].data(), c->p[1].data(), c->p[2].data(), c->p[3].data());
         /* planar 4:4:4 at the source's size (what sws_scale() runs for yuv444p -> rgb24: full chroma forced, no table converter): every
          * bank one tap on the sample itself -> the streaming kernel of sws_full444.hip */
-        if (!r && a.full && !a.has_alpha && t->srcFormat == FFHIP_PIX_FMT_YUV444P && t->srcW == t->dstW && t->srcH == t->dstH && t->dstW >= 8) {
-            bool id = true;
-            for (int b = 0; b < 4 && id; b++) {
-                id = c->d[b].size == 1 && c->d[b].n == (b < 2 ? t->dstW : t->dstH);
-                for (int x = 0; x < c->d[b].n && id; x++)
-                    id = c->p[b][x] == x && c->f[b][x] == (b < 2 ? 16384 : 4096);
-            }
-            c->f444_ok = id;
-        }
+        c->f444_ok = !r && a.full && !a.has_alpha && t->srcFormat == FFHIP_PIX_FMT_YUV444P && t->srcW == t->dstW && t->srcH == t->dstH && t->dstW >= 8 &&
+                     bank_is_identity(c, 0, t->dstW) && bank_is_identity(c, 1, t->dstW) && bank_is_identity(c, 2, t->dstH) &&
+                     bank_is_identity(c, 3, t->dstH);
         /* column walker with RGB output: 4-tap vertical banks (yuv2rgb_X), <= 4-tap horizontal banks, no int16 wrap */
         const int limits[4] = { a.srcW, a.chrSrcW, a.srcH, a.chrSrcH };
         if (!r && !a.full && !a.has_alpha && !(t->dstW & 7) && build_fast_view(c, limits, true))
@@ -1021,44 +1023,31 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
          * out differently (sws_copy420.hip) */
         {
             auto is420 = [](int f) { return f == FFHIP_PIX_FMT_YUV420P || f == FFHIP_PIX_FMT_NV12 || f == FFHIP_PIX_FMT_NV21; };
-            bool id = !r && is420(t->srcFormat) && is420(t->dstFormat) && t->srcW == t->dstW && t->srcH == t->dstH && t->dst_alpha_fill != 2 &&
-                      t->dstW >= 16 && c->d[1].n >= 16;
-            for (int b = 0; b < 4 && id; b++) {
-                id = c->d[b].size == 1;
-                for (int x = 0; x < c->d[b].n && id; x++)
-                    id = c->p[b][x] == x && c->f[b][x] == (b < 2 ? 16384 : 4096);
-            }
-            c->c420_ok = id;
+            c->c420_ok = !r && is420(t->srcFormat) && is420(t->dstFormat) && t->srcW == t->dstW && t->srcH == t->dstH && t->dst_alpha_fill != 2 &&
+                         t->dstW >= 16 && c->d[1].n >= 16 && bank_is_identity(c, 0) && bank_is_identity(c, 1) && bank_is_identity(c, 2) &&
+                         bank_is_identity(c, 3);
         }
         /* planar 4:4:4 -> 4:2:0 at the same size (a capture's frames subsampled for an encoder): the luma plane is the source's (one-tap
          * banks), the chroma planes go exactly 2:1 both ways — the layout kernel's copy job + the static-schedule kernel on two planes,
          * against the wide walker computing all three with its 8-tap classes */
         if (!r && !c->c420_ok && t->srcFormat == FFHIP_PIX_FMT_YUV444P && t->dstFormat == FFHIP_PIX_FMT_YUV420P && t->srcW == t->dstW &&
             t->srcH == t->dstH && t->dst_alpha_fill != 2 && t->dstW >= 16 && !(c->d[1].n & 3) && c->d[1].n >= 12) {
-            bool id = true;
-            for (int b = 0; b < 4 && id; b += 2) {
-                id = c->d[b].size == 1;
-                for (int x = 0; x < c->d[b].n && id; x++)
-                    id = c->p[b][x] == x && c->f[b][x] == (b < 2 ? 16384 : 4096);
-            }
             std::vector<uint32_t> vb[2];
-            if (id && ffhip_cw_bank_nowrap(c->f[1].data(), c->d[1].size, c->d[1].n) &&
+            if (bank_is_identity(c, 0) && bank_is_identity(c, 2) && ffhip_cw_bank_nowrap(c->f[1].data(), c->d[1].size, c->d[1].n) &&
                 ffhip_down2_virtual_bank(c->f[1].data(), c->p[1].data(), c->d[1].size, c->d[1].n, c->chrSrcW, &vb[0]) &&
                 ffhip_down2_virtual_bank(c->f[3].data(), c->p[3].data(), c->d[3].size, c->d[3].n, c->chrSrcH, &vb[1])) {
                 vb[1].resize((size_t)(c->d[3].n + 8) * 4, 0); /* the row loop reads four rows of coefficients at a time */
-                const size_t o1 = (vb[0].size() * 4 + 255) & ~(size_t)255;
-                if (hipMalloc(&c->dn2_dev, o1 + vb[1].size() * 4) == hipSuccess) {
-                    uint8_t *bb = static_cast<uint8_t *>(c->dn2_dev);
-                    if (hipMemcpy(bb, vb[0].data(), vb[0].size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                        hipMemcpy(bb + o1, vb[1].data(), vb[1].size() * 4, hipMemcpyHostToDevice) == hipSuccess) {
-                        c->dn2_h[1] = reinterpret_cast<const uint32_t *>(bb);
-                        c->dn2_v[1] = reinterpret_cast<const uint32_t *>(bb + o1);
-                        c->mix_dn2 = 1;
-                    }
+                void *at[2];
+                if (upload(c->dn2_dev, { part(vb[0]), part(vb[1]) }, 256, at)) {
+                    c->dn2_h[1] = static_cast<const uint32_t *>(at[0]);
+                    c->dn2_v[1] = static_cast<const uint32_t *>(at[1]);
+                    c->mix_dn2 = 1;
                 }
             }
         }
         const int limits[4] = { l.srcW, ch.srcW, l.srcH, ch.srcH };
+        /* no horizontal sum of the banks as they are leaves int16 (the static-schedule kernels) */
+        const bool nowrap = ffhip_cw_bank_nowrap(c->f[0].data(), c->d[0].size, c->d[0].n) && ffhip_cw_bank_nowrap(c->f[1].data(), c->d[1].size, c->d[1].n);
         {
             const bool ok = build_fast_view(c, limits, false);
             c->cw_ok = ok && ffhip_cw_bank_ok(c->np[0].data(), 4, c->d[0].n, l.srcW, c->np[2].data(), 4, c->d[2].n, l.srcH) &&
@@ -1077,17 +1066,9 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
         /* planar 4:2:0 -> 4:4:4 at the same size: the luma plane is the source's, the chroma planes go exactly 2x both ways */
         if (c->cw_opt && !c->up2_ok && t->srcFormat == FFHIP_PIX_FMT_YUV420P && t->dstFormat == FFHIP_PIX_FMT_YUV444P && l.dstW == l.srcW &&
             l.dstH == l.srcH && ch.dstW == 2 * ch.srcW && ch.dstH == 2 * ch.srcH && !(ch.srcW & 3) && ch.srcW >= 8 && l.dstW >= 16 &&
-            t->dst_alpha_fill != 2) {
-            bool id = true;
-            for (int b = 0; b < 4 && id; b += 2) {
-                id = c->d[b].size == 1;
-                for (int x = 0; x < c->d[b].n && id; x++)
-                    id = c->p[b][x] == x && c->f[b][x] == (b < 2 ? 16384 : 4096);
-            }
-            if (id) {
-                const int nsrc[4] = { l.srcW, ch.srcW, l.srcH, ch.srcH };
-                up2_build(c, nsrc, true);
-            }
+            t->dst_alpha_fill != 2 && bank_is_identity(c, 0) && bank_is_identity(c, 2)) {
+            const int nsrc[4] = { l.srcW, ch.srcW, l.srcH, ch.srcH };
+            up2_build(c, nsrc, true);
         }
         /* wide banks (down-scaling, long kernels): the LDS-backed walker; FFHIP_SWS_WIDE=1 builds it for narrow banks
          * too (parity tests of that kernel on up-scaling cases) */
@@ -1102,16 +1083,14 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
         }
         /* exact 2:1 in both directions, chroma laid out alike on both sides, no horizontal sum leaves int16: the
          * static-schedule kernel (sws_down2.hip) */
-        if (ffhip_cw_bank_nowrap(c->f[0].data(), c->d[0].size, c->d[0].n) && ffhip_cw_bank_nowrap(c->f[1].data(), c->d[1].size, c->d[1].n) &&
-            l.srcW == 2 * l.dstW && l.srcH == 2 * l.dstH && ch.srcW == 2 * ch.dstW && ch.srcH == 2 * ch.dstH &&
+        if (nowrap && l.srcW == 2 * l.dstW && l.srcH == 2 * l.dstH && ch.srcW == 2 * ch.dstW && ch.srcH == 2 * ch.dstH &&
             fmt_nv(t->srcFormat) == fmt_nv(t->dstFormat) && !(l.dstW & 3) && l.dstW >= 12 &&
             (fmt_nv(t->srcFormat) ? !(ch.dstW & 1) && ch.dstW >= 6 : !(ch.dstW & 3) && ch.dstW >= 12)) {
             const int nsrc[4] = { l.srcW, ch.srcW, l.srcH, ch.srcH };
             dn2_build(c, nsrc);
         }
         /* exact 3:2 in both directions (1080p -> 720p, 4K -> 1440p), chroma laid out alike on both sides: sws_down32.hip */
-        if (ffhip_cw_bank_nowrap(c->f[0].data(), c->d[0].size, c->d[0].n) && ffhip_cw_bank_nowrap(c->f[1].data(), c->d[1].size, c->d[1].n) &&
-            2 * l.srcW == 3 * l.dstW && 2 * l.srcH == 3 * l.dstH && 2 * ch.srcW == 3 * ch.dstW && 2 * ch.srcH == 3 * ch.dstH &&
+        if (nowrap && 2 * l.srcW == 3 * l.dstW && 2 * l.srcH == 3 * l.dstH && 2 * ch.srcW == 3 * ch.dstW && 2 * ch.srcH == 3 * ch.dstH &&
             fmt_nv(t->srcFormat) == fmt_nv(t->dstFormat) && !(l.dstW & 7) && l.dstW >= 24 && !(l.dstH & 1) && !(ch.dstH & 1) &&
             (fmt_nv(t->srcFormat) ? !(ch.dstW & 3) && ch.dstW >= 12 : !(ch.dstW & 7) && ch.dstW >= 24) && t->dst_alpha_fill != 2) {
             const int nsrc[4] = { l.srcW, ch.srcW, l.srcH, ch.srcH };
@@ -1121,8 +1100,7 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
          * sws_up32.hip (round 6; was the 4-tap column walker at 0.35 - 0.40 of HBM) */
         for (int q = 0; q < 2 && !c->u32_ok; q++) {
             const int pin = q ? 3 : 2, pout = q ? 4 : 3, no = 4 * pout;
-            if (ffhip_cw_bank_nowrap(c->f[0].data(), c->d[0].size, c->d[0].n) && ffhip_cw_bank_nowrap(c->f[1].data(), c->d[1].size, c->d[1].n) &&
-                pin * l.dstW == pout * l.srcW && pin * l.dstH == pout * l.srcH && pin * ch.dstW == pout * ch.srcW && pin * ch.dstH == pout * ch.srcH &&
+            if (nowrap && pin * l.dstW == pout * l.srcW && pin * l.dstH == pout * l.srcH && pin * ch.dstW == pout * ch.srcW && pin * ch.dstH == pout * ch.srcH &&
                 t->srcFormat == t->dstFormat /* (the same layout and channel order) */ && !(l.dstW % no) && l.dstW >= 3 * no && !(l.dstH % pout) &&
                 !(ch.dstH % pout) && (fmt_nv(t->srcFormat) ? !(ch.dstW % (no / 2)) && ch.dstW >= 3 * no / 2 : !(ch.dstW % no) && ch.dstW >= 3 * no) &&
                 t->dst_alpha_fill != 2) {
@@ -1150,21 +1128,14 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables(const FFHipSwsTables *t)
                         ys[k][p] = y;
                     }
                 }
-                const size_t o1 = (tl.size() + 255) & ~(size_t)255, o2 = o1 + ((tc.size() + 255) & ~(size_t)255);
-                const size_t o3 = o2 + ((ys[0].size() * 4 + 255) & ~(size_t)255), tot = o3 + ys[1].size() * 4 + 256;
-                if (hipMalloc(&c->mf_dev, tot) == hipSuccess) {
-                    uint8_t *b = static_cast<uint8_t *>(c->mf_dev);
-                    if (hipMemcpy(b, tl.data(), tl.size(), hipMemcpyHostToDevice) == hipSuccess &&
-                        hipMemcpy(b + o1, tc.data(), tc.size(), hipMemcpyHostToDevice) == hipSuccess &&
-                        hipMemcpy(b + o2, ys[0].data(), ys[0].size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                        hipMemcpy(b + o3, ys[1].data(), ys[1].size() * 4, hipMemcpyHostToDevice) == hipSuccess) {
-                        c->mf_tiles[0] = b; c->mf_tiles[1] = b + o1;
-                        c->mf_ys[0] = reinterpret_cast<const int32_t *>(b + o2);
-                        c->mf_ys[1] = reinterpret_cast<const int32_t *>(b + o3);
-                        c->mf_ntiles[0] = nl; c->mf_ntiles[1] = nc;
-                        c->mf_chr_pair = nv_in;
-                        c->mf_ok = 1;
-                    }
+                void *at[4];
+                if (upload(c->mf_dev, { part(tl), part(tc), part(ys[0]), part(ys[1]) }, 256, at, 256)) {
+                    c->mf_tiles[0] = static_cast<const uint8_t *>(at[0]); c->mf_tiles[1] = static_cast<const uint8_t *>(at[1]);
+                    c->mf_ys[0] = static_cast<const int32_t *>(at[2]);
+                    c->mf_ys[1] = static_cast<const int32_t *>(at[3]);
+                    c->mf_ntiles[0] = nl; c->mf_ntiles[1] = nc;
+                    c->mf_chr_pair = nv_in;
+                    c->mf_ok = 1;
                 }
             }
         }
@@ -1196,7 +1167,7 @@ extern "C" FFHipSwsContext *ffhip_sws_getContext(int srcW, int srcH, int srcForm
     g_sws_create_flat_dither = 0;
     ffhip_sws_tables_free(h);
     if (c && inner) {
-        c->rgb_in = ri;
+        c->rgb_in = std::move(ri);
         rgb_in_plan_luma(c);
     }
     return c;
@@ -1227,7 +1198,7 @@ extern "C" FFHipSwsContext *ffhip_sws_from_tables_rgb_source(const FFHipSwsTable
     FFHipSwsContext *c = ffhip_sws_from_tables(t);
     g_sws_create_flat_dither = 0;
     if (c) {
-        c->rgb_in = ri;
+        c->rgb_in = std::move(ri);
         rgb_in_plan_luma(c);
     }
     return c;
@@ -1248,54 +1219,47 @@ static void rgb_in_plan_luma(FFHipSwsContext *c)
     const FFHipSwsTables &t = c->t;
     int dd = 8, dl = 0;
     (void)ffhip_pixfmt_hbd(t.dstFormat, &dd, &dl, nullptr, nullptr);
-    bool id = c->w16_ok && dd == 8 && !fmt_rgb(t.dstFormat) && t.srcW == t.dstW && t.srcH == t.dstH && c->d[0].size == 1 && c->d[2].size == 1 &&
-              t.src_range == t.dst_range;
-    for (int x = 0; id && x < t.dstW; x++)
-        id = c->f[0][(size_t)x] == 16384 && c->p[0][(size_t)x] == x;
-    for (int y = 0; id && y < t.dstH; y++)
-        id = c->f[2][(size_t)y] == 4096 && c->p[2][(size_t)y] == y;
+    const bool id = c->w16_ok && dd == 8 && !fmt_rgb(t.dstFormat) && t.srcW == t.dstW && t.srcH == t.dstH && t.src_range == t.dst_range &&
+                    bank_is_identity(c, 0, t.dstW) && bank_is_identity(c, 2, t.dstH);
     c->rgb_in.y_direct = id;
     /* every bank the identity (round 6): a planar 8-bit target with a chroma sample per converter sample and a chroma row per source row */
-    {
-        bool dc = id && c->flat_dither == 1 && c->chrSrcH == t.srcH && c->d[3].n == t.srcH && c->d[3].size == 1 && c->d[1].size == 1 &&
-                  c->d[1].n == (c->rgb_in.half ? t.srcW / 2 : t.srcW) && !fmt_nv(t.dstFormat) && !t.dst_alpha_fill;
-        for (int x = 0; dc && x < c->d[1].n; x++)
-            dc = c->f[1][(size_t)x] == 16384 && c->p[1][(size_t)x] == x;
-        for (int y = 0; dc && y < c->d[3].n; y++)
-            dc = c->f[3][(size_t)y] == 4096 && c->p[3][(size_t)y] == y;
-        c->rgb_in.direct_c = dc;
-    }
+    c->rgb_in.direct_c = id && c->flat_dither == 1 && c->chrSrcH == t.srcH && !fmt_nv(t.dstFormat) && !t.dst_alpha_fill &&
+                         bank_is_identity(c, 1, c->rgb_in.half ? t.srcW / 2 : t.srcW) && bank_is_identity(c, 3, t.srcH);
     /* the whole conversion in one kernel (round 6): 4:2:0 target, chroma read at half width through the identity bank, 2:1 down the rows on
      * a bank of the exact-2:1 shape, the flat seed 64 */
-    bool f4 = id && c->rgb_in.half && c->flat_dither == 1 && !(t.srcW & 3) && t.srcW >= 4 && !(t.srcH & 1) && c->chrSrcH == t.srcH &&
-              c->d[3].n * 2 == t.srcH && c->d[1].n * 2 == t.srcW && c->d[1].size == 1 &&
-              (t.dstFormat == FFHIP_PIX_FMT_NV12 || t.dstFormat == FFHIP_PIX_FMT_YUV420P) && !c->rgb_in.vfv;
-    for (int x = 0; f4 && x < c->d[1].n; x++)
-        f4 = c->f[1][(size_t)x] == 16384 && c->p[1][(size_t)x] == x;
+    const bool f4 = id && c->rgb_in.half && c->flat_dither == 1 && !(t.srcW & 3) && t.srcW >= 4 && !(t.srcH & 1) && c->chrSrcH == t.srcH &&
+                    c->d[3].n * 2 == t.srcH && (t.dstFormat == FFHIP_PIX_FMT_NV12 || t.dstFormat == FFHIP_PIX_FMT_YUV420P) && !c->rgb_in.vfv.p &&
+                    bank_is_identity(c, 1, t.srcW / 2);
     std::vector<uint32_t> vb;
     if (f4 && ffhip_down2_virtual_bank(c->f[3].data(), c->p[3].data(), c->d[3].size, c->d[3].n, c->chrSrcH, &vb)) {
         vb.resize((size_t)(c->d[3].n + 8) * 4, 0);
-        if (hipMalloc(&c->rgb_in.vfv, vb.size() * 4) == hipSuccess &&
-            hipMemcpy(c->rgb_in.vfv, vb.data(), vb.size() * 4, hipMemcpyHostToDevice) == hipSuccess)
-            c->rgb_in.fused420 = 1;
+        void *at[1];
+        c->rgb_in.fused420 = upload(c->rgb_in.vfv, { part(vb) }, 4, at);
     }
+}
+
+/* the converter pass's source rows and coefficients (its targets are the caller's to fill) */
+static FFHipRgbInArgs rgb_in_args(const FFHipSwsContext *c, const void *src, ptrdiff_t src_stride, size_t src_fp, int rows)
+{
+    FFHipRgbInArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = static_cast<const uint8_t *>(src); a.src_stride = src_stride; a.src_fp = src_fp;
+    a.w = c->t.srcW; a.h = rows;
+    a.ro = c->rgb_in.ofs[0]; a.go = c->rgb_in.ofs[1]; a.bo = c->rgb_in.ofs[2];
+    const int32_t *T = c->rgb_in.table;
+    a.ry = T[0]; a.gy = T[1]; a.by = T[2]; a.ru = T[3]; a.gu = T[4]; a.bu = T[5]; a.rv = T[6]; a.gv = T[7]; a.bv = T[8];
+    return a;
 }
 
 /* the converter pass of an RGB-source context over `rows` source rows of nframes frames: src -> the 14-bit planes at p[] */
 static int rgb_in_launch(const FFHipSwsContext *c, int nframes, const uint8_t *src, ptrdiff_t src_stride, size_t src_fp, int rows, uint8_t *const p[3],
                          const int pitch[3], const size_t fp[3], hipStream_t stream, uint8_t *y8 = nullptr, ptrdiff_t y8_stride = 0, size_t y8_fp = 0)
 {
-    FFHipRgbInArgs a;
-    memset(&a, 0, sizeof(a));
+    FFHipRgbInArgs a = rgb_in_args(c, src, src_stride, src_fp, rows);
     a.y8 = y8; a.y8_stride = y8_stride; a.y8_fp = y8_fp;
-    a.src = src; a.src_stride = src_stride; a.src_fp = src_fp;
     for (int i = 0; i < 3; i++) {
         a.dst[i] = p[i]; a.dst_stride[i] = pitch[i]; a.dst_fp[i] = fp[i];
     }
-    a.w = c->t.srcW; a.h = rows;
-    a.ro = c->rgb_in.ofs[0]; a.go = c->rgb_in.ofs[1]; a.bo = c->rgb_in.ofs[2];
-    const int32_t *T = c->rgb_in.table;
-    a.ry = T[0]; a.gy = T[1]; a.by = T[2]; a.ru = T[3]; a.gu = T[4]; a.bu = T[5]; a.rv = T[6]; a.gv = T[7]; a.bv = T[8];
     return ffhip_launch_sws_rgb_in(a, c->rgb_in.bpp, c->rgb_in.half, nframes, stream);
 }
 
@@ -1397,54 +1361,115 @@ extern "C" void ffhip_sws_freeContext(FFHipSwsContext *c)
     if (!c)
         return;
     FFHipDeviceGuard dg(c->device);
-    if (c->dev_tables)
-        (void)hipFree(c->dev_tables);
-    if (c->widen_tmp)
-        (void)hipFree(c->widen_tmp);
-    if (c->rgb_in.vfv)
-        (void)hipFree(c->rgb_in.vfv);
-    if (c->rgb_in.planes)
-        (void)hipFree(c->rgb_in.planes);
-    if (c->rgb_in.stage)
-        (void)hipFree(c->rgb_in.stage);
-    if (c->mf_dev)
-        (void)hipFree(c->mf_dev);
-    if (c->up2_dev)
-        (void)hipFree(c->up2_dev);
-    for (int i = 0; i < 16; i++)
-        if (c->tune_ev[i])
-            (void)hipEventDestroy(c->tune_ev[i]);
-    if (c->u2r_dev)
-        (void)hipFree(c->u2r_dev);
-    if (c->rgb2_tmp)
-        (void)hipFree(c->rgb2_tmp);
-    if (c->rgb2_done)
-        (void)hipEventDestroy(c->rgb2_done);
-    if (c->rgb2_aux) {
-        (void)hipStreamSynchronize(c->rgb2_aux);
-        (void)hipStreamDestroy(c->rgb2_aux);
-    }
-    if (c->rgb2_fork)
-        (void)hipEventDestroy(c->rgb2_fork);
-    if (c->rgb2_join)
-        (void)hipEventDestroy(c->rgb2_join);
-    if (c->eqr_dev)
-        (void)hipFree(c->eqr_dev);
-    if (c->w16_dev)
-        (void)hipFree(c->w16_dev);
-    if (c->dn2_dev)
-        (void)hipFree(c->dn2_dev);
-    if (c->d32_dev)
-        (void)hipFree(c->d32_dev);
-    if (c->u32_dev)
-        (void)hipFree(c->u32_dev);
-    if (c->dev_ntables)
-        (void)hipFree(c->dev_ntables);
-    if (c->dev_wtables)
-        (void)hipFree(c->dev_wtables);
-    if (c->stage)
-        (void)hipFree(c->stage);
     delete c;
+}
+
+/* a knob of the measure build whose first character is `v` (the product build has none: FFHIP_KNOB() is a null constant there) */
+static inline bool knob_is(const char *e, char v) { return e && e[0] == v; }
+#define KNOB_IS(name, v) knob_is(FFHIP_KNOB(name), v)
+
+/* one side of a call: the luma plane and the two chroma channels (address, stride, frame pitch; the channels of an interleaved pair are its
+ * first U and V samples), the pair's lower address and whether V comes first in it, and what the fast kernels ask of the planes */
+struct SidePlanes {
+    uint8_t *p[3] = {};
+    ptrdiff_t stride[3] = {};
+    size_t fp[3] = {};
+    bool il = false;          /* the chroma is an interleaved pair: plane 1 */
+    uint8_t *pair = nullptr;  /* plane 1's address: the pair's lower one */
+    bool swap = false;        /* V at the lower address (NV21) */
+    uintptr_t lal = 0, cal = 0; /* luma / chroma: every address (a pair's lower one), stride and frame pitch or-ed (4-byte alignment) */
+    bool neg = false;         /* a stride below zero */
+    bool pos = true;          /* every stride above zero */
+    uintptr_t al() const { return lal | cal; }
+};
+
+/* np planes (1: one packed plane, 2: luma and an interleaved pair, 3: planar) of `bytes`-byte samples; vfirst: V leads the pair */
+static SidePlanes side_planes(const void *const pl[4], const int stride[4], const size_t fp[4], int np, bool vfirst = false, int bytes = 1)
+{
+    SidePlanes s;
+    for (int i = 0; i < np; i++) {
+        (i ? s.cal : s.lal) |= (uintptr_t)pl[i] | (size_t)stride[i] | fp[i];
+        s.neg = s.neg || stride[i] < 0;
+        s.pos = s.pos && stride[i] > 0;
+    }
+    s.il = np == 2;
+    for (int k = 0; k < (np > 1 ? 3 : 1); k++) {
+        const int i = s.il && k ? 1 : k;
+        s.p[k] = static_cast<uint8_t *>(const_cast<void *>(pl[i])) + (s.il && k && (k == 2) != vfirst ? bytes : 0);
+        s.stride[k] = stride[i];
+        s.fp[k] = fp[i];
+    }
+    s.pair = np > 1 ? static_cast<uint8_t *>(const_cast<void *>(pl[1])) : nullptr;
+    s.swap = s.il && vfirst;
+    return s;
+}
+
+/* a job of a static-schedule kernel: bank `which` (0 luma, 1 chroma) on one plane (0 Y, 1 U, 2 V), or on an interleaved pair (plane 1)
+ * through the lower addresses of both sides; swap: the two sides' pairs are in opposite orders, dswap: V leads the target's pair */
+struct PlaneJob {
+    int which, plane;
+    const uint8_t *src;
+    uint8_t *dst;
+    ptrdiff_t sstride, dstride;
+    size_t sfp, dfp;
+    int pair, swap, dswap;
+};
+
+/* the luma job (`luma`), then (`chroma`) the pair job when the source's chroma is an interleaved pair, else one job per chroma plane */
+template <class F> static void for_each_job(const SidePlanes &s, const SidePlanes &d, bool luma, bool chroma, F &&fill)
+{
+    if (luma)
+        fill(PlaneJob{ 0, 0, s.p[0], d.p[0], s.stride[0], d.stride[0], s.fp[0], d.fp[0], 0, 0, 0 });
+    if (!chroma)
+        return;
+    if (s.il)
+        fill(PlaneJob{ 1, 1, s.pair, d.pair, s.stride[1], d.stride[1], s.fp[1], d.fp[1], 1, s.swap != d.swap, d.swap });
+    else
+        for (int k = 1; k < 3; k++)
+            fill(PlaneJob{ 1, k, s.p[k], d.p[k], s.stride[k], d.stride[k], s.fp[k], d.fp[k], 0, 0, 0 });
+}
+template <class J> static void put_planes(J &j, const PlaneJob &q)
+{
+    j.src = q.src; j.dst = q.dst; j.sstride = q.sstride; j.dstride = q.dstride; j.sfp = q.sfp; j.dfp = q.dfp;
+    j.pair = q.pair;
+}
+
+/* a packed-RGB kernel's source: Y, U, V (an interleaved pair: its plane in both chroma slots) */
+template <class A> static void put_src(A &a, const SidePlanes &s)
+{
+    for (int i = 0; i < 3; i++) {
+        a.src[i] = i && s.il ? s.pair : s.p[i];
+        a.sstride[i] = s.stride[i];
+        a.sfp[i] = s.fp[i];
+    }
+}
+
+/* frames per wave of the exact-2x kernel (1 << fshift): the split that wastes the fewest lanes at the right edge of the rows, among those
+ * whose lane offsets (frame pitches included) stay below 2^31; -1 when none does */
+static int up2_fshift(const FFHipUp2Args &U, int nframes)
+{
+    int best = -1;
+    double bestw = 1e30;
+    for (int fsft = 0; fsft <= 2; fsft++) {
+        const int lpf = 64 >> fsft;
+        bool fits = !(nframes < (1 << fsft) && fsft);
+        double w = 0;
+        for (int i = 0; i < U.njobs; i++) {
+            const FFHipUp2Job &j = U.job[i];
+            const unsigned long long span_s = (unsigned long long)((1 << fsft) - 1) * j.sfp + (unsigned long long)j.srcH * (size_t)(j.sstride < 0 ? -j.sstride : j.sstride);
+            const unsigned long long span_d = (unsigned long long)((1 << fsft) - 1) * j.dfp + 2ull * j.srcH * (size_t)(j.dstride < 0 ? -j.dstride : j.dstride);
+            if (span_s >= (1ull << 31) || span_d >= (1ull << 31))
+                fits = false;
+            /* waves per frame and strip: the full blocks, plus this frame's share of the shared ragged-end blocks */
+            const int nfull = fsft ? j.ngroups / 64 : 0;
+            w += ((double)nfull + (double)cdiv(j.ngroups - nfull * 64, lpf) / (1 << fsft)) * j.srcH;
+        }
+        if (fits && w < bestw - 1e-9) {
+            bestw = w;
+            best = fsft;
+        }
+    }
+    return best;
 }
 
 /* a context with a side above 8 bits: luma, then the two chroma channels (planes of their own or the halves of an interleaved pair) */
@@ -1463,325 +1488,219 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
     for (int pl = 0; pl < (hrgb ? 1 : dl ? 2 : 3); pl++)
         if (!dst[pl] || (dstStride[pl] % dsz) || (dstFramePitch[pl] % dsz) || ((uintptr_t)dst[pl] % dsz))
             return FFHIP_EINVAL;
+    /* the caller's planes (down2, down32 and the tiled kernel read these), the walker's source (widened below) and the target */
+    const SidePlanes cs = side_planes(src, srcStride, srcFramePitch, sl ? 2 : 3, false, ssz);
+    const SidePlanes d = side_planes(dst, dstStride, dstFramePitch, hrgb ? 1 : dl ? 2 : 3, false, dsz);
+    SidePlanes ws = cs;
     /* (round 6) an 8-bit source on the walker: the planes widened to 16-bit samples in the context's own memory; from here on the source is
      * "depth 8 in words", planar or an interleaved pair plane.  When the walker cannot run (alignment) the tiled kernel takes the bytes. */
-    const void *wsrc[4] = { src[0], src[1], src[2], nullptr };
-    int wss[4] = { srcStride[0], srcStride[1], srcStride[2], 0 };
-    size_t wsf[4] = { srcFramePitch[0], srcFramePitch[1], srcFramePitch[2], 0 };
-    std::unique_lock<std::mutex> wlk;
+    ScratchLease wlease;
     bool widened = false;
-    if (c->widen8 && (c->w16_ok || c->up2_ok || c->u32_ok)) {
-        bool ok = true;
-        for (int pl = 0; ok && pl < (dl ? 2 : 3); pl++)
-            ok = dstStride[pl] > 0 && !(((uintptr_t)dst[pl] | (uintptr_t)dstStride[pl] | dstFramePitch[pl]) & 3);
-        for (int pl = 0; ok && pl < (sl ? 2 : 3); pl++)
-            ok = srcStride[pl] > 0;
-        const char *ew = FFHIP_KNOB(c->up2_ok ? "FFHIP_SWS_UP2" : "FFHIP_SWS_WALK16");
-        if (ok && !(ew && ew[0] == '0')) {
-            const int np = sl ? 2 : 3;
-            const int wb[3] = { t.srcW, sl ? 2 * c->chrSrcW : c->chrSrcW, c->chrSrcW }, rows[3] = { t.srcH, c->chrSrcH, c->chrSrcH };
-            size_t pitch[3], fp[3], off[3], need = 0;
-            for (int pl = 0; pl < np; pl++) {
-                pitch[pl] = ((size_t)2 * wb[pl] + 255) & ~(size_t)255;
-                fp[pl] = pitch[pl] * (size_t)rows[pl];
-                off[pl] = need;
-                need += fp[pl] * (size_t)nframes;
-            }
-            wlk = std::unique_lock<std::mutex>(c->rgb2_mu); /* the planes are the context's: one batch in flight */
-            if (need > c->widen_tmp_sz) {
-                if (c->widen_tmp) {
-                    HIP_TRY(hipDeviceSynchronize());
-                    HIP_TRY(hipFree(c->widen_tmp));
-                }
-                c->widen_tmp = nullptr;
-                c->widen_tmp_sz = 0;
-                HIP_TRY(hipMalloc(&c->widen_tmp, need));
-                c->widen_tmp_sz = need;
-            }
-            for (int pl = 0; pl < np; pl++) {
-                uint8_t *d = static_cast<uint8_t *>(c->widen_tmp) + off[pl];
-                const int r = ffhip_launch_sws_widen8(static_cast<const uint8_t *>(src[pl]), srcStride[pl], srcFramePitch[pl], d, (ptrdiff_t)pitch[pl], fp[pl],
-                                                      wb[pl], rows[pl], nframes, stream);
-                if (r < 0)
-                    return r;
-                wsrc[pl] = d; wss[pl] = (int)pitch[pl]; wsf[pl] = fp[pl];
-            }
-            widened = true;
-            sl = sl ? 1 : 0; /* an interleaved pair plane of words, as P01x has it (samples in the LOW bits: smsb stays off) */
+    if (c->widen8 && (c->w16_ok || c->up2_ok || c->u32_ok) && d.pos && !(d.al() & 3) && cs.pos &&
+        !KNOB_IS(c->up2_ok ? "FFHIP_SWS_UP2" : "FFHIP_SWS_WALK16", '0')) {
+        const int np = sl ? 2 : 3;
+        const int wb[3] = { t.srcW, sl ? 2 * c->chrSrcW : c->chrSrcW, c->chrSrcW }, rows[3] = { t.srcH, c->chrSrcH, c->chrSrcH };
+        size_t pitch[3], fp[3], off[3], need = 0;
+        for (int pl = 0; pl < np; pl++) {
+            pitch[pl] = ((size_t)2 * wb[pl] + 255) & ~(size_t)255;
+            fp[pl] = pitch[pl] * (size_t)rows[pl];
+            off[pl] = need;
+            need += fp[pl] * (size_t)nframes;
+        }
+        HIP_TRY(acquire(c->widen_tmp, wlease, need, stream)); /* the planes are the context's: one batch in flight */
+        const void *wsrc[4] = {};
+        int wss[4] = {};
+        size_t wsf[4] = {};
+        for (int pl = 0; pl < np; pl++) {
+            uint8_t *w = static_cast<uint8_t *>(c->widen_tmp.buf.p) + off[pl];
+            const int r = ffhip_launch_sws_widen8(static_cast<const uint8_t *>(src[pl]), srcStride[pl], srcFramePitch[pl], w, (ptrdiff_t)pitch[pl], fp[pl],
+                                                  wb[pl], rows[pl], nframes, stream);
+            if (r < 0)
+                return r;
+            wsrc[pl] = w; wss[pl] = (int)pitch[pl]; wsf[pl] = fp[pl];
+        }
+        widened = true;
+        sl = sl ? 1 : 0; /* an interleaved pair plane of words, as P01x has it (samples in the LOW bits: smsb stays off) */
+        ws = side_planes(wsrc, wss, wsf, np, false, 2);
+    }
+    /* (c->widen8 && !widened: the tiled kernel below, on the caller's planes) */
+    const uintptr_t al = ws.al() | (hrgb ? 0 : d.al()); /* (a packed target is written by the second stage, from the intermediate) */
+    const bool neg = ws.neg || d.neg;
+    const int sw[2] = { t.srcW, c->chrSrcW }, sh[2] = { t.srcH, c->chrSrcH };
+    if (c->up2_ok && (widened || !c->widen8) && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_UP2", '0')) {
+        /* exact 2x above 8 bits: the static-schedule kernel (FFHIP_SWS_UP2=0: the tiled k_sws_scale16) */
+        FFHipUp2Args U;
+        memset(&U, 0, sizeof(U));
+        U.nframes = nframes;
+        U.xcd = 1;
+        for_each_job(ws, d, true, true, [&](const PlaneJob &q) {
+            FFHipUp2Job &j = U.job[U.njobs++];
+            put_planes(j, q);
+            j.swap = q.swap;
+            j.srcW = sw[q.which]; j.srcH = sh[q.which];
+            j.ngroups = q.pair ? j.srcW / 2 : j.srcW / 4;
+            j.hfv = c->up2_h[q.which]; j.vfv = c->up2_v[q.which];
+            j.hb_sdepth = sd; j.hb_ddepth = dd; j.hb_smsb = sl == 1 && !widened; j.hb_dmsb = dl == 1;
+        });
+        /* frames per wave as at 8 bits; when no split keeps the lane offsets in range this side takes the next kernel (the 8-bit side
+         * launches with fshift 0) */
+        const int fs = up2_fshift(U, nframes);
+        if (fs >= 0) {
+            U.fshift = fs;
+            for (int i = 0; i < U.njobs; i++)
+                ffhip_up2_plan_job(&U.job[i], 64 >> U.fshift, 60);
+            const char *ev2 = FFHIP_KNOB("FFHIP_UP2_VAR"); /* measure build: rows in flight (FFHIP_UP2_DEPTH), 1 = non-temporal stores */
+            /* six rows in flight (round 6, with the straight-line rows: p010 1080p -> 4K 0.615 -> 0.63, planar unchanged) */
+            return ffhip_launch_up2(U, KNOB_IS("FFHIP_UP2_DEPTH", '3') ? 3 : 6, ev2 ? atoi(ev2) : 0, stream);
         }
     }
-    if (c->widen8 && !widened) { /* falls to the tiled kernel below with the caller's planes */ }
-    {
-        uintptr_t al = 0;
-        bool neg = false;
-        for (int pl = 0; pl < (sl ? 2 : 3); pl++) {
-            al |= (uintptr_t)wsrc[pl] | (uintptr_t)wss[pl] | wsf[pl] | (uintptr_t)dst[pl] | (uintptr_t)dstStride[pl] | dstFramePitch[pl];
-            neg = neg || wss[pl] < 0 || dstStride[pl] < 0;
-        }
-        const char *eu = FFHIP_KNOB("FFHIP_SWS_UP2");
-        if (c->up2_ok && (widened || !c->widen8) && !(al & 3) && !neg && !(eu && eu[0] == '0')) {
-            /* exact 2x above 8 bits: the static-schedule kernel (FFHIP_SWS_UP2=0: the tiled k_sws_scale16) */
-            FFHipUp2Args U;
-            memset(&U, 0, sizeof(U));
-            U.nframes = nframes;
-            U.xcd = 1;
-            const int cw = c->chrSrcW, chh = c->chrSrcH;
-            auto upjob = [&](int which, int plane, int w, int h, int pair) {
-                FFHipUp2Job &j = U.job[U.njobs++];
-                j.src = static_cast<const uint8_t *>(wsrc[plane]); j.dst = static_cast<uint8_t *>(dst[plane]);
-                j.sstride = wss[plane]; j.dstride = dstStride[plane]; j.sfp = wsf[plane]; j.dfp = dstFramePitch[plane];
-                j.pair = pair; j.swap = 0;
-                j.srcW = w; j.srcH = h;
-                j.ngroups = pair ? w / 2 : w / 4;
-                j.hfv = c->up2_h[which]; j.vfv = c->up2_v[which];
-                j.hb_sdepth = sd; j.hb_ddepth = dd; j.hb_smsb = sl == 1 && !widened; j.hb_dmsb = dl == 1;
-            };
-            upjob(0, 0, t.srcW, t.srcH, 0);
-            if (sl) {
-                upjob(1, 1, cw, chh, 1);
-            } else {
-                upjob(1, 1, cw, chh, 0);
-                upjob(1, 2, cw, chh, 0);
-            }
-            /* frames per wave: as at 8 bits, the split that wastes the fewest lanes at the right edge of the rows */
-            int best = 0;
-            double bestw = 1e30;
-            for (int fsft = 0; fsft <= 2; fsft++) {
-                const int lpf = 64 >> fsft;
-                bool fits = !(nframes < (1 << fsft) && fsft);
-                double w = 0;
-                for (int i = 0; i < U.njobs; i++) {
-                    const FFHipUp2Job &j = U.job[i];
-                    const unsigned long long span_s = (unsigned long long)((1 << fsft) - 1) * j.sfp + (unsigned long long)j.srcH * (size_t)j.sstride;
-                    const unsigned long long span_d = (unsigned long long)((1 << fsft) - 1) * j.dfp + 2ull * j.srcH * (size_t)j.dstride;
-                    if (span_s >= (1ull << 31) || span_d >= (1ull << 31))
-                        fits = false;
-                    const int nfull = fsft ? j.ngroups / 64 : 0;
-                    w += ((double)nfull + (double)cdiv(j.ngroups - nfull * 64, lpf) / (1 << fsft)) * j.srcH;
-                }
-                if (fits && w < bestw - 1e-9) { bestw = w; best = fsft; }
-            }
-            if (bestw < 1e29) {
-                U.fshift = best;
-                for (int i = 0; i < U.njobs; i++)
-                    ffhip_up2_plan_job(&U.job[i], 64 >> U.fshift, 60);
-                {
-                    const char *ed = FFHIP_KNOB("FFHIP_UP2_DEPTH"), *ev2 = FFHIP_KNOB("FFHIP_UP2_VAR"); /* measure build: rows in flight, 1 = non-temporal stores */
-                    /* six rows in flight (round 6, with the straight-line rows: p010 1080p -> 4K 0.615 -> 0.63, planar unchanged) */
-                    return ffhip_launch_up2(U, ed && ed[0] == '3' ? 3 : 6, ev2 ? atoi(ev2) : 0, stream);
-                }
-            }
-        }
-        const char *e2 = FFHIP_KNOB("FFHIP_SWS_DOWN2");
-        if (c->dn2_ok && !(al & 3) && !neg && !(e2 && e2[0] == '0')) {
-            /* exact 2:1 above 8 bits: the static-schedule kernel (FFHIP_SWS_DOWN2=0: the tiled k_sws_scale16) */
-            FFHipDn2Args D;
-            memset(&D, 0, sizeof(D));
-            D.nframes = nframes;
-            D.xcd = 1;
-            auto dnjob = [&](int which, int plane, int dw_, int sh_, int dh_, int pair) {
-                FFHipDn2Job &j = D.job[D.njobs++];
-                j.src = static_cast<const uint8_t *>(src[plane]); j.dst = static_cast<uint8_t *>(dst[plane]);
-                j.sstride = srcStride[plane]; j.dstride = dstStride[plane]; j.sfp = srcFramePitch[plane]; j.dfp = dstFramePitch[plane];
-                j.pair = pair; j.swap = 0;
-                j.srcH = sh_; j.dstH = dh_;
-                j.ngroups = pair ? dw_ / 2 : dw_ / 4;
-                j.hfv = c->dn2_h[which]; j.vfv = c->dn2_v[which];
-                j.hb_sdepth = sd; j.hb_ddepth = dd; j.hb_smsb = sl == 1; j.hb_dmsb = dd > 8 && dl == 1;
-                j.dither_off = plane == 2 ? 3 : 0;
-                ffhip_down2_plan_job(&j, 32);
-            };
-            dnjob(0, 0, t.dstW, t.srcH, t.dstH, 0);
-            if (sl) {
-                dnjob(1, 1, c->d[1].n, c->chrSrcH, c->d[3].n, 1);
-            } else {
-                dnjob(1, 1, c->d[1].n, c->chrSrcH, c->d[3].n, 0);
-                dnjob(1, 2, c->d[1].n, c->chrSrcH, c->d[3].n, 0);
-            }
-            return ffhip_launch_down2(D, stream);
-        }
+    if (c->dn2_ok && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_DOWN2", '0')) {
+        /* exact 2:1 above 8 bits: the static-schedule kernel (FFHIP_SWS_DOWN2=0: the tiled k_sws_scale16) */
+        FFHipDn2Args D;
+        memset(&D, 0, sizeof(D));
+        D.nframes = nframes;
+        D.xcd = 1;
+        for_each_job(cs, d, true, true, [&](const PlaneJob &q) {
+            FFHipDn2Job &j = D.job[D.njobs++];
+            put_planes(j, q);
+            j.swap = q.swap;
+            j.srcH = sh[q.which]; j.dstH = c->d[2 + q.which].n;
+            j.ngroups = q.pair ? c->d[q.which].n / 2 : c->d[q.which].n / 4;
+            j.hfv = c->dn2_h[q.which]; j.vfv = c->dn2_v[q.which];
+            j.hb_sdepth = sd; j.hb_ddepth = dd; j.hb_smsb = sl == 1; j.hb_dmsb = dd > 8 && dl == 1;
+            j.dither_off = q.plane == 2 ? 3 : 0;
+            ffhip_down2_plan_job(&j, 32);
+        });
+        return ffhip_launch_down2(D, stream);
     }
-    {
-        const char *ew = FFHIP_KNOB("FFHIP_SWS_WALK16"); /* measured variant: 0 = the tiled k_sws_scale16 */
-        uintptr_t al = 0;
-        bool neg = false;
-        for (int pl = 0; pl < (sl ? 2 : 3); pl++) {
-            al |= (uintptr_t)wsrc[pl] | (uintptr_t)wss[pl] | wsf[pl];
-            neg = neg || wss[pl] < 0;
+    if (hrgb && !(c->w16_ok && !(al & 3) && !neg)) {
+        ffhip_set_error("ffhip_sws: above 8 bits into packed RGB needs 4-byte aligned planes and pitches, top-down");
+        return FFHIP_EINVAL;
+    }
+    if (c->d32_ok && !hrgb && !widened && !c->widen8 && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_DOWN32", '0')) {
+        /* exact 3:2 down above 8 bits: the static-schedule kernel's 16-bit twin (FFHIP_SWS_DOWN32=0: the walker) */
+        FFHipD32Args D;
+        memset(&D, 0, sizeof(D));
+        D.nframes = nframes;
+        D.hb = 1; D.sdepth = sd; D.ddepth = dd; D.smsb = sl == 1; D.dmsb = dl == 1;
+        D.ratio43 = c->d32_ok == 2;
+        const int pin = D.ratio43 ? 4 : 3, pout = D.ratio43 ? 3 : 2;
+        for_each_job(cs, d, true, true, [&](const PlaneJob &q) {
+            FFHipD32Job &j = D.job[D.njobs++];
+            put_planes(j, q);
+            j.swap = q.swap;
+            j.srcH = sh[q.which]; j.dstH = j.srcH / pin * pout;
+            j.ngroups = q.pair ? c->d[q.which].n / pout : c->d[q.which].n / (2 * pout);
+            j.hfv = c->d32_h[q.which]; j.vfv = c->d32_v[q.which];
+            j.dither_off = q.plane == 2 ? 3 : 0;
+        });
+        return ffhip_launch_down32(D, stream);
+    }
+    if (c->u32_ok && !hrgb && (widened || !c->widen8) && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_UP32", '0')) {
+        /* exact 3:2 up above 8 bits: the static-schedule kernel (FFHIP_SWS_UP32=0: the walker) */
+        FFHipU32Args U;
+        memset(&U, 0, sizeof(U));
+        U.nframes = nframes;
+        U.sdepth = sd; U.ddepth = dd; U.smsb = sl == 1 && !widened; U.dmsb = dl == 1;
+        U.ratio43 = c->u32_ok == 2;
+        const int pin = U.ratio43 ? 3 : 2, pout = U.ratio43 ? 4 : 3;
+        for_each_job(ws, d, true, true, [&](const PlaneJob &q) {
+            FFHipU32Job &j = U.job[U.njobs++];
+            put_planes(j, q);
+            j.srcH = sh[q.which]; j.dstH = j.srcH / pin * pout;
+            j.ngroups = q.pair ? c->d[q.which].n / pout : c->d[q.which].n / (2 * pout);
+            j.hfv = c->u32_h[q.which]; j.vfv = c->u32_v[q.which];
+        });
+        return ffhip_launch_up32(U, stream);
+    }
+    if (c->w16_ok && (widened || !c->widen8) && !(al & 3) && !neg && (hrgb || !KNOB_IS("FFHIP_SWS_WALK16", '0'))) {
+        /* a packed-RGB target (round 6): the walker writes the first stage — an int16 luma plane of unclipped sums, 8-bit chroma planes of
+         * half the width with a line per target line, flat dither: what yuv2rgb_X_c_template computes before its tables (output.c:1789-1840) —
+         * into the context's intermediate, and k_y16_rgb (sws_y16rgb.hip) turns it into pixels */
+        SidePlanes wd = d;
+        ScratchLease rlease;
+        size_t ypitch = 0, cpitch = 0, yfp = 0, cfp = 0;
+        if (hrgb) {
+            ypitch = ((size_t)2 * t.dstW + 255) & ~(size_t)255; cpitch = ((size_t)(t.dstW / 2) + 255) & ~(size_t)255;
+            yfp = ypitch * (size_t)t.dstH; cfp = cpitch * (size_t)t.dstH;
+            HIP_TRY(acquire(c->rgb2_tmp, rlease, (yfp + 2 * cfp) * (size_t)nframes, stream));
+            uint8_t *ty = static_cast<uint8_t *>(c->rgb2_tmp.buf.p);
+            const void *x[4] = { ty, ty + yfp * (size_t)nframes, ty + (yfp + cfp) * (size_t)nframes, nullptr };
+            const int xs[4] = { (int)ypitch, (int)cpitch, (int)cpitch, 0 };
+            const size_t xf[4] = { yfp, cfp, cfp, 0 };
+            wd = side_planes(x, xs, xf, 3);
         }
-        for (int pl = 0; pl < (hrgb ? 0 : dl ? 2 : 3); pl++) {
-            al |= (uintptr_t)dst[pl] | (uintptr_t)dstStride[pl] | dstFramePitch[pl];
-            neg = neg || dstStride[pl] < 0;
-        }
-        if (hrgb)
-            neg = neg || dstStride[0] < 0;
-        if (hrgb && !(c->w16_ok && !(al & 3) && !neg)) {
-            ffhip_set_error("ffhip_sws: above 8 bits into packed RGB needs 4-byte aligned planes and pitches, top-down");
-            return FFHIP_EINVAL;
-        }
-        const char *ed3 = FFHIP_KNOB("FFHIP_SWS_DOWN32");
-        if (c->d32_ok && !hrgb && !widened && !c->widen8 && !(al & 3) && !neg && !(ed3 && ed3[0] == '0')) {
-            /* exact 3:2 down above 8 bits: the static-schedule kernel's 16-bit twin (FFHIP_SWS_DOWN32=0: the walker) */
-            FFHipD32Args D;
-            memset(&D, 0, sizeof(D));
-            D.nframes = nframes;
-            D.hb = 1; D.sdepth = sd; D.ddepth = dd; D.smsb = sl == 1; D.dmsb = dl == 1;
-            D.ratio43 = c->d32_ok == 2;
-            const int pin = D.ratio43 ? 4 : 3, pout = D.ratio43 ? 3 : 2;
-            auto d3job = [&](int which, int plane, int dw_, int sh_, int pair) {
-                FFHipD32Job &j = D.job[D.njobs++];
-                j.src = static_cast<const uint8_t *>(src[plane]); j.dst = static_cast<uint8_t *>(dst[plane]);
-                j.sstride = srcStride[plane]; j.dstride = dstStride[plane]; j.sfp = srcFramePitch[plane]; j.dfp = dstFramePitch[plane];
-                j.pair = pair; j.swap = 0;
-                j.srcH = sh_; j.dstH = sh_ / pin * pout;
-                j.ngroups = pair ? dw_ / pout : dw_ / (2 * pout);
-                j.hfv = c->d32_h[which]; j.vfv = c->d32_v[which];
-                j.dither_off = plane == 2 ? 3 : 0;
+        FFHipW16Args W;
+        memset(&W, 0, sizeof(W));
+        W.nframes = nframes;
+        W.ht = c->w16_ht; W.vt = c->w16_vt;
+        W.sdepth = sd; W.ddepth = dd; W.smsb = sl == 1 && !widened; W.dmsb = dl == 1;
+        W.flat_dither = hrgb ? (c->hrgb_seed0 ? 2 : 1) : c->flat_dither;
+        /* rows per strip: 64 when the batch fills the chip several times over; a strip re-filters VT - 1 source rows, but a
+         * wave is one dependent chain of rows, and a launch of fewer waves than the chip holds (32 frames of 720p -> 1080p: 6,656
+         * against 7,168 slots) runs at the speed of one chain: halve until there are 1.5 slots' worth (measured, 720p -> 1080p:
+         * 64 rows 0.263, 32 rows 0.308, 16 rows 0.298 of HBM; the larger pictures are best at 64) */
+        int strip = 64;
+        {
+            const char *es = FFHIP_KNOB("FFHIP_W16_STRIP"); /* measured variant */
+            auto waves = [&](int st) {
+                const long long lum = (long long)cdiv(c->d[0].n, 256) * cdiv(c->d[2].n, st);
+                const long long chr = (sl || dl) ? (long long)cdiv(c->d[1].n, 128) * cdiv(c->d[3].n, st)
+                                                 : 2LL * cdiv(c->d[1].n, 256) * cdiv(c->d[3].n, st);
+                return (lum + chr) * nframes;
             };
-            d3job(0, 0, c->d[0].n, t.srcH, 0);
-            if (sl) {
-                d3job(1, 1, c->d[1].n, c->chrSrcH, 1);
-            } else {
-                d3job(1, 1, c->d[1].n, c->chrSrcH, 0);
-                d3job(1, 2, c->d[1].n, c->chrSrcH, 0);
-            }
-            return ffhip_launch_down32(D, stream);
+            if (es && atoi(es) > 0)
+                strip = atoi(es) > 64 ? 64 : atoi(es);
+            else
+                while (strip > 16 && waves(strip) < 3 * 7168 / 2)
+                    strip >>= 1;
         }
-        const char *eu3 = FFHIP_KNOB("FFHIP_SWS_UP32");
-        if (c->u32_ok && !hrgb && (widened || !c->widen8) && !(al & 3) && !neg && !(eu3 && eu3[0] == '0')) {
-            /* exact 3:2 up above 8 bits: the static-schedule kernel (FFHIP_SWS_UP32=0: the walker) */
-            FFHipU32Args U;
-            memset(&U, 0, sizeof(U));
-            U.nframes = nframes;
-            U.sdepth = sd; U.ddepth = dd; U.smsb = sl == 1 && !widened; U.dmsb = dl == 1;
-            U.ratio43 = c->u32_ok == 2;
-            const int pin = U.ratio43 ? 3 : 2, pout = U.ratio43 ? 4 : 3;
-            auto u3job = [&](int which, int plane, int dw_, int sh_, int pair) {
-                FFHipU32Job &j = U.job[U.njobs++];
-                j.src = static_cast<const uint8_t *>(wsrc[plane]); j.dst = static_cast<uint8_t *>(dst[plane]);
-                j.sstride = wss[plane]; j.dstride = dstStride[plane]; j.sfp = wsf[plane]; j.dfp = dstFramePitch[plane];
-                j.pair = pair;
-                j.srcH = sh_; j.dstH = sh_ / pin * pout;
-                j.ngroups = pair ? dw_ / pout : dw_ / (2 * pout);
-                j.hfv = c->u32_h[which]; j.vfv = c->u32_v[which];
-            };
-            u3job(0, 0, c->d[0].n, t.srcH, 0);
-            if (sl) {
-                u3job(1, 1, c->d[1].n, c->chrSrcH, 1);
-            } else {
-                u3job(1, 1, c->d[1].n, c->chrSrcH, 0);
-                u3job(1, 2, c->d[1].n, c->chrSrcH, 0);
+        /* channels ch0 .. ch0 + nch - 1 (0 Y, 1 U, 2 V): an interleaved side has both chroma channels in plane 1, the second one sample on */
+        auto job = [&](int which, int nch, int ch0) {
+            FFHipW16Job &j = W.job[W.njobs++];
+            j.nch = nch;
+            j.sstep = which && ws.il ? 2 : 1; j.dstep = which && wd.il ? 2 : 1;
+            j.dither_off = ch0 == 2 ? 3 : 0;
+            for (int k = 0; k < nch; k++) {
+                j.src[k] = ws.p[ch0 + k]; j.dst[k] = wd.p[ch0 + k];
+                j.sstride[k] = ws.stride[ch0 + k]; j.dstride[k] = wd.stride[ch0 + k];
+                j.sfp[k] = ws.fp[ch0 + k]; j.dfp[k] = wd.fp[ch0 + k];
             }
-            return ffhip_launch_up32(U, stream);
-        }
-        if (c->w16_ok && (widened || !c->widen8) && !(al & 3) && !neg && (hrgb || !(ew && ew[0] == '0'))) {
-            /* a packed-RGB target (round 6): the walker writes the first stage — an int16 luma plane of unclipped sums, 8-bit chroma planes of
-             * half the width with a line per target line, flat dither: what yuv2rgb_X_c_template computes before its tables (output.c:1789-1840) —
-             * into the context's intermediate, and k_y16_rgb (sws_y16rgb.hip) turns it into pixels */
-            void *xdst[4] = { dst[0], dst[1], dst[2], nullptr };
-            int xds[4] = { dstStride[0], dstStride[1], dstStride[2], 0 };
-            size_t xdf[4] = { dstFramePitch[0], dstFramePitch[1], dstFramePitch[2], 0 };
-            std::unique_lock<std::mutex> rlk;
-            size_t ypitch = 0, cpitch = 0, yfp = 0, cfp = 0;
-            if (hrgb) {
-                ypitch = ((size_t)2 * t.dstW + 255) & ~(size_t)255; cpitch = ((size_t)(t.dstW / 2) + 255) & ~(size_t)255;
-                yfp = ypitch * (size_t)t.dstH; cfp = cpitch * (size_t)t.dstH;
-                const size_t need = (yfp + 2 * cfp) * (size_t)nframes;
-                rlk = std::unique_lock<std::mutex>(c->rgb2_mu);
-                if (!c->rgb2_done)
-                    HIP_TRY(hipEventCreateWithFlags(&c->rgb2_done, hipEventDisableTiming));
-                else
-                    HIP_TRY(hipStreamWaitEvent(stream, c->rgb2_done, 0));
-                if (need > c->rgb2_tmp_sz) {
-                    if (c->rgb2_tmp)
-                        HIP_TRY(hipFree(c->rgb2_tmp));
-                    c->rgb2_tmp = nullptr;
-                    c->rgb2_tmp_sz = 0;
-                    HIP_TRY(hipMalloc(&c->rgb2_tmp, need));
-                    c->rgb2_tmp_sz = need;
-                }
-                uint8_t *ty = static_cast<uint8_t *>(c->rgb2_tmp);
-                xdst[0] = ty; xdst[1] = ty + yfp * (size_t)nframes; xdst[2] = ty + (yfp + cfp) * (size_t)nframes;
-                xds[0] = (int)ypitch; xds[1] = xds[2] = (int)cpitch;
-                xdf[0] = yfp; xdf[1] = xdf[2] = cfp;
-            }
-            FFHipW16Args W;
-            memset(&W, 0, sizeof(W));
-            W.nframes = nframes;
-            W.ht = c->w16_ht; W.vt = c->w16_vt;
-            W.sdepth = sd; W.ddepth = dd; W.smsb = sl == 1 && !widened; W.dmsb = dl == 1;
-            W.flat_dither = hrgb ? (c->hrgb_seed0 ? 2 : 1) : c->flat_dither;
-            /* rows per strip: 64 when the batch fills the chip several times over; a strip re-filters VT - 1 source rows, but a
-             * wave is one dependent chain of rows, and a launch of fewer waves than the chip holds (32 frames of 720p -> 1080p: 6,656
-             * against 7,168 slots) runs at the speed of one chain: halve until there are 1.5 slots' worth (measured, 720p -> 1080p:
-             * 64 rows 0.263, 32 rows 0.308, 16 rows 0.298 of HBM; the larger pictures are best at 64) */
-            int strip = 64;
+            j.srcH = sh[which];
+            j.y16 = hrgb && !which;
+            j.dstW = c->d[which].n; j.dstH = c->d[2 + which].n;
+            j.hf = c->w16[which].filter; j.hp = c->w16[which].pos; j.vf = c->w16[2 + which].filter; j.vp = c->w16[2 + which].pos;
+            j.srcW = sw[which];
             {
-                const char *es = FFHIP_KNOB("FFHIP_W16_STRIP"); /* measured variant */
-                auto waves = [&](int st) {
-                    const long long lum = (long long)cdiv(c->d[0].n, 256) * cdiv(c->d[2].n, st);
-                    const long long chr = (sl || dl) ? (long long)cdiv(c->d[1].n, 128) * cdiv(c->d[3].n, st)
-                                                     : 2LL * cdiv(c->d[1].n, 256) * cdiv(c->d[3].n, st);
-                    return (lum + chr) * nframes;
-                };
-                if (es && atoi(es) > 0)
-                    strip = atoi(es) > 64 ? 64 : atoi(es);
-                else
-                    while (strip > 16 && waves(strip) < 3 * 7168 / 2)
-                        strip >>= 1;
+                const char *eg = FFHIP_KNOB("FFHIP_W16_STAGE"); /* measure build: 0 keeps the per-lane global loads */
+                const int sp = c->w16_span[which][nch == 1 ? 0 : j.sstep == 2 ? 2 : 1];
+                /* staged when a wave's windows cover at most 512 bytes of a source row, i.e. when the picture grows: adjacent lanes'
+                 * windows then overlap several times over and the per-lane loads fetched every sample four to eight times (measured,
+                 * profiles/r06_walk16_lds.txt: p010 720p -> 1080p 0.270 -> 0.353, yuv420p10 1080p -> 1440p 0.329 -> 0.401 of HBM); wider
+                 * spans (down-scaling: 4K -> 1440p flat, 1080p -> 720p -4 %) keep the direct loads; FFHIP_W16_STAGE=1 stages up to 1 KiB */
+                j.stage = sp > 0 && sp <= (eg && eg[0] == '1' ? 1024 : 512) && !(eg && eg[0] == '0');
             }
-            auto job = [&](int which, int nch, int splane0, int dplane0) {
-                FFHipW16Job &j = W.job[W.njobs++];
-                j.nch = nch;
-                j.sstep = which && sl ? 2 : 1; j.dstep = which && dl ? 2 : 1;
-                j.dither_off = dplane0 == 2 ? 3 : 0;
-                for (int k = 0; k < nch; k++) {
-                    /* an interleaved side: both channels live in plane 1, the second one sample on; a planar side: planes 1 and 2 */
-                    const int sp = which && sl ? 1 : splane0 + k, dp = which && dl ? 1 : dplane0 + k;
-                    j.src[k] = static_cast<const uint8_t *>(wsrc[sp]) + (which && sl ? 2 * k : 0);
-                    j.dst[k] = static_cast<uint8_t *>(xdst[dp]) + (which && dl ? (dd == 8 ? 1 : 2) * k : 0);
-                    j.sstride[k] = wss[sp]; j.dstride[k] = xds[dp];
-                    j.sfp[k] = wsf[sp]; j.dfp[k] = xdf[dp];
-                }
-                j.srcH = which ? c->chrSrcH : t.srcH;
-                j.y16 = hrgb && !which;
-                j.dstW = c->d[which].n; j.dstH = c->d[2 + which].n;
-                j.hf = c->w16_f[which]; j.hp = c->w16_p[which]; j.vf = c->w16_f[2 + which]; j.vp = c->w16_p[2 + which];
-                j.srcW = which ? c->chrSrcW : t.srcW;
-                {
-                    const char *eg = FFHIP_KNOB("FFHIP_W16_STAGE"); /* measure build: 0 keeps the per-lane global loads */
-                    const int sp = c->w16_span[which][nch == 1 ? 0 : j.sstep == 2 ? 2 : 1];
-                    /* staged when a wave's windows cover at most 512 bytes of a source row, i.e. when the picture grows: adjacent lanes'
-                     * windows then overlap several times over and the per-lane loads fetched every sample four to eight times (measured,
-                     * profiles/r06_walk16_lds.txt: p010 720p -> 1080p 0.270 -> 0.353, yuv420p10 1080p -> 1440p 0.329 -> 0.401 of HBM); wider
-                     * spans (down-scaling: 4K -> 1440p flat, 1080p -> 720p -4 %) keep the direct loads; FFHIP_W16_STAGE=1 stages up to 1 KiB */
-                    j.stage = sp > 0 && sp <= (eg && eg[0] == '1' ? 1024 : 512) && !(eg && eg[0] == '0');
-                }
-                ffhip_w16_plan_job(&j, strip);
-            };
-            if (!c->rgb_in_luma_done)
-                job(0, 1, 0, 0);
-            if (sl || dl) {
-                job(1, 2, 1, 1);
-            } else {
-                job(1, 1, 1, 1);
-                job(1, 1, 2, 2);
-            }
-            const int rw = ffhip_launch_walk16(W, stream);
-            if (rw < 0 || !hrgb)
-                return rw;
-            FFHipY16RgbArgs Y;
-            memset(&Y, 0, sizeof(Y));
-            Y.y = static_cast<const uint8_t *>(xdst[0]); Y.u = static_cast<const uint8_t *>(xdst[1]); Y.v = static_cast<const uint8_t *>(xdst[2]);
-            Y.dst = static_cast<uint8_t *>(dst[0]);
-            Y.ystride = (ptrdiff_t)ypitch; Y.cstride = (ptrdiff_t)cpitch; Y.dstride = dstStride[0];
-            Y.yfp = yfp; Y.cfp = cfp; Y.dfp = dstFramePitch[0];
-            Y.w = t.dstW; Y.h = t.dstH; Y.nframes = nframes; Y.lay = rgb_layout(t.dstFormat); Y.k = c->k;
-            const int ry = ffhip_launch_y16_rgb(Y, stream);
-            if (ry >= 0)
-                HIP_TRY(hipEventRecord(c->rgb2_done, stream));
-            return ry;
+            ffhip_w16_plan_job(&j, strip);
+        };
+        if (!c->rgb_in_luma_done)
+            job(0, 1, 0);
+        if (ws.il || wd.il) {
+            job(1, 2, 1);
+        } else {
+            job(1, 1, 1);
+            job(1, 1, 2);
         }
+        const int rw = ffhip_launch_walk16(W, stream);
+        if (rw < 0 || !hrgb)
+            return rw;
+        FFHipY16RgbArgs Y;
+        memset(&Y, 0, sizeof(Y));
+        Y.y = wd.p[0]; Y.u = wd.p[1]; Y.v = wd.p[2];
+        Y.dst = d.p[0];
+        Y.ystride = (ptrdiff_t)ypitch; Y.cstride = (ptrdiff_t)cpitch; Y.dstride = d.stride[0];
+        Y.yfp = yfp; Y.cfp = cfp; Y.dfp = d.fp[0];
+        Y.w = t.dstW; Y.h = t.dstH; Y.nframes = nframes; Y.lay = rgb_layout(t.dstFormat); Y.k = c->k;
+        return ffhip_launch_y16_rgb(Y, stream);
     }
     if (c->rgb_in_luma_done) {
         ffhip_set_error("ffhip_sws: internal: the converter pass wrote the luma plane but the walker does not run");
@@ -1852,19 +1771,13 @@ extern "C" int ffhip_sws_scale_batch_dev(FFHipSwsContext *c, int nframes, const 
         std::lock_guard<std::mutex> lk(c->mu);
         if (c->rgb_in.direct_c && dst && dstStride && dstFramePitch && dst[0] && dst[1] && dst[2] && !FFHIP_KNOB("FFHIP_SWS_RGB_DIRECT_OFF")) {
             /* every bank the identity: the converter pass writes the three 8-bit planes of the target (FFHipRgbInArgs.c8) */
-            FFHipRgbInArgs a;
-            memset(&a, 0, sizeof(a));
-            a.src = static_cast<const uint8_t *>(src[0]); a.src_stride = srcStride[0]; a.src_fp = srcFramePitch[0];
+            FFHipRgbInArgs a = rgb_in_args(c, src[0], srcStride[0], srcFramePitch[0], c->t.srcH);
             a.y8 = static_cast<uint8_t *>(dst[0]); a.y8_stride = dstStride[0]; a.y8_fp = dstFramePitch[0];
             a.c8 = 1;
             for (int i = 1; i < 3; i++) {
                 a.dst[i] = static_cast<uint8_t *>(dst[i]); a.dst_stride[i] = dstStride[i]; a.dst_fp[i] = dstFramePitch[i];
             }
             a.dst[0] = a.y8; a.dst_stride[0] = dstStride[0]; a.dst_fp[0] = dstFramePitch[0];
-            a.w = c->t.srcW; a.h = c->t.srcH;
-            a.ro = c->rgb_in.ofs[0]; a.go = c->rgb_in.ofs[1]; a.bo = c->rgb_in.ofs[2];
-            const int32_t *T = c->rgb_in.table;
-            a.ry = T[0]; a.gy = T[1]; a.by = T[2]; a.ru = T[3]; a.gu = T[4]; a.bu = T[5]; a.rv = T[6]; a.gv = T[7]; a.bv = T[8];
             return ffhip_launch_sws_rgb_in(a, c->rgb_in.bpp, c->rgb_in.half, nframes, (hipStream_t)stream_);
         }
         {
@@ -1879,16 +1792,12 @@ extern "C" int ffhip_sws_scale_batch_dev(FFHipSwsContext *c, int nframes, const 
             if (ok) {
                 FFHipRgb420Args A;
                 memset(&A, 0, sizeof(A));
-                A.in.src = static_cast<const uint8_t *>(src[0]); A.in.src_stride = srcStride[0]; A.in.src_fp = srcFramePitch[0];
+                A.in = rgb_in_args(c, src[0], srcStride[0], srcFramePitch[0], c->t.srcH);
                 A.in.y8 = static_cast<uint8_t *>(dst[0]); A.in.y8_stride = dstStride[0]; A.in.y8_fp = dstFramePitch[0];
-                A.in.w = c->t.srcW; A.in.h = c->t.srcH;
-                A.in.ro = c->rgb_in.ofs[0]; A.in.go = c->rgb_in.ofs[1]; A.in.bo = c->rgb_in.ofs[2];
-                const int32_t *T = c->rgb_in.table;
-                A.in.ry = T[0]; A.in.gy = T[1]; A.in.by = T[2]; A.in.ru = T[3]; A.in.gu = T[4]; A.in.bu = T[5]; A.in.rv = T[6]; A.in.gv = T[7]; A.in.bv = T[8];
                 A.cdst[0] = static_cast<uint8_t *>(dst[1]); A.cdst[1] = nv ? nullptr : static_cast<uint8_t *>(dst[2]);
                 A.cstride = dstStride[1]; A.cfp = dstFramePitch[1];
                 A.chrH = c->t.srcH / 2;
-                A.vfv = c->rgb_in.vfv;
+                A.vfv = static_cast<const uint32_t *>(c->rgb_in.vfv.p);
                 A.nframes = nframes;
                 return ffhip_launch_sws_rgb420(A, c->rgb_in.bpp, nv, (hipStream_t)stream_);
             }
@@ -1897,20 +1806,12 @@ extern "C" int ffhip_sws_scale_batch_dev(FFHipSwsContext *c, int nframes, const 
         const int pitch[3] = { ((c->t.srcW * 2) + 255) & ~255, ((cw * 2) + 255) & ~255, ((cw * 2) + 255) & ~255 };
         const size_t fp[3] = { (size_t)pitch[0] * c->t.srcH, (size_t)pitch[1] * c->t.srcH, (size_t)pitch[2] * c->t.srcH };
         const size_t need = (fp[0] + fp[1] + fp[2]) * (size_t)nframes + 256;
-        if (need > c->rgb_in.planes_sz) {
-            if (c->rgb_in.planes) {
-                (void)hipDeviceSynchronize(); /* an earlier batch may still read them */
-                (void)hipFree(c->rgb_in.planes);
-            }
-            c->rgb_in.planes = nullptr;
-            c->rgb_in.planes_sz = 0;
-            if (hipMalloc(&c->rgb_in.planes, need) != hipSuccess) {
-                ffhip_set_error("ffhip_sws_scale_batch_dev: hipMalloc(%zu) for an RGB source's converter lines failed", need);
-                return FFHIP_ENOMEM;
-            }
-            c->rgb_in.planes_sz = need;
+        ScratchLease lease;
+        if (acquire(c->rgb_in_planes, lease, need, (hipStream_t)stream_) != hipSuccess) {
+            ffhip_set_error("ffhip_sws_scale_batch_dev: hipMalloc(%zu) for an RGB source's converter lines failed", need);
+            return FFHIP_ENOMEM;
         }
-        uint8_t *b = static_cast<uint8_t *>(c->rgb_in.planes);
+        uint8_t *b = static_cast<uint8_t *>(c->rgb_in_planes.buf.p);
         uint8_t *const p[3] = { b, b + fp[0] * nframes, b + (fp[0] + fp[1]) * nframes };
         /* (the walker — the kernel that can leave the luma out — wants 4-byte aligned planes and pitches, top-down: scale16()) */
         bool yd = c->rgb_in.y_direct && dst && dstStride && dstFramePitch;
@@ -2074,34 +1975,28 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
         return FFHIP_EINVAL;
     FFHipDeviceGuard dg(c->device);
     const FFHipSwsTables &t = c->t;
-    const uint8_t *s0 = (const uint8_t *)src[0], *s1 = (const uint8_t *)src[1], *s2 = (const uint8_t *)src[2];
     if (c->hbd)
         return scale16(c, nframes, src, srcStride, srcFramePitch, dst, dstStride, dstFramePitch, stream);
 
     if (c->unscaled_yuv2rgb)
         return unscaled_launch(c, nframes, t.srcH, src, srcStride, srcFramePitch, dst, dstStride, dstFramePitch, stream);
 
-    /* chroma source description */
-    const uint8_t *cu, *cv;
-    ptrdiff_t cus, cvs;
-    size_t cuf, cvf;
-    int cstep;
-    if (fmt_nv(t.srcFormat)) {
-        const int sw = t.srcFormat == FFHIP_PIX_FMT_NV21;
-        cu = s1 + sw; cv = s1 + !sw;
-        cus = cvs = srcStride[1]; cuf = cvf = srcFramePitch[1]; cstep = 2;
-    } else {
-        cu = s1; cv = s2; cus = srcStride[1]; cvs = srcStride[2]; cuf = srcFramePitch[1]; cvf = srcFramePitch[2];
-        cstep = 1;
-    }
+    /* the call's planes (a packed RGB target: its one plane) and what the fast kernels ask of them */
+    const SidePlanes s = side_planes(src, srcStride, srcFramePitch, fmt_nv(t.srcFormat) ? 2 : 3, t.srcFormat == FFHIP_PIX_FMT_NV21);
+    const SidePlanes d = side_planes(dst, dstStride, dstFramePitch, fmt_rgb(t.dstFormat) ? 1 : fmt_nv(t.dstFormat) ? 2 : 3,
+                                     t.dstFormat == FFHIP_PIX_FMT_NV21);
+    const uintptr_t al = s.al() | d.al();
+    const bool neg = s.neg || d.neg, topdown = s.pos && d.pos;
+    /* fast paths: FFHIP_SWS_FAST=0 forces the LDS-tiled kernels; FFHIP_CW_LUMA_GROUPS / FFHIP_CW_PLAIN select measured variants */
+    const bool fast_off = KNOB_IS("FFHIP_SWS_FAST", '0');
 
     if (fmt_rgb(t.dstFormat)) {
         FFHipScaleRgbArgs a = c->rgb;
-        a.src[0] = s0; a.src[1] = cu; a.src[2] = cv;
-        a.src_stride[0] = srcStride[0]; a.src_stride[1] = cus; a.src_stride[2] = cvs;
-        a.src_fp[0] = srcFramePitch[0]; a.src_fp[1] = cuf; a.src_fp[2] = cvf;
-        a.chr_step = cstep;
-        a.dst = (uint8_t *)dst[0]; a.dst_stride = dstStride[0]; a.dst_fp = dstFramePitch[0];
+        for (int i = 0; i < 3; i++) {
+            a.src[i] = s.p[i]; a.src_stride[i] = s.stride[i]; a.src_fp[i] = s.fp[i];
+        }
+        a.chr_step = s.il ? 2 : 1;
+        a.dst = d.p[0]; a.dst_stride = d.stride[0]; a.dst_fp = d.fp[0];
         a.nframes = nframes;
         if (a.has_alpha) {
             if (!src[3]) {
@@ -2110,36 +2005,27 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             }
             a.alpha = (const uint8_t *)src[3]; a.alpha_stride = srcStride[3]; a.alpha_fp = srcFramePitch[3];
         }
-        const char *ev = FFHIP_KNOB("FFHIP_SWS_FAST");
-        uintptr_t al = (uintptr_t)s0 | (size_t)srcStride[0] | srcFramePitch[0] | (uintptr_t)a.dst | (size_t)a.dst_stride | a.dst_fp |
-                       (size_t)cus | (size_t)cvs | cuf | cvf | (uintptr_t)(cstep == 2 ? s1 : cu) | (uintptr_t)(cstep == 2 ? s1 : cv);
         /* (the round-5 kernels walk their rows with running pointers and were written for top-down pictures: a negative stride keeps the
          * older kernels) */
-        const bool topdown = srcStride[0] > 0 && cus > 0 && cvs > 0 && a.dst_stride > 0;
-        if (c->f444_ok && topdown && !(ev && ev[0] == '0') && !(al & 3)) {
+        if (c->f444_ok && topdown && !fast_off && !(al & 3)) {
             FFHipFull444Args F;
             memset(&F, 0, sizeof(F));
-            F.src[0] = s0; F.src[1] = cu; F.src[2] = cv;
-            F.sstride[0] = srcStride[0]; F.sstride[1] = cus; F.sstride[2] = cvs;
-            F.sfp[0] = srcFramePitch[0]; F.sfp[1] = cuf; F.sfp[2] = cvf;
+            put_src(F, s);
             F.dst = a.dst; F.dstride = a.dst_stride; F.dfp = a.dst_fp;
             F.w = a.dstW; F.h = a.dstH; F.nframes = nframes; F.lay = a.bgr;
             for (int i = 0; i < 6; i++)
                 F.fk[i] = a.fk[i];
             return ffhip_launch_full444(F, stream);
         }
-        const char *eq = FFHIP_KNOB("FFHIP_SWS_EQRGB"); /* measure build: 0 keeps the column walker */
-        if (c->eqr_ok && topdown && !(ev && ev[0] == '0') && !(eq && eq[0] == '0') && !(al & 3)) {
+        if (c->eqr_ok && topdown && !fast_off && !KNOB_IS("FFHIP_SWS_EQRGB", '0') /* measure build: 0 keeps the column walker */ && !(al & 3)) {
             /* the source's size: chroma lines interpolated by the exact-2x vertical bank, nothing else scaled (sws_eqrgb.hip) */
             FFHipEqRgbArgs E;
             memset(&E, 0, sizeof(E));
-            E.src[0] = s0; E.src[1] = cstep == 2 ? s1 : cu; E.src[2] = cstep == 2 ? s1 : cv;
-            E.sil = cstep == 2; E.swap = t.srcFormat == FFHIP_PIX_FMT_NV21;
-            E.sstride[0] = srcStride[0]; E.sstride[1] = cus; E.sstride[2] = cvs;
-            E.sfp[0] = srcFramePitch[0]; E.sfp[1] = cuf; E.sfp[2] = cvf;
+            put_src(E, s);
+            E.sil = s.il; E.swap = s.swap;
             E.dst = a.dst; E.dstride = a.dst_stride; E.dfp = a.dst_fp;
             E.chrH = a.chrSrcH; E.ngroups = a.dstW / 8; E.nframes = nframes;
-            E.vt = static_cast<const uint32_t *>(c->eqr_dev);
+            E.vt = static_cast<const uint32_t *>(c->eqr_dev.p);
             E.vround = c->cw_vround; E.lay = a.bgr; E.k = c->k;
             const char *es = FFHIP_KNOB("FFHIP_EQRGB_STEPS"), *ef = FFHIP_KNOB("FFHIP_EQRGB_FPP");
             /* (frames that share a wave address their planes by 32-bit lane offsets from the pack's first frame: up to three frame pitches) */
@@ -2148,14 +2034,12 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             return ffhip_launch_eqrgb(E, stream);
         }
         const char *eu2 = FFHIP_KNOB("FFHIP_SWS_UP2RGB"); /* measure build: 0 keeps the column walker, v<n> a measured variant */
-        if (c->u2r_ok && topdown && !(ev && ev[0] == '0') && !(eu2 && eu2[0] == '0') && !(al & 3)) {
+        if (c->u2r_ok && topdown && !fast_off && !(eu2 && eu2[0] == '0') && !(al & 3)) {
             /* exact 2x of 4:2:0: static schedule, regular windows, the RGB writer fused (sws_up2rgb.hip) */
             FFHipUp2RgbArgs U;
             memset(&U, 0, sizeof(U));
-            U.src[0] = s0; U.src[1] = cstep == 2 ? s1 : cu; U.src[2] = cstep == 2 ? s1 : cv;
-            U.sil = cstep == 2; U.swap = t.srcFormat == FFHIP_PIX_FMT_NV21;
-            U.sstride[0] = srcStride[0]; U.sstride[1] = cus; U.sstride[2] = cvs;
-            U.sfp[0] = srcFramePitch[0]; U.sfp[1] = cuf; U.sfp[2] = cvf;
+            put_src(U, s);
+            U.sil = s.il; U.swap = s.swap;
             U.dst = a.dst; U.dstride = a.dst_stride; U.dfp = a.dst_fp;
             U.srcW = a.srcW; U.srcH = a.srcH; U.ngroups = a.srcW / 4; U.nframes = nframes;
             U.hco = c->u2r_hco; U.vt = c->u2r_vt;
@@ -2169,34 +2053,32 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             ffhip_up2rgb_plan(&U, es && atoi(es) > 0 ? atoi(es) : U.lay < 2 ? 24 : 36, ef ? atoi(ef) : U.lay < 2 && !far ? 0 : 1);
             return ffhip_launch_up2rgb(U, eu2 && eu2[0] == 'v' ? atoi(eu2 + 1) : 0, stream);
         }
-        if (c->cw_rgb && !(ev && ev[0] == '0') && !(al & 3)) {
+        if (c->cw_rgb && !fast_off && !(al & 3)) {
             FFHipCwRgbArgs R;
             memset(&R, 0, sizeof(R));
-            R.src[0] = s0; R.src[1] = cstep == 2 ? s1 : cu; R.src[2] = cstep == 2 ? s1 : cv;
-            R.sstride[0] = srcStride[0]; R.sstride[1] = cus; R.sstride[2] = cvs;
-            R.sfp[0] = srcFramePitch[0]; R.sfp[1] = cuf; R.sfp[2] = cvf;
+            put_src(R, s);
             R.dst = a.dst; R.dstride = a.dst_stride; R.dfp = a.dst_fp;
-            R.sil = cstep == 2; R.src_swap = t.srcFormat == FFHIP_PIX_FMT_NV21; R.bgr = a.bgr;
+            R.sil = s.il; R.src_swap = s.swap; R.bgr = a.bgr;
             R.srcW = a.srcW; R.srcH = a.srcH; R.chrSrcW = a.chrSrcW; R.chrSrcH = a.chrSrcH; R.dstW = a.dstW; R.dstH = a.dstH;
             R.hlf = c->dn[0].filter; R.hlp = c->dn[0].pos; R.hcf = c->dn[1].filter; R.hcp = c->dn[1].pos;
             R.vlf = c->dn[2].filter; R.vlp = c->dn[2].pos; R.vcf = c->dn[3].filter; R.vcp = c->dn[3].pos;
             R.nframes = nframes; R.k = c->k; R.vround = c->cw_vround;
-            { const char *en = FFHIP_KNOB("FFHIP_CWRGB_NTS"); R.nts = !(en && en[0] == '0'); }
+            R.nts = !KNOB_IS("FFHIP_CWRGB_NTS", '0');
             return ffhip_launch_colwalk_rgb(R, stream);
         }
         const char *e2 = FFHIP_KNOB("FFHIP_SWS_RGB2"); /* measure build: 0 keeps the LDS-tiled kernel */
-        if (c->lw_ok && topdown && !(ev && ev[0] == '0') && !(e2 && e2[0] == '0') && !(al & 3)) {
+        if (c->lw_ok && topdown && !fast_off && !(e2 && e2[0] == '0') && !(al & 3)) {
             const char *ed = FFHIP_KNOB("FFHIP_SWS_DOWN2");
             const int chrW = a.dstW / 2;
             /* exact 2:1 from a 4:2:0 source: fused, no intermediate — before anything of the two-stage form (its lock, its buffer) is touched */
-            if (c->dn2_luma == 2 && (cstep == 2 || (cus == cvs && cuf == cvf)) && srcStride[0] > 0 && cus > 0 &&
+            if (c->dn2_luma == 2 && (s.il || (s.stride[1] == s.stride[2] && s.fp[1] == s.fp[2])) && s.stride[0] > 0 && s.stride[1] > 0 &&
                 !(ed && (ed[0] == '0' || ed[0] == 'l' || ed[0] == 't')) && !(a.dstW & 3) && a.dstW >= 12) {
                 /* ... and the whole conversion in ONE kernel, no intermediate (k_sws_down2_rgb; planar chroma: planes laid out alike;
                  * FFHIP_SWS_DOWN2=t: the two-stage form below) */
                 FFHipDn2RgbArgs F;
                 memset(&F, 0, sizeof(F));
-                F.ysrc = s0; F.ysstride = srcStride[0]; F.ysfp = srcFramePitch[0];
-                F.csrc = cstep == 2 ? s1 : cu; F.csrc2 = cstep == 2 ? nullptr : cv; F.csstride = cus; F.csfp = cuf; F.swap = cstep == 2 && cv < cu;
+                F.ysrc = s.p[0]; F.ysstride = s.stride[0]; F.ysfp = s.fp[0];
+                F.csrc = s.il ? s.pair : s.p[1]; F.csrc2 = s.il ? nullptr : s.p[2]; F.csstride = s.stride[1]; F.csfp = s.fp[1]; F.swap = s.swap;
                 F.dst = a.dst; F.dstride = a.dst_stride; F.dfp = a.dst_fp;
                 F.srcH = a.srcH; F.chrH = a.chrSrcH; F.dstH = a.dstH; F.ngroups = a.dstW / 4;
                 F.hfv_l = c->dn2_h[0]; F.hfv_c = c->dn2_h[1]; F.vfv = c->dn2_v[0];
@@ -2205,24 +2087,14 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             }
             /* two stages (see the context's creation): planes of the target's geometry, pitches and frames 256-byte aligned */
             const size_t ypitch = ((size_t)2 * a.dstW + 255) & ~(size_t)255, cpitch = ((size_t)(a.dstW / 2) + 255) & ~(size_t)255;
-            const size_t yfp = ypitch * (size_t)a.dstH, cfp = cpitch * (size_t)a.dstH, need = (yfp + 2 * cfp) * (size_t)nframes;
+            const size_t yfp = ypitch * (size_t)a.dstH, cfp = cpitch * (size_t)a.dstH;
             /* the intermediate is the context's: calls are serialised here, and a call on another stream waits for the last reader */
-            std::lock_guard<std::mutex> lk(c->rgb2_mu);
-            if (!c->rgb2_done)
-                HIP_TRY(hipEventCreateWithFlags(&c->rgb2_done, hipEventDisableTiming));
-            else
-                HIP_TRY(hipStreamWaitEvent(stream, c->rgb2_done, 0));
-            if (need > c->rgb2_tmp_sz) {
-                if (c->rgb2_tmp)
-                    HIP_TRY(hipFree(c->rgb2_tmp)); /* (waits for the launches that still use it) */
-                c->rgb2_tmp = nullptr;
-                c->rgb2_tmp_sz = 0;
-                HIP_TRY(hipMalloc(&c->rgb2_tmp, need));
-                c->rgb2_tmp_sz = need;
-            }
-            uint8_t *ty = static_cast<uint8_t *>(c->rgb2_tmp), *tu = ty + yfp * (size_t)nframes, *tv = tu + cfp * (size_t)nframes;
-            if (c->dn2_luma == 2 && srcStride[0] > 0 && !(ed && (ed[0] == '0' || ed[0] == 'l')) && chrW % (cstep == 2 ? 2 : 4) == 0 &&
-                chrW / (cstep == 2 ? 2 : 4) >= 3 && cus > 0 && cvs > 0) {
+            ScratchLease lease;
+            HIP_TRY(acquire(c->rgb2_tmp, lease, (yfp + 2 * cfp) * (size_t)nframes, stream));
+            uint8_t *ty = static_cast<uint8_t *>(c->rgb2_tmp.buf.p), *tu = ty + yfp * (size_t)nframes, *tv = tu + cfp * (size_t)nframes;
+            const int cstep = s.il ? 2 : 1, cg = s.il ? 2 : 4; /* (chroma columns per group of the down2 job) */
+            if (c->dn2_luma == 2 && s.stride[0] > 0 && !(ed && (ed[0] == '0' || ed[0] == 'l')) && chrW % cg == 0 && chrW / cg >= 3 &&
+                s.stride[1] > 0 && s.stride[2] > 0) {
                 /* exact 2:1 with a chroma line per output line: luma and chroma in ONE launch of the static-schedule kernel (the chroma
                  * jobs without a vertical filter), an interleaved pair leaves as a plane of (u, v) bytes (FFHIP_SWS_DOWN2=l: luma only,
                  * the chroma on the wide walker as before round 5's last step) */
@@ -2232,35 +2104,32 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
                 D.xcd = 1;
                 {
                     FFHipDn2Job &j = D.job[D.njobs++];
-                    j.src = s0; j.dst = ty; j.sstride = srcStride[0]; j.dstride = (ptrdiff_t)ypitch; j.sfp = srcFramePitch[0]; j.dfp = yfp;
+                    j.src = s.p[0]; j.dst = ty; j.sstride = s.stride[0]; j.dstride = (ptrdiff_t)ypitch; j.sfp = s.fp[0]; j.dfp = yfp;
                     j.srcH = a.srcH; j.dstH = a.dstH; j.ngroups = a.dstW / 4;
                     j.hfv = c->dn2_h[0]; j.vfv = c->dn2_v[0];
                     j.y16 = 1;
                     ffhip_down2_plan_job(&j, 32);
                 }
-                for (int k = 0; k < (cstep == 2 ? 1 : 2); k++) {
+                for (int k = 0; k < 3 - cstep; k++) {
                     FFHipDn2Job &j = D.job[D.njobs++];
-                    j.pair = cstep == 2; j.swap = cstep == 2 && cv < cu; j.v1 = 1;
-                    j.src = cstep == 2 ? s1 : k ? cv : cu; j.sstride = k ? cvs : cus; j.sfp = k ? cvf : cuf;
-                    j.dst = k ? tv : tu; j.dstride = (ptrdiff_t)(cstep == 2 ? 2 * cpitch : cpitch); j.dfp = cstep == 2 ? 2 * cfp : cfp;
-                    j.srcH = a.chrSrcH; j.dstH = a.dstH; j.ngroups = chrW / (cstep == 2 ? 2 : 4);
+                    j.pair = s.il; j.swap = s.swap; j.v1 = 1;
+                    j.src = s.il ? s.pair : s.p[1 + k]; j.sstride = s.stride[1 + k]; j.sfp = s.fp[1 + k];
+                    j.dst = k ? tv : tu; j.dstride = (ptrdiff_t)(cstep * cpitch); j.dfp = cstep * cfp;
+                    j.srcH = a.chrSrcH; j.dstH = a.dstH; j.ngroups = chrW / cg;
                     j.hfv = c->dn2_h[1]; j.vfv = c->dn2_v[0];
                     ffhip_down2_plan_job(&j, 32);
                 }
-                int r1 = ffhip_launch_down2(D, stream);
+                const int r1 = ffhip_launch_down2(D, stream);
                 if (r1 < 0)
                     return r1;
                 FFHipY16RgbArgs Y;
                 memset(&Y, 0, sizeof(Y));
                 Y.y = ty; Y.u = tu; Y.v = tv; Y.dst = a.dst;
-                Y.uvi = cstep == 2;
-                Y.ystride = (ptrdiff_t)ypitch; Y.cstride = (ptrdiff_t)(cstep == 2 ? 2 * cpitch : cpitch); Y.dstride = a.dst_stride;
-                Y.yfp = yfp; Y.cfp = cstep == 2 ? 2 * cfp : cfp; Y.dfp = a.dst_fp;
+                Y.uvi = s.il;
+                Y.ystride = (ptrdiff_t)ypitch; Y.cstride = (ptrdiff_t)(cstep * cpitch); Y.dstride = a.dst_stride;
+                Y.yfp = yfp; Y.cfp = cstep * cfp; Y.dfp = a.dst_fp;
                 Y.w = a.dstW; Y.h = a.dstH; Y.nframes = nframes; Y.lay = a.bgr; Y.k = c->k;
-                r1 = ffhip_launch_y16_rgb(Y, stream);
-                if (r1 >= 0)
-                    HIP_TRY(hipEventRecord(c->rgb2_done, stream));
-                return r1;
+                return ffhip_launch_y16_rgb(Y, stream);
             }
             FFHipLwArgs W;
             memset(&W, 0, sizeof(W));
@@ -2270,24 +2139,24 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
                 j.hf = c->dw[which].filter; j.hp = c->dw[which].pos; j.vf = c->dw[2 + which].filter; j.vp = c->dw[2 + which].pos;
                 ffhip_lw_plan_job(&j);
             };
-            if (cstep == 1) {
+            if (!s.il) {
                 for (int k = 0; k < 2; k++) {
                     FFHipLwJob &j = W.job[W.njobs++];
-                    j.src[0] = k ? cv : cu; j.sstride[0] = k ? cvs : cus; j.sfp[0] = k ? cvf : cuf;
+                    j.src[0] = s.p[1 + k]; j.sstride[0] = s.stride[1 + k]; j.sfp[0] = s.fp[1 + k];
                     j.dst[0] = k ? tv : tu; j.dstride[0] = (ptrdiff_t)cpitch; j.dfp[0] = cfp;
                     wbank(j, a.chrSrcW, a.chrSrcH, a.dstW / 2, 1);
                 }
             } else {
                 FFHipLwJob &j = W.job[W.njobs++];
                 j.pair = 1; j.sil = 1; j.dil = 0;
-                j.src_swap = cv < cu;
-                j.src[0] = j.src[1] = s1; j.sstride[0] = j.sstride[1] = cus; j.sfp[0] = j.sfp[1] = cuf;
+                j.src_swap = s.swap;
+                j.src[0] = j.src[1] = s.pair; j.sstride[0] = j.sstride[1] = s.stride[1]; j.sfp[0] = j.sfp[1] = s.fp[1];
                 j.dst[0] = tu; j.dst[1] = tv; j.dstride[0] = j.dstride[1] = (ptrdiff_t)cpitch; j.dfp[0] = j.dfp[1] = cfp;
                 wbank(j, a.chrSrcW, a.chrSrcH, a.dstW / 2, 1);
             }
             int r2 = 0;
             bool joined = false;
-            if (c->dn2_luma && srcStride[0] > 0 && !(ed && ed[0] == '0')) {
+            if (c->dn2_luma && s.stride[0] > 0 && !(ed && ed[0] == '0')) {
                 /* the two first-stage kernels do not depend on each other and neither fills the chip for long (the chroma walker waits on
                  * LDS round trips, VALU 29 % busy): side by side on two streams (FFHIP_SWS_RGB2=s: one after the other) */
                 hipStream_t ls = stream;
@@ -2307,7 +2176,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
                 D.nframes = nframes;
                 D.xcd = 1;
                 FFHipDn2Job &j = D.job[D.njobs++];
-                j.src = s0; j.dst = ty; j.sstride = srcStride[0]; j.dstride = (ptrdiff_t)ypitch; j.sfp = srcFramePitch[0]; j.dfp = yfp;
+                j.src = s.p[0]; j.dst = ty; j.sstride = s.stride[0]; j.dstride = (ptrdiff_t)ypitch; j.sfp = s.fp[0]; j.dfp = yfp;
                 j.srcH = a.srcH; j.dstH = a.dstH; j.ngroups = a.dstW / 4;
                 j.hfv = c->dn2_h[0]; j.vfv = c->dn2_v[0];
                 j.y16 = 1;
@@ -2317,7 +2186,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
                     HIP_TRY(hipEventRecord(c->rgb2_join, ls));
             } else {
                 FFHipLwJob &jl = W.job[W.njobs++];
-                jl.src[0] = s0; jl.sstride[0] = srcStride[0]; jl.sfp[0] = srcFramePitch[0];
+                jl.src[0] = s.p[0]; jl.sstride[0] = s.stride[0]; jl.sfp[0] = s.fp[0];
                 jl.dst[0] = ty; jl.dstride[0] = (ptrdiff_t)ypitch; jl.dfp[0] = yfp;
                 jl.y16 = 1;
                 wbank(jl, a.srcW, a.srcH, a.dstW, 0);
@@ -2334,117 +2203,92 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             Y.ystride = (ptrdiff_t)ypitch; Y.cstride = (ptrdiff_t)cpitch; Y.dstride = a.dst_stride;
             Y.yfp = yfp; Y.cfp = cfp; Y.dfp = a.dst_fp;
             Y.w = a.dstW; Y.h = a.dstH; Y.nframes = nframes; Y.lay = a.bgr; Y.k = c->k;
-            r2 = ffhip_launch_y16_rgb(Y, stream);
-            if (r2 >= 0)
-                HIP_TRY(hipEventRecord(c->rgb2_done, stream));
-            return r2;
+            return ffhip_launch_y16_rgb(Y, stream);
         }
         return ffhip_launch_scale_rgb(a, stream);
     }
 
     FFHipScalePlaneArgs l = c->lum, ch = c->chr;
-    l.src[0] = l.src[1] = s0; l.src_stride[0] = l.src_stride[1] = srcStride[0];
-    l.src_fp[0] = l.src_fp[1] = srcFramePitch[0]; l.src_step = 1;
-    l.dst[0] = l.dst[1] = (uint8_t *)dst[0]; l.dst_stride[0] = l.dst_stride[1] = dstStride[0];
-    l.dst_fp[0] = l.dst_fp[1] = dstFramePitch[0]; l.dst_step = 1;
+    l.src[0] = l.src[1] = s.p[0]; l.src_stride[0] = l.src_stride[1] = s.stride[0];
+    l.src_fp[0] = l.src_fp[1] = s.fp[0]; l.src_step = 1;
+    l.dst[0] = l.dst[1] = d.p[0]; l.dst_stride[0] = l.dst_stride[1] = d.stride[0];
+    l.dst_fp[0] = l.dst_fp[1] = d.fp[0]; l.dst_step = 1;
     l.nframes = nframes;
-    ch.src[0] = cu; ch.src[1] = cv; ch.src_stride[0] = cus; ch.src_stride[1] = cvs;
-    ch.src_fp[0] = cuf; ch.src_fp[1] = cvf; ch.src_step = cstep;
-    if (fmt_nv(t.dstFormat)) {
-        const int sw = t.dstFormat == FFHIP_PIX_FMT_NV21;
-        ch.dst[0] = (uint8_t *)dst[1] + sw; ch.dst[1] = (uint8_t *)dst[1] + !sw;
-        ch.dst_stride[0] = ch.dst_stride[1] = dstStride[1];
-        ch.dst_fp[0] = ch.dst_fp[1] = dstFramePitch[1];
-        ch.dst_step = 2;
-    } else {
-        ch.dst[0] = (uint8_t *)dst[1]; ch.dst[1] = (uint8_t *)dst[2];
-        ch.dst_stride[0] = dstStride[1]; ch.dst_stride[1] = dstStride[2];
-        ch.dst_fp[0] = dstFramePitch[1]; ch.dst_fp[1] = dstFramePitch[2];
-        ch.dst_step = 1;
+    for (int k = 0; k < 2; k++) {
+        ch.src[k] = s.p[1 + k]; ch.src_stride[k] = s.stride[1 + k]; ch.src_fp[k] = s.fp[1 + k];
+        ch.dst[k] = d.p[1 + k]; ch.dst_stride[k] = d.stride[1 + k]; ch.dst_fp[k] = d.fp[1 + k];
     }
+    ch.src_step = s.il ? 2 : 1;
+    ch.dst_step = d.il ? 2 : 1;
     ch.nframes = nframes;
 
-    /* fast path: 4x4-tap banks, dword-aligned planes.  FFHIP_SWS_FAST=0 forces the LDS-tiled kernel;
-     * FFHIP_CW_LUMA_GROUPS / FFHIP_CW_PLAIN select measured variants. */
-    const char *ev = FFHIP_KNOB("FFHIP_SWS_FAST");
-    if (c->c420_ok && !(ev && ev[0] == '0') && srcStride[0] > 0 && cus > 0 && cvs > 0 && dstStride[0] > 0 && dstStride[1] > 0 &&
-        (fmt_nv(t.dstFormat) || dstStride[2] > 0)) {
+    if (c->c420_ok && !fast_off && topdown) {
         FFHipCopy420Args K;
         memset(&K, 0, sizeof(K));
         K.nframes = nframes;
         const int cw = c->d[1].n, chh = c->d[3].n;
         {
             FFHipCopy420Job &j = K.job[K.njobs++];
-            j.src[0] = s0; j.sstride[0] = srcStride[0]; j.sfp[0] = srcFramePitch[0];
-            j.dst = (uint8_t *)dst[0]; j.dstride = dstStride[0]; j.dfp = dstFramePitch[0];
+            j.src[0] = s.p[0]; j.sstride[0] = s.stride[0]; j.sfp[0] = s.fp[0];
+            j.dst = d.p[0]; j.dstride = d.stride[0]; j.dfp = d.fp[0];
             j.kind = 0; j.wbytes = t.dstW; j.rows = t.dstH;
         }
-        if (fmt_nv(t.dstFormat)) {
+        if (d.il) {
             FFHipCopy420Job &j = K.job[K.njobs++];
-            j.dst = (uint8_t *)dst[1]; j.dstride = dstStride[1]; j.dfp = dstFramePitch[1];
+            j.dst = d.pair; j.dstride = d.stride[1]; j.dfp = d.fp[1];
             j.wbytes = 2 * cw; j.rows = chh;
-            const bool dsw = t.dstFormat == FFHIP_PIX_FMT_NV21;
-            if (cstep == 2) { /* pairs in, pairs out: as they are, or each pair turned round */
-                j.src[0] = s1; j.sstride[0] = cus; j.sfp[0] = cuf;
-                j.kind = dsw == (t.srcFormat == FFHIP_PIX_FMT_NV21) ? 0 : 3;
+            if (s.il) { /* pairs in, pairs out: as they are, or each pair turned round */
+                j.src[0] = s.pair; j.sstride[0] = s.stride[1]; j.sfp[0] = s.fp[1];
+                j.kind = d.swap == s.swap ? 0 : 3;
             } else {
                 j.kind = 2;
-                j.src[0] = dsw ? cv : cu; j.sstride[0] = dsw ? cvs : cus; j.sfp[0] = dsw ? cvf : cuf;
-                j.src[1] = dsw ? cu : cv; j.sstride[1] = dsw ? cus : cvs; j.sfp[1] = dsw ? cuf : cvf;
+                for (int k = 0; k < 2; k++) { /* the planes in the target's order */
+                    const int sp = d.swap ? 2 - k : 1 + k;
+                    j.src[k] = s.p[sp]; j.sstride[k] = s.stride[sp]; j.sfp[k] = s.fp[sp];
+                }
             }
         } else {
             for (int k = 0; k < 2; k++) {
                 FFHipCopy420Job &j = K.job[K.njobs++];
-                j.dst = (uint8_t *)dst[1 + k]; j.dstride = dstStride[1 + k]; j.dfp = dstFramePitch[1 + k];
+                j.dst = d.p[1 + k]; j.dstride = d.stride[1 + k]; j.dfp = d.fp[1 + k];
                 j.wbytes = cw; j.rows = chh;
-                if (cstep == 2) {
-                    j.src[0] = s1; j.sstride[0] = cus; j.sfp[0] = cuf;
-                    j.kind = 1; j.k = (t.srcFormat == FFHIP_PIX_FMT_NV21) ? !k : k;
+                if (s.il) {
+                    j.src[0] = s.pair; j.sstride[0] = s.stride[1]; j.sfp[0] = s.fp[1];
+                    j.kind = 1; j.k = s.swap ? !k : k;
                 } else {
-                    j.src[0] = k ? cv : cu; j.sstride[0] = k ? cvs : cus; j.sfp[0] = k ? cvf : cuf;
+                    j.src[0] = s.p[1 + k]; j.sstride[0] = s.stride[1 + k]; j.sfp[0] = s.fp[1 + k];
                     j.kind = 0;
                 }
             }
         }
         return ffhip_launch_copy420(K, stream);
     }
-    if (c->mix_dn2 && !(ev && ev[0] == '0') && srcStride[0] > 0 && cus > 0 && cvs > 0 && dstStride[0] > 0 && dstStride[1] > 0 && dstStride[2] > 0 &&
-        !(((uintptr_t)cu | (uintptr_t)cv | (size_t)cus | (size_t)cvs | cuf | cvf | (uintptr_t)dst[1] | (uintptr_t)dst[2] | (size_t)dstStride[1] |
-           (size_t)dstStride[2] | dstFramePitch[1] | dstFramePitch[2]) & 3)) {
+    if (c->mix_dn2 && !fast_off && topdown && !((s.cal | d.cal) & 3)) {
+        /* the luma plane copied, the chroma planes exactly 2:1 */
         FFHipCopy420Args K;
         memset(&K, 0, sizeof(K));
         K.nframes = nframes;
         FFHipCopy420Job &kj = K.job[K.njobs++];
-        kj.src[0] = s0; kj.sstride[0] = srcStride[0]; kj.sfp[0] = srcFramePitch[0];
-        kj.dst = (uint8_t *)dst[0]; kj.dstride = dstStride[0]; kj.dfp = dstFramePitch[0];
+        kj.src[0] = s.p[0]; kj.sstride[0] = s.stride[0]; kj.sfp[0] = s.fp[0];
+        kj.dst = d.p[0]; kj.dstride = d.stride[0]; kj.dfp = d.fp[0];
         kj.kind = 0; kj.wbytes = t.dstW; kj.rows = t.dstH;
-        int r1 = ffhip_launch_copy420(K, stream);
+        const int r1 = ffhip_launch_copy420(K, stream);
         if (r1 < 0)
             return r1;
         FFHipDn2Args D;
         memset(&D, 0, sizeof(D));
         D.nframes = nframes;
         D.xcd = 1;
-        for (int k = 0; k < 2; k++) {
+        for_each_job(s, d, false, true, [&](const PlaneJob &q) {
             FFHipDn2Job &j = D.job[D.njobs++];
-            j.src = k ? cv : cu; j.sstride = k ? cvs : cus; j.sfp = k ? cvf : cuf;
-            j.dst = (uint8_t *)dst[1 + k]; j.dstride = dstStride[1 + k]; j.dfp = dstFramePitch[1 + k];
+            put_planes(j, q);
             j.srcH = c->chrSrcH; j.dstH = c->d[3].n; j.ngroups = c->d[1].n / 4;
             j.hfv = c->dn2_h[1]; j.vfv = c->dn2_v[1];
             ffhip_down2_plan_job(&j, 32);
-        }
+        });
         return ffhip_launch_down2(D, stream);
     }
-    const char *eu3b = FFHIP_KNOB("FFHIP_SWS_UP32"); /* measure build: 0 keeps the column walker */
-    uintptr_t al3 = (uintptr_t)l.src[0] | (size_t)l.src_stride[0] | l.src_fp[0] | (uintptr_t)l.dst[0] | (size_t)l.dst_stride[0] | l.dst_fp[0];
-    bool neg3 = l.src_stride[0] < 0 || l.dst_stride[0] < 0;
-    for (int i = 0; i < 2; i++) {
-        al3 |= (size_t)ch.src_stride[i] | ch.src_fp[i] | (size_t)ch.dst_stride[i] | ch.dst_fp[i];
-        al3 |= ch.src_step == 2 ? (uintptr_t)(ch.src[0] < ch.src[1] ? ch.src[0] : ch.src[1]) : (uintptr_t)ch.src[i];
-        al3 |= ch.dst_step == 2 ? (uintptr_t)(ch.dst[0] < ch.dst[1] ? ch.dst[0] : ch.dst[1]) : (uintptr_t)ch.dst[i];
-        neg3 = neg3 || ch.src_stride[i] < 0 || ch.dst_stride[i] < 0;
-    }
-    if (!(al3 & 3) && c->u32_ok && !neg3 && !c->luma_pass && !(eu3b && eu3b[0] == '0')) {
+    if (!(al & 3) && c->u32_ok && !neg && !c->luma_pass && !KNOB_IS("FFHIP_SWS_UP32", '0') /* measure build: 0 keeps the column walker */) {
         /* exact 3:2 / 4:3 up: static schedule, no LDS (the 8-bit twin in sws_up32.hip) */
         FFHipU32Args U;
         memset(&U, 0, sizeof(U));
@@ -2452,115 +2296,66 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
         U.bytes = 1;
         U.ratio43 = c->u32_ok == 2;
         const int no = U.ratio43 ? 16 : 12;
-        auto ujob = [&](const FFHipScalePlaneArgs &p, int which, const uint8_t *src, ptrdiff_t ss, size_t sf, uint8_t *dst, ptrdiff_t dsr, size_t df, int pair) {
+        for_each_job(s, d, true, true, [&](const PlaneJob &q) {
+            const FFHipScalePlaneArgs &p = q.which ? ch : l;
             FFHipU32Job &j = U.job[U.njobs++];
-            j.src = src; j.dst = dst; j.sstride = ss; j.dstride = dsr; j.sfp = sf; j.dfp = df;
-            j.pair = pair;
+            put_planes(j, q);
             j.srcH = p.srcH; j.dstH = p.dstH;
-            j.ngroups = pair ? p.dstW / (no / 2) : p.dstW / no;
-            j.hfv = c->u32_h[which]; j.vfv = c->u32_v[which];
-        };
-        ujob(l, 0, l.src[0], l.src_stride[0], l.src_fp[0], l.dst[0], l.dst_stride[0], l.dst_fp[0], 0);
-        if (ch.src_step == 2) {
-            ujob(ch, 1, ch.src[1] < ch.src[0] ? ch.src[1] : ch.src[0], ch.src_stride[0], ch.src_fp[0], ch.dst[1] < ch.dst[0] ? ch.dst[1] : ch.dst[0],
-                 ch.dst_stride[0], ch.dst_fp[0], 1);
-        } else {
-            for (int k = 0; k < 2; k++)
-                ujob(ch, 1, ch.src[k], ch.src_stride[k], ch.src_fp[k], ch.dst[k], ch.dst_stride[k], ch.dst_fp[k], 0);
-        }
+            j.ngroups = q.pair ? p.dstW / (no / 2) : p.dstW / no;
+            j.hfv = c->u32_h[q.which]; j.vfv = c->u32_v[q.which];
+        });
         return ffhip_launch_up32(U, stream);
     }
-    if (c->cw_ok && !(ev && ev[0] == '0')) {
-        uintptr_t al = 0;
-        for (int i = 0; i < 2; i++) {
-            al |= (uintptr_t)l.src[i] | (size_t)l.src_stride[i] | l.src_fp[i] | (uintptr_t)l.dst[i] |
-                  (size_t)l.dst_stride[i] | l.dst_fp[i];
-            al |= (size_t)ch.src_stride[i] | ch.src_fp[i] | (size_t)ch.dst_stride[i] | ch.dst_fp[i];
-            /* an interleaved pair is addressed through its lower pointer */
-            al |= ch.src_step == 2 ? (uintptr_t)(ch.src[0] < ch.src[1] ? ch.src[0] : ch.src[1]) : (uintptr_t)ch.src[i];
-            al |= ch.dst_step == 2 ? (uintptr_t)(ch.dst[0] < ch.dst[1] ? ch.dst[0] : ch.dst[1]) : (uintptr_t)ch.dst[i];
-        }
-        const char *eu = FFHIP_KNOB("FFHIP_SWS_UP2");
-        if (!(al & 3) && (c->up2_ok || (c->mix_up2 && !c->luma_pass && l.src_stride[0] > 0 && l.dst_stride[0] > 0 && ch.src_stride[0] > 0 && ch.src_stride[1] > 0 &&
-                                            ch.dst_stride[0] > 0 && ch.dst_stride[1] > 0)) && !(eu && eu[0] == '0') && !(em_forced())) {
+    if (c->cw_ok && !fast_off) {
+        if (!(al & 3) && (c->up2_ok || (c->mix_up2 && !c->luma_pass && topdown)) && !KNOB_IS("FFHIP_SWS_UP2", '0') && !KNOB_IS("FFHIP_SWS_MFMA", '1')) {
             /* exact 2x: static schedule, regular windows (sws_up2.hip).  FFHIP_SWS_UP2=0 takes the general column walker. */
             FFHipUp2Args U;
             memset(&U, 0, sizeof(U));
             U.nframes = nframes;
-            auto upjob = [&](const FFHipScalePlaneArgs &p, int which, const uint8_t *src, ptrdiff_t ss, size_t sf, uint8_t *dst,
-                             ptrdiff_t dsr, size_t df, int pair, int swap) {
-                FFHipUp2Job &j = U.job[U.njobs++];
-                j.src = src; j.dst = dst; j.sstride = ss; j.dstride = dsr; j.sfp = sf; j.dfp = df;
-                j.pair = pair; j.swap = swap;
-                j.srcW = p.srcW; j.srcH = p.srcH;
-                j.ngroups = pair ? p.srcW / 2 : p.srcW / 4;
-                j.hfv = c->up2_h[which]; j.vfv = c->up2_v[which];
-                j.rc_coeff = p.rc_coeff; j.rc_offset = p.rc_offset;
-                j.hco_ok = c->up2_hco_ok[which];
-                memcpy(j.hco, c->up2_hco[which], sizeof(j.hco));
-            };
-            if (c->mix_up2) {
+            if (c->mix_up2) { /* the luma plane copied, the chroma planes exactly 2x */
                 FFHipCopy420Args K;
                 memset(&K, 0, sizeof(K));
                 K.nframes = nframes;
                 FFHipCopy420Job &kj = K.job[K.njobs++];
-                kj.src[0] = l.src[0]; kj.sstride[0] = l.src_stride[0]; kj.sfp[0] = l.src_fp[0];
-                kj.dst = l.dst[0]; kj.dstride = l.dst_stride[0]; kj.dfp = l.dst_fp[0];
+                kj.src[0] = s.p[0]; kj.sstride[0] = s.stride[0]; kj.sfp[0] = s.fp[0];
+                kj.dst = d.p[0]; kj.dstride = d.stride[0]; kj.dfp = d.fp[0];
                 kj.kind = 0; kj.wbytes = l.dstW; kj.rows = l.dstH;
                 const int r1 = ffhip_launch_copy420(K, stream);
                 if (r1 < 0)
                     return r1;
-            } else {
-                upjob(l, 0, l.src[0], l.src_stride[0], l.src_fp[0], l.dst[0], l.dst_stride[0], l.dst_fp[0], 0, 0);
             }
-            if (c->luma_pass) {
-            } else if (ch.src_step == 2) {
-                const bool ssw = ch.src[1] < ch.src[0], dsw = ch.dst[1] < ch.dst[0];
-                upjob(ch, 1, ssw ? ch.src[1] : ch.src[0], ch.src_stride[0], ch.src_fp[0], dsw ? ch.dst[1] : ch.dst[0],
-                      ch.dst_stride[0], ch.dst_fp[0], 1, ssw != dsw);
-            } else {
-                for (int k = 0; k < 2; k++)
-                    upjob(ch, 1, ch.src[k], ch.src_stride[k], ch.src_fp[k], ch.dst[k], ch.dst_stride[k], ch.dst_fp[k], 0, 0);
-            }
-            /* frames per wave: the split that wastes the fewest lanes at the right edge of the widest job's rows;
-             * lane offsets (frame pitch included) must stay below 2^32 */
+            for_each_job(s, d, !c->mix_up2, !c->luma_pass, [&](const PlaneJob &q) {
+                const FFHipScalePlaneArgs &p = q.which ? ch : l;
+                FFHipUp2Job &j = U.job[U.njobs++];
+                put_planes(j, q);
+                j.swap = q.swap;
+                j.srcW = p.srcW; j.srcH = p.srcH;
+                j.ngroups = q.pair ? p.srcW / 2 : p.srcW / 4;
+                j.hfv = c->up2_h[q.which]; j.vfv = c->up2_v[q.which];
+                j.rc_coeff = p.rc_coeff; j.rc_offset = p.rc_offset;
+                j.hco_ok = c->up2_hco_ok[q.which];
+                memcpy(j.hco, c->up2_hco[q.which], sizeof(j.hco));
+            });
             const char *ef = FFHIP_KNOB("FFHIP_UP2_FSHIFT"), *es = FFHIP_KNOB("FFHIP_UP2_STRIP"), *ed = FFHIP_KNOB("FFHIP_UP2_DEPTH");
             const char *ev2 = FFHIP_KNOB("FFHIP_UP2_VAR"), *ex = FFHIP_KNOB("FFHIP_UP2_XCD");
             U.xcd = ex ? atoi(ex) : 1;     /* measure build: 0 plain numbering, 1 an eighth per XCD (the product), 1 + k chunks of 2^k workgroups */
-            int best = 0;
-            double bestw = 1e30;
-            for (int fsft = 0; fsft <= 2; fsft++) {
-                const int lpf = 64 >> fsft;
-                bool fits = true;
-                double w = 0;
-                for (int i = 0; i < U.njobs; i++) {
-                    const FFHipUp2Job &j = U.job[i];
-                    const unsigned long long span_s = (unsigned long long)((1 << fsft) - 1) * j.sfp + (unsigned long long)j.srcH * (size_t)(j.sstride < 0 ? -j.sstride : j.sstride);
-                    const unsigned long long span_d = (unsigned long long)((1 << fsft) - 1) * j.dfp + 2ull * j.srcH * (size_t)(j.dstride < 0 ? -j.dstride : j.dstride);
-                    if (span_s >= (1ull << 31) || span_d >= (1ull << 31))
-                        fits = false;
-                    /* waves per frame and strip: the full blocks, plus this frame's share of the shared ragged-end blocks */
-                    const int nfull = fsft ? j.ngroups / 64 : 0;
-                    w += ((double)nfull + (double)cdiv(j.ngroups - nfull * 64, lpf) / (1 << fsft)) * j.srcH;
-                }
-                if (nframes < (1 << fsft) && fsft)
-                    fits = false;
-                if (fits && w < bestw - 1e-9) { bestw = w; best = fsft; }
-            }
-            U.fshift = ef && ef[0] >= '0' && ef[0] <= '2' ? ef[0] - '0' : best;
-            bool neg = false;
+            /* frames per wave (up2_fshift); when no split keeps the lane offsets in range this side launches with fshift 0 (the 16-bit side
+             * takes the next kernel) */
+            const int fs = up2_fshift(U, nframes);
+            U.fshift = ef && ef[0] >= '0' && ef[0] <= '2' ? ef[0] - '0' : fs < 0 ? 0 : fs;
+            bool jneg = false;
             for (int i = 0; i < U.njobs; i++)
-                neg = neg || U.job[i].sstride < 0 || U.job[i].dstride < 0;
-            if (!neg) {
+                jneg = jneg || U.job[i].sstride < 0 || U.job[i].dstride < 0;
+            if (!jneg) {
                 /* source rows per strip: 60 when that is eight waves per SIMD or more; shorter strips for a small batch — a strip
                  * re-reads the rows above it and pays a prologue, but ONE 1080p -> 4K frame in 60-row strips is 232 waves on 1,024
                  * SIMDs (measured, nv12: 1 frame 27.7 -> 20.6 us, 4 frames 30.5 -> 23.8 us, 16 frames 63.5 -> 56.6 us, 64 frames
                  * unchanged; what sws_scale_frame() on a filter graph's frames sees.  FFHIP_UP2_STRIP fixes it in the measure build) */
                 static const int wants[] = { 60, 36, 24, 12 };
-                for (int t = 0; t < 4; t++) {
+                for (int w = 0; w < 4; w++) {
                     long long u = 0;
                     for (int i = 0; i < U.njobs; i++) {
-                        ffhip_up2_plan_job(&U.job[i], 64 >> U.fshift, es && atoi(es) > 0 ? atoi(es) : wants[t]);
+                        ffhip_up2_plan_job(&U.job[i], 64 >> U.fshift, es && atoi(es) > 0 ? atoi(es) : wants[w]);
                         u += (long long)U.job[i].upj * U.job[i].nstrips;
                     }
                     if ((es && atoi(es) > 0) || u * ((nframes + (1 << U.fshift) - 1) >> U.fshift) >= 8192)
@@ -2580,37 +2375,26 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             }
         }
         if (!(al & 3) && !c->up2_rc) {
-            const char *em = FFHIP_KNOB("FFHIP_SWS_MFMA");
-            if (c->mf_ok && em && em[0] == '1') {
+            if (c->mf_ok && KNOB_IS("FFHIP_SWS_MFMA", '1')) {
                 /* horizontal pass on the matrix cores (k_sws_mfma) */
                 const char *est = FFHIP_KNOB("FFHIP_MF_STRIP");
                 FFHipMfArgs M;
                 memset(&M, 0, sizeof(M));
                 M.nframes = nframes;
-                auto mfjob = [&](const FFHipScalePlaneArgs &p, int which, const uint8_t *src, ptrdiff_t ss, size_t sf, uint8_t *dst,
-                                 ptrdiff_t dsr, size_t df, int pair, int dswap) {
+                for_each_job(s, d, true, !c->luma_pass, [&](const PlaneJob &q) {
+                    const FFHipScalePlaneArgs &p = q.which ? ch : l;
                     FFHipMfJob &j = M.job[M.njobs++];
-                    j.src = src; j.dst = dst; j.sstride = ss; j.dstride = dsr; j.sfp = sf; j.dfp = df;
-                    j.pair = pair; j.dst_swap = dswap;
+                    put_planes(j, q);
+                    j.dst_swap = q.dswap;
                     j.srcH = p.srcH; j.dstW = p.dstW; j.dstH = p.dstH;
-                    j.tiles = c->mf_tiles[which]; j.vf = c->dn[2 + which].filter; j.vp = c->dn[2 + which].pos; j.ys = c->mf_ys[which];
-                    j.ntiles = c->mf_ntiles[which];
+                    j.tiles = c->mf_tiles[q.which]; j.vf = c->dn[2 + q.which].filter; j.vp = c->dn[2 + q.which].pos; j.ys = c->mf_ys[q.which];
+                    j.ntiles = c->mf_ntiles[q.which];
                     j.ncb = cdiv(j.ntiles, 16);
                     const int want = est && atoi(est) > 0 ? atoi(est) : 540;
                     const int ns = cdiv(p.dstH, want);
                     j.strip_rows = cdiv(p.dstH, ns);
                     j.nstrips = cdiv(p.dstH, j.strip_rows);
-                };
-                mfjob(l, 0, l.src[0], l.src_stride[0], l.src_fp[0], l.dst[0], l.dst_stride[0], l.dst_fp[0], 0, 0);
-                if (c->luma_pass) {
-                } else if (c->mf_chr_pair) {
-                    const uint8_t *sp = ch.src[0] < ch.src[1] ? ch.src[0] : ch.src[1];
-                    uint8_t *dp = ch.dst[0] < ch.dst[1] ? ch.dst[0] : ch.dst[1];
-                    mfjob(ch, 1, sp, ch.src_stride[0], ch.src_fp[0], dp, ch.dst_stride[0], ch.dst_fp[0], 1, ch.dst[1] < ch.dst[0]);
-                } else {
-                    for (int k = 0; k < 2; k++)
-                        mfjob(ch, 1, ch.src[k], ch.src_stride[k], ch.src_fp[k], ch.dst[k], ch.dst_stride[k], ch.dst_fp[k], 0, 0);
-                }
+                });
                 return ffhip_launch_mfma(M, stream);
             }
             const char *eg = FFHIP_KNOB("FFHIP_CW_LUMA_GROUPS"), *ep = FFHIP_KNOB("FFHIP_CW_PLAIN");
@@ -2625,12 +2409,10 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             FFHipCwArgs A;
             memset(&A, 0, sizeof(A));
             A.nframes = nframes;
-            const char *eo = FFHIP_KNOB("FFHIP_CW_OPT");
             A.flags = ep && ep[0] == '1' ? 1 : 0;
-            if (c->cw_opt && !A.flags && !(eo && eo[0] == '0'))
+            if (c->cw_opt && !A.flags && !KNOB_IS("FFHIP_CW_OPT", '0'))
                 A.flags |= 2;
-            const char *edup = FFHIP_KNOB("FFHIP_CW_DUP");
-            if ((A.flags & 2) && c->cw_dup && !(edup && edup[0] == '0'))
+            if ((A.flags & 2) && c->cw_dup && !KNOB_IS("FFHIP_CW_DUP", '0'))
                 A.flags |= 4;
             auto bank = [&](FFHipCwJob &j, const FFHipScalePlaneArgs &p) {
                 const int which = &p == &ch ? 1 : 0; /* the padded 4-tap view of the banks */
@@ -2640,45 +2422,39 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             FFHipCwJob &jl = A.job[0];
             bank(jl, l);
             jl.kind = lg == 2 ? 1 : 0;
-            jl.src[0] = l.src[0]; jl.sstride[0] = l.src_stride[0]; jl.sfp[0] = l.src_fp[0];
-            jl.dst[0] = l.dst[0]; jl.dstride[0] = l.dst_stride[0]; jl.dfp[0] = l.dst_fp[0];
+            jl.src[0] = s.p[0]; jl.sstride[0] = s.stride[0]; jl.sfp[0] = s.fp[0];
+            jl.dst[0] = d.p[0]; jl.dstride[0] = d.stride[0]; jl.dfp[0] = d.fp[0];
             gpl[0] = lg;
             A.njobs = 1;
             if (c->luma_pass) {
-            } else if (ch.src_step == 1 && ch.dst_step == 1) {
-                for (int k = 0; k < 2; k++) {
+            } else if (!s.il && !d.il) {
+                for (int k = 1; k < 3; k++) {
                     FFHipCwJob &j = A.job[A.njobs++];
                     bank(j, ch);
                     j.kind = jl.kind;
-                    j.src[0] = ch.src[k]; j.sstride[0] = ch.src_stride[k]; j.sfp[0] = ch.src_fp[k];
-                    j.dst[0] = ch.dst[k]; j.dstride[0] = ch.dst_stride[k]; j.dfp[0] = ch.dst_fp[k];
+                    j.src[0] = s.p[k]; j.sstride[0] = s.stride[k]; j.sfp[0] = s.fp[k];
+                    j.dst[0] = d.p[k]; j.dstride[0] = d.stride[k]; j.dfp[0] = d.fp[k];
                     gpl[A.njobs - 1] = lg;
                 }
             } else {
+                /* an interleaved side is addressed through its lower pointer */
                 FFHipCwJob &j = A.job[A.njobs++];
                 bank(j, ch);
-                const bool src_il = ch.src_step == 2, dst_il = ch.dst_step == 2;
-                j.kind = src_il && dst_il ? 2 : src_il ? 3 : 4;
+                j.kind = s.il && d.il ? 2 : s.il ? 3 : 4;
                 for (int k = 0; k < 2; k++) {
-                    j.src[k] = ch.src[k]; j.sstride[k] = ch.src_stride[k]; j.sfp[k] = ch.src_fp[k];
-                    j.dst[k] = ch.dst[k]; j.dstride[k] = ch.dst_stride[k]; j.dfp[k] = ch.dst_fp[k];
+                    j.src[k] = s.il && !k ? s.pair : s.p[1 + k]; j.sstride[k] = s.stride[1 + k]; j.sfp[k] = s.fp[1 + k];
+                    j.dst[k] = d.il && !k ? d.pair : d.p[1 + k]; j.dstride[k] = d.stride[1 + k]; j.dfp[k] = d.fp[1 + k];
                 }
-                if (src_il) {
-                    j.src_swap = ch.src[1] < ch.src[0];
-                    j.src[0] = j.src_swap ? ch.src[1] : ch.src[0];
-                }
-                if (dst_il) {
-                    j.dst_swap = ch.dst[1] < ch.dst[0];
-                    j.dst[0] = j.dst_swap ? ch.dst[1] : ch.dst[0];
-                }
+                j.src_swap = s.swap;
+                j.dst_swap = d.swap;
                 gpl[A.njobs - 1] = 1;
             }
-            for (int t = 0; t < 4; t++) {
-                strip = es && atoi(es) > 0 ? atoi(es) : strips[t];
+            for (int i = 0; i < 4; i++) {
+                strip = es && atoi(es) > 0 ? atoi(es) : strips[i];
                 long long u = 0;
-                for (int i = 0; i < A.njobs; i++) {
-                    ffhip_cw_plan_job(&A.job[i], gpl[i], strip);
-                    u += (long long)A.job[i].ncb * A.job[i].nstrips;
+                for (int k = 0; k < A.njobs; k++) {
+                    ffhip_cw_plan_job(&A.job[k], gpl[k], strip);
+                    u += (long long)A.job[k].ncb * A.job[k].nstrips;
                 }
                 if ((es && atoi(es) > 0) || u * nframes >= 4096)
                     break;
@@ -2686,123 +2462,77 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             return ffhip_launch_colwalk(A, lg, depth, stream);
         }
     }
-    uintptr_t al2 = (uintptr_t)l.src[0] | (size_t)l.src_stride[0] | l.src_fp[0] | (uintptr_t)l.dst[0] | (size_t)l.dst_stride[0] | l.dst_fp[0];
-    for (int i = 0; i < 2; i++) {
-        al2 |= (size_t)ch.src_stride[i] | ch.src_fp[i] | (size_t)ch.dst_stride[i] | ch.dst_fp[i];
-        al2 |= ch.src_step == 2 ? (uintptr_t)(ch.src[0] < ch.src[1] ? ch.src[0] : ch.src[1]) : (uintptr_t)ch.src[i];
-        al2 |= ch.dst_step == 2 ? (uintptr_t)(ch.dst[0] < ch.dst[1] ? ch.dst[0] : ch.dst[1]) : (uintptr_t)ch.dst[i];
-    }
-    const char *e2 = FFHIP_KNOB("FFHIP_SWS_DOWN2");
-    bool neg = false;
-    for (int i = 0; i < 2; i++)
-        neg = neg || l.src_stride[i] < 0 || l.dst_stride[i] < 0 || ch.src_stride[i] < 0 || ch.dst_stride[i] < 0;
-    if (!(al2 & 3) && c->dn2_ok && !neg && !(e2 && e2[0] == '0') && !(ev && ev[0] == '0')) {
+    if (!(al & 3) && c->dn2_ok && !neg && !KNOB_IS("FFHIP_SWS_DOWN2", '0') && !fast_off) {
         /* exact 2:1: static schedule, regular windows, no LDS (sws_down2.hip).  FFHIP_SWS_DOWN2=0 takes the wide walker. */
         FFHipDn2Args D;
         memset(&D, 0, sizeof(D));
         D.nframes = nframes;
-        const char *ex = FFHIP_KNOB("FFHIP_DN2_XCD"), *es = FFHIP_KNOB("FFHIP_DN2_STRIP");
-        D.xcd = !(ex && ex[0] == '0');
-        auto dnjob = [&](const FFHipScalePlaneArgs &p, int which, const uint8_t *src, ptrdiff_t ss, size_t sf, uint8_t *dst,
-                         ptrdiff_t dsr, size_t df, int pair, int swap) {
+        const char *es = FFHIP_KNOB("FFHIP_DN2_STRIP");
+        D.xcd = !KNOB_IS("FFHIP_DN2_XCD", '0');
+        for_each_job(s, d, true, !c->luma_pass, [&](const PlaneJob &q) {
+            const FFHipScalePlaneArgs &p = q.which ? ch : l;
             FFHipDn2Job &j = D.job[D.njobs++];
-            j.src = src; j.dst = dst; j.sstride = ss; j.dstride = dsr; j.sfp = sf; j.dfp = df;
-            j.pair = pair; j.swap = swap;
+            put_planes(j, q);
+            j.swap = q.swap;
             j.srcH = p.srcH; j.dstH = p.dstH;
-            j.ngroups = pair ? p.dstW / 2 : p.dstW / 4;
-            j.hfv = c->dn2_h[which]; j.vfv = c->dn2_v[which];
+            j.ngroups = q.pair ? p.dstW / 2 : p.dstW / 4;
+            j.hfv = c->dn2_h[q.which]; j.vfv = c->dn2_v[q.which];
             ffhip_down2_plan_job(&j, es && atoi(es) > 0 ? atoi(es) : 32); /* measured: 28..36 rows per strip */
-        };
-        dnjob(l, 0, l.src[0], l.src_stride[0], l.src_fp[0], l.dst[0], l.dst_stride[0], l.dst_fp[0], 0, 0);
-        if (c->luma_pass) {
-        } else if (ch.src_step == 2) {
-            const bool ssw = ch.src[1] < ch.src[0], dsw = ch.dst[1] < ch.dst[0];
-            dnjob(ch, 1, ssw ? ch.src[1] : ch.src[0], ch.src_stride[0], ch.src_fp[0], dsw ? ch.dst[1] : ch.dst[0],
-                  ch.dst_stride[0], ch.dst_fp[0], 1, ssw != dsw);
-        } else {
-            for (int k = 0; k < 2; k++)
-                dnjob(ch, 1, ch.src[k], ch.src_stride[k], ch.src_fp[k], ch.dst[k], ch.dst_stride[k], ch.dst_fp[k], 0, 0);
-        }
+        });
         return ffhip_launch_down2(D, stream);
     }
-    const char *e3 = FFHIP_KNOB("FFHIP_SWS_DOWN32"); /* measure build: 0 keeps the wide walker */
-    if (!(al2 & 3) && c->d32_ok && !neg && !c->luma_pass && !(e3 && e3[0] == '0') && !(ev && ev[0] == '0')) {
+    if (!(al & 3) && c->d32_ok && !neg && !c->luma_pass && !KNOB_IS("FFHIP_SWS_DOWN32", '0') /* measure build: 0 keeps the wide walker */ && !fast_off) {
         /* exact 3:2: static schedule with period (3 in, 2 out), no LDS (sws_down32.hip) */
         FFHipD32Args D;
         memset(&D, 0, sizeof(D));
         D.nframes = nframes;
-        auto djob = [&](const FFHipScalePlaneArgs &p, int which, const uint8_t *src, ptrdiff_t ss, size_t sf, uint8_t *dst, ptrdiff_t dsr, size_t df,
-                        int pair, int swap) {
+        for_each_job(s, d, true, true, [&](const PlaneJob &q) {
+            const FFHipScalePlaneArgs &p = q.which ? ch : l;
             FFHipD32Job &j = D.job[D.njobs++];
-            j.src = src; j.dst = dst; j.sstride = ss; j.dstride = dsr; j.sfp = sf; j.dfp = df;
-            j.pair = pair; j.swap = swap;
+            put_planes(j, q);
+            j.swap = q.swap;
             j.srcH = p.srcH; j.dstH = p.dstH;
-            j.ngroups = pair ? p.dstW / 4 : p.dstW / 8;
-            j.hfv = c->d32_h[which]; j.vfv = c->d32_v[which];
-        };
-        djob(l, 0, l.src[0], l.src_stride[0], l.src_fp[0], l.dst[0], l.dst_stride[0], l.dst_fp[0], 0, 0);
-        if (ch.src_step == 2) {
-            const bool ssw = ch.src[1] < ch.src[0], dsw = ch.dst[1] < ch.dst[0];
-            djob(ch, 1, ssw ? ch.src[1] : ch.src[0], ch.src_stride[0], ch.src_fp[0], dsw ? ch.dst[1] : ch.dst[0], ch.dst_stride[0], ch.dst_fp[0], 1,
-                 ssw != dsw);
-        } else {
-            for (int k = 0; k < 2; k++)
-                djob(ch, 1, ch.src[k], ch.src_stride[k], ch.src_fp[k], ch.dst[k], ch.dst_stride[k], ch.dst_fp[k], 0, 0);
-        }
+            j.ngroups = q.pair ? p.dstW / 4 : p.dstW / 8;
+            j.hfv = c->d32_h[q.which]; j.vfv = c->d32_v[q.which];
+        });
         return ffhip_launch_down32(D, stream);
     }
     /* wide banks: the LDS-backed walker (FFHIP_SWS_WIDE=0 forces the LDS-tiled kernel) */
     const char *ew = FFHIP_KNOB("FFHIP_SWS_WIDE");
-    const bool cw_taken_off = ev && ev[0] == '0';
-    if (c->lw_ok && !(ew && ew[0] == '0') && !(cw_taken_off && !(ew && ew[0] == '1'))) {
-        uintptr_t al = (uintptr_t)l.src[0] | (size_t)l.src_stride[0] | l.src_fp[0] | (uintptr_t)l.dst[0] | (size_t)l.dst_stride[0] |
-                       l.dst_fp[0];
-        for (int i = 0; i < 2; i++) {
-            al |= (size_t)ch.src_stride[i] | ch.src_fp[i] | (size_t)ch.dst_stride[i] | ch.dst_fp[i];
-            al |= ch.src_step == 2 ? (uintptr_t)(ch.src[0] < ch.src[1] ? ch.src[0] : ch.src[1]) : (uintptr_t)ch.src[i];
-            al |= ch.dst_step == 2 ? (uintptr_t)(ch.dst[0] < ch.dst[1] ? ch.dst[0] : ch.dst[1]) : (uintptr_t)ch.dst[i];
-        }
-        if (!(al & 3)) {
-            FFHipLwArgs W;
-            memset(&W, 0, sizeof(W));
-            W.nframes = nframes; W.ht = c->lw_ht; W.vt = c->lw_vt;
-            auto wbank = [&](FFHipLwJob &j, const FFHipScalePlaneArgs &p, int which) {
-                j.srcW = p.srcW; j.srcH = p.srcH; j.dstW = p.dstW; j.dstH = p.dstH;
-                j.hf = c->dw[which].filter; j.hp = c->dw[which].pos; j.vf = c->dw[2 + which].filter; j.vp = c->dw[2 + which].pos;
-                ffhip_lw_plan_job(&j);
-            };
-            /* the heavier units (a U/V pair is twice a plane) are enumerated first: they start first */
-            if (c->luma_pass) {
-            } else if (ch.src_step == 1 && ch.dst_step == 1) {
-                for (int k = 0; k < 2; k++) {
-                    FFHipLwJob &j = W.job[W.njobs++];
-                    j.src[0] = ch.src[k]; j.sstride[0] = ch.src_stride[k]; j.sfp[0] = ch.src_fp[k];
-                    j.dst[0] = ch.dst[k]; j.dstride[0] = ch.dst_stride[k]; j.dfp[0] = ch.dst_fp[k];
-                    wbank(j, ch, 1);
-                }
-            } else {
+    if (c->lw_ok && !(ew && ew[0] == '0') && !(fast_off && !(ew && ew[0] == '1')) && !(al & 3)) {
+        FFHipLwArgs W;
+        memset(&W, 0, sizeof(W));
+        W.nframes = nframes; W.ht = c->lw_ht; W.vt = c->lw_vt;
+        auto wbank = [&](FFHipLwJob &j, const FFHipScalePlaneArgs &p, int which) {
+            j.srcW = p.srcW; j.srcH = p.srcH; j.dstW = p.dstW; j.dstH = p.dstH;
+            j.hf = c->dw[which].filter; j.hp = c->dw[which].pos; j.vf = c->dw[2 + which].filter; j.vp = c->dw[2 + which].pos;
+            ffhip_lw_plan_job(&j);
+        };
+        /* the heavier units (a U/V pair is twice a plane) are enumerated first: they start first */
+        if (c->luma_pass) {
+        } else if (!s.il && !d.il) {
+            for (int k = 1; k < 3; k++) {
                 FFHipLwJob &j = W.job[W.njobs++];
-                j.pair = 1; j.sil = ch.src_step == 2; j.dil = ch.dst_step == 2;
-                for (int k = 0; k < 2; k++) {
-                    j.src[k] = ch.src[k]; j.sstride[k] = ch.src_stride[k]; j.sfp[k] = ch.src_fp[k];
-                    j.dst[k] = ch.dst[k]; j.dstride[k] = ch.dst_stride[k]; j.dfp[k] = ch.dst_fp[k];
-                }
-                if (j.sil) {
-                    j.src_swap = ch.src[1] < ch.src[0];
-                    j.src[0] = j.src_swap ? ch.src[1] : ch.src[0];
-                }
-                if (j.dil) {
-                    j.dst_swap = ch.dst[1] < ch.dst[0];
-                    j.dst[0] = j.dst_swap ? ch.dst[1] : ch.dst[0];
-                }
+                j.src[0] = s.p[k]; j.sstride[0] = s.stride[k]; j.sfp[0] = s.fp[k];
+                j.dst[0] = d.p[k]; j.dstride[0] = d.stride[k]; j.dfp[0] = d.fp[k];
                 wbank(j, ch, 1);
             }
-            FFHipLwJob &jl = W.job[W.njobs++];
-            jl.src[0] = l.src[0]; jl.sstride[0] = l.src_stride[0]; jl.sfp[0] = l.src_fp[0];
-            jl.dst[0] = l.dst[0]; jl.dstride[0] = l.dst_stride[0]; jl.dfp[0] = l.dst_fp[0];
-            wbank(jl, l, 0);
-            return ffhip_launch_lwalk(W, stream);
+        } else {
+            FFHipLwJob &j = W.job[W.njobs++];
+            j.pair = 1; j.sil = s.il; j.dil = d.il;
+            for (int k = 0; k < 2; k++) {
+                j.src[k] = s.il && !k ? s.pair : s.p[1 + k]; j.sstride[k] = s.stride[1 + k]; j.sfp[k] = s.fp[1 + k];
+                j.dst[k] = d.il && !k ? d.pair : d.p[1 + k]; j.dstride[k] = d.stride[1 + k]; j.dfp[k] = d.fp[1 + k];
+            }
+            j.src_swap = s.swap;
+            j.dst_swap = d.swap;
+            wbank(j, ch, 1);
         }
+        FFHipLwJob &jl = W.job[W.njobs++];
+        jl.src[0] = s.p[0]; jl.sstride[0] = s.stride[0]; jl.sfp[0] = s.fp[0];
+        jl.dst[0] = d.p[0]; jl.dstride[0] = d.stride[0]; jl.dfp[0] = d.fp[0];
+        wbank(jl, l, 0);
+        return ffhip_launch_lwalk(W, stream);
     }
     if (c->luma_pass)
         ch.tiles_y = 0; /* the tiled kernel's grid is the luma tiles followed by the chroma tiles: none of the latter */
@@ -2918,18 +2648,11 @@ static int sws_scale_locked(FFHipSwsContext *c, const uint8_t *const src[], cons
         off_d[i] = total;
         total += (size_t)pitch_d[i] * dp[i].rows + 256;
     }
-    if (total > c->stage_sz) {
-        if (c->stage)
-            (void)hipFree(c->stage);
-        c->stage = nullptr;
-        c->stage_sz = 0;
-        if (hipMalloc(&c->stage, total) != hipSuccess) {
-            ffhip_set_error("ffhip_sws_scale: staging hipMalloc(%zu) failed", total);
-            return FFHIP_ENOMEM;
-        }
-        c->stage_sz = total;
+    if (grow(c->stage, c->stage_sz, total) != hipSuccess) {
+        ffhip_set_error("ffhip_sws_scale: staging hipMalloc(%zu) failed", total);
+        return FFHIP_ENOMEM;
     }
-    uint8_t *base = (uint8_t *)c->stage;
+    uint8_t *base = (uint8_t *)c->stage.p;
     const void *dsrc[4] = { 0, 0, 0, 0 };
     void *ddst[4] = { 0, 0, 0, 0 };
     size_t fp[4] = { 0, 0, 0, 0 };
@@ -2939,23 +2662,16 @@ static int sws_scale_locked(FFHipSwsContext *c, const uint8_t *const src[], cons
         const int rows = sliced ? srcSliceH : srcRows, row0 = sliced ? srcSliceY : 0;
         const int wb = t.srcW * c->rgb_in.bpp, rp = (wb + 255) & ~255;
         const size_t need = (size_t)rp * rows + 256;
-        if (need > c->rgb_in.stage_sz) {
-            if (c->rgb_in.stage)
-                (void)hipFree(c->rgb_in.stage);
-            c->rgb_in.stage = nullptr;
-            c->rgb_in.stage_sz = 0;
-            if (hipMalloc(&c->rgb_in.stage, need) != hipSuccess) {
-                ffhip_set_error("ffhip_sws_scale: staging hipMalloc(%zu) failed", need);
-                return FFHIP_ENOMEM;
-            }
-            c->rgb_in.stage_sz = need;
+        if (grow(c->rgb_in.stage, c->rgb_in.stage_sz, need) != hipSuccess) {
+            ffhip_set_error("ffhip_sws_scale: staging hipMalloc(%zu) failed", need);
+            return FFHIP_ENOMEM;
         }
-        HIP_TRY(copy2d(c->rgb_in.stage, rp, src[0], srcStride[0], wb, rows, hipMemcpyHostToDevice));
+        HIP_TRY(copy2d(c->rgb_in.stage.p, rp, src[0], srcStride[0], wb, rows, hipMemcpyHostToDevice));
         uint8_t *const pp[3] = { base + off_s[0] + (size_t)row0 * pitch_s[0], base + off_s[1] + (size_t)row0 * pitch_s[1],
                                  base + off_s[2] + (size_t)row0 * pitch_s[2] };
         /* (the target's staging planes lie behind the source's: base + off_d[]) */
         const bool yd = c->rgb_in.y_direct;
-        const int r = rgb_in_launch(c, 1, static_cast<const uint8_t *>(c->rgb_in.stage), rp, 0, rows, pp, pitch_s, fp, 0,
+        const int r = rgb_in_launch(c, 1, static_cast<const uint8_t *>(c->rgb_in.stage.p), rp, 0, rows, pp, pitch_s, fp, 0,
                                     yd ? base + off_d[0] + (size_t)row0 * pitch_d[0] : nullptr, yd ? pitch_d[0] : 0, 0);
         if (r < 0)
             return r;
