@@ -14,10 +14,10 @@
  *     in place), and a call that cannot run on the device — a HIP error anywhere, an argument outside the staged range, or
  *     FFHIP_FAULT=1 (test hook) — is answered by the displaced C function; ffhip_shim_fallbacks() counts them, and a face
  *     with nothing to fall back on records the member's name in ffhip_last_error();
- *   - host memory is written only after everything has come back: the whole scratch arena returns in ONE device-to-host copy
- *     into a host bounce buffer, results are committed from there (a failure can therefore not leave half a block behind for
- *     the C function to run on top of).
- * Thread-safe: one mutex (runtime.hip) guards the arena and the bounce buffer for a whole stage / run / copy-back sequence.
+ *   - host memory is written only after everything has come back: a face builds its device block as a host image (Stage,
+ *     kernels/shim_arena.h), sends it in ONE copy, and the block returns in ONE device-to-host copy into the same image; results
+ *     are committed from there (a failure can therefore not leave half a block behind for the C function to run on top of).
+ * Thread-safe: the device's mutex (runtime.hip) guards its arena and its image for a whole stage / run / copy-back sequence.
  */
 #include <atomic>
 #include <mutex>
@@ -33,27 +33,18 @@
 
 extern "C" long ffhip_shim_fallbacks(void) { return g_fallbacks.load(); }
 
-#include "kernels/shim_rect.h"
-
 /* ---- h264dsp: single blocks ---------------------------------------------------------------------- */
 static bool idct_single(int kind, uint8_t *dst, int16_t *block, ptrdiff_t stride)
 {
     const int size = (kind & 1) ? 8 : 4, ncoef = size * size; /* IDCT4 0, IDCT8 1, IDCT4_DC 2, IDCT8_DC 3, ADD_PIXELS4 4, ADD_PIXELS8 5 */
-    Rect d = { dst, stride, 0, size - 1, 0, size - 1, nullptr };
-    Arena A(rect_bytes(d) + 256 + 64);
-    if (!A.ok)
+    const Rect d = { dst, stride, 0, size - 1, 0, size - 1 };
+    Stage S;
+    const size_t blk = S.put(block, ncoef * 2), off = S.hole(4); /* off: a zero block offset */
+    const ptrdiff_t pix = S.rect(d);
+    if (!S.up() || ffhip_launch_h264_idct_add(kind, S.dev(pix), DP, S.dev<int32_t>(off), S.dev<int16_t>(blk), 1, 0) < 0 || !S.down())
         return false;
-    uint8_t *buf = A.buf;
-    int16_t *dblk = (int16_t *)buf;
-    int32_t *doff = (int32_t *)(buf + 128);
-    const int32_t zero = 0;
-    if (!rect_up(d, buf + 256) || hipMemcpy(dblk, block, ncoef * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(doff, &zero, 4, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_h264_idct_add(kind, d.dev, DP, doff, dblk, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, size - 1, 0, size - 1);
-    memcpy(block, A.host(dblk), ncoef * 2); /* cleared by the kernel */
+    S.commit(d, pix);
+    memcpy(block, S.img(blk), ncoef * 2); /* cleared by the kernel */
     return true;
 }
 static FFHipH264DSPContext g_fb_h264; /* the C functions ff_h264dsp_init_hip() displaced */
@@ -76,30 +67,19 @@ static bool idct_mb(int which, uint8_t *dst, const int *blockoffset, int16_t *bl
         if (blockoffset[i] > hi) hi = blockoffset[i];
     }
     const size_t span = (size_t)(hi - lo) + (size_t)(bs - 1) * stride + bs;
-    Arena A(span + 512 + 64 + 64 + 64 + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    int16_t *dblk = (int16_t *)buf;              /* 512 B */
-    int32_t *dbo = (int32_t *)(buf + 512);       /* 64 B  */
-    uint8_t *dnn = buf + 576;                    /* 40 B  */
-    int32_t *dmb = (int32_t *)(buf + 640);       /* 4 B   */
-    uint8_t *dpix = buf + 704;                   /* flat copy of the touched span, same stride */
-    const int32_t mboff = 0;
     int32_t bo[16];
     for (int i = 0; i < 16; i++)
         bo[i] = blockoffset[i] - lo;
-    if (hipMemcpy(dpix, dst + lo, span, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dblk, block, 512, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dbo, bo, 64, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dnn, nnzc, 40, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dmb, &mboff, 4, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_h264_idct_add_mb(which, dpix, stride, dmb, dbo, dblk, dnn, 1, 0) < 0 || !A.down())
+    Stage S;
+    const size_t blk = S.put(block, 512), dbo = S.put(bo, 64), nn = S.put(nnzc, 40), mb = S.hole(4);
+    const size_t pix = S.put(dst + lo, span); /* flat copy of the touched span, same stride */
+    if (!S.up() ||
+        ffhip_launch_h264_idct_add_mb(which, S.dev(pix), stride, S.dev<int32_t>(mb), S.dev<int32_t>(dbo), S.dev<int16_t>(blk), S.dev(nn), 1, 0) < 0 ||
+        !S.down())
         return false;
     for (int i = 0; i < 16; i += (which == 1 ? 4 : 1)) /* only this macroblock's own blocks travel back */
-        commit2d(A, dst + blockoffset[i], stride, dpix + bo[i], stride, bs, bs);
-    memcpy(block, A.host(dblk), 512);
+        S.get2d(dst + blockoffset[i], stride, pix + bo[i], stride, bs, bs);
+    memcpy(block, S.img(blk), 512);
     return true;
 }
 static void s_idct_add16(uint8_t *d, const int *bo, int16_t *b, ptrdiff_t s, const uint8_t n[5 * 8]) { if (!idct_mb(0, d, bo, b, s, n)) SHIM_FB(g_fb_h264, idct_add16, d, bo, b, s, n); }
@@ -120,33 +100,24 @@ static bool idct_add8_gpu(uint8_t **dest, const int *blockoffset, int16_t *block
             if (blockoffset[i] > hi[j]) hi[j] = blockoffset[i];
         }
     }
-    const size_t span[2] = { (size_t)(hi[0] - lo[0]) + 3 * (size_t)stride + 4, (size_t)(hi[1] - lo[1]) + 3 * (size_t)stride + 4 };
-    const size_t sp0 = (span[0] + 63) & ~(size_t)63, sp1 = (span[1] + 63) & ~(size_t)63;
-    Arena A(1536 + 192 + 128 + 64 + sp0 + sp1 + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    int16_t *dblk = (int16_t *)buf;              /* 1536 B */
-    int32_t *dbo = (int32_t *)(buf + 1536);      /* 192 B  */
-    uint8_t *dnn = buf + 1728;                   /* 120 B  */
-    int32_t *dmb = (int32_t *)(buf + 1856);      /* 4 B    */
-    uint8_t *dpix[2] = { buf + 1920, buf + 1920 + sp0 };
-    const int32_t mboff = 0;
     int32_t bo[48] = { 0 };
     for (int j = 0; j < 2; j++)
         for (int i = 16 * (j + 1); i < 16 * (j + 1) + 4; i++)
             bo[i] = blockoffset[i] - lo[j];
-    if (hipMemcpy(dpix[0], dest[0] + lo[0], span[0], hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dpix[1], dest[1] + lo[1], span[1], hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dblk, block, 1536, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dbo, bo, 192, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dnn, nnzc, 120, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dmb, &mboff, 4, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_h264_idct_add8(dpix[0], dpix[1], stride, dmb, dbo, dblk, dnn, 1, 0) < 0 || !A.down())
+    Stage S;
+    const size_t blk = S.put(block, 1536), dbo = S.put(bo, 192), nn = S.put(nnzc, 120), mb = S.hole(4);
+    size_t pix[2];
+    for (int j = 0; j < 2; j++)
+        pix[j] = S.put(dest[j] + lo[j], (size_t)(hi[j] - lo[j]) + 3 * (size_t)stride + 4);
+    if (!S.up() ||
+        ffhip_launch_h264_idct_add8(S.dev(pix[0]), S.dev(pix[1]), stride, S.dev<int32_t>(mb), S.dev<int32_t>(dbo), S.dev<int16_t>(blk), S.dev(nn),
+                                    1, 0) < 0 ||
+        !S.down())
         return false;
     for (int j = 0; j < 2; j++)
         for (int i = 16 * (j + 1); i < 16 * (j + 1) + 4; i++)
-            commit2d(A, dest[j] + blockoffset[i], stride, dpix[j] + bo[i], stride, 4, 4);
-    memcpy(block + 256, A.host(dblk + 256), 2 * 256 * sizeof(int16_t)); /* the chroma planes' coefficients (cleared where consumed) */
+            S.get2d(dest[j] + blockoffset[i], stride, pix[j] + bo[i], stride, 4, 4);
+    memcpy(block + 256, S.img(blk + 512), 2 * 256 * sizeof(int16_t)); /* the chroma planes' coefficients (cleared where consumed) */
     return true;
 }
 static void s_idct_add8(uint8_t **d, const int *bo, int16_t *b, ptrdiff_t s, const uint8_t n[15 * 8]) { if (!idct_add8_gpu(d, bo, b, s, n)) SHIM_FB(g_fb_h264, idct_add8, d, bo, b, s, n); }
@@ -154,28 +125,17 @@ static void s_idct_add8(uint8_t **d, const int *bo, int16_t *b, ptrdiff_t s, con
 /* the DC transforms: 16 (luma) / 4 (chroma) values in, dequantised values out */
 static bool dc_dequant_gpu(int luma, int16_t *output, int16_t *input, int qmul)
 {
-    Arena A(512 + 64 + 64 + 64);
-    if (!A.ok)
+    const int32_t q = qmul;
+    Stage S;
+    const size_t out = S.put(output, luma ? 512 : 128), in = S.put(luma ? input : nullptr, 32), dq = S.put(&q, 4), off = S.hole(4);
+    if (!S.up())
         return false;
-    uint8_t *buf = A.buf;
-    int16_t *dout = (int16_t *)buf, *din = (int16_t *)(buf + 512);
-    int32_t *dq = (int32_t *)(buf + 576), *doff = (int32_t *)(buf + 608);
-    const int32_t q = qmul, zero = 0;
-    if (hipMemcpy(dq, &q, 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(doff, &zero, 4, hipMemcpyHostToDevice) != hipSuccess)
+    const int r = luma ? ffhip_launch_h264_luma_dc_dequant(S.dev<int16_t>(out), 256, S.dev<int16_t>(in), 16, S.dev<int32_t>(dq), 1, 0)
+                       : ffhip_launch_h264_chroma_dc_dequant(S.dev<int16_t>(out), S.dev<int32_t>(off), S.dev<int32_t>(dq), 1, 0);
+    if (r < 0 || !S.down())
         return false;
-    if (luma) {
-        if (hipMemcpy(din, input, 32, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dout, output, 512, hipMemcpyHostToDevice) != hipSuccess ||
-            ffhip_launch_h264_luma_dc_dequant(dout, 256, din, 16, dq, 1, 0) < 0 || !A.down())
-            return false;
-        for (int i = 0; i < 16; i++) /* the 16 DC positions are all the function writes */
-            output[16 * i] = reinterpret_cast<const int16_t *>(A.host(dout))[16 * i];
-    } else {
-        if (hipMemcpy(dout, output, 128, hipMemcpyHostToDevice) != hipSuccess || ffhip_launch_h264_chroma_dc_dequant(dout, doff, dq, 1, 0) < 0 ||
-            !A.down())
-            return false;
-        for (int i = 0; i < 4; i++)
-            output[16 * i] = reinterpret_cast<const int16_t *>(A.host(dout))[16 * i];
-    }
+    for (int i = 0; i < (luma ? 16 : 4); i++) /* the 16 (luma) / 4 (chroma) DC positions are all the function writes */
+        output[16 * i] = S.img<int16_t>(out)[16 * i];
     return true;
 }
 static void s_luma_dc_dequant(int16_t *o, int16_t *i, int q) { if (!dc_dequant_gpu(1, o, i, q)) SHIM_FB(g_fb_h264, luma_dc_dequant_idct, o, i, q); }
@@ -186,24 +146,19 @@ static bool lf_single(int kind, uint8_t *pix, ptrdiff_t stride, int alpha, int b
 {
     const bool chroma = kind & 2, vert_edge = kind & 1;
     const int along = chroma ? 8 : 16, across = chroma ? 2 : 4; /* samples read each side of the edge */
-    Rect r = { pix, stride, vert_edge ? 0 : -across, vert_edge ? along - 1 : across - 1,
-               vert_edge ? -across : 0, vert_edge ? across - 1 : along - 1, nullptr };
-    Arena A(rect_bytes(r) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    FFHipH264Edge e;
-    memset(&e, 0, sizeof(e));
+    const Rect r = { pix, stride, vert_edge ? 0 : -across, vert_edge ? along - 1 : across - 1, vert_edge ? -across : 0, vert_edge ? across - 1 : along - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipH264Edge));
+    const ptrdiff_t org = S.rect(r);
+    FFHipH264Edge &e = *S.img<FFHipH264Edge>(hdr);
     e.kind = (uint8_t)kind;
     e.alpha = (uint8_t)(alpha < 0 ? 0 : alpha > 255 ? 255 : alpha); /* 8-bit tables top out at 255 / 18 */
     e.beta = (uint8_t)(beta < 0 ? 0 : beta > 255 ? 255 : beta);
     if (tc0)
         memcpy(e.tc0, tc0, 4);
-    if (!rect_up(r, buf + 64) || hipMemcpy(buf, &e, sizeof(e), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_loop_filter(S.dev(org), DP, S.dev<const FFHipH264Edge>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_loop_filter(r.dev, DP, (const FFHipH264Edge *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, r, r.r0, r.r1, r.c0, r.c1);
+    S.commit(r, org);
     return true;
 }
 static void s_v_lf_luma(uint8_t *p, ptrdiff_t s, int a, int b, int8_t *t) { if (!lf_single(FFHIP_H264_LF_V_LUMA, p, s, a, b, t)) SHIM_FB(g_fb_h264, v_loop_filter_luma, p, s, a, b, t); }
@@ -263,30 +218,23 @@ extern "C" int ff_h264dsp_init_hip(FFHipH264DSPContext *c, int bit_depth, int ch
 static bool qpel_single(int avg, int size_idx, int mcxy, uint8_t *dst, const uint8_t *src, ptrdiff_t stride)
 {
     const int n = 16 >> size_idx;
-    Rect d = { dst, stride, 0, n - 1, 0, n - 1, nullptr };
+    const Rect d = { dst, stride, 0, n - 1, 0, n - 1 };
     /* only what the reference function of this slot reads: the 6-tap margin exists on an axis only when that axis is
      * filtered (mc00 / mc0y / mcx0 read no margin on the other one; mc_dir_part emulates edges only then, h264_mb.c:206-300) */
     const bool fx = mcxy & 3, fy = mcxy >> 2;
-    Rect s = { const_cast<uint8_t *>(src), stride, fy ? -2 : 0, fy ? n + 2 : n - 1, fx ? -2 : 0, fx ? n + 2 : n - 1, nullptr };
-    Rect full = s;
-    full.r0 = -2; full.r1 = n + 2; full.c0 = -2; full.c1 = n + 2; /* the device tile always has the margin (unread part: whatever) */
-    Arena A(rect_bytes(d) + rect_bytes(full) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    /* the (possibly margin-less) source rectangle lands where a full-margin one would: row -2, column -2 at the tile's origin */
-    if (!rect_up(d, buf + 64) || !rect_up(s, buf + 64 + rect_bytes(d) + (size_t)(s.r0 + 2) * DP + (s.c0 + 2)))
-        return false;
-    FFHipQpelBlock b;
-    memset(&b, 0, sizeof(b));
-    /* both rectangles sit in one scratch arena: offsets relative to its start, one shared pitch */
-    b.dst_offset = (int32_t)(d.dev - buf); b.src_offset = (int32_t)(s.dev - buf);
+    const Rect s = { const_cast<uint8_t *>(src), stride, fy ? -2 : 0, fy ? n + 2 : n - 1, fx ? -2 : 0, fx ? n + 2 : n - 1 };
+    const Rect full = { s.host, stride, -2, n + 2, -2, n + 2 }; /* the device tile always has the margin (unread part: zeros) */
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipQpelBlock));
+    const ptrdiff_t dorg = S.rect(d), sorg = S.area(full);
+    S.fill(s, sorg);
+    /* both rectangles sit in one block: offsets relative to its start, one shared pitch */
+    FFHipQpelBlock &b = *S.img<FFHipQpelBlock>(hdr);
+    b.dst_offset = (int32_t)dorg; b.src_offset = (int32_t)sorg;
     b.mcxy = (uint8_t)mcxy; b.size_idx = (uint8_t)size_idx; b.avg = (uint8_t)avg;
-    if (hipMemcpy(buf, &b, sizeof(b), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_qpel(S.dev(0), S.dev(0), DP, S.dev<const FFHipQpelBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_qpel(buf, buf, DP, (const FFHipQpelBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, n - 1, 0, n - 1);
+    S.commit(d, dorg);
     return true;
 }
 static FFHipH264QpelContext g_fb_qpel;
@@ -330,23 +278,17 @@ static bool chroma_single(int avg, int w_idx, uint8_t *dst, const uint8_t *src, 
     const int w = 8 >> w_idx;
     if (h <= 0 || h > 16)
         return false;
-    Rect d = { dst, stride, 0, h - 1, 0, w - 1, nullptr };
-    Rect s = { const_cast<uint8_t *>(src), stride, 0, (y & 7) ? h : h - 1, 0, (x & 7) ? w : w - 1, nullptr };
-    Arena A(rect_bytes(d) + rect_bytes(s) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    if (!rect_up(d, buf + 64) || !rect_up(s, buf + 64 + rect_bytes(d)))
-        return false;
-    FFHipChromaBlock b;
-    memset(&b, 0, sizeof(b));
-    b.dst_offset = (int32_t)(d.dev - buf); b.src_offset = (int32_t)(s.dev - buf);
+    const Rect d = { dst, stride, 0, h - 1, 0, w - 1 };
+    const Rect s = { const_cast<uint8_t *>(src), stride, 0, (y & 7) ? h : h - 1, 0, (x & 7) ? w : w - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipChromaBlock));
+    const ptrdiff_t dorg = S.rect(d), sorg = S.rect(s);
+    FFHipChromaBlock &b = *S.img<FFHipChromaBlock>(hdr);
+    b.dst_offset = (int32_t)dorg; b.src_offset = (int32_t)sorg;
     b.w_idx = (uint8_t)w_idx; b.h = (uint8_t)h; b.x = (uint8_t)x; b.y = (uint8_t)y; b.avg = (uint8_t)avg;
-    if (hipMemcpy(buf, &b, sizeof(b), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_chroma_mc(S.dev(0), S.dev(0), DP, S.dev<const FFHipChromaBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_chroma_mc(buf, buf, DP, (const FFHipChromaBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, h - 1, 0, w - 1);
+    S.commit(d, dorg);
     return true;
 }
 static FFHipH264ChromaContext g_fb_chroma;
@@ -379,24 +321,17 @@ static bool weight_single(int bi, int w_idx, uint8_t *dst, uint8_t *src, ptrdiff
     const int w = 16 >> w_idx;
     if (height <= 0 || height > 16)
         return false;
-    Rect d = { dst, stride, 0, height - 1, 0, w - 1, nullptr };
-    Rect s = { bi ? src : dst, stride, 0, height - 1, 0, w - 1, nullptr };
-    Arena A(rect_bytes(d) + rect_bytes(s) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    if (!rect_up(d, buf + 64) || (bi && !rect_up(s, buf + 64 + rect_bytes(d))))
-        return false;
-    FFHipWeightBlock b;
-    memset(&b, 0, sizeof(b));
-    b.dst_offset = (int32_t)(d.dev - buf); b.src_offset = bi ? (int32_t)(s.dev - buf) : b.dst_offset;
+    const Rect d = { dst, stride, 0, height - 1, 0, w - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipWeightBlock));
+    const ptrdiff_t dorg = S.rect(d), sorg = bi ? S.rect({ src, stride, 0, height - 1, 0, w - 1 }) : dorg;
+    FFHipWeightBlock &b = *S.img<FFHipWeightBlock>(hdr);
+    b.dst_offset = (int32_t)dorg; b.src_offset = (int32_t)sorg;
     b.w_idx = (uint8_t)w_idx; b.height = (uint8_t)height; b.log2_denom = (uint8_t)log2_denom; b.bi = (uint8_t)bi;
     b.weightd = (int16_t)weightd; b.weights = (int16_t)weights; b.offset = (int16_t)offset;
-    if (hipMemcpy(buf, &b, sizeof(b), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_weight(S.dev(0), S.dev(0), DP, S.dev<const FFHipWeightBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_weight(buf, buf, DP, (const FFHipWeightBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, height - 1, 0, w - 1);
+    S.commit(d, dorg);
     return true;
 }
 static FFHipH264WeightContext g_fb_weight;
@@ -432,33 +367,27 @@ static constexpr int hevc_bdi(int bd) { return bd == 8 ? 0 : bd == 10 ? 1 : 2; }
 static FFHipHEVCDSPContext g_fb_hevc[3];
 #define HEVC_FB(BD) g_fb_hevc[hevc_bdi(BD)]
 
-/* layout in scratch: [0,64) the TU record, [64, 64+2*n*n) coefficients, then the picture rectangle */
+/* the TU record, the n x n coefficients, then (add_residual) the picture rectangle */
 static bool hevc_single(int bd, int kind, int log2_size, int16_t *coeffs, int col_limit, uint8_t *dst, ptrdiff_t stride)
 {
     const int n = 1 << log2_size, ps = bd > 8 ? 2 : 1;
     const size_t cbytes = (size_t)n * n * 2;
-    Rect d = { dst, stride, 0, n - 1, 0, n * ps - 1, nullptr };
-    Arena A(64 + cbytes + (dst ? rect_bytes(d) : 0) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    if (hipMemcpy(buf + 64, coeffs, cbytes, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (dst && !rect_up(d, buf + 64 + cbytes))
-        return false;
-    FFHipHevcTU tu;
+    const Rect d = { dst, stride, 0, n - 1, 0, n * ps - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipHevcTU)), co = S.put(coeffs, cbytes);
+    const ptrdiff_t org = dst ? S.rect(d) : -1;
+    FFHipHevcTU &tu = *S.img<FFHipHevcTU>(hdr);
     tu.coeff_offset = 0;
-    tu.dst_offset = dst ? (int32_t)(d.dev - (buf + 64 + cbytes)) : -1;
+    tu.dst_offset = (int32_t)org;
     tu.col_limit = col_limit;
-    if (hipMemcpy(buf, &tu, sizeof(tu), hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_hevc_idct_bd(bd, kind, log2_size, (int16_t *)(buf + 64), dst ? buf + 64 + cbytes : nullptr, DP, (const FFHipHevcTU *)buf, 1, 0) < 0 ||
-        !A.down())
+    if (!S.up() ||
+        ffhip_launch_hevc_idct_bd(bd, kind, log2_size, S.dev<int16_t>(co), dst ? S.dev(0) : nullptr, DP, S.dev<const FFHipHevcTU>(hdr), 1, 0) < 0 ||
+        !S.down())
         return false;
     if (kind != FFHIP_HEVC_ADD_ONLY)
-        memcpy(coeffs, A.host(buf + 64), cbytes);
+        memcpy(coeffs, S.img(co), cbytes);
     if (dst)
-        rect_commit(A, d, 0, n - 1, 0, n * ps - 1);
+        S.commit(d, org);
     return true;
 }
 template <int BD, int IDX> static void s_hevc_idct(int16_t *c, int col_limit)
@@ -475,22 +404,16 @@ static bool hevc_lf_single(int bd, int kind, uint8_t *pix, ptrdiff_t stride, int
 {
     const bool vertical = kind & 1;
     const int ps = bd > 8 ? 2 : 1;
-    Rect d = { pix, stride, vertical ? 0 : -4, vertical ? 7 : 3, vertical ? -4 * ps : 0, vertical ? 4 * ps - 1 : 8 * ps - 1, nullptr };
-    Arena A(rect_bytes(d) + 128);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    if (!rect_up(d, buf + 64))
-        return false;
-    FFHipHevcEdge e;
-    memset(&e, 0, sizeof(e));
-    e.offset = (int32_t)(d.dev - buf); e.kind = (uint8_t)kind; e.beta = (uint8_t)beta;
+    const Rect d = { pix, stride, vertical ? 0 : -4, vertical ? 7 : 3, vertical ? -4 * ps : 0, vertical ? 4 * ps - 1 : 8 * ps - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipHevcEdge));
+    const ptrdiff_t org = S.rect(d);
+    FFHipHevcEdge &e = *S.img<FFHipHevcEdge>(hdr);
+    e.offset = (int32_t)org; e.kind = (uint8_t)kind; e.beta = (uint8_t)beta;
     for (int j = 0; j < 2; j++) { e.tc[j] = (int16_t)tc[j]; e.no_p[j] = no_p[j]; e.no_q[j] = no_q[j]; }
-    if (hipMemcpy(buf, &e, sizeof(e), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_hevc_loop_filter_bd(bd, S.dev(0), DP, S.dev<const FFHipHevcEdge>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_hevc_loop_filter_bd(bd, buf, DP, (const FFHipHevcEdge *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, d.r0, d.r1, d.c0, d.c1);
+    S.commit(d, org);
     return true;
 }
 template <int BD> static void s_hevc_lf_hl(uint8_t *p, ptrdiff_t st, int beta, const int32_t *tc, const uint8_t *np_, const uint8_t *nq)
@@ -508,29 +431,16 @@ static bool hevc_sao_single(int bd, int edge, uint8_t *dst, const uint8_t *src, 
     if (w <= 0 || h <= 0 || w > 64 || h > 64)
         return false;
     const int P = 192, mg = edge ? 1 : 0, ps = bd > 8 ? 2 : 1;
-    Arena A(64 + (size_t)(h + 2) * P * 2 + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *dsrc = buf + 64, *ddst = dsrc + (size_t)(h + 2) * P;
-    const size_t rowb = (size_t)(w + 2 * mg) * ps;
-    if (ss >= (ptrdiff_t)rowb) {
-        if (hipMemcpy2D(dsrc + (size_t)(1 - mg) * P + (1 - mg) * ps, P, src - mg * ss - mg * ps, ss, rowb, h + 2 * mg, hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-    } else {
-        for (int y = -mg; y < h + mg; y++)
-            if (hipMemcpy(dsrc + (size_t)(y + 1) * P + (1 - mg) * ps, src + y * ss - mg * ps, rowb, hipMemcpyHostToDevice) != hipSuccess)
-                return false;
-    }
-    FFHipHevcSao k;
-    memset(&k, 0, sizeof(k));
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipHevcSao)), sv = S.hole((size_t)(h + 2) * P), dv = S.hole((size_t)(h + 2) * P);
+    S.put2d_at(sv + (size_t)(1 - mg) * P + (1 - mg) * ps, P, src - mg * ss - mg * ps, ss, (size_t)(w + 2 * mg) * ps, h + 2 * mg);
+    FFHipHevcSao &k = *S.img<FFHipHevcSao>(hdr);
     k.dst_offset = 0; k.src_offset = P + ps;
     for (int i = 0; i < 5; i++) k.offset_val[i] = off[i];
     k.edge = (uint8_t)edge; k.cls = (uint8_t)cls; k.width = (uint8_t)w; k.height = (uint8_t)h;
-    if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_hevc_sao_bd(bd, S.dev(dv), P, S.dev(sv), P, S.dev<const FFHipHevcSao>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_hevc_sao_bd(bd, ddst, P, dsrc, P, (const FFHipHevcSao *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    commit2d(A, dst, sd, ddst, P, (size_t)w * ps, h);
+    S.get2d(dst, sd, dv, P, (size_t)w * ps, h);
     return true;
 }
 /* the reference's table index of a block width: sao_tab[(FFALIGN(width, 8) >> 3) - 1] (libavcodec/hevc/filter.c) */
@@ -545,52 +455,35 @@ template <int BD> static void s_hevc_sao_edge(uint8_t *d, const uint8_t *s, ptrd
 static bool hevc_mc_single(int bd, int chroma, int uni, void *dst, ptrdiff_t dststride, const uint8_t *src, ptrdiff_t srcstride, int height, int mx,
                            int my, int width, const int16_t *src2 = nullptr, int denom = 0, int wx0 = 0, int wx1 = 0, int ox = 0)
 {
-    if (width <= 0 || height <= 0 || width > 64 || height > 64)
+    if (width <= 0 || height <= 0 || width > 64 || height > 64 || (uni >= 3 && !src2))
         return false;
     const int ps = bd > 8 ? 2 : 1, P = 128 * ps, DPX = 64 * ps, before = chroma ? 1 : 3, after = chroma ? 2 : 4;
-    const size_t sbytes = (size_t)(height + before + after) * P, dbytes = (size_t)height * (uni ? DPX : 128);
     const size_t s2bytes = uni >= 3 ? (size_t)height * 128 : 0;
-    Arena A(64 + sbytes + dbytes + s2bytes + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *dsrc = buf + 64, *ddst = dsrc + sbytes, *dsrc2 = ddst + dbytes;
-    if (s2bytes && (!src2 || hipMemcpy(dsrc2, src2, s2bytes - (size_t)(64 - width) * 2, hipMemcpyHostToDevice) != hipSuccess))
-        return false;
-    {
-        /* only what the reference function of this slot reads: margins exist on an axis only when that axis is filtered */
-        const int by = my ? before : 0, ay = my ? after : 0, bx = mx ? before : 0, ax = mx ? after : 0;
-        const int cols = width + bx + ax, rows = height + by + ay;
-        uint8_t *d0 = dsrc + (size_t)(before - by) * P + (size_t)(before - bx) * ps;
-        const uint8_t *s0 = src - by * srcstride - bx * ps;
-        if (srcstride >= (ptrdiff_t)cols * ps) {
-            if (hipMemcpy2D(d0, P, s0, srcstride, (size_t)cols * ps, rows, hipMemcpyHostToDevice) != hipSuccess)
-                return false;
-        } else {
-            for (int y = 0; y < rows; y++)
-                if (hipMemcpy(d0 + (size_t)y * P, s0 + y * srcstride, (size_t)cols * ps, hipMemcpyHostToDevice) != hipSuccess)
-                    return false;
-        }
-    }
+    Stage S;
+    const size_t hdr = S.hole(uni >= 2 ? sizeof(FFHipHevcMcWBlock) : sizeof(FFHipHevcMcBlock));
+    const size_t sv = S.hole((size_t)(height + before + after) * P), dv = S.hole((size_t)height * (uni ? DPX : 128)), s2 = S.hole(s2bytes);
+    if (s2bytes)
+        memcpy(S.img(s2), src2, s2bytes - (size_t)(64 - width) * 2);
+    /* only what the reference function of this slot reads: margins exist on an axis only when that axis is filtered */
+    const int by = my ? before : 0, ay = my ? after : 0, bx = mx ? before : 0, ax = mx ? after : 0;
+    S.put2d_at(sv + (size_t)(before - by) * P + (size_t)(before - bx) * ps, P, src - by * srcstride - bx * ps, srcstride,
+               (size_t)(width + bx + ax) * ps, height + by + ay);
     if (uni >= 2) {
-        FFHipHevcMcWBlock k = {};
+        FFHipHevcMcWBlock &k = *S.img<FFHipHevcMcWBlock>(hdr);
         k.src_offset = before * P + before * ps;
         k.width = (uint8_t)width; k.height = (uint8_t)height; k.mx = (uint8_t)mx; k.my = (uint8_t)my;
         k.wx0 = (int16_t)wx0; k.wx1 = (int16_t)wx1; k.ox = (int16_t)ox; k.denom = (uint8_t)denom;
-        if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
-            return false;
     } else {
-        FFHipHevcMcBlock k;
+        FFHipHevcMcBlock &k = *S.img<FFHipHevcMcBlock>(hdr);
         k.dst_offset = 0; k.src_offset = before * P + before * ps;
         k.width = (uint8_t)width; k.height = (uint8_t)height; k.mx = (uint8_t)mx; k.my = (uint8_t)my;
-        if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
-            return false;
     }
-    if (ffhip_launch_hevc_mc_bd(bd, chroma, uni, ddst, DPX, dsrc, P, (const int16_t *)dsrc2, buf, 1, 0) < 0 || !A.down())
+    if (!S.up() || ffhip_launch_hevc_mc_bd(bd, chroma, uni, S.dev(dv), DPX, S.dev(sv), P, S.dev<const int16_t>(s2), S.dev(hdr), 1, 0) < 0 || !S.down())
         return false;
     if (uni)
-        commit2d(A, dst, dststride, ddst, DPX, (size_t)width * ps, height);
+        S.get2d(dst, dststride, dv, DPX, (size_t)width * ps, height);
     else
-        commit2d(A, dst, 128, ddst, 128, (size_t)width * 2, height); /* int16 rows of MAX_PB_SIZE = 64 elements */
+        S.get2d(dst, 128, dv, 128, (size_t)width * 2, height); /* int16 rows of MAX_PB_SIZE = 64 elements */
     return true;
 }
 /* table slot of a call: [ff_hevc_pel_weight[width]][!!my][!!mx] (libavcodec/hevc/dsp.c, hevcdec.c) */
@@ -618,14 +511,10 @@ static bool hevc_restore_single(int bd, int variant, uint8_t *dst, const uint8_t
     if (w <= 0 || h <= 0 || w > 64 || h > 64 || c_idx < 0 || c_idx > 2)
         return false;
     const int ps = bd > 8 ? 2 : 1, P = 64 * ps;
-    Arena A(64 + 2 * (size_t)h * P + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *dsrc = buf + 64, *ddst = dsrc + (size_t)h * P;
-    if (hipMemcpy2D(dsrc, P, src, ss, (size_t)w * ps, h, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy2D(ddst, P, dst, sd, (size_t)w * ps, h, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    FFHipHevcSaoRestore k = {};
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipHevcSaoRestore));
+    const size_t sv = S.put2d(src, ss, (size_t)w * ps, h, P), dv = S.put2d(dst, sd, (size_t)w * ps, h, P);
+    FFHipHevcSaoRestore &k = *S.img<FFHipHevcSaoRestore>(hdr);
     k.offset0 = sao->offset_val[c_idx][0];
     k.width = (uint8_t)w; k.height = (uint8_t)h; k.eo = (uint8_t)sao->eo_class[c_idx]; k.variant = (uint8_t)variant;
     for (int i = 0; i < 4; i++) {
@@ -637,11 +526,9 @@ static bool hevc_restore_single(int bd, int variant, uint8_t *dst, const uint8_t
         k.vert_edge = (ve[0] != 0) | (ve[1] != 0) << 1;
         k.horiz_edge = (he[0] != 0) | (he[1] != 0) << 1;
     }
-    if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_hevc_sao_restore_bd(bd, S.dev(dv), P, S.dev(sv), P, S.dev<const FFHipHevcSaoRestore>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_hevc_sao_restore_bd(bd, ddst, P, dsrc, P, (const FFHipHevcSaoRestore *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    commit2d(A, dst, sd, ddst, P, (size_t)w * ps, h);
+    S.get2d(dst, sd, dv, P, (size_t)w * ps, h);
     return true;
 }
 template <int BD, int VAR>
@@ -716,30 +603,24 @@ extern "C" int ff_hevc_dsp_init_hip(FFHipHEVCDSPContext *c, int bit_depth)
 }
 
 /* ---- AVFloatDSPContext ------------------------------------------------------------------------------------ */
-/* operands packed one after another in scratch, each rounded up to 16 bytes */
+/* operands one after another, dst first */
 static bool fdsp_single(int op, float *dst, int dst_n, const float *s0, int n0, const float *s1, int n1, const float *s2, int n2, float mul,
                         int len)
 {
     if (len <= 0)
         return false;
-    const size_t bd = ((size_t)dst_n * 4 + 15) & ~(size_t)15, b0 = ((size_t)n0 * 4 + 15) & ~(size_t)15, b1 = ((size_t)n1 * 4 + 15) & ~(size_t)15,
-                 b2 = ((size_t)n2 * 4 + 15) & ~(size_t)15;
-    Arena A(bd + b0 + b1 + b2 + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    float *dd = (float *)buf, *d0 = (float *)(buf + bd), *d1 = (float *)(buf + bd + b0), *d2 = (float *)(buf + bd + b0 + b1);
     const bool dst_in = op == FFHIP_FDSP_FMAC_SCALAR || op == FFHIP_FDSP_BUTTERFLIES;
-    if ((dst_in && hipMemcpy(dd, dst, (size_t)dst_n * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(d0, s0, (size_t)n0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (s1 && hipMemcpy(d1, s1, (size_t)n1 * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-        (s2 && hipMemcpy(d2, s2, (size_t)n2 * 4, hipMemcpyHostToDevice) != hipSuccess))
+    Stage S;
+    const size_t dd = S.put(dst_in ? dst : nullptr, (size_t)dst_n * 4), d0 = S.put(s0, (size_t)n0 * 4), d1 = S.put(s1, (size_t)n1 * 4),
+                 d2 = S.put(s2, (size_t)n2 * 4);
+    if (!S.up() ||
+        ffhip_launch_fdsp(op, S.dev<float>(dd), 0, S.dev<float>(d0), 0, s1 ? S.dev<float>(d1) : nullptr, 0, s2 ? S.dev<float>(d2) : nullptr, 0, mul,
+                          len, 1, 0) < 0 ||
+        !S.down())
         return false;
-    if (ffhip_launch_fdsp(op, dd, 0, d0, 0, s1 ? d1 : nullptr, 0, s2 ? d2 : nullptr, 0, mul, len, 1, 0) < 0 || !A.down())
-        return false;
-    memcpy(dst, A.host(dd), (size_t)dst_n * 4);
+    memcpy(dst, S.img(dd), (size_t)dst_n * 4);
     if (op == FFHIP_FDSP_BUTTERFLIES)
-        memcpy(const_cast<float *>(s0), A.host(d0), (size_t)n0 * 4);
+        memcpy(const_cast<float *>(s0), S.img(d0), (size_t)n0 * 4);
     return true;
 }
 static FFHipFloatDSPContext g_fb_fdsp;
@@ -776,21 +657,19 @@ static bool cmp_single(int kind, int width, const uint8_t *blk1, const uint8_t *
     }
     /* what the C function of the slot reads: the half-pel forms one more column / row of blk2; sse and nsse stay inside the blocks */
     const int bx = kind == FFHIP_ME_SAD_X2 || kind == FFHIP_ME_SAD_XY2, by = kind == FFHIP_ME_SAD_Y2 || kind == FFHIP_ME_SAD_XY2;
-    Rect a = { const_cast<uint8_t *>(blk1), stride, 0, rows - 1, 0, width - 1, nullptr };
-    Rect b = { const_cast<uint8_t *>(blk2), stride, 0, rows - 1 + by, 0, width - 1 + bx, nullptr };
-    Arena A(rect_bytes(a) + rect_bytes(b) + 64);
-    if (!A.ok)
+    const Rect a = { const_cast<uint8_t *>(blk1), stride, 0, rows - 1, 0, width - 1 };
+    const Rect b = { const_cast<uint8_t *>(blk2), stride, 0, rows - 1 + by, 0, width - 1 + bx };
+    Stage S;
+    const size_t hdr = S.hole(12); /* [0] off1 [1] off2 [2] result */
+    const ptrdiff_t ao = S.rect(a), bo = S.rect(b);
+    S.img<int32_t>(hdr)[0] = (int32_t)ao;
+    S.img<int32_t>(hdr)[1] = (int32_t)bo;
+    if (!S.up())
         return false;
-    uint8_t *buf = A.buf;
-    if (!rect_up(a, buf + 64) || !rect_up(b, buf + 64 + rect_bytes(a)))
+    int32_t *d = S.dev<int32_t>(hdr);
+    if (ffhip_launch_me_cmp(kind, width, kind == FFHIP_ME_SATD ? rows : h, S.dev(0), d, S.dev(0), d + 1, DP, d + 2, 1, 0) < 0 || !S.down())
         return false;
-    const int32_t offs[2] = { (int32_t)(a.dev - buf), (int32_t)(b.dev - buf) };
-    int32_t *d = (int32_t *)buf; /* [0] off1 [1] off2 [2] result */
-    if (hipMemcpy(d, offs, 8, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_me_cmp(kind, width, kind == FFHIP_ME_SATD ? rows : h, buf, d, buf, d + 1, DP, d + 2, 1, 0) < 0 || !A.down())
-        return false;
-    *result = reinterpret_cast<const int32_t *>(A.host(d))[2];
+    *result = S.img<int32_t>(hdr)[2];
     return true;
 }
 static FFHipMECmpContext g_fb_me;
@@ -862,23 +741,14 @@ static bool vp9_itxfm_single(int bd, int tx, int txtp, uint8_t *dst, ptrdiff_t s
 {
     const int n = tx == 4 ? 4 : 4 << tx, ps = bd > 8 ? 2 : 1, P = 64 * ps;
     const size_t cbytes = (size_t)n * n * (bd > 8 ? 4 : 2);
-    Arena A(64 + cbytes + (size_t)n * P + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    uint8_t *dco = buf + 64;
-    uint8_t *ddst = buf + 64 + cbytes;
-    if (hipMemcpy(dco, block, cbytes, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy2D(ddst, P, dst, stride, (size_t)n * ps, n, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    FFHipVp9TU k = {};
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipVp9TU)), co = S.put(block, cbytes), pix = S.put2d(dst, stride, (size_t)n * ps, n, P);
+    FFHipVp9TU &k = *S.img<FFHipVp9TU>(hdr);
     k.txtp = (uint8_t)txtp; k.dc_only = eob == 1;
-    if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_vp9_itxfm_bd(bd, tx, S.dev(co), S.dev(pix), P, S.dev<const FFHipVp9TU>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_vp9_itxfm_bd(bd, tx, dco, ddst, P, (const FFHipVp9TU *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    memcpy(block, A.host(dco), cbytes);
-    commit2d(A, dst, stride, ddst, P, (size_t)n * ps, n);
+    memcpy(block, S.img(co), cbytes);
+    S.get2d(dst, stride, pix, P, (size_t)n * ps, n);
     return true;
 }
 static FFHipVP9ItxfmContext g_fb_vp9itx[3];
@@ -918,25 +788,18 @@ static bool vp9_mc_single(int bd, int width, int filter, int avg, uint8_t *dst, 
     if (h <= 0 || h > 64)
         return false;
     const int ps = bd > 8 ? 2 : 1, P = 128 * ps, DPX = 64 * ps, before = 3, after = 4;
-    const size_t sbytes = (size_t)(h + before + after) * P, dbytes = (size_t)h * DPX;
-    Arena A(64 + sbytes + dbytes + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *dsrc = buf + 64, *ddst = dsrc + sbytes;
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipVp9McBlock)), sv = S.hole((size_t)(h + before + after) * P);
+    const size_t dv = S.put2d(dst, ds, (size_t)width * ps, h, DPX);
     /* only what the reference function of this slot reads: rows / columns beyond the block exist when that axis is filtered */
     const int ry0 = my ? -before : 0, ry1 = my ? h + after : h, cx0 = mx ? -before : 0, cx1 = mx ? width + after : width;
-    if (hipMemcpy2D(dsrc + (size_t)(ry0 + before) * P + (size_t)(before + cx0) * ps, P, src + ry0 * ss + cx0 * ps, ss, (size_t)(cx1 - cx0) * ps,
-                    ry1 - ry0, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy2D(ddst, DPX, dst, ds, (size_t)width * ps, h, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    FFHipVp9McBlock k = {};
+    S.put2d_at(sv + (size_t)(ry0 + before) * P + (size_t)(before + cx0) * ps, P, src + ry0 * ss + cx0 * ps, ss, (size_t)(cx1 - cx0) * ps, ry1 - ry0);
+    FFHipVp9McBlock &k = *S.img<FFHipVp9McBlock>(hdr);
     k.src_offset = before * P + before * ps;
     k.width = (uint8_t)width; k.height = (uint8_t)h; k.filter = (uint8_t)filter; k.mx = (uint8_t)mx; k.my = (uint8_t)my; k.avg = (uint8_t)avg;
-    if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_vp9_mc_bd(bd, S.dev(dv), DPX, S.dev(sv), P, S.dev<const FFHipVp9McBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_vp9_mc_bd(bd, ddst, DPX, dsrc, P, (const FFHipVp9McBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    commit2d(A, dst, ds, ddst, DPX, (size_t)width * ps, h);
+    S.get2d(dst, ds, dv, DPX, (size_t)width * ps, h);
     return true;
 }
 static FFHipVP9McContext g_fb_vp9mc[3];
@@ -972,29 +835,23 @@ static bool vp9_lf_single(int bd, int nseg, const int wd_idx[2], int dir, uint8_
                           const int H[2])
 {
     const int ps = bd > 8 ? 2 : 1, P = 32 * ps, lines = 8 * nseg;
-    Arena A(64 + 32 * P + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *d = buf + 64;
     /* device layout: the edge at column 8 (dir 0: rows = lines) or row 8 (dir 1: columns = lines); only the samples the
      * reference function of this slot touches travel: 8 on either side for the 16-wide filter, 4 otherwise */
     const int r = (wd_idx[0] == 2 || (nseg == 2 && wd_idx[1] == 2)) ? 8 : 4;
     const int rows = dir ? 2 * r : lines, cols = dir ? lines : 2 * r;
-    const uint8_t *h0 = dir ? dst - r * stride : dst - r * ps;
-    uint8_t *dd = dir ? d + (8 - r) * P : d + (8 - r) * ps;
-    if (hipMemcpy2D(dd, P, h0, stride, (size_t)cols * ps, rows, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    FFHipVp9Edge k[2] = {};
+    uint8_t *h0 = dir ? dst - r * stride : dst - r * ps;
+    Stage S;
+    const size_t hdr = S.hole(2 * sizeof(FFHipVp9Edge)), pix = S.hole(32 * P), at = pix + (dir ? (8 - r) * P : (8 - r) * ps);
+    S.put2d_at(at, P, h0, stride, (size_t)cols * ps, rows);
+    FFHipVp9Edge *k = S.img<FFHipVp9Edge>(hdr);
     for (int sgm = 0; sgm < nseg; sgm++) {
         k[sgm].offset = dir ? 8 * P + 8 * sgm * ps : 8 * sgm * P + 8 * ps;
         k[sgm].wd_idx = (uint8_t)wd_idx[sgm]; k[sgm].dir = (uint8_t)dir;
         k[sgm].E = (uint8_t)E[sgm]; k[sgm].I = (uint8_t)I[sgm]; k[sgm].H = (uint8_t)H[sgm];
     }
-    if (hipMemcpy(buf, k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_vp9_loop_filter_bd(bd, S.dev(pix), P, S.dev<const FFHipVp9Edge>(hdr), nseg, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_vp9_loop_filter_bd(bd, d, P, (const FFHipVp9Edge *)buf, nseg, 0) < 0 || !A.down())
-        return false;
-    commit2d(A, (uint8_t *)h0, stride, dd, P, (size_t)cols * ps, rows);
+    S.get2d(h0, stride, at, P, (size_t)cols * ps, rows);
     return true;
 }
 static FFHipVP9LoopFilterContext g_fb_vp9lf[3];
@@ -1054,17 +911,13 @@ static bool vp9_intra_gpu(uint8_t *dst, ptrdiff_t stride, const uint8_t *left, c
     if (use_tl) memcpy(e + N * PS, top - PS, PS);
     if (use_top) memcpy(e + (N + 1) * PS, top, ntop * PS);
     constexpr int P = 32 * PS;
-    Arena A(64 + 256 + (size_t)N * P + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *de = buf + 64, *dd = de + 256;
     FFHipVp9Intra k = {};
     k.mode = MODE;
-    if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(de, e, sizeof(e), hipMemcpyHostToDevice) != hipSuccess)
+    Stage S;
+    const size_t hdr = S.put(&k, sizeof(k)), de = S.put(e, sizeof(e)), pix = S.hole((size_t)N * P);
+    if (!S.up() || ffhip_launch_vp9_intra_bd(BD, TX, S.dev(pix), P, S.dev(de), S.dev<const FFHipVp9Intra>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_vp9_intra_bd(BD, TX, dd, P, de, (const FFHipVp9Intra *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    commit2d(A, dst, stride, dd, P, (size_t)N * PS, N);
+    S.get2d(dst, stride, pix, P, (size_t)N * PS, N);
     return true;
 }
 template <int BD, int TX, int MODE>
@@ -1098,22 +951,15 @@ static bool vp9_smc_gpu(uint8_t *dst, ptrdiff_t ds, const uint8_t *src, ptrdiff_
     constexpr int PS = BD > 8 ? 2 : 1;
     const int P = 192 * PS, DPX = 64 * PS, bil = F == 3, before = bil ? 0 : 3, after = bil ? 1 : 4;
     const int cols = ((mx + (W - 1) * dx) >> 4) + 1 + before + after, rows = ((my + (h - 1) * dy) >> 4) + 1 + before + after;
-    const size_t sbytes = (size_t)rows * P, dbytes = (size_t)h * DPX;
-    Arena A(64 + sbytes + dbytes + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *dsrc = buf + 64, *ddst = dsrc + sbytes;
-    if (hipMemcpy2D(dsrc, P, src - before * ss - before * PS, ss, (size_t)cols * PS, rows, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy2D(ddst, DPX, dst, ds, (size_t)W * PS, h, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    FFHipVp9ScaledBlock k = {};
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipVp9ScaledBlock)), sv = S.put2d(src - before * ss - before * PS, ss, (size_t)cols * PS, rows, P);
+    const size_t dv = S.put2d(dst, ds, (size_t)W * PS, h, DPX);
+    FFHipVp9ScaledBlock &k = *S.img<FFHipVp9ScaledBlock>(hdr);
     k.src_offset = before * P + before * PS;
     k.width = W; k.height = (uint8_t)h; k.filter = F; k.mx = (uint8_t)mx; k.my = (uint8_t)my; k.avg = AVG; k.dx = (uint8_t)dx; k.dy = (uint8_t)dy;
-    if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_vp9_smc_bd(BD, S.dev(dv), DPX, S.dev(sv), P, S.dev<const FFHipVp9ScaledBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_vp9_smc_bd(BD, ddst, DPX, dsrc, P, (const FFHipVp9ScaledBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    commit2d(A, dst, ds, ddst, DPX, (size_t)W * PS, h);
+    S.get2d(dst, ds, dv, DPX, (size_t)W * PS, h);
     return true;
 }
 template <int BD, int W, int I, int F, int AVG>
@@ -1148,8 +994,10 @@ static bool h264_pred_host(int bd, int kind, int mode, int n, unsigned need, int
     if (!nh)
         nh = n; /* rows of the block (8 x 16: n = 8 columns, nh = 16) */
     const int px = bd > 8 ? 2 : 1;
-    uint8_t st[17 * HP_P] = { 0 };
-    uint8_t *o = st + HP_P + 16;
+    const bool k4 = kind == FFHIP_H264_PRED4x4 || (kind == FFHIP_H264_PRED_CODEC && n == 4); /* the 4x4 kinds take a topright pointer */
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipH264Pred)), pv = S.hole(17 * HP_P);
+    uint8_t *o = S.img(pv + HP_P + 16);
     if (need & 1)
         for (int y = 0; y < lrows; y++)
             memcpy(o + y * HP_P - px, src + y * stride - px, px);
@@ -1164,29 +1012,20 @@ static bool h264_pred_host(int bd, int kind, int mode, int n, unsigned need, int
     }
     if (need & 4)
         memcpy(o - HP_P - px, src - stride - px, px);
-    const bool k4 = kind == FFHIP_H264_PRED4x4 || (kind == FFHIP_H264_PRED_CODEC && n == 4); /* the 4x4 kinds take a topright pointer */
     if (k4 && (need & 8))
         memcpy(o - HP_P + 32, topright, 4 * px); /* wherever the caller's pointer leads, the record addresses the staged copy */
-    const int ncoef = block ? n * n * px : 0; /* in int16 units: int32 coefficients above 8 bits */
-    Arena A(64 + sizeof(st) + 256 + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf, *dp = buf + 64;
-    int16_t *dc = (int16_t *)(dp + sizeof(st));
-    FFHipH264Pred k = {};
+    const size_t ncoef = block ? (size_t)n * n * px : 0; /* in int16 units: int32 coefficients above 8 bits */
+    const size_t dc = S.put(block, ncoef * sizeof(int16_t));
+    FFHipH264Pred &k = *S.img<FFHipH264Pred>(hdr);
     k.offset = HP_P + 16;
     k.aux = k4 ? 16 + 32 : 0; /* where topright[] was staged: row 0 of the patch */
     k.mode = (uint8_t)mode;
     k.flags = (uint8_t)((has_tl ? FFHIP_H264_PRED_TOPLEFT : 0) | (has_tr ? FFHIP_H264_PRED_TOPRIGHT : 0));
-    if (hipMemcpy(buf, &k, sizeof(k), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dp, st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_pred_bd(bd, kind, S.dev(pv), HP_P, S.dev<int16_t>(dc), S.dev<const FFHipH264Pred>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ncoef && hipMemcpy(dc, block, ncoef * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_h264_pred_bd(bd, kind, dp, HP_P, dc, (const FFHipH264Pred *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    commit2d(A, src, stride, dp + HP_P + 16, HP_P, (size_t)n * px, nh);
+    S.get2d(src, stride, pv + HP_P + 16, HP_P, (size_t)n * px, nh);
     if (ncoef)
-        memcpy(block, A.host(dc), ncoef * sizeof(int16_t)); /* cleared by the kernel */
+        memcpy(block, S.img(dc), ncoef * sizeof(int16_t)); /* cleared by the kernel */
     return true;
 }
 /* the C functions our faces displaced, per depth; F = 1: the 4:2:2 forms of pred8x8[] / pred8x8_add[] (a 4:2:0 and a 4:2:2 context of

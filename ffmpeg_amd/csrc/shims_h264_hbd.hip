@@ -13,7 +13,7 @@
 
 #include "kernels/common.h"
 #include "kernels/h264_kernels.h"
-#include "kernels/shim_rect.h"
+#include "kernels/shim_arena.h"
 
 namespace {
 
@@ -40,21 +40,14 @@ template <int BD>
 bool idct_single(int kind, uint8_t *dst, int16_t *block, ptrdiff_t stride)
 {
     const int size = (kind & 1) ? 8 : 4, cbytes = size * size * 2 * PX(BD);
-    Rect d = { dst, stride, 0, size - 1, 0, size * PX(BD) - 1, nullptr };
-    Arena A(rect_bytes(d) + 512 + 64);
-    if (!A.ok)
+    const Rect d = { dst, stride, 0, size - 1, 0, size * PX(BD) - 1 };
+    Stage S;
+    const size_t blk = S.put(block, cbytes), off = S.hole(4); /* off: a zero block offset */
+    const ptrdiff_t pix = S.rect(d);
+    if (!S.up() || ffhip_launch_h264_idct_add_bd(BD, kind, S.dev(pix), DP, S.dev<int32_t>(off), S.dev<int16_t>(blk), 1, 0) < 0 || !S.down())
         return false;
-    uint8_t *buf = A.buf;
-    int16_t *dblk = (int16_t *)buf;
-    int32_t *doff = (int32_t *)(buf + 256);
-    const int32_t zero = 0;
-    if (!rect_up(d, buf + 512) || hipMemcpy(dblk, block, cbytes, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(doff, &zero, 4, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_h264_idct_add_bd(BD, kind, d.dev, DP, doff, dblk, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, size - 1, 0, size * PX(BD) - 1);
-    memcpy(block, A.host(dblk), cbytes);
+    S.commit(d, pix);
+    memcpy(block, S.img(blk), cbytes);
     return true;
 }
 
@@ -74,7 +67,7 @@ bool idct_mb(int which, uint8_t *const *planes, const int *blockoffset, int16_t 
             for (int r = 0; r < (which == 3 ? 4 : 8); r++)
                 slots[j][nslot[j]++] = 16 * (j + 1) + r + (r >= 4 ? 4 : 0);
     int lo[2], hi[2];
-    size_t span[2] = { 0, 0 }, sp[2] = { 0, 0 };
+    int32_t bo[48] = { 0 };
     for (int j = 0; j < npl; j++) {
         lo[j] = hi[j] = blockoffset[slots[j][0]];
         for (int k = 0; k < nslot[j]; k++) {
@@ -82,38 +75,26 @@ bool idct_mb(int which, uint8_t *const *planes, const int *blockoffset, int16_t 
             if (o < lo[j]) lo[j] = o;
             if (o > hi[j]) hi[j] = o;
         }
-        span[j] = (size_t)(hi[j] - lo[j]) + (size_t)(bs - 1) * stride + (size_t)bs * PX(BD);
-        sp[j] = (span[j] + 63) & ~(size_t)63;
-    }
-    Arena A(3072 + 256 + 128 + 64 + sp[0] + sp[1] + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    int16_t *dblk = (int16_t *)buf;              /* <= 3072 B */
-    int32_t *dbo = (int32_t *)(buf + 3072);      /* 192 B    */
-    uint8_t *dnn = buf + 3072 + 256;             /* 120 B    */
-    int32_t *dmb = (int32_t *)(buf + 3072 + 256 + 128);
-    uint8_t *dpix[2] = { buf + 3072 + 256 + 128 + 64, buf + 3072 + 256 + 128 + 64 + sp[0] };
-    const int32_t mboff = 0;
-    int32_t bo[48] = { 0 };
-    for (int j = 0; j < npl; j++)
         for (int k = 0; k < nslot[j]; k++)
             bo[slots[j][k]] = blockoffset[slots[j][k]] - lo[j];
+    }
+    Stage S;
+    const size_t blk = S.put(block, ncoef_bytes), dbo = S.put(bo, 192), nn = S.put(nnzc, nnz_bytes), mb = S.hole(4);
+    size_t pix[2] = { 0, 0 }; /* one plane: the second is not read */
     for (int j = 0; j < npl; j++)
-        if (hipMemcpy(dpix[j], planes[j] + lo[j], span[j], hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-    if (hipMemcpy(dblk, block, ncoef_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dbo, bo, 192, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dnn, nnzc, nnz_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dmb, &mboff, 4, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_h264_idct_mb_bd(BD, which, dpix[0], dpix[1], stride, dmb, dbo, dblk, dnn, 1, 0) < 0 || !A.down())
+        pix[j] = S.put(planes[j] + lo[j], (size_t)(hi[j] - lo[j]) + (size_t)(bs - 1) * stride + (size_t)bs * PX(BD));
+    if (!S.up() ||
+        ffhip_launch_h264_idct_mb_bd(BD, which, S.dev(pix[0]), S.dev(pix[1]), stride, S.dev<int32_t>(mb), S.dev<int32_t>(dbo), S.dev<int16_t>(blk),
+                                     S.dev(nn), 1, 0) < 0 ||
+        !S.down())
         return false;
     for (int j = 0; j < npl; j++)
         for (int k = 0; k < nslot[j]; k++) /* only this macroblock's own blocks travel back */
-            commit2d(A, planes[j] + blockoffset[slots[j][k]], stride, dpix[j] + bo[slots[j][k]], stride, (size_t)bs * PX(BD), bs);
+            S.get2d(planes[j] + blockoffset[slots[j][k]], stride, pix[j] + bo[slots[j][k]], stride, (size_t)bs * PX(BD), bs);
     if (which >= 3)
-        memcpy((uint8_t *)block + 256 * 2 * PX(BD), A.host((uint8_t *)dblk + 256 * 2 * PX(BD)), 512 * 2 * PX(BD)); /* the chroma planes' coefficients */
+        memcpy((uint8_t *)block + 256 * 2 * PX(BD), S.img(blk + 256 * 2 * PX(BD)), 512 * 2 * PX(BD)); /* the chroma planes' coefficients */
     else
-        memcpy(block, A.host(dblk), ncoef_bytes);
+        memcpy(block, S.img(blk), ncoef_bytes);
     return true;
 }
 
@@ -122,26 +103,18 @@ template <int BD>
 bool dc_dequant(int which, int16_t *output, int16_t *input, int qmul)
 {
     const int cb = 2 * PX(BD); /* bytes per coefficient */
-    Arena A(1024 + 128 + 64 + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    int16_t *dout = (int16_t *)buf, *din = (int16_t *)(buf + 1024);
-    int32_t *dq = (int32_t *)(buf + 1152), *doff = (int32_t *)(buf + 1184);
-    const int32_t q = qmul, zero = 0;
-    if (hipMemcpy(dq, &q, 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(doff, &zero, 4, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
     const int nout = which == 0 ? 256 : which == 1 ? 64 : 128; /* coefficients the function's writes span */
-    if (which == 0 && hipMemcpy(din, input, 16 * cb, hipMemcpyHostToDevice) != hipSuccess)
+    const int32_t q = qmul;
+    Stage S;
+    const size_t out = S.put(output, (size_t)nout * cb), in = S.put(which == 0 ? input : nullptr, 16 * cb), dq = S.put(&q, 4), off = S.hole(4);
+    if (!S.up() ||
+        ffhip_launch_h264_dc_dequant_bd(BD, which, S.dev<int16_t>(out), 256, S.dev<int16_t>(in), 16, S.dev<int32_t>(off), S.dev<int32_t>(dq), 1, 0) < 0 ||
+        !S.down())
         return false;
-    if (hipMemcpy(dout, output, (size_t)nout * cb, hipMemcpyHostToDevice) != hipSuccess ||
-        ffhip_launch_h264_dc_dequant_bd(BD, which, dout, 256, din, 16, doff, dq, 1, 0) < 0 || !A.down())
-        return false;
-    const uint8_t *h = A.host(dout);
     /* the DC positions are all the function writes: 16 (luma), 4 (4:2:0: blocks 0..3), 8 (4:2:2: blocks 0..7) */
     const int nblk = which == 0 ? 16 : which == 1 ? 4 : 8;
     for (int i = 0; i < nblk; i++)
-        memcpy((uint8_t *)output + (size_t)16 * i * cb, h + (size_t)16 * i * cb, cb);
+        memcpy((uint8_t *)output + (size_t)16 * i * cb, S.img(out + (size_t)16 * i * cb), cb);
     return true;
 }
 
@@ -152,25 +125,20 @@ bool lf_single(int kind, int inner, uint8_t *pix, ptrdiff_t stride, int alpha, i
     const bool chroma = kind & 2, vert_edge = kind & 1;
     const int along = 4 * inner, across = chroma ? 2 : 4; /* lines; samples read each side of the edge */
     const int px = PX(BD);
-    Rect r = { pix, stride, vert_edge ? 0 : -across, vert_edge ? along - 1 : across - 1,
-               vert_edge ? -across * px : 0, vert_edge ? across * px - 1 : along * px - 1, nullptr };
-    Arena A(rect_bytes(r) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    FFHipH264Edge e;
-    memset(&e, 0, sizeof(e));
+    const Rect r = { pix, stride, vert_edge ? 0 : -across, vert_edge ? along - 1 : across - 1,
+                     vert_edge ? -across * px : 0, vert_edge ? across * px - 1 : along * px - 1 };
+    const int32_t ab[2] = { alpha, beta }; /* the caller's ints as they are: the C function takes any (it scales them by the depth itself) */
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipH264Edge)), dab = S.put(ab, sizeof(ab));
+    const ptrdiff_t org = S.rect(r);
+    FFHipH264Edge &e = *S.img<FFHipH264Edge>(hdr);
     e.kind = (uint8_t)kind;
     e.pad = (uint8_t)inner;
-    const int32_t ab[2] = { alpha, beta }; /* the caller's ints as they are: the C function takes any (it scales them by the depth itself) */
     if (tc0)
         memcpy(e.tc0, tc0, 4);
-    if (!rect_up(r, buf + 64) || hipMemcpy(buf, &e, sizeof(e), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(buf + 16, ab, sizeof(ab), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_loop_filter_bd(BD, S.dev(org), DP, S.dev<const FFHipH264Edge>(hdr), 1, 0, S.dev<const int32_t>(dab)) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_loop_filter_bd(BD, r.dev, DP, (const FFHipH264Edge *)buf, 1, 0, (const int32_t *)(buf + 16)) < 0 || !A.down())
-        return false;
-    rect_commit(A, r, r.r0, r.r1, r.c0, r.c1);
+    S.commit(r, org);
     return true;
 }
 
@@ -179,26 +147,20 @@ template <int BD>
 bool qpel_single(int avg, int size_idx, int mcxy, uint8_t *dst, const uint8_t *src, ptrdiff_t stride)
 {
     const int n = 16 >> size_idx, px = PX(BD);
-    Rect d = { dst, stride, 0, n - 1, 0, n * px - 1, nullptr };
+    const Rect d = { dst, stride, 0, n - 1, 0, n * px - 1 };
     const bool fx = mcxy & 3, fy = mcxy >> 2; /* the 6-tap margin exists on an axis only when that axis is filtered */
-    Rect s = { const_cast<uint8_t *>(src), stride, fy ? -2 : 0, fy ? n + 2 : n - 1, fx ? -2 * px : 0, fx ? (n + 3) * px - 1 : n * px - 1, nullptr };
-    Rect full = s;
-    full.r0 = -2; full.r1 = n + 2; full.c0 = -2 * px; full.c1 = (n + 3) * px - 1;
-    Arena A(rect_bytes(d) + rect_bytes(full) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    if (!rect_up(d, buf + 64) || !rect_up(s, buf + 64 + rect_bytes(d) + (size_t)(s.r0 + 2) * DP + (s.c0 + 2 * px)))
-        return false;
-    FFHipQpelBlock b;
-    memset(&b, 0, sizeof(b));
-    b.dst_offset = (int32_t)(d.dev - buf); b.src_offset = (int32_t)(s.dev - buf);
+    const Rect s = { const_cast<uint8_t *>(src), stride, fy ? -2 : 0, fy ? n + 2 : n - 1, fx ? -2 * px : 0, fx ? (n + 3) * px - 1 : n * px - 1 };
+    const Rect full = { s.host, stride, -2, n + 2, -2 * px, (n + 3) * px - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipQpelBlock));
+    const ptrdiff_t dorg = S.rect(d), sorg = S.area(full);
+    S.fill(s, sorg);
+    FFHipQpelBlock &b = *S.img<FFHipQpelBlock>(hdr);
+    b.dst_offset = (int32_t)dorg; b.src_offset = (int32_t)sorg;
     b.mcxy = (uint8_t)mcxy; b.size_idx = (uint8_t)size_idx; b.avg = (uint8_t)avg;
-    if (hipMemcpy(buf, &b, sizeof(b), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_qpel_bd(BD, S.dev(0), S.dev(0), DP, S.dev<const FFHipQpelBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_qpel_bd(BD, buf, buf, DP, (const FFHipQpelBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, n - 1, 0, n * px - 1);
+    S.commit(d, dorg);
     return true;
 }
 
@@ -209,25 +171,19 @@ bool chroma_single(int avg, int w_idx, uint8_t *dst, const uint8_t *src, ptrdiff
     const int w = 8 >> w_idx, px = PX(BD);
     if (h <= 0 || h > 16 || (unsigned)x > 7u || (unsigned)y > 7u)
         return false;
-    Rect d = { dst, stride, 0, h - 1, 0, w * px - 1, nullptr };
-    Rect s = { const_cast<uint8_t *>(src), stride, 0, h - 1 + (y ? 1 : 0), 0, (w + (x ? 1 : 0)) * px - 1, nullptr };
-    Rect full = s;
-    full.r1 = h; full.c1 = (w + 1) * px - 1;
-    Arena A(rect_bytes(d) + rect_bytes(full) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    if (!rect_up(d, buf + 64) || !rect_up(s, buf + 64 + rect_bytes(d)))
-        return false;
-    FFHipChromaBlock b;
-    memset(&b, 0, sizeof(b));
-    b.dst_offset = (int32_t)(d.dev - buf); b.src_offset = (int32_t)(s.dev - buf);
+    const Rect d = { dst, stride, 0, h - 1, 0, w * px - 1 };
+    const Rect s = { const_cast<uint8_t *>(src), stride, 0, h - 1 + (y ? 1 : 0), 0, (w + (x ? 1 : 0)) * px - 1 };
+    const Rect full = { s.host, stride, 0, h, 0, (w + 1) * px - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipChromaBlock));
+    const ptrdiff_t dorg = S.rect(d), sorg = S.area(full);
+    S.fill(s, sorg);
+    FFHipChromaBlock &b = *S.img<FFHipChromaBlock>(hdr);
+    b.dst_offset = (int32_t)dorg; b.src_offset = (int32_t)sorg;
     b.w_idx = (uint8_t)w_idx; b.h = (uint8_t)h; b.x = (uint8_t)x; b.y = (uint8_t)y; b.avg = (uint8_t)avg;
-    if (hipMemcpy(buf, &b, sizeof(b), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_chroma_mc_bd(BD, S.dev(0), S.dev(0), DP, S.dev<const FFHipChromaBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_chroma_mc_bd(BD, buf, buf, DP, (const FFHipChromaBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, h - 1, 0, w * px - 1);
+    S.commit(d, dorg);
     return true;
 }
 
@@ -237,24 +193,17 @@ bool weight_single(int bi, int w_idx, uint8_t *dst, uint8_t *src, ptrdiff_t stri
     const int w = 16 >> w_idx, px = PX(BD);
     if (height <= 0 || height > 16 || log2_denom < 0 || log2_denom > 7)
         return false;
-    Rect d = { dst, stride, 0, height - 1, 0, w * px - 1, nullptr };
-    Rect s = { bi ? src : dst, stride, 0, height - 1, 0, w * px - 1, nullptr };
-    Arena A(rect_bytes(d) + rect_bytes(s) + 64);
-    if (!A.ok)
-        return false;
-    uint8_t *buf = A.buf;
-    if (!rect_up(d, buf + 64) || (bi && !rect_up(s, buf + 64 + rect_bytes(d))))
-        return false;
-    FFHipWeightBlock b;
-    memset(&b, 0, sizeof(b));
-    b.dst_offset = (int32_t)(d.dev - buf); b.src_offset = bi ? (int32_t)(s.dev - buf) : b.dst_offset;
+    const Rect d = { dst, stride, 0, height - 1, 0, w * px - 1 };
+    Stage S;
+    const size_t hdr = S.hole(sizeof(FFHipWeightBlock));
+    const ptrdiff_t dorg = S.rect(d), sorg = bi ? S.rect({ src, stride, 0, height - 1, 0, w * px - 1 }) : dorg;
+    FFHipWeightBlock &b = *S.img<FFHipWeightBlock>(hdr);
+    b.dst_offset = (int32_t)dorg; b.src_offset = (int32_t)sorg;
     b.w_idx = (uint8_t)w_idx; b.height = (uint8_t)height; b.log2_denom = (uint8_t)log2_denom; b.bi = (uint8_t)bi;
     b.weightd = (int16_t)weightd; b.weights = (int16_t)weights; b.offset = (int16_t)offset;
-    if (hipMemcpy(buf, &b, sizeof(b), hipMemcpyHostToDevice) != hipSuccess)
+    if (!S.up() || ffhip_launch_h264_weight_bd(BD, S.dev(0), S.dev(0), DP, S.dev<const FFHipWeightBlock>(hdr), 1, 0) < 0 || !S.down())
         return false;
-    if (ffhip_launch_h264_weight_bd(BD, buf, buf, DP, (const FFHipWeightBlock *)buf, 1, 0) < 0 || !A.down())
-        return false;
-    rect_commit(A, d, 0, height - 1, 0, w * px - 1);
+    S.commit(d, dorg);
     return true;
 }
 

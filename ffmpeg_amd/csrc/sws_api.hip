@@ -2741,7 +2741,7 @@ extern "C" int ffhip_sws_yuv2planeX8_dev(const int16_t *filter, int filterSize, 
 }
 
 /* ---- signature-exact per-line host faces (swscale_internal.h:128-266, 648-653; installed by ff_sws_init_swscale_<arch>(),
- * swscale.c:697-714): what tests/checkasm/sw_scale.c exercises.  One call = one launch through the scratch arena; a call that
+ * swscale.c:697-714): what tests/checkasm/sw_scale.c exercises.  One call = one launch through a Stage; a call that
  * cannot run on the device is answered by the displaced C function (kernels/shim_arena.h). -------------------------------- */
 static FFHipSwsLineContext g_fb_line;
 
@@ -2755,19 +2755,14 @@ static bool hscale_line_gpu(int16_t *dst, int dstW, const uint8_t *src, const in
             return false;
         else if (filterPos[i] + filterSize > span)
             span = filterPos[i] + filterSize;
-    const size_t bs = ((size_t)span + 63) & ~(size_t)63, bf = ((size_t)dstW * filterSize * 2 + 63) & ~(size_t)63;
-    const size_t bp = ((size_t)dstW * 4 + 63) & ~(size_t)63, bd = ((size_t)dstW * 2 + 63) & ~(size_t)63;
-    Arena A(bs + bf + bp + bd);
-    if (!A.ok)
+    Stage S;
+    const size_t ds = S.put(src, span), df = S.put(filter, (size_t)dstW * filterSize * 2), dp = S.put(filterPos, (size_t)dstW * 4);
+    const size_t dd = S.hole((size_t)dstW * 2);
+    if (!S.up() ||
+        ffhip_launch_hscale8to15(S.dev<int16_t>(dd), dstW, 0, S.dev(ds), 0, 1, S.dev<const int16_t>(df), S.dev<const int32_t>(dp), filterSize, 0) < 0 ||
+        !S.down())
         return false;
-    uint8_t *dsrc = A.buf, *df = dsrc + bs, *dp = df + bf, *dd = dp + bp;
-    if (hipMemcpy(dsrc, src, span, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(df, filter, (size_t)dstW * filterSize * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dp, filterPos, (size_t)dstW * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return false;
-    if (ffhip_launch_hscale8to15((int16_t *)dd, dstW, 0, dsrc, 0, 1, (const int16_t *)df, (const int32_t *)dp, filterSize, 0) < 0 || !A.down())
-        return false;
-    memcpy(dst, A.host(dd), (size_t)dstW * 2);
+    memcpy(dst, S.img(dd), (size_t)dstW * 2);
     return true;
 }
 static void s_hyscale(void *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
@@ -2775,12 +2770,15 @@ static void s_hyscale(void *c, int16_t *dst, int dstW, const uint8_t *src, const
 static void s_hcscale(void *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 { if (!hscale_line_gpu(dst, dstW, src, filter, filterPos, filterSize)) SHIM_FB(g_fb_line, hcScale, c, dst, dstW, src, filter, filterPos, filterSize); }
 
-/* nsrc int16 lines of n samples each, packed at a pitch of `pitch` bytes from `at` */
-static bool lines_up(uint8_t *at, size_t pitch, const int16_t *const *src, int nsrc, int n)
+/* nsrc int16 lines of n samples each, one slot at a pitch of `pitch` bytes; false when a line is missing */
+static bool put_lines(Stage &S, size_t &at, size_t pitch, const int16_t *const *src, int nsrc, int n)
 {
-    for (int j = 0; j < nsrc; j++)
-        if (!src[j] || hipMemcpy(at + j * pitch, src[j], (size_t)n * 2, hipMemcpyHostToDevice) != hipSuccess)
+    at = S.hole(pitch * nsrc);
+    for (int j = 0; j < nsrc; j++) {
+        if (!src[j])
             return false;
+        memcpy(S.img(at + j * pitch), src[j], (size_t)n * 2);
+    }
     return true;
 }
 
@@ -2789,17 +2787,18 @@ static bool planex_line_gpu(const int16_t *filter, int filterSize, const int16_t
 {
     if (dstW <= 0 || filterSize <= 0 || filterSize > 256 || !dither)
         return false;
-    const size_t pitch = ((size_t)dstW * 2 + 63) & ~(size_t)63, bd = ((size_t)dstW + 63) & ~(size_t)63;
-    Arena A(64 + 512 + pitch * filterSize + bd);
-    if (!A.ok)
+    const size_t pitch = ((size_t)dstW * 2 + 63) & ~(size_t)63;
+    Stage S;
+    const size_t ddi = S.put(dither, 8), df = S.put(filter, (size_t)filterSize * 2);
+    size_t dl;
+    if (!put_lines(S, dl, pitch, src, filterSize, dstW))
         return false;
-    uint8_t *ddi = A.buf, *df = ddi + 64, *dl = df + 512, *dd = dl + pitch * filterSize;
-    if (hipMemcpy(ddi, dither, 8, hipMemcpyHostToDevice) != hipSuccess ||
-        (filter && hipMemcpy(df, filter, (size_t)filterSize * 2, hipMemcpyHostToDevice) != hipSuccess) || !lines_up(dl, pitch, src, filterSize, dstW))
+    const size_t dd = S.hole(dstW);
+    if (!S.up() ||
+        ffhip_launch_yuv2planeX8(S.dev<const int16_t>(df), filterSize, S.dev<const int16_t>(dl), (ptrdiff_t)pitch, S.dev(dd), dstW, S.dev(ddi), offset, 0) < 0 ||
+        !S.down())
         return false;
-    if (ffhip_launch_yuv2planeX8((const int16_t *)df, filterSize, (const int16_t *)dl, (ptrdiff_t)pitch, dd, dstW, ddi, offset, 0) < 0 || !A.down())
-        return false;
-    memcpy(dest, A.host(dd), dstW);
+    memcpy(dest, S.img(dd), dstW);
     return true;
 }
 static void s_yuv2plane1(const int16_t *src, uint8_t *dest, int dstW, const uint8_t *dither, int offset)
@@ -2825,19 +2824,19 @@ static bool nv12cx_line_gpu(int dstFormat, const uint8_t *chrDither, const int16
 {
     if (chrDstW <= 0 || chrFilterSize <= 0 || chrFilterSize > 256 || !fmt_nv(dstFormat) || !chrDither || !chrFilter)
         return false;
-    const size_t pitch = ((size_t)chrDstW * 2 + 63) & ~(size_t)63, bd = ((size_t)chrDstW * 2 + 63) & ~(size_t)63;
-    Arena A(64 + 512 + 2 * pitch * chrFilterSize + bd);
-    if (!A.ok)
+    const size_t pitch = ((size_t)chrDstW * 2 + 63) & ~(size_t)63;
+    Stage S;
+    const size_t ddi = S.put(chrDither, 8), df = S.put(chrFilter, (size_t)chrFilterSize * 2);
+    size_t du, dv;
+    if (!put_lines(S, du, pitch, chrUSrc, chrFilterSize, chrDstW) || !put_lines(S, dv, pitch, chrVSrc, chrFilterSize, chrDstW))
         return false;
-    uint8_t *ddi = A.buf, *df = ddi + 64, *du = df + 512, *dv = du + pitch * chrFilterSize, *dd = dv + pitch * chrFilterSize;
-    if (hipMemcpy(ddi, chrDither, 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(df, chrFilter, (size_t)chrFilterSize * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        !lines_up(du, pitch, chrUSrc, chrFilterSize, chrDstW) || !lines_up(dv, pitch, chrVSrc, chrFilterSize, chrDstW))
+    const size_t dd = S.hole((size_t)chrDstW * 2);
+    if (!S.up() ||
+        ffhip_launch_yuv2nv12cX(dstFormat == FFHIP_PIX_FMT_NV21, S.dev(ddi), S.dev<const int16_t>(df), chrFilterSize, S.dev<const int16_t>(du),
+                                S.dev<const int16_t>(dv), (ptrdiff_t)pitch, S.dev(dd), chrDstW, 0) < 0 ||
+        !S.down())
         return false;
-    if (ffhip_launch_yuv2nv12cX(dstFormat == FFHIP_PIX_FMT_NV21, ddi, (const int16_t *)df, chrFilterSize, (const int16_t *)du, (const int16_t *)dv,
-                                (ptrdiff_t)pitch, dd, chrDstW, 0) < 0 || !A.down())
-        return false;
-    memcpy(dest, A.host(dd), (size_t)chrDstW * 2);
+    memcpy(dest, S.img(dd), (size_t)chrDstW * 2);
     return true;
 }
 static void s_yuv2nv12cx(int dstFormat, const uint8_t *chrDither, const int16_t *chrFilter, int chrFilterSize, const int16_t **chrUSrc,
@@ -2877,19 +2876,19 @@ static int packed_line(FFHipSwsContext *c, int mode, const int16_t *lf, const in
         return FFHIP_EINVAL;
     FFHipDeviceGuard dg(c->device);
     const int lay = rgb_layout(c->t.dstFormat), bpp = lay < 2 ? 3 : 4, cw = dstW >> 1;
-    const size_t pitch = ((size_t)dstW * 2 + 63) & ~(size_t)63, bd = ((size_t)dstW * bpp + 63) & ~(size_t)63;
-    Arena A(1024 + pitch * (lfs + 2 * cfs) + bd);
-    if (!A.ok)
+    const size_t pitch = ((size_t)dstW * 2 + 63) & ~(size_t)63;
+    Stage S;
+    const size_t dlf = S.put(lf, (size_t)lfs * 2), dcf = S.put(cf, (size_t)cfs * 2);
+    size_t dl, du, dv;
+    if (!put_lines(S, dl, pitch, lum, lfs, dstW) || !put_lines(S, du, pitch, cu, cfs, cw) || !put_lines(S, dv, pitch, cv, cfs, cw))
         return FFHIP_EIO;
-    uint8_t *dlf = A.buf, *dcf = dlf + 512, *dl = dcf + 512, *du = dl + pitch * lfs, *dv = du + pitch * cfs, *dd = dv + pitch * cfs;
-    if ((lf && hipMemcpy(dlf, lf, (size_t)lfs * 2, hipMemcpyHostToDevice) != hipSuccess) ||
-        (cf && hipMemcpy(dcf, cf, (size_t)cfs * 2, hipMemcpyHostToDevice) != hipSuccess) || !lines_up(dl, pitch, lum, lfs, dstW) ||
-        !lines_up(du, pitch, cu, cfs, cw) || !lines_up(dv, pitch, cv, cfs, cw))
+    const size_t dd = S.hole((size_t)dstW * bpp);
+    if (!S.up() ||
+        ffhip_launch_yuv2packed_line(mode, S.dev<const int16_t>(dlf), S.dev<const int16_t>(dl), lfs, S.dev<const int16_t>(dcf), S.dev<const int16_t>(du),
+                                     S.dev<const int16_t>(dv), cfs, (ptrdiff_t)pitch, yalpha, uvalpha, S.dev(dd), dstW, lay, c->k, 0) < 0 ||
+        !S.down())
         return FFHIP_EIO;
-    if (ffhip_launch_yuv2packed_line(mode, (const int16_t *)dlf, (const int16_t *)dl, lfs, (const int16_t *)dcf, (const int16_t *)du,
-                                     (const int16_t *)dv, cfs, (ptrdiff_t)pitch, yalpha, uvalpha, dd, dstW, lay, c->k, 0) < 0 || !A.down())
-        return FFHIP_EIO;
-    memcpy(dest, A.host(dd), (size_t)dstW * bpp);
+    memcpy(dest, S.img(dd), (size_t)dstW * bpp);
     return 0;
 }
 

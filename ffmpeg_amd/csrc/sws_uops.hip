@@ -929,11 +929,8 @@ bool host_run(FFHipSwsUOps *p, const FFHipSwsOpExec *e, int bx_start, int y_star
     }
     /* negative steps (flipped pictures) and steps smaller than a line are the caller's business in the C backend too; the staging
      * below needs lines that do not overlap */
-    size_t need = 0;
-    long in_off[4], out_off[4];
     for (int i = 0; i < 4; i++) {
         in_lines[i] = in_row[i] ? a.ny : 0;
-        in_off[i] = (long)need;
         if (in_row[i]) {
             if (pl.fv_size) { /* tap rows are in_stride apart; the last line of the call reaches last_skip + ny - 1 + taps - 1 */
                 if (a.in_step[i] != a.in_stride[i])
@@ -942,73 +939,52 @@ bool host_run(FFHipSwsUOps *p, const FFHipSwsOpExec *e, int bx_start, int y_star
             }
             if (a.in_step[i] < in_row[i] && in_lines[i] > 1)
                 return false;
-            need += (size_t)(in_row[i] + 15 & ~15L) * in_lines[i];
         }
+        if (out_row[i] && a.out_step[i] < out_row[i] && a.ny > 1)
+            return false;
     }
-    size_t pal_off = 0;
-    if (pl.palette) {
-        pal_off = need;
-        need += 1024;
-    }
-    for (int i = 0; i < 4; i++) {
-        out_off[i] = (long)need;
-        if (out_row[i]) {
-            if (a.out_step[i] < out_row[i] && a.ny > 1)
-                return false;
-            need += (size_t)(out_row[i] + 15 & ~15L) * a.ny;
-        }
-    }
-    const size_t tabs_off = need;
-    need += (rowtab.size() + (pl.fh_size ? (size_t)a.x0 + a.npx : 0)) * sizeof(int32_t) + 64;
 
-    Arena A(need);
-    if (!A.ok)
+    Stage S;
+    size_t in_off[4] = {}, out_off[4] = {}, pal = 0;
+    for (int i = 0; i < 4; i++)
+        if (in_row[i]) {
+            const long pitch = in_row[i] + 15 & ~15L;
+            in_off[i] = S.put2d(e->in[i], a.in_step[i], in_row[i], in_lines[i], pitch);
+            a.in_step[i] = a.in_stride[i] = pitch;
+        }
+    if (pl.palette)
+        pal = S.put(e->in[1], 1024);
+    for (int i = 0; i < 4; i++)
+        if (out_row[i]) { /* a write that leaves elements of a pixel alone (packed write with a partial mask) needs what the buffer held */
+            const long pitch = out_row[i] + 15 & ~15L;
+            out_off[i] = S.put2d(e->out[i], a.out_step[i], out_row[i], a.ny, pitch);
+            a.out_step[i] = pitch;
+        }
+    const size_t rt = S.put(rowtab.data(), rowtab.size() * sizeof(int32_t));
+    const size_t ox = S.put(pl.fh_size ? e->in_offset_x : nullptr, pl.fh_size ? ((size_t)a.x0 + a.npx) * sizeof(int32_t) : 0);
+    if (!S.up())
         return false;
     for (int i = 0; i < 4; i++) {
-        if (!in_row[i])
-            continue;
-        const long pitch = in_row[i] + 15 & ~15L;
-        if (hipMemcpy2D(A.buf + in_off[i], pitch, e->in[i], a.in_step[i], in_row[i], in_lines[i], hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-        a.in[i] = A.buf + in_off[i];
-        a.in_step[i] = pitch;
-        a.in_stride[i] = pitch;
+        if (in_row[i])
+            a.in[i] = S.dev(in_off[i]);
+        if (out_row[i])
+            a.out[i] = S.dev(out_off[i]);
     }
     if (pl.palette) {
-        if (hipMemcpy(A.buf + pal_off, e->in[1], 1024, hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-        a.in[1] = A.buf + pal_off;
+        a.in[1] = S.dev(pal);
         a.in_step[1] = a.in_stride[1] = 0;
     }
-    for (int i = 0; i < 4; i++) {
-        if (!out_row[i])
-            continue;
-        const long pitch = out_row[i] + 15 & ~15L;
-        /* a write that leaves elements of a pixel alone (packed write with a partial mask) needs what the buffer held */
-        if (hipMemcpy2D(A.buf + out_off[i], pitch, e->out[i], a.out_step[i], out_row[i], a.ny, hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-        a.out[i] = A.buf + out_off[i];
-        a.out_step[i] = pitch;
-    }
-    int32_t *tabs = reinterpret_cast<int32_t *>(A.buf + (tabs_off + 63 & ~(size_t)63));
-    if (!rowtab.empty()) {
-        if (hipMemcpy(tabs, rowtab.data(), rowtab.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-        a.rowtab = tabs;
-        tabs += rowtab.size();
-    }
-    if (pl.fh_size) {
-        if (hipMemcpy(tabs, e->in_offset_x, ((size_t)a.x0 + a.npx) * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
-            return false;
-        a.offx = tabs;
-    }
-    if (launch(p, a, 1, 0) < 0 || !A.down())
+    if (!rowtab.empty())
+        a.rowtab = S.dev<int32_t>(rt);
+    if (pl.fh_size)
+        a.offx = S.dev<int32_t>(ox);
+    if (launch(p, a, 1, 0) < 0 || !S.down())
         return false;
     for (int i = 0; i < 4; i++) {
         if (!out_row[i])
             continue;
         const long pitch = out_row[i] + 15 & ~15L;
-        const uint8_t *s = A.host(A.buf + out_off[i]);
+        const uint8_t *s = S.img(out_off[i]);
         uint8_t *d = e->out[i];
         for (int r = 0; r < a.ny; r++, s += pitch, d += e->out_bump[i] + ((long)a.npx * pl.adv_out[i] >> 3))
             memcpy(d, s, out_row[i]);
