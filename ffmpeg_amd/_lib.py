@@ -259,6 +259,9 @@ def lib():
         "ffhip_vp9_loop_filter_batch_dev_hbd": (C.c_int, [C.c_int, vp, C.c_ssize_t, vp, C.c_int, vp]),
         "ffhip_vp9_intra_pred_batch_dev_hbd": (C.c_int, [C.c_int, C.c_int, vp, C.c_ssize_t, vp, vp, C.c_int, vp]),
         "ffhip_hevc_sao_batch_dev_hbd": (C.c_int, [C.c_int, vp, C.c_ssize_t, vp, C.c_ssize_t, vp, C.c_int, vp]),
+        "ff_hevc_pred_init_hip": (C.c_int, [vp, C.c_int]),
+        "ffhip_hevc_intra_batch_dev": (C.c_int, [C.c_int, vp, C.c_ssize_t, vp, vp, C.c_int, vp]),
+        "ffhip_hevc_intra_record_size": (C.c_int, []),
         "ffhip_fdsp_batch_dev": (C.c_int, [C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_float, C.c_int,
                                            C.c_int, vp]),
         "ff_float_dsp_init_hip": (C.c_int, [vp]),

@@ -142,3 +142,39 @@ def dsp_init(bit_depth=8):
     c = HEVCDSPContext()
     _lib.check(_lib.lib().ff_hevc_dsp_init_hip(C.byref(c), bit_depth), "ff_hevc_dsp_init_hip")
     return c
+
+
+# ---- intra prediction: HEVCPredContext (libavcodec/hevc/pred.h) and the batch face ------------------------------------------------
+#: FFHipHevcIntra.flags (include/ffhip.h)
+INTRA_RAW, INTRA_CORNER, INTRA_STRONG, INTRA_NO_SMOOTH, INTRA_CHROMA444 = 1, 2, 4, 8, 16
+
+#: FFHipHevcIntra (include/ffhip.h).  The reference line at edge_offset holds 4N + 1 samples from bottom-left to top-right:
+#: left[2N-1] .. left[0], the corner, top[0] .. top[2N-1].
+INTRA_DTYPE = np.dtype([("dst_offset", np.int32), ("edge_offset", np.int32), ("avail_left", np.uint16), ("avail_top", np.uint16),
+                        ("log2_size", np.uint8), ("mode", np.uint8), ("flags", np.uint8), ("c_idx_unit", np.uint8)])
+
+
+def intra_c_idx_unit(c_idx, log2_uh=0, log2_uv=0):
+    """FFHipHevcIntra.c_idx_unit: c_idx and the availability unit sizes (log2 of 1, 2 or 4 samples along the top / down the left)"""
+    return c_idx | log2_uh << 2 | log2_uv << 4
+
+
+def intra_batch(dst, stride, edges, blocks, n, stream=None, bit_depth=8):
+    """dst: uint8 (8 bits) / uint16 device tensor; edges: device tensor of reference lines; blocks: uint8 [n, 16] FFHipHevcIntra records"""
+    return _lib.check(_lib.lib().ffhip_hevc_intra_batch_dev(bit_depth, dst.data_ptr(), stride, edges.data_ptr(), blocks.data_ptr(), n,
+                                                            _stream(stream)), "ffhip_hevc_intra_batch_dev")
+
+
+class HEVCPredContext(C.Structure):
+    """FFHipHEVCPredContext == HEVCPredContext: intra_pred[] is the decoder's and is left alone"""
+    _fields_ = [("intra_pred", C.c_void_p * 4),
+                ("pred_planar", C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ssize_t) * 4),
+                ("pred_dc", C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_int, C.c_int)),
+                ("pred_angular", C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_int, C.c_int) * 4)]
+
+
+def pred_init(bit_depth=8, c=None):
+    """ff_hevc_pred_init_hip on `c` (a fresh HEVCPredContext when None); raises, leaving `c` as it was, on failure"""
+    c = HEVCPredContext() if c is None else c
+    _lib.check(_lib.lib().ff_hevc_pred_init_hip(C.byref(c), bit_depth), "ff_hevc_pred_init_hip")
+    return c

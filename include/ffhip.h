@@ -1481,6 +1481,59 @@ int ffhip_hevc_mc_w_batch_dev_hbd(int bit_depth, int chroma, int mode, uint8_t *
                                   ptrdiff_t srcstride, const int16_t *src2, const FFHipHevcMcWBlock *blocks, int n, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* libavcodec: HEVC intra prediction (HEVCPredContext)                                         */
+/* ------------------------------------------------------------------------------------------ */
+/** == HEVCPredContext (libavcodec/hevc/pred.h), member order kept.  Host pointers, pixel = uint8_t at 8 bits and uint16_t above;
+ *  strides in bytes.  top[-1 .. 2N-1] and left[-1 .. 2N-1] are the reference samples (N = 4 << index, or 1 << log2_size); top[-1]
+ *  and left[-1] both hold the corner, and each face reads the copy hevc/pred_template.c reads at that point.  `top` / `left` may
+ *  point into `src`: every input is staged before anything is written.
+ *  intra_pred[] is decoder-level (it reads HEVCLocalContext) and is never written here: the reference's C intra_pred() calls the
+ *  pred_* members below, so installing these is what routes a decoder's prediction to the device. */
+typedef struct FFHipHEVCPredContext {      /* == HEVCPredContext (libavcodec/hevc/pred.h) */
+    void *intra_pred[4];                   /* decoder-level (reads HEVCLocalContext): never written by us */
+    void (*pred_planar[4])(uint8_t *src, const uint8_t *top, const uint8_t *left, ptrdiff_t stride);
+    void (*pred_dc)(uint8_t *src, const uint8_t *top, const uint8_t *left, ptrdiff_t stride, int log2_size, int c_idx);
+    void (*pred_angular[4])(uint8_t *src, const uint8_t *top, const uint8_t *left, ptrdiff_t stride, int c_idx, int mode);
+} FFHipHEVCPredContext;
+/** ff_hevc_pred_init_<arch> shape.  bit_depth 8, 10 or 12 (baked into the installed functions); FFHIP_EINVAL for any other depth
+ *  and FFHIP_ENOSYS without a device, both leaving *c untouched.  The members it displaces answer a face that cannot run. */
+int ff_hevc_pred_init_hip(FFHipHEVCPredContext *c, int bit_depth);
+
+/** One transform block of the intra batch face.  Its reference line (4N + 1 samples, N = 1 << log2_size) is stored from bottom-left
+ *  to top-right, the order substitution walks it:
+ *      line[k] = left[2N-1-k] for k < 2N,   line[2N] = the corner,   line[2N+1+x] = top[x] for x < 2N.
+ *  Without FFHIP_HEVC_INTRA_RAW the line is what the pred_* members receive (substituted and filtered by the decoder) and the
+ *  availability fields are ignored.  With it, the kernel substitutes unavailable samples (H.265 8.4.4.2.2), filters the line
+ *  (8.4.4.2.3, strong bi-linear smoothing included), then predicts.  Availability is counted in units: uh samples along the top,
+ *  uv samples down the left (1, 2 or 4; the decoder's minimum TU size in this plane), 2N / unit <= 16 on each side.
+ *  c_idx and the two unit sizes share a byte so that the record stays 16 bytes. */
+#define FFHIP_HEVC_INTRA_RAW        1  /* substitute + filter the line before predicting */
+#define FFHIP_HEVC_INTRA_CORNER     2  /* RAW: the corner sample is available */
+#define FFHIP_HEVC_INTRA_STRONG     4  /* RAW: sps strong_intra_smoothing_enabled_flag */
+#define FFHIP_HEVC_INTRA_NO_SMOOTH  8  /* RAW: sps intra_smoothing_disabled_flag */
+#define FFHIP_HEVC_INTRA_CHROMA444 16  /* RAW: ChromaArrayType == 3, chroma lines are filtered too */
+typedef struct FFHipHevcIntra {
+    int32_t  dst_offset;   /* bytes into dst: the block's top-left sample */
+    int32_t  edge_offset;  /* bytes into edges: the block's reference line, 4N + 1 samples */
+    uint16_t avail_left;   /* RAW only: bit i = left samples [i*uv, (i+1)*uv) counted from the top are available */
+    uint16_t avail_top;    /* RAW only: bit i = top samples [i*uh, (i+1)*uh) counted from the left are available */
+    uint8_t  log2_size;    /* 2..5 */
+    uint8_t  mode;         /* 0 planar, 1 DC, 2..34 angular */
+    uint8_t  flags;        /* FFHIP_HEVC_INTRA_* */
+    uint8_t  c_idx_unit;   /* bits 0-1: c_idx (0 luma, 1 / 2 chroma); bits 2-3: log2 uh; bits 4-5: log2 uv (sizeof == 16) */
+} FFHipHevcIntra;
+/** n blocks at bit_depth 8, 10 or 12 (uint16_t samples above 8; dst, edges and stride then 2-byte aligned, and so are the record
+ *  offsets).  Preconditions: blocks are pairwise disjoint in dst; edges does not alias dst; a raw line has 2N >> log2 unit <= 16 on
+ *  both sides.  A record with mode > 34, log2_size outside 2..5, or a raw line whose units break that bound writes nothing.
+ *  FFHIP_EINVAL for another depth, n < 0, NULL pointers or misaligned 16-bit planes; FFHIP_ENOSYS without a device.
+ *  Out of scope: the RExt implicit-RDPCM case that disables the boundary filters (disableIntraBoundaryFilter with
+ *  cu_transquant_bypass); the record cannot ask for it, and such blocks stay on the C path. */
+int ffhip_hevc_intra_batch_dev(int bit_depth, uint8_t *dst, ptrdiff_t stride, const uint8_t *edges, const FFHipHevcIntra *blocks, int n,
+                               void *stream);
+/** sizeof(FFHipHevcIntra), for bindings that mirror the record (no device needed). */
+int ffhip_hevc_intra_record_size(void);
+
+/* ------------------------------------------------------------------------------------------ */
 /* libavcodec: vp9dsp inverse transforms                                    */
 /* ------------------------------------------------------------------------------------------ */
 /** VP9DSPContext.itxfm_add (libavcodec/vp9dsp.h:71-75): [tx][txtp](dst, stride, block, eob); tx 0..3 = TX_4X4..TX_32X32,
