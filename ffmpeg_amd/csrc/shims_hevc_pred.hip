@@ -6,6 +6,9 @@
  * it with the block in one Stage image (kernels/shim_arena.h) before anything is written, since the caller's top / left may point
  * into src; the kernel runs with n = 1 and a prepared line, and the block travels back.  A call that cannot run on the device is
  * answered by the C function the init displaced, as in shims.hip.
+ *
+ * ffhip_hevc_intra_pictures_dev() validates what the host can see of a picture set and launches the intra reconstruction wavefront
+ * (kernels/hevc_intra_pic.hip) on the caller's stream.
  */
 #include <stdint.h>
 #include <string.h>
@@ -37,6 +40,51 @@ extern "C" int ffhip_hevc_intra_batch_dev(int bit_depth, uint8_t *dst, ptrdiff_t
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_hevc_intra(bit_depth, dst, stride, edges, blocks, n, (hipStream_t)stream);
+}
+
+/* ---- whole pictures: the intra reconstruction wavefront (kernels/hevc_intra_pic.hip) ---------------------- */
+extern "C" int ffhip_hevc_intra_tu_record_size(void) { return (int)sizeof(FFHipHevcIntraTU); }
+
+extern "C" int ffhip_hevc_intra_pictures_dev(int bit_depth, int chroma_format_idc, int width, int height, int log2_ctb_size, int npics,
+                                             const FFHipHevcIntraPic *pics, void *stream)
+{
+    if (!hpred_bd_ok(bit_depth) || chroma_format_idc < 0 || chroma_format_idc > 3 || log2_ctb_size < 4 || log2_ctb_size > 6) {
+        ffhip_set_error("ffhip_hevc_intra_pictures_dev: bit depth %d (8, 10 or 12), chroma format %d (0..3), log2 CTB size %d (4..6)",
+                        bit_depth, chroma_format_idc, log2_ctb_size);
+        return FFHIP_EINVAL;
+    }
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || (width | height) & 7) {
+        ffhip_set_error("ffhip_hevc_intra_pictures_dev: picture size %d x %d (multiples of 8, at most 65535)", width, height);
+        return FFHIP_EINVAL;
+    }
+    if (npics <= 0 || !pics) {
+        ffhip_set_error("ffhip_hevc_intra_pictures_dev: npics = %d, or a NULL picture array", npics);
+        return FFHIP_EINVAL;
+    }
+    const int ps = bit_depth > 8 ? 2 : 1, nplanes = chroma_format_idc ? 3 : 1;
+    const unsigned amask = 4u * ps - 1; /* four samples per access */
+    for (int i = 0; i < npics; i++)
+        for (int p = 0; p < nplanes; p++) {
+            const FFHipHevcIntraPlane &P = pics[i].plane[p];
+            const int pw = p && chroma_format_idc != 3 ? width >> 1 : width;
+            if (!P.base || !P.tus || !P.ctb_start || !P.res) {
+                ffhip_set_error("ffhip_hevc_intra_pictures_dev: picture %d plane %d: a NULL pointer", i, p);
+                return FFHIP_EINVAL;
+            }
+            if ((((uintptr_t)P.base | (size_t)P.stride) & amask) || P.stride < (ptrdiff_t)pw * ps) {
+                ffhip_set_error("ffhip_hevc_intra_pictures_dev: picture %d plane %d: base and stride must be %u-byte aligned, the stride at "
+                                "least the plane's width", i, p, amask + 1);
+                return FFHIP_EINVAL;
+            }
+        }
+    const int ctb_h = (height + (1 << log2_ctb_size) - 1) >> log2_ctb_size;
+    if (nplanes * ctb_h > FFHIP_PROGRESS_SLOT_INTS) {
+        ffhip_set_error("ffhip_hevc_intra_pictures_dev: %d CTB rows exceed the progress pool", nplanes * ctb_h);
+        return FFHIP_EINVAL;
+    }
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_hevc_intra_pictures(bit_depth, chroma_format_idc, width, height, log2_ctb_size, npics, pics, (hipStream_t)stream);
 }
 
 /* ---- host-pointer faces ---------------------------------------------------------------------------------- */

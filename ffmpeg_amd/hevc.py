@@ -165,6 +165,35 @@ def intra_batch(dst, stride, edges, blocks, n, stream=None, bit_depth=8):
                                                             _stream(stream)), "ffhip_hevc_intra_batch_dev")
 
 
+#: FFHipHevcIntraTU (include/ffhip.h): one intra transform block of ffhip_hevc_intra_pictures_dev.  res_offset counts int16 entries
+#: into its plane's residual array (N * N row-major; < 0: no residual); flags and c_idx_unit as INTRA_DTYPE (INTRA_RAW is implied).
+INTRA_TU_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("res_offset", np.int32), ("avail_left", np.uint16), ("avail_top", np.uint16),
+                           ("log2_size", np.uint8), ("mode", np.uint8), ("flags", np.uint8), ("c_idx_unit", np.uint8)])
+
+
+class IntraPlane(C.Structure):
+    """FFHipHevcIntraPlane (device pointers)"""
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_ssize_t), ("tus", C.c_void_p), ("ctb_start", C.c_void_p), ("res", C.c_void_p)]
+
+
+class IntraPic(C.Structure):
+    """FFHipHevcIntraPic"""
+    _fields_ = [("plane", IntraPlane * 3)]
+
+
+def intra_pictures(pics, width, height, log2_ctb_size, chroma_format_idc=1, stream=None, bit_depth=8):
+    """ffhip_hevc_intra_pictures_dev on npics = len(pics) pictures of one geometry.  pics[i]: one tuple per plane (1 for
+    chroma_format_idc 0, else 3) of (plane, stride, tus, ctb_start, res) — device tensors but the stride (bytes): the plane (uint8 at
+    8 bits, uint16 above), the INTRA_TU_DTYPE records as bytes sorted by raster CTB, the int32 CTB starts (ctb_w * ctb_h + 1) and the
+    int16 residuals.  Asynchronous on `stream`: ffhip_stream_synchronize reports a lost row hand-off."""
+    arr = (IntraPic * max(len(pics), 1))()
+    for i, planes in enumerate(pics):
+        for p, (plane, stride, tus, ctb_start, res) in enumerate(planes):
+            arr[i].plane[p] = IntraPlane(plane.data_ptr(), stride, tus.data_ptr(), ctb_start.data_ptr(), res.data_ptr())
+    return _lib.check(_lib.lib().ffhip_hevc_intra_pictures_dev(bit_depth, chroma_format_idc, width, height, log2_ctb_size, len(pics),
+                                                               C.cast(arr, C.c_void_p), _stream(stream)), "ffhip_hevc_intra_pictures_dev")
+
+
 class HEVCPredContext(C.Structure):
     """FFHipHEVCPredContext == HEVCPredContext: intra_pred[] is the decoder's and is left alone"""
     _fields_ = [("intra_pred", C.c_void_p * 4),

@@ -1533,6 +1533,57 @@ int ffhip_hevc_intra_batch_dev(int bit_depth, uint8_t *dst, ptrdiff_t stride, co
 /** sizeof(FFHipHevcIntra), for bindings that mirror the record (no device needed). */
 int ffhip_hevc_intra_record_size(void);
 
+/** Intra reconstruction of whole pictures in one launch: every intra transform block of a picture is predicted from the picture's
+ *  own samples (H.265 8.4.4.2: substitution, filtering, prediction), its residual is added and the sum clipped to
+ *  [0, (1 << bit_depth) - 1], in an order that honours HEVC's availability rules: one wave per (picture, plane, CTB row) walks its
+ *  row left to right, and CTB x of a row starts once the row above has finished CTB x + 1.
+ *  A block's reference samples sit at the same places as for FFHipHevcIntra with FFHIP_HEVC_INTRA_RAW; here they are read from the
+ *  plane (as reconstructed so far) instead of an edges buffer.
+ *
+ *  Contract:
+ *  - a sample a record marks available comes earlier in decoding order (6.4.1 z-scan availability, with slices, tiles and
+ *    constrained_intra_pred_flag already folded into the masks by the caller);
+ *  - samples no record covers (inter CUs, already reconstructed by the MC and residual stages; PCM CUs) are read as the plane holds
+ *    them at launch and are never written; bytes outside the picture (the stride padding) are never written;
+ *  - the planes are independent chains (intra prediction never crosses planes); monochrome uses plane 0 only;
+ *  - 4:2:2 chroma blocks arrive as the two square blocks the decoder predicts, the top one first.
+ *  A malformed record — mode > 34, log2_size outside 2..5, x or y not a multiple of 4, a block outside the picture or outside the
+ *  CTB it is listed under, unit sizes above 4 or more than 16 units on a side — writes nothing and reads nothing outside its plane.
+ *  A record that marks samples available that are not reconstructed yet predicts undefined values, but cannot hang the launch or
+ *  touch memory outside its plane.
+ *  Out of scope, as for the batch face: the RExt implicit-RDPCM case that disables the boundary filters (cu_transquant_bypass_flag);
+ *  such CUs stay on the C path. */
+typedef struct FFHipHevcIntraTU {   /* one intra transform block, 16 bytes */
+    uint16_t x, y;                  /* its top-left sample in its plane */
+    int32_t  res_offset;            /* int16 units into the plane's res: the block's N * N residuals, row-major; < 0: none (cbf 0) */
+    uint16_t avail_left;            /* bit i = left samples [i*uv, (i+1)*uv) counted from the top are available (as FFHipHevcIntra) */
+    uint16_t avail_top;             /* bit i = top samples [i*uh, (i+1)*uh) counted from the left are available */
+    uint8_t  log2_size;             /* 2..5 */
+    uint8_t  mode;                  /* 0 planar, 1 DC, 2..34 angular */
+    uint8_t  flags;                 /* FFHIP_HEVC_INTRA_CORNER / _STRONG / _NO_SMOOTH / _CHROMA444; _RAW is implied */
+    uint8_t  c_idx_unit;            /* as FFHipHevcIntra: bits 0-1 c_idx (it selects the luma-only rules), 2-3 log2 uh, 4-5 log2 uv */
+} FFHipHevcIntraTU;
+typedef struct FFHipHevcIntraPlane { /* device pointers */
+    uint8_t *base;                  /* the plane's top-left sample */
+    ptrdiff_t stride;               /* bytes, >= the plane's width in bytes */
+    const FFHipHevcIntraTU *tus;    /* sorted by raster CTB address; decoding order inside a CTB */
+    const int32_t *ctb_start;       /* ctb_w * ctb_h + 1 entries: the records of raster CTB a are tus[ctb_start[a] .. ctb_start[a + 1]) */
+    const int16_t *res;             /* final residuals (after the transform / transform skip / RDPCM / cross-component prediction) */
+} FFHipHevcIntraPlane;
+typedef struct FFHipHevcIntraPic {
+    FFHipHevcIntraPlane plane[3];   /* Y, Cb, Cr; chroma_format_idc 0: plane[0] only */
+} FFHipHevcIntraPic;
+/** npics pictures of one geometry: width x height luma samples (multiples of 8, at most 65535), CTBs of 1 << log2_ctb_size (4, 5 or 6)
+ *  luma samples, bit_depth 8, 10 or 12 (uint16_t samples above 8), chroma_format_idc 0..3.  Every used plane needs non-NULL
+ *  pointers; base and stride are multiples of 4 samples (4 bytes at 8 bits, 8 above).  Pictures go 16 to a launch (fewer when the
+ *  progress pool cannot hold their CTB rows).  Asynchronous on `stream`; a lost row hand-off is reported by ffhip_stream_synchronize.
+ *  FFHIP_EINVAL for another depth, chroma format, CTB or picture size, npics <= 0, NULL or misaligned planes, or more CTB rows than
+ *  one progress-pool slot holds; FFHIP_ENOSYS without a device. */
+int ffhip_hevc_intra_pictures_dev(int bit_depth, int chroma_format_idc, int width, int height, int log2_ctb_size, int npics,
+                                  const FFHipHevcIntraPic *pics /* host array */, void *stream);
+/** sizeof(FFHipHevcIntraTU), for bindings that mirror the record (no device needed). */
+int ffhip_hevc_intra_tu_record_size(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* libavcodec: vp9dsp inverse transforms                                    */
 /* ------------------------------------------------------------------------------------------ */
