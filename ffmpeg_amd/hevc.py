@@ -194,6 +194,57 @@ def intra_pictures(pics, width, height, log2_ctb_size, chroma_format_idc=1, stre
                                                                C.cast(arr, C.c_void_p), _stream(stream)), "ffhip_hevc_intra_pictures_dev")
 
 
+#: FFHipHevcInterPU (include/ffhip.h): one luma prediction block of ffhip_hevc_inter_pictures_dev.  flags: bit 0 predFlagL0, bit 1
+#: predFlagL1; mv: [list][x, y] in quarter luma samples; slice: index into the picture's slice table.
+INTER_PU_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("w", np.uint8), ("h", np.uint8), ("flags", np.uint8), ("pad", np.uint8),
+                           ("ref_idx", np.uint8, 2), ("slice", np.uint16), ("mv", np.int16, (2, 2))])
+#: FFHipHevcInterTU: one inter transform block of one plane; res_offset counts int16 entries into the plane's residuals (< 0: none).
+INTER_TU_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("res_offset", np.int32), ("log2_size", np.uint8), ("pad", np.uint8, 3)])
+#: FFHipHevcInterSlice: ref[list][ref_idx] -> DPB slot; weights and offsets as hevcdec.c passes them to put_hevc_*_w.
+INTER_SLICE_DTYPE = np.dtype([("ref", np.uint8, (2, 16)), ("num_ref", np.uint8, 2), ("weighted", np.uint8), ("luma_log2_denom", np.uint8),
+                              ("chroma_log2_denom", np.uint8), ("pad", np.uint8, 3), ("luma_weight", np.int16, (2, 16)),
+                              ("luma_offset", np.int16, (2, 16)), ("chroma_weight", np.int16, (2, 16, 2)),
+                              ("chroma_offset", np.int16, (2, 16, 2))])
+
+
+class InterPlane(C.Structure):
+    """FFHipHevcInterPlane (device pointers)"""
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_ssize_t), ("tus", C.c_void_p), ("tu_ctb_start", C.c_void_p), ("res", C.c_void_p)]
+
+
+class InterRef(C.Structure):
+    """FFHipHevcInterRef (device pointers, strides in bytes)"""
+    _fields_ = [("base", C.c_void_p * 3), ("stride", C.c_ssize_t * 3)]
+
+
+class InterPic(C.Structure):
+    """FFHipHevcInterPic"""
+    _fields_ = [("plane", InterPlane * 3), ("pus", C.c_void_p), ("pu_ctb_start", C.c_void_p), ("slices", C.c_void_p), ("nslices", C.c_int32),
+                ("nrefs", C.c_int32), ("ref", InterRef * 16)]
+
+
+def inter_pictures(pics, width, height, log2_ctb_size, chroma_format_idc=1, stream=None, bit_depth=8):
+    """ffhip_hevc_inter_pictures_dev on npics = len(pics) pictures of one geometry.  pics[i] = (planes, pus, pu_ctb_start, slices, refs):
+    planes, one tuple per plane (1 for chroma_format_idc 0, else 3) of (plane, stride, tus, tu_ctb_start, res) as intra_pictures();
+    pus the INTER_PU_DTYPE records as bytes sorted by raster CTB, pu_ctb_start the int32 CTB starts (ctb_w * ctb_h + 1), slices the
+    INTER_SLICE_DTYPE table as bytes — device tensors; refs a list (the DPB slots) of per-plane (plane tensor, stride in bytes) tuples.
+    Asynchronous on `stream`."""
+    arr = (InterPic * max(len(pics), 1))()
+    for i, (planes, pus, pu_ctb_start, slices, refs) in enumerate(pics):
+        for p, (plane, stride, tus, tu_ctb_start, res) in enumerate(planes):
+            arr[i].plane[p] = InterPlane(plane.data_ptr(), stride, tus.data_ptr(), tu_ctb_start.data_ptr(), res.data_ptr())
+        arr[i].pus, arr[i].pu_ctb_start = pus.data_ptr(), pu_ctb_start.data_ptr()
+        arr[i].slices = slices.data_ptr()
+        arr[i].nslices = slices.numel() * slices.element_size() // INTER_SLICE_DTYPE.itemsize
+        arr[i].nrefs = len(refs)
+        for r, ref in enumerate(refs):
+            for p, (plane, stride) in enumerate(ref):
+                arr[i].ref[r].base[p] = plane.data_ptr()
+                arr[i].ref[r].stride[p] = stride
+    return _lib.check(_lib.lib().ffhip_hevc_inter_pictures_dev(bit_depth, chroma_format_idc, width, height, log2_ctb_size, len(pics),
+                                                               C.cast(arr, C.c_void_p), _stream(stream)), "ffhip_hevc_inter_pictures_dev")
+
+
 class HEVCPredContext(C.Structure):
     """FFHipHEVCPredContext == HEVCPredContext: intra_pred[] is the decoder's and is left alone"""
     _fields_ = [("intra_pred", C.c_void_p * 4),

@@ -1584,6 +1584,95 @@ int ffhip_hevc_intra_pictures_dev(int bit_depth, int chroma_format_idc, int widt
 /** sizeof(FFHipHevcIntraTU), for bindings that mirror the record (no device needed). */
 int ffhip_hevc_intra_tu_record_size(void);
 
+/** Inter reconstruction of whole pictures in one launch: every prediction block of a picture is motion-compensated from its
+ *  reference pictures in HBM, then every inter transform block adds its residual (a batching decoder's order: idct batch with
+ *  dst = NULL -> inter pictures -> intra pictures -> deblocking -> SAO).  Prediction blocks never read the picture they write, so
+ *  there is no dependency chain: one workgroup per (picture, CTB).
+ *
+ *  Semantics:
+ *  - a PU samples its references with the picture-edge clamp of H.265 8.5.3.3.3.1 / .2 (xInt = Clip3(0, pic_width - 1, ...), the
+ *    same for rows): the bytes of the reference decoder's emulated_edge_mc path (libavcodec/hevc/hevcdec.c luma_mc_uni,
+ *    chroma_mc_uni, luma_mc_bi, chroma_mc_bi).  No padding is read and no window is refused: MVs may point anywhere;
+ *  - chroma follows chroma_mc_uni / chroma_mc_bi: mx = av_mod_uintp2(mv.x, 2 + hshift) << (1 - hshift) (an eighth-sample phase),
+ *    x_off = x0_c + (mv.x >> (2 + hshift)), the same vertically with vshift, for chroma formats 1, 2 and 3; the chroma block is
+ *    (w >> hshift) x (h >> vshift) at (x >> hshift, y >> vshift);
+ *  - the reference's operation order: a uni-predicted PU is put_hevc_{qpel,epel}_uni (_uni_w when its slice is weighted), a
+ *    bi-predicted one puts list 0 into the 14-bit intermediate and combines list 1 with it through _bi (_bi_w when weighted).  Byte
+ *    for byte the reference's output at 8, 10 and 12 bits; weights and offsets are the values hevcdec.c passes, the
+ *    << (bit_depth - 8) offset scaling happens inside (h2656_inter_template.c);
+ *  - when every PU of a CTB is predicted, the CTB's inter TUs add their residuals and clip to [0, (1 << bit_depth) - 1].  A TU only
+ *    changes samples a PU of its CTB covers;
+ *  - samples no PU covers (intra CUs, PCM CUs) are never written, nor is anything outside the picture (the stride padding);
+ *  - a malformed record writes nothing and reads nothing outside its planes and references: a PU with w or h outside 4..64 or not a
+ *    multiple of 4, outside the picture or the CTB it is listed under, flags & 3 == 0, slice >= nslices, ref_idx >= num_ref (or
+ *    num_ref > 16), a DPB slot >= nrefs; a TU with log2_size outside 2..5 or outside its CTB or its plane.
+ *  Trusted, as by the intra face (the ABI carries no lengths to check them against): the CTB start tables and the records they
+ *  index, the slice table entries below nslices, and each TU's res_offset (its N * N residuals must lie inside the plane's res).
+ *  The PUs of a CTB must be disjoint, as must the TUs of one plane of a CTB: overlapping ones leave undefined values where they
+ *  overlap, inside that CTB, and nothing outside it.
+ *  Out of scope: high_precision_offsets_enabled_flag (RExt; the reference's dsp scales offsets by << (bit_depth - 8)
+ *  unconditionally, such streams keep the C path), MV derivation (merge / AMVP stay with the decoder), PCM and the deblocking
+ *  boundary strengths. */
+typedef struct FFHipHevcInterPU {   /* one luma prediction block; it drives every plane, 20 bytes */
+    uint16_t x, y;                  /* its top-left luma sample */
+    uint8_t  w, h;                  /* 4..64, multiples of 4 (every partition mode, AMP included) */
+    uint8_t  flags;                 /* bit 0 predFlagL0, bit 1 predFlagL1 */
+    uint8_t  pad;
+    uint8_t  ref_idx[2];            /* per list, 0..15: an index into the slice's ref[list] */
+    uint16_t slice;                 /* index into the picture's slice table */
+    int16_t  mv[2][2];              /* [list][x, y]: quarter-sample luma MVs, final after merge / AMVP */
+} FFHipHevcInterPU;
+typedef struct FFHipHevcInterTU {   /* one inter transform block of one plane, 12 bytes */
+    uint16_t x, y;                  /* its top-left sample in its plane */
+    int32_t  res_offset;            /* int16 units into the plane's res: N * N final residuals, row-major; < 0: none */
+    uint8_t  log2_size;             /* 2..5; 4:2:2 chroma arrives as the two square blocks */
+    uint8_t  pad[3];
+} FFHipHevcInterTU;
+typedef struct FFHipHevcInterSlice { /* what hls_prediction_unit reads from the slice header, 424 bytes */
+    uint8_t  ref[2][16];            /* [list][ref_idx]: the DPB slot (index into FFHipHevcInterPic.ref) of that reference */
+    uint8_t  num_ref[2];            /* num_ref_idx_lX_active, 0..16 */
+    uint8_t  weighted;              /* P: weighted_pred_flag, B: weighted_bipred_flag (the weight_flag of hevcdec.c) */
+    uint8_t  luma_log2_denom, chroma_log2_denom;
+    uint8_t  pad[3];
+    int16_t  luma_weight[2][16], luma_offset[2][16];             /* sh.luma_weight_lX / luma_offset_lX */
+    int16_t  chroma_weight[2][16][2], chroma_offset[2][16][2];   /* sh.chroma_weight_lX / chroma_offset_lX, [.][.][Cb, Cr] */
+} FFHipHevcInterSlice;
+typedef struct FFHipHevcInterPlane { /* device pointers */
+    uint8_t *base;                  /* the plane's top-left sample */
+    ptrdiff_t stride;               /* bytes, >= the plane's width in bytes */
+    const FFHipHevcInterTU *tus;    /* sorted by raster CTB address */
+    const int32_t *tu_ctb_start;    /* ctb_w * ctb_h + 1 entries: the TUs of raster CTB a are tus[tu_ctb_start[a] .. [a + 1]) */
+    const int16_t *res;             /* final residuals (transform, transform skip, RDPCM, cross-component prediction, bypass applied) */
+} FFHipHevcInterPlane;
+typedef struct FFHipHevcInterRef {  /* one DPB picture (device pointers), same geometry and depth as the pictures of the call */
+    const uint8_t *base[3];         /* Y, Cb, Cr */
+    ptrdiff_t stride[3];            /* bytes */
+} FFHipHevcInterRef;
+typedef struct FFHipHevcInterPic {
+    FFHipHevcInterPlane plane[3];   /* Y, Cb, Cr; chroma_format_idc 0: plane[0] only */
+    const FFHipHevcInterPU *pus;    /* device, sorted by raster CTB address */
+    const int32_t *pu_ctb_start;    /* device, ctb_w * ctb_h + 1 entries, as tu_ctb_start */
+    const FFHipHevcInterSlice *slices; /* device */
+    int32_t nslices;
+    int32_t nrefs;                  /* 0..16: the DPB slots ref[0 .. nrefs) */
+    FFHipHevcInterRef ref[16];      /* in this host array: the face stages it to the device */
+} FFHipHevcInterPic;
+/** npics pictures of one geometry: width x height luma samples (multiples of 8, at most 65535), CTBs of 1 << log2_ctb_size (4, 5 or 6)
+ *  luma samples, bit_depth 8, 10 or 12 (uint16_t samples above 8), chroma_format_idc 0..3.  Every used plane needs non-NULL
+ *  pointers, base and stride multiples of 4 samples; reference planes are sample-aligned with a stride of at least the plane's width.
+ *  Pictures go 16 to a launch.  Asynchronous on `stream`.
+ *  FFHIP_EINVAL for another depth, chroma format, CTB or picture size, npics <= 0, NULL or misaligned planes, a stride below the
+ *  width, nrefs outside 0..16, a NULL or misaligned plane among the first nrefs references, nslices < 0, or a reference plane that
+ *  overlaps a destination plane of any picture of the call (the pictures of one launch must be independent); FFHIP_ENOSYS without a
+ *  device. */
+int ffhip_hevc_inter_pictures_dev(int bit_depth, int chroma_format_idc, int width, int height, int log2_ctb_size, int npics,
+                                  const FFHipHevcInterPic *pics /* host array */, void *stream);
+/** sizeof(FFHipHevcInterPU), sizeof(FFHipHevcInterTU), sizeof(FFHipHevcInterSlice), for bindings that mirror the records (no device
+ *  needed). */
+int ffhip_hevc_inter_pu_record_size(void);
+int ffhip_hevc_inter_tu_record_size(void);
+int ffhip_hevc_inter_slice_record_size(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* libavcodec: vp9dsp inverse transforms                                    */
 /* ------------------------------------------------------------------------------------------ */
