@@ -111,6 +111,9 @@ int ffhip_launch_hevc_intra_pictures(int bd, int chroma_format_idc, int width, i
 /* HEVC inter reconstruction of whole pictures (hevc_inter_pic.hip), arguments validated by ffhip_hevc_inter_pictures_dev() */
 int ffhip_launch_hevc_inter_pictures(int bd, int chroma_format_idc, int width, int height, int log2_ctb, int npics, const FFHipHevcInterPic *pics,
                                      hipStream_t stream);
+/* HEVC in-loop filtering of whole pictures (hevc_lf_pic.hip), arguments validated by ffhip_hevc_loop_filter_pictures_dev() */
+int ffhip_launch_hevc_loop_filter_pictures(int bd, int chroma_format_idc, int width, int height, int log2_ctb, int log2_min_cb, int npics,
+                                           const FFHipHevcLfPic *pics, hipStream_t stream);
 int ffhip_launch_hevc_loop_filter(uint8_t *base, ptrdiff_t stride, const FFHipHevcEdge *edges, int n, hipStream_t stream);
 int ffhip_launch_hevc_sao(uint8_t *dst, ptrdiff_t sd, const uint8_t *src, ptrdiff_t ss, const FFHipHevcSao *blocks, int n, hipStream_t stream);
 int ffhip_launch_vp9_smc(uint8_t *dst, ptrdiff_t dststride, const uint8_t *src, ptrdiff_t srcstride, const FFHipVp9ScaledBlock *blocks, int n,

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "h264_kernels.h"
+#include "hevc_lf_rules.h"
 
 /* |64 sqrt2 cos(m pi / 64)| as the standard rounds it; T32[k][i] = +-g[fold((2i+1)k mod 128)] */
 static int8_t hevc_t32_host[32][32];
@@ -634,8 +635,6 @@ int ffhip_launch_hevc_idct_bd(int bd, int kind, int log2_size, int16_t *coeffs, 
  * 8 lanes per segment, one per sample line; the two 4-line groups decide from their lines 0 and 3, which the lanes of a
  * group exchange with DPP-style shuffles.  Every read of a line happens before any write of it.
  */
-__device__ __forceinline__ int hv_abs(int v) { return v < 0 ? -v : v; }
-
 /* PIX = uint8_t (bd 8) / uint16_t: beta and tc arrive in 8-bit units and are scaled as the reference's templates scale them
  * (beta <<= BIT_DEPTH - 8, tc = _tc[j] << (BIT_DEPTH - 8): hevc/dsp_template.c:845,862,907); stride and offsets in bytes */
 template <typename PIX>
@@ -643,7 +642,6 @@ __device__ __forceinline__ void hevc_lf_lines(uint8_t *base, ptrdiff_t stride, c
 {
     constexpr int PS = (int)sizeof(PIX);
     const int maxv = (1 << bd) - 1;
-    auto clipp = [&](int v) { return min(max(v, 0), maxv); };
     const int line = lane_ & 7, j = line >> 2;
     const bool live = e < n;
     const FFHipHevcEdge ed = edges[live ? e : 0];
@@ -673,9 +671,10 @@ __device__ __forceinline__ void hevc_lf_lines(uint8_t *base, ptrdiff_t stride, c
     const int p3 = v[0], p2 = v[1], p1 = v[2], p0 = v[3], q0 = v[4], q1 = v[5], q2 = v[6], q3 = v[7];
     if (chroma) {
         if (live && tc > 0) {
-            const int delta = clip3((((q0 - p0) * 4) + p1 - q1 + 4) >> 3, -tc, tc);
-            if (!no_p) pix[-xs] = (PIX)clipp(p0 + delta);
-            if (!no_q) pix[0] = (PIX)clipp(q0 - delta);
+            int cp0 = p0, cq0 = q0;
+            hevc_lf_chroma(p1, cp0, cq0, q1, tc, no_p, no_q, maxv);
+            if (!no_p) pix[-xs] = (PIX)cp0;
+            if (!no_q) pix[0] = (PIX)cq0;
         }
         return;
     }
@@ -687,37 +686,11 @@ __device__ __forceinline__ void hevc_lf_lines(uint8_t *base, ptrdiff_t stride, c
     const int flat0 = __shfl(flat, l0, 64), flat3 = __shfl(flat, l3, 64), step0 = __shfl(step, l0, 64), step3 = __shfl(step, l3, 64);
     if (!live)
         return;
-    const int d0 = dp0 + dq0, d3 = dp3 + dq3;
-    if (d0 + d3 >= beta)
+    int nd_p = 1, nd_q = 1;
+    const int mode = hevc_lf_decide(dp0, dq0, dp3, dq3, flat0, flat3, step0, step3, beta, tc, nd_p, nd_q);
+    if (mode == HLF_NONE)
         return;
-    unsigned ch = 0; /* bit k: v[k] changed */
-    const int beta_3 = beta >> 3, beta_2 = beta >> 2, tc25 = (tc * 5 + 1) >> 1;
-    if (flat0 < beta_3 && step0 < tc25 && flat3 < beta_3 && step3 < tc25 && (d0 << 1) < beta_2 && (d3 << 1) < beta_2) {
-        const int t = tc << 1;
-        if (!no_p) {
-            v[3] = p0 + clip3(((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3) - p0, -t, t);
-            v[2] = p1 + clip3(((p2 + p1 + p0 + q0 + 2) >> 2) - p1, -t, t);
-            v[1] = p2 + clip3(((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3) - p2, -t, t);
-            ch |= 0x0E;
-        }
-        if (!no_q) {
-            v[4] = q0 + clip3(((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3) - q0, -t, t);
-            v[5] = q1 + clip3(((p0 + q0 + q1 + q2 + 2) >> 2) - q1, -t, t);
-            v[6] = q2 + clip3(((2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3) - q2, -t, t);
-            ch |= 0x70;
-        }
-    } else {
-        const int side = (beta + (beta >> 1)) >> 3;
-        const int nd_p = dp0 + dp3 < side ? 2 : 1, nd_q = dq0 + dq3 < side ? 2 : 1, tc_2 = tc >> 1;
-        int delta = (9 * (q0 - p0) - 3 * (q1 - p1) + 8) >> 4;
-        if (hv_abs(delta) < 10 * tc) {
-            delta = clip3(delta, -tc, tc);
-            if (!no_p) { v[3] = clipp(p0 + delta); ch |= 0x08; }
-            if (!no_q) { v[4] = clipp(q0 - delta); ch |= 0x10; }
-            if (!no_p && nd_p > 1) { v[2] = clipp(p1 + clip3((((p2 + p0 + 1) >> 1) - p1 + delta) >> 1, -tc_2, tc_2)); ch |= 0x04; }
-            if (!no_q && nd_q > 1) { v[5] = clipp(q1 + clip3((((q2 + q0 + 1) >> 1) - q1 - delta) >> 1, -tc_2, tc_2)); ch |= 0x20; }
-        }
-    }
+    const unsigned ch = mode == HLF_STRONG ? hevc_lf_strong(v, tc, no_p, no_q) : hevc_lf_weak(v, tc, nd_p, nd_q, no_p, no_q, maxv);
     if (!ch)
         return;
     if (wide) {
@@ -754,7 +727,6 @@ __device__ __forceinline__ void hevc_lf_hgroup(uint8_t *base, ptrdiff_t stride, 
     using ROW = typename std::conditional<PS == 1, uint32_t, uint2>::type;
     const bool chroma = ed.kind & 2;
     const int maxv = (1 << bd) - 1;
-    auto clipp = [&](int v) { return min(max(v, 0), maxv); };
     const int tc = ed.tc[j] << (bd - 8), no_p = ed.no_p[j], no_q = ed.no_q[j], beta = ed.beta << (bd - 8);
     uint8_t *pix = base + ed.offset + 4 * j * PS; /* the group's first column on row q0 */
     auto ld = [&](int r, int (&v)[4]) {
@@ -779,11 +751,8 @@ __device__ __forceinline__ void hevc_lf_hgroup(uint8_t *base, ptrdiff_t stride, 
         if (tc <= 0)
             return;
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const int delta = clip3((((q0[c] - p0[c]) * 4) + p1[c] - q1[c] + 4) >> 3, -tc, tc);
-            if (!no_p) p0[c] = clipp(p0[c] + delta);
-            if (!no_q) q0[c] = clipp(q0[c] - delta);
-        }
+        for (int c = 0; c < 4; c++)
+            hevc_lf_chroma(p1[c], p0[c], q0[c], q1[c], tc, no_p, no_q, maxv);
         if (!no_p) st(-1, p0);
         if (!no_q) st(0, q0);
         return;
@@ -792,54 +761,25 @@ __device__ __forceinline__ void hevc_lf_hgroup(uint8_t *base, ptrdiff_t stride, 
     ld(-4, p3); ld(-3, p2); ld(2, q2); ld(3, q3);
     auto dpf = [&](int c) { return hv_abs(p2[c] - 2 * p1[c] + p0[c]); };
     auto dqf = [&](int c) { return hv_abs(q2[c] - 2 * q1[c] + q0[c]); };
-    const int dp0 = dpf(0), dp3 = dpf(3), dq0 = dqf(0), dq3 = dqf(3);
-    const int d0 = dp0 + dq0, d3 = dp3 + dq3;
-    if (d0 + d3 >= beta)
-        return;
     const int flat0 = hv_abs(p3[0] - p0[0]) + hv_abs(q3[0] - q0[0]), flat3 = hv_abs(p3[3] - p0[3]) + hv_abs(q3[3] - q0[3]);
     const int step0 = hv_abs(p0[0] - q0[0]), step3 = hv_abs(p0[3] - q0[3]);
-    const int beta_3 = beta >> 3, beta_2 = beta >> 2, tc25 = (tc * 5 + 1) >> 1;
-    if (flat0 < beta_3 && step0 < tc25 && flat3 < beta_3 && step3 < tc25 && (d0 << 1) < beta_2 && (d3 << 1) < beta_2) {
-        const int t = tc << 1;
+    int nd_p = 1, nd_q = 1;
+    const int mode = hevc_lf_decide(dpf(0), dqf(0), dpf(3), dqf(3), flat0, flat3, step0, step3, beta, tc, nd_p, nd_q);
+    if (mode == HLF_NONE)
+        return;
+    unsigned any = 0;
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const int P3 = p3[c], P2 = p2[c], P1 = p1[c], P0 = p0[c], Q0 = q0[c], Q1 = q1[c], Q2 = q2[c], Q3 = q3[c];
-            if (!no_p) {
-                p0[c] = P0 + clip3(((P2 + 2 * P1 + 2 * P0 + 2 * Q0 + Q1 + 4) >> 3) - P0, -t, t);
-                p1[c] = P1 + clip3(((P2 + P1 + P0 + Q0 + 2) >> 2) - P1, -t, t);
-                p2[c] = P2 + clip3(((2 * P3 + 3 * P2 + P1 + P0 + Q0 + 4) >> 3) - P2, -t, t);
-            }
-            if (!no_q) {
-                q0[c] = Q0 + clip3(((P1 + 2 * P0 + 2 * Q0 + 2 * Q1 + Q2 + 4) >> 3) - Q0, -t, t);
-                q1[c] = Q1 + clip3(((P0 + Q0 + Q1 + Q2 + 2) >> 2) - Q1, -t, t);
-                q2[c] = Q2 + clip3(((2 * Q3 + 3 * Q2 + Q1 + Q0 + P0 + 4) >> 3) - Q2, -t, t);
-            }
-        }
+    for (int c = 0; c < 4; c++) {
+        int v[8] = { p3[c], p2[c], p1[c], p0[c], q0[c], q1[c], q2[c], q3[c] };
+        any |= mode == HLF_STRONG ? hevc_lf_strong(v, tc, no_p, no_q) : hevc_lf_weak(v, tc, nd_p, nd_q, no_p, no_q, maxv);
+        p2[c] = v[1]; p1[c] = v[2]; p0[c] = v[3]; q0[c] = v[4]; q1[c] = v[5]; q2[c] = v[6];
+    }
+    if (mode == HLF_STRONG) {
         if (!no_p) { st(-1, p0); st(-2, p1); st(-3, p2); }
         if (!no_q) { st(0, q0); st(1, q1); st(2, q2); }
-    } else {
-        const int side = (beta + (beta >> 1)) >> 3;
-        const int nd_p = dp0 + dp3 < side ? 2 : 1, nd_q = dq0 + dq3 < side ? 2 : 1, tc_2 = tc >> 1;
-        bool any = false;
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const int P2 = p2[c], P1 = p1[c], P0 = p0[c], Q0 = q0[c], Q1 = q1[c], Q2 = q2[c];
-            int delta = (9 * (Q0 - P0) - 3 * (Q1 - P1) + 8) >> 4;
-            if (hv_abs(delta) < 10 * tc) {
-                any = true;
-                delta = clip3(delta, -tc, tc);
-                if (!no_p) p0[c] = clipp(P0 + delta);
-                if (!no_q) q0[c] = clipp(Q0 - delta);
-                if (!no_p && nd_p > 1)
-                    p1[c] = clipp(P1 + clip3((((P2 + P0 + 1) >> 1) - P1 + delta) >> 1, -tc_2, tc_2));
-                if (!no_q && nd_q > 1)
-                    q1[c] = clipp(Q1 + clip3((((Q2 + Q0 + 1) >> 1) - Q1 - delta) >> 1, -tc_2, tc_2));
-            }
-        }
-        if (any) {
-            if (!no_p) { st(-1, p0); if (nd_p > 1) st(-2, p1); }
-            if (!no_q) { st(0, q0); if (nd_q > 1) st(1, q1); }
-        }
+    } else if (any) {
+        if (!no_p) { st(-1, p0); if (nd_p > 1) st(-2, p1); }
+        if (!no_q) { st(0, q0); if (nd_q > 1) st(1, q1); }
     }
 }
 
@@ -984,15 +924,7 @@ __global__ __launch_bounds__(256) void k_hevc_sao(uint8_t *dst, ptrdiff_t sd, co
         }
         for (int e = 0; e < m; e++) {
             const int c = p[e];
-            int off;
-            if (edge) {
-                const int na = p[e + a], nb = p[e + bb];
-                const int sel = 2 + (c > na) - (c < na) + (c > nb) - (c < nb); /* edge_idx = { 1, 2, 0, 3, 4 } */
-                off = sel == 0 ? o1 : sel == 1 ? o2 : sel == 2 ? o0 : sel == 3 ? o3 : o4;
-            } else {
-                const int band = ((c >> 3) - cls) & 31;                          /* 0..3: the signalled bands */
-                off = band == 0 ? o1 : band == 1 ? o2 : band == 2 ? o3 : band == 3 ? o4 : 0;
-            }
+            const int off = edge ? hevc_sao_edge_off(c, p[e + a], p[e + bb], o0, o1, o2, o3, o4) : hevc_sao_band_off(c, 3, cls, o1, o2, o3, o4);
             q[e] = (uint8_t)clip_u8(c + off);
         }
     }
@@ -1018,15 +950,7 @@ __global__ __launch_bounds__(256) void k_hevc_sao16(uint8_t *dst, ptrdiff_t sd, 
         const int y = t / w, x = t - y * w;
         const uint16_t *p = s0 + (ptrdiff_t)y * sp + x;
         const int c = p[0];
-        int off;
-        if (edge) {
-            const int na = p[a], nb = p[bb];
-            const int sel = 2 + (c > na) - (c < na) + (c > nb) - (c < nb); /* edge_idx = { 1, 2, 0, 3, 4 } */
-            off = sel == 0 ? o1 : sel == 1 ? o2 : sel == 2 ? o0 : sel == 3 ? o3 : o4;
-        } else {
-            const int band = (((c >> bshift) & 31) - cls) & 31;           /* 0..3: the signalled bands */
-            off = band == 0 ? o1 : band == 1 ? o2 : band == 2 ? o3 : band == 3 ? o4 : 0;
-        }
+        const int off = edge ? hevc_sao_edge_off(c, p[a], p[bb], o0, o1, o2, o3, o4) : hevc_sao_band_off(c, bshift, cls, o1, o2, o3, o4);
         reinterpret_cast<uint16_t *>(d0 + (ptrdiff_t)y * sd)[x] = (uint16_t)min(max(c + off, 0), maxv);
     }
 }
@@ -1074,15 +998,6 @@ __global__ __launch_bounds__(256) void k_hevc_sao_restore(uint8_t *dst, ptrdiff_
         return;
     const FFHipHevcSaoRestore k = blocks[b];
     const int W = k.width, H = k.height, eo = k.eo & 3, off = k.offset0;
-    const bool b0 = k.borders & 1, b1 = k.borders & 2, b2 = k.borders & 4, b3 = k.borders & 8;
-    const bool ve0 = k.vert_edge & 1, ve1 = k.vert_edge & 2, he0 = k.horiz_edge & 1, he1 = k.horiz_edge & 2;
-    const bool de0 = k.diag_edge & 1, de1 = k.diag_edge & 2, de2 = k.diag_edge & 4, de3 = k.diag_edge & 8;
-    enum { HORIZ = 0, VERT = 1, D135 = 2, D45 = 3 };
-    /* the running state of the reference after its border loops */
-    const int init_x = (eo != VERT && b0) ? 1 : 0, w = W - ((eo != VERT && b2) ? 1 : 0);
-    const int init_y = (eo != HORIZ && b1) ? 1 : 0, h = H - ((eo != HORIZ && b3) ? 1 : 0);
-    const int s_ul = !de0 && eo == D135 && !b0 && !b1, s_ur = !de1 && eo == D45 && !b1 && !b2;
-    const int s_lr = !de2 && eo == D135 && !b2 && !b3, s_ll = !de3 && eo == D45 && !b0 && !b3;
     const uint8_t *s0 = src + k.src_offset;
     uint8_t *d0 = dst + k.dst_offset;
     for (int t = lane; t < 3 * H + 3 * W; t += 64) {
@@ -1098,25 +1013,7 @@ __global__ __launch_bounds__(256) void k_hevc_sao_restore(uint8_t *dst, ptrdiff_
         }
         if (x < 0 || y < 0)
             continue;
-        int kind = 0; /* 1: src + offset, 2: src */
-        if (eo != VERT) {
-            if (b0 && x == 0) kind = 1;
-            if (b2 && x == W - 1) kind = 1;
-        }
-        if (eo != HORIZ) {
-            if (b1 && y == 0 && x >= init_x && x < w) kind = 1;
-            if (b3 && y == H - 1 && x >= init_x && x < w) kind = 1;
-        }
-        if (k.variant) {
-            if (ve0 && eo != VERT && x == 0 && y >= init_y + s_ul && y < h - s_ll) kind = 2;
-            if (ve1 && eo != VERT && x == w - 1 && y >= init_y + s_ur && y < h - s_lr) kind = 2;
-            if (he0 && eo != HORIZ && y == 0 && x >= init_x + s_ul && x < w - s_ur) kind = 2;
-            if (he1 && eo != HORIZ && y == h - 1 && x >= init_x + s_ll && x < w - s_lr) kind = 2;
-            if (de0 && eo == D135 && x == 0 && y == 0) kind = 2;
-            if (de1 && eo == D45 && x == w - 1 && y == 0) kind = 2;
-            if (de2 && eo == D135 && x == w - 1 && y == h - 1) kind = 2;
-            if (de3 && eo == D45 && x == 0 && y == h - 1) kind = 2;
-        }
+        const int kind = hevc_sao_restore_kind(x, y, W, H, eo, k.borders, k.vert_edge, k.horiz_edge, k.diag_edge, k.variant != 0);
         if (kind) {
             const int v = reinterpret_cast<const PIX *>(s0 + (ptrdiff_t)y * ss)[x];
             reinterpret_cast<PIX *>(d0 + (ptrdiff_t)y * sd)[x] = (PIX)(kind == 1 ? min(max(v + off, 0), maxv) : v);

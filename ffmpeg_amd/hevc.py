@@ -245,6 +245,45 @@ def inter_pictures(pics, width, height, log2_ctb_size, chroma_format_idc=1, stre
                                                                C.cast(arr, C.c_void_p), _stream(stream)), "ffhip_hevc_inter_pictures_dev")
 
 
+#: FFHipHevcLfCtb (include/ffhip.h): one CTB of ffhip_hevc_loop_filter_pictures_dev.  sao_type: 0 off, 1 band, 2 edge; sao_class:
+#: band_position or eo_class; restore / vert_edge / horiz_edge / diag_edge: sao_filter_CTB's restore operands as bit sets.
+LF_CTB_DTYPE = np.dtype([("beta_offset", np.int8), ("tc_offset", np.int8), ("sao_type", np.uint8, 3), ("sao_class", np.uint8, 3),
+                         ("restore", np.uint8), ("vert_edge", np.uint8), ("horiz_edge", np.uint8), ("diag_edge", np.uint8),
+                         ("sao_offset_val", np.int16, (3, 5)), ("pad", np.uint8, 2)])
+
+
+class LfPlane(C.Structure):
+    """FFHipHevcLfPlane (device pointers, strides in bytes)"""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_ssize_t), ("dst", C.c_void_p), ("dst_stride", C.c_ssize_t)]
+
+
+class LfPic(C.Structure):
+    """FFHipHevcLfPic"""
+    _fields_ = [("plane", LfPlane * 3), ("bs_ver", C.c_void_p), ("bs_hor", C.c_void_p), ("qp_y", C.c_void_p), ("bypass", C.c_void_p),
+                ("ctbs", C.c_void_p), ("bs_stride", C.c_int32), ("cb_stride", C.c_int32), ("cb_qp_offset", C.c_int8),
+                ("cr_qp_offset", C.c_int8), ("pad", C.c_uint8 * 6)]
+
+
+def loop_filter_pictures(pics, width, height, log2_ctb_size, log2_min_cb_size, chroma_format_idc=1, stream=None, bit_depth=8):
+    """ffhip_hevc_loop_filter_pictures_dev on npics = len(pics) pictures of one geometry.  pics[i] = (planes, maps): planes, one
+    tuple per plane (1 for chroma_format_idc 0, else 3) of (src, src_stride, dst, dst_stride) — device tensors, strides in bytes;
+    maps a dict with the device tensors bs_ver, bs_hor (uint8), qp_y (int8), ctbs (LF_CTB_DTYPE records as bytes), optionally
+    bypass (uint8; absent or None: no bypass CUs), and the ints bs_stride, cb_stride, cb_qp_offset, cr_qp_offset.
+    Asynchronous on `stream`."""
+    arr = (LfPic * max(len(pics), 1))()
+    for i, (planes, maps) in enumerate(pics):
+        for p, (src, ss, dst, ds) in enumerate(planes):
+            arr[i].plane[p] = LfPlane(src.data_ptr(), ss, dst.data_ptr(), ds)
+        arr[i].bs_ver, arr[i].bs_hor = maps["bs_ver"].data_ptr(), maps["bs_hor"].data_ptr()
+        arr[i].qp_y, arr[i].ctbs = maps["qp_y"].data_ptr(), maps["ctbs"].data_ptr()
+        arr[i].bypass = maps["bypass"].data_ptr() if maps.get("bypass") is not None else None
+        arr[i].bs_stride, arr[i].cb_stride = maps["bs_stride"], maps["cb_stride"]
+        arr[i].cb_qp_offset, arr[i].cr_qp_offset = maps.get("cb_qp_offset", 0), maps.get("cr_qp_offset", 0)
+    return _lib.check(_lib.lib().ffhip_hevc_loop_filter_pictures_dev(bit_depth, chroma_format_idc, width, height, log2_ctb_size,
+                                                                     log2_min_cb_size, len(pics), C.cast(arr, C.c_void_p), _stream(stream)),
+                      "ffhip_hevc_loop_filter_pictures_dev")
+
+
 class HEVCPredContext(C.Structure):
     """FFHipHEVCPredContext == HEVCPredContext: intra_pred[] is the decoder's and is left alone"""
     _fields_ = [("intra_pred", C.c_void_p * 4),

@@ -1673,6 +1673,73 @@ int ffhip_hevc_inter_pu_record_size(void);
 int ffhip_hevc_inter_tu_record_size(void);
 int ffhip_hevc_inter_slice_record_size(void);
 
+/** In-loop filtering of whole pictures in one launch: deblocking (H.265 8.7.2) and SAO (8.7.3) of up to 16 pictures, from the
+ *  reconstructed planes the intra and inter picture faces wrote (`src`, read only) into the DPB frames (`dst`, write only).  Out of
+ *  place because intra prediction of the current picture reads unfiltered samples while the DPB holds filtered ones.
+ *
+ *  Semantics, byte for byte those of the reference's per-CTB filters over the whole picture (libavcodec/hevc/filter.c
+ *  deblocking_filter_CTB, sao_filter_CTB, restore_tqb_pixels):
+ *  - every vertical edge of the picture, then every horizontal edge on their output; edges on the picture border are skipped.  A
+ *    luma segment with bS 1 or 2: qPL = (QpY(p) + QpY(q) + 1) >> 1, beta = betatable[Clip3(0, 51, qPL + beta_offset)], tC =
+ *    tctable[Clip3(0, 53, qPL + 2 * (bS - 1) + (tc_offset & -2))], the offsets of the CTB that contains q0,0, the sample rules of
+ *    hevc_{v,h}_loop_filter_luma (beta and tC scaled by << (bit_depth - 8) inside); no_p / no_q from `bypass` at p0 / q0;
+ *  - chroma edges lie on the 8-sample chroma grid and are filtered where bS == 2; each 4-line chroma group takes the bS and QPs of
+ *    the luma segment at its luma position, tC = tctable[Clip3(0, 53, QpC + 2 + tc_offset)] with QpC from qPi = Clip3(0, 57, qPL +
+ *    cb/cr_qp_offset) (Table 8-10 for chroma format 1, Min(qPi, 51) otherwise);
+ *  - a bS outside 0..2 leaves its segment unfiltered;
+ *  - SAO per CTB and component from the fully deblocked picture (partial CTBs clipped to the picture): sao_band_filter /
+ *    sao_edge_filter as the per-call faces, then for the edge type sao_edge_restore[restore] with the CTB's flags and the picture-
+ *    border flags from geometry, then the samples of bypass CUs get their deblocked value back.  An out-of-range sao_type,
+ *    sao_class or band position leaves that component of that CTB deblocked;
+ *  - every sample of every dst plane inside the picture is written once; nothing outside the picture (the stride padding) is
+ *    written, and src is never written.
+ *  Trusted (the ABI carries no lengths to check them against): the maps cover the picture at their strides, `ctbs` holds ctb_w *
+ *  ctb_h records.  Whatever their contents, no read or write leaves the planes and maps: bS, QP and SAO values only select
+ *  table entries after clipping, or skip.
+ *  Stays with the decoder: the boundary strengths (slice_deblocking_filter_disabled_flag, the slice and tile restrictions included)
+ *  and the SAO slice / tile flags below.  Out of scope: bS on the device, palette / SCC deblocking control, in-place filtering. */
+typedef struct FFHipHevcLfCtb {     /* one CTB, 44 bytes */
+    int8_t   beta_offset, tc_offset;  /* 2 * slice_beta_offset_div2, 2 * slice_tc_offset_div2 of the CTB's slice */
+    uint8_t  sao_type[3];           /* per component: 0 not applied, 1 band, 2 edge (SAOParams.type_idx after the slice's flags) */
+    uint8_t  sao_class[3];          /* band: band_position (0..31); edge: eo_class (0 horizontal, 1 vertical, 2 135 deg, 3 45 deg) */
+    uint8_t  restore;               /* the `restore` of sao_filter_CTB: 0 sao_edge_restore[0], 1 [1] */
+    uint8_t  vert_edge;             /* bits 0..1 = vert_edge[0..1] as sao_filter_CTB computes them */
+    uint8_t  horiz_edge;            /* bits 0..1 = horiz_edge[0..1] */
+    uint8_t  diag_edge;             /* bits 0..3 = diag_edge[0..3] */
+    int16_t  sao_offset_val[3][5];  /* SaoOffsetVal per component, as the per-call SAO faces take them */
+    uint8_t  pad[2];
+} FFHipHevcLfCtb;
+typedef struct FFHipHevcLfPlane {   /* device pointers */
+    const uint8_t *src;             /* the reconstructed plane */
+    ptrdiff_t src_stride;           /* bytes */
+    uint8_t *dst;                   /* the filtered plane (the DPB frame's) */
+    ptrdiff_t dst_stride;           /* bytes */
+} FFHipHevcLfPlane;
+typedef struct FFHipHevcLfPic {
+    FFHipHevcLfPlane plane[3];      /* Y, Cb, Cr; chroma_format_idc 0: plane[0] only */
+    const uint8_t *bs_ver, *bs_hor; /* device, [(y >> 2) * bs_stride + (x >> 2)]: the bS (0..2) of the 4-sample luma segment at
+                                     * (x, y): vertical ones at x % 8 == 0 over rows y..y+3, horizontal ones at y % 8 == 0 over
+                                     * columns x..x+3 (filter.c's vertical_bs / horizontal_bs with bs_stride = bs_width) */
+    const int8_t *qp_y;             /* device, QpY on the min-CB grid: [(y >> log2_min_cb_size) * cb_stride + (x >> log2_min_cb_size)] */
+    const uint8_t *bypass;          /* device, the same grid, != 0: pcm with pcm_loop_filter_disabled_flag or cu_transquant_bypass;
+                                     * NULL: none */
+    const FFHipHevcLfCtb *ctbs;     /* device, ctb_w * ctb_h records in raster order */
+    int32_t bs_stride, cb_stride;   /* entries */
+    int8_t cb_qp_offset, cr_qp_offset; /* pps_cb_qp_offset, pps_cr_qp_offset */
+    uint8_t pad[6];
+} FFHipHevcLfPic;
+/** npics pictures of one geometry: width x height luma samples (multiples of 8, at most 65535), CTBs of 1 << log2_ctb_size (4..6),
+ *  min CBs of 1 << log2_min_cb_size (3..log2_ctb_size), bit_depth 8, 10 or 12 (uint16_t samples above 8), chroma_format_idc 0..3.
+ *  Planes: non-NULL, base and stride multiples of 4 samples, strides at least the plane's width; bs_stride at least width / 4,
+ *  cb_stride at least the min-CB columns.  Pictures go 16 to a launch.  Asynchronous on `stream`.
+ *  FFHIP_EINVAL for another depth, chroma format, CTB, min-CB or picture size, npics <= 0, NULL or misaligned planes, NULL bs_ver /
+ *  bs_hor / qp_y / ctbs, a stride below its width, or any src plane that overlaps any dst plane of the call; FFHIP_ENOSYS without a
+ *  device. */
+int ffhip_hevc_loop_filter_pictures_dev(int bit_depth, int chroma_format_idc, int width, int height, int log2_ctb_size,
+                                        int log2_min_cb_size, int npics, const FFHipHevcLfPic *pics /* host array */, void *stream);
+/** sizeof(FFHipHevcLfCtb), for bindings that mirror the record (no device needed). */
+int ffhip_hevc_lf_ctb_record_size(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* libavcodec: vp9dsp inverse transforms                                    */
 /* ------------------------------------------------------------------------------------------ */
