@@ -114,6 +114,8 @@ int ffhip_launch_hevc_inter_pictures(int bd, int chroma_format_idc, int width, i
 /* HEVC in-loop filtering of whole pictures (hevc_lf_pic.hip), arguments validated by ffhip_hevc_loop_filter_pictures_dev() */
 int ffhip_launch_hevc_loop_filter_pictures(int bd, int chroma_format_idc, int width, int height, int log2_ctb, int log2_min_cb, int npics,
                                            const FFHipHevcLfPic *pics, hipStream_t stream);
+/* HEVC residuals of whole pictures (hevc_res_pic.hip), arguments validated by ffhip_hevc_residual_pictures_dev() */
+int ffhip_launch_hevc_residual_pictures(int bd, int chroma_format_idc, int npics, const FFHipHevcResPic *pics, hipStream_t stream);
 int ffhip_launch_hevc_loop_filter(uint8_t *base, ptrdiff_t stride, const FFHipHevcEdge *edges, int n, hipStream_t stream);
 int ffhip_launch_hevc_sao(uint8_t *dst, ptrdiff_t sd, const uint8_t *src, ptrdiff_t ss, const FFHipHevcSao *blocks, int n, hipStream_t stream);
 int ffhip_launch_vp9_smc(uint8_t *dst, ptrdiff_t dststride, const uint8_t *src, ptrdiff_t srcstride, const FFHipVp9ScaledBlock *blocks, int n,

@@ -14,111 +14,15 @@
  * entries are wave-uniform: int16 pairs in a __constant__ table, read with scalar loads and used as SGPR operands.  Residuals are written back
  * in place (the reference leaves them in coeffs) and added to the picture with packed byte stores.
  */
-#include <mutex>
 #include <stdlib.h>
 #include <type_traits>
 
 #include "common.h"
 #include "h264_kernels.h"
 #include "hevc_lf_rules.h"
+#include "hevc_tx_rules.h"
 
-/* |64 sqrt2 cos(m pi / 64)| as the standard rounds it; T32[k][i] = +-g[fold((2i+1)k mod 128)] */
-static int8_t hevc_t32_host[32][32];
-static std::once_flag hevc_tab_once;
-/* the same matrix as int16 PAIRS for v_dot2_i32_i16, per transform size N (offset hevc_pk_off(N)): entry [j][q][0] =
- * (T_N[4q][j], T_N[4q+2][j]) (even basis functions), [j][q][1] = (T_N[4q+1][j], T_N[4q+3][j]) (odd), j < N/2, q < N/4 */
-__constant__ uint32_t hevc_pk[352];
-static uint32_t hevc_pk_host[352];
-__host__ __device__ constexpr int hevc_pk_off(int n) { return n == 4 ? 0 : n == 8 ? 4 : n == 16 ? 4 + 16 : 4 + 16 + 64; }
-
-static void hevc_build_table()
-{
-    static const int g[32] = { 64, 90, 90, 90, 89, 88, 87, 85, 83, 82, 80, 78, 75, 73, 70, 67,
-                               64, 61, 57, 54, 50, 46, 43, 38, 36, 31, 25, 22, 18, 13, 9, 4 };
-    for (int k = 0; k < 32; k++)
-        for (int i = 0; i < 32; i++) {
-            const int m = ((2 * i + 1) * k) & 127;
-            int v;
-            if (k == 0) v = 64;
-            else if (m < 32) v = g[m];
-            else if (m == 32 || m == 96) v = 0;
-            else if (m < 64) v = -g[64 - m];
-            else if (m < 96) v = -g[m - 64];
-            else v = g[128 - m];
-            hevc_t32_host[k][i] = (int8_t)v;
-        }
-    for (int n = 4; n <= 32; n *= 2) {
-        const int sc = 32 / n;
-        uint32_t *t = hevc_pk_host + hevc_pk_off(n);
-        for (int j = 0; j < n / 2; j++)
-            for (int q = 0; q < n / 4; q++)
-                for (int odd = 0; odd < 2; odd++) {
-                    const int a = hevc_t32_host[(4 * q + odd) * sc][j], b = hevc_t32_host[(4 * q + 2 + odd) * sc][j];
-                    t[(j * (n / 4) + q) * 2 + odd] = (uint32_t)(a & 0xFFFF) | ((uint32_t)b << 16);
-                }
-    }
-}
-
-__device__ __forceinline__ int hevc_clip16(int v) { return min(max(v, -32768), 32767); }
-
-/* one 1-D pass over the vector at src (stride sstep int16) into dst (stride dstep): N outputs */
-template <int N>
-__device__ __forceinline__ void hevc_pass(int16_t *dst, int dstep, const int16_t *src, int sstep, int end, int shift)
-{
-    constexpr int SC = 32 / N;
-    int s[N];
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        bool keep = true;
-        if (N > 4) {
-            if (k & 1) keep = k < end;
-            else if (N == 32 && (k & 3) == 2) keep = (k >> 1) < (end >> 1);
-        }
-        const int v = src[k * sstep];
-        s[k] = keep ? v : 0;
-    }
-    const int add = 1 << (shift - 1);
-    /* inputs as int16 pairs (s[4q], s[4q+2]) and (s[4q+1], s[4q+3]): two multiply-adds per v_dot2_i32_i16 against the
-     * wave-uniform coefficient pairs */
-    typedef short hv_s2 __attribute__((ext_vector_type(2)));
-    hv_s2 pe[N / 4], po[N / 4];
-#pragma unroll
-    for (int q = 0; q < N / 4; q++) {
-        pe[q] = hv_s2{ (short)s[4 * q], (short)s[4 * q + 2] };
-        po[q] = hv_s2{ (short)s[4 * q + 1], (short)s[4 * q + 3] };
-    }
-    const uint32_t *tab = hevc_pk + hevc_pk_off(N);
-    (void)SC;
-#pragma unroll
-    for (int j = 0; j < N / 2; j++) {
-        int e = 0, o = 0;
-#pragma unroll
-        for (int q = 0; q < N / 4; q++) {
-            e = __builtin_amdgcn_sdot2(pe[q], __builtin_bit_cast(hv_s2, tab[(j * (N / 4) + q) * 2]), e, false);
-            o = __builtin_amdgcn_sdot2(po[q], __builtin_bit_cast(hv_s2, tab[(j * (N / 4) + q) * 2 + 1]), o, false);
-        }
-        dst[j * dstep] = (int16_t)hevc_clip16((e + o + add) >> shift);
-        dst[(N - 1 - j) * dstep] = (int16_t)hevc_clip16((e - o + add) >> shift);
-    }
-}
-
-__device__ __forceinline__ void hevc_dst4(int16_t *dst, const int16_t *src, int step, int shift)
-{
-    const int add = 1 << (shift - 1);
-    const int s0 = src[0], s1 = src[step], s2 = src[2 * step], s3 = src[3 * step];
-    const int c0 = s0 + s2, c1 = s2 + s3, c2 = s0 - s3, c3 = 74 * s1;
-    dst[0]        = (int16_t)hevc_clip16((29 * c0 + 55 * c1 + c3 + add) >> shift);
-    dst[step]     = (int16_t)hevc_clip16((55 * c2 - 29 * c1 + c3 + add) >> shift);
-    dst[2 * step] = (int16_t)hevc_clip16((74 * (s0 - s2 + s3) + add) >> shift);
-    dst[3 * step] = (int16_t)hevc_clip16((55 * c0 + 29 * c2 - c3 + add) >> shift);
-}
-
-__device__ __forceinline__ void hevc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+__constant__ uint32_t hevc_pk[352]; /* hevc_tx_rules.h's table image for this code object */
 
 /* bd: the depth the template was instantiated for in the reference (hevc/dsp.c:133-196): it sets the second-pass shift 20 - bd, the
  * DC shift 14 - bd, dequant's 15 - bd - log2 and the pixel type / clip of add_residual (uint16_t above 8 bits, stride in bytes) */
@@ -165,9 +69,9 @@ __global__ __launch_bounds__(256) void k_hevc_idct(int kind, int16_t *coeffs, ui
         for (int c = 4; c < i; c += 4)
             if (limit2 < N)
                 limit2 -= 4;
-        hevc_pass<N>(mine + i, N, mine + i, N, limit2, 7);
+        hevc_pass<N>(mine + i, N, mine + i, N, limit2, 7, hevc_pk);
         hevc_wave_sync();
-        hevc_pass<N>(mine + i * N, 1, mine + i * N, 1, limit, 20 - bd);
+        hevc_pass<N>(mine + i * N, 1, mine + i * N, 1, limit, 20 - bd, hevc_pk);
     } else if (kind == FFHIP_HEVC_IDCT_DC) {
         const int v = ((((int)mine[0] + 1) >> 1) + (1 << (13 - bd))) >> (14 - bd);
         hevc_wave_sync();
@@ -256,26 +160,6 @@ __global__ __launch_bounds__(256) void k_hevc_idct(int kind, int16_t *coeffs, ui
  * to the picture (8-bit or 16-bit samples).  The VALU kernel above needs N^2/4 = 256 v_dot2 per vector with a scalar coefficient
  * load behind each (measured 14 % of the dot issue rate); here the contraction costs 4 MFMAs per block.
  */
-typedef int hm_i4 __attribute__((ext_vector_type(4)));
-typedef int hm_i16 __attribute__((ext_vector_type(16)));
-struct HevcMfmaTab { int8_t b1[64][16], b2[64][16]; int32_t sum[32]; }; /* sum[j] = 128 * sum_k T[k][j] */
-static std::once_flag hm_once;
-
-__device__ __forceinline__ bool hm_keep(int k, int end) /* hevc_pass<32>'s rule */
-{
-    return (k & 1) ? k < end : ((k & 3) == 2 ? (k >> 1) < (end >> 1) : true);
-}
-/* 16 int16 values -> the high-byte plane and the (low byte - 128) plane, 4 bytes per dword in order */
-__device__ __forceinline__ void hm_split(const int (&v)[16], hm_i4 &hi, hm_i4 &lo)
-{
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t p01 = ((uint32_t)v[4 * q] & 0xFFFFu) | ((uint32_t)v[4 * q + 1] << 16);
-        const uint32_t p23 = ((uint32_t)v[4 * q + 2] & 0xFFFFu) | ((uint32_t)v[4 * q + 3] << 16);
-        hi[q] = (int)__builtin_amdgcn_perm(p23, p01, 0x07050301u);
-        lo[q] = (int)(__builtin_amdgcn_perm(p23, p01, 0x06040200u) ^ 0x80808080u);
-    }
-}
 
 __global__ __launch_bounds__(256) void k_hevc_idct32_mfma(int16_t *coeffs, uint8_t *dst, ptrdiff_t stride, const FFHipHevcTU *tus, int n, int bd,
                                                           const HevcMfmaTab *tab)
@@ -305,54 +189,7 @@ __global__ __launch_bounds__(256) void k_hevc_idct32_mfma(int16_t *coeffs, uint8
             reinterpret_cast<uint32_t *>(L + rr * 32 + 16 * rh)[k] = reinterpret_cast<const uint32_t *>(rowp)[k];
     }
     hevc_wave_sync();
-    const int c = lane & 31, g = lane >> 5;
-    const hm_i4 B1 = reinterpret_cast<const hm_i4 *>(tab->b1)[lane], B2 = reinterpret_cast<const hm_i4 *>(tab->b2)[lane];
-    const int sum_t = tab->sum[c];
-    /* ---- pass 1: my column c, rows 16 g .. 16 g + 15; limit2 has shrunk by 4 for every column 4, 8, ... before mine ---- */
-    int limit2 = min(col_limit + 4, 32);
-    for (int q = 4; q < c; q += 4)
-        if (limit2 < 32)
-            limit2 -= 4;
-    int v[16];
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-        const int k = 16 * g + s, x = L[k * 32 + c];
-        v[s] = hm_keep(k, limit2) ? x : 0;
-    }
-    hm_i4 ahi, alo;
-    hm_split(v, ahi, alo);
-    hm_i16 acc = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(ahi, B1, acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-        acc[r] = (int)(((uint32_t)acc[r] << 8) + (uint32_t)(sum_t + 64));
-    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(alo, B1, acc, 0, 0, 0);
-    /* ---- Y[j = c][cc], cc = (r & 3) + 8 (r >> 2) + 4 g: >> 7, clip, the second pass's limit ---- */
-    const int limit = min(col_limit, 32);
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int cc = (r & 3) + 8 * (r >> 2) + 4 * g;
-        const int y = hevc_clip16(acc[r] >> 7);
-        v[r] = hm_keep(cc, limit) ? y : 0;
-    }
-    hm_split(v, ahi, alo);
-    const int shift2 = 20 - bd;
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-        acc[r] = 0;
-    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(ahi, B2, acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-        acc[r] = (int)(((uint32_t)acc[r] << 8) + (uint32_t)(sum_t + (1 << (shift2 - 1))));
-    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(alo, B2, acc, 0, 0, 0);
-    /* ---- Z[j][m = c], j = (r & 3) + 8 (r >> 2) + 4 g: back through LDS into rows; residual in place, picture += residual ---- */
-    hevc_wave_sync(); /* every lane has read its inputs */
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int j = (r & 3) + 8 * (r >> 2) + 4 * g;
-        L[j * 32 + c] = (int16_t)hevc_clip16(acc[r] >> shift2);
-    }
-    hevc_wave_sync();
+    hevc_idct32_mfma_lds(lds, wave, col_limit, bd, tab, lane);
     const uint4 r0 = reinterpret_cast<const uint4 *>(L + rr * 32 + 16 * rh)[0], r1 = reinterpret_cast<const uint4 *>(L + rr * 32 + 16 * rh)[1];
     const uint32_t rw[8] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w };
     if (al16) {
@@ -488,87 +325,6 @@ __global__ __launch_bounds__(256) void k_hevc_idct16_mfma(int16_t *coeffs, uint8
     ffhip_add_row<8>(dst + rtu.dst_offset + (ptrdiff_t)rr * stride + 8 * rh * (bd > 8 ? 2 : 1), z, bd);
 }
 
-/* the host tables are built once; their device copies (the __constant__ hevc_pk image and the two MFMA operand tables) exist per
- * device, uploaded when a device first runs a transform */
-static HevcMfmaTab *g_hm_tab16_dev[64];
-static HevcMfmaTab *g_hm_tab_dev[64];
-static HevcMfmaTab hm_host, hm_host16;
-static FFHipPerDeviceOnce hevc_pk_dev_once, hm_dev_once;
-
-static int hevc_pk_upload()
-{
-    std::call_once(hevc_tab_once, [] { hevc_build_table(); });
-    if (hevc_pk_dev_once.enter()) {
-        const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(hevc_pk), hevc_pk_host, sizeof(hevc_pk_host));
-        hevc_pk_dev_once.leave(e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_hevc_idct: coefficient table upload failed: %s", hipGetErrorString(e));
-            return FFHIP_EIO;
-        }
-    }
-    return 0;
-}
-
-static int hm_tab_init()
-{
-    const int r = hevc_pk_upload();
-    if (r < 0)
-        return r;
-    std::call_once(hm_once, [] {
-        HevcMfmaTab &h = hm_host;
-        for (int l = 0; l < 64; l++) {
-            const int j = l & 31, g = l >> 5;
-            for (int s = 0; s < 16; s++) {
-                h.b1[l][s] = hevc_t32_host[16 * g + s][j];                              /* T[k = 16 g + s][j]               */
-                h.b2[l][s] = hevc_t32_host[(s & 3) + 8 * (s >> 2) + 4 * g][j];        /* T[c = the D row of register s][m] */
-            }
-        }
-        for (int j = 0; j < 32; j++) {
-            int t = 0;
-            for (int k = 0; k < 32; k++)
-                t += hevc_t32_host[k][j];
-            h.sum[j] = 128 * t;
-        }
-        /* the block-diagonal pair of 16-point matrices (T16[k][j] = T32[2 k][j]): slot s of group g belongs to unit s >> 3 and is
-         * row 8 g + (s & 7) of T16 in pass 1, row (s & 3) + 8 ((s >> 2) & 1) + 4 g in pass 2 */
-        HevcMfmaTab &h16 = hm_host16;
-        for (int l = 0; l < 64; l++) {
-            const int jp = l & 31, g = l >> 5, j = jp & 15;
-            for (int sl = 0; sl < 16; sl++) {
-                const bool mine = (sl >> 3) == (jp >> 4);
-                h16.b1[l][sl] = mine ? hevc_t32_host[2 * (8 * g + (sl & 7))][j] : 0;
-                h16.b2[l][sl] = mine ? hevc_t32_host[2 * ((sl & 3) + 8 * ((sl >> 2) & 1) + 4 * g)][j] : 0;
-            }
-        }
-        for (int jp = 0; jp < 32; jp++) {
-            int t = 0;
-            for (int k = 0; k < 16; k++)
-                t += hevc_t32_host[2 * k][jp & 15];
-            h16.sum[jp] = 128 * t;
-        }
-    });
-    if (hm_dev_once.enter()) {
-        const int d = ffhip_current_device();
-        HevcMfmaTab *t32 = nullptr, *t16 = nullptr;
-        const bool ok = hipMalloc(reinterpret_cast<void **>(&t32), sizeof(HevcMfmaTab)) == hipSuccess &&
-                        hipMalloc(reinterpret_cast<void **>(&t16), sizeof(HevcMfmaTab)) == hipSuccess &&
-                        hipMemcpy(t32, &hm_host, sizeof(HevcMfmaTab), hipMemcpyHostToDevice) == hipSuccess &&
-                        hipMemcpy(t16, &hm_host16, sizeof(HevcMfmaTab), hipMemcpyHostToDevice) == hipSuccess;
-        if (ok) {
-            g_hm_tab_dev[d] = t32;
-            g_hm_tab16_dev[d] = t16;
-        } else {
-            (void)hipFree(t32);
-            (void)hipFree(t16);
-        }
-        hm_dev_once.leave(ok);
-        if (!ok) {
-            ffhip_set_error("ffhip_hevc_idct: table upload failed");
-            return FFHIP_EIO;
-        }
-    }
-    return 0;
-}
 
 int ffhip_launch_hevc_idct(int kind, int log2_size, int16_t *coeffs, uint8_t *dst, ptrdiff_t stride, const FFHipHevcTU *tus, int n,
                            hipStream_t stream)
@@ -586,14 +342,14 @@ int ffhip_launch_hevc_idct_bd(int bd, int kind, int log2_size, int16_t *coeffs, 
         return FFHIP_EINVAL;
     }
     {
-        const int r = hevc_pk_upload();
+        const int r = hevc_pk_upload(HIP_SYMBOL(hevc_pk), "ffhip_hevc_idct");
         if (r < 0)
             return r;
     }
     {
         const char *eo = FFHIP_KNOB("FFHIP_HEVC_IDCT32_VALU"); /* measured variant: the dot2 kernel for 32x32 as well */
         if (kind == FFHIP_HEVC_IDCT && log2_size == 5 && !(eo && eo[0] == '1')) {
-            const int r = hm_tab_init();
+            const int r = hm_tab_init("ffhip_hevc_idct");
             if (r < 0)
                 return r;
             hipLaunchKernelGGL(k_hevc_idct32_mfma, dim3(cdiv(n, 4)), dim3(256), 0, stream, coeffs, dst, stride, tus, n, bd, g_hm_tab_dev[ffhip_current_device()]);
@@ -604,7 +360,7 @@ int ffhip_launch_hevc_idct_bd(int bd, int kind, int log2_size, int16_t *coeffs, 
          * work is discarded and whose columns move through LDS 2 bytes at a time); the latter stays as a measured variant */
         const char *e16 = FFHIP_KNOB("FFHIP_HEVC_IDCT16_MFMA");
         if (kind == FFHIP_HEVC_IDCT && log2_size == 4 && e16 && e16[0] == '1') {
-            const int r = hm_tab_init();
+            const int r = hm_tab_init("ffhip_hevc_idct");
             if (r < 0)
                 return r;
             hipLaunchKernelGGL(k_hevc_idct16_mfma, dim3(cdiv(n, 8)), dim3(256), 0, stream, coeffs, dst, stride, tus, n, bd, g_hm_tab16_dev[ffhip_current_device()]);

@@ -284,6 +284,43 @@ def loop_filter_pictures(pics, width, height, log2_ctb_size, log2_min_cb_size, c
                       "ffhip_hevc_loop_filter_pictures_dev")
 
 
+RES_DCT, RES_DC, RES_DST, RES_SKIP, RES_BYPASS, RES_ZERO = 0, 1, 2, 3, 4, 5
+RES_ROTATE, RES_RDPCM_H, RES_RDPCM_V, RES_CROSS = 0x08, 0x10, 0x20, 0x40
+
+#: FFHipHevcResTU (include/ffhip.h): one transform unit of ffhip_hevc_residual_pictures_dev; kind_flags = kind | RES_* flags
+RES_TU_DTYPE = np.dtype([("coeff_offset", np.int32), ("res_offset", np.int32), ("luma", np.int32), ("log2_size", np.uint8),
+                         ("kind_flags", np.uint8), ("res_scale_val", np.int8), ("col_limit", np.uint8)])
+
+
+class ResPlane(C.Structure):
+    """FFHipHevcResPlane (device pointers, lengths in int16 elements)"""
+    _fields_ = [("coeffs", C.c_void_p), ("ncoeffs", C.c_int32), ("nres", C.c_int32), ("res", C.c_void_p), ("tus", C.c_void_p),
+                ("size_start", C.c_int32 * 5), ("pad", C.c_int32)]
+
+
+class ResPic(C.Structure):
+    """FFHipHevcResPic"""
+    _fields_ = [("plane", ResPlane * 3)]
+
+
+def residual_pictures(pics, chroma_format_idc=1, stream=None, bit_depth=8):
+    """ffhip_hevc_residual_pictures_dev on npics = len(pics) pictures.  pics[i]: one tuple per plane (1 for chroma_format_idc 0,
+    else 3) of (coeffs, res, tus, size_start): coeffs / res int16 device tensors (their lengths are the planes' ncoeffs / nres), tus
+    a device tensor of RES_TU_DTYPE records as bytes grouped by log2_size, size_start 5 ints (size 2 + s is records size_start[s] ..
+    size_start[s + 1]).  Asynchronous on `stream`."""
+    arr = (ResPic * max(len(pics), 1))()
+    for i, planes in enumerate(pics):
+        for p, (coeffs, res, tus, size_start) in enumerate(planes):
+            pl = arr[i].plane[p]
+            pl.coeffs, pl.ncoeffs = coeffs.data_ptr(), coeffs.numel()
+            pl.res, pl.nres = res.data_ptr(), res.numel()
+            pl.tus = tus.data_ptr()
+            for s in range(5):
+                pl.size_start[s] = int(size_start[s])
+    return _lib.check(_lib.lib().ffhip_hevc_residual_pictures_dev(bit_depth, chroma_format_idc, len(pics), C.cast(arr, C.c_void_p),
+                                                                  _stream(stream)), "ffhip_hevc_residual_pictures_dev")
+
+
 class HEVCPredContext(C.Structure):
     """FFHipHEVCPredContext == HEVCPredContext: intra_pred[] is the decoder's and is left alone"""
     _fields_ = [("intra_pred", C.c_void_p * 4),

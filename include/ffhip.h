@@ -1740,6 +1740,75 @@ int ffhip_hevc_loop_filter_pictures_dev(int bit_depth, int chroma_format_idc, in
 /** sizeof(FFHipHevcLfCtb), for bindings that mirror the record (no device needed). */
 int ffhip_hevc_lf_ctb_record_size(void);
 
+/** Residuals of whole pictures in one launch: every transform unit of up to 16 pictures turned from its scaled coefficients into the
+ *  final residual that the intra and inter picture faces take (their TU records' res_offset points at it).
+ *
+ *  Input: the scaled TransCoeffLevel values the reference's HEVCDSPContext members receive; the decoder has applied the scaling
+ *  process and scaling lists while parsing (ff_hevc_hls_residual_coding).
+ *  Semantics: each record runs, in this order, rotate -> its kind's operation -> RDPCM -> cross-component, with int16 storage between
+ *  steps, byte for byte what the reference's per-call members produce in that order at bit_depth (libavcodec/hevc/dsp_template.c):
+ *    DCT     idct[log2 - 2](c, col_limit)            DC      idct_dc[log2 - 2](c)
+ *    DST     transform_4x4_luma(c), log2 2 only      SKIP    dequant(c, log2) (the tsShift scaling of transform skip)
+ *    BYPASS  nothing: the coefficients are the residual (cu_transquant_bypass)
+ *    ZERO    the residual is 0 and coeffs are not read (cbf 0; only useful as the luma of _CROSS or with _CROSS itself); its
+ *            coeff_offset is still checked like any other, so point it at an in-range span (e.g. 0)
+ *    _ROTATE     SKIP / BYPASS at log2 2: c[i] <-> c[15 - i] first (transform_skip_rotation_enabled_flag, cabac.c)
+ *    _RDPCM_H/V  SKIP / BYPASS: transform_rdpcm(c, log2, 0 / 1) after the kind's operation
+ *    _CROSS      planes 1 and 2 of chroma format 3 only: r[i] = (int16)(r[i] + ((res_scale_val * rY[i]) >> 3)) last, rY the FINAL
+ *                residual of record `luma` of plane 0 of the same picture (0 for a luma ZERO record)
+ *  The decoder decides, the face applies: it derives no implicit RDPCM, rotation or cross-component from SPS / PPS flags or intra
+ *  modes.  The output depends neither on record order nor on the launch layout: a _CROSS record recomputes its luma residual itself
+ *  and does not rely on the luma record having run.
+ *  Malformed records write nothing and read nothing outside their planes: log2_size outside 2..5 or not that of its size_start
+ *  group; an unknown kind or the reserved bit 0x80; DST or _ROTATE at log2 != 2; _ROTATE or an RDPCM flag on a kind other than
+ *  SKIP / BYPASS, or both RDPCM flags set; _CROSS outside planes 1 / 2 of chroma format 3, res_scale_val not in {0, +-1, +-2, +-4, +-8}, `luma` out of plane 0's
+ *  records, or a luma record that is of another size, carries _CROSS or is itself malformed; an offset not a multiple of 16, or
+ *  offset + N*N beyond ncoeffs / nres.
+ *  Written: the N*N residuals of each well-formed record and nothing else; coeffs is never written.  Trusted: the res ranges of one
+ *  plane's records are disjoint (where two overlap the values in the overlap are undefined and nothing else is affected).
+ *  Out of scope: extended_precision_processing_flag, scaling (the decoder's), boundary strengths. */
+#define FFHIP_HEVC_RES_DCT      0
+#define FFHIP_HEVC_RES_DC       1
+#define FFHIP_HEVC_RES_DST      2
+#define FFHIP_HEVC_RES_SKIP     3
+#define FFHIP_HEVC_RES_BYPASS   4
+#define FFHIP_HEVC_RES_ZERO     5
+#define FFHIP_HEVC_RES_KIND     0x07 /* kind_flags & FFHIP_HEVC_RES_KIND: the kind */
+#define FFHIP_HEVC_RES_ROTATE   0x08
+#define FFHIP_HEVC_RES_RDPCM_H  0x10
+#define FFHIP_HEVC_RES_RDPCM_V  0x20
+#define FFHIP_HEVC_RES_CROSS    0x40
+typedef struct FFHipHevcResTU {     /* one transform unit of one plane, 16 bytes */
+    int32_t coeff_offset;           /* int16 units into the plane's coeffs: N*N scaled coefficients, row-major; a multiple of 16 */
+    int32_t res_offset;             /* int16 units into the plane's res: the N*N residuals go here; a multiple of 16 */
+    int32_t luma;                   /* _CROSS: index of the co-located luma record in plane 0's tus of the same picture */
+    uint8_t log2_size;              /* 2..5 */
+    uint8_t kind_flags;             /* bits 0-2 the kind, then the flags above */
+    int8_t  res_scale_val;          /* _CROSS: ResScaleVal, one of 0, +-1, +-2, +-4, +-8 */
+    uint8_t col_limit;              /* DCT: the col_limit cabac.c computes from the last significant position */
+} FFHipHevcResTU;
+typedef struct FFHipHevcResPlane {  /* device pointers, host lengths */
+    const int16_t *coeffs;          /* read only */
+    int32_t ncoeffs;                /* int16 elements of coeffs */
+    int32_t nres;                   /* int16 elements of res */
+    int16_t *res;
+    const FFHipHevcResTU *tus;      /* grouped by log2_size, ascending */
+    int32_t size_start[5];          /* size 2 + s is tus[size_start[s] .. size_start[s + 1]); size_start[0] == 0, non-decreasing */
+    int32_t pad;
+} FFHipHevcResPlane;
+typedef struct FFHipHevcResPic {
+    FFHipHevcResPlane plane[3];     /* Y, Cb, Cr; chroma_format_idc 0: plane[0] only */
+} FFHipHevcResPic;
+/** npics pictures, bit_depth 8, 10 or 12, chroma_format_idc 0..3.  Pictures go 16 to a launch; asynchronous on `stream`.
+ *  A plane with records needs non-NULL, 16-byte aligned coeffs, res and tus (a plane without records is not looked at).
+ *  FFHIP_EINVAL for another depth or chroma format, npics <= 0, a NULL picture array, NULL or misaligned pointers of a used plane, a
+ *  size_start that does not start at 0 or decreases, negative lengths, or any res range of the call ([res, res + nres)) that
+ *  overlaps any coeffs range of the call or the res range of another plane or picture; FFHIP_ENOSYS without a device. */
+int ffhip_hevc_residual_pictures_dev(int bit_depth, int chroma_format_idc, int npics, const FFHipHevcResPic *pics /* host array */,
+                                     void *stream);
+/** sizeof(FFHipHevcResTU), for bindings that mirror the record (no device needed). */
+int ffhip_hevc_res_tu_record_size(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* libavcodec: vp9dsp inverse transforms                                    */
 /* ------------------------------------------------------------------------------------------ */
