@@ -869,11 +869,7 @@ __global__ __launch_bounds__(256) void k_sws_down2_rgb(FFHipDn2RgbArgs A)
     }
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
-    uint32_t blk = blockIdx.x;
-    if (A.xcd) {
-        const uint32_t nb = gridDim.x, x = blk & 7u, sl = blk >> 3, q = nb >> 3, r = nb & 7u;
-        blk = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + sl;
-    }
+    const uint32_t blk = sws_block_numbering(blockIdx.x, gridDim.x, A.xcd ? 1 : 0); /* an eighth of the launch per XCD */
     const uint32_t gw = blk * 4u + (uint32_t)wave;
     const uint32_t upf = (uint32_t)A.ncb * (uint32_t)A.nstrips;
     if (gw >= upf * (uint32_t)A.nframes)
@@ -889,13 +885,7 @@ __global__ __launch_bounds__(256) void k_sws_down2(FFHipDn2Args A)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
-    uint32_t blk = blockIdx.x;
-    if (A.xcd) {
-        /* workgroup b runs on XCD b % 8 (observed, not promised: speed only): every XCD gets one contiguous eighth of the units,
-         * so that the waves sharing source lines (adjacent column blocks, the halo rows of adjacent strips) meet in one L2 */
-        const uint32_t nb = gridDim.x, x = blk & 7u, sl = blk >> 3, q = nb >> 3, r = nb & 7u;
-        blk = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + sl;
-    }
+    const uint32_t blk = sws_block_numbering(blockIdx.x, gridDim.x, A.xcd ? 1 : 0); /* an eighth of the launch per XCD */
     const uint32_t gw = blk * 4u + (uint32_t)wave;
     if (gw >= (uint32_t)A.units_per_frame * (uint32_t)A.nframes)
         return;

@@ -6,6 +6,28 @@
 #include <stddef.h>
 #include <stdint.h>
 
+/* The workgroup numbering of the batch kernels (k_sws_up2, k_sws_down2, k_sws_down2_rgb, k_yuv420p_rgb24_t): workgroup b of a launch
+ * of nb takes the units of workgroup sws_block_numbering(b, nb, mode).  Workgroup b runs on XCD b % 8 (observed, not promised: speed
+ * only), so that the waves sharing source lines meet in one L2.  mode 0: plain; 1: every XCD one contiguous eighth of the launch, in
+ * order (the first nb % 8 XCDs one workgroup more); 1 + k: XCD-contiguous chunks of 2^k workgroups dealt round-robin, the eight XCDs'
+ * fronts within eight chunks of each other — the workgroups at and above nb & ~(8 * 2^k - 1) keep their own number.  Every mode is a
+ * permutation of [0, nb) for every nb (tests/test_sws_numbering_cpu.py, through ffhip_sws_block_numbering_host). */
+__host__ __device__ __forceinline__ uint32_t sws_block_numbering(uint32_t b, uint32_t nb, int mode)
+{
+    if (mode == 1) {
+        const uint32_t x = b & 7u, sl = b >> 3, q = nb >> 3, r = nb & 7u;
+        return (x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + sl;
+    }
+    if (mode > 1) {
+        const uint32_t lg = (uint32_t)mode - 1u, C = 1u << lg, full = nb & ~(8u * C - 1u);
+        if (b < full) {
+            const uint32_t x = b & 7u, sl = b >> 3;
+            return (((sl >> lg) << 3) + x) * C + (sl & (C - 1u));
+        }
+    }
+    return b;
+}
+
 /* closed-form yuv2rgb constants, all int32 (checked at context creation) */
 struct FFHipYuv2RgbK {
     int cy;
@@ -25,8 +47,8 @@ struct FFHipYuv2RgbArgs {
     int dst_y0;                      /* srcSliceY: first destination row */
     int nframes;
     int flat;                        /* set by the launcher: chunks numbered through the frame's row pairs (k_yuv420p_rgb24_t) */
-    int xcd;                         /* workgroup numbering of k_yuv420p_rgb24_t: 0 plain; 1 an eighth of the launch per XCD (chosen per context by the
-                                      * launch tuner of sws_api.hip: which of the two is faster depends on the box, profiles/r06_arena_offset_sweep.txt);
+    int xcd;                         /* sws_block_numbering mode of k_yuv420p_rgb24_t: 0 plain; 1 an eighth of the launch per XCD (chosen per context by
+                                      * the launch tuner of sws_api.hip: which of the two is faster depends on the box, profiles/r06_arena_offset_sweep.txt);
                                       * 1 + k (measure build): XCD-contiguous chunks of 2^k workgroups dealt round-robin */
     FFHipYuv2RgbK k;
     /* the converter's other forms (yuv2rgb.c:238-320, 540-553: YUV422FUNC, yuva2rgba_c / yuva2argb_c, yuv420p_gbrp_c) */

@@ -1347,6 +1347,15 @@ extern "C" int ffhip_sws_down2_virtual_bank_host(const int16_t *filter, const in
     return 1;
 }
 
+extern "C" int ffhip_sws_block_numbering_host(int mode, uint32_t nb, uint32_t *out)
+{
+    if (mode < 0 || mode > 8 || nb == 0 || !out)
+        return FFHIP_EINVAL;
+    for (uint32_t b = 0; b < nb; b++)
+        out[b] = sws_block_numbering(b, nb, mode);
+    return 0;
+}
+
 extern "C" int ffhip_sws_d32_virtual_bank_host(const int16_t *filter, const int32_t *pos, int fsize, int n_dst, int n_src, uint32_t *out)
 {
     std::vector<uint32_t> v;

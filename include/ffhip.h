@@ -313,7 +313,7 @@ void             ffhip_sws_freeContext(FFHipSwsContext *c);
  *  Diagnostic only: results are identical. */
 int              ffhip_sws_fast_path(const FFHipSwsContext *c);
 /** Diagnostic: the workgroup numbering the context's launch tuner settled on for large launches of the table converter
- *  (yuv2rgb_c_24_rgb's replacement, libswscale/yuv2rgb.c:530) — -1 undecided (fewer than four large launches so far), 0 plain,
+ *  (yuv2rgb_c_24_rgb's replacement, libswscale/yuv2rgb.c:530) — -1 undecided (fewer than eight large launches so far), 0 plain,
  *  1 an eighth of the launch per XCD.  Which one is faster is a property of the box; results are identical. */
 int              ffhip_sws_tuned_numbering(const FFHipSwsContext *c);
 /** Host-side preparation of the matrix-core horizontal pass (no device needed): turns one 4-tap horizontal
@@ -347,6 +347,10 @@ int              ffhip_sws_down2_virtual_bank_host(const int16_t *filter, const 
  *  even) as six coefficients per output on the regular window 3 (x >> 1) - 2 + (x & 1) .. + 5 of the edge-replicated row.  out: n_dst x 3
  *  dwords, (c0, c1) (c2, c3) (c4, c5).  Returns 1, or 0 when some tap does not sit on its regular window. */
 int              ffhip_sws_d32_virtual_bank_host(const int16_t *filter, const int32_t *pos, int fsize, int n_dst, int n_src, uint32_t *out);
+/** The workgroup numbering of the swscale batch kernels (sws_block_numbering, the same inline function the kernels call): out[b] =
+ *  the units workgroup b of a launch of nb workgroups takes, for every b < nb.  mode 0 plain, 1 an eighth of the launch per XCD, 1 + k
+ *  XCD-contiguous chunks of 2^k workgroups dealt round-robin.  Returns 0, or FFHIP_EINVAL for a mode outside 0..8 or nb == 0. */
+int              ffhip_sws_block_numbering_host(int mode, uint32_t nb, uint32_t *out);
 
 /** Host-table generation alone (no device needed): our initFilter().  `which`: 0 hLum 1 hChr 2 vLum
  *  3 vChr.  Returns filter size or <0; pointers stay valid until ffhip_sws_tables_free().  Used by

@@ -130,6 +130,9 @@ def test_argument_validation():
     assert L.ffhip_tx_init(C.byref(ctx), C.byref(fn), 2, 0, 1024, C.byref(sc), 0) == -38         # AV_TX_DOUBLE_FFT: not on the hip path
     assert L.ffhip_hevc_idct_batch_dev(0, 7, None, None, 0, None, 1, None) == EINVAL
     assert L.ffhip_fdsp_batch_dev(99, None, 0, None, 0, None, 0, None, 0, 0.0, 4, 1, None) == EINVAL
+    out = (C.c_uint32 * 8)()
+    assert L.ffhip_sws_block_numbering_host(9, 8, out) == EINVAL                                   # modes are 0..8
+    assert L.ffhip_sws_block_numbering_host(1, 0, out) == EINVAL                                   # an empty launch
 
 
 def test_host_tables_are_device_free():
