@@ -109,6 +109,7 @@ __device__ __forceinline__ void ffhip_add_row(uint8_t *d8, const int (&z)[NS], i
 int   ffhip_scratch_reserve(size_t bytes, void **dev);
 int   ffhip_have_device(void);     /* also binds a thread that never chose a device to the process default (runtime.hip) */
 int   ffhip_current_device(void);  /* the calling thread's HIP device */
+int   ffhip_cu_count(void);        /* the current device's compute units, queried once per device (runtime.hip) */
 #ifdef __cplusplus
 #include <mutex>
 #include <vector>
@@ -142,5 +143,13 @@ struct FFHipPerDeviceOnce {
 #else
 #define FFHIP_KNOB(name) ((const char *)0)
 #endif
+
+/* a knob whose first character is `v` (never, in the product build) */
+static inline bool knob_is(const char *name, char v)
+{
+    const char *e = FFHIP_KNOB(name);
+    (void)name;
+    return e && e[0] == v;
+}
 
 #endif

@@ -20,6 +20,7 @@
  * tests/test_gpu_tx.py), not bit for bit.  FFHIP_TX_RADIX=0 selects the split-radix kernels.
  */
 #include "common.h"
+#include "tx_host.h"
 #include "tx_kernels.h"
 #include "tx_radix_core.h"
 
@@ -152,14 +153,7 @@ int frw_go(const c32 *wtab, const float *in, size_t in_pitch, float *out, size_t
         (void)hipFuncSetAttribute((const void *)k_fft_rw<LG, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr.leave(true);
     }
-    int cus = 256, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-        cus = prop.multiProcessorCount;
-    int per_cu = (int)((160 * 1024) / (((lds + 1279) / 1280) * 1280));
-    if (per_cu * (T / 64) > 32) per_cu = 32 / (T / 64);
-    if (per_cu < 1) per_cu = 1;
-    const int blocks = nt < cus * per_cu ? nt : cus * per_cu;
+    const int blocks = tx_blocks(lds, T / 64, nt);
     hipLaunchKernelGGL((k_fft_rw<LG, INV>), dim3(blocks), dim3(T), lds, stream, wtab, in, in_pitch, out, out_pitch, nt);
     LAUNCH_CHECK();
     return 0;
@@ -266,11 +260,7 @@ __global__ __launch_bounds__(64 * FR_WAVES) void k_mdct_r(const c32 *wtab, const
 
 int fr_blocks(int nt)
 {
-    int cus = 256, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-        cus = prop.multiProcessorCount;
-    const int want = (nt + FR_WAVES - 1) / FR_WAVES, cap = cus * 4;
+    const int want = (nt + FR_WAVES - 1) / FR_WAVES, cap = ffhip_cu_count() * 4;
     return want < cap ? want : cap;
 }
 

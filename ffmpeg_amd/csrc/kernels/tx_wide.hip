@@ -26,9 +26,8 @@
 #include <vector>
 
 #include "common.h"
+#include "tx_host.h"
 #include "tx_kernels.h"
-
-#define TXW_PAD(i) ((i) + ((i) >> 5))
 
 template <typename T> struct TxwCpx { T re, im; };
 
@@ -122,7 +121,7 @@ __device__ __forceinline__ void txw_fft_lds(TxwCpx<T> *z, const TxwDev &d, int l
     for (int l = 2; l <= d.lg; l++) {
         txw_sync<WG>();
         const int q = 1 << (l - 2);
-        const int o1 = TXW_PAD(q), o2 = TXW_PAD(2 * q), o3 = TXW_PAD(3 * q);
+        const int o1 = TX_PAD(q), o2 = TX_PAD(2 * q), o3 = TX_PAD(3 * q);
         const T *tab = cos_tab + d.cos_off[l];
         const uint32_t *sc = d.sched + d.sched_off[l];
         for (int b = lane; b < d.sched_cnt[l]; b += TS) {
@@ -145,7 +144,7 @@ __global__ __launch_bounds__(1024) void k_txw(TxwDev d, const T *in, size_t in_p
     const int lane = WG ? (int)threadIdx.x : (int)(threadIdx.x & 63);
     const int TS = WG ? (int)blockDim.x : 64;
     const int n = d.n;
-    TxwCpx<T> *z = reinterpret_cast<TxwCpx<T> *>(lds_raw) + (size_t)wave * (TXW_PAD(n) + 1);
+    TxwCpx<T> *z = reinterpret_cast<TxwCpx<T> *>(lds_raw) + (size_t)wave * (TX_PAD(n) + 1);
     const TxwCpx<T> *ex = static_cast<const TxwCpx<T> *>(d.exp);
     for (int t = WG ? (int)blockIdx.x : (int)(blockIdx.x * (blockDim.x >> 6)) + wave; t < nt; t += teams_total) {
         const T *src = reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(in) + (size_t)t * in_pitch);
@@ -184,12 +183,12 @@ __global__ __launch_bounds__(1024) void k_txw(TxwDev d, const T *in, size_t in_p
         if (KIND == 0) {
             TxwCpx<T> *o2 = reinterpret_cast<TxwCpx<T> *>(dst);
             for (int i = lane; i < n; i += TS)
-                o2[i] = z[TXW_PAD(i)];
+                o2[i] = z[TX_PAD(i)];
         } else {
             const int len4 = n >> 1;
             for (int i = lane; i < len4; i += TS) {
                 const int i0 = len4 + i, i1 = len4 - i - 1;
-                const TxwCpx<T> z1 = z[TXW_PAD(i1)], z0 = z[TXW_PAD(i0)], e0 = ex[i0], e1 = ex[i1];
+                const TxwCpx<T> z1 = z[TX_PAD(i1)], z0 = z[TX_PAD(i0)], e0 = ex[i0], e1 = ex[i1];
                 if (KIND == 1) {
                     T a, b, c, f;
                     txw_cmul(a, b, z0.re, z0.im, e0.im, e0.re); /* dst[2 i1 + 1], dst[2 i0] */
@@ -208,39 +207,15 @@ __global__ __launch_bounds__(1024) void k_txw(TxwDev d, const T *in, size_t in_p
 }
 
 /* ---- host ---------------------------------------------------------------------------------------------------------------------- */
-static int txw_sr_perm(int i, int len, int inv) /* split_radix_permutation, libavutil/tx.c:125-135 */
-{
-    len >>= 1;
-    if (len <= 1)
-        return i & 1;
-    if (!(i & len))
-        return txw_sr_perm(i, len, inv) * 2;
-    len >>= 1;
-    return txw_sr_perm(i, len, inv) * 4 + 1 - 2 * (!(i & len) ^ inv);
-}
-
-static void txw_schedule(int o, int n, int lg, std::vector<uint32_t> *lev, std::vector<uint16_t> *b2)
-{
-    if (n == 1)
-        return;
-    if (n == 2) {
-        b2->push_back((uint16_t)TXW_PAD(o));
-        return;
-    }
-    const int q = n >> 2;
-    txw_schedule(o, n >> 1, lg - 1, lev, b2);
-    txw_schedule(o + 2 * q, q, lg - 2, lev, b2);
-    txw_schedule(o + 3 * q, q, lg - 2, lev, b2);
-    for (int k = 0; k < q; k++)
-        lev[lg].push_back((uint32_t)TXW_PAD(o + k) | ((uint32_t)k << 16));
-}
-
 /* RESCALE of TX_INT32 (tx_priv.h:139): the double product goes through llrintf, i.e. is rounded to float first */
 static int32_t txw_rescale(double x)
 {
     long long v = llrintf((float)(x * 2147483648.0));
     return (int32_t)(v < INT32_MIN ? INT32_MIN : v > INT32_MAX ? INT32_MAX : v);
 }
+/* a table value of the sample type: RESCALE, the identity for double */
+template <typename T> static T txw_tab(double x) { return x; }
+template <> int32_t txw_tab<int32_t>(double x) { return txw_rescale(x); }
 
 static size_t txw_elem(const FFHipTxWide *w) { return w->is_int ? sizeof(int32_t) : sizeof(double); }
 
@@ -252,6 +227,54 @@ void ffhip_txw_free(FFHipTxWide *w)
     if (w->dev)
         (void)hipFree(w->dev);
     delete w;
+}
+
+/* the context's tables in one blob: the scatter map, ff_tx_mdct_gen_exp's table (tx_template.c:2107-2134; MDCT only), the level
+ * tables; scale is the caller's float (int32: SCALE_TYPE float) or double */
+template <typename T>
+static int txw_tables(FFHipTxWide *w, double scale)
+{
+    const int n = w->is_mdct ? w->len >> 1 : w->len;
+    int lg = 0;
+    while ((1 << lg) < n)
+        lg++;
+    std::vector<int> map(n);
+    for (int i = 0; i < n; i++)
+        map[-sr_perm(i, n, w->inv) & (n - 1)] = i;
+    for (int i = 0; i < n; i++)
+        map[i] = TX_PAD(map[i]);
+    std::vector<T> ex(w->is_mdct ? (size_t)n * 2 : 16 / sizeof(T), T(0));
+    if (w->is_mdct) {
+        const double theta = (scale < 0 ? n : 0) + 1.0 / 8.0, rt = sqrt(fabs(scale));
+        for (int i = 0; i < n; i++) {
+            const double alpha = M_PI_2 * (i + theta) / n;
+            /* The reference writes cos(alpha) and sin(alpha) side by side; gcc turns such a pair into ONE sincos() call, and glibc's
+             * sincos() cosine is not always cos()'s — n = 2048, i = 1452 differ in the last bit.  A double table keeps that bit, so
+             * "the reference" is the gcc-built libavutil here (what distributions ship, and what oracle/_ref is): call sincos(). */
+            double sn, cs;
+            sincos(alpha, &sn, &cs);
+            ex[2 * i] = txw_tab<T>(cs * rt);
+            ex[2 * i + 1] = txw_tab<T>(sn * rt);
+        }
+    }
+    TxwDev &d = w->d;
+    d.n = n; d.lg = lg;
+    std::vector<T> cosv;
+    std::vector<uint32_t> sched;
+    std::vector<uint16_t> b2;
+    tx_sr_levels(d, lg, 1, cosv, sched, b2, txw_tab<T>);
+    TxBlob blob;
+    const size_t o_map = blob.add(map), o_exp = blob.add(ex), o_cos = blob.add(cosv), o_sched = blob.add(sched), o_b2 = blob.add(b2);
+    const int r = blob.upload(&w->dev, nullptr);
+    if (r < 0)
+        return r;
+    const uint8_t *base = (const uint8_t *)w->dev;
+    d.map = (const int *)(base + o_map);
+    d.exp = base + o_exp;
+    d.cos_tab = base + o_cos;
+    d.sched = (const uint32_t *)(base + o_sched);
+    d.blocks2 = (const uint16_t *)(base + o_b2);
+    return 0;
 }
 
 int ffhip_txw_max_points(int is_int) { return is_int ? 16384 : 8192; }
@@ -273,86 +296,11 @@ int ffhip_txw_create(FFHipTxWide **pw, int is_int, int is_mdct, int inv, int len
     memset(w, 0, sizeof(*w));
     w->device = ffhip_current_device();
     w->inv = !!inv; w->len = len; w->is_int = is_int; w->is_mdct = is_mdct;
-    int lg = 0;
-    while ((1 << lg) < n)
-        lg++;
-    const size_t es = txw_elem(w);
-    std::vector<int> map(n);
-    for (int i = 0; i < n; i++)
-        map[-txw_sr_perm(i, n, w->inv) & (n - 1)] = i;
-    for (int i = 0; i < n; i++)
-        map[i] = TXW_PAD(map[i]);
-    /* ff_tx_mdct_gen_exp (tx_template.c:2107-2134); scale_d is the caller's float (int32: SCALE_TYPE float) or double */
-    std::vector<uint8_t> ex(is_mdct ? (size_t)n * 2 * es : 16, 0);
-    if (is_mdct) {
-        const double theta = (scale < 0 ? n : 0) + 1.0 / 8.0, rt = sqrt(fabs(scale));
-        for (int i = 0; i < n; i++) {
-            const double alpha = M_PI_2 * (i + theta) / n;
-            /* The reference writes cos(alpha) and sin(alpha) side by side; gcc turns such a pair into ONE sincos() call, and glibc's
-             * sincos() cosine is not always cos()'s — n = 2048, i = 1452 differ in the last bit.  A double table keeps that bit, so
-             * "the reference" is the gcc-built libavutil here (what distributions ship, and what oracle/_ref is): call sincos(). */
-            double sn, cs;
-            sincos(alpha, &sn, &cs);
-            if (is_int) {
-                reinterpret_cast<int32_t *>(ex.data())[2 * i] = txw_rescale(cs * rt);
-                reinterpret_cast<int32_t *>(ex.data())[2 * i + 1] = txw_rescale(sn * rt);
-            } else {
-                reinterpret_cast<double *>(ex.data())[2 * i] = cs * rt;
-                reinterpret_cast<double *>(ex.data())[2 * i + 1] = sn * rt;
-            }
-        }
-    }
-    /* ff_tx_init_tab_<m> (tx_template.c:69-79): cos(2 pi i / m), i < m / 4, then an exact 0 */
-    TxwDev &d = w->d;
-    d.n = n; d.lg = lg;
-    std::vector<uint8_t> cosv;
-    int ncos = 0;
-    for (int l = 2; l <= lg; l++) {
-        const int m = 1 << l;
-        const double freq = 2 * M_PI / m;
-        d.cos_off[l] = ncos;
-        cosv.resize((size_t)(ncos + m / 4 + 1) * es, 0);
-        for (int i = 0; i < m / 4; i++) {
-            if (is_int)
-                reinterpret_cast<int32_t *>(cosv.data())[ncos + i] = txw_rescale(cos(i * freq));
-            else
-                reinterpret_cast<double *>(cosv.data())[ncos + i] = cos(i * freq);
-        }
-        ncos += m / 4 + 1;
-    }
-    std::vector<uint32_t> lev[20];
-    std::vector<uint16_t> b2;
-    txw_schedule(0, n, lg, lev, &b2);
-    std::vector<uint32_t> sched;
-    for (int l = 2; l <= lg; l++) {
-        d.sched_off[l] = (int)sched.size();
-        d.sched_cnt[l] = (int)lev[l].size();
-        sched.insert(sched.end(), lev[l].begin(), lev[l].end());
-    }
-    d.nblocks2 = (int)b2.size();
-    size_t off_map = 0, off_exp, off_cos, off_sched, off_b2, total;
-    off_exp = (off_map + map.size() * 4 + 15) & ~(size_t)15;
-    off_cos = (off_exp + ex.size() + 15) & ~(size_t)15;
-    off_sched = (off_cos + cosv.size() + 15) & ~(size_t)15;
-    off_b2 = (off_sched + sched.size() * 4 + 15) & ~(size_t)15;
-    total = (off_b2 + b2.size() * 2 + 16 + 15) & ~(size_t)15;
-    std::vector<uint8_t> blob(total, 0);
-    memcpy(blob.data() + off_map, map.data(), map.size() * 4);
-    memcpy(blob.data() + off_exp, ex.data(), ex.size());
-    memcpy(blob.data() + off_cos, cosv.data(), cosv.size());
-    memcpy(blob.data() + off_sched, sched.data(), sched.size() * 4);
-    memcpy(blob.data() + off_b2, b2.data(), b2.size() * 2);
-    if (hipMalloc(&w->dev, total) != hipSuccess || hipMemcpy(w->dev, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        ffhip_set_error("ffhip_tx_init: table upload failed");
+    const int r = w->is_int ? txw_tables<int32_t>(w, scale) : txw_tables<double>(w, scale);
+    if (r < 0) {
         ffhip_txw_free(w);
-        return FFHIP_ENOMEM;
+        return r;
     }
-    uint8_t *base = (uint8_t *)w->dev;
-    d.map = (const int *)(base + off_map);
-    d.exp = base + off_exp;
-    d.cos_tab = base + off_cos;
-    d.sched = (const uint32_t *)(base + off_sched);
-    d.blocks2 = (const uint16_t *)(base + off_b2);
     *pw = w;
     return 0;
 }
@@ -367,21 +315,12 @@ template <typename T>
 static int txw_launch(const FFHipTxWide *w, void *out, size_t out_pitch, const void *in, size_t in_pitch, int nt, hipStream_t stream)
 {
     const int n = w->d.n;
-    const size_t zb = ((size_t)TXW_PAD(n) + 1) * sizeof(TxwCpx<T>);
+    const size_t zb = ((size_t)TX_PAD(n) + 1) * sizeof(TxwCpx<T>);
     const bool wg = n > 1024;
     const int threads = wg ? (n >= 8192 ? 1024 : 512) : 256;
     const size_t lds = wg ? zb : 4 * zb;
-    int cus = 256, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-        cus = prop.multiProcessorCount;
-    int per_cu = (int)((160 * 1024) / (((lds + 1279) / 1280) * 1280));
-    if (per_cu * (threads / 64) > 32) per_cu = 32 / (threads / 64);
-    if (per_cu < 1) per_cu = 1;
     const int teams_per_block = wg ? 1 : 4;
-    int blocks = cus * per_cu;
-    if (blocks > cdiv(nt, teams_per_block))
-        blocks = cdiv(nt, teams_per_block);
+    const int blocks = tx_blocks(lds, threads / 64, cdiv(nt, teams_per_block));
     const int kind = w->is_mdct ? 1 + w->inv : 0;
 #define TXW_GO(KIND, WG)                                                                                                               \
     do {                                                                                                                               \

@@ -84,6 +84,22 @@ int ffhip_current_device(void)
     return d < FFHIP_MAX_DEVICES ? d : 0;
 }
 
+/* the current device's compute units, queried once per device (256 while the query fails): what the av_tx launch grids are sized by */
+int ffhip_cu_count(void)
+{
+    static std::atomic<int> cus[FFHIP_MAX_DEVICES];
+    const int d = ffhip_current_device();
+    int n = cus[d].load(std::memory_order_relaxed);
+    if (n > 0)
+        return n;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, d) != hipSuccess)
+        return 256;
+    n = prop.multiProcessorCount;
+    cus[d].store(n, std::memory_order_relaxed);
+    return n;
+}
+
 extern "C" int ffhip_set_device(int device)
 {
     if (device < 0 || device >= ffhip_device_count())

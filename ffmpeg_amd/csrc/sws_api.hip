@@ -1373,10 +1373,6 @@ extern "C" void ffhip_sws_freeContext(FFHipSwsContext *c)
     delete c;
 }
 
-/* a knob of the measure build whose first character is `v` (the product build has none: FFHIP_KNOB() is a null constant there) */
-static inline bool knob_is(const char *e, char v) { return e && e[0] == v; }
-#define KNOB_IS(name, v) knob_is(FFHIP_KNOB(name), v)
-
 /* one side of a call: the luma plane and the two chroma channels (address, stride, frame pitch; the channels of an interleaved pair are its
  * first U and V samples), the pair's lower address and whether V comes first in it, and what the fast kernels ask of the planes */
 struct SidePlanes {
@@ -1506,7 +1502,7 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
     ScratchLease wlease;
     bool widened = false;
     if (c->widen8 && (c->w16_ok || c->up2_ok || c->u32_ok) && d.pos && !(d.al() & 3) && cs.pos &&
-        !KNOB_IS(c->up2_ok ? "FFHIP_SWS_UP2" : "FFHIP_SWS_WALK16", '0')) {
+        !knob_is(c->up2_ok ? "FFHIP_SWS_UP2" : "FFHIP_SWS_WALK16", '0')) {
         const int np = sl ? 2 : 3;
         const int wb[3] = { t.srcW, sl ? 2 * c->chrSrcW : c->chrSrcW, c->chrSrcW }, rows[3] = { t.srcH, c->chrSrcH, c->chrSrcH };
         size_t pitch[3], fp[3], off[3], need = 0;
@@ -1536,7 +1532,7 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
     const uintptr_t al = ws.al() | (hrgb ? 0 : d.al()); /* (a packed target is written by the second stage, from the intermediate) */
     const bool neg = ws.neg || d.neg;
     const int sw[2] = { t.srcW, c->chrSrcW }, sh[2] = { t.srcH, c->chrSrcH };
-    if (c->up2_ok && (widened || !c->widen8) && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_UP2", '0')) {
+    if (c->up2_ok && (widened || !c->widen8) && !(al & 3) && !neg && !knob_is("FFHIP_SWS_UP2", '0')) {
         /* exact 2x above 8 bits: the static-schedule kernel (FFHIP_SWS_UP2=0: the tiled k_sws_scale16) */
         FFHipUp2Args U;
         memset(&U, 0, sizeof(U));
@@ -1560,10 +1556,10 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
                 ffhip_up2_plan_job(&U.job[i], 64 >> U.fshift, 60);
             const char *ev2 = FFHIP_KNOB("FFHIP_UP2_VAR"); /* measure build: rows in flight (FFHIP_UP2_DEPTH), 1 = non-temporal stores */
             /* six rows in flight (round 6, with the straight-line rows: p010 1080p -> 4K 0.615 -> 0.63, planar unchanged) */
-            return ffhip_launch_up2(U, KNOB_IS("FFHIP_UP2_DEPTH", '3') ? 3 : 6, ev2 ? atoi(ev2) : 0, stream);
+            return ffhip_launch_up2(U, knob_is("FFHIP_UP2_DEPTH", '3') ? 3 : 6, ev2 ? atoi(ev2) : 0, stream);
         }
     }
-    if (c->dn2_ok && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_DOWN2", '0')) {
+    if (c->dn2_ok && !(al & 3) && !neg && !knob_is("FFHIP_SWS_DOWN2", '0')) {
         /* exact 2:1 above 8 bits: the static-schedule kernel (FFHIP_SWS_DOWN2=0: the tiled k_sws_scale16) */
         FFHipDn2Args D;
         memset(&D, 0, sizeof(D));
@@ -1586,7 +1582,7 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
         ffhip_set_error("ffhip_sws: above 8 bits into packed RGB needs 4-byte aligned planes and pitches, top-down");
         return FFHIP_EINVAL;
     }
-    if (c->d32_ok && !hrgb && !widened && !c->widen8 && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_DOWN32", '0')) {
+    if (c->d32_ok && !hrgb && !widened && !c->widen8 && !(al & 3) && !neg && !knob_is("FFHIP_SWS_DOWN32", '0')) {
         /* exact 3:2 down above 8 bits: the static-schedule kernel's 16-bit twin (FFHIP_SWS_DOWN32=0: the walker) */
         FFHipD32Args D;
         memset(&D, 0, sizeof(D));
@@ -1605,7 +1601,7 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
         });
         return ffhip_launch_down32(D, stream);
     }
-    if (c->u32_ok && !hrgb && (widened || !c->widen8) && !(al & 3) && !neg && !KNOB_IS("FFHIP_SWS_UP32", '0')) {
+    if (c->u32_ok && !hrgb && (widened || !c->widen8) && !(al & 3) && !neg && !knob_is("FFHIP_SWS_UP32", '0')) {
         /* exact 3:2 up above 8 bits: the static-schedule kernel (FFHIP_SWS_UP32=0: the walker) */
         FFHipU32Args U;
         memset(&U, 0, sizeof(U));
@@ -1622,7 +1618,7 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
         });
         return ffhip_launch_up32(U, stream);
     }
-    if (c->w16_ok && (widened || !c->widen8) && !(al & 3) && !neg && (hrgb || !KNOB_IS("FFHIP_SWS_WALK16", '0'))) {
+    if (c->w16_ok && (widened || !c->widen8) && !(al & 3) && !neg && (hrgb || !knob_is("FFHIP_SWS_WALK16", '0'))) {
         /* a packed-RGB target (round 6): the walker writes the first stage — an int16 luma plane of unclipped sums, 8-bit chroma planes of
          * half the width with a line per target line, flat dither: what yuv2rgb_X_c_template computes before its tables (output.c:1789-1840) —
          * into the context's intermediate, and k_y16_rgb (sws_y16rgb.hip) turns it into pixels */
@@ -1997,7 +1993,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
     const uintptr_t al = s.al() | d.al();
     const bool neg = s.neg || d.neg, topdown = s.pos && d.pos;
     /* fast paths: FFHIP_SWS_FAST=0 forces the LDS-tiled kernels; FFHIP_CW_LUMA_GROUPS / FFHIP_CW_PLAIN select measured variants */
-    const bool fast_off = KNOB_IS("FFHIP_SWS_FAST", '0');
+    const bool fast_off = knob_is("FFHIP_SWS_FAST", '0');
 
     if (fmt_rgb(t.dstFormat)) {
         FFHipScaleRgbArgs a = c->rgb;
@@ -2026,7 +2022,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
                 F.fk[i] = a.fk[i];
             return ffhip_launch_full444(F, stream);
         }
-        if (c->eqr_ok && topdown && !fast_off && !KNOB_IS("FFHIP_SWS_EQRGB", '0') /* measure build: 0 keeps the column walker */ && !(al & 3)) {
+        if (c->eqr_ok && topdown && !fast_off && !knob_is("FFHIP_SWS_EQRGB", '0') /* measure build: 0 keeps the column walker */ && !(al & 3)) {
             /* the source's size: chroma lines interpolated by the exact-2x vertical bank, nothing else scaled (sws_eqrgb.hip) */
             FFHipEqRgbArgs E;
             memset(&E, 0, sizeof(E));
@@ -2072,7 +2068,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             R.hlf = c->dn[0].filter; R.hlp = c->dn[0].pos; R.hcf = c->dn[1].filter; R.hcp = c->dn[1].pos;
             R.vlf = c->dn[2].filter; R.vlp = c->dn[2].pos; R.vcf = c->dn[3].filter; R.vcp = c->dn[3].pos;
             R.nframes = nframes; R.k = c->k; R.vround = c->cw_vround;
-            R.nts = !KNOB_IS("FFHIP_CWRGB_NTS", '0');
+            R.nts = !knob_is("FFHIP_CWRGB_NTS", '0');
             return ffhip_launch_colwalk_rgb(R, stream);
         }
         const char *e2 = FFHIP_KNOB("FFHIP_SWS_RGB2"); /* measure build: 0 keeps the LDS-tiled kernel */
@@ -2297,7 +2293,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
         });
         return ffhip_launch_down2(D, stream);
     }
-    if (!(al & 3) && c->u32_ok && !neg && !c->luma_pass && !KNOB_IS("FFHIP_SWS_UP32", '0') /* measure build: 0 keeps the column walker */) {
+    if (!(al & 3) && c->u32_ok && !neg && !c->luma_pass && !knob_is("FFHIP_SWS_UP32", '0') /* measure build: 0 keeps the column walker */) {
         /* exact 3:2 / 4:3 up: static schedule, no LDS (the 8-bit twin in sws_up32.hip) */
         FFHipU32Args U;
         memset(&U, 0, sizeof(U));
@@ -2316,7 +2312,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
         return ffhip_launch_up32(U, stream);
     }
     if (c->cw_ok && !fast_off) {
-        if (!(al & 3) && (c->up2_ok || (c->mix_up2 && !c->luma_pass && topdown)) && !KNOB_IS("FFHIP_SWS_UP2", '0') && !KNOB_IS("FFHIP_SWS_MFMA", '1')) {
+        if (!(al & 3) && (c->up2_ok || (c->mix_up2 && !c->luma_pass && topdown)) && !knob_is("FFHIP_SWS_UP2", '0') && !knob_is("FFHIP_SWS_MFMA", '1')) {
             /* exact 2x: static schedule, regular windows (sws_up2.hip).  FFHIP_SWS_UP2=0 takes the general column walker. */
             FFHipUp2Args U;
             memset(&U, 0, sizeof(U));
@@ -2384,7 +2380,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             }
         }
         if (!(al & 3) && !c->up2_rc) {
-            if (c->mf_ok && KNOB_IS("FFHIP_SWS_MFMA", '1')) {
+            if (c->mf_ok && knob_is("FFHIP_SWS_MFMA", '1')) {
                 /* horizontal pass on the matrix cores (k_sws_mfma) */
                 const char *est = FFHIP_KNOB("FFHIP_MF_STRIP");
                 FFHipMfArgs M;
@@ -2419,9 +2415,9 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             memset(&A, 0, sizeof(A));
             A.nframes = nframes;
             A.flags = ep && ep[0] == '1' ? 1 : 0;
-            if (c->cw_opt && !A.flags && !KNOB_IS("FFHIP_CW_OPT", '0'))
+            if (c->cw_opt && !A.flags && !knob_is("FFHIP_CW_OPT", '0'))
                 A.flags |= 2;
-            if ((A.flags & 2) && c->cw_dup && !KNOB_IS("FFHIP_CW_DUP", '0'))
+            if ((A.flags & 2) && c->cw_dup && !knob_is("FFHIP_CW_DUP", '0'))
                 A.flags |= 4;
             auto bank = [&](FFHipCwJob &j, const FFHipScalePlaneArgs &p) {
                 const int which = &p == &ch ? 1 : 0; /* the padded 4-tap view of the banks */
@@ -2471,13 +2467,13 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             return ffhip_launch_colwalk(A, lg, depth, stream);
         }
     }
-    if (!(al & 3) && c->dn2_ok && !neg && !KNOB_IS("FFHIP_SWS_DOWN2", '0') && !fast_off) {
+    if (!(al & 3) && c->dn2_ok && !neg && !knob_is("FFHIP_SWS_DOWN2", '0') && !fast_off) {
         /* exact 2:1: static schedule, regular windows, no LDS (sws_down2.hip).  FFHIP_SWS_DOWN2=0 takes the wide walker. */
         FFHipDn2Args D;
         memset(&D, 0, sizeof(D));
         D.nframes = nframes;
         const char *es = FFHIP_KNOB("FFHIP_DN2_STRIP");
-        D.xcd = !KNOB_IS("FFHIP_DN2_XCD", '0');
+        D.xcd = !knob_is("FFHIP_DN2_XCD", '0');
         for_each_job(s, d, true, !c->luma_pass, [&](const PlaneJob &q) {
             const FFHipScalePlaneArgs &p = q.which ? ch : l;
             FFHipDn2Job &j = D.job[D.njobs++];
@@ -2490,7 +2486,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
         });
         return ffhip_launch_down2(D, stream);
     }
-    if (!(al & 3) && c->d32_ok && !neg && !c->luma_pass && !KNOB_IS("FFHIP_SWS_DOWN32", '0') /* measure build: 0 keeps the wide walker */ && !fast_off) {
+    if (!(al & 3) && c->d32_ok && !neg && !c->luma_pass && !knob_is("FFHIP_SWS_DOWN32", '0') /* measure build: 0 keeps the wide walker */ && !fast_off) {
         /* exact 3:2: static schedule with period (3 in, 2 out), no LDS (sws_down32.hip) */
         FFHipD32Args D;
         memset(&D, 0, sizeof(D));

@@ -27,9 +27,11 @@
 #include <new>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 #include "kernels/common.h"
+#include "kernels/tx_host.h"
 #include "kernels/tx_kernels.h"
 #include "kernels/tx_radix_core.h"
 
@@ -58,34 +60,7 @@ struct TxPfa {
     const int *sub_map;        /* m: where sub-transform i's F-point outputs start                       */
 };
 
-struct FFHipTXContext {
-    int device = 0;          /* the tables live on this device; every call of the context makes it current for its duration */
-    int type, inv, len;
-    int half = 0;            /* AV_TX_REAL_TO_REAL / _IMAGINARY (1 / 2) */
-    int full = 0;            /* AV_TX_FULL_IMDCT: the inverse writes 2 * len outputs (half transform in the middle, mirrored) */
-    float scale;
-    TxDev d;
-    TxPfa pfa = {};
-    void *dev = nullptr;
-    size_t blob_bytes = 0;   /* size of the table blob at `dev` (multiple of 16) */
-    float2 *wtab = nullptr;  /* exp(-2 pi i k / n), k < n: the register-resident kernels' twiddles (kernels/tx_radix.hip), or null */
-    FFHipTxWide *wide = nullptr; /* AV_TX_DOUBLE_* / AV_TX_INT32_* contexts: everything lives in kernels/tx_wide.hip */
-    FFHipTxDcst1 *dcst1 = nullptr; /* AV_TX_FLOAT_DCT_I / _DST_I contexts: kernels/tx_dcst1.hip */
-    /* host-pointer shim staging */
-    void *stage = nullptr;
-    size_t stage_sz = 0;
-    std::mutex mu;
-};
-
-/*
- * LDS layout of the complex work array: element i lives at i + (i >> 5), one pad element per 32 (= per 256-byte row
- * of the 64 LDS banks).  Every power-of-two operand stride of the split-radix levels then falls on distinct banks for
- * the 32 lanes an 8-byte access serves per cycle; with the plain layout the low levels (operands of neighbouring
- * lanes 32..512 bytes apart) serialised 4-16 ways.  The butterfly lists and the forward scatter map carry padded
- * indices from the host; a level's operand offsets k*q pad independently (no carry across bit 5: blocks are 4q
- * aligned).
- */
-#define TX_PAD(i) ((i) + ((i) >> 5))
+/* the LDS work array of n complex points, padded (TX_PAD, kernels/tx_host.h) */
 __host__ __device__ static inline size_t tx_z_bytes(int n) { return ((size_t)TX_PAD(n) * 8 + 15) & ~(size_t)15; }
 
 __device__ __forceinline__ void tx_wave_sync()
@@ -1240,33 +1215,26 @@ __global__ __launch_bounds__(256) void k_imdct_mirror(float *out, size_t out_pit
     row[2 * h2 - 1 - i] = make_float2(b.y, b.x);   /* dst[2 len - 2 - 2i] = dst[len + 2i + 1], dst[2 len - 1 - 2i] = dst[len + 2i] */
 }
 
-/* ---- host: tables ------------------------------------------------------------------------------- */
-static int sr_perm(int i, int len, int inv)
-{
-    len >>= 1;
-    if (len <= 1)
-        return i & 1;
-    if (!(i & len))
-        return sr_perm(i, len, inv) * 2;
-    len >>= 1;
-    return sr_perm(i, len, inv) * 4 + 1 - 2 * (!(i & len) ^ inv);
-}
-
-static void sr_schedule(int o, int n, int lg, std::vector<uint32_t> *lev, std::vector<uint16_t> *b2)
-{
-    if (n == 1)
-        return;
-    if (n == 2) {
-        b2->push_back((uint16_t)TX_PAD(o));
-        return;
-    }
-    const int q = n >> 2;
-    sr_schedule(o, n >> 1, lg - 1, lev, b2);
-    sr_schedule(o + 2 * q, q, lg - 2, lev, b2);
-    sr_schedule(o + 3 * q, q, lg - 2, lev, b2);
-    for (int k = 0; k < q; k++)
-        lev[lg].push_back((uint32_t)TX_PAD(o + k) | ((uint32_t)k << 16));
-}
+/* ---- host: tables ---------------------------------------------------------------------------------- */
+struct FFHipTXContext {
+    int device = 0;          /* the tables live on this device; every call of the context makes it current for its duration */
+    int type, inv, len;
+    int half = 0;            /* AV_TX_REAL_TO_REAL / _IMAGINARY (1 / 2) */
+    int full = 0;            /* AV_TX_FULL_IMDCT: the inverse writes 2 * len outputs (half transform in the middle, mirrored) */
+    float scale;
+    TxDev d;
+    TxPfa pfa = {};
+    TxTab53 tab53 = {};      /* the prime-factor kernel's small-transform constants */
+    void *dev = nullptr;
+    size_t blob_bytes = 0;   /* size of the table blob at `dev` (multiple of 16) */
+    float2 *wtab = nullptr;  /* exp(-2 pi i k / n), k < n: the register-resident kernels' twiddles (kernels/tx_radix.hip), or null */
+    FFHipTxWide *wide = nullptr; /* AV_TX_DOUBLE_* / AV_TX_INT32_* contexts: everything lives in kernels/tx_wide.hip */
+    FFHipTxDcst1 *dcst1 = nullptr; /* AV_TX_FLOAT_DCT_I / _DST_I contexts: kernels/tx_dcst1.hip */
+    /* host-pointer shim staging */
+    void *stage = nullptr;
+    size_t stage_sz = 0;
+    std::mutex mu;
+};
 
 extern "C" void ffhip_tx_uninit(FFHipTXContext **pctx)
 {
@@ -1289,6 +1257,9 @@ extern "C" void ffhip_tx_uninit(FFHipTXContext **pctx)
 }
 
 static void tx_single(FFHipTXContext *s, void *out, void *in, ptrdiff_t stride);
+
+/* the float kernels' table value */
+static float tx_float(double x) { return (float)x; }
 
 static int mulinv(int n, int m)
 {
@@ -1373,47 +1344,18 @@ static int tx_init_pfa(FFHipTXContext *c, float scale_f, int F, bool is_fft)
     TxDev &d = c->d;
     memset(&d, 0, sizeof(d));
     d.n = G * n1; d.lg = lg;
-    std::vector<float> cosv;
-    for (int l = 2; l <= lg; l++) {
-        const int mm = 1 << l;
-        const double freq = 2 * M_PI / mm;
-        d.cos_off[l] = (int)cosv.size();
-        for (int i = 0; i < mm / 4; i++)
-            cosv.push_back((float)cos(i * freq));
-        cosv.push_back(0.0f);
-    }
     /* one butterfly schedule for the wave's F G sub-transforms */
-    std::vector<uint32_t> lev[16];
-    std::vector<uint16_t> b2;
-    for (int g = 0; g < G; g++)
-        for (int a = 0; a < F; a++)
-            sr_schedule(g * n1 + a * m, m, lg, lev, &b2);
+    std::vector<float> cosv;
     std::vector<uint32_t> sched;
-    for (int l = 2; l <= lg; l++) {
-        d.sched_off[l] = (int)sched.size();
-        d.sched_cnt[l] = (int)lev[l].size();
-        sched.insert(sched.end(), lev[l].begin(), lev[l].end());
-        d.max_cnt = d.sched_cnt[l] > d.max_cnt ? d.sched_cnt[l] : d.max_cnt;
-    }
-    d.nblocks2 = (int)b2.size();
+    std::vector<uint16_t> b2;
+    d.max_cnt = tx_sr_levels(d, lg, G * F, cosv, sched, b2, tx_float);
     d.ahead = 0;
-    auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_in = 0, o_out = al(o_in + (size_t)n1 * 4), o_sub = al(o_out + (size_t)n1 * 4), o_exp = al(o_sub + (size_t)m * 4);
-    const size_t o_cos = al(o_exp + ex.size() * 8), o_sched = al(o_cos + cosv.size() * 4), o_b2 = al(o_sched + sched.size() * 4);
-    const size_t total = al(o_b2 + b2.size() * 2 + 16);
-    std::vector<uint8_t> blob(total, 0);
-    memcpy(blob.data() + o_in, in_map.data(), (size_t)n1 * 4);
-    memcpy(blob.data() + o_out, out_map.data(), (size_t)n1 * 4);
-    memcpy(blob.data() + o_sub, sub_map.data(), (size_t)m * 4);
-    memcpy(blob.data() + o_exp, ex.data(), ex.size() * 8);
-    memcpy(blob.data() + o_cos, cosv.data(), cosv.size() * 4);
-    memcpy(blob.data() + o_sched, sched.data(), sched.size() * 4);
-    memcpy(blob.data() + o_b2, b2.data(), b2.size() * 2);
-    if (hipMalloc(&c->dev, total) != hipSuccess || hipMemcpy(c->dev, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        ffhip_set_error("ffhip_tx_init: table upload failed");
-        return FFHIP_ENOMEM;
-    }
-    c->blob_bytes = total;
+    TxBlob blob;
+    const size_t o_in = blob.add(in_map), o_out = blob.add(out_map), o_sub = blob.add(sub_map), o_exp = blob.add(ex);
+    const size_t o_cos = blob.add(cosv), o_sched = blob.add(sched), o_b2 = blob.add(b2);
+    const int r = blob.upload(&c->dev, &c->blob_bytes);
+    if (r < 0)
+        return r;
     const uint8_t *base = (const uint8_t *)c->dev;
     TxPfa &P = c->pfa;
     P.n1 = n1; P.m = m; P.G = G; P.F = F;
@@ -1427,6 +1369,23 @@ static int tx_init_pfa(FFHipTXContext *c, float scale_f, int F, bool is_fft)
     d.cos_tab = (const float *)(base + o_cos);
     d.sched = (const uint32_t *)(base + o_sched);
     d.blocks2 = (const uint16_t *)(base + o_b2);
+    /* ff_tx_tab_53, ff_tx_tab_7, ff_tx_tab_9 (tx_template.c:92-130) */
+    TxTab53 &T = c->tab53;
+    T.t[0] = T.t[1] = (float)cos(2 * M_PI / 5);
+    T.t[2] = T.t[3] = (float)cos(2 * M_PI / 10);
+    T.t[4] = T.t[5] = (float)sin(2 * M_PI / 5);
+    T.t[6] = T.t[7] = (float)sin(2 * M_PI / 10);
+    T.t[8] = T.t[9] = (float)cos(2 * M_PI / 12);
+    T.t[10] = (float)cos(2 * M_PI / 6);
+    T.t[11] = (float)cos(8 * M_PI / 6);
+    T.t7[0] = (float)cos(2 * M_PI / 7);  T.t7[1] = (float)sin(2 * M_PI / 7);
+    T.t7[2] = (float)sin(2 * M_PI / 28); T.t7[3] = (float)cos(2 * M_PI / 28);
+    T.t7[4] = (float)cos(2 * M_PI / 14); T.t7[5] = (float)sin(2 * M_PI / 14);
+    T.t9[0] = (float)cos(2 * M_PI / 3);  T.t9[1] = (float)sin(2 * M_PI / 3);
+    T.t9[2] = (float)cos(2 * M_PI / 9);  T.t9[3] = (float)sin(2 * M_PI / 9);
+    T.t9[4] = (float)cos(2 * M_PI / 36); T.t9[5] = (float)sin(2 * M_PI / 36);
+    T.t9[6] = T.t9[2] + T.t9[5];
+    T.t9[7] = T.t9[3] - T.t9[4];
     return 0;
 }
 
@@ -1623,61 +1582,27 @@ extern "C" int ffhip_tx_init(FFHipTXContext **pctx, ffhip_tx_fn *fn, int type, i
     /* the map scatters into the padded work array */
     for (int i = 0; i < n; i++)
         map[i] = TX_PAD(map[i]);
-    /* cosine tables per level (cos(2*pi*k/m), k <= m/4; the last entry is an exact 0) */
-    std::vector<float> cosv;
     TxDev &d = c->d;
     memset(&d, 0, sizeof(d));
     d.n = n; d.lg = lg;
     d.half = c->half;
-    for (int l = 2; l <= lg; l++) {
-        const int m = 1 << l;
-        const double freq = 2 * M_PI / m;
-        d.cos_off[l] = (int)cosv.size();
-        for (int i = 0; i < m / 4; i++)
-            cosv.push_back((float)cos(i * freq));
-        cosv.push_back(0.0f);
-    }
-    std::vector<uint32_t> lev[16];
-    std::vector<uint16_t> b2;
-    sr_schedule(0, n, lg, lev, &b2);
+    std::vector<float> cosv;
     std::vector<uint32_t> sched;
-    for (int l = 2; l <= lg; l++) {
-        d.sched_off[l] = (int)sched.size();
-        d.sched_cnt[l] = (int)lev[l].size();
-        sched.insert(sched.end(), lev[l].begin(), lev[l].end());
-    }
-    d.nblocks2 = (int)b2.size();
-    for (int l = 2; l <= lg; l++)
-        d.max_cnt = d.sched_cnt[l] > d.max_cnt ? d.sched_cnt[l] : d.max_cnt;
-    {
-        const char *ea = FFHIP_KNOB("FFHIP_TX_AHEAD");
-        d.ahead = ea && ea[0] == '1'; /* measured slightly slower (350 vs 345 M transforms/s): opt-in */
-    }
-    /* one device allocation for all tables */
-    size_t off_map = 0, off_exp, off_cos, off_sched, off_b2, total;
-    off_exp = (off_map + map.size() * 4 + 15) & ~(size_t)15;
-    off_cos = (off_exp + ex.size() * 8 + 15) & ~(size_t)15;
-    off_sched = (off_cos + cosv.size() * 4 + 15) & ~(size_t)15;
-    off_b2 = (off_sched + sched.size() * 4 + 15) & ~(size_t)15;
-    total = (off_b2 + b2.size() * 2 + 16 + 15) & ~(size_t)15;
-    std::vector<uint8_t> blob(total, 0);
-    memcpy(blob.data() + off_map, map.data(), map.size() * 4);
-    memcpy(blob.data() + off_exp, ex.data(), ex.size() * 8);
-    memcpy(blob.data() + off_cos, cosv.data(), cosv.size() * 4);
-    memcpy(blob.data() + off_sched, sched.data(), sched.size() * 4);
-    memcpy(blob.data() + off_b2, b2.data(), b2.size() * 2);
-    if (hipMalloc(&c->dev, total) != hipSuccess || hipMemcpy(c->dev, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        ffhip_set_error("ffhip_tx_init: table upload failed");
+    std::vector<uint16_t> b2;
+    d.max_cnt = tx_sr_levels(d, lg, 1, cosv, sched, b2, tx_float);
+    d.ahead = knob_is("FFHIP_TX_AHEAD", '1'); /* measured slightly slower (350 vs 345 M transforms/s): opt-in */
+    TxBlob blob;
+    const size_t o_map = blob.add(map), o_exp = blob.add(ex), o_cos = blob.add(cosv), o_sched = blob.add(sched), o_b2 = blob.add(b2);
+    if (blob.upload(&c->dev, &c->blob_bytes) < 0) {
         ffhip_tx_uninit(&c);
         return FFHIP_ENOMEM;
     }
-    c->blob_bytes = total;
-    uint8_t *base = (uint8_t *)c->dev;
-    d.map = (const int *)(base + off_map);
-    d.exp = (const float2 *)(base + off_exp);
-    d.cos_tab = (const float *)(base + off_cos);
-    d.sched = (const uint32_t *)(base + off_sched);
-    d.blocks2 = (const uint16_t *)(base + off_b2);
+    const uint8_t *base = (const uint8_t *)c->dev;
+    d.map = (const int *)(base + o_map);
+    d.exp = (const float2 *)(base + o_exp);
+    d.cos_tab = (const float *)(base + o_cos);
+    d.sched = (const uint32_t *)(base + o_sched);
+    d.blocks2 = (const uint16_t *)(base + o_b2);
     if (!(flags & FFHIP_TX_BITEXACT) && (type == FFHIP_TX_FLOAT_FFT ? ffhip_tx_radix_fft_ok(n) : ffhip_tx_radix_ok(n))) {
         std::vector<float2> w(n);
         for (int k = 0; k < n; k++) {
@@ -1737,240 +1662,187 @@ extern "C" int ffhip_tx_batch_dev(FFHipTXContext *c, void *out, size_t out_pitch
     return 0;
 }
 
-static int tx_batch_half(FFHipTXContext *c, void *out, size_t out_pitch, const void *in, size_t in_pitch, ptrdiff_t stride, int nt,
-                         void *stream)
+/* runs f(std::integral_constant<int, V>()) for each V of Vs (tx_each) or for the V that equals v (tx_pick): run-time template arguments */
+template <int... Vs, class F>
+static void tx_each(F f)
+{
+    (f(std::integral_constant<int, Vs>()), ...);
+}
+template <int... Vs, class F>
+static void tx_pick(int v, F f)
+{
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+}
+
+/* the 160 KiB dynamic-LDS limit for every kernel here that may be launched with more than the default, once per device */
+static void tx_lds_limit(const void *k) { (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
+static void tx_lds_limits()
+{
+    static FFHipPerDeviceOnce once;
+    if (!once.enter())
+        return;
+    tx_lds_limit((const void *)k_fft_z<true>);
+    tx_lds_limit((const void *)k_fft_z<false>);
+    tx_lds_limit((const void *)k_fft_z<false, true>);
+    tx_each<0, 1>([](auto inv) {
+        tx_lds_limit((const void *)k_mdct_z<inv, true>);
+        tx_lds_limit((const void *)k_mdct_z<inv, false>);
+        tx_lds_limit((const void *)k_mdct_z<inv, false, true>);
+        tx_each<0, 1>([&](auto tl) {
+            tx_each<0, 8, 9, 10>([&](auto rlg) {
+                tx_lds_limit((const void *)k_rdft<inv, bool(tl), rlg>);
+                tx_lds_limit((const void *)k_dct<inv, bool(tl), rlg>);
+            });
+        });
+    });
+    tx_each<0, 1, 2>([](auto inv) {
+        tx_each<3, 5, 7, 9>([&](auto f) {
+            tx_lds_limit((const void *)k_mdct_pfa<inv, f, 1>);
+            tx_lds_limit((const void *)k_mdct_pfa<inv, f, 4>);
+        });
+        tx_lds_limit((const void *)k_mdct_pfa<inv, 15, 1>);
+    });
+    tx_lds_limit((const void *)k_mdct_pfa<2, 15, 2>);
+    once.leave(true);
+}
+
+/* FFHIP_TX_TABLDS=0/1 forces the tables out of / into LDS; by default they go there while they are small next to the waves' work
+ * arrays: the big transforms (n = 2048: 50 KB of tables, 17 KB per wave) keep them in L2 and spend the LDS on waves */
+static bool tx_tables_in_lds(const FFHipTXContext *c)
+{
+    const char *e = FFHIP_KNOB("FFHIP_TX_TABLDS");
+    return e ? e[0] == '1' : c->blob_bytes <= 32 * 1024;
+}
+
+/* 4096..16384 complex points: the work array (33..132 KiB padded) is the workgroup's, the whole workgroup runs each level (k_fft_z /
+ * k_mdct_z with WG); tables stay in L2 */
+static int tx_batch_wg(FFHipTXContext *c, float *out, size_t out_pitch, const float *in, size_t in_pitch, ptrdiff_t stride, int nt,
+                       hipStream_t stream)
 {
     const int n = c->d.n;
-    if (!c->pfa.n1 && n > 2048) {
-        /* 4096..16384 complex points: the work array (33..132 KiB padded) is the workgroup's, the whole workgroup runs each level
-         * (k_fft_z / k_mdct_z with WG); tables stay in L2 */
-        if ((c->type != FFHIP_TX_FLOAT_FFT && stride != (ptrdiff_t)sizeof(float)) || (((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7)) {
-            ffhip_set_error("ffhip_tx: transforms above 2048 complex points need contiguous, 8-byte aligned rows");
-            return FFHIP_EINVAL;
-        }
-        const size_t lds_z = tx_z_bytes(n);
-        const int threads = n >= 8192 ? 1024 : 512;
-        int cus = 256, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        int per_cu = (int)((160 * 1024) / (((lds_z + 1279) / 1280) * 1280));
-        if (per_cu * (threads / 64) > 32) per_cu = 32 / (threads / 64);
-        if (per_cu < 1) per_cu = 1;
-        const int blocks = nt < cus * per_cu ? nt : cus * per_cu;
-        static FFHipPerDeviceOnce wg_attr;
-        if (wg_attr.enter()) {
-            (void)hipFuncSetAttribute((const void *)k_fft_z<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_mdct_z<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_mdct_z<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            wg_attr.leave(true);
-        }
-#define TX_LAUNCH_WG(K)                                                                                                               \
-    hipLaunchKernelGGL((K), dim3(blocks), dim3(threads), lds_z, (hipStream_t)stream, c->d, (const uint8_t *)c->dev, 0,               \
-                       (const float *)in, in_pitch, (float *)out, out_pitch, nt, blocks)
-        {
-            const char *er = FFHIP_KNOB("FFHIP_TX_RADIX");
-            if (c->type == FFHIP_TX_FLOAT_FFT && c->wtab && !(er && er[0] == '0'))
-                return ffhip_launch_fft_r(n, c->inv, c->wtab, (const float *)in, in_pitch, (float *)out, out_pitch, nt, (hipStream_t)stream);
-        }
-        if (c->type == FFHIP_TX_FLOAT_FFT)
-            TX_LAUNCH_WG((k_fft_z<false, true>));
-        else if (c->inv)
-            TX_LAUNCH_WG((k_mdct_z<1, false, true>));
+    if ((c->type != FFHIP_TX_FLOAT_FFT && stride != (ptrdiff_t)sizeof(float)) || (((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7)) {
+        ffhip_set_error("ffhip_tx: transforms above 2048 complex points need contiguous, 8-byte aligned rows");
+        return FFHIP_EINVAL;
+    }
+    if (c->type == FFHIP_TX_FLOAT_FFT && c->wtab && !knob_is("FFHIP_TX_RADIX", '0'))
+        return ffhip_launch_fft_r(n, c->inv, c->wtab, in, in_pitch, out, out_pitch, nt, stream);
+    const size_t lds_z = tx_z_bytes(n);
+    const int threads = n >= 8192 ? 1024 : 512;
+    const int blocks = tx_blocks(lds_z, threads / 64, nt);
+    if (c->type == FFHIP_TX_FLOAT_FFT)
+        hipLaunchKernelGGL((k_fft_z<false, true>), dim3(blocks), dim3(threads), lds_z, stream, c->d, (const uint8_t *)c->dev, 0, in,
+                           in_pitch, out, out_pitch, nt, blocks);
+    else
+        tx_pick<0, 1>(c->inv, [&](auto inv) {
+            hipLaunchKernelGGL((k_mdct_z<inv, false, true>), dim3(blocks), dim3(threads), lds_z, stream, c->d, (const uint8_t *)c->dev, 0,
+                               in, in_pitch, out, out_pitch, nt, blocks);
+        });
+    LAUNCH_CHECK();
+    return 0;
+}
+
+/* FFT / RDFT / DCT up to 2048 complex points, one wave per transform: complex in, complex out, contiguous (av_tx's FFT ignores
+ * `stride`); 8-byte aligned rows.  RDFT: len reals on one side, len/2 + 1 complex bins on the other */
+static int tx_batch_wave(FFHipTXContext *c, float *out, size_t out_pitch, const float *in, size_t in_pitch, int nt, hipStream_t stream)
+{
+    const int n = c->d.n;
+    if (((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7) {
+        ffhip_set_error("ffhip_tx: FFT / RDFT batches need 8-byte aligned rows");
+        return FFHIP_EINVAL;
+    }
+    const bool tl = tx_tables_in_lds(c);
+    const size_t blob_lds = tl ? (c->blob_bytes + 15) & ~(size_t)15 : 0;
+    const int blob_arg = tl ? (int)c->blob_bytes : 0;
+    /* the forward DCT keeps its running-sum terms behind each wave's work array */
+    const bool dct_fwd = c->type == FFHIP_TX_FLOAT_DCT && !c->inv;
+    const size_t zw = tx_z_bytes(n) + (dct_fwd ? (((size_t)n + 1) * 4 + 15) & ~(size_t)15 : 0);
+    /* the forward DCT's workgroups meet at two barriers per transform (the running sums): two or three smaller ones per CU
+     * overlap one's chain with another's transforms */
+    const char *ewpb = FFHIP_KNOB("FFHIP_DCT_WPB");
+    int wpb = dct_fwd ? (ewpb ? atoi(ewpb) : 8) : 16;
+    if (wpb < 1 || wpb > 16 || (wpb & (wpb - 1)))
+        wpb = 8;
+    size_t lds_z = blob_lds + zw * wpb;
+    while (wpb > 1 && lds_z > 150 * 1024) {
+        wpb >>= 1;
+        lds_z = blob_lds + zw * wpb;
+    }
+    const int blocks = tx_blocks(lds_z, wpb, cdiv(nt, wpb));
+    const bool radix = c->wtab && !knob_is("FFHIP_TX_RADIX", '0');
+    if (c->type == FFHIP_TX_FLOAT_FFT) {
+        if (radix)
+            return ffhip_launch_fft_r(n, c->inv, c->wtab, in, in_pitch, out, out_pitch, nt, stream);
+        /* (the split-radix kernels take the pointer too and ignore it) */
+        tx_pick<0, 1>(tl, [&](auto t) {
+            hipLaunchKernelGGL((k_fft_z<bool(t)>), dim3(blocks), dim3(64 * wpb), lds_z, stream, c->d, (const uint8_t *)c->dev, blob_arg,
+                               in, in_pitch, out, out_pitch, nt, blocks * wpb);
+        });
+    } else {
+        const int rlg = radix && ffhip_tx_radix_ok(n) ? c->d.lg : 0;
+        tx_pick<0, 1>(c->inv, [&](auto inv) {
+            tx_pick<0, 1>(tl, [&](auto t) {
+                tx_pick<0, 8, 9, 10>(rlg, [&](auto r) {
+                    if (c->type == FFHIP_TX_FLOAT_RDFT)
+                        hipLaunchKernelGGL((k_rdft<inv, bool(t), r>), dim3(blocks), dim3(64 * wpb), lds_z, stream, c->d, (const uint8_t *)c->dev,
+                                           blob_arg, in, in_pitch, out, out_pitch, nt, blocks * wpb, (const float2 *)c->wtab);
+                    else
+                        hipLaunchKernelGGL((k_dct<inv, bool(t), r>), dim3(blocks), dim3(64 * wpb), lds_z, stream, c->d, (const uint8_t *)c->dev,
+                                           blob_arg, in, in_pitch, out, out_pitch, nt, blocks * wpb, (const float2 *)c->wtab);
+                });
+            });
+        });
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+/* the prime-factor lengths: k_mdct_pfa<direction (2: the FFT), F, sub-transform columns per lane> */
+static int tx_batch_pfa(FFHipTXContext *c, float *out, size_t out_pitch, const float *in, size_t in_pitch, ptrdiff_t stride, int nt,
+                        hipStream_t stream)
+{
+    const TxPfa &P = c->pfa;
+    if ((!P.fft && stride != (ptrdiff_t)sizeof(float)) || (((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7)) {
+        ffhip_set_error("ffhip_tx: the prime-factor lengths need contiguous, 8-byte aligned rows");
+        return FFHIP_EINVAL;
+    }
+    const size_t area = tx_z_bytes(c->d.n); /* G * n1 points, padded: the parked inputs (unpadded) fit the same bytes */
+    const size_t blob_al = (c->blob_bytes + 15) & ~(size_t)15;
+    int wpb = 16;
+    while (wpb > 1 && blob_al + area * wpb > 150 * 1024)
+        wpb >>= 1;
+    const size_t lds_p = blob_al + area * wpb;
+    const int blocks = tx_blocks(lds_p, wpb, cdiv(cdiv(nt, P.G), wpb));
+    auto go = [&](auto inv, auto f, auto cols) {
+        hipLaunchKernelGGL((k_mdct_pfa<inv, f, cols>), dim3(blocks), dim3(64 * wpb), lds_p, stream, c->d, P, c->tab53,
+                           (const uint8_t *)c->dev, (int)c->blob_bytes, in, in_pitch, out, out_pitch, nt, blocks * wpb);
+    };
+    using I1 = std::integral_constant<int, 1>;
+    const int inv = P.fft ? 2 : c->inv, big = P.m > 64;
+    if (P.F == 15) {
+        if (P.fft && big)
+            go(std::integral_constant<int, 2>(), std::integral_constant<int, 15>(), std::integral_constant<int, 2>());
         else
-            TX_LAUNCH_WG((k_mdct_z<0, false, true>));
-#undef TX_LAUNCH_WG
-        LAUNCH_CHECK();
-        return 0;
+            tx_pick<0, 1, 2>(inv, [&](auto i) { go(i, std::integral_constant<int, 15>(), I1()); });
+    } else {
+        tx_pick<0, 1, 2>(inv, [&](auto i) {
+            tx_pick<3, 5, 7, 9>(P.F, [&](auto f) {
+                if (big)
+                    go(i, f, std::integral_constant<int, 4>());
+                else
+                    go(i, f, I1());
+            });
+        });
     }
-    if (!c->pfa.n1 && (c->type == FFHIP_TX_FLOAT_FFT || c->type == FFHIP_TX_FLOAT_RDFT || c->type == FFHIP_TX_FLOAT_DCT)) {
-        /* complex in, complex out, contiguous (av_tx's FFT ignores `stride`); 8-byte aligned rows.  RDFT: len reals on one
-         * side, len/2 + 1 complex bins on the other */
-        if (((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7) {
-            ffhip_set_error("ffhip_tx: FFT / RDFT batches need 8-byte aligned rows");
-            return FFHIP_EINVAL;
-        }
-        /* tables in LDS while they are small next to the waves' work arrays; the big transforms (n = 2048: 50 KB of tables,
-         * 17 KB per wave) keep them in L2 and spend the LDS on waves (FFHIP_TX_TABLDS=0/1 forces either) */
-        const char *etl = FFHIP_KNOB("FFHIP_TX_TABLDS");
-        const bool tl = etl ? etl[0] == '1' : c->blob_bytes <= 32 * 1024;
-        const size_t blob_lds = tl ? (c->blob_bytes + 15) & ~(size_t)15 : 0;
-        const int blob_arg = tl ? (int)c->blob_bytes : 0;
-        /* the forward DCT keeps its running-sum terms behind each wave's work array */
-        const size_t zw = tx_z_bytes(n) + (c->type == FFHIP_TX_FLOAT_DCT && !c->inv ? (((size_t)n + 1) * 4 + 15) & ~(size_t)15 : 0);
-        /* the forward DCT's workgroups meet at two barriers per transform (the running sums): two or three smaller ones per CU
-         * overlap one's chain with another's transforms */
-        const char *ewpb = FFHIP_KNOB("FFHIP_DCT_WPB");
-        int wpb = c->type == FFHIP_TX_FLOAT_DCT && !c->inv ? (ewpb ? atoi(ewpb) : 8) : 16;
-        if (wpb < 1 || wpb > 16 || (wpb & (wpb - 1)))
-            wpb = 8;
-        size_t lds_z = blob_lds + zw * wpb;
-        while (wpb > 1 && lds_z > 150 * 1024) {
-            wpb >>= 1;
-            lds_z = blob_lds + zw * wpb;
-        }
-        int cus = 256, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        int per_cu = (int)((160 * 1024) / (((lds_z + 1279) / 1280) * 1280));
-        if (per_cu * wpb > 32) per_cu = 32 / wpb;
-        if (per_cu < 1) per_cu = 1;
-        int blocks = cus * per_cu;
-        if (blocks > (nt + wpb - 1) / wpb)
-            blocks = (nt + wpb - 1) / wpb;
-        int rlg = 0;
-        {
-            const char *er = FFHIP_KNOB("FFHIP_TX_RADIX");
-            if (c->wtab && !(er && er[0] == '0') && ffhip_tx_radix_ok(n))
-                rlg = c->d.lg;
-        }
-        static FFHipPerDeviceOnce fft_attr; /* function attributes are per device */
-        if (fft_attr.enter()) {
-            (void)hipFuncSetAttribute((const void *)k_fft_z<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_fft_z<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, true, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, true, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, true, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, true, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, false, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<0, false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, false, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_rdft<1, false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, true, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, true, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, true, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, true, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, false, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<0, false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, false, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dct<1, false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            fft_attr.leave(true);
-        }
-        if (c->type == FFHIP_TX_FLOAT_RDFT) {
-#define TX_LAUNCH(K)                                                                                                                  \
-    hipLaunchKernelGGL((K), dim3(blocks), dim3(64 * wpb), lds_z, (hipStream_t)stream, c->d, (const uint8_t *)c->dev, blob_arg,       \
-                       (const float *)in, in_pitch, (float *)out, out_pitch, nt, blocks * wpb)
-            /* (the split-radix kernels take the pointer too and ignore it) */
-#define TX_LAUNCH_R(K)                                                                                                                \
-    hipLaunchKernelGGL((K), dim3(blocks), dim3(64 * wpb), lds_z, (hipStream_t)stream, c->d, (const uint8_t *)c->dev, blob_arg,       \
-                       (const float *)in, in_pitch, (float *)out, out_pitch, nt, blocks * wpb, (const float2 *)c->wtab)
-#define TX_LAUNCH_RLG(KN, INV_)                                                                                                       \
-    do {                                                                                                                              \
-        switch (rlg) {                                                                                                                \
-        case 8:  if (tl) TX_LAUNCH_R((KN<INV_, true, 8>)); else TX_LAUNCH_R((KN<INV_, false, 8>)); break;                            \
-        case 9:  if (tl) TX_LAUNCH_R((KN<INV_, true, 9>)); else TX_LAUNCH_R((KN<INV_, false, 9>)); break;                            \
-        case 10: if (tl) TX_LAUNCH_R((KN<INV_, true, 10>)); else TX_LAUNCH_R((KN<INV_, false, 10>)); break;                          \
-        default: if (tl) TX_LAUNCH_R((KN<INV_, true, 0>)); else TX_LAUNCH_R((KN<INV_, false, 0>)); break;                            \
-        }                                                                                                                             \
-    } while (0)
-            if (c->inv) TX_LAUNCH_RLG(k_rdft, 1); else TX_LAUNCH_RLG(k_rdft, 0);
-            LAUNCH_CHECK();
-            return 0;
-        }
-        if (c->type == FFHIP_TX_FLOAT_DCT) {
-            if (c->inv) TX_LAUNCH_RLG(k_dct, 1); else TX_LAUNCH_RLG(k_dct, 0);
-            LAUNCH_CHECK();
-            return 0;
-        }
-        {
-            const char *er = FFHIP_KNOB("FFHIP_TX_RADIX");
-            if (c->wtab && !(er && er[0] == '0'))
-                return ffhip_launch_fft_r(n, c->inv, c->wtab, (const float *)in, in_pitch, (float *)out, out_pitch, nt, (hipStream_t)stream);
-        }
-        if (tl) TX_LAUNCH((k_fft_z<true>)); else TX_LAUNCH((k_fft_z<false>));
-        LAUNCH_CHECK();
-        return 0;
-    }
-    if (c->pfa.n1) {
-        const TxPfa &P = c->pfa;
-        if ((!P.fft && stride != (ptrdiff_t)sizeof(float)) || (((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7)) {
-            ffhip_set_error("ffhip_tx: the prime-factor lengths need contiguous, 8-byte aligned rows");
-            return FFHIP_EINVAL;
-        }
-        const size_t area = tx_z_bytes(n); /* G * n1 points, padded: the parked inputs (unpadded) fit the same bytes */
-        const size_t blob_al = (c->blob_bytes + 15) & ~(size_t)15;
-        int wpb = 16;
-        while (wpb > 1 && blob_al + area * wpb > 150 * 1024)
-            wpb >>= 1;
-        const size_t lds_p = blob_al + area * wpb;
-        int cus = 256, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        int per_cu = (int)((160 * 1024) / (((lds_p + 1279) / 1280) * 1280));
-        if (per_cu * wpb > 32) per_cu = 32 / wpb;
-        if (per_cu < 1) per_cu = 1;
-        const int groups = (nt + P.G - 1) / P.G;
-        int blocks = cus * per_cu;
-        if (blocks > (groups + wpb - 1) / wpb)
-            blocks = (groups + wpb - 1) / wpb;
-        TxTab53 T;
-        T.t[0] = T.t[1] = (float)cos(2 * M_PI / 5);
-        T.t[2] = T.t[3] = (float)cos(2 * M_PI / 10);
-        T.t[4] = T.t[5] = (float)sin(2 * M_PI / 5);
-        T.t[6] = T.t[7] = (float)sin(2 * M_PI / 10);
-        T.t[8] = T.t[9] = (float)cos(2 * M_PI / 12);
-        T.t[10] = (float)cos(2 * M_PI / 6);
-        T.t[11] = (float)cos(8 * M_PI / 6);
-        T.t7[0] = (float)cos(2 * M_PI / 7);  T.t7[1] = (float)sin(2 * M_PI / 7);
-        T.t7[2] = (float)sin(2 * M_PI / 28); T.t7[3] = (float)cos(2 * M_PI / 28);
-        T.t7[4] = (float)cos(2 * M_PI / 14); T.t7[5] = (float)sin(2 * M_PI / 14);
-        T.t9[0] = (float)cos(2 * M_PI / 3);  T.t9[1] = (float)sin(2 * M_PI / 3);
-        T.t9[2] = (float)cos(2 * M_PI / 9);  T.t9[3] = (float)sin(2 * M_PI / 9);
-        T.t9[4] = (float)cos(2 * M_PI / 36); T.t9[5] = (float)sin(2 * M_PI / 36);
-        T.t9[6] = T.t9[2] + T.t9[5];
-        T.t9[7] = T.t9[3] - T.t9[4];
-        const int big = P.m > 64;
-#define PFA_GO(INV_, F_, C_)                                                                                                               \
-    do {                                                                                                                                   \
-        static FFHipPerDeviceOnce attr;                                                                                                    \
-        if (attr.enter()) {                                                                                                                \
-            (void)hipFuncSetAttribute((const void *)k_mdct_pfa<INV_, F_, C_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-            attr.leave(true);                                                                                                              \
-        }                                                                                                                                  \
-        hipLaunchKernelGGL((k_mdct_pfa<INV_, F_, C_>), dim3(blocks), dim3(64 * wpb), lds_p, (hipStream_t)stream, c->d, P, T,              \
-                           (const uint8_t *)c->dev, (int)c->blob_bytes, (const float *)in, in_pitch, (float *)out, out_pitch, nt,         \
-                           blocks * wpb);                                                                                                  \
-    } while (0)
-#define PFA_F(F_)                                                                                                                          \
-    do {                                                                                                                                   \
-        if (P.fft)       { if (big) PFA_GO(2, F_, 4); else PFA_GO(2, F_, 1); }                                                             \
-        else if (c->inv) { if (big) PFA_GO(1, F_, 4); else PFA_GO(1, F_, 1); }                                                             \
-        else             { if (big) PFA_GO(0, F_, 4); else PFA_GO(0, F_, 1); }                                                             \
-    } while (0)
-        switch (P.F) {
-        case 3:  PFA_F(3); break;
-        case 5:  PFA_F(5); break;
-        case 7:  PFA_F(7); break;
-        case 9:  PFA_F(9); break;
-        default:
-            if (P.fft) { if (big) PFA_GO(2, 15, 2); else PFA_GO(2, 15, 1); }
-            else if (c->inv) PFA_GO(1, 15, 1);
-            else PFA_GO(0, 15, 1);
-            break;
-        }
-#undef PFA_F
-#undef PFA_GO
-        LAUNCH_CHECK();
-        return 0;
-    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+/* the power-of-two MDCT up to 2048 complex points: the register-resident k_mdct_r, the staging-free k_mdct_z, the persistent k_mdct_l,
+ * else the one-shot k_mdct (strided or unaligned rows) */
+static int tx_batch_mdct(FFHipTXContext *c, float *out, size_t out_pitch, const float *in, size_t in_pitch, ptrdiff_t stride, int nt,
+                         hipStream_t stream)
+{
+    const int n = c->d.n;
     const size_t per_wave = tx_z_bytes(n) + (size_t)n * 16;
     int wpb = (int)((60 * 1024) / per_wave);
     if (wpb > 4) wpb = 4;
@@ -1979,102 +1851,110 @@ static int tx_batch_half(FFHipTXContext *c, void *out, size_t out_pitch, const v
         return FFHIP_EINVAL;
     }
     const ptrdiff_t es = stride / (ptrdiff_t)sizeof(float);
-    const dim3 grid(cdiv(nt, wpb)), block(64 * wpb);
-    /* FFT-level tables in LDS when they fit next to the waves' areas (FFHIP_TX_LDSTAB=0 keeps them in L2) */
-    const char *et = FFHIP_KNOB("FFHIP_TX_LDSTAB");
-    const size_t ftab_sz = (size_t)((const uint8_t *)c->d.blocks2 - (const uint8_t *)c->d.cos_tab); /* twiddles + butterfly lists */
-    int ftab = 0;
-    size_t lds = per_wave * wpb;
-    /* measured (profiles/r01_sweep_tx.txt): 174 vs 149 M forward transforms/s with the level tables in LDS */
-    if (!(et && et[0] == '0') && lds + ftab_sz <= 64 * 1024) {
-        ftab = (int)ftab_sz;
-        lds += ftab_sz;
-    }
+    const bool contig8 = es == 1 && !(((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7);
+    if (contig8 && c->wtab && !knob_is("FFHIP_TX_RADIX", '0'))
+        return ffhip_launch_mdct_r(n, c->inv, c->wtab, c->d.exp, in, in_pitch, out, out_pitch, nt, stream);
     /* contiguous 8-byte aligned batches: the staging-free kernel (FFHIP_TX_Z=0 selects the older ones) */
     {
-        const char *ez = FFHIP_KNOB("FFHIP_TX_Z");
         const char *ew = FFHIP_KNOB("FFHIP_TX_WPB");
-        int wpb = ew && atoi(ew) > 0 ? atoi(ew) : 16; /* waves per workgroup: 16 measured best (the table copy is shared) */
-        if (wpb > 16) wpb = 16;
-        const char *etl = FFHIP_KNOB("FFHIP_TX_TABLDS");
-        const bool tl = etl ? etl[0] == '1' : c->blob_bytes <= 32 * 1024; /* as for the FFT: big transforms keep their tables in L2 */
+        int wpb_z = ew && atoi(ew) > 0 ? atoi(ew) : 16; /* waves per workgroup: 16 measured best (the table copy is shared) */
+        if (wpb_z > 16) wpb_z = 16;
+        const bool tl = tx_tables_in_lds(c); /* as for the FFT: big transforms keep their tables in L2 */
         const size_t blob_lds = tl ? (c->blob_bytes + 15) & ~(size_t)15 : 0;
         const int blob_arg = tl ? (int)c->blob_bytes : 0;
-        size_t lds_z = blob_lds + tx_z_bytes(n) * wpb;
-        while (wpb > 1 && lds_z > 150 * 1024) {
-            wpb >>= 1;
-            lds_z = blob_lds + tx_z_bytes(n) * wpb;
+        size_t lds_z = blob_lds + tx_z_bytes(n) * wpb_z;
+        while (wpb_z > 1 && lds_z > 150 * 1024) {
+            wpb_z >>= 1;
+            lds_z = blob_lds + tx_z_bytes(n) * wpb_z;
         }
-        if (es == 1 && !(((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7) && c->wtab) {
-            const char *er = FFHIP_KNOB("FFHIP_TX_RADIX");
-            if (!(er && er[0] == '0'))
-                return ffhip_launch_mdct_r(n, c->inv, c->wtab, c->d.exp, (const float *)in, in_pitch, (float *)out, out_pitch, nt,
-                                           (hipStream_t)stream);
-        }
-        if (es == 1 && !(((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 7) && lds_z <= 150 * 1024 && !(ez && ez[0] == '0')) {
-            int cus = 256, dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                cus = prop.multiProcessorCount;
-            int per_cu = (int)((160 * 1024) / (((lds_z + 1279) / 1280) * 1280));
-            if (per_cu * wpb > 32) per_cu = 32 / wpb;
-            if (per_cu < 1) per_cu = 1;
-            int blocks = cus * per_cu;
-            if (blocks > (nt + wpb - 1) / wpb)
-                blocks = (nt + wpb - 1) / wpb;
-            static FFHipPerDeviceOnce attr_done;
-            if (attr_done.enter()) {
-                (void)hipFuncSetAttribute((const void *)k_mdct_z<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_mdct_z<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_mdct_z<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)k_mdct_z<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_done.leave(true);
-            }
-            if (c->inv) {
-                if (tl) TX_LAUNCH((k_mdct_z<1, true>)); else TX_LAUNCH((k_mdct_z<1, false>));
-            } else {
-                if (tl) TX_LAUNCH((k_mdct_z<0, true>)); else TX_LAUNCH((k_mdct_z<0, false>));
-            }
+        if (contig8 && lds_z <= 150 * 1024 && !knob_is("FFHIP_TX_Z", '0')) {
+            const int blocks = tx_blocks(lds_z, wpb_z, cdiv(nt, wpb_z));
+            tx_pick<0, 1>(c->inv, [&](auto inv) {
+                tx_pick<0, 1>(tl, [&](auto t) {
+                    hipLaunchKernelGGL((k_mdct_z<inv, bool(t)>), dim3(blocks), dim3(64 * wpb_z), lds_z, stream, c->d, (const uint8_t *)c->dev,
+                                       blob_arg, in, in_pitch, out, out_pitch, nt, blocks * wpb_z);
+                });
+            });
             LAUNCH_CHECK();
             return 0;
         }
     }
-    const char *ev = FFHIP_KNOB("FFHIP_TX_PERSISTENT");
     const bool aligned = es == 1 && !(((uintptr_t)in | in_pitch | (uintptr_t)out | out_pitch) & 15);
     const size_t lds_p = ((c->blob_bytes + 15) & ~(size_t)15) + per_wave * 4;
     /* measured (profiles/r01_sweep_tx.txt, N = 1024): 180 vs 175 M forward and 247 vs 225 M inverse transforms/s against
      * the one-shot kernel with LDS level tables - the default for aligned contiguous batches; FFHIP_TX_PERSISTENT=0
      * selects the one-shot kernel */
-    if (aligned && lds_p <= 64 * 1024 && !(ev && ev[0] == '0')) {
-        int cus = 256, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        int blocks = cus * (int)((160 * 1024) / lds_p);
+    if (aligned && lds_p <= 64 * 1024 && !knob_is("FFHIP_TX_PERSISTENT", '0')) {
+        int blocks = ffhip_cu_count() * (int)((160 * 1024) / lds_p);
         if (blocks > (nt + 3) / 4)
             blocks = (nt + 3) / 4;
-        if (c->inv)
-            hipLaunchKernelGGL((k_mdct_l<1>), dim3(blocks), dim3(256), lds_p, (hipStream_t)stream, c->d, (const uint8_t *)c->dev,
-                               (int)c->blob_bytes, (const float *)in, in_pitch, (float *)out, out_pitch, nt, blocks * 4);
-        else
-            hipLaunchKernelGGL((k_mdct_l<0>), dim3(blocks), dim3(256), lds_p, (hipStream_t)stream, c->d, (const uint8_t *)c->dev,
-                               (int)c->blob_bytes, (const float *)in, in_pitch, (float *)out, out_pitch, nt, blocks * 4);
+        tx_pick<0, 1>(c->inv, [&](auto inv) {
+            hipLaunchKernelGGL((k_mdct_l<inv>), dim3(blocks), dim3(256), lds_p, stream, c->d, (const uint8_t *)c->dev, (int)c->blob_bytes,
+                               in, in_pitch, out, out_pitch, nt, blocks * 4);
+        });
         LAUNCH_CHECK();
         return 0;
     }
+    /* FFT-level tables in LDS when they fit next to the waves' areas (FFHIP_TX_LDSTAB=0 keeps them in L2) */
+    const size_t ftab_sz = (size_t)((const uint8_t *)c->d.blocks2 - (const uint8_t *)c->d.cos_tab); /* twiddles + butterfly lists */
+    int ftab = 0;
+    size_t lds = per_wave * wpb;
+    /* measured (profiles/r01_sweep_tx.txt): 174 vs 149 M forward transforms/s with the level tables in LDS */
+    if (!knob_is("FFHIP_TX_LDSTAB", '0') && lds + ftab_sz <= 64 * 1024) {
+        ftab = (int)ftab_sz;
+        lds += ftab_sz;
+    }
+    const dim3 grid(cdiv(nt, wpb)), block(64 * wpb);
     if (!c->inv) {
         const int vin = !(((uintptr_t)in | in_pitch) & 15);
         const int vout = es == 1 && !(((uintptr_t)out | out_pitch) & 15);
-        hipLaunchKernelGGL((k_mdct<0>), grid, block, lds, (hipStream_t)stream, c->d, (const float *)in, in_pitch, (float *)out,
-                           out_pitch, es, nt, wpb, vin, vout, ftab);
+        hipLaunchKernelGGL((k_mdct<0>), grid, block, lds, stream, c->d, in, in_pitch, out, out_pitch, es, nt, wpb, vin, vout, ftab);
     } else {
         const int vin = es == 1 && !(((uintptr_t)in | in_pitch) & 15);
         const int vout = !(((uintptr_t)out | out_pitch) & 15);
-        hipLaunchKernelGGL((k_mdct<1>), grid, block, lds, (hipStream_t)stream, c->d, (const float *)in, in_pitch, (float *)out,
-                           out_pitch, es, nt, wpb, vin, vout, ftab);
+        hipLaunchKernelGGL((k_mdct<1>), grid, block, lds, stream, c->d, in, in_pitch, out, out_pitch, es, nt, wpb, vin, vout, ftab);
     }
     LAUNCH_CHECK();
     return 0;
+}
+
+static int tx_batch_half(FFHipTXContext *c, void *out, size_t out_pitch, const void *in, size_t in_pitch, ptrdiff_t stride, int nt,
+                         void *stream)
+{
+    tx_lds_limits();
+    float *o = (float *)out;
+    const float *i = (const float *)in;
+    const hipStream_t st = (hipStream_t)stream;
+    if (!c->pfa.n1 && c->d.n > 2048)
+        return tx_batch_wg(c, o, out_pitch, i, in_pitch, stride, nt, st);
+    if (!c->pfa.n1 && (c->type == FFHIP_TX_FLOAT_FFT || c->type == FFHIP_TX_FLOAT_RDFT || c->type == FFHIP_TX_FLOAT_DCT))
+        return tx_batch_wave(c, o, out_pitch, i, in_pitch, nt, st);
+    if (c->pfa.n1)
+        return tx_batch_pfa(c, o, out_pitch, i, in_pitch, stride, nt, st);
+    return tx_batch_mdct(c, o, out_pitch, i, in_pitch, stride, nt, st);
+}
+
+/* the host-pointer faces' device round trip through the context's staging buffer: in_bytes from hin to offset 0, the output row at
+ * the next 16-byte boundary, both pitches rounded up to 16; run(dout, out_pitch, din, in_pitch) transforms the one row, then out_bytes
+ * go to hout.  False on any failure, before anything reaches hout */
+template <class Run>
+static bool tx_stage_run(FFHipTXContext *s, const void *hin, size_t in_bytes, void *hout, size_t out_bytes, Run run)
+{
+    const size_t in_pitch = (in_bytes + 15) & ~(size_t)15, out_pitch = (out_bytes + 15) & ~(size_t)15, need = in_pitch + out_pitch + 64;
+    if (need > s->stage_sz) {
+        if (s->stage)
+            (void)hipFree(s->stage);
+        s->stage = nullptr;
+        s->stage_sz = 0;
+        if (hipMalloc(&s->stage, need) != hipSuccess) {
+            ffhip_set_error("ffhip_tx: staging allocation failed");
+            return false;
+        }
+        s->stage_sz = need;
+    }
+    uint8_t *din = (uint8_t *)s->stage, *dout = din + in_pitch;
+    return hipMemcpy(din, hin, in_bytes, hipMemcpyHostToDevice) == hipSuccess && run(dout, out_pitch, din, in_pitch) >= 0 &&
+           hipMemcpy(hout, dout, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
 }
 
 /* av_tx_fn-shaped single transform with HOST pointers (libavutil/tx.h:151): stage, run, copy back */
@@ -2096,24 +1976,8 @@ static void tx_single(FFHipTXContext *s, void *out, void *in, ptrdiff_t stride)
     const float *fi = (const float *)in;
     for (size_t i = 0; i < in_elems; i++)
         hin[i] = (s->inv && !fft) ? fi[(ptrdiff_t)i * es] : fi[i];
-    const size_t need = (in_elems + out_elems) * sizeof(float) + 64;
-    if (need > s->stage_sz) {
-        if (s->stage)
-            (void)hipFree(s->stage);
-        s->stage = nullptr;
-        s->stage_sz = 0;
-        if (hipMalloc(&s->stage, need) != hipSuccess) {
-            ffhip_set_error("ffhip_tx: staging allocation failed");
-            return;
-        }
-        s->stage_sz = need;
-    }
-    float *din = (float *)s->stage, *dout = din + ((in_elems + 3) & ~(size_t)3);
-    if (hipMemcpy(din, hin.data(), in_elems * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return;
-    if (ffhip_tx_batch_dev(s, dout, ((out_elems * sizeof(float)) + 15) & ~(size_t)15, din, ((in_elems * sizeof(float)) + 15) & ~(size_t)15, sizeof(float), 1, 0) < 0)
-        return;
-    if (hipMemcpy(hout.data(), dout, out_elems * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+    if (!tx_stage_run(s, hin.data(), in_elems * sizeof(float), hout.data(), out_elems * sizeof(float),
+                      [&](void *o, size_t op, const void *i, size_t ip) { return ffhip_tx_batch_dev(s, o, op, i, ip, sizeof(float), 1, 0); }))
         return;
     float *fo = (float *)out;
     for (size_t i = 0; i < out_elems; i++)
@@ -2125,27 +1989,13 @@ static void tx_single_dcst1(FFHipTXContext *s, void *out, void *in, ptrdiff_t st
 {
     FFHipDeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
-    const size_t n = (size_t)s->len, row = (n * sizeof(float) + 15) & ~(size_t)15;
+    const size_t n = (size_t)s->len;
     std::vector<float> h(n);
     for (size_t i = 0; i < n; i++)
         h[i] = *(const float *)((const uint8_t *)in + (ptrdiff_t)i * stride);
-    if (2 * row > s->stage_sz) {
-        if (s->stage)
-            (void)hipFree(s->stage);
-        s->stage = nullptr;
-        s->stage_sz = 0;
-        if (hipMalloc(&s->stage, 2 * row) != hipSuccess) {
-            ffhip_set_error("ffhip_tx: staging allocation failed");
-            return;
-        }
-        s->stage_sz = 2 * row;
-    }
-    float *din = (float *)s->stage, *dout = (float *)((uint8_t *)s->stage + row);
-    if (hipMemcpy(din, h.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return;
-    if (ffhip_dcst1_batch(s->dcst1, dout, row, din, row, 1, 1, 0) < 0)
-        return;
-    (void)hipMemcpy(out, dout, n * sizeof(float), hipMemcpyDeviceToHost);
+    (void)tx_stage_run(s, h.data(), n * sizeof(float), out, n * sizeof(float), [&](void *o, size_t op, const void *i, size_t ip) {
+        return ffhip_dcst1_batch(s->dcst1, (float *)o, op, (const float *)i, ip, 1, 1, 0);
+    });
 }
 
 /* the same for the double / int32 contexts: the strided side (forward MDCT: output, inverse: input; an FFT has none) packed on the host */
@@ -2158,24 +2008,8 @@ static void tx_single_wide(FFHipTXContext *s, void *out, void *in, ptrdiff_t str
     std::vector<uint8_t> hin(ni * es), hout(no * es);
     for (size_t i = 0; i < ni; i++)
         memcpy(hin.data() + i * es, (const uint8_t *)in + ((mdct && s->inv) ? (ptrdiff_t)i * stride : (ptrdiff_t)(i * es)), es);
-    const size_t in_b = (ni * es + 15) & ~(size_t)15, out_b = (no * es + 15) & ~(size_t)15, need = in_b + out_b;
-    if (need > s->stage_sz) {
-        if (s->stage)
-            (void)hipFree(s->stage);
-        s->stage = nullptr;
-        s->stage_sz = 0;
-        if (hipMalloc(&s->stage, need) != hipSuccess) {
-            ffhip_set_error("ffhip_tx: staging allocation failed");
-            return;
-        }
-        s->stage_sz = need;
-    }
-    uint8_t *din = (uint8_t *)s->stage, *dout = din + in_b;
-    if (hipMemcpy(din, hin.data(), ni * es, hipMemcpyHostToDevice) != hipSuccess)
-        return;
-    if (ffhip_txw_batch(s->wide, dout, out_b, din, in_b, 1, 0) < 0)
-        return;
-    if (hipMemcpy(hout.data(), dout, no * es, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!tx_stage_run(s, hin.data(), ni * es, hout.data(), no * es,
+                      [&](void *o, size_t op, const void *i, size_t ip) { return ffhip_txw_batch(s->wide, o, op, i, ip, 1, 0); }))
         return;
     for (size_t i = 0; i < no; i++)
         memcpy((uint8_t *)out + ((mdct && !s->inv) ? (ptrdiff_t)i * stride : (ptrdiff_t)(i * es)), hout.data() + i * es, es);
