@@ -1,0 +1,363 @@
+/*
+ * vp9_inter_frame.hip — VP9 inter reconstruction of whole frames in one launch (ffhip_vp9_inter_frames_dev), 8 / 10 / 12 bits.
+ *
+ * Prediction reads reference frames only, never the frame being written, so the inter blocks of a frame carry no dependency chain:
+ * one workgroup (4 waves) per (frame, superblock), no hand-offs.  Per plane the workgroup
+ *   1. predicts the superblock's records of that plane, wave w taking records w, w + 4, ..., into an LDS tile of the superblock's
+ *      samples, and marks what it wrote in a coverage mask (a bit per sample); a compound record averages its second reference into
+ *      the same tile positions;
+ *   2. after a barrier, runs the superblock's TUs of the plane, a wave each, through the butterfly network of vp9_itxfm.hip
+ *      (vp9_itxfm_net.inc, 32-bit at 8 bits, 64-bit above) and adds them to the covered samples of the tile;
+ *   3. after a barrier, stores the covered samples inside the decoded area to the plane, four at a time where a quad is covered.
+ * What no record covers (intra blocks, the stride padding, anything outside the decoded area) is never written.
+ *
+ * Interpolation is vp9dsp_template.c's (the oracle's ffo_vp9_mc_bd): 8-tap passes clip((sum + 64) >> 7), the 2-D form through
+ * pixel-type temporaries of rows -3 .. h + 3 (wave-private LDS), bilinear a + ((m (b - a) + 8) >> 4) over rows 0 .. h, full-sample
+ * copies.  Every reference sample is fetched with its coordinates clamped to the reference's real size, which is what
+ * emulated_edge_mc gives mc_luma_unscaled / mc_chroma_unscaled, so MVs may point anywhere.  A lane computes one sample at a time;
+ * block sizes are powers of two, so a block's samples are spread over the wave by shifts.  Records are checked before they are used
+ * (include/ffhip.h lists what is malformed); a malformed record or TU is skipped.
+ */
+#include <stddef.h>
+#include <type_traits>
+
+#include "common.h"
+#include "h264_kernels.h"
+
+static_assert(sizeof(FFHipVp9InterPred) == 20, "FFHipVp9InterPred is a 20-byte record");
+static_assert(sizeof(FFHipVp9InterTU) == 12, "FFHipVp9InterTU is a 12-byte record");
+static_assert(sizeof(FFHipVp9InterPic) % 8 == 0, "FFHipVp9InterPic is staged as an array");
+
+#define VIF_PICS 16 /* frames per launch: their FFHipVp9InterPic structs travel in one progress-pool slot */
+static_assert(VIF_PICS * sizeof(FFHipVp9InterPic) <= FFHIP_PROGRESS_SLOT_INTS * sizeof(int), "a launch's frames fit one slot");
+
+namespace {
+namespace vq32 {
+#define VP_ST int
+#define VP_UT uint32_t
+#include "vp9_itxfm_net.inc"
+#undef VP_ST
+#undef VP_UT
+} // namespace vq32
+namespace vq64 {
+#define VP_ST long long
+#define VP_UT unsigned long long
+#include "vp9_itxfm_net.inc"
+#undef VP_ST
+#undef VP_UT
+} // namespace vq64
+
+/* ff_vp9_subpel_filters (libavcodec/vp9dsp.c): [filter 0 smooth / 1 regular / 2 sharp][m in sixteenths][tap]; m = 0 is never used */
+__constant__ int8_t vif_taps[3][16][8] = {
+    { { 0 }, { -3, -1, 32, 64, 38, 1, -3, 0 }, { -2, -2, 29, 63, 41, 2, -3, 0 }, { -2, -2, 26, 63, 43, 4, -4, 0 },
+      { -2, -3, 24, 62, 46, 5, -4, 0 }, { -2, -3, 21, 60, 49, 7, -4, 0 }, { -1, -4, 18, 59, 51, 9, -4, 0 }, { -1, -4, 16, 57, 53, 12, -4, -1 },
+      { -1, -4, 14, 55, 55, 14, -4, -1 }, { -1, -4, 12, 53, 57, 16, -4, -1 }, { 0, -4, 9, 51, 59, 18, -4, -1 }, { 0, -4, 7, 49, 60, 21, -3, -2 },
+      { 0, -4, 5, 46, 62, 24, -3, -2 }, { 0, -4, 4, 43, 63, 26, -2, -2 }, { 0, -3, 2, 41, 63, 29, -2, -2 }, { 0, -3, 1, 38, 64, 32, -1, -3 } },
+    { { 0 }, { 0, 1, -5, 126, 8, -3, 1, 0 }, { -1, 3, -10, 122, 18, -6, 2, 0 }, { -1, 4, -13, 118, 27, -9, 3, -1 },
+      { -1, 4, -16, 112, 37, -11, 4, -1 }, { -1, 5, -18, 105, 48, -14, 4, -1 }, { -1, 5, -19, 97, 58, -16, 5, -1 }, { -1, 6, -19, 88, 68, -18, 5, -1 },
+      { -1, 6, -19, 78, 78, -19, 6, -1 }, { -1, 5, -18, 68, 88, -19, 6, -1 }, { -1, 5, -16, 58, 97, -19, 5, -1 }, { -1, 4, -14, 48, 105, -18, 5, -1 },
+      { -1, 4, -11, 37, 112, -16, 4, -1 }, { -1, 3, -9, 27, 118, -13, 4, -1 }, { 0, 2, -6, 18, 122, -10, 3, -1 }, { 0, 1, -3, 8, 126, -5, 1, 0 } },
+    { { 0 }, { -1, 3, -7, 127, 8, -3, 1, 0 }, { -2, 5, -13, 125, 17, -6, 3, -1 }, { -3, 7, -17, 121, 27, -10, 5, -2 },
+      { -4, 9, -20, 115, 37, -13, 6, -2 }, { -4, 10, -23, 108, 48, -16, 8, -3 }, { -4, 10, -24, 100, 59, -19, 9, -3 }, { -4, 11, -24, 90, 70, -21, 10, -4 },
+      { -4, 11, -23, 80, 80, -23, 11, -4 }, { -4, 10, -21, 70, 90, -24, 11, -4 }, { -3, 9, -19, 59, 100, -24, 10, -4 }, { -3, 8, -16, 48, 108, -23, 10, -4 },
+      { -2, 6, -13, 37, 115, -20, 9, -4 }, { -2, 5, -10, 27, 121, -17, 7, -3 }, { -1, 3, -6, 17, 125, -13, 5, -2 }, { 0, 1, -3, 8, 127, -7, 3, -1 } },
+};
+
+constexpr int TILE = 64;          /* the tile's row pitch: a superblock plane is at most 64 x 64 */
+constexpr int TROWS = 64 + 7;     /* rows of the 2-D form's horizontal pass */
+
+__device__ __forceinline__ void vif_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+/* one reference of one block: the plane (clamped to rw x rh samples), the block's integer origin in it and its phases (sixteenths) */
+struct VifSrc {
+    const uint8_t *base;
+    ptrdiff_t stride;
+    int rw, rh, xi, yi, mx, my;
+};
+
+template <typename PIX>
+__device__ __forceinline__ int vif_ref(const VifSrc &s, int x, int y)
+{
+    const int cx = min(max(x, 0), s.rw - 1), cy = min(max(y, 0), s.rh - 1);
+    return reinterpret_cast<const PIX *>(s.base + (ptrdiff_t)cy * s.stride)[cx];
+}
+
+/* one pass of mc[!!mx][!!my] at phase m over taps at(k) = the sample k steps along the pass (k = -3 .. 4) */
+template <typename AT>
+__device__ __forceinline__ int vif_tap(int filter, int m, int maxv, AT at)
+{
+    if (filter == 3) {
+        const int a = at(0);
+        return a + ((m * (at(1) - a) + 8) >> 4);
+    }
+    const int8_t *f = vif_taps[filter][m];
+    int sum = 64;
+#pragma unroll
+    for (int t = 0; t < 8; t++)
+        sum += f[t] * at(t - 3);
+    return min(max(sum >> 7, 0), maxv);
+}
+
+/* put (AVG false) or avg (AVG true) of a w x h block at tile position (lx, ly); tmp: the wave's temporaries */
+template <typename PIX, bool AVG>
+__device__ __forceinline__ void vif_predict(uint16_t *tile, PIX *tmp, const VifSrc &s, int lx, int ly, int lgw, int h, int filter, int maxv,
+                                            int lane)
+{
+    const int w = 1 << lgw;
+    if (s.mx && s.my) { /* the horizontal pass over rows -3 .. h + 3 (bilinear: 0 .. h) into pixel temporaries */
+        const int r0 = filter == 3 ? 0 : -3, rows = filter == 3 ? h + 1 : h + 7;
+        for (int i = lane; i < rows << lgw; i += 64) {
+            const int r = i >> lgw, x = i & (w - 1), yy = s.yi + r + r0;
+            tmp[r * TILE + x] = (PIX)vif_tap(filter, s.mx, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x + k, yy); });
+        }
+        vif_wave_sync();
+    }
+    for (int i = lane; i < h << lgw; i += 64) {
+        const int y = i >> lgw, x = i & (w - 1);
+        int v;
+        if (s.mx && s.my) {
+            const PIX *t = tmp + (y + (filter == 3 ? 0 : 3)) * TILE + x;
+            v = vif_tap(filter, s.my, maxv, [&](int k) { return (int)t[k * TILE]; });
+        } else if (s.mx) {
+            v = vif_tap(filter, s.mx, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x + k, s.yi + y); });
+        } else if (s.my) {
+            v = vif_tap(filter, s.my, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x, s.yi + y + k); });
+        } else {
+            v = vif_ref<PIX>(s, s.xi + x, s.yi + y);
+        }
+        uint16_t &d = tile[(ly + y) * TILE + lx + x];
+        d = (uint16_t)(AVG ? (d + v + 1) >> 1 : v);
+    }
+    vif_wave_sync(); /* tmp is reused by the next pass; an avg pass reads what this lane's put wrote */
+}
+
+/* one TU of N = 4 << LOG2-2 samples (WHT: the lossless 4x4) added to the covered samples of the tile at (lx, ly); lanes 0 .. N - 1
+ * take a column each.  The order of the batch kernel (vp9_itxfm.hip): column i through the first pass into `mine` (wave-private
+ * LDS, as the reference's dctcoef tmp[]), row i of that through the second; its outputs are picture column i. */
+template <int LOG2, bool WHT, bool HBD>
+__device__ __forceinline__ void vif_tu(uint16_t *tile, const unsigned long long *cov, void *mine_, const void *coeffs_, int txtp, bool dc,
+                                       int lx, int ly, int maxv, int lane)
+{
+    using COEF = typename std::conditional<HBD, int32_t, int16_t>::type;
+    using ST = typename std::conditional<HBD, long long, int>::type;
+    using UT = typename std::conditional<HBD, unsigned long long, uint32_t>::type;
+    constexpr int N = 1 << LOG2, BITS = WHT ? 0 : LOG2 == 2 ? 4 : LOG2 == 3 ? 5 : 6;
+    const COEF *coeffs = static_cast<const COEF *>(coeffs_);
+    COEF *mine = static_cast<COEF *>(mine_);
+    const int i = lane;
+    const bool adst1 = !WHT && LOG2 < 5 && (txtp == 1 || txtp == 3), adst2 = !WHT && LOG2 < 5 && (txtp == 2 || txtp == 3);
+    const bool dc_only = !WHT && dc && !adst1 && !adst2;
+    auto r14 = [](UT x) { return (ST)(x + ((UT)1 << 13)) >> 14; };
+    ST x[N], o[N];
+    auto run = [&](bool adst, bool first) {
+        if constexpr (HBD) {
+            if constexpr (WHT) vq64::vp_iwht(x, o, first);
+            else if (adst) vq64::vp_iadst(x, o);
+            else vq64::vp_idct<N>(x, o);
+        } else {
+            if constexpr (WHT) vq32::vp_iwht(x, o, first);
+            else if (adst) vq32::vp_iadst(x, o);
+            else vq32::vp_idct<N>(x, o);
+        }
+    };
+    if (dc_only) {
+        const int dcv = (int)r14((UT)r14((UT)(ST)coeffs[0] * 11585u) * 11585u);
+#pragma unroll
+        for (int k = 0; k < N; k++)
+            o[k] = (COEF)dcv;
+    } else {
+        if (i < N) {
+#pragma unroll
+            for (int k = 0; k < N; k++)
+                x[k] = coeffs[k * N + i];
+            run(adst1, true);
+#pragma unroll
+            for (int k = 0; k < N; k++)
+                mine[k * N + i] = (COEF)o[k];
+        }
+        vif_wave_sync();
+        if (i < N) {
+#pragma unroll
+            for (int k = 0; k < N; k++)
+                x[k] = mine[i * N + k];
+            run(adst2, false);
+        }
+        vif_wave_sync(); /* `mine` is reused by the wave's next TU */
+    }
+    if (i < N) {
+        const int xx = lx + i;
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            const int r = (int)(COEF)o[k];
+            const int z = BITS ? (int)((uint32_t)r + (1u << (BITS ? BITS - 1 : 0))) >> BITS : r;
+            if (cov[ly + k] >> xx & 1) {
+                uint16_t &d = tile[(ly + k) * TILE + xx];
+                d = (uint16_t)min(max((int)d + z, 0), maxv);
+            }
+        }
+    }
+}
+} // namespace
+
+/* grid: (sb_w * sb_h, frames); 4 waves per workgroup */
+template <typename PIX>
+__global__ __launch_bounds__(256) void k_vp9_inter_frame(const FFHipVp9InterPic *__restrict__ pics, int ss_h, int ss_v, int width, int height,
+                                                         int sb_w, int bd)
+{
+    constexpr int PS = (int)sizeof(PIX);
+    constexpr bool HBD = PS == 2;
+    __shared__ uint16_t tile[TILE * TILE];
+    __shared__ unsigned long long cov[TILE];
+    __shared__ __align__(16) PIX tmp_all[4][TROWS * TILE]; /* 2-D temporaries, or a TU's first-pass output (32 x 32 coefficients) */
+    static_assert(TROWS * TILE * PS >= 32 * 32 * (HBD ? 4 : 2), "a TU's intermediate fits the wave's temporaries");
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const FFHipVp9InterPic &P = pics[blockIdx.y];
+    const int a = (int)blockIdx.x, sy = a / sb_w, sx = a - sy * sb_w;
+    const int k0 = P.pred_sb_start[a], k1 = P.pred_sb_start[a + 1];
+    if (k0 >= k1)
+        return; /* no inter samples in this superblock */
+    const int nrefs = P.nrefs, maxv = (1 << bd) - 1;
+    const int dw = ((width + 7) >> 3) << 3, dh = ((height + 7) >> 3) << 3; /* the decoded area, luma */
+    PIX *const tmp = tmp_all[wave];
+
+    for (int p = 0; p < 3; p++) {
+        const int hs = p ? ss_h : 0, vs = p ? ss_v : 0, chroma = p ? 1 : 0;
+        const int Cw = TILE >> hs, Ch = TILE >> vs, x0 = sx * Cw, y0 = sy * Ch;
+        const int rw = (width + hs) >> hs, rh = (height + vs) >> vs; /* the references' real size */
+        if (tid < TILE)
+            cov[tid] = 0;
+        __syncthreads();
+
+        /* ---- 1. the superblock's predictions of this plane, a wave each ---- */
+        for (int k = k0 + wave; k < k1; k += 4) {
+            const FFHipVp9InterPred R = P.preds[k];
+            const int fl = R.flags, w = R.w, h = R.h, filter = R.filter, x = R.x, y = R.y;
+            if ((fl & ~3) || ((fl >> 1) & 1) != chroma)
+                continue;
+            const bool comp = fl & 1;
+            const bool ok = w >= 4 && w <= 64 && !(w & (w - 1)) && h >= 4 && h <= 64 && !(h & (h - 1)) && filter <= 3 && R.ref[0] < nrefs &&
+                            (!comp || R.ref[1] < nrefs) && x >= x0 && x + w <= x0 + Cw && y >= y0 && y + h <= y0 + Ch;
+            if (!ok)
+                continue;
+            const int lgw = __builtin_ctz(w), lx = x - x0, ly = y - y0;
+            for (int l = 0; l <= (int)comp; l++) {
+                const FFHipVp9InterRef &Rf = P.ref[l ? R.ref[1] : R.ref[0]]; /* selects: R stays in registers */
+                const int mvx = l ? R.mv[1][0] : R.mv[0][0], mvy = l ? R.mv[1][1] : R.mv[0][1];
+                VifSrc s;
+                s.base = Rf.base[p];
+                s.stride = Rf.stride[p];
+                s.rw = rw;
+                s.rh = rh;
+                if (!chroma) {
+                    s.xi = x + (mvx >> 3);
+                    s.yi = y + (mvy >> 3);
+                    s.mx = (mvx & 7) << 1;
+                    s.my = (mvy & 7) << 1;
+                } else { /* mc_chroma_unscaled: the MV in sixteenths of a chroma sample */
+                    const int mx = mvx * (1 << !ss_h), my = mvy * (1 << !ss_v);
+                    s.xi = x + (mx >> 4);
+                    s.yi = y + (my >> 4);
+                    s.mx = mx & 15;
+                    s.my = my & 15;
+                }
+                if (l)
+                    vif_predict<PIX, true>(tile, tmp, s, lx, ly, lgw, h, filter, maxv, lane);
+                else
+                    vif_predict<PIX, false>(tile, tmp, s, lx, ly, lgw, h, filter, maxv, lane);
+            }
+            if (lane < h)
+                atomicOr(&cov[ly + lane], (w == 64 ? ~0ull : (1ull << w) - 1) << lx);
+        }
+        __syncthreads();
+
+        /* ---- 2. the superblock's TUs of this plane: residuals into the covered samples ---- */
+        const FFHipVp9InterPlane &D = P.plane[p];
+        const int t0 = D.tu_sb_start[a], t1 = D.tu_sb_start[a + 1];
+        for (int k = t0 + wave; k < t1; k += 4) {
+            const FFHipVp9InterTU T = D.tus[k];
+            const int tx = T.tx, N = tx == 4 ? 4 : 4 << (tx & 3), x = T.x, y = T.y;
+            if (tx > 4 || ((x | y) & (N - 1)) || x < x0 || x + N > x0 + Cw || y < y0 || y + N > y0 + Ch)
+                continue;
+            const void *co = HBD ? (const void *)(static_cast<const int32_t *>(D.coeffs) + T.coeff_offset)
+                                 : (const void *)(static_cast<const int16_t *>(D.coeffs) + T.coeff_offset);
+            const int lx = x - x0, ly = y - y0, tp = T.txtp;
+            const bool dc = T.dc_only != 0;
+            switch (tx) {
+            case 0: vif_tu<2, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            case 1: vif_tu<3, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            case 2: vif_tu<4, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            case 3: vif_tu<5, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            default: vif_tu<2, true, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            }
+        }
+        __syncthreads();
+
+        /* ---- 3. the covered samples inside the decoded area to the plane, a quad per item ---- */
+        uint8_t *const base = D.base;
+        const ptrdiff_t stride = D.stride;
+        const int xe = min(Cw, (dw >> hs) - x0), ye = min(Ch, (dh >> vs) - y0); /* multiples of 4 */
+        const int lq = __builtin_ctz(Cw) - 2;
+        for (int i = tid; i < (Ch * Cw) >> 2; i += 256) {
+            const int r = i >> lq, c = (i - (r << lq)) << 2;
+            if (r >= ye || c >= xe)
+                continue;
+            const unsigned m = (unsigned)(cov[r] >> c) & 15;
+            if (!m)
+                continue;
+            PIX *d = reinterpret_cast<PIX *>(base + (ptrdiff_t)(y0 + r) * stride) + x0 + c;
+            const uint16_t *t = &tile[r * TILE + c];
+            if (m == 15) { /* base and stride are 4-sample aligned */
+                if (PS == 1)
+                    *reinterpret_cast<uint32_t *>(d) = (uint32_t)(uint8_t)t[0] | (uint32_t)(uint8_t)t[1] << 8 | (uint32_t)(uint8_t)t[2] << 16 |
+                                                       (uint32_t)(uint8_t)t[3] << 24;
+                else
+                    *reinterpret_cast<uint2 *>(d) = make_uint2((uint32_t)t[0] | (uint32_t)t[1] << 16, (uint32_t)t[2] | (uint32_t)t[3] << 16);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (m >> j & 1)
+                        d[j] = (PIX)t[j];
+            }
+        }
+        __syncthreads(); /* the next plane reuses the tile and the mask */
+    }
+}
+
+int ffhip_launch_vp9_inter_frames(int bd, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPic *pics, hipStream_t stream)
+{
+    const int cols = (width + 7) >> 3, rows = (height + 7) >> 3, sb_w = (cols + 7) >> 3, sb_h = (rows + 7) >> 3;
+    for (int p0 = 0; p0 < npics; p0 += VIF_PICS) {
+        const int n = npics - p0 < VIF_PICS ? npics - p0 : VIF_PICS;
+        /* the frames (their reference tables included) go to the device in stream order: a progress-pool slot is device memory that
+         * is not handed out again before the launch behind it has finished, and the copy from pageable memory is staged by the time
+         * hipMemcpyAsync returns */
+        FFHipProgressSlot ps;
+        const int r = ffhip_progress_acquire(0, stream, &ps);
+        if (r < 0)
+            return r;
+        FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
+        hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipVp9InterPic), hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) {
+            if (bd > 8)
+                hipLaunchKernelGGL(k_vp9_inter_frame<uint16_t>, dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
+                                   sb_w, bd);
+            else
+                hipLaunchKernelGGL(k_vp9_inter_frame<uint8_t>, dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
+                                   sb_w, 8);
+            e = hipGetLastError();
+        }
+        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
+        if (e != hipSuccess) {
+            ffhip_set_error("ffhip_vp9_inter_frames_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+            return FFHIP_EIO;
+        }
+        if (r2 < 0)
+            return r2;
+    }
+    return 0;
+}

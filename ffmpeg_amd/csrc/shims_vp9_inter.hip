@@ -1,0 +1,201 @@
+/*
+ * shims_vp9_inter.hip — ffhip_vp9_inter_frames_dev(): validates what the host can see of a frame set (geometry, planes, references,
+ * reference / destination overlap) and launches the inter reconstruction (kernels/vp9_inter_frame.hip) on the caller's stream.  The
+ * records themselves are device data and are checked by the kernel.  Also ffhip_vp9_inter_block_preds(), the device-free expansion
+ * of one decoded block into its prediction records (libavcodec/vp9_mc_template.h).
+ */
+#include <algorithm>
+#include <stdint.h>
+#include <vector>
+
+#include "kernels/common.h"
+#include "kernels/h264_kernels.h"
+
+extern "C" int ffhip_vp9_inter_pred_record_size(void) { return (int)sizeof(FFHipVp9InterPred); }
+extern "C" int ffhip_vp9_inter_tu_record_size(void) { return (int)sizeof(FFHipVp9InterTU); }
+
+namespace {
+struct Span { /* the bytes a plane occupies: [lo, hi) */
+    uintptr_t lo, hi;
+};
+Span plane_span(const void *base, ptrdiff_t stride, int w_bytes, int rows)
+{
+    const uintptr_t b = (uintptr_t)base;
+    return { b, b + (uintptr_t)((ptrdiff_t)(rows - 1) * stride + w_bytes) };
+}
+
+/* ROUNDED_DIV (libavutil/common.h): half away from zero, then C division (towards zero) */
+int rounded_div(int a, int b) { return (a >= 0 ? a + (b >> 1) : a - (b >> 1)) / b; }
+struct Mv {
+    int x, y;
+};
+Mv mv_of(const int16_t mv[4][2][2], int sub, int r) { return { mv[sub][r][0], mv[sub][r][1] }; }
+Mv div2(Mv a, Mv b) { return { rounded_div(a.x + b.x, 2), rounded_div(a.y + b.y, 2) }; }
+Mv div4(Mv a, Mv b, Mv c, Mv d) { return { rounded_div(a.x + b.x + c.x + d.x, 4), rounded_div(a.y + b.y + c.y + d.y, 4) }; }
+} // namespace
+
+extern "C" int ffhip_vp9_inter_frames_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPic *pics,
+                                          void *stream)
+{
+    if ((bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (ss_h & ~1) || (ss_v & ~1)) {
+        ffhip_set_error("ffhip_vp9_inter_frames_dev: bit depth %d (8, 10 or 12), subsampling %d, %d (0 or 1 each)", bit_depth, ss_h, ss_v);
+        return FFHIP_EINVAL;
+    }
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) {
+        ffhip_set_error("ffhip_vp9_inter_frames_dev: frame size %d x %d (1..65535)", width, height);
+        return FFHIP_EINVAL;
+    }
+    if (npics <= 0 || !pics) {
+        ffhip_set_error("ffhip_vp9_inter_frames_dev: npics = %d, or a NULL frame array", npics);
+        return FFHIP_EINVAL;
+    }
+    const int ps = bit_depth > 8 ? 2 : 1;
+    const unsigned amask = 4u * ps - 1; /* four samples per access */
+    const int cols = (width + 7) >> 3, rows = (height + 7) >> 3;
+    int dw[3], dh[3], rw[3], rh[3]; /* decoded area and real size per plane, samples */
+    for (int p = 0; p < 3; p++) {
+        const int hs = p ? ss_h : 0, vs = p ? ss_v : 0;
+        dw[p] = (cols * 8) >> hs;
+        dh[p] = (rows * 8) >> vs;
+        rw[p] = (width + hs) >> hs;
+        rh[p] = (height + vs) >> vs;
+    }
+    for (int i = 0; i < npics; i++) {
+        const FFHipVp9InterPic &P = pics[i];
+        if (!P.preds || !P.pred_sb_start || P.nrefs < 1 || P.nrefs > 3) {
+            ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d: NULL prediction tables or nrefs = %d (1..3)", i, P.nrefs);
+            return FFHIP_EINVAL;
+        }
+        for (int p = 0; p < 3; p++) {
+            const FFHipVp9InterPlane &D = P.plane[p];
+            if (!D.base || !D.tus || !D.tu_sb_start || !D.coeffs) {
+                ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d plane %d: a NULL pointer", i, p);
+                return FFHIP_EINVAL;
+            }
+            if ((((uintptr_t)D.base | (size_t)D.stride) & amask) || D.stride < (ptrdiff_t)dw[p] * ps) {
+                ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d plane %d: base and stride must be %u-byte aligned, the stride at least "
+                                "the decoded width", i, p, amask + 1);
+                return FFHIP_EINVAL;
+            }
+            for (int r = 0; r < P.nrefs; r++) {
+                const uint8_t *b = P.ref[r].base[p];
+                const ptrdiff_t s = P.ref[r].stride[p];
+                if (!b || (((uintptr_t)b | (size_t)s) & (ps - 1)) || s < (ptrdiff_t)rw[p] * ps) {
+                    ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d reference %d plane %d: NULL, misaligned or a stride below the "
+                                    "width", i, r, p);
+                    return FFHIP_EINVAL;
+                }
+            }
+        }
+    }
+    /* no reference plane of the call may be a destination plane of the call: a launch's frames are predicted side by side.  The
+     * destination spans are sorted by start with a running maximum of their ends, so each reference span is one binary search */
+    std::vector<Span> dst;
+    dst.reserve((size_t)npics * 3);
+    for (int i = 0; i < npics; i++)
+        for (int p = 0; p < 3; p++)
+            dst.push_back(plane_span(pics[i].plane[p].base, pics[i].plane[p].stride, dw[p] * ps, dh[p]));
+    std::sort(dst.begin(), dst.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
+    std::vector<uintptr_t> hi_max(dst.size());
+    for (size_t k = 0; k < dst.size(); k++)
+        hi_max[k] = k ? std::max(hi_max[k - 1], dst[k].hi) : dst[k].hi;
+    for (int j = 0; j < npics; j++)
+        for (int r = 0; r < pics[j].nrefs; r++)
+            for (int q = 0; q < 3; q++) {
+                const Span s = plane_span(pics[j].ref[r].base[q], pics[j].ref[r].stride[q], rw[q] * ps, rh[q]);
+                const size_t n = (size_t)(std::lower_bound(dst.begin(), dst.end(), s.hi, [](const Span &x, uintptr_t v) { return x.lo < v; }) -
+                                          dst.begin());
+                if (n && hi_max[n - 1] > s.lo) {
+                    ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d reference %d plane %d overlaps a plane the call writes", j, r, q);
+                    return FFHIP_EINVAL;
+                }
+            }
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_vp9_inter_frames(bit_depth, ss_h, ss_v, width, height, npics, pics, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_vp9_inter_block_preds(FFHipVp9InterPred *out, int bs, int row, int col, const int16_t mv[4][2][2], int comp,
+                                           const uint8_t ref[2], int filter, int ss_h, int ss_v)
+{
+    if (!out || !mv || !ref || bs < 0 || bs > 12 || row < 0 || row > 8191 || col < 0 || col > 8191 || filter < 0 || filter > 3 ||
+        (ss_h & ~1) || (ss_v & ~1)) {
+        ffhip_set_error("ffhip_vp9_inter_block_preds: block size %d (0..12), row %d / col %d (0..8191), filter %d (0..3), subsampling %d, %d",
+                        bs, row, col, filter, ss_h, ss_v);
+        return FFHIP_EINVAL;
+    }
+    /* ff_vp9_bwh_tab[0] (libavcodec/vp9data.c) in samples: BS_64x64 .. BS_4x4 */
+    static const uint8_t bw_tab[13] = { 64, 64, 32, 32, 32, 16, 16, 16, 8, 8, 8, 4, 4 };
+    static const uint8_t bh_tab[13] = { 64, 32, 64, 32, 16, 32, 16, 8, 16, 8, 4, 8, 4 };
+    int n = 0;
+    const int nr = comp ? 2 : 1;
+    /* one call: (x, y, w, h) in its plane, the MV of each reference from `pick` */
+    auto emit = [&](bool chroma, int x, int y, int w, int h, auto pick) {
+        FFHipVp9InterPred &R = out[n++];
+        R = FFHipVp9InterPred();
+        R.x = (uint16_t)x;
+        R.y = (uint16_t)y;
+        R.w = (uint8_t)w;
+        R.h = (uint8_t)h;
+        R.filter = (uint8_t)filter;
+        R.flags = (uint8_t)((comp ? 1 : 0) | (chroma ? 2 : 0));
+        for (int r = 0; r < nr; r++) {
+            const Mv m = pick(r);
+            R.ref[r] = ref[r];
+            R.mv[r][0] = (int16_t)m.x;
+            R.mv[r][1] = (int16_t)m.y;
+        }
+    };
+    const int ly = row << 3, lx = col << 3, cy = row << (3 - ss_v), cx = col << (3 - ss_h);
+    auto sub = [&](int s) { return [&, s](int r) { return mv_of(mv, s, r); }; };
+    if (bs < 10) { /* at least 8 x 8 */
+        const int w = bw_tab[bs], h = bh_tab[bs];
+        emit(false, lx, ly, w, h, sub(0));
+        emit(true, cx, cy, w >> ss_h, h >> ss_v, sub(0));
+    } else if (bs == 10) { /* 8 x 4 */
+        emit(false, lx, ly, 8, 4, sub(0));
+        emit(false, lx, ly + 4, 8, 4, sub(2));
+        auto d02 = [&](int r) { return div2(mv_of(mv, 0, r), mv_of(mv, 2, r)); };
+        if (ss_v) {
+            emit(true, cx, row << 2, 8 >> ss_h, 4, d02);
+        } else {
+            emit(true, cx, ly, 8 >> ss_h, 4, sub(0));
+            /* libvpx takes the wrong block's MV for the bottom half in 4:2:2 (the reference emulates it) */
+            if (ss_h)
+                emit(true, cx, ly + 4, 4, 4, d02);
+            else
+                emit(true, cx, ly + 4, 8, 4, sub(2));
+        }
+    } else if (bs == 11) { /* 4 x 8 */
+        emit(false, lx, ly, 4, 8, sub(0));
+        emit(false, lx + 4, ly, 4, 8, sub(1));
+        if (ss_h) {
+            emit(true, col << 2, cy, 4, 8 >> ss_v, [&](int r) { return div2(mv_of(mv, 0, r), mv_of(mv, 1, r)); });
+        } else {
+            emit(true, lx, cy, 4, 8 >> ss_v, sub(0));
+            emit(true, lx + 4, cy, 4, 8 >> ss_v, sub(1));
+        }
+    } else { /* 4 x 4 */
+        emit(false, lx, ly, 4, 4, sub(0));
+        emit(false, lx + 4, ly, 4, 4, sub(1));
+        emit(false, lx, ly + 4, 4, 4, sub(2));
+        emit(false, lx + 4, ly + 4, 4, 4, sub(3));
+        auto d2 = [&](int a, int b) { return [&, a, b](int r) { return div2(mv_of(mv, a, r), mv_of(mv, b, r)); }; };
+        if (ss_h && ss_v) {
+            emit(true, col << 2, row << 2, 4, 4,
+                 [&](int r) { return div4(mv_of(mv, 0, r), mv_of(mv, 1, r), mv_of(mv, 2, r), mv_of(mv, 3, r)); });
+        } else if (ss_v) { /* 4:4:0 */
+            emit(true, lx, row << 2, 4, 4, d2(0, 2));
+            emit(true, lx + 4, row << 2, 4, 4, d2(1, 3));
+        } else if (ss_h) { /* 4:2:2, the same libvpx quirk for the bottom block */
+            emit(true, col << 2, ly, 4, 4, d2(0, 1));
+            emit(true, col << 2, ly + 4, 4, 4, d2(1, 2));
+        } else {
+            emit(true, lx, ly, 4, 4, sub(0));
+            emit(true, lx + 4, ly, 4, 4, sub(1));
+            emit(true, lx, ly + 4, 4, 4, sub(2));
+            emit(true, lx + 4, ly + 4, 4, 4, sub(3));
+        }
+    }
+    return n;
+}

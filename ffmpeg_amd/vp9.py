@@ -211,3 +211,59 @@ def loopfilter_frame_ssc(y, u, v, stride_y, stride_uv, cols, rows, tables, ctabl
     return _lib.check(_lib.lib().ffhip_vp9_loopfilter_frame_ssc_dev(bit_depth, ss[0], ss[1], y.data_ptr(), u.data_ptr(), v.data_ptr(), stride_y,
                                                                     stride_uv, cols, rows, tables.data_ptr(), ctables.data_ptr(), _st(stream)),
                       "ffhip_vp9_loopfilter_frame_ssc_dev")
+
+
+#: FFHipVp9InterPred (include/ffhip.h): one mc_luma_dir / mc_chroma_dir call of ffhip_vp9_inter_frames_dev.  flags: bit 0 compound,
+#: bit 1 chroma; ref: indices into the frame's references; mv: [ref][x, y] in eighths of a luma sample.
+INTER_PRED_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("w", np.uint8), ("h", np.uint8), ("filter", np.uint8), ("flags", np.uint8),
+                             ("ref", np.uint8, 2), ("pad", np.uint8, 2), ("mv", np.int16, (2, 2))])
+#: FFHipVp9InterTU: one itxfm_add call of inter_recon; coeff_offset counts coefficients (int16 at 8 bits, int32 above).
+INTER_TU_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("coeff_offset", np.int32), ("tx", np.uint8), ("txtp", np.uint8),
+                           ("dc_only", np.uint8), ("pad", np.uint8)])
+INTER_COMP, INTER_CHROMA = 1, 2
+
+
+class InterPlane(C.Structure):
+    """FFHipVp9InterPlane (device pointers)"""
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_ssize_t), ("tus", C.c_void_p), ("tu_sb_start", C.c_void_p), ("coeffs", C.c_void_p)]
+
+
+class InterRef(C.Structure):
+    """FFHipVp9InterRef (device pointers, strides in bytes)"""
+    _fields_ = [("base", C.c_void_p * 3), ("stride", C.c_ssize_t * 3)]
+
+
+class InterPic(C.Structure):
+    """FFHipVp9InterPic"""
+    _fields_ = [("plane", InterPlane * 3), ("preds", C.c_void_p), ("pred_sb_start", C.c_void_p), ("nrefs", C.c_int32), ("pad", C.c_int32),
+                ("ref", InterRef * 3)]
+
+
+def inter_frames(pics, width, height, ss=(1, 1), stream=None, bit_depth=8):
+    """ffhip_vp9_inter_frames_dev on npics = len(pics) frames of one geometry.  pics[i] = (planes, preds, pred_sb_start, refs): planes,
+    three tuples (Y, Cb, Cr) of (plane, stride, tus, tu_sb_start, coeffs); preds the INTER_PRED_DTYPE records as bytes sorted by raster
+    superblock, pred_sb_start the int32 superblock starts (sb_w * sb_h + 1) — device tensors; refs a list (1..3) of per-plane (plane
+    tensor, stride in bytes) tuples.  ss = (ss_h, ss_v).  Asynchronous on `stream`."""
+    arr = (InterPic * max(len(pics), 1))()
+    for i, (planes, preds, pred_sb_start, refs) in enumerate(pics):
+        for p, (plane, stride, tus, tu_sb_start, coeffs) in enumerate(planes):
+            arr[i].plane[p] = InterPlane(plane.data_ptr(), stride, tus.data_ptr(), tu_sb_start.data_ptr(), coeffs.data_ptr())
+        arr[i].preds, arr[i].pred_sb_start = preds.data_ptr(), pred_sb_start.data_ptr()
+        arr[i].nrefs = len(refs)
+        for r, ref in enumerate(refs):
+            for p, (plane, stride) in enumerate(ref):
+                arr[i].ref[r].base[p] = plane.data_ptr()
+                arr[i].ref[r].stride[p] = stride
+    return _lib.check(_lib.lib().ffhip_vp9_inter_frames_dev(bit_depth, ss[0], ss[1], width, height, len(pics), C.cast(arr, C.c_void_p),
+                                                            _st(stream)), "ffhip_vp9_inter_frames_dev")
+
+
+def inter_block_preds(bs, row, col, mv, comp, ref, filter, ss=(1, 1)):
+    """ffhip_vp9_inter_block_preds: the INTER_PRED_DTYPE records of one decoded block (enum BlockSize bs, row / col in 8-sample units,
+    mv = b->mv as [4][2][2], comp, ref = b->ref, filter = b->filter), in vp9_mc_template.h's call order"""
+    out = np.zeros(8, INTER_PRED_DTYPE)
+    mvs = np.ascontiguousarray(np.asarray(mv, np.int16).reshape(4, 2, 2))
+    refs = np.ascontiguousarray(np.asarray(ref, np.uint8).reshape(2))
+    n = _lib.check(_lib.lib().ffhip_vp9_inter_block_preds(out.ctypes.data, bs, row, col, mvs.ctypes.data, int(comp), refs.ctypes.data, filter,
+                                                          ss[0], ss[1]), "ffhip_vp9_inter_block_preds")
+    return out[:n]

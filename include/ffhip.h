@@ -1991,6 +1991,91 @@ int ffhip_vp9_loopfilter_frames_ssc_dev(int bit_depth, int ss_h, int ss_v, int n
                                         ptrdiff_t stride_uv, int cols, int rows, void *stream);
 
 /**
+ * VP9 inter reconstruction of whole frames in one launch: inter_pred() and the residual half of inter_recon() (libavcodec/vp9recon.c,
+ * vp9_mc_template.h) for every inter block of up to 16 frames, from references resident in device memory.  A decoder records a
+ * frame's prediction calls and transform blocks instead of running them; one launch then writes the frame, and
+ * ffhip_vp9_loopfilter_frames_dev() filters it.
+ *
+ *  Semantics, byte for byte those of the reference at bit_depth (vp9dsp_template.c, the oracle's ffo_vp9_mc_bd / ffo_vp9_itxfm_add_bd):
+ *  - prediction: each FFHipVp9InterPred record is one mc_luma_dir / mc_chroma_dir call: put from ref[0]; when compound, then avg from
+ *    ref[1] (the rounding average (a + b + 1) >> 1 of the two clipped predictions).  Each filter pass is clip((sum + 64) >> 7) into
+ *    pixel-type temporaries (the 2-D form filters rows -3 .. h + 3 horizontally first); bilinear is a + ((m (b - a) + 8) >> 4).
+ *    Luma: x' = x + (mv.x >> 3), phase (mv.x & 7) << 1 in sixteenths.  Chroma: m = mv.x * (1 << !ss_h), x' = x + (m >> 4), phase
+ *    m & 15; rows the same with mv.y and ss_v.  A chroma record drives Cb and Cr;
+ *  - reference edge: every reference sample is read with its coordinates clamped to the reference frame's real size, [0, width) x
+ *    [0, height) for luma and [0, (width + ss_h) >> ss_h) x [0, (height + ss_v) >> ss_v) for chroma: what emulated_edge_mc gives
+ *    mc_luma_unscaled / mc_chroma_unscaled (vp9recon.c).  MVs may point anywhere;
+ *  - residuals: when every prediction of a superblock is done, its TUs add itxfm_add[tx][txtp] (the dc-only shortcut of DCT_DCT when
+ *    dc_only, as the batch face).  Coefficients are read, never zeroed.  A TU changes only samples a prediction of its superblock covers;
+ *  - what is written: the covered samples inside the decoded area, cols * 8 x rows * 8 luma samples (cols = (width + 7) >> 3, rows =
+ *    (height + 7) >> 3), shifted by ss_h / ss_v for chroma: what ff_vp9_decode_block copies back from its overhang buffer.  Samples no
+ *    prediction covers (intra blocks, the stride padding, anything outside the decoded area) are never written;
+ *  - a malformed record writes nothing and reads nothing outside its planes and references: a prediction with w or h outside
+ *    {4, 8, 16, 32, 64}, filter > 3, a reference it uses at or above nrefs, flags bits other than 0 and 1, or lying outside the
+ *    superblock it is listed under (in its plane); a TU with tx > 4, not aligned to its size, or outside its superblock.
+ *  Trusted (the ABI carries no lengths to check them against): the superblock start tables and the records they index, each TU's
+ *  coeff_offset range, and disjointness: the predictions of one plane of a superblock must be disjoint, as must its TUs; overlapping
+ *  ones leave undefined values inside that superblock and nothing outside it.
+ *  Out of scope (they stay on the C path): scaled references (smc; every reference must have the frame's size), intra blocks of
+ *  inter frames (their samples are left untouched), MV parsing and clamping.
+ */
+typedef struct FFHipVp9InterPred {  /* one mc_luma_dir / mc_chroma_dir call (with its compound second half), 20 bytes */
+    uint16_t x, y;                  /* its top-left sample in its plane */
+    uint8_t  w, h;                  /* 4, 8, 16, 32 or 64 */
+    uint8_t  filter;                /* enum FilterMode 0..3 */
+    uint8_t  flags;                 /* bit 0 compound, bit 1 chroma (the record drives Cb and Cr) */
+    uint8_t  ref[2];                /* 0..2: indices into the frame's references (b->ref[]) */
+    uint8_t  pad[2];
+    int16_t  mv[2][2];              /* [ref][x, y]: the VP9mv passed to mc_*_dir, eighths of a luma sample */
+} FFHipVp9InterPred;
+typedef struct FFHipVp9InterTU {    /* one itxfm_add call of inter_recon, 12 bytes */
+    uint16_t x, y;                  /* its top-left sample in its plane */
+    int32_t  coeff_offset;          /* coefficients (int16 at 8 bits, int32 above) into the plane's coeffs: N * N, the decoder's layout */
+    uint8_t  tx;                    /* 0..3: 4x4 .. 32x32, 4: the lossless WHT */
+    uint8_t  txtp;                  /* enum TxfmType (DCT_DCT for inter blocks); ignored for 32x32 and the WHT */
+    uint8_t  dc_only;               /* eob == 1 */
+    uint8_t  pad;
+} FFHipVp9InterTU;
+typedef struct FFHipVp9InterPlane { /* device pointers */
+    uint8_t *base;                  /* the plane's top-left sample */
+    ptrdiff_t stride;               /* bytes, >= the decoded width in bytes */
+    const FFHipVp9InterTU *tus;     /* sorted by raster superblock address */
+    const int32_t *tu_sb_start;     /* sb_w * sb_h + 1 entries: the TUs of raster superblock a are tus[tu_sb_start[a] .. [a + 1]) */
+    const void *coeffs;             /* int16 (8 bits) or int32 (10 / 12 bits) coefficients */
+} FFHipVp9InterPlane;
+typedef struct FFHipVp9InterRef {   /* one reference frame (device pointers) of the call's size, depth and subsampling */
+    const uint8_t *base[3];         /* Y, Cb, Cr */
+    ptrdiff_t stride[3];            /* bytes */
+} FFHipVp9InterRef;
+typedef struct FFHipVp9InterPic {
+    FFHipVp9InterPlane plane[3];    /* Y, Cb, Cr */
+    const FFHipVp9InterPred *preds; /* device, sorted by raster superblock (64 x 64 luma) address */
+    const int32_t *pred_sb_start;   /* device, sb_w * sb_h + 1 entries, as tu_sb_start */
+    int32_t nrefs;                  /* 1..3 */
+    int32_t pad;
+    FFHipVp9InterRef ref[3];        /* in this host array: the face stages it to the device */
+} FFHipVp9InterPic;
+/** npics frames of one geometry: width x height luma samples (1..65535), bit_depth 8, 10 or 12 (uint16_t samples above 8), chroma
+ *  subsampling (ss_h, ss_v) in {0, 1}^2.  sb_w = (cols + 7) >> 3, sb_h = (rows + 7) >> 3.  Every plane needs non-NULL pointers, base
+ *  and stride multiples of 4 samples and a stride of at least the decoded width; references are sample-aligned with a stride of at
+ *  least the plane's real width.  Frames go 16 to a launch.  Asynchronous on `stream`.
+ *  FFHIP_EINVAL (before any device check) for another depth or subsampling, a size outside 1..65535, npics <= 0, NULL or misaligned
+ *  planes, a stride below the decoded width, nrefs outside 1..3, a NULL or misaligned plane among the first nrefs references, or a
+ *  reference plane that overlaps a destination plane of any frame of the call; FFHIP_ENOSYS without a device. */
+int ffhip_vp9_inter_frames_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics,
+                               const FFHipVp9InterPic *pics /* host array */, void *stream);
+/** sizeof(FFHipVp9InterPred), sizeof(FFHipVp9InterTU), for bindings that mirror the records (no device needed). */
+int ffhip_vp9_inter_pred_record_size(void);
+int ffhip_vp9_inter_tu_record_size(void);
+/** The prediction records of one decoded block, in vp9_mc_template.h's call order (device-free, like ffhip_vp9_lf_sb_tables): bs =
+ *  enum BlockSize 0..12 (BS_64x64 .. BS_4x4), row / col in 8-sample units (0..8191), mv = b->mv as [sub-block][ref][x, y], comp =
+ *  b->comp, ref = b->ref, filter = b->filter (0..3).  At least 8x8: one luma and one chroma call with mv[0].  8x4, 4x8 and 4x4: the
+ *  template's sub-block calls, chroma MVs from ROUNDED_DIV_MVx2 / x4 (rounding half away from zero) with the libvpx 4:2:2 quirks it
+ *  emulates.  Writes up to 8 records to out; returns their count, FFHIP_EINVAL for bad arguments. */
+int ffhip_vp9_inter_block_preds(FFHipVp9InterPred *out, int bs, int row, int col, const int16_t mv[4][2][2], int comp, const uint8_t ref[2],
+                                int filter, int ss_h, int ss_v);
+
+/**
  * vp9dsp above 8 bits (profiles 2 / 3): the batch faces above at the bpp ff_vp9dsp_init(dsp, bpp, bitexact) instantiates its template
  * for (libavcodec/vp9dsp.c:88-112, vp9dsp_10bpp.c / vp9dsp_12bpp.c).  bit_depth 8, 10 or 12.  Samples are uint16_t above 8 bits,
  * itxfm_add's coefficients int32_t (the reference's dctcoef; FFHipVp9TU.coeff_offset counts coefficients) and its butterflies run
