@@ -269,6 +269,9 @@ def lib():
         "ffhip_vp9_inter_pred_record_size": (C.c_int, []),
         "ffhip_vp9_inter_tu_record_size": (C.c_int, []),
         "ffhip_vp9_inter_block_preds": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
+        "ffhip_vp9_intra_frames_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_vp9_intra_record_size": (C.c_int, []),
+        "ffhip_vp9_intra_block_records": (C.c_int, [vp] + [C.c_int] * 5 + [vp, C.c_int, vp] + [C.c_int] * 5),
         "ffhip_hevc_inter_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_hevc_inter_pu_record_size": (C.c_int, []),
         "ffhip_hevc_inter_tu_record_size": (C.c_int, []),

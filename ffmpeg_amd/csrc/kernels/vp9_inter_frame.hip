@@ -7,7 +7,7 @@
  *      samples, and marks what it wrote in a coverage mask (a bit per sample); a compound record averages its second reference into
  *      the same tile positions;
  *   2. after a barrier, runs the superblock's TUs of the plane, a wave each, through the butterfly network of vp9_itxfm.hip
- *      (vp9_itxfm_net.inc, 32-bit at 8 bits, 64-bit above) and adds them to the covered samples of the tile;
+ *      (vp9_itxfm_net.inc, 32-bit at 8 bits, 64-bit above; vp9_itxfm_tile.h) and adds them to the covered samples of the tile;
  *   3. after a barrier, stores the covered samples inside the decoded area to the plane, four at a time where a quad is covered.
  * What no record covers (intra blocks, the stride padding, anything outside the decoded area) is never written.
  *
@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "h264_kernels.h"
+#include "vp9_itxfm_tile.h"
 
 static_assert(sizeof(FFHipVp9InterPred) == 20, "FFHipVp9InterPred is a 20-byte record");
 static_assert(sizeof(FFHipVp9InterTU) == 12, "FFHipVp9InterTU is a 12-byte record");
@@ -32,21 +33,6 @@ static_assert(sizeof(FFHipVp9InterPic) % 8 == 0, "FFHipVp9InterPic is staged as 
 static_assert(VIF_PICS * sizeof(FFHipVp9InterPic) <= FFHIP_PROGRESS_SLOT_INTS * sizeof(int), "a launch's frames fit one slot");
 
 namespace {
-namespace vq32 {
-#define VP_ST int
-#define VP_UT uint32_t
-#include "vp9_itxfm_net.inc"
-#undef VP_ST
-#undef VP_UT
-} // namespace vq32
-namespace vq64 {
-#define VP_ST long long
-#define VP_UT unsigned long long
-#include "vp9_itxfm_net.inc"
-#undef VP_ST
-#undef VP_UT
-} // namespace vq64
-
 /* ff_vp9_subpel_filters (libavcodec/vp9dsp.c): [filter 0 smooth / 1 regular / 2 sharp][m in sixteenths][tap]; m = 0 is never used */
 __constant__ int8_t vif_taps[3][16][8] = {
     { { 0 }, { -3, -1, 32, 64, 38, 1, -3, 0 }, { -2, -2, 29, 63, 41, 2, -3, 0 }, { -2, -2, 26, 63, 43, 4, -4, 0 },
@@ -65,13 +51,6 @@ __constant__ int8_t vif_taps[3][16][8] = {
 
 constexpr int TILE = 64;          /* the tile's row pitch: a superblock plane is at most 64 x 64 */
 constexpr int TROWS = 64 + 7;     /* rows of the 2-D form's horizontal pass */
-
-__device__ __forceinline__ void vif_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 /* one reference of one block: the plane (clamped to rw x rh samples), the block's integer origin in it and its phases (sixteenths) */
 struct VifSrc {
@@ -136,72 +115,6 @@ __device__ __forceinline__ void vif_predict(uint16_t *tile, PIX *tmp, const VifS
     vif_wave_sync(); /* tmp is reused by the next pass; an avg pass reads what this lane's put wrote */
 }
 
-/* one TU of N = 4 << LOG2-2 samples (WHT: the lossless 4x4) added to the covered samples of the tile at (lx, ly); lanes 0 .. N - 1
- * take a column each.  The order of the batch kernel (vp9_itxfm.hip): column i through the first pass into `mine` (wave-private
- * LDS, as the reference's dctcoef tmp[]), row i of that through the second; its outputs are picture column i. */
-template <int LOG2, bool WHT, bool HBD>
-__device__ __forceinline__ void vif_tu(uint16_t *tile, const unsigned long long *cov, void *mine_, const void *coeffs_, int txtp, bool dc,
-                                       int lx, int ly, int maxv, int lane)
-{
-    using COEF = typename std::conditional<HBD, int32_t, int16_t>::type;
-    using ST = typename std::conditional<HBD, long long, int>::type;
-    using UT = typename std::conditional<HBD, unsigned long long, uint32_t>::type;
-    constexpr int N = 1 << LOG2, BITS = WHT ? 0 : LOG2 == 2 ? 4 : LOG2 == 3 ? 5 : 6;
-    const COEF *coeffs = static_cast<const COEF *>(coeffs_);
-    COEF *mine = static_cast<COEF *>(mine_);
-    const int i = lane;
-    const bool adst1 = !WHT && LOG2 < 5 && (txtp == 1 || txtp == 3), adst2 = !WHT && LOG2 < 5 && (txtp == 2 || txtp == 3);
-    const bool dc_only = !WHT && dc && !adst1 && !adst2;
-    auto r14 = [](UT x) { return (ST)(x + ((UT)1 << 13)) >> 14; };
-    ST x[N], o[N];
-    auto run = [&](bool adst, bool first) {
-        if constexpr (HBD) {
-            if constexpr (WHT) vq64::vp_iwht(x, o, first);
-            else if (adst) vq64::vp_iadst(x, o);
-            else vq64::vp_idct<N>(x, o);
-        } else {
-            if constexpr (WHT) vq32::vp_iwht(x, o, first);
-            else if (adst) vq32::vp_iadst(x, o);
-            else vq32::vp_idct<N>(x, o);
-        }
-    };
-    if (dc_only) {
-        const int dcv = (int)r14((UT)r14((UT)(ST)coeffs[0] * 11585u) * 11585u);
-#pragma unroll
-        for (int k = 0; k < N; k++)
-            o[k] = (COEF)dcv;
-    } else {
-        if (i < N) {
-#pragma unroll
-            for (int k = 0; k < N; k++)
-                x[k] = coeffs[k * N + i];
-            run(adst1, true);
-#pragma unroll
-            for (int k = 0; k < N; k++)
-                mine[k * N + i] = (COEF)o[k];
-        }
-        vif_wave_sync();
-        if (i < N) {
-#pragma unroll
-            for (int k = 0; k < N; k++)
-                x[k] = mine[i * N + k];
-            run(adst2, false);
-        }
-        vif_wave_sync(); /* `mine` is reused by the wave's next TU */
-    }
-    if (i < N) {
-        const int xx = lx + i;
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            const int r = (int)(COEF)o[k];
-            const int z = BITS ? (int)((uint32_t)r + (1u << (BITS ? BITS - 1 : 0))) >> BITS : r;
-            if (cov[ly + k] >> xx & 1) {
-                uint16_t &d = tile[(ly + k) * TILE + xx];
-                d = (uint16_t)min(max((int)d + z, 0), maxv);
-            }
-        }
-    }
-}
 } // namespace
 
 /* grid: (sb_w * sb_h, frames); 4 waves per workgroup */
@@ -288,11 +201,11 @@ __global__ __launch_bounds__(256) void k_vp9_inter_frame(const FFHipVp9InterPic 
             const int lx = x - x0, ly = y - y0, tp = T.txtp;
             const bool dc = T.dc_only != 0;
             switch (tx) {
-            case 0: vif_tu<2, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
-            case 1: vif_tu<3, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
-            case 2: vif_tu<4, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
-            case 3: vif_tu<5, false, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
-            default: vif_tu<2, true, HBD>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            case 0: vif_tu<2, false, HBD, TILE, true>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            case 1: vif_tu<3, false, HBD, TILE, true>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            case 2: vif_tu<4, false, HBD, TILE, true>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            case 3: vif_tu<5, false, HBD, TILE, true>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
+            default: vif_tu<2, true, HBD, TILE, true>(tile, cov, tmp, co, tp, dc, lx, ly, maxv, lane); break;
             }
         }
         __syncthreads();

@@ -267,3 +267,51 @@ def inter_block_preds(bs, row, col, mv, comp, ref, filter, ss=(1, 1)):
     n = _lib.check(_lib.lib().ffhip_vp9_inter_block_preds(out.ctypes.data, bs, row, col, mvs.ctypes.data, int(comp), refs.ctypes.data, filter,
                                                           ss[0], ss[1]), "ffhip_vp9_inter_block_preds")
     return out[:n]
+
+
+#: FFHipVp9IntraRec (include/ffhip.h): one iteration of intra_recon's loops (intra_pred[tx][mode], then itxfm_add); mode is the coded
+#: enum IntraPredMode 0..9, tx 4 the lossless 4x4; coeff_offset counts coefficients (int16 at 8 bits, int32 above).
+INTRA_REC_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("coeff_offset", np.int32), ("tx", np.uint8), ("mode", np.uint8),
+                            ("txtp", np.uint8), ("flags", np.uint8)])
+INTRA_RESIDUAL, INTRA_DC_ONLY, INTRA_HAVE_RIGHT = 1, 2, 4
+
+
+class IntraPlane(C.Structure):
+    """FFHipVp9IntraPlane (device pointers)"""
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_ssize_t), ("recs", C.c_void_p), ("rec_sb_start", C.c_void_p), ("coeffs", C.c_void_p)]
+
+
+class IntraPic(C.Structure):
+    """FFHipVp9IntraPic"""
+    _fields_ = [("plane", IntraPlane * 3), ("log2_tile_cols", C.c_int32), ("pad", C.c_int32)]
+
+
+def intra_frames(pics, width, height, ss=(1, 1), stream=None, bit_depth=8):
+    """ffhip_vp9_intra_frames_dev on npics = len(pics) frames of one geometry.  pics[i] = (planes, log2_tile_cols): planes, three tuples
+    (Y, Cb, Cr) of (plane, stride, recs, rec_sb_start, coeffs) — device tensors; recs the INTRA_REC_DTYPE records as bytes sorted by raster
+    superblock (in decoding order within one), rec_sb_start the int32 superblock starts (sb_w * sb_h + 1).  ss = (ss_h, ss_v).
+    Asynchronous on `stream`."""
+    arr = (IntraPic * max(len(pics), 1))()
+    for i, (planes, log2_tile_cols) in enumerate(pics):
+        for p, (plane, stride, recs, rec_sb_start, coeffs) in enumerate(planes):
+            arr[i].plane[p] = IntraPlane(plane.data_ptr(), stride, recs.data_ptr(), rec_sb_start.data_ptr(), coeffs.data_ptr())
+        arr[i].log2_tile_cols = log2_tile_cols
+    return _lib.check(_lib.lib().ffhip_vp9_intra_frames_dev(bit_depth, ss[0], ss[1], width, height, len(pics), C.cast(arr, C.c_void_p),
+                                                            _st(stream)), "ffhip_vp9_intra_frames_dev")
+
+
+def intra_block_records(plane, bs, tx, row, col, mode, skip, eob, lossless, cols, rows, ss=(1, 1)):
+    """ffhip_vp9_intra_block_records: the INTRA_REC_DTYPE records of one decoded block in one plane, in intra_recon's order (plane 0:
+    tx = b->tx, mode = b->mode; planes 1 / 2: tx = b->uvtx, mode = [b->uvmode]; eob[n] as intra_recon reads it; coeff_offset = 16 n)"""
+    out = np.zeros(256, INTRA_REC_DTYPE)
+    modes = np.zeros(4, np.uint8)
+    m = np.asarray(mode, np.uint8).reshape(-1)
+    modes[:len(m)] = m
+    eobs = np.zeros(256, np.uint16)
+    if eob is not None:
+        e = np.asarray(eob, np.uint16).reshape(-1)
+        eobs[:len(e)] = e
+    n = _lib.check(_lib.lib().ffhip_vp9_intra_block_records(out.ctypes.data, plane, bs, tx, row, col, modes.ctypes.data, int(skip),
+                                                            eobs.ctypes.data, int(lossless), cols, rows, ss[0], ss[1]),
+                   "ffhip_vp9_intra_block_records")
+    return out[:n]

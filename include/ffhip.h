@@ -2016,8 +2016,8 @@ int ffhip_vp9_loopfilter_frames_ssc_dev(int bit_depth, int ss_h, int ss_v, int n
  *  Trusted (the ABI carries no lengths to check them against): the superblock start tables and the records they index, each TU's
  *  coeff_offset range, and disjointness: the predictions of one plane of a superblock must be disjoint, as must its TUs; overlapping
  *  ones leave undefined values inside that superblock and nothing outside it.
- *  Out of scope (they stay on the C path): scaled references (smc; every reference must have the frame's size), intra blocks of
- *  inter frames (their samples are left untouched), MV parsing and clamping.
+ *  Out of scope (they stay on the C path): scaled references (smc; every reference must have the frame's size), MV parsing and
+ *  clamping.  Intra blocks of inter frames are left untouched here: ffhip_vp9_intra_frames_dev() reconstructs them afterwards.
  */
 typedef struct FFHipVp9InterPred {  /* one mc_luma_dir / mc_chroma_dir call (with its compound second half), 20 bytes */
     uint16_t x, y;                  /* its top-left sample in its plane */
@@ -2074,6 +2074,77 @@ int ffhip_vp9_inter_tu_record_size(void);
  *  emulates.  Writes up to 8 records to out; returns their count, FFHIP_EINVAL for bad arguments. */
 int ffhip_vp9_inter_block_preds(FFHipVp9InterPred *out, int bs, int row, int col, const int16_t mv[4][2][2], int comp, const uint8_t ref[2],
                                 int filter, int ss_h, int ss_v);
+
+/**
+ * VP9 intra reconstruction of whole frames in one launch: intra_recon() with check_intra_mode() (libavcodec/vp9recon.c) for every
+ * intra block of up to 16 frames.  An intra block's edges are the reconstructed samples of earlier blocks, so a decoder records each
+ * intra_pred / itxfm_add pair instead of running it; one launch then reconstructs the frames' intra blocks in decoding order, after
+ * ffhip_vp9_inter_frames_dev() and before ffhip_vp9_loopfilter_frames_dev() on the same stream.
+ *
+ *  Semantics, byte for byte those of the reference at bit_depth (vp9dsp_template.c; the oracle's ffo_vp9_intra_pred_bd /
+ *  ffo_vp9_itxfm_add_bd), stated in plane coordinates.  The decoded area of a plane is dw x dh = (cols * 8) >> hs by (rows * 8) >> vs
+ *  (cols = (width + 7) >> 3, rows = (height + 7) >> 3); N = 4 << tx (4 for tx 4); base = 128 << (bit_depth - 8); P(u, v) is the plane
+ *  as reconstructed so far (earlier records final, inter samples as they stand at launch, nothing loop-filtered):
+ *  - availability: have_top = y > 0; have_left = x > the start of the tile column holding x, (min((i * sb_w) >> log2_tile_cols, sb_w)
+ *    * 64) >> hs for tile column i (set_tile_offset, vp9.c); have_right from the record;
+ *  - the coded mode becomes mode_conv[mode][have_left][have_top] (check_intra_mode), which selects the predictor; the coded mode
+ *    selects txtp (the caller's ff_vp9_intra_txfm_type[mode]);
+ *  - top[j], j < N: P(min(x + j, dw - 1), y - 1), or base - 1 without top.  4x4 DIAG_DOWN_LEFT / VERT_LEFT also read top[4..7]:
+ *    P(x + j, y - 1) when have_top, have_right and x + 8 <= dw, else all four are top[3] (the reference's rule, kept);
+ *  - the corner: P(x - 1, y - 1) with top and left, base + 1 with top but no left, base - 1 without top;
+ *  - left[i], i < N rows down: P(x - 1, min(y + i, dh - 1)), or base + 1 without left;
+ *  - the residual: itxfm_add[tx][txtp] when the residual flag is set (the dc-only shortcut of DCT_DCT when dc_only); coefficients are
+ *    read, never zeroed;
+ *  - what is written: the record's samples inside the decoded area.  Inter samples, the stride padding and anything past dw / dh keep
+ *    their bytes (no read above leaves the decoded area);
+ *  - a malformed record writes nothing and reads nothing outside its planes; later records run as if it were absent: tx > 4, mode >
+ *    9, txtp > 3, an unknown flag bit, dc_only without residual, (x, y) not a multiple of N, the N x N square outside the superblock
+ *    it is listed under, its origin outside the decoded area, or a 4x4 record with have_right whose top-right samples (x + 4 .. x + 7)
+ *    leave that superblock (intra_recon never sets it there).
+ *  Trusted (the ABI carries no lengths to check them against): the superblock start tables, each record's coeff_offset range, the
+ *  decoding order of the records within a superblock, and that the records of one plane of a superblock are disjoint.
+ */
+typedef struct FFHipVp9IntraRec {    /* one iteration of intra_recon's loops: intra_pred[tx][mode], then itxfm_add; 12 bytes */
+    uint16_t x, y;                   /* top-left sample in its plane */
+    int32_t  coeff_offset;           /* coefficients (int16 at 8 bits, int32 above) into the plane's coeffs; read only with the residual flag */
+    uint8_t  tx;                     /* 0..3: 4x4 .. 32x32; 4: 4x4 prediction and the lossless WHT (as FFHipVp9InterTU) */
+    uint8_t  mode;                   /* the CODED enum IntraPredMode 0..9 (b->mode[..] / b->uvmode), before check_intra_mode converts it */
+    uint8_t  txtp;                   /* ff_vp9_intra_txfm_type[mode] for luma, DCT_DCT for chroma; ignored for 32x32 and the WHT */
+    uint8_t  flags;                  /* FFHIP_VP9_INTRA_* */
+} FFHipVp9IntraRec;
+#define FFHIP_VP9_INTRA_RESIDUAL   1 /* !skip && eob != 0: itxfm_add follows the prediction */
+#define FFHIP_VP9_INTRA_DC_ONLY    2 /* eob == 1 (with the residual flag only) */
+#define FFHIP_VP9_INTRA_HAVE_RIGHT 4 /* x < w4 - 1 in intra_recon's loop (read by 4x4 records only) */
+typedef struct FFHipVp9IntraPlane {  /* device pointers */
+    uint8_t *base;                   /* the plane's top-left sample */
+    ptrdiff_t stride;                /* bytes, >= the decoded width in bytes */
+    const FFHipVp9IntraRec *recs;    /* sorted by raster superblock (64 x 64 luma) address; within a superblock in decoding order */
+    const int32_t *rec_sb_start;     /* sb_w * sb_h + 1 entries: the records of raster superblock a are recs[rec_sb_start[a] .. [a + 1]) */
+    const void *coeffs;              /* int16 (8 bits) or int32 (10 / 12 bits) coefficients */
+} FFHipVp9IntraPlane;
+typedef struct FFHipVp9IntraPic {
+    FFHipVp9IntraPlane plane[3];     /* Y, Cb, Cr */
+    int32_t log2_tile_cols;          /* 0..6: the frame header's tile columns (they decide have_left) */
+    int32_t pad;
+} FFHipVp9IntraPic;
+/** npics frames of one geometry: width x height luma samples (1..65535), bit_depth 8, 10 or 12 (uint16_t samples above 8), chroma
+ *  subsampling (ss_h, ss_v) in {0, 1}^2.  sb_w = (cols + 7) >> 3, sb_h = (rows + 7) >> 3.  Every plane needs non-NULL pointers, base
+ *  and stride multiples of 4 samples and a stride of at least the decoded width.  Asynchronous on `stream`; a lost hand-off is
+ *  reported by ffhip_stream_synchronize.
+ *  FFHIP_EINVAL (before any device check) for another depth or subsampling, a size outside 1..65535, npics <= 0 or a NULL array, NULL
+ *  or misaligned planes, a stride below the decoded width, log2_tile_cols outside 0..6, or two planes of the call that overlap;
+ *  FFHIP_ENOSYS without a device. */
+int ffhip_vp9_intra_frames_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics,
+                               const FFHipVp9IntraPic *pics /* host array */, void *stream);
+/** sizeof(FFHipVp9IntraRec), for bindings that mirror the record (no device needed). */
+int ffhip_vp9_intra_record_size(void);
+/** The records of one decoded block in one plane, in intra_recon's order (device-free, like ffhip_vp9_inter_block_preds): plane 0 takes
+ *  tx = b->tx and mode = b->mode; planes 1 and 2 take tx = b->uvtx and mode[0] = b->uvmode.  bs = enum BlockSize 0..12, row / col in
+ *  8-sample units, skip = b->skip, eob[n] the value intra_recon reads for transform n (td->eob / td->uveob[p]), lossless = the frame
+ *  header's; cols / rows as above.  coeff_offset = 16 * n (the caller adds the block's base offset).  Writes up to 256 records to out;
+ *  returns their count, FFHIP_EINVAL for bad arguments. */
+int ffhip_vp9_intra_block_records(FFHipVp9IntraRec *out /* up to 256 */, int plane, int bs, int tx, int row, int col, const uint8_t mode[4],
+                                  int skip, const uint16_t *eob, int lossless, int cols, int rows, int ss_h, int ss_v);
 
 /**
  * vp9dsp above 8 bits (profiles 2 / 3): the batch faces above at the bpp ff_vp9dsp_init(dsp, bpp, bitexact) instantiates its template
