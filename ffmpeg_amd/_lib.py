@@ -269,6 +269,8 @@ def lib():
         "ffhip_vp9_inter_pred_record_size": (C.c_int, []),
         "ffhip_vp9_inter_tu_record_size": (C.c_int, []),
         "ffhip_vp9_inter_block_preds": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
+        "ffhip_vp9_inter_frames_scaled_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_vp9_inter_block_preds_scaled": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
         "ffhip_vp9_intra_frames_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_vp9_intra_record_size": (C.c_int, []),
         "ffhip_vp9_intra_block_records": (C.c_int, [vp] + [C.c_int] * 5 + [vp, C.c_int, vp] + [C.c_int] * 5),

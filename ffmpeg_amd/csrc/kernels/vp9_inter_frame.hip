@@ -17,6 +17,14 @@
  * emulated_edge_mc gives mc_luma_unscaled / mc_chroma_unscaled, so MVs may point anywhere.  A lane computes one sample at a time;
  * block sizes are powers of two, so a block's samples are spread over the wave by shifts.  Records are checked before they are used
  * (include/ffhip.h lists what is malformed); a malformed record or TU is skipped.
+ *
+ * ffhip_vp9_inter_frames_scaled_dev() runs the SCALED instantiation when a launch has a reference of another size: each reference
+ * carries its own real size, scale and step (staged behind the frames in the same progress-pool slot), and a record of the SCALED
+ * template (FFHIP_VP9_PRED_SCALED) from such a reference takes mc_luma_scaled / mc_chroma_scaled: the MV clipped to its box, the
+ * scaled origin and phase, then smc's 2-D form (output x around (mx + x dx) >> 4 with the taps of (mx + x dx) & 15, phase 0 a copy)
+ * through the same clamped gather and tap code.  smc's horizontal pass needs up to 134 rows at 2x down; it runs in strips of 32
+ * output rows, whose rows -3 .. ((15 + 31 dy) >> 4) + 4 fit the TROWS temporaries at any step up to 32, so both instantiations have
+ * the same LDS.  Launches without such a reference run the unscaled instantiation, today's kernel.
  */
 #include <stddef.h>
 #include <type_traits>
@@ -31,6 +39,14 @@ static_assert(sizeof(FFHipVp9InterPic) % 8 == 0, "FFHipVp9InterPic is staged as 
 
 #define VIF_PICS 16 /* frames per launch: their FFHipVp9InterPic structs travel in one progress-pool slot */
 static_assert(VIF_PICS * sizeof(FFHipVp9InterPic) <= FFHIP_PROGRESS_SLOT_INTS * sizeof(int), "a launch's frames fit one slot");
+
+/* the references of one frame of a scaled launch: luma real size, scale (<< 14) and step per reference, 0 scale for an unscaled one */
+struct VifRefScale {
+    int32_t rw[3], rh[3];
+    int32_t scale[3][2], step[3][2];
+};
+static_assert(VIF_PICS * (sizeof(FFHipVp9InterPic) + sizeof(VifRefScale)) <= FFHIP_PROGRESS_SLOT_INTS * sizeof(int),
+              "a scaled launch's frames and reference scales fit one slot");
 
 namespace {
 /* ff_vp9_subpel_filters (libavcodec/vp9dsp.c): [filter 0 smooth / 1 regular / 2 sharp][m in sixteenths][tap]; m = 0 is never used */
@@ -115,10 +131,43 @@ __device__ __forceinline__ void vif_predict(uint16_t *tile, PIX *tmp, const VifS
     vif_wave_sync(); /* tmp is reused by the next pass; an avg pass reads what this lane's put wrote */
 }
 
+constexpr int SROWS = 32; /* output rows per strip of the scaled 2-D form */
+static_assert(((15 + (SROWS - 1) * 32) >> 4) + 8 <= TROWS, "a strip's horizontal pass fits the temporaries at any step up to 32");
+
+/* smc (vp9dsp_template.c, the oracle's ffo_vp9_smc_bd), put or avg of a w x h block at tile position (lx, ly) with steps dx, dy: the
+ * horizontal pass over the rows a strip of output rows reads, into pixel temporaries, then the vertical pass.  Phase 0 is a copy */
+template <typename PIX, bool AVG>
+__device__ __forceinline__ void vif_predict_scaled(uint16_t *tile, PIX *tmp, const VifSrc &s, int dx, int dy, int lx, int ly, int lgw, int h,
+                                                   int filter, int maxv, int lane)
+{
+    const int w = 1 << lgw, before = filter == 3 ? 0 : 3, extra = filter == 3 ? 2 : 8;
+    auto tap = [&](int m, auto at) { return m ? vif_tap(filter, m, maxv, at) : at(0); };
+    for (int y0 = 0; y0 < h; y0 += SROWS) {
+        const int sh = min(h - y0, SROWS), p0 = s.my + y0 * dy, m0 = p0 & 15;
+        const int ry = s.yi + (p0 >> 4) - before, rows = ((m0 + (sh - 1) * dy) >> 4) + extra;
+        for (int i = lane; i < rows << lgw; i += 64) {
+            const int r = i >> lgw, x = i & (w - 1), pos = s.mx + x * dx, xx = s.xi + (pos >> 4);
+            tmp[r * TILE + x] = (PIX)tap(pos & 15, [&](int k) { return vif_ref<PIX>(s, xx + k, ry + r); });
+        }
+        vif_wave_sync();
+        for (int i = lane; i < sh << lgw; i += 64) {
+            const int y = i >> lgw, x = i & (w - 1), pos = m0 + y * dy;
+            const PIX *t = tmp + ((pos >> 4) + before) * TILE + x;
+            const int v = tap(pos & 15, [&](int k) { return (int)t[k * TILE]; });
+            uint16_t &d = tile[(ly + y0 + y) * TILE + lx + x];
+            d = (uint16_t)(AVG ? (d + v + 1) >> 1 : v);
+        }
+        vif_wave_sync(); /* the next strip or pass reuses tmp */
+    }
+}
+
+/* scale_mv (vp9recon.c): ((int64) n * scale) >> 14, flooring */
+__device__ __forceinline__ int vif_scale_mv(int n, int scale) { return (int)(((long long)n * scale) >> 14); }
+
 } // namespace
 
-/* grid: (sb_w * sb_h, frames); 4 waves per workgroup */
-template <typename PIX>
+/* grid: (sb_w * sb_h, frames); 4 waves per workgroup.  SCALED: the frames' VifRefScale tables follow pics[0 .. VIF_PICS) */
+template <typename PIX, bool SCALED>
 __global__ __launch_bounds__(256) void k_vp9_inter_frame(const FFHipVp9InterPic *__restrict__ pics, int ss_h, int ss_v, int width, int height,
                                                          int sb_w, int bd)
 {
@@ -136,6 +185,7 @@ __global__ __launch_bounds__(256) void k_vp9_inter_frame(const FFHipVp9InterPic 
         return; /* no inter samples in this superblock */
     const int nrefs = P.nrefs, maxv = (1 << bd) - 1;
     const int dw = ((width + 7) >> 3) << 3, dh = ((height + 7) >> 3) << 3; /* the decoded area, luma */
+    const VifRefScale *const RS = SCALED ? reinterpret_cast<const VifRefScale *>(pics + VIF_PICS) + blockIdx.y : nullptr;
     PIX *const tmp = tmp_all[wave];
 
     for (int p = 0; p < 3; p++) {
@@ -150,12 +200,17 @@ __global__ __launch_bounds__(256) void k_vp9_inter_frame(const FFHipVp9InterPic 
         for (int k = k0 + wave; k < k1; k += 4) {
             const FFHipVp9InterPred R = P.preds[k];
             const int fl = R.flags, w = R.w, h = R.h, filter = R.filter, x = R.x, y = R.y;
-            if ((fl & ~3) || ((fl >> 1) & 1) != chroma)
+            if ((fl & (SCALED ? ~7 : ~3)) || ((fl >> 1) & 1) != chroma)
                 continue;
             const bool comp = fl & 1;
             const bool ok = w >= 4 && w <= 64 && !(w & (w - 1)) && h >= 4 && h <= 64 && !(h & (h - 1)) && filter <= 3 && R.ref[0] < nrefs &&
                             (!comp || R.ref[1] < nrefs) && x >= x0 && x + w <= x0 + Cw && y >= y0 && y + h <= y0 + Ch;
             if (!ok)
+                continue;
+            /* the clip box of a SCALED-template call: (px, py, pw, ph) */
+            const bool sc_rec = SCALED && (fl & FFHIP_VP9_PRED_SCALED);
+            const int px = R.box[0] & 15, py = R.box[0] >> 4, lpw = R.box[1] & 15, lph = R.box[1] >> 4;
+            if (sc_rec && (lpw < 2 || lpw > 6 || lph < 2 || lph > 6 || px + w > (1 << lpw) || py + h > (1 << lph)))
                 continue;
             const int lgw = __builtin_ctz(w), lx = x - x0, ly = y - y0;
             for (int l = 0; l <= (int)comp; l++) {
@@ -166,6 +221,39 @@ __global__ __launch_bounds__(256) void k_vp9_inter_frame(const FFHipVp9InterPic 
                 s.stride = Rf.stride[p];
                 s.rw = rw;
                 s.rh = rh;
+                if (SCALED) {
+                    const int ri = l ? R.ref[1] : R.ref[0];
+                    s.rw = (RS->rw[ri] + hs) >> hs; /* this reference's real size */
+                    s.rh = (RS->rh[ri] + vs) >> vs;
+                    const int scx = RS->scale[ri][0], scy = RS->scale[ri][1];
+                    if (sc_rec && scx) { /* mc_luma_scaled / mc_chroma_scaled */
+                        int mx, my;
+                        if (hs) { /* libvpx's rounding (webm issue 820) */
+                            const int mv = min(max(mvx, -(x + (1 << lpw) - px + 4) * 16), ((width + 7) >> 3) * 64 - (x - px - 3) * 16);
+                            mx = vif_scale_mv(mv, scx) + (vif_scale_mv(x * 16, scx) & ~15) + (vif_scale_mv(x * 32, scx) & 15);
+                        } else {
+                            const int mv = min(max(mvx, -(x + (1 << lpw) - px + 4) * 8), ((width + 7) >> 3) * 64 - (x - px - 3) * 8);
+                            mx = vif_scale_mv(mv * 2, scx) + vif_scale_mv(x * 16, scx);
+                        }
+                        if (vs) {
+                            const int mv = min(max(mvy, -(y + (1 << lph) - py + 4) * 16), ((height + 7) >> 3) * 64 - (y - py - 3) * 16);
+                            my = vif_scale_mv(mv, scy) + (vif_scale_mv(y * 16, scy) & ~15) + (vif_scale_mv(y * 32, scy) & 15);
+                        } else {
+                            const int mv = min(max(mvy, -(y + (1 << lph) - py + 4) * 8), ((height + 7) >> 3) * 64 - (y - py - 3) * 8);
+                            my = vif_scale_mv(mv * 2, scy) + vif_scale_mv(y * 16, scy);
+                        }
+                        s.xi = mx >> 4;
+                        s.yi = my >> 4;
+                        s.mx = mx & 15;
+                        s.my = my & 15;
+                        const int dx = RS->step[ri][0], dy = RS->step[ri][1];
+                        if (l)
+                            vif_predict_scaled<PIX, true>(tile, tmp, s, dx, dy, lx, ly, lgw, h, filter, maxv, lane);
+                        else
+                            vif_predict_scaled<PIX, false>(tile, tmp, s, dx, dy, lx, ly, lgw, h, filter, maxv, lane);
+                        continue;
+                    }
+                }
                 if (!chroma) {
                     s.xi = x + (mvx >> 3);
                     s.yi = y + (mvy >> 3);
@@ -257,16 +345,80 @@ int ffhip_launch_vp9_inter_frames(int bd, int ss_h, int ss_v, int width, int hei
         hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipVp9InterPic), hipMemcpyHostToDevice, stream);
         if (e == hipSuccess) {
             if (bd > 8)
-                hipLaunchKernelGGL(k_vp9_inter_frame<uint16_t>, dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
+                hipLaunchKernelGGL((k_vp9_inter_frame<uint16_t, false>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
                                    sb_w, bd);
             else
-                hipLaunchKernelGGL(k_vp9_inter_frame<uint8_t>, dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
+                hipLaunchKernelGGL((k_vp9_inter_frame<uint8_t, false>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
                                    sb_w, 8);
             e = hipGetLastError();
         }
         const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
         if (e != hipSuccess) {
             ffhip_set_error("ffhip_vp9_inter_frames_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+            return FFHIP_EIO;
+        }
+        if (r2 < 0)
+            return r2;
+    }
+    return 0;
+}
+
+
+int ffhip_launch_vp9_inter_frames_scaled(int bd, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPicScaled *pics,
+                                         hipStream_t stream)
+{
+    const int cols = (width + 7) >> 3, rows = (height + 7) >> 3, sb_w = (cols + 7) >> 3, sb_h = (rows + 7) >> 3;
+    struct Staged { /* one slot's image: the frames, then their reference scales */
+        FFHipVp9InterPic pic[VIF_PICS];
+        VifRefScale rs[VIF_PICS];
+    };
+    static_assert(offsetof(Staged, rs) == VIF_PICS * sizeof(FFHipVp9InterPic), "the kernel finds the scales behind VIF_PICS frames");
+    for (int p0 = 0; p0 < npics; p0 += VIF_PICS) {
+        const int n = npics - p0 < VIF_PICS ? npics - p0 : VIF_PICS;
+        Staged st = {};
+        bool scaled = false;
+        for (int i = 0; i < n; i++) {
+            const FFHipVp9InterPicScaled &S = pics[p0 + i];
+            st.pic[i] = S.pic;
+            for (int r = 0; r < S.pic.nrefs; r++) {
+                VifRefScale &R = st.rs[i];
+                R.rw[r] = S.ref_w[r];
+                R.rh[r] = S.ref_h[r];
+                if (S.ref_w[r] != width || S.ref_h[r] != height) { /* vp9.c: mvscale / mvstep */
+                    R.scale[r][0] = (S.ref_w[r] << 14) / width;
+                    R.scale[r][1] = (S.ref_h[r] << 14) / height;
+                    R.step[r][0] = (16 * R.scale[r][0]) >> 14;
+                    R.step[r][1] = (16 * R.scale[r][1]) >> 14;
+                    scaled = true;
+                }
+            }
+        }
+        if (!scaled) { /* no reference of another size: today's kernel on the frames */
+            const int r = ffhip_launch_vp9_inter_frames(bd, ss_h, ss_v, width, height, n, st.pic, stream);
+            if (r < 0)
+                return r;
+            continue;
+        }
+        /* as ffhip_launch_vp9_inter_frames: the slot is not handed out again before the launch behind it has finished, and the copy
+         * from pageable memory is staged by the time hipMemcpyAsync returns */
+        FFHipProgressSlot ps;
+        const int r = ffhip_progress_acquire(0, stream, &ps);
+        if (r < 0)
+            return r;
+        FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
+        hipError_t e = hipMemcpyAsync(dpics, &st, sizeof(st), hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) {
+            if (bd > 8)
+                hipLaunchKernelGGL((k_vp9_inter_frame<uint16_t, true>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width,
+                                   height, sb_w, bd);
+            else
+                hipLaunchKernelGGL((k_vp9_inter_frame<uint8_t, true>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width,
+                                   height, sb_w, 8);
+            e = hipGetLastError();
+        }
+        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
+        if (e != hipSuccess) {
+            ffhip_set_error("ffhip_vp9_inter_frames_scaled_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
             return FFHIP_EIO;
         }
         if (r2 < 0)

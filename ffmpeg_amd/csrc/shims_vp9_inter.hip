@@ -2,7 +2,8 @@
  * shims_vp9_inter.hip — ffhip_vp9_inter_frames_dev(): validates what the host can see of a frame set (geometry, planes, references,
  * reference / destination overlap) and launches the inter reconstruction (kernels/vp9_inter_frame.hip) on the caller's stream.  The
  * records themselves are device data and are checked by the kernel.  Also ffhip_vp9_inter_block_preds(), the device-free expansion
- * of one decoded block into its prediction records (libavcodec/vp9_mc_template.h).
+ * of one decoded block into its prediction records (libavcodec/vp9_mc_template.h).  ffhip_vp9_inter_frames_scaled_dev() and
+ * ffhip_vp9_inter_block_preds_scaled(): the same for frames with references of another size (the SCALED template).
  */
 #include <algorithm>
 #include <stdint.h>
@@ -32,57 +33,57 @@ struct Mv {
 Mv mv_of(const int16_t mv[4][2][2], int sub, int r) { return { mv[sub][r][0], mv[sub][r][1] }; }
 Mv div2(Mv a, Mv b) { return { rounded_div(a.x + b.x, 2), rounded_div(a.y + b.y, 2) }; }
 Mv div4(Mv a, Mv b, Mv c, Mv d) { return { rounded_div(a.x + b.x + c.x + d.x, 4), rounded_div(a.y + b.y + c.y + d.y, 4) }; }
-} // namespace
 
-extern "C" int ffhip_vp9_inter_frames_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPic *pics,
-                                          void *stream)
+
+/* what the host can see of a frame set: `fn` names the face in the messages, pics[i] is frame i's FFHipVp9InterPic and
+ * ref_size(i, r, p, &w, &h) gives the real size of plane p of frame i's reference r, samples */
+template <typename PICS, typename REFSIZE>
+int check_frames(const char *fn, int bit_depth, int ss_h, int ss_v, int width, int height, int npics, PICS pics, REFSIZE ref_size)
 {
     if ((bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (ss_h & ~1) || (ss_v & ~1)) {
-        ffhip_set_error("ffhip_vp9_inter_frames_dev: bit depth %d (8, 10 or 12), subsampling %d, %d (0 or 1 each)", bit_depth, ss_h, ss_v);
+        ffhip_set_error("%s: bit depth %d (8, 10 or 12), subsampling %d, %d (0 or 1 each)", fn, bit_depth, ss_h, ss_v);
         return FFHIP_EINVAL;
     }
     if (width <= 0 || height <= 0 || width > 65535 || height > 65535) {
-        ffhip_set_error("ffhip_vp9_inter_frames_dev: frame size %d x %d (1..65535)", width, height);
+        ffhip_set_error("%s: frame size %d x %d (1..65535)", fn, width, height);
         return FFHIP_EINVAL;
     }
     if (npics <= 0 || !pics) {
-        ffhip_set_error("ffhip_vp9_inter_frames_dev: npics = %d, or a NULL frame array", npics);
+        ffhip_set_error("%s: npics = %d, or a NULL frame array", fn, npics);
         return FFHIP_EINVAL;
     }
     const int ps = bit_depth > 8 ? 2 : 1;
     const unsigned amask = 4u * ps - 1; /* four samples per access */
     const int cols = (width + 7) >> 3, rows = (height + 7) >> 3;
-    int dw[3], dh[3], rw[3], rh[3]; /* decoded area and real size per plane, samples */
+    int dw[3], dh[3]; /* decoded area per plane, samples */
     for (int p = 0; p < 3; p++) {
-        const int hs = p ? ss_h : 0, vs = p ? ss_v : 0;
-        dw[p] = (cols * 8) >> hs;
-        dh[p] = (rows * 8) >> vs;
-        rw[p] = (width + hs) >> hs;
-        rh[p] = (height + vs) >> vs;
+        dw[p] = (cols * 8) >> (p ? ss_h : 0);
+        dh[p] = (rows * 8) >> (p ? ss_v : 0);
     }
     for (int i = 0; i < npics; i++) {
         const FFHipVp9InterPic &P = pics[i];
         if (!P.preds || !P.pred_sb_start || P.nrefs < 1 || P.nrefs > 3) {
-            ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d: NULL prediction tables or nrefs = %d (1..3)", i, P.nrefs);
+            ffhip_set_error("%s: frame %d: NULL prediction tables or nrefs = %d (1..3)", fn, i, P.nrefs);
             return FFHIP_EINVAL;
         }
         for (int p = 0; p < 3; p++) {
             const FFHipVp9InterPlane &D = P.plane[p];
             if (!D.base || !D.tus || !D.tu_sb_start || !D.coeffs) {
-                ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d plane %d: a NULL pointer", i, p);
+                ffhip_set_error("%s: frame %d plane %d: a NULL pointer", fn, i, p);
                 return FFHIP_EINVAL;
             }
             if ((((uintptr_t)D.base | (size_t)D.stride) & amask) || D.stride < (ptrdiff_t)dw[p] * ps) {
-                ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d plane %d: base and stride must be %u-byte aligned, the stride at least "
-                                "the decoded width", i, p, amask + 1);
+                ffhip_set_error("%s: frame %d plane %d: base and stride must be %u-byte aligned, the stride at least the decoded width", fn,
+                                i, p, amask + 1);
                 return FFHIP_EINVAL;
             }
             for (int r = 0; r < P.nrefs; r++) {
                 const uint8_t *b = P.ref[r].base[p];
                 const ptrdiff_t s = P.ref[r].stride[p];
-                if (!b || (((uintptr_t)b | (size_t)s) & (ps - 1)) || s < (ptrdiff_t)rw[p] * ps) {
-                    ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d reference %d plane %d: NULL, misaligned or a stride below the "
-                                    "width", i, r, p);
+                int rw, rh;
+                ref_size(i, r, p, &rw, &rh);
+                if (!b || (((uintptr_t)b | (size_t)s) & (ps - 1)) || s < (ptrdiff_t)rw * ps) {
+                    ffhip_set_error("%s: frame %d reference %d plane %d: NULL, misaligned or a stride below the width", fn, i, r, p);
                     return FFHIP_EINVAL;
                 }
             }
@@ -102,17 +103,65 @@ extern "C" int ffhip_vp9_inter_frames_dev(int bit_depth, int ss_h, int ss_v, int
     for (int j = 0; j < npics; j++)
         for (int r = 0; r < pics[j].nrefs; r++)
             for (int q = 0; q < 3; q++) {
-                const Span s = plane_span(pics[j].ref[r].base[q], pics[j].ref[r].stride[q], rw[q] * ps, rh[q]);
+                int rw, rh;
+                ref_size(j, r, q, &rw, &rh);
+                const Span s = plane_span(pics[j].ref[r].base[q], pics[j].ref[r].stride[q], rw * ps, rh);
                 const size_t n = (size_t)(std::lower_bound(dst.begin(), dst.end(), s.hi, [](const Span &x, uintptr_t v) { return x.lo < v; }) -
                                           dst.begin());
                 if (n && hi_max[n - 1] > s.lo) {
-                    ffhip_set_error("ffhip_vp9_inter_frames_dev: frame %d reference %d plane %d overlaps a plane the call writes", j, r, q);
+                    ffhip_set_error("%s: frame %d reference %d plane %d overlaps a plane the call writes", fn, j, r, q);
                     return FFHIP_EINVAL;
                 }
             }
+    return 0;
+}
+} // namespace
+
+extern "C" int ffhip_vp9_inter_frames_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPic *pics,
+                                          void *stream)
+{
+    const int r = check_frames("ffhip_vp9_inter_frames_dev", bit_depth, ss_h, ss_v, width, height, npics, pics, [&](int, int, int p, int *w, int *h) {
+        *w = (width + (p ? ss_h : 0)) >> (p ? ss_h : 0);
+        *h = (height + (p ? ss_v : 0)) >> (p ? ss_v : 0);
+    });
+    if (r < 0)
+        return r;
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_vp9_inter_frames(bit_depth, ss_h, ss_v, width, height, npics, pics, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_vp9_inter_frames_scaled_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics,
+                                                 const FFHipVp9InterPicScaled *pics, void *stream)
+{
+    static const char fn[] = "ffhip_vp9_inter_frames_scaled_dev";
+    if (npics > 0 && pics && width > 0 && height > 0)
+        for (int i = 0; i < npics; i++)
+            for (int r = 0; r < pics[i].pic.nrefs && r < 3; r++) {
+                const int rw = pics[i].ref_w[r], rh = pics[i].ref_h[r];
+                const bool same = rw == width && rh == height; /* vp9.c: unscaled; otherwise the 2x / 16x limits */
+                if (rw <= 0 || rh <= 0 || rw > 65535 || rh > 65535 ||
+                    (!same && ((int64_t)2 * width < rw || (int64_t)2 * height < rh || width > (int64_t)16 * rw || height > (int64_t)16 * rh))) {
+                    ffhip_set_error("%s: frame %d reference %d: size %d x %d for a %d x %d frame (1..65535, at most 2x larger, 16x smaller)",
+                                    fn, i, r, rw, rh, width, height);
+                    return FFHIP_EINVAL;
+                }
+            }
+    /* the frames as FFHipVp9InterPic for the common checks: pics[i].pic */
+    struct PicView {
+        const FFHipVp9InterPicScaled *s;
+        const FFHipVp9InterPic &operator[](int i) const { return s[i].pic; }
+        explicit operator bool() const { return s != nullptr; }
+    };
+    const int r = check_frames(fn, bit_depth, ss_h, ss_v, width, height, npics, PicView{ pics }, [&](int i, int ref, int p, int *w, int *h) {
+        *w = (pics[i].ref_w[ref] + (p ? ss_h : 0)) >> (p ? ss_h : 0);
+        *h = (pics[i].ref_h[ref] + (p ? ss_v : 0)) >> (p ? ss_v : 0);
+    });
+    if (r < 0)
+        return r;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_vp9_inter_frames_scaled(bit_depth, ss_h, ss_v, width, height, npics, pics, (hipStream_t)stream);
 }
 
 extern "C" int ffhip_vp9_inter_block_preds(FFHipVp9InterPred *out, int bs, int row, int col, const int16_t mv[4][2][2], int comp,
@@ -196,6 +245,69 @@ extern "C" int ffhip_vp9_inter_block_preds(FFHipVp9InterPred *out, int bs, int r
             emit(true, lx, ly + 4, 4, 4, sub(2));
             emit(true, lx + 4, ly + 4, 4, 4, sub(3));
         }
+    }
+    return n;
+}
+
+extern "C" int ffhip_vp9_inter_block_preds_scaled(FFHipVp9InterPred *out, int bs, int row, int col, const int16_t mv[4][2][2], int comp,
+                                                  const uint8_t ref[2], int filter, int ss_h, int ss_v)
+{
+    if (!out || !mv || !ref || bs < 0 || bs > 12 || row < 0 || row > 8191 || col < 0 || col > 8191 || filter < 0 || filter > 3 ||
+        (ss_h & ~1) || (ss_v & ~1)) {
+        ffhip_set_error("ffhip_vp9_inter_block_preds_scaled: block size %d (0..12), row %d / col %d (0..8191), filter %d (0..3), "
+                        "subsampling %d, %d", bs, row, col, filter, ss_h, ss_v);
+        return FFHIP_EINVAL;
+    }
+    static const uint8_t lw_tab[10] = { 6, 6, 5, 5, 5, 4, 4, 4, 3, 3 }; /* log2 of ff_vp9_bwh_tab[0] in samples, BS_64x64 .. BS_8x8 */
+    static const uint8_t lh_tab[10] = { 6, 5, 6, 5, 4, 5, 4, 3, 4, 3 };
+    int n = 0;
+    const int nr = comp ? 2 : 1;
+    /* one call of the SCALED template: (x, y, w, h) in its plane, its clip box (px, py, 1 << lpw, 1 << lph), the MV of each reference */
+    auto emit = [&](bool chroma, int x, int y, int lw, int lh, int px, int py, int lpw, int lph, auto pick) {
+        FFHipVp9InterPred &R = out[n++];
+        R = FFHipVp9InterPred();
+        R.x = (uint16_t)x;
+        R.y = (uint16_t)y;
+        R.w = (uint8_t)(1 << lw);
+        R.h = (uint8_t)(1 << lh);
+        R.filter = (uint8_t)filter;
+        R.flags = (uint8_t)((comp ? 1 : 0) | (chroma ? 2 : 0) | FFHIP_VP9_PRED_SCALED);
+        R.box[0] = (uint8_t)(px | py << 4);
+        R.box[1] = (uint8_t)(lpw | lph << 4);
+        for (int r = 0; r < nr; r++) {
+            const Mv m = pick(r);
+            R.ref[r] = ref[r];
+            R.mv[r][0] = (int16_t)m.x;
+            R.mv[r][1] = (int16_t)m.y;
+        }
+    };
+    const int ly = row << 3, lx = col << 3, cy = row << (3 - ss_v), cx = col << (3 - ss_h);
+    auto sub = [&](int s) { return [&, s](int r) { return mv_of(mv, s, r); }; };
+    auto d2 = [&](int a, int b) { return [&, a, b](int r) { return div2(mv_of(mv, a, r), mv_of(mv, b, r)); }; };
+    if (bs < 10) { /* at least 8 x 8: the whole block is the box */
+        const int lw = lw_tab[bs], lh = lh_tab[bs];
+        emit(false, lx, ly, lw, lh, 0, 0, lw, lh, sub(0));
+        emit(true, cx, cy, lw - ss_h, lh - ss_v, 0, 0, lw - ss_h, lh - ss_v, sub(0));
+        return n;
+    }
+    /* 8x4, 4x8 and 4x4: the 4x4 branch (vp9_mc_template.h keeps the 8x4 / 4x8 branches under SCALED == 0) */
+    emit(false, lx, ly, 2, 2, 0, 0, 3, 3, sub(0));
+    emit(false, lx + 4, ly, 2, 2, 4, 0, 3, 3, sub(1));
+    emit(false, lx, ly + 4, 2, 2, 0, 4, 3, 3, sub(2));
+    emit(false, lx + 4, ly + 4, 2, 2, 4, 4, 3, 3, sub(3));
+    if (ss_h && ss_v) {
+        emit(true, cx, cy, 2, 2, 0, 0, 2, 2, [&](int r) { return div4(mv_of(mv, 0, r), mv_of(mv, 1, r), mv_of(mv, 2, r), mv_of(mv, 3, r)); });
+    } else if (ss_v) { /* 4:4:0: the chroma of the 8 x 8 area is 8 x 4 */
+        emit(true, cx, cy, 2, 2, 0, 0, 3, 2, d2(0, 2));
+        emit(true, cx + 4, cy, 2, 2, 4, 0, 3, 2, d2(1, 3));
+    } else if (ss_h) { /* 4:2:2, 4 x 8, with libvpx's MV for the bottom block (webm issue 993) */
+        emit(true, cx, cy, 2, 2, 0, 0, 2, 3, d2(0, 1));
+        emit(true, cx, cy + 4, 2, 2, 0, 4, 2, 3, d2(1, 2));
+    } else {
+        emit(true, cx, cy, 2, 2, 0, 0, 3, 3, sub(0));
+        emit(true, cx + 4, cy, 2, 2, 4, 0, 3, 3, sub(1));
+        emit(true, cx, cy + 4, 2, 2, 0, 4, 3, 3, sub(2));
+        emit(true, cx + 4, cy + 4, 2, 2, 4, 4, 3, 3, sub(3));
     }
     return n;
 }

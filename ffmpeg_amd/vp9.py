@@ -214,13 +214,14 @@ def loopfilter_frame_ssc(y, u, v, stride_y, stride_uv, cols, rows, tables, ctabl
 
 
 #: FFHipVp9InterPred (include/ffhip.h): one mc_luma_dir / mc_chroma_dir call of ffhip_vp9_inter_frames_dev.  flags: bit 0 compound,
-#: bit 1 chroma; ref: indices into the frame's references; mv: [ref][x, y] in eighths of a luma sample.
+#: bit 1 chroma, bit 2 a call of the SCALED template (INTER_SCALED); ref: indices into the frame's references; box: the SCALED call's
+#: clip box, [px | py << 4, log2 pw | log2 ph << 4]; mv: [ref][x, y] in eighths of a luma sample.
 INTER_PRED_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("w", np.uint8), ("h", np.uint8), ("filter", np.uint8), ("flags", np.uint8),
-                             ("ref", np.uint8, 2), ("pad", np.uint8, 2), ("mv", np.int16, (2, 2))])
+                             ("ref", np.uint8, 2), ("box", np.uint8, 2), ("mv", np.int16, (2, 2))])
 #: FFHipVp9InterTU: one itxfm_add call of inter_recon; coeff_offset counts coefficients (int16 at 8 bits, int32 above).
 INTER_TU_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("coeff_offset", np.int32), ("tx", np.uint8), ("txtp", np.uint8),
                            ("dc_only", np.uint8), ("pad", np.uint8)])
-INTER_COMP, INTER_CHROMA = 1, 2
+INTER_COMP, INTER_CHROMA, INTER_SCALED = 1, 2, 4
 
 
 class InterPlane(C.Structure):
@@ -256,6 +257,45 @@ def inter_frames(pics, width, height, ss=(1, 1), stream=None, bit_depth=8):
                 arr[i].ref[r].stride[p] = stride
     return _lib.check(_lib.lib().ffhip_vp9_inter_frames_dev(bit_depth, ss[0], ss[1], width, height, len(pics), C.cast(arr, C.c_void_p),
                                                             _st(stream)), "ffhip_vp9_inter_frames_dev")
+
+
+class InterPicScaled(C.Structure):
+    """FFHipVp9InterPicScaled: a frame and the luma size of each of its references"""
+    _fields_ = [("pic", InterPic), ("ref_w", C.c_int32 * 3), ("ref_h", C.c_int32 * 3)]
+
+
+def _inter_pic(arr, planes, preds, pred_sb_start, refs):
+    for p, (plane, stride, tus, tu_sb_start, coeffs) in enumerate(planes):
+        arr.plane[p] = InterPlane(plane.data_ptr(), stride, tus.data_ptr(), tu_sb_start.data_ptr(), coeffs.data_ptr())
+    arr.preds, arr.pred_sb_start = preds.data_ptr(), pred_sb_start.data_ptr()
+    arr.nrefs = len(refs)
+    for r, ref in enumerate(refs):
+        for p, (plane, stride) in enumerate(ref):
+            arr.ref[r].base[p] = plane.data_ptr()
+            arr.ref[r].stride[p] = stride
+
+
+def inter_frames_scaled(pics, ref_sizes, width, height, ss=(1, 1), stream=None, bit_depth=8):
+    """ffhip_vp9_inter_frames_scaled_dev: inter_frames() with references of any valid size; ref_sizes[i] lists the luma (width,
+    height) of each reference of pics[i]"""
+    arr = (InterPicScaled * max(len(pics), 1))()
+    for i, (planes, preds, pred_sb_start, refs) in enumerate(pics):
+        _inter_pic(arr[i].pic, planes, preds, pred_sb_start, refs)
+        for r, (rw, rh) in enumerate(ref_sizes[i]):
+            arr[i].ref_w[r], arr[i].ref_h[r] = rw, rh
+    return _lib.check(_lib.lib().ffhip_vp9_inter_frames_scaled_dev(bit_depth, ss[0], ss[1], width, height, len(pics), C.cast(arr, C.c_void_p),
+                                                                   _st(stream)), "ffhip_vp9_inter_frames_scaled_dev")
+
+
+def inter_block_preds_scaled(bs, row, col, mv, comp, ref, filter, ss=(1, 1)):
+    """ffhip_vp9_inter_block_preds_scaled: inter_block_preds() for a block of the SCALED template (every record with INTER_SCALED and
+    its clip box)"""
+    out = np.zeros(8, INTER_PRED_DTYPE)
+    mvs = np.ascontiguousarray(np.asarray(mv, np.int16).reshape(4, 2, 2))
+    refs = np.ascontiguousarray(np.asarray(ref, np.uint8).reshape(2))
+    n = _lib.check(_lib.lib().ffhip_vp9_inter_block_preds_scaled(out.ctypes.data, bs, row, col, mvs.ctypes.data, int(comp), refs.ctypes.data,
+                                                                 filter, ss[0], ss[1]), "ffhip_vp9_inter_block_preds_scaled")
+    return out[:n]
 
 
 def inter_block_preds(bs, row, col, mv, comp, ref, filter, ss=(1, 1)):

@@ -2016,18 +2016,20 @@ int ffhip_vp9_loopfilter_frames_ssc_dev(int bit_depth, int ss_h, int ss_v, int n
  *  Trusted (the ABI carries no lengths to check them against): the superblock start tables and the records they index, each TU's
  *  coeff_offset range, and disjointness: the predictions of one plane of a superblock must be disjoint, as must its TUs; overlapping
  *  ones leave undefined values inside that superblock and nothing outside it.
- *  Out of scope (they stay on the C path): scaled references (smc; every reference must have the frame's size), MV parsing and
- *  clamping.  Intra blocks of inter frames are left untouched here: ffhip_vp9_intra_frames_dev() reconstructs them afterwards.
+ *  Every reference must have the frame's size here; references of another size take ffhip_vp9_inter_frames_scaled_dev() below.
+ *  Out of scope (they stay on the C path): MV parsing and clamping.  Intra blocks of inter frames are left untouched here: ffhip_vp9_intra_frames_dev() reconstructs them afterwards.
  */
 typedef struct FFHipVp9InterPred {  /* one mc_luma_dir / mc_chroma_dir call (with its compound second half), 20 bytes */
     uint16_t x, y;                  /* its top-left sample in its plane */
     uint8_t  w, h;                  /* 4, 8, 16, 32 or 64 */
     uint8_t  filter;                /* enum FilterMode 0..3 */
-    uint8_t  flags;                 /* bit 0 compound, bit 1 chroma (the record drives Cb and Cr) */
+    uint8_t  flags;                 /* bit 0 compound, bit 1 chroma (the record drives Cb and Cr), bit 2 FFHIP_VP9_PRED_SCALED */
     uint8_t  ref[2];                /* 0..2: indices into the frame's references (b->ref[]) */
-    uint8_t  pad[2];
+    uint8_t  box[2];                /* FFHIP_VP9_PRED_SCALED records: the call's clip box, [0] = px | py << 4, [1] = log2 pw | log2 ph << 4;
+                                       0 otherwise */
     int16_t  mv[2][2];              /* [ref][x, y]: the VP9mv passed to mc_*_dir, eighths of a luma sample */
 } FFHipVp9InterPred;
+#define FFHIP_VP9_PRED_SCALED 4     /* flags bit 2: a call of the SCALED template (ffhip_vp9_inter_frames_scaled_dev only) */
 typedef struct FFHipVp9InterTU {    /* one itxfm_add call of inter_recon, 12 bytes */
     uint16_t x, y;                  /* its top-left sample in its plane */
     int32_t  coeff_offset;          /* coefficients (int16 at 8 bits, int32 above) into the plane's coeffs: N * N, the decoder's layout */
@@ -2074,6 +2076,56 @@ int ffhip_vp9_inter_tu_record_size(void);
  *  emulates.  Writes up to 8 records to out; returns their count, FFHIP_EINVAL for bad arguments. */
 int ffhip_vp9_inter_block_preds(FFHipVp9InterPred *out, int bs, int row, int col, const int16_t mv[4][2][2], int comp, const uint8_t ref[2],
                                 int filter, int ss_h, int ss_v);
+
+/**
+ * VP9 inter reconstruction of whole frames from references of another size (reference scaling: libvpx resize_mode, WebRTC / SVC
+ * resolution changes, spatial layers): ffhip_vp9_inter_frames_dev() with the SCALED instantiation of vp9_mc_template.h and
+ * mc_luma_scaled / mc_chroma_scaled (libavcodec/vp9recon.c), the per-reference scale and step of the frame header (vp9.c).  Stated
+ * in plane coordinates; W x H is the frame's luma size, cols = (W + 7) >> 3, rows = (H + 7) >> 3, rw x rh a reference's luma size.
+ *  - per reference: of the frame's size when rw == W and rh == H (unscaled); otherwise scaled, valid when 2 W >= rw, 2 H >= rh,
+ *    W <= 16 rw and H <= 16 rh, with scale[0] = (rw << 14) / W, scale[1] = (rh << 14) / H, step[d] = (16 scale[d]) >> 14 (1..32)
+ *    and scale_mv(n, d) = ((int64) n * scale[d]) >> 14 (an arithmetic shift: it floors);
+ *  - a record without FFHIP_VP9_PRED_SCALED is a call of the unscaled template, exactly as in ffhip_vp9_inter_frames_dev().  A
+ *    record with it is a call of the SCALED template (inter_recon picks it when b->ref[0]'s reference is scaled, or b->comp and
+ *    b->ref[1]'s is): per reference it uses, a reference of the frame's size is read by the unscaled rule (mc_*_unscaled), a scaled
+ *    one as follows.  (x, y) is the record's origin in its plane, (px, py, pw, ph) its clip box from box[]: the call's offset inside
+ *    its enclosing block, and that block's size, in the record's plane;
+ *  - luma, scaled reference: mv.x = clip(mv.x, -(x + pw - px + 4) * 8, (cols * 8 - x + px + 3) * 8), mx = scale_mv(mv.x * 2, 0) +
+ *    scale_mv(x * 16, 0); the same with y, ph, py, rows and index 1 for my.  Output sample (i, j) of the w x h call is
+ *    VP9DSPContext.smc[..][filter][put / avg](..., h, mx & 15, my & 15, step[0], step[1]) from the origin (mx >> 4, my >> 4): the
+ *    oracle's ffo_vp9_smc_bd, horizontal pass first into pixel-type temporaries, phase 0 a copy;
+ *  - chroma, scaled reference, with ss_h set: mv.x = clip(mv.x, -(x + pw - px + 4) * 16, (cols * 4 - x + px + 3) * 16), mx =
+ *    scale_mv(mv.x, 0) + (scale_mv(x * 16, 0) & ~15) + (scale_mv(x * 32, 0) & 15) (libvpx's rounding, webm issue 820, which the
+ *    reference reproduces); with ss_h clear, the luma formulas.  The same for y with ss_v, rows and index 1;
+ *  - reference edge: every sample of a reference is read with its coordinates clamped to that reference's real size, [0, rw) x
+ *    [0, rh) for luma, [0, (rw + ss_h) >> ss_h) x [0, (rh + ss_v) >> ss_v) for chroma.  mc_luma_scaled / mc_chroma_scaled read
+ *    directly only when the whole window, rows y - 3 .. y + refbh_m1 + 4 and columns x - 3 .. x + refbw_m1 + 4, lies inside the
+ *    reference, and through emulated_edge_mc of that window otherwise, which replicates the edge samples: both give this clamp;
+ *  - compound averaging, the TUs, what is written and what is never written: as ffhip_vp9_inter_frames_dev().
+ *  A record with FFHIP_VP9_PRED_SCALED is malformed (writes nothing) when log2 pw or log2 ph lies outside 2..6, px + w > pw or
+ *  py + h > ph; the other malformed classes are ffhip_vp9_inter_frames_dev()'s.  A launch (16 frames) none of whose references is
+ *  scaled runs ffhip_vp9_inter_frames_dev()'s kernel, which treats FFHIP_VP9_PRED_SCALED as malformed: rule 2 of inter_recon never
+ *  gives such a record there.
+ */
+typedef struct FFHipVp9InterPicScaled {
+    FFHipVp9InterPic pic;           /* as for ffhip_vp9_inter_frames_dev(); references of their own size */
+    int32_t ref_w[3], ref_h[3];     /* the luma size of each of pic.ref[0 .. nrefs - 1] (1..65535) */
+} FFHipVp9InterPicScaled;
+/** ffhip_vp9_inter_frames_dev() with references of any valid size.  FFHIP_EINVAL (before any device check) for what
+ *  ffhip_vp9_inter_frames_dev() refuses, with each reference plane's stride and overlap checked over that reference's own plane size,
+ *  and for a reference size outside 1..65535 or outside the 2x / 16x limits above; FFHIP_ENOSYS without a device.  Frames whose
+ *  references all have the frame's size give the bytes ffhip_vp9_inter_frames_dev() gives. */
+int ffhip_vp9_inter_frames_scaled_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics,
+                                      const FFHipVp9InterPicScaled *pics /* host array */, void *stream);
+/** The records of one decoded block for the SCALED template (arguments as ffhip_vp9_inter_block_preds()), every one with
+ *  FFHIP_VP9_PRED_SCALED and its clip box, in its call order.  At least 8x8: one luma call with box (0, 0, bw, bh) and one chroma
+ *  call with (0, 0, bw >> ss_h, bh >> ss_v), mv[0].  8x4, 4x8 and 4x4 take the template's 4x4 branch (8x4 and 4x8 have their own
+ *  branches only under SCALED == 0): four 4x4 luma calls with mv[0..3] and boxes (0 | 4, 0 | 4, 8, 8); chroma as that branch, the
+ *  boxes in the chroma plane (offset in the 8 x 8 luma area's chroma, (8 >> ss_h) x (8 >> ss_v)).  A decoder calls this when inter_recon
+ *  picks the SCALED template, ffhip_vp9_inter_block_preds() otherwise.  Writes up to 8 records; returns their count, FFHIP_EINVAL
+ *  for bad arguments. */
+int ffhip_vp9_inter_block_preds_scaled(FFHipVp9InterPred *out, int bs, int row, int col, const int16_t mv[4][2][2], int comp,
+                                       const uint8_t ref[2], int filter, int ss_h, int ss_v);
 
 /**
  * VP9 intra reconstruction of whole frames in one launch: intra_recon() with check_intra_mode() (libavcodec/vp9recon.c) for every
