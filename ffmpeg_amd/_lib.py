@@ -274,6 +274,15 @@ def lib():
         "ffhip_vp9_intra_frames_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_vp9_intra_record_size": (C.c_int, []),
         "ffhip_vp9_intra_block_records": (C.c_int, [vp] + [C.c_int] * 5 + [vp, C.c_int, vp] + [C.c_int] * 5),
+        "ff_vp78dsp_init_hip": (C.c_int, [vp]),
+        "ff_vp8dsp_init_hip": (C.c_int, [vp]),
+        "ffhip_vp8_luma_dc_wht_batch_dev": (C.c_int, [vp, vp, C.c_int, vp]),
+        "ffhip_vp8_idct_add_batch_dev": (C.c_int, [vp, C.c_ssize_t, vp, vp, C.c_int, vp]),
+        "ffhip_vp8_mc_batch_dev": (C.c_int, [vp, C.c_ssize_t, vp, C.c_ssize_t, vp, C.c_int, vp]),
+        "ffhip_vp8_wht_record_size": (C.c_int, []),
+        "ffhip_vp8_idct_record_size": (C.c_int, []),
+        "ffhip_vp8_mc_record_size": (C.c_int, []),
+        "ffhip_vp8_loopfilter_frames_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t, vp]),
         "ffhip_hevc_inter_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_hevc_inter_pu_record_size": (C.c_int, []),
         "ffhip_hevc_inter_tu_record_size": (C.c_int, []),

@@ -2198,6 +2198,128 @@ int ffhip_vp9_intra_record_size(void);
 int ffhip_vp9_intra_block_records(FFHipVp9IntraRec *out /* up to 256 */, int plane, int bs, int tx, int row, int col, const uint8_t mode[4],
                                   int skip, const uint16_t *eob, int lossless, int cols, int rows, int ss_h, int ss_v);
 
+/* ------------------------------------------------------------------------------------------ */
+/* libavcodec: vp8dsp (VP8DSPContext, libavcodec/vp8dsp.h) — 8 bits, the only depth VP8 has    */
+/* ------------------------------------------------------------------------------------------ */
+/** VP8DSPContext member for member, with the reference's signatures.  put_vp8_*_pixels_tab[w][v][h]: w = 0, 1, 2 for blocks 16, 8 and
+ *  4 wide; v / h = 0 no filter along that axis, 1 the 4-tap form, 2 the 6-tap form (bilinear: 1 and 2 are the same function); mx, my
+ *  in eighths (1..7 along a filtered axis).  The semantics are vp8dsp.c's C, byte for byte, side effects included:
+ *  - vp8_luma_dc_wht writes the 16 second-stage DCs to block[i][j][0] and zeroes dc[0..15]; vp8_luma_dc_wht_dc writes (dc[0] + 3) >> 3
+ *    to all 16 and zeroes dc[0];
+ *  - vp8_idct_add adds the 4x4 inverse transform and zeroes all 16 coefficients; vp8_idct_dc_add adds (block[0] + 4) >> 3 and zeroes
+ *    block[0]; dc_add4y runs it on the blocks at +0, +4, +8, +12 samples, dc_add4uv at +0, +4, +4 * stride, +4 * stride + 4, each
+ *    zeroing its own block[i][0];
+ *  - the loop filters take (E, I, hev_thresh) as filter_mb() passes them (the simple ones take E only) and filter 16 lines (8 per
+ *    chroma plane) across the edge at dst: v_ members the row edge above dst, h_ members the column edge left of dst;
+ *  - h rows of width w for 1 <= h <= 2w (the reference's temporary); a filtered axis reads 2 samples before and 3 after (6-tap), 1 and
+ *    2 (4-tap), 0 and 1 (bilinear).
+ *  VP7's own members (ff_vp7dsp_init: its WHT, IDCT and loop filters) are not here. */
+typedef void (*ffhip_vp8_mc_func)(uint8_t *dst, ptrdiff_t dst_stride, const uint8_t *src, ptrdiff_t src_stride, int h, int mx, int my);
+typedef void (*ffhip_vp8_lf_func)(uint8_t *dst, ptrdiff_t stride, int flim_E, int flim_I, int hev_thresh);
+typedef void (*ffhip_vp8_lf_uv_func)(uint8_t *dst_u, uint8_t *dst_v, ptrdiff_t stride, int flim_E, int flim_I, int hev_thresh);
+typedef void (*ffhip_vp8_lf_simple_func)(uint8_t *dst, ptrdiff_t stride, int flim);
+typedef struct FFHipVP8DSPContext {
+    void (*vp8_luma_dc_wht)(int16_t block[4][4][16], int16_t dc[16]);
+    void (*vp8_luma_dc_wht_dc)(int16_t block[4][4][16], int16_t dc[16]);
+    void (*vp8_idct_add)(uint8_t *dst, int16_t block[16], ptrdiff_t stride);
+    void (*vp8_idct_dc_add)(uint8_t *dst, int16_t block[16], ptrdiff_t stride);
+    void (*vp8_idct_dc_add4y)(uint8_t *dst, int16_t block[4][16], ptrdiff_t stride);
+    void (*vp8_idct_dc_add4uv)(uint8_t *dst, int16_t block[4][16], ptrdiff_t stride);
+    ffhip_vp8_lf_func vp8_v_loop_filter16y;
+    ffhip_vp8_lf_func vp8_h_loop_filter16y;
+    ffhip_vp8_lf_uv_func vp8_v_loop_filter8uv;
+    ffhip_vp8_lf_uv_func vp8_h_loop_filter8uv;
+    ffhip_vp8_lf_func vp8_v_loop_filter16y_inner;
+    ffhip_vp8_lf_func vp8_h_loop_filter16y_inner;
+    ffhip_vp8_lf_uv_func vp8_v_loop_filter8uv_inner;
+    ffhip_vp8_lf_uv_func vp8_h_loop_filter8uv_inner;
+    ffhip_vp8_lf_simple_func vp8_v_loop_filter_simple;
+    ffhip_vp8_lf_simple_func vp8_h_loop_filter_simple;
+    ffhip_vp8_mc_func put_vp8_epel_pixels_tab[3][3][3];
+    ffhip_vp8_mc_func put_vp8_bilinear_pixels_tab[3][3][3];
+} FFHipVP8DSPContext;
+/** ff_vp78dsp_init shape: fills the two MC tables (shared by VP7 and VP8), nothing else.  ff_vp8dsp_init shape: fills the transforms
+ *  and the loop filters, nothing else.  Each remembers the C functions it displaces and answers a call that cannot run on the device
+ *  (or an argument outside the reference's range, such as mx = 0 in a filtered slot) through them.  0, FFHIP_EINVAL (NULL) or
+ *  FFHIP_ENOSYS (no device; the table is left as it was). */
+int ff_vp78dsp_init_hip(FFHipVP8DSPContext *c);
+int ff_vp8dsp_init_hip(FFHipVP8DSPContext *c);
+
+/** One macroblock of the WHT batch: vp8_luma_dc_wht (or _dc) from the 16 DCs at dc_offset into the block[4][4][16] array at
+ *  block_offset.  Offsets in bytes into coeffs, even. */
+typedef struct FFHipVp8WhtRec {
+    int32_t dc_offset;
+    int32_t block_offset;
+    uint8_t dc_only;                /* 1: vp8_luma_dc_wht_dc (only dc[0] is read and zeroed) */
+    uint8_t pad[3];                 /* sizeof == 12 */
+} FFHipVp8WhtRec;
+/** n macroblocks whose dc and block arrays are pairwise disjoint.  A record with an odd offset or dc_only > 1 is skipped.
+ *  FFHIP_EINVAL (before any device check) for a NULL or misaligned (odd) pointer or n < 0; FFHIP_ENOSYS without a device. */
+int ffhip_vp8_luma_dc_wht_batch_dev(int16_t *coeffs, const FFHipVp8WhtRec *recs, int n, void *stream);
+/** One 4x4 block of the IDCT batch: vp8_idct_add, or vp8_idct_dc_add when dc_only. */
+typedef struct FFHipVp8IdctRec {
+    int32_t dst_offset;             /* bytes into dst: the block's top-left sample */
+    int32_t coeff_offset;           /* bytes into coeffs (even): 16 int16 coefficients, consumed */
+    uint8_t dc_only;                /* 0 vp8_idct_add, 1 vp8_idct_dc_add */
+    uint8_t pad[3];                 /* sizeof == 12 */
+} FFHipVp8IdctRec;
+/** n blocks, pairwise disjoint in dst and in coeffs.  A decoder runs ffhip_vp8_luma_dc_wht_batch_dev() first on the same stream.  A
+ *  record with an odd coeff_offset or dc_only > 1 is skipped.  FFHIP_EINVAL (before any device check) for NULL pointers, an odd coeffs,
+ *  a stride of 0 or above 2^24 in magnitude, or n < 0; FFHIP_ENOSYS without a device. */
+int ffhip_vp8_idct_add_batch_dev(uint8_t *dst, ptrdiff_t stride, int16_t *coeffs, const FFHipVp8IdctRec *recs, int n, void *stream);
+/** One put_vp8_* call of the MC batch. */
+typedef struct FFHipVp8McRec {
+    int32_t dst_offset, src_offset; /* bytes into dst / src: the block's integer-sample origin */
+    uint8_t width;                  /* 16, 8 or 4 */
+    uint8_t h;                      /* 1 .. 2 * width */
+    uint8_t mx, my;                 /* eighths, 1..7 along a filtered axis (ignored along the others) */
+    uint8_t htaps, vtaps;           /* the table's [v][h] slot: 0 none, 1 the 4-tap form, 2 the 6-tap form */
+    uint8_t bilinear;               /* 1: put_vp8_bilinear_pixels_tab (slots 1 and 2 alike), 0: put_vp8_epel_pixels_tab */
+    uint8_t pad;                    /* sizeof == 16 */
+} FFHipVp8McRec;
+/** n calls, pairwise disjoint in dst.  src must be readable 2 samples left / up and 3 right / down of each block (only what the
+ *  record's slot reads is read).  A record with another width, h outside 1..2w, a slot above 2, bilinear above 1, or mx / my outside
+ *  1..7 along a filtered axis (0..7 bilinear) writes nothing.  FFHIP_EINVAL (before any device check) for NULL pointers, strides of 0 or
+ *  above 2^24 in magnitude, or n < 0; FFHIP_ENOSYS without a device. */
+int ffhip_vp8_mc_batch_dev(uint8_t *dst, ptrdiff_t dststride, const uint8_t *src, ptrdiff_t srcstride, const FFHipVp8McRec *recs, int n,
+                           void *stream);
+/** sizeof(FFHipVp8WhtRec), sizeof(FFHipVp8IdctRec), sizeof(FFHipVp8McRec), for bindings that mirror the records (no device needed). */
+int ffhip_vp8_wht_record_size(void);
+int ffhip_vp8_idct_record_size(void);
+int ffhip_vp8_mc_record_size(void);
+
+/**
+ * The VP8 loop filter of whole frames in one launch: what filter_mb_row() (libavcodec/vp8.c) does to a reconstructed frame, every
+ * macroblock in raster order, for up to 16 frames per launch (a larger npics is split into launches of 16).  A decoder stores
+ * td->filter_strength of every row into the frame's record array instead of filtering, and launches this after reconstruction.
+ *
+ *  Semantics, byte for byte: the frame as left by running, for mb_y = 0 .. mb_h - 1 and mb_x = 0 .. mb_w - 1, filter_mb() (filter_type
+ *  0, normal: Y, U and V) or filter_mb_simple() (filter_type 1: Y only, U and V untouched) of vp8.c with the record of that macroblock:
+ *  - level = filter_level, nothing at all when it is 0; a record with filter_level > 63, inner_limit > 63 or inner_filter > 1 counts as
+ *    level 0;
+ *  - mbedge_lim = 2 * level + inner_limit + 4, bedge_lim = 2 * level + inner_limit, hev_thresh = hev_thresh_lut[keyframe][level]
+ *    (0 below 15, then 1; from 20 2 for inter frames; from 40 2 for key frames and 3 for inter frames);
+ *  - normal: the left MB edge (mb_x > 0: h_loop_filter16y / 8uv), the inner column edges at 4, 8, 12 (luma) and 4 (chroma) when
+ *    inner_filter, the top MB edge (mb_y > 0: v_loop_filter16y / 8uv), then the inner row edges likewise; simple: the same order
+ *    with h_ / v_loop_filter_simple, mbedge_lim on the MB edges and bedge_lim inside.
+ *  Nothing outside mb_w * 16 x mb_h * 16 luma and mb_w * 8 x mb_h * 8 chroma samples is read or written.
+ */
+typedef struct FFHipVp8FilterStrength { /* == VP8FilterStrength (libavcodec/vp8.h): what filter_level_for_mb() leaves, 3 bytes */
+    uint8_t filter_level;
+    uint8_t inner_limit;
+    uint8_t inner_filter;
+} FFHipVp8FilterStrength;
+typedef struct FFHipVp8LfPic {         /* device pointers */
+    uint8_t *y, *u, *v;                /* the planes' top-left samples (u, v unused by the simple filter and may be NULL there) */
+    const FFHipVp8FilterStrength *strength; /* mb_w * mb_h records in raster order */
+} FFHipVp8LfPic;
+/** filter_type 0 normal, 1 simple; keyframe 0 or 1; mb_w, mb_h 1..1024.  Planes and strides must be multiples of 4 bytes, stride_y at
+ *  least 16 * mb_w and (normal) stride_uv at least 8 * mb_w.  Asynchronous on `stream`; a lost hand-off (never in a correct run) is
+ *  reported by ffhip_stream_synchronize.  FFHIP_EINVAL (before any device check) for other values, npics <= 0 or a NULL array, NULL or
+ *  misaligned planes, or two planes of the call that overlap; FFHIP_ENOSYS without a device. */
+int ffhip_vp8_loopfilter_frames_dev(int filter_type, int keyframe, int mb_w, int mb_h, int npics, const FFHipVp8LfPic *pics /* host array */,
+                                    ptrdiff_t stride_y, ptrdiff_t stride_uv, void *stream);
+
 /**
  * vp9dsp above 8 bits (profiles 2 / 3): the batch faces above at the bpp ff_vp9dsp_init(dsp, bpp, bitexact) instantiates its template
  * for (libavcodec/vp9dsp.c:88-112, vp9dsp_10bpp.c / vp9dsp_12bpp.c).  bit_depth 8, 10 or 12.  Samples are uint16_t above 8 bits,
