@@ -40,6 +40,7 @@
 #include "kernels/h264_kernels.h"
 #include "kernels/h264_lf_line.h"
 #include "kernels/progress_pool.h"
+#include "kernels/row_handoff.h"
 
 struct FFHipH264Mbaff {
     int mb_w, mb_h;                              /* the frame's macroblocks; mb_h even */
@@ -233,68 +234,25 @@ extern "C" int ffhip_h264_mbaff_lists(FFHipH264Mbaff *m, FFHipH264MbaffLists *ou
 /* kernels */
 
 namespace {
-__device__ __forceinline__ void mb_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 struct MbWave {
     int lane;
     template <class F>
     __device__ __forceinline__ void run(F body)
     {
         body(lane);
-        mb_wave_sync();
+        ffhip_wave_sync();
     }
 };
-__device__ __forceinline__ uint32_t mb_ld(const uint8_t *p)
-{
-    return __hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void mb_st(uint8_t *p, uint32_t v)
-{
-    __hip_atomic_store(reinterpret_cast<uint32_t *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-/* four samples: a dword at 8 bits, two above */
-template <typename PIX> struct MbQuad { typedef uint32_t T; };
-template <> struct MbQuad<uint16_t> { typedef uint64_t T; };
-template <typename Q>
-__device__ __forceinline__ Q mb_ldq(const uint8_t *p)
-{
-    return __hip_atomic_load(reinterpret_cast<const Q *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename Q>
-__device__ __forceinline__ void mb_stq(uint8_t *p, Q v)
-{
-    __hip_atomic_store(reinterpret_cast<Q *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+/* the hand-off of row_handoff.h with agent-scope fences and a wave_barrier behind the drain: as written in 17b7dc2; not re-measured */
 __device__ __forceinline__ bool mb_wait(const int *counter, int want, int *fail, int lane)
 {
-    int spins = 0;
-    while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++spins > (1 << 24)) {
-            if (lane == 0)
-                __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            return false;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return true;
+    return ffhip_row_wait_fresh<FFHIP_ROW_SLEEP, FFHIP_ROW_SPINS, FFHIP_ROW_FENCE_AGENT>(counter, want, fail, lane);
 }
 /* every store of the wave is out and visible (to its own later loads and to the other rows) */
-__device__ __forceinline__ void mb_drain()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-}
+__device__ __forceinline__ void mb_drain() { ffhip_row_drain<FFHIP_ROW_FENCE_AGENT, true>(); }
 __device__ __forceinline__ void mb_publish(int *counter, int value, int lane)
 {
-    mb_drain();
-    if (lane == 0)
-        __hip_atomic_store(counter, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ffhip_row_publish<FFHIP_ROW_FENCE_AGENT, true>(counter, value, lane);
 }
 } // namespace
 
@@ -305,7 +263,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_intra(uint8_t *py, uint8_t *p
                                                          const FFHipH264IntraMB *recs, const uint32_t *geo, const int32_t *row_start,
                                                          const int16_t *coefs, int *progress, int *fail, int maxv)
 {
-    typedef typename MbQuad<PIX>::T Q;
+    typedef typename FFHipQuad<PIX>::T Q;
     typedef typename ImbCoef<PIX>::T CF;
     constexpr int PS = (int)sizeof(PIX);
     __shared__ __align__(16) ImbTileT<PIX> T;
@@ -316,7 +274,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_intra(uint8_t *py, uint8_t *p
         p4tab[i] = imb_tab(i);
     if (lane < 16)
         T.zero[lane] = 0;
-    mb_wave_sync();
+    ffhip_wave_sync();
     int k = __builtin_amdgcn_readfirstlane(row_start[p]);
     const int kend = __builtin_amdgcn_readfirstlane(row_start[p + 1]);
     mb_publish(&progress[p], k < kend ? (int)(geo[k] & 0xFFF) : mb_w, lane);
@@ -326,7 +284,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_intra(uint8_t *py, uint8_t *p
             reinterpret_cast<uint32_t *>(&R)[lane] = reinterpret_cast<const uint32_t *>(recs + k)[lane];
         const uint32_t g = geo[k];
         const int mx = (int)(g & 0xFFF), my = (int)((g >> 12) & 0xFFF), field = (int)(g >> 24) & 1;
-        mb_wave_sync();
+        ffhip_wave_sync();
         if (p > 0 && !mb_wait(&progress[p - 1], min(mx + 2, mb_w), fail, lane))
             return;
         /* the macroblock's first frame line and its line step: a field macroblock of pair p starts on the pair's line 0 / 1 */
@@ -344,34 +302,34 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_intra(uint8_t *py, uint8_t *p
             if (lane < 8) {
                 const int c = 4 * lane - 4;
                 if (has_t && (c >= 0 || has_l) && (c < 16 || has_r))
-                    v = mb_ldq<Q>(ymb - ysy + c * PS);
+                    v = ffhip_row_ld<Q>(ymb - ysy + c * PS);
                 *reinterpret_cast<Q *>(&T.y[imb_yi(-1, c)]) = v;
             } else if (lane < 24) {
                 const int r = lane - 8;
                 if (has_l)
-                    v = mb_ldq<Q>(ymb + (ptrdiff_t)r * ysy - 4 * PS);
+                    v = ffhip_row_ld<Q>(ymb + (ptrdiff_t)r * ysy - 4 * PS);
                 *reinterpret_cast<Q *>(&T.y[imb_yi(r, -4)]) = v;
                 *reinterpret_cast<Q *>(&T.y[imb_yi(r, 16)]) = 0;
                 *reinterpret_cast<Q *>(&T.y[imb_yi(r, 20)]) = 0;
             } else if (lane < 30) {
                 const int pl = (lane - 24) / 3, c = 4 * ((lane - 24) % 3) - 4;
                 if (has_t && (c >= 0 || has_l))
-                    v = mb_ldq<Q>(cmb[pl] - csc + c * PS);
+                    v = ffhip_row_ld<Q>(cmb[pl] - csc + c * PS);
                 *reinterpret_cast<Q *>(&T.c[pl][imb_ci(-1, c)]) = v;
             } else if (lane < 46) {
                 const int pl = (lane - 30) >> 3, r = (lane - 30) & 7;
                 if (has_l)
-                    v = mb_ldq<Q>(cmb[pl] + (ptrdiff_t)r * csc - 4 * PS);
+                    v = ffhip_row_ld<Q>(cmb[pl] + (ptrdiff_t)r * csc - 4 * PS);
                 *reinterpret_cast<Q *>(&T.c[pl][imb_ci(r, -4)]) = v;
             }
         }
-        mb_wave_sync();
+        ffhip_wave_sync();
         imb_reconstruct<PIX>(X, T, R, reinterpret_cast<const CF *>(coefs + R.coef), p4tab, maxv, 3);
         /* the macroblock back into the picture: 64 luma quads, 32 chroma quads */
-        mb_stq<Q>(ymb + (ptrdiff_t)(lane >> 2) * ysy + 4 * (lane & 3) * PS, *reinterpret_cast<const Q *>(&T.y[imb_yi(lane >> 2, 4 * (lane & 3))]));
+        ffhip_row_st<Q>(ymb + (ptrdiff_t)(lane >> 2) * ysy + 4 * (lane & 3) * PS, *reinterpret_cast<const Q *>(&T.y[imb_yi(lane >> 2, 4 * (lane & 3))]));
         if (lane < 32) {
             const int pl = lane >> 4, r = (lane >> 1) & 7, c = 4 * (lane & 1);
-            mb_stq<Q>(cmb[pl] + (ptrdiff_t)r * csc + c * PS, *reinterpret_cast<const Q *>(&T.c[pl][imb_ci(r, c)]));
+            ffhip_row_st<Q>(cmb[pl] + (ptrdiff_t)r * csc + c * PS, *reinterpret_cast<const Q *>(&T.c[pl][imb_ci(r, c)]));
         }
         /* the next record: the other macroblock of this pair (the pair is not finished), or a pair further right */
         const int nx = k + 1 < kend ? (int)(geo[k + 1] & 0xFFF) : mb_w;
@@ -455,7 +413,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock(MbaffLfArgs A, int *p
             have[k] = d < ND && line0 + tl >= 0 && col0 + 4 * tc >= 0;
             orig[k] = 0;
             if (have[k])
-                orig[k] = mb_ld(plane + (ptrdiff_t)(line0 + tl) * stride + col0 + 4 * tc);
+                orig[k] = ffhip_row_ld<uint32_t>(plane + (ptrdiff_t)(line0 + tl) * stride + col0 + 4 * tc);
         }
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -465,7 +423,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock(MbaffLfArgs A, int *p
             if (lane < n) {
                 C[3 * lane] = c0; C[3 * lane + 1] = c1; C[3 * lane + 2] = c2;
             }
-            mb_wave_sync();
+            ffhip_wave_sync();
             for (int i = 0; i < n; i++) {
                 const uint32_t w0 = C[3 * i], w1 = C[3 * i + 1];
                 const int toff = (int)(w0 & 0xFFFF), kf = (int)(w0 >> 16) & 255, alpha = (int)(w0 >> 24), beta = (int)(w1 & 255);
@@ -508,7 +466,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock(MbaffLfArgs A, int *p
                         if (m & 32) c[2 * step] = (uint8_t)v.q2;
                     }
                 }
-                mb_wave_sync(); /* the next call reads what this one wrote, through other lanes */
+                ffhip_wave_sync(); /* the next call reads what this one wrote, through other lanes */
             }
             at += n;
             if (at >= end)
@@ -526,7 +484,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock(MbaffLfArgs A, int *p
             if (have[k]) {
                 const uint32_t cur = reinterpret_cast<const uint32_t *>(tile)[d];
                 if (cur != orig[k])
-                    mb_st(plane + (ptrdiff_t)(line0 + tl) * stride + col0 + 4 * tc, cur);
+                    ffhip_row_st<uint32_t>(plane + (ptrdiff_t)(line0 + tl) * stride + col0 + 4 * tc, cur);
             }
         }
         mb_publish(&progress[p], x + 1, lane);
@@ -576,7 +534,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock_hbd(MbaffLfArgs A, in
             have[k] = d < ND && line0 + tl >= 0 && col0 + 2 * tc >= 0;
             orig[k] = 0;
             if (have[k])
-                orig[k] = mb_ld(plane + (ptrdiff_t)(line0 + tl) * stride + 2 * (col0 + 2 * tc));
+                orig[k] = ffhip_row_ld<uint32_t>(plane + (ptrdiff_t)(line0 + tl) * stride + 2 * (col0 + 2 * tc));
         }
 #pragma unroll
         for (int k = 0; k < 7; k++)
@@ -586,7 +544,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock_hbd(MbaffLfArgs A, in
             if (lane < n) {
                 C[3 * lane] = c0; C[3 * lane + 1] = c1; C[3 * lane + 2] = c2;
             }
-            mb_wave_sync();
+            ffhip_wave_sync();
             for (int i = 0; i < n; i++) {
                 const uint32_t w0 = C[3 * i], w1 = C[3 * i + 1];
                 const int toff = (int)(w0 & 0xFFFF), kf = (int)(w0 >> 16) & 255, alpha = (int)(w0 >> 24) << sh, beta = (int)(w1 & 255) << sh;
@@ -617,7 +575,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock_hbd(MbaffLfArgs A, in
                     if (m & 16) c[xs] = (uint16_t)v.q1;
                     if (m & 32) c[2 * xs] = (uint16_t)v.q2;
                 }
-                mb_wave_sync();
+                ffhip_wave_sync();
             }
             at += n;
             if (at >= end)
@@ -634,7 +592,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock_hbd(MbaffLfArgs A, in
             if (have[k]) {
                 const uint32_t cur = reinterpret_cast<const uint32_t *>(tile)[d];
                 if (cur != orig[k])
-                    mb_st(plane + (ptrdiff_t)(line0 + tl) * stride + 2 * (col0 + 2 * tc), cur);
+                    ffhip_row_st<uint32_t>(plane + (ptrdiff_t)(line0 + tl) * stride + 2 * (col0 + 2 * tc), cur);
             }
         }
         mb_publish(&progress[p], x + 1, lane);
@@ -760,27 +718,20 @@ extern "C" int ffhip_h264_mbaff_flush(FFHipH264Mbaff *m, uint8_t *const dst[3], 
     };
     int rc = 0;
     if (!m->recs.empty()) {
-        FFHipProgressSlot ps;
-        rc = ffhip_progress_acquire(prow, stream, &ps);
+        rc = ffhip_progress_launch(prow, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            if (m->bd == 8)
+                hipLaunchKernelGGL(k_h264_mbaff_intra<uint8_t>, dim3(prow), dim3(64), 0, stream, dst[0], dst[1], dst[2], (ptrdiff_t)stride[0], (ptrdiff_t)stride[1],
+                                   m->mb_w, m->mb_h, reinterpret_cast<const FFHipH264IntraMB *>(b + off[0]), reinterpret_cast<const uint32_t *>(b + off[1]),
+                                   reinterpret_cast<const int32_t *>(b + off[3]), reinterpret_cast<const int16_t *>(b + off[2]), ps.prog, ps.fail, 255);
+            else
+                hipLaunchKernelGGL(k_h264_mbaff_intra<uint16_t>, dim3(prow), dim3(64), 0, stream, dst[0], dst[1], dst[2], (ptrdiff_t)stride[0],
+                                   (ptrdiff_t)stride[1], m->mb_w, m->mb_h, reinterpret_cast<const FFHipH264IntraMB *>(b + off[0]),
+                                   reinterpret_cast<const uint32_t *>(b + off[1]), reinterpret_cast<const int32_t *>(b + off[3]),
+                                   reinterpret_cast<const int16_t *>(b + off[2]), ps.prog, ps.fail, (1 << m->bd) - 1);
+            return hipGetLastError();
+        });
         if (rc < 0)
             return leave(rc);
-        if (m->bd == 8)
-            hipLaunchKernelGGL(k_h264_mbaff_intra<uint8_t>, dim3(prow), dim3(64), 0, stream, dst[0], dst[1], dst[2], (ptrdiff_t)stride[0], (ptrdiff_t)stride[1],
-                               m->mb_w, m->mb_h, reinterpret_cast<const FFHipH264IntraMB *>(b + off[0]), reinterpret_cast<const uint32_t *>(b + off[1]),
-                               reinterpret_cast<const int32_t *>(b + off[3]), reinterpret_cast<const int16_t *>(b + off[2]), ps.prog, ps.fail, 255);
-        else
-            hipLaunchKernelGGL(k_h264_mbaff_intra<uint16_t>, dim3(prow), dim3(64), 0, stream, dst[0], dst[1], dst[2], (ptrdiff_t)stride[0],
-                               (ptrdiff_t)stride[1], m->mb_w, m->mb_h, reinterpret_cast<const FFHipH264IntraMB *>(b + off[0]),
-                               reinterpret_cast<const uint32_t *>(b + off[1]), reinterpret_cast<const int32_t *>(b + off[3]),
-                               reinterpret_cast<const int16_t *>(b + off[2]), ps.prog, ps.fail, (1 << m->bd) - 1);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return leave(FFHIP_EIO);
-        }
-        if (r2 < 0)
-            return leave(r2);
     }
     if (!m->calls[0].empty() || !m->calls[1].empty() || !m->calls[2].empty()) {
         MbaffLfArgs A;
@@ -792,22 +743,15 @@ extern "C" int ffhip_h264_mbaff_flush(FFHipH264Mbaff *m, uint8_t *const dst[3], 
         }
         A.mb_w = m->mb_w;
         A.prow = prow;
-        FFHipProgressSlot ps;
-        rc = ffhip_progress_acquire(3 * prow, stream, &ps);
+        rc = ffhip_progress_launch(3 * prow, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            if (m->bd == 8)
+                hipLaunchKernelGGL(k_h264_mbaff_deblock, dim3(prow, 3), dim3(64), 0, stream, A, ps.prog, ps.fail);
+            else
+                hipLaunchKernelGGL(k_h264_mbaff_deblock_hbd, dim3(prow, 3), dim3(64), 0, stream, A, ps.prog, ps.fail, m->bd);
+            return hipGetLastError();
+        });
         if (rc < 0)
             return leave(rc);
-        if (m->bd == 8)
-            hipLaunchKernelGGL(k_h264_mbaff_deblock, dim3(prow, 3), dim3(64), 0, stream, A, ps.prog, ps.fail);
-        else
-            hipLaunchKernelGGL(k_h264_mbaff_deblock_hbd, dim3(prow, 3), dim3(64), 0, stream, A, ps.prog, ps.fail, m->bd);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return leave(FFHIP_EIO);
-        }
-        if (r2 < 0)
-            return leave(r2);
     }
     return leave(0);
 }

@@ -51,6 +51,15 @@ __device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d)
     return (uint32_t)a | ((uint32_t)b << 8) | ((uint32_t)c << 16) | ((uint32_t)d << 24);
 }
 
+/* A wave's LDS operations execute in order, but the compiler may reorder them: this orders one wave's LDS stores before its later LDS
+ * loads (other lanes' data) without a workgroup barrier.  For tiles no other wave touches. */
+__device__ __forceinline__ void ffhip_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 /* the residual row segment z[0..NS-1] (NS = 4, 8, 16, 32) added to NS picture samples at d8 (bd 8: bytes; above: uint16_t, clipped to
  * (1 << bd) - 1), as wide as d8's alignment allows: 16-byte accesses for 16-bit samples, 8-byte ones for bytes (one dword for NS = 4) */
 template <int NS>

@@ -22,60 +22,28 @@
 #include "common.h"
 #include "h264_intra_mb.h"
 #include "h264_kernels.h"
+#include "row_handoff.h"
 
 static_assert(sizeof(FFHipH264IntraC422) == 32, "FFHipH264IntraC422 is a 32-byte record");
 
 namespace {
-__device__ __forceinline__ void c4_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 struct C4Wave {
     int lane;
     template <class F>
     __device__ __forceinline__ void run(F body)
     {
         body(lane);
-        c4_wave_sync();
+        ffhip_wave_sync();
     }
 };
-template <typename PIX> struct C4Quad { typedef uint32_t T; };
-template <> struct C4Quad<uint16_t> { typedef uint64_t T; };
-template <typename Q>
-__device__ __forceinline__ Q c4_ld(const uint8_t *p)
-{
-    return __hip_atomic_load(reinterpret_cast<const Q *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename Q>
-__device__ __forceinline__ void c4_st(uint8_t *p, Q v)
-{
-    __hip_atomic_store(reinterpret_cast<Q *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-/* waits until the row above has published `want`; false after a timeout (never in a correct run) */
+/* the hand-off of row_handoff.h with agent-scope fences and a wave_barrier behind the drain: as written in c837e0c; not re-measured */
 __device__ __forceinline__ bool c4_wait(const int *counter, int want, int *fail, int lane)
 {
-    int spins = 0;
-    while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++spins > (1 << 24)) {
-            if (lane == 0)
-                __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            return false;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return true;
+    return ffhip_row_wait_fresh<FFHIP_ROW_SLEEP, FFHIP_ROW_SPINS, FFHIP_ROW_FENCE_AGENT>(counter, want, fail, lane);
 }
-/* every store of the wave is out and visible before the counter moves */
 __device__ __forceinline__ void c4_publish(int *counter, int value, int lane)
 {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0)
-        __hip_atomic_store(counter, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ffhip_row_publish<FFHIP_ROW_FENCE_AGENT, true>(counter, value, lane);
 }
 } // namespace
 
@@ -91,7 +59,7 @@ __global__ __launch_bounds__(64) void k_h264_intra_c422(FFHipC422IntraSet S, ptr
     const int32_t *const row_start = S.pic[blockIdx.y].row_start;
     const int16_t *const coefs = S.pic[blockIdx.y].coefs;
     progress += (size_t)blockIdx.y * (size_t)mb_h;
-    typedef typename C4Quad<PIX>::T Q;
+    typedef typename FFHipQuad<PIX>::T Q;
     typedef typename ImbCoef<PIX>::T CF;
     constexpr int PS = (int)sizeof(PIX);
     __shared__ __align__(16) ImbTileC422<PIX> T;
@@ -108,7 +76,7 @@ __global__ __launch_bounds__(64) void k_h264_intra_c422(FFHipC422IntraSet S, ptr
     for (; k < kend; k++) {
         if (lane < 8)
             reinterpret_cast<uint32_t *>(&Rs)[lane] = reinterpret_cast<const uint32_t *>(recs + k)[lane];
-        c4_wave_sync();
+        ffhip_wave_sync();
         const int mx = __builtin_amdgcn_readfirstlane((int)Rs.mb_x);
         const bool has_l = mx > 0, has_t = my > 0;
         if (has_t && !c4_wait(&progress[my - 1], min(mx + 1, mb_w), fail, lane))
@@ -120,24 +88,24 @@ __global__ __launch_bounds__(64) void k_h264_intra_c422(FFHipC422IntraSet S, ptr
         if (lane < 6) {
             const int p = lane / 3, c = 4 * (lane % 3) - 4;
             if (has_t && (c >= 0 || has_l))
-                nb = c4_ld<Q>(base[p] - sc + c * PS);
+                nb = ffhip_row_ld<Q>(base[p] - sc + c * PS);
         } else if (lane >= 8 && lane < 40) {
             const int p = (lane - 8) >> 4, r = (lane - 8) & 15;
             if (prev_mx == mx - 1)
                 nb = *reinterpret_cast<const Q *>(&T.c[p][imb_ci(r, 4)]);
             else if (has_l)
-                nb = c4_ld<Q>(base[p] + (ptrdiff_t)r * sc - 4 * PS);
+                nb = ffhip_row_ld<Q>(base[p] + (ptrdiff_t)r * sc - 4 * PS);
         }
-        c4_wave_sync();
+        ffhip_wave_sync();
         if (lane < 6)
             *reinterpret_cast<Q *>(&T.c[lane / 3][imb_ci(-1, 4 * (lane % 3) - 4)]) = nb;
         else if (lane >= 8 && lane < 40)
             *reinterpret_cast<Q *>(&T.c[(lane - 8) >> 4][imb_ci((lane - 8) & 15, -4)]) = nb;
-        c4_wave_sync();
+        ffhip_wave_sync();
         imb_c422_reconstruct<PIX>(X, T, Rs, reinterpret_cast<const CF *>(coefs + Rs.coef), maxv);
         {
             const int p = lane >> 5, r = (lane >> 1) & 15, c = 4 * (lane & 1);
-            c4_st<Q>(base[p] + (ptrdiff_t)r * sc + c * PS, *reinterpret_cast<const Q *>(&T.c[p][imb_ci(r, c)]));
+            ffhip_row_st<Q>(base[p] + (ptrdiff_t)r * sc + c * PS, *reinterpret_cast<const Q *>(&T.c[p][imb_ci(r, c)]));
         }
         c4_publish(&progress[my], k + 1 < kend ? (int)recs[k + 1].mb_x : mb_w, lane);
         prev_mx = mx;
@@ -174,7 +142,7 @@ __global__ __launch_bounds__(64) void k_h264_deblock_c422(FFHipC422PlaneSet S, p
     uint8_t *const plane = S.plane[blockIdx.y];
     const FFHipH264Edge *const edges = S.edges[blockIdx.y];
     progress += (size_t)blockIdx.y * (size_t)mb_h;
-    typedef typename C4Quad<PIX>::T Q;
+    typedef typename FFHipQuad<PIX>::T Q;
     constexpr int PS = (int)sizeof(PIX);
     /* tile[r + 2][c + 4]: rows -2 .. 15, columns -4 .. 7 of the macroblock */
     __shared__ __align__(16) PIX tile[18 * C4_TP];
@@ -192,50 +160,50 @@ __global__ __launch_bounds__(64) void k_h264_deblock_c422(FFHipC422PlaneSet S, p
          * the left stay in the tile from the previous macroblock (this wave filtered it: its latest values are nowhere else yet in order) */
         if (lane < 32) {
             const int r = lane >> 1, c = 4 * (lane & 1);
-            *reinterpret_cast<Q *>(&tile[(r + 2) * C4_TP + c + 4]) = c4_ld<Q>(mb + (ptrdiff_t)r * stride + c * PS);
+            *reinterpret_cast<Q *>(&tile[(r + 2) * C4_TP + c + 4]) = ffhip_row_ld<Q>(mb + (ptrdiff_t)r * stride + c * PS);
         } else if (lane < 38 && my > 0) {
             const int r = (lane - 32) / 3 - 2, c = 4 * ((lane - 32) % 3) - 4;
             if (c >= 0 || mx > 0)
-                *reinterpret_cast<Q *>(&tile[(r + 2) * C4_TP + c + 4]) = c4_ld<Q>(mb + (ptrdiff_t)r * stride + c * PS);
+                *reinterpret_cast<Q *>(&tile[(r + 2) * C4_TP + c + 4]) = ffhip_row_ld<Q>(mb + (ptrdiff_t)r * stride + c * PS);
         }
-        c4_wave_sync();
+        ffhip_wave_sync();
         /* vertical edges x = 0, 4: lane = line */
         for (int k = 0; k < 2; k++) {
             const FFHipH264Edge e = ed[k];
             if (lane < 16 && e.alpha && e.beta && !(k == 0 && mx == 0))
                 c4_edge<PIX>(&tile[(lane + 2) * C4_TP + 4 + 4 * k], 1, e.kind >= 4, e.alpha, e.beta, e.tc0[lane >> 2], bd);
-            c4_wave_sync();
+            ffhip_wave_sync();
         }
         /* horizontal edges y = 0, 4, 8, 12: lane = column */
         for (int k = 0; k < 4; k++) {
             const FFHipH264Edge e = ed[2 + k];
             if (lane < 8 && e.alpha && e.beta && !(k == 0 && my == 0))
                 c4_edge<PIX>(&tile[(4 * k + 2) * C4_TP + 4 + lane], C4_TP, e.kind >= 4, e.alpha, e.beta, e.tc0[lane >> 1], bd);
-            c4_wave_sync();
+            ffhip_wave_sync();
         }
         /* what this macroblock may have changed goes back: its own samples, row -1 above it (p0 of the top edge), and the quad of
          * columns -4 .. -1 of rows 0 .. 15 (p0 of the left edge is column -1) */
         if (lane < 32) {
             const int r = lane >> 1, c = 4 * (lane & 1);
-            c4_st<Q>(mb + (ptrdiff_t)r * stride + c * PS, *reinterpret_cast<const Q *>(&tile[(r + 2) * C4_TP + c + 4]));
+            ffhip_row_st<Q>(mb + (ptrdiff_t)r * stride + c * PS, *reinterpret_cast<const Q *>(&tile[(r + 2) * C4_TP + c + 4]));
         } else if (lane < 34) {
             if (my > 0) {
                 const int c = 4 * (lane - 32);
-                c4_st<Q>(mb - stride + c * PS, *reinterpret_cast<const Q *>(&tile[1 * C4_TP + c + 4]));
+                ffhip_row_st<Q>(mb - stride + c * PS, *reinterpret_cast<const Q *>(&tile[1 * C4_TP + c + 4]));
             }
         } else if (lane >= 40 && lane < 56 && mx > 0) {
             const int r = lane - 40;
-            c4_st<Q>(mb + (ptrdiff_t)r * stride - 4 * PS, *reinterpret_cast<const Q *>(&tile[(r + 2) * C4_TP]));
+            ffhip_row_st<Q>(mb + (ptrdiff_t)r * stride - 4 * PS, *reinterpret_cast<const Q *>(&tile[(r + 2) * C4_TP]));
         }
         c4_publish(&progress[my], mx + 1, lane);
         /* the next macroblock's left context: columns 4 .. 7 of rows -2 .. 15 become its columns -4 .. -1 */
         Q carry = 0;
         if (lane < 18)
             carry = *reinterpret_cast<const Q *>(&tile[lane * C4_TP + 8]);
-        c4_wave_sync();
+        ffhip_wave_sync();
         if (lane < 18)
             *reinterpret_cast<Q *>(&tile[lane * C4_TP]) = carry;
-        c4_wave_sync();
+        ffhip_wave_sync();
     }
 }
 
@@ -266,22 +234,15 @@ int ffhip_launch_h264_intra_c422_pics(int bd, int npics, const FFHipH264C422Pic 
         FFHipC422IntraSet S;
         for (int i = 0; i < FFHIP_C422_PICS; i++)
             S.pic[i] = pics[p0 + (i < n ? i : 0)];
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(mb_h * n, stream, &ps);
+        const int r = ffhip_progress_launch(mb_h * n, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            if (bd > 8)
+                hipLaunchKernelGGL(k_h264_intra_c422<uint16_t>, dim3(mb_h, n), dim3(64), 0, stream, S, sc, mb_w, mb_h, ps.prog, ps.fail, (1 << bd) - 1);
+            else
+                hipLaunchKernelGGL(k_h264_intra_c422<uint8_t>, dim3(mb_h, n), dim3(64), 0, stream, S, sc, mb_w, mb_h, ps.prog, ps.fail, 255);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        if (bd > 8)
-            hipLaunchKernelGGL(k_h264_intra_c422<uint16_t>, dim3(mb_h, n), dim3(64), 0, stream, S, sc, mb_w, mb_h, ps.prog, ps.fail, (1 << bd) - 1);
-        else
-            hipLaunchKernelGGL(k_h264_intra_c422<uint8_t>, dim3(mb_h, n), dim3(64), 0, stream, S, sc, mb_w, mb_h, ps.prog, ps.fail, 255);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }
@@ -322,22 +283,15 @@ int ffhip_launch_h264_deblock_c422_planes(int bd, int nplanes, uint8_t *const *p
             S.plane[i] = planes[p0 + (i < n ? i : 0)];
             S.edges[i] = edges[p0 + (i < n ? i : 0)];
         }
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(mb_h * n, stream, &ps);
+        const int r = ffhip_progress_launch(mb_h * n, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            if (bd > 8)
+                hipLaunchKernelGGL(k_h264_deblock_c422<uint16_t>, dim3(mb_h, n), dim3(64), 0, stream, S, stride, mb_w, mb_h, ps.prog, ps.fail, bd);
+            else
+                hipLaunchKernelGGL(k_h264_deblock_c422<uint8_t>, dim3(mb_h, n), dim3(64), 0, stream, S, stride, mb_w, mb_h, ps.prog, ps.fail, bd);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        if (bd > 8)
-            hipLaunchKernelGGL(k_h264_deblock_c422<uint16_t>, dim3(mb_h, n), dim3(64), 0, stream, S, stride, mb_w, mb_h, ps.prog, ps.fail, bd);
-        else
-            hipLaunchKernelGGL(k_h264_deblock_c422<uint8_t>, dim3(mb_h, n), dim3(64), 0, stream, S, stride, mb_w, mb_h, ps.prog, ps.fail, bd);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

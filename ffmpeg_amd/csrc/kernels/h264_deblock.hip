@@ -27,6 +27,7 @@
 #include "h264_kernels.h"
 
 #include "h264_lf_line.h"
+#include "row_handoff.h"
 
 /* load / filter / store one line through any byte pointer; xs = step across the edge */
 template <typename P>
@@ -91,13 +92,6 @@ int ffhip_launch_h264_loop_filter(uint8_t *base, ptrdiff_t stride, const FFHipH2
 /* ---- frame order ---------------------------------------------------------------------------------- */
 #define TP 24 /* LDS tile pitch: 4 context columns + 16 + pad */
 
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t frame_pitch, ptrdiff_t stride, int mb_w, int mb_h,
                                                            const FFHipH264Edge *edges, int *progress, int *fail)
 {
@@ -159,6 +153,8 @@ __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t
         if (my > 0) {
             const int want = min(mx + 2, mb_w);
             if (!have_top || !dw_ok) {
+                /* ffhip_row_wait() of row_handoff.h by hand: pictures that are not dword-aligned (!dw_ok) poll with acquire loads
+                 * and publish with a release store instead of the fences */
                 int spins = 0;
                 while (known < want) {
                     /* dword-aligned pictures: everything that crosses rows moves with device-scope (cache-bypassing)
@@ -191,7 +187,7 @@ __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t
                 have_top = true;
             }
         }
-        wave_lds_sync();
+        ffhip_wave_sync();
         const FFHipH264Edge *e = reinterpret_cast<const FFHipH264Edge *>(edl);
         /* ---- vertical edges, left to right: lane = row ---- */
         for (int k = 0; k < 4; k++) {
@@ -200,7 +196,7 @@ __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t
                 const bool intra = ed.kind >= 4;
                 lf_apply(&tile[(lane + 4) * TP + 4 + 4 * k], 1, intra ? 2 : 0, ed.alpha, ed.beta, intra ? 0 : ed.tc0[lane >> 2]);
             }
-            wave_lds_sync();
+            ffhip_wave_sync();
         }
         /* ---- horizontal edges, top to bottom: lane = column ---- */
         for (int k = 0; k < 4; k++) {
@@ -209,7 +205,7 @@ __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t
                 const bool intra = ed.kind >= 4;
                 lf_apply(&tile[(4 + 4 * k) * TP + 4 + lane], TP, intra ? 2 : 0, ed.alpha, ed.beta, intra ? 0 : ed.tc0[lane >> 2]);
             }
-            wave_lds_sync();
+            ffhip_wave_sync();
         }
         /* ---- write back what this MB may have changed: rows -3..-1 x columns 0..15, rows 0..15 x columns -4..15
          * (column -4 and untouched pixels are rewritten with their own final values; the corner is left alone) ---- */
@@ -234,18 +230,15 @@ __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t
             }
         }
         /* ---- the MB's right 4 columns (and those of the context rows) are the next MB's left context ---- */
-        wave_lds_sync();
+        ffhip_wave_sync();
         const uint32_t keep = *reinterpret_cast<const uint32_t *>(&tile[(lane < 20 ? lane : 0) * TP + 4 + 12]);
-        wave_lds_sync();
+        ffhip_wave_sync();
         if (lane < 20)
             *reinterpret_cast<uint32_t *>(&tile[lane * TP]) = keep;
         /* ---- publish (release: this wave's stores above become visible before the counter does) ---- */
         if (dw_ok) {
             /* the write-through stores above are complete (acknowledged) before the counter moves */
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0);
-            if (lane == 0)
-                __hip_atomic_store(&progress[my], mx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ffhip_row_publish(&progress[my], mx + 1, lane);
         } else if (lane == 0) {
             __hip_atomic_store(&progress[my], mx + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -469,10 +462,7 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
         if (to_mem && mx >= 3 && !(fault & 1)) {
             /* through memory to the next band: the stores issued at the top of the previous step (macroblock mx - 2's rows,
              * mx - 3's last dword column) are acknowledged: macroblocks < mx - 2 are complete in memory */
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0);
-            if (lane == 0)
-                __hip_atomic_store(&gprog[band], mx - 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ffhip_row_publish(&gprog[band], mx - 2, lane);
         }
         if (mx > 0)
             flush(mx - 1, prev, cur, false); /* before the tile of macroblock mx - 2 (`cur`) is overwritten */
@@ -480,7 +470,7 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
             *reinterpret_cast<uint32_t *>(cur + lown) = mine;
         if (!last)
             fetch(mx + 1);
-        wave_lds_sync();
+        ffhip_wave_sync();
         /* ---- vertical edges, left to right: lane = row; samples -4 .. MB-1 of the row ---- */
         if (lane < MB && !(fault & 4)) {
             uint8_t *trow = cur + (lane + CTX) * TPP, *tprev = prev + (lane + CTX) * TPP + MB - 4;
@@ -520,6 +510,7 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
             /* LDS progress counts finished steps (the ring slot's last dword arrives a step late); the memory progress counts
              * macroblocks complete in memory */
             const int want = (fault & 8) ? 0 : from_lds ? min(mx + 2, mb_w) : mx + 1;
+            /* ffhip_row_wait() of row_handoff.h by hand: the counter is the LDS one or the global one (from_lds); sleep 1 */
             int spins = 0;
             while (known < want) {
                 known = from_lds ? __hip_atomic_load(&lprog[w - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
@@ -544,7 +535,7 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
                 *reinterpret_cast<uint32_t *>(cur + (lane / NDW) * TPP + 4 * ps) = v;
             }
         }
-        wave_lds_sync();
+        ffhip_wave_sync();
         /* ---- horizontal edges, top to bottom: lane = column; y[i] = row i - 4 (chroma: rows -2 .. 7, y[0], y[1] unused) ---- */
         if (lane < MB && !(fault & 4)) {
             uint8_t *tcol = cur + lane;
@@ -572,22 +563,14 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
             for (int r = 5 - CTX; r < MB + 3; r++)
                 tcol[(r - (4 - CTX)) * TPP] = (uint8_t)y[r];
         }
-        wave_lds_sync();
+        ffhip_wave_sync();
         /* ---- the row below, inside the band: bottom CTX rows into the ring ---- */
         if (to_lds) {
             if (mx >= DB_R) { /* slot reuse: the consumer must be done with macroblock mx - DB_R */
-                int spins = 0;
-                while (kbelow < mx - DB_R + 1) {
-                    kbelow = __hip_atomic_load(&lprog[w + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (kbelow >= mx - DB_R + 1)
-                        break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > (1 << 24)) {
-                        if (lane == 0)
-                            __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        return;
-                    }
-                }
+                /* an LDS counter, sleep 1, nothing is read behind it: as written in d7766d0; not re-measured */
+                if (!ffhip_row_wait<1, FFHIP_ROW_SPINS, FFHIP_ROW_FENCE_NONE, __HIP_MEMORY_SCOPE_WORKGROUP>(&lprog[w + 1], mx - DB_R + 1, kbelow,
+                                                                                                          fail, lane))
+                    return;
             }
             if (in_ring) {
                 if (!sprev)
@@ -606,13 +589,10 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
             __hip_atomic_store(&lprog[w], mx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     /* the last macroblock's stores, its row-end dword column included */
-    wave_lds_sync();
+    ffhip_wave_sync();
     flush(mb_w - 1, tbase + ((mb_w - 1) & 1) * TSZ, tbase + (((mb_w - 1) & 1) ^ 1) * TSZ, true);
     if (to_mem && !(fault & 1)) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_s_waitcnt(0);
-        if (lane == 0)
-            __hip_atomic_store(&gprog[band], mb_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ffhip_row_publish(&gprog[band], mb_w, lane);
     }
 }
 
@@ -736,21 +716,6 @@ __device__ __forceinline__ void db_edge(int (&v)[8], uint32_t rec, uint32_t tcw,
 #ifndef DB_SKEW
 #define DB_SKEW 1
 #endif
-/* spin on an LDS counter of another wave of the workgroup; false (and the launch's fail flag) after 2^22 polls — never in a correct run */
-__device__ __forceinline__ bool db_wait_lds(const int *ctr, int want, int *fail)
-{
-    int spins = 0;
-    while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > (1 << 22)) {
-            if ((threadIdx.x & 63) == 0)
-                __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            return false;
-        }
-    }
-    asm volatile("" ::: "memory");
-    return true;
-}
 /* the pictures of a launch that do not sit at a constant pitch (round 4: the picture objects of a batched flush, each with its own
  * planes and its own edge records): picture f's plane and records by table */
 struct FFHipDbPtrs { uint8_t *plane[FFHIP_DB_PTRS]; const FFHipH264Edge *edges[FFHIP_DB_PTRS]; };
@@ -871,7 +836,7 @@ __global__ __launch_bounds__(256) void k_h264_deblock_skew(uint8_t *plane, size_
         if (act && l < 3 * NE / 4)
             *reinterpret_cast<db_u4 *>(&etab[q][4 * l]) = eown;
         const rowv cur = own;                        /* this step's macroblock row: straight from the registers it was loaded into */
-        wave_lds_sync();
+        ffhip_wave_sync();
         uint32_t erec[NE], etcw[NE];
 #pragma unroll
         for (int k = 0; k < NE; k++) {
@@ -895,10 +860,10 @@ __global__ __launch_bounds__(256) void k_h264_deblock_skew(uint8_t *plane, size_
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        wave_lds_sync();
+        ffhip_wave_sync();
         /* ---- the ring is SL macroblocks long: the last row group is about to overwrite the column of macroblock x - SL, whose bottom
          *      rows the wave below reads until its step x - SL + 2 (two steps behind its top edge: the store pass) ---- */
-        if (to_lds && !(fault & 8) && !db_wait_lds(&hdone[wv + 1], base + s - SK * qb - SL + 3, fail))
+        if (to_lds && !(fault & 8) && !ffhip_row_wait_lds(&hdone[wv + 1], base + s - SK * qb - SL + 3, fail))
             return;
         /* ---- vertical edges, left to right: lane = row; samples -4 .. MB-1 of the row, in registers throughout ---- */
         if (act) {
@@ -932,19 +897,20 @@ __global__ __launch_bounds__(256) void k_h264_deblock_skew(uint8_t *plane, size_
             *reinterpret_cast<rowv *>(pm) = mw;
         }
         if (to_lds) { /* this step's vertical pass is in LDS (one wave's LDS operations execute in order: the counter follows the rows) */
-            wave_lds_sync();
+            ffhip_wave_sync();
             if (lane == 0 && !(fault & 1)) /* fault & 1: the test hook — no hand-off is published, the waiting wave must time out and report */
                 __hip_atomic_store(&vdone[wv], base + s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         /* ---- the band's top context.  From the wave above, in place: its last row group must have filtered the left edge of
          *      macroblock s + 1 (its step s + 1 + SK (Q - 1)) ---- */
-        if (from_lds && s < mb_w && !(fault & 8) && !db_wait_lds(&vdone[wv - 1], base + s + 2 + SK * (Q - 1), fail))
+        if (from_lds && s < mb_w && !(fault & 8) && !ffhip_row_wait_lds(&vdone[wv - 1], base + s + 2 + SK * (Q - 1), fail))
             return;
         /* ---- from the workgroup above, through memory: it must have its bottom rows of macroblock s in memory (count >= s + 1).  Only
          *      the horizontal edges of row group 0 read (and rewrite) them, so the wait sits behind the vertical pass ---- */
         if (from_mem && s < mb_w) {
             if (!have_top) {
                 const int want = (fault & 8) ? 0 : s + 1;
+                /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
                 int spins = 0;
                 while (known < want) {
                     known = __hip_atomic_load(&gprog[band - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -957,7 +923,7 @@ __global__ __launch_bounds__(256) void k_h264_deblock_skew(uint8_t *plane, size_
                         return;
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the neighbour loads are issued after the counter was seen */
                 if (lane < MB)
                     load_top(s);
             }
@@ -967,7 +933,7 @@ __global__ __launch_bounds__(256) void k_h264_deblock_skew(uint8_t *plane, size_
                     reinterpret_cast<uint32_t *>(ctxl + (s & (SL - 1)) * MBB)[i] = topv[i];
             }
         }
-        wave_lds_sync();
+        ffhip_wave_sync();
         /* the next macroblock's context, if the band above has already published it: its latency hides behind the H pass */
         have_top = false;
         if (from_mem && s + 1 < mb_w && known >= s + 2) {
@@ -996,18 +962,15 @@ __global__ __launch_bounds__(256) void k_h264_deblock_skew(uint8_t *plane, size_
                 if (!CHROMA || (r & 3) == 3 || (r & 3) == 0)
                     *reinterpret_cast<PIX *>(tcol + r * PITCH + (r >= 4 ? 16 : 0)) = (PIX)yv[r];
         }
-        wave_lds_sync();
+        ffhip_wave_sync();
         if (from_lds && lane == 0)
             __hip_atomic_store(&hdone[wv], base + s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     /* the last step's stores (the flush of the band's last row) are out: publish the whole row */
     if (to_mem && !(fault & 1)) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_s_waitcnt(0);
-        if (lane == 0)
-            __hip_atomic_store(&gprog[band], mb_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ffhip_row_publish(&gprog[band], mb_w, lane);
     }
-    wave_lds_sync();
+    ffhip_wave_sync();
     } /* band < nbands */
     __syncthreads(); /* the strip is reused: every wave is through with this super-band */
     } /* super-bands of this workgroup */
@@ -1071,58 +1034,51 @@ static int deblock_frames(bool chroma, uint8_t *plane, size_t frame_pitch, int n
         per_launch = FFHIP_DB_PTRS;
     for (int f0 = 0; f0 < nframes; f0 += per_launch) {
         const int nf = nframes - f0 < per_launch ? nframes - f0 : per_launch;
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(nf * per_frame, stream, &ps);
+        const int r = ffhip_progress_launch(nf * per_frame, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            int *const prog = ps.prog, *const fail = ps.fail;
+            uint8_t *pl = planes ? nullptr : plane + (size_t)f0 * frame_pitch;
+            const FFHipH264Edge *ed = planes ? nullptr : edges + (size_t)f0 * mb_w * mb_h * ne;
+            FFHipDbPtrs PT;
+            memset(&PT, 0, sizeof(PT));
+            if (planes)
+                for (int f = 0; f < nf; f++) {
+                    PT.plane[f] = planes[f0 + f];
+                    PT.edges[f] = edge_tabs[f0 + f];
+                }
+            if (skew) {
+                /* waves per picture: one per band while the chip has SIMDs to spare (a lone picture is latency-bound), else what an
+                 * XCD's 128 SIMDs leave each of its pictures, but never fewer than a quarter of the bands (the wavefront's width) */
+                const char *eb = FFHIP_KNOB("FFHIP_DEBLOCK_WAVES"), *ewp = FFHIP_KNOB("FFHIP_DEBLOCK_WPB");
+                int wpb = ewp && atoi(ewp) >= 1 && atoi(ewp) <= 4 ? atoi(ewp) : 4; /* cooperating waves per workgroup (bands per super-band) */
+                if (bd > 8 && !chroma && wpb > 3)
+                    wpb = 3; /* 16-bit luma: a strip row is 272 bytes, 3 waves' strip is what 64 KB of LDS hold */
+                const int per_xcd = cdiv(nf, 8);
+                int bwaves = eb && atoi(eb) > 0 ? atoi(eb) : 128 / per_xcd;
+                if (bwaves < cdiv(nbands, 4)) bwaves = cdiv(nbands, 4);
+                if (bwaves > nbands) bwaves = nbands;
+                bwaves = cdiv(bwaves, wpb) * wpb; /* whole workgroups (waves beyond the last band idle) */
+                const dim3 g(8 * (bwaves / wpb) * per_xcd), t(64 * wpb);
+                const int mbs = chroma ? 8 : 16, qq = 64 / mbs, nee = chroma ? 4 : 8, psz = bd > 8 ? 2 : 1;
+                const unsigned lds = (((unsigned)((4 + wpb * qq * mbs) * (8 * mbs * psz + 16) + (wpb * qq + 1) * 16 + 15)) & ~15u) +
+                                     (unsigned)wpb * (unsigned)qq * (3 * nee + 4) * 4 + 2u * wpb * 4;
+                static std::atomic<unsigned> launches{0};
+                const int xrot = nf < 8 ? (int)(launches.fetch_add((unsigned)nf, std::memory_order_relaxed) & 7) : 0; /* where the batch's first picture goes */
+#define DBS_LAUNCH(CH, T) hipLaunchKernelGGL((k_h264_deblock_skew<CH, T>), g, t, lds, stream, pl, frame_pitch, stride, mb_w, mb_h, ed, prog, nbands, bwaves, \
+                                                 nf, fail, fault, xrot, bd, PT, planes ? 1 : 0)
+                if (bd > 8) { if (chroma) DBS_LAUNCH(true, uint16_t); else DBS_LAUNCH(false, uint16_t); }
+                else        { if (chroma) DBS_LAUNCH(true, uint8_t); else DBS_LAUNCH(false, uint8_t); }
+#undef DBS_LAUNCH
+            } else if (!band)
+                hipLaunchKernelGGL(k_h264_deblock_frame, dim3(mb_h, nf), dim3(64), 0, stream, pl, frame_pitch, stride, mb_w, mb_h, ed, prog, fail);
+#define DB_LAUNCH(CH, W) hipLaunchKernelGGL((k_h264_deblock_band<CH, W>), dim3(nbands, nf), dim3(64 * W), 0, stream, pl, frame_pitch, stride, \
+                                                mb_w, mb_h, ed, prog, nbands, fail, fault)
+            else if (chroma) { if (bw == 16) DB_LAUNCH(true, 16); else if (bw == 8) DB_LAUNCH(true, 8); else DB_LAUNCH(true, 4); }
+            else             { if (bw == 16) DB_LAUNCH(false, 16); else if (bw == 8) DB_LAUNCH(false, 8); else DB_LAUNCH(false, 4); }
+#undef DB_LAUNCH
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        int *const prog = ps.prog, *const fail = ps.fail;
-        uint8_t *pl = planes ? nullptr : plane + (size_t)f0 * frame_pitch;
-        const FFHipH264Edge *ed = planes ? nullptr : edges + (size_t)f0 * mb_w * mb_h * ne;
-        FFHipDbPtrs PT;
-        memset(&PT, 0, sizeof(PT));
-        if (planes)
-            for (int f = 0; f < nf; f++) {
-                PT.plane[f] = planes[f0 + f];
-                PT.edges[f] = edge_tabs[f0 + f];
-            }
-        if (skew) {
-            /* waves per picture: one per band while the chip has SIMDs to spare (a lone picture is latency-bound), else what an
-             * XCD's 128 SIMDs leave each of its pictures, but never fewer than a quarter of the bands (the wavefront's width) */
-            const char *eb = FFHIP_KNOB("FFHIP_DEBLOCK_WAVES"), *ewp = FFHIP_KNOB("FFHIP_DEBLOCK_WPB");
-            int wpb = ewp && atoi(ewp) >= 1 && atoi(ewp) <= 4 ? atoi(ewp) : 4; /* cooperating waves per workgroup (bands per super-band) */
-            if (bd > 8 && !chroma && wpb > 3)
-                wpb = 3; /* 16-bit luma: a strip row is 272 bytes, 3 waves' strip is what 64 KB of LDS hold */
-            const int per_xcd = cdiv(nf, 8);
-            int bwaves = eb && atoi(eb) > 0 ? atoi(eb) : 128 / per_xcd;
-            if (bwaves < cdiv(nbands, 4)) bwaves = cdiv(nbands, 4);
-            if (bwaves > nbands) bwaves = nbands;
-            bwaves = cdiv(bwaves, wpb) * wpb; /* whole workgroups (waves beyond the last band idle) */
-            const dim3 g(8 * (bwaves / wpb) * per_xcd), t(64 * wpb);
-            const int mbs = chroma ? 8 : 16, qq = 64 / mbs, nee = chroma ? 4 : 8, psz = bd > 8 ? 2 : 1;
-            const unsigned lds = (((unsigned)((4 + wpb * qq * mbs) * (8 * mbs * psz + 16) + (wpb * qq + 1) * 16 + 15)) & ~15u) +
-                                 (unsigned)wpb * (unsigned)qq * (3 * nee + 4) * 4 + 2u * wpb * 4;
-            static std::atomic<unsigned> launches{0};
-            const int xrot = nf < 8 ? (int)(launches.fetch_add((unsigned)nf, std::memory_order_relaxed) & 7) : 0; /* where the batch's first picture goes */
-#define DBS_LAUNCH(CH, T) hipLaunchKernelGGL((k_h264_deblock_skew<CH, T>), g, t, lds, stream, pl, frame_pitch, stride, mb_w, mb_h, ed, prog, nbands, bwaves, \
-                                             nf, fail, fault, xrot, bd, PT, planes ? 1 : 0)
-            if (bd > 8) { if (chroma) DBS_LAUNCH(true, uint16_t); else DBS_LAUNCH(false, uint16_t); }
-            else        { if (chroma) DBS_LAUNCH(true, uint8_t); else DBS_LAUNCH(false, uint8_t); }
-#undef DBS_LAUNCH
-        } else if (!band)
-            hipLaunchKernelGGL(k_h264_deblock_frame, dim3(mb_h, nf), dim3(64), 0, stream, pl, frame_pitch, stride, mb_w, mb_h, ed, prog, fail);
-#define DB_LAUNCH(CH, W) hipLaunchKernelGGL((k_h264_deblock_band<CH, W>), dim3(nbands, nf), dim3(64 * W), 0, stream, pl, frame_pitch, stride, \
-                                            mb_w, mb_h, ed, prog, nbands, fail, fault)
-        else if (chroma) { if (bw == 16) DB_LAUNCH(true, 16); else if (bw == 8) DB_LAUNCH(true, 8); else DB_LAUNCH(true, 4); }
-        else             { if (bw == 16) DB_LAUNCH(false, 16); else if (bw == 8) DB_LAUNCH(false, 8); else DB_LAUNCH(false, 4); }
-#undef DB_LAUNCH
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

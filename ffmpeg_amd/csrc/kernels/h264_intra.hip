@@ -22,40 +22,21 @@
 #include "common.h"
 #include "h264_intra_mb.h"
 #include "h264_kernels.h"
+#include "row_handoff.h"
 
 static_assert(sizeof(FFHipH264IntraMB) == 108, "FFHipH264IntraMB is a 108-byte record");
 
 namespace {
-__device__ __forceinline__ void imb_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 struct ImbWave {
     int lane;
     template <class F>
     __device__ __forceinline__ void run(F body)
     {
         body(lane);
-        imb_wave_sync();
+        ffhip_wave_sync();
     }
 };
 
-/* four samples: a dword at 8 bits, two above */
-template <typename PIX> struct ImbQuad { typedef uint32_t T; };
-template <> struct ImbQuad<uint16_t> { typedef uint64_t T; };
-template <typename Q>
-__device__ __forceinline__ Q ld_dev(const uint8_t *p)
-{
-    return __hip_atomic_load(reinterpret_cast<const Q *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename Q>
-__device__ __forceinline__ void st_dev(uint8_t *p, Q v)
-{
-    __hip_atomic_store(reinterpret_cast<Q *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 /* the top neighbours of macroblock (mx, my) out of memory, as the lanes hold them: luma columns -4 .. 27 in lanes 0..7, Cb / Cr columns
  * -4 .. 7 in lanes 24..29; what lies outside the picture reads as 0 */
 template <typename Q, int PS>
@@ -68,11 +49,11 @@ __device__ __forceinline__ Q imb_top_from_mem(const uint8_t *py, const uint8_t *
     } else if (lane < 8) {
         const int c = 4 * lane - 4;
         if ((c >= 0 || has_l) && (c < 16 || has_r))
-            v = ld_dev<Q>(py + ((ptrdiff_t)my * 16 - 1) * sy + (mx * 16 + c) * PS);
+            v = ffhip_row_ld<Q>(py + ((ptrdiff_t)my * 16 - 1) * sy + (mx * 16 + c) * PS);
     } else if (lane >= 24 && lane < 30) {
         const int p = (lane - 24) / 3, c = 4 * ((lane - 24) % 3) - 4;
         if (c >= 0 || has_l)
-            v = ld_dev<Q>((p ? pcr : pcb) + ((ptrdiff_t)my * 8 - 1) * sc + (mx * 8 + c) * PS);
+            v = ffhip_row_ld<Q>((p ? pcr : pcb) + ((ptrdiff_t)my * 8 - 1) * sc + (mx * 8 + c) * PS);
     }
     return v;
 }
@@ -110,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
     const FFHipH264IntraMB *const recs = S.pic[blockIdx.y].recs;
     const int32_t *const row_start = S.pic[blockIdx.y].row_start;
     const int16_t *const coefs = S.pic[blockIdx.y].coefs;
-    typedef typename ImbQuad<PIX>::T Q;
+    typedef typename FFHipQuad<PIX>::T Q;
     typedef typename ImbCoef<PIX>::T CF;
     constexpr int PS = (int)sizeof(PIX), NDW = PS == 1 ? 3 : 7, IMB_RUN_MAX = NDW * 128 /* int16 */, WMAX = 4;
     __shared__ __align__(16) ImbTileT<PIX> Ts[WMAX];
@@ -201,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
         fetch_run(r0);
         park(0, r0);
     }
-    imb_wave_sync();
+    ffhip_wave_sync();
     int known = 0;       /* last value seen of the counter of the row above */
     int ahead = 0;       /* from_mem: that counter, read a step ahead (lane 0) */
     int prev_mx = -2;    /* the macroblock this wave reconstructed last: its right columns are still in the tile */
@@ -220,15 +201,13 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
         const FFHipH264IntraMB &R = Rb[cur];
         if (to_mem) {
             /* the previous macroblock's write-through stores left a whole step ago: acknowledged, the counter moves */
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0);
-            if (lane == 0)
-                __hip_atomic_store(&progress[my], mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ffhip_row_publish(&progress[my], mx, lane);
         }
         const uint32_t nrec2 = fetch_rec(k + 2);
         /* ---- the row above has finished macroblock mx + 1 ---- */
         const int want = min(mx + 2, mb_w);
         if (from_lds) {
+            /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
             int spins = 0;
             while (known < want) {
                 known = __hip_atomic_load(&ldone[wv - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -241,16 +220,17 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
                     return;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the neighbour loads are issued after the counter was seen */
         } else if (from_mem && !have_pf) {
             known = max(known, __builtin_amdgcn_readfirstlane(ahead));
+            /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
             int spins = 0;
             while (known < want) {
                 known = __hip_atomic_load(&progress[my - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (known >= want)
                     break;
                 __builtin_amdgcn_s_sleep(2);
-                if (++spins > (1 << 24)) {
+                if (++spins > (1 << 24)) { /* never in a correct run; do not hang the device */
                     if (lane == 0)
                         __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     return;
@@ -285,12 +265,12 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
             else if (left_here)
                 nb = *reinterpret_cast<const Q *>(&T.y[imb_yi(lane - 8, 12)]);
             else if (has_l)
-                nb = ld_dev<Q>(ymb + (ptrdiff_t)(lane - 8) * sy - 4 * PS);
+                nb = ffhip_row_ld<Q>(ymb + (ptrdiff_t)(lane - 8) * sy - 4 * PS);
         } else if (lane >= 30 && lane < 46 && do_c) {
             if (left_here)
                 nb = *reinterpret_cast<const Q *>(&T.c[(lane - 30) >> 3][imb_ci((lane - 30) & 7, 4)]);
             else if (has_l)
-                nb = ld_dev<Q>(cmb0 + (((lane - 30) >> 3) ? cr_off : 0) + (ptrdiff_t)((lane - 30) & 7) * sc - 4 * PS);
+                nb = ffhip_row_ld<Q>(cmb0 + (((lane - 30) >> 3) ? cr_off : 0) + (ptrdiff_t)((lane - 30) & 7) * sc - 4 * PS);
         }
         if (lane < 8) {
             *reinterpret_cast<Q *>(&T.y[imb_yi(-1, 4 * lane - 4)]) = nb;
@@ -304,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
         } else if (lane < 46) {
             *reinterpret_cast<Q *>(&T.c[(lane - 30) >> 3][imb_ci((lane - 30) & 7, -4)]) = nb;
         }
-        imb_wave_sync();
+        ffhip_wave_sync();
         /* the next record's mb_x (read out of the lanes whether or not there is a next record: a load left pending on one path makes the
          * compiler wait for ALL memory operations — the previous macroblock's stores included — at the top of the loop) */
         const int next_x = (int)(__builtin_amdgcn_readlane(nrec, 0) & 0xFFFFu);
@@ -330,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
             if (!do_y)
                 ;
             else if (to_mem)
-                st_dev<Q>(dy, vy);
+                ffhip_row_st<Q>(dy, vy);
             else
                 *reinterpret_cast<Q *>(dy) = vy;
             if (to_lds && (lane >> 2) == 15 && do_y)
@@ -340,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
                 uint8_t *dc = cmb0 + (p ? cr_off : 0) + (ptrdiff_t)r * sc + c * PS;
                 const Q vc = *reinterpret_cast<const Q *>(&T.c[p][imb_ci(r, c)]);
                 if (to_mem)
-                    st_dev<Q>(dc, vc);
+                    ffhip_row_st<Q>(dc, vc);
                 else
                     *reinterpret_cast<Q *>(dc) = vc;
                 if (to_lds && r == 7)
@@ -355,13 +335,10 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
         prev_mx = mx;
         mx = next;
         nrec = nrec2;
-        imb_wave_sync(); /* the other record / run and the tile are rewritten by the next step */
+        ffhip_wave_sync(); /* the other record / run and the tile are rewritten by the next step */
     }
     if (to_mem) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_s_waitcnt(0);
-        if (lane == 0)
-            __hip_atomic_store(&progress[my], mb_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ffhip_row_publish(&progress[my], mb_w, lane);
     }
 }
 
@@ -439,23 +416,16 @@ int ffhip_launch_h264_intra_frames_bd(int bd, int npics, const FFHipIntraPic *pi
         S.n = n;
         for (int i = 0; i < FFHIP_INTRA_PICS; i++)
             S.pic[i] = pics[p0 + (i < n ? i : 0)];
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire((mb_h + 1) * (split ? 2 : 1) * n, stream, &ps);
+        const int r = ffhip_progress_launch((mb_h + 1) * (split ? 2 : 1) * n, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            int *const prog = ps.prog, *const fail = ps.fail;
+            if (bd > 8)
+                hipLaunchKernelGGL(k_h264_intra_frame<uint16_t>, dim3(split ? 2 * nwg : nwg, n), dim3(64 * W), lds, stream, S, sy, sc, mb_w, mb_h, prog, fail, (1 << bd) - 1, luma_only);
+            else
+                hipLaunchKernelGGL(k_h264_intra_frame<uint8_t>, dim3(split ? 2 * nwg : nwg, n), dim3(64 * W), lds, stream, S, sy, sc, mb_w, mb_h, prog, fail, 255, luma_only);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        int *const prog = ps.prog, *const fail = ps.fail;
-        if (bd > 8)
-            hipLaunchKernelGGL(k_h264_intra_frame<uint16_t>, dim3(split ? 2 * nwg : nwg, n), dim3(64 * W), lds, stream, S, sy, sc, mb_w, mb_h, prog, fail, (1 << bd) - 1, luma_only);
-        else
-            hipLaunchKernelGGL(k_h264_intra_frame<uint8_t>, dim3(split ? 2 * nwg : nwg, n), dim3(64 * W), lds, stream, S, sy, sc, mb_w, mb_h, prog, fail, 255, luma_only);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_hevc_idct(int kind, int16_t *coeffs, ui
             }
         }
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     int16_t *mine = blk + ul * N * N;
     if (kind == FFHIP_HEVC_IDCT) {
         const int limit = min(tu.col_limit, N);
@@ -70,18 +70,18 @@ __global__ __launch_bounds__(256) void k_hevc_idct(int kind, int16_t *coeffs, ui
             if (limit2 < N)
                 limit2 -= 4;
         hevc_pass<N>(mine + i, N, mine + i, N, limit2, 7, hevc_pk);
-        hevc_wave_sync();
+        ffhip_wave_sync();
         hevc_pass<N>(mine + i * N, 1, mine + i * N, 1, limit, 20 - bd, hevc_pk);
     } else if (kind == FFHIP_HEVC_IDCT_DC) {
         const int v = ((((int)mine[0] + 1) >> 1) + (1 << (13 - bd))) >> (14 - bd);
-        hevc_wave_sync();
+        ffhip_wave_sync();
 #pragma unroll
         for (int k = 0; k < N; k++)
             mine[i * N + k] = (int16_t)v;
     } else if (kind == FFHIP_HEVC_DST_4X4) {
         if (N == 4) {
             hevc_dst4(mine + i, mine + i, 4, 7);
-            hevc_wave_sync();
+            ffhip_wave_sync();
             hevc_dst4(mine + 4 * i, mine + 4 * i, 1, 20 - bd);
         }
     } else if (kind == FFHIP_HEVC_DEQUANT) {
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_hevc_idct(int kind, int16_t *coeffs, ui
             v[k * step] = (int16_t)acc;
         }
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     /* ---- residual back in place; picture += residual (row i of my unit) ---- */
     if (kind != FFHIP_HEVC_ADD_ONLY) {
         for (int t = lane; t < UPW * Q4; t += 64) {
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void k_hevc_idct32_mfma(int16_t *coeffs, uint8
         for (int k = 0; k < 8; k++)
             reinterpret_cast<uint32_t *>(L + rr * 32 + 16 * rh)[k] = reinterpret_cast<const uint32_t *>(rowp)[k];
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     hevc_idct32_mfma_lds(lds, wave, col_limit, bd, tab, lane);
     const uint4 r0 = reinterpret_cast<const uint4 *>(L + rr * 32 + 16 * rh)[0], r1 = reinterpret_cast<const uint4 *>(L + rr * 32 + 16 * rh)[1];
     const uint32_t rw[8] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w };
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void k_hevc_idct16_mfma(int16_t *coeffs, uint8
         }
         *reinterpret_cast<uint4 *>(L + rb * 256 + rr * 16 + 8 * rh) = raw;
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     /* column view: my unit, my column (pass 1) / row (pass 2) / column (output) */
     const int cp = lane & 31, g = lane >> 5, b = cp >> 4, c = cp & 15;
     const hm_i4 B1 = reinterpret_cast<const hm_i4 *>(tab->b1)[lane], B2 = reinterpret_cast<const hm_i4 *>(tab->b2)[lane];
@@ -297,13 +297,13 @@ __global__ __launch_bounds__(256) void k_hevc_idct16_mfma(int16_t *coeffs, uint8
         acc[r] = (int)(((uint32_t)acc[r] << 8) + (uint32_t)(sum_t + (1 << (shift2 - 1))));
     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(alo, B2, acc, 0, 0, 0);
     /* ---- Z_b[j][m = c], j = (r & 3) + 8 ((r >> 2) & 1) + 4 g for r = 8 b .. 8 b + 7: back through LDS into rows ---- */
-    hevc_wave_sync(); /* every lane has read its inputs */
+    ffhip_wave_sync(); /* every lane has read its inputs */
 #pragma unroll
     for (int t = 0; t < 8; t++) {
         const int j = (t & 3) + 8 * (t >> 2) + 4 * g;
         L[b * 256 + j * 16 + c] = (int16_t)hevc_clip16((b ? acc[8 + t] : acc[t]) >> shift2);
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     if (!rlive)
         return;
     const uint4 res = *reinterpret_cast<const uint4 *>(L + rb * 256 + rr * 16 + 8 * rh);

@@ -45,13 +45,6 @@ constexpr int ROWS = 64 + 7;        /* rows of the horizontal pass: h + TAPS - 1
 
 enum { M_PUT = 0, M_UNI = 1, M_UNI_W = 2, M_BI = 3, M_BI_W = 4 };
 
-__device__ __forceinline__ void hip_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* one list of one block: the reference plane (clamped to rw x rh samples), the block's integer origin in it and its phases */
 struct HipSrc {
     const uint8_t *base;
@@ -91,7 +84,7 @@ __device__ __forceinline__ void hip_predict(int16_t *tile, int16_t *tmp, const H
                 acc += hf[t] * hip_ref<PIX>(s, s.xi + x + t - B, s.yi + r - B);
             tmp[r * TILE + x] = (int16_t)(acc >> sh1);
         }
-        hip_wave_sync();
+        ffhip_wave_sync();
     }
     const int wsh = denom + shu; /* uni_w: shift; bi_w: log2Wd */
     for (int i = lane; i < bw * bh; i += 64) {
@@ -131,7 +124,7 @@ __device__ __forceinline__ void hip_predict(int16_t *tile, int16_t *tmp, const H
         }
         d = (int16_t)min(max(out, 0), maxv);
     }
-    hip_wave_sync(); /* tmp is reused by the next pass */
+    ffhip_wave_sync(); /* tmp is reused by the next pass */
 }
 } // namespace
 
@@ -294,28 +287,21 @@ int ffhip_launch_hevc_inter_pictures(int bd, int cfi, int width, int height, int
         /* the pictures (their DPB tables included) go to the device in stream order: a progress-pool slot is device memory that is
          * not handed out again before the launch behind it has finished, and the copy from pageable memory is staged by the time
          * hipMemcpyAsync returns */
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(0, stream, &ps);
-        if (r < 0)
-            return r;
-        FFHipHevcInterPic *dpics = reinterpret_cast<FFHipHevcInterPic *>(ps.prog);
-        hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipHevcInterPic), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) {
+        const int r = ffhip_progress_launch(0, stream, "ffhip_hevc_inter_pictures_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
+            FFHipHevcInterPic *dpics = reinterpret_cast<FFHipHevcInterPic *>(ps.prog);
+            const hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipHevcInterPic), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess)
+                return e;
             if (bd > 8)
                 hipLaunchKernelGGL(k_hevc_inter_pic<uint16_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    ctb_w, bd);
             else
                 hipLaunchKernelGGL(k_hevc_inter_pic<uint8_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    ctb_w, 8);
-            e = hipGetLastError();
-        }
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_hevc_inter_pictures_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
+            return hipGetLastError();
+        });
+        if (r < 0)
+            return r;
     }
     return 0;
 }

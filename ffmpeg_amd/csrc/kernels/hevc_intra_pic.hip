@@ -15,19 +15,13 @@
  * the rules of hevc_intra_rules.h (shared with k_hevc_intra), predicts, adds its residual, clips, and writes the result to the tile
  * and to the plane — only the samples of its own block, so what no record covers is never written.
  *
- * Hand-off between rows (cdna_hip_programming Guideline 16, the protocol of k_h264_intra_frame): every sample store is an agent-scope
- * relaxed store (write-through to L2: the 8 XCDs' L2s are not coherent with each other), the wave waits for all of them to be
- * acknowledged (s_waitcnt 0) before it moves its row's counter with an agent-scope store, and the consumer polls that counter with
- * agent-scope loads and reads the bottom line with agent-scope loads issued after the poll (they bypass the CU's L1).  What else a wave
- * loads (records, residuals, its own CTB, the left column of a CTB without records) nobody writes in this launch.
- *
- * Dispatch order: the same assumption k_h264_intra_frame makes — workgroups are dispatched in order of their linear id (x fastest),
- * so the row a wave waits for (blockIdx.x - 1, same blockIdx.y) was dispatched before it and runs to completion whatever waits behind
- * it.  Every spin is bounded; on a timeout the wave sets the progress slot's fail word and leaves.
+ * Hand-off between rows: row_handoff.h, lag 1 (CTB x reads the top-right CTB x + 1 of the row above), rows mapped to workgroups by
+ * blockIdx: the row a wave waits for (blockIdx.x - 1, same blockIdx.y) was dispatched before it.
  */
 #include <stddef.h>
 
 #include "hevc_intra_rules.h"
+#include "row_handoff.h"
 
 static_assert(sizeof(FFHipHevcIntraTU) == 16, "FFHipHevcIntraTU is a 16-byte record");
 
@@ -39,26 +33,6 @@ struct HipPicSet {
     FFHipHevcIntraPic pic[HIP_PICS];
 };
 
-__device__ __forceinline__ void hip_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-/* four samples: a dword at 8 bits, two above */
-template <typename PIX> struct HipQuad { typedef uint32_t T; };
-template <> struct HipQuad<uint16_t> { typedef uint64_t T; };
-template <typename Q>
-__device__ __forceinline__ Q ld_dev(const uint8_t *p)
-{
-    return __hip_atomic_load(reinterpret_cast<const Q *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename Q>
-__device__ __forceinline__ void st_dev(uint8_t *p, Q v)
-{
-    __hip_atomic_store(reinterpret_cast<Q *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 template <typename PIX, typename Q>
 __device__ __forceinline__ void quad_to_tile(uint16_t *t, Q q)
 {
@@ -73,7 +47,7 @@ template <typename PIX>
 __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes, int cfi, int width, int height, int log2_ctb, int ctb_w,
                                                        int ctb_h, int *progress_all, int *fail, int bd)
 {
-    typedef typename HipQuad<PIX>::T Q;
+    typedef typename FFHipQuad<PIX>::T Q;
     constexpr int PS = (int)sizeof(PIX);
     __shared__ uint16_t T[HIP_TILE];
     __shared__ int S0[HI_LINE], S1[HI_LINE];
@@ -95,7 +69,7 @@ __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes,
 
     for (int i = lane; i < (Ch + 1) * TP; i += 64)
         T[i] = 0;
-    hip_wave_sync();
+    ffhip_wave_sync();
     int known = 0;          /* last value seen of the counter of the row above */
     bool have_left = false; /* column -1 of the next CTB is column Cw - 1 of the tile */
     for (int cx = 0; cx < ctb_w; cx++) {
@@ -111,7 +85,7 @@ __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes,
                 for (int r = lane; r < Ch && cy0 + r < ph; r += 64)
                     T[TI(r, -1)] = *reinterpret_cast<const PIX *>(base + (ptrdiff_t)(cy0 + r) * stride + (cx0 - 1) * PS);
             }
-            hip_wave_sync();
+            ffhip_wave_sync();
             /* ---- the CTB as the plane holds it, clipped to the picture ---- */
             const int qw = Cw >> 2;
             for (int i = lane; i < Ch * qw; i += 64) {
@@ -122,6 +96,7 @@ __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes,
             /* ---- the row above has finished CTB cx + 1 ---- */
             if (row > 0) {
                 const int want = min(cx + 2, ctb_w);
+                /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
                 int spins = 0;
                 while (known < want) {
                     known = __hip_atomic_load(&progress[-1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -134,18 +109,18 @@ __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes,
                         return;
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the line's loads are issued after the counter was seen */
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the neighbour loads are issued after the counter was seen */
                 /* row -1, columns -4 .. 2Cw - 1 in quads (column -1 is the last sample of the first); widths are multiples of 4 */
                 const int c = 4 * lane - 4;
                 if (lane <= 2 * qw && cx0 + c >= 0 && cx0 + c < pw) {
-                    const Q q = ld_dev<Q>(base + (ptrdiff_t)(cy0 - 1) * stride + (cx0 + c) * PS);
+                    const Q q = ffhip_row_ld<Q>(base + (ptrdiff_t)(cy0 - 1) * stride + (cx0 + c) * PS);
                     if (c < 0)
                         T[TI(-1, -1)] = (PIX)(q >> (3 * 8 * PS));
                     else
                         quad_to_tile<PIX>(&T[TI(-1, c)], q);
                 }
             }
-            hip_wave_sync();
+            ffhip_wave_sync();
 
             /* ---- the CTB's blocks in decoding order ---- */
             FFHipHevcIntraTU nx = tus[k0];
@@ -180,10 +155,10 @@ __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes,
                         v = s < n2 ? T[TI(min(ly + n2 - 1 - s, Ch - 1), lx - 1)] : s == n2 ? T[TI(ly - 1, lx - 1)] : T[TI(ly - 1, lx + s - n2 - 1)];
                     S0[i] = v;
                 }
-                hip_wave_sync();
+                ffhip_wave_sync();
                 /* 2. filtering (8.4.4.2.3) */
                 hi_filter_line(S0, S1, lane, N, log2, mode, cidx, true, R.flags, bd);
-                hip_wave_sync();
+                ffhip_wave_sync();
                 /* 3. prediction + residual, clipped: lane = 4 samples of one row, into the tile and the plane */
                 const int dc = mode == 1 ? hi_dc(S1, N, log2) : 0;
 #pragma unroll
@@ -198,10 +173,10 @@ __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes,
                             T[TI(ly + y, lx + xq + e)] = (uint16_t)v;
                             q |= (Q)v << (e * 8 * PS);
                         }
-                        st_dev<Q>(base + (ptrdiff_t)(y0 + y) * stride + (x0 + xq) * PS, q);
+                        ffhip_row_st<Q>(base + (ptrdiff_t)(y0 + y) * stride + (x0 + xq) * PS, q);
                     }
                 }
-                hip_wave_sync(); /* S0 / S1 and the tile are read by the next block */
+                ffhip_wave_sync(); /* S0 / S1 and the tile are read by the next block */
             }
             have_left = true;
         } else {
@@ -209,10 +184,7 @@ __global__ __launch_bounds__(64) void k_hevc_intra_pic(HipPicSet S, int nplanes,
         }
         /* ---- CTB cx is done: its stores are acknowledged, then the counter moves ---- */
         if (publish) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0);
-            if (lane == 0)
-                __hip_atomic_store(&progress[0], cx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ffhip_row_publish(&progress[0], cx + 1, lane);
         }
     }
 #undef TI
@@ -230,24 +202,17 @@ int ffhip_launch_hevc_intra_pictures(int bd, int cfi, int width, int height, int
         HipPicSet S;
         for (int i = 0; i < HIP_PICS; i++)
             S.pic[i] = pics[p0 + (i < n ? i : 0)];
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(rows * n, stream, &ps);
+        const int r = ffhip_progress_launch(rows * n, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            if (bd > 8)
+                hipLaunchKernelGGL(k_hevc_intra_pic<uint16_t>, dim3(rows, n), dim3(64), 0, stream, S, nplanes, cfi, width, height, log2_ctb, ctb_w, ctb_h,
+                                   ps.prog, ps.fail, bd);
+            else
+                hipLaunchKernelGGL(k_hevc_intra_pic<uint8_t>, dim3(rows, n), dim3(64), 0, stream, S, nplanes, cfi, width, height, log2_ctb, ctb_w, ctb_h,
+                                   ps.prog, ps.fail, 8);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        if (bd > 8)
-            hipLaunchKernelGGL(k_hevc_intra_pic<uint16_t>, dim3(rows, n), dim3(64), 0, stream, S, nplanes, cfi, width, height, log2_ctb, ctb_w, ctb_h,
-                               ps.prog, ps.fail, bd);
-        else
-            hipLaunchKernelGGL(k_hevc_intra_pic<uint8_t>, dim3(rows, n), dim3(64), 0, stream, S, nplanes, cfi, width, height, log2_ctb, ctb_w, ctb_h,
-                               ps.prog, ps.fail, 8);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

@@ -260,28 +260,21 @@ int ffhip_launch_hevc_loop_filter_pictures(int bd, int cfi, int width, int heigh
     for (int p0 = 0; p0 < npics; p0 += HLP_PICS) {
         const int n = npics - p0 < HLP_PICS ? npics - p0 : HLP_PICS;
         /* the pictures go to the device in stream order through a progress-pool slot, as the inter picture face stages them */
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(0, stream, &ps);
-        if (r < 0)
-            return r;
-        FFHipHevcLfPic *dpics = reinterpret_cast<FFHipHevcLfPic *>(ps.prog);
-        hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipHevcLfPic), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) {
+        const int r = ffhip_progress_launch(0, stream, "ffhip_hevc_loop_filter_pictures_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
+            FFHipHevcLfPic *dpics = reinterpret_cast<FFHipHevcLfPic *>(ps.prog);
+            const hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipHevcLfPic), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess)
+                return e;
             if (bd > 8)
                 hipLaunchKernelGGL(k_hevc_lf_pic<uint16_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    log2_min_cb, ctb_w, ctb_h, bd);
             else
                 hipLaunchKernelGGL(k_hevc_lf_pic<uint8_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    log2_min_cb, ctb_w, ctb_h, 8);
-            e = hipGetLastError();
-        }
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_hevc_loop_filter_pictures_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
+            return hipGetLastError();
+        });
+        if (r < 0)
+            return r;
     }
     return 0;
 }

@@ -22,13 +22,6 @@
 
 typedef short mc_s2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void hevc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 static_assert(sizeof(FFHipHevcMcBlock) == 12, "FFHipHevcMcBlock is a 12-byte record");
 /* 16-byte aligned: the tuned kernel reads a row of taps as one or two dwords (scalar loads) */
 __constant__ __attribute__((aligned(16))) int8_t hevc_lf8[4][8] = { { 0 }, { -1, 4, -10, 58, 17, -5, 1, 0 }, { -1, 4, -11, 40, 40, -11, 4, -1 }, { 0, 1, -5, 17, 58, -10, 4, -1 } };
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(256) void k_hevc_mc(void *dst_, ptrdiff_t dststride
             int16_t *t16 = reinterpret_cast<int16_t *>(tmp + (r >> 1) * MC_PITCH + 4 * xg) + (r & 1);
             t16[0] = (int16_t)o[0]; t16[2] = (int16_t)o[1]; t16[4] = (int16_t)o[2]; t16[6] = (int16_t)o[3];
         }
-        hevc_wave_sync();
+        ffhip_wave_sync();
         for (int i = lane; i < h * ngt; i += 64) {
             const int y = (i * invt) >> 16, xg = i - y * ngt;
             const uint4 *t = reinterpret_cast<const uint4 *>(tmp + (y >> 1) * MC_PITCH + 4 * xg);
@@ -238,7 +231,7 @@ __global__ __launch_bounds__(256) void k_hevc_mc(void *dst_, ptrdiff_t dststride
             }
             emit(y, tx + 4 * xg, acc);
         }
-        hevc_wave_sync(); /* the next tile overwrites the plane */
+        ffhip_wave_sync(); /* the next tile overwrites the plane */
       }
     } else {
         for (int i = lane; i < h * ng; i += 64) {
@@ -255,7 +248,7 @@ __global__ __launch_bounds__(256) void k_hevc_mc(void *dst_, ptrdiff_t dststride
         }
     }
     if (SKIP16)
-        hevc_wave_sync(); /* the next block reuses the plane */
+        ffhip_wave_sync(); /* the next block reuses the plane */
     }
     }
 }
@@ -313,7 +306,7 @@ __global__ __launch_bounds__(256) void k_hevc_mc_s(void *dst_, ptrdiff_t dststri
                 acc += hf[t] * p[t];
             tmp[r * 64 + x] = (int16_t)(acc >> sh1);
         }
-        hevc_wave_sync();
+        ffhip_wave_sync();
     }
     for (int i = lane; i < w * h; i += 64) {
         const int y = i / w, x = i - y * w;

@@ -82,12 +82,12 @@ __device__ __forceinline__ void hrp_unit(int16_t *mine, int i, bool act, int kin
 #pragma unroll
         for (int x = 0; x < 4; x++)
             r[x] = mine[(3 - i) * 4 + 3 - x];
-        hevc_wave_sync();
+        ffhip_wave_sync();
 #pragma unroll
         for (int x = 0; x < 4; x++)
             mine[i * 4 + x] = (int16_t)r[x];
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     if (N < 32 && act && kind == FFHIP_HEVC_RES_DCT) {
         const int limit = min(col_limit, N);
         int limit2 = min(col_limit + 4, N); /* shrunk by 4 for every column 4, 8, ... before mine while it was < N */
@@ -95,17 +95,17 @@ __device__ __forceinline__ void hrp_unit(int16_t *mine, int i, bool act, int kin
             if (limit2 < N)
                 limit2 -= 4;
         hevc_pass<N < 32 ? N : 16>(mine + i, N, mine + i, N, limit2, 7, hevc_res_pk);
-        hevc_wave_sync();
+        ffhip_wave_sync();
         hevc_pass<N < 32 ? N : 16>(mine + i * N, 1, mine + i * N, 1, limit, 20 - bd, hevc_res_pk);
     } else if (act && kind == FFHIP_HEVC_RES_DC) {
         const int v = ((((int)mine[0] + 1) >> 1) + (1 << (13 - bd))) >> (14 - bd);
-        hevc_wave_sync();
+        ffhip_wave_sync();
 #pragma unroll
         for (int k = 0; k < N; k++)
             mine[i * N + k] = (int16_t)v;
     } else if (N == 4 && act && kind == FFHIP_HEVC_RES_DST) {
         hevc_dst4(mine + i, mine + i, 4, 7);
-        hevc_wave_sync();
+        ffhip_wave_sync();
         hevc_dst4(mine + 4 * i, mine + 4 * i, 1, 20 - bd);
     } else if (act && kind == FFHIP_HEVC_RES_SKIP) {
         /* dequant (hevc/dsp_template.c:110-143), row i: as k_hevc_idct's DEQUANT */
@@ -116,7 +116,7 @@ __device__ __forceinline__ void hrp_unit(int16_t *mine, int i, bool act, int kin
             mine[i * N + k] = (int16_t)(shift > 0 ? (c + (1 << (shift - 1))) >> shift : shift < 0 ? (int)((uint32_t)(uint16_t)c << -shift) : c);
         }
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     if (act && (kf & (FFHIP_HEVC_RES_RDPCM_H | FFHIP_HEVC_RES_RDPCM_V))) {
         /* transform_rdpcm (hevc/dsp_template.c:85-105): running sums in int16 along row i (mode 0) or down column i (mode 1) */
         const bool h = kf & FFHIP_HEVC_RES_RDPCM_H;
@@ -129,7 +129,7 @@ __device__ __forceinline__ void hrp_unit(int16_t *mine, int i, bool act, int kin
             v[k * step] = (int16_t)acc;
         }
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
 }
 
 /* the wave's units of one segment: UPW units of N lanes (one unit of 64 lanes at 32x32) */
@@ -179,7 +179,7 @@ __device__ __forceinline__ void hrp_wave(const HrpSeg &S, int unit0, int16_t (*l
                 reinterpret_cast<uint4 *>(blkl)[q] = lv;
         }
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     int16_t *mine = blk + ul * N * N, *lmine = blkl + ul * N * N;
     if (N == 32) { /* one unit per wave: the record is wave-uniform */
         if (__builtin_amdgcn_readfirstlane(ok ? kind : -1) == FFHIP_HEVC_RES_DCT)
@@ -197,7 +197,7 @@ __device__ __forceinline__ void hrp_wave(const HrpSeg &S, int unit0, int16_t (*l
         for (int k = 0; k < N; k++)
             mine[i * N + k] = (int16_t)(mine[i * N + k] + ((sc * (int)lmine[i * N + k]) >> 3));
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
     /* ---- the residuals of the well-formed units ---- */
     for (int it = 0; it < ITER; it++) {
         const int q = lane + 64 * it, b = min(q / Q4, UPW - 1), w = q % Q4;
@@ -280,23 +280,16 @@ int ffhip_launch_hevc_residual_pictures(int bd, int cfi, int npics, const FFHipH
         }
         /* the segment table goes to the device in stream order: a progress-pool slot is device memory that is not handed out again
          * before the launch behind it has finished, and the copy from pageable memory is staged by the time hipMemcpyAsync returns */
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(0, stream, &ps);
+        const int r = ffhip_progress_launch(0, stream, "ffhip_hevc_residual_pictures_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
+            HrpSeg *dsegs = reinterpret_cast<HrpSeg *>(ps.prog);
+            const hipError_t e = hipMemcpyAsync(dsegs, segs, (size_t)nsegs * sizeof(HrpSeg), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess)
+                return e;
+            hipLaunchKernelGGL(k_hevc_res_pic, dim3((unsigned)blocks), dim3(256), 0, stream, dsegs, nsegs, bd, tab);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        HrpSeg *dsegs = reinterpret_cast<HrpSeg *>(ps.prog);
-        hipError_t e = hipMemcpyAsync(dsegs, segs, (size_t)nsegs * sizeof(HrpSeg), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_hevc_res_pic, dim3((unsigned)blocks), dim3(256), 0, stream, dsegs, nsegs, bd, tab);
-            e = hipGetLastError();
-        }
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_hevc_residual_pictures_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

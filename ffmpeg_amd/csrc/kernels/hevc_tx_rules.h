@@ -106,13 +106,6 @@ __device__ __forceinline__ void hevc_dst4(int16_t *dst, const int16_t *src, int 
     dst[3 * step] = (int16_t)hevc_clip16((55 * c0 + 29 * c2 - c3 + add) >> shift);
 }
 
-__device__ __forceinline__ void hevc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 typedef int hm_i4 __attribute__((ext_vector_type(4)));
 typedef int hm_i16 __attribute__((ext_vector_type(16)));
 struct HevcMfmaTab { int8_t b1[64][16], b2[64][16]; int32_t sum[32]; }; /* sum[j] = 128 * sum_k T[k][j] */
@@ -181,13 +174,13 @@ __device__ __forceinline__ void hevc_idct32_mfma_lds(int16_t (*lds)[1024], int w
         acc[r] = (int)(((uint32_t)acc[r] << 8) + (uint32_t)(sum_t + (1 << (shift2 - 1))));
     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(alo, B2, acc, 0, 0, 0);
     /* ---- Z[j][m = c], j = (r & 3) + 8 (r >> 2) + 4 g: back through LDS into rows; residual in place, picture += residual ---- */
-    hevc_wave_sync(); /* every lane has read its inputs */
+    ffhip_wave_sync(); /* every lane has read its inputs */
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int j = (r & 3) + 8 * (r >> 2) + 4 * g;
         L[j * 32 + c] = (int16_t)hevc_clip16(acc[r] >> shift2);
     }
-    hevc_wave_sync();
+    ffhip_wave_sync();
 }
 
 /* the host tables are built once; their device copies (the includer's __constant__ table image and the two MFMA operand tables)

@@ -230,14 +230,6 @@ __device__ __forceinline__ uint32_t me_satd8_cols(const uint4 *va, const uint4 *
     return acc;
 }
 
-/* a wave's LDS operations execute in order and the waves of a workgroup share nothing: no barrier */
-__device__ __forceinline__ void me_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* WPB independent waves (macroblocks bx .. bx + WPB - 1 of a row) per workgroup: a CU holds only about 16 workgroups whatever
  * their size, so one-wave workgroups leave half of its 32 wave slots empty (measured: 4.5 waves per SIMD) */
 template <int KIND, int MB, bool SHARE = false, int QUAD = 0, int WPB = 1>
@@ -293,7 +285,7 @@ __global__ __launch_bounds__(64 * WPB) void k_me_esa(const uint8_t *cur, const u
             }
         }
     }
-    me_wave_sync();
+    ffhip_wave_sync();
     /* SATD with SHARED column transforms: the vertical Hadamard of a window column segment (8 rows) serves the 8
      * candidates that contain it, so it is computed once per macroblock into LDS — va: the current block's columns
      * per 8-row band, vb[r][c]: window column c, rows r..r+7 */
@@ -312,7 +304,7 @@ __global__ __launch_bounds__(64 * WPB) void k_me_esa(const uint8_t *cur, const u
             const int r = i / wcols, c = i - r * wcols;
             vb[i] = me_hadamard_col(win + r * pitch + c, pitch);
         }
-        me_wave_sync();
+        ffhip_wave_sync();
     }
 
     uint32_t best = 0xFFFFFFFFu, best_ci = 0xFFFFFFFFu, cost0 = 0;

@@ -59,13 +59,6 @@ __device__ const MsHadTab ms_had_tab = ms_had_make();
 
 #define MS_BIAS (1 << 20)
 
-__device__ __forceinline__ void ms_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /*
  * 16 MFMAs (operand B q with the accumulator inputs c[4q .. 4q + 3]) and the absolute sums of their 16 x 4 results: sum q receives
  * B q's.  Product k lands in quartet k & 3 of v[112:127]; its sums are issued behind MFMA k + 3.
@@ -289,7 +282,7 @@ __global__ __launch_bounds__(64 * WPB) void k_me_esa_satd_mx(const uint8_t *cur,
             }
         }
     }
-    ms_wave_sync();
+    ffhip_wave_sync();
 
     ms_i4 A[4];
 #pragma unroll
@@ -351,7 +344,7 @@ __global__ __launch_bounds__(64 * WPB) void k_me_esa_satd_mx(const uint8_t *cur,
                 __hip_atomic_fetch_add(pc + 16 * k, s[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    ms_wave_sync();
+    ffhip_wave_sync();
 
     /* the winner: smaller cost, then smaller raster index; the zero vector unless a candidate is strictly cheaper */
     const int ci0 = (y_mb - y0) * ncx + (x_mb - x0);

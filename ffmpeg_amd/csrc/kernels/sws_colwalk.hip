@@ -535,13 +535,6 @@ __device__ __forceinline__ void cw_hgroup(uint32_t (&Pnew)[4], int (&hprev)[4], 
     }
 }
 
-__device__ __forceinline__ void cw_wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* LUT (round 4): the chroma part of the closed form — 23 VALU instructions per chroma sample and output row, a third of the kernel — is
  * a function of one byte per term: r(V), b(U), g = gu(U) + gv(V) (the products distribute over the sum exactly in wrapping int32
  * arithmetic).  The workgroup builds the four 256-entry tables in 4 KB of LDS once (one entry per thread) and a sample costs two
@@ -773,7 +766,7 @@ __global__ __launch_bounds__(256) void k_sws_colwalk_rgb(FFHipCwRgbArgs A)
             *reinterpret_cast<uint2 *>(t) = make_uint2(w[0], w[1]);
             *reinterpret_cast<uint2 *>(t + 2) = make_uint2(w[2], w[3]);
             *reinterpret_cast<uint2 *>(t + 4) = make_uint2(w[4], w[5]);
-            cw_wave_sync_lds();
+            ffhip_wave_sync();
             cw_gptr d = (cw_gptr)dr + cw_opaque(tcol);
 #pragma unroll
             for (int i = 0; i < 3; i++) {
@@ -785,7 +778,7 @@ __global__ __launch_bounds__(256) void k_sws_colwalk_rgb(FFHipCwRgbArgs A)
                     else *(cw_g2)(d + i * 512) = s;
                 }
             }
-            cw_wave_sync_lds();
+            ffhip_wave_sync();
         } else if (act) {
             cw_gptr d = (cw_gptr)dr + cw_opaque(dcol);
             cw_u2 s;

@@ -80,13 +80,6 @@ __device__ __forceinline__ int er_mad24(int a, int b, int c)
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
     return r;
 }
-__device__ __forceinline__ void er_wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 struct ErRawC { uint32_t q[2]; };                 /* SIL: 4 (u, v) pairs; planar: q[0] = 4 U, q[1] = 4 V */
 struct ErRawY { uint32_t q[2]; };                 /* 8 luma bytes */
 
@@ -261,7 +254,7 @@ __global__ __launch_bounds__(256, 4) void k_sws_eq_rgb(FFHipEqRgbArgs A)
             *reinterpret_cast<uint2 *>(t + 2) = make_uint2(w[2], w[3]);
             *reinterpret_cast<uint2 *>(t + 4) = make_uint2(w[4], w[5]);
         }
-        er_wave_sync_lds();
+        ffhip_wave_sync();
         const uint4 q0 = *reinterpret_cast<const uint4 *>(tile + lane * 4);
         uint4 q1 = make_uint4(0, 0, 0, 0);
         uint2 q2 = make_uint2(0, 0);
@@ -269,7 +262,7 @@ __global__ __launch_bounds__(256, 4) void k_sws_eq_rgb(FFHipEqRgbArgs A)
             q1 = *reinterpret_cast<const uint4 *>(tile + 256 + lane * 4);
         else
             q2 = *reinterpret_cast<const uint2 *>(tile + 256 + lane * 2);
-        er_wave_sync_lds();
+        ffhip_wave_sync();
         if (store) { /* uniform */
             er_gp d = (er_gp)dr;
             er_u4 v0, v1;

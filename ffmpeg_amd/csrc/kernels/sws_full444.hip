@@ -41,13 +41,6 @@ __device__ __forceinline__ uint32_t f4_pk4(int a, int b, int c, int d)
         : "=&v"(r) : "v"(a), "v"(b), "v"(c), "v"(d));
     return r;
 }
-__device__ __forceinline__ void f4_wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* LAY: 0 rgb24, 1 bgr24, 2 argb, 3 rgba, 4 abgr, 5 bgra (alpha = 255) */
 template <int LAY>
 __global__ __launch_bounds__(256) void k_yuv444_rgb_full(FFHipFull444Args A)
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(256) void k_yuv444_rgb_full(FFHipFull444Args A)
 #pragma unroll
     for (int i = 0; i < NW / 2; i++)
         *reinterpret_cast<uint2 *>(t + 2 * i) = make_uint2(w[2 * i], w[2 * i + 1]);
-    f4_wave_sync_lds();
+    ffhip_wave_sync();
     const int nbytes = (NW / 2) * min(A.w - cb * 512, 512); /* valid bytes of the segment: 3 or 4 per pixel */
     uint8_t *pd = A.dst + (size_t)f * A.dfp + (ptrdiff_t)row * A.dstride;
     f4_gp d = (f4_gp)pd + (uint32_t)(NW * 256) * (uint32_t)cb + 8u * (uint32_t)lane;

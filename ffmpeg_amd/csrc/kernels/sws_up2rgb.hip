@@ -164,13 +164,6 @@ __device__ __forceinline__ int ur_mad24(int a, int b, int c)
     return r;
 }
 
-__device__ __forceinline__ void ur_wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 struct UrRawL { uint32_t q[3]; };
 struct UrRawC { uint32_t u[2], v[2]; };
 
@@ -520,12 +513,12 @@ __global__ __launch_bounds__(256, 4) void k_sws_up2_rgb(FFHipUp2RgbArgs A)
         /* transpose through the wave's 1.5 / 2 KiB of LDS: a store instruction covers 512 (ST 1) or 1024 (ST 2) contiguous bytes of
          * the row instead of 8 / 16 bytes in every 24 / 32 */
         tile_write(w);
-        ur_wave_sync_lds();
+        ffhip_wave_sync();
         if (ST == 2) {
             uint4 q0, q1;
             uint2 q2;
             tile_read(q0, q1, q2);
-            ur_wave_sync_lds();
+            ffhip_wave_sync();
             if (store) /* uniform */
                 put_pieces(dr, q0, q1, q2);
         } else {
@@ -533,7 +526,7 @@ __global__ __launch_bounds__(256, 4) void k_sws_up2_rgb(FFHipUp2RgbArgs A)
 #pragma unroll
             for (int i = 0; i < NW / 2; i++)
                 q[i] = *reinterpret_cast<const uint2 *>(tile + i * 128 + lane * 2);
-            ur_wave_sync_lds();
+            ffhip_wave_sync();
             if (store) {
                 ur_gp d = (ur_gp)dr;
 #pragma unroll

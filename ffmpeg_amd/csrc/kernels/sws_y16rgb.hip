@@ -44,13 +44,6 @@ __device__ __forceinline__ uint32_t yr_pk4(int a, int b, int c, int d)
         : "=&v"(r) : "v"(a), "v"(b), "v"(c), "v"(d));
     return r;
 }
-__device__ __forceinline__ void yr_wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* LAY: 0 rgb24, 1 bgr24, 2 argb, 3 rgba, 4 abgr, 5 bgra (alpha = 255).  A wave = 64 lanes x 8 pixels of one row. */
 /* UVI: the chroma samples arrive as ONE plane of (u, v) byte pairs (the exact-2:1 first stage writes them that way, sws_down2.hip) */
 template <int LAY, bool UVI = false>
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(256) void k_y16_rgb(FFHipY16RgbArgs A)
 #pragma unroll
     for (int i = 0; i < NW / 2; i++)
         *reinterpret_cast<uint2 *>(t + 2 * i) = make_uint2(w[2 * i], w[2 * i + 1]);
-    yr_wave_sync_lds();
+    ffhip_wave_sync();
     const int nbytes = (NW / 2) * min(A.w - cb * 512, 512); /* valid bytes of the segment: 3 or 4 per pixel */
     yr_gp d = (yr_gp)pd + (uint32_t)(NW * 256) * (uint32_t)cb + 8u * (uint32_t)lane;
 #pragma unroll

@@ -137,13 +137,6 @@ __device__ __forceinline__ uint32_t pk16(int a, int b)
     return r;
 }
 
-__device__ __forceinline__ void wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <bool BGR, bool PLAIN, bool NTS = true, bool NTL = false>
 __global__ __launch_bounds__(256) void k_yuv420p_rgb24_t(FFHipYuv2RgbArgs a)
 {
@@ -252,7 +245,7 @@ __global__ __launch_bounds__(256) void k_yuv420p_rgb24_t(FFHipYuv2RgbArgs a)
             my[3 * lane + 1] = make_uint4(o[4], o[5], o[6], o[7]);
             my[3 * lane + 2] = make_uint4(o[8], o[9], o[10], o[11]);
         }
-        wave_sync_lds();
+        ffhip_wave_sync();
         uint8_t *drow = (row ? d1 : d0) + run;
 #pragma unroll
         for (int j = 0; j < 3; j++) {
@@ -269,7 +262,7 @@ __global__ __launch_bounds__(256) void k_yuv420p_rgb24_t(FFHipYuv2RgbArgs a)
                 }
             }
         }
-        wave_sync_lds();
+        ffhip_wave_sync();
     }
     if (!flat && !full && x0 < a.wvalid) { /* the ragged last chunk of a row: straight to memory */
         const int npairs = (a.wvalid - x0) >> 1;

@@ -15,17 +15,14 @@
  * filter_mb keeps within one plane (planes are independent).  The tile then goes back to the frame in dwords, halo included (its
  * untouched samples are final and nothing else writes them at that point).
  *
- * Hand-off (the protocol of k_vp9_intra_frame): sample stores are agent-scope relaxed stores, the wave waits for all of them
- * (s_waitcnt 0) before it moves its row's counter with an agent-scope store; the consumer polls with agent-scope loads and reads the
- * rows above with agent-scope loads issued after the poll.  Work units come from an agent-scope ticket counter in the progress slot,
- * ticket t = row * npics + frame, so the unit a wave waits on has a smaller ticket and belongs to a running wave; forward progress
- * does not rest on dispatch order.  The grid is min(units, resident capacity).  Every spin is bounded; on a timeout the wave sets the
- * progress slot's fail word and leaves.
+ * Hand-off between rows: row_handoff.h, lag 1 (the left edge of macroblock x + 1 of the row above writes into the rows this one
+ * reads), work units by ticket t = row * npics + frame; the grid is min(units, resident capacity).
  */
 #include <stddef.h>
 
 #include "common.h"
 #include "progress_pool.h"
+#include "row_handoff.h"
 #include "vp8_kernels.h"
 
 static_assert(sizeof(FFHipVp8FilterStrength) == 3, "FFHipVp8FilterStrength mirrors VP8FilterStrength");
@@ -48,20 +45,6 @@ __constant__ uint8_t c_vp8_hev_lut[2][64] = {
       1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2 },
 };
 
-__device__ __forceinline__ void v8f_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t v8f_ld(const uint8_t *p)
-{
-    return __hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void v8f_st(uint8_t *p, uint32_t v)
-{
-    __hip_atomic_store(reinterpret_cast<uint32_t *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 /* the dword item k of a macroblock's tiles: plane (0 Y, 1 U, 2 V), tile row, dword column, for `rows` x `dw` dwords per plane */
 struct V8fItem {
@@ -115,10 +98,7 @@ __global__ __launch_bounds__(64) void k_vp8_lf_frame(V8fPicSet S, int npics, int
     const int kind_mb = simple ? VP8_LF_SIMPLE : VP8_LF_MBEDGE, kind_in = simple ? VP8_LF_SIMPLE : VP8_LF_INNER;
 
     for (;;) {
-        int t = 0;
-        if (lane == 0)
-            t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = __shfl(t, 0);
+        const int t = ffhip_row_ticket(ticket, lane);
         if (t >= units)
             return;
         const int row = t / npics, f = t - row * npics;
@@ -139,7 +119,7 @@ __global__ __launch_bounds__(64) void k_vp8_lf_frame(V8fPicSet S, int npics, int
                     const int p = (lane - 20) / 12, r = lane - 20 - 12 * p;
                     reinterpret_cast<uint32_t *>(Tc[p])[r * 3] = reinterpret_cast<const uint32_t *>(Tc[p])[r * 3 + 2];
                 }
-                v8f_sync();
+                ffhip_wave_sync();
             }
             /* ---- rows 0..15 of the macroblock's own columns ---- */
             for (int k = lane; k < 64 + 32; k += 64) {
@@ -154,28 +134,17 @@ __global__ __launch_bounds__(64) void k_vp8_lf_frame(V8fPicSet S, int npics, int
             /* ---- the row above has finished min(cx + 2, mb_w) macroblocks: rows -4..-1 ---- */
             if (row > 0) {
                 const int want = min(cx + 2, mb_w);
-                int spins = 0;
-                while (known < want) {
-                    known = __hip_atomic_load(&progress[-1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (known >= want)
-                        break;
-                    __builtin_amdgcn_s_sleep(2);
-                    if (++spins > (1 << 24)) { /* never in a correct run; do not hang the device */
-                        if (lane == 0)
-                            __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        return;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the rows' loads are issued after the counter was seen */
+                if (!ffhip_row_wait(&progress[-1], want, known, fail, lane))
+                    return;
                 V8fItem it;
                 if (lane < 32 && v8f_item(lane, nplanes, 4, 4, 4, 2, it)) {
                     const int bs = it.plane ? 8 : 16, pitch = it.plane ? V8F_CP : V8F_YP;
                     const uint8_t *src = pl[it.plane] + (ptrdiff_t)(row * bs - 4 + it.r) * st[it.plane] + cx * bs + 4 * it.c;
                     uint8_t *T = it.plane ? Tc[it.plane - 1] : Ty;
-                    *reinterpret_cast<uint32_t *>(T + it.r * pitch + 4 + 4 * it.c) = v8f_ld(src);
+                    *reinterpret_cast<uint32_t *>(T + it.r * pitch + 4 + 4 * it.c) = ffhip_row_ld<uint32_t>(src);
                 }
             }
-            v8f_sync();
+            ffhip_wave_sync();
 
             /* ---- the macroblock's filters ---- */
             const FFHipVp8FilterStrength R = rec[cx];
@@ -200,7 +169,7 @@ __global__ __launch_bounds__(64) void k_vp8_lf_frame(V8fPicSet S, int npics, int
                         if (k < n)
                             T[(4 + i) * pitch + k] = (uint8_t)v[k];
                 }
-                v8f_sync();
+                ffhip_wave_sync();
                 /* row edges: a lane per column i (tile column 4 + i) */
                 if (active) {
 #pragma unroll
@@ -212,7 +181,7 @@ __global__ __launch_bounds__(64) void k_vp8_lf_frame(V8fPicSet S, int npics, int
                         if (k < n)
                             T[k * pitch + 4 + i] = (uint8_t)v[k];
                 }
-                v8f_sync();
+                ffhip_wave_sync();
                 /* ---- the tile back to the frame: rows from -4 (row > 0) or 0, columns from -4 (cx > 0) or 0 ---- */
                 const int r0 = row > 0 ? 0 : 4, c0 = cx > 0 ? 0 : 1;
                 const int yrows = 20 - r0, ydw = 5 - c0, crows = 12 - r0, cdw = 3 - c0;
@@ -223,17 +192,14 @@ __global__ __launch_bounds__(64) void k_vp8_lf_frame(V8fPicSet S, int npics, int
                     const int bs = it.plane ? 8 : 16, pitch = it.plane ? V8F_CP : V8F_YP, tr = r0 + it.r, tc = c0 + it.c;
                     const uint8_t *T = it.plane ? Tc[it.plane - 1] : Ty;
                     uint8_t *dst = pl[it.plane] + (ptrdiff_t)(row * bs - 4 + tr) * st[it.plane] + cx * bs - 4 + 4 * tc;
-                    v8f_st(dst, *reinterpret_cast<const uint32_t *>(T + tr * pitch + 4 * tc));
+                    ffhip_row_st<uint32_t>(dst, *reinterpret_cast<const uint32_t *>(T + tr * pitch + 4 * tc));
                 }
             }
             /* ---- macroblock cx is done: its stores are acknowledged, then the counter moves ---- */
             if (publish) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_s_waitcnt(0);
-                if (lane == 0)
-                    __hip_atomic_store(&progress[0], cx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ffhip_row_publish(&progress[0], cx + 1, lane);
             }
-            v8f_sync(); /* the tile's columns 12..15 are carried over next */
+            ffhip_wave_sync(); /* the tile's columns 12..15 are carried over next */
         }
     }
 }
@@ -251,21 +217,14 @@ int ffhip_launch_vp8_lf_frames(int filter_type, int keyframe, int mb_w, int mb_h
         for (int i = 0; i < V8F_PICS; i++)
             S.pic[i] = pics[p0 + (i < n ? i : 0)];
         const int units = n * mb_h;
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(units + 1, stream, &ps);
+        const int r = ffhip_progress_launch(units + 1, stream, "ffhip_vp8_loopfilter_frames_dev: kernel launch", [&](const FFHipProgressSlot &ps) {
+            const int grid = units < cap ? units : cap;
+            hipLaunchKernelGGL(k_vp8_lf_frame, dim3(grid), dim3(64), 0, stream, S, n, mb_w, mb_h, stride_y, stride_uv, filter_type, keyframe,
+                               ps.prog, ps.fail);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        const int grid = units < cap ? units : cap;
-        hipLaunchKernelGGL(k_vp8_lf_frame, dim3(grid), dim3(64), 0, stream, S, n, mb_w, mb_h, stride_y, stride_uv, filter_type, keyframe,
-                           ps.prog, ps.fail);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_vp8_loopfilter_frames_dev: kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

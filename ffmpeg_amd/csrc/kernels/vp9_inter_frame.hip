@@ -110,7 +110,7 @@ __device__ __forceinline__ void vif_predict(uint16_t *tile, PIX *tmp, const VifS
             const int r = i >> lgw, x = i & (w - 1), yy = s.yi + r + r0;
             tmp[r * TILE + x] = (PIX)vif_tap(filter, s.mx, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x + k, yy); });
         }
-        vif_wave_sync();
+        ffhip_wave_sync();
     }
     for (int i = lane; i < h << lgw; i += 64) {
         const int y = i >> lgw, x = i & (w - 1);
@@ -128,7 +128,7 @@ __device__ __forceinline__ void vif_predict(uint16_t *tile, PIX *tmp, const VifS
         uint16_t &d = tile[(ly + y) * TILE + lx + x];
         d = (uint16_t)(AVG ? (d + v + 1) >> 1 : v);
     }
-    vif_wave_sync(); /* tmp is reused by the next pass; an avg pass reads what this lane's put wrote */
+    ffhip_wave_sync(); /* tmp is reused by the next pass; an avg pass reads what this lane's put wrote */
 }
 
 constexpr int SROWS = 32; /* output rows per strip of the scaled 2-D form */
@@ -149,7 +149,7 @@ __device__ __forceinline__ void vif_predict_scaled(uint16_t *tile, PIX *tmp, con
             const int r = i >> lgw, x = i & (w - 1), pos = s.mx + x * dx, xx = s.xi + (pos >> 4);
             tmp[r * TILE + x] = (PIX)tap(pos & 15, [&](int k) { return vif_ref<PIX>(s, xx + k, ry + r); });
         }
-        vif_wave_sync();
+        ffhip_wave_sync();
         for (int i = lane; i < sh << lgw; i += 64) {
             const int y = i >> lgw, x = i & (w - 1), pos = m0 + y * dy;
             const PIX *t = tmp + ((pos >> 4) + before) * TILE + x;
@@ -157,7 +157,7 @@ __device__ __forceinline__ void vif_predict_scaled(uint16_t *tile, PIX *tmp, con
             uint16_t &d = tile[(ly + y0 + y) * TILE + lx + x];
             d = (uint16_t)(AVG ? (d + v + 1) >> 1 : v);
         }
-        vif_wave_sync(); /* the next strip or pass reuses tmp */
+        ffhip_wave_sync(); /* the next strip or pass reuses tmp */
     }
 }
 
@@ -337,28 +337,21 @@ int ffhip_launch_vp9_inter_frames(int bd, int ss_h, int ss_v, int width, int hei
         /* the frames (their reference tables included) go to the device in stream order: a progress-pool slot is device memory that
          * is not handed out again before the launch behind it has finished, and the copy from pageable memory is staged by the time
          * hipMemcpyAsync returns */
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(0, stream, &ps);
-        if (r < 0)
-            return r;
-        FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
-        hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipVp9InterPic), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) {
+        const int r = ffhip_progress_launch(0, stream, "ffhip_vp9_inter_frames_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
+            FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
+            const hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipVp9InterPic), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess)
+                return e;
             if (bd > 8)
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint16_t, false>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
                                    sb_w, bd);
             else
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint8_t, false>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
                                    sb_w, 8);
-            e = hipGetLastError();
-        }
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_vp9_inter_frames_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
+            return hipGetLastError();
+        });
+        if (r < 0)
+            return r;
     }
     return 0;
 }
@@ -401,28 +394,21 @@ int ffhip_launch_vp9_inter_frames_scaled(int bd, int ss_h, int ss_v, int width, 
         }
         /* as ffhip_launch_vp9_inter_frames: the slot is not handed out again before the launch behind it has finished, and the copy
          * from pageable memory is staged by the time hipMemcpyAsync returns */
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(0, stream, &ps);
-        if (r < 0)
-            return r;
-        FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
-        hipError_t e = hipMemcpyAsync(dpics, &st, sizeof(st), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) {
+        const int r = ffhip_progress_launch(0, stream, "ffhip_vp9_inter_frames_scaled_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
+            FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
+            const hipError_t e = hipMemcpyAsync(dpics, &st, sizeof(st), hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess)
+                return e;
             if (bd > 8)
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint16_t, true>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width,
                                    height, sb_w, bd);
             else
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint8_t, true>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width,
                                    height, sb_w, 8);
-            e = hipGetLastError();
-        }
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_vp9_inter_frames_scaled_dev: copy or launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
+            return hipGetLastError();
+        });
+        if (r < 0)
+            return r;
     }
     return 0;
 }

@@ -15,21 +15,14 @@
  * vp9_intra_rules.h (shared with k_vp9_intra), adds its residual with vp9_itxfm_tile.h (shared with k_vp9_inter_frame), which clips,
  * and writes its samples inside the decoded area to the tile and to the plane.  What no record covers is never written.
  *
- * Hand-off between rows (cdna_hip_programming Guideline 16, the protocol of k_hevc_intra_pic): every sample store is an agent-scope
- * relaxed store, the wave waits for all of them (s_waitcnt 0) before it moves its row's counter with an agent-scope store, and the
- * consumer polls that counter with agent-scope loads and reads the bottom line with agent-scope loads issued after the poll.  What
- * else a wave loads (records, coefficients, its own superblock, the left column of a superblock without records) nobody writes in
- * this launch.
- *
- * Forward progress does not rest on dispatch order: a wave claims its work units from an agent-scope ticket counter in the progress
- * slot, ticket t = row * chains + chain, so the unit a wave waits on (same chain, row - 1) has a smaller ticket and was claimed by a
- * wave that is already running.  The grid is min(units, resident capacity).  Every spin is bounded; on a timeout the wave sets the
- * progress slot's fail word and leaves.
+ * Hand-off between rows: row_handoff.h, lag 0 (superblock c reads nothing right of superblock c of the row above), work units by
+ * ticket t = row * chains + chain; the grid is min(units, resident capacity).
  */
 #include <stddef.h>
 
 #include "common.h"
 #include "h264_kernels.h"
+#include "row_handoff.h"
 #include "vp9_intra_rules.h"
 #include "vp9_itxfm_tile.h"
 
@@ -44,18 +37,6 @@ struct ViaPicSet {
     FFHipVp9IntraPic pic[VIA_PICS];
 };
 
-template <typename PIX> struct ViaQuad { typedef uint32_t T; };
-template <> struct ViaQuad<uint16_t> { typedef uint64_t T; };
-template <typename Q>
-__device__ __forceinline__ Q via_ld(const uint8_t *p)
-{
-    return __hip_atomic_load(reinterpret_cast<const Q *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename Q>
-__device__ __forceinline__ void via_st(uint8_t *p, Q v)
-{
-    __hip_atomic_store(reinterpret_cast<Q *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 template <typename PIX, typename Q>
 __device__ __forceinline__ void via_quad_to_tile(uint16_t *t, Q q)
 {
@@ -96,7 +77,7 @@ template <typename PIX>
 __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, int ss_h, int ss_v, int width, int height, int sb_w, int sb_h,
                                                         int *progress_all, int *fail, int bd)
 {
-    typedef typename ViaQuad<PIX>::T Q;
+    typedef typename FFHipQuad<PIX>::T Q;
     constexpr int PS = (int)sizeof(PIX);
     constexpr bool HBD = PS == 2;
     __shared__ uint16_t Tall[VIA_TP * 65];
@@ -110,10 +91,7 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
     const int maxv = (1 << bd) - 1, base1 = 128 << (bd - 8);
 
     for (;;) {
-        int t = 0;
-        if (lane == 0)
-            t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = __shfl(t, 0);
+        const int t = ffhip_row_ticket(ticket, lane);
         if (t >= units)
             return;
         const int row = t / chains, chain = t - row * chains, f = chain / 3, p = chain - 3 * f;
@@ -152,7 +130,7 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
                     for (int r = lane; r < Ch && cy0 + r < dh; r += 64)
                         T[r * VIA_TP - 1] = *reinterpret_cast<const PIX *>(pbase + (ptrdiff_t)(cy0 + r) * stride + (cx0 - 1) * PS);
                 }
-                vif_wave_sync();
+                ffhip_wave_sync();
                 /* ---- the superblock as the plane holds it, clipped to the decoded area ---- */
                 for (int i = lane; i < Ch * qw; i += 64) {
                     const int r = i / qw, c = 4 * (i - r * qw);
@@ -162,6 +140,7 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
                 /* ---- the row above has finished superblock cx ---- */
                 if (row > 0) {
                     const int want = cx + 1;
+                    /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
                     int spins = 0;
                     while (known < want) {
                         known = __hip_atomic_load(&progress[-1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -174,18 +153,18 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
                             return;
                         }
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the line's loads are issued after the counter was seen */
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the neighbour loads are issued after the counter was seen */
                     /* row -1, columns -4 .. Cw - 1 in quads (column -1 is the last sample of the first); dw is a multiple of 4 */
                     const int c = 4 * lane - 4;
                     if (lane <= qw && cx0 + c >= 0 && cx0 + c < dw) {
-                        const Q q = via_ld<Q>(pbase + (ptrdiff_t)(cy0 - 1) * stride + (cx0 + c) * PS);
+                        const Q q = ffhip_row_ld<Q>(pbase + (ptrdiff_t)(cy0 - 1) * stride + (cx0 + c) * PS);
                         if (c < 0)
                             T[-VIA_TP - 1] = (PIX)(q >> (3 * 8 * PS));
                         else
                             via_quad_to_tile<PIX>(&T[-VIA_TP + c], q);
                     }
                 }
-                vif_wave_sync();
+                ffhip_wave_sync();
 
                 /* ---- the superblock's records in decoding order ---- */
                 for (int k = k0; k < k1; k++) {
@@ -221,7 +200,7 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
                         }
                         E[i] = v;
                     }
-                    vif_wave_sync();
+                    ffhip_wave_sync();
                     /* 2. prediction into the tile */
                     switch (lg) {
                     case 2: via_predict<2>(T, E, mode, lx, ly, bd, maxv, lane); break;
@@ -229,7 +208,7 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
                     case 4: via_predict<4>(T, E, mode, lx, ly, bd, maxv, lane); break;
                     default: via_predict<5>(T, E, mode, lx, ly, bd, maxv, lane); break;
                     }
-                    vif_wave_sync();
+                    ffhip_wave_sync();
                     /* 3. the residual, added and clipped in the tile */
                     if (fl & 1) {
                         const void *co = HBD ? (const void *)(static_cast<const int32_t *>(coeffs) + R.coeff_offset)
@@ -242,7 +221,7 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
                         case 3: vif_tu<5, false, HBD, VIA_TP, false>(T, nullptr, mine, co, txtp, dc, lx, ly, maxv, lane); break;
                         default: vif_tu<2, true, HBD, VIA_TP, false>(T, nullptr, mine, co, txtp, dc, lx, ly, maxv, lane); break;
                         }
-                        vif_wave_sync();
+                        ffhip_wave_sync();
                     }
                     /* 4. the record's samples inside the decoded area to the plane, a quad per item */
                     const int qn = N >> 2;
@@ -254,7 +233,7 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
 #pragma unroll
                             for (int e = 0; e < 4; e++)
                                 q |= (Q)(PIX)s[e] << (e * 8 * PS);
-                            via_st<Q>(pbase + (ptrdiff_t)(y + r) * stride + (x + c) * PS, q);
+                            ffhip_row_st<Q>(pbase + (ptrdiff_t)(y + r) * stride + (x + c) * PS, q);
                         }
                     }
                 }
@@ -264,13 +243,10 @@ __global__ __launch_bounds__(64) void k_vp9_intra_frame(ViaPicSet S, int npics, 
             }
             /* ---- superblock cx is done: its stores are acknowledged, then the counter moves ---- */
             if (publish) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_s_waitcnt(0);
-                if (lane == 0)
-                    __hip_atomic_store(&progress[0], cx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ffhip_row_publish(&progress[0], cx + 1, lane);
             }
         }
-        vif_wave_sync(); /* the tile is reused by the next unit */
+        ffhip_wave_sync(); /* the tile is reused by the next unit */
     }
 }
 
@@ -287,25 +263,18 @@ int ffhip_launch_vp9_intra_frames(int bd, int ss_h, int ss_v, int width, int hei
         for (int i = 0; i < VIA_PICS; i++)
             S.pic[i] = pics[p0 + (i < n ? i : 0)];
         const int units = 3 * n * sb_h;
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(units + 1, stream, &ps);
+        const int r = ffhip_progress_launch(units + 1, stream, "ffhip_vp9_intra_frames_dev: kernel launch", [&](const FFHipProgressSlot &ps) {
+            const int grid = units < cap ? units : cap;
+            if (bd > 8)
+                hipLaunchKernelGGL(k_vp9_intra_frame<uint16_t>, dim3(grid), dim3(64), 0, stream, S, n, ss_h, ss_v, width, height, sb_w, sb_h, ps.prog,
+                                   ps.fail, bd);
+            else
+                hipLaunchKernelGGL(k_vp9_intra_frame<uint8_t>, dim3(grid), dim3(64), 0, stream, S, n, ss_h, ss_v, width, height, sb_w, sb_h, ps.prog,
+                                   ps.fail, 8);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        const int grid = units < cap ? units : cap;
-        if (bd > 8)
-            hipLaunchKernelGGL(k_vp9_intra_frame<uint16_t>, dim3(grid), dim3(64), 0, stream, S, n, ss_h, ss_v, width, height, sb_w, sb_h, ps.prog,
-                               ps.fail, bd);
-        else
-            hipLaunchKernelGGL(k_vp9_intra_frame<uint8_t>, dim3(grid), dim3(64), 0, stream, S, n, ss_h, ss_v, width, height, sb_w, sb_h, ps.prog,
-                               ps.fail, 8);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("ffhip_vp9_intra_frames_dev: kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

@@ -35,13 +35,6 @@ namespace vp64 {
 #undef VP_UT
 } // namespace vp64
 
-__device__ __forceinline__ void vp_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* HBD: coefficients are int32 (dctcoef), the networks run in 64 bits (namespace vp64), samples are uint16_t clipped to (1 << bd) - 1 */
 template <int LOG2, bool WHT, bool HBD>
 __global__ __launch_bounds__(256) void k_vp9_itxfm(void *coeffs_, uint8_t *dst, ptrdiff_t stride, const FFHipVp9TU *tus, int n, int bd)
@@ -77,7 +70,7 @@ __global__ __launch_bounds__(256) void k_vp9_itxfm(void *coeffs_, uint8_t *dst, 
             }
         }
     }
-    vp_wave_sync();
+    ffhip_wave_sync();
     COEF *mine = blk + ul * N * N;
     const bool adst1 = !WHT && LOG2 < 5 && (tu.txtp == 1 || tu.txtp == 3), adst2 = !WHT && LOG2 < 5 && (tu.txtp == 2 || tu.txtp == 3);
     const bool dc_only = !WHT && tu.dc_only && !adst1 && !adst2;
@@ -104,13 +97,13 @@ __global__ __launch_bounds__(256) void k_vp9_itxfm(void *coeffs_, uint8_t *dst, 
             x[k] = mine[k * N + i];
         run(adst1, true);
     }
-    vp_wave_sync();
+    ffhip_wave_sync();
     if (!dc_only) {
 #pragma unroll
         for (int k = 0; k < N; k++)
             mine[k * N + i] = (COEF)o[k];
     }
-    vp_wave_sync();
+    ffhip_wave_sync();
     /* second pass: row i of that matrix; its outputs are picture column i, so they go back transposed */
     if (!dc_only) {
 #pragma unroll
@@ -118,11 +111,11 @@ __global__ __launch_bounds__(256) void k_vp9_itxfm(void *coeffs_, uint8_t *dst, 
             x[k] = mine[i * N + k];
         run(adst2, false);
     }
-    vp_wave_sync();
+    ffhip_wave_sync();
 #pragma unroll
     for (int k = 0; k < N; k++)
         mine[k * N + i] = dc_only ? (COEF)dcv : (COEF)o[k];
-    vp_wave_sync();
+    ffhip_wave_sync();
     /* ---- picture += (residual + round) >> bits, row i of my unit ---- */
     if (live) {
         const COEF *r = mine + i * N;

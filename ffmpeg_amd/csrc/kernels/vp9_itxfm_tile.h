@@ -27,13 +27,6 @@ namespace vq64 {
 #undef VP_UT
 } // namespace vq64
 
-__device__ __forceinline__ void vif_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* one TU of N = 4 << LOG2-2 samples (WHT: the lossless 4x4) added to the tile at (lx, ly) (row pitch PITCH samples), clipped to
  * 0 .. maxv; MASKED: only to the samples whose bit is set in cov[row] (bit = column).  Lanes 0 .. N - 1 take a column each.  The order of the batch kernel (vp9_itxfm.hip): column i through the first pass into `mine` (wave-private
  * LDS, as the reference's dctcoef tmp[]), row i of that through the second; its outputs are picture column i. */
@@ -78,14 +71,14 @@ __device__ __forceinline__ void vif_tu(uint16_t *tile, const unsigned long long 
             for (int k = 0; k < N; k++)
                 mine[k * N + i] = (COEF)o[k];
         }
-        vif_wave_sync();
+        ffhip_wave_sync();
         if (i < N) {
 #pragma unroll
             for (int k = 0; k < N; k++)
                 x[k] = mine[i * N + k];
             run(adst2, false);
         }
-        vif_wave_sync(); /* `mine` is reused by the wave's next TU */
+        ffhip_wave_sync(); /* `mine` is reused by the wave's next TU */
     }
     if (i < N) {
         const int xx = lx + i;

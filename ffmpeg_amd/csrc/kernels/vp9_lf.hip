@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "h264_kernels.h"
+#include "row_handoff.h"
 
 static_assert(sizeof(FFHipVp9Edge) == 12, "FFHipVp9Edge is a 12-byte record");
 static_assert(sizeof(FFHipVp9LfSb) == 1280, "FFHipVp9LfSb is 320 dwords");
@@ -311,6 +312,7 @@ __device__ __forceinline__ void vp9_lf_sb_row(uint8_t *p0, uint8_t *p1, ptrdiff_
          *      overlaps; then the 8 rows above (the corner is never read) ---- */
         if (row > 0) {
             const int want = min(col + 2, sb_cols);
+            /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
             int spins = 0;
             while (known < want) {
                 known = __hip_atomic_load(&progress[row - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -323,7 +325,7 @@ __device__ __forceinline__ void vp9_lf_sb_row(uint8_t *p0, uint8_t *p1, ptrdiff_
                     return;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the neighbour loads are issued after the counter was seen */
         }
         if (row) {
             uint32_t vt[NP][Top::K];
@@ -434,19 +436,20 @@ __device__ __forceinline__ void vp9_lf_plane_row(uint8_t *p0, ptrdiff_t stride, 
         /* ---- the row above has finished superblock col + 1; then its last 8 rows ---- */
         if (row > 0) {
             const int want = min(col + 2, sb_cols);
+            /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
             int spins = 0;
             while (known < want) {
                 known = __hip_atomic_load(&progress[row - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (known >= want)
                     break;
                 __builtin_amdgcn_s_sleep(2);
-                if (++spins > (1 << 24)) {
+                if (++spins > (1 << 24)) { /* never in a correct run; do not hang the device */
                     if (lane == 0)
                         __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     return;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the neighbour loads are issued after the counter was seen */
             uint32_t vt[Top::K];
             Top::issue(vt, sb - 8 * stride, stride, 8, w / SPD, lane);
             Top::commit(vt, t32 + D8, PD, 8, w / SPD, lane);
@@ -536,26 +539,19 @@ int ffhip_launch_vp9_lf_frames_ssc(int bd, int ss_h, int ss_v, int npics, const 
     per = per > FFHIP_VP9_LF_PICS ? FFHIP_VP9_LF_PICS : per;
     for (int p0 = 0; p0 < npics; p0 += per) {
         const int n = npics - p0 < per ? npics - p0 : per;
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(n * per_pic + 1, stream, &ps);
+        const int r = ffhip_progress_launch(n * per_pic + 1, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            FFHipVp9LfPicsC S;
+            S.n = n;
+            for (int i = 0; i < FFHIP_VP9_LF_PICS; i++)
+                S.pic[i] = pics[p0 + (i < n ? i : 0)];
+            if (bd == 8)
+                hipLaunchKernelGGL(k_vp9_lf_frames_ssc<uint8_t>, dim3(3 * sb_rows, n), dim3(64), 0, stream, S, sy, suv, cols, rows, ps.prog, ps.fail, 8, ss_h);
+            else
+                hipLaunchKernelGGL(k_vp9_lf_frames_ssc<uint16_t>, dim3(3 * sb_rows, n), dim3(64), 0, stream, S, sy, suv, cols, rows, ps.prog, ps.fail, bd, ss_h);
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        FFHipVp9LfPicsC S;
-        S.n = n;
-        for (int i = 0; i < FFHIP_VP9_LF_PICS; i++)
-            S.pic[i] = pics[p0 + (i < n ? i : 0)];
-        if (bd == 8)
-            hipLaunchKernelGGL(k_vp9_lf_frames_ssc<uint8_t>, dim3(3 * sb_rows, n), dim3(64), 0, stream, S, sy, suv, cols, rows, ps.prog, ps.fail, 8, ss_h);
-        else
-            hipLaunchKernelGGL(k_vp9_lf_frames_ssc<uint16_t>, dim3(3 * sb_rows, n), dim3(64), 0, stream, S, sy, suv, cols, rows, ps.prog, ps.fail, bd, ss_h);
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }
@@ -573,21 +569,13 @@ int ffhip_launch_vp9_lf_frame_ssc(int bd, int ss_h, int ss_v, uint8_t *y, uint8_
     }
     if (3 * sb_rows + 1 > FFHIP_PROGRESS_SLOT_INTS)
         return FFHIP_EINVAL;
-    FFHipProgressSlot ps;
-    const int r = ffhip_progress_acquire(3 * sb_rows + 1, stream, &ps);
-    if (r < 0)
-        return r;
-    if (bd == 8)
-        hipLaunchKernelGGL(k_vp9_lf_frame_ssc<uint8_t>, dim3(3 * sb_rows), dim3(64), 0, stream, y, u, v, sy, suv, cols, rows, tabs, ctabs, ps.prog, ps.fail, 8, ss_h);
-    else
-        hipLaunchKernelGGL(k_vp9_lf_frame_ssc<uint16_t>, dim3(3 * sb_rows), dim3(64), 0, stream, y, u, v, sy, suv, cols, rows, tabs, ctabs, ps.prog, ps.fail, bd, ss_h);
-    const hipError_t e = hipGetLastError();
-    const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-    if (e != hipSuccess) {
-        ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-        return FFHIP_EIO;
-    }
-    return r2 < 0 ? r2 : 0;
+    return ffhip_progress_launch(3 * sb_rows + 1, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+        if (bd == 8)
+            hipLaunchKernelGGL(k_vp9_lf_frame_ssc<uint8_t>, dim3(3 * sb_rows), dim3(64), 0, stream, y, u, v, sy, suv, cols, rows, tabs, ctabs, ps.prog, ps.fail, 8, ss_h);
+        else
+            hipLaunchKernelGGL(k_vp9_lf_frame_ssc<uint16_t>, dim3(3 * sb_rows), dim3(64), 0, stream, y, u, v, sy, suv, cols, rows, tabs, ctabs, ps.prog, ps.fail, bd, ss_h);
+        return hipGetLastError();
+    });
 }
 
 /* ---- the frame kernel's line filter: the same arithmetic as vp9_lf_line (vp9dsp_template.c:1777-1930) without per-lane control
@@ -715,20 +703,6 @@ __device__ __forceinline__ void vp9_lf_line2(const int (&px)[16], int (&o)[16], 
 typedef __attribute__((address_space(3))) uint8_t vl_lds_u8;
 typedef __attribute__((address_space(3))) uint32_t vl_lds_u32;
 typedef __attribute__((address_space(3))) int vl_lds_int;
-__device__ __forceinline__ bool vl_wait_lds(const vl_lds_int *ctr, int want, int *fail)
-{
-    int spins = 0;
-    while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > (1 << 22)) { /* never in a correct run; do not hang the device */
-            if ((threadIdx.x & 63) == 0)
-                __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            return false;
-        }
-    }
-    asm volatile("" ::: "memory");
-    return true;
-}
 
 template <typename PIX, bool CHROMA>
 __device__ __forceinline__ void vp9_lf_sb_rows(vl_lds_u8 *lds, int W, uint8_t *p0, uint8_t *p1, ptrdiff_t stride, int cols, int rows, int row0,
@@ -793,7 +767,7 @@ __device__ __forceinline__ void vp9_lf_sb_rows(vl_lds_u8 *lds, int W, uint8_t *p
         LPIX *tile = (LPIX *)t32[pl];
         uint8_t *sb[2] = { prow[0] + (ptrdiff_t)col * N * PS, prow[1] + (ptrdiff_t)col * N * PS };
         /* ---- this stack held superblock col - 2, whose last rows the wave below reads until the end of its step col - 2 ---- */
-        if (live && to_lds && col >= 2 && !(fault & 8) && !vl_wait_lds(&hdone[wv + 1], col - 1, fail))
+        if (live && to_lds && col >= 2 && !(fault & 8) && !ffhip_row_wait_lds(&hdone[wv + 1], col - 1, fail))
             return;
         if (live) {
             /* ---- stack <- the prefetched N x N; its 8 context columns <- the last columns of superblock col - 1 ---- */
@@ -893,10 +867,11 @@ __device__ __forceinline__ void vp9_lf_sb_rows(vl_lds_u8 *lds, int W, uint8_t *p
             break;
         /* ---- only the row edges read (and rewrite) the last rows of the superblock above: it must have run the column edges of
          *      superblock col + 1, which reach into them ---- */
-        if (from_lds && !(fault & 8) && !vl_wait_lds(&cdone[wv - 1], col + 2, fail))
+        if (from_lds && !(fault & 8) && !ffhip_row_wait_lds(&cdone[wv - 1], col + 2, fail))
             return;
         if (from_mem) {
             const int want = (fault & 8) ? 0 : col + 1;
+            /* ffhip_row_wait() of row_handoff.h, kept inline: the helper form compiles to another schedule here (see docs/EXPERIMENTS.md) */
             int spins = 0;
             while (known < want) {
                 known = __hip_atomic_load(&progress[row - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -909,7 +884,7 @@ __device__ __forceinline__ void vp9_lf_sb_rows(vl_lds_u8 *lds, int W, uint8_t *p
                     return;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* the neighbour loads are issued after the counter was seen */
             uint32_t vt[NP][Top::K];
 #pragma unroll
             for (int q = 0; q < NP; q++)
@@ -1025,41 +1000,34 @@ int ffhip_launch_vp9_lf_frames(int bd, int npics, const FFHipVp9LfPic *pics, ptr
     per = per > FFHIP_VP9_LF_PICS ? FFHIP_VP9_LF_PICS : per;
     for (int p0 = 0; p0 < npics; p0 += per) {
         const int n = npics - p0 < per ? npics - p0 : per;
-        FFHipProgressSlot ps;
-        const int r = ffhip_progress_acquire(n * per_pic + 1, stream, &ps);
+        const int r = ffhip_progress_launch(n * per_pic + 1, stream, "kernel launch", [&](const FFHipProgressSlot &ps) {
+            int *const prog = ps.prog, *const fail = ps.fail;
+            if (old) {
+                const FFHipVp9LfPic &P = pics[p0];
+                if (bd == 8)
+                    hipLaunchKernelGGL(k_vp9_lf_frame<uint8_t>, dim3(2 * sb_rows), dim3(64), 0, stream, P.y, P.u, P.v, sy, suv, cols, rows, P.tables, prog, fail, 8);
+                else
+                    hipLaunchKernelGGL(k_vp9_lf_frame<uint16_t>, dim3(2 * sb_rows), dim3(64), 0, stream, P.y, P.u, P.v, sy, suv, cols, rows, P.tables, prog, fail, bd);
+            } else {
+                FFHipVp9LfPics S;
+                S.n = n;
+                for (int i = 0; i < FFHIP_VP9_LF_PICS; i++)
+                    S.pic[i] = pics[p0 + (i < n ? i : 0)];
+                /* superblock rows per workgroup: what 64 KB of LDS hold (two stacks of 8 + 64 W rows, 76 samples wide) */
+                const int wmax = bd == 8 ? 4 : 2;
+                const int W = ew && atoi(ew) >= 1 && atoi(ew) <= wmax ? atoi(ew) : wmax;
+                const int ps_ = bd == 8 ? 1 : 2, nwg = (sb_rows + W - 1) / W;
+                const unsigned luma = (2u * (8 + W * 64) * (76 * ps_ / 4) + W * 256u + 2u * W) * 4u, chroma = (4u * (8 + W * 32) * (44 * ps_ / 4) + W * 64u + 2u * W) * 4u;
+                const unsigned lds = ((luma > chroma ? luma : chroma) + 15u) & ~15u;
+                if (bd == 8)
+                    hipLaunchKernelGGL(k_vp9_lf_frame_wg<uint8_t>, dim3((planes444 ? 3 : 2) * nwg, n), dim3(64 * W), lds, stream, S, sy, suv, cols, rows, prog, fail, 8, fault, planes444);
+                else
+                    hipLaunchKernelGGL(k_vp9_lf_frame_wg<uint16_t>, dim3((planes444 ? 3 : 2) * nwg, n), dim3(64 * W), lds, stream, S, sy, suv, cols, rows, prog, fail, bd, fault, planes444);
+            }
+            return hipGetLastError();
+        });
         if (r < 0)
             return r;
-        int *const prog = ps.prog, *const fail = ps.fail;
-        if (old) {
-            const FFHipVp9LfPic &P = pics[p0];
-            if (bd == 8)
-                hipLaunchKernelGGL(k_vp9_lf_frame<uint8_t>, dim3(2 * sb_rows), dim3(64), 0, stream, P.y, P.u, P.v, sy, suv, cols, rows, P.tables, prog, fail, 8);
-            else
-                hipLaunchKernelGGL(k_vp9_lf_frame<uint16_t>, dim3(2 * sb_rows), dim3(64), 0, stream, P.y, P.u, P.v, sy, suv, cols, rows, P.tables, prog, fail, bd);
-        } else {
-            FFHipVp9LfPics S;
-            S.n = n;
-            for (int i = 0; i < FFHIP_VP9_LF_PICS; i++)
-                S.pic[i] = pics[p0 + (i < n ? i : 0)];
-            /* superblock rows per workgroup: what 64 KB of LDS hold (two stacks of 8 + 64 W rows, 76 samples wide) */
-            const int wmax = bd == 8 ? 4 : 2;
-            const int W = ew && atoi(ew) >= 1 && atoi(ew) <= wmax ? atoi(ew) : wmax;
-            const int ps_ = bd == 8 ? 1 : 2, nwg = (sb_rows + W - 1) / W;
-            const unsigned luma = (2u * (8 + W * 64) * (76 * ps_ / 4) + W * 256u + 2u * W) * 4u, chroma = (4u * (8 + W * 32) * (44 * ps_ / 4) + W * 64u + 2u * W) * 4u;
-            const unsigned lds = ((luma > chroma ? luma : chroma) + 15u) & ~15u;
-            if (bd == 8)
-                hipLaunchKernelGGL(k_vp9_lf_frame_wg<uint8_t>, dim3((planes444 ? 3 : 2) * nwg, n), dim3(64 * W), lds, stream, S, sy, suv, cols, rows, prog, fail, 8, fault, planes444);
-            else
-                hipLaunchKernelGGL(k_vp9_lf_frame_wg<uint16_t>, dim3((planes444 ? 3 : 2) * nwg, n), dim3(64 * W), lds, stream, S, sy, suv, cols, rows, prog, fail, bd, fault, planes444);
-        }
-        const hipError_t e = hipGetLastError();
-        const int r2 = ffhip_progress_release(&ps, stream, e == hipSuccess);
-        if (e != hipSuccess) {
-            ffhip_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            return FFHIP_EIO;
-        }
-        if (r2 < 0)
-            return r2;
     }
     return 0;
 }

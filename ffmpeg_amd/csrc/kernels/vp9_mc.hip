@@ -86,13 +86,6 @@ __constant__ __attribute__((aligned(16))) uint32_t vp9_v2[48][12] = {
 
 constexpr int VM_TW = 16, VM_PITCH = 20, VM_PAIRS = 37; /* tile width, dwords per row pair, (64 + 7 + 1) / 2 + 1 row pairs */
 
-__device__ __forceinline__ void vm_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* four horizontally filtered, rounded and clipped samples: p = the first window's first byte (x0 - 3), any alignment */
 __device__ __forceinline__ void vm_hrow4(const uint8_t *p, int clo, int chi, int (&o)[4])
 {
@@ -215,7 +208,7 @@ __global__ __launch_bounds__(256) void k_vp9_mc(uint8_t *dst, ptrdiff_t dststrid
             int16_t *t16 = reinterpret_cast<int16_t *>(tmp + (r >> 1) * VM_PITCH + 4 * xg) + (r & 1);
             t16[0] = (int16_t)o[0]; t16[2] = (int16_t)o[1]; t16[4] = (int16_t)o[2]; t16[6] = (int16_t)o[3];
         }
-        vm_wave_sync();
+        ffhip_wave_sync();
         for (int i = lane; i < h * ngt; i += 64) {
             const int y = i >> sh, xg = i & (ngt - 1);
             int v[4];
@@ -244,7 +237,7 @@ __global__ __launch_bounds__(256) void k_vp9_mc(uint8_t *dst, ptrdiff_t dststrid
             }
             emit(y, tx + 4 * xg, v);
         }
-        vm_wave_sync(); /* the next tile overwrites the plane */
+        ffhip_wave_sync(); /* the next tile overwrites the plane */
     }
     }
     }
@@ -543,7 +536,7 @@ __global__ __launch_bounds__(64 * WPB) void k_vp9_smc(uint8_t *dst, ptrdiff_t ds
         const int r = i >> lgw, x = i & (w - 1), pos = mx + x * dx;
         tmp[r * 64 + x] = (PIX)tap(pos & 15, s + (ptrdiff_t)(r - before) * sst + (pos >> 4), 1);
     }
-    vm_wave_sync();
+    ffhip_wave_sync();
     for (int i = lane; i < h * w; i += 64) {
         const int y = i >> lgw, x = i & (w - 1), pos = my + y * dy;
         const int v = tap(pos & 15, tmp + ((pos >> 4) + before) * 64 + x, 64);

@@ -63,13 +63,6 @@ struct TxPfa {
 /* the LDS work array of n complex points, padded (TX_PAD, kernels/tx_host.h) */
 __host__ __device__ static inline size_t tx_z_bytes(int n) { return ((size_t)TX_PAD(n) * 8 + 15) & ~(size_t)15; }
 
-__device__ __forceinline__ void tx_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* ff_tx_fft_sr_combine's TRANSFORM (libavutil/tx_template.c:540-586) on one butterfly: the reference's float
  * operations in the reference's order */
 __device__ __forceinline__ void tx_butterfly(float2 &v0, float2 &v1, float2 &v2, float2 &v3, float wre, float wim)
@@ -121,7 +114,7 @@ __device__ __forceinline__ void tx_fft_levels_ahead(float2 *z, const TxDev &d, c
     load_entries(2, e);
     load_twiddles(2, e, wre, wim);
     for (int l = 2; l <= d.lg; l++) {
-        tx_wave_sync();
+        ffhip_wave_sync();
         const int q = 1 << (l - 2);
         const int o1 = TX_PAD(q), o2 = TX_PAD(2 * q), o3 = TX_PAD(3 * q);
         float2 v[MI][4];
@@ -160,7 +153,7 @@ __device__ __forceinline__ void tx_team_sync()
     if (WG)
         __syncthreads();
     else
-        tx_wave_sync();
+        ffhip_wave_sync();
 }
 
 /* in-place split-radix FFT of z[0..n) held in LDS, one team; `lane` is the thread's index in the team */
@@ -177,7 +170,7 @@ __device__ __forceinline__ void tx_fft_lds(float2 *z, const TxDev &d, const floa
     }
     if (!WG && d.max_cnt <= 128 && d.ahead) {
         tx_fft_levels_ahead<2>(z, d, cos_tab, sched, lane);
-        tx_wave_sync();
+        ffhip_wave_sync();
         return;
     }
     for (int l = 2; l <= d.lg; l++) {
@@ -250,7 +243,7 @@ __global__ __launch_bounds__(256) void k_mdct(TxDev d, const float *in, size_t i
             for (int j = lane; j < 4 * n; j += 64)
                 st[j] = src[j];
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         /* ---- fold + pre-twiddle, scattered through map (ff_tx_mdct_fwd, tx_template.c:1285-1296) ---- */
         const int len3 = 3 * n;
         for (int i = lane; i < n; i += 64) {
@@ -266,7 +259,7 @@ __global__ __launch_bounds__(256) void k_mdct(TxDev d, const float *in, size_t i
             const float2 e = d.exp[i];
             z[d.map[i]] = make_float2(re * e.y + im * e.x, re * e.x - im * e.y);
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         tx_fft_lds(z, d, f_cos, f_sched, f_b2, lane);
         /* ---- post-twiddle (tx_template.c:1300-1309) ---- */
         for (int i = lane; i < q; i += 64) {
@@ -296,7 +289,7 @@ __global__ __launch_bounds__(256) void k_mdct(TxDev d, const float *in, size_t i
             for (int j = lane; j < 2 * n; j += 64)
                 st[j] = src[j * stride];
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         /* ---- pre-twiddle (ff_tx_mdct_inv, tx_template.c:1321-1328: z[i] from in[map[i]]) walked in INPUT order j =
          * map[i] and scattered through the inverse permutation: the staging area is then read in order instead of
          * through a bit-reversal-like gather (up to 32 lanes on one LDS bank); same operands, same operations ---- */
@@ -306,7 +299,7 @@ __global__ __launch_bounds__(256) void k_mdct(TxDev d, const float *in, size_t i
             const float2 e = d.exp[j];
             z[d.map[j]] = make_float2(tre * e.x - tim * e.y, tre * e.y + tim * e.x);
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         tx_fft_lds(z, d, f_cos, f_sched, f_b2, lane);
         /* ---- post-twiddle (tx_template.c:1332-1341) ---- */
         const float2 *ex = d.exp;
@@ -327,7 +320,7 @@ __global__ __launch_bounds__(256) void k_mdct(TxDev d, const float *in, size_t i
         }
     }
     if (vec_out) {
-        tx_wave_sync();
+        ffhip_wave_sync();
         const float4 *s4 = reinterpret_cast<const float4 *>(st);
         float4 *d4 = reinterpret_cast<float4 *>(dst);
         for (int j = lane; j < (n >> 1); j += 64)
@@ -375,7 +368,7 @@ __global__ __launch_bounds__(256) void k_mdct_l(TxDev d, const uint8_t *blob, in
         float4 *d4 = reinterpret_cast<float4 *>(reinterpret_cast<uint8_t *>(out) + (size_t)t * out_pitch);
         for (int j = lane; j < nin4; j += 64)
             l4[j] = s4[j];
-        tx_wave_sync();
+        ffhip_wave_sync();
         if (!INV) {
             const int len3 = 3 * n;
             for (int i = lane; i < n; i += 64) {
@@ -399,7 +392,7 @@ __global__ __launch_bounds__(256) void k_mdct_l(TxDev d, const uint8_t *blob, in
                 z[l_map[j]] = make_float2(tre * e.x - tim * e.y, tre * e.y + tim * e.x);
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         tx_fft_lds(z, d, l_cos, l_sched, l_b2, lane);
         const float2 *ex = l_exp;
         for (int i = lane; i < q; i += 64) {
@@ -419,10 +412,10 @@ __global__ __launch_bounds__(256) void k_mdct_l(TxDev d, const uint8_t *blob, in
                 reinterpret_cast<float2 *>(st)[i0] = make_float2(c, b);
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         for (int j = lane; j < n / 2; j += 64)
             d4[j] = l4[j];
-        tx_wave_sync();
+        ffhip_wave_sync();
     }
 }
 
@@ -629,7 +622,7 @@ __global__ __launch_bounds__(1024) void k_rdft(TxDev d, const uint8_t *blob, int
                 }
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         if constexpr (RLG != 0)
             fr_fft_lds<RLG, INV>(z, rtw, lane);
         else
@@ -691,7 +684,7 @@ __global__ __launch_bounds__(1024) void k_rdft(TxDev d, const uint8_t *blob, int
             for (int i = lane; i < len2; i += 64)
                 out2[i] = z[TX_PAD(i)];
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
     }
 }
 
@@ -806,7 +799,7 @@ __global__ __launch_bounds__(1024) void k_dct(TxDev d, const uint8_t *blob, int 
                 }
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         if (RLG && !active)
             continue; /* (no barriers with the radix core: the running sums are a wave's own scan) */
         if constexpr (RLG != 0)
@@ -846,7 +839,7 @@ __global__ __launch_bounds__(1024) void k_dct(TxDev d, const uint8_t *blob, int 
                 /* the same sums as a suffix scan of the wave's own terms: lane l owns acc[l C .. l C + C - 1], adds up its chunk from the
                  * top, and takes the sum of the chunks above it (and of acc[len2]) from a shuffle scan.  A different order of float
                  * additions than the reference's chain: within the tolerance, not bit-identical. */
-                tx_wave_sync();
+                ffhip_wave_sync();
                 constexpr int C = (1 << RLG) / 64;
                 float sfx[C];
 #pragma unroll
@@ -864,11 +857,11 @@ __global__ __launch_bounds__(1024) void k_dct(TxDev d, const uint8_t *blob, int 
                 }
                 float above = __shfl_down(incl, 1);
                 above = (lane == 63 ? 0.0f : above) + acc[len2];
-                tx_wave_sync();
+                ffhip_wave_sync();
 #pragma unroll
                 for (int i = 0; i < C; i++)
                     acc[lane * C + i] = sfx[i] + above;
-                tx_wave_sync();
+                ffhip_wave_sync();
             } else {
             __syncthreads();
             if (wave == 0 && lane < W && t0 + lane < nt) {
@@ -917,7 +910,7 @@ __global__ __launch_bounds__(1024) void k_dct(TxDev d, const uint8_t *blob, int 
                 y[j] = t1 - t2;
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
     }
 }
 
@@ -1129,7 +1122,7 @@ __global__ __launch_bounds__(1024) void k_mdct_pfa(TxDev d, TxPfa P, TxTab53 T, 
                 w[j] = make_float2(f.y * e1.x - h.x * e1.y, f.y * e1.y + h.x * e1.x);
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         /* 2. this lane's F points per sub-transform, through the Ruritanian input map */
         float2 f[C][F];
 #pragma unroll
@@ -1142,7 +1135,7 @@ __global__ __launch_bounds__(1024) void k_mdct_pfa(TxDev d, TxPfa P, TxTab53 T, 
                     f[c][j] = w[l_in[sc * F + j]];
             }
         }
-        tx_wave_sync(); /* every lane has its inputs: the same bytes become the work array */
+        ffhip_wave_sync(); /* every lane has its inputs: the same bytes become the work array */
 #pragma unroll
         for (int c = 0; c < C; c++) {
             const int sc = si + 64 * c;
@@ -1157,7 +1150,7 @@ __global__ __launch_bounds__(1024) void k_mdct_pfa(TxDev d, TxPfa P, TxTab53 T, 
                 }
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
         /* 3. the F G sub-transforms */
         tx_fft_lds(z, d, l_cos, l_sched, l_b2, lane);
         /* 4. post-twiddle (the FFT: the CRT output map alone, tx_template.c:1078-1079) */
@@ -1190,7 +1183,7 @@ __global__ __launch_bounds__(1024) void k_mdct_pfa(TxDev d, TxPfa P, TxTab53 T, 
                 out2[i0] = make_float2(b, c);
             }
         }
-        tx_wave_sync();
+        ffhip_wave_sync();
     }
 }
 #undef TXBF
