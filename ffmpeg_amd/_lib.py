@@ -283,6 +283,10 @@ def lib():
         "ffhip_vp8_idct_record_size": (C.c_int, []),
         "ffhip_vp8_mc_record_size": (C.c_int, []),
         "ffhip_vp8_loopfilter_frames_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t, vp]),
+        "ffhip_vp8_recon_frames_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t, vp]),
+        "ffhip_vp8_mb_record_size": (C.c_int, []),
+        "ffhip_vp8_mb_preds": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
+        "ffhip_vp8_intra_modes": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "ffhip_hevc_inter_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_hevc_inter_pu_record_size": (C.c_int, []),
         "ffhip_hevc_inter_tu_record_size": (C.c_int, []),

@@ -19,12 +19,6 @@ static_assert(sizeof(FFHipVp8WhtRec) == 12, "FFHipVp8WhtRec is a 12-byte record"
 static_assert(sizeof(FFHipVp8IdctRec) == 12, "FFHipVp8IdctRec is a 12-byte record");
 static_assert(sizeof(FFHipVp8McRec) == 16, "FFHipVp8McRec is a 16-byte record");
 
-/* subpel_filters[mx - 1] (vp8dsp.c) */
-__constant__ uint8_t c_vp8_subpel[7][6] = {
-    { 0, 6, 123, 12, 1, 0 }, { 2, 11, 108, 36, 8, 1 }, { 0, 9, 93, 50, 6, 0 }, { 3, 16, 77, 77, 16, 3 },
-    { 0, 6, 50, 93, 9, 0 },  { 1, 8, 36, 108, 11, 2 }, { 0, 1, 12, 123, 6, 0 },
-};
-
 __global__ __launch_bounds__(256) void k_vp8_wht(uint8_t *base, const FFHipVp8WhtRec *recs, int n)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -41,34 +35,18 @@ __global__ __launch_bounds__(256) void k_vp8_wht(uint8_t *base, const FFHipVp8Wh
             blk[16 * k] = val;
         return;
     }
-    int16_t d[16];
+    int16_t d[16], o[16];
 #pragma unroll
     for (int k = 0; k < 16; k++)
         d[k] = dc[k];
+    vp8_wht16(d, o);
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int t0 = d[c] + d[12 + c], t1 = d[4 + c] + d[8 + c], t2 = d[4 + c] - d[8 + c], t3 = d[c] - d[12 + c];
-        d[c] = (int16_t)(t0 + t1);
-        d[4 + c] = (int16_t)(t3 + t2);
-        d[8 + c] = (int16_t)(t0 - t1);
-        d[12 + c] = (int16_t)(t3 - t2);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int t0 = d[4 * r] + d[4 * r + 3] + 3, t1 = d[4 * r + 1] + d[4 * r + 2], t2 = d[4 * r + 1] - d[4 * r + 2],
-                  t3 = d[4 * r] - d[4 * r + 3] + 3;
-        blk[(4 * r + 0) * 16] = (int16_t)((t0 + t1) >> 3);
-        blk[(4 * r + 1) * 16] = (int16_t)((t3 + t2) >> 3);
-        blk[(4 * r + 2) * 16] = (int16_t)((t0 - t1) >> 3);
-        blk[(4 * r + 3) * 16] = (int16_t)((t3 - t2) >> 3);
-    }
+    for (int k = 0; k < 16; k++)
+        blk[k * 16] = o[k];
 #pragma unroll
     for (int k = 0; k < 16; k++)
         dc[k] = 0;
 }
-
-__device__ __forceinline__ int vp8_mul20091(int a) { return ((a * 20091) >> 16) + a; }
-__device__ __forceinline__ int vp8_mul35468(int a) { return (a * 35468) >> 16; }
 
 __global__ __launch_bounds__(256) void k_vp8_idct(uint8_t *dst, ptrdiff_t stride, uint8_t *cbase, const FFHipVp8IdctRec *recs, int n)
 {
@@ -88,31 +66,14 @@ __global__ __launch_bounds__(256) void k_vp8_idct(uint8_t *dst, ptrdiff_t stride
         for (int k = 0; k < 16; k++)
             z[k] = dc;
     } else {
-        int16_t c[16], tmp[16];
+        int16_t c[16];
 #pragma unroll
         for (int k = 0; k < 16; k++)
             c[k] = b[k];
 #pragma unroll
         for (int k = 0; k < 16; k++)
             b[k] = 0;
-#pragma unroll
-        for (int col = 0; col < 4; col++) {
-            const int t0 = c[col] + c[8 + col], t1 = c[col] - c[8 + col];
-            const int t2 = vp8_mul35468(c[4 + col]) - vp8_mul20091(c[12 + col]), t3 = vp8_mul20091(c[4 + col]) + vp8_mul35468(c[12 + col]);
-            tmp[4 * col + 0] = (int16_t)(t0 + t3);
-            tmp[4 * col + 1] = (int16_t)(t1 + t2);
-            tmp[4 * col + 2] = (int16_t)(t1 - t2);
-            tmp[4 * col + 3] = (int16_t)(t0 - t3);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int t0 = tmp[r] + tmp[8 + r], t1 = tmp[r] - tmp[8 + r];
-            const int t2 = vp8_mul35468(tmp[4 + r]) - vp8_mul20091(tmp[12 + r]), t3 = vp8_mul20091(tmp[4 + r]) + vp8_mul35468(tmp[12 + r]);
-            z[4 * r + 0] = (t0 + t3 + 4) >> 3;
-            z[4 * r + 1] = (t1 + t2 + 4) >> 3;
-            z[4 * r + 2] = (t1 - t2 + 4) >> 3;
-            z[4 * r + 3] = (t0 - t3 + 4) >> 3;
-        }
+        vp8_idct16(c, z);
     }
     const bool aligned = !((reinterpret_cast<uintptr_t>(d) | (uintptr_t)stride) & 3);
 #pragma unroll

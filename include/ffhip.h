@@ -2321,6 +2321,132 @@ int ffhip_vp8_loopfilter_frames_dev(int filter_type, int keyframe, int mb_w, int
                                     ptrdiff_t stride_y, ptrdiff_t stride_uv, void *stream);
 
 /**
+ * VP8 reconstruction of whole frames: what decode_mb_row_no_filter() (libavcodec/vp8.c) does per macroblock between parsing and the
+ * loop filter — intra_predict() or inter_predict(), then idct_mb() — for every macroblock of up to 16 frames per call (a larger npics
+ * is split into launches of 16).  A decoder fills one FFHipVp8Mb per macroblock instead of calling those three, and launches this,
+ * then ffhip_vp8_loopfilter_frames_dev() on the same stream: the filtered frame is the next frame's reference and never leaves the
+ * device.  VP8 only (not VP7); the frame and its references have the same size.  The rules below restate vp8.c from memory of its
+ * structure; treat a difference from vp8.c as a defect of this face.
+ *
+ *  The record holds what VP8Macroblock and the row's non_zero_count_cache hold at that point:
+ *  - ref_frame 0: intra; 1, 2, 3: VP8_FRAME_PREVIOUS, _GOLDEN, _ALTREF, planes ref[ref_frame - 1][0..2] of the frame's struct.
+ *  - intra: mode = FFHIP_VP8_PRED_DC / _HOR / _VERT / _TM (mb->mode's values) or FFHIP_VP8_MODE_I4x4 with the sixteen sub_mode[] =
+ *    FFHIP_VP8_B_VERT .. _TM (intra4x4_pred_mode_mb, raster order); chroma_mode = FFHIP_VP8_PRED_DC .. _TM.
+ *  - inter: partitioning = FFHIP_VP8_PART_NONE (mv[0] = mb->mv), _16x8 (mv[0..1] = bmv[0..1]: top, bottom), _8x16 (left, right), _8x8
+ *    (mv[0..3]), _4x4 (mv[0..15] = bmv[], raster order); luma MVs in quarter-pel, { x, y }.
+ *  - y2: 0 nothing (the luma DCs are already in the blocks), 1 vp8_luma_dc_wht_dc, 2 vp8_luma_dc_wht, from block_dc into the
+ *    sixteen luma blocks' [0].
+ *  - block_code: 2 bits per 4x4 block, block b (0..15 Y in raster order, 16..19 U, 20..23 V) in bits 2 (b & 3) of byte b >> 2:
+ *    0 nothing, 1 vp8_idct_dc_add, 2 vp8_idct_add (idct_mb's dc_add4y / dc_add4uv shortcuts leave the same bytes as the per-block
+ *    members).  mb->skip is "all codes 0 and y2 0".
+ *  - coeff_offset: index of the macroblock's 400 coefficients in the frame's `coeffs`, a multiple of 16: td->block[6][4][16] (384)
+ *    followed by td->block_dc[16]; ignored when nothing is coded.  The coefficients are READ ONLY here: unlike the VP8DSPContext
+ *    members and the batch faces above (which keep their clearing side effect), this face does not clear them.
+ *
+ *  Inter (inter_predict, vp8_mc_part, vp8_mc_luma, vp8_mc_chroma): ffhip_vp8_mb_preds() lists the calls.
+ *  - luma: mx = (mv.x * 2) & 7, my = (mv.y * 2) & 7, the source is the block's position + (mv.x >> 2, mv.y >> 2); the [v][h] table
+ *    slot of a fraction is subpel_idx[0][]: 0 for 0, 1 (4 taps) for odd eighths, 2 (6 taps) for even ones; `bilinear` (s->profile != 0)
+ *    takes put_vp8_bilinear_pixels_tab, whose slots 1 and 2 are one function.  A zero fraction pair is a copy.
+ *  - chroma: the luma MV read as eighths of the half-size plane: mx = mv.x & 7, the source + (mv.x >> 3); with fullpel_chroma
+ *    (s->profile == 3) both components & ~7 first.  4x4 partitioning: each 4x4 chroma block takes the sum s of its 2x2 group's four
+ *    luma MVs, (s + 2 + (s >> 31)) >> 2 per component, then the full-pel mask; the others: each part's MV on the half-size block.
+ *  - reference samples are read as emulated_edge_mc gives them against a 16 mb_w x 16 mb_h (chroma 8 mb_w x 8 mb_h) plane:
+ *    coordinates clamped to the plane.  An MV may point anywhere; no padded border is read.
+ *  - then the residual: the WHT per y2, then each block per its code.
+ *
+ *  Intra (intra_predict and its check_*_mode helpers, the VP8 branch): prediction reads the unfiltered samples of the frame being
+ *  reconstructed, inter macroblocks included.  Outside the frame the border is virtual: the row above is 127, (-1, -1) included;
+ *  the column to the left is 129.  ffhip_vp8_intra_modes() gives the slots taken.
+ *  - 4x4 modes see that border (intra_predict's copy_dst, or the substitutes DC_127 / DC_129 / plain VERT / plain HOR, which equal
+ *    it).  Top-right of a sub-block: columns 0..2 read the row above the sub-block (rows 1..3: the reconstructed sub-block above
+ *    right, inside the macroblock); column 3 of EVERY row reads the four samples above-right of the macroblock (row 16 mb_y - 1,
+ *    columns 16 mb_x + 16..19), which in the last macroblock column are the sample at column 16 mb_x + 15 of that row, repeated.
+ *  - 16x16 and chroma modes: VERT -> DC_127 in the top row, HOR -> DC_129 in the left column, TM -> VERT / HOR / DC_129; DC uses only
+ *    the sides that exist (TOP_DC / LEFT_DC at an edge, 128 in the corner macroblock).
+ *  - an I4x4 macroblock: sub-blocks in raster order, each predicted, then its residual added, the next one predicts from the
+ *    result; other macroblocks and chroma: the whole block is predicted, then the residuals are added.
+ *
+ *  A malformed record makes its macroblock write nothing; the rest of the frame is unaffected (a neighbour predicts from the bytes
+ *  that were there): ref_frame > 3 or naming a reference with a NULL plane, mode > 4, chroma_mode > 3, sub_mode > 9 (I4x4),
+ *  partitioning > 4, y2 > 2, a block code of 3, or (something coded) a coeff_offset that is negative, not a multiple of 16 or with
+ *  coeff_offset + 400 > coeff_count.
+ */
+#define FFHIP_VP8_PRED_DC       0   /* 16x16 / chroma modes and the slots they take: h264pred.h's DC_PRED8x8 .. DC_129_PRED8x8 */
+#define FFHIP_VP8_PRED_HOR      1
+#define FFHIP_VP8_PRED_VERT     2
+#define FFHIP_VP8_PRED_TM       3   /* PLANE_PRED8x8's slot */
+#define FFHIP_VP8_MODE_I4x4     4   /* FFHipVp8Mb.mode only */
+#define FFHIP_VP8_PRED_LEFT_DC  4   /* slots only, from here on */
+#define FFHIP_VP8_PRED_TOP_DC   5
+#define FFHIP_VP8_PRED_DC_128   6
+#define FFHIP_VP8_PRED_DC_127   7
+#define FFHIP_VP8_PRED_DC_129   8
+#define FFHIP_VP8_PRED_NONE     255 /* FFHipVp8IntraModes.mode16 of an I4x4 macroblock: no pred16x16[] slot is taken */
+#define FFHIP_VP8_B_VERT        0   /* 4x4 modes: h264pred.h's VERT_PRED .. HOR_UP_PRED, TM_VP8_PRED */
+#define FFHIP_VP8_B_HOR         1
+#define FFHIP_VP8_B_DC          2
+#define FFHIP_VP8_B_DDL         3
+#define FFHIP_VP8_B_DDR         4
+#define FFHIP_VP8_B_VR          5
+#define FFHIP_VP8_B_HD          6
+#define FFHIP_VP8_B_VL          7
+#define FFHIP_VP8_B_HU          8
+#define FFHIP_VP8_B_TM          9
+#define FFHIP_VP8_B_VERT_PLAIN  10  /* slots only: VERT_VP8_PRED, DC_127_PRED, DC_129_PRED, HOR_VP8_PRED */
+#define FFHIP_VP8_B_DC_127      12
+#define FFHIP_VP8_B_DC_129      13
+#define FFHIP_VP8_B_HOR_PLAIN   14
+#define FFHIP_VP8_PART_NONE     0
+#define FFHIP_VP8_PART_16x8     1
+#define FFHIP_VP8_PART_8x16     2
+#define FFHIP_VP8_PART_8x8      3
+#define FFHIP_VP8_PART_4x4      4
+typedef struct FFHipVp8Mb {            /* 96 bytes */
+    int32_t coeff_offset;
+    int16_t mv[16][2];
+    uint8_t sub_mode[16];
+    uint8_t block_code[6];
+    uint8_t ref_frame, mode, chroma_mode, partitioning, y2, reserved;
+} FFHipVp8Mb;
+typedef struct FFHipVp8ReconPic {      /* device pointers */
+    uint8_t *y, *u, *v;                /* the frame being reconstructed */
+    const uint8_t *ref[3][3];          /* [VP8_FRAME_PREVIOUS, _GOLDEN, _ALTREF - 1][Y, U, V]: same strides and geometry; NULL where no record names it */
+    const FFHipVp8Mb *mbs;             /* mb_w * mb_h records in raster order */
+    const int16_t *coeffs;             /* never written */
+    int64_t coeff_count;
+} FFHipVp8ReconPic;
+/** mb_w, mb_h 1..1024; bilinear, fullpel_chroma 0 or 1.  Two launches per 16 frames on `stream`: the inter macroblocks (a wave each;
+ *  intra records return at once — no keyframe hint is taken and nothing is scanned on the host), then the intra macroblocks, a
+ *  wave per macroblock row that starts macroblock x once the row above has finished min(x + 2, mb_w).  Asynchronous; a lost hand-off
+ *  (never in a correct run) is reported by ffhip_stream_synchronize.  FFHIP_EINVAL (before any device check) for values outside
+ *  those, npics <= 0, a NULL array, a NULL y / u / v / mbs, a NULL coeffs with coeff_count > 0, planes (references too) or strides
+ *  that are not multiples of 4, stride_y < 16 * mb_w, stride_uv < 8 * mb_w, a reference plane that overlaps a destination plane of
+ *  the call, or two destination planes that overlap; FFHIP_ENOSYS without a device. */
+int ffhip_vp8_recon_frames_dev(int mb_w, int mb_h, int bilinear, int fullpel_chroma, int npics, const FFHipVp8ReconPic *pics /* host array */,
+                               ptrdiff_t stride_y, ptrdiff_t stride_uv, void *stream);
+int ffhip_vp8_mb_record_size(void);
+/** One put_vp8_{epel,bilinear}_pixels_tab[.][vslot][hslot] call of inter_predict(): a w x h block at (x, y) of the macroblock in
+ *  `plane` (0 Y, 1 U, 2 V; chroma in chroma samples), whose source block starts at (sx, sy) of the reference plane (before clamping;
+ *  the taps reach around it), with mx, my in eighths. */
+typedef struct FFHipVp8Pred {
+    uint8_t plane, x, y, w, h, mx, my, vslot, hslot, pad[3];
+    int32_t sx, sy;
+} FFHipVp8Pred;
+/** Device-free.  The calls inter_predict() makes for `mb` at (mb_x, mb_y), in its order (per part luma, U, V; 4x4: the sixteen luma
+ *  blocks, then U, V of each chroma block): returns their number (3, 6, 12 or 24), FFHIP_EINVAL for NULL, an intra record, ref_frame > 3, a
+ *  partitioning > 4 or a negative mb_x / mb_y. */
+int ffhip_vp8_mb_preds(const FFHipVp8Mb *mb, int mb_x, int mb_y, int fullpel_chroma, FFHipVp8Pred out[24]);
+typedef struct FFHipVp8IntraModes {
+    uint8_t mode16;                    /* the pred16x16[] slot (FFHIP_VP8_PRED_*); FFHIP_VP8_PRED_NONE for I4x4 (4 is LEFT_DC's slot) */
+    uint8_t chroma;                    /* the pred8x8[] slot */
+    uint8_t sub[16];                   /* I4x4: the pred4x4[] slots (FFHIP_VP8_B_*) */
+    uint8_t copy[16];                  /* I4x4: 1 where intra_predict() predicts into its bordered copy_dst */
+} FFHipVp8IntraModes;
+/** Device-free.  The slots intra_predict() takes for `mb` at (mb_x, mb_y) after the edge substitutions.  FFHIP_EINVAL for NULL, an
+ *  inter record, a mode out of range or a negative mb_x / mb_y. */
+int ffhip_vp8_intra_modes(const FFHipVp8Mb *mb, int mb_x, int mb_y, FFHipVp8IntraModes *out);
+
+/**
  * vp9dsp above 8 bits (profiles 2 / 3): the batch faces above at the bpp ff_vp9dsp_init(dsp, bpp, bitexact) instantiates its template
  * for (libavcodec/vp9dsp.c:88-112, vp9dsp_10bpp.c / vp9dsp_12bpp.c).  bit_depth 8, 10 or 12.  Samples are uint16_t above 8 bits,
  * itxfm_add's coefficients int32_t (the reference's dctcoef; FFHipVp9TU.coeff_offset counts coefficients) and its butterflies run

@@ -1,0 +1,71 @@
+"""Generated VP8 frames for ffhip_vp8_recon_frames_dev: macroblock records (ffmpeg_amd.vp8.MB_DTYPE) and their coefficients."""
+import numpy as np
+
+from ffmpeg_amd import vp8
+
+import vp8_recon_model as RM
+
+
+def set_code(mb, b, c):
+    mb["block_code"][b >> 2] = (int(mb["block_code"][b >> 2]) & ~(3 << (2 * (b & 3)))) | (c << (2 * (b & 3)))
+
+
+def frame(seed, mb_w, mb_h, keyframe=False, intra=0.1, mv_range=40, refs=(1, 2, 3), parts=None, far=0.0, skip=0.15, i4=0.2):
+    """(mbs, coeffs): mb_w * mb_h records in raster order.  intra: the share of intra macroblocks of an inter frame; mv_range: luma MVs
+    in quarter-pel, uniform in +-mv_range; far: the share of inter macroblocks whose MV points far outside the frame (any side); refs:
+    the references the records may name; parts: the partitionings to draw from; i4: the share of I4x4 among intra macroblocks."""
+    rng = np.random.default_rng(seed)
+    n = mb_w * mb_h
+    mbs = np.zeros(n, vp8.MB_DTYPE)
+    co = np.zeros(n * RM.MB_COEFFS, np.int16)
+    parts = list(range(5)) if parts is None else parts
+    for m in range(n):
+        mb = mbs[m]
+        if keyframe or rng.random() < intra:
+            mb["mode"] = RM.MODE_I4x4 if rng.random() < i4 else rng.integers(0, 4)
+            mb["chroma_mode"] = rng.integers(0, 4)
+            if mb["mode"] == RM.MODE_I4x4:
+                mb["sub_mode"] = rng.integers(0, 10, 16)
+        else:
+            mb["ref_frame"] = refs[rng.integers(0, len(refs))]
+            mb["partitioning"] = parts[rng.integers(0, len(parts))]
+            mv = rng.integers(-mv_range, mv_range + 1, (16, 2))
+            if rng.random() < 0.1:
+                mv[:] = 0
+            if rng.random() < far:
+                side = rng.integers(0, 4)
+                big = 4 * (16 * max(mb_w, mb_h) + 100)
+                mv += np.array([(-big, 0), (big, 0), (0, -big), (0, big)][side])
+            mb["mv"] = np.clip(mv, -32768, 32767)
+        mb["coeff_offset"] = m * RM.MB_COEFFS
+        if rng.random() < skip:
+            continue
+        split = mb["mode"] == RM.MODE_I4x4 if not mb["ref_frame"] else mb["partitioning"] == RM.PART_4x4
+        mb["y2"] = 0 if split else rng.integers(0, 3)
+        base = co[m * RM.MB_COEFFS:(m + 1) * RM.MB_COEFFS]
+        for b in range(24):
+            c = int(rng.choice([0, 1, 2], p=[0.3, 0.3, 0.4]))
+            set_code(mb, b, c)
+            if c:
+                blk = rng.integers(-300, 301, 16) if rng.random() < 0.9 else rng.integers(-32768, 32768, 16)
+                if c == 1:
+                    blk[1:] = 0
+                base[16 * b:16 * b + 16] = blk
+        if mb["y2"]:
+            base[384:400] = rng.integers(-2000, 2001, 16)
+            if mb["y2"] == 1:
+                base[385:400] = 0
+    return mbs, co
+
+
+def planes(seed, mb_w, mb_h):
+    rng = np.random.default_rng(seed)
+    return [rng.integers(0, 256, (16 * mb_h, 16 * mb_w), dtype=np.uint8), rng.integers(0, 256, (8 * mb_h, 8 * mb_w), dtype=np.uint8),
+            rng.integers(0, 256, (8 * mb_h, 8 * mb_w), dtype=np.uint8)]
+
+
+def border_class(mb_x, mb_y, mb_w, mb_h):
+    """0..8: (top, middle, bottom) x (left, middle, right); a one-macroblock axis counts as its first edge"""
+    cx = 0 if mb_x == 0 else 2 if mb_x == mb_w - 1 else 1
+    cy = 0 if mb_y == 0 else 2 if mb_y == mb_h - 1 else 1
+    return 3 * cy + cx
