@@ -293,6 +293,11 @@ def lib():
         "ffhip_hevc_inter_slice_record_size": (C.c_int, []),
         "ffhip_hevc_loop_filter_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_hevc_lf_ctb_record_size": (C.c_int, []),
+        "ffhip_hevc_boundary_strengths_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_hevc_boundary_strengths_pictures_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "ffhip_hevc_bs_mark_tu": (None, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "ffhip_hevc_bs_mvf_record_size": (C.c_int, []),
+        "ffhip_hevc_bs_slice_record_size": (C.c_int, []),
         "ffhip_hevc_residual_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_hevc_res_tu_record_size": (C.c_int, []),
         "ffhip_fdsp_batch_dev": (C.c_int, [C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_float, C.c_int,

@@ -120,6 +120,8 @@ int ffhip_launch_vp9_intra_frames(int bd, int ss_h, int ss_v, int width, int hei
 /* HEVC in-loop filtering of whole pictures (hevc_lf_pic.hip), arguments validated by ffhip_hevc_loop_filter_pictures_dev() */
 int ffhip_launch_hevc_loop_filter_pictures(int bd, int chroma_format_idc, int width, int height, int log2_ctb, int log2_min_cb, int npics,
                                            const FFHipHevcLfPic *pics, hipStream_t stream);
+/* HEVC deblocking boundary strengths of whole pictures (hevc_bs_pic.hip), arguments validated by ffhip_hevc_boundary_strengths_pictures_dev() */
+int ffhip_launch_hevc_boundary_strengths_pictures(int width, int height, int log2_ctb, int npics, const FFHipHevcBsPic *pics, hipStream_t stream);
 /* HEVC residuals of whole pictures (hevc_res_pic.hip), arguments validated by ffhip_hevc_residual_pictures_dev() */
 int ffhip_launch_hevc_residual_pictures(int bd, int chroma_format_idc, int npics, const FFHipHevcResPic *pics, hipStream_t stream);
 int ffhip_launch_hevc_loop_filter(uint8_t *base, ptrdiff_t stride, const FFHipHevcEdge *edges, int n, hipStream_t stream);

@@ -284,6 +284,57 @@ def loop_filter_pictures(pics, width, height, log2_ctb_size, log2_min_cb_size, c
                       "ffhip_hevc_loop_filter_pictures_dev")
 
 
+#: FFHipHevcMvField (include/ffhip.h): one 4 x 4 luma unit of the motion field.  mv: [list][x, y] in quarter samples; pred_flag: bit 0
+#: L0, bit 1 L1, 0 intra.
+BS_MVF_DTYPE = np.dtype([("mv", np.int16, (2, 2)), ("ref_idx", np.int8, 2), ("pred_flag", np.uint8), ("pad", np.uint8)])
+#: FFHipHevcBsSlice: ref[list][ref_idx] -> DPB slot; flags: bit 0 deblocking disabled, bit 1 loop filter across slices enabled.
+BS_SLICE_DTYPE = np.dtype([("ref", np.uint8, (2, 16)), ("num_ref", np.uint8, 2), ("flags", np.uint8), ("pad", np.uint8)])
+BS_TU_LEFT, BS_TU_TOP, BS_TU_CBF = 1, 2, 4
+BS_SLICE_DEBLOCK_OFF, BS_SLICE_ACROSS = 1, 2
+
+
+class BsPic(C.Structure):
+    """FFHipHevcBsPic"""
+    _fields_ = [("mvf", C.c_void_p), ("tu", C.c_void_p), ("ctb_slice", C.c_void_p), ("ctb_tile", C.c_void_p), ("slices", C.c_void_p),
+                ("bs_ver", C.c_void_p), ("bs_hor", C.c_void_p), ("mvf_stride", C.c_int32), ("tu_stride", C.c_int32),
+                ("bs_stride", C.c_int32), ("nslices", C.c_int32), ("loop_filter_across_tiles", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+def _bs_pics(pics, ptr):
+    arr = (BsPic * max(len(pics), 1))()
+    for i, m in enumerate(pics):
+        arr[i].mvf, arr[i].tu, arr[i].ctb_slice, arr[i].slices = ptr(m["mvf"]), ptr(m["tu"]), ptr(m["ctb_slice"]), ptr(m["slices"])
+        arr[i].ctb_tile = ptr(m["ctb_tile"]) if m.get("ctb_tile") is not None else None
+        arr[i].bs_ver, arr[i].bs_hor = ptr(m["bs_ver"]), ptr(m["bs_hor"])
+        arr[i].mvf_stride, arr[i].tu_stride, arr[i].bs_stride = m["mvf_stride"], m["tu_stride"], m["bs_stride"]
+        arr[i].nslices, arr[i].loop_filter_across_tiles = m["nslices"], int(bool(m.get("loop_filter_across_tiles", 1)))
+    return arr
+
+
+def boundary_strengths_pictures(pics, width, height, log2_ctb_size, stream=None):
+    """ffhip_hevc_boundary_strengths_pictures_dev on npics = len(pics) pictures of one geometry.  pics[i]: a dict with the device
+    tensors mvf (BS_MVF_DTYPE records as bytes), tu (uint8), ctb_slice (uint16 as int16 or bytes), slices (BS_SLICE_DTYPE records as
+    bytes), optionally ctb_tile (absent or None: one tile), the outputs bs_ver, bs_hor (uint8), and the ints mvf_stride, tu_stride,
+    bs_stride (entries), nslices, loop_filter_across_tiles.  bs_ver / bs_hor / bs_stride are what loop_filter_pictures() takes.
+    Asynchronous on `stream`."""
+    arr = _bs_pics(pics, lambda t: t.data_ptr())
+    return _lib.check(_lib.lib().ffhip_hevc_boundary_strengths_pictures_dev(width, height, log2_ctb_size, len(pics), C.cast(arr, C.c_void_p),
+                                                                            _stream(stream)), "ffhip_hevc_boundary_strengths_pictures_dev")
+
+
+def boundary_strengths_pictures_host(pics, width, height, log2_ctb_size):
+    """ffhip_hevc_boundary_strengths_pictures_host (device-free): as boundary_strengths_pictures() with numpy arrays; bs_ver / bs_hor
+    are written in place."""
+    arr = _bs_pics(pics, lambda a: a.ctypes.data)
+    return _lib.check(_lib.lib().ffhip_hevc_boundary_strengths_pictures_host(width, height, log2_ctb_size, len(pics), C.cast(arr, C.c_void_p)),
+                      "ffhip_hevc_boundary_strengths_pictures_host")
+
+
+def bs_mark_tu(tu, x0, y0, log2_size, cbf_luma):
+    """ffhip_hevc_bs_mark_tu (device-free) on a 2-D uint8 numpy map of 4 x 4 units"""
+    _lib.lib().ffhip_hevc_bs_mark_tu(tu.ctypes.data, tu.strides[0], x0, y0, log2_size, int(bool(cbf_luma)))
+
+
 RES_DCT, RES_DC, RES_DST, RES_SKIP, RES_BYPASS, RES_ZERO = 0, 1, 2, 3, 4, 5
 RES_ROTATE, RES_RDPCM_H, RES_RDPCM_V, RES_CROSS = 0x08, 0x10, 0x20, 0x40
 

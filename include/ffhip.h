@@ -1615,8 +1615,8 @@ int ffhip_hevc_intra_tu_record_size(void);
  *  The PUs of a CTB must be disjoint, as must the TUs of one plane of a CTB: overlapping ones leave undefined values where they
  *  overlap, inside that CTB, and nothing outside it.
  *  Out of scope: high_precision_offsets_enabled_flag (RExt; the reference's dsp scales offsets by << (bit_depth - 8)
- *  unconditionally, such streams keep the C path), MV derivation (merge / AMVP stay with the decoder), PCM and the deblocking
- *  boundary strengths. */
+ *  unconditionally, such streams keep the C path), MV derivation (merge / AMVP stay with the decoder) and PCM.  The deblocking
+ *  boundary strengths have a face of their own, ffhip_hevc_boundary_strengths_pictures_dev(). */
 typedef struct FFHipHevcInterPU {   /* one luma prediction block; it drives every plane, 20 bytes */
     uint16_t x, y;                  /* its top-left luma sample */
     uint8_t  w, h;                  /* 4..64, multiples of 4 (every partition mode, AMP included) */
@@ -1700,8 +1700,9 @@ int ffhip_hevc_inter_slice_record_size(void);
  *  Trusted (the ABI carries no lengths to check them against): the maps cover the picture at their strides, `ctbs` holds ctb_w *
  *  ctb_h records.  Whatever their contents, no read or write leaves the planes and maps: bS, QP and SAO values only select
  *  table entries after clipping, or skip.
- *  Stays with the decoder: the boundary strengths (slice_deblocking_filter_disabled_flag, the slice and tile restrictions included)
- *  and the SAO slice / tile flags below.  Out of scope: bS on the device, palette / SCC deblocking control, in-place filtering. */
+ *  Stays with the decoder: the SAO slice / tile flags below.  The boundary strengths (slice_deblocking_filter_disabled_flag, the
+ *  slice and tile restrictions included) come from the decoder or from ffhip_hevc_boundary_strengths_pictures_dev() below.
+ *  Out of scope: palette / SCC deblocking control, in-place filtering. */
 typedef struct FFHipHevcLfCtb {     /* one CTB, 44 bytes */
     int8_t   beta_offset, tc_offset;  /* 2 * slice_beta_offset_div2, 2 * slice_tc_offset_div2 of the CTB's slice */
     uint8_t  sao_type[3];           /* per component: 0 not applied, 1 band, 2 edge (SAOParams.type_idx after the slice's flags) */
@@ -1743,6 +1744,80 @@ int ffhip_hevc_loop_filter_pictures_dev(int bit_depth, int chroma_format_idc, in
                                         int log2_min_cb_size, int npics, const FFHipHevcLfPic *pics /* host array */, void *stream);
 /** sizeof(FFHipHevcLfCtb), for bindings that mirror the record (no device needed). */
 int ffhip_hevc_lf_ctb_record_size(void);
+
+/** Deblocking boundary strengths of whole pictures in one launch: the two maps the in-loop filter face reads (bs_ver / bs_hor of
+ *  FFHipHevcLfPic), made on the device from what the decoder parsed: the motion field, the transform tree, the slice and tile maps.
+ *  What libavcodec/hevc/filter.c's ff_hevc_deblocking_boundary_strengths() computes per transform unit (H.265 8.7.2.3 / 8.7.2.4), here
+ *  per 4-sample segment.  The rule below is restated from the standard and from the reference's documented behaviour, not checked
+ *  against the reference's source.
+ *
+ *  The grid is the 4 x 4 luma unit grid, w4 = width / 4 by h4 = height / 4.  The vertical segment of unit (ux, uy) has q = (ux, uy) and
+ *  p = (ux - 1, uy); the horizontal one has p = (ux, uy - 1).  The first rule that applies gives its bS:
+ *  1. ux (vertical) resp. uy (horizontal) odd, or 0 (the picture border): 0.
+ *  2. the slice of q's CTB has flags bit 0 (slice_deblocking_filter_disabled_flag): 0.
+ *  3. p and q lie in different slices and q's slice has flags bit 1 clear (slice_loop_filter_across_slices_enabled_flag == 0): 0;
+ *     p and q lie in different tiles and loop_filter_across_tiles == 0: 0.
+ *  4. q's tu marks that side as a transform-block edge and p or q is intra (pred_flag 0): 2.
+ *  5. q's tu marks that side as a transform-block edge and p's or q's tu has cbf_luma: 1.
+ *  6. otherwise motion decides, on every 8-sample line, marked or not (inside one prediction block both sides carry the same motion:
+ *     0).  A reference picture is its DPB slot, slices[slice of the unit's CTB].ref[list][ref_idx], each side through the slice of its
+ *     own CTB; two motion vectors differ when their x or their y components are at least 4 quarter samples apart.
+ *     - one of p, q intra: 2 (possible only on a TU edge, which rule 4 has taken); both intra: 0 (inside one TU);
+ *     - both bi-predicted, q from slots A0 / A1 and p from B0 / B1:
+ *         A0 == B0, A0 == A1 and B0 == B1: 1 iff (mv0s differ or mv1s differ) and (p's mv1 and q's mv0 differ or p's mv0 and q's mv1 differ);
+ *         else A0 == B0 and A1 == B1: 1 iff the mv0s differ or the mv1s differ;
+ *         else A0 == B1 and A1 == B0: 1 iff p's mv1 and q's mv0 differ or p's mv0 and q's mv1 differ;
+ *         else 1;
+ *     - both uni-predicted, each from either list: 1 if the slots differ, else 1 iff the two used motion vectors differ;
+ *     - one bi-predicted, one uni-predicted: 1.
+ *  Malformed input has a defined result and never causes an access outside the maps: a ctb_slice entry >= nslices makes the
+ *  segments of its units (as q) 0, and as p such a unit has no resolvable reference; a used ref_idx outside 0 .. num_ref - 1 (or
+ *  beyond 15) or an unresolvable reference names a picture different from every other, another such one included; a pred_flag above 3
+ *  counts as intra.
+ *  Every entry of bs_ver and bs_hor inside w4 x h4 is written (0 off the 8-sample grid); nothing outside is, and no input is written.
+ *  Stays with the decoder: the maps themselves (tab_mvf after merge / AMVP, the tu marks through ffhip_hevc_bs_mark_tu(), the slice
+ *  and tile ids per CTB).  Out of scope: palette / SCC deblocking control, pps_deblocking_control beyond the per-slice disabled flag. */
+typedef struct FFHipHevcMvField {   /* one 4 x 4 luma unit, 12 bytes: the decoder's tab_mvf entry */
+    int16_t mv[2][2];               /* [list][x, y], quarter samples */
+    int8_t  ref_idx[2];
+    uint8_t pred_flag;              /* bit 0 L0, bit 1 L1; 0: intra / PCM */
+    uint8_t pad;
+} FFHipHevcMvField;
+typedef struct FFHipHevcBsSlice {   /* 36 bytes */
+    uint8_t ref[2][16];             /* [list][ref_idx] -> DPB slot: the same numbering as FFHipHevcInterSlice.ref */
+    uint8_t num_ref[2];
+    uint8_t flags;                  /* bit 0 slice_deblocking_filter_disabled_flag, bit 1 slice_loop_filter_across_slices_enabled_flag */
+    uint8_t pad;
+} FFHipHevcBsSlice;
+typedef struct FFHipHevcBsPic {     /* _dev: device pointers; _host: host pointers */
+    const FFHipHevcMvField *mvf;    /* [uy * mvf_stride + ux], 4-byte aligned */
+    const uint8_t *tu;              /* [uy * tu_stride + ux]: bit 0 the unit's left side is a TU edge, bit 1 its top side, bit 2 cbf_luma of its TU */
+    const uint16_t *ctb_slice;      /* ctb_w * ctb_h, raster: index into slices (the slice, not the slice segment) */
+    const uint16_t *ctb_tile;       /* the same grid: tile id; NULL: one tile */
+    const FFHipHevcBsSlice *slices; /* nslices records */
+    uint8_t *bs_ver, *bs_hor;       /* out: FFHipHevcLfPic's layout, [uy * bs_stride + ux] */
+    int32_t mvf_stride, tu_stride, bs_stride, nslices;   /* strides in entries */
+    uint8_t loop_filter_across_tiles;  /* loop_filter_across_tiles_enabled_flag */
+    uint8_t pad[7];
+} FFHipHevcBsPic;
+/** npics pictures of one geometry: width x height luma samples (multiples of 8, at most 65535), CTBs of 1 << log2_ctb_size (4..6).
+ *  Pictures go 16 to a launch.  Asynchronous on `stream`; the maps are ready for ffhip_hevc_loop_filter_pictures_dev() on the same
+ *  stream with no synchronisation in between.
+ *  FFHIP_EINVAL for another CTB or picture size, npics <= 0, NULL mvf / tu / ctb_slice / slices / bs_ver / bs_hor, an mvf that is not
+ *  4-byte aligned, a stride below width / 4, nslices < 1, or an output map whose span (first to last entry) overlaps the span of any
+ *  input map or of any other output map of the call; FFHIP_ENOSYS without a device (after the argument checks). */
+int ffhip_hevc_boundary_strengths_pictures_dev(int width, int height, int log2_ctb_size, int npics,
+                                               const FFHipHevcBsPic *pics /* host array */, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free): the same arguments, refusals but FFHIP_ENOSYS, and bytes.
+ *  For pictures a decoder does not send to the GPU; the _dev face never calls it. */
+int ffhip_hevc_boundary_strengths_pictures_host(int width, int height, int log2_ctb_size, int npics, const FFHipHevcBsPic *pics);
+/** What a decoder calls per luma transform unit of 1 << log2_size (2..5) samples at (x0, y0) (multiples of 4) on a host tu map:
+ *  sets bit 0 on the units of the TU's left column, bit 1 on those of its top row, and bit 2 on all of them when cbf_luma.  The map
+ *  starts zeroed.  Device-free. */
+void ffhip_hevc_bs_mark_tu(uint8_t *tu, int tu_stride, int x0, int y0, int log2_size, int cbf_luma);
+/** sizeof(FFHipHevcMvField), sizeof(FFHipHevcBsSlice), for bindings that mirror the records (no device needed). */
+int ffhip_hevc_bs_mvf_record_size(void);
+int ffhip_hevc_bs_slice_record_size(void);
 
 /** Residuals of whole pictures in one launch: every transform unit of up to 16 pictures turned from its scaled coefficients into the
  *  final residual that the intra and inter picture faces take (their TU records' res_offset points at it).
