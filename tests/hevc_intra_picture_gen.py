@@ -45,7 +45,7 @@ class Picture:
     res[p]: the plane's int16 residuals."""
 
     def __init__(self, rng, width, height, log2_ctb, bd, cfi, p_intra=1.0, tiles=(1, 1), slices=1, cip=False, strong=None,
-                 no_smooth=None, p_res=0.5, modes=None, p_nxn=0.3):
+                 no_smooth=None, p_res=0.5, modes=None, p_nxn=0.3, inter_rows=()):
         assert width % 8 == 0 and height % 8 == 0
         self.rng, self.W, self.H, self.log2_ctb, self.bd, self.cfi, self.cip = rng, width, height, log2_ctb, bd, cfi, cip
         self.C = C = 1 << log2_ctb
@@ -56,6 +56,7 @@ class Picture:
         self.strong = bool(rng.integers(2)) if strong is None else strong
         self.no_smooth = bool(rng.integers(4) == 0) if no_smooth is None else no_smooth
         self.modes = modes
+        self.inter_rows = frozenset(inter_rows)                    # CTB rows whose CUs are all inter: rows without a record
         mx = (1 << bd) - 1
 
         # ---- tiles, tile-scan order, slices ----
@@ -113,7 +114,7 @@ class Picture:
                 for dx in (0, h):
                     self._cu_tree(a, x + dx, y + dy, log2 - 1)
             return
-        if self.rng.random() >= self.p_intra:
+        if (y >> self.log2_ctb) in self.inter_rows or self.rng.random() >= self.p_intra:
             self.intra[y >> 2:(y + s) >> 2, x >> 2:(x + s) >> 2] = False
             for p in range(self.nplanes):   # already reconstructed by MC and the residual add
                 hs, vs = self.hs[p], self.vs[p]

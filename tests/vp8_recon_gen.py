@@ -10,10 +10,13 @@ def set_code(mb, b, c):
     mb["block_code"][b >> 2] = (int(mb["block_code"][b >> 2]) & ~(3 << (2 * (b & 3)))) | (c << (2 * (b & 3)))
 
 
-def frame(seed, mb_w, mb_h, keyframe=False, intra=0.1, mv_range=40, refs=(1, 2, 3), parts=None, far=0.0, skip=0.15, i4=0.2):
+def frame(seed, mb_w, mb_h, keyframe=False, intra=0.1, mv_range=40, refs=(1, 2, 3), parts=None, far=0.0, skip=0.15, i4=0.2,
+          place=None, place_i4=()):
     """(mbs, coeffs): mb_w * mb_h records in raster order.  intra: the share of intra macroblocks of an inter frame; mv_range: luma MVs
     in quarter-pel, uniform in +-mv_range; far: the share of inter macroblocks whose MV points far outside the frame (any side); refs:
-    the references the records may name; parts: the partitionings to draw from; i4: the share of I4x4 among intra macroblocks."""
+    the references the records may name; parts: the partitionings to draw from; i4: the share of I4x4 among intra macroblocks.  place: the intra macroblocks placed, not drawn
+    (mb_w * mb_h truth values in raster order; `intra` is then unused); place_i4: raster indices of intra macroblocks that are I4x4
+    whatever the draw would say.  Without the two, a seed generates what it always has."""
     rng = np.random.default_rng(seed)
     n = mb_w * mb_h
     mbs = np.zeros(n, vp8.MB_DTYPE)
@@ -21,8 +24,8 @@ def frame(seed, mb_w, mb_h, keyframe=False, intra=0.1, mv_range=40, refs=(1, 2, 
     parts = list(range(5)) if parts is None else parts
     for m in range(n):
         mb = mbs[m]
-        if keyframe or rng.random() < intra:
-            mb["mode"] = RM.MODE_I4x4 if rng.random() < i4 else rng.integers(0, 4)
+        if keyframe or (rng.random() < intra if place is None else place[m]):
+            mb["mode"] = RM.MODE_I4x4 if m in place_i4 or rng.random() < i4 else rng.integers(0, 4)
             mb["chroma_mode"] = rng.integers(0, 4)
             if mb["mode"] == RM.MODE_I4x4:
                 mb["sub_mode"] = rng.integers(0, 10, 16)
