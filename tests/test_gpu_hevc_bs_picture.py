@@ -33,13 +33,10 @@ def upload(torch, pic, pad=0):
     return d, m
 
 
-def run(pics, pad=0):
-    torch = _torch()
+def compare(pics, up):
+    """the device maps of upload()'s (d, m) pairs against the host face and model A, guard bytes included; the inputs unchanged"""
+    import torch
     P0 = pics[0]
-    up = [upload(torch, p, pad) for p in pics]
-    hevc.boundary_strengths_pictures([d for d, _ in up], P0.W, P0.H, P0.log2_ctb)
-    assert _lib.lib().ffhip_stream_synchronize(None) == 0, _lib.lib().ffhip_last_error()
-    torch.cuda.synchronize()
     hevc.boundary_strengths_pictures_host([m for _, m in up], P0.W, P0.H, P0.log2_ctb)
     for k, (pic, (d, m)) in enumerate(zip(pics, up)):
         av, ah, _, _ = G.model_a_of(pic)
@@ -53,6 +50,16 @@ def run(pics, pad=0):
                 k, name, len(bad), (bad[:3] - [1, 0]).tolist(), got[tuple(bad[0])], exp[tuple(bad[0])])
         for key, before in d["_in"].items():
             assert torch.equal(d[key], before), "picture %d: %s was written" % (k, key)
+
+
+def run(pics, pad=0, stream=None):
+    torch = _torch()
+    P0 = pics[0]
+    up = [upload(torch, p, pad) for p in pics]
+    hevc.boundary_strengths_pictures([d for d, _ in up], P0.W, P0.H, P0.log2_ctb, stream=stream)
+    assert _lib.lib().ffhip_stream_synchronize(stream) == 0, _lib.lib().ffhip_last_error()
+    torch.cuda.synchronize()
+    compare(pics, up)
 
 
 @pytest.mark.parametrize("i", range(len(G.SET)))
@@ -88,32 +95,59 @@ def test_malformed_maps_give_the_defined_output():
     run([pic], pad=3)
 
 
-def test_chained_into_the_loop_filter_on_one_stream():
+class Chain:
     """_dev -> ffhip_hevc_loop_filter_pictures_dev with no synchronisation between them: the planes equal the planes filtered from
-    model A's maps uploaded from the host"""
-    import hevc_lf_picture_gen as LG
-    import test_gpu_hevc_lf_picture as TL
-    torch = _torch()
-    rng = np.random.default_rng(9304)
+    model A's maps uploaded from the host.  upload / call(stream) / compare, inputs() / outputs() as tests/picture_faces.py has them."""
+    name = "hevc_boundary_strengths+loop_filter"
     W, H, lc, bd, cfi = 264, 200, 5, 8, 1
-    bpic = G.BsPicture(rng, W, H, lc, tiles=(2, 2), nslices=3)
-    lf = LG.LfPicture(rng, W, H, lc, bd, cfi, tiles=(2, 2), nslices=3)
-    av, ah, _, _ = G.model_a_of(bpic)
-    assert {1, 2} <= set(av.ravel().tolist()) and {1, 2} <= set(ah.ravel().tolist())
-    # a: the maps made on the device, into the tensors the filter reads
-    (planes_a, maps_a), io_a = TL.upload(torch, lf, bs=(np.full_like(av, 0xEE), np.full_like(ah, 0xEE)))
-    d, _ = upload(torch, bpic)
-    d["bs_ver"], d["bs_hor"], d["bs_stride"] = maps_a["bs_ver"], maps_a["bs_hor"], maps_a["bs_stride"]
-    # b: model A's maps uploaded from the host
-    (planes_b, maps_b), io_b = TL.upload(torch, lf, bs=(av, ah))
+
+    def upload(self, torch):
+        import hevc_lf_picture_gen as LG
+        import test_gpu_hevc_lf_picture as TL
+        rng = np.random.default_rng(9304)
+        self.bpic = G.BsPicture(rng, self.W, self.H, self.lc, tiles=(2, 2), nslices=3)
+        self.lf = lf = LG.LfPicture(rng, self.W, self.H, self.lc, self.bd, self.cfi, tiles=(2, 2), nslices=3)
+        self.av, self.ah, _, _ = av, ah, _, _ = G.model_a_of(self.bpic)
+        assert {1, 2} <= set(av.ravel().tolist()) and {1, 2} <= set(ah.ravel().tolist())
+        # a: the maps made on the device, into the tensors the filter reads
+        (self.planes_a, self.maps_a), self.io_a = TL.upload(torch, lf, bs=(np.full_like(av, 0xEE), np.full_like(ah, 0xEE)))
+        self.d, _ = upload(torch, self.bpic)
+        self.d["bs_ver"], self.d["bs_hor"], self.d["bs_stride"] = self.maps_a["bs_ver"], self.maps_a["bs_hor"], self.maps_a["bs_stride"]
+        # b: model A's maps uploaded from the host
+        (self.planes_b, self.maps_b), self.io_b = TL.upload(torch, lf, bs=(av, ah))
+
+    def call(self, stream):
+        lf, kw = self.lf, dict(chroma_format_idc=self.cfi, bit_depth=self.bd, stream=stream)
+        hevc.boundary_strengths_pictures([self.d], self.W, self.H, self.lc, stream=stream)
+        hevc.loop_filter_pictures([(self.planes_a, self.maps_a)], self.W, self.H, self.lc, lf.lmc, **kw)
+        hevc.loop_filter_pictures([(self.planes_b, self.maps_b)], self.W, self.H, self.lc, lf.lmc, **kw)
+
+    def inputs(self):
+        ins = [self.d[k] for k in ("mvf", "tu", "ctb_slice", "slices", "ctb_tile") if self.d[k] is not None]
+        ins += [t for k, t in self.maps_a.items() if hasattr(t, "is_cuda") and k not in ("bs_ver", "bs_hor")]
+        return ins + [t for t in self.maps_b.values() if hasattr(t, "is_cuda")] + [s for io in (self.io_a, self.io_b) for s, _, _, _ in io]
+
+    def outputs(self):
+        return [self.maps_a["bs_ver"], self.maps_a["bs_hor"]] + [d for io in (self.io_a, self.io_b) for _, _, d, _ in io]
+
+    def compare(self, view=lambda t: t):
+        import hevc_lf_picture_gen as LG
+        import test_gpu_hevc_lf_picture as TL
+        lf = self.lf
+        lf.bs_ver, lf.bs_hor = self.av, self.ah
+        want = LG.model(lf)
+        TL.compare(lf, [(s, sh, view(d), dh) for s, sh, d, dh in self.io_b], want)
+        TL.compare(lf, [(s, sh, view(d), dh) for s, sh, d, dh in self.io_a], want)
+        assert any((w != s).any() for w, s in zip(want, lf.src))
+
+
+def test_chained_into_the_loop_filter_on_one_stream():
+    """Chain on the NULL stream (tests/test_gpu_picture_streams.py runs it on a created one)"""
+    torch = _torch()
+    chain = Chain()
+    chain.upload(torch)
     torch.cuda.synchronize()
-    hevc.boundary_strengths_pictures([d], W, H, lc)
-    hevc.loop_filter_pictures([(planes_a, maps_a)], W, H, lc, lf.lmc, chroma_format_idc=cfi, bit_depth=bd)
-    hevc.loop_filter_pictures([(planes_b, maps_b)], W, H, lc, lf.lmc, chroma_format_idc=cfi, bit_depth=bd)
+    chain.call(None)
     assert _lib.lib().ffhip_stream_synchronize(None) == 0, _lib.lib().ffhip_last_error()
     torch.cuda.synchronize()
-    lf.bs_ver, lf.bs_hor = av, ah
-    want = LG.model(lf)
-    TL.compare(lf, io_b, want)
-    TL.compare(lf, io_a, want)
-    assert any((w != s).any() for w, s in zip(want, lf.src))
+    chain.compare()

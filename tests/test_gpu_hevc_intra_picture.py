@@ -17,11 +17,8 @@ def _torch():
     return torch
 
 
-def run(pics, extra=0, recs=None):
-    """reconstruct the pictures (one geometry) in one call; compare every plane, padding included, with the model.
-    extra: bytes of stride padding beyond the plane (a sentinel there must survive); recs: per picture, per plane record lists
-    to send instead of the generator's (the model still uses the generator's)"""
-    torch = _torch()
+def upload(torch, pics, extra=0, recs=None):
+    """(the face's list of pictures, per plane (pic, p, host image, device plane, stride, h, w), tensors to keep alive)"""
     P0 = pics[0]
     ps = 1 if P0.bd == 8 else 2
     dt = np.uint8 if ps == 1 else np.uint16
@@ -42,11 +39,15 @@ def run(pics, extra=0, recs=None):
             planes.append((d_plane, stride, d_tus, d_st, d_res))
             hosts.append((pic, p, host, d_plane, stride, h, w))
         args.append(planes)
-    hevc.intra_pictures(args, P0.W, P0.H, P0.log2_ctb, chroma_format_idc=P0.cfi, bit_depth=P0.bd)
-    assert _lib.lib().ffhip_stream_synchronize(None) == 0, _lib.lib().ffhip_last_error()
-    torch.cuda.synchronize()
-    models = {}
+    return args, hosts, keep
+
+
+def compare(hosts, models=None):
+    """every plane of upload()'s `hosts`, padding included, against the model (models: id(pic) -> planes; computed here when absent)"""
+    models = {} if models is None else models
     for pic, p, host, d_plane, stride, h, w in hosts:
+        ps = 1 if pic.bd == 8 else 2
+        dt = np.uint8 if ps == 1 else np.uint16
         if id(pic) not in models:
             models[id(pic)] = G.model(pic)
         want = host.copy()
@@ -55,6 +56,19 @@ def run(pics, extra=0, recs=None):
         bad = np.argwhere(got != want)
         assert not len(bad), "plane %d: %d mismatches, first (row, byte) %s: got %s want %s" % (
             p, len(bad), bad[:3].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def run(pics, extra=0, recs=None, stream=None):
+    """reconstruct the pictures (one geometry) in one call; compare every plane, padding included, with the model.
+    extra: bytes of stride padding beyond the plane (a sentinel there must survive); recs: per picture, per plane record lists
+    to send instead of the generator's (the model still uses the generator's)"""
+    torch = _torch()
+    P0 = pics[0]
+    args, hosts, keep = upload(torch, pics, extra, recs)
+    hevc.intra_pictures(args, P0.W, P0.H, P0.log2_ctb, chroma_format_idc=P0.cfi, bit_depth=P0.bd, stream=stream)
+    assert _lib.lib().ffhip_stream_synchronize(stream) == 0, _lib.lib().ffhip_last_error()
+    torch.cuda.synchronize()
+    compare(hosts)
 
 
 GRID = [(bd, cfi, log2_ctb) for bd in (8, 10, 12) for cfi in (0, 1, 2, 3) for log2_ctb in (4, 5, 6)]

@@ -36,17 +36,22 @@ def _sync():
     assert _lib.lib().ffhip_stream_synchronize(None) == 0, _lib.lib().ffhip_last_error()
 
 
-def _run_and_check(pics, bd, cfi):
-    torch = _torch()
-    dev = _upload(torch, pics)
-    hevc.residual_pictures(dev, chroma_format_idc=cfi, bit_depth=bd)
-    _sync()
+def _compare(pics, dev, bd, cfi, wants=None):
+    """the res buffers of _upload()'s tensors against the model (computed here unless given), the coefficients unchanged"""
     for i, planes in enumerate(pics):
-        want = G.model(planes, bd, cfi, fill=SENT)
+        want = G.model(planes, bd, cfi, fill=SENT) if wants is None else wants[i]
         for p, D in enumerate(planes):
             got = dev[i][p][1].cpu().numpy()
             assert np.array_equal(got, want[p]), (i, p, np.nonzero(got != want[p])[0][:8])
             assert np.array_equal(dev[i][p][0].cpu().numpy(), D.coeffs), "coeffs were written"
+
+
+def _run_and_check(pics, bd, cfi, stream=None):
+    torch = _torch()
+    dev = _upload(torch, pics)
+    hevc.residual_pictures(dev, chroma_format_idc=cfi, bit_depth=bd, stream=stream)
+    assert _lib.lib().ffhip_stream_synchronize(stream) == 0, _lib.lib().ffhip_last_error()
+    _compare(pics, dev, bd, cfi)
     return dev
 
 
@@ -203,89 +208,128 @@ def test_same_residuals_as_the_batch_path(bd):
     assert n_checked > 500
 
 
-@pytest.mark.parametrize("bd,cfi", [(8, 0), (8, 1), (10, 2), (10, 3), (8, 3), (12, 1)])
-def test_chained_into_inter_intra_and_loop_filter_pictures(bd, cfi):
+class Chain:
     """residual face -> inter pictures -> intra pictures -> loop filter pictures on one stream, with no host sync in between: the DPB
     planes equal those of the same chain of models fed with the model's residuals.  One residual launch makes both res buffers per
-    plane (the inter TUs' and the intra TUs', as two pictures of the call); the faces take them at the TU records' res_offset."""
-    import hevc_inter_picture_gen as PG
-    import hevc_intra_picture_gen as IG
-    import hevc_lf_picture_gen as LG
-    import test_gpu_hevc_inter_picture as TI
-    import test_gpu_hevc_lf_picture as TL
+    plane (the inter TUs' and the intra TUs', as two pictures of the call); the faces take them at the TU records' res_offset.
+    upload() draws the pictures and puts them on the device, call(stream) queues the four faces, compare() runs the models;
+    inputs() / outputs() are the device tensors the chain only reads / writes (tests/picture_faces.py: run_staged)."""
+    name = "hevc_residual+inter+intra+loop_filter"
+
+    def __init__(self, bd, cfi):
+        self.bd, self.cfi = bd, cfi
+
+    def upload(self, torch):
+        import hevc_inter_picture_gen as PG
+        import hevc_intra_picture_gen as IG
+        import hevc_lf_picture_gen as LG
+        import test_gpu_hevc_inter_picture as TI
+        import test_gpu_hevc_lf_picture as TL
+        bd, cfi = self.bd, self.cfi
+        rng = np.random.default_rng(9100 + 10 * bd + cfi)
+        W, H, lc = self.geom = 192, 128, 5
+        hs, vs = int(cfi in (1, 2)), int(cfi == 1)
+        ip = IG.Picture(rng, W, H, lc, bd, cfi, p_intra=0.5)
+        pic = PG.InterPicture(rng, W, H, lc, bd, cfi, nrefs=3, nslices=1, slice_types=["P"], p_inter=1.0, p_pcm=0.0)
+        nplanes = pic.nplanes
+        pus, tus = [], [[] for _ in range(nplanes)]
+        blocks, nres = [[] for _ in range(nplanes)], [0] * nplanes
+        for y in range(0, H, 8):
+            for x in range(0, W, 8):
+                if ip.intra[y >> 2, x >> 2]:
+                    continue
+                a = (y >> lc) * pic.ctb_w + (x >> lc)
+                pus.append(dict(x=x, y=y, w=8, h=8, flags=1, ref_idx=[int(rng.integers(0, pic.slices[0]["num_ref"][0])), 0], slice=0,
+                                mv=[[int(v) for v in rng.integers(-80, 81, 2)], [0, 0]], ctb=a, part="2Nx2N"))
+                for p in range(nplanes):
+                    # the CU's transform blocks: 8x8 luma; chroma 4x4 (4:2:0), two 4x4 stacked (4:2:2), 8x8 (4:4:4)
+                    if p == 0 or cfi == 3:
+                        boxes = [(x, y, 3)]
+                    else:
+                        boxes = [(x >> hs, (y >> vs) + 4 * j, 2) for j in range(1 if vs else 2)]
+                    for bx, by, log2 in boxes:
+                        if rng.random() < 0.15:          # cbf 0: no residual
+                            continue
+                        tus[p].append(dict(x=bx, y=by, res_offset=nres[p], log2_size=log2, ctb=a))
+                        blocks[p].append((bx, by, log2, nres[p]))
+                        nres[p] += 1 << (2 * log2)
+        pic.pus, pic.tus = pus, tus
+        inter_planes = G.planes_for_blocks(rng, blocks, [max(n, 16) for n in nres], cfi, intra=False)
+        iblocks = [[(r["x"], r["y"], r["log2_size"], r["res_offset"]) for r in ip.recs[p] if r["res_offset"] >= 0] for p in range(nplanes)]
+        intra_planes = G.planes_for_blocks(rng, iblocks, [ip.res[p].size for p in range(nplanes)], cfi, intra=True)
+        assert any(int(t["kind_flags"]) & G.CROSS for D in inter_planes + intra_planes for t in D.tus) == (cfi == 3)
+        dev = _upload(torch, [inter_planes, intra_planes])
+        # the faces' inputs; their res buffers are the residual face's outputs
+        pic.res = [np.zeros(max(n, 16), np.int16) for n in nres]
+        start = [pl.copy() for pl in ip.planes]
+        a, dst, keep = TI.upload(torch, pic, planes=start)
+        for p in range(nplanes):
+            d, st, d_tus, d_st, _ = a[0][p]
+            a[0][p] = (d, st, d_tus, d_st, dev[0][p][1])
+        intra_args = []
+        for p in range(nplanes):
+            arr, starts = ip.pack(p, dtype=hevc.INTRA_TU_DTYPE)
+            d_tus = torch.from_numpy(arr.view(np.uint8).copy()).cuda()
+            d_st = torch.from_numpy(starts).cuda()
+            keep += [d_tus, d_st]
+            intra_args.append((dst[p][1], a[0][p][1], d_tus, d_st, dev[1][p][1]))
+        lf = LG.LfPicture(rng, W, H, lc, bd, cfi, tiles=(2, 1), nslices=2)
+        maps = TL.upload_maps(torch, lf)
+        outs, lf_planes = [], []
+        for p in range(lf.nplanes):
+            h, w = lf.src[p].shape
+            ds = TL._stride(w, bd, 16)
+            dh = np.full((h, ds), 0x5A, np.uint8)
+            d = torch.from_numpy(dh.copy()).cuda()
+            outs.append((d, dh))
+            lf_planes.append((dst[p][1], a[0][p][1], d, ds))
+        self.ip, self.pic, self.lf, self.start = ip, pic, lf, start
+        self.inter_planes, self.intra_planes = inter_planes, intra_planes
+        self.dev, self.a, self.dst, self.keep, self.intra_args, self.maps, self.outs, self.lf_planes = dev, a, dst, keep, intra_args, maps, outs, lf_planes
+
+    def call(self, stream):
+        (W, H, lc), bd, cfi = self.geom, self.bd, self.cfi
+        hevc.residual_pictures(self.dev, chroma_format_idc=cfi, bit_depth=bd, stream=stream)
+        hevc.inter_pictures([self.a], W, H, lc, chroma_format_idc=cfi, bit_depth=bd, stream=stream)
+        hevc.intra_pictures([self.intra_args], W, H, lc, chroma_format_idc=cfi, bit_depth=bd, stream=stream)
+        hevc.loop_filter_pictures([(self.lf_planes, self.maps)], W, H, lc, self.lf.lmc, chroma_format_idc=cfi, bit_depth=bd, stream=stream)
+
+    def inputs(self):
+        pl, pus, pst, sl, refs = self.a
+        ins = [t for d in self.dev for q in d for t in (q[0], q[2])] + [t for q in pl for t in q[2:4]] + [pus, pst, sl]
+        ins += [t for ref in refs for t, _ in ref] + [t for q in self.intra_args for t in q[2:4]]
+        return ins + [t for t in self.maps.values() if hasattr(t, "is_cuda")]
+
+    def outputs(self):
+        """the res buffers, the DPB planes reconstructed in place, the filtered planes"""
+        return [q[1] for d in self.dev for q in d] + [d for _, d in self.dst] + [d for d, _ in self.outs]
+
+    def compare(self, view=lambda t: t):
+        import hevc_inter_picture_gen as PG
+        import hevc_intra_picture_gen as IG
+        import hevc_lf_picture_gen as LG
+        bd, cfi, pic, ip = self.bd, self.cfi, self.pic, self.ip
+        # the same chain of models, fed with the model's residuals
+        pic.res = G.model(self.inter_planes, bd, cfi)
+        ip.res = G.model(self.intra_planes, bd, cfi)
+        ip.planes = PG.model(pic, planes=self.start)
+        recon = IG.model(ip)
+        want = LG.model(self.lf, planes=recon)
+        ps = 1 if bd == 8 else 2
+        for p, (d, dh) in enumerate(self.outs):
+            h, w = want[p].shape
+            exp = dh.copy()
+            exp[:, :w * ps] = want[p].astype(np.uint8 if bd == 8 else np.uint16).view(np.uint8).reshape(h, w * ps)
+            assert np.array_equal(view(d).cpu().numpy(), exp), "plane %d differs from the chained models" % p
+
+
+@pytest.mark.parametrize("bd,cfi", [(8, 0), (8, 1), (10, 2), (10, 3), (8, 3), (12, 1)])
+def test_chained_into_inter_intra_and_loop_filter_pictures(bd, cfi):
+    """Chain on the NULL stream (tests/test_gpu_picture_streams.py runs it on a created one)"""
     torch = _torch()
-    rng = np.random.default_rng(9100 + 10 * bd + cfi)
-    W, H, lc = 192, 128, 5
-    hs, vs = int(cfi in (1, 2)), int(cfi == 1)
-    ip = IG.Picture(rng, W, H, lc, bd, cfi, p_intra=0.5)
-    pic = PG.InterPicture(rng, W, H, lc, bd, cfi, nrefs=3, nslices=1, slice_types=["P"], p_inter=1.0, p_pcm=0.0)
-    nplanes = pic.nplanes
-    pus, tus = [], [[] for _ in range(nplanes)]
-    blocks, nres = [[] for _ in range(nplanes)], [0] * nplanes
-    for y in range(0, H, 8):
-        for x in range(0, W, 8):
-            if ip.intra[y >> 2, x >> 2]:
-                continue
-            a = (y >> lc) * pic.ctb_w + (x >> lc)
-            pus.append(dict(x=x, y=y, w=8, h=8, flags=1, ref_idx=[int(rng.integers(0, pic.slices[0]["num_ref"][0])), 0], slice=0,
-                            mv=[[int(v) for v in rng.integers(-80, 81, 2)], [0, 0]], ctb=a, part="2Nx2N"))
-            for p in range(nplanes):
-                # the CU's transform blocks: 8x8 luma; chroma 4x4 (4:2:0), two 4x4 stacked (4:2:2), 8x8 (4:4:4)
-                if p == 0 or cfi == 3:
-                    boxes = [(x, y, 3)]
-                else:
-                    boxes = [(x >> hs, (y >> vs) + 4 * j, 2) for j in range(1 if vs else 2)]
-                for bx, by, log2 in boxes:
-                    if rng.random() < 0.15:          # cbf 0: no residual
-                        continue
-                    tus[p].append(dict(x=bx, y=by, res_offset=nres[p], log2_size=log2, ctb=a))
-                    blocks[p].append((bx, by, log2, nres[p]))
-                    nres[p] += 1 << (2 * log2)
-    pic.pus, pic.tus = pus, tus
-    inter_planes = G.planes_for_blocks(rng, blocks, [max(n, 16) for n in nres], cfi, intra=False)
-    iblocks = [[(r["x"], r["y"], r["log2_size"], r["res_offset"]) for r in ip.recs[p] if r["res_offset"] >= 0] for p in range(nplanes)]
-    intra_planes = G.planes_for_blocks(rng, iblocks, [ip.res[p].size for p in range(nplanes)], cfi, intra=True)
-    assert any(int(t["kind_flags"]) & G.CROSS for D in inter_planes + intra_planes for t in D.tus) == (cfi == 3)
-    dev = _upload(torch, [inter_planes, intra_planes])
-    # the faces' inputs; their res buffers are the residual face's outputs
-    pic.res = [np.zeros(max(n, 16), np.int16) for n in nres]
-    start = [pl.copy() for pl in ip.planes]
-    a, dst, keep = TI.upload(torch, pic, planes=start)
-    for p in range(nplanes):
-        d, st, d_tus, d_st, _ = a[0][p]
-        a[0][p] = (d, st, d_tus, d_st, dev[0][p][1])
-    intra_args = []
-    for p in range(nplanes):
-        arr, starts = ip.pack(p, dtype=hevc.INTRA_TU_DTYPE)
-        d_tus = torch.from_numpy(arr.view(np.uint8).copy()).cuda()
-        d_st = torch.from_numpy(starts).cuda()
-        keep += [d_tus, d_st]
-        intra_args.append((dst[p][1], a[0][p][1], d_tus, d_st, dev[1][p][1]))
-    lf = LG.LfPicture(rng, W, H, lc, bd, cfi, tiles=(2, 1), nslices=2)
-    maps = TL.upload_maps(torch, lf)
-    outs, lf_planes = [], []
-    for p in range(lf.nplanes):
-        h, w = lf.src[p].shape
-        ds = TL._stride(w, bd, 16)
-        dh = np.full((h, ds), 0x5A, np.uint8)
-        d = torch.from_numpy(dh.copy()).cuda()
-        outs.append((d, dh))
-        lf_planes.append((dst[p][1], a[0][p][1], d, ds))
-    hevc.residual_pictures(dev, chroma_format_idc=cfi, bit_depth=bd)
-    hevc.inter_pictures([a], W, H, lc, chroma_format_idc=cfi, bit_depth=bd)
-    hevc.intra_pictures([intra_args], W, H, lc, chroma_format_idc=cfi, bit_depth=bd)
-    hevc.loop_filter_pictures([(lf_planes, maps)], W, H, lc, lf.lmc, chroma_format_idc=cfi, bit_depth=bd)
+    chain = Chain(bd, cfi)
+    chain.upload(torch)
+    chain.call(None)
     _sync()
     torch.cuda.synchronize()
-    # the same chain of models, fed with the model's residuals
-    pic.res = G.model(inter_planes, bd, cfi)
-    ip.res = G.model(intra_planes, bd, cfi)
-    ip.planes = PG.model(pic, planes=start)
-    recon = IG.model(ip)
-    want = LG.model(lf, planes=recon)
-    ps = 1 if bd == 8 else 2
-    for p, (d, dh) in enumerate(outs):
-        h, w = want[p].shape
-        exp = dh.copy()
-        exp[:, :w * ps] = want[p].astype(np.uint8 if bd == 8 else np.uint16).view(np.uint8).reshape(h, w * ps)
-        assert np.array_equal(d.cpu().numpy(), exp), "plane %d differs from the chained models" % p
+    chain.compare()

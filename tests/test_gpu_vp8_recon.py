@@ -42,10 +42,9 @@ def _up(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
 
 
-def _run(frames, mb_w, mb_h, bilinear=0, fullpel=0, pad=(16, 12)):
-    """frames: [(mbs, coeffs, refs (host planes or None), initial planes)]; returns the device's frames as host arrays, after checking
-    that the stride padding, the references and the coefficients are as they were"""
-    torch = _torch()
+def _upload(torch, frames, mb_w, mb_h, pad=(16, 12)):
+    """frames: [(mbs, coeffs, refs (host planes or None), initial planes)]; (the face's pictures, per frame the device (planes,
+    references, coefficients), the strides)"""
     sy, suv = 16 * mb_w + pad[0], 8 * mb_w + pad[1]
     pics, keep = [], []
     for mbs, co, refs, init in frames:
@@ -54,8 +53,12 @@ def _run(frames, mb_w, mb_h, bilinear=0, fullpel=0, pad=(16, 12)):
         dco = torch.from_numpy(co.copy()).cuda() if len(co) else None
         pics.append(dict(y=d[0], u=d[1], v=d[2], refs=dr, mbs=_up(torch, mbs), coeffs=dco))
         keep.append((d, dr, dco))
-    vp8.recon_frames(pics, mb_w, mb_h, sy, suv, bilinear, fullpel)
-    _sync()
+    return pics, keep, sy, suv
+
+
+def _download(frames, keep, sy, suv):
+    """the device's frames as host arrays, after checking that the stride padding, the references and the coefficients are as they
+    were"""
     got = []
     for (mbs, co, refs, init), (d, dr, dco) in zip(frames, keep):
         out = []
@@ -71,6 +74,15 @@ def _run(frames, mb_w, mb_h, bilinear=0, fullpel=0, pad=(16, 12)):
             assert np.array_equal(dco.cpu().numpy(), co), "the coefficients were written"
         got.append(out)
     return got
+
+
+def _run(frames, mb_w, mb_h, bilinear=0, fullpel=0, pad=(16, 12), stream=None):
+    """reconstruct the frames in one call; returns the device's frames as host arrays (see _download)"""
+    torch = _torch()
+    pics, keep, sy, suv = _upload(torch, frames, mb_w, mb_h, pad)
+    vp8.recon_frames(pics, mb_w, mb_h, sy, suv, bilinear, fullpel, stream=stream)
+    assert _lib.lib().ffhip_stream_synchronize(stream) == 0
+    return _download(frames, keep, sy, suv)
 
 
 def _check(got, want, what=""):
@@ -194,30 +206,54 @@ def test_batch_face_route_equals_the_frame_face(seed, key, bilinear, fullpel):
     _check(route.result(), face, "batch route")
 
 
-def test_chain_with_the_loop_filter():
-    """recon_frames then loopfilter_frames on one stream, twice: the second frame predicts from the first filtered one"""
-    torch = _torch()
+class Chain:
+    """recon_frames then loopfilter_frames on one stream, twice: the second frame predicts from the first filtered one.
+    upload / call(stream) / compare, inputs() / outputs() as tests/picture_faces.py has them."""
+    name = "vp8_recon+loopfilter"
     mb_w, mb_h, sy, suv = 9, 7, 16 * 9 + 16, 8 * 9 + 8
-    rng = np.random.default_rng(21)
-    st = np.zeros((mb_h, mb_w), vp8.STRENGTH_DTYPE)
-    st["filter_level"], st["inner_limit"], st["inner_filter"] = rng.integers(0, 64, st.shape), rng.integers(0, 10, st.shape), rng.integers(0, 2, st.shape)
-    k_mbs, k_co = G.frame(31, mb_w, mb_h, keyframe=True)
-    i_mbs, i_co = G.frame(32, mb_w, mb_h, intra=0.15, refs=(1,))
-    # the model
-    w1 = RM.recon_frame(G.planes(1, mb_w, mb_h), k_mbs, k_co, [None] * 3, mb_w, mb_h)
-    M.loop_filter_frame(w1[0], w1[1], w1[2], st, 0, 1)
-    w2 = RM.recon_frame(G.planes(2, mb_w, mb_h), i_mbs, i_co, [w1, None, None], mb_w, mb_h)
-    M.loop_filter_frame(w2[0], w2[1], w2[2], st, 0, 0)
-    # the device: four calls on the stream, one wait
-    d1 = [_up(torch, a) for a in _padded(G.planes(1, mb_w, mb_h), sy, suv)]
-    d2 = [_up(torch, a) for a in _padded(G.planes(2, mb_w, mb_h), sy, suv)]
-    dst = _up(torch, st)
-    keep = [_up(torch, k_mbs), torch.from_numpy(k_co.copy()).cuda(), _up(torch, i_mbs), torch.from_numpy(i_co.copy()).cuda()]
-    vp8.recon_frames([dict(y=d1[0], u=d1[1], v=d1[2], refs=None, mbs=keep[0], coeffs=keep[1])], mb_w, mb_h, sy, suv)
-    vp8.loopfilter_frames([(d1[0], d1[1], d1[2], dst)], 0, 1, mb_w, mb_h, sy, suv)
-    vp8.recon_frames([dict(y=d2[0], u=d2[1], v=d2[2], refs=[d1, None, None], mbs=keep[2], coeffs=keep[3])], mb_w, mb_h, sy, suv)
-    vp8.loopfilter_frames([(d2[0], d2[1], d2[2], dst)], 0, 0, mb_w, mb_h, sy, suv)
+
+    def upload(self, torch):
+        mb_w, mb_h, sy, suv = self.mb_w, self.mb_h, self.sy, self.suv
+        rng = np.random.default_rng(21)
+        self.st = st = np.zeros((mb_h, mb_w), vp8.STRENGTH_DTYPE)
+        st["filter_level"], st["inner_limit"], st["inner_filter"] = rng.integers(0, 64, st.shape), rng.integers(0, 10, st.shape), rng.integers(0, 2, st.shape)
+        self.k_mbs, self.k_co = G.frame(31, mb_w, mb_h, keyframe=True)
+        self.i_mbs, self.i_co = G.frame(32, mb_w, mb_h, intra=0.15, refs=(1,))
+        self.d1 = [_up(torch, a) for a in _padded(G.planes(1, mb_w, mb_h), sy, suv)]
+        self.d2 = [_up(torch, a) for a in _padded(G.planes(2, mb_w, mb_h), sy, suv)]
+        self.dst = _up(torch, st)
+        self.keep = [_up(torch, self.k_mbs), torch.from_numpy(self.k_co.copy()).cuda(), _up(torch, self.i_mbs), torch.from_numpy(self.i_co.copy()).cuda()]
+
+    def call(self, stream):
+        """the device: four calls on the stream, no wait"""
+        mb_w, mb_h, sy, suv, d1, d2, keep = self.mb_w, self.mb_h, self.sy, self.suv, self.d1, self.d2, self.keep
+        vp8.recon_frames([dict(y=d1[0], u=d1[1], v=d1[2], refs=None, mbs=keep[0], coeffs=keep[1])], mb_w, mb_h, sy, suv, stream=stream)
+        vp8.loopfilter_frames([(d1[0], d1[1], d1[2], self.dst)], 0, 1, mb_w, mb_h, sy, suv, stream=stream)
+        vp8.recon_frames([dict(y=d2[0], u=d2[1], v=d2[2], refs=[d1, None, None], mbs=keep[2], coeffs=keep[3])], mb_w, mb_h, sy, suv, stream=stream)
+        vp8.loopfilter_frames([(d2[0], d2[1], d2[2], self.dst)], 0, 0, mb_w, mb_h, sy, suv, stream=stream)
+
+    def inputs(self):
+        return [self.dst] + self.keep
+
+    def outputs(self):
+        return self.d1 + self.d2
+
+    def compare(self, view=lambda t: t):
+        mb_w, mb_h, st = self.mb_w, self.mb_h, self.st
+        # the model
+        w1 = RM.recon_frame(G.planes(1, mb_w, mb_h), self.k_mbs, self.k_co, [None] * 3, mb_w, mb_h)
+        M.loop_filter_frame(w1[0], w1[1], w1[2], st, 0, 1)
+        w2 = RM.recon_frame(G.planes(2, mb_w, mb_h), self.i_mbs, self.i_co, [w1, None, None], mb_w, mb_h)
+        M.loop_filter_frame(w2[0], w2[1], w2[2], st, 0, 0)
+        for d, w, what in ((self.d1, w1, "key frame"), (self.d2, w2, "inter frame")):
+            got = [view(d[p]).cpu().numpy().reshape(w[p].shape[0], -1)[:, :w[p].shape[1]] for p in range(3)]
+            _check(got, w, what)
+
+
+def test_chain_with_the_loop_filter():
+    """Chain on the NULL stream (tests/test_gpu_picture_streams.py runs it on a created one)"""
+    chain = Chain()
+    chain.upload(_torch())
+    chain.call(None)
     _sync()
-    for d, w, what in ((d1, w1, "key frame"), (d2, w2, "inter frame")):
-        got = [d[p].cpu().numpy().reshape(w[p].shape[0], -1)[:, :w[p].shape[1]] for p in range(3)]
-        _check(got, w, what)
+    chain.compare()

@@ -283,9 +283,10 @@ def _strengths(rng, mb_h, mb_w):
     return st
 
 
-def _frame_case(torch, rng, npics, mb_w, mb_h, filter_type, keyframe):
+def _frame_host(rng, npics, mb_w, mb_h, filter_type, keyframe):
+    """(per frame the buffers (Y, U, V, strengths), per frame the model's buffers, the strides) on the host"""
     sy, suv = 16 * mb_w + 4 * int(rng.integers(1, 9)), 8 * mb_w + 4 * int(rng.integers(1, 9))
-    hosts, pics, keep, wants = [], [], [], []
+    frames, wants = [], []
     for _ in range(npics):
         Y = rng.integers(0, 256, (16 * mb_h + 3, sy)).astype(np.uint8)  # stride padding and rows below: garbage that must stay
         U = rng.integers(0, 256, (8 * mb_h + 3, suv)).astype(np.uint8)
@@ -296,20 +297,45 @@ def _frame_case(torch, rng, npics, mb_w, mb_h, filter_type, keyframe):
         st = _strengths(rng, mb_h, mb_w)
         w = [Y.copy(), U.copy(), V.copy()]
         M.loop_filter_frame(w[0], w[1], w[2], st, filter_type, keyframe)
+        frames.append((Y, U, V, st))
+        wants.append(w)
+    return frames, wants, sy, suv
+
+
+def _frames_to_device(torch, frames):
+    """_frame_host()'s frames on the device: (the face's pictures, per frame the device planes, tensors to keep alive)"""
+    hosts, pics, keep = [], [], []
+    for Y, U, V, st in frames:
         d = [torch.from_numpy(a.copy()).cuda() for a in (Y, U, V)]
         ds = torch.from_numpy(st.view(np.uint8).reshape(-1).copy()).cuda()
         keep += d + [ds]
         pics.append((d[0], d[1], d[2], ds))
-        wants.append(w)
         hosts.append(d)
-    vp8.loopfilter_frames(pics, filter_type, keyframe, mb_w, mb_h, sy, suv)
-    _sync()
+    return pics, hosts, keep
+
+
+def _frame_upload(torch, rng, npics, mb_w, mb_h, filter_type, keyframe):
+    """(the face's pictures, per frame the device planes, per frame the model's buffers, the strides, tensors to keep alive)"""
+    frames, wants, sy, suv = _frame_host(rng, npics, mb_w, mb_h, filter_type, keyframe)
+    pics, hosts, keep = _frames_to_device(torch, frames)
+    return pics, hosts, wants, sy, suv, keep
+
+
+def _frame_compare(hosts, wants):
+    """whole buffers, stride padding and the rows below included"""
     for i, (d, w) in enumerate(zip(hosts, wants)):
         for p in range(3):
             g = d[p].cpu().numpy()
             if not np.array_equal(g, w[p]):
                 bad = np.argwhere(g != w[p])
                 raise AssertionError("frame %d plane %d: %d samples differ, first at %s" % (i, p, len(bad), bad[0]))
+
+
+def _frame_case(torch, rng, npics, mb_w, mb_h, filter_type, keyframe, stream=None):
+    pics, hosts, wants, sy, suv, keep = _frame_upload(torch, rng, npics, mb_w, mb_h, filter_type, keyframe)
+    vp8.loopfilter_frames(pics, filter_type, keyframe, mb_w, mb_h, sy, suv, stream=stream)
+    assert _lib.lib().ffhip_stream_synchronize(stream) == 0
+    _frame_compare(hosts, wants)
 
 
 @pytest.mark.parametrize("mb_w,mb_h", [(1, 1), (1, 23), (37, 1), (17, 9)])

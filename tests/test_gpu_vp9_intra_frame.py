@@ -186,49 +186,72 @@ def test_malformed_records_write_nothing():
     run([fr], recs=[recs])
 
 
-def test_chained_with_inter_and_the_loop_filter_on_one_stream():
+class Chain:
     """inter face -> intra face -> ffhip_vp9_loopfilter_frames_dev on the same planes and stream: equal to the loop filter run on the
-    model chain's planes"""
-    import vp9_inter_frame_gen as IG
-    import vp9_lf_gen as LG
+    model chain's planes.  upload / call(stream) / compare, inputs() / outputs() as tests/picture_faces.py has them."""
+    name = "vp9_inter+intra+loopfilter"
+
+    def upload(self, torch):
+        import vp9_inter_frame_gen as IG
+        import vp9_lf_gen as LG
+        import test_gpu_vp9_inter_frame as TI
+        rng = np.random.default_rng(7900)
+        lim, mblim = LG.filter_lut(2)
+        self.fr = fr = G.IntraFrame(rng, 200, 136, 8, 1, 1, inter=True, p_intra=0.3)
+        ifr = fr.inter
+        self.cols, self.rows, sbc, sbr = fr.cols, fr.rows, fr.sb_w, fr.sb_h
+        big = [np.zeros(((sbr * 64) >> fr.vs[p], (sbc * 64) >> fr.hs[p]), np.int64) for p in range(3)]
+        for p in range(3):
+            big[p][:fr.dh[p], :fr.dw[p]] = ifr.planes[p]               # what the inter stage starts from
+        # the device chain: inter face, intra face, loop filter
+        self.a_inter, dst, self.keep = TI.upload(torch, ifr, planes=big)
+        self.planes = [dst[p][1] for p in range(3)]
+        self.strides = [self.a_inter[0][p][1] for p in range(3)]
+        self.intra_pl = []
+        for p in range(3):
+            arr, starts = fr.pack(p)
+            d_recs = torch.from_numpy(arr.view(np.uint8).copy()).cuda()
+            d_st = torch.from_numpy(starts).cuda()
+            d_co = torch.from_numpy(fr.coeff_array(p)).cuda()
+            self.intra_pl.append((self.planes[p], self.strides[p], d_recs, d_st, d_co))
+        filt = np.zeros(sbr * sbc, LG.FILTER_DT)
+        for r in range(sbr):
+            for c in range(sbc):
+                filt[r * sbc + c] = LG.structured(rng, r, c, self.cols, self.rows)
+        self.tabs = torch.from_numpy(vp9.lf_sb_tables(filt.view(np.uint8).reshape(sbr * sbc, 192), sbc, sbr, lim, mblim).view(np.int32)).cuda()
+        # the model chain's planes, filtered by a launch of their own
+        m = G.model(fr, planes=IG.model(ifr, planes=big))
+        self.other = [torch.from_numpy(TI._plane_bytes(m[p], fr.bd, self.strides[p])).cuda() for p in range(3)]
+
+    def call(self, stream):
+        fr, planes, other, strides = self.fr, self.planes, self.other, self.strides
+        vp9.inter_frames([self.a_inter], fr.W, fr.H, ss=(1, 1), bit_depth=8, stream=stream)
+        vp9.intra_frames([(self.intra_pl, 0)], fr.W, fr.H, ss=(1, 1), bit_depth=8, stream=stream)
+        vp9.loopfilter_frames([(planes[0], planes[1], planes[2], self.tabs)], strides[0], strides[1], self.cols, self.rows, bit_depth=8, stream=stream)
+        vp9.loopfilter_frames([(other[0], other[1], other[2], self.tabs)], strides[0], strides[1], self.cols, self.rows, bit_depth=8, stream=stream)
+
+    def inputs(self):
+        pl, preds, pst, refs = self.a_inter
+        return [t for q in pl for t in q[2:]] + [preds, pst] + [t for ref in refs for t, _ in ref] + [t for q in self.intra_pl for t in q[2:]] + [self.tabs]
+
+    def outputs(self):
+        return self.planes + self.other
+
+    def compare(self, view=lambda t: t):
+        import torch
+        for p in range(3):
+            assert torch.equal(view(self.planes[p]), view(self.other[p])), p
+
+
+def test_chained_with_inter_and_the_loop_filter_on_one_stream():
+    """Chain on the NULL stream (tests/test_gpu_picture_streams.py runs it on a created one)"""
     torch = _torch()
-    rng = np.random.default_rng(7900)
-    lim, mblim = LG.filter_lut(2)
-    fr = G.IntraFrame(rng, 200, 136, 8, 1, 1, inter=True, p_intra=0.3)
-    ifr = fr.inter
-    cols, rows, sbc, sbr = fr.cols, fr.rows, fr.sb_w, fr.sb_h
-    big = [np.zeros(((sbr * 64) >> fr.vs[p], (sbc * 64) >> fr.hs[p]), np.int64) for p in range(3)]
-    for p in range(3):
-        big[p][:fr.dh[p], :fr.dw[p]] = ifr.planes[p]               # what the inter stage starts from
-    # the device chain: inter face, intra face, loop filter
-    import test_gpu_vp9_inter_frame as TI
-    a_inter, dst, keep = TI.upload(torch, ifr, planes=big)
-    planes = [dst[p][1] for p in range(3)]
-    strides = [a_inter[0][p][1] for p in range(3)]
-    intra_pl, keep2 = [], []
-    for p in range(3):
-        arr, starts = fr.pack(p)
-        d_recs = torch.from_numpy(arr.view(np.uint8).copy()).cuda()
-        d_st = torch.from_numpy(starts).cuda()
-        d_co = torch.from_numpy(fr.coeff_array(p)).cuda()
-        keep2 += [d_recs, d_st, d_co]
-        intra_pl.append((planes[p], strides[p], d_recs, d_st, d_co))
-    filt = np.zeros(sbr * sbc, LG.FILTER_DT)
-    for r in range(sbr):
-        for c in range(sbc):
-            filt[r * sbc + c] = LG.structured(rng, r, c, cols, rows)
-    tabs = torch.from_numpy(vp9.lf_sb_tables(filt.view(np.uint8).reshape(sbr * sbc, 192), sbc, sbr, lim, mblim).view(np.int32)).cuda()
-    # the model chain's planes, filtered by a launch of their own
-    m = G.model(fr, planes=IG.model(ifr, planes=big))
-    other = [torch.from_numpy(TI._plane_bytes(m[p], fr.bd, strides[p])).cuda() for p in range(3)]
-    vp9.inter_frames([a_inter], fr.W, fr.H, ss=(1, 1), bit_depth=8)
-    vp9.intra_frames([(intra_pl, 0)], fr.W, fr.H, ss=(1, 1), bit_depth=8)
-    vp9.loopfilter_frames([(planes[0], planes[1], planes[2], tabs)], strides[0], strides[1], cols, rows, bit_depth=8)
-    vp9.loopfilter_frames([(other[0], other[1], other[2], tabs)], strides[0], strides[1], cols, rows, bit_depth=8)
+    chain = Chain()
+    chain.upload(torch)
+    chain.call(None)
     sync()
     torch.cuda.synchronize()
-    for p in range(3):
-        assert torch.equal(planes[p], other[p]), p
+    chain.compare()
 
 
 @pytest.mark.parametrize("bd,ss", [(8, (1, 1)), (10, (0, 0)), (12, (1, 0))])

@@ -20,6 +20,34 @@ def _plane(rng, h, w, pad, bd):
     return np.clip(base, 0, (1 << bd) - 1).astype(np.uint8 if bd == 8 else np.uint16)
 
 
+def oracle_frame(planes, filt, sbc, sbr, bd, ss, lim, mblim):
+    """ffo_vp9_loopfilter_sb superblock by superblock in raster order, in place: what the frame kernels are pinned to"""
+    O = ffi.oracle()
+    ss_h, ss_v = ss
+    cw, ch = 64 >> ss_h, 64 >> ss_v
+    for r in range(sbr):
+        for c in range(sbc):
+            f = filt[r * sbc + c]
+            level, mask = np.ascontiguousarray(f["level"]), np.ascontiguousarray(f["mask"])
+            at = [planes[0].ctypes.data + r * 64 * planes[0].strides[0] + c * 64 * planes[0].itemsize] + \
+                 [p.ctypes.data + r * ch * p.strides[0] + c * cw * p.itemsize for p in planes[1:]]
+            O.ffo_vp9_loopfilter_sb(bd, ss_h, ss_v, ptr(level, u8p), ptr(mask, u8p), 8 * r, 8 * c, *(C.cast(a, u8p) for a in at),
+                                    planes[0].strides[0], planes[1].strides[0], ptr(lim, u8p), ptr(mblim, u8p))
+
+
+def compare(dev, wants, before, cols, rows, ss):
+    """the picture proper (cols x rows 8x8 blocks) equals the oracle's; beyond it nothing is written (a decoder's frame buffer ends
+    there, give or take its alignment)"""
+    for k, (d, want, b) in enumerate(zip(dev, wants, before)):
+        got = d.cpu().numpy().view(want.dtype).reshape(want.shape)
+        h, w = (8 * rows, 8 * cols) if k == 0 else ((8 >> ss[1]) * rows, (8 >> ss[0]) * cols)
+        bad = np.argwhere(got[:h, :w] != want[:h, :w])
+        assert bad.size == 0, (k, bad[:5], len(bad))
+        outside = got != b
+        outside[:h, :w] = False
+        assert not outside.any(), "plane %d: written beyond the picture" % k
+
+
 @pytest.mark.parametrize("bd", [8, 10, 12])
 @pytest.mark.parametrize("sbc,sbr,kind", [(9, 5, "structured"), (9, 5, "bits0"), (7, 6, "bits1"), (1, 1, "structured"), (1, 7, "bits1"), (12, 1, "structured"),
                                           (2, 40, "bits2"), (30, 17, "structured")])
@@ -35,15 +63,10 @@ def test_vp9_loopfilter_frame(sbc, sbr, kind, bd):
     planes = [_plane(rng, 64 * sbr, 64 * sbc, 12, bd), _plane(rng, 32 * sbr, 32 * sbc, 4, bd), _plane(rng, 32 * sbr, 32 * sbc, 4, bd)]
     before = [p.copy() for p in planes]
     filt = np.zeros(sbr * sbc, G.FILTER_DT)
-    O = ffi.oracle()
     for r in range(sbr):
         for c in range(sbc):
-            f = G.structured(rng, r, c, cols, rows) if kind == "structured" else G.random_bits(rng, int(kind[-1]))
-            filt[r * sbc + c] = f
-            level, mask = np.ascontiguousarray(f["level"]), np.ascontiguousarray(f["mask"])
-            at = [p.ctypes.data + r * (64 >> (k > 0)) * p.strides[0] + c * (64 >> (k > 0)) * p.itemsize for k, p in enumerate(planes)]
-            O.ffo_vp9_loopfilter_sb(bd, 1, 1, ptr(level, u8p), ptr(mask, u8p), 8 * r, 8 * c, *(C.cast(a, u8p) for a in at),
-                                    planes[0].strides[0], planes[1].strides[0], ptr(lim, u8p), ptr(mblim, u8p))
+            filt[r * sbc + c] = G.structured(rng, r, c, cols, rows) if kind == "structured" else G.random_bits(rng, int(kind[-1]))
+    oracle_frame(planes, filt, sbc, sbr, bd, (1, 1), lim, mblim)
     tabs = vp9.lf_sb_tables(filt.view(np.uint8).reshape(sbr * sbc, 192), sbc, sbr, lim, mblim)
     dev = [torch.from_numpy(b.view(np.uint8).reshape(-1).copy()).cuda() for b in before]
     d_tabs = torch.from_numpy(tabs.view(np.int32)).cuda()
@@ -51,16 +74,8 @@ def test_vp9_loopfilter_frame(sbc, sbr, kind, bd):
     torch.cuda.synchronize()
     from ffmpeg_amd import _lib
     assert _lib.lib().ffhip_stream_synchronize(None) == 0
-    changed = 0
-    for k, (d, want, b) in enumerate(zip(dev, planes, before)):
-        got = d.cpu().numpy().view(want.dtype).reshape(want.shape)
-        h, w = (8 * rows, 8 * cols) if k == 0 else (4 * rows, 4 * cols)       # the picture proper: cols x rows 8x8 blocks
-        bad = np.argwhere(got[:h, :w] != want[:h, :w])
-        assert bad.size == 0, (k, bad[:5], len(bad))
-        outside = got != b                                                      # beyond it nothing is written (a decoder's frame
-        outside[:h, :w] = False                                                 # buffer ends there, give or take its alignment)
-        assert not outside.any()
-        changed += int((want != b).sum())
+    compare(dev, planes, before, cols, rows, (1, 1))
+    changed = sum(int((want != b).sum()) for want, b in zip(planes, before))
     assert changed > (20 * sbc * sbr if sbc * sbr > 8 else -1)
 
 
@@ -121,31 +136,18 @@ def test_vp9_loopfilter_frame_444(sbc, sbr, kind, bd):
     planes = [_plane(rng, 64 * sbr, 64 * sbc, 12 if k == 0 else 4, bd) for k in range(3)]
     before = [p.copy() for p in planes]
     filt = np.zeros(sbr * sbc, G.FILTER_DT)
-    O = ffi.oracle()
     for r in range(sbr):
         for c in range(sbc):
-            f = G.structured(rng, r, c, cols, rows) if kind == "structured" else G.random_bits(rng, int(kind[-1]))
-            filt[r * sbc + c] = f
-            level, mask = np.ascontiguousarray(f["level"]), np.ascontiguousarray(f["mask"])
-            at = [p.ctypes.data + r * 64 * p.strides[0] + c * 64 * p.itemsize for p in planes]
-            O.ffo_vp9_loopfilter_sb(bd, 0, 0, ptr(level, u8p), ptr(mask, u8p), 8 * r, 8 * c, *(C.cast(a, u8p) for a in at),
-                                    planes[0].strides[0], planes[1].strides[0], ptr(lim, u8p), ptr(mblim, u8p))
+            filt[r * sbc + c] = G.structured(rng, r, c, cols, rows) if kind == "structured" else G.random_bits(rng, int(kind[-1]))
+    oracle_frame(planes, filt, sbc, sbr, bd, (0, 0), lim, mblim)
     tabs = vp9.lf_sb_tables(filt.view(np.uint8).reshape(sbr * sbc, 192), sbc, sbr, lim, mblim)
     dev = [torch.from_numpy(b.view(np.uint8).reshape(-1).copy()).cuda() for b in before]
     d_tabs = torch.from_numpy(tabs.view(np.int32)).cuda()
     vp9.loopfilter_frame(dev[0], dev[1], dev[2], before[0].strides[0], before[1].strides[0], cols, rows, d_tabs, bit_depth=bd, ss=(0, 0))
     torch.cuda.synchronize()
     assert _lib.lib().ffhip_stream_synchronize(None) == 0
-    changed = 0
-    for k, (d, want, b) in enumerate(zip(dev, planes, before)):
-        got = d.cpu().numpy().view(want.dtype).reshape(want.shape)
-        h, w = 8 * rows, 8 * cols
-        bad = np.argwhere(got[:h, :w] != want[:h, :w])
-        assert bad.size == 0, (k, bad[:5], len(bad))
-        outside = got != b
-        outside[:h, :w] = False
-        assert not outside.any()
-        changed += int((want != b).sum())
+    compare(dev, planes, before, cols, rows, (0, 0))
+    changed = sum(int((want != b).sum()) for want, b in zip(planes, before))
     assert changed > (30 * sbc * sbr if sbc * sbr > 8 else -1)
     with pytest.raises(Exception):
         vp9.loopfilter_frame(dev[0], dev[1], dev[2], before[0].strides[0], before[1].strides[0], cols, rows, d_tabs, bit_depth=bd, ss=(1, 0))
@@ -212,7 +214,6 @@ def test_vp9_loopfilter_frame_422_440(sbc, sbr, kind, ss, bd):
     planes = [_plane(rng, 64 * sbr, 64 * sbc, 12, bd), _plane(rng, chh * sbr, cw * sbc, 4, bd), _plane(rng, chh * sbr, cw * sbc, 4, bd)]
     before = [p.copy() for p in planes]
     filt = np.zeros(sbr * sbc, G.FILTER_DT)
-    O = ffi.oracle()
     L = _lib.lib()
     for r in range(sbr):
         for c in range(sbc):
@@ -225,27 +226,15 @@ def test_vp9_loopfilter_frame_422_440(sbc, sbr, kind, ss, bd):
             else:
                 pytest.fail("no acceptable filter drawn")
             filt[r * sbc + c] = f
-            level, mask = np.ascontiguousarray(f["level"]), np.ascontiguousarray(f["mask"])
-            at = [planes[0].ctypes.data + r * 64 * planes[0].strides[0] + c * 64 * planes[0].itemsize] + \
-                 [p.ctypes.data + r * chh * p.strides[0] + c * cw * p.itemsize for p in planes[1:]]
-            O.ffo_vp9_loopfilter_sb(bd, ss_h, ss_v, ptr(level, u8p), ptr(mask, u8p), 8 * r, 8 * c, *(C.cast(a, u8p) for a in at),
-                                    planes[0].strides[0], planes[1].strides[0], ptr(lim, u8p), ptr(mblim, u8p))
+    oracle_frame(planes, filt, sbc, sbr, bd, ss, lim, mblim)
     tabs, ctabs = vp9.lf_sb_tables_ss(filt.view(np.uint8).reshape(sbr * sbc, 192), sbc, sbr, lim, mblim, ss)
     dev = [torch.from_numpy(b.view(np.uint8).reshape(-1).copy()).cuda() for b in before]
     d_tabs, d_ctabs = torch.from_numpy(tabs.view(np.int32)).cuda(), torch.from_numpy(ctabs.view(np.int32)).cuda()
     vp9.loopfilter_frame_ssc(dev[0], dev[1], dev[2], before[0].strides[0], before[1].strides[0], cols, rows, d_tabs, d_ctabs, ss, bit_depth=bd)
     torch.cuda.synchronize()
     assert L.ffhip_stream_synchronize(None) == 0
-    changed = 0
-    for k, (d, want, b) in enumerate(zip(dev, planes, before)):
-        got = d.cpu().numpy().view(want.dtype).reshape(want.shape)
-        h, w = (8 * rows, 8 * cols) if k == 0 else ((8 >> ss_v) * rows, (8 >> ss_h) * cols)
-        bad = np.argwhere(got[:h, :w] != want[:h, :w])
-        assert bad.size == 0, (k, bad[:5], len(bad))
-        outside = got != b
-        outside[:h, :w] = False
-        assert not outside.any()
-        changed += int((want[1:] != b[1:]).sum()) if k else 0
+    compare(dev, planes, before, cols, rows, ss)
+    changed = sum(int((want[1:] != b[1:]).sum()) for want, b in zip(planes[1:], before[1:]))
     assert changed > (20 * sbc * sbr if sbc * sbr > 8 else -1)
     with pytest.raises(Exception):               # the 4:2:0 / 4:4:4 entry points refuse these formats by name
         vp9.loopfilter_frame(dev[0], dev[1], dev[2], before[0].strides[0], before[1].strides[0], cols, rows, d_tabs, bit_depth=bd, ss=ss)
