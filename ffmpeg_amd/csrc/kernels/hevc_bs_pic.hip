@@ -121,14 +121,9 @@ int ffhip_launch_hevc_boundary_strengths_pictures(int width, int height, int log
     const int w4 = width >> 2, h4 = height >> 2, tiles_x = (w4 + T - 1) / T, tiles_y = (h4 + T - 1) / T;
     for (int p0 = 0; p0 < npics; p0 += HBP_PICS) {
         const int n = npics - p0 < HBP_PICS ? npics - p0 : HBP_PICS;
-        /* the pictures go to the device in stream order through a progress-pool slot, as the in-loop filter face stages them */
-        const int r = ffhip_progress_launch(0, stream, "ffhip_hevc_boundary_strengths_pictures_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
-            FFHipHevcBsPic *dpics = reinterpret_cast<FFHipHevcBsPic *>(ps.prog);
-            const hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipHevcBsPic), hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess)
-                return e;
+        const int r = ffhip_progress_launch_table(stream, "ffhip_hevc_boundary_strengths_pictures_dev: copy or launch", pics + p0, n,
+                                                  [&](FFHipHevcBsPic *dpics) {
             hipLaunchKernelGGL(k_hevc_bs_pic, dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, dpics, w4, h4, log2_ctb, ctb_w, ctb_h, tiles_x);
-            return hipGetLastError();
         });
         if (r < 0)
             return r;

@@ -284,21 +284,15 @@ int ffhip_launch_hevc_inter_pictures(int bd, int cfi, int width, int height, int
     const int C = 1 << log2_ctb, ctb_w = (width + C - 1) / C, ctb_h = (height + C - 1) / C;
     for (int p0 = 0; p0 < npics; p0 += HIP_PICS) {
         const int n = npics - p0 < HIP_PICS ? npics - p0 : HIP_PICS;
-        /* the pictures (their DPB tables included) go to the device in stream order: a progress-pool slot is device memory that is
-         * not handed out again before the launch behind it has finished, and the copy from pageable memory is staged by the time
-         * hipMemcpyAsync returns */
-        const int r = ffhip_progress_launch(0, stream, "ffhip_hevc_inter_pictures_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
-            FFHipHevcInterPic *dpics = reinterpret_cast<FFHipHevcInterPic *>(ps.prog);
-            const hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipHevcInterPic), hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess)
-                return e;
+        /* the pictures travel with their DPB tables */
+        const int r = ffhip_progress_launch_table(stream, "ffhip_hevc_inter_pictures_dev: copy or launch", pics + p0, n,
+                                                  [&](FFHipHevcInterPic *dpics) {
             if (bd > 8)
                 hipLaunchKernelGGL(k_hevc_inter_pic<uint16_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    ctb_w, bd);
             else
                 hipLaunchKernelGGL(k_hevc_inter_pic<uint8_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    ctb_w, 8);
-            return hipGetLastError();
         });
         if (r < 0)
             return r;

@@ -259,19 +259,14 @@ int ffhip_launch_hevc_loop_filter_pictures(int bd, int cfi, int width, int heigh
     const int C = 1 << log2_ctb, ctb_w = (width + C - 1) / C, ctb_h = (height + C - 1) / C;
     for (int p0 = 0; p0 < npics; p0 += HLP_PICS) {
         const int n = npics - p0 < HLP_PICS ? npics - p0 : HLP_PICS;
-        /* the pictures go to the device in stream order through a progress-pool slot, as the inter picture face stages them */
-        const int r = ffhip_progress_launch(0, stream, "ffhip_hevc_loop_filter_pictures_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
-            FFHipHevcLfPic *dpics = reinterpret_cast<FFHipHevcLfPic *>(ps.prog);
-            const hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipHevcLfPic), hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess)
-                return e;
+        const int r = ffhip_progress_launch_table(stream, "ffhip_hevc_loop_filter_pictures_dev: copy or launch", pics + p0, n,
+                                                  [&](FFHipHevcLfPic *dpics) {
             if (bd > 8)
                 hipLaunchKernelGGL(k_hevc_lf_pic<uint16_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    log2_min_cb, ctb_w, ctb_h, bd);
             else
                 hipLaunchKernelGGL(k_hevc_lf_pic<uint8_t>, dim3(ctb_w * ctb_h, n), dim3(256), 0, stream, dpics, cfi, width, height, log2_ctb,
                                    log2_min_cb, ctb_w, ctb_h, 8);
-            return hipGetLastError();
         });
         if (r < 0)
             return r;

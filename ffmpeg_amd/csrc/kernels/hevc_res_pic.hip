@@ -278,15 +278,8 @@ int ffhip_launch_hevc_residual_pictures(int bd, int cfi, int npics, const FFHipH
             ffhip_set_error("ffhip_hevc_residual_pictures_dev: %lld workgroups in one launch", blocks);
             return FFHIP_EINVAL;
         }
-        /* the segment table goes to the device in stream order: a progress-pool slot is device memory that is not handed out again
-         * before the launch behind it has finished, and the copy from pageable memory is staged by the time hipMemcpyAsync returns */
-        const int r = ffhip_progress_launch(0, stream, "ffhip_hevc_residual_pictures_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
-            HrpSeg *dsegs = reinterpret_cast<HrpSeg *>(ps.prog);
-            const hipError_t e = hipMemcpyAsync(dsegs, segs, (size_t)nsegs * sizeof(HrpSeg), hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess)
-                return e;
+        const int r = ffhip_progress_launch_table(stream, "ffhip_hevc_residual_pictures_dev: copy or launch", segs, nsegs, [&](HrpSeg *dsegs) {
             hipLaunchKernelGGL(k_hevc_res_pic, dim3((unsigned)blocks), dim3(256), 0, stream, dsegs, nsegs, bd, tab);
-            return hipGetLastError();
         });
         if (r < 0)
             return r;

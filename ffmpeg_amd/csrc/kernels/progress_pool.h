@@ -1,5 +1,6 @@
 /* progress_pool.h — the progress counters of the row-ordered ("wavefront") launches in flight (the kernels of row_handoff.h) and the
- * one way a launcher takes a slot, ffhip_progress_launch().  Internal to libffhip (progress_pool.hip). */
+ * ways a launcher takes a slot: ffhip_progress_launch() and, with a table staged in it, ffhip_progress_launch_table().  Internal to
+ * libffhip (progress_pool.hip). */
 #ifndef FFHIP_PROGRESS_POOL_H
 #define FFHIP_PROGRESS_POOL_H
 
@@ -29,10 +30,8 @@ int ffhip_progress_check(hipStream_t stream);
 void ffhip_progress_report_to(hipStream_t stream, bool on);
 
 /* One launch on a slot of `nints` zeroed counters.  launch(slot) queues the work on `stream` and returns its hipError_t: the kernel
- * launch followed by hipGetLastError(), behind a hipMemcpyAsync into slot.prog where the launcher stages a table in the slot (nints 0:
- * the slot is device memory that is not handed out again before the launch behind it has finished).  A failed launch frees the slot
- * at once, sets "<what> failed: <HIP's text> (<the caller's file:line>)" and wins over a failed release: FFHIP_EIO.  Otherwise the
- * acquire's or the release's error, or 0. */
+ * launch followed by hipGetLastError().  A failed launch frees the slot at once, sets "<what> failed: <HIP's text> (<the caller's
+ * file:line>)" and wins over a failed release: FFHIP_EIO.  Otherwise the acquire's or the release's error, or 0. */
 template <class Launch>
 static inline int ffhip_progress_launch(int nints, hipStream_t stream, const char *what, Launch &&launch, const char *file = __builtin_FILE(),
                                         int line = __builtin_LINE())
@@ -48,6 +47,30 @@ static inline int ffhip_progress_launch(int nints, hipStream_t stream, const cha
         return FFHIP_EIO;
     }
     return r2 < 0 ? r2 : 0;
+}
+
+/* One launch behind a table: `count` T of `host` go to the device in stream order and launch(dev) queues the kernel(s) that read
+ * them.  The table travels in a slot without counters (nints 0): a slot is device memory that is not handed out again before the
+ * launch behind it has finished, and a copy from pageable memory is staged by the time hipMemcpyAsync returns, so `host` may be the
+ * caller's array or a local.  FFHIP_EINVAL for a table larger than a slot (the launchers' static_asserts keep theirs below it);
+ * otherwise as ffhip_progress_launch(), a failed copy included. */
+template <class T, class Launch>
+static inline int ffhip_progress_launch_table(hipStream_t stream, const char *what, const T *host, size_t count, Launch &&launch,
+                                              const char *file = __builtin_FILE(), int line = __builtin_LINE())
+{
+    const size_t bytes = count * sizeof(T);
+    if (bytes > FFHIP_PROGRESS_SLOT_INTS * sizeof(int)) {
+        ffhip_set_error("%s: a table of %zu bytes exceeds a progress-pool slot", what, bytes);
+        return FFHIP_EINVAL;
+    }
+    return ffhip_progress_launch(0, stream, what, [&](const FFHipProgressSlot &ps) {
+        T *dev = reinterpret_cast<T *>(ps.prog);
+        const hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess)
+            return e;
+        launch(dev);
+        return hipGetLastError();
+    }, file, line);
 }
 
 #endif

@@ -334,21 +334,14 @@ int ffhip_launch_vp9_inter_frames(int bd, int ss_h, int ss_v, int width, int hei
     const int cols = (width + 7) >> 3, rows = (height + 7) >> 3, sb_w = (cols + 7) >> 3, sb_h = (rows + 7) >> 3;
     for (int p0 = 0; p0 < npics; p0 += VIF_PICS) {
         const int n = npics - p0 < VIF_PICS ? npics - p0 : VIF_PICS;
-        /* the frames (their reference tables included) go to the device in stream order: a progress-pool slot is device memory that
-         * is not handed out again before the launch behind it has finished, and the copy from pageable memory is staged by the time
-         * hipMemcpyAsync returns */
-        const int r = ffhip_progress_launch(0, stream, "ffhip_vp9_inter_frames_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
-            FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
-            const hipError_t e = hipMemcpyAsync(dpics, pics + p0, (size_t)n * sizeof(FFHipVp9InterPic), hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess)
-                return e;
+        /* the frames travel with their reference tables */
+        const int r = ffhip_progress_launch_table(stream, "ffhip_vp9_inter_frames_dev: copy or launch", pics + p0, n, [&](FFHipVp9InterPic *dpics) {
             if (bd > 8)
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint16_t, false>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
                                    sb_w, bd);
             else
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint8_t, false>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width, height,
                                    sb_w, 8);
-            return hipGetLastError();
         });
         if (r < 0)
             return r;
@@ -392,20 +385,14 @@ int ffhip_launch_vp9_inter_frames_scaled(int bd, int ss_h, int ss_v, int width, 
                 return r;
             continue;
         }
-        /* as ffhip_launch_vp9_inter_frames: the slot is not handed out again before the launch behind it has finished, and the copy
-         * from pageable memory is staged by the time hipMemcpyAsync returns */
-        const int r = ffhip_progress_launch(0, stream, "ffhip_vp9_inter_frames_scaled_dev: copy or launch", [&](const FFHipProgressSlot &ps) {
-            FFHipVp9InterPic *dpics = reinterpret_cast<FFHipVp9InterPic *>(ps.prog);
-            const hipError_t e = hipMemcpyAsync(dpics, &st, sizeof(st), hipMemcpyHostToDevice, stream);
-            if (e != hipSuccess)
-                return e;
+        const int r = ffhip_progress_launch_table(stream, "ffhip_vp9_inter_frames_scaled_dev: copy or launch", &st, 1, [&](Staged *dst) {
+            FFHipVp9InterPic *dpics = dst->pic;
             if (bd > 8)
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint16_t, true>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width,
                                    height, sb_w, bd);
             else
                 hipLaunchKernelGGL((k_vp9_inter_frame<uint8_t, true>), dim3(sb_w * sb_h, n), dim3(256), 0, stream, dpics, ss_h, ss_v, width,
                                    height, sb_w, 8);
-            return hipGetLastError();
         });
         if (r < 0)
             return r;

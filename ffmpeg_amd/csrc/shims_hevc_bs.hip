@@ -1,17 +1,15 @@
 /*
- * shims_hevc_bs.hip — ffhip_hevc_boundary_strengths_pictures_dev(): validates what the host can see of a picture set (geometry, map
- * pointers and strides, output / input overlap) and launches kernels/hevc_bs_pic.hip on the caller's stream; and the device-free
- * faces: ffhip_hevc_boundary_strengths_pictures_host(), the same checks and the same rules (kernels/hevc_bs_rules.h) on host
- * arrays, ffhip_hevc_bs_mark_tu() and the record sizes.
+ * shims_hevc_bs.hip — ffhip_hevc_boundary_strengths_pictures_dev(): the host checks (kernels/picture_check.h, map pointers and
+ * strides, output / input overlap) and the launch of kernels/hevc_bs_pic.hip on the caller's stream; and the device-free faces:
+ * ffhip_hevc_boundary_strengths_pictures_host(), the same checks and the same rules (kernels/hevc_bs_rules.h) on host arrays,
+ * ffhip_hevc_bs_mark_tu() and the record sizes.
  */
-#include <algorithm>
-#include <stdint.h>
 #include <string.h>
-#include <vector>
 
 #include "kernels/common.h"
 #include "kernels/h264_kernels.h"
 #include "kernels/hevc_bs_rules.h"
+#include "kernels/picture_check.h"
 
 extern "C" int ffhip_hevc_bs_mvf_record_size(void) { return (int)sizeof(FFHipHevcMvField); }
 extern "C" int ffhip_hevc_bs_slice_record_size(void) { return (int)sizeof(FFHipHevcBsSlice); }
@@ -28,30 +26,11 @@ extern "C" void ffhip_hevc_bs_mark_tu(uint8_t *tu, int tu_stride, int x0, int y0
 }
 
 namespace {
-struct Span { /* the bytes a map occupies from its first to its last entry: [lo, hi) */
-    uintptr_t lo, hi;
-};
-Span map_span(const void *base, int stride, int w, int rows, size_t entry)
-{
-    const uintptr_t b = (uintptr_t)base;
-    return { b, b + ((size_t)(rows - 1) * (size_t)stride + (size_t)w) * entry };
-}
-
 /* the argument checks of both faces */
 int check(const char *who, int width, int height, int log2_ctb_size, int npics, const FFHipHevcBsPic *pics)
 {
-    if (log2_ctb_size < 4 || log2_ctb_size > 6) {
-        ffhip_set_error("%s: log2 CTB size %d (4..6)", who, log2_ctb_size);
-        return FFHIP_EINVAL;
-    }
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || (width | height) & 7) {
-        ffhip_set_error("%s: picture size %d x %d (multiples of 8, at most 65535)", who, width, height);
-        return FFHIP_EINVAL;
-    }
-    if (npics <= 0 || !pics) {
-        ffhip_set_error("%s: npics = %d, or a NULL picture array", who, npics);
-        return FFHIP_EINVAL;
-    }
+    if (const int r = ffhip_check_hevc_geometry(who, log2_ctb_size, width, height, npics, pics))
+        return r;
     const int w4 = width >> 2, h4 = height >> 2, C = 1 << log2_ctb_size, nctb = ((width + C - 1) / C) * ((height + C - 1) / C);
     for (int i = 0; i < npics; i++) {
         const FFHipHevcBsPic &P = pics[i];
@@ -62,36 +41,28 @@ int check(const char *who, int width, int height, int log2_ctb_size, int npics, 
             return FFHIP_EINVAL;
         }
     }
-    /* no output map of the call may overlap another one or an input map: workgroups of every picture read while others write.
-     * The output spans are sorted by start with a running maximum of their ends, so each span is one binary search */
-    std::vector<Span> out;
+    /* no output map of the call may overlap another one or an input map: workgroups of every picture read while others write */
+    FFHipSpanSet out;
     out.reserve((size_t)npics * 2);
     for (int i = 0; i < npics; i++) {
-        out.push_back(map_span(pics[i].bs_ver, pics[i].bs_stride, w4, h4, 1));
-        out.push_back(map_span(pics[i].bs_hor, pics[i].bs_stride, w4, h4, 1));
+        out.add(ffhip_map_span(pics[i].bs_ver, pics[i].bs_stride, w4, h4, 1));
+        out.add(ffhip_map_span(pics[i].bs_hor, pics[i].bs_stride, w4, h4, 1));
     }
-    std::sort(out.begin(), out.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
-    std::vector<uintptr_t> hi_max(out.size());
-    for (size_t k = 0; k < out.size(); k++) {
-        if (k && hi_max[k - 1] > out[k].lo) {
-            ffhip_set_error("%s: an output map overlaps another output map of the call", who);
-            return FFHIP_EINVAL;
-        }
-        hi_max[k] = k ? std::max(hi_max[k - 1], out[k].hi) : out[k].hi;
+    if (out.seal()) {
+        ffhip_set_error("%s: an output map overlaps another output map of the call", who);
+        return FFHIP_EINVAL;
     }
     for (int i = 0; i < npics; i++) {
         const FFHipHevcBsPic &P = pics[i];
-        const Span in[5] = { map_span(P.mvf, P.mvf_stride, w4, h4, sizeof(FFHipHevcMvField)), map_span(P.tu, P.tu_stride, w4, h4, 1),
-                             map_span(P.ctb_slice, nctb, nctb, 1, 2), map_span(P.slices, P.nslices, P.nslices, 1, sizeof(FFHipHevcBsSlice)),
-                             map_span(P.ctb_tile, nctb, nctb, 1, 2) };
-        for (int k = 0; k < (P.ctb_tile ? 5 : 4); k++) {
-            const size_t n = (size_t)(std::lower_bound(out.begin(), out.end(), in[k].hi, [](const Span &x, uintptr_t v) { return x.lo < v; }) -
-                                      out.begin());
-            if (n && hi_max[n - 1] > in[k].lo) {
+        const FFHipSpan in[5] = { ffhip_map_span(P.mvf, P.mvf_stride, w4, h4, sizeof(FFHipHevcMvField)), ffhip_map_span(P.tu, P.tu_stride, w4, h4, 1),
+                                  ffhip_map_span(P.ctb_slice, nctb, nctb, 1, 2),
+                                  ffhip_map_span(P.slices, P.nslices, P.nslices, 1, sizeof(FFHipHevcBsSlice)),
+                                  ffhip_map_span(P.ctb_tile, nctb, nctb, 1, 2) };
+        for (int k = 0; k < (P.ctb_tile ? 5 : 4); k++)
+            if (out.hits(in[k])) {
                 ffhip_set_error("%s: picture %d: an input map overlaps an output map of the call", who, i);
                 return FFHIP_EINVAL;
             }
-        }
     }
     return 0;
 }

@@ -7,8 +7,8 @@
  * into src; the kernel runs with n = 1 and a prepared line, and the block travels back.  A call that cannot run on the device is
  * answered by the C function the init displaced, as in shims.hip.
  *
- * ffhip_hevc_intra_pictures_dev() validates what the host can see of a picture set and launches the intra reconstruction wavefront
- * (kernels/hevc_intra_pic.hip) on the caller's stream.
+ * ffhip_hevc_intra_pictures_dev(): the host checks (kernels/picture_check.h; no overlap check) and the launch of the intra
+ * reconstruction wavefront (kernels/hevc_intra_pic.hip) on the caller's stream.
  */
 #include <stdint.h>
 #include <string.h>
@@ -16,6 +16,7 @@
 
 #include "kernels/common.h"
 #include "kernels/h264_kernels.h"
+#include "kernels/picture_check.h"
 #include "kernels/shim_arena.h"
 
 static bool hpred_bd_ok(int bd) { return bd == 8 || bd == 10 || bd == 12; }
@@ -48,38 +49,27 @@ extern "C" int ffhip_hevc_intra_tu_record_size(void) { return (int)sizeof(FFHipH
 extern "C" int ffhip_hevc_intra_pictures_dev(int bit_depth, int chroma_format_idc, int width, int height, int log2_ctb_size, int npics,
                                              const FFHipHevcIntraPic *pics, void *stream)
 {
-    if (!hpred_bd_ok(bit_depth) || chroma_format_idc < 0 || chroma_format_idc > 3 || log2_ctb_size < 4 || log2_ctb_size > 6) {
-        ffhip_set_error("ffhip_hevc_intra_pictures_dev: bit depth %d (8, 10 or 12), chroma format %d (0..3), log2 CTB size %d (4..6)",
-                        bit_depth, chroma_format_idc, log2_ctb_size);
-        return FFHIP_EINVAL;
-    }
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || (width | height) & 7) {
-        ffhip_set_error("ffhip_hevc_intra_pictures_dev: picture size %d x %d (multiples of 8, at most 65535)", width, height);
-        return FFHIP_EINVAL;
-    }
-    if (npics <= 0 || !pics) {
-        ffhip_set_error("ffhip_hevc_intra_pictures_dev: npics = %d, or a NULL picture array", npics);
-        return FFHIP_EINVAL;
-    }
-    const int ps = bit_depth > 8 ? 2 : 1, nplanes = chroma_format_idc ? 3 : 1;
-    const unsigned amask = 4u * ps - 1; /* four samples per access */
+    static const char who[] = "ffhip_hevc_intra_pictures_dev";
+    if (const int r = ffhip_check_hevc_pictures(who, bit_depth, chroma_format_idc, log2_ctb_size, width, height, npics, pics))
+        return r;
+    const FFHipPlaneGeom G = FFHipPlaneGeom::hevc(bit_depth, chroma_format_idc, width, height);
+    const int nplanes = G.nplanes;
     for (int i = 0; i < npics; i++)
         for (int p = 0; p < nplanes; p++) {
             const FFHipHevcIntraPlane &P = pics[i].plane[p];
-            const int pw = p && chroma_format_idc != 3 ? width >> 1 : width;
             if (!P.base || !P.tus || !P.ctb_start || !P.res) {
-                ffhip_set_error("ffhip_hevc_intra_pictures_dev: picture %d plane %d: a NULL pointer", i, p);
+                ffhip_set_error("%s: picture %d plane %d: a NULL pointer", who, i, p);
                 return FFHIP_EINVAL;
             }
-            if ((((uintptr_t)P.base | (size_t)P.stride) & amask) || P.stride < (ptrdiff_t)pw * ps) {
-                ffhip_set_error("ffhip_hevc_intra_pictures_dev: picture %d plane %d: base and stride must be %u-byte aligned, the stride at "
-                                "least the plane's width", i, p, amask + 1);
+            if (!ffhip_plane_ok(P.base, P.stride, G.amask, G.row_bytes(p))) {
+                ffhip_set_error("%s: picture %d plane %d: base and stride must be %u-byte aligned, the stride at least the plane's width", who,
+                                i, p, G.amask + 1);
                 return FFHIP_EINVAL;
             }
         }
     const int ctb_h = (height + (1 << log2_ctb_size) - 1) >> log2_ctb_size;
     if (nplanes * ctb_h > FFHIP_PROGRESS_SLOT_INTS) {
-        ffhip_set_error("ffhip_hevc_intra_pictures_dev: %d CTB rows exceed the progress pool", nplanes * ctb_h);
+        ffhip_set_error("%s: %d CTB rows exceed the progress pool", who, nplanes * ctb_h);
         return FFHIP_EINVAL;
     }
     if (!ffhip_have_device())

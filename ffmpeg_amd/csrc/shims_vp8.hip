@@ -7,12 +7,11 @@
  * image back in one copy and committed from there; a call that cannot run on the device (or an argument outside the reference's
  * range) is answered by the C function the init displaced (SHIM_FB).  Only what the reference reads of the caller's memory is staged.
  */
-#include <algorithm>
 #include <stdint.h>
 #include <string.h>
-#include <vector>
 
 #include "kernels/common.h"
+#include "kernels/picture_check.h"
 #include "kernels/shim_arena.h"
 #include "kernels/vp8_kernels.h"
 
@@ -271,50 +270,39 @@ extern "C" int ffhip_vp8_mc_batch_dev(uint8_t *dst, ptrdiff_t dststride, const u
 extern "C" int ffhip_vp8_loopfilter_frames_dev(int filter_type, int keyframe, int mb_w, int mb_h, int npics, const FFHipVp8LfPic *pics,
                                                ptrdiff_t stride_y, ptrdiff_t stride_uv, void *stream)
 {
+    static const char who[] = "ffhip_vp8_loopfilter_frames_dev";
     if ((filter_type & ~1) || (keyframe & ~1) || mb_w < 1 || mb_w > 1024 || mb_h < 1 || mb_h > 1024) {
-        ffhip_set_error("ffhip_vp8_loopfilter_frames_dev: filter type %d, keyframe %d (0 or 1 each), %d x %d macroblocks (1..1024)", filter_type,
-                        keyframe, mb_w, mb_h);
+        ffhip_set_error("%s: filter type %d, keyframe %d (0 or 1 each), %d x %d macroblocks (1..1024)", who, filter_type, keyframe, mb_w, mb_h);
         return FFHIP_EINVAL;
     }
-    if (npics <= 0 || !pics) {
-        ffhip_set_error("ffhip_vp8_loopfilter_frames_dev: npics = %d, or a NULL frame array", npics);
-        return FFHIP_EINVAL;
-    }
+    if (const int r = ffhip_check_count(who, npics, pics, "frame"))
+        return r;
     const bool normal = filter_type == 0;
     if ((stride_y & 3) || stride_y < 16 * mb_w || (normal && ((stride_uv & 3) || stride_uv < 8 * mb_w))) {
-        ffhip_set_error("ffhip_vp8_loopfilter_frames_dev: strides %td / %td must be multiples of 4 and at least the planes' widths", stride_y,
-                        stride_uv);
+        ffhip_set_error("%s: strides %td / %td must be multiples of 4 and at least the planes' widths", who, stride_y, stride_uv);
         return FFHIP_EINVAL;
     }
-    struct Span {
-        uintptr_t lo, hi;
-    };
-    std::vector<Span> spans;
+    FFHipSpanSet planes;
     for (int i = 0; i < npics; i++) {
         const FFHipVp8LfPic &P = pics[i];
         uint8_t *const pl[3] = { P.y, P.u, P.v };
         if (!P.strength) {
-            ffhip_set_error("ffhip_vp8_loopfilter_frames_dev: frame %d: a NULL record array", i);
+            ffhip_set_error("%s: frame %d: a NULL record array", who, i);
             return FFHIP_EINVAL;
         }
         for (int p = 0; p < (normal ? 3 : 1); p++) {
             if (!pl[p] || ((uintptr_t)pl[p] & 3)) {
-                ffhip_set_error("ffhip_vp8_loopfilter_frames_dev: frame %d plane %d: NULL, or not 4-byte aligned", i, p);
+                ffhip_set_error("%s: frame %d plane %d: NULL, or not 4-byte aligned", who, i, p);
                 return FFHIP_EINVAL;
             }
-            const int bs = p ? 8 : 16;
-            const ptrdiff_t s = p ? stride_uv : stride_y;
-            const uintptr_t b = (uintptr_t)pl[p];
-            spans.push_back({ b, b + (uintptr_t)((ptrdiff_t)(bs * mb_h - 1) * s + bs * mb_w) });
+            planes.add(ffhip_plane_span(pl[p], p ? stride_uv : stride_y, (p ? 8 : 16) * mb_w, (p ? 8 : 16) * mb_h));
         }
     }
     /* the frames of a launch are filtered side by side: no two planes may share a byte */
-    std::sort(spans.begin(), spans.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
-    for (size_t k = 1; k < spans.size(); k++)
-        if (spans[k].lo < spans[k - 1].hi) {
-            ffhip_set_error("ffhip_vp8_loopfilter_frames_dev: two planes of the call overlap");
-            return FFHIP_EINVAL;
-        }
+    if (planes.seal()) {
+        ffhip_set_error("%s: two planes of the call overlap", who);
+        return FFHIP_EINVAL;
+    }
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_vp8_lf_frames(filter_type, keyframe, mb_w, mb_h, npics, pics, stride_y, stride_uv, (hipStream_t)stream);

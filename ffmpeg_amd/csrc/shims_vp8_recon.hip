@@ -1,13 +1,10 @@
 /*
- * shims_vp8_recon.hip — VP8 reconstruction of whole frames: the validation of ffhip_vp8_recon_frames_dev() (kernels in
+ * shims_vp8_recon.hip — VP8 reconstruction of whole frames: the host checks of ffhip_vp8_recon_frames_dev() (kernels/picture_check.h; kernels in
  * kernels/vp8_recon_frame.hip) and the device-free faces ffhip_vp8_mb_preds() / ffhip_vp8_intra_modes(), which run the rules the
  * kernels run (kernels/vp8_recon_rules.h) on the host.
  */
-#include <algorithm>
-#include <stdint.h>
-#include <vector>
-
 #include "kernels/common.h"
+#include "kernels/picture_check.h"
 #include "kernels/vp8_kernels.h"
 #include "kernels/vp8_recon_rules.h"
 
@@ -42,46 +39,39 @@ extern "C" int ffhip_vp8_intra_modes(const FFHipVp8Mb *mb, int mb_x, int mb_y, F
 extern "C" int ffhip_vp8_recon_frames_dev(int mb_w, int mb_h, int bilinear, int fullpel_chroma, int npics, const FFHipVp8ReconPic *pics,
                                           ptrdiff_t stride_y, ptrdiff_t stride_uv, void *stream)
 {
+    static const char who[] = "ffhip_vp8_recon_frames_dev";
     if ((bilinear & ~1) || (fullpel_chroma & ~1) || mb_w < 1 || mb_w > 1024 || mb_h < 1 || mb_h > 1024) {
-        ffhip_set_error("ffhip_vp8_recon_frames_dev: bilinear %d, fullpel_chroma %d (0 or 1 each), %d x %d macroblocks (1..1024)", bilinear,
-                        fullpel_chroma, mb_w, mb_h);
+        ffhip_set_error("%s: bilinear %d, fullpel_chroma %d (0 or 1 each), %d x %d macroblocks (1..1024)", who, bilinear, fullpel_chroma, mb_w,
+                        mb_h);
         return FFHIP_EINVAL;
     }
-    if (npics <= 0 || !pics) {
-        ffhip_set_error("ffhip_vp8_recon_frames_dev: npics = %d, or a NULL frame array", npics);
-        return FFHIP_EINVAL;
-    }
+    if (const int r = ffhip_check_count(who, npics, pics, "frame"))
+        return r;
     if ((stride_y & 3) || stride_y < 16 * mb_w || (stride_uv & 3) || stride_uv < 8 * mb_w) {
-        ffhip_set_error("ffhip_vp8_recon_frames_dev: strides %td / %td must be multiples of 4 and at least the planes' widths", stride_y, stride_uv);
+        ffhip_set_error("%s: strides %td / %td must be multiples of 4 and at least the planes' widths", who, stride_y, stride_uv);
         return FFHIP_EINVAL;
     }
-    struct Span {
-        uintptr_t lo, hi;
-    };
-    auto span = [&](const uint8_t *b, int p) {
-        const int bs = p ? 8 : 16;
-        const ptrdiff_t s = p ? stride_uv : stride_y;
-        return Span{ (uintptr_t)b, (uintptr_t)b + (uintptr_t)((ptrdiff_t)(bs * mb_h - 1) * s + bs * mb_w) };
-    };
-    std::vector<Span> dsts, refs;
+    auto span = [&](const uint8_t *b, int p) { return ffhip_plane_span(b, p ? stride_uv : stride_y, (p ? 8 : 16) * mb_w, (p ? 8 : 16) * mb_h); };
+    FFHipSpanSet dsts;
+    std::vector<FFHipSpan> refs;
     for (int i = 0; i < npics; i++) {
         const FFHipVp8ReconPic &P = pics[i];
         const uint8_t *const pl[3] = { P.y, P.u, P.v };
         if (!P.mbs || P.coeff_count < 0 || (!P.coeffs && P.coeff_count > 0)) {
-            ffhip_set_error("ffhip_vp8_recon_frames_dev: frame %d: a NULL record array, or coefficients counted but NULL", i);
+            ffhip_set_error("%s: frame %d: a NULL record array, or coefficients counted but NULL", who, i);
             return FFHIP_EINVAL;
         }
         for (int p = 0; p < 3; p++) {
             if (!pl[p] || ((uintptr_t)pl[p] & 3)) {
-                ffhip_set_error("ffhip_vp8_recon_frames_dev: frame %d plane %d: NULL, or not 4-byte aligned", i, p);
+                ffhip_set_error("%s: frame %d plane %d: NULL, or not 4-byte aligned", who, i, p);
                 return FFHIP_EINVAL;
             }
-            dsts.push_back(span(pl[p], p));
+            dsts.add(span(pl[p], p));
             for (int r = 0; r < 3; r++) {
                 if (!P.ref[r][p])
                     continue;
                 if ((uintptr_t)P.ref[r][p] & 3) {
-                    ffhip_set_error("ffhip_vp8_recon_frames_dev: frame %d reference %d plane %d: not 4-byte aligned", i, r + 1, p);
+                    ffhip_set_error("%s: frame %d reference %d plane %d: not 4-byte aligned", who, i, r + 1, p);
                     return FFHIP_EINVAL;
                 }
                 refs.push_back(span(P.ref[r][p], p));
@@ -90,20 +80,15 @@ extern "C" int ffhip_vp8_recon_frames_dev(int mb_w, int mb_h, int bilinear, int 
     }
     /* the frames of a call are reconstructed side by side: no two destination planes may share a byte, and no frame may be read
      * as a reference while the call writes it */
-    std::sort(dsts.begin(), dsts.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
-    for (size_t k = 1; k < dsts.size(); k++)
-        if (dsts[k].lo < dsts[k - 1].hi) {
-            ffhip_set_error("ffhip_vp8_recon_frames_dev: two destination planes of the call overlap");
-            return FFHIP_EINVAL;
-        }
-    for (const Span &r : refs) {
-        /* the first destination that ends behind r's start */
-        auto it = std::upper_bound(dsts.begin(), dsts.end(), r.lo, [](uintptr_t v, const Span &d) { return v < d.hi; });
-        if (it != dsts.end() && it->lo < r.hi) {
-            ffhip_set_error("ffhip_vp8_recon_frames_dev: a reference plane overlaps a destination plane of the call");
-            return FFHIP_EINVAL;
-        }
+    if (dsts.seal()) {
+        ffhip_set_error("%s: two destination planes of the call overlap", who);
+        return FFHIP_EINVAL;
     }
+    for (const FFHipSpan &r : refs)
+        if (dsts.hits(r)) {
+            ffhip_set_error("%s: a reference plane overlaps a destination plane of the call", who);
+            return FFHIP_EINVAL;
+        }
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_vp8_recon_frames(mb_w, mb_h, bilinear, fullpel_chroma, npics, pics, stride_y, stride_uv, (hipStream_t)stream);

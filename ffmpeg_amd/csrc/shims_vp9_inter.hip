@@ -1,30 +1,18 @@
 /*
- * shims_vp9_inter.hip — ffhip_vp9_inter_frames_dev(): validates what the host can see of a frame set (geometry, planes, references,
- * reference / destination overlap) and launches the inter reconstruction (kernels/vp9_inter_frame.hip) on the caller's stream.  The
- * records themselves are device data and are checked by the kernel.  Also ffhip_vp9_inter_block_preds(), the device-free expansion
+ * shims_vp9_inter.hip — ffhip_vp9_inter_frames_dev(): the host checks (kernels/picture_check.h, references, reference / destination
+ * overlap) and the launch of the inter reconstruction (kernels/vp9_inter_frame.hip) on the caller's stream.  The records themselves
+ * are device data and are checked by the kernel.  Also ffhip_vp9_inter_block_preds(), the device-free expansion
  * of one decoded block into its prediction records (libavcodec/vp9_mc_template.h).  ffhip_vp9_inter_frames_scaled_dev() and
  * ffhip_vp9_inter_block_preds_scaled(): the same for frames with references of another size (the SCALED template).
  */
-#include <algorithm>
-#include <stdint.h>
-#include <vector>
-
 #include "kernels/common.h"
 #include "kernels/h264_kernels.h"
+#include "kernels/picture_check.h"
 
 extern "C" int ffhip_vp9_inter_pred_record_size(void) { return (int)sizeof(FFHipVp9InterPred); }
 extern "C" int ffhip_vp9_inter_tu_record_size(void) { return (int)sizeof(FFHipVp9InterTU); }
 
 namespace {
-struct Span { /* the bytes a plane occupies: [lo, hi) */
-    uintptr_t lo, hi;
-};
-Span plane_span(const void *base, ptrdiff_t stride, int w_bytes, int rows)
-{
-    const uintptr_t b = (uintptr_t)base;
-    return { b, b + (uintptr_t)((ptrdiff_t)(rows - 1) * stride + w_bytes) };
-}
-
 /* ROUNDED_DIV (libavutil/common.h): half away from zero, then C division (towards zero) */
 int rounded_div(int a, int b) { return (a >= 0 ? a + (b >> 1) : a - (b >> 1)) / b; }
 struct Mv {
@@ -34,82 +22,57 @@ Mv mv_of(const int16_t mv[4][2][2], int sub, int r) { return { mv[sub][r][0], mv
 Mv div2(Mv a, Mv b) { return { rounded_div(a.x + b.x, 2), rounded_div(a.y + b.y, 2) }; }
 Mv div4(Mv a, Mv b, Mv c, Mv d) { return { rounded_div(a.x + b.x + c.x + d.x, 4), rounded_div(a.y + b.y + c.y + d.y, 4) }; }
 
-
-/* what the host can see of a frame set: `fn` names the face in the messages, pics[i] is frame i's FFHipVp9InterPic and
- * ref_size(i, r, p, &w, &h) gives the real size of plane p of frame i's reference r, samples */
-template <typename PICS, typename REFSIZE>
-int check_frames(const char *fn, int bit_depth, int ss_h, int ss_v, int width, int height, int npics, PICS pics, REFSIZE ref_size)
+/* the host checks of both faces: pic(i) is frame i's FFHipVp9InterPic and ref_size(i, r, p, &w, &h) gives the real size of plane p of
+ * frame i's reference r, samples */
+template <typename PIC, typename REFSIZE>
+int check_frames(const char *who, int bit_depth, int ss_h, int ss_v, int width, int height, int npics, const void *pics, PIC pic,
+                 REFSIZE ref_size)
 {
-    if ((bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (ss_h & ~1) || (ss_v & ~1)) {
-        ffhip_set_error("%s: bit depth %d (8, 10 or 12), subsampling %d, %d (0 or 1 each)", fn, bit_depth, ss_h, ss_v);
-        return FFHIP_EINVAL;
-    }
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) {
-        ffhip_set_error("%s: frame size %d x %d (1..65535)", fn, width, height);
-        return FFHIP_EINVAL;
-    }
-    if (npics <= 0 || !pics) {
-        ffhip_set_error("%s: npics = %d, or a NULL frame array", fn, npics);
-        return FFHIP_EINVAL;
-    }
-    const int ps = bit_depth > 8 ? 2 : 1;
-    const unsigned amask = 4u * ps - 1; /* four samples per access */
-    const int cols = (width + 7) >> 3, rows = (height + 7) >> 3;
-    int dw[3], dh[3]; /* decoded area per plane, samples */
-    for (int p = 0; p < 3; p++) {
-        dw[p] = (cols * 8) >> (p ? ss_h : 0);
-        dh[p] = (rows * 8) >> (p ? ss_v : 0);
-    }
+    if (const int r = ffhip_check_vp9_frames(who, bit_depth, ss_h, ss_v, width, height, npics, pics))
+        return r;
+    const FFHipPlaneGeom G = FFHipPlaneGeom::vp9(bit_depth, ss_h, ss_v, width, height);
     for (int i = 0; i < npics; i++) {
-        const FFHipVp9InterPic &P = pics[i];
+        const FFHipVp9InterPic &P = pic(i);
         if (!P.preds || !P.pred_sb_start || P.nrefs < 1 || P.nrefs > 3) {
-            ffhip_set_error("%s: frame %d: NULL prediction tables or nrefs = %d (1..3)", fn, i, P.nrefs);
+            ffhip_set_error("%s: frame %d: NULL prediction tables or nrefs = %d (1..3)", who, i, P.nrefs);
             return FFHIP_EINVAL;
         }
         for (int p = 0; p < 3; p++) {
             const FFHipVp9InterPlane &D = P.plane[p];
             if (!D.base || !D.tus || !D.tu_sb_start || !D.coeffs) {
-                ffhip_set_error("%s: frame %d plane %d: a NULL pointer", fn, i, p);
+                ffhip_set_error("%s: frame %d plane %d: a NULL pointer", who, i, p);
                 return FFHIP_EINVAL;
             }
-            if ((((uintptr_t)D.base | (size_t)D.stride) & amask) || D.stride < (ptrdiff_t)dw[p] * ps) {
-                ffhip_set_error("%s: frame %d plane %d: base and stride must be %u-byte aligned, the stride at least the decoded width", fn,
-                                i, p, amask + 1);
+            if (!ffhip_plane_ok(D.base, D.stride, G.amask, G.row_bytes(p))) {
+                ffhip_set_error("%s: frame %d plane %d: base and stride must be %u-byte aligned, the stride at least the decoded width", who,
+                                i, p, G.amask + 1);
                 return FFHIP_EINVAL;
             }
             for (int r = 0; r < P.nrefs; r++) {
-                const uint8_t *b = P.ref[r].base[p];
-                const ptrdiff_t s = P.ref[r].stride[p];
                 int rw, rh;
                 ref_size(i, r, p, &rw, &rh);
-                if (!b || (((uintptr_t)b | (size_t)s) & (ps - 1)) || s < (ptrdiff_t)rw * ps) {
-                    ffhip_set_error("%s: frame %d reference %d plane %d: NULL, misaligned or a stride below the width", fn, i, r, p);
+                if (!ffhip_plane_ok(P.ref[r].base[p], P.ref[r].stride[p], G.ps - 1, (ptrdiff_t)rw * G.ps)) {
+                    ffhip_set_error("%s: frame %d reference %d plane %d: NULL, misaligned or a stride below the width", who, i, r, p);
                     return FFHIP_EINVAL;
                 }
             }
         }
     }
-    /* no reference plane of the call may be a destination plane of the call: a launch's frames are predicted side by side.  The
-     * destination spans are sorted by start with a running maximum of their ends, so each reference span is one binary search */
-    std::vector<Span> dst;
+    /* no reference plane of the call may be a destination plane of the call: a launch's frames are predicted side by side
+     * (destination planes that coincide are not refused) */
+    FFHipSpanSet dst;
     dst.reserve((size_t)npics * 3);
     for (int i = 0; i < npics; i++)
         for (int p = 0; p < 3; p++)
-            dst.push_back(plane_span(pics[i].plane[p].base, pics[i].plane[p].stride, dw[p] * ps, dh[p]));
-    std::sort(dst.begin(), dst.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
-    std::vector<uintptr_t> hi_max(dst.size());
-    for (size_t k = 0; k < dst.size(); k++)
-        hi_max[k] = k ? std::max(hi_max[k - 1], dst[k].hi) : dst[k].hi;
+            dst.add(G.span(pic(i).plane[p].base, pic(i).plane[p].stride, p));
+    dst.seal();
     for (int j = 0; j < npics; j++)
-        for (int r = 0; r < pics[j].nrefs; r++)
+        for (int r = 0; r < pic(j).nrefs; r++)
             for (int q = 0; q < 3; q++) {
                 int rw, rh;
                 ref_size(j, r, q, &rw, &rh);
-                const Span s = plane_span(pics[j].ref[r].base[q], pics[j].ref[r].stride[q], rw * ps, rh);
-                const size_t n = (size_t)(std::lower_bound(dst.begin(), dst.end(), s.hi, [](const Span &x, uintptr_t v) { return x.lo < v; }) -
-                                          dst.begin());
-                if (n && hi_max[n - 1] > s.lo) {
-                    ffhip_set_error("%s: frame %d reference %d plane %d overlaps a plane the call writes", fn, j, r, q);
+                if (dst.hits(ffhip_plane_span(pic(j).ref[r].base[q], pic(j).ref[r].stride[q], (ptrdiff_t)rw * G.ps, rh))) {
+                    ffhip_set_error("%s: frame %d reference %d plane %d overlaps a plane the call writes", who, j, r, q);
                     return FFHIP_EINVAL;
                 }
             }
@@ -120,10 +83,13 @@ int check_frames(const char *fn, int bit_depth, int ss_h, int ss_v, int width, i
 extern "C" int ffhip_vp9_inter_frames_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPic *pics,
                                           void *stream)
 {
-    const int r = check_frames("ffhip_vp9_inter_frames_dev", bit_depth, ss_h, ss_v, width, height, npics, pics, [&](int, int, int p, int *w, int *h) {
-        *w = (width + (p ? ss_h : 0)) >> (p ? ss_h : 0);
-        *h = (height + (p ? ss_v : 0)) >> (p ? ss_v : 0);
-    });
+    const int r = check_frames(
+        "ffhip_vp9_inter_frames_dev", bit_depth, ss_h, ss_v, width, height, npics, pics,
+        [&](int i) -> const FFHipVp9InterPic & { return pics[i]; },
+        [&](int, int, int p, int *w, int *h) {
+            *w = (width + (p ? ss_h : 0)) >> (p ? ss_h : 0);
+            *h = (height + (p ? ss_v : 0)) >> (p ? ss_v : 0);
+        });
     if (r < 0)
         return r;
     if (!ffhip_have_device())
@@ -147,16 +113,12 @@ extern "C" int ffhip_vp9_inter_frames_scaled_dev(int bit_depth, int ss_h, int ss
                     return FFHIP_EINVAL;
                 }
             }
-    /* the frames as FFHipVp9InterPic for the common checks: pics[i].pic */
-    struct PicView {
-        const FFHipVp9InterPicScaled *s;
-        const FFHipVp9InterPic &operator[](int i) const { return s[i].pic; }
-        explicit operator bool() const { return s != nullptr; }
-    };
-    const int r = check_frames(fn, bit_depth, ss_h, ss_v, width, height, npics, PicView{ pics }, [&](int i, int ref, int p, int *w, int *h) {
-        *w = (pics[i].ref_w[ref] + (p ? ss_h : 0)) >> (p ? ss_h : 0);
-        *h = (pics[i].ref_h[ref] + (p ? ss_v : 0)) >> (p ? ss_v : 0);
-    });
+    const int r = check_frames(
+        fn, bit_depth, ss_h, ss_v, width, height, npics, pics, [&](int i) -> const FFHipVp9InterPic & { return pics[i].pic; },
+        [&](int i, int ref, int p, int *w, int *h) {
+            *w = (pics[i].ref_w[ref] + (p ? ss_h : 0)) >> (p ? ss_h : 0);
+            *h = (pics[i].ref_h[ref] + (p ? ss_v : 0)) >> (p ? ss_v : 0);
+        });
     if (r < 0)
         return r;
     if (!ffhip_have_device())

@@ -1,74 +1,51 @@
 /*
- * shims_vp9_intra.hip — ffhip_vp9_intra_frames_dev(): validates what the host can see of a frame set (geometry, planes, tile columns,
- * plane overlap) and launches the intra reconstruction (kernels/vp9_intra_frame.hip) on the caller's stream.  The records themselves
- * are device data and are checked by the kernel.  Also ffhip_vp9_intra_block_records(), the device-free expansion of one decoded
+ * shims_vp9_intra.hip — ffhip_vp9_intra_frames_dev(): the host checks (kernels/picture_check.h, tile columns, plane overlap) and the
+ * launch of the intra reconstruction (kernels/vp9_intra_frame.hip) on the caller's stream.  The records themselves are device data
+ * and are checked by the kernel.  Also ffhip_vp9_intra_block_records(), the device-free expansion of one decoded
  * block into its records in intra_recon's order (libavcodec/vp9recon.c).
  */
 #include <algorithm>
-#include <stdint.h>
-#include <vector>
 
 #include "kernels/common.h"
 #include "kernels/h264_kernels.h"
+#include "kernels/picture_check.h"
 
 extern "C" int ffhip_vp9_intra_record_size(void) { return (int)sizeof(FFHipVp9IntraRec); }
 
 extern "C" int ffhip_vp9_intra_frames_dev(int bit_depth, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9IntraPic *pics,
                                           void *stream)
 {
-    if ((bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (ss_h & ~1) || (ss_v & ~1)) {
-        ffhip_set_error("ffhip_vp9_intra_frames_dev: bit depth %d (8, 10 or 12), subsampling %d, %d (0 or 1 each)", bit_depth, ss_h, ss_v);
-        return FFHIP_EINVAL;
-    }
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) {
-        ffhip_set_error("ffhip_vp9_intra_frames_dev: frame size %d x %d (1..65535)", width, height);
-        return FFHIP_EINVAL;
-    }
-    if (npics <= 0 || !pics) {
-        ffhip_set_error("ffhip_vp9_intra_frames_dev: npics = %d, or a NULL frame array", npics);
-        return FFHIP_EINVAL;
-    }
-    const int ps = bit_depth > 8 ? 2 : 1;
-    const unsigned amask = 4u * ps - 1; /* four samples per access */
-    const int cols = (width + 7) >> 3, rows = (height + 7) >> 3;
-    int dw[3], dh[3]; /* decoded area per plane, samples */
-    for (int p = 0; p < 3; p++) {
-        dw[p] = (cols * 8) >> (p ? ss_h : 0);
-        dh[p] = (rows * 8) >> (p ? ss_v : 0);
-    }
-    struct Span { /* the bytes a plane occupies: [lo, hi) */
-        uintptr_t lo, hi;
-    };
-    std::vector<Span> spans;
-    spans.reserve((size_t)npics * 3);
+    static const char who[] = "ffhip_vp9_intra_frames_dev";
+    if (const int r = ffhip_check_vp9_frames(who, bit_depth, ss_h, ss_v, width, height, npics, pics))
+        return r;
+    const FFHipPlaneGeom G = FFHipPlaneGeom::vp9(bit_depth, ss_h, ss_v, width, height);
+    FFHipSpanSet planes;
+    planes.reserve((size_t)npics * 3);
     for (int i = 0; i < npics; i++) {
         const FFHipVp9IntraPic &P = pics[i];
         if (P.log2_tile_cols < 0 || P.log2_tile_cols > 6) {
-            ffhip_set_error("ffhip_vp9_intra_frames_dev: frame %d: log2_tile_cols %d (0..6)", i, P.log2_tile_cols);
+            ffhip_set_error("%s: frame %d: log2_tile_cols %d (0..6)", who, i, P.log2_tile_cols);
             return FFHIP_EINVAL;
         }
         for (int p = 0; p < 3; p++) {
             const FFHipVp9IntraPlane &D = P.plane[p];
             if (!D.base || !D.recs || !D.rec_sb_start || !D.coeffs) {
-                ffhip_set_error("ffhip_vp9_intra_frames_dev: frame %d plane %d: a NULL pointer", i, p);
+                ffhip_set_error("%s: frame %d plane %d: a NULL pointer", who, i, p);
                 return FFHIP_EINVAL;
             }
-            if ((((uintptr_t)D.base | (size_t)D.stride) & amask) || D.stride < (ptrdiff_t)dw[p] * ps) {
-                ffhip_set_error("ffhip_vp9_intra_frames_dev: frame %d plane %d: base and stride must be %u-byte aligned, the stride at least "
-                                "the decoded width", i, p, amask + 1);
+            if (!ffhip_plane_ok(D.base, D.stride, G.amask, G.row_bytes(p))) {
+                ffhip_set_error("%s: frame %d plane %d: base and stride must be %u-byte aligned, the stride at least the decoded width", who, i,
+                                p, G.amask + 1);
                 return FFHIP_EINVAL;
             }
-            const uintptr_t b = (uintptr_t)D.base;
-            spans.push_back({ b, b + (uintptr_t)((ptrdiff_t)(dh[p] - 1) * D.stride + (ptrdiff_t)dw[p] * ps) });
+            planes.add(G.span(D.base, D.stride, p));
         }
     }
     /* no two planes of the call may overlap: a launch's planes are reconstructed side by side */
-    std::sort(spans.begin(), spans.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
-    for (size_t k = 1; k < spans.size(); k++)
-        if (spans[k].lo < spans[k - 1].hi) {
-            ffhip_set_error("ffhip_vp9_intra_frames_dev: two planes of the call overlap");
-            return FFHIP_EINVAL;
-        }
+    if (planes.seal()) {
+        ffhip_set_error("%s: two planes of the call overlap", who);
+        return FFHIP_EINVAL;
+    }
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_vp9_intra_frames(bit_depth, ss_h, ss_v, width, height, npics, pics, (hipStream_t)stream);
