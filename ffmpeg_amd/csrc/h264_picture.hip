@@ -31,15 +31,36 @@ enum { ST_PUT = 0, ST_TMP = 1, ST_AVG = 2 };
 
 struct Section { size_t off = 0; int n = 0; };
 
-template <typename T>
-size_t place(size_t &total, const std::vector<T> &v, Section &s)
-{
-    total = (total + 15) & ~(size_t)15;
-    s.off = total;
-    s.n = (int)v.size();
-    total += v.size() * sizeof(T);
-    return s.off;
-}
+/* The one staging buffer of a flush.  add() names a list once: it lays the list out behind the ones before it, 16-byte aligned, and
+ * notes where its bytes come from; copy_to() runs the copies.  The lists stay as they are between the two. */
+struct Staging {
+    /* qpel and chroma MC per stage, weights, residual offsets and coefficients, edges, three lists per intra wavefront (4:4:4: three
+     * wavefronts; 4:2:2: the luma one and the chroma planes' own): no flush has more lists */
+    enum { MAX_PARTS = 3 * 3 + 2 * 3 + 3 + 2 * 3 * 6 + 3 + 3 * 3 + 3 };
+    struct Part { size_t off; const void *src; size_t bytes; } part[MAX_PARTS];
+    int nparts = 0;
+    size_t total = 0;
+
+    template <typename T>
+    Section add(const std::vector<T> &v)
+    {
+        total = (total + 15) & ~(size_t)15;
+        Section s;
+        s.off = total;
+        s.n = (int)v.size();
+        if (!v.empty()) { /* (one Section per add(): flush_impl checks their number against MAX_PARTS when it is compiled) */
+            part[nparts++] = Part{ total, v.data(), v.size() * sizeof(T) };
+            total += v.size() * sizeof(T);
+        }
+        return s;
+    }
+    size_t bytes() const { return (total + 255) & ~(size_t)255; }
+    void copy_to(uint8_t *hb) const
+    {
+        for (int i = 0; i < nparts; i++)
+            memcpy(hb + part[i].off, part[i].src, part[i].bytes);
+    }
+};
 } // namespace
 
 struct FFHipH264Picture {
@@ -843,55 +864,64 @@ struct FlushBack {
     const int16_t *c422_coef = nullptr;
 };
 
+/* `side` on the picture's second stream beside `main_` on the caller's, forked and joined with the picture's events.  A hand-off lost on
+ * the second stream is the caller's stream's to hear about (the wavefronts there file their failures under the caller's).  When `side`
+ * fails `main_` is skipped; the join is recorded and waited for all the same. */
+template <class Side, class Main>
+static int beside(FFHipH264Picture *p, hipStream_t stream, Side side, Main main_)
+{
+    HIP_TRY(hipEventRecord(p->fork, stream));
+    HIP_TRY(hipStreamWaitEvent(p->aux, p->fork, 0));
+    ffhip_progress_report_to(stream, true);
+    int r = side(p->aux);
+    ffhip_progress_report_to(nullptr, false);
+    HIP_TRY(hipEventRecord(p->join, p->aux));
+    if (r >= 0)
+        r = main_();
+    HIP_TRY(hipStreamWaitEvent(stream, p->join, 0));
+    return r;
+}
+
 /* the picture's intra wavefront(s) and in-loop filter, from what the front half left in `B` */
 static int flush_tail(FFHipH264Picture *p, uint8_t *const dst[3], const int stride[3], const FlushBack &B, hipStream_t stream)
 {
     const int bd = p->bd;
-    int r = 0;
     /* ---- intra macroblocks: every inter macroblock is complete now; one wavefront over the three planes (4:4:4: one per plane, side by
      * side in one launch) ---- */
-    if (B.c422) {
-        /* 4:2:2: the luma wavefront below is luma-only; the 8 x 16 chroma planes are a wavefront of their own, beside it on the picture's
-         * second stream (prediction never crosses planes) */
-        HIP_TRY(hipEventRecord(p->fork, stream));
-        HIP_TRY(hipStreamWaitEvent(p->aux, p->fork, 0));
-        ffhip_progress_report_to(stream, true); /* a hand-off lost on the second stream is the caller's stream's to hear about */
-        r = ffhip_launch_h264_intra_c422(bd, dst[1], dst[2], stride[1], p->mb_w, p->mb_h, B.c422, B.c422_rows, B.c422_coef, p->aux);
-        ffhip_progress_report_to(nullptr, false);
-        HIP_TRY(hipEventRecord(p->join, p->aux));
-    }
-    if (r >= 0 && B.nintra)
-        r = ffhip_launch_h264_intra_frames_bd(bd, B.nintra, B.ip, stride[0], stride[1], p->mb_w, p->mb_h, stream, p->cfmt != 1);
-    if (B.c422)
-        HIP_TRY(hipStreamWaitEvent(stream, p->join, 0));
+    auto intra = [&]() {
+        return B.nintra ? ffhip_launch_h264_intra_frames_bd(bd, B.nintra, B.ip, stride[0], stride[1], p->mb_w, p->mb_h, stream, p->cfmt != 1) : 0;
+    };
+    /* 4:2:2: that wavefront is luma-only; the 8 x 16 chroma planes are a wavefront of their own, beside it on the picture's second stream
+     * (prediction never crosses planes) */
+    auto intra_c422 = [&](hipStream_t aux) {
+        return ffhip_launch_h264_intra_c422(bd, dst[1], dst[2], stride[1], p->mb_w, p->mb_h, B.c422, B.c422_rows, B.c422_coef, aux);
+    };
+    int r = B.c422 ? beside(p, stream, intra_c422, intra) : intra();
     if (r < 0)
         return r;
     /* ---- in-loop filter, decoder order: the planes are independent, and a lone wavefront is a chain of dependent hand-offs that
      * leaves the GPU mostly idle — the chroma planes run beside the luma plane on the second stream ---- */
     const bool chroma = B.edges[1] || B.edges[2];
+    auto luma = [&]() {
+        return B.edges[0] ? ffhip_launch_h264_deblock_frames_bd(bd, 0, dst[0], 0, 1, stride[0], p->mb_w, p->mb_h, B.edges[0], stream) : 0;
+    };
     if (p->cfmt == 2) {
         /* 4:2:2: 8 x 16 chroma macroblocks with six edges each: a frame-order kernel of their own (both planes in one launch when they
          * share a stride), beside the luma plane's on the second stream */
-        if (chroma) {
-            HIP_TRY(hipEventRecord(p->fork, stream));
-            HIP_TRY(hipStreamWaitEvent(p->aux, p->fork, 0));
-            ffhip_progress_report_to(stream, true);
+        auto chroma_422 = [&](hipStream_t aux) {
+            int rc = 0;
             if (B.edges[1] && B.edges[2] && stride[1] == stride[2]) {
                 uint8_t *const pl_[2] = { dst[1], dst[2] };
                 const FFHipH264Edge *const ed_[2] = { B.edges[1], B.edges[2] };
-                r = ffhip_launch_h264_deblock_c422_planes(bd, 2, pl_, ed_, stride[1], p->mb_w, p->mb_h, p->aux);
+                rc = ffhip_launch_h264_deblock_c422_planes(bd, 2, pl_, ed_, stride[1], p->mb_w, p->mb_h, aux);
             } else {
-                for (int pl = 1; pl < 3 && r >= 0; pl++)
+                for (int pl = 1; pl < 3 && rc >= 0; pl++)
                     if (B.edges[pl])
-                        r = ffhip_launch_h264_deblock_c422(bd, dst[pl], stride[pl], p->mb_w, p->mb_h, B.edges[pl], p->aux);
+                        rc = ffhip_launch_h264_deblock_c422(bd, dst[pl], stride[pl], p->mb_w, p->mb_h, B.edges[pl], aux);
             }
-            ffhip_progress_report_to(nullptr, false);
-            HIP_TRY(hipEventRecord(p->join, p->aux));
-        }
-        if (r >= 0 && B.edges[0])
-            r = ffhip_launch_h264_deblock_frames_bd(bd, 0, dst[0], 0, 1, stride[0], p->mb_w, p->mb_h, B.edges[0], stream);
-        if (chroma)
-            HIP_TRY(hipStreamWaitEvent(stream, p->join, 0));
+            return rc;
+        };
+        r = chroma ? beside(p, stream, chroma_422, luma) : luma();
         return r < 0 ? r : 0;
     }
     if (p->cfmt == 3) {
@@ -909,34 +939,84 @@ static int flush_tail(FFHipH264Picture *p, uint8_t *const dst[3], const int stri
             }
         if (n > 1 && tab)
             return ffhip_launch_h264_deblock_pictures_bd(bd, 0, pl_, ed_, n, stride[0], p->mb_w, p->mb_h, stream);
-        n = 0;
         for (int pl = 0; pl < 3 && r >= 0; pl++)
             if (B.edges[pl])
                 r = ffhip_launch_h264_deblock_frames_bd(bd, 0, dst[pl], 0, 1, stride[pl], p->mb_w, p->mb_h, B.edges[pl], stream);
         return r < 0 ? r : 0;
     }
-    if (chroma) {
-        HIP_TRY(hipEventRecord(p->fork, stream));
-        HIP_TRY(hipStreamWaitEvent(p->aux, p->fork, 0));
+    auto chroma_420 = [&](hipStream_t aux) {
         const ptrdiff_t gap = dst[2] - dst[1];
-        ffhip_progress_report_to(stream, true); /* a hand-off lost on the second stream is the caller's stream's to hear about */
+        int rc = 0;
         /* (8 bits: Cb and Cr as ONE launch of two "pictures" when Cr follows Cb at a 4-byte aligned distance and both are filtered) */
         if (bd == 8 && B.edges[1] && B.edges[2] && stride[1] == stride[2] && gap > 0 && !(gap & 3) &&
             B.edges[2] == B.edges[1] + p->edges[1].size()) {
-            r = ffhip_launch_h264_deblock_frames_chroma(dst[1], (size_t)gap, 2, stride[1], p->mb_w, p->mb_h, B.edges[1], p->aux);
+            rc = ffhip_launch_h264_deblock_frames_chroma(dst[1], (size_t)gap, 2, stride[1], p->mb_w, p->mb_h, B.edges[1], aux);
         } else {
-            for (int pl = 1; pl < 3 && r >= 0; pl++)
+            for (int pl = 1; pl < 3 && rc >= 0; pl++)
                 if (B.edges[pl])
-                    r = ffhip_launch_h264_deblock_frames_bd(bd, 1, dst[pl], 0, 1, stride[pl], p->mb_w, p->mb_h, B.edges[pl], p->aux);
+                    rc = ffhip_launch_h264_deblock_frames_bd(bd, 1, dst[pl], 0, 1, stride[pl], p->mb_w, p->mb_h, B.edges[pl], aux);
         }
-        ffhip_progress_report_to(nullptr, false);
-        HIP_TRY(hipEventRecord(p->join, p->aux));
-    }
-    if (r >= 0 && B.edges[0])
-        r = ffhip_launch_h264_deblock_frames_bd(bd, 0, dst[0], 0, 1, stride[0], p->mb_w, p->mb_h, B.edges[0], stream);
-    if (chroma)
-        HIP_TRY(hipStreamWaitEvent(stream, p->join, 0));
+        return rc;
+    };
+    r = chroma ? beside(p, stream, chroma_420, luma) : luma();
     return r < 0 ? r : 0;
+}
+
+/* The wavefronts walk a row's intra macroblocks left to right: `in` sorted by (mb_y, mb_x) into `sorted`, recording order kept among
+ * equals, and the mb_h + 1 row starts into `rows`.  Returns the index in `sorted` of the first record that names the macroblock of the
+ * record before it, or -1 when every macroblock is named once. */
+template <typename Rec>
+static int sort_rows(const std::vector<Rec> &in, std::vector<Rec> &sorted, std::vector<int32_t> &rows, int mb_h)
+{
+    sorted = in;
+    std::stable_sort(sorted.begin(), sorted.end(), [](const Rec &a, const Rec &b) { return a.mb_y != b.mb_y ? a.mb_y < b.mb_y : a.mb_x < b.mb_x; });
+    rows.assign((size_t)mb_h + 1, 0);
+    int twice = -1;
+    for (size_t i = 0; i < sorted.size(); i++) {
+        if (twice < 0 && i && sorted[i].mb_y == sorted[i - 1].mb_y && sorted[i].mb_x == sorted[i - 1].mb_x)
+            twice = (int)i;
+        rows[(size_t)sorted[i].mb_y + 1]++;
+    }
+    for (int r = 0; r < mb_h; r++)
+        rows[(size_t)r + 1] += rows[r];
+    return twice;
+}
+
+/* a device buffer of `need` bytes: kept when it is large enough, else `want` bytes anew — the old one may still be read by launches of
+ * the previous picture on this stream */
+static int grow_device(void **buf, size_t *size, size_t need, size_t want, hipStream_t stream, const char *what)
+{
+    if (need <= *size)
+        return 0;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (*buf)
+        (void)hipFree(*buf);
+    *buf = nullptr;
+    *size = 0;
+    if (hipMalloc(buf, want) != hipSuccess) {
+        ffhip_set_error("ffhip_h264_picture_flush: %shipMalloc(%zu) failed", what, want);
+        return FFHIP_ENOMEM;
+    }
+    *size = want;
+    return 0;
+}
+
+/* the pinned buffer: no launch reads it, and the copy that does has been waited for */
+static int grow_pinned(FFHipH264Picture *p, size_t need)
+{
+    if (need <= p->pinned_sz)
+        return 0;
+    if (p->pinned)
+        (void)hipHostFree(p->pinned);
+    p->pinned = nullptr;
+    p->pinned_sz = 0;
+    const size_t want = need + need / 2;
+    if (hipHostMalloc(&p->pinned, want, hipHostMallocDefault) != hipSuccess) {
+        ffhip_set_error("ffhip_h264_picture_flush: hipHostMalloc(%zu) failed", want);
+        return FFHIP_ENOMEM;
+    }
+    p->pinned_sz = want;
+    return 0;
 }
 
 static int flush_impl(FFHipH264Picture *p, uint8_t *const dst[3], const int stride[3], const uint8_t *const ref[3], void *stream_, FlushBack *defer)
@@ -990,151 +1070,75 @@ static int flush_impl(FFHipH264Picture *p, uint8_t *const dst[3], const int stri
                         "aligned", p->bd > 8 ? 8 : 4);
         return FFHIP_EINVAL;
     }
-    /* layout of the one staging buffer */
-    size_t total = 0;
+    /* the one staging buffer: every list is named once, in the order it is laid out */
+    Staging S;
     Section s_qpel[3][3], s_cmc[2][3], s_wt[3], s_ioff[3][6], s_icoef[3][6], s_edge[3], s_intra[3], s_irows[3], s_intracoef[3];
     Section s_c422, s_c422rows, s_c422coef;
+    static_assert((sizeof s_qpel + sizeof s_cmc + sizeof s_wt + sizeof s_ioff + sizeof s_icoef + sizeof s_edge + sizeof s_intra + sizeof s_irows +
+                   sizeof s_intracoef + 3 * sizeof(Section)) / sizeof(Section) == Staging::MAX_PARTS, "one part of the staging table per Section");
     if (!p->intra_c422.empty()) {
-        p->intra_c422_sorted = p->intra_c422;
-        std::stable_sort(p->intra_c422_sorted.begin(), p->intra_c422_sorted.end(), [](const FFHipH264IntraC422 &a, const FFHipH264IntraC422 &b) {
-            return a.mb_y != b.mb_y ? a.mb_y < b.mb_y : a.mb_x < b.mb_x;
-        });
-        p->intra_c422_rows.assign((size_t)p->mb_h + 1, 0);
-        for (const FFHipH264IntraC422 &a : p->intra_c422_sorted)
-            p->intra_c422_rows[(size_t)a.mb_y + 1]++; /* (a macroblock recorded twice is caught on its luma record below) */
-        for (int r = 0; r < p->mb_h; r++)
-            p->intra_c422_rows[(size_t)r + 1] += p->intra_c422_rows[r];
+        (void)sort_rows(p->intra_c422, p->intra_c422_sorted, p->intra_c422_rows, p->mb_h); /* (a macroblock recorded twice is caught on its luma record below) */
         if (p->intra_c422_coef.empty())
             p->intra_c422_coef.assign(8, 0);
-        place(total, p->intra_c422_sorted, s_c422);
-        place(total, p->intra_c422_rows, s_c422rows);
-        place(total, p->intra_c422_coef, s_c422coef);
+        s_c422 = S.add(p->intra_c422_sorted);
+        s_c422rows = S.add(p->intra_c422_rows);
+        s_c422coef = S.add(p->intra_c422_coef);
     }
     for (int q = 0; q < nsets; q++) {
         if (p->intra[q].empty())
             continue;
-        /* the wavefront walks a row's intra macroblocks left to right: by (mb_y, mb_x), one record per macroblock */
-        p->intra_sorted[q] = p->intra[q];
-        std::stable_sort(p->intra_sorted[q].begin(), p->intra_sorted[q].end(), [](const FFHipH264IntraMB &a, const FFHipH264IntraMB &b) {
-            return a.mb_y != b.mb_y ? a.mb_y < b.mb_y : a.mb_x < b.mb_x;
-        });
-        p->intra_rows[q].assign((size_t)p->mb_h + 1, 0);
-        for (size_t i = 0; i < p->intra_sorted[q].size(); i++) {
-            const FFHipH264IntraMB &a = p->intra_sorted[q][i];
-            if (i && a.mb_y == p->intra_sorted[q][i - 1].mb_y && a.mb_x == p->intra_sorted[q][i - 1].mb_x) {
-                ffhip_set_error("ffhip_h264_picture_flush: macroblock (%d, %d) recorded twice as intra", a.mb_x, a.mb_y);
-                return FFHIP_EINVAL;
-            }
-            p->intra_rows[q][(size_t)a.mb_y + 1]++;
+        /* one record per macroblock */
+        const int twice = sort_rows(p->intra[q], p->intra_sorted[q], p->intra_rows[q], p->mb_h);
+        if (twice >= 0) {
+            const FFHipH264IntraMB &a = p->intra_sorted[q][(size_t)twice];
+            ffhip_set_error("ffhip_h264_picture_flush: macroblock (%d, %d) recorded twice as intra", a.mb_x, a.mb_y);
+            return FFHIP_EINVAL;
         }
-        for (int r = 0; r < p->mb_h; r++)
-            p->intra_rows[q][(size_t)r + 1] += p->intra_rows[q][r];
         if (p->intra_coef[q].empty())
             p->intra_coef[q].assign(8, 0); /* a picture of coefficient-free intra macroblocks still hands the kernel a base */
-        place(total, p->intra_sorted[q], s_intra[q]);
-        place(total, p->intra_rows[q], s_irows[q]);
-        place(total, p->intra_coef[q], s_intracoef[q]);
+        s_intra[q] = S.add(p->intra_sorted[q]);
+        s_irows[q] = S.add(p->intra_rows[q]);
+        s_intracoef[q] = S.add(p->intra_coef[q]);
     }
     for (int s = 0; s < 3; s++) {
         for (int pl = 0; pl < 3; pl++)
-            place(total, p->qpel[pl][s], s_qpel[pl][s]);
-        place(total, p->cmc[0][s], s_cmc[0][s]);
-        place(total, p->cmc[1][s], s_cmc[1][s]);
+            s_qpel[pl][s] = S.add(p->qpel[pl][s]);
+        for (int c = 0; c < 2; c++)
+            s_cmc[c][s] = S.add(p->cmc[c][s]);
     }
+    bool need_tmp[3];
     for (int pl = 0; pl < 3; pl++) {
-        place(total, p->wt[pl], s_wt[pl]);
+        need_tmp[pl] = s_qpel[pl][ST_TMP].n || (pl && s_cmc[pl - 1][ST_TMP].n);
+        s_wt[pl] = S.add(p->wt[pl]);
+        for (const FFHipWeightBlock &w : p->wt[pl])
+            need_tmp[pl] = need_tmp[pl] || w.bi;
         for (int k = 0; k < 6; k++) {
-            place(total, p->idct_off[pl][k], s_ioff[pl][k]);
-            place(total, p->idct_coef[pl][k], s_icoef[pl][k]);
+            s_ioff[pl][k] = S.add(p->idct_off[pl][k]);
+            s_icoef[pl][k] = S.add(p->idct_coef[pl][k]);
         }
         if (p->any_edge[pl])
-            place(total, p->edges[pl], s_edge[pl]);
+            s_edge[pl] = S.add(p->edges[pl]);
     }
-    total = (total + 255) & ~(size_t)255;
+    const size_t total = S.bytes();
     if (p->copy_pending) { /* the previous picture's records are still leaving the pinned buffer */
         HIP_TRY(hipEventSynchronize(p->copied));
         p->copy_pending = false;
     }
-    if (total > p->pinned_sz) {
-        if (p->pinned)
-            (void)hipHostFree(p->pinned);
-        p->pinned = nullptr;
-        p->pinned_sz = 0;
-        const size_t want = total + total / 2;
-        if (hipHostMalloc(&p->pinned, want, hipHostMallocDefault) != hipSuccess) {
-            ffhip_set_error("ffhip_h264_picture_flush: hipHostMalloc(%zu) failed", want);
-            return FFHIP_ENOMEM;
-        }
-        p->pinned_sz = want;
-    }
-    if (total > p->dev_sz) {
-        /* the old buffer may still be read by launches of the previous picture on this stream */
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (p->dev)
-            (void)hipFree(p->dev);
-        p->dev = nullptr;
-        p->dev_sz = 0;
-        const size_t want = total + total / 2;
-        if (hipMalloc(&p->dev, want) != hipSuccess) {
-            ffhip_set_error("ffhip_h264_picture_flush: hipMalloc(%zu) failed", want);
-            return FFHIP_ENOMEM;
-        }
-        p->dev_sz = want;
-    }
+    int r = grow_pinned(p, total);
+    if (r >= 0)
+        r = grow_device(&p->dev, &p->dev_sz, total, total + total / 2, stream, "");
+    if (r < 0)
+        return r;
     uint8_t *hb = (uint8_t *)p->pinned, *db = (uint8_t *)p->dev;
-    auto put = [&](const Section &s, const void *src, size_t bytes) {
-        if (bytes)
-            memcpy(hb + s.off, src, bytes);
-    };
-    for (int q = 0; q < nsets; q++)
-        if (!p->intra[q].empty()) {
-            put(s_intra[q], p->intra_sorted[q].data(), p->intra_sorted[q].size() * sizeof(FFHipH264IntraMB));
-            put(s_irows[q], p->intra_rows[q].data(), p->intra_rows[q].size() * sizeof(int32_t));
-            put(s_intracoef[q], p->intra_coef[q].data(), p->intra_coef[q].size() * sizeof(int16_t));
-        }
-    if (!p->intra_c422.empty()) {
-        put(s_c422, p->intra_c422_sorted.data(), p->intra_c422_sorted.size() * sizeof(FFHipH264IntraC422));
-        put(s_c422rows, p->intra_c422_rows.data(), p->intra_c422_rows.size() * sizeof(int32_t));
-        put(s_c422coef, p->intra_c422_coef.data(), p->intra_c422_coef.size() * sizeof(int16_t));
-    }
-    bool need_tmp[3] = { false, false, false };
-    for (int s = 0; s < 3; s++) {
-        for (int pl = 0; pl < 3; pl++)
-            put(s_qpel[pl][s], p->qpel[pl][s].data(), p->qpel[pl][s].size() * sizeof(FFHipQpelBlock));
-        for (int c = 0; c < 2; c++)
-            put(s_cmc[c][s], p->cmc[c][s].data(), p->cmc[c][s].size() * sizeof(FFHipChromaBlock));
-    }
-    for (int pl = 0; pl < 3; pl++)
-        need_tmp[pl] = !p->qpel[pl][ST_TMP].empty() || (pl && !p->cmc[pl - 1][ST_TMP].empty());
-    for (int pl = 0; pl < 3; pl++) {
-        put(s_wt[pl], p->wt[pl].data(), p->wt[pl].size() * sizeof(FFHipWeightBlock));
-        for (const FFHipWeightBlock &w : p->wt[pl])
-            need_tmp[pl] = need_tmp[pl] || w.bi;
-        for (int k = 0; k < 6; k++) {
-            put(s_ioff[pl][k], p->idct_off[pl][k].data(), p->idct_off[pl][k].size() * sizeof(int32_t));
-            put(s_icoef[pl][k], p->idct_coef[pl][k].data(), p->idct_coef[pl][k].size() * sizeof(int16_t));
-        }
-        if (p->any_edge[pl])
-            put(s_edge[pl], p->edges[pl].data(), p->edges[pl].size() * sizeof(FFHipH264Edge));
-    }
+    S.copy_to(hb);
     /* bi-prediction scratch planes: same stride as the picture (the MC kernels take one stride for both operands) */
-    for (int pl = 0; pl < 3; pl++) {
-        if (!need_tmp[pl])
-            continue;
-        const size_t rows = (size_t)p->plane_h(pl), need = rows * (size_t)stride[pl] + 64;
-        if (need > p->tmp_sz[pl]) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (p->tmp[pl])
-                (void)hipFree(p->tmp[pl]);
-            p->tmp[pl] = nullptr;
-            p->tmp_sz[pl] = 0;
-            if (hipMalloc((void **)&p->tmp[pl], need) != hipSuccess) {
-                ffhip_set_error("ffhip_h264_picture_flush: scratch plane hipMalloc(%zu) failed", need);
-                return FFHIP_ENOMEM;
-            }
-            p->tmp_sz[pl] = need;
-        }
+    for (int pl = 0; pl < 3 && r >= 0; pl++) {
+        const size_t need = (size_t)p->plane_h(pl) * (size_t)stride[pl] + 64;
+        if (need_tmp[pl])
+            r = grow_device((void **)&p->tmp[pl], &p->tmp_sz[pl], need, need, stream, "scratch plane ");
     }
+    if (r < 0)
+        return r;
     if (total) {
         HIP_TRY(hipMemcpyAsync(db, hb, total, hipMemcpyHostToDevice, stream));
         HIP_TRY(hipEventRecord(p->copied, stream));
@@ -1143,7 +1147,7 @@ static int flush_impl(FFHipH264Picture *p, uint8_t *const dst[3], const int stri
 
     FlushBack B;
     for (int q = 0; q < nsets; q++)
-        if (!p->intra[q].empty()) {
+        if (s_intra[q].n) {
             /* 4:4:4: the plane as the "luma" of a luma-only wavefront (cb / cr are never touched there) */
             uint8_t *const y = p->cfmt == 3 ? dst[q] : dst[0];
             B.ip[B.nintra++] = FFHipH264IntraPic{ y, p->cfmt == 3 ? y : dst[1], p->cfmt == 3 ? y : dst[2], (const FFHipH264IntraMB *)(db + s_intra[q].off),
@@ -1152,13 +1156,12 @@ static int flush_impl(FFHipH264Picture *p, uint8_t *const dst[3], const int stri
     for (int pl = 0; pl < 3; pl++)
         if (p->any_edge[pl])
             B.edges[pl] = (const FFHipH264Edge *)(db + s_edge[pl].off);
-    if (!p->intra_c422.empty()) {
+    if (s_c422.n) {
         B.c422 = (const FFHipH264IntraC422 *)(db + s_c422.off);
         B.c422_rows = (const int32_t *)(db + s_c422rows.off);
         B.c422_coef = (const int16_t *)(db + s_c422coef.off);
     }
 
-    int r = 0;
     if (p->bd > 8) {
         /* the same stages on the kernels templated on the sample type (kernels/h264_hbd.hip): one launch per list */
         const int bd = p->bd;
@@ -1244,42 +1247,35 @@ static int flush_impl(FFHipH264Picture *p, uint8_t *const dst[3], const int stri
     return flush_tail(p, dst, stride, B, stream);
 }
 
+/* no C++ exception crosses the C boundary: the host side of a flush allocates (vectors, strings, threads).  std::bad_alloc is
+ * FFHIP_ENOMEM; any other exception is `other` with the message `other_what` */
+template <class F>
+static int no_exceptions(const char *who, int other, const char *other_what, F f)
+{
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        ffhip_set_error("%s: out of host memory", who);
+        return FFHIP_ENOMEM;
+    } catch (...) {
+        ffhip_set_error("%s: %s", who, other_what);
+        return other;
+    }
+}
+
 extern "C" int ffhip_h264_picture_flush(FFHipH264Picture *p, uint8_t *const dst[3], const int stride[3], const uint8_t *const ref[3],
                                         void *stream)
 {
-    int r;
-    try { /* no C++ exception crosses the C boundary */
-        r = flush_impl(p, dst, stride, ref, stream, nullptr);
-    } catch (...) {
-        ffhip_set_error("ffhip_h264_picture_flush: out of host memory");
-        r = FFHIP_ENOMEM;
-    }
+    const int r = no_exceptions("ffhip_h264_picture_flush", FFHIP_ENOMEM, "out of host memory", [&]() { return flush_impl(p, dst, stride, ref, stream, nullptr); });
     if (p)
         p->last_status = r < 0 ? r : 0;
     return r;
 }
 
-/* Several pictures together: every picture's own staging copy, prediction and residual launches (throughput kernels), then what is a
- * latency chain per picture — the intra reconstruction wavefront and the in-loop filter — ONCE for all of them, side by side. */
-static int pictures_flush(FFHipH264Picture *const *pics, int n, uint8_t *const *dst, const int stride[3], const uint8_t *const *ref, void *stream_);
-
 extern "C" int ffhip_h264_picture_status(const FFHipH264Picture *p) { return p ? p->last_status : FFHIP_EINVAL; }
 
-extern "C" int ffhip_h264_pictures_flush(FFHipH264Picture *const *pics, int n, uint8_t *const *dst, const int stride[3], const uint8_t *const *ref,
-                                         void *stream_)
-{
-    /* no C++ exception crosses the C boundary: the host side of a flush allocates (vectors, strings) */
-    try {
-        return pictures_flush(pics, n, dst, stride, ref, stream_);
-    } catch (const std::bad_alloc &) {
-        ffhip_set_error("ffhip_h264_pictures_flush: out of host memory");
-        return FFHIP_ENOMEM;
-    } catch (...) {
-        ffhip_set_error("ffhip_h264_pictures_flush: unexpected failure on the host side");
-        return FFHIP_EIO;
-    }
-}
-
+/* Several pictures together: every picture's own staging copy, prediction and residual launches (throughput kernels), then what is a
+ * latency chain per picture — the intra reconstruction wavefront and the in-loop filter — ONCE for all of them, side by side. */
 static int pictures_flush(FFHipH264Picture *const *pics, int n, uint8_t *const *dst, const int stride[3], const uint8_t *const *ref, void *stream_)
 {
     if (n < 0 || (n && (!pics || !dst || !stride || !ref)))
@@ -1389,22 +1385,18 @@ static int pictures_flush(FFHipH264Picture *const *pics, int n, uint8_t *const *
             ic.push_back(FFHipH264C422Pic{ dst[3 * i + 1], dst[3 * i + 2], B[i].c422, B[i].c422_rows, B[i].c422_coef });
     }
     int r = 0;
-    if (!ic.empty()) { /* the chroma planes' wavefronts of all pictures beside the luma ones, on the first object's second stream */
-        if (stride[1] != stride[2]) {
-            ffhip_set_error("ffhip_h264_pictures_flush: Cb and Cr share a stride");
-            return FFHIP_EINVAL;
-        }
-        HIP_TRY(hipEventRecord(p0->fork, stream));
-        HIP_TRY(hipStreamWaitEvent(p0->aux, p0->fork, 0));
-        ffhip_progress_report_to(stream, true);
-        r = ffhip_launch_h264_intra_c422_pics(bd, (int)ic.size(), ic.data(), stride[1], mb_w, mb_h, p0->aux);
-        ffhip_progress_report_to(nullptr, false);
-        HIP_TRY(hipEventRecord(p0->join, p0->aux));
+    /* the chroma planes' wavefronts of all pictures beside the luma ones, on the first object's second stream */
+    if (!ic.empty() && stride[1] != stride[2]) {
+        ffhip_set_error("ffhip_h264_pictures_flush: Cb and Cr share a stride");
+        return FFHIP_EINVAL;
     }
-    if (r >= 0 && !ip.empty())
-        r = ffhip_launch_h264_intra_frames_bd(bd, (int)ip.size(), ip.data(), stride[0], stride[1], mb_w, mb_h, stream, c444 || c422);
-    if (!ic.empty())
-        HIP_TRY(hipStreamWaitEvent(stream, p0->join, 0));
+    auto intra = [&]() {
+        return ip.empty() ? 0 : ffhip_launch_h264_intra_frames_bd(bd, (int)ip.size(), ip.data(), stride[0], stride[1], mb_w, mb_h, stream, c444 || c422);
+    };
+    auto intra_c422 = [&](hipStream_t aux) {
+        return ffhip_launch_h264_intra_c422_pics(bd, (int)ic.size(), ic.data(), stride[1], mb_w, mb_h, aux);
+    };
+    r = ic.empty() ? intra() : beside(p0, stream, intra_c422, intra);
     if (r < 0)
         return r;
     /* the in-loop filter: all chroma planes (Cb and Cr of every picture: up to 2 n "pictures") on the first object's second stream
@@ -1427,19 +1419,14 @@ static int pictures_flush(FFHipH264Picture *const *pics, int n, uint8_t *const *
         return FFHIP_EINVAL;
     }
 
-    if (!pl_c.empty()) {
-        HIP_TRY(hipEventRecord(p0->fork, stream));
-        HIP_TRY(hipStreamWaitEvent(p0->aux, p0->fork, 0));
-        ffhip_progress_report_to(stream, true);
-        r = c422 ? ffhip_launch_h264_deblock_c422_planes(bd, (int)pl_c.size(), pl_c.data(), ed_c.data(), stride[1], mb_w, mb_h, p0->aux)
-                 : ffhip_launch_h264_deblock_pictures_bd(bd, 1, pl_c.data(), ed_c.data(), (int)pl_c.size(), stride[1], mb_w, mb_h, p0->aux);
-        ffhip_progress_report_to(nullptr, false);
-        HIP_TRY(hipEventRecord(p0->join, p0->aux));
-    }
-    if (r >= 0 && !pl_y.empty())
-        r = ffhip_launch_h264_deblock_pictures_bd(bd, 0, pl_y.data(), ed_y.data(), (int)pl_y.size(), stride[0], mb_w, mb_h, stream);
-    if (!pl_c.empty())
-        HIP_TRY(hipStreamWaitEvent(stream, p0->join, 0));
+    auto luma = [&]() {
+        return pl_y.empty() ? 0 : ffhip_launch_h264_deblock_pictures_bd(bd, 0, pl_y.data(), ed_y.data(), (int)pl_y.size(), stride[0], mb_w, mb_h, stream);
+    };
+    auto chroma = [&](hipStream_t aux) {
+        return c422 ? ffhip_launch_h264_deblock_c422_planes(bd, (int)pl_c.size(), pl_c.data(), ed_c.data(), stride[1], mb_w, mb_h, aux)
+                    : ffhip_launch_h264_deblock_pictures_bd(bd, 1, pl_c.data(), ed_c.data(), (int)pl_c.size(), stride[1], mb_w, mb_h, aux);
+    };
+    r = pl_c.empty() ? luma() : beside(p0, stream, chroma, luma);
     if (r < 0) { /* a shared stage failed: no picture of the batch is known to be complete */
         for (int i = 0; i < n; i++)
             if (!pics[i]->last_status)
@@ -1448,4 +1435,10 @@ static int pictures_flush(FFHipH264Picture *const *pics, int n, uint8_t *const *
     }
     shared_guard.armed = false;
     return first_err;
+}
+
+extern "C" int ffhip_h264_pictures_flush(FFHipH264Picture *const *pics, int n, uint8_t *const *dst, const int stride[3], const uint8_t *const *ref,
+                                         void *stream)
+{
+    return no_exceptions("ffhip_h264_pictures_flush", FFHIP_EIO, "unexpected failure on the host side", [&]() { return pictures_flush(pics, n, dst, stride, ref, stream); });
 }

@@ -1,4 +1,4 @@
-"""One adapter per whole-picture face (12 faces: five HEVC, five VP9, two VP8) for the tests that run the faces on a caller's stream:
+"""One adapter per whole-picture face (14 faces: five HEVC, five VP9, two VP8, two H.264) for the tests that run the faces on a caller's stream:
 tests/test_picture_faces_cpu.py (the staged tests can fail), tests/test_gpu_picture_streams.py and tests/picture_stream_child.py.
 
 An adapter splits a face's test into the steps a stream test has to interleave with its own work:
@@ -12,7 +12,8 @@ For the CPU tier: wants() the model's outputs, prefill() what the same samples h
 faces the source plane), alt_wants(seed) the model's outputs when the input samples alone are drawn again with another seed.
 
 Shapes are the smallest of the existing GPU tests at which each face still has its structure: 200 x 136 or 264 x 200 with 32 x 32
-CTBs, tiles and slices (HEVC), 200 x 136 (VP9: 4 x 3 superblocks), 5 x 4 macroblocks with intra and inter macroblocks (VP8)."""
+CTBs, tiles and slices (HEVC), 200 x 136 (VP9: 4 x 3 superblocks), 5 x 4 macroblocks with intra and inter macroblocks (VP8), 6 x 4 macroblocks,
+30 % of them intra (H.264: the picture object alone and three of them as a batch; 4:2:2 and 4:4:4 flushes are not covered here)."""
 import copy
 
 import numpy as np
@@ -540,9 +541,119 @@ class Vp8LoopFilter(Face):
         T._frame_compare([[view(t) for t in self.hosts[0]]], [self.want])
 
 
+# ================================================================================================================= H.264
+class H264Picture(Face):
+    """One 4:2:0 picture of 6 x 4 macroblocks, 30 % of them intra, recorded into a picture object and flushed on the stream: MC, weights,
+    residuals, an intra wavefront, and the chroma planes' in-loop filter beside the luma plane's on the object's second stream.
+    The records travel from host memory at the flush, so the inputs on the device are the reference planes alone."""
+    name, codec, mb_w, mb_h, pad, npics = "h264_picture", "h264", 6, 4, 32, 1
+
+    def _p_intra(self, i):
+        return 0.3
+
+    def _record(self, seed, alt=None):
+        """the pictures of `seed` recorded into picture objects of their own and decoded by the oracle: (objects, references, planes
+        before, planes wanted).  alt: the references and the planes before (the samples, not the records) drawn with that seed"""
+        import ffi
+        import test_gpu_h264_picture as T
+        from ffmpeg_amd import h264
+        rng = np.random.default_rng(seed)
+        H, P = 16 * self.mb_h, self.pad
+        sy, sc = self.strides[0], self.strides[1]
+        refs = [rng.integers(0, 256, (2 * (H + 2 * P), sy), dtype=np.uint8), rng.integers(0, 256, (2 * (H // 2 + P), sc), dtype=np.uint8),
+                rng.integers(0, 256, (2 * (H // 2 + P), sc), dtype=np.uint8)]
+        arng = None if alt is None else np.random.default_rng(alt)
+        if arng is not None:
+            refs = [_alt_like(arng, r, 255) for r in refs]
+        pics, before, want = [], [], []
+        for i in range(self.npics):
+            planes = None if arng is None else [arng.integers(0, 256, (h, s), dtype=np.uint8) for h, s in ((H, sy), (H // 2, sc), (H // 2, sc))]
+            pics.append(h264.Picture(self.mb_w, self.mb_h))
+            d, w = T._record_one(pics[-1], rng, ffi.oracle(), h264, self.mb_w, self.mb_h, P, refs, self.strides, self._p_intra(i), planes)
+            before.append(d)
+            want.append(w)
+        return pics, refs, before, want
+
+    @property
+    def strides(self):
+        sy, sc = 16 * self.mb_w + 2 * self.pad, 8 * self.mb_w + self.pad
+        return [sy, sc, sc]
+
+    def _lists(self, pic):
+        import ctypes as C
+
+        import test_h264_picture_cpu as TC
+        from ffmpeg_amd import _lib
+        ls = TC.Lists()
+        assert _lib.lib().ffhip_h264_picture_lists(pic._p, C.byref(ls)) == 0
+        return ls
+
+    def build(self, seed):
+        self.seed = seed
+        self.pics, self.refs, self.before, self.want = self._record(seed)
+        for i, pic in enumerate(self.pics):
+            ls = self._lists(pic)
+            assert bool(ls.nintra[0]) == bool(self._p_intra(i)), "picture %d: intra macroblocks" % i
+            assert all(ls.nqpel[0]) and all(ls.nwt) and all(ls.edges), "picture %d needs every MC stage, weights and edges in three planes" % i
+        return self
+
+    def fresh(self):
+        """the object owns staging buffers and streams: a copy records the same pictures into objects of its own.  (The decoy of a
+        late=True run flushes its recorded lists once per pool slot, in place on planes of its own: a flush keeps the lists until the
+        next begin(), and what the repeated flushes leave in those planes is never compared.  The objects are closed when collected.)"""
+        g = copy.copy(self)
+        g.pics = self._record(self.seed)[0]
+        return g
+
+    def wants(self):
+        return [pl for w in self.want for pl in w]
+
+    def prefill(self):
+        return [pl for d in self.before for pl in d]
+
+    def alt_wants(self, seed):
+        pics, _, _, want = self._record(self.seed, alt=seed)
+        for p in pics:
+            p.close()
+        return [pl for w in want for pl in w]
+
+    def upload(self, torch):
+        self.d_refs = [torch.from_numpy(r).cuda() for r in self.refs]
+        self.d_dst = [[torch.from_numpy(a.copy()).cuda() for a in d] for d in self.before]
+
+    def call(self, stream):
+        self.pics[0].flush(self.d_dst[0], self.strides, self.d_refs, stream=stream)
+
+    def inputs(self):
+        return list(self.d_refs)
+
+    def outputs(self):
+        return [t for d in self.d_dst for t in d]
+
+    def compare(self, view=lambda t: t):
+        for i, (d, w) in enumerate(zip(self.d_dst, self.want)):
+            for pl in range(3):
+                got = view(d[pl]).cpu().numpy()
+                assert np.array_equal(got, w[pl]), "%s: picture %d plane %d: %d mismatches" % (self.name, i, pl, (got != w[pl]).sum())
+
+
+class H264PicturesBatch(H264Picture):
+    """three such pictures flushed together, the second without an intra macroblock: the smallest batch whose front halves run on
+    threads of the call, with the intra wavefronts and the in-loop filter of all three shared"""
+    name, npics = "h264_pictures_batch", 3
+
+    def _p_intra(self, i):
+        return 0.0 if i == 1 else 0.3
+
+    def call(self, stream):
+        from ffmpeg_amd import h264
+        h264.pictures_flush(self.pics, self.d_dst, self.strides, [self.d_refs] * self.npics, stream=stream)
+
+
 FACES = [HevcResidual, HevcInter, HevcIntra, HevcLoopFilter, HevcBoundaryStrengths,
-         Vp9Inter, Vp9InterScaled, Vp9Intra, Vp9LoopFilter, Vp9LoopFilterSsc, Vp8Recon, Vp8LoopFilter]
+         Vp9Inter, Vp9InterScaled, Vp9Intra, Vp9LoopFilter, Vp9LoopFilterSsc, Vp8Recon, Vp8LoopFilter, H264Picture, H264PicturesBatch]
 NAMES = [F.name for F in FACES]
+#: the codecs whose faces chain, run on frame threads and have a first-use child (the H.264 picture object has none of the three)
 CODECS = ["hevc", "vp9", "vp8"]
 #: the seeds of the stream tests; tests/test_picture_faces_cpu.py shows that with them a staged test cannot pass by accident
 SEED = {name: 8800 + i for i, name in enumerate(NAMES)}

@@ -111,12 +111,15 @@ def _make_mb(rng, mx, my, W, H, P, sy, sc, p_intra=0.0, depth=8):
     return calls
 
 
-def _record_one(pic, rng, O, h264, mb_w, mb_h, P, refs, strides, p_intra):
-    """one picture recorded into `pic` (begin() .. the last deblock_mb) and decoded by the oracle: returns (dst0, want)"""
+def _record_one(pic, rng, O, h264, mb_w, mb_h, P, refs, strides, p_intra, planes=None):
+    """one picture recorded into `pic` (begin() .. the last deblock_mb) and decoded by the oracle: returns (dst0, want).
+    planes: what the picture's planes hold before the call, in place of the ones drawn here (the draw is made all the same)"""
     W, H = mb_w * 16, mb_h * 16
     sy, sc = strides[0], strides[1]
     dst0 = [rng.integers(0, 256, (H, sy), dtype=np.uint8), rng.integers(0, 256, (H // 2, sc), dtype=np.uint8),
             rng.integers(0, 256, (H // 2, sc), dtype=np.uint8)]
+    if planes is not None:
+        dst0 = planes
     want = [a.copy() for a in dst0]
     tmp = [np.zeros_like(a) for a in dst0]                # the oracle's bi-prediction scratch
     edges = [np.zeros(mb_w * mb_h * (8 if pl == 0 else 4), EDGE_DT) for pl in range(3)]

@@ -3,7 +3,7 @@ streams made by ffhip_stream_create are hipStreamNonBlocking, so whatever a laun
 counters, the copy of the picture structs into a pool slot, the first kernel of a two-kernel call, a first-use table upload) is not
 ordered against the caller's work at all.  Every other picture-face test runs on the NULL stream, where that cannot show.
 
-test_face_on_a_created_stream   each of the 12 faces alone: poisoned tensors, then on one created stream a delay, the copies that put
+test_face_on_a_created_stream   each of the 14 faces alone: poisoned tensors, then on one created stream a delay, the copies that put
                                 the real inputs in place, the face, and a snapshot of its outputs; one ffhip_stream_synchronize.  A
                                 face that runs any part of itself elsewhere reads poison or is snapshotted too early
                                 (tests/test_picture_faces_cpu.py shows that both give a mismatch).

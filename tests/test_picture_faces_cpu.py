@@ -6,7 +6,7 @@ the staged input.  For every adapter of picture_faces.py, with the seeds the GPU
   - every output plane or map of the model differs from its pre-call fill (the sentinel, or for in-place faces the source plane),
     and from a buffer of the poison byte, which is what a face that read poisoned records (all malformed: it writes nothing) leaves;
   - the model's output changes in every compared plane or map when the input samples alone are drawn again with a second seed: the
-    weaker form of the check, for all twelve, since most generators' models do not take malformed records;
+    weaker form of the check, for all fourteen, since most generators' models do not take malformed records;
   - the stronger form where the model does take them (VP8 reconstruction, whose model applies the kernels' own well-formedness
     rule): run on the records, coefficients, references and planes as they sit on the device before staging, every byte poison, it
     finds no record well formed, writes nothing, and so differs from the model run on the real input in every plane.
@@ -71,6 +71,6 @@ def test_the_vp8_recon_model_on_poison_writes_nothing():
 
 
 def test_every_face_is_listed_once():
-    assert len(PF.NAMES) == len(set(PF.NAMES)) == 12
-    assert sorted(n for c in PF.CODECS for n in PF.of_codec(c)) == sorted(PF.NAMES)
-    assert len(set(PF.SEED.values())) == 12
+    assert len(PF.NAMES) == len(set(PF.NAMES)) == 14
+    assert sorted(n for c in PF.CODECS + ["h264"] for n in PF.of_codec(c)) == sorted(PF.NAMES)
+    assert len(set(PF.SEED.values())) == 14
