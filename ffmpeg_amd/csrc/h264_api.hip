@@ -435,8 +435,12 @@ extern "C" int ffhip_vp9_intra_pred_batch_dev_hbd(int bit_depth, int tx, uint8_t
 extern "C" int ffhip_vp9_loopfilter_frame_dev(int bit_depth, uint8_t *y, uint8_t *u, uint8_t *v, ptrdiff_t stride_y, ptrdiff_t stride_uv, int cols,
                                               int rows, const FFHipVp9LfSb *tables, void *stream)
 {
-    if (!hevc_bd_ok(bit_depth) || !y || !u || !v || !tables || cols < 0 || rows < 0 || rows > 8 * 2047)
+    if (!hevc_bd_ok(bit_depth) || !y || !u || !v || !tables || cols < 0 || rows < 0)
         return FFHIP_EINVAL;
+    if (rows > 8 * 2047) {
+        ffhip_set_error("ffhip_vp9_loopfilter_frame_dev: %d rows of 8x8 blocks exceed the supported %d (2047 superblock rows)", rows, 8 * 2047);
+        return FFHIP_EINVAL;
+    }
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_vp9_lf_frame(bit_depth, y, u, v, stride_y, stride_uv, cols, rows, tables, (hipStream_t)stream);
@@ -447,8 +451,12 @@ extern "C" int ffhip_vp9_loopfilter_frame_ss_dev(int bit_depth, int ss_h, int ss
 {
     if (ss_h == 1 && ss_v == 1)
         return ffhip_vp9_loopfilter_frame_dev(bit_depth, y, u, v, stride_y, stride_uv, cols, rows, tables, stream);
-    if (!hevc_bd_ok(bit_depth) || !y || !u || !v || !tables || cols < 0 || rows < 0 || rows > 8 * 1364)
+    if (!hevc_bd_ok(bit_depth) || !y || !u || !v || !tables || cols < 0 || rows < 0)
         return FFHIP_EINVAL;
+    if (rows > 8 * 1364) {
+        ffhip_set_error("ffhip_vp9_loopfilter_frame_ss_dev: %d rows of 8x8 blocks exceed the supported %d (1364 superblock rows)", rows, 8 * 1364);
+        return FFHIP_EINVAL;
+    }
     if (ss_h || ss_v) { /* 4:4:0 / 4:2:2: rectangular chroma superblocks take tables of their own */
         ffhip_set_error("ffhip_vp9_loopfilter_frame_ss_dev: chroma sub-sampling %d x %d needs the chroma tables (ffhip_vp9_loopfilter_frame_ssc_dev)", ss_h, ss_v);
         return FFHIP_EINVAL;
@@ -462,9 +470,12 @@ extern "C" int ffhip_vp9_loopfilter_frame_ssc_dev(int bit_depth, int ss_h, int s
                                                   ptrdiff_t stride_uv, int cols, int rows, const FFHipVp9LfSb *tables, const FFHipVp9LfSbC *ctables,
                                                   void *stream)
 {
-    if (!hevc_bd_ok(bit_depth) || !y || !u || !v || !tables || !ctables || cols < 0 || rows < 0 || rows > 8 * 1364 || ss_h == ss_v ||
-        ((ss_h | ss_v) & ~1))
+    if (!hevc_bd_ok(bit_depth) || !y || !u || !v || !tables || !ctables || cols < 0 || rows < 0 || ss_h == ss_v || ((ss_h | ss_v) & ~1))
         return FFHIP_EINVAL;
+    if (rows > 8 * 1364) {
+        ffhip_set_error("ffhip_vp9_loopfilter_frame_ssc_dev: %d rows of 8x8 blocks exceed the supported %d (1364 superblock rows)", rows, 8 * 1364);
+        return FFHIP_EINVAL;
+    }
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_vp9_lf_frame_ssc(bit_depth, ss_h, ss_v, y, u, v, stride_y, stride_uv, cols, rows, tables, ctables, (hipStream_t)stream);
@@ -473,8 +484,12 @@ extern "C" int ffhip_vp9_loopfilter_frame_ssc_dev(int bit_depth, int ss_h, int s
 extern "C" int ffhip_vp9_loopfilter_frames_dev(int bit_depth, int ss_h, int ss_v, int npics, const FFHipVp9LfPic *pics, ptrdiff_t stride_y,
                                                ptrdiff_t stride_uv, int cols, int rows, void *stream)
 {
-    if (!hevc_bd_ok(bit_depth) || npics < 0 || (npics && !pics) || cols < 0 || rows < 0 || rows > 8 * 1364)
+    if (!hevc_bd_ok(bit_depth) || npics < 0 || (npics && !pics) || cols < 0 || rows < 0)
         return FFHIP_EINVAL;
+    if (rows > 8 * 1364) {
+        ffhip_set_error("ffhip_vp9_loopfilter_frames_dev: %d rows of 8x8 blocks exceed the supported %d (1364 superblock rows)", rows, 8 * 1364);
+        return FFHIP_EINVAL;
+    }
     if (ss_h != ss_v) { /* 4:4:0 / 4:2:2 need the chroma tables of their rectangular superblocks: ffhip_vp9_loopfilter_frames_ssc_dev */
         ffhip_set_error("ffhip_vp9_loopfilter_frames_dev: chroma sub-sampling %d x %d takes chroma tables: ffhip_vp9_loopfilter_frames_ssc_dev", ss_h, ss_v);
         return FFHIP_EINVAL;
@@ -487,8 +502,12 @@ extern "C" int ffhip_vp9_loopfilter_frames_dev(int bit_depth, int ss_h, int ss_v
 extern "C" int ffhip_vp9_loopfilter_frames_ssc_dev(int bit_depth, int ss_h, int ss_v, int npics, const FFHipVp9LfPicC *pics, ptrdiff_t stride_y,
                                                    ptrdiff_t stride_uv, int cols, int rows, void *stream)
 {
-    if (!hevc_bd_ok(bit_depth) || npics < 0 || (npics && !pics) || cols < 0 || rows < 0 || rows > 8 * 1364 || ss_h == ss_v || ((ss_h | ss_v) & ~1))
+    if (!hevc_bd_ok(bit_depth) || npics < 0 || (npics && !pics) || cols < 0 || rows < 0 || ss_h == ss_v || ((ss_h | ss_v) & ~1))
         return FFHIP_EINVAL;
+    if (rows > 8 * 1364) {
+        ffhip_set_error("ffhip_vp9_loopfilter_frames_ssc_dev: %d rows of 8x8 blocks exceed the supported %d (1364 superblock rows)", rows, 8 * 1364);
+        return FFHIP_EINVAL;
+    }
     if (!ffhip_have_device())
         return FFHIP_ENOSYS;
     return ffhip_launch_vp9_lf_frames_ssc(bit_depth, ss_h, ss_v, npics, pics, stride_y, stride_uv, cols, rows, (hipStream_t)stream);
