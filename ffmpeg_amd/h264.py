@@ -121,6 +121,55 @@ EDGE_DTYPE = np.dtype([("offset", "<i4"), ("kind", "u1"), ("alpha", "u1"), ("bet
 assert QPEL_DTYPE.itemsize == 16 and CHROMA_DTYPE.itemsize == 20 and WEIGHT_DTYPE.itemsize == 20 and EDGE_DTYPE.itemsize == 12
 
 
+#: FFHipH264MvField (include/ffhip.h): one 4 x 4 luma block of the motion field.  mv: [list][x, y] in quarter samples; ref_idx < 0:
+#: the list is unused.
+BS_MVF_DTYPE = np.dtype([("mv", np.int16, (2, 2)), ("ref_idx", np.int8, 2), ("pad", np.uint8, 2)])
+#: FFHipH264BsMb: one macroblock.  nnz: bit (bx + 4 * by) per 4 x 4 luma block; flags: BS_MB_INTRA, BS_MB_T8X8.
+BS_MB_DTYPE = np.dtype([("slice", np.uint16), ("nnz", np.uint16), ("qp", np.uint8), ("flags", np.uint8), ("pad", np.uint8, 2)])
+#: FFHipH264BsSlice: ref[list][ref_idx] -> picture identity; the offsets are the slice header's _div2 values times 2; flags: BS_SLICE_B.
+BS_SLICE_DTYPE = np.dtype([("ref", np.uint8, (2, 32)), ("num_ref", np.uint8, 2), ("alpha_c0_offset", np.int8), ("beta_offset", np.int8),
+                           ("idc", np.uint8), ("flags", np.uint8), ("pad", np.uint8, 2)])
+assert BS_MVF_DTYPE.itemsize == 12 and BS_MB_DTYPE.itemsize == 8 and BS_SLICE_DTYPE.itemsize == 72
+BS_MB_INTRA, BS_MB_T8X8 = 1, 2
+BS_SLICE_B = 1
+LF_V_LUMA, LF_H_LUMA, LF_V_CHROMA, LF_H_CHROMA, LF_V_LUMA_INTRA, LF_H_LUMA_INTRA, LF_V_CHROMA_INTRA, LF_H_CHROMA_INTRA = range(8)
+
+
+class BsPic(C.Structure):
+    """FFHipH264BsPic"""
+    _fields_ = [("mb", C.c_void_p), ("mvf", C.c_void_p), ("slices", C.c_void_p), ("chroma_qp", C.c_void_p), ("luma", C.c_void_p),
+                ("cb", C.c_void_p), ("cr", C.c_void_p), ("mvf_stride", C.c_int32), ("nslices", C.c_int32)]
+
+
+def _bs_pics(pics, ptr):
+    arr = (BsPic * max(len(pics), 1))()
+    opt = lambda m, k: ptr(m[k]) if m.get(k) is not None else None
+    for i, m in enumerate(pics):
+        arr[i].mb, arr[i].mvf, arr[i].slices, arr[i].luma = ptr(m["mb"]), ptr(m["mvf"]), ptr(m["slices"]), ptr(m["luma"])
+        arr[i].chroma_qp, arr[i].cb, arr[i].cr = opt(m, "chroma_qp"), opt(m, "cb"), opt(m, "cr")
+        arr[i].mvf_stride, arr[i].nslices = m["mvf_stride"], m["nslices"]
+    return arr
+
+
+def edge_params_pictures(pics, mb_w, mb_h, field=0, qp_bd_offset=0, stream=None):
+    """ffhip_h264_edge_params_pictures_dev on npics = len(pics) pictures of mb_w x mb_h macroblocks.  pics[i]: a dict with the device
+    tensors mb (BS_MB_DTYPE records as bytes), mvf (BS_MVF_DTYPE), slices (BS_SLICE_DTYPE), optionally chroma_qp (uint8 [2, 88]), the
+    outputs luma (EDGE_DTYPE records as bytes, mb_w * mb_h * 8 of them) and optionally cb, cr (mb_w * mb_h * 4 each), and the ints
+    mvf_stride (records), nslices.  luma / cb / cr are what deblock_frames(), deblock_frames_chroma() and deblock_frames_hbd() take.
+    Asynchronous on `stream`."""
+    arr = _bs_pics(pics, lambda t: t.data_ptr())
+    return _lib.check(_lib.lib().ffhip_h264_edge_params_pictures_dev(mb_w, mb_h, field, qp_bd_offset, len(pics), C.cast(arr, C.c_void_p),
+                                                                     _stream(stream)), "ffhip_h264_edge_params_pictures_dev")
+
+
+def edge_params_pictures_host(pics, mb_w, mb_h, field=0, qp_bd_offset=0):
+    """ffhip_h264_edge_params_pictures_host (device-free): as edge_params_pictures() with numpy arrays; luma / cb / cr are written in
+    place."""
+    arr = _bs_pics(pics, lambda a: a.ctypes.data)
+    return _lib.check(_lib.lib().ffhip_h264_edge_params_pictures_host(mb_w, mb_h, field, qp_bd_offset, len(pics), C.cast(arr, C.c_void_p)),
+                      "ffhip_h264_edge_params_pictures_host")
+
+
 class Picture:
     """ctypes mirror of FFHipH264Picture: record a picture's per-block dsp calls on the host, flush them as a handful of
     launches (include/ffhip.h).  Records are numpy structured scalars / arrays of the batch faces' dtypes."""

@@ -585,6 +585,89 @@ int ffhip_h264_deblock_frames_dev_hbd(int bit_depth, int chroma, uint8_t *plane,
                                       int mb_h, const FFHipH264Edge *edges, void *stream);
 
 /**
+ * The edge tables of the three frame-order faces above, made from what the decoder has parsed: per macroblock its slice, non-zero
+ * bits, qp and flags, the per-4x4 motion field, and per slice the reference lists and filter offsets.  What ff_h264_filter_mb() derives
+ * on the host, macroblock by macroblock, as one gather over the picture.  Non-MBAFF pictures: frames (field 0) and field pictures
+ * (field 1: the field is the picture); 4:2:0 chroma, monochrome with NULL chroma_qp / cb / cr.
+ * Restated from H.264 8.7.2.1 / 8.7.2.2 and the behaviour of libavcodec/h264_loopfilter.c; NOT checked against the reference's
+ * source, which the build does not have.
+ *
+ * For macroblock q = (mb_x, mb_y): dir 0 is the vertical edges at x = 4e, dir 1 the horizontal edges at y = 4e, e = 0..3.  On e = 0
+ * p is the macroblock to the left / above, otherwise p = q.  S = slices[q.slice].
+ *  1. An edge is skipped when: e = 0 at the picture border; S.idc == 1; e = 0, S.idc == 2 and p.slice != q.slice; e odd and q has
+ *     the 8x8 transform; q.slice >= nslices.  A skipped edge's record is zero but for `kind` (the non-intra kind of its plane and
+ *     direction) and tc0 ({-1,-1,-1,-1} luma, {0,0,0,0} chroma).
+ *  2. bS of the 4-line group g (the 4x4 blocks on either side of the edge): p or q intra: 4 when e = 0 and (field == 0 or
+ *     dir == 0), otherwise 3; else the nnz bit of the p-side or the q-side block: 2; else motion decides, 1 or 0:
+ *     - a block's reference of a list is slices[slice of its own macroblock].ref[list][ref_idx]; ref_idx < 0 is "unused": all
+ *       unused references are equal, and the list's motion vector counts as (0, 0) whatever the record holds; a ref_idx >= that
+ *       slice's num_ref or >= 32, or a macroblock whose slice is >= nslices, gives a reference that differs from every other,
+ *       another such one and the unused ones included, and (0, 0) as well;
+ *     - lists: 2 if S is a B slice, else list 0 alone; two vectors differ when |dx| >= 4 or |dy| >= (field ? 2 : 4);
+ *     - straight: ref0 differ or mv0 differ; if not, and with two lists, ref1 differ or mv1 differ;
+ *     - if straight says different and there are two lists, crossed: 1 if p.ref0 != q.ref1 or p.ref1 != q.ref0, else 1 iff
+ *       (p.mv0, q.mv1) differ or (p.mv1, q.mv0) differ.
+ *  3. Every group 0: the skipped record.  Otherwise qp = (p.qp + q.qp + 1) >> 1 on e = 0, else q.qp; indexA = clip(qp -
+ *     qp_bd_offset + S.alpha_c0_offset, 0, 51), indexB with beta_offset; alpha, beta from Tables 8-16; bS 4: the *_INTRA kind,
+ *     tc0 {0,0,0,0} (unused); else the normal kind, tc0[g] = tc0'[indexA][bS_g] (Table 8-17), -1 at bS 0.  alpha or beta 0 stay: the
+ *     filter disables itself.
+ *  4. Chroma plane c (Cb 0, Cr 1), edge e' = 0, 1 is luma edge 2e' with its skip rule and its four bS (an 8x8-transform
+ *     macroblock keeps its chroma edge 1); qp from chroma_qp[c][p.qp] and chroma_qp[c][q.qp] the same way (a qp above 87 reads
+ *     entry 87); tc0[g] = tc0'[indexA][bS_g] + 1, 0 at bS 0; the *_CHROMA / *_CHROMA_INTRA kinds.
+ *  5. offset and pad are 0.  Every record of every table is written exactly once, nothing else is, and no input is written; malformed
+ *     input has the result defined above and never causes an access outside the maps.
+ * The records are in the 8-bit units the deblock faces scale by depth.
+ * Out of scope: MBAFF, 4:2:2 / 4:4:4 chroma tables.
+ */
+typedef struct FFHipH264MvField {  /* one 4x4 luma block, 12 bytes, grid w4 = 4*mb_w by h4 = 4*mb_h */
+    int16_t mv[2][2];              /* [list][x, y], quarter samples */
+    int8_t  ref_idx[2];            /* < 0: list unused */
+    uint8_t pad[2];
+} FFHipH264MvField;
+typedef struct FFHipH264BsMb {     /* one macroblock, 8 bytes */
+    uint16_t slice;                /* index into slices */
+    uint16_t nnz;                  /* bit (bx + 4*by): that 4x4 luma block has non-zero coefficients.  For a macroblock with the
+                                      8x8 transform the decoder sets all four bits of an 8x8 block or none: the reference's CAVLC
+                                      fix-up, the caller's job. */
+    uint8_t  qp;                   /* QP'Y as the decoder stores it (0 for I_PCM; above 8 bits with the depth offset) */
+    uint8_t  flags;                /* bit 0 intra (I_PCM included), bit 1 transform_size_8x8_flag */
+    uint8_t  pad[2];
+} FFHipH264BsMb;
+typedef struct FFHipH264BsSlice {  /* 72 bytes */
+    uint8_t ref[2][32];            /* [list][ref_idx] -> picture identity: equal bytes name the same reference picture.  In a field
+                                      picture the two parities of a frame have different bytes. */
+    uint8_t num_ref[2];
+    int8_t  alpha_c0_offset, beta_offset;  /* slice_alpha_c0_offset_div2 * 2, slice_beta_offset_div2 * 2: -12 .. 12 */
+    uint8_t idc;                   /* disable_deblocking_filter_idc: 0, 1, 2 */
+    uint8_t flags;                 /* bit 0: B slice (both lists take part in the comparison) */
+    uint8_t pad[2];
+} FFHipH264BsSlice;
+typedef struct FFHipH264BsPic {    /* _dev: device pointers, _host: host pointers */
+    const FFHipH264BsMb    *mb;        /* mb_w * mb_h, raster */
+    const FFHipH264MvField *mvf;       /* [by * mvf_stride + bx], 4-byte aligned */
+    const FFHipH264BsSlice *slices;    /* nslices records */
+    const uint8_t *chroma_qp;          /* [2][88]: Cb then Cr, the pps's chroma_qp_table indexed by QP'Y; NULL: no chroma tables */
+    FFHipH264Edge *luma;               /* out: [(mb*2 + dir)*4 + e], the layout of ffhip_h264_deblock_frames_dev */
+    FFHipH264Edge *cb, *cr;            /* out: [(mb*2 + dir)*2 + e], the layout of ..._chroma_dev; both NULL or both set */
+    int32_t mvf_stride, nslices;       /* mvf_stride in records */
+} FFHipH264BsPic;
+/** npics pictures of mb_w x mb_h macroblocks (1..4096 each); field 0 / 1; qp_bd_offset 0, 6, 12, 24 or 36 (6 * (bit depth - 8)).
+ *  Pictures go 16 to a launch.  Asynchronous on `stream`; the tables are ready for the deblock faces on the same stream with no
+ *  synchronisation in between.
+ *  FFHIP_EINVAL for another size, qp_bd_offset or field, npics <= 0, NULL mb / mvf / slices / luma, only one of cb / cr, cb without
+ *  chroma_qp, an mvf or an output table that is not 4-byte aligned, mvf_stride < 4*mb_w, nslices < 1, or an output table whose span
+ *  overlaps the span of any input or of any other output table of the call; FFHIP_ENOSYS without a device (after the argument checks). */
+int ffhip_h264_edge_params_pictures_dev(int mb_w, int mb_h, int field, int qp_bd_offset, int npics,
+                                        const FFHipH264BsPic *pics /* host array */, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free): the same arguments, refusals but FFHIP_ENOSYS, and bytes.
+ *  The _dev face never calls it. */
+int ffhip_h264_edge_params_pictures_host(int mb_w, int mb_h, int field, int qp_bd_offset, int npics, const FFHipH264BsPic *pics);
+/** sizeof(FFHipH264BsMb), sizeof(FFHipH264MvField), sizeof(FFHipH264BsSlice), for bindings that mirror the records (no device needed). */
+int ffhip_h264_bs_mb_record_size(void);
+int ffhip_h264_bs_mvf_record_size(void);
+int ffhip_h264_bs_slice_record_size(void);
+
+/**
  * The batched faces above at ANY depth the reference instantiates (bit_depth 8 / 9 / 10 / 12 / 14), plus the members that exist
  * only here: MBAFF and 4:2:2.  Above 8 bits samples are uint16_t and coefficients int32_t (libavcodec/bit_depth_template.c);
  * strides and offsets stay in BYTES, coefficient pitches in coefficients.  Bit-exact restatement of the reference's templates

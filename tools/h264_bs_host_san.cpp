@@ -1,0 +1,121 @@
+/*
+ * tools/h264_bs_host_san.cpp — a stand-alone host program over ffhip_h264_edge_params_pictures_host() for AddressSanitizer and
+ * UBSan: random and malformed pictures (slice indices, ref_idx and qp out of range, num_ref 33) in heap blocks exactly as large as the
+ * geometry says, so a read or write outside a map is an error the sanitizer reports.  CPU only: nothing here touches a device.
+ *
+ * Build and run from the repository root (the face's file and this one, nothing else of the library):
+ *   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
+ *         --offload-arch=gfx950 -Iinclude -Iffmpeg_amd/csrc -Iffmpeg_amd/csrc/host ffmpeg_amd/csrc/shims_h264_bs.hip \
+ *         tools/h264_bs_host_san.cpp -o h264_bs_host_san && ./h264_bs_host_san
+ * Prints a checksum of the tables per case and "ok"; the sanitizer aborts on the first finding.
+ */
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "ffhip.h"
+
+/* what shims_h264_bs.hip takes from the rest of the library */
+extern "C" void ffhip_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    fputc('\n', stderr);
+}
+int ffhip_have_device(void) { return 0; }
+struct ihipStream_t;
+int ffhip_launch_h264_edge_params_pictures(int, int, int, int, int, const FFHipH264BsPic *, ihipStream_t *) { return FFHIP_ENOSYS; }
+
+static uint32_t rnd_state = 12345;
+static uint32_t rnd(void)
+{
+    rnd_state = rnd_state * 1664525u + 1013904223u;
+    return rnd_state >> 8;
+}
+
+template <class T>
+static T *block(size_t n)
+{
+    return static_cast<T *>(malloc(n * sizeof(T) ? n * sizeof(T) : 1));
+}
+
+static int run(int mb_w, int mb_h, int field, int bd_off, int nslices, int pad, bool chroma, bool malformed)
+{
+    const size_t nmb = (size_t)mb_w * mb_h;
+    const int w4 = 4 * mb_w, h4 = 4 * mb_h, stride = w4 + pad;
+    /* the last row of the motion field ends with the picture, not with the stride */
+    const size_t nmvf = (size_t)(h4 - 1) * stride + w4;
+    FFHipH264BsMb *mb = block<FFHipH264BsMb>(nmb);
+    FFHipH264MvField *mvf = block<FFHipH264MvField>(nmvf);
+    FFHipH264BsSlice *slices = block<FFHipH264BsSlice>(nslices);
+    uint8_t *cqp = block<uint8_t>(176);
+    FFHipH264Edge *luma = block<FFHipH264Edge>(nmb * 8), *cb = block<FFHipH264Edge>(nmb * 4), *cr = block<FFHipH264Edge>(nmb * 4);
+    for (size_t i = 0; i < nmb; i++) {
+        mb[i].slice = (uint16_t)(malformed && rnd() % 8 == 0 ? rnd() : (i * nslices) / nmb);
+        mb[i].nnz = (uint16_t)(rnd() & rnd() & rnd());
+        mb[i].qp = (uint8_t)(malformed ? rnd() : rnd() % 52 + bd_off);
+        mb[i].flags = (uint8_t)(rnd() % 5 == 0 ? 1 : 0) | (uint8_t)(rnd() % 3 == 0 ? 2 : 0);
+        mb[i].pad[0] = mb[i].pad[1] = 0;
+    }
+    for (size_t i = 0; i < nmvf; i++) {
+        for (int l = 0; l < 2; l++) {
+            mvf[i].mv[l][0] = (int16_t)(malformed ? rnd() : rnd() % 9 - 4);
+            mvf[i].mv[l][1] = (int16_t)(malformed ? rnd() : rnd() % 9 - 4);
+            mvf[i].ref_idx[l] = (int8_t)(malformed ? rnd() : (int)(rnd() % 4) - 1);
+        }
+        mvf[i].pad[0] = mvf[i].pad[1] = 0;
+    }
+    for (int s = 0; s < nslices; s++) {
+        for (int l = 0; l < 2; l++) {
+            for (int k = 0; k < 32; k++)
+                slices[s].ref[l][k] = (uint8_t)(rnd() % 3);
+            slices[s].num_ref[l] = (uint8_t)(malformed ? rnd() : 3);
+        }
+        slices[s].alpha_c0_offset = (int8_t)(malformed ? rnd() : 2 * ((int)(rnd() % 13) - 6));
+        slices[s].beta_offset = (int8_t)(malformed ? rnd() : 2 * ((int)(rnd() % 13) - 6));
+        slices[s].idc = (uint8_t)(malformed ? rnd() : rnd() % 3);
+        slices[s].flags = (uint8_t)(malformed ? rnd() : rnd() & 1);
+        slices[s].pad[0] = slices[s].pad[1] = 0;
+    }
+    if (malformed)
+        slices[0].num_ref[0] = 33;
+    for (int i = 0; i < 176; i++)
+        cqp[i] = (uint8_t)(malformed ? rnd() : i % 88);
+    FFHipH264BsPic pic;
+    memset(&pic, 0, sizeof(pic));
+    pic.mb = mb; pic.mvf = mvf; pic.slices = slices; pic.luma = luma;
+    if (chroma) {
+        pic.chroma_qp = cqp; pic.cb = cb; pic.cr = cr;
+    }
+    pic.mvf_stride = stride; pic.nslices = nslices;
+    const int r = ffhip_h264_edge_params_pictures_host(mb_w, mb_h, field, bd_off, 1, &pic);
+    uint32_t sum = 0;
+    const uint8_t *tabs[3] = { (const uint8_t *)luma, (const uint8_t *)cb, (const uint8_t *)cr };
+    for (int t = 0; t < (chroma ? 3 : 1); t++)
+        for (size_t i = 0; i < nmb * (t ? 4 : 8) * sizeof(FFHipH264Edge); i++)
+            sum = sum * 31 + tabs[t][i];
+    printf("%d x %d field %d bd_off %d slices %d pad %d chroma %d malformed %d: rc %d checksum %08x\n", mb_w, mb_h, field, bd_off, nslices, pad,
+           (int)chroma, (int)malformed, r, sum);
+    free(mb); free(mvf); free(slices); free(cqp); free(luma); free(cb); free(cr);
+    return r;
+}
+
+int main(void)
+{
+    int bad = 0;
+    const int bd[5] = { 0, 6, 12, 24, 36 };
+    for (int k = 0; k < 20; k++) {
+        const int mb_w = 1 + (int)(rnd() % 11), mb_h = 1 + (int)(rnd() % 9);
+        bad |= run(mb_w, mb_h, k & 1, bd[k % 5], 1 + (int)(rnd() % 4), (int)(rnd() % 4), (k & 2) != 0, k >= 6) != 0;
+    }
+    bad |= run(120, 68, 0, 0, 4, 0, true, false) != 0;
+    bad |= run(120, 68, 1, 12, 4, 3, true, true) != 0;
+    puts(bad ? "FAILED" : "ok");
+    return bad;
+}
