@@ -250,6 +250,9 @@ def lib():
         "ffhip_vp9_lf_sb_tables": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_vp9_lf_sb_ctables": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_vp9_loopfilter_frames_ssc_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_int, vp]),
+        "ffhip_vp9_lf_tables_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_vp9_lf_tables_pictures_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "ffhip_vp9_lf_block_record_size": (C.c_int, []),
         "ffhip_vp9_loopfilter_frame_ssc_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_int, vp, vp, vp]),
         "ffhip_vp9_loopfilter_frame_dev": (C.c_int, [C.c_int, vp, vp, vp, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_int, vp, vp]),
         "ffhip_vp9_loopfilter_frame_ss_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_int, vp, vp]),

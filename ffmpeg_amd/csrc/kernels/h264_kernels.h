@@ -115,6 +115,8 @@ int ffhip_launch_hevc_inter_pictures(int bd, int chroma_format_idc, int width, i
 int ffhip_launch_vp9_inter_frames(int bd, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPic *pics, hipStream_t stream);
 int ffhip_launch_vp9_inter_frames_scaled(int bd, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9InterPicScaled *pics,
                                          hipStream_t stream);
+/* VP9 loop-filter tables of whole frames (vp9_lf_tab_pic.hip), arguments validated by ffhip_vp9_lf_tables_pictures_dev() */
+int ffhip_launch_vp9_lf_tables_pictures(int ss_h, int ss_v, int cols, int rows, int npics, const FFHipVp9LfTabPic *pics, hipStream_t stream);
 /* VP9 intra reconstruction of whole frames (vp9_intra_frame.hip), arguments validated by ffhip_vp9_intra_frames_dev() */
 int ffhip_launch_vp9_intra_frames(int bd, int ss_h, int ss_v, int width, int height, int npics, const FFHipVp9IntraPic *pics, hipStream_t stream);
 /* HEVC in-loop filtering of whole pictures (hevc_lf_pic.hip), arguments validated by ffhip_hevc_loop_filter_pictures_dev() */

@@ -128,6 +128,47 @@ def loopfilter_frames_ssc(pics, stride_y, stride_uv, cols, rows, ss, stream=None
                                                                      cols, rows, _st(stream)), "ffhip_vp9_loopfilter_frames_ssc_dev")
 
 
+#: FFHipVp9LfBlock (include/ffhip.h): one decoded block.  pos = (row & 7) << 3 | (col & 7), bs = enum BlockSize (0 = 64x64 .. 12 = 4x4),
+#: tx_skip = b->tx | skip_inter << 2, lvl_idx = seg_id << 3 | (intra ? 0 : ref[0] + 1) << 1 | (mode[3] != ZEROMV)
+LF_BLOCK_DTYPE = np.dtype([("pos", np.uint8), ("bs", np.uint8), ("tx_skip", np.uint8), ("lvl_idx", np.uint8)])
+assert LF_BLOCK_DTYPE.itemsize == 4
+
+
+class LfTabPic(C.Structure):   # FFHipVp9LfTabPic (include/ffhip.h)
+    _fields_ = [("blocks", C.c_void_p), ("sb_first", C.c_void_p), ("nblocks", C.c_uint32), ("level", C.c_uint8 * 64),
+                ("lim_lut", C.c_uint8 * 64), ("mblim_lut", C.c_uint8 * 64), ("tables", C.c_void_p), ("ctables", C.c_void_p),
+                ("filters", C.c_void_p)]
+
+
+def _lf_tab_pics(pics, ptr):
+    arr = (LfTabPic * max(len(pics), 1))()
+    opt = lambda m, k: ptr(m[k]) if m.get(k) is not None else None
+    for i, m in enumerate(pics):
+        arr[i].blocks, arr[i].sb_first, arr[i].nblocks = opt(m, "blocks"), opt(m, "sb_first"), m["nblocks"]
+        for k in ("level", "lim_lut", "mblim_lut"):
+            getattr(arr[i], k)[:] = np.ascontiguousarray(m[k], np.uint8).reshape(64).tolist()
+        arr[i].tables, arr[i].ctables, arr[i].filters = opt(m, "tables"), opt(m, "ctables"), opt(m, "filters")
+    return arr
+
+
+def lf_tables_pictures(pics, cols, rows, ss=(1, 1), stream=None):
+    """ffhip_vp9_lf_tables_pictures_dev on npics = len(pics) pictures of cols x rows 8x8 blocks.  pics[i]: a dict with the device tensors
+    blocks (LF_BLOCK_DTYPE records as bytes, a superblock's contiguous), sb_first (int32 / uint32 [sb_rows * sb_cols + 1]), the int
+    nblocks, the uint8 [64] arrays level, lim_lut, mblim_lut, and the outputs tables (uint32 [n, 320]), ctables (uint32 [n, 128], when
+    ss[0] != ss[1], else None) and optionally filters (uint8 [n, 192]).  tables / ctables are what loopfilter_frames() and
+    loopfilter_frames_ssc() take.  Asynchronous on `stream`."""
+    arr = _lf_tab_pics(pics, lambda t: t.data_ptr())
+    return _lib.check(_lib.lib().ffhip_vp9_lf_tables_pictures_dev(ss[0], ss[1], cols, rows, len(pics), C.cast(arr, C.c_void_p), _st(stream)),
+                      "ffhip_vp9_lf_tables_pictures_dev")
+
+
+def lf_tables_pictures_host(pics, cols, rows, ss=(1, 1)):
+    """ffhip_vp9_lf_tables_pictures_host (device-free): as lf_tables_pictures() with numpy arrays; the outputs are written in place."""
+    arr = _lf_tab_pics(pics, lambda a: a.ctypes.data)
+    return _lib.check(_lib.lib().ffhip_vp9_lf_tables_pictures_host(ss[0], ss[1], cols, rows, len(pics), C.cast(arr, C.c_void_p)),
+                      "ffhip_vp9_lf_tables_pictures_host")
+
+
 _LF = C.CFUNCTYPE(None, C.c_void_p, C.c_ssize_t, C.c_int, C.c_int, C.c_int)
 
 

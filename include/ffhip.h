@@ -2149,6 +2149,66 @@ int ffhip_vp9_loopfilter_frames_ssc_dev(int bit_depth, int ss_h, int ss_v, int n
                                         ptrdiff_t stride_uv, int cols, int rows, void *stream);
 
 /**
+ * The VP9 loop-filter tables of whole frames on the device: what the tail of ff_vp9_decode_block and mask_edges
+ * (libavcodec/vp9block.c:1141-1262, 1433-1447) and then ffhip_vp9_lf_sb_tables() / ffhip_vp9_lf_sb_ctables() do on the host per
+ * superblock, for every superblock of up to 16 pictures in one launch, from one 4-byte record per decoded block.  The tables never
+ * exist on the host: ffhip_vp9_loopfilter_frames_dev() / _ssc_dev() read them on the same stream.  Restated from the behaviour of
+ * the reference, not checked against its source.
+ *
+ *  Per superblock (sb_row, sb_col), from its records blocks[sb_first[i] .. sb_first[i + 1]) in order:
+ *  1. an all-zero VP9Filter.  (The reference clears only `mask` between superblock rows and leaves stale levels, which it reads only
+ *     where a block has just written them; here every cell that no record with a level above 0 covers is 0.)
+ *  2. lvl = level[lvl_idx]; a record whose lvl is 0 does nothing.  Otherwise, with row7 / col7 = pos >> 3 / pos & 7, row / col = 8 sb_row +
+ *     row7 / 8 sb_col + col7, w8 x h8 the block's size in 8x8 cells (sub-8x8 sizes count as 1):
+ *  3. lvl goes to the block's w8 x h8 cells of level[], clipped by the 8x8 table only;
+ *  4. mask_edges(mask[0], 0, 0, row7, col7, x_end, y_end, 0, 0, tx, skip_inter), x_end = min(cols - col, w8), y_end = min(rows - row, h8);
+ *  5. if ss_h | ss_v: mask_edges(mask[1], ss_h, ss_v, row7, col7, x_end, y_end, col_end, row_end, uvtx, skip_inter) with
+ *     uvtx = tx - ((ss_h && w8 * 2 == 1 << tx) || (ss_v && h8 * 2 == 1 << tx)), col_end = (cols & 1 && col + w8 >= cols) ? cols & 7 : 0,
+ *     row_end = (rows & 1 && row + h8 >= rows) ? rows & 7 : 0;
+ *  6. tables[i] is what ffhip_vp9_lf_sb_tables(out, &filter, 8 sb_row, 8 sb_col, ss_h, ss_v, lim_lut, mblim_lut) writes (the zero `uv`
+ *     part outside 4:2:0 included), ctables[i] what ffhip_vp9_lf_sb_ctables() writes, filters[i] the VP9Filter itself.
+ *  Every word of every output is written, zeros included: a superblock without records gets all-zero tables.
+ *
+ *  Malformed records cannot be refused (they are in device memory): a record is skipped as if its level were 0 when bs > 12, a bit above
+ *  bit 2 of tx_skip is set, tx is larger than the largest transform that fits the block (tx > 0 below 8x8), pos is not aligned to the
+ *  block's own size (or has a bit above bit 5), the first cell lies outside the picture, or lvl_idx > 63.  sb_first entries are clamped to
+ *  nblocks, a decreasing pair is an empty superblock, a superblock may have any number of records.  Where records of one superblock
+ *  overlap (no stream does that) the masks are the union and a cell's level is that of any one of the records that cover it (the host
+ *  face: of the last one).  Nothing outside the arrays of the call is read or written, whatever the records hold.  A 16-wide chroma entry
+ *  on a tile's last 4-sample position, which the frame kernels cannot take and no record set produces (docs/KERNELS.md), is cleared.
+ *
+ *  FFHIP_EINVAL: cols or rows outside 1..10912 (8 x 1364 superblock rows, the filter faces' limit), ss_h / ss_v outside 0 / 1, npics
+ *  outside 1..16, a NULL sb_first or tables, NULL blocks with nblocks > 0, blocks / sb_first / an output that is not 4-byte aligned, a
+ *  level[] above 63, ctables present when ss_h == ss_v or absent when they differ, an output that overlaps another output or an input
+ *  of the call.
+ */
+typedef struct FFHipVp9LfBlock {   /* one ff_vp9_decode_block call, 4 bytes */
+    uint8_t pos;      /* (row & 7) << 3 | (col & 7): the block's first 8x8 cell inside its superblock */
+    uint8_t bs;       /* enum BlockSize, 0 = 64x64 ... 12 = 4x4, as ffhip_vp9_inter_block_preds takes it */
+    uint8_t tx_skip;  /* bits 0..1 b->tx, bit 2 skip_inter = !b->intra && b->skip */
+    uint8_t lvl_idx;  /* seg_id << 3 | (b->intra ? 0 : b->ref[0] + 1) << 1 | (b->mode[3] != ZEROMV) */
+} FFHipVp9LfBlock;
+
+typedef struct FFHipVp9LfTabPic {
+    const FFHipVp9LfBlock *blocks;   /* device; a superblock's records are contiguous */
+    const uint32_t *sb_first;        /* device; sb_rows * sb_cols + 1 entries, raster order: records [sb_first[i], sb_first[i+1]) */
+    uint32_t nblocks;
+    uint8_t level[64];               /* segmentation.feat[seg].lflvl[ref][mode], indexed by lvl_idx; all 0 when filter.level is 0 */
+    uint8_t lim_lut[64], mblim_lut[64];
+    FFHipVp9LfSb *tables;            /* device out, sb_rows * sb_cols */
+    FFHipVp9LfSbC *ctables;          /* device out; required when ss_h != ss_v, NULL otherwise */
+    FFHipVp9Filter *filters;         /* device out, optional (NULL: not written) */
+} FFHipVp9LfTabPic;
+
+/** cols x rows in 8x8 blocks, as for ffhip_vp9_loopfilter_frames_dev(); `pics` is a host array.  Asynchronous on `stream`.
+ *  FFHIP_ENOSYS without a device, after the checks. */
+int ffhip_vp9_lf_tables_pictures_dev(int ss_h, int ss_v, int cols, int rows, int npics, const FFHipVp9LfTabPic *pics, void *stream);
+/** The same rules on host arrays (device-free): every pointer of `pics` is a host pointer. */
+int ffhip_vp9_lf_tables_pictures_host(int ss_h, int ss_v, int cols, int rows, int npics, const FFHipVp9LfTabPic *pics);
+/** sizeof(FFHipVp9LfBlock), for bindings that mirror the record (no device needed). */
+int ffhip_vp9_lf_block_record_size(void);
+
+/**
  * VP9 inter reconstruction of whole frames in one launch: inter_pred() and the residual half of inter_recon() (libavcodec/vp9recon.c,
  * vp9_mc_template.h) for every inter block of up to 16 frames, from references resident in device memory.  A decoder records a
  * frame's prediction calls and transform blocks instead of running them; one launch then writes the frame, and
