@@ -6,6 +6,7 @@ import pytest
 
 import ffi
 from ffi import ptr, u8p
+from mc_matrix import weights as _weights
 
 pytestmark = pytest.mark.gpu
 
@@ -478,14 +479,6 @@ def test_hevc_mc_host_faces():
         (c.put_hevc_epel_uni if chroma else c.put_hevc_qpel_uni)[idx][int(bool(my))][int(bool(mx))](a8.ctypes.data, 72, sp, 100, h, mx, my, w)
         O.ffo_hevc_mc(chroma, 1, b8.ctypes.data, 72, C.cast(sp, u8p), 100, h, mx, my, w)
         assert np.array_equal(a8, b8), (chroma, w, h, mx, my, "uni")
-
-
-def _weights(rng, rep):
-    """(denom, wx0, wx1, ox): slice-header ranges mixed with tests/checkasm/hevc_pel.c's ladders"""
-    if rep % 3 == 0:
-        return int(rng.choice([0, 7, 12])), int(rng.choice([0, 128, 255])), int(rng.choice([0, 128, 255])), int(rng.choice([0, 255]))
-    d = int(rng.integers(0, 8))
-    return d, (1 << d) + int(rng.integers(-128, 128)), (1 << d) + int(rng.integers(-128, 128)), int(rng.integers(-256, 255))
 
 
 @pytest.mark.parametrize("old", ["default", "0", "1"])
