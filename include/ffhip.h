@@ -1450,7 +1450,9 @@ int ff_hevc_dsp_init_hip(FFHipHEVCDSPContext *c, int bit_depth);
 /** One transform unit of the batch face: what hls_residual_coding / hls_transform_unit pass per TU
  *  (libavcodec/hevc/cabac.c, hevcdec.c). */
 typedef struct FFHipHevcTU {
-    int32_t coeff_offset; /* in int16 units into coeffs: the TU's size*size block, row-major      */
+    int32_t coeff_offset; /* in int16 units into coeffs: the TU's size*size block, row-major.  coeffs + coeff_offset must be
+                           * 4-byte aligned (coeff_offset even on an aligned array): the kernels move a block in 16-byte pieces
+                           * where it is 16-byte aligned and as dwords otherwise, unit by unit; an odd address is undefined */
     int32_t dst_offset;   /* in bytes into dst; < 0: leave the picture alone                      */
     int32_t col_limit;    /* FFHIP_HEVC_IDCT only                                                 */
 } FFHipHevcTU;
@@ -1522,7 +1524,8 @@ typedef struct FFHipHevcSao {
     int16_t offset_val[5];           /* sao_offset_val: [0] unused by the band filter */
     uint8_t edge;                    /* 0: sao_band_filter, 1: sao_edge_filter */
     uint8_t cls;                     /* band: sao_left_class (0..31); edge: eo = SAO_EO_* (0 horizontal, 1 vertical, 2 135 deg, 3 45 deg) */
-    uint8_t width, height;           /* 1..64 */
+    uint8_t width, height;           /* 1..64; larger values give undefined sample values (rows are split by a reciprocal table
+                                      * that ends at 64 samples), 0 does nothing */
     uint8_t pad[2];                  /* sizeof == 24 */
 } FFHipHevcSao;
 /** n SAO blocks: dst[..] = clip(src[..] + offset(class)); src and dst are different buffers (the decoder filters from a

@@ -48,7 +48,26 @@ def test_hevc_idct_other_kernel(lg, env, with_dst, monkeypatch):
     _run_idct(lg, 0, with_dst)
 
 
-def _run_idct(lg, kind, with_dst):
+@pytest.mark.parametrize("with_dst", [True, False])
+@pytest.mark.parametrize("lg,env", [(2, None), (3, None), (4, None), (5, None), (4, "FFHIP_HEVC_IDCT16_MFMA"), (5, "FFHIP_HEVC_IDCT32_VALU")])
+def test_hevc_idct_coeff_alignment(lg, env, with_dst, monkeypatch):
+    """coefficient blocks on every allowed alignment (coeff_offset even: 4 bytes), mixed inside a wave: the kernels stage a block
+    in 16-byte pieces where it is 16-byte aligned and as dwords where it is not, unit by unit"""
+    if env:
+        monkeypatch.setenv(env, "1")
+    _run_idct(lg, 0, with_dst, spread=True)
+
+
+def idct_coeff_offsets(ntu, n, spread):
+    """int16 offsets of the units' blocks and the array's length: packed, or 8 entries apart with coeff_offset % 8 walking 0, 2, 4, 6
+    so that neighbours (a wave holds 16 / 8 / 4 / 2 units) differ"""
+    if not spread:
+        return np.arange(ntu) * n * n, ntu * n * n
+    t = np.arange(ntu)
+    return t * (n * n + 8) + 2 * ((t + t // 4) % 4), ntu * (n * n + 8) + 8
+
+
+def _run_idct(lg, kind, with_dst, spread=False):
     from ffmpeg_amd import hevc
     torch = _torch()
     if kind == hevc.DST_4X4 and lg != 2:
@@ -60,10 +79,15 @@ def _run_idct(lg, kind, with_dst):
     W, H = 256 + 24, 128
     bw, bh = 256 // n, H // n
     ntu = bw * bh - 3
-    coeffs = np.stack([_coeffs(rng, n, t % 4) for t in range(ntu)])
+    blocks = np.stack([_coeffs(rng, n, t % 4) for t in range(ntu)])
     tus = np.zeros(ntu, hevc.TU_DTYPE)
     order = rng.permutation(bw * bh)[:ntu]
-    tus["coeff_offset"] = np.arange(ntu) * n * n
+    offs, total = idct_coeff_offsets(ntu, n, spread)
+    assert not spread or ({int(o) % 8 for o in offs} == {0, 2, 4, 6} and all(offs[t] % 8 != offs[t + 1] % 8 for t in range(ntu - 1)))
+    coeffs = rng.integers(-32768, 32768, total).astype(np.int16)     # the gaps between spread blocks must come back untouched
+    at = offs[:, None] + np.arange(n * n)[None, :]
+    coeffs[at] = blocks.reshape(ntu, n * n)
+    tus["coeff_offset"] = offs
     tus["dst_offset"] = (order // bw) * n * W + (order % bw) * n + 5          # unaligned picture columns
     tus["dst_offset"][::7] = -1
     tus["col_limit"] = rng.integers(0, 2 * n + 6, ntu)
@@ -72,14 +96,14 @@ def _run_idct(lg, kind, with_dst):
     want_c, want_p = coeffs.copy(), pic.copy()
     O = ffi.oracle()
     for t in range(ntu):
-        c = np.ascontiguousarray(want_c[t])
+        c = np.ascontiguousarray(want_c[at[t]].reshape(n, n))
         if kind == hevc.IDCT:
             O.ffo_hevc_idct(lg, ptr(c, ffi.i16p), int(tus["col_limit"][t]))
         elif kind == hevc.IDCT_DC:
             O.ffo_hevc_idct_dc(lg, ptr(c, ffi.i16p))
         elif kind == hevc.DST_4X4:
             O.ffo_hevc_transform_4x4_luma(ptr(c, ffi.i16p))
-        want_c[t] = c
+        want_c[at[t]] = c.reshape(-1)
         if with_dst and tus["dst_offset"][t] >= 0:
             O.ffo_hevc_add_residual(lg, C.cast(want_p.ctypes.data + int(tus["dst_offset"][t]), u8p), ptr(c, ffi.i16p), W)
     d_c = torch.from_numpy(coeffs.copy()).cuda()

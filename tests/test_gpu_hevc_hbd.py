@@ -8,7 +8,7 @@ import pytest
 
 import ffi
 from ffi import ptr, u8p, i16p, i32p
-from test_gpu_hevc import _coeffs
+from test_gpu_hevc import _coeffs, idct_coeff_offsets
 
 pytestmark = pytest.mark.gpu
 DEPTHS = [10, 12]
@@ -46,18 +46,37 @@ def at(a, byte_off):
 @pytest.mark.parametrize("lg", [2, 3, 4, 5])
 def test_hevc_idct_batch_hbd(lg, kind, bd):
     from ffmpeg_amd import hevc
-    torch = _torch()
     if kind == hevc.DST_4X4 and lg != 2:
         pytest.skip("transform_4x4_luma is 4x4 only")
+    _run_idct_hbd(lg, kind, bd)
+
+
+@pytest.mark.parametrize("bd", DEPTHS)
+@pytest.mark.parametrize("lg,env", [(2, None), (3, None), (4, None), (5, None), (4, "FFHIP_HEVC_IDCT16_MFMA"), (5, "FFHIP_HEVC_IDCT32_VALU")])
+def test_hevc_idct_coeff_alignment_hbd(lg, env, bd, monkeypatch):
+    """coefficient blocks on every allowed alignment (coeff_offset even), mixed inside a wave, on 16-bit pictures"""
+    if env:
+        monkeypatch.setenv(env, "1")
+    _run_idct_hbd(lg, 0, bd, spread=True)
+
+
+def _run_idct_hbd(lg, kind, bd, spread=False):
+    from ffmpeg_amd import hevc
+    torch = _torch()
     n = 1 << lg
     rng = np.random.default_rng(lg * 10 + kind + bd)
     W, H = 256 + 24, 128                                   # samples
     bw, bh = 256 // n, H // n
     ntu = bw * bh - 3
-    coeffs = np.stack([_coeffs(rng, n, t % 4) for t in range(ntu)])
+    blocks = np.stack([_coeffs(rng, n, t % 4) for t in range(ntu)])
     tus = np.zeros(ntu, hevc.TU_DTYPE)
     order = rng.permutation(bw * bh)[:ntu]
-    tus["coeff_offset"] = np.arange(ntu) * n * n
+    offs, total = idct_coeff_offsets(ntu, n, spread)
+    assert not spread or {int(o) % 8 for o in offs} == {0, 2, 4, 6}
+    coeffs = rng.integers(-32768, 32768, total).astype(np.int16)     # the gaps between spread blocks must come back untouched
+    where = offs[:, None] + np.arange(n * n)[None, :]
+    coeffs[where] = blocks.reshape(ntu, n * n)
+    tus["coeff_offset"] = offs
     tus["dst_offset"] = 2 * ((order // bw) * n * W + (order % bw) * n + 5)     # bytes; odd sample columns: dword-unaligned rows
     tus["dst_offset"][::7] = -1
     tus["col_limit"] = rng.integers(0, 2 * n + 6, ntu)
@@ -67,7 +86,7 @@ def test_hevc_idct_batch_hbd(lg, kind, bd):
     O = ffi.oracle()
     with_dst = kind != hevc.DEQUANT
     for t in range(ntu):
-        c = np.ascontiguousarray(want_c[t])
+        c = np.ascontiguousarray(want_c[where[t]].reshape(n, n))
         if kind == hevc.IDCT:
             O.ffo_hevc_idct_bd(bd, lg, ptr(c, i16p), int(tus["col_limit"][t]))
         elif kind == hevc.IDCT_DC:
@@ -76,7 +95,7 @@ def test_hevc_idct_batch_hbd(lg, kind, bd):
             O.ffo_hevc_transform_4x4_luma_bd(bd, ptr(c, i16p))
         elif kind == hevc.DEQUANT:
             O.ffo_hevc_dequant_bd(bd, ptr(c, i16p), lg)
-        want_c[t] = c
+        want_c[where[t]] = c.reshape(-1)
         if with_dst and tus["dst_offset"][t] >= 0:
             O.ffo_hevc_add_residual_bd(bd, lg, at(want_p, tus["dst_offset"][t]), ptr(c, i16p), 2 * W)
     d_c = torch.from_numpy(coeffs.copy()).cuda()
