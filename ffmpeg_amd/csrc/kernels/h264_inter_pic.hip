@@ -1,0 +1,202 @@
+/*
+ * h264_inter_pic.hip — H.264 inter prediction of whole pictures in one launch (ffhip_h264_inter_pictures_dev): the predicted
+ * samples of every inter macroblock from the macroblock records, the 4x4 motion field and the slice table the edge-parameter face
+ * (h264_bs_pic.hip) takes, both lists and the weighting combined in registers, every sample written once.
+ *
+ * One workgroup of 4 waves per (picture, macroblock); an intra macroblock's workgroup exits at once.  Wave q takes the 8x8 quadrant q
+ * as four 4x4 blocks of 16 lanes, a lane per luma sample.  Nothing is shared between waves, so there is no workgroup barrier:
+ *   1. every lane resolves its block's plan (h264_inter_rules.h): the 16 lanes of a block read the same words, which broadcast;
+ *   2. per list: the 16 lanes of a block fetch the clamped 9x9 reference window of the block (only the rows / columns the position's
+ *      filter reads) into wave-private LDS, then each lane filters its sample from LDS; lanes 0..7 of the block compute the 2x2 Cb and
+ *      Cr samples straight from the (cached) reference, 4 reads each.  List 0's samples stay in registers while list 1 is computed;
+ *   3. average / weight / biweight in registers;
+ *   4. the samples go through a wave-private LDS tile and leave as whole rows of a block: one 4-sample store per luma row and one
+ *      2-sample store per chroma row.  Nothing goes to HBM between the lists.
+ * The interpolation is the per-sample statement of h264_hbd.hip's kernels (h264qpel_template.c, h264chroma_template.c) with the depth
+ * as an argument; the source coordinates are clamped as FFHIP_MC_EMU records are.
+ */
+#include <stddef.h>
+
+#include "common.h"
+#include "h264_kernels.h"
+#include "h264_inter_rules.h"
+
+static_assert(sizeof(FFHipH264MvField) == 12 && sizeof(FFHipH264BsMb) == 8, "the records of the edge-parameter face");
+static_assert(sizeof(FFHipH264InterSlice) == 2888, "FFHipH264InterSlice is a 2888-byte record");
+static_assert(sizeof(FFHipH264InterRef) == 56, "FFHipH264InterRef is a 56-byte record");
+static_assert(sizeof(FFHipH264InterPic) == 1880, "FFHipH264InterPic is staged as an array");
+static_assert(sizeof(FFHipH264InterBlockPlan) == 28, "FFHipH264InterBlockPlan is a 28-byte record");
+
+#define H4I_PICS 16 /* pictures per launch: their FFHipH264InterPic structs travel in one progress-pool slot */
+static_assert(H4I_PICS * sizeof(FFHipH264InterPic) <= FFHIP_PROGRESS_SLOT_INTS * sizeof(int), "a launch's pictures fit one slot");
+
+namespace {
+constexpr int WIN = 9;              /* a 4x4 block's window: 2 samples before, 3 after */
+constexpr int WIN_PITCH = 84;       /* uint16_t entries per block window (81 used) */
+constexpr int WAVE_LDS = 4 * WIN_PITCH + 64 + 32; /* four windows, the luma tile, the chroma tile */
+
+__device__ __forceinline__ int tap6(int a, int b, int c, int d, int e, int f) { return (c + d) * 20 - (b + e) * 5 + (a + f); }
+
+template <typename P>
+__global__ __launch_bounds__(256) void k_h264_inter_pic(const FFHipH264InterPic *pics, int mb_w, int mb_h, int bd, int chroma)
+{
+    __shared__ uint16_t lds[4 * WAVE_LDS];
+    const FFHipH264InterPic &Pc = pics[blockIdx.z];
+    const int mx = blockIdx.x, my = blockIdx.y;
+    const FFHipH264BsMb m = Pc.mb[(ptrdiff_t)my * mb_w + mx];
+    if (m.flags & 1)
+        return;
+    const int t = threadIdx.x, q = t >> 6, lane = t & 63, k = lane >> 4, j = lane & 15, x4 = j & 3, y4 = j >> 2;
+    const int bx = mx * 4 + (q & 1) * 2 + (k & 1), by = my * 4 + (q >> 1) * 2 + (k >> 1);   /* the block, in 4x4 units of the picture */
+    const FFHipH264MvField f = Pc.mvf[(ptrdiff_t)by * Pc.mvf_stride + bx];
+    const FFHipH264InterBlockPlan plan = h264inter_plan(&m, &f, Pc.slices, Pc.nslices, Pc.nrefs);
+    const bool live = plan.mode != FFHIP_H264_INTER_SKIP, bi = plan.mode >= FFHIP_H264_INTER_BI_AVG;
+    const bool has_c = chroma && Pc.dst[1], clane = has_c && j < 8;
+    const int cpl = (j >> 2) & 1, cxs = j & 1, cys = (j >> 1) & 1;      /* a chroma lane's plane (0 Cb, 1 Cr) and sample of the 2x2 block */
+    uint16_t *win = lds + q * WAVE_LDS + k * WIN_PITCH, *ytile = lds + q * WAVE_LDS + 4 * WIN_PITCH, *ctile = ytile + 64;
+    const int pw = mb_w * 16, ph = mb_h * 16, maxv = (1 << bd) - 1;
+    int pl[2] = { 0, 0 }, pc[2] = { 0, 0 };
+
+#pragma unroll
+    for (int n = 0; n < 2; n++) {
+        const bool on = live && (n == 0 || bi);
+        const int L = bi ? n : plan.list;
+        const int mvx = L ? f.mv[1][0] : f.mv[0][0], mvy = L ? f.mv[1][1] : f.mv[0][1], fx = mvx & 3, fy = mvy & 3;
+        const FFHipH264InterRef &R = Pc.ref[on ? (n ? plan.slot[1] : plan.slot[0]) : 0];
+        if (on) {
+            /* the window's origin is 2 left of / above the block's source position */
+            const int ox = bx * 4 + (mvx >> 2) - 2, oy = by * 4 + (mvy >> 2) - 2;
+            const uint8_t *base = R.base[0];
+            const ptrdiff_t s = R.stride[0];
+            for (int i = j; i < WIN * WIN; i += 16) {
+                const int r = i / WIN, c = i - r * WIN;
+                if ((!fy && (r < 2 || r > 5)) || (!fx && (c < 2 || c > 5)))
+                    continue;
+                const int yy = min(max(oy + r, 0), ph - 1), xx = min(max(ox + c, 0), pw - 1);
+                win[i] = reinterpret_cast<const P *>(base + (ptrdiff_t)yy * s)[xx];
+            }
+        }
+        ffhip_wave_sync();
+        if (on) {
+            const uint16_t *w0 = win + (y4 + 2) * WIN + x4 + 2;
+            auto at = [&](int dx, int dy) { return (int)w0[dy * WIN + dx]; };
+            auto h = [&](int dx, int dy) { return tap6(at(dx - 2, dy), at(dx - 1, dy), at(dx, dy), at(dx + 1, dy), at(dx + 2, dy), at(dx + 3, dy)); };
+            auto v = [&](int dx, int dy) { return tap6(at(dx, dy - 2), at(dx, dy - 1), at(dx, dy), at(dx, dy + 1), at(dx, dy + 2), at(dx, dy + 3)); };
+#define QH(dx, dy) min(max((h(dx, dy) + 16) >> 5, 0), maxv)
+#define QV(dx, dy) min(max((v(dx, dy) + 16) >> 5, 0), maxv)
+#define QA(a, b) (((a) + (b) + 1) >> 1)
+            int hv = 0;
+            if ((fx == 2 && fy) || (fy == 2 && fx)) {   /* the centre column / row: vertical 6-tap over the unrounded horizontal sums */
+                int tt[6];
+#pragma unroll
+                for (int i = 0; i < 6; i++)
+                    tt[i] = h(0, i - 2);
+                hv = min(max((tap6(tt[0], tt[1], tt[2], tt[3], tt[4], tt[5]) + 512) >> 10, 0), maxv);
+            }
+            int val;
+            switch (fx + 4 * fy) {
+            case 0:  val = at(0, 0); break;
+            case 1:  val = QA(at(0, 0), QH(0, 0)); break;
+            case 2:  val = QH(0, 0); break;
+            case 3:  val = QA(at(1, 0), QH(0, 0)); break;
+            case 4:  val = QA(at(0, 0), QV(0, 0)); break;
+            case 8:  val = QV(0, 0); break;
+            case 12: val = QA(at(0, 1), QV(0, 0)); break;
+            case 5:  val = QA(QH(0, 0), QV(0, 0)); break;
+            case 7:  val = QA(QH(0, 0), QV(1, 0)); break;
+            case 13: val = QA(QH(0, 1), QV(0, 0)); break;
+            case 15: val = QA(QH(0, 1), QV(1, 0)); break;
+            case 10: val = hv; break;
+            case 6:  val = QA(QH(0, 0), hv); break;
+            case 14: val = QA(QH(0, 1), hv); break;
+            case 9:  val = QA(QV(0, 0), hv); break;
+            default: val = QA(QV(1, 0), hv); break;
+            }
+#undef QH
+#undef QV
+            pl[n] = val;
+            if (clane) {
+                const int cx = mvx, cy = mvy + R.chroma_dy, ax = cx & 7, ay = cy & 7;
+                const int x0 = bx * 2 + cxs + (cx >> 3), y0 = by * 2 + cys + (cy >> 3), cw = pw >> 1, chh = ph >> 1;
+                const uint8_t *base = R.base[1 + cpl];
+                const ptrdiff_t s = R.stride[1 + cpl];
+                auto cat = [&](int dx, int dy) {
+                    return (int)reinterpret_cast<const P *>(base + (ptrdiff_t)min(max(y0 + dy, 0), chh - 1) * s)[min(max(x0 + dx, 0), cw - 1)];
+                };
+                const int A = (8 - ax) * (8 - ay), B = ax * (8 - ay), Cc = (8 - ax) * ay, D = ax * ay;
+                int vv = A * cat(0, 0);
+                if (B) vv += B * cat(1, 0);
+                if (Cc) vv += Cc * cat(0, 1);
+                if (D) vv += D * cat(1, 1);
+                pc[n] = (vv + 32) >> 6;
+            }
+        }
+        ffhip_wave_sync(); /* list 1's window overwrites list 0's */
+    }
+
+    /* ---- 3. the lists combined ---- */
+    const int cw0 = cpl ? plan.chroma_weight[1][0] : plan.chroma_weight[0][0], cw1 = cpl ? plan.chroma_weight[1][1] : plan.chroma_weight[0][1];
+    const int co = cpl ? plan.chroma_offset[1] : plan.chroma_offset[0];
+    int yv = pl[0], cv = pc[0];
+    switch (plan.mode) {
+    case FFHIP_H264_INTER_UNI_W:
+        yv = h264inter_weight(pl[0], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_offset);
+        if (plan.chroma_weighted)
+            cv = h264inter_weight(pc[0], bd, plan.chroma_log2_denom, cw0, co);
+        break;
+    case FFHIP_H264_INTER_BI_AVG:
+        yv = QA(pl[0], pl[1]);
+        cv = QA(pc[0], pc[1]);
+        break;
+    case FFHIP_H264_INTER_BI_W:
+        yv = h264inter_biweight(pl[0], pl[1], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_weight[1], plan.luma_offset);
+        cv = h264inter_biweight(pc[0], pc[1], bd, plan.chroma_log2_denom, cw0, cw1, co);
+        break;
+    default:
+        break;
+    }
+#undef QA
+
+    /* ---- 4. whole rows of a block ---- */
+    ytile[lane] = (uint16_t)yv;
+    if (j < 8)
+        ctile[k * 8 + j] = (uint16_t)cv;
+    ffhip_wave_sync();
+    if (!live)
+        return;
+    if (x4 == 0) { /* lanes j = 0, 4, 8, 12: luma row y4 of the block, 4 samples; dst base and stride are multiples of 4 samples */
+        const uint16_t *r = ytile + k * 16 + y4 * 4;
+        uint8_t *d = Pc.dst[0] + (ptrdiff_t)(by * 4 + y4) * Pc.dst_stride[0] + (size_t)bx * 4 * sizeof(P);
+        if (sizeof(P) == 1)
+            *reinterpret_cast<uint32_t *>(d) = pack4(r[0], r[1], r[2], r[3]);
+        else
+            *reinterpret_cast<uint2 *>(d) = make_uint2((uint32_t)r[0] | (uint32_t)r[1] << 16, (uint32_t)r[2] | (uint32_t)r[3] << 16);
+    } else if (has_c && x4 == 1) { /* lanes j = 1, 5, 9, 13: chroma row (y4 & 1) of plane (y4 >> 1), 2 samples */
+        const int c = y4 >> 1, row = y4 & 1;
+        const uint16_t *r = ctile + k * 8 + c * 4 + row * 2;
+        uint8_t *d = Pc.dst[1 + c] + (ptrdiff_t)(by * 2 + row) * Pc.dst_stride[1 + c] + (size_t)bx * 2 * sizeof(P);
+        if (sizeof(P) == 1)
+            *reinterpret_cast<uint16_t *>(d) = (uint16_t)(r[0] | r[1] << 8);
+        else
+            *reinterpret_cast<uint32_t *>(d) = (uint32_t)r[0] | (uint32_t)r[1] << 16;
+    }
+}
+} // namespace
+
+int ffhip_launch_h264_inter_pictures(int bd, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264InterPic *pics, hipStream_t stream)
+{
+    for (int p0 = 0; p0 < npics; p0 += H4I_PICS) {
+        const int n = npics - p0 < H4I_PICS ? npics - p0 : H4I_PICS;
+        const int r = ffhip_progress_launch_table(stream, "ffhip_h264_inter_pictures_dev: copy or launch", pics + p0, n,
+                                                  [&](FFHipH264InterPic *dpics) {
+            const dim3 grid(mb_w, mb_h, n); /* at most 4096 x 4096 x 16 */
+            if (bd > 8)
+                hipLaunchKernelGGL(k_h264_inter_pic<uint16_t>, grid, dim3(256), 0, stream, dpics, mb_w, mb_h, bd, chroma_format_idc);
+            else
+                hipLaunchKernelGGL(k_h264_inter_pic<uint8_t>, grid, dim3(256), 0, stream, dpics, mb_w, mb_h, bd, chroma_format_idc);
+        });
+        if (r < 0)
+            return r;
+    }
+    return 0;
+}

@@ -1,0 +1,114 @@
+/*
+ * h264_inter_rules.h — how the lists of one 4x4 block combine in H.264 inter prediction (rules 1, 2 and 5 to 8 of
+ * ffhip_h264_inter_pictures_dev as include/ffhip.h states them), once: shared by the kernel of h264_inter_pic.hip and by the
+ * device-free face ffhip_h264_inter_plan_pictures_host() (shims_h264_inter.hip), which runs it on the host.  Restated from memory of
+ * the reference's h264_mb.c (mc_part and what it calls) and from H.264 8.4.2.2 / 8.4.2.3, not checked against its source.  One plain
+ * function of the macroblock record, the block's motion record and the slice table; it reads nothing else.
+ */
+#ifndef FFHIP_H264_INTER_RULES_H
+#define FFHIP_H264_INTER_RULES_H
+
+#include <stdint.h>
+
+#include "ffhip.h"
+
+#if defined(__HIPCC__)
+#define H264INTER_FN __host__ __device__ __forceinline__
+#else
+#define H264INTER_FN static inline
+#endif
+
+/* the plan of the block whose motion record is f, in macroblock m; every field the mode does not use is 0 */
+H264INTER_FN FFHipH264InterBlockPlan h264inter_plan(const FFHipH264BsMb *m, const FFHipH264MvField *f, const FFHipH264InterSlice *slices,
+                                                    int nslices, int nrefs)
+{
+    FFHipH264InterBlockPlan p = {};
+    if ((m->flags & 1) || (int)m->slice >= nslices)                         /* rule 1; rule 2: no slice */
+        return p;
+    const FFHipH264InterSlice *S = slices + m->slice;
+    if (S->luma_log2_denom > 7 || S->chroma_log2_denom > 7 || S->use_weight > 2)
+        return p;
+    const int r0 = f->ref_idx[0], r1 = f->ref_idx[1];
+    const int nlists = (r0 >= 0) + (r1 >= 0);
+    if (!nlists)
+        return p;
+    int slot[2] = { 0, 0 };
+    for (int l = 0; l < 2; l++) {
+        const int r = l ? r1 : r0;
+        if (r < 0)
+            continue;
+        if (r >= 32 || S->num_ref[l] > 32 || r >= (int)S->num_ref[l] || (int)S->ref[l][r] >= nrefs)
+            return p;
+        slot[l] = S->ref[l][r];
+    }
+    if (nlists == 2) {
+        p.slot[0] = (uint8_t)slot[0];
+        p.slot[1] = (uint8_t)slot[1];
+        if (S->use_weight == 2 && S->implicit_weight[r0][r1] != 32) {      /* rule 7, implicit */
+            const int w0 = S->implicit_weight[r0][r1];
+            p.mode = FFHIP_H264_INTER_BI_W;
+            p.chroma_weighted = 1;
+            p.luma_log2_denom = p.chroma_log2_denom = 5;
+            p.luma_weight[0] = (int16_t)w0;
+            p.luma_weight[1] = (int16_t)(64 - w0);
+            for (int c = 0; c < 2; c++) {
+                p.chroma_weight[c][0] = (int16_t)w0;
+                p.chroma_weight[c][1] = (int16_t)(64 - w0);
+            }
+        } else if (S->use_weight == 1) {                                     /* rule 7, explicit */
+            p.mode = FFHIP_H264_INTER_BI_W;
+            p.chroma_weighted = 1;
+            p.luma_log2_denom = S->luma_log2_denom;
+            p.chroma_log2_denom = S->chroma_log2_denom;
+            p.luma_weight[0] = S->luma_weight[r0][0][0];
+            p.luma_weight[1] = S->luma_weight[r1][1][0];
+            p.luma_offset = (int16_t)(S->luma_weight[r0][0][1] + S->luma_weight[r1][1][1]);
+            for (int c = 0; c < 2; c++) {
+                p.chroma_weight[c][0] = S->chroma_weight[r0][0][c][0];
+                p.chroma_weight[c][1] = S->chroma_weight[r1][1][c][0];
+                p.chroma_offset[c] = (int16_t)(S->chroma_weight[r0][0][c][1] + S->chroma_weight[r1][1][c][1]);
+            }
+        } else {
+            p.mode = FFHIP_H264_INTER_BI_AVG;                                /* rule 6 */
+        }
+        return p;
+    }
+    const int L = r0 >= 0 ? 0 : 1, r = L ? r1 : r0;
+    p.list = (uint8_t)L;
+    p.slot[0] = (uint8_t)slot[L];
+    if (S->use_weight != 1) {
+        p.mode = FFHIP_H264_INTER_UNI;                                       /* rule 6; implicit weights need two lists */
+        return p;
+    }
+    p.mode = FFHIP_H264_INTER_UNI_W;                                         /* rule 8 */
+    p.luma_log2_denom = S->luma_log2_denom;
+    p.luma_weight[0] = S->luma_weight[r][L][0];
+    p.luma_offset = S->luma_weight[r][L][1];
+    if (S->use_weight_chroma) {
+        p.chroma_weighted = 1;
+        p.chroma_log2_denom = S->chroma_log2_denom;
+        for (int c = 0; c < 2; c++) {
+            p.chroma_weight[c][0] = S->chroma_weight[r][L][c][0];
+            p.chroma_offset[c] = S->chroma_weight[r][L][c][1];
+        }
+    }
+    return p;
+}
+
+/* weight_h264_pixels / biweight_h264_pixels for one sample at depth bd (h264dsp_template.c); the offset in 8-bit units */
+H264INTER_FN int h264inter_clip(int v, int maxv) { return v < 0 ? 0 : v > maxv ? maxv : v; }
+H264INTER_FN int h264inter_weight(int p, int bd, int ld, int w, int o)
+{
+    int offset = (int)((unsigned)o << (ld + (bd - 8)));
+    if (ld)
+        offset += 1 << (ld - 1);
+    return h264inter_clip((p * w + offset) >> ld, (1 << bd) - 1);
+}
+H264INTER_FN int h264inter_biweight(int p0, int p1, int bd, int ld, int w0, int w1, int o)
+{
+    int offset = (int)((unsigned)o << (bd - 8));
+    offset = (int)((unsigned)((offset + 1) | 1) << ld);
+    return h264inter_clip((p1 * w1 + p0 * w0 + offset) >> (ld + 1), (1 << bd) - 1);
+}
+
+#endif /* FFHIP_H264_INTER_RULES_H */

@@ -170,6 +170,79 @@ def edge_params_pictures_host(pics, mb_w, mb_h, field=0, qp_bd_offset=0):
                       "ffhip_h264_edge_params_pictures_host")
 
 
+#: FFHipH264InterSlice (include/ffhip.h): what the inter face reads from a slice.  ref[list][ref_idx] -> slot of InterPic.ref;
+#: luma_weight[ref_idx][list][weight, offset]; chroma_weight[ref_idx][list][Cb, Cr][weight, offset]; implicit_weight[ref_idx0][ref_idx1].
+INTER_SLICE_DTYPE = np.dtype([("ref", np.uint8, (2, 32)), ("num_ref", np.uint8, 2), ("use_weight", np.uint8), ("use_weight_chroma", np.uint8),
+                              ("luma_log2_denom", np.uint8), ("chroma_log2_denom", np.uint8), ("pad", np.uint8, 2),
+                              ("luma_weight", np.int16, (32, 2, 2)), ("chroma_weight", np.int16, (32, 2, 2, 2)),
+                              ("implicit_weight", np.int16, (32, 32))])
+#: FFHipH264InterBlockPlan: how the lists of one 4 x 4 block combine (mode: INTER_SKIP .. INTER_BI_W)
+INTER_PLAN_DTYPE = np.dtype([("mode", np.uint8), ("list", np.uint8), ("slot", np.uint8, 2), ("chroma_weighted", np.uint8),
+                             ("luma_log2_denom", np.uint8), ("chroma_log2_denom", np.uint8), ("pad", np.uint8),
+                             ("luma_weight", np.int16, 2), ("luma_offset", np.int16), ("chroma_weight", np.int16, (2, 2)),
+                             ("chroma_offset", np.int16, 2), ("pad2", np.int16)])
+assert INTER_SLICE_DTYPE.itemsize == 2888 and INTER_PLAN_DTYPE.itemsize == 28
+INTER_SKIP, INTER_UNI, INTER_UNI_W, INTER_BI_AVG, INTER_BI_W = range(5)
+INTER_PICS_PER_LAUNCH = 16
+
+
+class InterRef(C.Structure):
+    """FFHipH264InterRef"""
+    _fields_ = [("base", C.c_void_p * 3), ("stride", C.c_ssize_t * 3), ("chroma_dy", C.c_int8), ("pad", C.c_uint8 * 7)]
+
+
+class InterPic(C.Structure):
+    """FFHipH264InterPic"""
+    _fields_ = [("dst", C.c_void_p * 3), ("dst_stride", C.c_ssize_t * 3), ("mb", C.c_void_p), ("mvf", C.c_void_p), ("slices", C.c_void_p),
+                ("mvf_stride", C.c_int32), ("nslices", C.c_int32), ("nrefs", C.c_int32), ("pad", C.c_int32), ("ref", InterRef * 32)]
+
+
+class InterPlanPic(C.Structure):
+    """FFHipH264InterPlanPic"""
+    _fields_ = [("mb", C.c_void_p), ("mvf", C.c_void_p), ("slices", C.c_void_p), ("plans", C.c_void_p), ("mvf_stride", C.c_int32),
+                ("nslices", C.c_int32), ("nrefs", C.c_int32), ("pad", C.c_int32)]
+
+
+def inter_pics(pics):
+    """the FFHipH264InterPic array of inter_pictures()'s dicts (the pointers are taken as they are: the caller keeps the tensors)"""
+    arr = (InterPic * max(len(pics), 1))()
+    ptr = lambda t: None if t is None else t if isinstance(t, int) else t.data_ptr()
+    for i, m in enumerate(pics):
+        a = arr[i]
+        for p, (t, s) in enumerate(zip(m["dst"], m["dst_stride"])):
+            a.dst[p], a.dst_stride[p] = ptr(t), s
+        a.mb, a.mvf, a.slices = ptr(m["mb"]), ptr(m["mvf"]), ptr(m["slices"])
+        a.mvf_stride, a.nslices, a.nrefs = m["mvf_stride"], m["nslices"], len(m["refs"])
+        for k, r in enumerate(m["refs"]):
+            for p, (t, s) in enumerate(zip(r["base"], r["stride"])):
+                a.ref[k].base[p], a.ref[k].stride[p] = ptr(t), s
+            a.ref[k].chroma_dy = r.get("chroma_dy", 0)
+    return arr
+
+
+def inter_pictures(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1, stream=None):
+    """ffhip_h264_inter_pictures_dev on npics = len(pics) pictures of mb_w x mb_h macroblocks.  pics[i]: a dict with dst (up to three
+    device tensors or addresses, Cb / Cr None for luma only) and dst_stride (bytes), the device tensors mb (BS_MB_DTYPE records as
+    bytes), mvf (BS_MVF_DTYPE) and slices (INTER_SLICE_DTYPE), the ints mvf_stride (records) and nslices, and refs: at most 32 dicts
+    with base (three tensors or addresses), stride (bytes) and optionally chroma_dy.  mb and mvf are the arrays edge_params_pictures()
+    takes.  Asynchronous on `stream`."""
+    arr = inter_pics(pics)
+    return _lib.check(_lib.lib().ffhip_h264_inter_pictures_dev(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p),
+                                                               _stream(stream)), "ffhip_h264_inter_pictures_dev")
+
+
+def inter_plan_host(pics, mb_w, mb_h):
+    """ffhip_h264_inter_plan_pictures_host (device-free): pics[i] is a dict with the numpy arrays mb, mvf, slices, plans (INTER_PLAN_DTYPE,
+    16 * mb_w * mb_h records, written in place) and the ints mvf_stride, nslices, nrefs."""
+    arr = (InterPlanPic * max(len(pics), 1))()
+    for i, m in enumerate(pics):
+        a = arr[i]
+        a.mb, a.mvf, a.slices, a.plans = (m[k].ctypes.data for k in ("mb", "mvf", "slices", "plans"))
+        a.mvf_stride, a.nslices, a.nrefs = m["mvf_stride"], m["nslices"], m["nrefs"]
+    return _lib.check(_lib.lib().ffhip_h264_inter_plan_pictures_host(mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p)),
+                      "ffhip_h264_inter_plan_pictures_host")
+
+
 class Picture:
     """ctypes mirror of FFHipH264Picture: record a picture's per-block dsp calls on the host, flush them as a handful of
     launches (include/ffhip.h).  Records are numpy structured scalars / arrays of the batch faces' dtypes."""

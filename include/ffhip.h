@@ -668,6 +668,112 @@ int ffhip_h264_bs_mvf_record_size(void);
 int ffhip_h264_bs_slice_record_size(void);
 
 /**
+ * The inter prediction of whole H.264 pictures in one launch, from the same two arrays the edge-parameter face above takes (mb, mvf)
+ * plus one record per slice: what hl_motion() / mc_part() / mc_part_std() / mc_part_weighted() / mc_dir_part() of
+ * libavcodec/h264_mb.c do macroblock by macroblock, as one gather over the picture.  Both lists and the weighting are combined in
+ * registers and every sample is written once.  Non-MBAFF pictures (a frame, or one field as base + doubled stride); 4:2:0 and
+ * monochrome.  Restated from memory of h264_mb.c and from H.264 8.4.2.2 / 8.4.2.3, pinned through the oracle's members; NOT checked
+ * against the reference's source, which the build does not have.
+ *
+ * H.264 prediction is a function of the sample: its value depends only on the vector and the reference of the 4x4 block that covers
+ * it, never on the partition shape, and emulated_edge_mc is a clamp of each source coordinate.  So the face takes no partition types.
+ * For each 4x4 luma block b of macroblock m (and its 2x2 block of Cb and of Cr), S = slices[m.slice]:
+ *  1. m intra (flags & 1): none of its samples is written.
+ *  2. b is malformed, reads no reference and writes nothing (luma and chroma), when: m.slice >= nslices; no list is used
+ *     (ref_idx[list] < 0 for both); a used list has ref_idx >= S.num_ref[list], ref_idx >= 32, S.num_ref[list] > 32 or the slot
+ *     S.ref[list][ref_idx] >= nrefs; a log2 denominator of S is above 7; S.use_weight > 2.
+ *  3. the luma sample of one list: h264qpel's put at position (mvx & 3) + ((mvy & 3) << 2), source origin the block's position plus
+ *     (mvx >> 2, mvy >> 2), every source sample fetched at row clamp(y, 0, 16*mb_h - 1), column clamp(x, 0, 16*mb_w - 1) of the
+ *     slot's plane.  Vectors may point anywhere in int16_t.
+ *  4. the chroma sample of one list: cx = mvx, cy = mvy + ref.chroma_dy; h264chroma's put with the fractions (cx & 7, cy & 7), origin
+ *     the chroma block's position plus (cx >> 3, cy >> 3), coordinates clamped to 8*mb_w x 8*mb_h.
+ *  5. weighted: S.use_weight == 1; or S.use_weight == 2, both lists used and S.implicit_weight[r0][r1] != 32 (r0, r1: the ref_idx).
+ *  6. not weighted: one list: its sample; two lists: (p0 + p1 + 1) >> 1.
+ *  7. weighted, two lists: implicit: biweight(p0, p1, log2_denom 5, w0 = implicit_weight[r0][r1], w1 = 64 - w0, offset 0) on all
+ *     planes; explicit: luma biweight(p0, p1, luma_log2_denom, luma_weight[r0][0][0], luma_weight[r1][1][0], luma_weight[r0][0][1] +
+ *     luma_weight[r1][1][1]), chroma the same with chroma_weight[..][..][c] and chroma_log2_denom (always; use_weight_chroma is not
+ *     consulted).
+ *  8. weighted, one list L: luma weight(p, luma_log2_denom, luma_weight[r][L][0], luma_weight[r][L][1]); chroma the same way with
+ *     chroma_weight only when S.use_weight_chroma is set, plain otherwise.
+ *  9. weight / biweight are h264dsp's weight_h264_pixels / biweight_h264_pixels (dst = list 0 with weightd, src = list 1 with
+ *     weights); offsets in 8-bit units, scaled by the depth inside as the batch faces take them.
+ * 10. Every sample of every well-formed block of a non-intra macroblock is written exactly once; nothing else is: not intra
+ *     macroblocks, not the stride padding, no input.
+ * Out of scope: the residual (ffhip_h264_idct_add_mb_batch_dev and its family follow on the same stream), 4:2:2 / 4:4:4, MBAFF.
+ */
+typedef struct FFHipH264InterSlice {       /* what mc_part() reads from the slice, 2888 bytes */
+    uint8_t  ref[2][32];                   /* [list][ref_idx] -> slot: index into FFHipH264InterPic.ref */
+    uint8_t  num_ref[2];                   /* 0..32 */
+    uint8_t  use_weight;                   /* pwt.use_weight: 0 none, 1 explicit, 2 implicit */
+    uint8_t  use_weight_chroma;            /* pwt.use_weight_chroma */
+    uint8_t  luma_log2_denom, chroma_log2_denom;   /* 0..7 */
+    uint8_t  pad[2];
+    int16_t  luma_weight[32][2][2];        /* [ref_idx][list][weight, offset]: pwt.luma_weight, defaults filled in by the decoder */
+    int16_t  chroma_weight[32][2][2][2];   /* [ref_idx][list][Cb, Cr][weight, offset] */
+    int16_t  implicit_weight[32][32];      /* [ref_idx0][ref_idx1]: list 0's weight, -64..128 (non-MBAFF: both parities equal) */
+} FFHipH264InterSlice;
+typedef struct FFHipH264InterRef {         /* one reference picture (a frame, or one field as base + doubled stride), 56 bytes */
+    const uint8_t *base[3];                /* device; Cb / Cr are read only where the picture has chroma */
+    ptrdiff_t stride[3];                   /* bytes; a multiple of the sample size, any sign */
+    int8_t  chroma_dy;                     /* added to the chroma vector's y (eighth samples) before it is split: the decoder sets
+                                              2 * (current parity - reference parity) for 4:2:0 field pictures, else 0 */
+    uint8_t pad[7];
+} FFHipH264InterRef;
+typedef struct FFHipH264InterPic {         /* 1880 bytes */
+    uint8_t *dst[3];                       /* device; Cb and Cr NULL: luma only (monochrome) */
+    ptrdiff_t dst_stride[3];               /* bytes; base and stride multiples of 4 samples, stride >= the plane's width */
+    const FFHipH264BsMb *mb;               /* device, mb_w * mb_h raster: predicted iff !(flags & 1); `slice` indexes slices */
+    const FFHipH264MvField *mvf;           /* device, [by * mvf_stride + bx], 4-byte aligned; a list is used iff ref_idx[list] >= 0 */
+    const FFHipH264InterSlice *slices;     /* device, nslices records */
+    int32_t mvf_stride, nslices, nrefs, pad;
+    FFHipH264InterRef ref[32];             /* in this host array: the face stages it to the device */
+} FFHipH264InterPic;
+/** npics pictures of mb_w x mb_h macroblocks (1..4096 each) at bit_depth 8, 9, 10, 12 or 14 (uint16_t samples above 8; strides stay
+ *  in bytes), chroma_format_idc 0 (Cb / Cr ignored) or 1.  Pictures go 16 to a launch.  Asynchronous on `stream`.
+ *  FFHIP_ENOSYS (with a text) for chroma_format_idc 2 or 3; MBAFF pictures have no entry here: the caller keeps them on its own path.
+ *  FFHIP_EINVAL for another depth, format or size, npics <= 0, a NULL or misaligned dst plane or stride, a stride below the plane's
+ *  width, only one of Cb / Cr, NULL mb / mvf / slices, an mvf that is not 4-byte aligned, mvf_stride < 4*mb_w, nslices < 1, nrefs
+ *  outside 0..32, a NULL or sample-misaligned plane among the first nrefs references, or an overlap: a reference row that shares a
+ *  byte with a destination row of any picture of the call, or two destination planes that do.  Rows, not spans: the two fields of a
+ *  frame (equal strides s, bases a row apart) are accepted, the second predicted from the first; with d = (ref.base - dst.base) mod s
+ *  the rows are disjoint iff d >= dst_row_bytes and d + ref_row_bytes <= s.  Overlapping spans with unequal strides are refused.
+ *  FFHIP_ENOSYS without a device (after the argument checks). */
+int ffhip_h264_inter_pictures_dev(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics,
+                                  const FFHipH264InterPic *pics /* host array */, void *stream);
+
+/** Rules 1, 2 and 5 to 8 for one block, resolved: what the kernel computes per block before it touches a sample. */
+enum { FFHIP_H264_INTER_SKIP = 0,          /* intra or malformed: nothing read, nothing written; every other field 0 */
+       FFHIP_H264_INTER_UNI, FFHIP_H264_INTER_UNI_W, FFHIP_H264_INTER_BI_AVG, FFHIP_H264_INTER_BI_W };
+typedef struct FFHipH264InterBlockPlan {   /* 28 bytes; fields a mode does not use are 0 */
+    uint8_t mode;                          /* FFHIP_H264_INTER_* */
+    uint8_t list;                          /* UNI / UNI_W: the list used (whose vector is read) */
+    uint8_t slot[2];                       /* BI_*: the slots of list 0 and list 1; UNI*: slot[0] alone */
+    uint8_t chroma_weighted;               /* UNI_W: S.use_weight_chroma != 0; BI_W: 1 */
+    uint8_t luma_log2_denom, chroma_log2_denom;    /* *_W; chroma's only if chroma_weighted */
+    uint8_t pad;
+    int16_t luma_weight[2], luma_offset;   /* UNI_W: weight[0]; BI_W: weightd (list 0), weights (list 1), the summed offset */
+    int16_t chroma_weight[2][2], chroma_offset[2]; /* [Cb, Cr][as luma_weight], [Cb, Cr] */
+    int16_t pad2;
+} FFHipH264InterBlockPlan;
+typedef struct FFHipH264InterPlanPic {     /* host pointers */
+    const FFHipH264BsMb *mb;
+    const FFHipH264MvField *mvf;
+    const FFHipH264InterSlice *slices;
+    FFHipH264InterBlockPlan *plans;        /* out: [by * 4*mb_w + bx], 16 * mb_w * mb_h plans */
+    int32_t mvf_stride, nslices, nrefs, pad;
+} FFHipH264InterPlanPic;
+/** The plan of every 4x4 block of npics pictures, by the function the kernel uses (device-free).  FFHIP_EINVAL for mb_w / mb_h
+ *  outside 1..4096, npics <= 0, NULL mb / mvf / slices / plans, an mvf that is not 4-byte aligned, mvf_stride < 4*mb_w, nslices < 1,
+ *  nrefs outside 0..32, or a plan array that overlaps an input or another plan array of the call. */
+int ffhip_h264_inter_plan_pictures_host(int mb_w, int mb_h, int npics, const FFHipH264InterPlanPic *pics);
+/** sizeof the records above, for bindings that mirror them (no device needed). */
+int ffhip_h264_inter_slice_record_size(void);
+int ffhip_h264_inter_ref_record_size(void);
+int ffhip_h264_inter_pic_record_size(void);
+int ffhip_h264_inter_plan_record_size(void);
+int ffhip_h264_inter_plan_pic_record_size(void);
+
+/**
  * The batched faces above at ANY depth the reference instantiates (bit_depth 8 / 9 / 10 / 12 / 14), plus the members that exist
  * only here: MBAFF and 4:2:2.  Above 8 bits samples are uint16_t and coefficients int32_t (libavcodec/bit_depth_template.c);
  * strides and offsets stay in BYTES, coefficient pitches in coefficients.  Bit-exact restatement of the reference's templates
