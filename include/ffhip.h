@@ -2096,7 +2096,10 @@ int ff_vp9dsp_itxfm_init_hip(FFHipVP9ItxfmContext *c, int bpp);
 
 /** One transform block of the batch face. */
 typedef struct FFHipVp9TU {
-    int32_t coeff_offset; /* int16 elements into coeffs: size * size coefficients, the decoder's layout */
+    int32_t coeff_offset; /* int16 elements into coeffs: size * size coefficients, the decoder's layout.  coeffs + coeff_offset
+                           * must be 4-byte aligned (coeff_offset even on an aligned int16 array; any value on the int32 array of the
+                           * _hbd face): a block moves in 16-byte pieces where it is 16-byte aligned and as dwords otherwise, unit by
+                           * unit; an odd address is undefined */
     int32_t dst_offset;   /* bytes into dst                                                           */
     uint8_t txtp;         /* enum TxfmType; ignored for 32x32 and the WHT                              */
     uint8_t dc_only;      /* eob == 1: DCT_DCT takes its dc-only shortcut                              */
@@ -2158,7 +2161,9 @@ typedef struct FFHipVP9LoopFilterContext {
 int ff_vp9dsp_loopfilter_init_hip(FFHipVP9LoopFilterContext *c, int bpp);
 /** One 8-sample segment of an edge: what one loop_filter() call of the reference covers (vp9dsp_template.c:1780-1889). */
 typedef struct FFHipVp9Edge {
-    int32_t offset;      /* bytes into the plane: the first q0 sample of the segment */
+    int32_t offset;      /* bytes into the plane: the first q0 sample of the segment; base + offset even above 8 bits (a uint16_t
+                          * sample), an odd address is undefined.  Any other alignment is allowed: a column edge's line is moved as
+                          * dwords where its address is 4-byte aligned and sample by sample otherwise, line by line */
     uint8_t wd_idx;      /* 0: 4, 1: 8, 2: 16 */
     uint8_t dir;         /* 0: column edge (loop_filter_h_*), 1: row edge (loop_filter_v_*) */
     uint8_t E, I, H;     /* mb_lim, lim, hev_thr */

@@ -54,6 +54,62 @@ def test_vp9_itxfm_batch(tx):
     assert (want != dst).sum() > 1000
     assert np.array_equal(d_dst.cpu().numpy(), want)
     assert np.array_equal(d_co.cpu().numpy(), wcoef)
+    itxfm_alignment_launches(tx, 8)
+
+
+def itxfm_alignment_launches(tx, bd):
+    """the two staging paths of k_vp9_itxfm, chosen by the alignment of coeffs + coeff_offset: blocks on every dword of a 16-byte
+    line (the 16-byte path on the first, the dword path on the other three), in launches of 1, UPW - 1, UPW, UPW + 1, 4 UPW - 1 and
+    4 UPW + 1 units (UPW = 64 / N units per wave, four waves per workgroup), a dc-only unit beside full ones in every wave.  The
+    coefficients between the blocks belong to nobody and stay as they are."""
+    from ffmpeg_amd import vp9
+    torch = _torch()
+    O = ffi.oracle()
+    rng = np.random.default_rng(460 + 10 * tx + bd)
+    n = 4 if tx == 4 else 4 << tx
+    upw = 64 // n
+    cdt, sdt, ps = (np.int16, np.uint8, 1) if bd == 8 else (np.int32, np.uint16, 2)
+    per_dword = 4 // np.dtype(cdt).itemsize
+    seen = set()
+    for nu in sorted({1, upw - 1, upw, upw + 1, 4 * upw - 1, 4 * upw + 1} - {0}):
+        stride = (nu * n + 5) * ps                                    # bytes
+        dst = rng.integers(0, 1 << bd, (n, nu * n + 5)).astype(sdt)
+        want = dst.copy()
+        offs, pos = [], 0
+        for j in range(nu):
+            off = (pos + 4 * per_dword - 1) // (4 * per_dword) * (4 * per_dword) + (j % 4) * per_dword
+            offs.append(off)
+            pos = off + n * n
+        coeffs = np.full(pos + 4 * per_dword, 1234, cdt)
+        wcoef = coeffs.copy()
+        rec = np.zeros(nu, vp9.TU_DTYPE)
+        for j, off in enumerate(offs):
+            dc = j % 3 == 1                                           # units 1, 4, 7 ..: dc-only between full units
+            txtp = 0 if dc else j % 4
+            if bd == 8:
+                blk = vp9_block(rng, n, 2 if dc else 4 * (j & 1))
+            else:
+                from test_oracle_vs_ref_hbd import vp9_block32
+                blk = vp9_block32(rng, n, 2 if dc else 4 * (j & 1), bd)
+            eob = 1 if dc else n * n
+            coeffs[off:off + n * n] = blk
+            rec[j] = (off, j * n * ps, txtp, int(dc), (0, 0))
+            wb = blk.copy()
+            if bd == 8:
+                O.ffo_vp9_itxfm_add(tx, txtp, C.cast(want.ctypes.data + j * n * ps, u8p), stride, ptr(wb, i16p), eob)
+            else:
+                O.ffo_vp9_itxfm_add_bd(bd, tx, txtp, C.cast(want.ctypes.data + j * n * ps, u8p), stride, ptr(wb, ffi.i32p), eob)
+            wcoef[off:off + n * n] = wb
+            seen.add((off * np.dtype(cdt).itemsize) % 16)
+        d_dst = torch.from_numpy(dst.view(np.uint8).reshape(-1).copy()).cuda()
+        d_co = torch.from_numpy(coeffs.copy()).cuda()
+        assert d_co.data_ptr() % 16 == 0
+        vp9.itxfm_add_batch(tx, d_co, d_dst, stride, torch.from_numpy(rec.view(np.uint8).reshape(nu, 12).copy()).cuda(), nu, bit_depth=bd)
+        torch.cuda.synchronize()
+        assert np.array_equal(d_dst.cpu().numpy().view(sdt).reshape(dst.shape), want), (tx, bd, nu)
+        assert np.array_equal(d_co.cpu().numpy(), wcoef), (tx, bd, nu)
+        assert (want != dst).any() and (wcoef != coeffs).any()
+    assert seen == {0, 4, 8, 12}
 
 
 def test_vp9_itxfm_host_faces():

@@ -57,6 +57,8 @@ def test_vp9_itxfm_batch_hbd(tx, bd):
     assert (want != dst).sum() > 1000
     assert np.array_equal(back(d_dst, dst), want)
     assert np.array_equal(d_co.cpu().numpy(), wcoef)
+    from test_gpu_vp9 import itxfm_alignment_launches
+    itxfm_alignment_launches(tx, bd)
 
 
 @pytest.mark.parametrize("bd", DEPTHS)
