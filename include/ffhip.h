@@ -535,7 +535,10 @@ int ffhip_h264_chroma_dc_dequant_idct_batch_dev(int16_t *blocks, const int32_t *
 #define FFHIP_H264_LF_H_LUMA_INTRA    5
 #define FFHIP_H264_LF_V_CHROMA_INTRA  6
 #define FFHIP_H264_LF_H_CHROMA_INTRA  7
-/** One edge descriptor of the batch face: everything the reference call takes besides pix/stride. */
+/** One edge descriptor of the batch face: everything the reference call takes besides pix/stride.
+ *  alpha == 0 or beta == 0 leaves the edge untouched on every face (no difference is below 0).  tc0 of a bS = 4 record (an _INTRA kind) is
+ *  ignored, whatever it holds.  The frame faces read kind >= 4 as bS = 4 and nothing else of `kind` (bits 0 / 1: the direction and the
+ *  plane follow from the record's place in the table) and ignore `offset`. */
 typedef struct FFHipH264Edge {
     int32_t offset;      /* pix = base + offset                                    */
     uint8_t kind;        /* FFHIP_H264_LF_*                                         */
@@ -546,6 +549,9 @@ typedef struct FFHipH264Edge {
 /**
  * n edges whose touched pixels are pairwise DISJOINT (function-level batch, as checkasm's tiles).
  * Order-dependent frame deblocking is ffhip_h264_deblock_frame_dev().
+ * Any `offset` and any stride are accepted: a line of a vertical edge (an h_ kind) whose address base + offset + line * stride is 4-byte
+ * aligned moves as two dwords, every other line sample by sample; the choice is made line by line.  (Above 8 bits,
+ * ffhip_h264_loop_filter_batch_dev_hbd(), base + offset and the stride are even: samples are uint16_t.)
  */
 int ffhip_h264_loop_filter_batch_dev(uint8_t *base, ptrdiff_t stride, const FFHipH264Edge *edges, int n,
                                      void *stream);
@@ -554,7 +560,8 @@ int ffhip_h264_loop_filter_batch_dev(uint8_t *base, ptrdiff_t stride, const FFHi
  * raster order, vertical edges 0..3 left-to-right then horizontal edges 0..3 top-to-bottom, as
  * ff_h264_filter_mb() orders the h264dsp calls (libavcodec/h264_loopfilter.c:716).
  * edges[(mb*2 + dir)*4 + e] describes MB mb, dir 0 = vertical edges (h_loop_filter_*), 1 =
- * horizontal; `kind` selects normal (tc0 used) vs intra, alpha == 0 skips the edge; `offset` ignored.
+ * horizontal; kind >= 4 selects intra (bS = 4: tc0 ignored), anything below normal (tc0 used); bits 0 / 1 of `kind` and `offset` are
+ * ignored; alpha == 0 or beta == 0 skips the edge.
  * Implemented as a 2-D wavefront over MBs — bit-exact with the serial order.
  */
 int ffhip_h264_deblock_frame_dev(uint8_t *luma, ptrdiff_t stride, int mb_w, int mb_h,
@@ -568,7 +575,8 @@ int ffhip_h264_deblock_frames_dev(uint8_t *luma, size_t frame_pitch, int nframes
  * The same for one 4:2:0 CHROMA plane (8x8 samples per macroblock; call once for Cb and once for Cr — their alpha / beta / tc0
  * come from different QPs): per MB the vertical edges at x = 0 and 4, then the horizontal ones at y = 0 and 4, as
  * filter_mb_dir() filters chroma on the even luma edges (libavcodec/h264_loopfilter.c:644-700).
- * edges[((f * mb_h * mb_w + mb) * 2 + dir) * 2 + e]; kinds FFHIP_H264_LF_*_CHROMA[_INTRA]; alpha == 0 skips an edge.
+ * edges[((f * mb_h * mb_w + mb) * 2 + dir) * 2 + e]; kinds FFHIP_H264_LF_*_CHROMA[_INTRA], read as kind >= 4: bS = 4; alpha == 0 or
+ * beta == 0 skips an edge.
  * plane, stride and frame_pitch must be 4-byte aligned.
  */
 int ffhip_h264_deblock_frames_chroma_dev(uint8_t *plane, size_t frame_pitch, int nframes, ptrdiff_t stride, int mb_w, int mb_h,
