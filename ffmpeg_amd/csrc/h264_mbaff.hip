@@ -435,36 +435,13 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock(MbaffLfArgs A, int *p
                 if (hfilt) {
                     /* lines = rows: luma 16 (tc0 per 4), chroma 8 (per 2); _mbaff: 8 (per 2), 4 (per 1) (h264dsp_template.c:127-133,262-272) */
                     const int nlines = (chroma ? 8 : 16) >> half, per = (chroma ? 2 : 4) >> half;
-                    if (lane < nlines) {
-                        uint8_t *l = tile + toff + lane * step - 4;
-                        const uint32_t a = *reinterpret_cast<const uint32_t *>(l), b = *reinterpret_cast<const uint32_t *>(l + 4);
-                        LfLine v = { (int)(a & 255), (int)((a >> 8) & 255), (int)((a >> 16) & 255), (int)(a >> 24),
-                                     (int)(b & 255), (int)((b >> 8) & 255), (int)((b >> 16) & 255), (int)(b >> 24) };
-                        const int m = lf_line(v, cls, alpha, beta, intra ? 0 : tc0[lane / per]);
-                        if (m & 7)
-                            *reinterpret_cast<uint32_t *>(l) = (uint32_t)v.p3 | (uint32_t)v.p2 << 8 | (uint32_t)v.p1 << 16 | (uint32_t)v.p0 << 24;
-                        if (m & 56)
-                            *reinterpret_cast<uint32_t *>(l + 4) = (uint32_t)v.q0 | (uint32_t)v.q1 << 8 | (uint32_t)v.q2 << 16 | (uint32_t)v.q3 << 24;
-                    }
+                    if (lane < nlines)
+                        lf_apply_dwords(reinterpret_cast<uint32_t *>(tile + toff + lane * step - 4), cls, alpha, beta, intra ? 0 : tc0[lane / per]);
                 } else {
                     /* lines = columns, a lane each: luma 16 (tc0 per 4; rows -4 .. 3: the strong filter's p3 / q3), chroma 8 (per 2; rows -2 .. 1) */
                     const int ncols = chroma ? 8 : 16, per = chroma ? 2 : 4;
-                    if (lane < ncols) {
-                        uint8_t *c = tile + toff + lane;
-                        LfLine v;
-                        v.p1 = c[-2 * step]; v.p0 = c[-step]; v.q0 = c[0]; v.q1 = c[step];
-                        v.p3 = v.p2 = v.q2 = v.q3 = 0;
-                        if (!chroma) {
-                            v.p3 = c[-4 * step]; v.p2 = c[-3 * step]; v.q2 = c[2 * step]; v.q3 = c[3 * step];
-                        }
-                        const int m = lf_line(v, cls, alpha, beta, intra ? 0 : tc0[lane / per]);
-                        if (m & 1)  c[-3 * step] = (uint8_t)v.p2;
-                        if (m & 2)  c[-2 * step] = (uint8_t)v.p1;
-                        if (m & 4)  c[-step] = (uint8_t)v.p0;
-                        if (m & 8)  c[0] = (uint8_t)v.q0;
-                        if (m & 16) c[step] = (uint8_t)v.q1;
-                        if (m & 32) c[2 * step] = (uint8_t)v.q2;
-                    }
+                    if (lane < ncols)
+                        lf_apply<uint8_t, true>(tile + toff + lane, step, cls, alpha, beta, intra ? 0 : tc0[lane / per]);
                 }
                 ffhip_wave_sync(); /* the next call reads what this one wrote, through other lanes */
             }
@@ -547,7 +524,7 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock_hbd(MbaffLfArgs A, in
             ffhip_wave_sync();
             for (int i = 0; i < n; i++) {
                 const uint32_t w0 = C[3 * i], w1 = C[3 * i + 1];
-                const int toff = (int)(w0 & 0xFFFF), kf = (int)(w0 >> 16) & 255, alpha = (int)(w0 >> 24) << sh, beta = (int)(w1 & 255) << sh;
+                const int toff = (int)(w0 & 0xFFFF), kf = (int)(w0 >> 16) & 255, alpha = (int)(w0 >> 24), beta = (int)(w1 & 255);
                 const bool chroma = kf & 2, intra = kf & 4, hfilt = kf & 1;
                 const int half = (kf >> 4) & 1;
                 const int step = (kf & 8) ? 2 * TP : TP; /* samples from a line of the call to the next */
@@ -559,21 +536,8 @@ __global__ __launch_bounds__(64) void k_h264_mbaff_deblock_hbd(MbaffLfArgs A, in
                     /* h_: the line = row `lane`, its samples one apart; v_: the line = column `lane`, its samples a tile line (or two) apart */
                     uint16_t *c = hfilt ? tile + toff + lane * step : tile + toff + lane;
                     const int xs = hfilt ? 1 : step;
-                    const int t0 = intra ? 0 : (int)tc0[lane / per];
-                    const int tcs = chroma ? (int)(((uint32_t)(t0 - 1) << sh) + 1u) : t0 * (1 << sh);
-                    LfLine v;
-                    v.p1 = c[-2 * xs]; v.p0 = c[-xs]; v.q0 = c[0]; v.q1 = c[xs];
-                    v.p3 = v.p2 = v.q2 = v.q3 = 0;
-                    if (!chroma) {
-                        v.p3 = c[-4 * xs]; v.p2 = c[-3 * xs]; v.q2 = c[2 * xs]; v.q3 = c[3 * xs];
-                    }
-                    const int m = lf_line(v, cls, alpha, beta, tcs, maxv);
-                    if (m & 1)  c[-3 * xs] = (uint16_t)v.p2;
-                    if (m & 2)  c[-2 * xs] = (uint16_t)v.p1;
-                    if (m & 4)  c[-xs] = (uint16_t)v.p0;
-                    if (m & 8)  c[0] = (uint16_t)v.q0;
-                    if (m & 16) c[xs] = (uint16_t)v.q1;
-                    if (m & 32) c[2 * xs] = (uint16_t)v.q2;
+                    const LfDepth D = lf_depth(cls, alpha, beta, intra ? 0 : (int)tc0[lane / per], sh);
+                    lf_apply<uint16_t, true>(c, xs, cls, D.alpha, D.beta, D.tc0, maxv);
                 }
                 ffhip_wave_sync();
             }

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "h264_intra_mb.h"
 #include "h264_kernels.h"
+#include "h264_lf_line.h"
 #include "row_handoff.h"
 
 static_assert(sizeof(FFHipH264IntraC422) == 32, "FFHipH264IntraC422 is a 32-byte record");
@@ -115,28 +116,6 @@ __global__ __launch_bounds__(64) void k_h264_intra_c422(FFHipC422IntraSet S, ptr
 /* ---- the in-loop filter ---- */
 #define C4_TP 16 /* tile pitch in samples: columns -4 .. 7 at [c + 4] */
 template <typename PIX>
-__device__ __forceinline__ void c4_edge(PIX *pix, int xs, bool intra, int alpha, int beta, int tc0, int bd)
-{
-    /* h264_loop_filter_chroma / _chroma_intra (h264dsp_template.c:228-322) on one line */
-    const int p0 = pix[-xs], p1 = pix[-2 * xs], q0 = pix[0], q1 = pix[xs], maxv = (1 << bd) - 1;
-    alpha <<= bd - 8;
-    beta <<= bd - 8;
-    if (!(abs(p0 - q0) < alpha && abs(p1 - p0) < beta && abs(q1 - q0) < beta))
-        return;
-    if (intra) {
-        pix[-xs] = (PIX)((2 * p1 + p0 + q1 + 2) >> 2);
-        pix[0] = (PIX)((2 * q1 + q0 + p1 + 2) >> 2);
-        return;
-    }
-    const int tc = (int)(((unsigned)(tc0 - 1)) << (bd - 8)) + 1;
-    if (tc <= 0)
-        return;
-    const int delta = min(max(((q0 - p0) * 4 + (p1 - q1) + 4) >> 3, -tc), tc);
-    pix[-xs] = (PIX)min(max(p0 + delta, 0), maxv);
-    pix[0] = (PIX)min(max(q0 - delta, 0), maxv);
-}
-
-template <typename PIX>
 __global__ __launch_bounds__(64) void k_h264_deblock_c422(FFHipC422PlaneSet S, ptrdiff_t stride, int mb_w, int mb_h, int *progress, int *fail, int bd)
 {
     uint8_t *const plane = S.plane[blockIdx.y];
@@ -170,15 +149,21 @@ __global__ __launch_bounds__(64) void k_h264_deblock_c422(FFHipC422PlaneSet S, p
         /* vertical edges x = 0, 4: lane = line */
         for (int k = 0; k < 2; k++) {
             const FFHipH264Edge e = ed[k];
-            if (lane < 16 && e.alpha && e.beta && !(k == 0 && mx == 0))
-                c4_edge<PIX>(&tile[(lane + 2) * C4_TP + 4 + 4 * k], 1, e.kind >= 4, e.alpha, e.beta, e.tc0[lane >> 2], bd);
+            if (lane < 16 && e.alpha && e.beta && !(k == 0 && mx == 0)) {
+                const int cls = 1 | (e.kind >= 4) << 1;
+                const LfDepth D = lf_depth(cls, e.alpha, e.beta, e.tc0[lane >> 2], bd - 8);
+                lf_apply<PIX>(&tile[(lane + 2) * C4_TP + 4 + 4 * k], 1, cls, D.alpha, D.beta, D.tc0, (1 << bd) - 1);
+            }
             ffhip_wave_sync();
         }
         /* horizontal edges y = 0, 4, 8, 12: lane = column */
         for (int k = 0; k < 4; k++) {
             const FFHipH264Edge e = ed[2 + k];
-            if (lane < 8 && e.alpha && e.beta && !(k == 0 && my == 0))
-                c4_edge<PIX>(&tile[(4 * k + 2) * C4_TP + 4 + lane], C4_TP, e.kind >= 4, e.alpha, e.beta, e.tc0[lane >> 1], bd);
+            if (lane < 8 && e.alpha && e.beta && !(k == 0 && my == 0)) {
+                const int cls = 1 | (e.kind >= 4) << 1;
+                const LfDepth D = lf_depth(cls, e.alpha, e.beta, e.tc0[lane >> 1], bd - 8);
+                lf_apply<PIX>(&tile[(4 * k + 2) * C4_TP + 4 + lane], C4_TP, cls, D.alpha, D.beta, D.tc0, (1 << bd) - 1);
+            }
             ffhip_wave_sync();
         }
         /* what this macroblock may have changed goes back: its own samples, row -1 above it (p0 of the top edge), and the quad of

@@ -29,24 +29,6 @@
 #include "h264_lf_line.h"
 #include "row_handoff.h"
 
-/* load / filter / store one line through any byte pointer; xs = step across the edge */
-template <typename P>
-__device__ __forceinline__ void lf_apply(P pix, ptrdiff_t xs, int cls, int alpha, int beta, int tc0)
-{
-    LfLine v;
-    const bool luma = !(cls & 1);
-    v.p1 = pix[-2 * xs]; v.p0 = pix[-xs]; v.q0 = pix[0]; v.q1 = pix[xs];
-    v.p2 = luma ? pix[-3 * xs] : 0; v.q2 = luma ? pix[2 * xs] : 0;
-    v.p3 = cls == 2 ? pix[-4 * xs] : 0; v.q3 = cls == 2 ? pix[3 * xs] : 0;
-    const int m = lf_line(v, cls, alpha, beta, tc0);
-    if (m & 1)  pix[-3 * xs] = (uint8_t)v.p2;
-    if (m & 2)  pix[-2 * xs] = (uint8_t)v.p1;
-    if (m & 4)  pix[-xs] = (uint8_t)v.p0;
-    if (m & 8)  pix[0] = (uint8_t)v.q0;
-    if (m & 16) pix[xs] = (uint8_t)v.q1;
-    if (m & 32) pix[2 * xs] = (uint8_t)v.q2;
-}
-
 /* ---- function-level batch ------------------------------------------------------------------------ */
 __global__ __launch_bounds__(256) void k_h264_loop_filter(uint8_t *base, ptrdiff_t stride, const FFHipH264Edge *edges, int n)
 {
@@ -64,17 +46,8 @@ __global__ __launch_bounds__(256) void k_h264_loop_filter(uint8_t *base, ptrdiff
     uint8_t *pix = base + ed.offset + d * ys;
     const int cls = (chroma ? 1 : 0) + (intra ? 2 : 0);
     if (vert_edge && !(reinterpret_cast<uintptr_t>(pix) & 3)) {
-        /* a vertical edge's line is 8 contiguous bytes p3 .. q3: two dwords in, the dwords that changed out (the sample-wise
-         * form below costs up to 8 byte loads and 6 byte stores per lane) */
-        uint32_t *w = reinterpret_cast<uint32_t *>(pix - 4);
-        const uint32_t a = w[0], b = w[1];
-        LfLine v = { (int)(a & 255), (int)((a >> 8) & 255), (int)((a >> 16) & 255), (int)(a >> 24),
-                     (int)(b & 255), (int)((b >> 8) & 255), (int)((b >> 16) & 255), (int)(b >> 24) };
-        const int m = lf_line(v, cls, ed.alpha, ed.beta, tc0);
-        if (m & 7)
-            w[0] = (uint32_t)v.p3 | (uint32_t)v.p2 << 8 | (uint32_t)v.p1 << 16 | (uint32_t)v.p0 << 24;
-        if (m & 56)
-            w[1] = (uint32_t)v.q0 | (uint32_t)v.q1 << 8 | (uint32_t)v.q2 << 16 | (uint32_t)v.q3 << 24;
+        /* a vertical edge's line is 8 contiguous bytes p3 .. q3 */
+        lf_apply_dwords(reinterpret_cast<uint32_t *>(pix - 4), cls, ed.alpha, ed.beta, tc0);
         return;
     }
     lf_apply(pix, xs, cls, ed.alpha, ed.beta, tc0);
@@ -256,7 +229,7 @@ __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t
  *   - a pass keeps its line in REGISTERS across its edges: lane = row for the vertical edges (the row's samples arrive as
  *     dwords), lane = column for the horizontal ones; the tile is touched once per pass, no barrier between edges;
  *   - the macroblock's edge records arrive through SCALAR loads one macroblock ahead: alpha / beta / kind are SGPRs, the
- *     skip and intra decisions are scalar branches, the filters themselves are branch-free (selects, v_sad_u32, v_med3);
+ *     skip decision is a scalar branch, the filter itself is db_edge of h264_lf_line.h (signs, v_sad_u32, v_med3);
  *   - two tiles alternate: the left context of a macroblock is simply the previous tile's last dword column (no copy), and
  *     the store list of a step is FIXED per lane (its rows' first NDW-1 dwords + the previous macroblock's last dword, final
  *     now that this macroblock's left-edge filter has run): one store instruction for the rows, one for the context rows.
@@ -272,70 +245,6 @@ __global__ __launch_bounds__(64) void k_h264_deblock_frame(uint8_t *luma, size_t
  * h264_loopfilter.c:644-700).  Dword-aligned planes only (the byte path stays on k_h264_deblock_frame).
  */
 #define DB_R 16      /* ring slots per row boundary */
-
-__device__ __forceinline__ int db_sad(int a, int b)
-{
-    int d;
-    asm("v_sad_u32 %0, %1, %2, 0" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-
-/* one sample line across one edge, in registers, branch-free; v[0..7] = p3 p2 p1 p0 q0 q1 q2 q3.  Same arithmetic as lf_line
- * (h264dsp_template.c:104-330): `if (tc0) p1 += clip(..., -tc0, tc0)` is the unconditional form because the clip range is empty
- * when tc0 == 0. */
-template <bool CHROMA>
-__device__ __forceinline__ void db_normal(int (&v)[8], int alpha, int beta, int tc0, int en = 1)
-{
-    const int p2 = v[1], p1 = v[2], p0 = v[3], q0 = v[4], q1 = v[5], q2 = v[6];
-    /* `&`, not `&&`: no short-circuit control flow — the lanes of an edge take every path anyway */
-    int c = en & (int)(db_sad(p0, q0) < alpha) & (int)(db_sad(p1, p0) < beta) & (int)(db_sad(q1, q0) < beta);
-    if (CHROMA) {
-        c &= (int)(tc0 > 0);
-        const int delta = clip3((((q0 - p0) * 4) + (p1 - q1) + 4) >> 3, -tc0, tc0);
-        v[3] = c ? clip3(p0 + delta, 0, 255) : p0;
-        v[4] = c ? clip3(q0 - delta, 0, 255) : q0;
-        return;
-    }
-    c &= (int)(tc0 >= 0);
-    const int ap = db_sad(p2, p0) < beta, aq = db_sad(q2, q0) < beta;
-    const int avg = (p0 + q0 + 1) >> 1;
-    const int dp = clip3(((p2 + avg) >> 1) - p1, -tc0, tc0), dq = clip3(((q2 + avg) >> 1) - q1, -tc0, tc0);
-    const int tc = tc0 + ap + aq;
-    const int delta = clip3((((q0 - p0) * 4) + (p1 - q1) + 4) >> 3, -tc, tc);
-    v[2] = (c & ap) ? p1 + dp : p1;
-    v[5] = (c & aq) ? q1 + dq : q1;
-    v[3] = c ? clip3(p0 + delta, 0, 255) : p0;
-    v[4] = c ? clip3(q0 - delta, 0, 255) : q0;
-}
-
-template <bool CHROMA>
-__device__ __forceinline__ void db_intra(int (&v)[8], int alpha, int beta, int en = 1)
-{
-    const int p3 = v[0], p2 = v[1], p1 = v[2], p0 = v[3], q0 = v[4], q1 = v[5], q2 = v[6], q3 = v[7];
-    const int d0 = db_sad(p0, q0);
-    const int c = en & (int)(d0 < alpha) & (int)(db_sad(p1, p0) < beta) & (int)(db_sad(q1, q0) < beta);
-    const int wp0 = (2 * p1 + p0 + q1 + 2) >> 2, wq0 = (2 * q1 + q0 + p1 + 2) >> 2; /* the weak forms */
-    if (CHROMA) {
-        v[3] = c ? wp0 : p0;
-        v[4] = c ? wq0 : q0;
-        return;
-    }
-    const int strong = d0 < ((alpha >> 2) + 2);
-    const int sp = c & strong & (int)(db_sad(p2, p0) < beta), sq = c & strong & (int)(db_sad(q2, q0) < beta);
-    const int s4 = p0 + q0;
-    /* every candidate value is computed first and made opaque: with the arithmetic visible behind the selects the compiler sinks it
-     * into divergent branches (exec-mask bookkeeping around three-instruction blocks) instead of emitting v_cndmask */
-    int sp0 = (p2 + 2 * p1 + 2 * s4 + q1 + 4) >> 3, sp1 = (p2 + p1 + s4 + 2) >> 2, sp2 = (2 * p3 + 3 * p2 + p1 + s4 + 4) >> 3;
-    int sq0 = (p1 + 2 * s4 + 2 * q1 + q2 + 4) >> 3, sq1 = (s4 + q1 + q2 + 2) >> 2, sq2 = (2 * q3 + 3 * q2 + q1 + s4 + 4) >> 3;
-    int w0 = c ? wp0 : p0, w1 = c ? wq0 : q0;
-    asm("" : "+v"(sp0), "+v"(sp1), "+v"(sp2), "+v"(sq0), "+v"(sq1), "+v"(sq2), "+v"(w0), "+v"(w1));
-    v[3] = sp ? sp0 : w0;
-    v[2] = sp ? sp1 : p1;
-    v[1] = sp ? sp2 : p2;
-    v[4] = sq ? sq0 : w1;
-    v[5] = sq ? sq1 : q1;
-    v[6] = sq ? sq2 : q2;
-}
 
 typedef uint32_t db_u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t db_u8 __attribute__((ext_vector_type(8)));
@@ -486,10 +395,7 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
                 const int alpha = (rec >> 8) & 255, beta = (rec >> 16) & 255;
                 if (alpha && beta && !(k == 0 && mx == 0)) { /* scalar */
                     int v[8] = { x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3], x[4 * k + 4], x[4 * k + 5], x[4 * k + 6], x[4 * k + 7] };
-                    if ((rec & 255) >= 4)
-                        db_intra<CHROMA>(v, alpha, beta);
-                    else
-                        db_normal<CHROMA>(v, alpha, beta, (int)(int8_t)(tcw >> tcsh));
+                    db_edge<CHROMA>(v, rec, tcw, tcsh, false);
 #pragma unroll
                     for (int i = 1; i < 7; i++)
                         x[4 * k + i] = v[i];
@@ -549,10 +455,7 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
                 const int alpha = (rec >> 8) & 255, beta = (rec >> 16) & 255;
                 if (alpha && beta && !(k == 0 && my == 0)) {
                     int v[8] = { y[4 * k], y[4 * k + 1], y[4 * k + 2], y[4 * k + 3], y[4 * k + 4], y[4 * k + 5], y[4 * k + 6], y[4 * k + 7] };
-                    if ((rec & 255) >= 4)
-                        db_intra<CHROMA>(v, alpha, beta);
-                    else
-                        db_normal<CHROMA>(v, alpha, beta, (int)(int8_t)(tcw >> tcsh));
+                    db_edge<CHROMA>(v, rec, tcw, tcsh, false);
 #pragma unroll
                     for (int i = 1; i < 7; i++)
                         y[4 * k + i] = v[i];
@@ -618,101 +521,8 @@ __global__ __launch_bounds__(64 * DB_W) void k_h264_deblock_band(uint8_t *plane,
  * A picture's bands sit on ONE XCD (block L -> XCD L & 7: picture f on XCD f & 7), so the hand-off traffic of a picture stays in
  * one L2 and eight pictures run side by side on the eight XCDs.
  * Needs 16-byte (chroma: 8-byte) aligned planes / strides / pitches and 16-byte aligned edge records; anything else takes the
- * band kernel (4-byte aligned) or the row kernel.
+ * band kernel (4-byte aligned) or the row kernel.  The edge filter is db_edge, the register form of h264_lf_line.h.
  */
-/* ---- the skewed-rows kernel's edge filter ----------------------------------------------------------
- * A wave that is alone on its SIMD issues ONE instruction every four cycles, scalar or vector, and a step of the wavefront is eight
- * DEPENDENT edges: the filter is written for the fewest instructions, not for the fewest operations.
- *   - every comparison of h264dsp_template.c:104-330 is a sign: |a - b| < t  <=>  v_sad_u32(a, b, -t) < 0, and a conjunction is the
- *     sign of a maximum (v_max3_i32) — no compare / s_and chains, no exec-mask control flow;
- *   - alpha == 0 or beta == 0 (a bS = 0 edge) disables itself: |a - b| - 0 is never negative;
- *   - clips are v_med3_i32 (lanes whose range is empty, tc0 < 0, are deselected anyway);
- *   - the bS = 4 filter runs behind one wave-uniform branch and overrides the lanes it owns from the ORIGINAL samples.
- * v[0..7] = p3 p2 p1 p0 q0 q1 q2 q3 of one line; rec = {bS, alpha, beta, -} bytes, tcw = the edge's four tc0 bytes. */
-__device__ __forceinline__ int db_sad3(int a, int b, int c)
-{
-    int d;
-    asm("v_sad_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ int db_med3(int a, int lo, int hi)
-{
-    int d;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(lo), "v"(hi));
-    return d;
-}
-__device__ __forceinline__ int db_clip255(int a)
-{
-    int d;
-    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(d) : "v"(a), "s"(255));
-    return d;
-}
-__device__ __forceinline__ int db_max3(int a, int b, int c)
-{
-    int d;
-    asm("v_max3_i32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-
-/* sh = bit depth - 8: alpha, beta and tc0 arrive in 8-bit units and are scaled as h264dsp_template.c:104-330 scales them (alpha, beta
- * << sh; luma tc0 * (1 << sh); chroma ((tc0 - 1) << sh) + 1); maxv = 2^depth - 1 */
-template <bool CHROMA>
-__device__ __forceinline__ void db_edge(int (&v)[8], uint32_t rec, uint32_t tcw, int tcsh, bool skip, int sh = 0, int maxv = 255)
-{
-    const int p3 = v[0], p2 = v[1], p1 = v[2], p0 = v[3], q0 = v[4], q1 = v[5], q2 = v[6], q3 = v[7];
-    const int alpha = (int)((rec >> 8) & 255) << sh, negb = -((int)((rec >> 16) & 255) << sh);
-    const int nega = skip ? 0 : -alpha;                       /* a picture edge: never filtered */
-    const int tc8 = __builtin_amdgcn_sbfe(tcw, tcsh, 8);
-    const int tc0 = CHROMA ? (tc8 - 1) * (1 << sh) + 1 : tc8 * (1 << sh);
-    const bool is4 = (rec & 255) >= 4;
-    /* m < 0: |p0 - q0| < alpha && |p1 - p0| < beta && |q1 - q0| < beta */
-    const int m = db_max3(db_sad3(p0, q0, nega), db_sad3(p1, p0, negb), db_sad3(q1, q0, negb));
-    const int mn = max(m, CHROMA ? -tc0 : ~tc0);              /* ... && tc0 > 0 (chroma) / tc0 >= 0 (luma): the bS < 4 filter's lanes */
-    {   /* the bS < 4 filter, every lane (four macroblocks of different rows share an instruction: they are rarely all bS = 0, and a
-         * wave-uniform skip costs register copies on both paths) */
-        const int x4 = ((q0 - p0) << 2) + (p1 - q1) + 4;
-        if (CHROMA) {
-            const int delta = (mn >> 31) & db_med3(x4 >> 3, -tc0, tc0);
-            v[3] = db_med3(p0 + delta, 0, maxv);
-            v[4] = db_med3(q0 - delta, 0, maxv);
-        } else {
-            const int dap = db_sad3(p2, p0, negb), daq = db_sad3(q2, q0, negb);     /* < 0: |p2 - p0| < beta */
-            const int avg = (p0 + q0 + 1) >> 1, ntc0 = -tc0;
-            const int dp = db_med3(((p2 + avg) >> 1) - p1, ntc0, tc0), dq = db_med3(((q2 + avg) >> 1) - q1, ntc0, tc0);
-            const int tc = tc0 + (int)((uint32_t)dap >> 31) + (int)((uint32_t)daq >> 31);
-            const int delta = (mn >> 31) & db_med3(x4 >> 3, -tc, tc);
-            v[2] = p1 + (dp & (max(mn, dap) >> 31));
-            v[5] = q1 + (dq & (max(mn, daq) >> 31));
-            v[3] = db_med3(p0 + delta, 0, maxv);
-            v[4] = db_med3(q0 - delta, 0, maxv);
-        }
-    }
-    const int mi = is4 ? m : 0;                               /* < 0: a bS = 4 line that passes the alpha / beta test */
-    if (__builtin_amdgcn_ballot_w64(mi < 0)) {
-        const int wp0 = (2 * p1 + p0 + q1 + 2) >> 2, wq0 = (2 * q1 + q0 + p1 + 2) >> 2;   /* the weak forms */
-        if (CHROMA) {
-            v[3] = mi < 0 ? wp0 : v[3];
-            v[4] = mi < 0 ? wq0 : v[4];
-        } else {
-            const int ds = db_sad3(p0, q0, -((alpha >> 2) + 2));                        /* < 0: the strong filter */
-            const int msp = db_max3(mi, ds, db_sad3(p2, p0, negb)), msq = db_max3(mi, ds, db_sad3(q2, q0, negb));
-            const int s4 = p0 + q0, ep = p1 + s4, eq = q1 + s4;
-            int sp0 = (2 * ep + p2 + q1 + 4) >> 3, sp1 = (p2 + ep + 2) >> 2, sp2 = (2 * (p3 + p2) + p2 + ep + 4) >> 3;
-            int sq0 = (2 * eq + q2 + p1 + 4) >> 3, sq1 = (q2 + eq + 2) >> 2, sq2 = (2 * (q3 + q2) + q2 + eq + 4) >> 3;
-            int w0 = mi < 0 ? wp0 : v[3], w1 = mi < 0 ? wq0 : v[4], w2 = mi < 0 ? p1 : v[2], w3 = mi < 0 ? q1 : v[5];
-            /* every candidate first, opaque: with the arithmetic visible behind the selects the compiler sinks it into divergent
-             * branches (exec-mask bookkeeping around three-instruction blocks) instead of emitting v_cndmask */
-            asm("" : "+v"(sp0), "+v"(sp1), "+v"(sp2), "+v"(sq0), "+v"(sq1), "+v"(sq2), "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3));
-            v[3] = msp < 0 ? sp0 : w0;
-            v[2] = msp < 0 ? sp1 : w2;
-            v[1] = msp < 0 ? sp2 : p2;
-            v[4] = msq < 0 ? sq0 : w1;
-            v[5] = msq < 0 ? sq1 : w3;
-            v[6] = msq < 0 ? sq2 : q2;
-        }
-    }
-}
-
 #ifndef DB_SKEW
 #define DB_SKEW 1
 #endif

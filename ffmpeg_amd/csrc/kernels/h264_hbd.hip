@@ -20,6 +20,7 @@
  */
 #include "common.h"
 #include "h264_kernels.h"
+#include "h264_lf_line.h"
 
 namespace {
 
@@ -273,66 +274,9 @@ __global__ __launch_bounds__(256) void k_h264_loop_filter_hbd(uint8_t *base, ptr
     const int maxv = (1 << bd) - 1, sh = bd - 8;
     /* the record holds alpha / beta as the decoder's tables do (bytes); the host faces pass the caller's ints through `ab`, whatever
      * they are (checkasm hands the functions values far outside the tables' range) */
-    const int alpha = (int)((unsigned)(ab ? ab[2 * e] : (int)ed.alpha) << sh), beta = (int)((unsigned)(ab ? ab[2 * e + 1] : (int)ed.beta) << sh);
-    const int p0 = pix[-xs], p1 = pix[-2 * xs], q0 = pix[0], q1 = pix[xs];
-    if (!(abs(p0 - q0) < alpha && abs(p1 - p0) < beta && abs(q1 - q0) < beta))
-        return;
-    if (intra) {
-        if (chroma) {
-            pix[-xs] = (P)((2 * p1 + p0 + q1 + 2) >> 2);
-            pix[0] = (P)((2 * q1 + q0 + p1 + 2) >> 2);
-            return;
-        }
-        const int p2 = pix[-3 * xs], q2 = pix[2 * xs];
-        if (abs(p0 - q0) < ((alpha >> 2) + 2)) {
-            if (abs(p2 - p0) < beta) {
-                const int p3 = pix[-4 * xs];
-                pix[-xs] = (P)((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3);
-                pix[-2 * xs] = (P)((p2 + p1 + p0 + q0 + 2) >> 2);
-                pix[-3 * xs] = (P)((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3);
-            } else
-                pix[-xs] = (P)((2 * p1 + p0 + q1 + 2) >> 2);
-            if (abs(q2 - q0) < beta) {
-                const int q3 = pix[3 * xs];
-                pix[0] = (P)((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3);
-                pix[xs] = (P)((p0 + q0 + q1 + q2 + 2) >> 2);
-                pix[2 * xs] = (P)((2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3);
-            } else
-                pix[0] = (P)((2 * q1 + q0 + p1 + 2) >> 2);
-        } else {
-            pix[-xs] = (P)((2 * p1 + p0 + q1 + 2) >> 2);
-            pix[0] = (P)((2 * q1 + q0 + p1 + 2) >> 2);
-        }
-        return;
-    }
-    const int t0 = ed.tc0[d / inner];
-    if (chroma) {
-        const int tc = (int)(((unsigned)t0 - 1U) << sh) + 1;
-        if (tc <= 0)
-            return;
-        const int delta = clip3(((q0 - p0) * 4 + (p1 - q1) + 4) >> 3, -tc, tc);
-        pix[-xs] = (P)hclip(p0 + delta, maxv);
-        pix[0] = (P)hclip(q0 - delta, maxv);
-        return;
-    }
-    const int tc_orig = t0 * (1 << sh);
-    if (tc_orig < 0)
-        return;
-    const int p2 = pix[-3 * xs], q2 = pix[2 * xs];
-    int tc = tc_orig;
-    if (abs(p2 - p0) < beta) {
-        if (tc_orig)
-            pix[-2 * xs] = (P)(p1 + clip3(((p2 + ((p0 + q0 + 1) >> 1)) >> 1) - p1, -tc_orig, tc_orig));
-        tc++;
-    }
-    if (abs(q2 - q0) < beta) {
-        if (tc_orig)
-            pix[xs] = (P)(q1 + clip3(((q2 + ((p0 + q0 + 1) >> 1)) >> 1) - q1, -tc_orig, tc_orig));
-        tc++;
-    }
-    const int delta = clip3((((q0 - p0) * 4) + (p1 - q1) + 4) >> 3, -tc, tc);
-    pix[-xs] = (P)hclip(p0 + delta, maxv);
-    pix[0] = (P)hclip(q0 - delta, maxv);
+    const int cls = (chroma ? 1 : 0) + (intra ? 2 : 0);
+    const LfDepth D = lf_depth(cls, ab ? ab[2 * e] : (int)ed.alpha, ab ? ab[2 * e + 1] : (int)ed.beta, intra ? 0 : ed.tc0[d / inner], sh);
+    lf_apply<P, true>(pix, xs, cls, D.alpha, D.beta, D.tc0, maxv);
 }
 
 /* ---- luma qpel: a lane per output sample (16 lanes per row of a 16-wide block) --------------------------------------------- */

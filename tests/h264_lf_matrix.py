@@ -1,8 +1,8 @@
 """The cells of the H.264 in-loop filter as deterministic lists, shared by tests/test_h264_lf_matrix_cpu.py and
-tests/test_gpu_h264_lf_matrix.py.  h264dsp_template.c:104-330 exists several times in this tree, each written separately: lf_line
-(kernels/h264_lf_line.h: k_h264_loop_filter, the row kernel k_h264_deblock_frame, the MBAFF kernels), db_normal / db_intra
-(k_h264_deblock_band), db_edge (k_h264_deblock_skew at every depth), the inline form of k_h264_loop_filter_hbd and c4_edge
-(k_h264_deblock_c422).  Nothing here is random but the seeded background of the buffers.
+tests/test_gpu_h264_lf_matrix.py.  h264dsp_template.c:104-330 is written twice in this tree, both times in kernels/h264_lf_line.h:
+lf_line (branching: k_h264_loop_filter, k_h264_loop_filter_hbd, the row kernel k_h264_deblock_frame, k_h264_deblock_c422, the MBAFF
+kernels) and db_edge (in registers: k_h264_deblock_skew at every depth, k_h264_deblock_band); every kernel is still a route of its
+own here, with its own loads, stores and lane maps.  Nothing here is random but the seeded background of the buffers.
 
 A *cell* is one 8-sample line p3 p2 p1 p0 q0 q1 q2 q3 built by construction with its class (0 luma, 1 chroma, 2 luma intra, 3 chroma
 intra), alpha, beta and tc0 in the 8-bit units the decoder passes, the label it is built for and the output indices that must

@@ -17,9 +17,9 @@ HIP_PER_CU = 8        # no constant of the launcher (it has no cap): the workgro
 VP8_MAX_MB = 1024     # the faces' limit on mb_w and mb_h, shims_vp8_recon.hip:45 and shims_vp8.hip:274
 CHUNK = 64            # records per ballot of the intra search, vp8_recon_frame.hip:318
 DB_PTRS = 32          # FFHIP_DB_PTRS, ffmpeg_amd/csrc/kernels/h264_kernels.h:78
-DB_BAND_ROWS = 2048   # frames x rows above which the band kernel takes 16 rows a band, ffmpeg_amd/csrc/kernels/h264_deblock.hip:1020
-DB_XCD_SIMDS = 128    # the SIMDs of one XCD shared by its pictures, h264_deblock.hip:1056
-DB_XCDS = 8           # h264_deblock.hip:1055, :1060
+DB_BAND_ROWS = 2048   # frames x rows above which the band kernel takes 16 rows a band, ffmpeg_amd/csrc/kernels/h264_deblock.hip:830
+DB_XCD_SIMDS = 128    # the SIMDs of one XCD shared by its pictures, h264_deblock.hip:866
+DB_XCDS = 8           # h264_deblock.hip:865, :870
 INTRA_PICS = 32       # FFHIP_INTRA_PICS, h264_kernels.h:58
 INTRA_SPLIT_WGS = 576 # workgroups up to which chroma gets a wavefront of its own, ffmpeg_amd/csrc/kernels/h264_intra.hip:404
 INTRA_LDS = 64 * 1024 # the LDS a workgroup of k_h264_intra_frame may take, h264_intra.hip:393
@@ -107,7 +107,7 @@ def _cdiv(a, b):
     return -(-a // b)
 
 
-# ---- H.264 frame-order deblocking: deblock_frames(), ffmpeg_amd/csrc/kernels/h264_deblock.hip:980-1084 ----------------------------
+# ---- H.264 frame-order deblocking: deblock_frames(), ffmpeg_amd/csrc/kernels/h264_deblock.hip:790-894 ----------------------------
 def h264_deblock(mb_w, mb_h, nf, cus=256, chroma=False, bd=8, align=16, edges_align=16, ptrs=False):
     """what deblock_frames() does with nf pictures of mb_w x mb_h macroblocks.  align: the largest power of two (up to 16) that
     divides the plane's address, the stride and the frame pitch; edges_align: the same of the edge records' address; ptrs: pictures by
@@ -115,44 +115,44 @@ def h264_deblock(mb_w, mb_h, nf, cus=256, chroma=False, bd=8, align=16, edges_al
     Returns None for a call the launcher refuses, else a dict: kernel ('skew' / 'band' / 'row'), bw, nbands, per_frame, launches
     (frames of each launch) and grids (one per launch); for skew also, per launch, wpb, per_xcd, bwaves, wgs (workgroups a picture),
     superbands and walked (the fewest, the most super-bands a workgroup of a picture walks)."""
-    aligned = align % 4 == 0                                            # :998
-    if chroma and not aligned:                                          # :999-1002
+    aligned = align % 4 == 0                                            # :808
+    if chroma and not aligned:                                          # :809-812
         return None
-    amask = 8 if chroma and bd == 8 else 16                             # :1008
-    skew = align % amask == 0 and edges_align % 16 == 0                 # :1009 (no FFHIP_DEBLOCK_OLD in the product build)
-    if bd > 8 and not skew:                                             # :1010-1013
+    amask = 8 if chroma and bd == 8 else 16                             # :818
+    skew = align % amask == 0 and edges_align % 16 == 0                 # :819 (no FFHIP_DEBLOCK_OLD in the product build)
+    if bd > 8 and not skew:                                             # :820-823
         return None
-    band = not skew and aligned                                         # :1014
-    bw = (8 if chroma else 4) if skew else 16 if nf * mb_h > DB_BAND_ROWS else 4     # :1019-1020
-    nbands = _cdiv(mb_h, bw)                                            # :1021
-    per_frame = nbands if band or skew else mb_h + 1                    # :1022
-    if per_frame > SLOT_INTS or (ptrs and not skew):                    # :1023-1031
+    band = not skew and aligned                                         # :824
+    bw = (8 if chroma else 4) if skew else 16 if nf * mb_h > DB_BAND_ROWS else 4     # :829-830
+    nbands = _cdiv(mb_h, bw)                                            # :831
+    per_frame = nbands if band or skew else mb_h + 1                    # :832
+    if per_frame > SLOT_INTS or (ptrs and not skew):                    # :833-841
         return None
-    per_launch = SLOT_INTS // per_frame                                 # :1032
+    per_launch = SLOT_INTS // per_frame                                 # :842
     if ptrs:
-        per_launch = min(per_launch, DB_PTRS)                           # :1033-1034
-    launches = _split(nf, per_launch)                                   # :1035-1036
+        per_launch = min(per_launch, DB_PTRS)                           # :843-844
+    launches = _split(nf, per_launch)                                   # :845-846
     d = dict(kernel="skew" if skew else "band" if band else "row", bw=bw, nbands=nbands, per_frame=per_frame, per_launch=per_launch,
              launches=launches, last_band_rows=mb_h - (nbands - 1) * bw)
     if not skew:
-        d["grids"] = [(nbands, n) if band else (mb_h, n) for n in launches]         # :1073, :1072
+        d["grids"] = [(nbands, n) if band else (mb_h, n) for n in launches]         # :883, :882
         d["threads"] = 64 * bw if band else 64
         return d
-    wpb = 3 if bd > 8 and not chroma else 4                             # :1052-1054
+    wpb = 3 if bd > 8 and not chroma else 4                             # :862-864
     d.update(wpb=wpb, superbands=_cdiv(nbands, wpb), idle_waves=_cdiv(nbands, wpb) * wpb - nbands, per_xcd=[], bwaves=[], wgs=[], grids=[],
              walked=[], floor_wins=[])
     for n in launches:
-        per_xcd = _cdiv(n, DB_XCDS)                                     # :1055
-        bwaves, floor = DB_XCD_SIMDS // per_xcd, _cdiv(nbands, 4)      # :1056-1057
+        per_xcd = _cdiv(n, DB_XCDS)                                     # :865
+        bwaves, floor = DB_XCD_SIMDS // per_xcd, _cdiv(nbands, 4)      # :866-867
         d["floor_wins"].append(bwaves < floor)
-        bwaves = min(max(bwaves, floor), nbands)                        # :1057-1058
-        bwaves = _cdiv(bwaves, wpb) * wpb                               # :1059
+        bwaves = min(max(bwaves, floor), nbands)                        # :867-868
+        bwaves = _cdiv(bwaves, wpb) * wpb                               # :869
         wgs = bwaves // wpb
         d["per_xcd"].append(per_xcd)
         d["bwaves"].append(bwaves)
         d["wgs"].append(wgs)
-        d["grids"].append(DB_XCDS * wgs * per_xcd)                      # :1060; blocks of pictures f >= n leave at once, :759-761
-        d["walked"].append((d["superbands"] // wgs, _cdiv(d["superbands"], wgs)))   # :774: sb = sb0, sb0 + wgs, ...
+        d["grids"].append(DB_XCDS * wgs * per_xcd)                      # :870; blocks of pictures f >= n leave at once, :569-571
+        d["walked"].append((d["superbands"] // wgs, _cdiv(d["superbands"], wgs)))   # :584: sb = sb0, sb0 + wgs, ...
     d["threads"] = 64 * wpb
     return d
 

@@ -157,7 +157,7 @@ def test_frame_faces(face, chroma, bd, monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bd", [8, 10])
 def test_c422_object(bd):
-    """k_h264_deblock_c422 (c4_edge) through h264.Picture(chroma_format=2).deblock_mb() and flush() on planes 1 and 2: the four cell
+    """k_h264_deblock_c422 (lf_line) through h264.Picture(chroma_format=2).deblock_mb() and flush() on planes 1 and 2: the four cell
     pictures and a mixed one per plane, Cb and Cr holding different ones, against ffo_h264_deblock_frame_c422_bd; luma carries no
     record and must not change"""
     from ffmpeg_amd import h264

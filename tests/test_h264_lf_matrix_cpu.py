@@ -325,7 +325,7 @@ def test_mutations_change_a_cell_on_every_route(bd):
 @pytest.mark.parametrize("bd", M.MEMBER_DEPTHS)
 def test_unobservable_changes(bd):
     """the `if (tc_orig)` guard of the p1 / q1 corrections and chroma's `tc <= 0` against `tc < 0` cannot show in any output: over every
-    cell in every tc0 slot, and by the arithmetic itself - which is why db_normal and db_edge may drop the guard"""
+    cell in every tc0 slot, and by the arithmetic itself - which is why db_edge may drop the guard"""
     sh = bd - 8
     for mut in M.UNOBSERVABLE:
         for c in M.cells(bd):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_deblock.py — frame-order luma deblocking of 4K planes: per-frame time vs frames per launch.  DB_DEPTH=10 (9 / 12 / 14):
-the same at that depth (uint16 samples) through ffhip_h264_deblock_frames_dev_hbd."""
+the same at that depth (uint16 samples) through ffhip_h264_deblock_frames_dev_hbd.  DB_PAD=n (8 bits): planes whose stride is n samples
+wider than the picture (default 0) - 4 gives strides of 3844 and 1924, multiples of 4 off the 16 / 8 grid, which take k_h264_deblock_band."""
 import json
 import os
 import sys
@@ -33,6 +34,7 @@ else:
 ed["tc"] = rng.integers(0, 4, (ed.size, 4))
 ded = torch.from_numpy(ed.view(np.uint8).reshape(-1, 12)).to(dev)
 depth = int(os.environ.get("DB_DEPTH", "8"))
+pad = int(os.environ.get("DB_PAD", "0"))
 if depth > 8:
     for nf in (1, 8, 32):
         batch = (torch.randint(100, 140, (nf, h, w), dtype=torch.int32, device=dev) << (depth - 8)).to(torch.int16)
@@ -47,12 +49,12 @@ if depth > 8:
         print(json.dumps({"depth": depth, "frames_per_launch": nf, "ms": round(ms, 3), "ms_per_frame": round(ms / nf, 4), "Gpixel/s": round(nf * w * h / ms / 1e6, 2)}), flush=True)
     sys.exit(0)
 for nf in (1, 2, 4, 8, 16, 32, 64):
-    batch = torch.randint(100, 140, (nf, h, w), dtype=torch.uint8, device=dev)
+    batch = torch.randint(100, 140, (nf, h, w + pad), dtype=torch.uint8, device=dev)
     dd = ded.repeat(nf, 1)
-    h264.deblock_frames(batch, w * h, nf, w, mbw, mbh, dd)
+    h264.deblock_frames(batch, (w + pad) * h, nf, w + pad, mbw, mbh, dd)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    h264.deblock_frames(batch, w * h, nf, w, mbw, mbh, dd)
+    h264.deblock_frames(batch, (w + pad) * h, nf, w + pad, mbw, mbh, dd)
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
@@ -68,12 +70,12 @@ edc["k"] = kc.ravel()
 edc["tc"] = rng.integers(0, 4, (edc.size, 4))
 dedc = torch.from_numpy(edc.view(np.uint8).reshape(-1, 12)).to(dev)
 for nf in (1, 8, 32, 64):
-    batch = torch.randint(100, 140, (nf, ch, cw), dtype=torch.uint8, device=dev)
+    batch = torch.randint(100, 140, (nf, ch, cw + pad), dtype=torch.uint8, device=dev)
     dd = dedc.repeat(nf, 1)
-    h264.deblock_frames_chroma(batch, cw * ch, nf, cw, mbw, mbh, dd)
+    h264.deblock_frames_chroma(batch, (cw + pad) * ch, nf, cw + pad, mbw, mbh, dd)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    h264.deblock_frames_chroma(batch, cw * ch, nf, cw, mbw, mbh, dd)
+    h264.deblock_frames_chroma(batch, (cw + pad) * ch, nf, cw + pad, mbw, mbh, dd)
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
