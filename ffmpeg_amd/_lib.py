@@ -313,6 +313,10 @@ def lib():
         "ffhip_h264_inter_pic_record_size": (C.c_int, []),
         "ffhip_h264_inter_plan_record_size": (C.c_int, []),
         "ffhip_h264_inter_plan_pic_record_size": (C.c_int, []),
+        "ffhip_h264_residual_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_h264_residual_pictures_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "ffhip_h264_res_mb_record_size": (C.c_int, []),
+        "ffhip_h264_res_pic_record_size": (C.c_int, []),
         "ffhip_hevc_residual_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_hevc_res_tu_record_size": (C.c_int, []),
         "ffhip_fdsp_batch_dev": (C.c_int, [C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_float, C.c_int,

@@ -130,6 +130,9 @@ int ffhip_launch_h264_edge_params_pictures(int mb_w, int mb_h, int field, int qp
 /* H.264 inter prediction of whole pictures (h264_inter_pic.hip), arguments validated by ffhip_h264_inter_pictures_dev() */
 int ffhip_launch_h264_inter_pictures(int bd, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264InterPic *pics,
                                      hipStream_t stream);
+/* H.264 residuals of whole pictures (h264_res_pic.hip), arguments validated by ffhip_h264_residual_pictures_dev() */
+int ffhip_launch_h264_residual_pictures(int bd, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264ResPic *pics,
+                                        hipStream_t stream);
 /* HEVC residuals of whole pictures (hevc_res_pic.hip),arguments validated by ffhip_hevc_residual_pictures_dev() */
 int ffhip_launch_hevc_residual_pictures(int bd, int chroma_format_idc, int npics, const FFHipHevcResPic *pics, hipStream_t stream);
 int ffhip_launch_hevc_loop_filter(uint8_t *base, ptrdiff_t stride, const FFHipHevcEdge *edges, int n, hipStream_t stream);

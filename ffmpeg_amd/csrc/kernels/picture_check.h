@@ -62,6 +62,47 @@ private:
     std::vector<FFHipSpan> v;
 };
 
+/* ---- rows: where two planes may interleave (the two fields of a frame) a span says too little ------------- */
+/* `rows` rows of `row_bytes` bytes, `stride` bytes (of any sign) apart */
+struct FFHipRows {
+    uintptr_t base;
+    ptrdiff_t stride, row_bytes;
+    int rows;
+    FFHipSpan span() const
+    {
+        const uintptr_t last = base + (uintptr_t)((ptrdiff_t)(rows - 1) * stride);
+        return { std::min(base, last), std::max(base, last) + (uintptr_t)row_bytes };
+    }
+};
+/* Does a row of `a` share a byte with a row of `b`?  Disjoint spans: no.  Equal strides s: the rows of both lie on one lattice of
+ * pitch |s|; with d = (b.base - a.base) mod |s| they are disjoint iff d >= a.row_bytes and d + b.row_bytes <= |s| (the two fields of a
+ * frame).  Overlapping spans with unequal strides count as shared. */
+inline bool ffhip_rows_share(const FFHipRows &a, const FFHipRows &b)
+{
+    const FFHipSpan sa = a.span(), sb = b.span();
+    if (sa.hi <= sb.lo || sb.hi <= sa.lo)
+        return false;
+    if (a.stride != b.stride || a.stride == 0)
+        return true;
+    const uintptr_t s = (uintptr_t)(a.stride < 0 ? -a.stride : a.stride);
+    const uintptr_t d = (b.base >= a.base ? (b.base - a.base) % s : (s - (a.base - b.base) % s) % s);
+    return !(d >= (uintptr_t)a.row_bytes && d + (uintptr_t)b.row_bytes <= s);
+}
+/* Do two of the destination planes share a byte of a row?  The span set sorts out the calls whose spans are disjoint before the
+ * pairwise rule; `out` is left sealed over the planes' spans for the caller's hits() */
+inline bool ffhip_any_rows_share(const std::vector<FFHipRows> &dst, FFHipSpanSet &out)
+{
+    out.reserve(dst.size());
+    for (const FFHipRows &d : dst)
+        out.add(d.span());
+    if (out.seal())
+        for (size_t a = 0; a < dst.size(); a++)
+            for (size_t b = a + 1; b < dst.size(); b++)
+                if (ffhip_rows_share(dst[a], dst[b]))
+                    return true;
+    return false;
+}
+
 /* ---- the arguments the faces share: `who` names the face in the message; 0 or FFHIP_EINVAL ---------------- */
 inline int ffhip_check_count(const char *who, int npics, const void *pics, const char *what /* "picture" or "frame" */)
 {

@@ -37,32 +37,6 @@ int check_maps(const char *who, int i, int mb_w, const void *mb, const void *mvf
     return 0;
 }
 
-/* `rows` rows of `row_bytes` bytes, `stride` bytes (of any sign) apart */
-struct Rows {
-    uintptr_t base;
-    ptrdiff_t stride, row_bytes;
-    int rows;
-    FFHipSpan span() const
-    {
-        const uintptr_t last = base + (uintptr_t)((ptrdiff_t)(rows - 1) * stride);
-        return { std::min(base, last), std::max(base, last) + (uintptr_t)row_bytes };
-    }
-};
-/* Does a row of `a` share a byte with a row of `b`?  Disjoint spans: no.  Equal strides s: the rows of both lie on one lattice of
- * pitch |s|; with d = (b.base - a.base) mod |s| they are disjoint iff d >= a.row_bytes and d + b.row_bytes <= |s| (the two fields of a
- * frame).  Overlapping spans with unequal strides count as shared. */
-bool rows_share(const Rows &a, const Rows &b)
-{
-    const FFHipSpan sa = a.span(), sb = b.span();
-    if (sa.hi <= sb.lo || sb.hi <= sa.lo)
-        return false;
-    if (a.stride != b.stride || a.stride == 0)
-        return true;
-    const uintptr_t s = (uintptr_t)(a.stride < 0 ? -a.stride : a.stride);
-    const uintptr_t d = (b.base >= a.base ? (b.base - a.base) % s : (s - (a.base - b.base) % s) % s);
-    return !(d >= (uintptr_t)a.row_bytes && d + (uintptr_t)b.row_bytes <= s);
-}
-
 int check_dev(const char *who, int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264InterPic *pics)
 {
     if (chroma_format_idc == 2 || chroma_format_idc == 3) {
@@ -77,10 +51,10 @@ int check_dev(const char *who, int bit_depth, int chroma_format_idc, int mb_w, i
         return r;
     const int ps = bit_depth > 8 ? 2 : 1;
     const unsigned amask = 4u * ps - 1;
-    std::vector<Rows> dst;
+    std::vector<FFHipRows> dst;
     dst.reserve((size_t)npics * 3);
     auto plane_rows = [&](const void *base, ptrdiff_t stride, int p) {
-        return Rows{ (uintptr_t)base, stride, (ptrdiff_t)(mb_w * (p ? 8 : 16)) * ps, mb_h * (p ? 8 : 16) };
+        return FFHipRows{ (uintptr_t)base, stride, (ptrdiff_t)(mb_w * (p ? 8 : 16)) * ps, mb_h * (p ? 8 : 16) };
     };
     for (int i = 0; i < npics; i++) {
         const FFHipH264InterPic &P = pics[i];
@@ -110,26 +84,20 @@ int check_dev(const char *who, int bit_depth, int chroma_format_idc, int mb_w, i
     /* workgroups of every picture of the call read while others write: no destination row may share a byte with another destination
      * row or with a reference row of any picture; the span set sorts out the planes that cannot before the pairwise row rule */
     FFHipSpanSet out;
-    out.reserve(dst.size());
-    for (const Rows &d : dst)
-        out.add(d.span());
-    if (out.seal())
-        for (size_t a = 0; a < dst.size(); a++)
-            for (size_t b = a + 1; b < dst.size(); b++)
-                if (rows_share(dst[a], dst[b])) {
-                    ffhip_set_error("%s: a destination plane overlaps another destination plane of the call", who);
-                    return FFHIP_EINVAL;
-                }
+    if (ffhip_any_rows_share(dst, out)) {
+        ffhip_set_error("%s: a destination plane overlaps another destination plane of the call", who);
+        return FFHIP_EINVAL;
+    }
     for (int i = 0; i < npics; i++) {
         const FFHipH264InterPic &P = pics[i];
         const bool has_c = chroma_format_idc && P.dst[1];
         for (int k = 0; k < P.nrefs; k++)
             for (int p = 0; p < (has_c ? 3 : 1); p++) {
-                const Rows r = plane_rows(P.ref[k].base[p], P.ref[k].stride[p], p);
+                const FFHipRows r = plane_rows(P.ref[k].base[p], P.ref[k].stride[p], p);
                 if (!out.hits(r.span()))
                     continue;
-                for (const Rows &d : dst)
-                    if (rows_share(d, r)) {
+                for (const FFHipRows &d : dst)
+                    if (ffhip_rows_share(d, r)) {
                         ffhip_set_error("%s: picture %d: reference %d: a row of plane %d overlaps a destination row of the call", who, i, k, p);
                         return FFHIP_EINVAL;
                     }

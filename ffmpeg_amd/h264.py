@@ -243,6 +243,48 @@ def inter_plan_host(pics, mb_w, mb_h):
                       "ffhip_h264_inter_plan_pictures_host")
 
 
+#: FFHipH264ResMb (include/ffhip.h): one macroblock of residual_pictures(), parallel to BS_MB_DTYPE.  coeff_offset in coefficients (a
+#: multiple of 16); chroma: bit j Cb block j, bit 4 + j Cr block j; chroma_dc: bit 0 Cb, bit 1 Cr; qmul: Cb, Cr.
+RES_MB_DTYPE = np.dtype([("coeff_offset", np.int32), ("chroma", np.uint8), ("chroma_dc", np.uint8), ("pad", np.uint8, 2), ("qmul", np.int32, 2)])
+assert RES_MB_DTYPE.itemsize == 16
+RES_PICS_PER_LAUNCH = 16
+
+
+class ResPic(C.Structure):
+    """FFHipH264ResPic"""
+    _fields_ = [("dst", C.c_void_p * 3), ("dst_stride", C.c_ssize_t * 3), ("mb", C.c_void_p), ("res", C.c_void_p), ("coeffs", C.c_void_p),
+                ("ncoeffs", C.c_int64)]
+
+
+def res_pics(pics, ptr):
+    """the FFHipH264ResPic array of residual_pictures()'s dicts; ptr: an entry's address (ints are taken as they are)"""
+    arr = (ResPic * max(len(pics), 1))()
+    at = lambda t: None if t is None else t if isinstance(t, int) else ptr(t)
+    for i, m in enumerate(pics):
+        a = arr[i]
+        for p, (t, s) in enumerate(zip(m["dst"], m["dst_stride"])):
+            a.dst[p], a.dst_stride[p] = at(t), s
+        a.mb, a.res, a.coeffs, a.ncoeffs = at(m["mb"]), at(m["res"]), at(m["coeffs"]), m["ncoeffs"]
+    return arr
+
+
+def residual_pictures(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1, stream=None):
+    """ffhip_h264_residual_pictures_dev on npics = len(pics) pictures of mb_w x mb_h macroblocks.  pics[i]: a dict with dst (up to three
+    device tensors or addresses, Cb / Cr None for luma only) and dst_stride (bytes), the device tensors mb (BS_MB_DTYPE records as bytes,
+    the array inter_pictures() and edge_params_pictures() take), res (RES_MB_DTYPE) and coeffs (int16 at 8 bits, int32 above, never
+    written), and the int ncoeffs.  Asynchronous on `stream`."""
+    arr = res_pics(pics, lambda t: t.data_ptr())
+    return _lib.check(_lib.lib().ffhip_h264_residual_pictures_dev(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p),
+                                                                  _stream(stream)), "ffhip_h264_residual_pictures_dev")
+
+
+def residual_pictures_host(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1):
+    """ffhip_h264_residual_pictures_host (device-free): as residual_pictures() with numpy arrays; the planes are written in place."""
+    arr = res_pics(pics, lambda a: a.ctypes.data)
+    return _lib.check(_lib.lib().ffhip_h264_residual_pictures_host(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p)),
+                      "ffhip_h264_residual_pictures_host")
+
+
 class Picture:
     """ctypes mirror of FFHipH264Picture: record a picture's per-block dsp calls on the host, flush them as a handful of
     launches (include/ffhip.h).  Records are numpy structured scalars / arrays of the batch faces' dtypes."""

@@ -707,7 +707,7 @@ int ffhip_h264_bs_slice_record_size(void);
  *     weights); offsets in 8-bit units, scaled by the depth inside as the batch faces take them.
  * 10. Every sample of every well-formed block of a non-intra macroblock is written exactly once; nothing else is: not intra
  *     macroblocks, not the stride padding, no input.
- * Out of scope: the residual (ffhip_h264_idct_add_mb_batch_dev and its family follow on the same stream), 4:2:2 / 4:4:4, MBAFF.
+ * Out of scope: the residual (ffhip_h264_residual_pictures_dev below follows on the same stream), 4:2:2 / 4:4:4, MBAFF.
  */
 typedef struct FFHipH264InterSlice {       /* what mc_part() reads from the slice, 2888 bytes */
     uint8_t  ref[2][32];                   /* [list][ref_idx] -> slot: index into FFHipH264InterPic.ref */
@@ -780,6 +780,75 @@ int ffhip_h264_inter_ref_record_size(void);
 int ffhip_h264_inter_pic_record_size(void);
 int ffhip_h264_inter_plan_record_size(void);
 int ffhip_h264_inter_plan_pic_record_size(void);
+
+/**
+ * The residual of every inter macroblock of whole H.264 pictures in one launch, between the inter face above and the edge-parameter
+ * face: what hl_decode_mb_idct_luma() and the chroma part of hl_decode_mb() do for an inter macroblock through idct_add16 /
+ * idct8_add4, chroma_dc_dequant_idct and idct_add8, from the macroblock array those faces take (its nnz bits and flags) plus one small
+ * record per macroblock.  Non-MBAFF pictures (a frame, or one field as base + doubled stride); 4:2:0 and monochrome.
+ *
+ * The coefficients of a macroblock lie as in the decoder's sl->mb, `coeff_offset` coefficients into `coeffs`: luma block i of the
+ * decoder's block order at 16*i, its position x4 = (i&1) + 2*((i>>2)&1), y4 = ((i>>1)&1) + 2*(i>>3); an 8x8 block k in the 64
+ * coefficients at 64*k; Cb block j at 256 + 16*j, Cr block j at 512 + 16*j (j = x + 2*y), the chroma DC values on their blocks' first
+ * coefficients; stored transposed, as the idct faces take them.  Macroblocks may lie in any order and need only what they use.
+ * For macroblock m, with record r:
+ *  1. m intra (flags & 1): none of its samples is touched (they belong to the intra wavefront).
+ *  2. need = 768 where the picture has chroma planes and r.chroma | r.chroma_dc is non-zero (monochrome ignores both fields);
+ *     otherwise 256 if m.nnz is non-zero, else 0: nothing happens.
+ *  3. m is malformed and writes nothing on any plane when r.coeff_offset < 0, is not a multiple of 16, or coeff_offset + need > ncoeffs.
+ *  4. luma, m without the 8x8 flag: every block i whose nnz bit (x4 + 4*y4) is set gets idct_add.
+ *  5. luma, m with the 8x8 flag (flags & 2): 8x8 block k gets idct8_add iff the nnz bit of its top-left 4x4 block is set (the test of
+ *     idct8_add4; the FFHipH264BsMb contract makes the four bits equal).
+ *  6. chroma plane c with r.chroma_dc bit c: the first coefficients of the plane's four blocks go through chroma_dc_dequant_idct
+ *     with r.qmul[c], in registers, truncated to the coefficient type as the reference stores them; then all four blocks are added:
+ *     a block whose r.chroma bit is set by idct_add with that DC, a block whose bit is clear by idct_dc_add of it.
+ *  7. chroma plane c without its DC bit: the blocks whose r.chroma bit is set get idct_add.
+ *  8. a block whose bit is clear is not read (under rule 6 its first coefficient is).
+ *  9. Bits, not counts.  idct_add16, idct8_add4 and idct_add8 choose *_dc_add from a non-zero count of 1 or from block[0];
+ *     (dc + 32) >> 6 on every sample is what the full transform gives for a block with nothing but a DC, in both coefficient widths,
+ *     with one exception: the transform adds the 32 in the coefficient type, so at 8 bits a DC of 32736 .. 32767 wraps there and not
+ *     in *_dc_add.  The face follows the reference there too: a luma block whose other coefficients are all zero takes the *_dc_add
+ *     form (what a count of 1 with block[0] set means in a decoder's data), a chroma block with its bit the transform, one without
+ *     (rule 6) the *_dc_add form.  For every other content the choice does not change a byte.
+ * 10. the samples of the transformed blocks are written once each; nothing else is touched: not the padding, not coeffs (the batch
+ *     faces clear what they consume; this one does not), not a map.
+ * 11. results clip to (1 << bit_depth) - 1.
+ * 12. m.slice and m.qp are not looked at: a caller whose inter call dropped a macroblock as malformed drops it here too (nnz 0, no
+ *     chroma bits).
+ * Out of scope: the lossless bypass, MBAFF, luma DC (intra 16x16), I_PCM, 4:2:2 / 4:4:4.
+ */
+typedef struct FFHipH264ResMb {            /* one macroblock, 16 bytes; parallel to FFHipH264BsMb */
+    int32_t coeff_offset;                  /* in coefficients into FFHipH264ResPic.coeffs; a multiple of 16 */
+    uint8_t chroma;                        /* bit j: Cb 4x4 block j has coefficients; bit 4 + j: Cr block j (j = x + 2*y) */
+    uint8_t chroma_dc;                     /* bit 0: Cb DC coded (chroma_dc_dequant_idct runs on it); bit 1: Cr */
+    uint8_t pad[2];
+    int32_t qmul[2];                       /* Cb, Cr: the decoder's dequant4_coeff[4 + c][chroma qp][0] */
+} FFHipH264ResMb;
+typedef struct FFHipH264ResPic {           /* _dev: device pointers, _host: host pointers; 80 bytes */
+    uint8_t *dst[3];                       /* as FFHipH264InterPic: Cb and Cr both NULL = monochrome */
+    ptrdiff_t dst_stride[3];               /* bytes; base and stride multiples of 4 samples, stride >= the plane's width */
+    const FFHipH264BsMb  *mb;              /* mb_w * mb_h raster: flags bit 0 intra, bit 1 8x8 transform, nnz */
+    const FFHipH264ResMb *res;             /* mb_w * mb_h raster, 4-byte aligned */
+    const void *coeffs;                    /* int16_t at 8 bits, int32_t above; 16-byte aligned; never written */
+    int64_t ncoeffs;
+} FFHipH264ResPic;
+/** npics pictures of mb_w x mb_h macroblocks (1..4096 each) at bit_depth 8, 9, 10, 12 or 14 (uint16_t samples above 8; strides stay
+ *  in bytes), chroma_format_idc 0 (Cb / Cr ignored) or 1.  Pictures go 16 to a launch.  Asynchronous on `stream`: behind
+ *  ffhip_h264_inter_pictures_dev and ahead of ffhip_h264_edge_params_pictures_dev and the deblock faces with no synchronisation.
+ *  FFHIP_ENOSYS (with a text) for chroma_format_idc 2 or 3.
+ *  FFHIP_EINVAL for another depth, format or size, npics <= 0, NULL pics, dst[0], mb, res or coeffs, only one of Cb / Cr, a dst base
+ *  or stride that is not a multiple of 4 samples, a stride below the plane's width, a res that is not 4-byte or a coeffs that is not
+ *  16-byte aligned, a negative ncoeffs, or an overlap: two destination planes of the call that share a byte of a row (the row rule of
+ *  ffhip_h264_inter_pictures_dev: the two fields of one frame in one call are accepted), or a coeffs, mb or res span that shares a
+ *  byte with a destination span of the call.  FFHIP_ENOSYS without a device (after the argument checks). */
+int ffhip_h264_residual_pictures_dev(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics,
+                                     const FFHipH264ResPic *pics /* host array */, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free): the same arguments, refusals but FFHIP_ENOSYS without a
+ *  device, and bytes.  The _dev face never calls it. */
+int ffhip_h264_residual_pictures_host(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264ResPic *pics);
+/** sizeof(FFHipH264ResMb), sizeof(FFHipH264ResPic), for bindings that mirror the records (no device needed). */
+int ffhip_h264_res_mb_record_size(void);
+int ffhip_h264_res_pic_record_size(void);
 
 /**
  * The batched faces above at ANY depth the reference instantiates (bit_depth 8 / 9 / 10 / 12 / 14), plus the members that exist
