@@ -14,4 +14,7 @@ int ffhip_launch_me_esa(const uint8_t *cur, const uint8_t *ref, int width, int h
 /* SATD search on the matrix cores (me_satd.hip): 1 = launched, 0 = not its case */
 int ffhip_launch_me_esa_satd_mx(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
                                 int mb_size, int R, int16_t *mv_out, uint32_t *cost_out, hipStream_t stream);
+/* the per-block fast searches (me_search.hip): method FFHIP_ME_METHOD_TSS .. _HEXBS, nblocks = b_w * b_h * nframes > 0 */
+int ffhip_launch_me_search(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                           int nframes, int mb_size, int R, int cost_kind, int16_t *mv_out, uint32_t *cost_out, hipStream_t stream);
 #endif

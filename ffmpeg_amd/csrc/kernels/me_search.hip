@@ -1,0 +1,192 @@
+/*
+ * me_search.hip — the filter's per-block fast motion searches (TSS, TDLS, NTSS, FSS, DS, HEXBS) of whole frame pairs in one launch.
+ *
+ * The rules — pattern tables, window, the candidates of a step and the state transition — are kernels/me_search_rules.h, the same code
+ * ffhip_me_search_frames_host() runs on the CPU; this file owns how a cost is computed.
+ *
+ * The search of one block is a short chain of dependent steps of at most 8 independent candidates, so the parallelism is candidates x
+ * pixels inside a step and blocks across the grid:
+ *   - one wave per block, eight lanes per candidate: lane = 8 * i + r evaluates candidate i of the step, rows r and (16x16) r + 8 of
+ *     the block: one 16-byte (8x8: 8-byte) load per row at the candidate's byte-exact address in `ref`.  The current block's rows
+ *     stay in registers for the whole search.  A candidate outside the window issues no load; the 4- and 6-candidate patterns leave
+ *     lane groups idle (the next step depends on this one's result, so nothing can be packed in).
+ *   - SAD: v_sad_u8 over the dwords.  SATD: the horizontal 8-point transform of a row's differences in the lane, the vertical one
+ *     across the eight lanes of the candidate (rows r and r + 8 belong to different 8x8 blocks), then the absolute sum.
+ *   - the eight partial sums of a candidate are added with DPP moves (quad_perm, quad_perm, row_half_mirror), no LDS; the Hadamard
+ *     butterfly across lanes r and r ^ 4 is a ds_swizzle (the crossbar, no LDS memory).
+ *   - the ordered minimum of cost << 3 | index over the in-window candidates (rules header) is one DPP row rotate, four v_readlane and
+ *     scalar minima; the state (method, step, first, centre, cost_min) is wave-uniform and lives in scalar registers.
+ *   - a grid-stride loop over blocks x frames: a 4K pair and a 64x48 one run the same code.
+ * No LDS, no scratch; every loop is bounded by the rules header's step bound.
+ */
+#include <stdlib.h>
+
+#include "common.h"
+#include "me_kernels.h"
+#include "me_search_rules.h"
+
+#define MES_WAVES 4                 /* blocks (waves) per workgroup */
+#define MES_DPP_XOR1 0xB1           /* quad_perm:[1,0,3,2] */
+#define MES_DPP_XOR2 0x4E           /* quad_perm:[2,3,0,1] */
+#define MES_DPP_HALF_MIRROR 0x141   /* lane r of an 8-lane half row reads lane 7 - r */
+#define MES_DPP_ROR8 0x128          /* row_ror:8: lane l of a 16-lane row reads lane l ^ 8 */
+#define MES_SWIZZLE_XOR4 0x101F     /* bit mode: and 0x1F, or 0, xor 4 */
+
+template <int CTRL>
+__device__ __forceinline__ int mes_dpp(int v)
+{
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
+}
+
+/* the sum of v over the eight lanes of a candidate, in every one of them (all 64 lanes take part) */
+__device__ __forceinline__ uint32_t mes_sum8(uint32_t v)
+{
+    v += (uint32_t)mes_dpp<MES_DPP_XOR1>((int)v);
+    v += (uint32_t)mes_dpp<MES_DPP_XOR2>((int)v);
+    v += (uint32_t)mes_dpp<MES_DPP_HALF_MIRROR>((int)v);   /* the quads are uniform by now: the other quad's sum */
+    return v;
+}
+
+/* one row of eight differences a - b (two dwords each) of an 8x8 block whose row r lives in lane r of the candidate's eight: the
+ * lane's share of sum |H8 (a - b) H8^T|.  The transform is the un-normalised Walsh-Hadamard one in any row order and sign, which
+ * the absolute sum does not see. */
+__device__ __forceinline__ uint32_t mes_satd_row(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, int lane)
+{
+    int d[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        d[i] = (int)((a0 >> (8 * i)) & 255u) - (int)((b0 >> (8 * i)) & 255u);
+        d[4 + i] = (int)((a1 >> (8 * i)) & 255u) - (int)((b1 >> (8 * i)) & 255u);
+    }
+#pragma unroll
+    for (int span = 1; span < 8; span <<= 1)
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (!(i & span)) {
+                const int p = d[i], q = d[i + span];
+                d[i] = p + q;
+                d[i + span] = p - q;
+            }
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        int v = d[i], o;
+        o = mes_dpp<MES_DPP_XOR1>(v);
+        v = (lane & 1) ? o - v : o + v;
+        o = mes_dpp<MES_DPP_XOR2>(v);
+        v = (lane & 2) ? o - v : o + v;
+        o = __builtin_amdgcn_ds_swizzle(v, MES_SWIZZLE_XOR4);
+        v = (lane & 4) ? o - v : o + v;
+        sum += (uint32_t)abs(v);
+    }
+    return sum;
+}
+
+/* cost(x, y) of the lane's candidate, summed over its eight lanes.  c: the lane's rows of the current block; rf: the reference
+ * frame.  Every lane of the wave calls it; valid (uniform over a candidate's eight lanes) false: no load, the result means nothing. */
+template <int MB, int KIND>
+__device__ __forceinline__ uint32_t mes_cost(const uint32_t (&c)[MB / 8][MB / 4], const uint8_t *rf, ptrdiff_t stride, bool valid, int x, int y,
+                                             int lane)
+{
+    constexpr int NR = MB / 8, ND = MB / 4;
+    uint32_t v[NR][ND];
+#pragma unroll
+    for (int k = 0; k < NR; k++)
+#pragma unroll
+        for (int j = 0; j < ND; j++)
+            v[k][j] = 0;
+    if (valid) {
+        const uint8_t *p = rf + (ptrdiff_t)(y + (lane & 7)) * stride + x;
+#pragma unroll
+        for (int k = 0; k < NR; k++)
+            __builtin_memcpy(v[k], p + (ptrdiff_t)(8 * k) * stride, MB);
+    }
+    uint32_t part = 0;
+#pragma unroll
+    for (int k = 0; k < NR; k++) {
+        if (KIND == FFHIP_ME_SAD) {
+#pragma unroll
+            for (int j = 0; j < ND; j++)
+                part = __builtin_amdgcn_sad_u8(c[k][j], v[k][j], part);
+        } else {
+#pragma unroll
+            for (int j = 0; j < ND; j += 2)
+                part += mes_satd_row(c[k][j], c[k][j + 1], v[k][j], v[k][j + 1], lane);
+        }
+    }
+    return mes_sum8(part);
+}
+
+template <int MB, int KIND>
+__global__ __launch_bounds__(64 * MES_WAVES) void k_me_search(int method, const uint8_t *cur, const uint8_t *ref, int width, int height,
+                                                              ptrdiff_t stride, size_t frame_pitch, uint32_t nblocks, int R, int16_t *mv_out,
+                                                              uint32_t *cost_out)
+{
+    constexpr int LOG2 = MB == 16 ? 4 : 3, NR = MB / 8;
+    const int bw = width >> LOG2, bh = height >> LOG2;
+    const uint32_t per = (uint32_t)bw * (uint32_t)bh;                    /* blocks of a frame */
+    const int lane = threadIdx.x & 63, cand = lane >> 3;
+    const uint32_t wave = blockIdx.x * MES_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t nwaves = gridDim.x * MES_WAVES;
+    for (uint32_t b = wave; b < nblocks; b += nwaves) {
+        const uint32_t f = b / per, rem = b - f * per;
+        const int by = (int)(rem / (uint32_t)bw), bx = (int)(rem - (uint32_t)by * (uint32_t)bw);
+        const int x_mb = bx << LOG2, y_mb = by << LOG2;
+        const uint8_t *cf = cur + (size_t)f * frame_pitch, *rf = ref + (size_t)f * frame_pitch;
+        uint32_t c[NR][MB / 4];
+        {
+            const uint8_t *p = cf + (ptrdiff_t)(y_mb + (lane & 7)) * stride + x_mb;
+#pragma unroll
+            for (int k = 0; k < NR; k++)
+                __builtin_memcpy(c[k], p + (ptrdiff_t)(8 * k) * stride, MB);
+        }
+        const MesWindow w = mes_window(x_mb, y_mb, R, bw, bh, LOG2);
+        /* the start: every candidate group evaluates the centre */
+        const uint32_t cost0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mes_cost<MB, KIND>(c, rf, stride, true, x_mb, y_mb, lane));
+        MesState s = mes_start(method, x_mb, y_mb, R, cost0);
+        const uint32_t bound = mes_step_bound(w);
+        for (uint32_t n = 0; !s.done && n < bound; n++) {
+            const MesStep st = mes_step(s);
+            int x, y;
+            const bool valid = mes_candidate(s, st, w, cand, x, y) && cand < st.n;
+            const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
+            uint32_t key = valid ? mes_key(cost, cand) : MES_NO_KEY;
+            key = min(key, (uint32_t)mes_dpp<MES_DPP_ROR8>((int)key));
+            const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, 0), k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, 16);
+            const uint32_t k2 = (uint32_t)__builtin_amdgcn_readlane((int)key, 32), k3 = (uint32_t)__builtin_amdgcn_readlane((int)key, 48);
+            mes_advance(s, st, w, min(min(k0, k1), min(k2, k3)));
+        }
+        if (lane == 0) {
+            mv_out[2 * (size_t)b] = (int16_t)s.mvx;
+            mv_out[2 * (size_t)b + 1] = (int16_t)s.mvy;
+            cost_out[b] = s.cost_min;
+        }
+    }
+}
+
+int ffhip_launch_me_search(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                           int nframes, int mb_size, int R, int cost_kind, int16_t *mv_out, uint32_t *cost_out, hipStream_t stream)
+{
+    const int lg = mb_size == 16 ? 4 : 3;
+    const int64_t nblocks = (int64_t)(width >> lg) * (height >> lg) * nframes;
+    if (nblocks <= 0)
+        return 0;
+    /* as many workgroups as stay resident at 8 waves per SIMD; the rest of the blocks are the waves' next rounds.
+     * FFHIP_ME_SEARCH_WGS (measurement build) fixes the number, so that a small picture takes several rounds */
+    int64_t wgs = (int64_t)ffhip_cu_count() * (32 / MES_WAVES);
+    const char *e = FFHIP_KNOB("FFHIP_ME_SEARCH_WGS");
+    if (e && atoi(e) > 0)
+        wgs = atoi(e);
+    if (wgs > (nblocks + MES_WAVES - 1) / MES_WAVES)
+        wgs = (nblocks + MES_WAVES - 1) / MES_WAVES;
+#define MES(M, K) hipLaunchKernelGGL((k_me_search<M, K>), dim3((unsigned)wgs), dim3(64 * MES_WAVES), 0, stream, method, cur, ref, width, height, \
+                                     stride, frame_pitch, (uint32_t)nblocks, R, mv_out, cost_out)
+    if (cost_kind == FFHIP_ME_SAD) {
+        if (mb_size == 16) MES(16, FFHIP_ME_SAD); else MES(8, FFHIP_ME_SAD);
+    } else {
+        if (mb_size == 16) MES(16, FFHIP_ME_SATD); else MES(8, FFHIP_ME_SATD);
+    }
+#undef MES
+    LAUNCH_CHECK();
+    return 0;
+}

@@ -1,8 +1,12 @@
 /*
  * me_api.hip — C-ABI entry points of the me_cmp / motion-search part of libffhip (include/ffhip.h).
  */
+#include <limits.h>
+#include <stdlib.h>
+
 #include "kernels/common.h"
 #include "kernels/me_kernels.h"
+#include "kernels/me_search_rules.h"
 
 extern "C" int ffhip_me_cmp_batch_dev(int kind, int width, int h, const uint8_t *blk1, const int32_t *off1,
                                       const uint8_t *blk2, const int32_t *off2, ptrdiff_t stride, int32_t *out, int n,
@@ -29,4 +33,157 @@ extern "C" int ffhip_me_esa_batch_dev(const uint8_t *cur, const uint8_t *ref, in
         return FFHIP_ENOSYS;
     return ffhip_launch_me_esa(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind,
                                mv_out, cost_out, (hipStream_t)stream);
+}
+
+/* ---- the filter's per-block searches (kernels/me_search_rules.h) ----------------------------------------------------------------- */
+/* the checks both faces share: 0, FFHIP_EINVAL, or FFHIP_ENOSYS with a text for the two methods that are not per-block functions */
+static int me_search_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                           int nframes, int mb_size, int search_param, int cost_kind, const int16_t *mv_out, const uint32_t *cost_out)
+{
+    if (!cur || !ref || !mv_out || !cost_out || method < FFHIP_ME_METHOD_ESA || method > FFHIP_ME_METHOD_UMH || width < 0 || height < 0 ||
+        nframes < 0 || search_param < 0 || (mb_size != 16 && mb_size != 8) || (cost_kind != FFHIP_ME_SAD && cost_kind != FFHIP_ME_SATD) ||
+        stride < width)
+        return FFHIP_EINVAL;
+    if (nframes > 1 && height && frame_pitch / (size_t)height < (size_t)stride)     /* frame_pitch < stride * height, without the product */
+        return FFHIP_EINVAL;
+    const int lg = mb_size == 16 ? 4 : 3;
+    if ((int64_t)(width >> lg) * (height >> lg) * nframes > INT_MAX)
+        return FFHIP_EINVAL;
+    if (method >= FFHIP_ME_METHOD_EPZS) {
+        ffhip_set_error("motion search method %d (%s) needs the neighbouring blocks' vectors of the current and the previous frame: "
+                        "it is not a function of one block and stays on the CPU", method, method == FFHIP_ME_METHOD_EPZS ? "EPZS" : "UMH");
+        return FFHIP_ENOSYS;
+    }
+    return 0;
+}
+
+extern "C" int ffhip_me_search_batch_dev(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                         size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                         int16_t *mv_out, uint32_t *cost_out, void *stream)
+{
+    const int r = me_search_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out,
+                                  cost_out);
+    if (r)
+        return r;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    if (method == FFHIP_ME_METHOD_ESA)
+        return ffhip_launch_me_esa(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out,
+                                   cost_out, (hipStream_t)stream);
+    return ffhip_launch_me_search(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out,
+                                  cost_out, (hipStream_t)stream);
+}
+
+/* the two metrics on the CPU: cur = blk1 (the current block), ref = blk2 */
+static uint32_t host_sad(const uint8_t *a, const uint8_t *b, ptrdiff_t stride, int mb)
+{
+    uint32_t s = 0;
+    for (int y = 0; y < mb; y++, a += stride, b += stride)
+        for (int x = 0; x < mb; x++)
+            s += (uint32_t)abs((int)a[x] - (int)b[x]);
+    return s;
+}
+
+static uint32_t host_satd8x8(const uint8_t *a, const uint8_t *b, ptrdiff_t stride)
+{
+    int t[64];
+    for (int y = 0; y < 8; y++)
+        for (int x = 0; x < 8; x++)
+            t[8 * y + x] = (int)a[y * stride + x] - (int)b[y * stride + x];
+    for (int pass = 0; pass < 2; pass++) {              /* rows, then columns */
+        const int st = pass ? 8 : 1, line = pass ? 1 : 8;
+        for (int l = 0; l < 8; l++)
+            for (int span = 1; span < 8; span <<= 1)
+                for (int i = 0; i < 8; i++)
+                    if (!(i & span)) {
+                        int *p = t + l * line + i * st, *q = p + span * st;
+                        const int u = *p, v = *q;
+                        *p = u + v;
+                        *q = u - v;
+                    }
+    }
+    uint32_t s = 0;
+    for (int i = 0; i < 64; i++)
+        s += (uint32_t)abs(t[i]);
+    return s;
+}
+
+struct HostCost {
+    const uint8_t *cur_blk, *ref;   /* the current block's first sample, the reference plane */
+    ptrdiff_t stride;
+    int mb, kind;
+    uint64_t n;
+    uint32_t operator()(int x, int y)
+    {
+        const uint8_t *b = ref + (ptrdiff_t)y * stride + x;
+        n++;
+        if (kind == FFHIP_ME_SAD)
+            return host_sad(cur_blk, b, stride, mb);
+        uint32_t s = 0;
+        for (int by = 0; by < mb; by += 8)
+            for (int bx = 0; bx < mb; bx += 8)
+                s += host_satd8x8(cur_blk + by * stride + bx, b + by * stride + bx, stride);
+        return s;
+    }
+};
+
+static thread_local uint64_t t_host_blocks, t_host_costs;
+
+extern "C" void ffhip_me_search_host_counts(uint64_t *blocks, uint64_t *costs)
+{
+    if (blocks)
+        *blocks = t_host_blocks;
+    if (costs)
+        *costs = t_host_costs;
+}
+
+extern "C" int ffhip_me_search_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                           size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                           int16_t *mv_out, uint32_t *cost_out)
+{
+    const int r = me_search_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out,
+                                  cost_out);
+    if (r)
+        return r;
+    const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
+    uint64_t blocks = 0, costs = 0;
+    for (int f = 0; f < nframes; f++)
+        for (int by = 0; by < bh; by++)
+            for (int bx = 0; bx < bw; bx++) {
+                const int x_mb = bx << lg, y_mb = by << lg;
+                const MesWindow w = mes_window(x_mb, y_mb, search_param, bw, bh, lg);
+                HostCost cost = { cur + (size_t)f * frame_pitch + (ptrdiff_t)y_mb * stride + x_mb, ref + (size_t)f * frame_pitch, stride, mb_size,
+                                  cost_kind, 0 };
+                int mvx, mvy;
+                uint32_t cost_min;
+                if (method == FFHIP_ME_METHOD_ESA) {
+                    mes_search_esa(x_mb, y_mb, w, cost, mvx, mvy, cost_min);
+                } else {
+                    MesState s = mes_start(method, x_mb, y_mb, search_param, cost(x_mb, y_mb));
+                    for (uint32_t n = 0, bound = mes_step_bound(w); !s.done && n < bound; n++) {
+                        const MesStep st = mes_step(s);
+                        uint32_t key = MES_NO_KEY;
+                        for (int i = 0; i < st.n; i++) {
+                            int x, y;
+                            if (mes_candidate(s, st, w, i, x, y)) {
+                                const uint32_t k = mes_key(cost(x, y), i);
+                                key = k < key ? k : key;
+                            }
+                        }
+                        mes_advance(s, st, w, key);
+                    }
+                    mvx = s.mvx;
+                    mvy = s.mvy;
+                    cost_min = s.cost_min;
+                }
+                const size_t b = ((size_t)f * bh + by) * bw + bx;
+                mv_out[2 * b] = (int16_t)mvx;
+                mv_out[2 * b + 1] = (int16_t)mvy;
+                cost_out[b] = cost_min;
+                blocks++;
+                costs += cost.n;
+            }
+    t_host_blocks = blocks;
+    t_host_costs = costs;
+    return 0;
 }

@@ -2,6 +2,8 @@
 from . import _lib
 
 SAD, SATD = 0, 1
+# the filter's search methods (== AV_ME_METHOD_*); EPZS and UMH are refused by name: they need the neighbouring blocks' vectors
+ESA, TSS, TDLS, NTSS, FSS, DS, HEXBS, EPZS, UMH = range(1, 10)
 
 
 def _stream(stream):
@@ -22,3 +24,25 @@ def esa_batch(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, se
     return _lib.check(_lib.lib().ffhip_me_esa_batch_dev(cur.data_ptr(), ref.data_ptr(), width, height, stride, frame_pitch,
                                                         nframes, mb_size, search_param, cost_kind, mv_out.data_ptr(),
                                                         cost_out.data_ptr(), _stream(stream)), "ffhip_me_esa_batch_dev")
+
+
+def search_batch(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out,
+                 stream=None):
+    """The filter's per-block search `method` (ESA .. HEXBS) of every mb_size block of `cur` in `ref`, nframes pairs in one launch;
+    tensors on the device, outputs as esa_batch()."""
+    return _lib.check(_lib.lib().ffhip_me_search_batch_dev(method, cur.data_ptr(), ref.data_ptr(), width, height, stride, frame_pitch,
+                                                           nframes, mb_size, search_param, cost_kind, mv_out.data_ptr(),
+                                                           cost_out.data_ptr(), _stream(stream)), "ffhip_me_search_batch_dev")
+
+
+def search_frames_host(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out):
+    """The same rules on the CPU (device-free): numpy arrays (uint8 planes, int16 vectors, uint32 costs).  Returns (blocks searched,
+    costs evaluated)."""
+    import ctypes as C
+    L = _lib.lib()
+    _lib.check(L.ffhip_me_search_frames_host(method, cur.ctypes.data, ref.ctypes.data, width, height, stride, frame_pitch, nframes,
+                                             mb_size, search_param, cost_kind, mv_out.ctypes.data, cost_out.ctypes.data),
+               "ffhip_me_search_frames_host")
+    blocks, costs = C.c_uint64(), C.c_uint64()
+    L.ffhip_me_search_host_counts(C.byref(blocks), C.byref(costs))
+    return blocks.value, costs.value

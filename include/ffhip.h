@@ -2919,8 +2919,63 @@ int ffhip_me_esa_batch_dev(const uint8_t *cur, const uint8_t *ref, int width, in
                            size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
                            int16_t *mv_out, uint32_t *cost_out, void *stream);
 
+#define FFHIP_ME_METHOD_ESA   1   /* == AV_ME_METHOD_* (libavfilter/motion_estimation.h) */
+#define FFHIP_ME_METHOD_TSS   2
+#define FFHIP_ME_METHOD_TDLS  3
+#define FFHIP_ME_METHOD_NTSS  4
+#define FFHIP_ME_METHOD_FSS   5
+#define FFHIP_ME_METHOD_DS    6
+#define FFHIP_ME_METHOD_HEXBS 7
+#define FFHIP_ME_METHOD_EPZS  8   /* refused: FFHIP_ENOSYS */
+#define FFHIP_ME_METHOD_UMH   9   /* refused: FFHIP_ENOSYS */
+/**
+ * The filter's per-block searches (what vf_mestimate's SEARCH_MV(method) runs over a frame pair), every block of nframes pairs in one
+ * launch on `stream`.  Geometry, frame addressing, metrics and outputs are ffhip_me_esa_batch_dev()'s: log2mb = log2(mb_size),
+ * b_w = width >> log2mb, b_h = height >> log2mb, blocks in raster order at (x_mb, y_mb) = (bx << log2mb, by << log2mb), the window
+ * x_min = max(0, x_mb - R), x_max = min(x_mb + R, (b_w - 1) << log2mb) and the same for y; mv_out[2 * b + {0, 1}] the absolute best
+ * position, cost_out[b] its cost.  Every candidate evaluated lies in the window, so no read leaves the width x height plane.
+ *
+ * The rules below are RESTATED, NOT CHECKED AGAINST THE SOURCE (libavfilter/motion_estimation.c was not at hand); this text is the
+ * definition the tests pin (kernels/me_search_rules.h is its one implementation, tests/me_search_model.py the model written from it).
+ *   cost(x, y): the metric between the current block at (x_mb, y_mb) and the reference block at absolute (x, y); FFHIP_ME_SAD is
+ *     ff_me_cmp_sad, FFHIP_ME_SATD hadamard8_diff16 / hadamard8_diff8x8 with blk1 = current.
+ *   COST_MV(x, y): c = cost(x, y); if (c < cost_min) { cost_min = c; mv = (x, y); } — strict.  COST_P_MV(x, y): COST_MV only if (x, y)
+ *     is inside the window, nothing otherwise.  The candidates of an iteration are applied in table order: on equal costs the earliest
+ *     wins, and an equal cost never displaces the centre.
+ *   Tables (dx, dy): sqr1 = (0,-1) (0,1) (-1,0) (1,0) (-1,-1) (-1,1) (1,-1) (1,1); dia1 = (-1,0) (0,-1) (1,0) (0,1);
+ *     dia2 = (-2,0) (-1,-1) (0,-2) (1,-1) (2,0) (1,1) (0,2) (-1,1); hex2 = (-2,0) (-1,-2) (-1,2) (1,-2) (1,2) (2,0).
+ *   Start: mv = (x_mb, y_mb), cost_min = cost(x_mb, y_mb); 0 returns at once.  Below (x, y) is the centre copied from mv at the top of an
+ *     iteration, step0 = (R + 1) >> 1, and every candidate goes through COST_P_MV.
+ *   ESA  (1): the raster scan of the window with COST_MV.  The device face forwards to ffhip_me_esa_batch_dev()'s launcher.
+ *   TSS  (2): step = step0; do { the 8 of sqr1 * step; step >>= 1; } while (step > 0).
+ *   TDLS (3): step = step0; do { the 4 of dia1 * step; if mv is still (x, y), step >>= 1; } while (step > 0).
+ *   NTSS (4): step = step0, first = 1; do { the 8 of sqr1 * step; if (first) { the 8 of sqr1 * 1 round the same (x, y); if mv == (x, y)
+ *     return; if |x - mv.x| <= 1 and |y - mv.y| <= 1 { (x, y) = mv; the 8 of sqr1 * 1 round it; return; } first = 0; } step >>= 1; }
+ *     while (step > 0).
+ *   FSS  (5): step = 2; do { the 8 of sqr1 * step; if mv is still (x, y), step >>= 1; } while (step > 0).
+ *   DS   (6): do { the 8 of dia2 } while (mv != (x, y)); then the 4 of dia1 round the last (x, y).
+ *   HEXBS(7): do { the 6 of hex2 } while (mv != (x, y)); then the 4 of dia1 round the last (x, y).
+ *   EPZS (8) and UMH (9) take the neighbouring blocks' vectors of the current and the previous frame (a raster dependency plus the
+ *     filter's predictor bookkeeping): FFHIP_ENOSYS with a text that names the method.
+ * mb_size 16 or 8, cost_kind FFHIP_ME_SAD or FFHIP_ME_SATD, search_param >= 0 (0: each step method collapses to the centre), nframes >= 0
+ * (0: nothing is done); a picture smaller than one block has no blocks.  FFHIP_EINVAL (before any device check): NULL pointers, a method
+ * outside 1..9, another mb_size or cost_kind, a negative width, height, nframes or search_param, stride < width, nframes > 1 with
+ * frame_pitch < stride * height, more than 2^31 - 1 blocks.  FFHIP_ENOSYS without a device, after the checks.
+ */
+int ffhip_me_search_batch_dev(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                              size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                              int16_t *mv_out, uint32_t *cost_out, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free): the same arguments but the stream, the same refusals but the
+ *  one for a missing device, the same bytes.  Method 1 runs the start and the raster scan from the rules header too. */
+int ffhip_me_search_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                int16_t *mv_out, uint32_t *cost_out);
+/** What the calling thread's last successful ffhip_me_search_frames_host() did: the blocks it searched and the costs it evaluated
+ *  (the start of each block included).  Either pointer may be NULL. */
+void ffhip_me_search_host_counts(uint64_t *blocks, uint64_t *costs);
+
 /* ------------------------------------------------------------------------------------------ */
-/* libavutil: av_tx float MDCT                                                                */
+/* libavutil: av_tx float MDCT                                                               */
 /* ------------------------------------------------------------------------------------------ */
 typedef struct FFHipTXContext FFHipTXContext;
 #define FFHIP_TX_FLOAT_FFT  0   /* == AV_TX_FLOAT_FFT  (libavutil/tx.h:47-132) */

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Times the filter's per-block motion searches (ffhip_me_search_batch_dev, methods TSS .. HEXBS) beside the exhaustive face
+(ffhip_me_esa_batch_dev) on 3840 x 2160 frame pairs, 8 pairs per launch, 16 x 16 blocks, at search_param 7 and 32, SAD and SATD.
+
+Input: a smooth texture (box-filtered noise, stretched to the full range), the current frame = the reference moved by (3, -2) plus
+noise of +-2: uniform noise alone has no slope for a pattern search to follow.  Per row: milliseconds per frame pair (median of
+--rounds timed windows of at least --window seconds each, after two warm-up launches; device events round whole windows), the spread of
+the windows, MB-searches/s, and the mean number of costs a block evaluates — the counters of ffhip_me_search_frames_host() on the FIRST
+pair of the same input (the exhaustive rows: the window sizes, from the geometry).  The last column compares with the exhaustive face
+at the same search_param and metric, from the same run.
+
+    python tools/bench_me_search.py [--out profiles/me_search_bench.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+W, H, NF, MB = 3840, 2160, 8, 16
+NAMES = {1: "esa", 2: "tss", 3: "tdls", 4: "ntss", 5: "fss", 6: "ds", 7: "hexbs"}
+
+
+def make_input(torch):
+    g = torch.Generator(device="cuda").manual_seed(4)
+    big = torch.rand((NF, 1, H + 16, W + 16), device="cuda", generator=g)
+    big = torch.nn.functional.avg_pool2d(big, 9, stride=1, padding=4)
+    big = (big - big.amin()) / (big.amax() - big.amin()) * 255.0
+    ref = big[:, 0, 8:8 + H, 8:8 + W]
+    cur = big[:, 0, 8 - 2:8 - 2 + H, 8 + 3:8 + 3 + W] + torch.randint(-2, 3, (NF, H, W), device="cuda", generator=g)
+    to8 = lambda t: t.round().clamp(0, 255).to(torch.uint8).contiguous()
+    return to8(cur), to8(ref)
+
+
+def timed(torch, call, window, rounds):
+    """-> the per-launch milliseconds of `rounds` windows"""
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    for _ in range(2):
+        call()
+    e0, e1 = ev(), ev()
+    e0.record()
+    for _ in range(3):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    reps = max(3, min(2000, int(window * 1e3 / max(e0.elapsed_time(e1) / 3, 1e-3))))
+    out = []
+    for _ in range(rounds):
+        e0, e1 = ev(), ev()
+        e0.record()
+        for _ in range(reps):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / reps)
+    return out
+
+
+def esa_costs_per_block(R):
+    """the start plus the window, averaged over the blocks of a frame"""
+    bw, bh = W // MB, H // MB
+    nx = [min(x * MB + R, (bw - 1) * MB) - max(0, x * MB - R) + 1 for x in range(bw)]
+    ny = [min(y * MB + R, (bh - 1) * MB) - max(0, y * MB - R) + 1 for y in range(bh)]
+    return 1 + sum(nx) * sum(ny) / (bw * bh)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "me_search_bench.txt"))
+    ap.add_argument("--window", type=float, default=0.25)
+    ap.add_argument("--rounds", type=int, default=5)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_me_search: no GPU: nothing is measured")
+    from ffmpeg_amd import me
+    cur, ref = make_input(torch)
+    hcur, href = cur[0].cpu().numpy(), ref[0].cpu().numpy()
+    nb = (W // MB) * (H // MB)
+    mv = torch.empty((NF, nb * 2), dtype=torch.int16, device="cuda")
+    cost = torch.empty((NF, nb), dtype=torch.int32, device="cuda")
+    import numpy as np
+    hmv, hcost = np.zeros(nb * 2, np.int16), np.zeros(nb, np.uint32)
+    lines = ["# tools/bench_me_search.py on %s: %d pairs of %d x %d per launch, %d x %d blocks; ms per pair = median of %d windows of >= %.2f s"
+             % (torch.cuda.get_device_name(0), NF, W, H, MB, MB, a.rounds, a.window),
+             "# costs/block: the host face's counters on the first pair (esa: from the window sizes); x esa: this row's time over esa's at the same R and metric",
+             "%-6s %-5s %3s %12s %18s %16s %12s %8s" % ("method", "cost", "R", "ms/pair", "windows min..max", "MB-searches/s", "costs/block", "x esa")]
+    for kind, kname in ((me.SAD, "sad"), (me.SATD, "satd")):
+        for R in (7, 32):
+            esa_ms = None
+            for method in range(1, 8):
+                if method == me.ESA:
+                    call = lambda: me.esa_batch(cur, ref, W, H, W, W * H, NF, MB, R, kind, mv, cost)
+                    per_block = esa_costs_per_block(R)
+                else:
+                    call = lambda: me.search_batch(method, cur, ref, W, H, W, W * H, NF, MB, R, kind, mv, cost)
+                    blocks, costs = me.search_frames_host(method, hcur, href, W, H, W, W * H, 1, MB, R, kind, hmv, hcost)
+                    per_block = costs / blocks
+                    call()
+                    torch.cuda.synchronize()
+                    assert np.array_equal(mv[0].cpu().numpy(), hmv) and np.array_equal(cost[0].cpu().numpy().view(np.uint32), hcost), \
+                        "the device and the host face differ"
+                t = [x / NF for x in timed(torch, call, a.window, a.rounds)]
+                ms = statistics.median(t)
+                if method == me.ESA:
+                    esa_ms = ms
+                lines.append("%-6s %-5s %3d %12.4f %8.4f..%-8.4f %16.4g %12.1f %8.3f"
+                             % (NAMES[method], kname, R, ms, min(t), max(t), nb / (ms * 1e-3), per_block, ms / esa_ms))
+                print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
