@@ -17,4 +17,9 @@ int ffhip_launch_me_esa_satd_mx(const uint8_t *cur, const uint8_t *ref, int widt
 /* the per-block fast searches (me_search.hip): method FFHIP_ME_METHOD_TSS .. _HEXBS, nblocks = b_w * b_h * nframes > 0 */
 int ffhip_launch_me_search(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
                            int nframes, int mb_size, int R, int cost_kind, int16_t *mv_out, uint32_t *cost_out, hipStream_t stream);
+/* the predictive searches (me_search_pred.hip): method FFHIP_ME_METHOD_EPZS or _UMH, prev1 / prev2 NULL or fields laid out as mv_out,
+ * mv_out 4-byte aligned; calls of more block rows than a progress-pool slot counts are split by pairs */
+int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                int nframes, int mb_size, int R, int cost_kind, const int16_t *prev1, const int16_t *prev2, int16_t *mv_out,
+                                uint32_t *cost_out, hipStream_t stream);
 #endif

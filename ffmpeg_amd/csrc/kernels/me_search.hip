@@ -2,7 +2,7 @@
  * me_search.hip — the filter's per-block fast motion searches (TSS, TDLS, NTSS, FSS, DS, HEXBS) of whole frame pairs in one launch.
  *
  * The rules — pattern tables, window, the candidates of a step and the state transition — are kernels/me_search_rules.h, the same code
- * ffhip_me_search_frames_host() runs on the CPU; this file owns how a cost is computed.
+ * ffhip_me_search_frames_host() runs on the CPU; how a cost is computed is kernels/me_search_cost.h, shared with me_search_pred.hip.
  *
  * The search of one block is a short chain of dependent steps of at most 8 independent candidates, so the parallelism is candidates x
  * pixels inside a step and blocks across the grid:
@@ -23,99 +23,10 @@
 
 #include "common.h"
 #include "me_kernels.h"
+#include "me_search_cost.h"
 #include "me_search_rules.h"
 
 #define MES_WAVES 4                 /* blocks (waves) per workgroup */
-#define MES_DPP_XOR1 0xB1           /* quad_perm:[1,0,3,2] */
-#define MES_DPP_XOR2 0x4E           /* quad_perm:[2,3,0,1] */
-#define MES_DPP_HALF_MIRROR 0x141   /* lane r of an 8-lane half row reads lane 7 - r */
-#define MES_DPP_ROR8 0x128          /* row_ror:8: lane l of a 16-lane row reads lane l ^ 8 */
-#define MES_SWIZZLE_XOR4 0x101F     /* bit mode: and 0x1F, or 0, xor 4 */
-
-template <int CTRL>
-__device__ __forceinline__ int mes_dpp(int v)
-{
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
-}
-
-/* the sum of v over the eight lanes of a candidate, in every one of them (all 64 lanes take part) */
-__device__ __forceinline__ uint32_t mes_sum8(uint32_t v)
-{
-    v += (uint32_t)mes_dpp<MES_DPP_XOR1>((int)v);
-    v += (uint32_t)mes_dpp<MES_DPP_XOR2>((int)v);
-    v += (uint32_t)mes_dpp<MES_DPP_HALF_MIRROR>((int)v);   /* the quads are uniform by now: the other quad's sum */
-    return v;
-}
-
-/* one row of eight differences a - b (two dwords each) of an 8x8 block whose row r lives in lane r of the candidate's eight: the
- * lane's share of sum |H8 (a - b) H8^T|.  The transform is the un-normalised Walsh-Hadamard one in any row order and sign, which
- * the absolute sum does not see. */
-__device__ __forceinline__ uint32_t mes_satd_row(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, int lane)
-{
-    int d[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        d[i] = (int)((a0 >> (8 * i)) & 255u) - (int)((b0 >> (8 * i)) & 255u);
-        d[4 + i] = (int)((a1 >> (8 * i)) & 255u) - (int)((b1 >> (8 * i)) & 255u);
-    }
-#pragma unroll
-    for (int span = 1; span < 8; span <<= 1)
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            if (!(i & span)) {
-                const int p = d[i], q = d[i + span];
-                d[i] = p + q;
-                d[i + span] = p - q;
-            }
-    uint32_t sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        int v = d[i], o;
-        o = mes_dpp<MES_DPP_XOR1>(v);
-        v = (lane & 1) ? o - v : o + v;
-        o = mes_dpp<MES_DPP_XOR2>(v);
-        v = (lane & 2) ? o - v : o + v;
-        o = __builtin_amdgcn_ds_swizzle(v, MES_SWIZZLE_XOR4);
-        v = (lane & 4) ? o - v : o + v;
-        sum += (uint32_t)abs(v);
-    }
-    return sum;
-}
-
-/* cost(x, y) of the lane's candidate, summed over its eight lanes.  c: the lane's rows of the current block; rf: the reference
- * frame.  Every lane of the wave calls it; valid (uniform over a candidate's eight lanes) false: no load, the result means nothing. */
-template <int MB, int KIND>
-__device__ __forceinline__ uint32_t mes_cost(const uint32_t (&c)[MB / 8][MB / 4], const uint8_t *rf, ptrdiff_t stride, bool valid, int x, int y,
-                                             int lane)
-{
-    constexpr int NR = MB / 8, ND = MB / 4;
-    uint32_t v[NR][ND];
-#pragma unroll
-    for (int k = 0; k < NR; k++)
-#pragma unroll
-        for (int j = 0; j < ND; j++)
-            v[k][j] = 0;
-    if (valid) {
-        const uint8_t *p = rf + (ptrdiff_t)(y + (lane & 7)) * stride + x;
-#pragma unroll
-        for (int k = 0; k < NR; k++)
-            __builtin_memcpy(v[k], p + (ptrdiff_t)(8 * k) * stride, MB);
-    }
-    uint32_t part = 0;
-#pragma unroll
-    for (int k = 0; k < NR; k++) {
-        if (KIND == FFHIP_ME_SAD) {
-#pragma unroll
-            for (int j = 0; j < ND; j++)
-                part = __builtin_amdgcn_sad_u8(c[k][j], v[k][j], part);
-        } else {
-#pragma unroll
-            for (int j = 0; j < ND; j += 2)
-                part += mes_satd_row(c[k][j], c[k][j + 1], v[k][j], v[k][j + 1], lane);
-        }
-    }
-    return mes_sum8(part);
-}
 
 template <int MB, int KIND>
 __global__ __launch_bounds__(64 * MES_WAVES) void k_me_search(int method, const uint8_t *cur, const uint8_t *ref, int width, int height,

@@ -6,7 +6,9 @@
 
 #include "kernels/common.h"
 #include "kernels/me_kernels.h"
+#include "kernels/me_search_pred_rules.h"
 #include "kernels/me_search_rules.h"
+#include "kernels/picture_check.h"
 
 extern "C" int ffhip_me_cmp_batch_dev(int kind, int width, int h, const uint8_t *blk1, const int32_t *off1,
                                       const uint8_t *blk2, const int32_t *off2, ptrdiff_t stride, int32_t *out, int n,
@@ -37,17 +39,26 @@ extern "C" int ffhip_me_esa_batch_dev(const uint8_t *cur, const uint8_t *ref, in
 
 /* ---- the filter's per-block searches (kernels/me_search_rules.h) ----------------------------------------------------------------- */
 /* the checks both faces share: 0, FFHIP_EINVAL, or FFHIP_ENOSYS with a text for the two methods that are not per-block functions */
-static int me_search_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
-                           int nframes, int mb_size, int search_param, int cost_kind, const int16_t *mv_out, const uint32_t *cost_out)
+/* what the per-block and the predictive faces check alike, the method apart */
+static int me_search_check_args(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                                int mb_size, int search_param, int cost_kind, const int16_t *mv_out, const uint32_t *cost_out)
 {
-    if (!cur || !ref || !mv_out || !cost_out || method < FFHIP_ME_METHOD_ESA || method > FFHIP_ME_METHOD_UMH || width < 0 || height < 0 ||
-        nframes < 0 || search_param < 0 || (mb_size != 16 && mb_size != 8) || (cost_kind != FFHIP_ME_SAD && cost_kind != FFHIP_ME_SATD) ||
-        stride < width)
+    if (!cur || !ref || !mv_out || !cost_out || width < 0 || height < 0 || nframes < 0 || search_param < 0 || (mb_size != 16 && mb_size != 8) ||
+        (cost_kind != FFHIP_ME_SAD && cost_kind != FFHIP_ME_SATD) || stride < width)
         return FFHIP_EINVAL;
     if (nframes > 1 && height && frame_pitch / (size_t)height < (size_t)stride)     /* frame_pitch < stride * height, without the product */
         return FFHIP_EINVAL;
     const int lg = mb_size == 16 ? 4 : 3;
     if ((int64_t)(width >> lg) * (height >> lg) * nframes > INT_MAX)
+        return FFHIP_EINVAL;
+    return 0;
+}
+
+static int me_search_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                           int nframes, int mb_size, int search_param, int cost_kind, const int16_t *mv_out, const uint32_t *cost_out)
+{
+    if (method < FFHIP_ME_METHOD_ESA || method > FFHIP_ME_METHOD_UMH ||
+        me_search_check_args(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out))
         return FFHIP_EINVAL;
     if (method >= FFHIP_ME_METHOD_EPZS) {
         ffhip_set_error("motion search method %d (%s) needs the neighbouring blocks' vectors of the current and the previous frame: "
@@ -180,6 +191,137 @@ extern "C" int ffhip_me_search_frames_host(int method, const uint8_t *cur, const
                 mv_out[2 * b] = (int16_t)mvx;
                 mv_out[2 * b + 1] = (int16_t)mvy;
                 cost_out[b] = cost_min;
+                blocks++;
+                costs += cost.n;
+            }
+    t_host_blocks = blocks;
+    t_host_costs = costs;
+    return 0;
+}
+
+/* ---- the predictive searches, EPZS and UMH (kernels/me_search_pred_rules.h) ------------------------------------------------------- */
+#define MESP_WHO "ffhip_me_search_pred_batch_dev / _frames_host"
+static int me_search_pred_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                int nframes, int mb_size, int search_param, int cost_kind, const int16_t *prev1, const int16_t *prev2,
+                                const int16_t *mv_out, const uint32_t *cost_out)
+{
+    if (me_search_check_args(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out)) {
+        ffhip_set_error(MESP_WHO ": a NULL cur, ref, mv_out or cost_out, mb_size %d (16 or 8), cost_kind %d (0 or 1), a negative width, height, "
+                        "nframes or search_param, stride < width, frame_pitch < stride * height, or more than 2^31 - 1 blocks", mb_size, cost_kind);
+        return FFHIP_EINVAL;
+    }
+    if (method != FFHIP_ME_METHOD_EPZS && method != FFHIP_ME_METHOD_UMH) {
+        ffhip_set_error(MESP_WHO ": method %d is neither EPZS (8) nor UMH (9); the per-block methods 1 to 7 are ffhip_me_search_batch_dev's", method);
+        return FFHIP_EINVAL;
+    }
+    if (width > 32768 || height > 32768) {
+        ffhip_set_error(MESP_WHO ": %d x %d: positions of a picture above 32768 do not fit the int16 vector fields", width, height);
+        return FFHIP_EINVAL;
+    }
+    if ((uintptr_t)mv_out & 3) {
+        ffhip_set_error(MESP_WHO ": mv_out is not 4-byte aligned (a block's vector travels as one dword)");
+        return FFHIP_EINVAL;
+    }
+    /* mv_out is read back while it is written: it shares no byte with anything else the call reads or writes */
+    const int lg = mb_size == 16 ? 4 : 3;
+    const ptrdiff_t field = (ptrdiff_t)(width >> lg) * (height >> lg) * nframes * 4;
+    const ptrdiff_t planes = nframes && height ? (ptrdiff_t)(nframes - 1) * (ptrdiff_t)frame_pitch + (ptrdiff_t)(height - 1) * stride + width : 0;
+    FFHipSpanSet others;
+    others.add(ffhip_plane_span(cur, 0, field ? planes : 0, 1));
+    others.add(ffhip_plane_span(ref, 0, field ? planes : 0, 1));
+    others.add(ffhip_plane_span(cost_out, 0, field, 1));
+    if (prev1)
+        others.add(ffhip_plane_span(prev1, 0, field, 1));
+    if (prev2)
+        others.add(ffhip_plane_span(prev2, 0, field, 1));
+    others.seal();
+    if (others.hits(ffhip_plane_span(mv_out, 0, field, 1))) {
+        ffhip_set_error(MESP_WHO ": mv_out overlaps prev1, prev2, cur, ref or cost_out");
+        return FFHIP_EINVAL;
+    }
+    return 0;
+}
+
+extern "C" int ffhip_me_search_pred_batch_dev(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                              size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                              const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out, void *stream)
+{
+    const int r = me_search_pred_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
+                                       prev2, mv_out, cost_out);
+    if (r)
+        return r;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_me_search_pred(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
+                                       prev2, mv_out, cost_out, (hipStream_t)stream);
+}
+
+/* block (bx, by)'s relative vector of a field of absolute positions; NULL: a field of zero vectors */
+static MespVec host_rel(const int16_t *field, size_t b, int bx, int by, int lg)
+{
+    MespVec v = { 0, 0 };
+    return field ? mesp_rel(field[2 * b], field[2 * b + 1], bx, by, lg) : v;
+}
+
+extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                                size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                                const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out)
+{
+    const int r = me_search_pred_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
+                                       prev2, mv_out, cost_out);
+    if (r)
+        return r;
+    const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
+    const bool epzs = method == FFHIP_ME_METHOD_EPZS;
+    const MespVec zero = { 0, 0 };
+    uint64_t blocks = 0, costs = 0;
+    for (int f = 0; f < nframes; f++)
+        for (int by = 0; by < bh; by++)
+            for (int bx = 0; bx < bw; bx++) {
+                const int x_mb = bx << lg, y_mb = by << lg;
+                const size_t b = ((size_t)f * bh + by) * bw + bx;
+                const MesWindow w = mes_window(x_mb, y_mb, search_param, bw, bh, lg);
+                HostCost cost = { cur + (size_t)f * frame_pitch + (ptrdiff_t)y_mb * stride + x_mb, ref + (size_t)f * frame_pitch, stride, mb_size,
+                                  cost_kind, 0 };
+                /* raster order: the neighbours of the current frame are in mv_out already */
+                MespVec left = zero, top = zero, diag = zero, c1 = zero, c2 = zero, pl = zero, pt = zero, pr = zero, pb = zero;
+                if (bx > 0)
+                    left = host_rel(mv_out, b - 1, bx - 1, by, lg);
+                if (by > 0) {
+                    top = host_rel(mv_out, b - bw, bx, by - 1, lg);
+                    if (bx + 1 < bw)
+                        diag = host_rel(mv_out, b - bw + 1, bx + 1, by - 1, lg);
+                    else if (!epzs && bx > 0)
+                        diag = host_rel(mv_out, b - bw - 1, bx - 1, by - 1, lg);
+                }
+                if (epzs) {
+                    c1 = host_rel(prev1, b, bx, by, lg);
+                    c2 = host_rel(prev2, b, bx, by, lg);
+                    if (bx > 0)
+                        pl = host_rel(prev1, b - 1, bx - 1, by, lg);
+                    if (by > 0)
+                        pt = host_rel(prev1, b - bw, bx, by - 1, lg);
+                    if (bx + 1 < bw)
+                        pr = host_rel(prev1, b + 1, bx + 1, by, lg);
+                    if (by + 1 < bh)
+                        pb = host_rel(prev1, b + bw, bx, by + 1, lg);
+                }
+                const MespPred P = mesp_predictors(method, bx, by, bw, bh, left, top, diag, c1, c2, pl, pt, pr, pb);
+                MespState s = mesp_start(method, x_mb, y_mb, search_param);
+                for (uint32_t n = 0, bound = mesp_step_bound(w); !s.done && n < bound; n++) {
+                    uint32_t key = MES_NO_KEY;
+                    for (int i = 0; i < 8; i++) {
+                        int x, y;
+                        if (mesp_candidate(s, w, P, s.pos + i, x, y)) {
+                            const uint32_t k = mes_key(cost(x, y), i);
+                            key = k < key ? k : key;
+                        }
+                    }
+                    mesp_advance(s, w, P, key);
+                }
+                mv_out[2 * b] = (int16_t)s.mvx;
+                mv_out[2 * b + 1] = (int16_t)s.mvy;
+                cost_out[b] = s.cost_min;
                 blocks++;
                 costs += cost.n;
             }

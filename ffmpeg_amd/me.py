@@ -2,7 +2,7 @@
 from . import _lib
 
 SAD, SATD = 0, 1
-# the filter's search methods (== AV_ME_METHOD_*); EPZS and UMH are refused by name: they need the neighbouring blocks' vectors
+# the filter's search methods (== AV_ME_METHOD_*); EPZS and UMH take the neighbouring blocks' vectors: search_pred_batch()
 ESA, TSS, TDLS, NTSS, FSS, DS, HEXBS, EPZS, UMH = range(1, 10)
 
 
@@ -43,6 +43,33 @@ def search_frames_host(method, cur, ref, width, height, stride, frame_pitch, nfr
     _lib.check(L.ffhip_me_search_frames_host(method, cur.ctypes.data, ref.ctypes.data, width, height, stride, frame_pitch, nframes,
                                              mb_size, search_param, cost_kind, mv_out.ctypes.data, cost_out.ctypes.data),
                "ffhip_me_search_frames_host")
+    blocks, costs = C.c_uint64(), C.c_uint64()
+    L.ffhip_me_search_host_counts(C.byref(blocks), C.byref(costs))
+    return blocks.value, costs.value
+
+
+def search_pred_batch(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1, prev2,
+                      mv_out, cost_out, stream=None):
+    """The filter's predictive search `method` (EPZS or UMH) of every mb_size block of `cur` in `ref`, nframes independent pairs in
+    one launch; tensors on the device, outputs as esa_batch().  prev1 / prev2: the vector fields (laid out as mv_out) of the previous
+    and the one-before-previous pair, or None for zero vectors."""
+    p = lambda t: None if t is None else t.data_ptr()
+    return _lib.check(_lib.lib().ffhip_me_search_pred_batch_dev(method, cur.data_ptr(), ref.data_ptr(), width, height, stride, frame_pitch,
+                                                                nframes, mb_size, search_param, cost_kind, p(prev1), p(prev2),
+                                                                mv_out.data_ptr(), cost_out.data_ptr(), _stream(stream)),
+                      "ffhip_me_search_pred_batch_dev")
+
+
+def search_pred_frames_host(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1, prev2,
+                            mv_out, cost_out):
+    """The same rules on the CPU (device-free): numpy arrays (uint8 planes, int16 vectors, uint32 costs), prev1 / prev2 arrays or
+    None.  Returns (blocks searched, costs evaluated)."""
+    import ctypes as C
+    L = _lib.lib()
+    p = lambda a: None if a is None else a.ctypes.data
+    _lib.check(L.ffhip_me_search_pred_frames_host(method, cur.ctypes.data, ref.ctypes.data, width, height, stride, frame_pitch, nframes,
+                                                  mb_size, search_param, cost_kind, p(prev1), p(prev2), mv_out.ctypes.data,
+                                                  cost_out.ctypes.data), "ffhip_me_search_pred_frames_host")
     blocks, costs = C.c_uint64(), C.c_uint64()
     L.ffhip_me_search_host_counts(C.byref(blocks), C.byref(costs))
     return blocks.value, costs.value

@@ -2926,8 +2926,8 @@ int ffhip_me_esa_batch_dev(const uint8_t *cur, const uint8_t *ref, int width, in
 #define FFHIP_ME_METHOD_FSS   5
 #define FFHIP_ME_METHOD_DS    6
 #define FFHIP_ME_METHOD_HEXBS 7
-#define FFHIP_ME_METHOD_EPZS  8   /* refused: FFHIP_ENOSYS */
-#define FFHIP_ME_METHOD_UMH   9   /* refused: FFHIP_ENOSYS */
+#define FFHIP_ME_METHOD_EPZS  8   /* ffhip_me_search_pred_batch_dev(); refused by the per-block face: FFHIP_ENOSYS */
+#define FFHIP_ME_METHOD_UMH   9   /* the same */
 /**
  * The filter's per-block searches (what vf_mestimate's SEARCH_MV(method) runs over a frame pair), every block of nframes pairs in one
  * launch on `stream`.  Geometry, frame addressing, metrics and outputs are ffhip_me_esa_batch_dev()'s: log2mb = log2(mb_size),
@@ -2970,9 +2970,65 @@ int ffhip_me_search_batch_dev(int method, const uint8_t *cur, const uint8_t *ref
 int ffhip_me_search_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
                                 size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
                                 int16_t *mv_out, uint32_t *cost_out);
-/** What the calling thread's last successful ffhip_me_search_frames_host() did: the blocks it searched and the costs it evaluated
- *  (the start of each block included).  Either pointer may be NULL. */
+/** What the calling thread's last successful ffhip_me_search_frames_host() or ffhip_me_search_pred_frames_host() did: the blocks it
+ *  searched and the costs it evaluated (the start of each block included).  Either pointer may be NULL. */
 void ffhip_me_search_host_counts(uint64_t *blocks, uint64_t *costs);
+
+/**
+ * The filter's two predictive searches, EPZS (8, vf_minterpolate's default) and UMH (9), every block of nframes pairs in one launch on
+ * `stream`.  Geometry, frame addressing, metrics, window and outputs are ffhip_me_search_batch_dev()'s: mv_out holds absolute best
+ * positions, cost_out their costs.  A block takes the vectors of its left, top and top-right neighbours of the same pair, so the blocks
+ * of a pair are searched in wavefront order (one wave per block row, kernels/row_handoff.h); the nframes pairs of a call are independent
+ * of each other (different streams, or the two directions of one frame).
+ *
+ * prev1 / prev2: the vector fields of the previous and of the one-before-previous frame pair (the filter's mv_table[1] and
+ * mv_table[2]) in the layout of mv_out: nframes fields of b_w * b_h absolute positions.  rel(b), a block's relative vector, is its
+ * position minus the block's origin (x_mb, y_mb); rel1 and rel2 are those of prev1 and prev2.  Either may be NULL: a field of zero
+ * vectors (the filter's zero-initialised tables at the first frame).  A caller chains a sequence by rotating three buffers, one call per
+ * frame on one stream.  UMH reads neither.  Any int16 content is legal: relative vectors are formed in 32 bits, and a candidate outside
+ * the window is refused by COST_P_MV as always.
+ *
+ * The rules below are RESTATED, NOT CHECKED AGAINST THE SOURCE (libavfilter/motion_estimation.c and vf_mestimate.c were not at hand);
+ * this text is the definition the tests pin (kernels/me_search_pred_rules.h is its one implementation, tests/me_pred_search_model.py the
+ * model written from it).  cost, COST_MV (strict <), COST_P_MV (only inside the window), dia1 and hex2 are those of
+ * ffhip_me_search_batch_dev() above.
+ *   Start, both methods: mv = (x_mb, y_mb), cost_min is "none yet" and the first cost evaluated always takes it; there is NO early
+ *     return at cost 0.  Predictor (0,0) is always evaluated and always lies in the window, so every block ends with a real cost.
+ *   Predictor lists, as vf_mestimate fills them — entries are simply appended, duplicates stay and are evaluated again:
+ *     EPZS  P0 = (0,0); rel(left block) if bx > 0; rel(top block) if by > 0; rel(top-right block) if by > 0 && bx + 1 < b_w.  The median
+ *           is taken from P0 as it stands at that point, n its count, mid the median of three per component: n == 4:
+ *           mid(P0[1], P0[2], P0[3]); n == 3: mid((0,0), P0[1], P0[2]); n == 2: P0[1]; otherwise (0,0).  Then rel1(b), the collocated
+ *           block of prev1, is appended to P0.  P1 = the accelerator 2 * rel1(b) - rel2(b); rel1 of the left neighbour if bx > 0; of the
+ *           top neighbour if by > 0; of the right neighbour if bx + 1 < b_w; of the bottom neighbour if by + 1 < b_h.
+ *     UMH   P0 = (0,0); rel(left block) if bx > 0; if by > 0: rel(top block), then rel(top-right block) if bx + 1 < b_w, else
+ *           rel(top-left block) if bx > 0.  The median by the same rule.  No P1.
+ *   EPZS (8): COST_P_MV(origin + median); each entry of P0 in order; each entry of P1 in order (all as origin + entry, through
+ *     COST_P_MV); then do { (x, y) = mv; the 4 of dia1 round (x, y); } while (mv != (x, y)).
+ *   UMH  (9), R = search_param:
+ *     1. the median, then each entry of P0;
+ *     2. the cross, (x, y) = mv: for (d = 1; d <= R; d += 2) { (x - d, y); (x + d, y); if (d <= R / 2) { (x, y - d); (x, y + d); } };
+ *     3. the 5 x 5 raster with COST_MV, bounds from mv as it is after the cross: for y = max(y_min, mv.y - 2) .. min(mv.y + 2, y_max),
+ *        for x likewise (mv's own position is evaluated again);
+ *     4. the rings, (x, y) = mv: for (d = 1; d <= R / 4; d++) entries 1 .. 15 of hex4, scaled by d;
+ *        hex4 = (-4,-2) (-4,-1) (-4,0) (-4,1) (-4,2) (4,-2) (4,-1) (4,0) (4,1) (4,2) (-2,3) (0,4) (2,3) (-2,-3) (0,-4) (2,-3);
+ *        entry 0 is never evaluated;
+ *     5. do { (x, y) = mv; the 6 of hex2 round (x, y); } while (mv != (x, y));
+ *     6. the 4 of dia1 round the last (x, y).
+ *   The d loops may stop at the first d beyond which every candidate lies outside the window: what is left out is refused anyway, so
+ *   vectors, costs and cost counts do not change, and the work is bounded for any search_param >= 0.
+ * FFHIP_EINVAL (before any device check, each with a text): what ffhip_me_search_batch_dev() refuses; a method other than 8
+ * or 9; a width or height above 32768 (positions would not fit int16); mv_out not 4-byte aligned; mv_out sharing a byte with prev1,
+ * prev2, cur, ref or cost_out.  FFHIP_ENOSYS without a device, after the checks.  A lost hand-off between rows (never in a correct run)
+ * is reported by ffhip_stream_synchronize() as FFHIP_EIO.
+ */
+int ffhip_me_search_pred_batch_dev(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                   size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                   const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free), blocks in raster order: the same arguments but the stream, the
+ *  same refusals but the one for a missing device, the same bytes. */
+int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                     size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                     const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out);
 
 /* ------------------------------------------------------------------------------------------ */
 /* libavutil: av_tx float MDCT                                                               */

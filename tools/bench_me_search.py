@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Times the filter's per-block motion searches (ffhip_me_search_batch_dev, methods TSS .. HEXBS) beside the exhaustive face
-(ffhip_me_esa_batch_dev) on 3840 x 2160 frame pairs, 8 pairs per launch, 16 x 16 blocks, at search_param 7 and 32, SAD and SATD.
+"""Times the filter's per-block motion searches (ffhip_me_search_batch_dev, methods TSS .. HEXBS) and its predictive ones
+(ffhip_me_search_pred_batch_dev, EPZS and UMH) beside the exhaustive face (ffhip_me_esa_batch_dev) on 3840 x 2160 frame pairs, 8 pairs
+per launch, 16 x 16 blocks, at search_param 7 and 32, SAD and SATD.
 
 Input: a smooth texture (box-filtered noise, stretched to the full range), the current frame = the reference moved by (3, -2) plus
 noise of +-2: uniform noise alone has no slope for a pattern search to follow.  Per row: milliseconds per frame pair (median of
@@ -8,6 +9,12 @@ noise of +-2: uniform noise alone has no slope for a pattern search to follow.  
 the windows, MB-searches/s, and the mean number of costs a block evaluates — the counters of ffhip_me_search_frames_host() on the FIRST
 pair of the same input (the exhaustive rows: the window sizes, from the geometry).  The last column compares with the exhaustive face
 at the same search_param and metric, from the same run.
+
+EPZS and UMH search a pair in wavefront order (one wave per block row, each two blocks behind the row above), so a pair's time is a
+chain of about b_w + 2 * b_h blocks, and pairs of one launch overlap: their rows come twice, at 8 pairs per launch and ("/1") at 1 pair
+per launch, the latter with the chain's time per block.  prev1 = prev2 = the vectors EPZS finds without them (a sequence at rest).  The
+last section runs EPZS's predictor list in plain order (the measurement build's FFHIP_ME_PRED_ORDER=plain) against the overlapped one,
+both from the measurement build.
 
     python tools/bench_me_search.py [--out profiles/me_search_bench.txt]
 """
@@ -20,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 W, H, NF, MB = 3840, 2160, 8, 16
-NAMES = {1: "esa", 2: "tss", 3: "tdls", 4: "ntss", 5: "fss", 6: "ds", 7: "hexbs"}
+NAMES = {1: "esa", 2: "tss", 3: "tdls", 4: "ntss", 5: "fss", 6: "ds", 7: "hexbs", 8: "epzs", 9: "umh"}
 
 
 def make_input(torch):
@@ -58,6 +65,59 @@ def timed(torch, call, window, rounds):
     return out
 
 
+def pred_rows(torch, np, me, a, cur, ref, hcur, href, mv, cost, hmv, hcost, kind, kname, R, esa_ms):
+    """the EPZS and UMH rows of one metric and search_param: 8 pairs per launch, then 1 pair per launch"""
+    nb = (W // MB) * (H // MB)
+    out = []
+    prev = torch.empty_like(mv)
+    me.search_pred_batch(me.EPZS, cur, ref, W, H, W, W * H, NF, MB, R, kind, None, None, prev, cost)
+    torch.cuda.synchronize()
+    hprev = prev[0].cpu().numpy()
+    for method in (me.EPZS, me.UMH):
+        blocks, costs = me.search_pred_frames_host(method, hcur, href, W, H, W, W * H, 1, MB, R, kind, hprev, hprev, hmv, hcost)
+        me.search_pred_batch(method, cur, ref, W, H, W, W * H, NF, MB, R, kind, prev, prev, mv, cost)
+        torch.cuda.synchronize()
+        assert np.array_equal(mv[0].cpu().numpy(), hmv) and np.array_equal(cost[0].cpu().numpy().view(np.uint32), hcost), \
+            "the device and the host face differ"
+        for nf in (NF, 1):
+            call = lambda: me.search_pred_batch(method, cur, ref, W, H, W, W * H, nf, MB, R, kind, prev, prev, mv, cost)
+            t = [x / nf for x in timed(torch, call, a.window, a.rounds)]
+            ms = statistics.median(t)
+            out.append("%-6s %-5s %3d %12.4f %8.4f..%-8.4f %16.4g %12.1f %8.3f"
+                       % (NAMES[method] + ("" if nf == NF else "/1"), kname, R, ms, min(t), max(t), nb / (ms * 1e-3), costs / blocks, ms / esa_ms))
+            if nf == 1:
+                out[-1] += "   chain: %.2f us per block over b_w + 2 * b_h = %d blocks" % (ms * 1e3 / (W // MB + 2 * (H // MB)), W // MB + 2 * (H // MB))
+            print(out[-1], flush=True)
+    return out
+
+
+def order_rows(torch, a, cur, ref, mv, cost):
+    """EPZS, SAD: the predictor list in plain order behind the wait against the overlapped order, both from the measurement build"""
+    from ffmpeg_amd import _lib, me
+    out = ["# EPZS predictor order (measurement build, SAD): ms per pair at 8 pairs and at 1 pair per launch"]
+    _lib.select("measure")
+    try:
+        prev = torch.empty_like(mv)
+        for R in (7, 32):
+            me.search_pred_batch(me.EPZS, cur, ref, W, H, W, W * H, NF, MB, R, me.SAD, None, None, prev, cost)
+            torch.cuda.synchronize()
+            for order in ("overlapped", "plain"):
+                if order == "plain":
+                    os.environ["FFHIP_ME_PRED_ORDER"] = "plain"
+                else:
+                    os.environ.pop("FFHIP_ME_PRED_ORDER", None)
+                ms = []
+                for nf in (NF, 1):
+                    call = lambda: me.search_pred_batch(me.EPZS, cur, ref, W, H, W, W * H, nf, MB, R, me.SAD, prev, prev, mv, cost)
+                    ms.append(statistics.median(x / nf for x in timed(torch, call, a.window, a.rounds)))
+                out.append("epzs   sad   %3d %-10s %12.4f (8 pairs) %12.4f (1 pair)" % (R, order, ms[0], ms[1]))
+                print(out[-1], flush=True)
+    finally:
+        os.environ.pop("FFHIP_ME_PRED_ORDER", None)
+        _lib.select("product")
+    return out
+
+
 def esa_costs_per_block(R):
     """the start plus the window, averaged over the blocks of a frame"""
     bw, bh = W // MB, H // MB
@@ -86,6 +146,7 @@ def main():
     lines = ["# tools/bench_me_search.py on %s: %d pairs of %d x %d per launch, %d x %d blocks; ms per pair = median of %d windows of >= %.2f s"
              % (torch.cuda.get_device_name(0), NF, W, H, MB, MB, a.rounds, a.window),
              "# costs/block: the host face's counters on the first pair (esa: from the window sizes); x esa: this row's time over esa's at the same R and metric",
+             "# epzs, umh: blocks in wavefront order; name/1: 1 pair per launch, with the time per block of the b_w + 2 * b_h chain; prev1 = prev2 = EPZS's vectors without them",
              "%-6s %-5s %3s %12s %18s %16s %12s %8s" % ("method", "cost", "R", "ms/pair", "windows min..max", "MB-searches/s", "costs/block", "x esa")]
     for kind, kname in ((me.SAD, "sad"), (me.SATD, "satd")):
         for R in (7, 32):
@@ -109,6 +170,9 @@ def main():
                 lines.append("%-6s %-5s %3d %12.4f %8.4f..%-8.4f %16.4g %12.1f %8.3f"
                              % (NAMES[method], kname, R, ms, min(t), max(t), nb / (ms * 1e-3), per_block, ms / esa_ms))
                 print(lines[-1], flush=True)
+                if method == me.HEXBS:
+                    lines.extend(pred_rows(torch, np, me, a, cur, ref, hcur, href, mv, cost, hmv, hcost, kind, kname, R, esa_ms))
+    lines.extend(order_rows(torch, a, cur, ref, mv, cost))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")

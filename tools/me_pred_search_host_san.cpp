@@ -1,0 +1,204 @@
+/*
+ * tools/me_pred_search_host_san.cpp — a stand-alone host program over ffhip_me_search_pred_frames_host() and the argument checks of
+ * ffhip_me_search_pred_batch_dev() for AddressSanitizer and UBSan: the shapes of tests/test_me_pred_search_cpu.py at both block sizes,
+ * both methods and both metrics, three frame pairs each (noise, a shifted copy with exactly matching blocks, a flat one with sparse
+ * marks), with prev fields of small vectors, of any int16 and NULL, in heap blocks exactly as large as the geometry says — the planes end
+ * at height * stride, the fields at the last block — so a read or write outside them is an error the sanitizer reports, and a signed
+ * overflow in the window, the relative vectors or the d loops (search_param up to INT_MAX, vectors of any int16) one UBSan reports; then
+ * the refusals of both faces on pointers they never follow.  CPU only: nothing here touches a device.
+ *
+ * Build and run from the repository root (the faces' file and this one, nothing else of the library):
+ *   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
+ *         --offload-arch=gfx950 -Iinclude -Iffmpeg_amd/csrc -Iffmpeg_amd/csrc/host ffmpeg_amd/csrc/me_api.hip \
+ *         tools/me_pred_search_host_san.cpp -o me_pred_search_host_san && ./me_pred_search_host_san
+ * Prints a checksum of the outputs per case and "ok"; the sanitizer aborts on the first finding.
+ */
+#include <limits.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "ffhip.h"
+
+/* what me_api.hip takes from the rest of the library */
+static char last_error[512];
+extern "C" void ffhip_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(last_error, sizeof(last_error), fmt, ap);
+    va_end(ap);
+}
+int ffhip_have_device(void) { return 0; }
+struct ihipStream_t;
+int ffhip_launch_me_cmp(int, int, int, const uint8_t *, const int32_t *, const uint8_t *, const int32_t *, ptrdiff_t, int32_t *, int, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
+int ffhip_launch_me_esa(const uint8_t *, const uint8_t *, int, int, ptrdiff_t, size_t, int, int, int, int, int16_t *, uint32_t *, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
+int ffhip_launch_me_search(int, const uint8_t *, const uint8_t *, int, int, ptrdiff_t, size_t, int, int, int, int, int16_t *, uint32_t *, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
+
+int ffhip_launch_me_search_pred(int, const uint8_t *, const uint8_t *, int, int, ptrdiff_t, size_t, int, int, int, int, const int16_t *, const int16_t *,
+                                int16_t *, uint32_t *, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
+
+static uint32_t rnd_state = 24680;
+static uint32_t rnd(void)
+{
+    rnd_state = rnd_state * 1664525u + 1013904223u;
+    return rnd_state >> 8;
+}
+
+/* n bytes exactly: the byte after them is the sanitizer's */
+static uint8_t *block(size_t n)
+{
+    uint8_t *p = static_cast<uint8_t *>(malloc(n ? n : 1));
+    if (!p)
+        abort();
+    return p;
+}
+
+static int run(int w, int h, int pad, int mb, int R)
+{
+    const int nf = 3, stride = w + pad, bw = w / mb, bh = h / mb;
+    const size_t plane = (size_t)h * stride, nb = (size_t)nf * bw * bh;
+    uint8_t *cur = block(nf * plane), *ref = block(nf * plane);
+    int16_t *mv = reinterpret_cast<int16_t *>(block(nb * 4)), *small1 = reinterpret_cast<int16_t *>(block(nb * 4));
+    int16_t *small2 = reinterpret_cast<int16_t *>(block(nb * 4)), *any1 = reinterpret_cast<int16_t *>(block(nb * 4));
+    int16_t *any2 = reinterpret_cast<int16_t *>(block(nb * 4));
+    uint32_t *cost = reinterpret_cast<uint32_t *>(block(nb * 4));
+    for (size_t i = 0; i < plane; i++) {
+        ref[i] = (uint8_t)rnd();
+        cur[i] = (uint8_t)rnd();                                            /* frame 0: noise against noise */
+        ref[plane + i] = (uint8_t)(rnd() % 7 ? 100 + i % 23 : rnd());
+        ref[2 * plane + i] = (uint8_t)(i % 37 ? 128 : 130);                /* frame 2: flat with sparse marks */
+    }
+    const int rs = R < 8 ? R : 8, dx = (int)(rnd() % (2 * rs + 1)) - rs;
+    for (size_t i = 0; i < plane; i++) {                                    /* frame 1: a shifted copy, and blocks that match exactly */
+        const ptrdiff_t j = (ptrdiff_t)i + dx;
+        cur[plane + i] = i < (size_t)(2 * mb) * stride || j < 0 || j >= (ptrdiff_t)plane ? ref[plane + i] : ref[plane + j];
+        cur[2 * plane + i] = (uint8_t)((i + 3) % 37 ? 128 : 130);
+    }
+    for (size_t b = 0; b < nb; b++)
+        for (int k = 0; k < 2; k++) {
+            const int o = k ? (int)(b / bw % bh) * mb : (int)(b % bw) * mb;
+            small1[2 * b + k] = (int16_t)(o + (int)(rnd() % 13) - 6);
+            small2[2 * b + k] = (int16_t)(o + (int)(rnd() % 13) - 6);
+            any1[2 * b + k] = (int16_t)rnd();
+            any2[2 * b + k] = (int16_t)rnd();
+        }
+    int bad = 0;
+    for (int method = FFHIP_ME_METHOD_EPZS; method <= FFHIP_ME_METHOD_UMH; method++)
+        for (int kind = FFHIP_ME_SAD; kind <= FFHIP_ME_SATD; kind++)
+            for (int prev = 0; prev < 3; prev++) {
+                const int16_t *p1 = prev == 0 ? small1 : prev == 1 ? any1 : nullptr, *p2 = prev == 0 ? small2 : prev == 1 ? any2 : nullptr;
+                memset(mv, 0x5A, nb * 4);
+                memset(cost, 0x5A, nb * 4);
+                const int r = ffhip_me_search_pred_frames_host(method, cur, ref, w, h, stride, plane, nf, mb, R, kind, p1, p2, mv, cost);
+                uint64_t blocks = 0, costs = 0;
+                ffhip_me_search_host_counts(&blocks, &costs);
+                uint32_t sum = 0;
+                for (size_t b = 0; b < nb; b++) {
+                    sum = sum * 31 + (uint32_t)mv[2 * b] * 65537u + (uint32_t)mv[2 * b + 1] + cost[b];
+                    const int bx = (int)(b % bw) * mb, by = (int)(b / bw % bh) * mb;
+                    bad |= mv[2 * b] < 0 || mv[2 * b] > (bw - 1) * mb || mv[2 * b + 1] < 0 || mv[2 * b + 1] > (bh - 1) * mb;
+                    bad |= abs(mv[2 * b] - bx) > R || abs(mv[2 * b + 1] - by) > R;          /* the window */
+                    bad |= cost[b] == 0x5A5A5A5Au;                                          /* every block ends with a real cost */
+                }
+                bad |= r != 0 || blocks != nb || costs < 2 * nb;
+                printf("%3d x %3d pad %d mb %2d R %10d method %d kind %d prev %d: rc %d, %llu costs, checksum %08x\n", w, h, pad, mb, R, method, kind,
+                       prev, r, (unsigned long long)costs, sum);
+            }
+    free(cur); free(ref); free(mv); free(cost); free(small1); free(small2); free(any1); free(any2);
+    return bad;
+}
+
+/* the checks of both faces: pointers into arenas that are never dereferenced when the call is refused */
+static int refusals(void)
+{
+    static uint8_t arena[4 * 64 * 48];
+    uint8_t *cur = arena, *ref = arena + 2 * 64 * 48;
+    alignas(4) static int16_t fields[4][2 * 12 * 2 + 2];
+    static uint32_t cost[2 * 12];
+    int bad = 0;
+    struct Args { int method; const uint8_t *cur, *ref; int w, h; ptrdiff_t stride; size_t pitch; int nf, mb, R, kind; const int16_t *p1, *p2; int16_t *mv; uint32_t *cost; };
+    const Args good = { FFHIP_ME_METHOD_EPZS, cur, ref, 64, 48, 64, 64 * 48, 2, 16, 7, FFHIP_ME_SAD, fields[1], fields[2], fields[0], cost };
+    auto expect = [&](int want_host, int want_dev, Args a, const char *what, const char *word) {
+        last_error[0] = 0;
+        const int rh = ffhip_me_search_pred_frames_host(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.p1, a.p2, a.mv, a.cost);
+        const bool th = !word || strstr(last_error, word);
+        last_error[0] = 0;
+        const int rd = ffhip_me_search_pred_batch_dev(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.p1, a.p2, a.mv, a.cost, nullptr);
+        const bool td = !word || strstr(last_error, word);
+        if (rh != want_host || rd != want_dev || !th || !td) {
+            printf("refusals: %s: host rc %d (expected %d), dev rc %d (expected %d), text \"%s\"\n", what, rh, want_host, rd, want_dev, last_error);
+            bad = 1;
+        }
+    };
+    Args a = good;
+    expect(0, FFHIP_ENOSYS, a, "a well-formed call", nullptr);
+#define BAD(field, value, what, word) a = good; a.field = value; expect(FFHIP_EINVAL, FFHIP_EINVAL, a, what, word)
+    BAD(cur, nullptr, "a NULL cur", "NULL");
+    BAD(ref, nullptr, "a NULL ref", "NULL");
+    BAD(mv, nullptr, "a NULL mv_out", "NULL");
+    BAD(cost, nullptr, "a NULL cost_out", "NULL");
+    for (int m = 0; m <= 10; m++)
+        if (m != FFHIP_ME_METHOD_EPZS && m != FFHIP_ME_METHOD_UMH) {
+            BAD(method, m, "a method other than 8 or 9", "neither EPZS");
+        }
+    BAD(mb, 4, "mb_size 4", "mb_size");
+    BAD(mb, 32, "mb_size 32", "mb_size");
+    BAD(kind, 2, "cost_kind 2", "cost_kind");
+    BAD(kind, -1, "cost_kind -1", "cost_kind");
+    BAD(w, -1, "a negative width", "negative");
+    BAD(h, -1, "a negative height", "negative");
+    BAD(nf, -1, "a negative nframes", "negative");
+    BAD(R, -1, "a negative search_param", "negative");
+    BAD(stride, 63, "stride < width", "stride");
+    BAD(stride, -64, "a negative stride", "stride");
+    BAD(pitch, 64 * 48 - 1, "frame_pitch < stride * height", "frame_pitch");
+    BAD(nf, INT_MAX, "more blocks than an int counts", "blocks");
+    BAD(mv, fields[0] + 1, "mv_out not 4-byte aligned", "4-byte aligned");
+    BAD(p1, fields[0], "mv_out == prev1", "overlaps");
+    BAD(p2, fields[0] + 46, "mv_out overlapping prev2", "overlaps");
+    BAD(cost, reinterpret_cast<uint32_t *>(fields[0] + 2), "mv_out overlapping cost_out", "overlaps");
+    BAD(mv, reinterpret_cast<int16_t *>(arena + 64), "mv_out inside cur", "overlaps");
+    BAD(mv, reinterpret_cast<int16_t *>(arena + 4 * 64 * 48 - 4), "mv_out at the last samples of ref", "overlaps");
+    a = good; a.w = 32784; a.stride = 32784; a.h = 16; a.nf = 1; expect(FFHIP_EINVAL, FFHIP_EINVAL, a, "a width above 32768", "32784");
+    a = good; a.h = 32776; a.w = 16; a.stride = 16; a.nf = 1; expect(FFHIP_EINVAL, FFHIP_EINVAL, a, "a height above 32768", "32776");
+#undef BAD
+    a = good; a.nf = 0; expect(0, FFHIP_ENOSYS, a, "no frames", nullptr);
+    a = good; a.w = 15; expect(0, FFHIP_ENOSYS, a, "no whole block", nullptr);
+    a = good; a.nf = 1; a.pitch = 0; expect(0, FFHIP_ENOSYS, a, "one frame, no pitch", nullptr);
+    a = good; a.p1 = nullptr; a.p2 = nullptr; expect(0, FFHIP_ENOSYS, a, "NULL prev fields", nullptr);
+    a = good; a.p2 = a.p1; expect(0, FFHIP_ENOSYS, a, "prev1 == prev2", nullptr);
+    return bad;
+}
+
+int main(void)
+{
+    static const int shapes[9][5] = { { 64, 48, 0, 16, 7 }, { 52, 36, 1, 16, 5 }, { 16, 64, 0, 16, 7 }, { 40, 8, 0, 8, 3 }, { 32, 48, 0, 16, 4 },
+                                      { 72, 56, 0, 16, 0 }, { 64, 64, 0, 8, 1 }, { 96, 80, 3, 16, 32 }, { 64, 48, 0, 8, 9 } };
+    int bad = 0;
+    for (int i = 0; i < 9; i++)
+        for (int k = 0; k < 2; k++) {
+            const int mb = k ? 24 - shapes[i][3] : shapes[i][3];
+            if (shapes[i][0] >= mb && shapes[i][1] >= mb)
+                bad |= run(shapes[i][0], shapes[i][1], shapes[i][2], mb, shapes[i][4]);
+        }
+    bad |= run(64, 48, 0, 16, INT_MAX);         /* the window, the cross and the rings without overflow or an endless loop */
+    bad |= run(40, 24, 5, 8, 1 << 30);
+    bad |= refusals();
+    puts(bad ? "FAILED" : "ok");
+    return bad;
+}
