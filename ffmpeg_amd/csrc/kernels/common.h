@@ -146,8 +146,8 @@ struct FFHipPerDeviceOnce {
 
 /* experiment / fault-injection switches exist only in the measurement build (libffhip_measure.so, -DFFHIP_MEASURE): the product
  * library reads no environment variable, so nothing a user exports can change its pixels */
-#ifdef FFHIP_MEASURE
 #include <stdlib.h>
+#ifdef FFHIP_MEASURE
 #define FFHIP_KNOB(name) getenv(name)
 #else
 #define FFHIP_KNOB(name) ((const char *)0)
@@ -159,6 +159,14 @@ static inline bool knob_is(const char *name, char v)
     const char *e = FFHIP_KNOB(name);
     (void)name;
     return e && e[0] == v;
+}
+
+/* a knob holding a number above 0, or `dflt` (always, in the product build) */
+static inline int knob_int(const char *name, int dflt)
+{
+    const char *e = FFHIP_KNOB(name);
+    (void)name;
+    return e && atoi(e) > 0 ? atoi(e) : dflt;
 }
 
 #endif

@@ -45,27 +45,20 @@ __global__ __launch_bounds__(64 * MES_WAVES) void k_me_search(int method, const 
         const int x_mb = bx << LOG2, y_mb = by << LOG2;
         const uint8_t *cf = cur + (size_t)f * frame_pitch, *rf = ref + (size_t)f * frame_pitch;
         uint32_t c[NR][MB / 4];
-        {
-            const uint8_t *p = cf + (ptrdiff_t)(y_mb + (lane & 7)) * stride + x_mb;
-#pragma unroll
-            for (int k = 0; k < NR; k++)
-                __builtin_memcpy(c[k], p + (ptrdiff_t)(8 * k) * stride, MB);
-        }
+        mes_load_cur<MB>(c, cf, stride, x_mb, y_mb, lane);
         const MesWindow w = mes_window(x_mb, y_mb, R, bw, bh, LOG2);
         /* the start: every candidate group evaluates the centre */
         const uint32_t cost0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mes_cost<MB, KIND>(c, rf, stride, true, x_mb, y_mb, lane));
         MesState s = mes_start(method, x_mb, y_mb, R, cost0);
+        /* the text of mes_run(), not a call: through the call the compiler joins the loop's two exit tests differently and emits one
+         * conditional branch more per instantiation (docs/KERNELS.md 5.7b), and a block's time here is its chain of scalar steps */
         const uint32_t bound = mes_step_bound(w);
         for (uint32_t n = 0; !s.done && n < bound; n++) {
             const MesStep st = mes_step(s);
             int x, y;
             const bool valid = mes_candidate(s, st, w, cand, x, y) && cand < st.n;
             const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-            uint32_t key = valid ? mes_key(cost, cand) : MES_NO_KEY;
-            key = min(key, (uint32_t)mes_dpp<MES_DPP_ROR8>((int)key));
-            const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, 0), k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, 16);
-            const uint32_t k2 = (uint32_t)__builtin_amdgcn_readlane((int)key, 32), k3 = (uint32_t)__builtin_amdgcn_readlane((int)key, 48);
-            mes_advance(s, st, w, min(min(k0, k1), min(k2, k3)));
+            mes_advance(s, st, w, mes_wave_min(valid ? mes_key(cost, cand) : MES_NO_KEY));
         }
         if (lane == 0) {
             mv_out[2 * (size_t)b] = (int16_t)s.mvx;
@@ -84,20 +77,13 @@ int ffhip_launch_me_search(int method, const uint8_t *cur, const uint8_t *ref, i
         return 0;
     /* as many workgroups as stay resident at 8 waves per SIMD; the rest of the blocks are the waves' next rounds.
      * FFHIP_ME_SEARCH_WGS (measurement build) fixes the number, so that a small picture takes several rounds */
-    int64_t wgs = (int64_t)ffhip_cu_count() * (32 / MES_WAVES);
-    const char *e = FFHIP_KNOB("FFHIP_ME_SEARCH_WGS");
-    if (e && atoi(e) > 0)
-        wgs = atoi(e);
+    int64_t wgs = knob_int("FFHIP_ME_SEARCH_WGS", ffhip_cu_count() * (32 / MES_WAVES));
     if (wgs > (nblocks + MES_WAVES - 1) / MES_WAVES)
         wgs = (nblocks + MES_WAVES - 1) / MES_WAVES;
-#define MES(M, K) hipLaunchKernelGGL((k_me_search<M, K>), dim3((unsigned)wgs), dim3(64 * MES_WAVES), 0, stream, method, cur, ref, width, height, \
-                                     stride, frame_pitch, (uint32_t)nblocks, R, mv_out, cost_out)
-    if (cost_kind == FFHIP_ME_SAD) {
-        if (mb_size == 16) MES(16, FFHIP_ME_SAD); else MES(8, FFHIP_ME_SAD);
-    } else {
-        if (mb_size == 16) MES(16, FFHIP_ME_SATD); else MES(8, FFHIP_ME_SATD);
-    }
-#undef MES
+    mes_dispatch(mb_size, cost_kind, [&](auto mb, auto kind) {
+        hipLaunchKernelGGL((k_me_search<decltype(mb)::value, decltype(kind)::value>), dim3((unsigned)wgs), dim3(64 * MES_WAVES), 0, stream, method,
+                           cur, ref, width, height, stride, frame_pitch, (uint32_t)nblocks, R, mv_out, cost_out);
+    });
     LAUNCH_CHECK();
     return 0;
 }

@@ -4,12 +4,15 @@
  * the candidate's byte-exact address in `ref`, against the current block's rows in registers.  SAD: v_sad_u8 over the dwords.  SATD: the
  * horizontal 8-point transform of a row's differences in the lane, the vertical one across the eight lanes of the candidate, then the
  * absolute sum.  The eight partial sums are added with DPP moves, the butterfly across lanes r and r ^ 4 is a ds_swizzle: no LDS.
- * Device only.
+ * With it what else the two kernels share: the load of the current block, the wave minimum of a step's keys, and the launchers' choice of
+ * a (block size, metric) instantiation.  For the two kernel files only.
  */
 #ifndef FFHIP_ME_SEARCH_COST_H
 #define FFHIP_ME_SEARCH_COST_H
 
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -102,6 +105,40 @@ __device__ __forceinline__ uint32_t mes_cost(const uint32_t (&c)[MB / 8][MB / 4]
         }
     }
     return mes_sum8(part);
+}
+
+/* the lane's rows of the current block at (x_mb, y_mb) of the frame `cf`: what mes_cost() takes as c */
+template <int MB>
+__device__ __forceinline__ void mes_load_cur(uint32_t (&c)[MB / 8][MB / 4], const uint8_t *cf, ptrdiff_t stride, int x_mb, int y_mb, int lane)
+{
+    const uint8_t *p = cf + (ptrdiff_t)(y_mb + (lane & 7)) * stride + x_mb;
+#pragma unroll
+    for (int k = 0; k < MB / 8; k++)
+        __builtin_memcpy(c[k], p + (ptrdiff_t)(8 * k) * stride, MB);
+}
+
+/* the minimum of a key that is uniform over each candidate's eight lanes, in scalar registers: one DPP row rotate, four v_readlane */
+__device__ __forceinline__ uint32_t mes_wave_min(uint32_t key)
+{
+    key = min(key, (uint32_t)mes_dpp<MES_DPP_ROR8>((int)key));
+    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, 0), k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, 16);
+    const uint32_t k2 = (uint32_t)__builtin_amdgcn_readlane((int)key, 32), k3 = (uint32_t)__builtin_amdgcn_readlane((int)key, 48);
+    return min(min(k0, k1), min(k2, k3));
+}
+
+/* the launchers' choice of an instantiation: launch(mb, kind) with std::integral_constants of mb_size (16, else 8) and cost_kind */
+template <class Launch>
+static inline void mes_dispatch(int mb_size, int cost_kind, Launch launch)
+{
+    using Sad = std::integral_constant<int, FFHIP_ME_SAD>;
+    using Satd = std::integral_constant<int, FFHIP_ME_SATD>;
+    using Mb16 = std::integral_constant<int, 16>;
+    using Mb8 = std::integral_constant<int, 8>;
+    if (cost_kind == FFHIP_ME_SAD) {
+        if (mb_size == 16) launch(Mb16(), Sad()); else launch(Mb8(), Sad());
+    } else {
+        if (mb_size == 16) launch(Mb16(), Satd()); else launch(Mb8(), Satd());
+    }
 }
 
 #endif

@@ -14,11 +14,10 @@
  *     (row_handoff.h).  cost_out and the prev fields use plain accesses: nobody else touches them in the launch.
  *   - the critical path of a picture is about b_w + 2 * b_h blocks, each the whole loop body of a wave, so a block's chain of dependent
  *     memory round trips is what counts (fetching the current block and the prev vectors one block ahead was measured and did not
- *     pay: docs/EXPERIMENTS.md).  EPZS
- *     (`overlap`): the costs of (0,0), the left vector, the collocated vector, the accelerator and prev1's four neighbours — eight
- *     candidates, one pass — are evaluated BEFORE the wait, with the current block's loads; the median, top and top-right follow the
- *     wait in a second pass, and the ordered minimum over both carries the list position (the rules header's mesp_advance_list).
- *     Without `overlap` (the measurement build's FFHIP_ME_PRED_ORDER=plain) the list runs in order behind the wait, two steps.
+ *     pay: docs/EXPERIMENTS.md).  EPZS: the costs of (0,0), the left vector, the collocated vector, the accelerator and prev1's four
+ *     neighbours — eight candidates, one pass — are evaluated BEFORE the wait, with the current block's loads; the median, top and
+ *     top-right follow the wait in a second pass, and the ordered minimum over both carries the list position (the rules header's
+ *     mesp_advance_list).  Running the list in order behind the wait, two steps, was measured 14 to 19 % slower and taken out.
  * A lost hand-off sets the slot's fail word and the kernel leaves (ffhip_progress_check reports it).  No LDS, no scratch; every loop is
  * bounded by the rules header's step bound and the hand-off's spin limit.
  */
@@ -34,15 +33,6 @@
 #define MESP_PER_CU 8   /* resident waves per CU the grid counts on */
 
 namespace {
-/* the minimum of a key that is uniform over each candidate's eight lanes, in scalar registers */
-__device__ __forceinline__ uint32_t mesp_wave_min(uint32_t key)
-{
-    key = min(key, (uint32_t)mes_dpp<MES_DPP_ROR8>((int)key));
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, 0), k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, 16);
-    const uint32_t k2 = (uint32_t)__builtin_amdgcn_readlane((int)key, 32), k3 = (uint32_t)__builtin_amdgcn_readlane((int)key, 48);
-    return min(min(k0, k1), min(k2, k3));
-}
-
 /* block (bx, by)'s relative vector of a prev field (NULL: zero vectors); nobody writes the field in the launch */
 __device__ __forceinline__ MespVec mesp_prev_rel(const int16_t *field, size_t b, int bx, int by, int log2mb)
 {
@@ -66,7 +56,7 @@ __device__ __forceinline__ MespVec mesp_row_rel(const int16_t *mv_out, size_t b,
 template <int MB, int KIND>
 __global__ __launch_bounds__(64) void k_me_search_pred(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
                                                        size_t frame_pitch, int npairs, int R, const int16_t *prev1, const int16_t *prev2,
-                                                       int16_t *mv_out, uint32_t *cost_out, int overlap, int *progress_all, int *fail)
+                                                       int16_t *mv_out, uint32_t *cost_out, int *progress_all, int *fail)
 {
     constexpr int LOG2 = MB == 16 ? 4 : 3, NR = MB / 8;
     const int bw = width >> LOG2, bh = height >> LOG2;
@@ -93,68 +83,50 @@ __global__ __launch_bounds__(64) void k_me_search_pred(int method, const uint8_t
         for (int bx = 0; bx < bw; bx++) {
             const int x_mb = bx << LOG2;
             const size_t b = rb + (size_t)bx;
+            const MespNeigh N = mesp_neighbours(method, bx, row, bw, bh);
             /* ---- what needs nothing of the row above: the current block, the prev fields ---- */
             uint32_t c[NR][MB / 4];
-            {
-                const uint8_t *p = cf + (ptrdiff_t)(y_mb + (lane & 7)) * stride + x_mb;
-#pragma unroll
-                for (int k = 0; k < NR; k++)
-                    __builtin_memcpy(c[k], p + (ptrdiff_t)(8 * k) * stride, MB);
-            }
-            MespVec c1 = zero, c2 = zero, pl = zero, pt = zero, pr = zero, pb = zero;
-            if (epzs) {
-                c1 = mesp_prev_rel(prev1, b, bx, row, LOG2);
-                c2 = mesp_prev_rel(prev2, b, bx, row, LOG2);
-                if (bx > 0)
-                    pl = mesp_prev_rel(prev1, b - 1, bx - 1, row, LOG2);
-                if (row > 0)
-                    pt = mesp_prev_rel(prev1, b - (size_t)bw, bx, row - 1, LOG2);
-                if (bx + 1 < bw)
-                    pr = mesp_prev_rel(prev1, b + 1, bx + 1, row, LOG2);
-                if (row + 1 < bh)
-                    pb = mesp_prev_rel(prev1, b + (size_t)bw, bx, row + 1, LOG2);
-            }
+            mes_load_cur<MB>(c, cf, stride, x_mb, y_mb, lane);
+            MespNear v = {};
+            v.left = left;
+            mesp_fetch_prev(v, N, [&](int which, int dbx, int dby) {
+                return mesp_prev_rel(which == 1 ? prev1 : prev2, b + (ptrdiff_t)dby * bw + dbx, bx + dbx, row + dby, LOG2);
+            });
             const MesWindow w = mes_window(x_mb, y_mb, R, bw, bh, LOG2);
             MespState s = mesp_start(method, x_mb, y_mb, R);
             uint32_t key_early = MES_NO_KEY;
-            if (epzs && overlap) {
+            if (epzs) {
                 /* list positions zero, left, collocated, accelerator, prev1's left, top, right, bottom: one per candidate group */
                 const int k = (int)(0xA9876521u >> (4 * cand)) & 15;
-                const MespPred P = mesp_predictors(method, bx, row, bw, bh, left, zero, zero, c1, c2, pl, pt, pr, pb);
+                const MespPred P = mesp_predictors(N, v);
                 int x, y;
                 const bool valid = mesp_candidate(s, w, P, k, x, y);
                 const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
                 key_early = valid ? mesp_list_key(cost, k) : MES_NO_KEY;
             }
             /* ---- the row above has published min(bx + 2, b_w) blocks: its vectors ---- */
-            MespVec top = zero, diag = zero;
-            if (row > 0) {
+            if (mesp_has(N, MESP_TOP)) {
                 const int want = min(bx + 2, bw);
                 if (!ffhip_row_wait(&progress[-1], want, known, fail, lane))
                     return;
-                top = mesp_row_rel(mv_out, b - (size_t)bw, bx, row - 1, LOG2);
-                if (bx + 1 < bw)
-                    diag = mesp_row_rel(mv_out, b - (size_t)bw + 1, bx + 1, row - 1, LOG2);
-                else if (!epzs && bx > 0)
-                    diag = mesp_row_rel(mv_out, b - (size_t)bw - 1, bx - 1, row - 1, LOG2);
+                mesp_fetch_above(v, N, [&](int dbx) { return mesp_row_rel(mv_out, b - (size_t)bw + dbx, bx + dbx, row - 1, LOG2); });
             }
-            const MespPred P = mesp_predictors(method, bx, row, bw, bh, left, top, diag, c1, c2, pl, pt, pr, pb);
-            if (epzs && overlap) {
+            const MespPred P = mesp_predictors(N, v);
+            if (epzs) {
                 /* the median, top, top-right: the rest of the list */
                 const int k = cand == 0 ? MESP_MEDIAN : cand == 1 ? MESP_TOP : cand == 2 ? MESP_DIAG : -1;
                 int x, y;
                 const bool valid = mesp_candidate(s, w, P, k, x, y);
                 const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
                 const uint32_t key = valid ? mesp_list_key(cost, k) : MES_NO_KEY;
-                mesp_advance_list(s, w, P, mesp_wave_min(min(key, key_early)));
+                mesp_advance_list(s, w, P, mes_wave_min(min(key, key_early)));
             }
-            const uint32_t bound = mesp_step_bound(w);
-            for (uint32_t n = 0; !s.done && n < bound; n++) {
+            mesp_run(s, w, P, [&](const MespState &s) {
                 int x, y;
                 const bool valid = mesp_candidate(s, w, P, s.pos + cand, x, y);
                 const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-                mesp_advance(s, w, P, mesp_wave_min(valid ? mes_key(cost, cand) : MES_NO_KEY));
-            }
+                return mes_wave_min(valid ? mes_key(cost, cand) : MES_NO_KEY);
+            });
             /* ---- the block's vector: to the row below, and to the next block of this row ---- */
             if (lane == 0) {
                 ffhip_row_st<uint32_t>(reinterpret_cast<uint8_t *>(mv_out + 2 * b), (uint32_t)(uint16_t)s.mvx | (uint32_t)(uint16_t)s.mvy << 16);
@@ -180,13 +152,8 @@ int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *r
         ffhip_set_error("ffhip_me_search_pred_batch_dev: %d block rows exceed a progress-pool slot", bh);
         return FFHIP_EINVAL;
     }
-    /* FFHIP_ME_PRED_WGS (measurement build) fixes the number of workgroups, so that a small picture takes several ticket rounds;
-     * FFHIP_ME_PRED_ORDER=plain runs EPZS's predictor list in order behind the wait */
-    int cap = ffhip_cu_count() * MESP_PER_CU;
-    const char *e = FFHIP_KNOB("FFHIP_ME_PRED_WGS");
-    if (e && atoi(e) > 0)
-        cap = atoi(e);
-    const int overlap = !knob_is("FFHIP_ME_PRED_ORDER", 'p');
+    /* FFHIP_ME_PRED_WGS (measurement build) fixes the number of workgroups, so that a small picture takes several ticket rounds */
+    const int cap = knob_int("FFHIP_ME_PRED_WGS", ffhip_cu_count() * MESP_PER_CU);
     const size_t blocks = (size_t)bw * (size_t)bh;
     for (int p0 = 0; p0 < nframes; p0 += per) {
         const int n = nframes - p0 < per ? nframes - p0 : per, units = n * bh;
@@ -196,14 +163,10 @@ int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *r
         uint32_t *k0 = cost_out + blocks * (size_t)p0;
         const int r = ffhip_progress_launch(units + 1, stream, "ffhip_me_search_pred_batch_dev: kernel launch", [&](const FFHipProgressSlot &ps) {
             const int grid = units < cap ? units : cap;
-#define MESP(M, K) hipLaunchKernelGGL((k_me_search_pred<M, K>), dim3((unsigned)grid), dim3(64), 0, stream, method, c0, r0, width, height, stride, \
-                                      frame_pitch, n, R, q1, q2, mv0, k0, overlap, ps.prog, ps.fail)
-            if (cost_kind == FFHIP_ME_SAD) {
-                if (mb_size == 16) MESP(16, FFHIP_ME_SAD); else MESP(8, FFHIP_ME_SAD);
-            } else {
-                if (mb_size == 16) MESP(16, FFHIP_ME_SATD); else MESP(8, FFHIP_ME_SATD);
-            }
-#undef MESP
+            mes_dispatch(mb_size, cost_kind, [&](auto mb, auto kind) {
+                hipLaunchKernelGGL((k_me_search_pred<decltype(mb)::value, decltype(kind)::value>), dim3((unsigned)grid), dim3(64), 0, stream, method,
+                                   c0, r0, width, height, stride, frame_pitch, n, R, q1, q2, mv0, k0, ps.prog, ps.fail);
+            });
             return hipGetLastError();
         });
         if (r < 0)

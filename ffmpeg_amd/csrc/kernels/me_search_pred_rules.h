@@ -4,16 +4,13 @@
  * SOURCE: the rules were written down without the reference's source at hand; the statement in include/ffhip.h is the definition the
  * tests pin.  Tables, window and key are me_search_rules.h's.
  *
- * The header owns the predictor list of a block (from its position and the neighbour vectors handed in) and the step machine of the
- * phases.  It does not own how a cost is computed or how a neighbour's vector arrives: k_me_search_pred (me_search_pred.hip, one wave
- * per block row, hand-off between the rows) and ffhip_me_search_pred_frames_host() (me_api.hip, raster order on the CPU) both run
- *
- *     MespPred P = mesp_predictors(method, bx, by, b_w, b_h, left, top, diag, c1, c2, pl, pt, pr, pb);
- *     MespState s = mesp_start(method, x_mb, y_mb, R);
- *     for (uint32_t n = 0; !s.done && n < mesp_step_bound(w); n++) {
- *         key = the minimum of mes_key(cost(x, y), i) over the i < 8 with mesp_candidate(s, w, P, s.pos + i, x, y), MES_NO_KEY if none
- *         mesp_advance(s, w, P, key);
- *     }
+ * The header owns which neighbours a block has (mesp_neighbours) and which of their vectors are fetched (mesp_fetch_prev,
+ * mesp_fetch_above), the predictor list made of them, the step machine of the phases and the loop over the steps, mesp_run().  It does
+ * not own how a cost is computed or how a neighbour's vector arrives: k_me_search_pred (me_search_pred.hip, one wave per block row,
+ * hand-off between the rows) and ffhip_me_search_pred_frames_host() (me_api.hip, raster order on the CPU) both fetch through the two
+ * functions, call mesp_predictors(), mesp_start() and mesp_run(), and differ in the callbacks they hand them alone: how a block's
+ * vector is read, and step_key, the minimum of mes_key(cost(x, y), i) over the i < 8 with mesp_candidate(s, w, P, s.pos + i, x, y),
+ * MES_NO_KEY if there is none.
  *
  * Every phase is an ordered list of candidates round a centre that is fixed during the phase (the predictors round the block's origin;
  * the cross, the 5 x 5 raster, all rings together, one turn of a closing loop round the mv the phase found at its start).  Cutting
@@ -85,29 +82,83 @@ MES_FN MespVec mesp_rel(int px, int py, int bx, int by, int log2mb)
     return v;
 }
 
-/* Block (bx, by) of b_w x b_h.  All vectors are relative ones of the block they belong to; one of a neighbour the block does not
- * have is not looked at.  left, top: of the current frame; diag: the top-right block's, or, for UMH in the last column, the top-left
- * block's.  c1, c2: the collocated block's of prev1 and prev2; pl, pt, pr, pb: prev1's of the four neighbours (EPZS alone; UMH takes
- * nothing of them). */
-MES_FN MespPred mesp_predictors(int method, int bx, int by, int b_w, int b_h, MespVec left, MespVec top, MespVec diag, MespVec c1, MespVec c2,
-                                MespVec pl, MespVec pt, MespVec pr, MespVec pb)
+/* The neighbour rule: which list positions block (bx, by) of b_w x b_h has, and where its "diag" neighbour stands.  This is the one
+ * place that looks at the block's position; whoever fetches a vector or builds the list tests a bit of `have`. */
+struct MespNeigh {
+    uint32_t have;      /* bit k: list position k exists */
+    int diag_dx;        /* the diag neighbour is block (bx + diag_dx, by - 1): the top-right one, or, for UMH in the last column, the top-left */
+};
+
+MES_FN MespNeigh mesp_neighbours(int method, int bx, int by, int b_w, int b_h)
 {
     const bool epzs = method == FFHIP_ME_METHOD_EPZS;
-    const bool hl = bx > 0, ht = by > 0;
-    const bool hd = ht && (bx + 1 < b_w || (!epzs && bx > 0));
+    const bool hl = bx > 0, ht = by > 0, hr = bx + 1 < b_w, hb = by + 1 < b_h;
+    const bool hd = ht && (hr || (!epzs && hl));   /* the top-right block; UMH falls back on the top-left one */
+    MespNeigh N;
+    N.diag_dx = hr ? 1 : -1;
+    N.have = 1u << MESP_MEDIAN | 1u << MESP_ZERO | (uint32_t)hl << MESP_LEFT | (uint32_t)ht << MESP_TOP | (uint32_t)hd << MESP_DIAG;
+    if (epzs)                                       /* UMH takes nothing of the prev fields */
+        N.have |= 1u << MESP_COLLOC | 1u << MESP_ACCEL | (uint32_t)hl << MESP_PLEFT | (uint32_t)ht << MESP_PTOP |
+                  (uint32_t)hr << MESP_PRIGHT | (uint32_t)hb << MESP_PBOTTOM;
+    return N;
+}
+
+MES_FN bool mesp_has(const MespNeigh &N, int k) { return N.have >> k & 1u; }
+
+/* The vectors a block takes of its neighbours, all relative ones of the block they belong to; one of a neighbour the block does not
+ * have stays zero and is not looked at. */
+struct MespNear {
+    MespVec left, top, diag;    /* of the current frame */
+    MespVec c1, c2;             /* the collocated block's of prev1 and prev2 */
+    MespVec pl, pt, pr, pb;     /* prev1's of the left, top, right, bottom neighbour */
+};
+
+/* The two fetch points: the prev fields, which nothing of the current frame writes, and the row above of the current frame (the
+ * kernel waits for it in between).  prev(which, dbx, dby), above(dbx) -> MespVec: block (bx + dbx, by + dby)'s relative vector of
+ * prev`which`, block (bx + dbx, by - 1)'s of the current frame.  `left` is the caller's: the block it searched last, if MESP_LEFT. */
+template <class Prev>
+MES_FN void mesp_fetch_prev(MespNear &v, const MespNeigh &N, Prev prev)
+{
+    if (mesp_has(N, MESP_COLLOC))
+        v.c1 = prev(1, 0, 0);
+    if (mesp_has(N, MESP_ACCEL))
+        v.c2 = prev(2, 0, 0);
+    if (mesp_has(N, MESP_PLEFT))
+        v.pl = prev(1, -1, 0);
+    if (mesp_has(N, MESP_PTOP))
+        v.pt = prev(1, 0, -1);
+    if (mesp_has(N, MESP_PRIGHT))
+        v.pr = prev(1, 1, 0);
+    if (mesp_has(N, MESP_PBOTTOM))
+        v.pb = prev(1, 0, 1);
+}
+
+template <class Above>
+MES_FN void mesp_fetch_above(MespNear &v, const MespNeigh &N, Above above)
+{
+    if (mesp_has(N, MESP_TOP))
+        v.top = above(0);
+    if (mesp_has(N, MESP_DIAG))
+        v.diag = above(N.diag_dx);
+}
+
+/* the list of a block from its neighbours' vectors */
+MES_FN MespPred mesp_predictors(const MespNeigh &N, const MespNear &v)
+{
+    const bool hl = mesp_has(N, MESP_LEFT), ht = mesp_has(N, MESP_TOP), hd = mesp_has(N, MESP_DIAG);
     MespPred P;
-    P.have = 1u << MESP_MEDIAN | 1u << MESP_ZERO | (uint32_t)hl << MESP_LEFT | (uint32_t)ht << MESP_TOP | (uint32_t)hd << MESP_DIAG;
-    P.left = left;
-    P.top = top;
-    P.diag = diag;
+    P.have = N.have;
+    P.left = v.left;
+    P.top = v.top;
+    P.diag = v.diag;
     /* the median of P0 as it stands: (0, 0) and what of left, top, diag the block has, in that order */
     const int n = 1 + hl + ht + hd;
     MespVec a, b;                                   /* P0[1], P0[2] */
-    a = hl ? left : top;                            /* without left, top comes first (a diag implies a top) */
-    b = hl ? (ht ? top : left) : diag;
+    a = hl ? v.left : v.top;                        /* without left, top comes first (a diag implies a top) */
+    b = hl ? (ht ? v.top : v.left) : v.diag;
     if (n == 4) {
-        P.median.x = mesp_mid(left.x, top.x, diag.x);
-        P.median.y = mesp_mid(left.y, top.y, diag.y);
+        P.median.x = mesp_mid(v.left.x, v.top.x, v.diag.x);
+        P.median.y = mesp_mid(v.left.y, v.top.y, v.diag.y);
     } else if (n == 3) {
         P.median.x = mesp_mid(0, a.x, b.x);
         P.median.y = mesp_mid(0, a.y, b.y);
@@ -116,16 +167,13 @@ MES_FN MespPred mesp_predictors(int method, int bx, int by, int b_w, int b_h, Me
     } else {
         P.median.x = P.median.y = 0;
     }
-    P.colloc = c1;
-    P.accel.x = 2 * c1.x - c2.x;
-    P.accel.y = 2 * c1.y - c2.y;
-    P.pleft = pl;
-    P.ptop = pt;
-    P.pright = pr;
-    P.pbottom = pb;
-    if (epzs)
-        P.have |= 1u << MESP_COLLOC | 1u << MESP_ACCEL | (uint32_t)hl << MESP_PLEFT | (uint32_t)ht << MESP_PTOP |
-                  (uint32_t)(bx + 1 < b_w) << MESP_PRIGHT | (uint32_t)(by + 1 < b_h) << MESP_PBOTTOM;
+    P.colloc = v.c1;
+    P.accel.x = 2 * v.c1.x - v.c2.x;
+    P.accel.y = 2 * v.c1.y - v.c2.y;
+    P.pleft = v.pl;
+    P.ptop = v.pt;
+    P.pright = v.pr;
+    P.pbottom = v.pb;
     return P;
 }
 
@@ -318,6 +366,16 @@ MES_FN void mesp_advance(MespState &s, const MesWindow &w, const MespPred &P, ui
     s.pos += 8;
     if (s.pos >= s.n)
         mesp_phase_end(s, w);
+}
+
+/* the search of one block from the state it is given: mesp_start()'s, or what mesp_advance_list() made of it.  step_key(s) ->
+ * uint32_t: the ordered minimum of the step's 8 list entries from s.pos on, or MES_NO_KEY. */
+template <class StepKey>
+MES_FN void mesp_run(MespState &s, const MesWindow &w, const MespPred &P, StepKey step_key)
+{
+    const uint32_t bound = mesp_step_bound(w);
+    for (uint32_t n = 0; !s.done && n < bound; n++)
+        mesp_advance(s, w, P, step_key(s));
 }
 
 /* A whole list of at most 16 entries at once (the predictors): the minimum of mesp_list_key(cost, k) over the entries k evaluated,

@@ -4,18 +4,13 @@
  * ffhip_me_search_batch_dev().  RESTATED, NOT CHECKED AGAINST THE SOURCE: the rules were written down without the reference's source at
  * hand; the statement in include/ffhip.h is the definition the tests pin.
  *
- * The header owns the pattern tables, the window, and per method the ordered candidate list of an evaluation step and the state
- * transition given that step's result.  It does not own how a cost is computed: the kernel of me_search.hip (one wave per block,
- * eight lanes per candidate) and ffhip_me_search_frames_host() (me_api.hip, plain loops on the CPU) both run
+ * The header owns the pattern tables, the window, per method the ordered candidate list of an evaluation step and the state
+ * transition given that step's result, and the loop over the steps, mes_run().  It does not own how a cost is computed: the kernel
+ * of me_search.hip (one wave per block, eight lanes per candidate) and ffhip_me_search_frames_host() (me_api.hip, plain loops on the
+ * CPU) both run mes_run() on the state of mes_start() (the kernel as its text, for the reason given there) and differ in step_key
+ * alone: the minimum of mes_key(cost(x, y), i) over the i < st.n with mes_candidate(s, st, w, i, x, y), MES_NO_KEY if there is none.
  *
- *     MesState s = mes_start(method, x_mb, y_mb, R, cost(x_mb, y_mb));
- *     for (uint32_t n = 0; !s.done && n < mes_step_bound(w); n++) {
- *         const MesStep st = mes_step(s);
- *         key = the minimum of mes_key(cost(x, y), i) over the i < st.n with mes_candidate(s, st, w, i, x, y), MES_NO_KEY if none
- *         mes_advance(s, st, w, key);
- *     }
- *
- * and differ in the middle line alone.  A step holds at most 8 candidates, all round one centre, so they are independent of each
+ * A step holds at most 8 candidates, all round one centre, so they are independent of each
  * other; applying them in table order with a strict comparison (COST_MV) equals taking the minimum of cost << 3 | index and
  * comparing its cost strictly with cost_min: on equal costs the lowest index wins, and an equal cost never displaces the centre.
  * NTSS's first iteration has 16 candidates round one centre (the large ring, then the unit ring): it is two steps.
@@ -216,6 +211,17 @@ MES_FN void mes_advance(MesState &s, const MesStep &st, const MesWindow &w, uint
     }
     s.x = s.mvx;
     s.y = s.mvy;
+}
+
+/* the search of one block from the state mes_start() gave.  step_key(s, st) -> uint32_t: the step's ordered minimum, or MES_NO_KEY. */
+template <class StepKey>
+MES_FN void mes_run(MesState &s, const MesWindow &w, StepKey step_key)
+{
+    const uint32_t bound = mes_step_bound(w);
+    for (uint32_t n = 0; !s.done && n < bound; n++) {
+        const MesStep st = mes_step(s);
+        mes_advance(s, st, w, step_key(s, st));
+    }
 }
 
 /* ESA through the same two macros: the start, then the raster scan of the window with COST_MV.  cost(x, y) -> uint32_t. */

@@ -38,8 +38,7 @@ extern "C" int ffhip_me_esa_batch_dev(const uint8_t *cur, const uint8_t *ref, in
 }
 
 /* ---- the filter's per-block searches (kernels/me_search_rules.h) ----------------------------------------------------------------- */
-/* the checks both faces share: 0, FFHIP_EINVAL, or FFHIP_ENOSYS with a text for the two methods that are not per-block functions */
-/* what the per-block and the predictive faces check alike, the method apart */
+/* what the per-block and the predictive faces check alike, the method apart: 0 or FFHIP_EINVAL, no text */
 static int me_search_check_args(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
                                 int mb_size, int search_param, int cost_kind, const int16_t *mv_out, const uint32_t *cost_out)
 {
@@ -54,6 +53,7 @@ static int me_search_check_args(const uint8_t *cur, const uint8_t *ref, int widt
     return 0;
 }
 
+/* the per-block faces: 0, FFHIP_EINVAL, or FFHIP_ENOSYS with a text for the two methods that are not functions of one block */
 static int me_search_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
                            int nframes, int mb_size, int search_param, int cost_kind, const int16_t *mv_out, const uint32_t *cost_out)
 {
@@ -148,6 +148,53 @@ extern "C" void ffhip_me_search_host_counts(uint64_t *blocks, uint64_t *costs)
         *costs = t_host_costs;
 }
 
+struct HostBest {
+    int mvx, mvy;
+    uint32_t cost_min;
+};
+
+/* The driver of both host faces: every block of every frame in raster order.  search_block(bx, by, b, w, cost) -> HostBest searches
+ * block (bx, by) of a frame, the b-th of the call, in the window w with cost(x, y). */
+template <class SearchBlock>
+static void me_search_host(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                           int mb_size, int search_param, int cost_kind, int16_t *mv_out, uint32_t *cost_out, SearchBlock search_block)
+{
+    const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
+    uint64_t blocks = 0, costs = 0;
+    for (int f = 0; f < nframes; f++)
+        for (int by = 0; by < bh; by++)
+            for (int bx = 0; bx < bw; bx++) {
+                const int x_mb = bx << lg, y_mb = by << lg;
+                const size_t b = ((size_t)f * bh + by) * bw + bx;
+                const MesWindow w = mes_window(x_mb, y_mb, search_param, bw, bh, lg);
+                HostCost cost = { cur + (size_t)f * frame_pitch + (ptrdiff_t)y_mb * stride + x_mb, ref + (size_t)f * frame_pitch, stride, mb_size,
+                                  cost_kind, 0 };
+                const HostBest best = search_block(bx, by, b, w, cost);
+                mv_out[2 * b] = (int16_t)best.mvx;
+                mv_out[2 * b + 1] = (int16_t)best.mvy;
+                cost_out[b] = best.cost_min;
+                blocks++;
+                costs += cost.n;
+            }
+    t_host_blocks = blocks;
+    t_host_costs = costs;
+}
+
+/* a step's ordered minimum on the CPU: the n candidates one by one.  candidate(i, x, y) -> bool */
+template <class Candidate>
+static uint32_t host_step_key(HostCost &cost, int n, Candidate candidate)
+{
+    uint32_t key = MES_NO_KEY;
+    for (int i = 0; i < n; i++) {
+        int x, y;
+        if (candidate(i, x, y)) {
+            const uint32_t k = mes_key(cost(x, y), i);
+            key = k < key ? k : key;
+        }
+    }
+    return key;
+}
+
 extern "C" int ffhip_me_search_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
                                            size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
                                            int16_t *mv_out, uint32_t *cost_out)
@@ -156,46 +203,21 @@ extern "C" int ffhip_me_search_frames_host(int method, const uint8_t *cur, const
                                   cost_out);
     if (r)
         return r;
-    const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
-    uint64_t blocks = 0, costs = 0;
-    for (int f = 0; f < nframes; f++)
-        for (int by = 0; by < bh; by++)
-            for (int bx = 0; bx < bw; bx++) {
-                const int x_mb = bx << lg, y_mb = by << lg;
-                const MesWindow w = mes_window(x_mb, y_mb, search_param, bw, bh, lg);
-                HostCost cost = { cur + (size_t)f * frame_pitch + (ptrdiff_t)y_mb * stride + x_mb, ref + (size_t)f * frame_pitch, stride, mb_size,
-                                  cost_kind, 0 };
-                int mvx, mvy;
-                uint32_t cost_min;
-                if (method == FFHIP_ME_METHOD_ESA) {
-                    mes_search_esa(x_mb, y_mb, w, cost, mvx, mvy, cost_min);
-                } else {
-                    MesState s = mes_start(method, x_mb, y_mb, search_param, cost(x_mb, y_mb));
-                    for (uint32_t n = 0, bound = mes_step_bound(w); !s.done && n < bound; n++) {
-                        const MesStep st = mes_step(s);
-                        uint32_t key = MES_NO_KEY;
-                        for (int i = 0; i < st.n; i++) {
-                            int x, y;
-                            if (mes_candidate(s, st, w, i, x, y)) {
-                                const uint32_t k = mes_key(cost(x, y), i);
-                                key = k < key ? k : key;
-                            }
-                        }
-                        mes_advance(s, st, w, key);
-                    }
-                    mvx = s.mvx;
-                    mvy = s.mvy;
-                    cost_min = s.cost_min;
-                }
-                const size_t b = ((size_t)f * bh + by) * bw + bx;
-                mv_out[2 * b] = (int16_t)mvx;
-                mv_out[2 * b + 1] = (int16_t)mvy;
-                cost_out[b] = cost_min;
-                blocks++;
-                costs += cost.n;
-            }
-    t_host_blocks = blocks;
-    t_host_costs = costs;
+    const int lg = mb_size == 16 ? 4 : 3;
+    me_search_host(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out,
+                   [&](int bx, int by, size_t, const MesWindow &w, HostCost &cost) {
+                       const int x_mb = bx << lg, y_mb = by << lg;
+                       if (method == FFHIP_ME_METHOD_ESA) {
+                           HostBest best;
+                           mes_search_esa(x_mb, y_mb, w, cost, best.mvx, best.mvy, best.cost_min);
+                           return best;
+                       }
+                       MesState s = mes_start(method, x_mb, y_mb, search_param, cost(x_mb, y_mb));
+                       mes_run(s, w, [&](const MesState &s, const MesStep &st) {
+                           return host_step_key(cost, st.n, [&](int i, int &x, int &y) { return mes_candidate(s, st, w, i, x, y); });
+                       });
+                       return HostBest{ s.mvx, s.mvy, s.cost_min };
+                   });
     return 0;
 }
 
@@ -256,13 +278,6 @@ extern "C" int ffhip_me_search_pred_batch_dev(int method, const uint8_t *cur, co
                                        prev2, mv_out, cost_out, (hipStream_t)stream);
 }
 
-/* block (bx, by)'s relative vector of a field of absolute positions; NULL: a field of zero vectors */
-static MespVec host_rel(const int16_t *field, size_t b, int bx, int by, int lg)
-{
-    MespVec v = { 0, 0 };
-    return field ? mesp_rel(field[2 * b], field[2 * b + 1], bx, by, lg) : v;
-}
-
 extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
                                                 size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
                                                 const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out)
@@ -272,60 +287,27 @@ extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, 
     if (r)
         return r;
     const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
-    const bool epzs = method == FFHIP_ME_METHOD_EPZS;
-    const MespVec zero = { 0, 0 };
-    uint64_t blocks = 0, costs = 0;
-    for (int f = 0; f < nframes; f++)
-        for (int by = 0; by < bh; by++)
-            for (int bx = 0; bx < bw; bx++) {
-                const int x_mb = bx << lg, y_mb = by << lg;
-                const size_t b = ((size_t)f * bh + by) * bw + bx;
-                const MesWindow w = mes_window(x_mb, y_mb, search_param, bw, bh, lg);
-                HostCost cost = { cur + (size_t)f * frame_pitch + (ptrdiff_t)y_mb * stride + x_mb, ref + (size_t)f * frame_pitch, stride, mb_size,
-                                  cost_kind, 0 };
-                /* raster order: the neighbours of the current frame are in mv_out already */
-                MespVec left = zero, top = zero, diag = zero, c1 = zero, c2 = zero, pl = zero, pt = zero, pr = zero, pb = zero;
-                if (bx > 0)
-                    left = host_rel(mv_out, b - 1, bx - 1, by, lg);
-                if (by > 0) {
-                    top = host_rel(mv_out, b - bw, bx, by - 1, lg);
-                    if (bx + 1 < bw)
-                        diag = host_rel(mv_out, b - bw + 1, bx + 1, by - 1, lg);
-                    else if (!epzs && bx > 0)
-                        diag = host_rel(mv_out, b - bw - 1, bx - 1, by - 1, lg);
-                }
-                if (epzs) {
-                    c1 = host_rel(prev1, b, bx, by, lg);
-                    c2 = host_rel(prev2, b, bx, by, lg);
-                    if (bx > 0)
-                        pl = host_rel(prev1, b - 1, bx - 1, by, lg);
-                    if (by > 0)
-                        pt = host_rel(prev1, b - bw, bx, by - 1, lg);
-                    if (bx + 1 < bw)
-                        pr = host_rel(prev1, b + 1, bx + 1, by, lg);
-                    if (by + 1 < bh)
-                        pb = host_rel(prev1, b + bw, bx, by + 1, lg);
-                }
-                const MespPred P = mesp_predictors(method, bx, by, bw, bh, left, top, diag, c1, c2, pl, pt, pr, pb);
-                MespState s = mesp_start(method, x_mb, y_mb, search_param);
-                for (uint32_t n = 0, bound = mesp_step_bound(w); !s.done && n < bound; n++) {
-                    uint32_t key = MES_NO_KEY;
-                    for (int i = 0; i < 8; i++) {
-                        int x, y;
-                        if (mesp_candidate(s, w, P, s.pos + i, x, y)) {
-                            const uint32_t k = mes_key(cost(x, y), i);
-                            key = k < key ? k : key;
-                        }
-                    }
-                    mesp_advance(s, w, P, key);
-                }
-                mv_out[2 * b] = (int16_t)s.mvx;
-                mv_out[2 * b + 1] = (int16_t)s.mvy;
-                cost_out[b] = s.cost_min;
-                blocks++;
-                costs += cost.n;
-            }
-    t_host_blocks = blocks;
-    t_host_costs = costs;
+    me_search_host(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out,
+                   [&](int bx, int by, size_t b, const MesWindow &w, HostCost &cost) {
+                       /* block (bx + dbx, by + dby)'s relative vector of a field of absolute positions; NULL: a field of zero vectors */
+                       auto rel = [&](const int16_t *field, int dbx, int dby) {
+                           const size_t n = b + (ptrdiff_t)dby * bw + dbx;
+                           const MespVec zero = { 0, 0 };
+                           return field ? mesp_rel(field[2 * n], field[2 * n + 1], bx + dbx, by + dby, lg) : zero;
+                       };
+                       /* raster order: the neighbours of the current frame are in mv_out already */
+                       const MespNeigh N = mesp_neighbours(method, bx, by, bw, bh);
+                       MespNear v = {};
+                       if (mesp_has(N, MESP_LEFT))
+                           v.left = rel(mv_out, -1, 0);
+                       mesp_fetch_prev(v, N, [&](int which, int dbx, int dby) { return rel(which == 1 ? prev1 : prev2, dbx, dby); });
+                       mesp_fetch_above(v, N, [&](int dbx) { return rel(mv_out, dbx, -1); });
+                       const MespPred P = mesp_predictors(N, v);
+                       MespState s = mesp_start(method, bx << lg, by << lg, search_param);
+                       mesp_run(s, w, P, [&](const MespState &s) {
+                           return host_step_key(cost, 8, [&](int i, int &x, int &y) { return mesp_candidate(s, w, P, s.pos + i, x, y); });
+                       });
+                       return HostBest{ s.mvx, s.mvy, s.cost_min };
+                   });
     return 0;
 }

@@ -35,17 +35,21 @@ def search_batch(method, cur, ref, width, height, stride, frame_pitch, nframes, 
                                                            cost_out.data_ptr(), _stream(stream)), "ffhip_me_search_batch_dev")
 
 
+def _host_counts():
+    """(blocks searched, costs evaluated) of this thread's last *_frames_host call"""
+    import ctypes as C
+    blocks, costs = C.c_uint64(), C.c_uint64()
+    _lib.lib().ffhip_me_search_host_counts(C.byref(blocks), C.byref(costs))
+    return blocks.value, costs.value
+
+
 def search_frames_host(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out):
     """The same rules on the CPU (device-free): numpy arrays (uint8 planes, int16 vectors, uint32 costs).  Returns (blocks searched,
     costs evaluated)."""
-    import ctypes as C
-    L = _lib.lib()
-    _lib.check(L.ffhip_me_search_frames_host(method, cur.ctypes.data, ref.ctypes.data, width, height, stride, frame_pitch, nframes,
-                                             mb_size, search_param, cost_kind, mv_out.ctypes.data, cost_out.ctypes.data),
-               "ffhip_me_search_frames_host")
-    blocks, costs = C.c_uint64(), C.c_uint64()
-    L.ffhip_me_search_host_counts(C.byref(blocks), C.byref(costs))
-    return blocks.value, costs.value
+    _lib.check(_lib.lib().ffhip_me_search_frames_host(method, cur.ctypes.data, ref.ctypes.data, width, height, stride, frame_pitch,
+                                                      nframes, mb_size, search_param, cost_kind, mv_out.ctypes.data,
+                                                      cost_out.ctypes.data), "ffhip_me_search_frames_host")
+    return _host_counts()
 
 
 def search_pred_batch(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1, prev2,
@@ -64,12 +68,8 @@ def search_pred_frames_host(method, cur, ref, width, height, stride, frame_pitch
                             mv_out, cost_out):
     """The same rules on the CPU (device-free): numpy arrays (uint8 planes, int16 vectors, uint32 costs), prev1 / prev2 arrays or
     None.  Returns (blocks searched, costs evaluated)."""
-    import ctypes as C
-    L = _lib.lib()
     p = lambda a: None if a is None else a.ctypes.data
-    _lib.check(L.ffhip_me_search_pred_frames_host(method, cur.ctypes.data, ref.ctypes.data, width, height, stride, frame_pitch, nframes,
-                                                  mb_size, search_param, cost_kind, p(prev1), p(prev2), mv_out.ctypes.data,
-                                                  cost_out.ctypes.data), "ffhip_me_search_pred_frames_host")
-    blocks, costs = C.c_uint64(), C.c_uint64()
-    L.ffhip_me_search_host_counts(C.byref(blocks), C.byref(costs))
-    return blocks.value, costs.value
+    _lib.check(_lib.lib().ffhip_me_search_pred_frames_host(method, cur.ctypes.data, ref.ctypes.data, width, height, stride, frame_pitch,
+                                                           nframes, mb_size, search_param, cost_kind, p(prev1), p(prev2),
+                                                           mv_out.ctypes.data, cost_out.ctypes.data), "ffhip_me_search_pred_frames_host")
+    return _host_counts()

@@ -1,8 +1,8 @@
 """GPU tier of the filter's predictive motion searches: ffhip_me_search_pred_batch_dev == ffhip_me_search_pred_frames_host == the model of
 tests/me_pred_search_model.py, on the inputs and references of tests/test_me_pred_search_cpu.py (computed once, shared).  The kernel
 searches the blocks of a pair in wavefront order, one wave per block row, the rows handing their vectors on through mv_out; so beside
-the shapes there are runs with the number of workgroups fixed (several ticket rounds, one wave doing every row in turn), EPZS's
-predictor list in plain order, a call split into several launches by pairs, a chained run on one stream and a 1920 x 1080 pair."""
+the shapes there are runs with the number of workgroups fixed (several ticket rounds, one wave doing every row in turn), a call split
+into several launches by pairs, a chained run on one stream and a 1920 x 1080 pair."""
 import functools
 
 import numpy as np
@@ -75,15 +75,6 @@ def test_ticket_rounds(w, h, pad, mb, R, wgs, monkeypatch):
     for kind in T.KINDS:
         for method in T.METHODS:
             _check(torch, method, kind, (w, h, pad, mb, R))
-
-
-@pytest.mark.parametrize("w,h,pad,mb,R", [T.CASES[0], (96, 80, 3, 8, 32)])
-def test_epzs_predictors_in_plain_order(w, h, pad, mb, R, monkeypatch):
-    """the measurement build's other order: the whole list behind the wait, in steps of 8; the same bytes"""
-    torch = _torch()
-    monkeypatch.setenv("FFHIP_ME_PRED_ORDER", "plain")
-    for kind in T.KINDS:
-        _check(torch, M.EPZS, kind, (w, h, pad, mb, R))
 
 
 def test_a_call_split_into_several_launches():

@@ -12,9 +12,7 @@ at the same search_param and metric, from the same run.
 
 EPZS and UMH search a pair in wavefront order (one wave per block row, each two blocks behind the row above), so a pair's time is a
 chain of about b_w + 2 * b_h blocks, and pairs of one launch overlap: their rows come twice, at 8 pairs per launch and ("/1") at 1 pair
-per launch, the latter with the chain's time per block.  prev1 = prev2 = the vectors EPZS finds without them (a sequence at rest).  The
-last section runs EPZS's predictor list in plain order (the measurement build's FFHIP_ME_PRED_ORDER=plain) against the overlapped one,
-both from the measurement build.
+per launch, the latter with the chain's time per block.  prev1 = prev2 = the vectors EPZS finds without them (a sequence at rest).
 
     python tools/bench_me_search.py [--out profiles/me_search_bench.txt]
 """
@@ -91,33 +89,6 @@ def pred_rows(torch, np, me, a, cur, ref, hcur, href, mv, cost, hmv, hcost, kind
     return out
 
 
-def order_rows(torch, a, cur, ref, mv, cost):
-    """EPZS, SAD: the predictor list in plain order behind the wait against the overlapped order, both from the measurement build"""
-    from ffmpeg_amd import _lib, me
-    out = ["# EPZS predictor order (measurement build, SAD): ms per pair at 8 pairs and at 1 pair per launch"]
-    _lib.select("measure")
-    try:
-        prev = torch.empty_like(mv)
-        for R in (7, 32):
-            me.search_pred_batch(me.EPZS, cur, ref, W, H, W, W * H, NF, MB, R, me.SAD, None, None, prev, cost)
-            torch.cuda.synchronize()
-            for order in ("overlapped", "plain"):
-                if order == "plain":
-                    os.environ["FFHIP_ME_PRED_ORDER"] = "plain"
-                else:
-                    os.environ.pop("FFHIP_ME_PRED_ORDER", None)
-                ms = []
-                for nf in (NF, 1):
-                    call = lambda: me.search_pred_batch(me.EPZS, cur, ref, W, H, W, W * H, nf, MB, R, me.SAD, prev, prev, mv, cost)
-                    ms.append(statistics.median(x / nf for x in timed(torch, call, a.window, a.rounds)))
-                out.append("epzs   sad   %3d %-10s %12.4f (8 pairs) %12.4f (1 pair)" % (R, order, ms[0], ms[1]))
-                print(out[-1], flush=True)
-    finally:
-        os.environ.pop("FFHIP_ME_PRED_ORDER", None)
-        _lib.select("product")
-    return out
-
-
 def esa_costs_per_block(R):
     """the start plus the window, averaged over the blocks of a frame"""
     bw, bh = W // MB, H // MB
@@ -172,7 +143,6 @@ def main():
                 print(lines[-1], flush=True)
                 if method == me.HEXBS:
                     lines.extend(pred_rows(torch, np, me, a, cur, ref, hcur, href, mv, cost, hmv, hcost, kind, kname, R, esa_ms))
-    lines.extend(order_rows(torch, a, cur, ref, mv, cost))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -1,10 +1,12 @@
 /*
- * tools/me_search_host_san.cpp — a stand-alone host program over ffhip_me_search_frames_host() and the argument checks of
- * ffhip_me_search_batch_dev() for AddressSanitizer and UBSan: the shapes of tests/test_me_search_cpu.py at both block sizes, every
- * method and both metrics, three frame pairs each (noise, a shifted copy with exactly matching blocks, a flat one with sparse marks), in
- * heap blocks exactly as large as the geometry says — the planes end at height * stride, the outputs at the last block — so a read or
- * write outside them is an error the sanitizer reports, and a signed overflow in the window or step arithmetic (search_param up to
- * INT_MAX) one UBSan reports; then the refusals of both faces on pointers they never follow.  CPU only: nothing here touches a device.
+ * tools/me_search_host_san.cpp — a stand-alone host program over ffhip_me_search_frames_host(), ffhip_me_search_pred_frames_host() and the
+ * argument checks of ffhip_me_search_batch_dev() and ffhip_me_search_pred_batch_dev() for AddressSanitizer and UBSan: the shapes of
+ * tests/test_me_search_cpu.py and tests/test_me_pred_search_cpu.py at both block sizes, every method (1 to 9) and both metrics, three frame
+ * pairs each (noise, a shifted copy with exactly matching blocks, a flat one with sparse marks), the predictive methods with prev fields of
+ * small vectors, of any int16 and NULL, in heap blocks exactly as large as the geometry says — the planes end at height * stride, the
+ * fields and outputs at the last block — so a read or write outside them is an error the sanitizer reports, and a signed overflow in the
+ * window, the step arithmetic, the relative vectors or the d loops (search_param up to INT_MAX, vectors of any int16) one UBSan reports;
+ * then the refusals of all four faces on pointers they never follow.  CPU only: nothing here touches a device.
  *
  * Build and run from the repository root (the faces' file and this one, nothing else of the library):
  *   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
@@ -44,6 +46,11 @@ int ffhip_launch_me_search(int, const uint8_t *, const uint8_t *, int, int, ptrd
 {
     return FFHIP_ENOSYS;
 }
+int ffhip_launch_me_search_pred(int, const uint8_t *, const uint8_t *, int, int, ptrdiff_t, size_t, int, int, int, int, const int16_t *, const int16_t *,
+                                int16_t *, uint32_t *, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
 
 static uint32_t rnd_state = 24680;
 static uint32_t rnd(void)
@@ -61,12 +68,16 @@ static uint8_t *block(size_t n)
     return p;
 }
 
+static bool predictive(int method) { return method >= FFHIP_ME_METHOD_EPZS; }
+
 static int run(int w, int h, int pad, int mb, int R)
 {
     const int nf = 3, stride = w + pad, bw = w / mb, bh = h / mb;
     const size_t plane = (size_t)h * stride, nb = (size_t)nf * bw * bh;
     uint8_t *cur = block(nf * plane), *ref = block(nf * plane);
-    int16_t *mv = reinterpret_cast<int16_t *>(block(nb * 4));
+    int16_t *mv = reinterpret_cast<int16_t *>(block(nb * 4)), *small1 = reinterpret_cast<int16_t *>(block(nb * 4));
+    int16_t *small2 = reinterpret_cast<int16_t *>(block(nb * 4)), *any1 = reinterpret_cast<int16_t *>(block(nb * 4));
+    int16_t *any2 = reinterpret_cast<int16_t *>(block(nb * 4));
     uint32_t *cost = reinterpret_cast<uint32_t *>(block(nb * 4));
     for (size_t i = 0; i < plane; i++) {
         ref[i] = (uint8_t)rnd();
@@ -80,93 +91,153 @@ static int run(int w, int h, int pad, int mb, int R)
         cur[plane + i] = i < (size_t)(2 * mb) * stride || j < 0 || j >= (ptrdiff_t)plane ? ref[plane + i] : ref[plane + j];
         cur[2 * plane + i] = (uint8_t)((i + 3) % 37 ? 128 : 130);
     }
-    int bad = 0;
-    for (int method = FFHIP_ME_METHOD_ESA; method <= FFHIP_ME_METHOD_HEXBS; method++)
-        for (int kind = FFHIP_ME_SAD; kind <= FFHIP_ME_SATD; kind++) {
-            memset(mv, 0x5A, nb * 4);
-            memset(cost, 0x5A, nb * 4);
-            const int r = ffhip_me_search_frames_host(method, cur, ref, w, h, stride, plane, nf, mb, R, kind, mv, cost);
-            uint64_t blocks = 0, costs = 0;
-            ffhip_me_search_host_counts(&blocks, &costs);
-            uint32_t sum = 0;
-            for (size_t b = 0; b < nb; b++) {
-                sum = sum * 31 + (uint32_t)mv[2 * b] * 65537u + (uint32_t)mv[2 * b + 1] + cost[b];
-                const int bx = (int)(b % bw) * mb, by = (int)(b / bw % bh) * mb;
-                bad |= mv[2 * b] < 0 || mv[2 * b] > (bw - 1) * mb || mv[2 * b + 1] < 0 || mv[2 * b + 1] > (bh - 1) * mb;
-                bad |= abs(mv[2 * b] - bx) > R || abs(mv[2 * b + 1] - by) > R;          /* the window */
-            }
-            bad |= r != 0 || blocks != nb || costs < nb;
-            printf("%3d x %3d pad %d mb %2d R %10d method %d kind %d: rc %d, %llu costs, checksum %08x\n", w, h, pad, mb, R, method, kind, r,
-                   (unsigned long long)costs, sum);
+    for (size_t b = 0; b < nb; b++)
+        for (int k = 0; k < 2; k++) {
+            const int o = k ? (int)(b / bw % bh) * mb : (int)(b % bw) * mb;
+            small1[2 * b + k] = (int16_t)(o + (int)(rnd() % 13) - 6);
+            small2[2 * b + k] = (int16_t)(o + (int)(rnd() % 13) - 6);
+            any1[2 * b + k] = (int16_t)rnd();
+            any2[2 * b + k] = (int16_t)rnd();
         }
-    free(cur); free(ref); free(mv); free(cost);
+    int bad = 0;
+    for (int method = FFHIP_ME_METHOD_ESA; method <= FFHIP_ME_METHOD_UMH; method++)
+        for (int kind = FFHIP_ME_SAD; kind <= FFHIP_ME_SATD; kind++)
+            for (int prev = 0; prev < (predictive(method) ? 3 : 1); prev++) {
+                const int16_t *p1 = prev == 0 ? small1 : prev == 1 ? any1 : nullptr, *p2 = prev == 0 ? small2 : prev == 1 ? any2 : nullptr;
+                memset(mv, 0x5A, nb * 4);
+                memset(cost, 0x5A, nb * 4);
+                const int r = predictive(method) ? ffhip_me_search_pred_frames_host(method, cur, ref, w, h, stride, plane, nf, mb, R, kind, p1, p2, mv, cost)
+                                                 : ffhip_me_search_frames_host(method, cur, ref, w, h, stride, plane, nf, mb, R, kind, mv, cost);
+                uint64_t blocks = 0, costs = 0;
+                ffhip_me_search_host_counts(&blocks, &costs);
+                uint32_t sum = 0;
+                for (size_t b = 0; b < nb; b++) {
+                    sum = sum * 31 + (uint32_t)mv[2 * b] * 65537u + (uint32_t)mv[2 * b + 1] + cost[b];
+                    const int bx = (int)(b % bw) * mb, by = (int)(b / bw % bh) * mb;
+                    bad |= mv[2 * b] < 0 || mv[2 * b] > (bw - 1) * mb || mv[2 * b + 1] < 0 || mv[2 * b + 1] > (bh - 1) * mb;
+                    bad |= abs(mv[2 * b] - bx) > R || abs(mv[2 * b + 1] - by) > R;          /* the window */
+                    bad |= cost[b] == 0x5A5A5A5Au;                                          /* every block ends with a real cost */
+                }
+                bad |= r != 0 || blocks != nb || costs < (predictive(method) ? 2 : 1) * nb;
+                printf("%3d x %3d pad %d mb %2d R %10d method %d kind %d prev %d: rc %d, %llu costs, checksum %08x\n", w, h, pad, mb, R, method, kind,
+                       predictive(method) ? prev : -1, r, (unsigned long long)costs, sum);
+            }
+    free(cur); free(ref); free(mv); free(cost); free(small1); free(small2); free(any1); free(any2);
     return bad;
 }
 
-/* the checks of both faces: pointers into one arena that is never dereferenced when the call is refused */
+/* the checks of the faces: pointers into arenas that are never dereferenced when the call is refused.  One table per pair of faces;
+ * `word`: what the text of the refusal holds, "" for no text at all, NULL for whatever it is. */
 static int refusals(void)
 {
     static uint8_t arena[4 * 64 * 48];
     uint8_t *cur = arena, *ref = arena + 2 * 64 * 48;
-    static int16_t mv[2 * 12 * 2];
+    alignas(4) static int16_t fields[4][2 * 12 * 2 + 2];
     static uint32_t cost[2 * 12];
     int bad = 0;
-    struct Args { int method; const uint8_t *cur, *ref; int w, h; ptrdiff_t stride; size_t pitch; int nf, mb, R, kind; int16_t *mv; uint32_t *cost; };
-    const Args good = { FFHIP_ME_METHOD_DS, cur, ref, 64, 48, 64, 64 * 48, 2, 16, 7, FFHIP_ME_SAD, mv, cost };
-    auto expect = [&](int want_host, int want_dev, Args a, const char *what) {
-        const int rh = ffhip_me_search_frames_host(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.mv, a.cost);
-        const int rd = ffhip_me_search_batch_dev(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.mv, a.cost, nullptr);
-        if (rh != want_host || rd != want_dev) {
-            printf("refusals: %s: host rc %d (expected %d), dev rc %d (expected %d)\n", what, rh, want_host, rd, want_dev);
+    struct Args { int method; const uint8_t *cur, *ref; int w, h; ptrdiff_t stride; size_t pitch; int nf, mb, R, kind; const int16_t *p1, *p2; int16_t *mv; uint32_t *cost; };
+    Args good = { FFHIP_ME_METHOD_DS, cur, ref, 64, 48, 64, 64 * 48, 2, 16, 7, FFHIP_ME_SAD, fields[1], fields[2], fields[0], cost };
+    bool pred = false;      /* which pair of faces expect() calls */
+    auto expect = [&](int want_host, int want_dev, Args a, const char *what, const char *word) {
+        auto text_ok = [&] { return !word || (word[0] ? strstr(last_error, word) != nullptr : !last_error[0]); };
+        last_error[0] = 0;
+        const int rh = pred ? ffhip_me_search_pred_frames_host(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.p1, a.p2, a.mv, a.cost)
+                            : ffhip_me_search_frames_host(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.mv, a.cost);
+        const bool th = text_ok();
+        last_error[0] = 0;
+        const int rd = pred ? ffhip_me_search_pred_batch_dev(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.p1, a.p2, a.mv, a.cost, nullptr)
+                            : ffhip_me_search_batch_dev(a.method, a.cur, a.ref, a.w, a.h, a.stride, a.pitch, a.nf, a.mb, a.R, a.kind, a.mv, a.cost, nullptr);
+        const bool td = text_ok();
+        if (rh != want_host || rd != want_dev || !th || !td) {
+            printf("refusals: %s face, %s: host rc %d (expected %d), dev rc %d (expected %d), text \"%s\"\n", pred ? "predictive" : "per-block", what, rh,
+                   want_host, rd, want_dev, last_error);
             bad = 1;
         }
     };
     Args a = good;
-    expect(0, FFHIP_ENOSYS, a, "a well-formed call");
-#define BAD(field, value, what) a = good; a.field = value; expect(FFHIP_EINVAL, FFHIP_EINVAL, a, what)
-    BAD(cur, nullptr, "a NULL cur");
-    BAD(ref, nullptr, "a NULL ref");
-    BAD(mv, nullptr, "a NULL mv_out");
-    BAD(cost, nullptr, "a NULL cost_out");
-    BAD(method, 0, "method 0");
-    BAD(method, 10, "method 10");
-    BAD(mb, 4, "mb_size 4");
-    BAD(mb, 32, "mb_size 32");
-    BAD(kind, 2, "cost_kind 2");
-    BAD(kind, -1, "cost_kind -1");
-    BAD(w, -1, "a negative width");
-    BAD(h, -1, "a negative height");
-    BAD(nf, -1, "a negative nframes");
-    BAD(R, -1, "a negative search_param");
-    BAD(stride, 63, "stride < width");
-    BAD(stride, -64, "a negative stride");
-    BAD(pitch, 64 * 48 - 1, "frame_pitch < stride * height");
-    BAD(nf, INT_MAX, "more blocks than an int counts");
-#undef BAD
+#define BAD(field, value, what, word) a = good; a.field = value; expect(FFHIP_EINVAL, FFHIP_EINVAL, a, what, word)
+    /* ---- the per-block faces: FFHIP_EINVAL carries no text ---- */
+    expect(0, FFHIP_ENOSYS, a, "a well-formed call", nullptr);
+    BAD(cur, nullptr, "a NULL cur", "");
+    BAD(ref, nullptr, "a NULL ref", "");
+    BAD(mv, nullptr, "a NULL mv_out", "");
+    BAD(cost, nullptr, "a NULL cost_out", "");
+    BAD(method, 0, "method 0", "");
+    BAD(method, 10, "method 10", "");
+    BAD(mb, 4, "mb_size 4", "");
+    BAD(mb, 32, "mb_size 32", "");
+    BAD(kind, 2, "cost_kind 2", "");
+    BAD(kind, -1, "cost_kind -1", "");
+    BAD(w, -1, "a negative width", "");
+    BAD(h, -1, "a negative height", "");
+    BAD(nf, -1, "a negative nframes", "");
+    BAD(R, -1, "a negative search_param", "");
+    BAD(stride, 63, "stride < width", "");
+    BAD(stride, -64, "a negative stride", "");
+    BAD(pitch, 64 * 48 - 1, "frame_pitch < stride * height", "");
+    BAD(nf, INT_MAX, "more blocks than an int counts", "");
     for (int method = FFHIP_ME_METHOD_EPZS; method <= FFHIP_ME_METHOD_UMH; method++) {
         a = good; a.method = method;
-        last_error[0] = 0;
-        expect(FFHIP_ENOSYS, FFHIP_ENOSYS, a, "EPZS / UMH");
-        if (!strstr(last_error, method == FFHIP_ME_METHOD_EPZS ? "EPZS" : "UMH") || !strstr(last_error, "neighbouring blocks' vectors")) {
-            printf("refusals: method %d: the text is \"%s\"\n", method, last_error);
-            bad = 1;
-        }
+        expect(FFHIP_ENOSYS, FFHIP_ENOSYS, a, "EPZS / UMH", method == FFHIP_ME_METHOD_EPZS ? "EPZS" : "UMH");
+        expect(FFHIP_ENOSYS, FFHIP_ENOSYS, a, "EPZS / UMH", "neighbouring blocks' vectors");
     }
-    a = good; a.nf = 0; expect(0, FFHIP_ENOSYS, a, "no frames");
-    a = good; a.w = 15; expect(0, FFHIP_ENOSYS, a, "no whole block");
-    a = good; a.nf = 1; a.pitch = 0; expect(0, FFHIP_ENOSYS, a, "one frame, no pitch");
+    a = good; a.nf = 0; expect(0, FFHIP_ENOSYS, a, "no frames", nullptr);
+    a = good; a.w = 15; expect(0, FFHIP_ENOSYS, a, "no whole block", nullptr);
+    a = good; a.nf = 1; a.pitch = 0; expect(0, FFHIP_ENOSYS, a, "one frame, no pitch", nullptr);
+    /* ---- the predictive faces: every refusal says why ---- */
+    pred = true;
+    good.method = FFHIP_ME_METHOD_EPZS;
+    a = good;
+    expect(0, FFHIP_ENOSYS, a, "a well-formed call", nullptr);
+    BAD(cur, nullptr, "a NULL cur", "NULL");
+    BAD(ref, nullptr, "a NULL ref", "NULL");
+    BAD(mv, nullptr, "a NULL mv_out", "NULL");
+    BAD(cost, nullptr, "a NULL cost_out", "NULL");
+    for (int m = 0; m <= 10; m++)
+        if (!predictive(m) || m > FFHIP_ME_METHOD_UMH) {
+            BAD(method, m, "a method other than 8 or 9", "neither EPZS");
+        }
+    BAD(mb, 4, "mb_size 4", "mb_size");
+    BAD(mb, 32, "mb_size 32", "mb_size");
+    BAD(kind, 2, "cost_kind 2", "cost_kind");
+    BAD(kind, -1, "cost_kind -1", "cost_kind");
+    BAD(w, -1, "a negative width", "negative");
+    BAD(h, -1, "a negative height", "negative");
+    BAD(nf, -1, "a negative nframes", "negative");
+    BAD(R, -1, "a negative search_param", "negative");
+    BAD(stride, 63, "stride < width", "stride");
+    BAD(stride, -64, "a negative stride", "stride");
+    BAD(pitch, 64 * 48 - 1, "frame_pitch < stride * height", "frame_pitch");
+    BAD(nf, INT_MAX, "more blocks than an int counts", "blocks");
+    BAD(mv, fields[0] + 1, "mv_out not 4-byte aligned", "4-byte aligned");
+    BAD(p1, fields[0], "mv_out == prev1", "overlaps");
+    BAD(p2, fields[0] + 46, "mv_out overlapping prev2", "overlaps");
+    BAD(cost, reinterpret_cast<uint32_t *>(fields[0] + 2), "mv_out overlapping cost_out", "overlaps");
+    BAD(mv, reinterpret_cast<int16_t *>(arena + 64), "mv_out inside cur", "overlaps");
+    BAD(mv, reinterpret_cast<int16_t *>(arena + 4 * 64 * 48 - 4), "mv_out at the last samples of ref", "overlaps");
+    a = good; a.w = 32784; a.stride = 32784; a.h = 16; a.nf = 1; expect(FFHIP_EINVAL, FFHIP_EINVAL, a, "a width above 32768", "32784");
+    a = good; a.h = 32776; a.w = 16; a.stride = 16; a.nf = 1; expect(FFHIP_EINVAL, FFHIP_EINVAL, a, "a height above 32768", "32776");
+#undef BAD
+    a = good; a.nf = 0; expect(0, FFHIP_ENOSYS, a, "no frames", nullptr);
+    a = good; a.w = 15; expect(0, FFHIP_ENOSYS, a, "no whole block", nullptr);
+    a = good; a.nf = 1; a.pitch = 0; expect(0, FFHIP_ENOSYS, a, "one frame, no pitch", nullptr);
+    a = good; a.p1 = nullptr; a.p2 = nullptr; expect(0, FFHIP_ENOSYS, a, "NULL prev fields", nullptr);
+    a = good; a.p2 = a.p1; expect(0, FFHIP_ENOSYS, a, "prev1 == prev2", nullptr);
     return bad;
 }
 
 int main(void)
 {
-    static const int shapes[6][5] = { { 64, 48, 0, 16, 7 }, { 52, 36, 1, 16, 5 }, { 40, 40, 0, 8, 3 }, { 72, 56, 0, 16, 0 }, { 64, 64, 0, 8, 1 },
-                                      { 96, 80, 3, 16, 32 } };
+    static const int shapes[10][5] = { { 64, 48, 0, 16, 7 }, { 52, 36, 1, 16, 5 }, { 40, 40, 0, 8, 3 }, { 16, 64, 0, 16, 7 }, { 40, 8, 0, 8, 3 },
+                                       { 32, 48, 0, 16, 4 }, { 72, 56, 0, 16, 0 }, { 64, 64, 0, 8, 1 }, { 96, 80, 3, 16, 32 }, { 64, 48, 0, 8, 9 } };
     int bad = 0;
-    for (int i = 0; i < 6; i++)
-        for (int k = 0; k < 2; k++)
-            bad |= run(shapes[i][0], shapes[i][1], shapes[i][2], k ? 24 - shapes[i][3] : shapes[i][3], shapes[i][4]);
-    bad |= run(64, 48, 0, 16, INT_MAX);         /* the window and the steps in 64 bits */
+    for (int i = 0; i < 10; i++)
+        for (int k = 0; k < 2; k++) {
+            const int mb = k ? 24 - shapes[i][3] : shapes[i][3];
+            if (shapes[i][0] >= mb && shapes[i][1] >= mb)
+                bad |= run(shapes[i][0], shapes[i][1], shapes[i][2], mb, shapes[i][4]);
+        }
+    bad |= run(64, 48, 0, 16, INT_MAX);         /* the window, the steps, the cross and the rings without overflow or an endless loop */
     bad |= run(40, 24, 5, 8, 1 << 30);
     bad |= refusals();
     puts(bad ? "FAILED" : "ok");
