@@ -22,4 +22,10 @@ int ffhip_launch_me_search(int method, const uint8_t *cur, const uint8_t *ref, i
 int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
                                 int nframes, int mb_size, int R, int cost_kind, const int16_t *prev1, const int16_t *prev2, int16_t *mv_out,
                                 uint32_t *cost_out, hipStream_t stream);
+/* the same of whole sequences (me_search_seq.hip): nseq sequences of nframes pictures, pair k chained to the fields of pairs k - 1 and
+ * k - 2 inside the launch; outputs pair-major, init1 / init2 NULL or nseq fields each; calls of more units than a progress-pool slot
+ * counts are split at pair boundaries, and by sequences where one step alone does not fit */
+int ffhip_launch_me_search_seq(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                               size_t seq_pitch, int nseq, int direction, int mb_size, int R, int cost_kind, const int16_t *init1,
+                               const int16_t *init2, int16_t *mv_out, uint32_t *cost_out, hipStream_t stream);
 #endif

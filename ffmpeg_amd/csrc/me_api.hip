@@ -223,6 +223,24 @@ extern "C" int ffhip_me_search_frames_host(int method, const uint8_t *cur, const
 
 /* ---- the predictive searches, EPZS and UMH (kernels/me_search_pred_rules.h) ------------------------------------------------------- */
 #define MESP_WHO "ffhip_me_search_pred_batch_dev / _frames_host"
+/* what every predictive face checks of the method, the size of the picture and the vector field it writes */
+static int me_search_pred_check_field(const char *who, int method, int width, int height, const int16_t *mv_out)
+{
+    if (method != FFHIP_ME_METHOD_EPZS && method != FFHIP_ME_METHOD_UMH) {
+        ffhip_set_error("%s: method %d is neither EPZS (8) nor UMH (9); the per-block methods 1 to 7 are ffhip_me_search_batch_dev's", who, method);
+        return FFHIP_EINVAL;
+    }
+    if (width > 32768 || height > 32768) {
+        ffhip_set_error("%s: %d x %d: positions of a picture above 32768 do not fit the int16 vector fields", who, width, height);
+        return FFHIP_EINVAL;
+    }
+    if ((uintptr_t)mv_out & 3) {
+        ffhip_set_error("%s: mv_out is not 4-byte aligned (a block's vector travels as one dword)", who);
+        return FFHIP_EINVAL;
+    }
+    return 0;
+}
+
 static int me_search_pred_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
                                 int nframes, int mb_size, int search_param, int cost_kind, const int16_t *prev1, const int16_t *prev2,
                                 const int16_t *mv_out, const uint32_t *cost_out)
@@ -232,18 +250,8 @@ static int me_search_pred_check(int method, const uint8_t *cur, const uint8_t *r
                         "nframes or search_param, stride < width, frame_pitch < stride * height, or more than 2^31 - 1 blocks", mb_size, cost_kind);
         return FFHIP_EINVAL;
     }
-    if (method != FFHIP_ME_METHOD_EPZS && method != FFHIP_ME_METHOD_UMH) {
-        ffhip_set_error(MESP_WHO ": method %d is neither EPZS (8) nor UMH (9); the per-block methods 1 to 7 are ffhip_me_search_batch_dev's", method);
+    if (me_search_pred_check_field(MESP_WHO, method, width, height, mv_out))
         return FFHIP_EINVAL;
-    }
-    if (width > 32768 || height > 32768) {
-        ffhip_set_error(MESP_WHO ": %d x %d: positions of a picture above 32768 do not fit the int16 vector fields", width, height);
-        return FFHIP_EINVAL;
-    }
-    if ((uintptr_t)mv_out & 3) {
-        ffhip_set_error(MESP_WHO ": mv_out is not 4-byte aligned (a block's vector travels as one dword)");
-        return FFHIP_EINVAL;
-    }
     /* mv_out is read back while it is written: it shares no byte with anything else the call reads or writes */
     const int lg = mb_size == 16 ? 4 : 3;
     const ptrdiff_t field = (ptrdiff_t)(width >> lg) * (height >> lg) * nframes * 4;
@@ -278,14 +286,11 @@ extern "C" int ffhip_me_search_pred_batch_dev(int method, const uint8_t *cur, co
                                        prev2, mv_out, cost_out, (hipStream_t)stream);
 }
 
-extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
-                                                size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
-                                                const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out)
+/* the predictive searches of nframes independent pairs on the CPU, arguments checked: the body of the host faces */
+static void me_search_pred_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                int nframes, int mb_size, int search_param, int cost_kind, const int16_t *prev1, const int16_t *prev2,
+                                int16_t *mv_out, uint32_t *cost_out)
 {
-    const int r = me_search_pred_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
-                                       prev2, mv_out, cost_out);
-    if (r)
-        return r;
     const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
     me_search_host(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out,
                    [&](int bx, int by, size_t b, const MesWindow &w, HostCost &cost) {
@@ -309,5 +314,117 @@ extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, 
                        });
                        return HostBest{ s.mvx, s.mvy, s.cost_min };
                    });
+}
+
+extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                                size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
+                                                const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out)
+{
+    const int r = me_search_pred_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
+                                       prev2, mv_out, cost_out);
+    if (r)
+        return r;
+    me_search_pred_host(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1, prev2, mv_out,
+                        cost_out);
+    return 0;
+}
+
+/* ---- the predictive searches of whole sequences: pair k chained to the fields of pairs k - 1 and k - 2 ----------------------------- */
+#define MESQ_WHO "ffhip_me_search_pred_sequence_dev / _host"
+static int me_search_seq_check(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                               size_t seq_pitch, int nseq, int direction, int mb_size, int search_param, int cost_kind, const int16_t *init1,
+                               const int16_t *init2, const int16_t *mv_out, const uint32_t *cost_out)
+{
+    /* what the pair face refuses, applied to the pictures; the blocks are counted below, over all pairs and sequences */
+    if (me_search_check_args(frames, frames, width, height, stride, frame_pitch, nframes < 2 ? nframes : 2, mb_size, search_param, cost_kind, mv_out,
+                             cost_out)) {
+        ffhip_set_error(MESQ_WHO ": a NULL frames, mv_out or cost_out, mb_size %d (16 or 8), cost_kind %d (0 or 1), a negative width, height, "
+                        "nframes or search_param, stride < width, or frame_pitch < stride * height", mb_size, cost_kind);
+        return FFHIP_EINVAL;
+    }
+    if (me_search_pred_check_field(MESQ_WHO, method, width, height, mv_out))
+        return FFHIP_EINVAL;
+    if (direction < 0 || direction > 1) {
+        ffhip_set_error(MESQ_WHO ": direction %d is neither 0 (cur = picture k + 1, ref = picture k) nor 1 (cur = picture k, ref = picture k + 1)",
+                        direction);
+        return FFHIP_EINVAL;
+    }
+    if (nseq < 0) {
+        ffhip_set_error(MESQ_WHO ": a negative nseq (%d)", nseq);
+        return FFHIP_EINVAL;
+    }
+    if (nseq > 1 && nframes > 0) {
+        /* a sequence's pictures end (nframes - 1) * frame_pitch + stride * height bytes behind its first */
+        size_t gap, need;
+        if (__builtin_mul_overflow((size_t)(nframes - 1), frame_pitch, &gap) ||
+            __builtin_add_overflow(gap, (size_t)stride * (size_t)height, &need) || seq_pitch < need) {
+            ffhip_set_error(MESQ_WHO ": seq_pitch %zu < (nframes - 1) * frame_pitch + stride * height: the pictures of two sequences would share bytes",
+                            seq_pitch);
+            return FFHIP_EINVAL;
+        }
+    }
+    const int lg = mb_size == 16 ? 4 : 3, np = nframes > 1 ? nframes - 1 : 0;
+    const int64_t per = (int64_t)(width >> lg) * (height >> lg);          /* at most 2^24 */
+    if (per * nseq > INT_MAX || per * nseq * np > INT_MAX) {
+        ffhip_set_error(MESQ_WHO ": %d pairs of %d sequences of %lld blocks each are more than 2^31 - 1 blocks", np, nseq, (long long)per);
+        return FFHIP_EINVAL;
+    }
+    /* mv_out is read back while it is written: it shares no byte with anything else the call reads or writes */
+    const ptrdiff_t step = (ptrdiff_t)per * nseq * 4, field = step * np;
+    const ptrdiff_t planes = field ? (ptrdiff_t)(nseq - 1) * (ptrdiff_t)seq_pitch + (ptrdiff_t)(nframes - 1) * (ptrdiff_t)frame_pitch +
+                                     (ptrdiff_t)(height - 1) * stride + width : 0;
+    FFHipSpanSet others;
+    others.add(ffhip_plane_span(frames, 0, planes, 1));
+    others.add(ffhip_plane_span(cost_out, 0, field, 1));
+    if (init1)
+        others.add(ffhip_plane_span(init1, 0, field ? step : 0, 1));
+    if (init2)
+        others.add(ffhip_plane_span(init2, 0, field ? step : 0, 1));
+    others.seal();
+    if (others.hits(ffhip_plane_span(mv_out, 0, field, 1))) {
+        ffhip_set_error(MESQ_WHO ": mv_out overlaps init1, init2, frames or cost_out");
+        return FFHIP_EINVAL;
+    }
+    return 0;
+}
+
+extern "C" int ffhip_me_search_pred_sequence_dev(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                                 int nframes, size_t seq_pitch, int nseq, int direction, int mb_size, int search_param,
+                                                 int cost_kind, const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out,
+                                                 void *stream)
+{
+    const int r = me_search_seq_check(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
+                                      cost_kind, init1, init2, mv_out, cost_out);
+    if (r)
+        return r;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_me_search_seq(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size,
+                                      search_param, cost_kind, init1, init2, mv_out, cost_out, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_me_search_pred_sequence_host(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                                  int nframes, size_t seq_pitch, int nseq, int direction, int mb_size, int search_param,
+                                                  int cost_kind, const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out)
+{
+    const int r = me_search_seq_check(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
+                                      cost_kind, init1, init2, mv_out, cost_out);
+    if (r)
+        return r;
+    /* the definition: step k is the pair face over the nseq pairs (picture k, picture k + 1), its prev fields the two steps before */
+    const int lg = mb_size == 16 ? 4 : 3;
+    const size_t step = (size_t)(width >> lg) * (size_t)(height >> lg) * (size_t)nseq;    /* blocks of a step */
+    uint64_t blocks = 0, costs = 0;
+    for (int k = 0; k + 1 < nframes; k++) {
+        const uint8_t *lo = frames + (size_t)k * frame_pitch, *hi = lo + frame_pitch;
+        int16_t *mv = mv_out + 2 * step * (size_t)k;
+        const int16_t *prev1 = k >= 1 ? mv - 2 * step : init1, *prev2 = k >= 2 ? mv - 4 * step : k == 1 ? init1 : init2;
+        me_search_pred_host(method, direction ? lo : hi, direction ? hi : lo, width, height, stride, seq_pitch, nseq, mb_size, search_param,
+                            cost_kind, prev1, prev2, mv, cost_out + step * (size_t)k);
+        blocks += t_host_blocks;
+        costs += t_host_costs;
+    }
+    t_host_blocks = blocks;
+    t_host_costs = costs;
     return 0;
 }

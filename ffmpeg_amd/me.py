@@ -73,3 +73,27 @@ def search_pred_frames_host(method, cur, ref, width, height, stride, frame_pitch
                                                            nframes, mb_size, search_param, cost_kind, p(prev1), p(prev2),
                                                            mv_out.ctypes.data, cost_out.ctypes.data), "ffhip_me_search_pred_frames_host")
     return _host_counts()
+
+
+def search_pred_sequence(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
+                         cost_kind, init1, init2, mv_out, cost_out, stream=None):
+    """The predictive search `method` (EPZS or UMH) of nseq sequences of nframes pictures in one launch, pair k chained to the fields
+    of pairs k - 1 and k - 2; tensors on the device.  Picture p of sequence s is at frames + s * seq_pitch + p * frame_pitch;
+    direction 0: cur = picture k + 1, ref = picture k, 1: the other way round.  Outputs pair-major: step k's nseq fields are one batch
+    in search_pred_batch()'s layout.  init1 / init2: nseq fields each, those of the pairs before pair 0, or None for zero vectors."""
+    p = lambda t: None if t is None else t.data_ptr()
+    return _lib.check(_lib.lib().ffhip_me_search_pred_sequence_dev(method, frames.data_ptr(), width, height, stride, frame_pitch, nframes,
+                                                                   seq_pitch, nseq, direction, mb_size, search_param, cost_kind, p(init1),
+                                                                   p(init2), mv_out.data_ptr(), cost_out.data_ptr(), _stream(stream)),
+                      "ffhip_me_search_pred_sequence_dev")
+
+
+def search_pred_sequence_host(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
+                              cost_kind, init1, init2, mv_out, cost_out):
+    """The same loop on the CPU (device-free): numpy arrays, init1 / init2 arrays or None.  Returns (blocks searched, costs
+    evaluated) over all pairs."""
+    p = lambda a: None if a is None else a.ctypes.data
+    _lib.check(_lib.lib().ffhip_me_search_pred_sequence_host(method, frames.ctypes.data, width, height, stride, frame_pitch, nframes, seq_pitch,
+                                                             nseq, direction, mb_size, search_param, cost_kind, p(init1), p(init2),
+                                                             mv_out.ctypes.data, cost_out.ctypes.data), "ffhip_me_search_pred_sequence_host")
+    return _host_counts()

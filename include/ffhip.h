@@ -2985,7 +2985,8 @@ void ffhip_me_search_host_counts(uint64_t *blocks, uint64_t *costs);
  * mv_table[2]) in the layout of mv_out: nframes fields of b_w * b_h absolute positions.  rel(b), a block's relative vector, is its
  * position minus the block's origin (x_mb, y_mb); rel1 and rel2 are those of prev1 and prev2.  Either may be NULL: a field of zero
  * vectors (the filter's zero-initialised tables at the first frame).  A caller chains a sequence by rotating three buffers, one call per
- * frame on one stream.  UMH reads neither.  Any int16 content is legal: relative vectors are formed in 32 bits, and a candidate outside
+ * frame on one stream — or hands the whole sequence to ffhip_me_search_pred_sequence_dev() below, which chains the pairs inside one
+ * launch.  UMH reads neither.  Any int16 content is legal: relative vectors are formed in 32 bits, and a candidate outside
  * the window is refused by COST_P_MV as always.
  *
  * The rules below are RESTATED, NOT CHECKED AGAINST THE SOURCE (libavfilter/motion_estimation.c and vf_mestimate.c were not at hand);
@@ -3029,6 +3030,43 @@ int ffhip_me_search_pred_batch_dev(int method, const uint8_t *cur, const uint8_t
 int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
                                      size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
                                      const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out);
+
+/**
+ * The same two searches of whole sequences, every pair chained to the fields of the two pairs before it inside the launch.  There are
+ * nseq independent sequences of nframes pictures each; picture p of sequence s is at frames + s * seq_pitch + p * frame_pitch, and a
+ * sequence has np = nframes - 1 pairs.  direction 0 is the filter's dir 0: pair k is cur = picture k + 1, ref = picture k; direction 1
+ * is its dir 1: cur = picture k, ref = picture k + 1.  (The two directions of vf_minterpolate's bidirectional mode are two calls, or two
+ * sequences over differently ordered pictures; they are not interleaved here.)
+ *
+ * Outputs are pair-major, per = b_w * b_h: the field of pair k of sequence s starts at mv_out + 2 * per * (k * nseq + s), its costs at
+ * cost_out + per * (k * nseq + s), so step k's nseq fields are one contiguous batch in the layout of ffhip_me_search_pred_batch_dev().
+ * init1 / init2 hold nseq fields each in that layout: the fields of the pairs before pair 0 (k = -1 and k = -2); NULL means zero vectors.
+ * A caller continues a sequence across calls by passing the last two steps of the previous call's mv_out.
+ *
+ * DEFINITION: the bytes of mv_out and cost_out are those of this loop of calls of the pair face —
+ *   for k in 0 .. np - 1:
+ *       prev1 = k >= 1 ? field step k - 1 : init1;   prev2 = k >= 2 ? field step k - 2 : (k == 1 ? init1 : init2)
+ *       ffhip_me_search_pred_batch_dev(method, cur_k, ref_k, ..., frame_pitch = seq_pitch, nframes = nseq, ..., prev1, prev2,
+ *                                      field step k, cost step k, stream)
+ * — and no search rule is added.  Block (bx, r) of pair k reads of pair k - 1 only the collocated block and its four neighbours, so pair k
+ * runs about three block steps behind pair k - 1: a sequence is a wavefront over (pair, row), one wave per block row of a pair
+ * (kernels/me_search_seq.hip).  UMH reads no prev field; its pairs run unchained in the same launches.
+ *
+ * FFHIP_EINVAL (before any device check, each with a text): what ffhip_me_search_pred_batch_dev() refuses, applied to the pictures (NULL
+ * frames, mv_out or cost_out, the method, mb_size, cost_kind, negative sizes, stride < width, a width or height above 32768, mv_out not
+ * 4-byte aligned); direction outside 0..1; nseq < 0; nframes > 1 with frame_pitch < stride * height; nseq > 1 with
+ * seq_pitch < (nframes - 1) * frame_pitch + stride * height; mv_out sharing a byte with init1, init2, frames or cost_out; more than
+ * 2^31 - 1 blocks in total.  nframes <= 1, nseq == 0 or a picture smaller than a block: nothing is done, 0.  FFHIP_ENOSYS without a
+ * device, after the checks.  A lost hand-off (never in a correct run) is reported by ffhip_stream_synchronize() as FFHIP_EIO.
+ */
+int ffhip_me_search_pred_sequence_dev(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                      int nframes, size_t seq_pitch, int nseq, int direction, int mb_size, int search_param, int cost_kind,
+                                      const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out, void *stream);
+/** The same loop on host arrays (device-free), blocks in raster order: the same arguments but the stream, the same refusals but the
+ *  one for a missing device, the same bytes.  ffhip_me_search_host_counts() reports the blocks and costs of all its pairs. */
+int ffhip_me_search_pred_sequence_host(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                       int nframes, size_t seq_pitch, int nseq, int direction, int mb_size, int search_param, int cost_kind,
+                                       const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out);
 
 /* ------------------------------------------------------------------------------------------ */
 /* libavutil: av_tx float MDCT                                                               */

@@ -15,6 +15,12 @@ chain of about b_w + 2 * b_h blocks, and pairs of one launch overlap: their rows
 per launch, the latter with the chain's time per block.  prev1 = prev2 = the vectors EPZS finds without them (a sequence at rest).
 
     python tools/bench_me_search.py [--out profiles/me_search_bench.txt]
+
+--sequences runs another section instead: whole sequences (2, 9, 17 and 61 pictures, 1 and 2 sequences per call) through
+ffhip_me_search_pred_sequence_dev against the same pairs as chained calls of the pair face on one stream — the caller's only way before
+that face — and, for EPZS, against the same number of independent pairs in one call (sequence_section()).
+
+    python tools/bench_me_search.py --sequences [--out profiles/me_seq_search_bench.txt]
 """
 import argparse
 import os
@@ -26,6 +32,7 @@ sys.path.insert(0, ROOT)
 
 W, H, NF, MB = 3840, 2160, 8, 16
 NAMES = {1: "esa", 2: "tss", 3: "tdls", 4: "ntss", 5: "fss", 6: "ds", 7: "hexbs", 8: "epzs", 9: "umh"}
+SEQ_PICTURES, SEQ_NSEQ = (2, 9, 17, 61), (1, 2)     # the sequence section: pictures per sequence, sequences per call
 
 
 def make_input(torch):
@@ -97,16 +104,95 @@ def esa_costs_per_block(R):
     return 1 + sum(nx) * sum(ny) / (bw * bh)
 
 
+def make_sequences(torch, nseq, nframes):
+    """nseq sequences of nframes pictures: a smooth texture per sequence that drifts by a vector that changes from picture to picture
+    (at most 3 samples a picture in x and y), plus noise of +-2 -> (nseq, nframes, H, W) uint8"""
+    g = torch.Generator(device="cuda").manual_seed(61)
+    frames = torch.empty((nseq, nframes, H, W), dtype=torch.uint8, device="cuda")
+    m = 3 * nframes + 8
+    for s in range(nseq):
+        big = torch.rand((1, 1, H + 2 * m, W + 2 * m), device="cuda", generator=g)
+        big = torch.nn.functional.avg_pool2d(big, 9, stride=1, padding=4)[0, 0]
+        big = (big - big.amin()) / (big.amax() - big.amin()) * 255.0
+        x = y = m
+        for p in range(nframes):
+            dx, dy = (int(v) for v in torch.randint(-3, 4, (2,), device="cuda", generator=g).cpu())
+            x, y = x + dx, y + dy
+            frames[s, p] = (big[y:y + H, x:x + W] + torch.randint(-2, 3, (H, W), device="cuda", generator=g)).round().clamp(0, 255).to(torch.uint8)
+    return frames
+
+
+def sequence_section(torch, me, a):
+    """Sequences of 2, 9, 17 and 61 pictures, 1 and 2 sequences per call, EPZS and UMH, SAD and SATD, search_param a.R, per pair:
+      (a) chained  np calls of ffhip_me_search_pred_batch_dev on one stream, one step (nseq pairs) each, prev fields the two steps before;
+      (b) sequence one call of ffhip_me_search_pred_sequence_dev, checked equal to (a) before it is timed;
+      (c) batch    EPZS only: the np * nseq pairs as INDEPENDENT pairs in one call of the pair face (prev NULL) — not the same result:
+                   the bound a pipeline can approach, not a like-for-like figure."""
+    nb = (W // MB) * (H // MB)
+    longest = max(SEQ_PICTURES)
+    all_frames = make_sequences(torch, 2, longest)
+    plane = W * H
+    lines = ["# tools/bench_me_search.py --sequences on %s: %d x %d, %d x %d blocks, search_param %d; ms per pair = median of %d windows of >= %.2f s"
+             % (torch.cuda.get_device_name(0), W, H, MB, MB, a.R, a.rounds, a.window),
+             "# chained: np calls of the pair face on one stream (one step of nseq pairs each); sequence: one call of the sequence face, checked equal to chained;",
+             "# batch: the same pairs as independent ones in one call of the pair face (EPZS; another result: the bound, not a like-for-like figure)",
+             "%-6s %-5s %4s %4s %-9s %12s %18s %10s" % ("method", "cost", "pics", "nseq", "path", "ms/pair", "windows min..max", "x chained")]
+    for kind, kname in ((me.SAD, "sad"), (me.SATD, "satd")):
+        for method in (me.EPZS, me.UMH):
+            for nframes in SEQ_PICTURES:
+                for nseq in SEQ_NSEQ:
+                    np_ = nframes - 1
+                    frames = all_frames[:nseq]          # seq_pitch stays that of the longest sequence
+                    mv_a = torch.zeros((np_, nseq, nb * 2), dtype=torch.int16, device="cuda")
+                    mv_b, mv_c = torch.ones_like(mv_a), torch.empty_like(mv_a)
+                    cost_a = torch.zeros((np_, nseq, nb), dtype=torch.int32, device="cuda")
+                    cost_b, cost_c = torch.ones_like(cost_a), torch.empty_like(cost_a)
+
+                    def chained():
+                        for k in range(np_):
+                            me.search_pred_batch(method, frames[0, k + 1], frames[0, k], W, H, W, longest * plane, nseq, MB, a.R, kind,
+                                                 mv_a[k - 1] if k >= 1 else None, mv_a[k - 2] if k >= 2 else None, mv_a[k], cost_a[k])
+
+                    def sequence():
+                        me.search_pred_sequence(method, frames, W, H, W, plane, nframes, longest * plane, nseq, 0, MB, a.R, kind, None, None, mv_b, cost_b)
+
+                    def batch():
+                        for s in range(nseq):
+                            me.search_pred_batch(method, frames[s, 1], frames[s, 0], W, H, W, plane, np_, MB, a.R, kind, None, None, mv_c[:, s], cost_c[:, s])
+
+                    chained()
+                    sequence()
+                    torch.cuda.synchronize()
+                    assert torch.equal(mv_a, mv_b) and torch.equal(cost_a, cost_b), "the sequence face and the chained calls differ"
+                    base = None
+                    for path, call in (("chained", chained), ("sequence", sequence)) + ((("batch", batch),) if method == me.EPZS and nseq == 1 else ()):
+                        t = [x / (np_ * nseq) for x in timed(torch, call, a.window, a.rounds)]
+                        ms = statistics.median(t)
+                        base = ms if base is None else base
+                        lines.append("%-6s %-5s %4d %4d %-9s %12.4f %8.4f..%-8.4f %10.3f" % (NAMES[method], kname, nframes, nseq, path, ms, min(t), max(t), ms / base))
+                        print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "me_search_bench.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--window", type=float, default=0.25)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--sequences", action="store_true", help="the section on whole sequences (the sequence face against chained calls) instead")
+    ap.add_argument("--R", type=int, default=7, help="search_param of the sequence section")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "me_seq_search_bench.txt" if a.sequences else "me_search_bench.txt")
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_me_search: no GPU: nothing is measured")
     from ffmpeg_amd import me
+    if a.sequences:
+        lines = sequence_section(torch, me, a)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     cur, ref = make_input(torch)
     hcur, href = cur[0].cpu().numpy(), ref[0].cpu().numpy()
     nb = (W // MB) * (H // MB)
