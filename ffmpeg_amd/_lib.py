@@ -208,6 +208,13 @@ def lib():
                                                         C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
         "ffhip_me_search_pred_sequence_host": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int,
                                                          C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+        # src, dst: FFHipMePlanes *; jobs: FFHipMeInterpJob * (ffmpeg_amd/me.py has the structures)
+        "ffhip_me_interp_sequence_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   vp, vp, vp, vp, C.c_int, vp]),
+        "ffhip_me_interp_sequence_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    vp, vp, vp, vp, C.c_int]),
+        "ffhip_me_interp_host_counts": (None, [C.POINTER(C.c_uint64)]),
+        "ffhip_me_interp_job_size": (C.c_int, []),
         "ffhip_tx_init": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_uint64]),
         "ffhip_tx_uninit": (None, [C.POINTER(vp)]),

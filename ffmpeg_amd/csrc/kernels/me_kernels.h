@@ -28,4 +28,9 @@ int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *r
 int ffhip_launch_me_search_seq(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
                                size_t seq_pitch, int nseq, int direction, int mb_size, int R, int cost_kind, const int16_t *init1,
                                const int16_t *init2, int16_t *mv_out, uint32_t *cost_out, hipStream_t stream);
+/* vf_minterpolate's compensation (me_interp.hip): arguments checked, window and jobs on the host; calls of more jobs than a launch's
+ * table holds are split in stream order */
+int ffhip_launch_me_interp(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
+                           int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
+                           const FFHipMeInterpJob *jobs, int njobs, hipStream_t stream);
 #endif

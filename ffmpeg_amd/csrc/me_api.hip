@@ -2,9 +2,15 @@
  * me_api.hip — C-ABI entry points of the me_cmp / motion-search part of libffhip (include/ffhip.h).
  */
 #include <limits.h>
+#include <stdarg.h>
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+
+#include <vector>
 
 #include "kernels/common.h"
+#include "kernels/me_interp_rules.h"
 #include "kernels/me_kernels.h"
 #include "kernels/me_search_pred_rules.h"
 #include "kernels/me_search_rules.h"
@@ -426,5 +432,187 @@ extern "C" int ffhip_me_search_pred_sequence_host(int method, const uint8_t *fra
     }
     t_host_blocks = blocks;
     t_host_costs = costs;
+    return 0;
+}
+
+/* ---- vf_minterpolate's compensation of whole sequences (kernels/me_interp_rules.h) -------------------------------------------------- */
+#define MEI_WHO "ffhip_me_interp_sequence_dev / _host"
+extern "C" int ffhip_me_interp_job_size(void) { return (int)sizeof(FFHipMeInterpJob); }
+static_assert(sizeof(FFHipMeInterpJob) == 16, "the job record of include/ffhip.h");
+
+static int me_interp_refuse(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+static int me_interp_refuse(const char *fmt, ...)
+{
+    char text[400];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(text, sizeof text, fmt, ap);
+    va_end(ap);
+    ffhip_set_error(MEI_WHO ": %s", text);
+    return FFHIP_EINVAL;
+}
+
+/* plane i's size */
+static int mei_pw(int i, int width, int sw) { return i ? (width + (1 << sw) - 1) >> sw : width; }
+static int mei_ph(int i, int height, int sh) { return i ? (height + (1 << sh) - 1) >> sh : height; }
+
+static int me_interp_check(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int sw, int sh, int width, int height, int nframes,
+                           int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
+                           const FFHipMeInterpJob *jobs, int njobs)
+{
+    if (!src || !dst || !window || !jobs)
+        return me_interp_refuse("a NULL src, dst, window or jobs");
+    if (nplanes != 1 && nplanes != 3)
+        return me_interp_refuse("nplanes %d is neither 1 nor 3", nplanes);
+    for (int i = 0; i < nplanes; i++)
+        if (!src->base[i] || !dst->base[i])
+            return me_interp_refuse("plane %d of %s is NULL", i, !src->base[i] ? "src" : "dst");
+    if (sw < 0 || sw > 1 || sh < 0 || sh > 1)
+        return me_interp_refuse("chroma shifts %d, %d (0 or 1 each)", sw, sh);
+    if (mb_size != 16 && mb_size != 8)
+        return me_interp_refuse("mb_size %d (16 or 8)", mb_size);
+    if (mv_range < 0 || mv_range > MEI_MAX_RANGE)
+        return me_interp_refuse("mv_range %d outside 0..%d", mv_range, MEI_MAX_RANGE);
+    if (width < 0 || height < 0 || nframes < 0 || nseq < 0 || njobs < 0)
+        return me_interp_refuse("a negative width, height, nframes, nseq or njobs (%d, %d, %d, %d, %d)", width, height, nframes, nseq, njobs);
+    if (width > 32768 || height > 32768)
+        return me_interp_refuse("%d x %d: positions of a picture above 32768 do not fit the int16 vector fields", width, height);
+    for (int i = 0; i < nplanes; i++) {
+        const int pw = mei_pw(i, width, sw), ph = mei_ph(i, height, sh);
+        if (src->stride[i] < pw || dst->stride[i] < pw)
+            return me_interp_refuse("plane %d: a stride (src %td, dst %td) below the plane's width %d", i, src->stride[i], dst->stride[i], pw);
+        /* the sequence face's rule per plane: a picture is stride * height bytes, a sequence ends that far behind its last picture */
+        const size_t pic = (size_t)src->stride[i] * (size_t)ph, dpic = (size_t)dst->stride[i] * (size_t)ph;
+        if (nframes > 1 && src->frame_pitch[i] < pic)
+            return me_interp_refuse("plane %d: src frame_pitch %zu < stride * height %zu", i, src->frame_pitch[i], pic);
+        if (nseq > 1 && nframes > 0) {
+            size_t gap, need;
+            if (__builtin_mul_overflow((size_t)(nframes - 1), src->frame_pitch[i], &gap) || __builtin_add_overflow(gap, pic, &need) ||
+                src->seq_pitch[i] < need)
+                return me_interp_refuse("plane %d: src seq_pitch %zu < (nframes - 1) * frame_pitch + stride * height: the pictures of two sequences "
+                                        "would share bytes", i, src->seq_pitch[i]);
+        }
+        if (njobs > 1 && dst->frame_pitch[i] < dpic)
+            return me_interp_refuse("plane %d: dst frame_pitch %zu < stride * height %zu", i, dst->frame_pitch[i], dpic);
+    }
+    bool mci = false;
+    for (int j = 0; j < njobs; j++) {
+        const FFHipMeInterpJob &J = jobs[j];
+        if (J.seq < 0 || J.seq >= nseq || J.pair < 0 || J.pair > nframes - 2 || J.alpha < 0 || J.alpha > 1024 ||
+            (J.mode != FFHIP_ME_INTERP_MCI && J.mode != FFHIP_ME_INTERP_BLEND))
+            return me_interp_refuse("job %d: seq %d (0..%d), pair %d (0..%d), alpha %d (0..1024), mode %d (0 or 1)", j, J.seq, nseq - 1, J.pair,
+                                    nframes - 2, J.alpha, J.mode);
+        mci |= J.mode == FFHIP_ME_INTERP_MCI;
+    }
+    if (mci && (!mv_fwd || !mv_bwd))
+        return me_interp_refuse("a NULL mv_fwd or mv_bwd with an MCI job");
+    /* what the call writes shares no byte with what it reads */
+    const bool any = njobs > 0 && width > 0 && height > 0;
+    const int lg = mb_size == 16 ? 4 : 3;
+    const ptrdiff_t field = any && mci ? (ptrdiff_t)(width >> lg) * (height >> lg) * nseq * (nframes - 1) * 4 : 0;
+    FFHipSpanSet reads;
+    std::vector<FFHipSpan> writes;
+    for (int i = 0; i < nplanes && any; i++) {
+        const int pw = mei_pw(i, width, sw), ph = mei_ph(i, height, sh);
+        reads.add(ffhip_plane_span(src->base[i], 0, (ptrdiff_t)(nseq - 1) * (ptrdiff_t)src->seq_pitch[i] + (ptrdiff_t)(nframes - 1) * (ptrdiff_t)src->frame_pitch[i] +
+                                                        (ptrdiff_t)(ph - 1) * src->stride[i] + pw, 1));
+        writes.push_back(ffhip_plane_span(dst->base[i], 0, (ptrdiff_t)(njobs - 1) * (ptrdiff_t)dst->frame_pitch[i] + (ptrdiff_t)(ph - 1) * dst->stride[i] + pw, 1));
+    }
+    if (mv_fwd)
+        reads.add(ffhip_plane_span(mv_fwd, 0, field, 1));
+    if (mv_bwd)
+        reads.add(ffhip_plane_span(mv_bwd, 0, field, 1));
+    reads.seal();
+    for (const FFHipSpan &w : writes)
+        if (reads.hits(w))
+            return me_interp_refuse("dst overlaps src, mv_fwd or mv_bwd");
+    return 0;
+}
+
+extern "C" int ffhip_me_interp_sequence_dev(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                            int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                            const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs, void *stream)
+{
+    const int r = me_interp_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                                  mv_bwd, jobs, njobs);
+    if (r)
+        return r;
+    if (!njobs)
+        return 0;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_me_interp(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd,
+                                  jobs, njobs, (hipStream_t)stream);
+}
+
+static thread_local uint64_t t_interp_counts[MEI_NCOUNTS];
+static_assert(MEI_NCOUNTS == 8, "ffhip_me_interp_host_counts() reports eight");
+
+extern "C" void ffhip_me_interp_host_counts(uint64_t counts[8])
+{
+    if (counts)
+        memcpy(counts, t_interp_counts, sizeof t_interp_counts);
+}
+
+extern "C" int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                             int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                             const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs)
+{
+    const int r = me_interp_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                                  mv_bwd, jobs, njobs);
+    if (r)
+        return r;
+    const MeiGeom g = mei_geom(width, height, mb_size, mv_range);
+    const size_t per = (size_t)g.bw * g.bh;
+    uint64_t cnt[MEI_NCOUNTS] = {};
+    std::vector<MeiBlock> blocks(2 * per);      /* a job's windows, formed once; a malformed block's is empty */
+    for (int j = 0; j < njobs; j++) {
+        const FFHipMeInterpJob &J = jobs[j];
+        const int alpha = J.alpha;
+        const uint8_t *A[3] = {}, *B[3] = {};
+        uint8_t *D[3] = {};
+        for (int i = 0; i < nplanes; i++) {
+            A[i] = src->base[i] + (size_t)J.seq * src->seq_pitch[i] + (size_t)J.pair * src->frame_pitch[i];
+            B[i] = A[i] + src->frame_pitch[i];
+            D[i] = dst->base[i] + (size_t)j * dst->frame_pitch[i];
+        }
+        if (J.mode == FFHIP_ME_INTERP_MCI)
+            for (int dir = 0; dir < 2; dir++) {
+                const int16_t *f = (dir ? mv_bwd : mv_fwd) + 2 * per * ((size_t)J.pair * nseq + J.seq);
+                for (int by = 0; by < g.bh; by++)
+                    for (int bx = 0; bx < g.bw; bx++) {
+                        const size_t b = (size_t)by * g.bw + bx;
+                        int vx, vy;
+                        const bool ok = mei_vector(g, bx, by, f[2 * b], f[2 * b + 1], vx, vy);
+                        cnt[MEI_N_MALFORMED] += !ok;
+                        blocks[dir * per + b] = ok ? mei_block(g, alpha, dir, bx, by, vx, vy) : mei_no_block();
+                    }
+            }
+        auto block = [&](int dir, int bx, int by) -> const MeiBlock & { return blocks[dir * per + (size_t)by * g.bw + bx]; };
+        for (int i = 0; i < nplanes; i++) {
+            const int sw = i ? log2_chroma_w : 0, sh = i ? log2_chroma_h : 0, pw = mei_pw(i, width, sw), ph = mei_ph(i, height, sh);
+            const ptrdiff_t ss = src->stride[i];
+            for (int cy = 0; cy < ph; cy++)
+                for (int cx = 0; cx < pw; cx++) {
+                    uint8_t *d = D[i] + (ptrdiff_t)cy * dst->stride[i] + cx;
+                    cnt[MEI_N_SAMPLES]++;
+                    if (J.mode == FFHIP_ME_INTERP_BLEND) {
+                        *d = (uint8_t)mei_blend(A[i][cy * ss + cx], B[i][cy * ss + cx], alpha);
+                        cnt[MEI_N_BLEND]++;
+                        continue;
+                    }
+                    /* the luma pixel whose list the sample uses: itself, or the last writer of the reference's walk */
+                    const int x = std::min(((cx + 1) << sw) - 1, width - 1), y = std::min(((cy + 1) << sh) - 1, height - 1);
+                    uint64_t S = 0, Wt = 0;
+                    mei_walk(g, alpha, x, y, window, block, [&](int wa, int dxa, int dya, int wb, int dxb, int dyb) {
+                        S += (uint64_t)wa * A[i][((y >> sh) + mei_tshift(dya, sh)) * ss + (x >> sw) + mei_tshift(dxa, sw)] +
+                             (uint64_t)wb * B[i][((y >> sh) + mei_tshift(dyb, sh)) * ss + (x >> sw) + mei_tshift(dxb, sw)];
+                        Wt += (uint64_t)(wa + wb);
+                    }, i ? nullptr : cnt);
+                    *d = (uint8_t)((S + (Wt >> 1)) / Wt);
+                }
+        }
+    }
+    memcpy(t_interp_counts, cnt, sizeof cnt);
     return 0;
 }

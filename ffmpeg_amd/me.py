@@ -97,3 +97,91 @@ def search_pred_sequence_host(method, frames, width, height, stride, frame_pitch
                                                              nseq, direction, mb_size, search_param, cost_kind, p(init1), p(init2),
                                                              mv_out.ctypes.data, cost_out.ctypes.data), "ffhip_me_search_pred_sequence_host")
     return _host_counts()
+
+
+# ---- vf_minterpolate's compensation (ffhip_me_interp_sequence_dev / _host) ----------------------------------------------------------
+MCI, BLEND = 0, 1
+INTERP_COUNTS = ("taken", "zero_weight", "capped", "malformed", "fallback", "clipped", "samples", "blend")
+
+
+def _structs():
+    import ctypes as C
+
+    class Planes(C.Structure):              # FFHipMePlanes
+        _fields_ = [("base", C.c_void_p * 3), ("stride", C.c_ssize_t * 3), ("frame_pitch", C.c_size_t * 3), ("seq_pitch", C.c_size_t * 3)]
+
+    class Job(C.Structure):                 # FFHipMeInterpJob
+        _fields_ = [("seq", C.c_int32), ("pair", C.c_int32), ("alpha", C.c_int32), ("mode", C.c_int32)]
+    return Planes, Job
+
+
+def _ptr(a):
+    """an address: None, an int, a torch tensor or a numpy array"""
+    if a is None or isinstance(a, int):
+        return a
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+def planes(bases, strides, frame_pitches, seq_pitches=None):
+    """An FFHipMePlanes: picture p of sequence s, plane i, is at bases[i] + s * seq_pitches[i] + p * frame_pitches[i].  One or three
+    planes; a base is an address, a tensor or an array."""
+    Planes, _ = _structs()
+    P = Planes()
+    for i, b in enumerate(bases):
+        P.base[i] = _ptr(b)
+        P.stride[i] = strides[i]
+        P.frame_pitch[i] = frame_pitches[i]
+        P.seq_pitch[i] = seq_pitches[i] if seq_pitches is not None else 0
+    return P
+
+
+def interp_jobs(jobs):
+    """An FFHipMeInterpJob array of (seq, pair, alpha, mode) tuples"""
+    _, Job = _structs()
+    arr = (Job * max(len(jobs), 1))()
+    for j, t in enumerate(jobs):
+        arr[j] = Job(*t)
+    return arr
+
+
+def _interp_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd, jobs):
+    import ctypes as C
+    import numpy as np
+    window = np.ascontiguousarray(window, dtype=np.uint8)
+    if window.size != 4 * mb_size * mb_size and mb_size in (8, 16):
+        raise ValueError("window holds %d bytes, not (2 * mb_size)^2" % window.size)
+    arr = interp_jobs(jobs)
+    keep = (window, arr, src, dst)
+    return keep, (C.addressof(src), C.addressof(dst), nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range,
+                  window.ctypes.data, _ptr(mv_fwd), _ptr(mv_bwd), C.addressof(arr), len(jobs))
+
+
+def interp_sequence(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd,
+                    jobs, stream=None):
+    """vf_minterpolate's compensation (mci / bidir / obmc, or the blend) of every job in one launch.  src, dst: planes() of device
+    memory; window: (2 * mb_size)^2 bytes on the host; mv_fwd, mv_bwd: the direction-0 and direction-1 fields of
+    search_pred_sequence(), on the device; jobs: (seq, pair, alpha, mode) tuples, job j writes output picture j."""
+    keep, args = _interp_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                              mv_bwd, jobs)
+    r = _lib.lib().ffhip_me_interp_sequence_dev(*args, _stream(stream))
+    del keep
+    return _lib.check(r, "ffhip_me_interp_sequence_dev")
+
+
+def interp_host_counts():
+    """What this thread's last interp_sequence_host() did: a dict over INTERP_COUNTS"""
+    import ctypes as C
+    c = (C.c_uint64 * 8)()
+    _lib.lib().ffhip_me_interp_host_counts(c)
+    return dict(zip(INTERP_COUNTS, (int(v) for v in c)))
+
+
+def interp_sequence_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                         mv_bwd, jobs):
+    """The same rule on the CPU (device-free): planes() of numpy memory, numpy fields.  Returns interp_host_counts()."""
+    keep, args = _interp_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                              mv_bwd, jobs)
+    r = _lib.lib().ffhip_me_interp_sequence_host(*args)
+    del keep
+    _lib.check(r, "ffhip_me_interp_sequence_host")
+    return interp_host_counts()

@@ -3068,6 +3068,87 @@ int ffhip_me_search_pred_sequence_host(int method, const uint8_t *frames, int wi
                                        int nframes, size_t seq_pitch, int nseq, int direction, int mb_size, int search_param, int cost_kind,
                                        const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out);
 
+/**
+ * vf_minterpolate's motion-compensated interpolation of whole sequences in one launch: mi_mode=mci, me_mode=bidir, mc_mode=obmc — the
+ * overlapped-block accumulation of bidirectional_obmc() and the per-pixel weighted average of set_frame_data() — and the filter's
+ * scene-change fallback, the blend.  It consumes the fields of two ffhip_me_search_pred_sequence_dev() calls (direction 0 and 1), so
+ * frame-rate conversion is search forward, search backward, interpolation on one stream with no host round trip.  Fusing search and
+ * compensation into one launch, me_mode=bilat, mc_mode=aobmc, vsbmc, scene detection and depths above 8 bits are not here: the caller
+ * decides per job between MCI and BLEND, and the other modes stay on the CPU.
+ *
+ * Pictures are 8-bit planar, nplanes 1 (luma alone) or 3; picture p of sequence s, plane i, is at
+ * base[i] + s * seq_pitch[i] + p * frame_pitch[i], rows stride[i] apart.  Job j interpolates between pictures A = `pair` and
+ * B = `pair` + 1 of sequence `seq` at instant alpha (0 .. 1024; 0 is A's instant, 1024 is B's) and writes output picture j, at
+ * dst->base[i] + j * dst->frame_pitch[i] (dst->seq_pitch is ignored).  Any number of jobs may name the same pair.  All jobs run in one
+ * launch (in launches of 1024 jobs: a launch's jobs travel with the window table in one small device table).
+ *
+ * The rule below is RESTATED FROM MEMORY and NOT CHECKED against libavfilter/vf_minterpolate.c, which was not at hand; this text is the
+ * definition the tests pin (kernels/me_interp_rules.h is its one implementation, tests/me_interp_model.py the model written from it).
+ *   Geometry is that of the search faces: mb = mb_size (16 or 8), log2mb its logarithm, b_w = width >> log2mb, b_h = height >> log2mb,
+ *     per = b_w * b_h.  Vector fields are in the sequence face's pair-major layout: the field of pair k of sequence s starts at
+ *     mv + 2 * per * (k * nseq + s); entry b = by * b_w + bx holds an absolute position (X, Y), and its relative vector is
+ *     v = (X - (bx << log2mb), Y - (by << log2mb)), formed in 32 bits.  mv_fwd is a direction-0 field (cur = B, ref = A), mv_bwd a
+ *     direction-1 field (cur = A, ref = B).  tdiv(n) = n / 1024 is C division (towards zero); clip(v, lo, hi) is av_clip; W and H are
+ *     the luma width and height.
+ *   The contribution list of luma pixel (x, y) is built in the order dir = 0, 1; then by = 0 .. b_h - 1; then bx = 0 .. b_w - 1.  For
+ *   each block:
+ *     1. v is the block's relative vector, from mv_fwd for dir 0 and from mv_bwd for dir 1.  If |v.x| > mv_range or |v.y| > mv_range the
+ *        block is malformed and contributes nothing.  (A search window guarantees |v| <= search_param: a caller passes its
+ *        search_param as mv_range.)
+ *     2. a = dir ? alpha : 1024 - alpha;  sx = (bx << log2mb) - mb / 2 + tdiv(v.x * a), sy the same in y.
+ *     3. x0 = clip(sx, 0, W - 1), x1 = clip(sx + 2 * mb, 0, W - 1), y0 and y1 the same with H.  The block covers the pixel iff
+ *        x0 <= x < x1 and y0 <= y < y1 — so column W - 1 and row H - 1 are never covered (the reference's behaviour, kept).
+ *     4. w = window[(x - sx) + (y - sy) * 2 * mb].  If w == 0, skip.  If the list already holds 16 contributions, skip (the reference's
+ *        nb + 1 >= NB_PIXEL_MVS with two entries per contribution).
+ *     5. m = dir ? -v : v.  Append one contribution of two entries: entry one takes its sample from A with weight w * (1024 - alpha) and
+ *        displacement (clip(tdiv(m.x * alpha), -x, W - 1 - x), clip(tdiv(m.y * alpha), -y, H - 1 - y)); entry two takes its sample
+ *        from B with weight w * alpha and displacement (clip(tdiv(-m.x * (1024 - alpha)), -x, W - 1 - x), the same in y).  The tdiv
+ *        arguments are the 32-bit products (-m.x) * (1024 - alpha), not a negated quotient.
+ *   An empty list is replaced by (A, 1024 - alpha, (0, 0)), (B, alpha, (0, 0)).
+ *   Luma sample (x, y): S = sum of weight_i * ref_i[y + dy_i][x + dx_i], Wt = sum of weight_i, both unsigned 64-bit; the sample is
+ *     (S + (Wt >> 1)) / Wt.  (Wt is 1024 times the sum of the w taken, so never 0, and both sums fit 32 bits.)
+ *   Chroma sample (cx, cy) of plane 1 or 2, shifts sw = log2_chroma_w and sh = log2_chroma_h, plane size ceil(W / 2^sw) x ceil(H / 2^sh):
+ *     the reference walks luma positions and lets the last writer win, so the sample uses the list of luma pixel
+ *     x = min(((cx + 1) << sw) - 1, W - 1), y = min(((cy + 1) << sh) - 1, H - 1); entry i reads ref_i's chroma plane at
+ *     ((x >> sw) + dx_i / (1 << sw), (y >> sh) + dy_i / (1 << sh)), C divisions; the rounding is that of luma.
+ *   The displacement clips keep every read inside its plane: 0 <= x + dx <= W - 1 gives 0 <= (x >> sw) + dx / (1 << sw) <= (W - 1) >> sw,
+ *     the plane's last column; no sample outside the planes described by width, height and the shifts is read or written, and of the
+ *     fields only the per entries of the jobs' pairs are read.
+ *   FFHIP_ME_INTERP_BLEND: every sample of every plane is (alpha * B + (1024 - alpha) * A + 512) >> 10; the fields are not read.
+ * window: the caller's table of (2 * mb_size)^2 bytes on the host (the filter passes its obmc_tab_linear[4 - log2mb]); any byte content
+ * is legal.  jobs is on the host too.  A picture smaller than one block is legal: every MCI pixel then takes the empty-list fallback.
+ *
+ * FFHIP_EINVAL (before any device check, each with a text, identically in both faces): NULL src, dst, window or jobs; nplanes other
+ * than 1 or 3; a NULL plane among the first nplanes; a chroma shift outside 0..1; another mb_size; mv_range outside 0..256; a negative
+ * width, height, nframes, nseq or njobs; a width or height above 32768; a stride below its plane's width; nframes > 1 with
+ * frame_pitch < stride * plane height, nseq > 1 with seq_pitch < (nframes - 1) * frame_pitch + stride * plane height, njobs > 1 with
+ * dst->frame_pitch < stride * plane height (per plane); a job with seq outside 0..nseq - 1, pair outside 0..nframes - 2, alpha outside
+ * 0..1024 or an unknown mode (the text names the job's index); NULL mv_fwd or mv_bwd when any job is MCI; dst sharing a byte with src or
+ * with a field.  njobs == 0 (after the checks): nothing is done, 0.  FFHIP_ENOSYS without a device, after the checks.
+ */
+typedef struct FFHipMePlanes {   /* 8-bit planar; picture p of sequence s, plane i: base[i] + s * seq_pitch[i] + p * frame_pitch[i] */
+    uint8_t *base[3]; ptrdiff_t stride[3]; size_t frame_pitch[3]; size_t seq_pitch[3];
+} FFHipMePlanes;
+typedef struct FFHipMeInterpJob { int32_t seq, pair, alpha, mode; } FFHipMeInterpJob;   /* 16 bytes == ffhip_me_interp_job_size() */
+#define FFHIP_ME_INTERP_MCI   0
+#define FFHIP_ME_INTERP_BLEND 1
+int ffhip_me_interp_sequence_dev(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes /* 1 | 3 */, int log2_chroma_w, int log2_chroma_h,
+                                 int width, int height, int nframes, int nseq, int mb_size, int mv_range,
+                                 const uint8_t *window /* host, (2 * mb_size)^2 bytes */,
+                                 const int16_t *mv_fwd, const int16_t *mv_bwd /* device, pair-major */,
+                                 const FFHipMeInterpJob *jobs /* host */, int njobs, void *stream);
+/** The same rule compiled for the CPU (device-free): the same arguments but the stream, everything on the host, the same refusals but
+ *  the one for a missing device, the same bytes. */
+int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                  int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                  const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs);
+/** What the calling thread's last successful ffhip_me_interp_sequence_host() did, over all its jobs.  Per luma pixel of an MCI job, as
+ *  its list is built: [0] contributions taken, [1] skipped for weight 0, [2] skipped by the cap of 16, [5] entries (two per
+ *  contribution) whose displacement a clip changed, [4] pixels on the empty-list fallback; [3] malformed blocks, per job and direction;
+ *  [6] samples written, every plane and both modes; [7] those of them written by BLEND jobs. */
+void ffhip_me_interp_host_counts(uint64_t counts[8]);
+int ffhip_me_interp_job_size(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* libavutil: av_tx float MDCT                                                               */
 /* ------------------------------------------------------------------------------------------ */

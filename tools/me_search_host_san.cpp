@@ -57,6 +57,11 @@ int ffhip_launch_me_search_seq(int, const uint8_t *, int, int, ptrdiff_t, size_t
 {
     return FFHIP_ENOSYS;
 }
+int ffhip_launch_me_interp(const FFHipMePlanes *, const FFHipMePlanes *, int, int, int, int, int, int, int, int, const uint8_t *, const int16_t *,
+                           const int16_t *, const FFHipMeInterpJob *, int, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
 
 static uint32_t rnd_state = 24680;
 static uint32_t rnd(void)
