@@ -215,6 +215,16 @@ def lib():
                                                     vp, vp, vp, vp, C.c_int]),
         "ffhip_me_interp_host_counts": (None, [C.POINTER(C.c_uint64)]),
         "ffhip_me_interp_job_size": (C.c_int, []),
+        # the interpolation faces' arguments, then scene (pair-major flags or NULL) and scene_action
+        "ffhip_me_interp_sequence_scd_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]),
+        "ffhip_me_interp_sequence_scd_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        vp, vp, vp, vp, C.c_int, vp, C.c_int]),
+        # frames, depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, threshold, mafd_in, mafd_out, sad_out, score_out, flags_out
+        "ffhip_me_scene_sequence_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_double,
+                                                  vp, vp, vp, vp, vp, vp]),
+        "ffhip_me_scene_sequence_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_double,
+                                                   vp, vp, vp, vp, vp]),
         "ffhip_tx_init": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_uint64]),
         "ffhip_tx_uninit": (None, [C.POINTER(vp)]),

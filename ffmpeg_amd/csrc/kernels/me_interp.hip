@@ -1,6 +1,7 @@
 /*
- * me_interp.hip — k_me_interp<MB>: vf_minterpolate's motion-compensated interpolation (mci / bidir / obmc) of every job of a call in
- * one launch, and its scene-change fallback, the blend.  The rule is kernels/me_interp_rules.h; include/ffhip.h states it.
+ * me_interp.hip — k_me_interp<MB, SCD>: vf_minterpolate's motion-compensated interpolation (mci / bidir / obmc) of every job of a call in
+ * one launch, and its scene-change fallback, the blend.  The rule is kernels/me_interp_rules.h; include/ffhip.h states it.  The SCD
+ * instance serves ffhip_me_interp_sequence_scd_dev(): an MCI job whose pair is flagged in device memory takes the streaming branch.
  *
  * The reference scatters blocks into per-pixel lists; here a pixel gathers.  One workgroup (4 waves) owns a tile of MEI_TW x MEI_TH =
  * 64 x 4 luma pixels of one job, one lane per pixel — a wave takes 16 x 4 of them, so that few windows touch a wave and most of its
@@ -43,9 +44,12 @@ struct MeiParams {
     size_t sframe[3], sseq[3], dframe[3];
     const int16_t *mvf, *mvb;
     int W, H, range, nplanes, sw, sh, nseq, tiles_x, job0;
+    const uint8_t *scene;           /* ffhip_me_interp_sequence_scd_dev(): pair-major flags, or NULL */
+    int scene_action;
 };
 
-template <int MB>
+/* SCD: the launch has scene flags (ffhip_me_interp_sequence_scd_dev() with a non-NULL scene); without them the kernel is the one it was */
+template <int MB, bool SCD>
 __global__ __launch_bounds__(256) void k_me_interp(const MeiParams P, const uint8_t *__restrict__ table)
 {
     constexpr int WIN = 4 * MB * MB;
@@ -57,7 +61,9 @@ __global__ __launch_bounds__(256) void k_me_interp(const MeiParams P, const uint
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tx = blockIdx.x % P.tiles_x, ty = blockIdx.x / P.tiles_x;
     const int px0 = tx * MEI_TW, py0 = ty * MEI_TH;
-    const bool blend = job.mode == FFHIP_ME_INTERP_BLEND;       /* uniform over the workgroup */
+    /* an MCI job whose pair is flagged runs the scene action in the streaming pass: one byte per workgroup, uniform like the job */
+    const bool cut = SCD && job.mode == FFHIP_ME_INTERP_MCI && P.scene[(size_t)job.pair * P.nseq + job.seq];
+    const bool blend = job.mode == FFHIP_ME_INTERP_BLEND || cut;       /* uniform over the workgroup */
     const int wx0 = px0 + MEI_WW * wave;                        /* the walk: wave w owns columns [wx0, wx0 + 16) of the tile's 4 rows */
     const int x = blend ? px0 + lane : wx0 + (lane & (MEI_WW - 1)), y = py0 + (blend ? wave : lane / MEI_WW);
     const bool valid = x < P.W && y < P.H;
@@ -79,13 +85,14 @@ __global__ __launch_bounds__(256) void k_me_interp(const MeiParams P, const uint
     const ptrdiff_t cpos2 = ((ptrdiff_t)(y >> sh)) * P.sstride[2] + (x >> sw);
 
     if (blend) {                                        /* the streaming pass */
+        const int wb = mei_scene_alpha(cut, P.scene_action, alpha);     /* DUP: the blend at 0 or 1024 is picture A or B, exactly */
         if (valid) {
             const ptrdiff_t o = (ptrdiff_t)y * P.sstride[0] + x;
-            D[0][(ptrdiff_t)y * P.dstride[0] + x] = (uint8_t)mei_blend(A[0][o], B[0][o], alpha);
+            D[0][(ptrdiff_t)y * P.dstride[0] + x] = (uint8_t)mei_blend(A[0][o], B[0][o], wb);
         }
         if (site) {
-            D[1][((ptrdiff_t)(y >> sh)) * P.dstride[1] + (x >> sw)] = (uint8_t)mei_blend(A[1][cpos], B[1][cpos], alpha);
-            D[2][((ptrdiff_t)(y >> sh)) * P.dstride[2] + (x >> sw)] = (uint8_t)mei_blend(A[2][cpos2], B[2][cpos2], alpha);
+            D[1][((ptrdiff_t)(y >> sh)) * P.dstride[1] + (x >> sw)] = (uint8_t)mei_blend(A[1][cpos], B[1][cpos], wb);
+            D[2][((ptrdiff_t)(y >> sh)) * P.dstride[2] + (x >> sw)] = (uint8_t)mei_blend(A[2][cpos2], B[2][cpos2], wb);
         }
         return;
     }
@@ -174,6 +181,14 @@ int ffhip_launch_me_interp(const FFHipMePlanes *src, const FFHipMePlanes *dst, i
                            int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
                            const FFHipMeInterpJob *jobs, int njobs, hipStream_t stream)
 {
+    return ffhip_launch_me_interp_scd(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd,
+                                      jobs, njobs, nullptr, FFHIP_ME_SCENE_BLEND, stream);
+}
+
+int ffhip_launch_me_interp_scd(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
+                               int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
+                               const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream)
+{
     if (width <= 0 || height <= 0 || njobs <= 0)
         return 0;
     MeiParams P = {};
@@ -188,6 +203,8 @@ int ffhip_launch_me_interp(const FFHipMePlanes *src, const FFHipMePlanes *dst, i
     }
     P.mvf = mv_fwd;
     P.mvb = mv_bwd;
+    P.scene = scene;
+    P.scene_action = scene_action;
     P.W = width;
     P.H = height;
     P.range = mv_range;
@@ -217,10 +234,14 @@ int ffhip_launch_me_interp(const FFHipMePlanes *src, const FFHipMePlanes *dst, i
         S.put(jobs + j0, (size_t)n * sizeof(FFHipMeInterpJob), MEI_TABLE_WINDOW);
         P.job0 = j0;
         const int r = ffhip_progress_launch_table(stream, "ffhip_me_interp_sequence_dev: copy or launch", S.img(0), S.n, [&](uint8_t *table) {
-            if (mb_size == 16)
-                hipLaunchKernelGGL((k_me_interp<16>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+            if (mb_size == 16 && scene)
+                hipLaunchKernelGGL((k_me_interp<16, true>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+            else if (mb_size == 16)
+                hipLaunchKernelGGL((k_me_interp<16, false>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+            else if (scene)
+                hipLaunchKernelGGL((k_me_interp<8, true>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
             else
-                hipLaunchKernelGGL((k_me_interp<8>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+                hipLaunchKernelGGL((k_me_interp<8, false>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
         });
         if (r < 0)
             return r;

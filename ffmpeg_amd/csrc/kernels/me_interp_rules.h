@@ -163,4 +163,8 @@ MES_FN int mei_walk(const MeiGeom &g, int alpha, int x, int y, const uint8_t *wi
 MES_FN uint32_t mei_sample(uint32_t S, uint32_t Wt) { return (S + (Wt >> 1)) / Wt; }
 MES_FN uint32_t mei_blend(int a, int b, int alpha) { return (uint32_t)(alpha * b + (1024 - alpha) * a + 512) >> 10; }
 
+/* ffhip_me_interp_sequence_scd_dev(): the weight of picture B in the streaming pass of a job.  A flagged pair (`cut`) under
+ * FFHIP_ME_SCENE_DUP copies picture A when alpha <= 512 and picture B otherwise: mei_blend() at 0 is A and at 1024 is B, exactly */
+MES_FN int mei_scene_alpha(bool cut, int scene_action, int alpha) { return cut && scene_action == FFHIP_ME_SCENE_DUP ? (alpha <= 512 ? 0 : 1024) : alpha; }
+
 #endif

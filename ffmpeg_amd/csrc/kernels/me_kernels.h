@@ -33,4 +33,13 @@ int ffhip_launch_me_search_seq(int method, const uint8_t *frames, int width, int
 int ffhip_launch_me_interp(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
                            int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
                            const FFHipMeInterpJob *jobs, int njobs, hipStream_t stream);
+/* the same with the scene flags of ffhip_me_interp_sequence_scd_dev(): scene NULL, or pair-major flags on the device and their action */
+int ffhip_launch_me_interp_scd(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
+                               int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
+                               const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream);
+/* vf_minterpolate's scene-change detection (me_scene.hip): arguments checked, every pointer on the device; calls of more pairs than a
+ * launch's sums hold are split in stream order */
+int ffhip_launch_me_scene(const uint8_t *frames, int depth, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes, size_t seq_pitch,
+                          int nseq, double threshold, const double *mafd_in, double *mafd_out, uint64_t *sad_out, float *score_out,
+                          uint8_t *flags_out, hipStream_t stream);
 #endif

@@ -12,6 +12,7 @@
 #include "kernels/common.h"
 #include "kernels/me_interp_rules.h"
 #include "kernels/me_kernels.h"
+#include "kernels/me_scene_rules.h"
 #include "kernels/me_search_pred_rules.h"
 #include "kernels/me_search_rules.h"
 #include "kernels/picture_check.h"
@@ -554,14 +555,11 @@ extern "C" void ffhip_me_interp_host_counts(uint64_t counts[8])
         memcpy(counts, t_interp_counts, sizeof t_interp_counts);
 }
 
-extern "C" int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
-                                             int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
-                                             const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs)
+/* the host face after the checks; scene: NULL or the pair-major flags of ffhip_me_interp_sequence_scd_host() */
+static int me_interp_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width, int height,
+                          int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
+                          const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action)
 {
-    const int r = me_interp_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
-                                  mv_bwd, jobs, njobs);
-    if (r)
-        return r;
     const MeiGeom g = mei_geom(width, height, mb_size, mv_range);
     const size_t per = (size_t)g.bw * g.bh;
     uint64_t cnt[MEI_NCOUNTS] = {};
@@ -569,6 +567,10 @@ extern "C" int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFH
     for (int j = 0; j < njobs; j++) {
         const FFHipMeInterpJob &J = jobs[j];
         const int alpha = J.alpha;
+        /* an MCI job whose pair is flagged runs the scene action, sample by sample like the blend */
+        const bool cut = scene && J.mode == FFHIP_ME_INTERP_MCI && scene[(size_t)J.pair * nseq + J.seq];
+        const bool blend = J.mode == FFHIP_ME_INTERP_BLEND || cut;
+        const int wb = mei_scene_alpha(cut, scene_action, alpha);
         const uint8_t *A[3] = {}, *B[3] = {};
         uint8_t *D[3] = {};
         for (int i = 0; i < nplanes; i++) {
@@ -576,7 +578,7 @@ extern "C" int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFH
             B[i] = A[i] + src->frame_pitch[i];
             D[i] = dst->base[i] + (size_t)j * dst->frame_pitch[i];
         }
-        if (J.mode == FFHIP_ME_INTERP_MCI)
+        if (!blend)
             for (int dir = 0; dir < 2; dir++) {
                 const int16_t *f = (dir ? mv_bwd : mv_fwd) + 2 * per * ((size_t)J.pair * nseq + J.seq);
                 for (int by = 0; by < g.bh; by++)
@@ -596,8 +598,8 @@ extern "C" int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFH
                 for (int cx = 0; cx < pw; cx++) {
                     uint8_t *d = D[i] + (ptrdiff_t)cy * dst->stride[i] + cx;
                     cnt[MEI_N_SAMPLES]++;
-                    if (J.mode == FFHIP_ME_INTERP_BLEND) {
-                        *d = (uint8_t)mei_blend(A[i][cy * ss + cx], B[i][cy * ss + cx], alpha);
+                    if (blend) {
+                        *d = (uint8_t)mei_blend(A[i][cy * ss + cx], B[i][cy * ss + cx], wb);
                         cnt[MEI_N_BLEND]++;
                         continue;
                     }
@@ -614,5 +616,193 @@ extern "C" int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFH
         }
     }
     memcpy(t_interp_counts, cnt, sizeof cnt);
+    return 0;
+}
+
+extern "C" int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                             int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                             const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs)
+{
+    const int r = me_interp_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                                  mv_bwd, jobs, njobs);
+    if (r)
+        return r;
+    return me_interp_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd, jobs, njobs,
+                          nullptr, FFHIP_ME_SCENE_BLEND);
+}
+
+/* ---- the interpolation that takes its MCI-or-fallback choice from scene flags ------------------------------------------------------ */
+/* what the scd faces check beyond me_interp_check() */
+static int me_interp_scd_check(const FFHipMePlanes *dst, int nplanes, int sw, int sh, int width, int height, int nframes, int nseq, int njobs,
+                               const uint8_t *scene, int scene_action)
+{
+    if (scene_action != FFHIP_ME_SCENE_BLEND && scene_action != FFHIP_ME_SCENE_DUP) {
+        ffhip_set_error("ffhip_me_interp_sequence_scd_dev / _host: scene_action %d (1: blend, 2: duplicate)", scene_action);
+        return FFHIP_EINVAL;
+    }
+    if (!scene || njobs <= 0 || width <= 0 || height <= 0 || nframes < 2 || nseq < 1)
+        return 0;
+    FFHipSpanSet reads;
+    reads.add(ffhip_plane_span(scene, 0, (ptrdiff_t)(nframes - 1) * nseq, 1));
+    reads.seal();
+    for (int i = 0; i < nplanes; i++) {
+        const int pw = mei_pw(i, width, sw), ph = mei_ph(i, height, sh);
+        if (reads.hits(ffhip_plane_span(dst->base[i], 0, (ptrdiff_t)(njobs - 1) * (ptrdiff_t)dst->frame_pitch[i] + (ptrdiff_t)(ph - 1) * dst->stride[i] + pw, 1))) {
+            ffhip_set_error("ffhip_me_interp_sequence_scd_dev / _host: dst overlaps scene");
+            return FFHIP_EINVAL;
+        }
+    }
+    return 0;
+}
+
+extern "C" int ffhip_me_interp_sequence_scd_dev(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                                int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                                const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs,
+                                                const uint8_t *scene, int scene_action, void *stream)
+{
+    int r = me_interp_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd,
+                            jobs, njobs);
+    if (!r)
+        r = me_interp_scd_check(dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, njobs, scene, scene_action);
+    if (r)
+        return r;
+    if (!njobs)
+        return 0;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_me_interp_scd(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd,
+                                      jobs, njobs, scene, scene_action, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_me_interp_sequence_scd_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                                 int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                                 const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs,
+                                                 const uint8_t *scene, int scene_action)
+{
+    int r = me_interp_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd,
+                            jobs, njobs);
+    if (!r)
+        r = me_interp_scd_check(dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, njobs, scene, scene_action);
+    if (r)
+        return r;
+    return me_interp_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd, jobs, njobs,
+                          scene, scene_action);
+}
+
+/* ---- vf_minterpolate's scene-change detection of whole sequences (kernels/me_scene_rules.h) ------------------------------------------ */
+static int me_scene_refuse(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+static int me_scene_refuse(const char *fmt, ...)
+{
+    char text[400];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(text, sizeof text, fmt, ap);
+    va_end(ap);
+    ffhip_set_error("ffhip_me_scene_sequence_dev / _host: %s", text);
+    return FFHIP_EINVAL;
+}
+
+static int me_scene_check(const uint8_t *frames, int depth, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes, size_t seq_pitch,
+                          int nseq, double threshold, const double *mafd_in, double *mafd_out, uint64_t *sad_out, float *score_out, uint8_t *flags_out)
+{
+    if (!frames || (!sad_out && !score_out && !flags_out))
+        return me_scene_refuse("a NULL frames, or sad_out, score_out and flags_out all NULL");
+    if (depth < 8 || depth > 16)
+        return me_scene_refuse("depth %d outside 8..16", depth);
+    if (width < 1 || width > 32768 || height < 1 || height > 32768)
+        return me_scene_refuse("%d x %d: width and height are 1..32768", width, height);
+    if (nframes < 0 || nseq < 0)
+        return me_scene_refuse("a negative nframes or nseq (%d, %d)", nframes, nseq);
+    const int px = depth > 8 ? 2 : 1;
+    const ptrdiff_t row = (ptrdiff_t)width * px;
+    if (stride < row)
+        return me_scene_refuse("stride %td below the row's %td bytes", stride, row);
+    if (px == 2 && (((uintptr_t)frames | (uintptr_t)stride | frame_pitch | seq_pitch) & 1))
+        return me_scene_refuse("above 8 bits samples are uint16_t: an odd frames address, stride, frame_pitch or seq_pitch (%p, %td, %zu, %zu)",
+                               (const void *)frames, stride, frame_pitch, seq_pitch);
+    const size_t pic = (size_t)stride * (size_t)height;
+    if (nframes > 1 && frame_pitch < pic)
+        return me_scene_refuse("frame_pitch %zu < stride * height %zu", frame_pitch, pic);
+    size_t seq_end = pic;           /* a sequence ends stride * height behind the start of its last picture */
+    if (nframes > 1 && (__builtin_mul_overflow((size_t)(nframes - 1), frame_pitch, &seq_end) || __builtin_add_overflow(seq_end, pic, &seq_end)))
+        return me_scene_refuse("(nframes - 1) * frame_pitch + stride * height does not fit size_t");
+    if (nseq > 1 && nframes > 0 && seq_pitch < seq_end)
+        return me_scene_refuse("seq_pitch %zu < (nframes - 1) * frame_pitch + stride * height %zu: the pictures of two sequences would share bytes",
+                               seq_pitch, seq_end);
+    if (!(threshold >= 0.0 && threshold <= 100.0))
+        return me_scene_refuse("threshold %g is not a number in 0..100", threshold);
+    const int64_t npairs = nframes > 1 ? (int64_t)(nframes - 1) * nseq : 0;
+    if (npairs > INT_MAX)
+        return me_scene_refuse("%lld pairs: more than 2^31 - 1", (long long)npairs);
+    /* what the call writes shares no byte with what it reads or with another output */
+    FFHipSpanSet reads, writes;
+    if (nframes > 0 && nseq > 0)
+        reads.add(ffhip_plane_span(frames, 0, (ptrdiff_t)(nseq - 1) * (ptrdiff_t)seq_pitch + (ptrdiff_t)(nframes - 1) * (ptrdiff_t)frame_pitch +
+                                                  (ptrdiff_t)(height - 1) * stride + row, 1));
+    if (mafd_in)
+        reads.add(ffhip_plane_span(mafd_in, 0, (ptrdiff_t)nseq * 8, 1));
+    reads.seal();
+    const FFHipSpan out[4] = { ffhip_plane_span(mafd_out, 0, mafd_out ? (ptrdiff_t)nseq * 8 : 0, 1), ffhip_plane_span(sad_out, 0, sad_out ? (ptrdiff_t)npairs * 8 : 0, 1),
+                               ffhip_plane_span(score_out, 0, score_out ? (ptrdiff_t)npairs * 4 : 0, 1),
+                               ffhip_plane_span(flags_out, 0, flags_out ? (ptrdiff_t)npairs : 0, 1) };
+    bool shared = false;
+    for (const FFHipSpan &o : out) {
+        shared |= reads.hits(o);
+        writes.add(o);
+    }
+    if (writes.seal() || shared)
+        return me_scene_refuse("an output (mafd_out, sad_out, score_out, flags_out) overlaps frames, mafd_in or another output");
+    return 0;
+}
+
+extern "C" int ffhip_me_scene_sequence_dev(const uint8_t *frames, int depth, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                                           size_t seq_pitch, int nseq, double threshold, const double *mafd_in, double *mafd_out, uint64_t *sad_out,
+                                           float *score_out, uint8_t *flags_out, void *stream)
+{
+    const int r = me_scene_check(frames, depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, threshold, mafd_in, mafd_out, sad_out,
+                                 score_out, flags_out);
+    if (r)
+        return r;
+    if (!nseq || (nframes <= 1 && !mafd_out))
+        return 0;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_me_scene(frames, depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, threshold, mafd_in, mafd_out, sad_out,
+                                 score_out, flags_out, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_me_scene_sequence_host(const uint8_t *frames, int depth, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                                            size_t seq_pitch, int nseq, double threshold, const double *mafd_in, double *mafd_out, uint64_t *sad_out,
+                                            float *score_out, uint8_t *flags_out)
+{
+    const int r = me_scene_check(frames, depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, threshold, mafd_in, mafd_out, sad_out,
+                                 score_out, flags_out);
+    if (r)
+        return r;
+    const int steps = nframes > 1 ? nframes - 1 : 0;
+    for (int s = 0; s < nseq; s++) {
+        const uint8_t *const S = frames + (size_t)s * seq_pitch;
+        const double prev = mes_scene_walk(steps, width, height, depth, threshold, mafd_in ? mafd_in[s] : 0.0,
+            [&](int k) {
+                const uint8_t *const A = S + (size_t)k * frame_pitch, *const B = A + frame_pitch;
+                uint64_t sad = 0;
+                for (int y = 0; y < height; y++)
+                    sad += depth > 8 ? mes_scene_sad_row(reinterpret_cast<const uint16_t *>(A + (ptrdiff_t)y * stride),
+                                                         reinterpret_cast<const uint16_t *>(B + (ptrdiff_t)y * stride), width)
+                                     : mes_scene_sad_row(A + (ptrdiff_t)y * stride, B + (ptrdiff_t)y * stride, width);
+                return sad;
+            },
+            [&](int k, uint64_t sad, float score, int flag) {
+                const size_t o = (size_t)k * nseq + s;
+                if (sad_out)
+                    sad_out[o] = sad;
+                if (score_out)
+                    score_out[o] = score;
+                if (flags_out)
+                    flags_out[o] = (uint8_t)flag;
+            });
+        if (mafd_out)
+            mafd_out[s] = prev;
+    }
     return 0;
 }

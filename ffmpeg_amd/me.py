@@ -185,3 +185,48 @@ def interp_sequence_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width,
     del keep
     _lib.check(r, "ffhip_me_interp_sequence_host")
     return interp_host_counts()
+
+
+# ---- vf_minterpolate's scene-change detection (ffhip_me_scene_sequence_dev / _host) and the interpolation that takes its flags -------
+SCENE_BLEND, SCENE_DUP = 1, 2
+
+
+def scene_sequence(frames, depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, threshold, mafd_in=None, mafd_out=None,
+                   sad_out=None, score_out=None, flags_out=None, stream=None):
+    """The scene-change detection of nseq sequences of nframes pictures, nothing read back: per pair (pair-major, k * nseq + s) the
+    whole-picture SAD (sad_out, uint64), the score (score_out, float32) and the flag score >= threshold (flags_out, uint8); any of the
+    three may be None, not all.  mafd_in / mafd_out: nseq doubles, the carried value before the first and after the last pair.
+    Everything is an address or a tensor on the device; frames as in search_pred_sequence(), uint16 samples above depth 8."""
+    return _lib.check(_lib.lib().ffhip_me_scene_sequence_dev(_ptr(frames), depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq,
+                                                             threshold, _ptr(mafd_in), _ptr(mafd_out), _ptr(sad_out), _ptr(score_out),
+                                                             _ptr(flags_out), _stream(stream)), "ffhip_me_scene_sequence_dev")
+
+
+def scene_sequence_host(frames, depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, threshold, mafd_in=None, mafd_out=None,
+                        sad_out=None, score_out=None, flags_out=None):
+    """The same rule on the CPU (device-free): addresses or numpy arrays."""
+    return _lib.check(_lib.lib().ffhip_me_scene_sequence_host(_ptr(frames), depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq,
+                                                              threshold, _ptr(mafd_in), _ptr(mafd_out), _ptr(sad_out), _ptr(score_out),
+                                                              _ptr(flags_out)), "ffhip_me_scene_sequence_host")
+
+
+def interp_sequence_scd(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd,
+                        jobs, scene, scene_action=SCENE_BLEND, stream=None):
+    """interp_sequence() with the MCI-or-fallback choice taken from device memory: scene is scene_sequence()'s flags_out (or None); an
+    MCI job whose pair is flagged runs scene_action (SCENE_BLEND, or SCENE_DUP: picture A when alpha <= 512, else picture B)."""
+    keep, args = _interp_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                              mv_bwd, jobs)
+    r = _lib.lib().ffhip_me_interp_sequence_scd_dev(*args, _ptr(scene), scene_action, _stream(stream))
+    del keep
+    return _lib.check(r, "ffhip_me_interp_sequence_scd_dev")
+
+
+def interp_sequence_scd_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                             mv_bwd, jobs, scene, scene_action=SCENE_BLEND):
+    """The same on the CPU (device-free): scene a numpy array of flags or None.  Returns interp_host_counts()."""
+    keep, args = _interp_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv_fwd,
+                              mv_bwd, jobs)
+    r = _lib.lib().ffhip_me_interp_sequence_scd_host(*args, _ptr(scene), scene_action)
+    del keep
+    _lib.check(r, "ffhip_me_interp_sequence_scd_host")
+    return interp_host_counts()

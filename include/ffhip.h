@@ -3073,8 +3073,9 @@ int ffhip_me_search_pred_sequence_host(int method, const uint8_t *frames, int wi
  * overlapped-block accumulation of bidirectional_obmc() and the per-pixel weighted average of set_frame_data() — and the filter's
  * scene-change fallback, the blend.  It consumes the fields of two ffhip_me_search_pred_sequence_dev() calls (direction 0 and 1), so
  * frame-rate conversion is search forward, search backward, interpolation on one stream with no host round trip.  Fusing search and
- * compensation into one launch, me_mode=bilat, mc_mode=aobmc, vsbmc, scene detection and depths above 8 bits are not here: the caller
- * decides per job between MCI and BLEND, and the other modes stay on the CPU.
+ * compensation into one launch, me_mode=bilat, mc_mode=aobmc, vsbmc and depths above 8 bits are not here: in this face the caller
+ * decides per job between MCI and BLEND (ffhip_me_scene_sequence_dev() and ffhip_me_interp_sequence_scd_dev() below take that decision
+ * on the device), and the other modes stay on the CPU.
  *
  * Pictures are 8-bit planar, nplanes 1 (luma alone) or 3; picture p of sequence s, plane i, is at
  * base[i] + s * seq_pitch[i] + p * frame_pitch[i], rows stride[i] apart.  Job j interpolates between pictures A = `pair` and
@@ -3148,6 +3149,75 @@ int ffhip_me_interp_sequence_host(const FFHipMePlanes *src, const FFHipMePlanes 
  *  [6] samples written, every plane and both modes; [7] those of them written by BLEND jobs. */
 void ffhip_me_interp_host_counts(uint64_t counts[8]);
 int ffhip_me_interp_job_size(void);
+
+/**
+ * vf_minterpolate's scene-change detection (detect_scene_change() with scd=fdiff) of whole sequences on the device, nothing read back:
+ * the whole-picture SAD of every pair of consecutive pictures (the ff_scene_sad_get_fn() member that vf_scdet, vf_select and
+ * vf_freezedetect call too), the score with its one carried double, and the threshold.  flags_out is what
+ * ffhip_me_interp_sequence_scd_dev() takes as `scene`, so frame-rate conversion is search forward, search backward, detection,
+ * interpolation: four calls on one stream with no host round trip.  Clearing the chained search's previous fields at a cut and fusing
+ * the SAD into the search are not here.
+ *
+ * Pictures are one plane (luma); picture p of sequence s is at frames + s * seq_pitch + p * frame_pitch, rows `stride` bytes apart: the
+ * layout of ffhip_me_search_pred_sequence_dev().  Samples are uint8_t at depth 8 and uint16_t at depths 9..16.
+ *
+ * The rule below is RESTATED FROM MEMORY and NOT CHECKED against libavfilter/vf_minterpolate.c and scene_sad.c, which were not at hand;
+ * this text is the definition the tests pin (kernels/me_scene_rules.h is its one implementation, tests/me_scene_model.py the model).
+ *   Pair k of sequence s is pictures A = k and B = k + 1 of that sequence.  Outputs are pair-major: pair k of sequence s is element
+ *     k * nseq + s, the layout of the search and interpolation faces.
+ *   sad(k, s) = the sum over the width x height samples of |A - B|, exact, uint64_t.  At depths 9..16 a sample is the full 16-bit value
+ *     of its uint16_t (as ff_scene_sad16_c reads it), whatever `depth` says.  Bytes of a row beyond `width` samples are never read.
+ *   mafd = (double)sad * 100.0 / (height * width) / (1 << depth): the int product, then the two divisions, in that order.
+ *   diff = fabs(mafd - prev);  score = av_clipf((float)FFMIN(mafd, diff), 0.0f, 100.0f): the conversion to float is part of the rule.
+ *   flag = (double)score >= threshold.
+ *   prev = mafd afterwards.  Before pair 0 of sequence s, prev is mafd_in[s], or 0.0 when mafd_in is NULL; after the last pair it goes to
+ *     mafd_out[s] when mafd_out is non-NULL, so a call continues another.
+ *   The library is built with -ffp-contract=off and without fast-math: doubles and floats come out bit-identical on host and device.
+ * sad_out (uint64_t), score_out (float) and flags_out (uint8_t, 0 or 1) hold one element per pair; any of the three may be NULL, not all.
+ * Every element of every pair is overwritten: the caller clears nothing.  mafd_in and mafd_out hold nseq doubles.  All pointers are
+ * device memory (naturally aligned for their type); the call is queued on `stream` and returns.  Any pair count runs: the sums of a
+ * launch live in a small device table of 4096 pairs, and a call with more is split in stream order.
+ * nframes <= 1 or nseq == 0: no pair output is written; mafd_out, when given, receives mafd_in (or zeros); 0.
+ *
+ * FFHIP_EINVAL (before any device check, each with a text, identically in both faces): NULL frames, or all three outputs NULL; depth
+ * outside 8..16; width or height outside 1..32768; a negative nframes or nseq; stride below the row's bytes; above 8 bits an odd frames
+ * address, stride, frame_pitch or seq_pitch; nframes > 1 with frame_pitch < stride * height; nseq > 1 with seq_pitch <
+ * (nframes - 1) * frame_pitch + stride * height; threshold not a number in 0..100; an output (mafd_out counts as one) sharing a byte with
+ * frames, with mafd_in or with another output; more than 2^31 - 1 pairs.  FFHIP_ENOSYS without a device, after the checks.
+ */
+int ffhip_me_scene_sequence_dev(const uint8_t *frames, int depth, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                                size_t seq_pitch, int nseq, double threshold, const double *mafd_in, double *mafd_out, uint64_t *sad_out,
+                                float *score_out, uint8_t *flags_out, void *stream);
+/** The same rule compiled for the CPU (device-free): the same arguments but the stream, everything on the host, the same refusals but
+ *  the one for a missing device, the same bits. */
+int ffhip_me_scene_sequence_host(const uint8_t *frames, int depth, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                                 size_t seq_pitch, int nseq, double threshold, const double *mafd_in, double *mafd_out, uint64_t *sad_out,
+                                 float *score_out, uint8_t *flags_out);
+
+/**
+ * ffhip_me_interp_sequence_dev() with its MCI-or-fallback choice taken from device memory: `scene` holds one flag byte per pair,
+ * pair-major (nframes - 1 steps of nseq bytes: flags_out of ffhip_me_scene_sequence_dev()).  A job whose mode is FFHIP_ME_INTERP_MCI and
+ * whose pair's flag is non-zero runs `scene_action` instead:
+ *   FFHIP_ME_SCENE_BLEND  the blend of FFHIP_ME_INTERP_BLEND;
+ *   FFHIP_ME_SCENE_DUP    every plane of picture A is copied when alpha <= 512, else of picture B (the filter's "duplicate frame" at a
+ *                         cut, alpha > ALPHA_MAX / 2).
+ * Both are offered because this restatement is not certain which one the reference takes.  Job modes stay 0 or 1: DUP is reached only
+ * through a flag.  A flag on a BLEND job changes nothing; scene NULL gives exactly ffhip_me_interp_sequence_dev()'s bytes.  In the
+ * kernel the choice is one uniform byte load per workgroup.  ffhip_me_interp_host_counts() keeps its eight meanings after the host
+ * face; samples written by either action count under [7].
+ * FFHIP_EINVAL: everything ffhip_me_interp_sequence_dev() refuses, an unknown scene_action, dst sharing a byte with scene.
+ */
+#define FFHIP_ME_SCENE_BLEND 1
+#define FFHIP_ME_SCENE_DUP   2
+int ffhip_me_interp_sequence_scd_dev(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                     int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                     const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs,
+                                     const uint8_t *scene /* device, or NULL */, int scene_action, void *stream);
+/** The same on the CPU: scene on the host. */
+int ffhip_me_interp_sequence_scd_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                      int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                      const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs,
+                                      const uint8_t *scene /* host, or NULL */, int scene_action);
 
 /* ------------------------------------------------------------------------------------------ */
 /* libavutil: av_tx float MDCT                                                               */
