@@ -142,17 +142,19 @@ class Batch:
     dpos[i], dslot[i] the same for the destination; flat (put_hevc_*): dpos[i] is an int16 offset, dslot[i] = (o0, o1)
     s2pos[i] int16 offset of the other list's block"""
 
-    def __init__(self, cells, margin, sstride, dstride, flat=False):
+    def __init__(self, cells, margin, sstride, dstride, flat=False, smodulus=4, dmodulus=4, dmax=64):
+        """smodulus / dmodulus: what c.smod / c.dmod are residues of (tests/h264_mc_matrix.py: 16); dmax: the largest block, the
+        side of a destination slot's interior"""
         self.cells, self.margin, self.sstride, self.dstride, self.flat = cells, margin, sstride, dstride, flat
         b, a = margin
-        sizes = [(c.h + b + a + 2 * SLACK_Y, c.w + b + a + 2 * SLACK_X + 3) for c in cells]
+        sizes = [(c.h + b + a + 2 * SLACK_Y, c.w + b + a + 2 * SLACK_X + smodulus - 1) for c in cells]
         at, rows = _pack(sizes, sstride)
         self.srows = rows + 2                                   # a guard row above and below: the plane's own slack
         self.spos, self.foot, self.sslot = [], [], []
         for c, (y, x), (hh, ww) in zip(cells, at, sizes):
             y += 1
             py, px = y + SLACK_Y + b, x + SLACK_X + b
-            px += (c.smod - (py * sstride + px)) % 4
+            px += (c.smod - (py * sstride + px)) % smodulus
             self.spos.append((py, px))
             self.foot.append((py - (b if c.my else 0), py + c.h + (a if c.my else 0), px - (b if c.mx else 0), px + c.w + (a if c.mx else 0)))
             self.sslot.append((y, y + hh, x, x + ww))
@@ -166,11 +168,11 @@ class Batch:
                 self.dslot.append((i * size, (i + 1) * size))
             self.dlen = len(cells) * size
         else:
-            hh, ww = 64 + 2 * DSLACK, 64 + 2 * DSLACK + 3
+            hh, ww = dmax + 2 * DSLACK, dmax + 2 * DSLACK + dmodulus - 1
             at, self.drows = _pack([(hh, ww)] * len(cells), dstride)
             for c, (y, x) in zip(cells, at):
                 py, px = y + DSLACK, x + DSLACK
-                px += (c.dmod - (py * dstride + px)) % 4
+                px += (c.dmod - (py * dstride + px)) % dmodulus
                 self.dpos.append((py, px))
                 self.dslot.append((y, y + hh, x, x + ww))
         self.s2size = 64 * 64 + 8
