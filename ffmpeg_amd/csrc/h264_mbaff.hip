@@ -257,14 +257,14 @@ __device__ __forceinline__ void mb_publish(int *counter, int value, int lane)
 } // namespace
 
 /* one wave per pair row; progress[p] = "every pair left of this one is reconstructed".  PIX = uint8_t, or uint16_t above 8 bits (strides and
- * plane pointers in bytes, int32 coefficients: h264_intra_mb.h ImbCoef) */
+ * plane pointers in bytes, int32 coefficients: h264_tx_rules.h H264Coef) */
 template <typename PIX>
 __global__ __launch_bounds__(64) void k_h264_mbaff_intra(uint8_t *py, uint8_t *pcb, uint8_t *pcr, ptrdiff_t sy, ptrdiff_t sc, int mb_w, int mb_h,
                                                          const FFHipH264IntraMB *recs, const uint32_t *geo, const int32_t *row_start,
                                                          const int16_t *coefs, int *progress, int *fail, int maxv)
 {
     typedef typename FFHipQuad<PIX>::T Q;
-    typedef typename ImbCoef<PIX>::T CF;
+    typedef typename H264Coef<PIX>::T CF;
     constexpr int PS = (int)sizeof(PIX);
     __shared__ __align__(16) ImbTileT<PIX> T;
     __shared__ __align__(16) FFHipH264IntraMB R;

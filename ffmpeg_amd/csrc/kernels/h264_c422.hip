@@ -61,7 +61,7 @@ __global__ __launch_bounds__(64) void k_h264_intra_c422(FFHipC422IntraSet S, ptr
     const int16_t *const coefs = S.pic[blockIdx.y].coefs;
     progress += (size_t)blockIdx.y * (size_t)mb_h;
     typedef typename FFHipQuad<PIX>::T Q;
-    typedef typename ImbCoef<PIX>::T CF;
+    typedef typename H264Coef<PIX>::T CF;
     constexpr int PS = (int)sizeof(PIX);
     __shared__ __align__(16) ImbTileC422<PIX> T;
     __shared__ __align__(16) FFHipH264IntraC422 Rs;

@@ -21,37 +21,20 @@
 #include "common.h"
 #include "h264_kernels.h"
 #include "h264_lf_line.h"
+#include "h264_tx_rules.h"
 
 namespace {
-
-template <typename P> struct HbdCoef { typedef int16_t T; };
-template <> struct HbdCoef<uint16_t> { typedef int32_t T; };
 
 __device__ __forceinline__ int hclip(int v, int maxv) { return min(max(v, 0), maxv); }
 
 /* ---- IDCT ------------------------------------------------------------------------------------------------------------------ */
-__device__ __forceinline__ void hbd_idct8_1d(const int (&in)[8], uint32_t (&out)[8])
-{
-    const uint32_t a0 = (uint32_t)in[0] + (uint32_t)in[4], a2 = (uint32_t)in[0] - (uint32_t)in[4];
-    const uint32_t a4 = (uint32_t)(in[2] >> 1) - (uint32_t)in[6], a6 = (uint32_t)(in[6] >> 1) + (uint32_t)in[2];
-    const uint32_t b0 = a0 + a6, b2 = a2 + a4, b4 = a2 - a4, b6 = a0 - a6;
-    const int a1 = (int)(-(uint32_t)in[3] + (uint32_t)in[5] - (uint32_t)in[7] - (uint32_t)(in[7] >> 1));
-    const int a3 = (int)((uint32_t)in[1] + (uint32_t)in[7] - (uint32_t)in[3] - (uint32_t)(in[3] >> 1));
-    const int a5 = (int)(-(uint32_t)in[1] + (uint32_t)in[7] + (uint32_t)in[5] + (uint32_t)(in[5] >> 1));
-    const int a7 = (int)((uint32_t)in[3] + (uint32_t)in[5] + (uint32_t)in[1] + (uint32_t)(in[1] >> 1));
-    const uint32_t b1 = (uint32_t)(a7 >> 2) + (uint32_t)a1, b3 = (uint32_t)a3 + (uint32_t)(a5 >> 2);
-    const uint32_t b5 = (uint32_t)(a3 >> 2) - (uint32_t)a5, b7 = (uint32_t)a7 - (uint32_t)(a1 >> 2);
-    out[0] = b0 + b7; out[7] = b0 - b7; out[1] = b2 + b5; out[6] = b2 - b5;
-    out[2] = b4 + b3; out[5] = b4 - b3; out[3] = b6 + b1; out[4] = b6 - b1;
-}
-
 /* one block: kind FFHIP_H264_IDCT4 .. ADD_PIXELS8_CLEAR; c = its N*N coefficients (cleared as the reference clears them) */
 template <typename P, int N>
-__device__ __forceinline__ void hbd_block(int kind, P *dst, ptrdiff_t s, typename HbdCoef<P>::T *c, int maxv)
+__device__ __forceinline__ void hbd_block(int kind, P *dst, ptrdiff_t s, typename H264Coef<P>::T *c, int maxv)
 {
-    typedef typename HbdCoef<P>::T CF;
+    typedef typename H264Coef<P>::T CF;
     if (kind == FFHIP_H264_IDCT4_DC || kind == FFHIP_H264_IDCT8_DC) {
-        const int dc = ((int)c[0] + 32) >> 6;
+        const int dc = h264tx_dc(c[0]);
         c[0] = 0;
 #pragma unroll
         for (int y = 0; y < N; y++)
@@ -60,10 +43,10 @@ __device__ __forceinline__ void hbd_block(int kind, P *dst, ptrdiff_t s, typenam
                 dst[y * s + x] = (P)hclip((int)dst[y * s + x] + dc, maxv);
         return;
     }
-    int v[N][N]; /* v[row][col] */
+    int v[N * N]; /* block[], the layout of h264tx_idct4 / h264tx_idct8 */
 #pragma unroll
     for (int i = 0; i < N * N; i++)
-        v[i / N][i % N] = (int)c[i];
+        v[i] = (int)c[i];
 #pragma unroll
     for (int i = 0; i < N * N; i++)
         c[i] = 0;
@@ -72,48 +55,25 @@ __device__ __forceinline__ void hbd_block(int kind, P *dst, ptrdiff_t s, typenam
         for (int y = 0; y < N; y++)
 #pragma unroll
             for (int x = 0; x < N; x++)
-                dst[y * s + x] = (P)((unsigned)dst[y * s + x] + (unsigned)v[y][x]); /* the sample type's wrap-around, no clip */
+                dst[y * s + x] = (P)((unsigned)dst[y * s + x] + (unsigned)v[y * N + x]); /* the sample type's wrap-around, no clip */
         return;
     }
-    v[0][0] += 32;
-    if (N == 4) {
-        /* pass 1 over block[i + 4 k] (k = 0..3: down a column of the stored 4x4), results stored back through the coefficient type */
+    if constexpr (N == 4) {
+        h264tx_idct4<CF>(v);
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t z0 = (uint32_t)v[0][i] + (uint32_t)v[2][i], z1 = (uint32_t)v[0][i] - (uint32_t)v[2][i];
-            const uint32_t z2 = (uint32_t)(v[1][i] >> 1) - (uint32_t)v[3][i], z3 = (uint32_t)v[1][i] + (uint32_t)(v[3][i] >> 1);
-            v[0][i] = (CF)(z0 + z3); v[1][i] = (CF)(z1 + z2); v[2][i] = (CF)(z1 - z2); v[3][i] = (CF)(z0 - z3);
-        }
+        for (int i = 0; i < 4; i++)     /* v[4 * i + k] goes DOWN column i of dst */
 #pragma unroll
-        for (int i = 0; i < 4; i++) { /* pass 2 over block[4 i + k]: its outputs go DOWN column i of dst */
-            const uint32_t z0 = (uint32_t)v[i][0] + (uint32_t)v[i][2], z1 = (uint32_t)v[i][0] - (uint32_t)v[i][2];
-            const uint32_t z2 = (uint32_t)(v[i][1] >> 1) - (uint32_t)v[i][3], z3 = (uint32_t)v[i][1] + (uint32_t)(v[i][3] >> 1);
-            dst[i] = (P)hclip((int)dst[i] + ((int)(z0 + z3) >> 6), maxv);
-            dst[i + s] = (P)hclip((int)dst[i + s] + ((int)(z1 + z2) >> 6), maxv);
-            dst[i + 2 * s] = (P)hclip((int)dst[i + 2 * s] + ((int)(z1 - z2) >> 6), maxv);
-            dst[i + 3 * s] = (P)hclip((int)dst[i + 3 * s] + ((int)(z0 - z3) >> 6), maxv);
-        }
+            for (int k = 0; k < 4; k++)
+                dst[i + k * s] = (P)hclip((int)dst[i + k * s] + v[4 * i + k], maxv);
     } else {
+        h264tx_idct8_first<CF>(v);
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int in[8];
-            uint32_t out[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) in[k] = v[k % N][i % N];
-            hbd_idct8_1d(in, out);
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k % N][i % N] = (CF)out[k];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int in[8];
-            uint32_t out[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) in[k] = v[i % N][k % N];
-            hbd_idct8_1d(in, out);
+        for (int i = 0; i < 8; i++) {   /* column i is added as it comes: all 64 results at once cost an occupancy step at 8 bits */
+            uint32_t o[8];
+            h264tx_idct8_1d<1>(v + 8 * i, o);
 #pragma unroll
             for (int k = 0; k < 8; k++)
-                dst[i + k * s] = (P)hclip((int)dst[i + k * s] + ((int)out[k] >> 6), maxv);
+                dst[i + k * s] = (P)hclip((int)dst[i + k * s] + ((int)o[k] >> 6), maxv);
         }
     }
 }
@@ -122,7 +82,7 @@ template <typename P>
 __global__ __launch_bounds__(64) void k_h264_idct_hbd(int kind, uint8_t *dst_base, ptrdiff_t stride, const int32_t *dst_offset, int16_t *blocks,
                                                      int n, int bd)
 {
-    typedef typename HbdCoef<P>::T CF;
+    typedef typename H264Coef<P>::T CF;
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n)
         return;
@@ -153,7 +113,7 @@ template <typename P>
 __global__ __launch_bounds__(64) void k_h264_idct_mb_hbd(int which, uint8_t *dst_base, uint8_t *dst2, ptrdiff_t stride, const int32_t *mb_offset,
                                                         const int32_t *blockoffset, int16_t *blocks, const uint8_t *nnzc, int nmb, int bd)
 {
-    typedef typename HbdCoef<P>::T CF;
+    typedef typename H264Coef<P>::T CF;
     const int per = which == 1 ? 4 : which == 3 ? 8 : 16; /* lanes per macroblock */
     const int t = blockIdx.x * 64 + threadIdx.x, m = t / per, k = t % per;
     if (m >= nmb)
@@ -201,57 +161,41 @@ __global__ __launch_bounds__(64) void k_h264_dc_dequant_hbd(int which, CF *outpu
     const int m = blockIdx.x * 64 + threadIdx.x;
     if (m >= n)
         return;
-    const uint32_t q = (uint32_t)qmul[m];
     if (which == 0) {
         const CF *in = input + (size_t)m * in_pitch;
         CF *out = output + (size_t)m * out_pitch;
-        int temp[16];
+        int dc[16];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int z0 = (int)in[4 * i] + (int)in[4 * i + 1], z1 = (int)in[4 * i] - (int)in[4 * i + 1];
-            const int z2 = (int)in[4 * i + 2] - (int)in[4 * i + 3], z3 = (int)in[4 * i + 2] + (int)in[4 * i + 3];
-            temp[4 * i] = z0 + z3; temp[4 * i + 1] = z0 - z3; temp[4 * i + 2] = z1 - z2; temp[4 * i + 3] = z1 + z2;
-        }
+        for (int i = 0; i < 16; i++)
+            dc[i] = (int)in[i];
+        h264tx_luma_dc<CF>(dc, qmul[m]);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int o = i == 0 ? 0 : i == 1 ? 32 : i == 2 ? 128 : 160;
-            const uint32_t z0 = (uint32_t)temp[i] + (uint32_t)temp[8 + i], z1 = (uint32_t)temp[i] - (uint32_t)temp[8 + i];
-            const uint32_t z2 = (uint32_t)temp[4 + i] - (uint32_t)temp[12 + i], z3 = (uint32_t)temp[4 + i] + (uint32_t)temp[12 + i];
-            out[o] = (CF)((int)((z0 + z3) * q + 128) >> 8);
-            out[16 + o] = (CF)((int)((z1 + z2) * q + 128) >> 8);
-            out[64 + o] = (CF)((int)((z1 - z2) * q + 128) >> 8);
-            out[80 + o] = (CF)((int)((z0 - z3) * q + 128) >> 8);
+            out[o] = (CF)dc[4 * i];
+            out[16 + o] = (CF)dc[4 * i + 1];
+            out[64 + o] = (CF)dc[4 * i + 2];
+            out[80 + o] = (CF)dc[4 * i + 3];
         }
         return;
     }
     CF *b = output + block_offset[m];
     if (which == 1) {
-        uint32_t a = (uint32_t)(int)b[0], bb = (uint32_t)(int)b[16], c = (uint32_t)(int)b[32], d = (uint32_t)(int)b[48];
-        const uint32_t e = a - bb;
-        a = a + bb;
-        bb = c - d;
-        c = c + d;
-        b[0] = (CF)((int)((a + c) * q) >> 7);
-        b[16] = (CF)((int)((e + bb) * q) >> 7);
-        b[32] = (CF)((int)((a - c) * q) >> 7);
-        b[48] = (CF)((int)((e - bb) * q) >> 7);
+        int dc[4] = { (int)b[0], (int)b[16], (int)b[32], (int)b[48] };
+        h264tx_chroma_dc<CF>(dc, qmul[m]);
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            b[16 * j] = (CF)dc[j];
         return;
     }
-    uint32_t temp[8];
+    int dc[8];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        temp[2 * i] = (uint32_t)(int)b[32 * i] + (uint32_t)(int)b[32 * i + 16];
-        temp[2 * i + 1] = (uint32_t)(int)b[32 * i] - (uint32_t)(int)b[32 * i + 16];
-    }
+    for (int j = 0; j < 8; j++)
+        dc[j] = (int)b[16 * j];
+    h264tx_chroma422_dc<CF>(dc, qmul[m]);
 #pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const int o = 16 * i;
-        const uint32_t z0 = temp[i] + temp[4 + i], z1 = temp[i] - temp[4 + i], z2 = temp[2 + i] - temp[6 + i], z3 = temp[2 + i] + temp[6 + i];
-        b[o] = (CF)((int)((z0 + z3) * q + 128) >> 8);
-        b[32 + o] = (CF)((int)((z1 + z2) * q + 128) >> 8);
-        b[64 + o] = (CF)((int)((z1 - z2) * q + 128) >> 8);
-        b[96 + o] = (CF)((int)((z0 - z3) * q + 128) >> 8);
-    }
+    for (int j = 0; j < 8; j++)
+        b[16 * j] = (CF)dc[j];
 }
 
 /* ---- loop filter: 16 lanes per edge, lane = sample line.  FFHipH264Edge.pad = lines per tc0 entry (0: luma 4, chroma 2) ------------ */

@@ -20,33 +20,12 @@
  */
 #include "common.h"
 #include "h264_kernels.h"
+#include "h264_tx_rules.h"
 
 #define NT 256
 
 __device__ __forceinline__ int16_t lo16(uint32_t v) { return (int16_t)(v & 0xFFFF); }
 __device__ __forceinline__ int16_t hi16(uint32_t v) { return (int16_t)(v >> 16); }
-
-/* one 8-point pass of the 8x8 transform; in/out as 32-bit wrap-around values */
-__device__ __forceinline__ void idct8_1d(const int in[8], uint32_t out[8])
-{
-    const uint32_t a0 = (uint32_t)in[0] + (uint32_t)in[4];
-    const uint32_t a2 = (uint32_t)in[0] - (uint32_t)in[4];
-    const uint32_t a4 = (uint32_t)(in[2] >> 1) - (uint32_t)in[6];
-    const uint32_t a6 = (uint32_t)(in[6] >> 1) + (uint32_t)in[2];
-    const uint32_t b0 = a0 + a6, b2 = a2 + a4, b4 = a2 - a4, b6 = a0 - a6;
-    const int a1 = (int)(-(uint32_t)in[3] + (uint32_t)in[5] - (uint32_t)in[7] - (uint32_t)(in[7] >> 1));
-    const int a3 = (int)((uint32_t)in[1] + (uint32_t)in[7] - (uint32_t)in[3] - (uint32_t)(in[3] >> 1));
-    const int a5 = (int)(-(uint32_t)in[1] + (uint32_t)in[7] + (uint32_t)in[5] + (uint32_t)(in[5] >> 1));
-    const int a7 = (int)((uint32_t)in[3] + (uint32_t)in[5] + (uint32_t)in[1] + (uint32_t)(in[1] >> 1));
-    const uint32_t b1 = (uint32_t)(a7 >> 2) + (uint32_t)a1;
-    const uint32_t b3 = (uint32_t)a3 + (uint32_t)(a5 >> 2);
-    const uint32_t b5 = (uint32_t)(a3 >> 2) - (uint32_t)a5;
-    const uint32_t b7 = (uint32_t)a7 - (uint32_t)(a1 >> 2);
-    out[0] = b0 + b7; out[7] = b0 - b7;
-    out[1] = b2 + b5; out[6] = b2 - b5;
-    out[2] = b4 + b3; out[5] = b4 - b3;
-    out[3] = b6 + b1; out[4] = b6 - b1;
-}
 
 /* full 8x8 on coefficients held as 8 rows of 4 packed dwords (row k = block[8k..8k+7]) */
 __device__ __forceinline__ void idct8_add_regs(const uint32_t rows[8][4], uint8_t *dst, ptrdiff_t stride, bool vec)
@@ -63,7 +42,7 @@ __device__ __forceinline__ void idct8_add_regs(const uint32_t rows[8][4], uint8_
         }
         if (i == 0)
             in[0] = (int16_t)(in[0] + 32); /* block[0] += 32 in int16 */
-        idct8_1d(in, o);
+        h264tx_idct8_1d<1>(in, o);
 #pragma unroll
         for (int k = 0; k < 8; k++)
             t[k][i] = (int16_t)o[k];
@@ -90,7 +69,7 @@ __device__ __forceinline__ void idct8_add_regs(const uint32_t rows[8][4], uint8_
 #pragma unroll
         for (int k = 0; k < 8; k++)
             in[k] = t[i][k];
-        idct8_1d(in, o);
+        h264tx_idct8_1d<1>(in, o);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const int px = (drow[k][i >> 2] >> (8 * (i & 3))) & 0xFF;
@@ -154,22 +133,11 @@ __global__ __launch_bounds__(NT) void k_h264_idct8_add(uint8_t *dst_base, ptrdif
 __device__ __forceinline__ void idct4_add_regs(const uint4 &c0, const uint4 &c1, uint8_t *dst, ptrdiff_t stride, bool vec)
 {
     const uint32_t w[8] = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w };
-    int16_t b[16];
+    int v[16];
 #pragma unroll
     for (int i = 0; i < 16; i++)
-        b[i] = (i & 1) ? hi16(w[i >> 1]) : lo16(w[i >> 1]);
-    b[0] = (int16_t)(b[0] + 32);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t z0 = (uint32_t)b[i] + (uint32_t)b[i + 8];
-        const uint32_t z1 = (uint32_t)b[i] - (uint32_t)b[i + 8];
-        const uint32_t z2 = (uint32_t)(b[i + 4] >> 1) - (uint32_t)b[i + 12];
-        const uint32_t z3 = (uint32_t)b[i + 4] + (uint32_t)(b[i + 12] >> 1);
-        b[i]      = (int16_t)(z0 + z3);
-        b[i + 4]  = (int16_t)(z1 + z2);
-        b[i + 8]  = (int16_t)(z1 - z2);
-        b[i + 12] = (int16_t)(z0 - z3);
-    }
+        v[i] = (i & 1) ? hi16(w[i >> 1]) : lo16(w[i >> 1]);
+    h264tx_idct4<int16_t>(v);   /* v[4 * i + k]: row k, column i */
     uint32_t drow[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -179,17 +147,10 @@ __device__ __forceinline__ void idct4_add_regs(const uint4 &c0, const uint4 &c1,
     }
     int res[4][4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int16_t *r = b + 4 * i;
-        const uint32_t z0 = (uint32_t)r[0] + (uint32_t)r[2];
-        const uint32_t z1 = (uint32_t)r[0] - (uint32_t)r[2];
-        const uint32_t z2 = (uint32_t)(r[1] >> 1) - (uint32_t)r[3];
-        const uint32_t z3 = (uint32_t)r[1] + (uint32_t)(r[3] >> 1);
-        const uint32_t o[4] = { z0 + z3, z1 + z2, z1 - z2, z0 - z3 };
+    for (int i = 0; i < 4; i++)
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            res[k][i] = clip_u8((int)((drow[k] >> (8 * i)) & 0xFF) + ((int)o[k] >> 6));
-    }
+            res[k][i] = clip_u8((int)((drow[k] >> (8 * i)) & 0xFF) + v[4 * i + k]);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         uint8_t *p = dst + k * stride;
@@ -234,7 +195,7 @@ __global__ __launch_bounds__(NT) void k_h264_idct_dc_add(uint8_t *dst_base, ptrd
     if (i >= n)
         return;
     int16_t *b = blocks + i * (N * N);
-    const int dc = (b[0] + 32) >> 6;
+    const int dc = h264tx_dc(b[0]);
     b[0] = 0;
     dc_add_regs<N>(dc, dst_base + dst_offset[i], stride);
 }
@@ -323,7 +284,7 @@ __global__ __launch_bounds__(NT) void k_h264_idct_multi(FFHipIdctMulti M)
     } else {
         const int N = S.kind == FFHIP_H264_IDCT8_DC ? 8 : 4;
         int16_t *b = S.coef + i * (N * N);
-        const int dc = (b[0] + 32) >> 6;
+        const int dc = h264tx_dc(b[0]);
         b[0] = 0;
         if (N == 8)
             dc_add_regs<8>(dc, dst, stride);
@@ -387,7 +348,7 @@ __global__ __launch_bounds__(NT) void k_h264_idct_add16(int which, uint8_t *dst_
         g[1] = make_uint4(0, 0, 0, 0);
         idct4_add_regs(c0, c1, dst, stride, dst_vec && !((uintptr_t)dst & 3));
     } else if (dc) {
-        const int v = (b[0] + 32) >> 6;
+        const int v = h264tx_dc(b[0]);
         b[0] = 0;
         dc_add_regs<4>(v, dst, stride);
     }
@@ -408,7 +369,7 @@ __global__ __launch_bounds__(NT) void k_h264_idct8_add4(uint8_t *dst_base, ptrdi
     int16_t *b = blocks + ((size_t)mb * 16 + i) * 16;
     uint8_t *dst = dst_base + mb_offset[mb] + blockoffset[i];
     if (nnz == 1 && b[0]) {
-        const int v = (b[0] + 32) >> 6;
+        const int v = h264tx_dc(b[0]);
         b[0] = 0;
         dc_add_regs<8>(v, dst, stride);
         return;
@@ -462,7 +423,7 @@ __global__ __launch_bounds__(NT) void k_h264_idct_add8(uint8_t *cb_base, uint8_t
         g[1] = make_uint4(0, 0, 0, 0);
         idct4_add_regs(c0, c1, dst, stride, dst_vec && !((uintptr_t)dst & 3));
     } else if (b[0]) {
-        const int v = (b[0] + 32) >> 6;
+        const int v = h264tx_dc(b[0]);
         b[0] = 0;
         dc_add_regs<4>(v, dst, stride);
     }
@@ -489,22 +450,18 @@ __global__ __launch_bounds__(NT) void k_h264_luma_dc_dequant(int16_t *output, si
         return;
     const int16_t *in = input + m * in_pitch;
     int16_t *out = output + m * out_pitch;
-    const uint32_t q = (uint32_t)qmul[m];
-    int t[16];
+    int dc[16];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int z0 = in[4 * i] + in[4 * i + 1], z1 = in[4 * i] - in[4 * i + 1], z2 = in[4 * i + 2] - in[4 * i + 3], z3 = in[4 * i + 2] + in[4 * i + 3];
-        t[4 * i] = z0 + z3; t[4 * i + 1] = z0 - z3; t[4 * i + 2] = z1 - z2; t[4 * i + 3] = z1 + z2;
-    }
+    for (int i = 0; i < 16; i++)
+        dc[i] = in[i];
+    h264tx_luma_dc<int16_t>(dc, qmul[m]);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int o = (i & 1) * 32 + (i >> 1) * 128;  /* x_offset[] = { 0, 2*16, 8*16, 10*16 } */
-        const uint32_t z0 = (uint32_t)t[i] + (uint32_t)t[8 + i], z1 = (uint32_t)t[i] - (uint32_t)t[8 + i];
-        const uint32_t z2 = (uint32_t)t[4 + i] - (uint32_t)t[12 + i], z3 = (uint32_t)t[4 + i] + (uint32_t)t[12 + i];
-        out[o]      = (int16_t)((int)((z0 + z3) * q + 128) >> 8);
-        out[16 + o] = (int16_t)((int)((z1 + z2) * q + 128) >> 8);
-        out[64 + o] = (int16_t)((int)((z1 - z2) * q + 128) >> 8);
-        out[80 + o] = (int16_t)((int)((z0 - z3) * q + 128) >> 8);
+        out[o]      = (int16_t)dc[4 * i];
+        out[16 + o] = (int16_t)dc[4 * i + 1];
+        out[64 + o] = (int16_t)dc[4 * i + 2];
+        out[80 + o] = (int16_t)dc[4 * i + 3];
     }
 }
 
@@ -515,14 +472,12 @@ __global__ __launch_bounds__(NT) void k_h264_chroma_dc_dequant(int16_t *blocks, 
     if (m >= n)
         return;
     int16_t *b = blocks + block_offset[m];
-    const uint32_t q = (uint32_t)qmul[m];
-    uint32_t a = (uint32_t)(int)b[0], bb = (uint32_t)(int)b[16], c = (uint32_t)(int)b[32], d = (uint32_t)(int)b[48];
-    const uint32_t e = a - bb;
-    a = a + bb; bb = c - d; c = c + d;
-    b[0]  = (int16_t)((int)((a + c) * q) >> 7);
-    b[16] = (int16_t)((int)((e + bb) * q) >> 7);
-    b[32] = (int16_t)((int)((a - c) * q) >> 7);
-    b[48] = (int16_t)((int)((e - bb) * q) >> 7);
+    int dc[4] = { b[0], b[16], b[32], b[48] };
+    h264tx_chroma_dc<int16_t>(dc, qmul[m]);
+    b[0]  = (int16_t)dc[0];
+    b[16] = (int16_t)dc[1];
+    b[32] = (int16_t)dc[2];
+    b[48] = (int16_t)dc[3];
 }
 
 int ffhip_launch_h264_luma_dc_dequant(int16_t *output, size_t out_pitch, const int16_t *input, size_t in_pitch, const int32_t *qmul, int n,

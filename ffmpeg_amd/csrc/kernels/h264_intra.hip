@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void k_h264_intra_frame(FFHipIntraPics S, p
     const int32_t *const row_start = S.pic[blockIdx.y].row_start;
     const int16_t *const coefs = S.pic[blockIdx.y].coefs;
     typedef typename FFHipQuad<PIX>::T Q;
-    typedef typename ImbCoef<PIX>::T CF;
+    typedef typename H264Coef<PIX>::T CF;
     constexpr int PS = (int)sizeof(PIX), NDW = PS == 1 ? 3 : 7, IMB_RUN_MAX = NDW * 128 /* int16 */, WMAX = 4;
     __shared__ __align__(16) ImbTileT<PIX> Ts[WMAX];
     /* the macroblock being reconstructed and the next one: its record and coefficient run are fetched while this one is

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "ffhip.h"
+#include "h264_tx_rules.h"
 
 #if defined(__HIPCC__)
 #define IMB_FN __host__ __device__ __forceinline__
@@ -150,8 +151,9 @@ IMB_FN int hp_filter8(const int *w, int j, unsigned need, bool tl, bool tr)
 }
 
 /* ---- the tile ---- */
-template <typename PIX> struct ImbCoef { typedef int16_t T; };
-template <> struct ImbCoef<uint16_t> { typedef int32_t T; };
+/* the tile's coefficient type under the name the host emulation takes it by (oracle/emul_h264_intra.cpp, emul_h264_mbaff.cpp: the
+ * tests' reference side, which stays as it is); the library's own code says H264Coef */
+template <typename PIX> using ImbCoef = H264Coef<PIX>;
 
 template <typename PIX>
 struct ImbTileT {
@@ -160,7 +162,7 @@ struct ImbTileT {
     int t8[4][64];         /* first pass of the four 8x8 inverse transforms */
     int dcq[16];           /* luma_dc_dequant_idct's results by block */
     int edge[32];          /* pred8x8l: the block's low-pass filtered edge line (25 entries) */
-    typename ImbCoef<PIX>::T zero[16]; /* sixteen zero coefficients: the block of a lane whose block was not stored (set once per tile) */
+    typename H264Coef<PIX>::T zero[16]; /* sixteen zero coefficients: the block of a lane whose block was not stored (set once per tile) */
 };
 typedef ImbTileT<uint8_t> ImbTile;
 
@@ -238,15 +240,8 @@ IMB_FN int imb_run_len(int type, uint32_t blocks, int psz = 1, int flags = 0)
     return psz == 1 ? n : 2 * (n + ((flags & FFHIP_H264_INTRA_LUMA_DC) ? 16 : 0));
 }
 
-/* output k of the 4-point butterfly of ff_h264_idct_add (h264idct_template.c:39-64): modulo 2^32, arithmetic shifts */
-IMB_FN int imb_bfly4(int k, int s0, int s1, int s2, int s3)
-{
-    const uint32_t e0 = (uint32_t)s0 + (uint32_t)s2, e1 = (uint32_t)s0 - (uint32_t)s2;
-    const uint32_t o0 = (uint32_t)(s1 >> 1) - (uint32_t)s3, o1 = (uint32_t)s1 + (uint32_t)(s3 >> 1);
-    return (int)(k == 0 ? e0 + o1 : k == 1 ? e1 + o0 : k == 2 ? e1 - o0 : e0 - o1);
-}
-
-/* what ff_h264_idct_add adds to sample (x, y) of its block; b[0] is passed separately (Intra16x16 puts the dequantised DC there) */
+/* what ff_h264_idct_add adds to sample (x, y) of its block, the sample-per-lane form of h264tx_idct4 (h264_tx_rules.h) over its butterfly;
+ * b[0] is passed separately (Intra16x16 puts the dequantised DC there) */
 template <typename CF>
 IMB_FN int imb_idct4_at(const CF *b, int b0, int x, int y)
 {
@@ -254,9 +249,9 @@ IMB_FN int imb_idct4_at(const CF *b, int b0, int x, int y)
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int s0 = j == 0 ? (CF)(b0 + 32) : (b ? b[j] : 0);
-        r[j] = (CF)imb_bfly4(x, s0, b ? b[j + 4] : 0, b ? b[j + 8] : 0, b ? b[j + 12] : 0); /* the first pass stores dctcoef */
+        r[j] = (CF)h264tx_bfly4(x, s0, b ? b[j + 4] : 0, b ? b[j + 8] : 0, b ? b[j + 12] : 0); /* the first pass stores dctcoef */
     }
-    return imb_bfly4(y, r[0], r[1], r[2], r[3]) >> 6;
+    return h264tx_bfly4(y, r[0], r[1], r[2], r[3]) >> 6;
 }
 
 /* the same for the four samples (x, 0..3) of a column: the four first-pass butterflies serve all of them */
@@ -266,15 +261,15 @@ IMB_FN void imb_idct4_col(const CF *b, int b0, int x, int out[4])
     int r[4];
 #pragma unroll
     for (int j = 0; j < 4; j++)
-        r[j] = (CF)imb_bfly4(x, j == 0 ? (CF)(b0 + 32) : (b ? b[j] : 0), b ? b[j + 4] : 0, b ? b[j + 8] : 0, b ? b[j + 12] : 0);
+        r[j] = (CF)h264tx_bfly4(x, j == 0 ? (CF)(b0 + 32) : (b ? b[j] : 0), b ? b[j + 4] : 0, b ? b[j + 8] : 0, b ? b[j + 12] : 0);
 #pragma unroll
     for (int y = 0; y < 4; y++)
-        out[y] = imb_bfly4(y, r[0], r[1], r[2], r[3]) >> 6;
+        out[y] = h264tx_bfly4(y, r[0], r[1], r[2], r[3]) >> 6;
 }
 
 /* The residual of column x of a 4x4 block for EVERY lane in one straight line: b = the block's coefficients, or the tile's zero block
  * when it has none / only its DC counts — ff_h264_idct_add on (dc, 0, 0, ...) adds (dc + 32) >> 6 everywhere, which is
- * ff_h264_idct_dc_add (h264idct_template.c:145-160), and on all zeros adds nothing.  The one difference between the two functions is
+ * ff_h264_idct_dc_add (h264tx_dc), and on all zeros adds nothing.  The one difference between the two functions is
  * kept: idct_add stores block[0] + 32 back as dctcoef before it is read, idct_dc_add computes in int. */
 /* bypass (FFHIP_H264_INTRA_BYPASS): the block holds residual samples, row-major — add_pixels4_clear (h264addpx_template.c:30-48) */
 template <typename CF>
@@ -287,36 +282,14 @@ IMB_FN void imb_resid4_col(const CF *b, int dc, bool dconly, int x, int out[4], 
         return;
     }
     int r[4];
-    r[0] = imb_bfly4(x, dconly ? dc + 32 : (int)(CF)(dc + 32), b[4], b[8], b[12]);
+    r[0] = h264tx_bfly4(x, dconly ? dc + 32 : (int)(CF)(dc + 32), b[4], b[8], b[12]);
     r[0] = dconly ? r[0] : (int)(CF)r[0];
 #pragma unroll
     for (int j = 1; j < 4; j++)
-        r[j] = (CF)imb_bfly4(x, b[j], b[j + 4], b[j + 8], b[j + 12]);
+        r[j] = (CF)h264tx_bfly4(x, b[j], b[j + 4], b[j + 8], b[j + 12]);
 #pragma unroll
     for (int y = 0; y < 4; y++)
-        out[y] = imb_bfly4(y, r[0], r[1], r[2], r[3]) >> 6;
-}
-
-/* one 8-point pass of ff_h264_idct8_add (h264idct_template.c:69-143) */
-IMB_FN void imb_idct8_1d(const int in[8], uint32_t out[8])
-{
-    const uint32_t a0 = (uint32_t)in[0] + (uint32_t)in[4];
-    const uint32_t a2 = (uint32_t)in[0] - (uint32_t)in[4];
-    const uint32_t a4 = (uint32_t)(in[2] >> 1) - (uint32_t)in[6];
-    const uint32_t a6 = (uint32_t)(in[6] >> 1) + (uint32_t)in[2];
-    const uint32_t b0 = a0 + a6, b2 = a2 + a4, b4 = a2 - a4, b6 = a0 - a6;
-    const int a1 = (int)(-(uint32_t)in[3] + (uint32_t)in[5] - (uint32_t)in[7] - (uint32_t)(in[7] >> 1));
-    const int a3 = (int)((uint32_t)in[1] + (uint32_t)in[7] - (uint32_t)in[3] - (uint32_t)(in[3] >> 1));
-    const int a5 = (int)(-(uint32_t)in[1] + (uint32_t)in[7] + (uint32_t)in[5] + (uint32_t)(in[5] >> 1));
-    const int a7 = (int)((uint32_t)in[3] + (uint32_t)in[5] + (uint32_t)in[1] + (uint32_t)(in[1] >> 1));
-    const uint32_t b1 = (uint32_t)(a7 >> 2) + (uint32_t)a1;
-    const uint32_t b3 = (uint32_t)a3 + (uint32_t)(a5 >> 2);
-    const uint32_t b5 = (uint32_t)(a3 >> 2) - (uint32_t)a5;
-    const uint32_t b7 = (uint32_t)a7 - (uint32_t)(a1 >> 2);
-    out[0] = b0 + b7; out[7] = b0 - b7;
-    out[1] = b2 + b5; out[6] = b2 - b5;
-    out[2] = b4 + b3; out[5] = b4 - b3;
-    out[3] = b6 + b1; out[4] = b6 - b1;
+        out[y] = h264tx_bfly4(y, r[0], r[1], r[2], r[3]) >> 6;
 }
 
 /* pred8x8 (N = 8, with the one-sided "mad cow" DC variants) / pred16x16 (N = 16) sample (x, y); t / l index the tile's row above
@@ -622,11 +595,11 @@ IMB_FN int imb_pred_px(int mode, const ImbPred &P, int j, int x, int y, int maxv
  * wavefront of its own beside the luma one when it has the room: a macroblock step of the luma chain is a quarter shorter without it).
  */
 template <typename PIX, class X>
-IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, const typename ImbCoef<PIX>::T *coefs /* the macroblock's run */,
+IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, const typename H264Coef<PIX>::T *coefs /* the macroblock's run */,
                             const uint32_t *p4tab /* imb_tab(0 .. IMB_TABS - 1) */, int maxv = 255 /* (1 << bit_depth) - 1 */,
                             int parts = 3 /* 1: the luma samples, 2: the two chroma planes; the same in every lane */)
 {
-    typedef typename ImbCoef<PIX>::T CF;
+    typedef typename H264Coef<PIX>::T CF;
     const int mid = (maxv + 1) >> 1;
     const ImbHead H = { IMB_UNIFORM((int)R.type), IMB_UNIFORM((int)R.cbp), IMB_UNIFORM((int)R.flags), (uint32_t)IMB_UNIFORM((int)R.blocks) };
     const bool byp = (H.flags & FFHIP_H264_INTRA_BYPASS) != 0; /* the transform bypass: the run holds residual samples (the packer made them so) */
@@ -665,7 +638,8 @@ IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, c
                 const uint32_t cb = H.blocks >> 16;
                 const CF *c0 = coefs + (sizeof(CF) == 4 && (H.flags & FFHIP_H264_INTRA_LUMA_DC) ? 16 : 0) +
                                imb_popc(H.blocks & 0xFFFFu) * (H.type == FFHIP_H264_INTRA_8x8 ? 64 : 16);
-                /* chroma_dc_dequant_idct (h264idct_template.c:323-345) on the four DCs of the plane; taken when the plane has a DC block */
+                /* chroma_dc_dequant_idct on the four DCs of the plane, taken when the plane has a DC block: the per-lane form of
+                 * h264tx_chroma_dc, lane k keeps output k */
                 int d4[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
@@ -696,7 +670,7 @@ IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, c
             return;
         } else if (H.type == FFHIP_H264_INTRA_8x8) {
             /* first pass of the four 8x8 inverse transforms (they depend on the coefficients alone): lane 32 + 8 q + j = transform j
-             * of block 4 q, working on block[j + 8 k], results stored as int16 */
+             * of block 4 q, working on block[j + 8 k], results stored as dctcoef: the per-lane form of h264tx_idct8_first */
             const int q = (lane - 32) >> 3, j = lane & 7, nnz = R.nnz[4 * q];
             const CF *b = nnz ? imb_block(H, coefs, 4 * q) : nullptr;
             if (b && byp) {
@@ -712,13 +686,13 @@ IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, c
                     in[k] = b[j + 8 * k];
                 if (j == 0)
                     in[0] = (CF)(in[0] + 32);
-                imb_idct8_1d(in, out);
+                h264tx_idct8_1d<1>(in, out);
 #pragma unroll
                 for (int k = 0; k < 8; k++)
                     T.t8[q][j + 8 * k] = (CF)out[k];
             }
         } else if (lane < 48 && H.type == FFHIP_H264_INTRA_16x16 && (H.flags & FFHIP_H264_INTRA_LUMA_DC)) {
-            /* luma_dc_dequant_idct (h264idct_template.c:259-293): lane 32 + o computes output o of the 4x4 Hadamard */
+            /* luma_dc_dequant_idct: lane 32 + o computes output o of the 4x4 Hadamard, the per-lane form of h264tx_luma_dc */
             const int o = lane - 32, i = o & 3, w = o >> 2; /* second-pass column i, output w of { z0+z3, z1+z2, z1-z2, z0-z3 } */
             int t[4];
 #pragma unroll
@@ -845,7 +819,7 @@ IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, c
 #pragma unroll
         for (int k = 0; k < 8; k++)
             in[k] = T.t8[q][8 * xx + k];
-        imb_idct8_1d(in, out);
+        h264tx_idct8_1d<1>(in, out);
 #pragma unroll
         for (int k = 0; k < 8; k++)
             T.t8[q][8 * xx + k] = (int)out[k] >> 6;
@@ -891,7 +865,7 @@ IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, c
 /* ================================================================================================================================
  * 4:2:2 (round 4): the two 8 x 16 chroma planes of an intra macroblock — hl_decode_mb() at chroma_format_idc 2
  * (libavcodec/h264_mb_template.c:151-262): pred8x8[chroma_pred_mode] is a pred8x16 function there (h264pred.c:480-512,
- * h264pred_template.c:567-817), the residual is chroma422_dc_dequant_idct per plane (h264idct_template.c:295-321, qmul =
+ * h264pred_template.c:567-817), the residual is chroma422_dc_dequant_idct per plane (h264tx_chroma422_dc, qmul =
  * dequant4_coeff[1 + p][chroma_qp[p] + 3][0]: h264_mb_template.c:230-245) + idct_add8_422 (:230-252: eight blocks per plane, the cache
  * rows running on downwards).  The luma plane of such a macroblock is a luma-only record of the wavefront above; the chroma planes
  * are a record and a wavefront of their own (k_h264_intra_c422: chroma prediction reads the left, upper-left and upper neighbours only).
@@ -902,7 +876,7 @@ IMB_FN void imb_reconstruct(X &x, ImbTileT<PIX> &T, const FFHipH264IntraMB &R, c
 template <typename PIX>
 struct ImbTileC422 {
     PIX c[2][17 * 16];    /* sample (r, c), r = -1..15, c = -4..11, at [(r + 1) * 16 + c + 4] (imb_ci) */
-    typename ImbCoef<PIX>::T zero[16];
+    typename H264Coef<PIX>::T zero[16];
 };
 
 /* pred8x16 sample column (xc, y0 .. y0 + 3) of block k: modes as H264PredContext.pred8x8[] at chroma_format_idc 2 */
@@ -962,9 +936,9 @@ IMB_FN void imb_pred8x16_col(int mode, int k, int xc, int y0, Top TOP, Left LEFT
 }
 
 template <typename PIX, class X>
-IMB_FN void imb_c422_reconstruct(X &x, ImbTileC422<PIX> &T, const FFHipH264IntraC422 &R, const typename ImbCoef<PIX>::T *coefs, int maxv)
+IMB_FN void imb_c422_reconstruct(X &x, ImbTileC422<PIX> &T, const FFHipH264IntraC422 &R, const typename H264Coef<PIX>::T *coefs, int maxv)
 {
-    typedef typename ImbCoef<PIX>::T CF;
+    typedef typename H264Coef<PIX>::T CF;
     if (R.type == FFHIP_H264_INTRA_PCM) {
         /* 8 x 16 samples of Cb, then of Cr, as they stand in the bitstream (h264_mb_template.c:98-150 with block_h = 16) */
         const PIX *pcm = reinterpret_cast<const PIX *>(coefs);
@@ -993,7 +967,8 @@ IMB_FN void imb_c422_reconstruct(X &x, ImbTileC422<PIX> &T, const FFHipH264Intra
                 d[q] = blk(8 * p + q)[0];
             const int own = d[k];
             if ((R.flags >> p) & 1) {
-                /* chroma422_dc_dequant_idct: block q = row q >> 1, column q & 1 of the 4 x 2 DC array */
+                /* chroma422_dc_dequant_idct: block q = row q >> 1, column q & 1 of the 4 x 2 DC array; the per-lane form of
+                 * h264tx_chroma422_dc, lane k keeps output k */
                 uint32_t t[8];
                 for (int i = 0; i < 4; i++) {
                     t[2 * i] = (uint32_t)d[2 * i] + (uint32_t)d[2 * i + 1];

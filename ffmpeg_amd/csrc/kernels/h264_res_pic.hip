@@ -58,14 +58,14 @@ __device__ __forceinline__ void load_coefs(const int32_t *c, int (&v)[N])
 __device__ __forceinline__ void add_row4(uint8_t *p, uint8_t, int d0, int d1, int d2, int d3, int maxv)
 {
     const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
-    *reinterpret_cast<uint32_t *>(p) = pack4(h264res_clip((int)(w & 0xFF) + d0, maxv), h264res_clip((int)((w >> 8) & 0xFF) + d1, maxv),
-                                             h264res_clip((int)((w >> 16) & 0xFF) + d2, maxv), h264res_clip((int)(w >> 24) + d3, maxv));
+    *reinterpret_cast<uint32_t *>(p) = pack4(h264tx_clip((int)(w & 0xFF) + d0, maxv), h264tx_clip((int)((w >> 8) & 0xFF) + d1, maxv),
+                                             h264tx_clip((int)((w >> 16) & 0xFF) + d2, maxv), h264tx_clip((int)(w >> 24) + d3, maxv));
 }
 __device__ __forceinline__ void add_row4(uint8_t *p, uint16_t, int d0, int d1, int d2, int d3, int maxv)
 {
     const uint2 w = *reinterpret_cast<const uint2 *>(p);
-    const uint32_t a = (uint32_t)h264res_clip((int)(w.x & 0xFFFF) + d0, maxv) | (uint32_t)h264res_clip((int)(w.x >> 16) + d1, maxv) << 16;
-    const uint32_t b = (uint32_t)h264res_clip((int)(w.y & 0xFFFF) + d2, maxv) | (uint32_t)h264res_clip((int)(w.y >> 16) + d3, maxv) << 16;
+    const uint32_t a = (uint32_t)h264tx_clip((int)(w.x & 0xFFFF) + d0, maxv) | (uint32_t)h264tx_clip((int)(w.x >> 16) + d1, maxv) << 16;
+    const uint32_t b = (uint32_t)h264tx_clip((int)(w.y & 0xFFFF) + d2, maxv) | (uint32_t)h264tx_clip((int)(w.y >> 16) + d3, maxv) << 16;
     *reinterpret_cast<uint2 *>(p) = make_uint2(a, b);
 }
 
@@ -115,8 +115,8 @@ __device__ __forceinline__ void idct8_add_quad(const CF *c, uint8_t *dst, ptrdif
     ac |= quad_xor1(ac);
     ac |= quad_xor2(ac);
     const int first = quad_lane<0>(a[0]);
-    if (!ac) {  /* nothing but the DC (h264res_flat over the quad): the *_dc_add form; uniform over the quad */
-        const int dc = h264res_dc(first);
+    if (!ac) {  /* nothing but the DC (h264tx_flat over the quad): the *_dc_add form; uniform over the quad */
+        const int dc = h264tx_dc(first);
 #pragma unroll
         for (int i = 0; i < 16; i++)
             d[i] = dc;
@@ -127,7 +127,7 @@ __device__ __forceinline__ void idct8_add_quad(const CF *c, uint8_t *dst, ptrdif
 #pragma unroll
         for (int n = 0; n < 2; n++) {
             uint32_t o[8];
-            h264res_idct8_1d<1>(b + 8 * n, o);
+            h264tx_idct8_1d<1>(b + 8 * n, o);
 #pragma unroll
             for (int k = 0; k < 8; k++)
                 b[8 * n + k] = (CF)o[k];
@@ -136,7 +136,7 @@ __device__ __forceinline__ void idct8_add_quad(const CF *c, uint8_t *dst, ptrdif
 #pragma unroll
         for (int n = 0; n < 2; n++) {
             uint32_t o[8];
-            h264res_idct8_1d<1>(a + 8 * n, o);
+            h264tx_idct8_1d<1>(a + 8 * n, o);
 #pragma unroll
             for (int k = 0; k < 8; k++)
                 a[8 * n + k] = (int)o[k] >> 6;  /* row k, column 2q + n */
@@ -200,16 +200,16 @@ __global__ __launch_bounds__(32 * H4R_MBS) void k_h264_res_pic(const FFHipH264Re
     }
     if (dc_on) {    /* uniform over the plane's four lanes, which are all here */
         int dc[4] = { quad_lane<0>(v[0]), quad_lane<1>(v[0]), quad_lane<2>(v[0]), quad_lane<3>(v[0]) };
-        h264res_chroma_dc<CF>(dc, pl == 1 ? R.qmul[0] : R.qmul[1]);
+        h264tx_chroma_dc<CF>(dc, pl == 1 ? R.qmul[0] : R.qmul[1]);
         v[0] = j == 0 ? dc[0] : j == 1 ? dc[1] : j == 2 ? dc[2] : dc[3];
     }
-    if (luma ? h264res_flat(v) : !ac_on) {  /* rule 9: the *_dc_add form */
-        const int d = h264res_dc(v[0]);
+    if (luma ? h264tx_flat(v) : !ac_on) {  /* rule 9: the *_dc_add form */
+        const int d = h264tx_dc(v[0]);
 #pragma unroll
         for (int i = 0; i < 16; i++)
             v[i] = d;
     } else {
-        h264res_idct4<CF>(v);
+        h264tx_idct4<CF>(v);
     }
 #pragma unroll
     for (int k = 0; k < 4; k++)

@@ -88,7 +88,7 @@ void add_block(uint8_t *dst, ptrdiff_t stride, const int (&v)[N * N], int maxv)
         for (int i = 0; i < N; i++) {
             PIX px;
             memcpy(&px, dst + k * stride + i * sizeof(PIX), sizeof(px));
-            px = (PIX)h264res_clip((int)px + v[N * i + k], maxv);
+            px = (PIX)h264tx_clip((int)px + v[N * i + k], maxv);
             memcpy(dst + k * stride + i * sizeof(PIX), &px, sizeof(px));
         }
 }
@@ -130,7 +130,7 @@ void residual_mb(const FFHipH264ResPic &P, int mb_w, ptrdiff_t m, bool has_c, in
         if (dc_on) {
             for (int j = 0; j < 4; j++)
                 dc[j] = cp[16 * j];
-            h264res_chroma_dc<CF>(dc, R.qmul[pl]);
+            h264tx_chroma_dc<CF>(dc, R.qmul[pl]);
         }
         for (int j = 0; j < 4; j++) {
             const bool ac_on = (plan.chroma >> (4 * pl + j)) & 1;
@@ -141,10 +141,10 @@ void residual_mb(const FFHipH264ResPic &P, int mb_w, ptrdiff_t m, bool has_c, in
                 load_coefs(cp + 16 * j, v);
                 if (dc_on)
                     v[0] = dc[j];
-                h264res_idct4<CF>(v);
+                h264tx_idct4<CF>(v);
             } else {
                 for (int i = 0; i < 16; i++)
-                    v[i] = h264res_dc(dc[j]);
+                    v[i] = h264tx_dc(dc[j]);
             }
             add_block<PIX, 4>(P.dst[1 + pl] + (ptrdiff_t)(my * 8 + 4 * (j >> 1)) * P.dst_stride[1 + pl] + (size_t)(mx * 8 + 4 * (j & 1)) * sizeof(PIX),
                               P.dst_stride[1 + pl], v, maxv);

@@ -93,6 +93,20 @@ def test_h264_golden():
         assert np.array_equal(o[6:22, 8:24], d["qpel_out"][i]), (avg, size_idx, mc)
 
 
+@pytest.mark.parametrize("hbd", [False, True], ids=["8bit", "bd8"])
+def test_h264_dc_wrap_cell(hbd):
+    """where idct_add and idct_dc_add differ at 8 bits (tests/h264_dc_wrap.py), on the oracle alone: every list kind and dispatcher, the
+    8-bit functions and the any-depth restatement at depth 8.  tests/test_gpu_h264.py compares the device faces on the same cases."""
+    import h264_dc_wrap as W
+    O = ffi.oracle()
+    done = []
+    for c in W.cases(hbd):
+        planes, coefs = W.want(O, c, hbd)
+        assert not coefs.any(), (c["face"], c["arg"])
+        done.append((c, planes))
+    W.assert_cell(done)
+
+
 def test_h264_misc_golden():
     """idct_add8, luma / chroma dc_dequant_idct, add_pixels{4,8}_clear: oracle == the reference's committed outputs"""
     from test_oracle_vs_ref import h264_misc_apply

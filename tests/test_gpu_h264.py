@@ -92,6 +92,42 @@ def test_idct_add_mb_batch(which):
     assert np.array_equal(d_plane.cpu().numpy(), want) and np.array_equal(d_b.cpu().numpy(), wb)
 
 
+@pytest.mark.parametrize("hbd", [False, True], ids=["8bit", "hbd8"])
+def test_idct_dc_wrap_cell(hbd):
+    """the one place where the reference's transform and *_dc_add differ at 8 bits, a DC of 32736 .. 32767 (tests/h264_dc_wrap.py): every
+    list kind and every dispatcher down both forms, the 8-bit faces and the depth-8 instantiation of the `_hbd` faces == the oracle,
+    samples and cleared coefficients bit for bit.  The oracle's outputs are checked to hold the cell before the device is looked at."""
+    import h264_dc_wrap as W
+    from ffmpeg_amd import h264, _lib
+    torch = _torch()
+    O, L = ffi.oracle(), _lib.lib()
+    cs = W.cases(hbd)
+    wants = [W.want(O, c, hbd) for c in cs]
+    W.assert_cell([(c, w[0]) for c, w in zip(cs, wants)])
+    for c, (wp, wc) in zip(cs, wants):
+        dev = lambda a: torch.from_numpy(a).cuda()
+        dp, dc, s = [dev(p) for p in c["planes"]], dev(c["coefs"]), c["stride"]
+        if c["face"] == "list":
+            do = dev(c["offs"])
+            if hbd:
+                assert L.ffhip_h264_idct_add_batch_dev_hbd(8, c["arg"], dp[0].data_ptr(), s, do.data_ptr(), dc.data_ptr(), len(c["offs"]), None) == 0
+            else:
+                h264.idct_add_batch(c["arg"], dp[0], s, do, dc)
+        else:
+            dmo, dbo, dnn = dev(c["mb_off"]), dev(c["bo"]), dev(c["nnzc"])
+            if hbd:
+                assert L.ffhip_h264_idct_mb_batch_dev_hbd(8, c["arg"], dp[0].data_ptr(), dp[-1].data_ptr(), s, dmo.data_ptr(), dbo.data_ptr(),
+                                                          dc.data_ptr(), dnn.data_ptr(), len(c["mb_off"]), None) == 0, L.ffhip_last_error()
+            elif c["face"] == "mb":
+                h264.idct_add_mb_batch(c["arg"], dp[0], s, dmo, dbo, dc, dnn)
+            else:
+                h264.idct_add8_batch(dp[0], dp[1], s, dmo, dbo, dc, dnn)
+        torch.cuda.synchronize()
+        for g, w in zip(dp, wp):
+            assert np.array_equal(g.cpu().numpy(), w), (c["face"], c["arg"])
+        assert np.array_equal(dc.cpu().numpy(), wc), (c["face"], c["arg"])
+
+
 # ---------------------------------------------------------------------------------------------
 # loop filters, frame-order deblocking, luma qpel
 # ---------------------------------------------------------------------------------------------
