@@ -3,9 +3,10 @@
  *
  * Bit-exact restatement of
  *   put/avg_h264_chroma_mc{8,4,2}_8_c          libavcodec/h264chroma_template.c:28-172
- *       A=(8-x)(8-y) B=x(8-y) C=(8-x)y D=xy;  v = (A*s[0] + B*s[1] + C*s[stride] + D*s[stride+1] + 32) >> 6,
+ *       v = (A*s[0] + B*s[1] + C*s[stride] + D*s[stride+1] + 32) >> 6 with the weights of h264mc_chroma_weights(),
  *       avg: (dst + v + 1) >> 1; only samples with a non-zero weight are read (three cases, as the reference)
  *   weight_h264_pixels{16,8,4,2}_8_c, biweight_  libavcodec/h264dsp_template.c:30-100
+ * The weights, the packed average and weight / biweight are h264_mc_rules.h's.
  *
  * GPU design: 16 lanes per block, one lane per row (h <= 16) — these are the reference's per-call operands, one record per call;
  * throughput comes from the batch size.  Chroma MC moves its rows as dwords (below); weight / biweight still byte by byte.
@@ -13,6 +14,7 @@
  */
 #include "common.h"
 #include "h264_kernels.h"
+#include "h264_mc_rules.h"
 
 /* bytes p[0 .. nb-1] (nb <= 9, any alignment) as three dwords in stream order: only the aligned dwords that hold one of those
  * bytes are read (a block at the picture's edge reads nothing the reference does not read, rounded to its dwords) */
@@ -57,7 +59,7 @@ __device__ __forceinline__ void chroma_mc_group(uint8_t *dst, const uint8_t *src
     if (row >= blk.h)
         return;
     const int w = halves ? 4 : 8 >> blk.w_idx, x = blk.x & 7, y = blk.y & 7;
-    const uint32_t A = (8 - x) * (8 - y), B = x * (8 - y), C = (8 - x) * y, D = x * y;
+    const H264McBilin cw = h264mc_chroma_weights(x, y);
     const uint8_t *s = src + blk.src_offset + (ptrdiff_t)row * stride + xo;
     uint8_t *d = dst + blk.dst_offset + (ptrdiff_t)row * stride + xo;
     /* the reference's three cases read only samples with a non-zero weight: the right neighbour if x, the row below if y */
@@ -72,7 +74,7 @@ __device__ __forceinline__ void chroma_mc_group(uint8_t *dst, const uint8_t *src
         if (y)
             cm_row(s + stride, w + (x ? 1 : 0), tw);
     }
-    const uint32_t coef = A | B << 8 | C << 16 | D << 24;
+    const uint32_t coef = (uint32_t)cw.a | (uint32_t)cw.b << 8 | (uint32_t)cw.c << 16 | (uint32_t)cw.d << 24;
     uint32_t out[2] = { 0, 0 };
 #pragma unroll
     for (int k = 0; k < 8; k++) {
@@ -92,7 +94,7 @@ __device__ __forceinline__ void chroma_mc_group(uint8_t *dst, const uint8_t *src
                 uint32_t o = out[q];
                 if (blk.avg) {
                     const uint32_t p = dw[q];
-                    o = (p | o) - (((p ^ o) & 0xFEFEFEFEu) >> 1); /* four (a + b + 1) >> 1 at once (libavcodec/rnd_avg.h) */
+                    o = h264mc_avg4(p, o);
                 }
                 dw[q] = o;
             }
@@ -111,13 +113,19 @@ __global__ __launch_bounds__(256) void k_h264_chroma_mc(uint8_t *dst, const uint
 }
 
 /* the lists of several planes in one launch (the picture layer: Cb and Cr of a stage) */
-__global__ __launch_bounds__(256) void k_h264_chroma_mc_multi(FFHipPlaneMulti M)
+/* the segment of a launch over several lists that this workgroup serves: the last whose range of workgroups starts at or below it */
+__device__ __forceinline__ int plane_multi_seg(const FFHipPlaneMulti &M)
 {
     int si = 0;
     for (int i = 1; i < M.nseg; i++)
         if ((int)blockIdx.x >= M.seg[i].first)
             si = i;
-    const FFHipPlaneSeg &S = M.seg[si];
+    return si;
+}
+
+__global__ __launch_bounds__(256) void k_h264_chroma_mc_multi(FFHipPlaneMulti M)
+{
+    const FFHipPlaneSeg &S = M.seg[plane_multi_seg(M)];
     chroma_mc_group(S.dst, S.src, S.stride, static_cast<const FFHipChromaBlock *>(S.blocks), S.n, (int)blockIdx.x - S.first, M.pic_w, M.pic_h);
 }
 
@@ -167,16 +175,12 @@ __device__ __forceinline__ void weight_group(uint8_t *dst, const uint8_t *src, p
     const int w = 16 >> blk.w_idx, ld = blk.log2_denom;
     uint8_t *d = dst + blk.dst_offset + (ptrdiff_t)row * stride;
     if (!blk.bi) {
-        int off = (int)((unsigned)(int)blk.offset << ld);
-        if (ld)
-            off += 1 << (ld - 1);
         for (int k = 0; k < w; k++)
-            d[k] = (uint8_t)min(max((d[k] * blk.weightd + off) >> ld, 0), 255);
+            d[k] = (uint8_t)h264mc_weight(d[k], 8, ld, blk.weightd, blk.offset);
     } else {
         const uint8_t *s = src + blk.src_offset + (ptrdiff_t)row * stride;
-        const int off = (int)((unsigned)(((int)blk.offset + 1) | 1) << ld);
         for (int k = 0; k < w; k++)
-            d[k] = (uint8_t)min(max((s[k] * blk.weights + d[k] * blk.weightd + off) >> (ld + 1), 0), 255);
+            d[k] = (uint8_t)h264mc_biweight(d[k], s[k], 8, ld, blk.weightd, blk.weights, blk.offset);
     }
 }
 
@@ -188,11 +192,7 @@ __global__ __launch_bounds__(256) void k_h264_weight(uint8_t *dst, const uint8_t
 
 __global__ __launch_bounds__(256) void k_h264_weight_multi(FFHipPlaneMulti M)
 {
-    int si = 0;
-    for (int i = 1; i < M.nseg; i++)
-        if ((int)blockIdx.x >= M.seg[i].first)
-            si = i;
-    const FFHipPlaneSeg &S = M.seg[si];
+    const FFHipPlaneSeg &S = M.seg[plane_multi_seg(M)];
     weight_group(S.dst, S.src, S.stride, static_cast<const FFHipWeightBlock *>(S.blocks), S.n, (int)blockIdx.x - S.first);
 }
 

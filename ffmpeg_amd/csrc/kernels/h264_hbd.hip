@@ -21,6 +21,7 @@
 #include "common.h"
 #include "h264_kernels.h"
 #include "h264_lf_line.h"
+#include "h264_mc_rules.h"
 #include "h264_tx_rules.h"
 
 namespace {
@@ -223,9 +224,7 @@ __global__ __launch_bounds__(256) void k_h264_loop_filter_hbd(uint8_t *base, ptr
     lf_apply<P, true>(pix, xs, cls, D.alpha, D.beta, D.tc0, maxv);
 }
 
-/* ---- luma qpel: a lane per output sample (16 lanes per row of a 16-wide block) --------------------------------------------- */
-__device__ __forceinline__ int hbd_tap6(int a, int b, int c, int d, int e, int f) { return (c + d) * 20 - (b + e) * 5 + (a + f); }
-
+/* ---- luma qpel: a lane per output sample (16 lanes per row of a 16-wide block); the arithmetic is h264_mc_rules.h's -------------- */
 /* The reference samples around one output sample: at(dx, dy).  A record flagged FFHIP_MC_EMU (include/ffhip.h; h264_mb.c:229-247,
  * 297-317 -> videodsp_template.c:24-100) reads them at clamped coordinates of the reference picture whose (0, 0) is `p`. */
 template <typename P>
@@ -240,8 +239,6 @@ struct HbdSrc {
             return (int)p[(ptrdiff_t)min(max(y + dy, 0), ph - 1) * s + min(max(x + dx, 0), pw - 1)];
         return (int)p[dy * s + dx];
     }
-    __device__ __forceinline__ int h(int dx, int dy) const { return hbd_tap6(at(dx - 2, dy), at(dx - 1, dy), at(dx, dy), at(dx + 1, dy), at(dx + 2, dy), at(dx + 3, dy)); }
-    __device__ __forceinline__ int v(int dx, int dy) const { return hbd_tap6(at(dx, dy - 2), at(dx, dy - 1), at(dx, dy), at(dx, dy + 1), at(dx, dy + 2), at(dx, dy + 3)); }
 };
 
 template <typename P>
@@ -262,42 +259,10 @@ __global__ __launch_bounds__(256) void k_h264_qpel_hbd(uint8_t *dst_base, const 
     S.x = bl.src_x + x; S.y = bl.src_y + y;
     S.p = reinterpret_cast<const P *>(src_base + bl.src_offset) + (S.emu ? 0 : y * s + x);
     P *dst = reinterpret_cast<P *>(dst_base + bl.dst_offset) + y * s + x;
-    const int maxv = (1 << bd) - 1, mc = bl.mcxy & 15, mx = mc & 3, my = mc >> 2;
-#define QH(dx, dy) hclip((S.h(dx, dy) + 16) >> 5, maxv)
-#define QV(dx, dy) hclip((S.v(dx, dy) + 16) >> 5, maxv)
-#define QA(a, b) (((a) + (b) + 1) >> 1)
-    int hv = 0;
-    if (mx == 2 || my == 2) {
-        if ((mx == 2 && my == 2) || (mx != 0 && my != 0)) {
-            int tt[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++)
-                tt[k] = S.h(0, k - 2);
-            hv = hclip((hbd_tap6(tt[0], tt[1], tt[2], tt[3], tt[4], tt[5]) + 512) >> 10, maxv);
-        }
-    }
+    const int mc = bl.mcxy & 15;
     int v;
-    switch (mc) {
-    case 0:  v = S.at(0, 0); break;
-    case 1:  v = QA(S.at(0, 0), QH(0, 0)); break;
-    case 2:  v = QH(0, 0); break;
-    case 3:  v = QA(S.at(1, 0), QH(0, 0)); break;
-    case 4:  v = QA(S.at(0, 0), QV(0, 0)); break;
-    case 8:  v = QV(0, 0); break;
-    case 12: v = QA(S.at(0, 1), QV(0, 0)); break;
-    case 5:  v = QA(QH(0, 0), QV(0, 0)); break;
-    case 7:  v = QA(QH(0, 0), QV(1, 0)); break;
-    case 13: v = QA(QH(0, 1), QV(0, 0)); break;
-    case 15: v = QA(QH(0, 1), QV(1, 0)); break;
-    case 10: v = hv; break;
-    case 6:  v = QA(QH(0, 0), hv); break;
-    case 14: v = QA(QH(0, 1), hv); break;
-    case 9:  v = QA(QV(0, 0), hv); break;
-    default: v = QA(QV(1, 0), hv); break;
-    }
-    dst[0] = (P)(bl.avg ? QA((int)dst[0], v) : v);
-#undef QH
-#undef QV
+    H264MC_LUMA(v, S, mc & 3, mc >> 2, (1 << bd) - 1);
+    dst[0] = (P)(bl.avg ? h264mc_avg((int)dst[0], v) : v);
 }
 
 /* ---- chroma MC and explicit weighting: a lane per output sample ---------------------------------------------------------------- */
@@ -319,13 +284,8 @@ __global__ __launch_bounds__(128) void k_h264_chroma_mc_hbd(uint8_t *dst_base, c
     S.x = bl.src_x + x; S.y = bl.src_y + y;
     S.p = reinterpret_cast<const P *>(src_base + bl.src_offset) + (S.emu ? 0 : y * s + x);
     P *dst = reinterpret_cast<P *>(dst_base + bl.dst_offset) + y * s + x;
-    const int fx = bl.x, fy = bl.y, A = (8 - fx) * (8 - fy), B = fx * (8 - fy), Cc = (8 - fx) * fy, D = fx * fy;
-    int v = A * S.at(0, 0);
-    if (B) v += B * S.at(1, 0);        /* the template never reads a neighbour whose weight is zero */
-    if (Cc) v += Cc * S.at(0, 1);
-    if (D) v += D * S.at(1, 1);
-    v = (v + 32) >> 6;
-    dst[0] = (P)(bl.avg ? ((int)dst[0] + v + 1) >> 1 : v);
+    const int v = h264mc_chroma(S, bl.x, bl.y);
+    dst[0] = (P)(bl.avg ? h264mc_avg((int)dst[0], v) : v);
 }
 
 template <typename P>
@@ -341,17 +301,11 @@ __global__ __launch_bounds__(256) void k_h264_weight_hbd(uint8_t *dst_base, cons
         return;
     const ptrdiff_t s = stride / (ptrdiff_t)sizeof(P);
     P *dst = reinterpret_cast<P *>(dst_base + bl.dst_offset) + y * s + x;
-    const int maxv = (1 << bd) - 1, ld = bl.log2_denom;
     if (!bl.bi) {
-        int offset = (int)((unsigned)(int)bl.offset << (ld + (bd - 8)));
-        if (ld)
-            offset += 1 << (ld - 1);
-        dst[0] = (P)hclip(((int)dst[0] * (int)bl.weightd + offset) >> ld, maxv);
+        dst[0] = (P)h264mc_weight((int)dst[0], bd, bl.log2_denom, bl.weightd, bl.offset);
     } else {
         const P *src = reinterpret_cast<const P *>(src_base + bl.src_offset) + y * s + x;
-        int offset = (int)((unsigned)(int)bl.offset << (bd - 8));
-        offset = (int)((unsigned)((offset + 1) | 1) << ld);
-        dst[0] = (P)hclip(((int)src[0] * (int)bl.weights + (int)dst[0] * (int)bl.weightd + offset) >> (ld + 1), maxv);
+        dst[0] = (P)h264mc_biweight((int)dst[0], (int)src[0], bd, bl.log2_denom, bl.weightd, bl.weights, bl.offset);
     }
 }
 

@@ -12,14 +12,15 @@
  *   3. average / weight / biweight in registers;
  *   4. the samples go through a wave-private LDS tile and leave as whole rows of a block: one 4-sample store per luma row and one
  *      2-sample store per chroma row.  Nothing goes to HBM between the lists.
- * The interpolation is the per-sample statement of h264_hbd.hip's kernels (h264qpel_template.c, h264chroma_template.c) with the depth
- * as an argument; the source coordinates are clamped as FFHIP_MC_EMU records are.
+ * The interpolation and the weighting are h264_mc_rules.h's per-sample statements, which h264_hbd.hip's kernels run too; the source
+ * coordinates are clamped as FFHIP_MC_EMU records are.
  */
 #include <stddef.h>
 
 #include "common.h"
 #include "h264_kernels.h"
 #include "h264_inter_rules.h"
+#include "h264_mc_rules.h"
 
 static_assert(sizeof(FFHipH264MvField) == 12 && sizeof(FFHipH264BsMb) == 8, "the records of the edge-parameter face");
 static_assert(sizeof(FFHipH264InterSlice) == 2888, "FFHipH264InterSlice is a 2888-byte record");
@@ -35,7 +36,22 @@ constexpr int WIN = 9;              /* a 4x4 block's window: 2 samples before, 3
 constexpr int WIN_PITCH = 84;       /* uint16_t entries per block window (81 used) */
 constexpr int WAVE_LDS = 4 * WIN_PITCH + 64 + 32; /* four windows, the luma tile, the chroma tile */
 
-__device__ __forceinline__ int tap6(int a, int b, int c, int d, int e, int f) { return (c + d) * 20 - (b + e) * 5 + (a + f); }
+/* a lane's sample in its block's LDS window */
+struct WinSrc {
+    const uint16_t *w0;
+    __device__ __forceinline__ int at(int dx, int dy) const { return (int)w0[dy * WIN + dx]; }
+};
+/* a chroma sample of a reference plane of cw x ch samples, at clamped coordinates */
+template <typename P>
+struct ClampSrc {
+    const uint8_t *base;
+    ptrdiff_t s;
+    int x0, y0, cw, ch;
+    __device__ __forceinline__ int at(int dx, int dy) const
+    {
+        return (int)reinterpret_cast<const P *>(base + (ptrdiff_t)min(max(y0 + dy, 0), ch - 1) * s)[min(max(x0 + dx, 0), cw - 1)];
+    }
+};
 
 template <typename P>
 __global__ __launch_bounds__(256) void k_h264_inter_pic(const FFHipH264InterPic *pics, int mb_w, int mb_h, int bd, int chroma)
@@ -78,57 +94,12 @@ __global__ __launch_bounds__(256) void k_h264_inter_pic(const FFHipH264InterPic 
         }
         ffhip_wave_sync();
         if (on) {
-            const uint16_t *w0 = win + (y4 + 2) * WIN + x4 + 2;
-            auto at = [&](int dx, int dy) { return (int)w0[dy * WIN + dx]; };
-            auto h = [&](int dx, int dy) { return tap6(at(dx - 2, dy), at(dx - 1, dy), at(dx, dy), at(dx + 1, dy), at(dx + 2, dy), at(dx + 3, dy)); };
-            auto v = [&](int dx, int dy) { return tap6(at(dx, dy - 2), at(dx, dy - 1), at(dx, dy), at(dx, dy + 1), at(dx, dy + 2), at(dx, dy + 3)); };
-#define QH(dx, dy) min(max((h(dx, dy) + 16) >> 5, 0), maxv)
-#define QV(dx, dy) min(max((v(dx, dy) + 16) >> 5, 0), maxv)
-#define QA(a, b) (((a) + (b) + 1) >> 1)
-            int hv = 0;
-            if ((fx == 2 && fy) || (fy == 2 && fx)) {   /* the centre column / row: vertical 6-tap over the unrounded horizontal sums */
-                int tt[6];
-#pragma unroll
-                for (int i = 0; i < 6; i++)
-                    tt[i] = h(0, i - 2);
-                hv = min(max((tap6(tt[0], tt[1], tt[2], tt[3], tt[4], tt[5]) + 512) >> 10, 0), maxv);
-            }
-            int val;
-            switch (fx + 4 * fy) {
-            case 0:  val = at(0, 0); break;
-            case 1:  val = QA(at(0, 0), QH(0, 0)); break;
-            case 2:  val = QH(0, 0); break;
-            case 3:  val = QA(at(1, 0), QH(0, 0)); break;
-            case 4:  val = QA(at(0, 0), QV(0, 0)); break;
-            case 8:  val = QV(0, 0); break;
-            case 12: val = QA(at(0, 1), QV(0, 0)); break;
-            case 5:  val = QA(QH(0, 0), QV(0, 0)); break;
-            case 7:  val = QA(QH(0, 0), QV(1, 0)); break;
-            case 13: val = QA(QH(0, 1), QV(0, 0)); break;
-            case 15: val = QA(QH(0, 1), QV(1, 0)); break;
-            case 10: val = hv; break;
-            case 6:  val = QA(QH(0, 0), hv); break;
-            case 14: val = QA(QH(0, 1), hv); break;
-            case 9:  val = QA(QV(0, 0), hv); break;
-            default: val = QA(QV(1, 0), hv); break;
-            }
-#undef QH
-#undef QV
-            pl[n] = val;
+            const WinSrc S = { win + (y4 + 2) * WIN + x4 + 2 };
+            H264MC_LUMA(pl[n], S, fx, fy, maxv);
             if (clane) {
                 const int cx = mvx, cy = mvy + R.chroma_dy, ax = cx & 7, ay = cy & 7;
-                const int x0 = bx * 2 + cxs + (cx >> 3), y0 = by * 2 + cys + (cy >> 3), cw = pw >> 1, chh = ph >> 1;
-                const uint8_t *base = R.base[1 + cpl];
-                const ptrdiff_t s = R.stride[1 + cpl];
-                auto cat = [&](int dx, int dy) {
-                    return (int)reinterpret_cast<const P *>(base + (ptrdiff_t)min(max(y0 + dy, 0), chh - 1) * s)[min(max(x0 + dx, 0), cw - 1)];
-                };
-                const int A = (8 - ax) * (8 - ay), B = ax * (8 - ay), Cc = (8 - ax) * ay, D = ax * ay;
-                int vv = A * cat(0, 0);
-                if (B) vv += B * cat(1, 0);
-                if (Cc) vv += Cc * cat(0, 1);
-                if (D) vv += D * cat(1, 1);
-                pc[n] = (vv + 32) >> 6;
+                const ClampSrc<P> Sc = { R.base[1 + cpl], R.stride[1 + cpl], bx * 2 + cxs + (cx >> 3), by * 2 + cys + (cy >> 3), pw >> 1, ph >> 1 };
+                pc[n] = h264mc_chroma(Sc, ax, ay);
             }
         }
         ffhip_wave_sync(); /* list 1's window overwrites list 0's */
@@ -140,22 +111,21 @@ __global__ __launch_bounds__(256) void k_h264_inter_pic(const FFHipH264InterPic 
     int yv = pl[0], cv = pc[0];
     switch (plan.mode) {
     case FFHIP_H264_INTER_UNI_W:
-        yv = h264inter_weight(pl[0], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_offset);
+        yv = h264mc_weight(pl[0], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_offset);
         if (plan.chroma_weighted)
-            cv = h264inter_weight(pc[0], bd, plan.chroma_log2_denom, cw0, co);
+            cv = h264mc_weight(pc[0], bd, plan.chroma_log2_denom, cw0, co);
         break;
     case FFHIP_H264_INTER_BI_AVG:
-        yv = QA(pl[0], pl[1]);
-        cv = QA(pc[0], pc[1]);
+        yv = h264mc_avg(pl[0], pl[1]);
+        cv = h264mc_avg(pc[0], pc[1]);
         break;
     case FFHIP_H264_INTER_BI_W:
-        yv = h264inter_biweight(pl[0], pl[1], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_weight[1], plan.luma_offset);
-        cv = h264inter_biweight(pc[0], pc[1], bd, plan.chroma_log2_denom, cw0, cw1, co);
+        yv = h264mc_biweight(pl[0], pl[1], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_weight[1], plan.luma_offset);
+        cv = h264mc_biweight(pc[0], pc[1], bd, plan.chroma_log2_denom, cw0, cw1, co);
         break;
     default:
         break;
     }
-#undef QA
 
     /* ---- 4. whole rows of a block ---- */
     ytile[lane] = (uint16_t)yv;

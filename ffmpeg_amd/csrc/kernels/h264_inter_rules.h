@@ -3,7 +3,8 @@
  * ffhip_h264_inter_pictures_dev as include/ffhip.h states them), once: shared by the kernel of h264_inter_pic.hip and by the
  * device-free face ffhip_h264_inter_plan_pictures_host() (shims_h264_inter.hip), which runs it on the host.  Restated from memory of
  * the reference's h264_mb.c (mc_part and what it calls) and from H.264 8.4.2.2 / 8.4.2.3, not checked against its source.  One plain
- * function of the macroblock record, the block's motion record and the slice table; it reads nothing else.
+ * function of the macroblock record, the block's motion record and the slice table; it reads nothing else.  What a mode does to the
+ * samples (weight / biweight_h264_pixels) is h264_mc_rules.h's.
  */
 #ifndef FFHIP_H264_INTER_RULES_H
 #define FFHIP_H264_INTER_RULES_H
@@ -93,22 +94,6 @@ H264INTER_FN FFHipH264InterBlockPlan h264inter_plan(const FFHipH264BsMb *m, cons
         }
     }
     return p;
-}
-
-/* weight_h264_pixels / biweight_h264_pixels for one sample at depth bd (h264dsp_template.c); the offset in 8-bit units */
-H264INTER_FN int h264inter_clip(int v, int maxv) { return v < 0 ? 0 : v > maxv ? maxv : v; }
-H264INTER_FN int h264inter_weight(int p, int bd, int ld, int w, int o)
-{
-    int offset = (int)((unsigned)o << (ld + (bd - 8)));
-    if (ld)
-        offset += 1 << (ld - 1);
-    return h264inter_clip((p * w + offset) >> ld, (1 << bd) - 1);
-}
-H264INTER_FN int h264inter_biweight(int p0, int p1, int bd, int ld, int w0, int w1, int o)
-{
-    int offset = (int)((unsigned)o << (bd - 8));
-    offset = (int)((unsigned)((offset + 1) | 1) << ld);
-    return h264inter_clip((p1 * w1 + p0 * w0 + offset) >> (ld + 1), (1 << bd) - 1);
 }
 
 #endif /* FFHIP_H264_INTER_RULES_H */

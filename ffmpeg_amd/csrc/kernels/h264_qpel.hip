@@ -2,11 +2,10 @@
  * h264_qpel.hip — H.264 8-bit luma quarter-pel motion compensation, batched.
  *
  * Bit-exact restatement of put/avg_h264_qpel{16,8,4}_mcXY_8_c (libavcodec/h264qpel_template.c:313-459)
- * stated per output sample:
- *   tap6(a..f) = (c+d)*20 - (b+e)*5 + (a+f)                      (:77-305, the 6-tap lowpass)
+ * stated per output sample.  The scalar 6-tap h264mc_tap6, the table of which of {F, H, V, J} a position
+ * combines (h264mc_pos) and the packed rnd_avg h264mc_avg4 live in h264_mc_rules.h; here:
  *   H = clip_u8((tap6 along x + 16) >> 5), V likewise along y,
  *   J = clip_u8((tap6 along y of the UNCLIPPED horizontal sums + 512) >> 10)     (the "hv" centre)
- *   quarter positions = rnd_avg (a+b+1)>>1 of two of {F, H, V, J} per the 16-entry table,
  *   avg_ variants rnd_avg the result with dst (op_avg, :461).
  *
  * GPU design: one wave per block; lane (y, xg) owns the 4 horizontally adjacent samples
@@ -22,6 +21,7 @@
 
 #include "common.h"
 #include "h264_kernels.h"
+#include "h264_mc_rules.h"
 
 /* 12 source bytes starting at p (any alignment): aligned dword loads, funnel-shifted into place */
 struct Row12 { uint32_t w[3]; };
@@ -63,13 +63,11 @@ __device__ __forceinline__ Row12 load_row12_emu(const uint8_t *org, ptrdiff_t st
 }
 
 __device__ __forceinline__ int rbyte(const Row12 &r, int i) { return (int)((r.w[i >> 2] >> (8 * (i & 3))) & 0xFF); }
-__device__ __forceinline__ int tap6(int a, int b, int c, int d, int e, int f) { return (c + d) * 20 - (b + e) * 5 + (a + f); }
 /* unclipped horizontal sum at sample i (0..4) of the lane; stream byte 0 is x-2 */
 __device__ __forceinline__ int hraw(const Row12 &r, int i)
 {
-    return tap6(rbyte(r, i), rbyte(r, i + 1), rbyte(r, i + 2), rbyte(r, i + 3), rbyte(r, i + 4), rbyte(r, i + 5));
+    return h264mc_tap6(rbyte(r, i), rbyte(r, i + 1), rbyte(r, i + 2), rbyte(r, i + 3), rbyte(r, i + 4), rbyte(r, i + 5));
 }
-__device__ __forceinline__ uint32_t rnd_avg4(uint32_t a, uint32_t b) { return (a | b) - (((a ^ b) & 0xFEFEFEFEu) >> 1); }
 
 __global__ __launch_bounds__(256) void k_h264_qpel(uint8_t *dst, const uint8_t *src, ptrdiff_t stride,
                                                    const FFHipQpelBlock *blocks, int n, int pic_w, int pic_h)
@@ -87,15 +85,12 @@ __global__ __launch_bounds__(256) void k_h264_qpel(uint8_t *dst, const uint8_t *
     const int y = lane / per_row, xg = lane - y * per_row;
     if (y >= size)
         return;
-    const int mx = mc & 3, my = mc >> 2;
     const uint8_t *s = src + __builtin_amdgcn_readfirstlane(blk.src_offset) + (ptrdiff_t)y * stride + 4 * xg - 2;
     uint8_t *d = dst + __builtin_amdgcn_readfirstlane(blk.dst_offset) + (ptrdiff_t)y * stride + 4 * xg;
 
-    /* which of F/H/V/J the position combines (appendix A.6 table), all wave-uniform */
-    const bool useJ = (mx == 2 && my != 0) || (my == 2 && mx != 0);
-    const bool useV = (mx != 2 && my != 0) || (mc == 8);       /* V at x (mx 0,1) or x+1 (mx 3) */
-    const bool useH = (my != 2 && mx != 0) || (mc == 2);       /* H at y (my 0,1) or y+1 (my 3) */
-    const bool vcol1 = mx == 3, hrow1 = my == 3;
+    /* which of F/H/V/J the position combines, all wave-uniform */
+    const H264McPos pos = h264mc_pos(mc & 3, mc >> 2);
+    const bool useJ = pos.useJ, useV = pos.useV, useH = pos.useH, vcol1 = pos.vcol1, hrow1 = pos.hrow1;
 
     Row12 r[6]; /* rows y-2 .. y+3 */
     if (pic_w > 0 && (__builtin_amdgcn_readfirstlane((int)blk.flags) & FFHIP_MC_EMU)) {
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(256) void k_h264_qpel(uint8_t *dst, const uint8_t *
     if (useJ) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int v = tap6(hraw(r[0], i), hraw(r[1], i), hraw(r[2], i), hraw(r[3], i), hraw(r[4], i), hraw(r[5], i));
+            const int v = h264mc_tap6(hraw(r[0], i), hraw(r[1], i), hraw(r[2], i), hraw(r[3], i), hraw(r[4], i), hraw(r[5], i));
             pj |= (uint32_t)clip_u8((v + 512) >> 10) << (8 * i);
         }
     }
@@ -132,32 +127,32 @@ __global__ __launch_bounds__(256) void k_h264_qpel(uint8_t *dst, const uint8_t *
         const int c0 = vcol1 ? 3 : 2; /* stream byte of sample 0's column */
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int v = tap6(rbyte(r[0], c0 + i), rbyte(r[1], c0 + i), rbyte(r[2], c0 + i), rbyte(r[3], c0 + i),
+            const int v = h264mc_tap6(rbyte(r[0], c0 + i), rbyte(r[1], c0 + i), rbyte(r[2], c0 + i), rbyte(r[3], c0 + i),
                                rbyte(r[4], c0 + i), rbyte(r[5], c0 + i));
             pv |= (uint32_t)clip_u8((v + 16) >> 5) << (8 * i);
         }
     }
     /* full-pel samples: F, F(+1,0) for mc30, F(0,+1) for mc03 */
     {
-        const Row12 &fr = (mc == 12) ? r[3] : r[2];
-        const uint32_t sh = (mc == 3) ? 3 : 2;
+        const Row12 &fr = pos.fdy ? r[3] : r[2];
+        const uint32_t sh = pos.fdx ? 3 : 2;
         pf = __builtin_amdgcn_alignbyte(fr.w[1], fr.w[0], sh);
     }
     switch (mc) {
     case 0:  out = pf; break;
-    case 1: case 3:  out = rnd_avg4(pf, ph); break;
+    case 1: case 3:  out = h264mc_avg4(pf, ph); break;
     case 2:  out = ph; break;
-    case 4: case 12: out = rnd_avg4(pf, pv); break;
-    case 5: case 7: case 13: case 15: out = rnd_avg4(ph, pv); break;
-    case 6: case 14: out = rnd_avg4(ph, pj); break;
+    case 4: case 12: out = h264mc_avg4(pf, pv); break;
+    case 5: case 7: case 13: case 15: out = h264mc_avg4(ph, pv); break;
+    case 6: case 14: out = h264mc_avg4(ph, pj); break;
     case 8:  out = pv; break;
-    case 9: case 11: out = rnd_avg4(pv, pj); break;
+    case 9: case 11: out = h264mc_avg4(pv, pj); break;
     default: out = pj; break; /* 10 */
     }
     if (!((reinterpret_cast<uintptr_t>(d)) & 3)) {
         uint32_t *dw = reinterpret_cast<uint32_t *>(d);
         if (avg)
-            out = rnd_avg4(*dw, out);
+            out = h264mc_avg4(*dw, out);
         *dw = out;
     } else {
         for (int i = 0; i < 4; i++) {
@@ -270,11 +265,8 @@ __device__ __forceinline__ void qp_block(const QpBlk &q, const uint32_t *f, uint
     const uint32_t sh = q.sh;
     const bool avg = q.avg;
     const int per_row = size >> 2, lgp = size == 16 ? 2 : size == 8 ? 1 : 0; /* 4-sample groups per row, and their log2 */
-    const int mx = mc & 3, my = mc >> 2;
-    const bool useJ = (mx == 2 && my != 0) || (my == 2 && mx != 0);
-    const bool useV = (mx != 2 && my != 0) || (mc == 8);
-    const bool useH = (my != 2 && mx != 0) || (mc == 2);
-    const bool vcol1 = mx == 3, hrow1 = my == 3;
+    const H264McPos pos = h264mc_pos(mc & 3, mc >> 2);
+    const bool useJ = pos.useJ, useV = pos.useV, useH = pos.useH, vcol1 = pos.vcol1, hrow1 = pos.hrow1;
 
     /* ---- 1. footprint -> LDS ---- */
     if (f) {
@@ -350,20 +342,20 @@ __device__ __forceinline__ void qp_block(const QpBlk &q, const uint32_t *f, uint
             pv = qp_round5(qp_tap6(c01[0], c01[1], c01[2], c01[3], c01[4], c01[5]), qp_tap6(c23[0], c23[1], c23[2], c23[3], c23[4], c23[5]));
         }
         {
-            const uint32_t o = sh + (mc == 3 ? 3 : 2);
-            const uint32_t *p = raw + (y + (mc == 12 ? 3 : 2)) * rp + xg + (o >> 2);
+            const uint32_t o = sh + (pos.fdx ? 3 : 2);
+            const uint32_t *p = raw + (y + (pos.fdy ? 3 : 2)) * rp + xg + (o >> 2);
             pf = __builtin_amdgcn_alignbyte(p[1], p[0], o & 3);
         }
         uint32_t out;
         switch (mc) {
         case 0:  out = pf; break;
-        case 1: case 3:  out = rnd_avg4(pf, ph); break;
+        case 1: case 3:  out = h264mc_avg4(pf, ph); break;
         case 2:  out = ph; break;
-        case 4: case 12: out = rnd_avg4(pf, pv); break;
-        case 5: case 7: case 13: case 15: out = rnd_avg4(ph, pv); break;
-        case 6: case 14: out = rnd_avg4(ph, pj); break;
+        case 4: case 12: out = h264mc_avg4(pf, pv); break;
+        case 5: case 7: case 13: case 15: out = h264mc_avg4(ph, pv); break;
+        case 6: case 14: out = h264mc_avg4(ph, pj); break;
         case 8:  out = pv; break;
-        case 9: case 11: out = rnd_avg4(pv, pj); break;
+        case 9: case 11: out = h264mc_avg4(pv, pj); break;
         default: out = pj; break; /* 10 */
         }
         if (ob) {
@@ -371,7 +363,7 @@ __device__ __forceinline__ void qp_block(const QpBlk &q, const uint32_t *f, uint
         } else if (!((reinterpret_cast<uintptr_t>(d)) & 3)) {
             uint32_t *dw = reinterpret_cast<uint32_t *>(d);
             if (avg)
-                out = rnd_avg4(*dw, out);
+                out = h264mc_avg4(*dw, out);
             *dw = out;
         } else {
             for (int i = 0; i < 4; i++) {
@@ -489,7 +481,7 @@ __global__ __launch_bounds__(256) void k_h264_qpel_t(uint8_t *dst, const uint8_t
         qp_u4 *dp = reinterpret_cast<qp_u4 *>(dst + doff + (ptrdiff_t)y * stride);
         if (avg) {
             const qp_u4 old = *dp;
-            o.x = rnd_avg4(old.x, o.x); o.y = rnd_avg4(old.y, o.y); o.z = rnd_avg4(old.z, o.z); o.w = rnd_avg4(old.w, o.w);
+            o.x = h264mc_avg4(old.x, o.x); o.y = h264mc_avg4(old.y, o.y); o.z = h264mc_avg4(old.z, o.z); o.w = h264mc_avg4(old.w, o.w);
         }
         *dp = o;
     }
@@ -640,13 +632,13 @@ __device__ __forceinline__ uint32_t qm_block(int mc, long fa, long fb, uint32_t 
         pv = qm_pack4<5>(vv.x, vv.y, vv.z, vv.w, 0);
     }
     /* a position averages the first and the last of the planes it has (one plane: with itself), still 4-row column strips */
-    uint32_t c = rnd_avg4(F.useH ? ph : F.useV ? pv : pj, F.useJ ? pj : F.useV ? pv : ph);
+    uint32_t c = h264mc_avg4(F.useH ? ph : F.useV ? pv : pj, F.useJ ? pj : F.useV ? pv : ph);
     /* 4 x 4 byte transposition inside each lane quad: lane 4q + j gets row 4g + j, columns 4q .. 4q + 3 */
     const uint32_t t1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)c, 0xB1, 0xf, 0xf, true);     /* quad_perm [1,0,3,2] */
     const uint32_t c1 = __builtin_amdgcn_perm(t1, c, selT1);
     const uint32_t t2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)c1, 0x4E, 0xf, 0xf, true);    /* quad_perm [2,3,0,1] */
     c = __builtin_amdgcn_perm(t2, c1, selT2);
-    return mc == 0 ? ff : F.wantF ? rnd_avg4(ff, c) : c;
+    return mc == 0 ? ff : F.wantF ? h264mc_avg4(ff, c) : c;
 }
 
 /* The memory side is k_h264_qpel_t's, which tools/ubench/tilecopy found to be the cheapest way to move 16 x 16 tiles (the cost follows
@@ -741,7 +733,7 @@ __device__ __forceinline__ void qm_compute(const int (&Gsize)[4], const int (&Gm
             if (!((reinterpret_cast<uintptr_t>(d)) & 3)) {
                 uint32_t *dw = reinterpret_cast<uint32_t *>(d);
                 if (Gavg[k])
-                    out = rnd_avg4(*dw, out);
+                    out = h264mc_avg4(*dw, out);
                 *dw = out;
             } else {
                 for (int i = 0; i < 4; i++) {
@@ -761,7 +753,7 @@ __device__ __forceinline__ void qm_compute(const int (&Gsize)[4], const int (&Gm
         qp_u4 *dp = reinterpret_cast<qp_u4 *>(dst + doff + (ptrdiff_t)y * stride);
         if (avg) {
             const qp_u4 old = *dp;
-            o.x = rnd_avg4(old.x, o.x); o.y = rnd_avg4(old.y, o.y); o.z = rnd_avg4(old.z, o.z); o.w = rnd_avg4(old.w, o.w);
+            o.x = h264mc_avg4(old.x, o.x); o.y = h264mc_avg4(old.y, o.y); o.z = h264mc_avg4(old.z, o.z); o.w = h264mc_avg4(old.w, o.w);
         }
         *dp = o;
         __builtin_amdgcn_wave_barrier(); /* the next group refills the tile */
@@ -828,7 +820,7 @@ __device__ __forceinline__ void qm_compute_p(const int (&Gsize)[4], const int (&
                 if (!((reinterpret_cast<uintptr_t>(d)) & 3)) {
                     uint32_t *dw = reinterpret_cast<uint32_t *>(d);
                     if (Gavg[k])
-                        out = rnd_avg4(*dw, out);
+                        out = h264mc_avg4(*dw, out);
                     *dw = out;
                 } else {
                     for (int i = 0; i < 4; i++) {
@@ -849,7 +841,7 @@ __device__ __forceinline__ void qm_compute_p(const int (&Gsize)[4], const int (&
         qp_u4 *dp = reinterpret_cast<qp_u4 *>(dst + doff + (ptrdiff_t)y * stride);
         if (avg) {
             const qp_u4 old = *dp;
-            o.x = rnd_avg4(old.x, o.x); o.y = rnd_avg4(old.y, o.y); o.z = rnd_avg4(old.z, o.z); o.w = rnd_avg4(old.w, o.w);
+            o.x = h264mc_avg4(old.x, o.x); o.y = h264mc_avg4(old.y, o.y); o.z = h264mc_avg4(old.z, o.z); o.w = h264mc_avg4(old.w, o.w);
         }
         *dp = o;
         __builtin_amdgcn_wave_barrier();

@@ -11,8 +11,9 @@ The model knows partitions; the face does not.  model() expands a picture into t
 and plane the put of the first list, then the put of the second list into a scratch array and biweight, or its avg, or weight on the
 one list, each run by the oracle (ffo_h264_qpel_bd, ffo_h264_chroma_mc_bd, ffo_h264_weight_bd, ffo_h264_biweight_bd) on a source window
 gathered with numpy index clipping (what emulated_edge_mc gives).  Its decisions (decide()) are written from the rules of
-include/ffhip.h on their own, not from kernels/h264_inter_rules.h.  It also returns the plan of every 4x4 block and what it covered:
-the (size, mcxy) pairs, chroma fractions, modes, partition shapes and picture sides crossed."""
+include/ffhip.h on their own, not from kernels/h264_inter_rules.h, and its samples are the oracle's, not kernels/h264_mc_rules.h's.  It
+also returns the plan of every 4x4 block and what it covered: the (size, mcxy) pairs, chroma fractions, modes, partition shapes and
+picture sides crossed."""
 import ctypes as C
 import functools
 

@@ -233,6 +233,22 @@ def test_mc_and_weight_batch_hbd(depth):
     assert np.array_equal(back(dd, dst0), want)
 
 
+@pytest.mark.parametrize("depth", [8, 9, 10, 12, 14])
+def test_weight_matrix_hbd(depth):
+    """k_h264_weight_hbd over the cell matrix of test_gpu_mc_matrix.py::test_h264_weight_matrix (tests/h264_weight_matrix.py; its
+    conditions are tests/test_h264_weight_matrix_cpu.py's): every w_idx x height x log2_denom x {weight, biweight}, the weights and
+    offsets at their ends, bands at 0 and (1 << depth) - 1, the whole destination buffer compared.  Depth 8 is the uint8_t instantiation"""
+    import h264_weight_matrix as WM
+    torch, L = _torch(), _lib()
+    c = WM.case(depth)
+    n = len(c.cells)
+    dd, ds, dr = dev(c.dst0), dev(c.src), torch.from_numpy(c.rec.view(np.uint8).reshape(-1).copy()).cuda()
+    assert L.ffhip_h264_weight_batch_dev_hbd(depth, dd.data_ptr(), ds.data_ptr(), WM.STRIDE * c.px, dr.data_ptr(), n, None) == 0
+    torch.cuda.synchronize()
+    bad = WM.first_bad(c, back(dd, c.dst0))
+    assert bad is None, bad
+
+
 def test_depths_the_standard_does_not_define_are_refused():
     L = _lib()
     p = C.c_void_p(16)
