@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "h264_kernels.h"
+#include "hevc_mc_rules.h"
 
 static_assert(sizeof(FFHipHevcInterPU) == 20, "FFHipHevcInterPU is a 20-byte record");
 static_assert(sizeof(FFHipHevcInterTU) == 12, "FFHipHevcInterTU is a 12-byte record");
@@ -35,15 +36,8 @@ static_assert(sizeof(FFHipHevcInterPic) % 8 == 0, "FFHipHevcInterPic is staged a
 static_assert(HIP_PICS * sizeof(FFHipHevcInterPic) <= FFHIP_PROGRESS_SLOT_INTS * sizeof(int), "a launch's pictures fit one slot");
 
 namespace {
-/* the standard's filters (Table 8-11 luma, Table 8-12 chroma): the same values hevc_mc.hip lays out for its dot-product operands */
-__constant__ int8_t hip_lf[4][8] = { { 0 }, { -1, 4, -10, 58, 17, -5, 1, 0 }, { -1, 4, -11, 40, 40, -11, 4, -1 }, { 0, 1, -5, 17, 58, -10, 4, -1 } };
-__constant__ int8_t hip_cf[8][4] = { { 0 }, { -2, 58, 10, -2 }, { -4, 54, 16, -2 }, { -6, 46, 28, -4 }, { -4, 36, 36, -4 },
-                                     { -4, 28, 46, -6 }, { -2, 16, 54, -4 }, { -2, 10, 58, -2 } };
-
 constexpr int TILE = 64;            /* the tile's row pitch: a CTB plane is at most 64 x 64 */
 constexpr int ROWS = 64 + 7;        /* rows of the horizontal pass: h + TAPS - 1 */
-
-enum { M_PUT = 0, M_UNI = 1, M_UNI_W = 2, M_BI = 3, M_BI_W = 4 };
 
 /* one list of one block: the reference plane (clamped to rw x rh samples), the block's integer origin in it and its phases */
 struct HipSrc {
@@ -59,22 +53,25 @@ __device__ __forceinline__ int hip_ref(const HipSrc &s, int x, int y)
     return reinterpret_cast<const PIX *>(s.base + (ptrdiff_t)cy * s.stride)[cx];
 }
 
-/* MODE: M_PUT leaves the 14-bit intermediate in the tile (list 0 of a bi block); the others leave pixels, M_BI / M_BI_W reading
- * list 0's intermediate from the same tile positions.  wx0 / wx1 / ox / denom as the reference's output stages (ox already scaled). */
+template <typename PIX>
+struct HipWin { /* a source of hevc_mc_rules.h: the samples around (x, y) of the plane */
+    const HipSrc &s;
+    int x, y;
+    __device__ __forceinline__ int at(int dx, int dy) const { return hip_ref<PIX>(s, x + dx, y + dy); }
+};
+
+/* mode: HEVCMC_PUT leaves the 14-bit intermediate in the tile (list 0 of a bi block); the others leave pixels, HEVCMC_BI / HEVCMC_BI_W
+ * reading list 0's intermediate from the same tile positions.  wx0 / wx1 / ox / denom as the reference's output stages (ox already
+ * scaled).  The steps and stages are hevc_mc_rules.h's; the two loops over the block are written out here (the header says why). */
 template <typename PIX, bool CHROMA>
 __device__ __forceinline__ void hip_predict(int16_t *tile, int16_t *tmp, const HipSrc &s, int lx, int ly, int bw, int bh, int mode, int wx0,
                                             int wx1, int ox, int denom, int bd, int lane)
 {
-    constexpr int TAPS = CHROMA ? 4 : 8, B = CHROMA ? 1 : 3;
-    const int sh1 = bd - 8, shu = 14 - bd, maxv = (1 << bd) - 1;
+    constexpr int TAPS = CHROMA ? 4 : 8, B = hevcmc_before<TAPS>();
     int hf[TAPS], vf[TAPS];
-#pragma unroll
-    for (int t = 0; t < TAPS; t++) {
-        hf[t] = CHROMA ? hip_cf[s.mx][t] : hip_lf[s.mx][t];
-        vf[t] = CHROMA ? hip_cf[s.my][t] : hip_lf[s.my][t];
-    }
+    hevcmc_taps_c<TAPS>(s.mx, s.my, hf, vf);
     const float inv = 1.0f / (float)bw;
-    if (s.mx && s.my) { /* horizontal pass over rows -B .. bh + TAPS - 2 - B */
+    if (s.mx && s.my) { /* first pass over rows -B .. bh + TAPS - 2 - B */
         const int items = bw * (bh + TAPS - 1);
         for (int i = lane; i < items; i += 64) {
             const int r = (int)(((float)i + 0.5f) * inv), x = i - r * bw;
@@ -82,11 +79,11 @@ __device__ __forceinline__ void hip_predict(int16_t *tile, int16_t *tmp, const H
 #pragma unroll
             for (int t = 0; t < TAPS; t++)
                 acc += hf[t] * hip_ref<PIX>(s, s.xi + x + t - B, s.yi + r - B);
-            tmp[r * TILE + x] = (int16_t)(acc >> sh1);
+            tmp[r * TILE + x] = (int16_t)hevcmc_first(acc, bd);
         }
         ffhip_wave_sync();
     }
-    const int wsh = denom + shu; /* uni_w: shift; bi_w: log2Wd */
+    const int wsh = hevcmc_wshift(denom, bd);
     for (int i = lane; i < bw * bh; i += 64) {
         const int y = (int)(((float)i + 0.5f) * inv), x = i - y * bw;
         int val = 0;
@@ -94,35 +91,12 @@ __device__ __forceinline__ void hip_predict(int16_t *tile, int16_t *tmp, const H
 #pragma unroll
             for (int t = 0; t < TAPS; t++)
                 val += vf[t] * tmp[(y + t) * TILE + x];
-            val >>= 6;
-        } else if (s.mx) {
-#pragma unroll
-            for (int t = 0; t < TAPS; t++)
-                val += hf[t] * hip_ref<PIX>(s, s.xi + x + t - B, s.yi + y);
-            val >>= sh1;
-        } else if (s.my) {
-#pragma unroll
-            for (int t = 0; t < TAPS; t++)
-                val += vf[t] * hip_ref<PIX>(s, s.xi + x, s.yi + y + t - B);
-            val >>= sh1;
+            val = hevcmc_second(val);
         } else {
-            val = hip_ref<PIX>(s, s.xi + x, s.yi + y) << shu;
+            val = hevcmc_direct<TAPS>(HipWin<PIX>{ s, s.xi + x, s.yi + y }, hf, vf, s.mx, s.my, bd);
         }
         int16_t &d = tile[(ly + y) * TILE + lx + x];
-        int out;
-        if (mode == M_PUT) {
-            d = (int16_t)val;
-            continue;
-        } else if (mode == M_UNI) {
-            out = (val + (1 << (shu - 1))) >> shu;
-        } else if (mode == M_UNI_W) {
-            out = ((val * wx0 + (1 << (wsh - 1))) >> wsh) + ox;
-        } else if (mode == M_BI) {
-            out = (val + d + (1 << shu)) >> (shu + 1);
-        } else {
-            out = (val * wx1 + d * wx0 + (ox + 1) * (1 << wsh)) >> (wsh + 1);
-        }
-        d = (int16_t)min(max(out, 0), maxv);
+        d = (int16_t)hevcmc_out(mode, val, mode >= HEVCMC_BI ? d : 0, wx0, wx1, ox, wsh, bd);
     }
     ffhip_wave_sync(); /* tmp is reused by the next pass */
 }
@@ -200,16 +174,16 @@ __global__ __launch_bounds__(256) void k_hevc_inter_pic(const FFHipHevcInterPic 
                 }
             }
             const bool weighted = S.weighted;
-            const int denom = p ? S.chroma_log2_denom : S.luma_log2_denom, c = p - 1, osc = 1 << (bd - 8);
+            const int denom = p ? S.chroma_log2_denom : S.luma_log2_denom, c = p - 1;
             auto wt = [&](int l, int ri) { return p ? S.chroma_weight[l][ri][c] : S.luma_weight[l][ri]; };
-            auto of = [&](int l, int ri) { return (p ? S.chroma_offset[l][ri][c] : S.luma_offset[l][ri]) * osc; };
+            auto of = [&](int l, int ri) { return hevcmc_offset(p ? S.chroma_offset[l][ri][c] : S.luma_offset[l][ri], bd); };
             if (fl == 3) {
                 const int r0 = R.ref_idx[0], r1 = R.ref_idx[1];
                 if (p)
-                    hip_predict<PIX, true>(tile, tmp, src[0], lx, ly, bw, bh, M_PUT, 0, 0, 0, 0, bd, lane);
+                    hip_predict<PIX, true>(tile, tmp, src[0], lx, ly, bw, bh, HEVCMC_PUT, 0, 0, 0, 0, bd, lane);
                 else
-                    hip_predict<PIX, false>(tile, tmp, src[0], lx, ly, bw, bh, M_PUT, 0, 0, 0, 0, bd, lane);
-                const int mode = weighted ? M_BI_W : M_BI;
+                    hip_predict<PIX, false>(tile, tmp, src[0], lx, ly, bw, bh, HEVCMC_PUT, 0, 0, 0, 0, bd, lane);
+                const int mode = weighted ? HEVCMC_BI_W : HEVCMC_BI;
                 const int w0 = weighted ? wt(0, r0) : 0, w1 = weighted ? wt(1, r1) : 0, o = weighted ? of(0, r0) + of(1, r1) : 0;
                 if (p)
                     hip_predict<PIX, true>(tile, tmp, src[1], lx, ly, bw, bh, mode, w0, w1, o, denom, bd, lane);
@@ -217,7 +191,7 @@ __global__ __launch_bounds__(256) void k_hevc_inter_pic(const FFHipHevcInterPic 
                     hip_predict<PIX, false>(tile, tmp, src[1], lx, ly, bw, bh, mode, w0, w1, o, denom, bd, lane);
             } else {
                 const int l = fl >> 1, ri = R.ref_idx[l];
-                const int mode = weighted ? M_UNI_W : M_UNI;
+                const int mode = weighted ? HEVCMC_UNI_W : HEVCMC_UNI;
                 const int w0 = weighted ? wt(l, ri) : 0, o = weighted ? of(l, ri) : 0;
                 const HipSrc &su = l ? src[1] : src[0];
                 if (p)

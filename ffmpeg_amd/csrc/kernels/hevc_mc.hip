@@ -19,32 +19,14 @@
 
 #include "common.h"
 #include "h264_kernels.h"
+#include "hevc_mc_rules.h"
 
 typedef short mc_s2 __attribute__((ext_vector_type(2)));
 
 static_assert(sizeof(FFHipHevcMcBlock) == 12, "FFHipHevcMcBlock is a 12-byte record");
-/* 16-byte aligned: the tuned kernel reads a row of taps as one or two dwords (scalar loads) */
-__constant__ __attribute__((aligned(16))) int8_t hevc_lf8[4][8] = { { 0 }, { -1, 4, -10, 58, 17, -5, 1, 0 }, { -1, 4, -11, 40, 40, -11, 4, -1 }, { 0, 1, -5, 17, 58, -10, 4, -1 } };
-__constant__ __attribute__((aligned(16))) int8_t hevc_cf4[8][4] = { { 0 }, { -2, 58, 10, -2 }, { -4, 54, 16, -2 }, { -6, 46, 28, -4 }, { -4, 36, 36, -4 },
-                                       { -4, 28, 46, -6 }, { -2, 16, 54, -4 }, { -2, 10, 58, -2 } };
-
-
-/* the vertical taps as v_dot2_i32_i16 operands over row pairs (generated: pk(a, b) = a | b << 16):
- * [my][0..NP-1] first row even: (c0,c1)(c2,c3)..(0,0);  [my][NP..2NP-1] first row odd: (0,c0)(c1,c2)..(c_last,0) */
-__constant__ __attribute__((aligned(16))) uint32_t hevc_lv2[4][12] = {
-    { 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u },
-    { 0x0004ffffu, 0x003afff6u, 0xfffb0011u, 0x00000001u, 0x00000000u, 0xffff0000u, 0xfff60004u, 0x0011003au, 0x0001fffbu, 0x00000000u, 0x00000000u, 0x00000000u },
-    { 0x0004ffffu, 0x0028fff5u, 0xfff50028u, 0xffff0004u, 0x00000000u, 0xffff0000u, 0xfff50004u, 0x00280028u, 0x0004fff5u, 0x0000ffffu, 0x00000000u, 0x00000000u },
-    { 0x00010000u, 0x0011fffbu, 0xfff6003au, 0xffff0004u, 0x00000000u, 0x00000000u, 0xfffb0001u, 0x003a0011u, 0x0004fff6u, 0x0000ffffu, 0x00000000u, 0x00000000u } };
-__constant__ __attribute__((aligned(16))) uint32_t hevc_cv2[8][8] = {
-    { 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u },
-    { 0x003afffeu, 0xfffe000au, 0x00000000u, 0xfffe0000u, 0x000a003au, 0x0000fffeu, 0x00000000u, 0x00000000u },
-    { 0x0036fffcu, 0xfffe0010u, 0x00000000u, 0xfffc0000u, 0x00100036u, 0x0000fffeu, 0x00000000u, 0x00000000u },
-    { 0x002efffau, 0xfffc001cu, 0x00000000u, 0xfffa0000u, 0x001c002eu, 0x0000fffcu, 0x00000000u, 0x00000000u },
-    { 0x0024fffcu, 0xfffc0024u, 0x00000000u, 0xfffc0000u, 0x00240024u, 0x0000fffcu, 0x00000000u, 0x00000000u },
-    { 0x001cfffcu, 0xfffa002eu, 0x00000000u, 0xfffc0000u, 0x002e001cu, 0x0000fffau, 0x00000000u, 0x00000000u },
-    { 0x0010fffeu, 0xfffc0036u, 0x00000000u, 0xfffe0000u, 0x00360010u, 0x0000fffcu, 0x00000000u, 0x00000000u },
-    { 0x000afffeu, 0xfffe003au, 0x00000000u, 0xfffe0000u, 0x003a000au, 0x0000fffeu, 0x00000000u, 0x00000000u } };
+/* the vertical taps as v_dot2_i32_i16 operands over row pairs: hevcmc_dot2_rows() has the layout */
+__constant__ __attribute__((aligned(16))) HevcMcTab<uint32_t, 4, 12> hevc_lv2 = hevcmc_dot2_rows<8>();
+__constant__ __attribute__((aligned(16))) HevcMcTab<uint32_t, 8, 8> hevc_cv2 = hevcmc_dot2_rows<4>();
 /* ceil(65536 / ng), ng = 1..16 groups of 4 samples per row: i / ng == (i * inv) >> 16 for i < 4096 */
 __constant__ uint32_t hevc_mc_inv[17] = { 0, 65536, 32768, 21846, 16384, 13108, 10923, 9363, 8192, 7282, 6554, 5958, 5462, 5042, 4682, 4370, 4096 };
 
@@ -75,8 +57,6 @@ __device__ __forceinline__ void mc_hrow4(const uint8_t *p, int clo, int chi, int
                                       __builtin_amdgcn_sdot4((int)__builtin_amdgcn_alignbyte(d1, d0, 3), clo, 8192, false), false);
     }
 }
-
-__device__ __forceinline__ uint32_t mc_pk16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }
 
 /* MODE 0 put (int16), 1 uni, 2 uni_w, 3 bi, 4 bi_w; modes 2..4 read the 24-byte weighted record */
 /* SKIP16: the 16 x 16 blocks of the batch are k_hevc_qpel_m's (hevc_qpel_m.hip) — this launch leaves them alone */
@@ -114,23 +94,22 @@ __global__ __launch_bounds__(256) void k_hevc_mc(void *dst_, ptrdiff_t dststride
     uint32_t *tmp = tmp_all[wave];
 
     /* the taps as the dot instructions want them */
-    const int hlo = CHROMA ? reinterpret_cast<const int *>(hevc_cf4)[mx] : reinterpret_cast<const int *>(hevc_lf8)[2 * mx];
-    const int hhi = CHROMA ? 0 : reinterpret_cast<const int *>(hevc_lf8)[2 * mx + 1];
+    const int hlo = CHROMA ? reinterpret_cast<const int *>(hevc_cf4.v)[mx] : reinterpret_cast<const int *>(hevc_lf8.v)[2 * mx];
+    const int hhi = CHROMA ? 0 : reinterpret_cast<const int *>(hevc_lf8.v)[2 * mx + 1];
     uint32_t ce[NP], co[NP];
 #pragma unroll
     for (int q = 0; q < NP; q++) {
-        ce[q] = CHROMA ? hevc_cv2[my][q] : hevc_lv2[my][q];
-        co[q] = CHROMA ? hevc_cv2[my][NP + q] : hevc_lv2[my][NP + q];
+        ce[q] = CHROMA ? hevc_cv2.v[my][q] : hevc_lv2.v[my][q];
+        co[q] = CHROMA ? hevc_cv2.v[my][NP + q] : hevc_lv2.v[my][NP + q];
     }
 
-    int wx0 = 0, wx1 = 0, wofs = 0, wsh = 0, ox = 0;
+    int wx0 = 0, wx1 = 0, wsh = 0, ox = 0;
     const int16_t *s2 = nullptr;
     bool s2_al = false;
     if constexpr (MODE >= 2) {
         wx0 = __builtin_amdgcn_readfirstlane((int)k.wx0); wx1 = __builtin_amdgcn_readfirstlane((int)k.wx1);
-        ox = __builtin_amdgcn_readfirstlane((int)k.ox);
-        wsh = __builtin_amdgcn_readfirstlane((int)k.denom) + 6; /* uni_w: shift = denom + 14 - 8;  bi_w: log2Wd = denom + 6 */
-        wofs = MODE == 2 ? 1 << (wsh - 1) : (ox + 1) << wsh;
+        ox = hevcmc_offset(__builtin_amdgcn_readfirstlane((int)k.ox), 8);
+        wsh = hevcmc_wshift(__builtin_amdgcn_readfirstlane((int)k.denom), 8);
         s2 = src2 + __builtin_amdgcn_readfirstlane(k.src2_offset);
         s2_al = (reinterpret_cast<uintptr_t>(s2) & 7) == 0;
     }
@@ -145,7 +124,7 @@ __global__ __launch_bounds__(256) void k_hevc_mc(void *dst_, ptrdiff_t dststride
         if constexpr (MODE == 0) {
             int16_t *d = d16 + y * 64 + x0;
             if (cnt >= 4 && d_al) {
-                *reinterpret_cast<uint2 *>(d) = make_uint2(mc_pk16(val[0], val[1]), mc_pk16(val[2], val[3]));
+                *reinterpret_cast<uint2 *>(d) = make_uint2(hevcmc_pk16(val[0], val[1]), hevcmc_pk16(val[2], val[3]));
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; j++)
@@ -154,31 +133,12 @@ __global__ __launch_bounds__(256) void k_hevc_mc(void *dst_, ptrdiff_t dststride
             }
         } else {
             int o2[4] = { 0, 0, 0, 0 };
-            if constexpr (MODE >= 3) {
-                const int16_t *q = s2 + y * 64 + x0;
-                if (s2_al) {
-                    const uint2 v = *reinterpret_cast<const uint2 *>(q);
-                    o2[0] = (int16_t)(v.x & 0xffff); o2[1] = (int)v.x >> 16; o2[2] = (int16_t)(v.y & 0xffff); o2[3] = (int)v.y >> 16;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        o2[j] = q[j];
-                }
-            }
+            if constexpr (MODE >= 3)
+                hevcmc_ld4(s2 + y * 64 + x0, s2_al, o2);
             int out[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                int v;
-                if constexpr (MODE == 1)
-                    v = (val[j] + 32) >> 6;
-                else if constexpr (MODE == 2)
-                    v = ((val[j] * wx0 + wofs) >> wsh) + ox;
-                else if constexpr (MODE == 3)
-                    v = (val[j] + o2[j] + 64) >> 7;
-                else
-                    v = (val[j] * wx1 + o2[j] * wx0 + wofs) >> (wsh + 1);
-                out[j] = clip_u8(v);
-            }
+            for (int j = 0; j < 4; j++)
+                out[j] = clip_u8(hevcmc_stage(MODE, val[j], o2[j], wx0, wx1, ox, wsh, 8));
             uint8_t *d = d8 + (ptrdiff_t)y * dststride + x0;
             if (cnt >= 4 && d_al) {
                 *reinterpret_cast<uint32_t *>(d) = (uint32_t)out[0] | (uint32_t)out[1] << 8 | (uint32_t)out[2] << 16 | (uint32_t)out[3] << 24;
@@ -267,10 +227,9 @@ __global__ __launch_bounds__(256) void k_hevc_mc_s(void *dst_, ptrdiff_t dststri
     /* PIX = uint8_t (bd 8) / uint16_t (bd 10, 12; strides and offsets stay in bytes).  Above 8 bits the one-dimensional sums drop
      * bd - 8 bits, the unfiltered copy gains 14 - bd, and every output stage shifts by its 8-bit amount minus (bd - 8), offsets
      * scaled by << (bd - 8) (h2656_inter_template.c:29-88,113-245; hevc/dsp_template.c:368-440) */
-    constexpr bool UNI = MODE == 1;
     using Rec = typename std::conditional<(MODE >= 2), FFHipHevcMcWBlock, FFHipHevcMcBlock>::type;
     const Rec *blocks = static_cast<const Rec *>(blocks_);
-    constexpr int TAPS = CHROMA ? 4 : 8, BEFORE = CHROMA ? 1 : 3;
+    constexpr int TAPS = CHROMA ? 4 : 8, BEFORE = hevcmc_before<TAPS>();
     __shared__ int16_t tmp_all[4][(64 + TAPS - 1) * 64];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
@@ -278,25 +237,19 @@ __global__ __launch_bounds__(256) void k_hevc_mc_s(void *dst_, ptrdiff_t dststri
         return;
     const Rec k = blocks[b];
     const int w = k.width, h = k.height, mx = k.mx & (CHROMA ? 7 : 3), my = k.my & (CHROMA ? 7 : 3);
-    const int sh1 = bd - 8, shu = 14 - bd, maxv = (1 << bd) - 1;
     const ptrdiff_t sst = srcstride / (ptrdiff_t)sizeof(PIX);
-    int wx0 = 0, wx1 = 0, wofs = 0, wsh = 0, ox = 0;
+    int wx0 = 0, wx1 = 0, wsh = 0, ox = 0;
     const int16_t *s2 = nullptr;
     if constexpr (MODE >= 2) {
-        wx0 = k.wx0; wx1 = k.wx1; ox = k.ox * (1 << sh1);
-        wsh = k.denom + shu;                                 /* uni_w: shift = denom + 14 - bd;  bi_w: log2Wd = denom + 14 - bd */
-        wofs = MODE == 2 ? 1 << (wsh - 1) : (ox + 1) << wsh;
+        wx0 = k.wx0; wx1 = k.wx1; ox = hevcmc_offset(k.ox, bd);
+        wsh = hevcmc_wshift(k.denom, bd);
         s2 = src2 + k.src2_offset;
     }
     const PIX *s = reinterpret_cast<const PIX *>(src + k.src_offset);
     int16_t *tmp = tmp_all[wave];
     int hf[TAPS], vf[TAPS];
-#pragma unroll
-    for (int t = 0; t < TAPS; t++) {
-        hf[t] = CHROMA ? hevc_cf4[mx][t] : hevc_lf8[mx][t];
-        vf[t] = CHROMA ? hevc_cf4[my][t] : hevc_lf8[my][t];
-    }
-    if (mx && my) {
+    hevcmc_taps_c<TAPS>(mx, my, hf, vf);
+    if (mx && my) { /* first pass over rows -BEFORE .. h + TAPS - 2 - BEFORE */
         for (int i = lane; i < w * (h + TAPS - 1); i += 64) {
             const int r = i / w, x = i - r * w;
             const PIX *p = s + (ptrdiff_t)(r - BEFORE) * sst + x - BEFORE;
@@ -304,7 +257,7 @@ __global__ __launch_bounds__(256) void k_hevc_mc_s(void *dst_, ptrdiff_t dststri
 #pragma unroll
             for (int t = 0; t < TAPS; t++)
                 acc += hf[t] * p[t];
-            tmp[r * 64 + x] = (int16_t)(acc >> sh1);
+            tmp[r * 64 + x] = (int16_t)hevcmc_first(acc, bd);
         }
         ffhip_wave_sync();
     }
@@ -313,38 +266,30 @@ __global__ __launch_bounds__(256) void k_hevc_mc_s(void *dst_, ptrdiff_t dststri
         const PIX *p = s + (ptrdiff_t)y * sst + x;
         int val;
         if (!mx && !my) {
-            val = p[0] << shu;
+            val = hevcmc_full(p[0], bd);
         } else if (!my) {
             val = 0;
 #pragma unroll
             for (int t = 0; t < TAPS; t++)
                 val += hf[t] * p[t - BEFORE];
-            val >>= sh1;
+            val = hevcmc_first(val, bd);
         } else if (!mx) {
             val = 0;
 #pragma unroll
             for (int t = 0; t < TAPS; t++)
                 val += vf[t] * p[(ptrdiff_t)(t - BEFORE) * sst];
-            val >>= sh1;
+            val = hevcmc_first(val, bd);
         } else {
-            int acc = 0;
+            val = 0;
 #pragma unroll
             for (int t = 0; t < TAPS; t++)
-                acc += vf[t] * tmp[(y + t) * 64 + x];
-            val = acc >> 6;
+                val += vf[t] * tmp[(y + t) * 64 + x];
+            val = hevcmc_second(val);
         }
         if constexpr (MODE >= 1) {
-            PIX *d = reinterpret_cast<PIX *>(static_cast<uint8_t *>(dst_) + k.dst_offset + (ptrdiff_t)y * dststride) + x;
-            int out;
-            if constexpr (UNI)
-                out = (!mx && !my) ? p[0] : (val + (1 << (shu - 1))) >> shu;
-            else if constexpr (MODE == 2)
-                out = ((val * wx0 + wofs) >> wsh) + ox;
-            else if constexpr (MODE == 3)
-                out = (val + s2[y * 64 + x] + (1 << shu)) >> (shu + 1);
-            else
-                out = (val * wx1 + s2[y * 64 + x] * wx0 + wofs) >> (wsh + 1);
-            *d = (PIX)min(max(out, 0), maxv);
+            const int v2 = MODE >= 3 ? s2[y * 64 + x] : 0;
+            reinterpret_cast<PIX *>(static_cast<uint8_t *>(dst_) + k.dst_offset + (ptrdiff_t)y * dststride)[x] =
+                (PIX)hevcmc_out(MODE, val, v2, wx0, wx1, ox, wsh, bd);
         } else {
             static_cast<int16_t *>(dst_)[(ptrdiff_t)k.dst_offset + y * 64 + x] = (int16_t)val;
         }
@@ -356,17 +301,11 @@ static void hevc_mc_launch(int mode, bool old, void *dst, ptrdiff_t dststride, c
                            const void *blocks, int n, hipStream_t stream)
 {
     const dim3 grid(cdiv(n, 4)), block(256);
-#define MC_CASE(M)                                                                                                                  \
-    case M:                                                                                                                         \
-        if (old) hipLaunchKernelGGL((k_hevc_mc_s<uint8_t, CHROMA, M>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n, 8); \
-        else     hipLaunchKernelGGL((k_hevc_mc<CHROMA, M>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n);   \
-        break;
-    switch (mode) {
-    MC_CASE(0) MC_CASE(1) MC_CASE(2) MC_CASE(3)
-    default:
-    MC_CASE(4)
-    }
-#undef MC_CASE
+    hevcmc_with_mode(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (old) hipLaunchKernelGGL((k_hevc_mc_s<uint8_t, CHROMA, M>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n, 8);
+        else     hipLaunchKernelGGL((k_hevc_mc<CHROMA, M>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n);
+    });
 }
 
 /* mode 0/1: blocks are FFHipHevcMcBlock, src2 unused; mode 2..4: FFHipHevcMcWBlock */
@@ -382,13 +321,9 @@ int ffhip_launch_hevc_mc(int chroma, int mode, void *dst, ptrdiff_t dststride, c
         /* luma: the 16 x 16 blocks on the matrix cores, everything else in a second launch that skips those */
         ffhip_launch_hevc_qpel_m(mode, dst, dststride, src, srcstride, src2, blocks, n, stream);
         const dim3 grid(min(cdiv(n, 64), 32768)), block(256); /* 64 records per wave and step; enough waves for a batch that is all other sizes */
-#define MC_SKIP(M) case M: hipLaunchKernelGGL((k_hevc_mc<false, M, true>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n); break;
-        switch (mode) {
-        MC_SKIP(0) MC_SKIP(1) MC_SKIP(2) MC_SKIP(3)
-        default:
-        MC_SKIP(4)
-        }
-#undef MC_SKIP
+        hevcmc_with_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL((k_hevc_mc<false, decltype(m)::value, true>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n);
+        });
         LAUNCH_CHECK();
         return 0;
     }
@@ -406,13 +341,9 @@ static void hevc_mc_launch16(int mode, int bd, void *dst, ptrdiff_t dststride, c
                              const void *blocks, int n, hipStream_t stream)
 {
     const dim3 grid(cdiv(n, 4)), block(256);
-#define MC_CASE(M) case M: hipLaunchKernelGGL((k_hevc_mc_s<uint16_t, CHROMA, M>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n, bd); break;
-    switch (mode) {
-    MC_CASE(0) MC_CASE(1) MC_CASE(2) MC_CASE(3)
-    default:
-    MC_CASE(4)
-    }
-#undef MC_CASE
+    hevcmc_with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((k_hevc_mc_s<uint16_t, CHROMA, decltype(m)::value>), grid, block, 0, stream, dst, dststride, src, srcstride, src2, blocks, n, bd);
+    });
 }
 
 int ffhip_launch_hevc_mc_bd(int bd, int chroma, int mode, void *dst, ptrdiff_t dststride, const uint8_t *src, ptrdiff_t srcstride,

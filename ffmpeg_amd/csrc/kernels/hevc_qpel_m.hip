@@ -27,17 +27,16 @@
 
 #include "common.h"
 #include "h264_kernels.h"
+#include "hevc_mc_rules.h"
 
 typedef int hq_i4 __attribute__((ext_vector_type(4)));
 typedef short hq_s2 __attribute__((ext_vector_type(2)));
 typedef uint32_t hq_u4 __attribute__((ext_vector_type(4)));
 
 struct HqTab { unsigned long long th[4][64], tv[4][64]; };
-constexpr int hq_tap(int f, int t)
-{
-    constexpr int c[4][8] = { { 0, 0, 0, 1, 0, 0, 0, 0 }, { -1, 4, -10, 58, 17, -5, 1, 0 }, { -1, 4, -11, 40, 40, -11, 4, -1 }, { 0, 1, -5, 17, 58, -10, 4, -1 } };
-    return (t < 0 || t > 7) ? 0 : c[f][t];
-}
+/* the luma taps of hevc_mc_rules.h, but fraction 0 is the shifted identity (1 at tap 3) that hands the raw samples through a product,
+ * not the rules' row of zeros */
+constexpr int hq_tap(int f, int t) { return f ? hevcmc_tap<8>(f, t) : t == 3; }
 constexpr HqTab hq_make()
 {
     HqTab t{};
@@ -122,8 +121,8 @@ __global__ __launch_bounds__(256) void k_hevc_qpel_m(void *dst_, ptrdiff_t dstst
         Gwx0[k] = Gwx1[k] = Gox[k] = Gwsh[k] = Gs2[k] = 0;
         if constexpr (MODE >= 2) {
             Gwx0[k] = __builtin_amdgcn_readfirstlane((int)rec.wx0); Gwx1[k] = __builtin_amdgcn_readfirstlane((int)rec.wx1);
-            Gox[k] = __builtin_amdgcn_readfirstlane((int)rec.ox);
-            Gwsh[k] = __builtin_amdgcn_readfirstlane((int)rec.denom) + 6; /* uni_w: shift = denom + 14 - 8;  bi_w: log2Wd = denom + 6 */
+            Gox[k] = hevcmc_offset(__builtin_amdgcn_readfirstlane((int)rec.ox), 8);
+            Gwsh[k] = hevcmc_wshift(__builtin_amdgcn_readfirstlane((int)rec.denom), 8);
             Gs2[k] = __builtin_amdgcn_readfirstlane(rec.src2_offset);
         }
         Gel[k] = b0 + k < n && w == 16 && h == 16;
@@ -147,14 +146,7 @@ __global__ __launch_bounds__(256) void k_hevc_qpel_m(void *dst_, ptrdiff_t dstst
         int o2[4] = { 0, 0, 0, 0 };
         if constexpr (MODE >= 3) {
             const int16_t *q = src2 + Gs2[k] + ry * 64 + 4 * rxg;
-            if (!(reinterpret_cast<uintptr_t>(q) & 7)) {
-                const uint2 v = *reinterpret_cast<const uint2 *>(q);
-                o2[0] = (int16_t)(v.x & 0xffff); o2[1] = (int)v.x >> 16; o2[2] = (int16_t)(v.y & 0xffff); o2[3] = (int)v.y >> 16;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    o2[j] = q[j];
-            }
+            hevcmc_ld4(q, !(reinterpret_cast<uintptr_t>(q) & 7), o2);
         }
         *reinterpret_cast<hq_u4 *>(raw + fr0 * 12 + 4 * fc0) = Gf0[k];
         if (lane < 5)
@@ -219,7 +211,7 @@ __global__ __launch_bounds__(256) void k_hevc_qpel_m(void *dst_, ptrdiff_t dstst
         if constexpr (MODE == 0) {
             int16_t *d = static_cast<int16_t *>(dst_) + Gdoff[k] + ry * 64 + 4 * rxg;
             if (!(reinterpret_cast<uintptr_t>(d) & 7)) {
-                *reinterpret_cast<uint2 *>(d) = make_uint2(((uint32_t)v[0] & 0xffffu) | ((uint32_t)v[1] << 16), ((uint32_t)v[2] & 0xffffu) | ((uint32_t)v[3] << 16));
+                *reinterpret_cast<uint2 *>(d) = make_uint2(hevcmc_pk16(v[0], v[1]), hevcmc_pk16(v[2], v[3]));
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; j++)
@@ -227,19 +219,11 @@ __global__ __launch_bounds__(256) void k_hevc_qpel_m(void *dst_, ptrdiff_t dstst
             }
         } else {
             if constexpr (MODE >= 2) {
-                const int wsh = Gwsh[k], wx0 = Gwx0[k], wx1 = Gwx1[k], ox = Gox[k];
-                const int wofs = MODE == 2 ? 1 << (wsh - 1) : (ox + 1) << wsh;
                 int r[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if constexpr (MODE == 2)
-                        r[j] = ((v[j] * wx0 + wofs) >> wsh) + ox;
-                    else if constexpr (MODE == 3)
-                        r[j] = (v[j] + o2[j] + 64) >> 7;
-                    else
-                        r[j] = (v[j] * wx1 + o2[j] * wx0 + wofs) >> (wsh + 1);
-                }
-                out = (uint32_t)clip_u8(r[0]) | (uint32_t)clip_u8(r[1]) << 8 | (uint32_t)clip_u8(r[2]) << 16 | (uint32_t)clip_u8(r[3]) << 24;
+                for (int j = 0; j < 4; j++)
+                    r[j] = clip_u8(hevcmc_stage(MODE, v[j], o2[j], Gwx0[k], Gwx1[k], Gox[k], Gwsh[k], 8));
+                out = (uint32_t)r[0] | (uint32_t)r[1] << 8 | (uint32_t)r[2] << 16 | (uint32_t)r[3] << 24;
             }
             if (tile) {
                 ob[64 * k + 4 * ry + rxg] = out;
@@ -273,11 +257,8 @@ void ffhip_launch_hevc_qpel_m(int mode, void *dst, ptrdiff_t dststride, const ui
     const int per_xcd = cdiv(cdiv(n, 16), 8);
     const char *ef = FFHIP_KNOB("FFHIP_HEVC_QM_FULL"); /* measured variant: 1 = every block loads its whole 23 x 23 footprint */
     const int full = ef && ef[0] == '1' ? 1 : 0;
-#define QM_CASE(M) case M: hipLaunchKernelGGL((k_hevc_qpel_m<M>), dim3(8 * per_xcd), dim3(256), 0, stream, dst, dststride, src, srcstride, src2, blocks, n, per_xcd, full); break;
-    switch (mode) {
-    QM_CASE(0) QM_CASE(1) QM_CASE(2) QM_CASE(3)
-    default:
-    QM_CASE(4)
-    }
-#undef QM_CASE
+    hevcmc_with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((k_hevc_qpel_m<decltype(m)::value>), dim3(8 * per_xcd), dim3(256), 0, stream, dst, dststride, src, srcstride, src2, blocks, n,
+                           per_xcd, full);
+    });
 }
