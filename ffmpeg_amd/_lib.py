@@ -208,6 +208,17 @@ def lib():
                                                         C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
         "ffhip_me_search_pred_sequence_host": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int,
                                                          C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+        # the predictive faces' arguments without cost_kind (and, for the sequence, without direction)
+        "ffhip_me_search_bilat_batch_dev": (C.c_int, [C.c_int, vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_int,
+                                                      C.c_int, vp, vp, vp, vp, vp]),
+        "ffhip_me_search_bilat_frames_host": (C.c_int, [C.c_int, vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_int,
+                                                        C.c_int, vp, vp, vp, vp]),
+        "ffhip_me_search_bilat_cost_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, vp]),
+        "ffhip_me_search_bilat_sequence_dev": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int,
+                                                         C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+        "ffhip_me_search_bilat_sequence_host": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int,
+                                                          C.c_int, C.c_int, vp, vp, vp, vp]),
         # src, dst: FFHipMePlanes *; jobs: FFHipMeInterpJob * (ffmpeg_amd/me.py has the structures)
         "ffhip_me_interp_sequence_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                    vp, vp, vp, vp, C.c_int, vp]),
@@ -220,6 +231,11 @@ def lib():
                                                        vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]),
         "ffhip_me_interp_sequence_scd_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                         vp, vp, vp, vp, C.c_int, vp, C.c_int]),
+        # the scd faces' arguments with one field mv for mv_fwd / mv_bwd
+        "ffhip_me_interp_bilat_sequence_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                         vp, vp, vp, C.c_int, vp, C.c_int, vp]),
+        "ffhip_me_interp_bilat_sequence_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                          vp, vp, vp, C.c_int, vp, C.c_int]),
         # frames, depth, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, threshold, mafd_in, mafd_out, sad_out, score_out, flags_out
         "ffhip_me_scene_sequence_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_double,
                                                   vp, vp, vp, vp, vp, vp]),

@@ -15,6 +15,8 @@
  *      the set bits from the lowest, which is the reference's order.  A survivor's window travels by v_readlane, so everything about
  *      it is scalar.
  *   3. Per lane mei_contribute(): the window weight from LDS, the cap, the displacement clips, two bytes gathered per plane.
+ * k_me_interp_bilat<MB, SCD> (the BILAT instance) serves ffhip_me_interp_bilat_sequence_dev(): steps 1 and 2 fall away — a lane reads
+ * the vectors of the at most four blocks whose unshifted windows hold its pixel and runs step 3 on them (mei_walk_bilat()).
  * There is no wait between workgroups, no atomic and no hand-off.  Every read is inside its plane: fields are read at blocks of
  * [0, b_w) x [0, b_h) only, and the displacement clips keep x + dx in [0, W - 1], y + dy in [0, H - 1] (chroma: see mei_site()).
  *
@@ -48,8 +50,11 @@ struct MeiParams {
     int scene_action;
 };
 
-/* SCD: the launch has scene flags (ffhip_me_interp_sequence_scd_dev() with a non-NULL scene); without them the kernel is the one it was */
-template <int MB, bool SCD>
+/* SCD: the launch has scene flags (ffhip_me_interp_sequence_scd_dev() with a non-NULL scene); without them the kernel is the one it was.
+ * BILAT: the bilateral compensation of ffhip_me_interp_bilat_sequence_dev() (k_me_interp_bilat below): one field, P.mvf, of
+ * half-vectors; a pixel computes the indices of the at most four blocks whose unshifted windows hold it instead of walking a staged
+ * candidate list — no candidates in LDS, no ballot.  Tiles, planes, the streaming branch and the sums are the same code. */
+template <int MB, bool SCD, bool BILAT = false>
 __global__ __launch_bounds__(256) void k_me_interp(const MeiParams P, const uint8_t *__restrict__ table)
 {
     constexpr int WIN = 4 * MB * MB;
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(256) void k_me_interp(const MeiParams P, const uint
     /* ---- 1. the table and the candidates' vectors ---- */
     for (int i = tid; i < WIN / 4; i += 256)
         mei_lds[i] = reinterpret_cast<const int *>(table)[i];
-    {
+    if (!BILAT) {
         const size_t field = 2 * (size_t)g.bw * g.bh * ((size_t)job.pair * P.nseq + job.seq);
         for (int c = tid; c < ncand; c += 256) {
             const int dir = c >= nper, rr = c - dir * nper, cy = rr / ncx, bx = r.bx0 + rr - cy * ncx, by = r.by0 + cy;
@@ -135,6 +140,23 @@ __global__ __launch_bounds__(256) void k_me_interp(const MeiParams P, const uint
             S2 += (uint32_t)wa * a2[ya * s2 + xa] + (uint32_t)wb * b2[yb * s2 + xb];
         }
     };
+    if (BILAT) {
+        /* the four blocks in (by, bx) order, their vectors straight from the field: entries of [0, b_w) x [0, b_h) only */
+        if (!valid)
+            return;
+        const int16_t *const field = P.mvf + 2 * (size_t)g.bw * g.bh * ((size_t)job.pair * P.nseq + job.seq);
+        mei_walk_bilat(g, alpha, x, y, win, [&](int bx, int by) {
+            const int16_t *e = field + 2 * ((size_t)by * g.bw + bx);
+            int vx, vy;
+            return mei_vector(g, bx, by, e[0], e[1], vx, vy) ? mei_block_bilat(g, bx, by, vx, vy) : mei_no_block();
+        }, take, nullptr);
+        D[0][(ptrdiff_t)y * P.dstride[0] + x] = (uint8_t)mei_sample(S, Wt);
+        if (site) {
+            D[1][((ptrdiff_t)(y >> sh)) * P.dstride[1] + (x >> sw)] = (uint8_t)mei_sample(S1, Wt);
+            D[2][((ptrdiff_t)(y >> sh)) * P.dstride[2] + (x >> sw)] = (uint8_t)mei_sample(S2, Wt);
+        }
+        return;
+    }
     const int wx1 = min(wx0 + MEI_WW, P.W), wy1 = min(py0 + MEI_TH, P.H);
     for (int c0 = 0; c0 < ncand; c0 += 64) {
         const int c = c0 + lane;
@@ -185,9 +207,34 @@ int ffhip_launch_me_interp(const FFHipMePlanes *src, const FFHipMePlanes *dst, i
                                       jobs, njobs, nullptr, FFHIP_ME_SCENE_BLEND, stream);
 }
 
+/* the bilateral compensation kernel: k_me_interp with the four-block walk */
+template <int MB, bool SCD>
+static constexpr auto k_me_interp_bilat = k_me_interp<MB, SCD, true>;
+
+/* every face's launcher.  bilat: mv_fwd is the one field of half-vectors, mv_bwd is not looked at */
+static int me_interp_launch(bool bilat, const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
+                            int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
+                            const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream);
+
 int ffhip_launch_me_interp_scd(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
                                int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
                                const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream)
+{
+    return me_interp_launch(false, src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd, jobs,
+                            njobs, scene, scene_action, stream);
+}
+
+int ffhip_launch_me_interp_bilat(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
+                                 int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv,
+                                 const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream)
+{
+    return me_interp_launch(true, src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv, nullptr, jobs,
+                            njobs, scene, scene_action, stream);
+}
+
+static int me_interp_launch(bool bilat, const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
+                            int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
+                            const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream)
 {
     if (width <= 0 || height <= 0 || njobs <= 0)
         return 0;
@@ -216,7 +263,8 @@ int ffhip_launch_me_interp_scd(const FFHipMePlanes *src, const FFHipMePlanes *ds
     const unsigned tiles = (unsigned)P.tiles_x * (unsigned)cdiv(height, MEI_TH);      /* at most 512 * 8192 */
     const MeiGeom g = mei_geom(width, height, mb_size, mv_range);
     const int ncx = std::min(mei_max_candidates(g, MEI_TW), g.bw), ncy = std::min(mei_max_candidates(g, MEI_TH), g.bh);
-    const size_t lds = (size_t)4 * mb_size * mb_size + (size_t)8 * ncx * ncy;         /* 39 KB at mb 8, mv_range 256; 1.6 KB at the defaults */
+    /* 39 KB at mb 8, mv_range 256; 1.6 KB at the defaults; the bilateral kernel stages the window table alone */
+    const size_t lds = (size_t)4 * mb_size * mb_size + (bilat ? 0 : (size_t)8 * ncx * ncy);
     if (lds > 64 * 1024) {
         ffhip_set_error("ffhip_me_interp_sequence_dev: %zu bytes of LDS for the candidates of a tile", lds);
         return FFHIP_EINVAL;
@@ -233,8 +281,17 @@ int ffhip_launch_me_interp_scd(const FFHipMePlanes *src, const FFHipMePlanes *ds
         memcpy(S.img(0), window, (size_t)4 * mb_size * mb_size);
         S.put(jobs + j0, (size_t)n * sizeof(FFHipMeInterpJob), MEI_TABLE_WINDOW);
         P.job0 = j0;
-        const int r = ffhip_progress_launch_table(stream, "ffhip_me_interp_sequence_dev: copy or launch", S.img(0), S.n, [&](uint8_t *table) {
-            if (mb_size == 16 && scene)
+        const char *const what = bilat ? "ffhip_me_interp_bilat_sequence_dev: copy or launch" : "ffhip_me_interp_sequence_dev: copy or launch";
+        const int r = ffhip_progress_launch_table(stream, what, S.img(0), S.n, [&](uint8_t *table) {
+            if (bilat && mb_size == 16 && scene)
+                hipLaunchKernelGGL((k_me_interp_bilat<16, true>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+            else if (bilat && mb_size == 16)
+                hipLaunchKernelGGL((k_me_interp_bilat<16, false>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+            else if (bilat && scene)
+                hipLaunchKernelGGL((k_me_interp_bilat<8, true>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+            else if (bilat)
+                hipLaunchKernelGGL((k_me_interp_bilat<8, false>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
+            else if (mb_size == 16 && scene)
                 hipLaunchKernelGGL((k_me_interp<16, true>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);
             else if (mb_size == 16)
                 hipLaunchKernelGGL((k_me_interp<16, false>), dim3(tiles, (unsigned)n), dim3(256), lds, stream, P, table);

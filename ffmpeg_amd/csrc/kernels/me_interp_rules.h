@@ -11,6 +11,8 @@
  *   - mei_candidates(): the block rectangle that can reach a pixel rectangle under mv_range;
  *   - mei_contribute(): what one block adds to one pixel (steps 3 - 5), and mei_walk(), the ordered walk of one pixel with the
  *     empty-list fallback.
+ *   - mei_block_bilat(), mei_walk_bilat(): the same for the bilateral compensation of ffhip_me_interp_bilat_sequence_dev(), whose one
+ *     field of half-vectors does not shift the windows: at most four blocks at computed indices reach a pixel.
  * It does not own where a sample comes from: take(wa, dxa, dya, wb, dxb, dyb) is the caller's and receives one contribution, the
  * weight and the clipped displacement of its entry in picture A and of its entry in picture B.  ffhip_me_interp_sequence_host()
  * (me_api.hip) is mei_walk() in a plain loop over samples; k_me_interp (me_interp.hip) sorts the candidates of a wave out with a
@@ -88,6 +90,22 @@ MES_FN MeiBlock mei_block(const MeiGeom &g, int alpha, int dir, int bx, int by, 
     return b;
 }
 
+/* The bilateral compensation (me_mode=bilat: the filter's bilateral_obmc, as include/ffhip.h states it for
+ * ffhip_me_interp_bilat_sequence_dev()) takes ONE field of half-vectors.  A well-formed block's window is not shifted by its vector,
+ * and its contribution is step 5 of the rule above read with m = 2 * v: the block is given to mei_contribute() as a direction-0 block
+ * whose vector is m.  Windows of 2 mb stand mb apart, so at most two blocks per axis, four in all, reach a pixel — mei_bilat_first()
+ * and the one after it per axis — and the cap of MEI_CAP never binds. */
+MES_FN MeiBlock mei_block_bilat(const MeiGeom &g, int bx, int by, int vx, int vy)
+{
+    MeiBlock b = mei_block(g, 0, 0, bx, by, 0, 0);      /* no displacement: sx = (bx << lg) - mb / 2 */
+    b.vx = 2 * vx;
+    b.vy = 2 * vy;
+    return b;
+}
+/* the first of the two block columns (rows) whose unshifted window [b * mb - mb / 2, b * mb + 3 * mb / 2) holds column (row) x; it
+ * may be -1, and the second may be b_w (b_h): neither is a block then */
+MES_FN int mei_bilat_first(const MeiGeom &g, int x) { return ((x + g.mb / 2) >> g.lg) - 1; }
+
 /* The blocks [bx0, bx1) x [by0, by1) that can reach a pixel of [px0, px1) x [py0, py1).  |tdiv(v * a)| <= mv_range, so block bx covers
  * only columns of [bx * mb - mb / 2 - range, bx * mb + 3 * mb / 2 + range): it reaches the rectangle only if
  * bx * mb <= px1 - 1 + mb / 2 + range and bx * mb > px0 - 3 * mb / 2 - range.  (>> of a negative int floors.) */
@@ -150,6 +168,25 @@ MES_FN int mei_walk(const MeiGeom &g, int alpha, int x, int y, const uint8_t *wi
         for (int by = r.by0; by < r.by1; by++)
             for (int bx = r.bx0; bx < r.bx1; bx++)
                 mei_contribute(g, alpha, block(dir, bx, by), dir, x, y, window, n, take, cnt);
+    if (!n) {
+        if (cnt)
+            cnt[MEI_N_FALLBACK]++;
+        take(1024 - alpha, 0, 0, alpha, 0, 0);
+    }
+    return n;
+}
+
+/* The bilateral walk of luma pixel (x, y): the at most four blocks in (by, bx) order, then the fallback.  block(bx, by) gives the
+ * block's window (mei_block_bilat()), mei_no_block() for a malformed one. */
+template <class Block, class Take>
+MES_FN int mei_walk_bilat(const MeiGeom &g, int alpha, int x, int y, const uint8_t *window, Block &&block, Take &&take, uint64_t *cnt)
+{
+    const int bx0 = mei_bilat_first(g, x), by0 = mei_bilat_first(g, y);
+    int n = 0;
+    for (int by = by0; by < by0 + 2; by++)
+        for (int bx = bx0; bx < bx0 + 2; bx++)
+            if (bx >= 0 && bx < g.bw && by >= 0 && by < g.bh)
+                mei_contribute(g, alpha, block(bx, by), 0, x, y, window, n, take, cnt);
     if (!n) {
         if (cnt)
             cnt[MEI_N_FALLBACK]++;

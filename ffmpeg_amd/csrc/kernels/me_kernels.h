@@ -17,6 +17,9 @@ int ffhip_launch_me_esa_satd_mx(const uint8_t *cur, const uint8_t *ref, int widt
 /* the per-block fast searches (me_search.hip): method FFHIP_ME_METHOD_TSS .. _HEXBS, nblocks = b_w * b_h * nframes > 0 */
 int ffhip_launch_me_search(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
                            int nframes, int mb_size, int R, int cost_kind, int16_t *mv_out, uint32_t *cost_out, hipStream_t stream);
+/* cost_kind of the bilateral cost (me_search_bilat_rules.h) for the two predictive launchers below, beside FFHIP_ME_SAD and
+ * FFHIP_ME_SATD: picture A is `cur`, picture B `ref`.  Internal: the public faces of the bilateral search have no cost_kind. */
+#define MES_COST_BILAT 2
 /* the predictive searches (me_search_pred.hip): method FFHIP_ME_METHOD_EPZS or _UMH, prev1 / prev2 NULL or fields laid out as mv_out,
  * mv_out 4-byte aligned; calls of more block rows than a progress-pool slot counts are split by pairs */
 int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
@@ -37,6 +40,10 @@ int ffhip_launch_me_interp(const FFHipMePlanes *src, const FFHipMePlanes *dst, i
 int ffhip_launch_me_interp_scd(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
                                int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
                                const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream);
+/* the bilateral compensation (me_interp.hip, k_me_interp_bilat): one field `mv` of half-vectors, otherwise as the launcher above */
+int ffhip_launch_me_interp_bilat(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width,
+                                 int height, int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv,
+                                 const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action, hipStream_t stream);
 /* vf_minterpolate's scene-change detection (me_scene.hip): arguments checked, every pointer on the device; calls of more pairs than a
  * launch's sums hold are split in stream order */
 int ffhip_launch_me_scene(const uint8_t *frames, int depth, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes, size_t seq_pitch,

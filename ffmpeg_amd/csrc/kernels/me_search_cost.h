@@ -4,8 +4,9 @@
  * the candidate's byte-exact address in `ref`, against the current block's rows in registers.  SAD: v_sad_u8 over the dwords.  SATD: the
  * horizontal 8-point transform of a row's differences in the lane, the vertical one across the eight lanes of the candidate, then the
  * absolute sum.  The eight partial sums are added with DPP moves, the butterfly across lanes r and r ^ 4 is a ds_swizzle: no LDS.
- * With it what else the two kernels share: the load of the current block, the wave minimum of a step's keys, and the launchers' choice of
- * a (block size, metric) instantiation.  For the two kernel files only.
+ * With it what else the kernels share: the load of the current block, the wave minimum of a step's keys, and the launchers' choice of
+ * a (block size, metric) instantiation; and, for the predictive kernels (me_search_pred.hip, me_search_seq.hip), the bilateral cost
+ * mes_cost_bilat() and the cost policies they are instantiated with.  For the kernel files only.
  */
 #ifndef FFHIP_ME_SEARCH_COST_H
 #define FFHIP_ME_SEARCH_COST_H
@@ -15,6 +16,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "me_kernels.h"
+#include "me_search_bilat_rules.h"
 
 #define MES_DPP_XOR1 0xB1           /* quad_perm:[1,0,3,2] */
 #define MES_DPP_XOR2 0x4E           /* quad_perm:[2,3,0,1] */
@@ -107,6 +110,31 @@ __device__ __forceinline__ uint32_t mes_cost(const uint32_t (&c)[MB / 8][MB / 4]
     return mes_sum8(part);
 }
 
+/* The bilateral cost's sum (me_search_bilat_rules.h: the filter's get_sbad_ob) of the lane's candidate, summed over its eight lanes:
+ * |A - B| over the two windows of 2 MB x 2 MB samples whose top-left samples `at` names.  Lane l & 7 takes rows l & 7, + 8, ... of the
+ * windows (4 at MB 16, 2 at MB 8), each 2 MB bytes of A and of B at their byte-exact addresses, loaded as mes_cost() loads; a row's
+ * dwords go through v_sad_u8 before the next row's are needed, so only the rows in flight hold registers.  valid false: no load. */
+template <int MB>
+__device__ __forceinline__ uint32_t mes_cost_bilat(const uint8_t *a, const uint8_t *b, ptrdiff_t stride, bool valid, const MesbPlace &at, int lane)
+{
+    constexpr int NR = MB / 4, ND = MB / 2;
+    uint32_t part = 0;
+    if (valid) {
+        const uint8_t *pa = a + (ptrdiff_t)(at.ay + (lane & 7)) * stride + at.ax;
+        const uint8_t *pb = b + (ptrdiff_t)(at.by + (lane & 7)) * stride + at.bx;
+#pragma unroll
+        for (int k = 0; k < NR; k++) {
+            uint32_t va[ND], vb[ND];
+            __builtin_memcpy(va, pa + (ptrdiff_t)(8 * k) * stride, 2 * MB);
+            __builtin_memcpy(vb, pb + (ptrdiff_t)(8 * k) * stride, 2 * MB);
+#pragma unroll
+            for (int j = 0; j < ND; j++)
+                part = __builtin_amdgcn_sad_u8(va[j], vb[j], part);
+        }
+    }
+    return mes_sum8(part);
+}
+
 /* the lane's rows of the current block at (x_mb, y_mb) of the frame `cf`: what mes_cost() takes as c */
 template <int MB>
 __device__ __forceinline__ void mes_load_cur(uint32_t (&c)[MB / 8][MB / 4], const uint8_t *cf, ptrdiff_t stride, int x_mb, int y_mb, int lane)
@@ -116,6 +144,62 @@ __device__ __forceinline__ void mes_load_cur(uint32_t (&c)[MB / 8][MB / 4], cons
     for (int k = 0; k < MB / 8; k++)
         __builtin_memcpy(c[k], p + (ptrdiff_t)(8 * k) * stride, MB);
 }
+
+/* ---- a block's cost as the predictive kernels (me_search_pred.hip, me_search_seq.hip) take it: a policy per (MB, KIND) --------------
+ * load(): what the block needs before its first cost, issued with the block's other loads; set_window(): the block's window.  sum(): the part of cost(x, y) that needs
+ * nothing of the row above, over the candidate's eight lanes.  penalty(): the part that needs the block's median predictor (set_pred),
+ * added by the kernel once the row above has arrived; zero for the two block metrics, whose cost is sum() alone. */
+template <int MB, int KIND>
+struct MesCostPolicy {
+    uint32_t c[MB / 8][MB / 4];
+    const uint8_t *rf;
+    ptrdiff_t stride;
+    __device__ __forceinline__ void load(const uint8_t *cf, const uint8_t *ref, ptrdiff_t st, int x_mb, int y_mb, int lane)
+    {
+        rf = ref;
+        stride = st;
+        uint32_t t[MB / 8][MB / 4];
+        mes_load_cur<MB>(t, cf, st, x_mb, y_mb, lane);
+#pragma unroll
+        for (int k = 0; k < MB / 8; k++)
+#pragma unroll
+            for (int j = 0; j < MB / 4; j++)
+                c[k][j] = t[k][j];
+    }
+    __device__ __forceinline__ void set_window(const MesWindow &) {}
+    __device__ __forceinline__ void set_pred(int, int) {}
+    __device__ __forceinline__ uint32_t sum(bool valid, int x, int y, int lane) const { return mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane); }
+    __device__ __forceinline__ uint32_t penalty(int, int) const { return 0; }
+};
+
+template <int MB>
+struct MesCostPolicy<MB, MES_COST_BILAT> {
+    const uint8_t *a, *b;
+    ptrdiff_t stride;
+    int x_mb, y_mb, pred_x, pred_y;
+    MesWindow w;
+    __device__ __forceinline__ void load(const uint8_t *cf, const uint8_t *ref, ptrdiff_t st, int x, int y, int)
+    {
+        a = cf;
+        b = ref;
+        stride = st;
+        x_mb = x;
+        y_mb = y;
+    }
+    /* the block's window: the placement clamps against it */
+    __device__ __forceinline__ void set_window(const MesWindow &win) { w = win; }
+    /* the block's median predictor */
+    __device__ __forceinline__ void set_pred(int px, int py)
+    {
+        pred_x = px;
+        pred_y = py;
+    }
+    __device__ __forceinline__ uint32_t sum(bool valid, int x, int y, int lane) const
+    {
+        return mes_cost_bilat<MB>(a, b, stride, valid, mesb_place(w, x_mb, y_mb, MB, x, y), lane);
+    }
+    __device__ __forceinline__ uint32_t penalty(int x, int y) const { return mesb_penalty(x, y, x_mb, y_mb, pred_x, pred_y); }
+};
 
 /* the minimum of a key that is uniform over each candidate's eight lanes, in scalar registers: one DPP row rotate, four v_readlane */
 __device__ __forceinline__ uint32_t mes_wave_min(uint32_t key)
@@ -139,6 +223,19 @@ static inline void mes_dispatch(int mb_size, int cost_kind, Launch launch)
     } else {
         if (mb_size == 16) launch(Mb16(), Satd()); else launch(Mb8(), Satd());
     }
+}
+
+/* the same for the predictive kernels, which have the bilateral cost as a third kind */
+template <class Launch>
+static inline void mes_dispatch_pred(int mb_size, int cost_kind, Launch launch)
+{
+    using Bilat = std::integral_constant<int, MES_COST_BILAT>;
+    if (cost_kind != MES_COST_BILAT)
+        mes_dispatch(mb_size, cost_kind, launch);
+    else if (mb_size == 16)
+        launch(std::integral_constant<int, 16>(), Bilat());
+    else
+        launch(std::integral_constant<int, 8>(), Bilat());
 }
 
 #endif

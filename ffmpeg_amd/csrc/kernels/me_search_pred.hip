@@ -18,6 +18,9 @@
  *     neighbours — eight candidates, one pass — are evaluated BEFORE the wait, with the current block's loads; the median, top and
  *     top-right follow the wait in a second pass, and the ordered minimum over both carries the list position (the rules header's
  *     mesp_advance_list).  Running the list in order behind the wait, two steps, was measured 14 to 19 % slower and taken out.
+ *   - the cost is a policy (MesCostPolicy<MB, KIND>, me_search_cost.h): the two block metrics, and KIND MES_COST_BILAT, the bilateral
+ *     cost of ffhip_me_search_bilat_batch_dev() (cur = picture A, ref = picture B).  Its penalty needs the block's median predictor,
+ *     hence the row above: the early pass computes its candidates' sums before the wait and their penalties join the keys after it.
  * A lost hand-off sets the slot's fail word and the kernel leaves (ffhip_progress_check reports it).  No LDS, no scratch; every loop is
  * bounded by the rules header's step bound and the hand-off's spin limit.
  */
@@ -53,12 +56,12 @@ __device__ __forceinline__ MespVec mesp_row_rel(const int16_t *mv_out, size_t b,
 }
 } // namespace
 
-template <int MB, int KIND>
+template <int MB, int KIND, bool EARLY = true>
 __global__ __launch_bounds__(64) void k_me_search_pred(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
                                                        size_t frame_pitch, int npairs, int R, const int16_t *prev1, const int16_t *prev2,
                                                        int16_t *mv_out, uint32_t *cost_out, int *progress_all, int *fail)
 {
-    constexpr int LOG2 = MB == 16 ? 4 : 3, NR = MB / 8;
+    constexpr int LOG2 = MB == 16 ? 4 : 3;
     const int bw = width >> LOG2, bh = height >> LOG2;
     const size_t per = (size_t)bw * (size_t)bh;                          /* blocks of a frame */
     const int lane = (int)threadIdx.x, cand = lane >> 3;
@@ -85,24 +88,28 @@ __global__ __launch_bounds__(64) void k_me_search_pred(int method, const uint8_t
             const size_t b = rb + (size_t)bx;
             const MespNeigh N = mesp_neighbours(method, bx, row, bw, bh);
             /* ---- what needs nothing of the row above: the current block, the prev fields ---- */
-            uint32_t c[NR][MB / 4];
-            mes_load_cur<MB>(c, cf, stride, x_mb, y_mb, lane);
+            MesCostPolicy<MB, KIND> cost;
+            cost.load(cf, rf, stride, x_mb, y_mb, lane);
             MespNear v = {};
             v.left = left;
             mesp_fetch_prev(v, N, [&](int which, int dbx, int dby) {
                 return mesp_prev_rel(which == 1 ? prev1 : prev2, b + (ptrdiff_t)dby * bw + dbx, bx + dbx, row + dby, LOG2);
             });
             const MesWindow w = mes_window(x_mb, y_mb, R, bw, bh, LOG2);
+            cost.set_window(w);
             MespState s = mesp_start(method, x_mb, y_mb, R);
             uint32_t key_early = MES_NO_KEY;
-            if (epzs) {
+            int x_early = 0, y_early = 0;                     /* the early candidate of the lane's group */
+            if (epzs && EARLY) {
                 /* list positions zero, left, collocated, accelerator, prev1's left, top, right, bottom: one per candidate group */
                 const int k = (int)(0xA9876521u >> (4 * cand)) & 15;
                 const MespPred P = mesp_predictors(N, v);
                 int x, y;
                 const bool valid = mesp_candidate(s, w, P, k, x, y);
-                const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-                key_early = valid ? mesp_list_key(cost, k) : MES_NO_KEY;
+                const uint32_t c = cost.sum(valid, x, y, lane);
+                key_early = valid ? mesp_list_key(c, k) : MES_NO_KEY;
+                x_early = x;
+                y_early = y;
             }
             /* ---- the row above has published min(bx + 2, b_w) blocks: its vectors ---- */
             if (mesp_has(N, MESP_TOP)) {
@@ -112,20 +119,24 @@ __global__ __launch_bounds__(64) void k_me_search_pred(int method, const uint8_t
                 mesp_fetch_above(v, N, [&](int dbx) { return mesp_row_rel(mv_out, b - (size_t)bw + dbx, bx + dbx, row - 1, LOG2); });
             }
             const MespPred P = mesp_predictors(N, v);
-            if (epzs) {
+            cost.set_pred(P.median.x, P.median.y);
+            if (epzs && EARLY) {
                 /* the median, top, top-right: the rest of the list */
                 const int k = cand == 0 ? MESP_MEDIAN : cand == 1 ? MESP_TOP : cand == 2 ? MESP_DIAG : -1;
                 int x, y;
                 const bool valid = mesp_candidate(s, w, P, k, x, y);
-                const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-                const uint32_t key = valid ? mesp_list_key(cost, k) : MES_NO_KEY;
+                const uint32_t c = cost.sum(valid, x, y, lane) + cost.penalty(x, y);
+                const uint32_t key = valid ? mesp_list_key(c, k) : MES_NO_KEY;
+                /* the early pass's sums take their penalty now that the median is known */
+                key_early = mesp_list_key_add(key_early, cost.penalty(x_early, y_early));
                 mesp_advance_list(s, w, P, mes_wave_min(min(key, key_early)));
             }
+            /* EARLY false (a measured variant): the whole list in order behind the wait, two steps of mesp_run() below */
             mesp_run(s, w, P, [&](const MespState &s) {
                 int x, y;
                 const bool valid = mesp_candidate(s, w, P, s.pos + cand, x, y);
-                const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-                return mes_wave_min(valid ? mes_key(cost, cand) : MES_NO_KEY);
+                const uint32_t c = cost.sum(valid, x, y, lane) + cost.penalty(x, y);
+                return mes_wave_min(valid ? mes_key(c, cand) : MES_NO_KEY);
             });
             /* ---- the block's vector: to the row below, and to the next block of this row ---- */
             if (lane == 0) {
@@ -148,8 +159,11 @@ int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *r
         return 0;
     /* a launch's counters (one per block row and pair) and its ticket fit one progress slot: larger calls are split by pairs */
     const int per = (FFHIP_PROGRESS_SLOT_INTS - 1) / bh;
+    const bool bilat = cost_kind == MES_COST_BILAT;
+    const char *const who = bilat ? "ffhip_me_search_bilat_batch_dev" : "ffhip_me_search_pred_batch_dev";
+    const char *const what = bilat ? "ffhip_me_search_bilat_batch_dev: kernel launch" : "ffhip_me_search_pred_batch_dev: kernel launch";
     if (per < 1) {
-        ffhip_set_error("ffhip_me_search_pred_batch_dev: %d block rows exceed a progress-pool slot", bh);
+        ffhip_set_error("%s: %d block rows exceed a progress-pool slot", who, bh);
         return FFHIP_EINVAL;
     }
     /* FFHIP_ME_PRED_WGS (measurement build) fixes the number of workgroups, so that a small picture takes several ticket rounds */
@@ -161,9 +175,9 @@ int ffhip_launch_me_search_pred(int method, const uint8_t *cur, const uint8_t *r
         const int16_t *q1 = prev1 ? prev1 + 2 * blocks * (size_t)p0 : nullptr, *q2 = prev2 ? prev2 + 2 * blocks * (size_t)p0 : nullptr;
         int16_t *mv0 = mv_out + 2 * blocks * (size_t)p0;
         uint32_t *k0 = cost_out + blocks * (size_t)p0;
-        const int r = ffhip_progress_launch(units + 1, stream, "ffhip_me_search_pred_batch_dev: kernel launch", [&](const FFHipProgressSlot &ps) {
+        const int r = ffhip_progress_launch(units + 1, stream, what, [&](const FFHipProgressSlot &ps) {
             const int grid = units < cap ? units : cap;
-            mes_dispatch(mb_size, cost_kind, [&](auto mb, auto kind) {
+            mes_dispatch_pred(mb_size, cost_kind, [&](auto mb, auto kind) {
                 hipLaunchKernelGGL((k_me_search_pred<decltype(mb)::value, decltype(kind)::value>), dim3((unsigned)grid), dim3(64), 0, stream, method,
                                    c0, r0, width, height, stride, frame_pitch, n, R, q1, q2, mv0, k0, ps.prog, ps.fail);
             });

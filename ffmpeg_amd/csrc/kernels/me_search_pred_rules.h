@@ -381,6 +381,8 @@ MES_FN void mesp_run(MespState &s, const MesWindow &w, const MespPred &P, StepKe
 /* A whole list of at most 16 entries at once (the predictors): the minimum of mesp_list_key(cost, k) over the entries k evaluated,
  * in any order.  Equals the steps of 8 in order. */
 MES_FN uint32_t mesp_list_key(uint32_t cost, int k) { return cost << 4 | (uint32_t)k; }
+/* the key of cost + extra from the key of cost, for a cost whose second part is known later; MES_NO_KEY stays */
+MES_FN uint32_t mesp_list_key_add(uint32_t key, uint32_t extra) { return key == MES_NO_KEY ? key : key + (extra << 4); }
 MES_FN void mesp_advance_list(MespState &s, const MesWindow &w, const MespPred &P, uint32_t key)
 {
     if (key != MES_NO_KEY && (key >> 4) < s.cost_min) {

@@ -18,6 +18,7 @@
  *     vector is stored with ffhip_row_st before the publish; init1 / init2 and the fields of an earlier launch are read plainly.  Which
  *     it is is decided per unit in scalar code.
  * UMH reads no prev field: its pairs are independent and run unchained in the same launches.
+ * The cost is k_me_search_pred's policy; with KIND MES_COST_BILAT and direction 1 this is ffhip_me_search_bilat_sequence_dev().
  * A lost hand-off sets the slot's fail word and the kernel leaves (ffhip_progress_check reports it).  No LDS, no scratch; every loop is
  * bounded by the rules header's step bound and the hand-off's spin limit.
  */
@@ -58,13 +59,13 @@ __device__ __forceinline__ MespVec mesq_field_rel(const int16_t *field, bool liv
 
 /* pairs k0 .. k0 + nk - 1 of the sequences s0 .. s0 + ns - 1 of a call over nseq sequences; `frames`, `init1`, `init2`, `mv_out` and
  * `cost_out` are the call's */
-template <int MB, int KIND>
+template <int MB, int KIND, bool EARLY = true>
 __global__ __launch_bounds__(64) void k_me_search_seq(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
                                                       size_t seq_pitch, int direction, int R, int k0, int nk, int s0, int ns, int nseq,
                                                       const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out,
                                                       int *progress_all, int *fail)
 {
-    constexpr int LOG2 = MB == 16 ? 4 : 3, NR = MB / 8;
+    constexpr int LOG2 = MB == 16 ? 4 : 3;
     const int bw = width >> LOG2, bh = height >> LOG2;
     const size_t per = (size_t)bw * (size_t)bh;                          /* blocks of a field */
     const int lane = (int)threadIdx.x, cand = lane >> 3;
@@ -100,8 +101,8 @@ __global__ __launch_bounds__(64) void k_me_search_seq(int method, const uint8_t 
             const int x_mb = bx << LOG2;
             const size_t b = rb + (size_t)bx;
             const MespNeigh N = mesp_neighbours(method, bx, row, bw, bh);
-            uint32_t c[NR][MB / 4];
-            mes_load_cur<MB>(c, cf, stride, x_mb, y_mb, lane);
+            MesCostPolicy<MB, KIND> cost;
+            cost.load(cf, rf, stride, x_mb, y_mb, lane);
             /* ---- pair k - 1 has searched what this block reads of it ---- */
             if (chained) {
                 const int want = last ? min(bx + 2, bw) : bx + 1;
@@ -114,16 +115,20 @@ __global__ __launch_bounds__(64) void k_me_search_seq(int method, const uint8_t 
                 return mesq_field_rel(which == 1 ? p1 : p2, which == 1 ? live1 : live2, b + (ptrdiff_t)dby * bw + dbx, bx + dbx, row + dby, LOG2);
             });
             const MesWindow w = mes_window(x_mb, y_mb, R, bw, bh, LOG2);
+            cost.set_window(w);
             MespState st = mesp_start(method, x_mb, y_mb, R);
             uint32_t key_early = MES_NO_KEY;
-            if (epzs) {
+            int x_early = 0, y_early = 0;                     /* the early candidate of the lane's group */
+            if (epzs && EARLY) {
                 /* list positions zero, left, collocated, accelerator, prev1's left, top, right, bottom: one per candidate group */
                 const int pos = (int)(0xA9876521u >> (4 * cand)) & 15;
                 const MespPred P = mesp_predictors(N, v);
                 int x, y;
                 const bool valid = mesp_candidate(st, w, P, pos, x, y);
-                const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-                key_early = valid ? mesp_list_key(cost, pos) : MES_NO_KEY;
+                const uint32_t c = cost.sum(valid, x, y, lane);
+                key_early = valid ? mesp_list_key(c, pos) : MES_NO_KEY;
+                x_early = x;
+                y_early = y;
             }
             /* ---- the row above has published min(bx + 2, b_w) blocks: its vectors ---- */
             if (mesp_has(N, MESP_TOP)) {
@@ -133,20 +138,24 @@ __global__ __launch_bounds__(64) void k_me_search_seq(int method, const uint8_t 
                 mesp_fetch_above(v, N, [&](int dbx) { return mesq_field_rel(mv, true, b - (size_t)bw + dbx, bx + dbx, row - 1, LOG2); });
             }
             const MespPred P = mesp_predictors(N, v);
-            if (epzs) {
+            cost.set_pred(P.median.x, P.median.y);
+            if (epzs && EARLY) {
                 /* the median, top, top-right: the rest of the list */
                 const int pos = cand == 0 ? MESP_MEDIAN : cand == 1 ? MESP_TOP : cand == 2 ? MESP_DIAG : -1;
                 int x, y;
                 const bool valid = mesp_candidate(st, w, P, pos, x, y);
-                const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-                const uint32_t key = valid ? mesp_list_key(cost, pos) : MES_NO_KEY;
+                const uint32_t c = cost.sum(valid, x, y, lane) + cost.penalty(x, y);
+                const uint32_t key = valid ? mesp_list_key(c, pos) : MES_NO_KEY;
+                /* the early pass's sums take their penalty now that the median is known */
+                key_early = mesp_list_key_add(key_early, cost.penalty(x_early, y_early));
                 mesp_advance_list(st, w, P, mes_wave_min(min(key, key_early)));
             }
+            /* EARLY false (a measured variant): the whole list in order behind the wait, two steps of mesp_run() below */
             mesp_run(st, w, P, [&](const MespState &st) {
                 int x, y;
                 const bool valid = mesp_candidate(st, w, P, st.pos + cand, x, y);
-                const uint32_t cost = mes_cost<MB, KIND>(c, rf, stride, valid, x, y, lane);
-                return mes_wave_min(valid ? mes_key(cost, cand) : MES_NO_KEY);
+                const uint32_t c = cost.sum(valid, x, y, lane) + cost.penalty(x, y);
+                return mes_wave_min(valid ? mes_key(c, cand) : MES_NO_KEY);
             });
             /* ---- the block's vector: to the row below, to the next pair, and to the next block of this row ---- */
             if (lane == 0) {
@@ -171,8 +180,11 @@ int ffhip_launch_me_search_seq(int method, const uint8_t *frames, int width, int
      * boundaries, all sequences together, and by sequences as well when one step alone does not fit.  Stream order carries the
      * dependency between the launches; the kernel reads the fields of an earlier launch plainly */
     const int room = FFHIP_PROGRESS_SLOT_INTS - 1;
+    const bool bilat = cost_kind == MES_COST_BILAT;
+    const char *const who = bilat ? "ffhip_me_search_bilat_sequence_dev" : "ffhip_me_search_pred_sequence_dev";
+    const char *const what = bilat ? "ffhip_me_search_bilat_sequence_dev: kernel launch" : "ffhip_me_search_pred_sequence_dev: kernel launch";
     if (bh > room) {
-        ffhip_set_error("ffhip_me_search_pred_sequence_dev: %d block rows exceed a progress-pool slot", bh);
+        ffhip_set_error("%s: %d block rows exceed a progress-pool slot", who, bh);
         return FFHIP_EINVAL;
     }
     const int seqs = nseq < room / bh ? nseq : room / bh;
@@ -182,9 +194,23 @@ int ffhip_launch_me_search_seq(int method, const uint8_t *frames, int width, int
     for (int k0 = 0; k0 < np; k0 += pairs)
         for (int s0 = 0; s0 < nseq; s0 += seqs) {
             const int nk = np - k0 < pairs ? np - k0 : pairs, ns = nseq - s0 < seqs ? nseq - s0 : seqs, units = nk * ns * bh;
-            const int r = ffhip_progress_launch(units + 1, stream, "ffhip_me_search_pred_sequence_dev: kernel launch", [&](const FFHipProgressSlot &ps) {
+            const int r = ffhip_progress_launch(units + 1, stream, what, [&](const FFHipProgressSlot &ps) {
                 const int grid = units < cap ? units : cap;
-                mes_dispatch(mb_size, cost_kind, [&](auto mb, auto kind) {
+#ifdef FFHIP_MEASURE
+                /* FFHIP_ME_BILAT_NO_EARLY (measurement build): the bilateral instances without the early predictor pass (docs/EXPERIMENTS.md) */
+                if (bilat && knob_int("FFHIP_ME_BILAT_NO_EARLY", 0)) {
+                    if (mb_size == 16)
+                        hipLaunchKernelGGL((k_me_search_seq<16, MES_COST_BILAT, false>), dim3((unsigned)grid), dim3(64), 0, stream, method, frames, width,
+                                           height, stride, frame_pitch, seq_pitch, direction, R, k0, nk, s0, ns, nseq, init1, init2, mv_out, cost_out,
+                                           ps.prog, ps.fail);
+                    else
+                        hipLaunchKernelGGL((k_me_search_seq<8, MES_COST_BILAT, false>), dim3((unsigned)grid), dim3(64), 0, stream, method, frames, width,
+                                           height, stride, frame_pitch, seq_pitch, direction, R, k0, nk, s0, ns, nseq, init1, init2, mv_out, cost_out,
+                                           ps.prog, ps.fail);
+                    return hipGetLastError();
+                }
+#endif
+                mes_dispatch_pred(mb_size, cost_kind, [&](auto mb, auto kind) {
                     hipLaunchKernelGGL((k_me_search_seq<decltype(mb)::value, decltype(kind)::value>), dim3((unsigned)grid), dim3(64), 0, stream, method,
                                        frames, width, height, stride, frame_pitch, seq_pitch, direction, R, k0, nk, s0, ns, nseq, init1, init2, mv_out,
                                        cost_out, ps.prog, ps.fail);

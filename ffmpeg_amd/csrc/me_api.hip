@@ -13,6 +13,7 @@
 #include "kernels/me_interp_rules.h"
 #include "kernels/me_kernels.h"
 #include "kernels/me_scene_rules.h"
+#include "kernels/me_search_bilat_rules.h"
 #include "kernels/me_search_pred_rules.h"
 #include "kernels/me_search_rules.h"
 #include "kernels/picture_check.h"
@@ -160,11 +161,12 @@ struct HostBest {
     uint32_t cost_min;
 };
 
-/* The driver of both host faces: every block of every frame in raster order.  search_block(bx, by, b, w, cost) -> HostBest searches
- * block (bx, by) of a frame, the b-th of the call, in the window w with cost(x, y). */
-template <class SearchBlock>
-static void me_search_host(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
-                           int mb_size, int search_param, int cost_kind, int16_t *mv_out, uint32_t *cost_out, SearchBlock search_block)
+/* The driver of every host face: every block of every frame in raster order.  make_cost(f, x_mb, y_mb, w) gives the block's cost
+ * (a callable cost(x, y) that counts its calls in .n); search_block(bx, by, b, w, cost) -> HostBest searches block (bx, by) of a frame,
+ * the b-th of the call, in the window w with it. */
+template <class MakeCost, class SearchBlock>
+static void me_search_host_with(int width, int height, int nframes, int mb_size, int search_param, int16_t *mv_out, uint32_t *cost_out,
+                                MakeCost make_cost, SearchBlock search_block)
 {
     const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
     uint64_t blocks = 0, costs = 0;
@@ -174,8 +176,7 @@ static void me_search_host(const uint8_t *cur, const uint8_t *ref, int width, in
                 const int x_mb = bx << lg, y_mb = by << lg;
                 const size_t b = ((size_t)f * bh + by) * bw + bx;
                 const MesWindow w = mes_window(x_mb, y_mb, search_param, bw, bh, lg);
-                HostCost cost = { cur + (size_t)f * frame_pitch + (ptrdiff_t)y_mb * stride + x_mb, ref + (size_t)f * frame_pitch, stride, mb_size,
-                                  cost_kind, 0 };
+                auto cost = make_cost(f, x_mb, y_mb, w);
                 const HostBest best = search_block(bx, by, b, w, cost);
                 mv_out[2 * b] = (int16_t)best.mvx;
                 mv_out[2 * b + 1] = (int16_t)best.mvy;
@@ -187,9 +188,22 @@ static void me_search_host(const uint8_t *cur, const uint8_t *ref, int width, in
     t_host_costs = costs;
 }
 
+/* the driver with the block metrics: cost(x, y) is HostCost's */
+template <class SearchBlock>
+static void me_search_host(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                           int mb_size, int search_param, int cost_kind, int16_t *mv_out, uint32_t *cost_out, SearchBlock search_block)
+{
+    me_search_host_with(width, height, nframes, mb_size, search_param, mv_out, cost_out,
+                        [&](int f, int x_mb, int y_mb, const MesWindow &) {
+                            return HostCost{ cur + (size_t)f * frame_pitch + (ptrdiff_t)y_mb * stride + x_mb, ref + (size_t)f * frame_pitch, stride, mb_size,
+                                             cost_kind, 0 };
+                        },
+                        search_block);
+}
+
 /* a step's ordered minimum on the CPU: the n candidates one by one.  candidate(i, x, y) -> bool */
-template <class Candidate>
-static uint32_t host_step_key(HostCost &cost, int n, Candidate candidate)
+template <class Cost, class Candidate>
+static uint32_t host_step_key(Cost &cost, int n, Candidate candidate)
 {
     uint32_t key = MES_NO_KEY;
     for (int i = 0; i < n; i++) {
@@ -248,16 +262,16 @@ static int me_search_pred_check_field(const char *who, int method, int width, in
     return 0;
 }
 
-static int me_search_pred_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+static int me_search_pred_check(const char *who, int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
                                 int nframes, int mb_size, int search_param, int cost_kind, const int16_t *prev1, const int16_t *prev2,
                                 const int16_t *mv_out, const uint32_t *cost_out)
 {
     if (me_search_check_args(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out)) {
-        ffhip_set_error(MESP_WHO ": a NULL cur, ref, mv_out or cost_out, mb_size %d (16 or 8), cost_kind %d (0 or 1), a negative width, height, "
-                        "nframes or search_param, stride < width, frame_pitch < stride * height, or more than 2^31 - 1 blocks", mb_size, cost_kind);
+        ffhip_set_error("%s: a NULL cur, ref, mv_out or cost_out, mb_size %d (16 or 8), cost_kind %d (0 or 1), a negative width, height, "
+                        "nframes or search_param, stride < width, frame_pitch < stride * height, or more than 2^31 - 1 blocks", who, mb_size, cost_kind);
         return FFHIP_EINVAL;
     }
-    if (me_search_pred_check_field(MESP_WHO, method, width, height, mv_out))
+    if (me_search_pred_check_field(who, method, width, height, mv_out))
         return FFHIP_EINVAL;
     /* mv_out is read back while it is written: it shares no byte with anything else the call reads or writes */
     const int lg = mb_size == 16 ? 4 : 3;
@@ -273,7 +287,7 @@ static int me_search_pred_check(int method, const uint8_t *cur, const uint8_t *r
         others.add(ffhip_plane_span(prev2, 0, field, 1));
     others.seal();
     if (others.hits(ffhip_plane_span(mv_out, 0, field, 1))) {
-        ffhip_set_error(MESP_WHO ": mv_out overlaps prev1, prev2, cur, ref or cost_out");
+        ffhip_set_error("%s: mv_out overlaps prev1, prev2, cur, ref or cost_out", who);
         return FFHIP_EINVAL;
     }
     return 0;
@@ -283,7 +297,7 @@ extern "C" int ffhip_me_search_pred_batch_dev(int method, const uint8_t *cur, co
                                               size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
                                               const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out, void *stream)
 {
-    const int r = me_search_pred_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
+    const int r = me_search_pred_check(MESP_WHO, method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
                                        prev2, mv_out, cost_out);
     if (r)
         return r;
@@ -291,6 +305,33 @@ extern "C" int ffhip_me_search_pred_batch_dev(int method, const uint8_t *cur, co
         return FFHIP_ENOSYS;
     return ffhip_launch_me_search_pred(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
                                        prev2, mv_out, cost_out, (hipStream_t)stream);
+}
+
+/* one block of a predictive search on the CPU: its neighbours' vectors, the list, the run.  Raster order: the neighbours of the current
+ * frame are in mv_out already.  before_run(P) sees the list before the first cost (the bilateral cost takes its median). */
+template <class Cost, class BeforeRun>
+static HostBest me_search_pred_block(int method, int bx, int by, size_t b, int bw, int bh, int lg, int search_param, const MesWindow &w,
+                                     const int16_t *prev1, const int16_t *prev2, const int16_t *mv_out, Cost &cost, BeforeRun before_run)
+{
+    /* block (bx + dbx, by + dby)'s relative vector of a field of absolute positions; NULL: a field of zero vectors */
+    auto rel = [&](const int16_t *field, int dbx, int dby) {
+        const size_t n = b + (ptrdiff_t)dby * bw + dbx;
+        const MespVec zero = { 0, 0 };
+        return field ? mesp_rel(field[2 * n], field[2 * n + 1], bx + dbx, by + dby, lg) : zero;
+    };
+    const MespNeigh N = mesp_neighbours(method, bx, by, bw, bh);
+    MespNear v = {};
+    if (mesp_has(N, MESP_LEFT))
+        v.left = rel(mv_out, -1, 0);
+    mesp_fetch_prev(v, N, [&](int which, int dbx, int dby) { return rel(which == 1 ? prev1 : prev2, dbx, dby); });
+    mesp_fetch_above(v, N, [&](int dbx) { return rel(mv_out, dbx, -1); });
+    const MespPred P = mesp_predictors(N, v);
+    before_run(P);
+    MespState s = mesp_start(method, bx << lg, by << lg, search_param);
+    mesp_run(s, w, P, [&](const MespState &s) {
+        return host_step_key(cost, 8, [&](int i, int &x, int &y) { return mesp_candidate(s, w, P, s.pos + i, x, y); });
+    });
+    return HostBest{ s.mvx, s.mvy, s.cost_min };
 }
 
 /* the predictive searches of nframes independent pairs on the CPU, arguments checked: the body of the host faces */
@@ -301,25 +342,7 @@ static void me_search_pred_host(int method, const uint8_t *cur, const uint8_t *r
     const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
     me_search_host(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, mv_out, cost_out,
                    [&](int bx, int by, size_t b, const MesWindow &w, HostCost &cost) {
-                       /* block (bx + dbx, by + dby)'s relative vector of a field of absolute positions; NULL: a field of zero vectors */
-                       auto rel = [&](const int16_t *field, int dbx, int dby) {
-                           const size_t n = b + (ptrdiff_t)dby * bw + dbx;
-                           const MespVec zero = { 0, 0 };
-                           return field ? mesp_rel(field[2 * n], field[2 * n + 1], bx + dbx, by + dby, lg) : zero;
-                       };
-                       /* raster order: the neighbours of the current frame are in mv_out already */
-                       const MespNeigh N = mesp_neighbours(method, bx, by, bw, bh);
-                       MespNear v = {};
-                       if (mesp_has(N, MESP_LEFT))
-                           v.left = rel(mv_out, -1, 0);
-                       mesp_fetch_prev(v, N, [&](int which, int dbx, int dby) { return rel(which == 1 ? prev1 : prev2, dbx, dby); });
-                       mesp_fetch_above(v, N, [&](int dbx) { return rel(mv_out, dbx, -1); });
-                       const MespPred P = mesp_predictors(N, v);
-                       MespState s = mesp_start(method, bx << lg, by << lg, search_param);
-                       mesp_run(s, w, P, [&](const MespState &s) {
-                           return host_step_key(cost, 8, [&](int i, int &x, int &y) { return mesp_candidate(s, w, P, s.pos + i, x, y); });
-                       });
-                       return HostBest{ s.mvx, s.mvy, s.cost_min };
+                       return me_search_pred_block(method, bx, by, b, bw, bh, lg, search_param, w, prev1, prev2, mv_out, cost, [](const MespPred &) {});
                    });
 }
 
@@ -327,7 +350,7 @@ extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, 
                                                 size_t frame_pitch, int nframes, int mb_size, int search_param, int cost_kind,
                                                 const int16_t *prev1, const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out)
 {
-    const int r = me_search_pred_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
+    const int r = me_search_pred_check(MESP_WHO, method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, cost_kind, prev1,
                                        prev2, mv_out, cost_out);
     if (r)
         return r;
@@ -338,26 +361,26 @@ extern "C" int ffhip_me_search_pred_frames_host(int method, const uint8_t *cur, 
 
 /* ---- the predictive searches of whole sequences: pair k chained to the fields of pairs k - 1 and k - 2 ----------------------------- */
 #define MESQ_WHO "ffhip_me_search_pred_sequence_dev / _host"
-static int me_search_seq_check(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+static int me_search_seq_check(const char *who, int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
                                size_t seq_pitch, int nseq, int direction, int mb_size, int search_param, int cost_kind, const int16_t *init1,
                                const int16_t *init2, const int16_t *mv_out, const uint32_t *cost_out)
 {
     /* what the pair face refuses, applied to the pictures; the blocks are counted below, over all pairs and sequences */
     if (me_search_check_args(frames, frames, width, height, stride, frame_pitch, nframes < 2 ? nframes : 2, mb_size, search_param, cost_kind, mv_out,
                              cost_out)) {
-        ffhip_set_error(MESQ_WHO ": a NULL frames, mv_out or cost_out, mb_size %d (16 or 8), cost_kind %d (0 or 1), a negative width, height, "
-                        "nframes or search_param, stride < width, or frame_pitch < stride * height", mb_size, cost_kind);
+        ffhip_set_error("%s: a NULL frames, mv_out or cost_out, mb_size %d (16 or 8), cost_kind %d (0 or 1), a negative width, height, "
+                        "nframes or search_param, stride < width, or frame_pitch < stride * height", who, mb_size, cost_kind);
         return FFHIP_EINVAL;
     }
-    if (me_search_pred_check_field(MESQ_WHO, method, width, height, mv_out))
+    if (me_search_pred_check_field(who, method, width, height, mv_out))
         return FFHIP_EINVAL;
     if (direction < 0 || direction > 1) {
-        ffhip_set_error(MESQ_WHO ": direction %d is neither 0 (cur = picture k + 1, ref = picture k) nor 1 (cur = picture k, ref = picture k + 1)",
+        ffhip_set_error("%s: direction %d is neither 0 (cur = picture k + 1, ref = picture k) nor 1 (cur = picture k, ref = picture k + 1)", who,
                         direction);
         return FFHIP_EINVAL;
     }
     if (nseq < 0) {
-        ffhip_set_error(MESQ_WHO ": a negative nseq (%d)", nseq);
+        ffhip_set_error("%s: a negative nseq (%d)", who, nseq);
         return FFHIP_EINVAL;
     }
     if (nseq > 1 && nframes > 0) {
@@ -365,7 +388,7 @@ static int me_search_seq_check(int method, const uint8_t *frames, int width, int
         size_t gap, need;
         if (__builtin_mul_overflow((size_t)(nframes - 1), frame_pitch, &gap) ||
             __builtin_add_overflow(gap, (size_t)stride * (size_t)height, &need) || seq_pitch < need) {
-            ffhip_set_error(MESQ_WHO ": seq_pitch %zu < (nframes - 1) * frame_pitch + stride * height: the pictures of two sequences would share bytes",
+            ffhip_set_error("%s: seq_pitch %zu < (nframes - 1) * frame_pitch + stride * height: the pictures of two sequences would share bytes", who,
                             seq_pitch);
             return FFHIP_EINVAL;
         }
@@ -373,7 +396,7 @@ static int me_search_seq_check(int method, const uint8_t *frames, int width, int
     const int lg = mb_size == 16 ? 4 : 3, np = nframes > 1 ? nframes - 1 : 0;
     const int64_t per = (int64_t)(width >> lg) * (height >> lg);          /* at most 2^24 */
     if (per * nseq > INT_MAX || per * nseq * np > INT_MAX) {
-        ffhip_set_error(MESQ_WHO ": %d pairs of %d sequences of %lld blocks each are more than 2^31 - 1 blocks", np, nseq, (long long)per);
+        ffhip_set_error("%s: %d pairs of %d sequences of %lld blocks each are more than 2^31 - 1 blocks", who, np, nseq, (long long)per);
         return FFHIP_EINVAL;
     }
     /* mv_out is read back while it is written: it shares no byte with anything else the call reads or writes */
@@ -389,7 +412,7 @@ static int me_search_seq_check(int method, const uint8_t *frames, int width, int
         others.add(ffhip_plane_span(init2, 0, field ? step : 0, 1));
     others.seal();
     if (others.hits(ffhip_plane_span(mv_out, 0, field, 1))) {
-        ffhip_set_error(MESQ_WHO ": mv_out overlaps init1, init2, frames or cost_out");
+        ffhip_set_error("%s: mv_out overlaps init1, init2, frames or cost_out", who);
         return FFHIP_EINVAL;
     }
     return 0;
@@ -400,7 +423,7 @@ extern "C" int ffhip_me_search_pred_sequence_dev(int method, const uint8_t *fram
                                                  int cost_kind, const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out,
                                                  void *stream)
 {
-    const int r = me_search_seq_check(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
+    const int r = me_search_seq_check(MESQ_WHO, method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
                                       cost_kind, init1, init2, mv_out, cost_out);
     if (r)
         return r;
@@ -414,7 +437,7 @@ extern "C" int ffhip_me_search_pred_sequence_host(int method, const uint8_t *fra
                                                   int nframes, size_t seq_pitch, int nseq, int direction, int mb_size, int search_param,
                                                   int cost_kind, const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out)
 {
-    const int r = me_search_seq_check(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
+    const int r = me_search_seq_check(MESQ_WHO, method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, direction, mb_size, search_param,
                                       cost_kind, init1, init2, mv_out, cost_out);
     if (r)
         return r;
@@ -436,10 +459,213 @@ extern "C" int ffhip_me_search_pred_sequence_host(int method, const uint8_t *fra
     return 0;
 }
 
+/* ---- the bilateral searches: EPZS and UMH under the cost of kernels/me_search_bilat_rules.h ----------------------------------------- */
+#define MESB_WHO "ffhip_me_search_bilat_batch_dev / _frames_host"
+#define MESBQ_WHO "ffhip_me_search_bilat_sequence_dev / _host"
+/* what the bilateral faces refuse beyond the predictive faces' checks, which ran with `method` replaced by EPZS for 1..7: the
+ * per-block methods, and the geometry for which the cost's two windows could leave the plane.  searching: the call has a block */
+static int me_search_bilat_check(const char *who, int method, int width, int height, int mb_size, int search_param, bool searching)
+{
+    if (method >= FFHIP_ME_METHOD_ESA && method <= FFHIP_ME_METHOD_HEXBS) {
+        static const char *const name[] = { "ESA", "TSS", "TDLS", "NTSS", "FSS", "DS", "HEXBS" };
+        ffhip_set_error("%s: motion search method %d (%s) is not offered under the bilateral cost: EPZS (8) and UMH (9) are", who, method,
+                        name[method - FFHIP_ME_METHOD_ESA]);
+        return FFHIP_ENOSYS;
+    }
+    if (search_param < mb_size) {
+        ffhip_set_error("%s: search_param %d below mb_size %d: the overlapped windows of the bilateral cost would leave the picture", who, search_param,
+                        mb_size);
+        return FFHIP_EINVAL;
+    }
+    const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
+    if (searching && bw > 0 && bh > 0 && (bw < 2 || bh < 2)) {
+        ffhip_set_error("%s: %d x %d is %d x %d blocks: the bilateral cost needs two block columns and two block rows", who, width, height, bw, bh);
+        return FFHIP_EINVAL;
+    }
+    return 0;
+}
+
+static int me_search_bilat_pair_check(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                      int nframes, int mb_size, int search_param, const int16_t *prev1, const int16_t *prev2, const int16_t *mv_out,
+                                      const uint32_t *cost_out)
+{
+    /* the order of the refusals: the arguments every method shares (this text, the faces have no cost_kind), then what the predictive
+     * faces refuse of the field and of overlaps with the per-block methods standing in as EPZS, then the method, then the geometry */
+    if (me_search_check_args(cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, FFHIP_ME_SAD, mv_out, cost_out)) {
+        ffhip_set_error(MESB_WHO ": a NULL cur, ref, mv_out or cost_out, mb_size %d (16 or 8), a negative width, height, nframes or search_param, "
+                        "stride < width, frame_pitch < stride * height, or more than 2^31 - 1 blocks", mb_size);
+        return FFHIP_EINVAL;
+    }
+    const bool per_block = method >= FFHIP_ME_METHOD_ESA && method <= FFHIP_ME_METHOD_HEXBS;
+    const int r = me_search_pred_check(MESB_WHO, per_block ? FFHIP_ME_METHOD_EPZS : method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size,
+                                       search_param, FFHIP_ME_SAD, prev1, prev2, mv_out, cost_out);
+    return r ? r : me_search_bilat_check(MESB_WHO, method, width, height, mb_size, search_param, nframes > 0);
+}
+
+static int me_search_bilat_seq_check(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch, int nframes,
+                                     size_t seq_pitch, int nseq, int mb_size, int search_param, const int16_t *init1, const int16_t *init2,
+                                     const int16_t *mv_out, const uint32_t *cost_out)
+{
+    /* the order of the pair face's refusals */
+    if (me_search_check_args(frames, frames, width, height, stride, frame_pitch, nframes < 2 ? nframes : 2, mb_size, search_param, FFHIP_ME_SAD, mv_out,
+                             cost_out)) {
+        ffhip_set_error(MESBQ_WHO ": a NULL frames, mv_out or cost_out, mb_size %d (16 or 8), a negative width, height, nframes or search_param, "
+                        "stride < width, or frame_pitch < stride * height", mb_size);
+        return FFHIP_EINVAL;
+    }
+    const bool per_block = method >= FFHIP_ME_METHOD_ESA && method <= FFHIP_ME_METHOD_HEXBS;
+    const int r = me_search_seq_check(MESBQ_WHO, per_block ? FFHIP_ME_METHOD_EPZS : method, frames, width, height, stride, frame_pitch, nframes, seq_pitch,
+                                      nseq, 1, mb_size, search_param, FFHIP_ME_SAD, init1, init2, mv_out, cost_out);
+    return r ? r : me_search_bilat_check(MESBQ_WHO, method, width, height, mb_size, search_param, nframes > 1 && nseq > 0);
+}
+
+/* cost(X, Y) of the block at (x_mb, y_mb) on the CPU: the sum over the two windows mesb_place() names, and the penalty round `pred` */
+struct HostBilatCost {
+    const uint8_t *a, *b;           /* pictures A and B */
+    ptrdiff_t stride;
+    int mb, x_mb, y_mb;
+    MesWindow w;
+    MespVec pred;
+    uint64_t n;
+    uint32_t operator()(int X, int Y)
+    {
+        const MesbPlace at = mesb_place(w, x_mb, y_mb, mb, X, Y);
+        const uint8_t *pa = a + (ptrdiff_t)at.ay * stride + at.ax, *pb = b + (ptrdiff_t)at.by * stride + at.bx;
+        uint32_t s = 0;
+        n++;
+        for (int j = 0; j < 2 * mb; j++, pa += stride, pb += stride)
+            for (int i = 0; i < 2 * mb; i++)
+                s += (uint32_t)abs((int)pa[i] - (int)pb[i]);
+        return s + mesb_penalty(X, Y, x_mb, y_mb, pred.x, pred.y);
+    }
+};
+
+/* the bilateral searches of nframes independent pairs on the CPU, arguments checked: the body of the host faces */
+static void me_search_bilat_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                 int nframes, int mb_size, int search_param, const int16_t *prev1, const int16_t *prev2, int16_t *mv_out,
+                                 uint32_t *cost_out)
+{
+    const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
+    me_search_host_with(width, height, nframes, mb_size, search_param, mv_out, cost_out,
+                        [&](int f, int x_mb, int y_mb, const MesWindow &w) {
+                            const MespVec zero = { 0, 0 };
+                            return HostBilatCost{ cur + (size_t)f * frame_pitch, ref + (size_t)f * frame_pitch, stride, mb_size, x_mb, y_mb, w, zero, 0 };
+                        },
+                        [&](int bx, int by, size_t b, const MesWindow &w, HostBilatCost &cost) {
+                            return me_search_pred_block(method, bx, by, b, bw, bh, lg, search_param, w, prev1, prev2, mv_out, cost,
+                                                        [&](const MespPred &P) { cost.pred = P.median; });
+                        });
+}
+
+extern "C" int ffhip_me_search_bilat_cost_host(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, int mb_size,
+                                               int search_param, int bx, int by, int x, int y, int pred_x, int pred_y, uint32_t *cost)
+{
+    static const char who[] = "ffhip_me_search_bilat_cost_host";
+    if (!cur || !ref || !cost || width < 0 || height < 0 || width > 32768 || height > 32768 || stride < width || (mb_size != 16 && mb_size != 8) ||
+        search_param < 0) {
+        ffhip_set_error("%s: a NULL cur, ref or cost, mb_size %d (16 or 8), a width or height outside 0..32768, stride < width or a negative search_param",
+                        who, mb_size);
+        return FFHIP_EINVAL;
+    }
+    /* the geometry the pair face refuses: the cost's two windows could leave the plane */
+    const int r = me_search_bilat_check(who, FFHIP_ME_METHOD_EPZS, width, height, mb_size, search_param, true);
+    if (r)
+        return r;
+    const int lg = mb_size == 16 ? 4 : 3, bw = width >> lg, bh = height >> lg;
+    if (bx < 0 || bx >= bw || by < 0 || by >= bh || pred_x < -32768 || pred_x > 32768 || pred_y < -32768 || pred_y > 32768) {
+        ffhip_set_error("%s: block (%d, %d) outside %d x %d blocks, or a predictor (%d, %d) beyond +-32768", who, bx, by, bw, bh, pred_x, pred_y);
+        return FFHIP_EINVAL;
+    }
+    const MesWindow w = mes_window(bx << lg, by << lg, search_param, bw, bh, lg);
+    if (x < w.x_min || x > w.x_max || y < w.y_min || y > w.y_max) {
+        ffhip_set_error("%s: (%d, %d) lies outside the block's window %d..%d x %d..%d", who, x, y, w.x_min, w.x_max, w.y_min, w.y_max);
+        return FFHIP_EINVAL;
+    }
+    HostBilatCost c = { cur, ref, stride, mb_size, bx << lg, by << lg, w, MespVec{ pred_x, pred_y }, 0 };
+    *cost = c(x, y);
+    return 0;
+}
+
+extern "C" int ffhip_me_search_bilat_batch_dev(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                               size_t frame_pitch, int nframes, int mb_size, int search_param, const int16_t *prev1,
+                                               const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out, void *stream)
+{
+    const int r = me_search_bilat_pair_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, prev1, prev2, mv_out,
+                                             cost_out);
+    if (r)
+        return r;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_me_search_pred(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, MES_COST_BILAT, prev1,
+                                       prev2, mv_out, cost_out, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_me_search_bilat_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                                 size_t frame_pitch, int nframes, int mb_size, int search_param, const int16_t *prev1,
+                                                 const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out)
+{
+    const int r = me_search_bilat_pair_check(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, prev1, prev2, mv_out,
+                                             cost_out);
+    if (r)
+        return r;
+    me_search_bilat_host(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, prev1, prev2, mv_out, cost_out);
+    return 0;
+}
+
+extern "C" int ffhip_me_search_bilat_sequence_dev(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                                  int nframes, size_t seq_pitch, int nseq, int mb_size, int search_param, const int16_t *init1,
+                                                  const int16_t *init2, int16_t *mv_out, uint32_t *cost_out, void *stream)
+{
+    const int r = me_search_bilat_seq_check(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, mb_size, search_param, init1,
+                                            init2, mv_out, cost_out);
+    if (r)
+        return r;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    /* picture A is picture k, picture B picture k + 1: the sequence kernel's direction 1 */
+    return ffhip_launch_me_search_seq(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, 1, mb_size, search_param,
+                                      MES_COST_BILAT, init1, init2, mv_out, cost_out, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_me_search_bilat_sequence_host(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                                   int nframes, size_t seq_pitch, int nseq, int mb_size, int search_param, const int16_t *init1,
+                                                   const int16_t *init2, int16_t *mv_out, uint32_t *cost_out)
+{
+    const int r = me_search_bilat_seq_check(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, mb_size, search_param, init1,
+                                            init2, mv_out, cost_out);
+    if (r)
+        return r;
+    /* the definition: step k is the pair face over the nseq pairs (picture k, picture k + 1), its prev fields the two steps before */
+    const int lg = mb_size == 16 ? 4 : 3;
+    const size_t step = (size_t)(width >> lg) * (size_t)(height >> lg) * (size_t)nseq;    /* blocks of a step */
+    uint64_t blocks = 0, costs = 0;
+    for (int k = 0; k + 1 < nframes; k++) {
+        const uint8_t *lo = frames + (size_t)k * frame_pitch;
+        int16_t *mv = mv_out + 2 * step * (size_t)k;
+        const int16_t *prev1 = k >= 1 ? mv - 2 * step : init1, *prev2 = k >= 2 ? mv - 4 * step : k == 1 ? init1 : init2;
+        me_search_bilat_host(method, lo, lo + frame_pitch, width, height, stride, seq_pitch, nseq, mb_size, search_param, prev1, prev2, mv,
+                             cost_out + step * (size_t)k);
+        blocks += t_host_blocks;
+        costs += t_host_costs;
+    }
+    t_host_blocks = blocks;
+    t_host_costs = costs;
+    return 0;
+}
+
 /* ---- vf_minterpolate's compensation of whole sequences (kernels/me_interp_rules.h) -------------------------------------------------- */
 #define MEI_WHO "ffhip_me_interp_sequence_dev / _host"
 extern "C" int ffhip_me_interp_job_size(void) { return (int)sizeof(FFHipMeInterpJob); }
 static_assert(sizeof(FFHipMeInterpJob) == 16, "the job record of include/ffhip.h");
+
+/* the faces the texts of me_interp_refuse() name: the bilateral faces put their own here for the length of their checks */
+static const char mei_who_default[] = MEI_WHO;
+static thread_local const char *t_mei_who = mei_who_default;
+struct MeiWho {
+    const char *before;
+    explicit MeiWho(const char *who) : before(t_mei_who) { t_mei_who = who; }
+    ~MeiWho() { t_mei_who = before; }
+};
 
 static int me_interp_refuse(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 static int me_interp_refuse(const char *fmt, ...)
@@ -449,7 +675,7 @@ static int me_interp_refuse(const char *fmt, ...)
     va_start(ap, fmt);
     vsnprintf(text, sizeof text, fmt, ap);
     va_end(ap);
-    ffhip_set_error(MEI_WHO ": %s", text);
+    ffhip_set_error("%s: %s", t_mei_who, text);
     return FFHIP_EINVAL;
 }
 
@@ -505,8 +731,9 @@ static int me_interp_check(const FFHipMePlanes *src, const FFHipMePlanes *dst, i
                                     nframes - 2, J.alpha, J.mode);
         mci |= J.mode == FFHIP_ME_INTERP_MCI;
     }
+    const bool one_field = mv_fwd == mv_bwd && t_mei_who != mei_who_default;      /* the bilateral faces pass their one field twice */
     if (mci && (!mv_fwd || !mv_bwd))
-        return me_interp_refuse("a NULL mv_fwd or mv_bwd with an MCI job");
+        return me_interp_refuse("a NULL %s with an MCI job", one_field ? "mv" : "mv_fwd or mv_bwd");
     /* what the call writes shares no byte with what it reads */
     const bool any = njobs > 0 && width > 0 && height > 0;
     const int lg = mb_size == 16 ? 4 : 3;
@@ -526,7 +753,7 @@ static int me_interp_check(const FFHipMePlanes *src, const FFHipMePlanes *dst, i
     reads.seal();
     for (const FFHipSpan &w : writes)
         if (reads.hits(w))
-            return me_interp_refuse("dst overlaps src, mv_fwd or mv_bwd");
+            return me_interp_refuse("dst overlaps src, %s", one_field ? "or mv" : "mv_fwd or mv_bwd");
     return 0;
 }
 
@@ -556,6 +783,7 @@ extern "C" void ffhip_me_interp_host_counts(uint64_t counts[8])
 }
 
 /* the host face after the checks; scene: NULL or the pair-major flags of ffhip_me_interp_sequence_scd_host() */
+template <bool BILAT = false>
 static int me_interp_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h, int width, int height,
                           int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv_fwd, const int16_t *mv_bwd,
                           const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action)
@@ -579,7 +807,7 @@ static int me_interp_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, in
             D[i] = dst->base[i] + (size_t)j * dst->frame_pitch[i];
         }
         if (!blend)
-            for (int dir = 0; dir < 2; dir++) {
+            for (int dir = 0; dir < (BILAT ? 1 : 2); dir++) {         /* BILAT: mv_fwd is the one field of half-vectors */
                 const int16_t *f = (dir ? mv_bwd : mv_fwd) + 2 * per * ((size_t)J.pair * nseq + J.seq);
                 for (int by = 0; by < g.bh; by++)
                     for (int bx = 0; bx < g.bw; bx++) {
@@ -587,7 +815,7 @@ static int me_interp_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, in
                         int vx, vy;
                         const bool ok = mei_vector(g, bx, by, f[2 * b], f[2 * b + 1], vx, vy);
                         cnt[MEI_N_MALFORMED] += !ok;
-                        blocks[dir * per + b] = ok ? mei_block(g, alpha, dir, bx, by, vx, vy) : mei_no_block();
+                        blocks[dir * per + b] = !ok ? mei_no_block() : BILAT ? mei_block_bilat(g, bx, by, vx, vy) : mei_block(g, alpha, dir, bx, by, vx, vy);
                     }
             }
         auto block = [&](int dir, int bx, int by) -> const MeiBlock & { return blocks[dir * per + (size_t)by * g.bw + bx]; };
@@ -606,11 +834,15 @@ static int me_interp_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, in
                     /* the luma pixel whose list the sample uses: itself, or the last writer of the reference's walk */
                     const int x = std::min(((cx + 1) << sw) - 1, width - 1), y = std::min(((cy + 1) << sh) - 1, height - 1);
                     uint64_t S = 0, Wt = 0;
-                    mei_walk(g, alpha, x, y, window, block, [&](int wa, int dxa, int dya, int wb, int dxb, int dyb) {
+                    auto take = [&](int wa, int dxa, int dya, int wb, int dxb, int dyb) {
                         S += (uint64_t)wa * A[i][((y >> sh) + mei_tshift(dya, sh)) * ss + (x >> sw) + mei_tshift(dxa, sw)] +
                              (uint64_t)wb * B[i][((y >> sh) + mei_tshift(dyb, sh)) * ss + (x >> sw) + mei_tshift(dxb, sw)];
                         Wt += (uint64_t)(wa + wb);
-                    }, i ? nullptr : cnt);
+                    };
+                    if (BILAT)
+                        mei_walk_bilat(g, alpha, x, y, window, [&](int bx, int by) -> const MeiBlock & { return block(0, bx, by); }, take, i ? nullptr : cnt);
+                    else
+                        mei_walk(g, alpha, x, y, window, block, take, i ? nullptr : cnt);
                     *d = (uint8_t)((S + (Wt >> 1)) / Wt);
                 }
         }
@@ -637,7 +869,8 @@ static int me_interp_scd_check(const FFHipMePlanes *dst, int nplanes, int sw, in
                                const uint8_t *scene, int scene_action)
 {
     if (scene_action != FFHIP_ME_SCENE_BLEND && scene_action != FFHIP_ME_SCENE_DUP) {
-        ffhip_set_error("ffhip_me_interp_sequence_scd_dev / _host: scene_action %d (1: blend, 2: duplicate)", scene_action);
+        ffhip_set_error("%s: scene_action %d (1: blend, 2: duplicate)", t_mei_who != mei_who_default ? t_mei_who : "ffhip_me_interp_sequence_scd_dev / _host",
+                        scene_action);
         return FFHIP_EINVAL;
     }
     if (!scene || njobs <= 0 || width <= 0 || height <= 0 || nframes < 2 || nseq < 1)
@@ -648,7 +881,7 @@ static int me_interp_scd_check(const FFHipMePlanes *dst, int nplanes, int sw, in
     for (int i = 0; i < nplanes; i++) {
         const int pw = mei_pw(i, width, sw), ph = mei_ph(i, height, sh);
         if (reads.hits(ffhip_plane_span(dst->base[i], 0, (ptrdiff_t)(njobs - 1) * (ptrdiff_t)dst->frame_pitch[i] + (ptrdiff_t)(ph - 1) * dst->stride[i] + pw, 1))) {
-            ffhip_set_error("ffhip_me_interp_sequence_scd_dev / _host: dst overlaps scene");
+            ffhip_set_error("%s: dst overlaps scene", t_mei_who != mei_who_default ? t_mei_who : "ffhip_me_interp_sequence_scd_dev / _host");
             return FFHIP_EINVAL;
         }
     }
@@ -687,6 +920,46 @@ extern "C" int ffhip_me_interp_sequence_scd_host(const FFHipMePlanes *src, const
         return r;
     return me_interp_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv_fwd, mv_bwd, jobs, njobs,
                           scene, scene_action);
+}
+
+/* ---- the bilateral compensation: one field of half-vectors (kernels/me_interp_rules.h: mei_block_bilat, mei_walk_bilat) ------------- */
+#define MEIB_WHO "ffhip_me_interp_bilat_sequence_dev / _host"
+static int me_interp_bilat_check(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int sw, int sh, int width, int height, int nframes,
+                                 int nseq, int mb_size, int mv_range, const uint8_t *window, const int16_t *mv, const FFHipMeInterpJob *jobs, int njobs,
+                                 const uint8_t *scene, int scene_action)
+{
+    const MeiWho who(MEIB_WHO);
+    const int r = me_interp_check(src, dst, nplanes, sw, sh, width, height, nframes, nseq, mb_size, mv_range, window, mv, mv, jobs, njobs);
+    return r ? r : me_interp_scd_check(dst, nplanes, sw, sh, width, height, nframes, nseq, njobs, scene, scene_action);
+}
+
+extern "C" int ffhip_me_interp_bilat_sequence_dev(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                                  int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                                  const int16_t *mv, const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action,
+                                                  void *stream)
+{
+    const int r = me_interp_bilat_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, jobs,
+                                        njobs, scene, scene_action);
+    if (r)
+        return r;
+    if (!njobs)
+        return 0;
+    if (!ffhip_have_device())
+        return FFHIP_ENOSYS;
+    return ffhip_launch_me_interp_bilat(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv, jobs, njobs,
+                                        scene, scene_action, (hipStream_t)stream);
+}
+
+extern "C" int ffhip_me_interp_bilat_sequence_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                                   int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                                   const int16_t *mv, const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action)
+{
+    const int r = me_interp_bilat_check(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, jobs,
+                                        njobs, scene, scene_action);
+    if (r)
+        return r;
+    return me_interp_host<true>(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nseq, mb_size, mv_range, window, mv, mv, jobs, njobs, scene,
+                                scene_action);
 }
 
 /* ---- vf_minterpolate's scene-change detection of whole sequences (kernels/me_scene_rules.h) ------------------------------------------ */

@@ -99,6 +99,54 @@ def search_pred_sequence_host(method, frames, width, height, stride, frame_pitch
     return _host_counts()
 
 
+# ---- bilateral motion estimation (vf_minterpolate's me_mode=bilat): one search per pair, half-vectors ------------------------------
+def search_bilat_batch(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, prev1, prev2, mv_out, cost_out,
+                       stream=None):
+    """EPZS or UMH under the bilateral cost, nframes independent pairs in one launch: picture A is `cur`, picture B `ref`, and a block's
+    vector is the half-vector v with A sampled at +v and B at -v.  Arguments and outputs as search_pred_batch(), without cost_kind."""
+    return _lib.check(_lib.lib().ffhip_me_search_bilat_batch_dev(method, _ptr(cur), _ptr(ref), width, height, stride, frame_pitch, nframes,
+                                                                 mb_size, search_param, _ptr(prev1), _ptr(prev2), _ptr(mv_out),
+                                                                 _ptr(cost_out), _stream(stream)), "ffhip_me_search_bilat_batch_dev")
+
+
+def search_bilat_frames_host(method, cur, ref, width, height, stride, frame_pitch, nframes, mb_size, search_param, prev1, prev2, mv_out,
+                             cost_out):
+    """The same rules on the CPU (device-free): numpy arrays, prev1 / prev2 arrays or None.  Returns (blocks searched, costs
+    evaluated)."""
+    _lib.check(_lib.lib().ffhip_me_search_bilat_frames_host(method, _ptr(cur), _ptr(ref), width, height, stride, frame_pitch, nframes, mb_size,
+                                                            search_param, _ptr(prev1), _ptr(prev2), _ptr(mv_out), _ptr(cost_out)),
+               "ffhip_me_search_bilat_frames_host")
+    return _host_counts()
+
+
+def search_bilat_cost_host(cur, ref, width, height, stride, mb_size, search_param, bx, by, x, y, pred):
+    """A test hook, not for callers: cost(x, y) of block (bx, by) of the pair (cur, ref) under the bilateral rule with the predictor
+    `pred`, on the CPU"""
+    import ctypes as C
+    c = C.c_uint32()
+    _lib.check(_lib.lib().ffhip_me_search_bilat_cost_host(_ptr(cur), _ptr(ref), width, height, stride, mb_size, search_param, bx, by, x, y,
+                                                          pred[0], pred[1], C.addressof(c)), "ffhip_me_search_bilat_cost_host")
+    return c.value
+
+
+def search_bilat_sequence(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, mb_size, search_param, init1, init2,
+                          mv_out, cost_out, stream=None):
+    """The bilateral search of nseq sequences of nframes pictures in one launch, pair k (pictures k and k + 1) chained to the fields of
+    pairs k - 1 and k - 2; tensors on the device.  Layouts as search_pred_sequence(), without cost_kind and direction."""
+    return _lib.check(_lib.lib().ffhip_me_search_bilat_sequence_dev(method, _ptr(frames), width, height, stride, frame_pitch, nframes, seq_pitch,
+                                                                    nseq, mb_size, search_param, _ptr(init1), _ptr(init2), _ptr(mv_out),
+                                                                    _ptr(cost_out), _stream(stream)), "ffhip_me_search_bilat_sequence_dev")
+
+
+def search_bilat_sequence_host(method, frames, width, height, stride, frame_pitch, nframes, seq_pitch, nseq, mb_size, search_param, init1, init2,
+                               mv_out, cost_out):
+    """The same loop on the CPU (device-free): numpy arrays.  Returns (blocks searched, costs evaluated) over all pairs."""
+    _lib.check(_lib.lib().ffhip_me_search_bilat_sequence_host(method, _ptr(frames), width, height, stride, frame_pitch, nframes, seq_pitch, nseq,
+                                                              mb_size, search_param, _ptr(init1), _ptr(init2), _ptr(mv_out), _ptr(cost_out)),
+               "ffhip_me_search_bilat_sequence_host")
+    return _host_counts()
+
+
 # ---- vf_minterpolate's compensation (ffhip_me_interp_sequence_dev / _host) ----------------------------------------------------------
 MCI, BLEND = 0, 1
 INTERP_COUNTS = ("taken", "zero_weight", "capped", "malformed", "fallback", "clipped", "samples", "blend")
@@ -229,4 +277,29 @@ def interp_sequence_scd_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, wi
     r = _lib.lib().ffhip_me_interp_sequence_scd_host(*args, _ptr(scene), scene_action)
     del keep
     _lib.check(r, "ffhip_me_interp_sequence_scd_host")
+    return interp_host_counts()
+
+
+def _interp_bilat_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, jobs):
+    keep, a = _interp_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, None, jobs)
+    return keep, a[:13] + a[14:]        # one field: mv_bwd's place is dropped
+
+
+def interp_bilat_sequence(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, jobs,
+                          scene=None, scene_action=SCENE_BLEND, stream=None):
+    """The bilateral compensation (me_mode=bilat) of every job in one launch: interp_sequence_scd() with the one field `mv` of
+    search_bilat_sequence()'s half-vectors in place of mv_fwd / mv_bwd; scene may be None."""
+    keep, args = _interp_bilat_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, jobs)
+    r = _lib.lib().ffhip_me_interp_bilat_sequence_dev(*args, _ptr(scene), scene_action, _stream(stream))
+    del keep
+    return _lib.check(r, "ffhip_me_interp_bilat_sequence_dev")
+
+
+def interp_bilat_sequence_host(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, jobs,
+                               scene=None, scene_action=SCENE_BLEND):
+    """The same on the CPU (device-free).  Returns interp_host_counts()."""
+    keep, args = _interp_bilat_args(src, dst, nplanes, log2_chroma_w, log2_chroma_h, width, height, nframes, nseq, mb_size, mv_range, window, mv, jobs)
+    r = _lib.lib().ffhip_me_interp_bilat_sequence_host(*args, _ptr(scene), scene_action)
+    del keep
+    _lib.check(r, "ffhip_me_interp_bilat_sequence_host")
     return interp_host_counts()

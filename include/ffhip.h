@@ -3069,11 +3069,79 @@ int ffhip_me_search_pred_sequence_host(int method, const uint8_t *frames, int wi
                                        const int16_t *init1, const int16_t *init2, int16_t *mv_out, uint32_t *cost_out);
 
 /**
+ * Bilateral motion estimation (vf_minterpolate's me_mode=bilat, the filter's default): EPZS (8) and UMH (9) of nframes independent pairs
+ * in one launch on `stream`, under the bilateral cost.  One search per pair: picture A is `cur`, picture B is `ref`, and the vector of a
+ * block is a HALF-vector v of a block of the picture halfway between them — A is sampled at +v and B at -v.  The arguments are
+ * ffhip_me_search_pred_batch_dev()'s without cost_kind.  mv_out and cost_out have the same layouts; mv_out holds the absolute positions
+ * (x_mb + v.x, y_mb + v.y).
+ *
+ * The rule below is RESTATED FROM MEMORY and NOT CHECKED against libavfilter/vf_minterpolate.c, which was not at hand; this text is the
+ * definition the tests pin (kernels/me_search_bilat_rules.h is its one implementation beside the search rules of
+ * kernels/me_search_pred_rules.h, tests/me_bilat_model.py the model written from it).
+ *   Geometry, the window (x_min, x_max, y_min, y_max) and COST_MV / COST_P_MV are those of ffhip_me_search_batch_dev().  The predictor
+ *   lists, the median and the phases are those of ffhip_me_search_pred_batch_dev(); the list's vectors are the relative vectors of this
+ *   face's own fields (mv_out, prev1, prev2).  Only cost differs.  h = mb / 2; clip(v, lo, hi) = v < lo ? lo : v > hi ? hi : v.
+ *   cost(X, Y) of the block at (x_mb, y_mb) (the filter's get_sbad_ob):
+ *     lo_x = x_min + h, hi_x = x_max - h;  cx = clip(x_mb, lo_x, hi_x);  rx = min(cx - lo_x, hi_x - cx);  dx = clip(X - cx, -rx, rx);
+ *     the same gives cy, dy;
+ *     sbad = sum of |A[cy + dy + j][cx + dx + i] - B[cy - dy + j][cx - dx + i]|, j and i each over -h .. 3 * h - 1: an overlapped window
+ *       of twice the block size;
+ *     cost = sbad + 64 * (|X - x_mb - pred.x| + |Y - y_mb - pred.y|), held in uint32_t.
+ *   pred is the block's median predictor.  The pred rules compute it from the list as it stands; it is fixed before the block's first
+ *   cost, whether or not the median candidate lies in the window.
+ *   Reads stay inside the plane when lo <= hi, which holds for every block when search_param >= mb_size, b_w >= 2 and b_h >= 2; the faces
+ *   refuse everything else, and the kernel takes no argument for which the inequality can fail.
+ * Methods 1..7 (the per-block methods), SATD under this cost, depths above 8 bits and fusing the search with the compensation are not
+ * here.
+ * FFHIP_EINVAL (before any device check, each with a text): everything ffhip_me_search_pred_batch_dev() refuses; search_param < mb_size;
+ * a picture of fewer than two block columns or two block rows when there is anything to search (nframes > 0 and at least one block).
+ * FFHIP_ENOSYS with a text that names the method: methods 1..7.  The order: the shared argument checks; then the predictive faces'
+ * checks of the field (sizes above 32768, mv_out's alignment, mv_out's overlaps), which a method 1..7 goes through like EPZS; then the
+ * method (a method outside 1..9: FFHIP_EINVAL with the field checks, 1..7: FFHIP_ENOSYS); then search_param and the block counts.
+ * FFHIP_ENOSYS without a device, after the checks.  A lost hand-off is reported as by the predictive faces.
+ */
+int ffhip_me_search_bilat_batch_dev(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                    size_t frame_pitch, int nframes, int mb_size, int search_param, const int16_t *prev1,
+                                    const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free), blocks in raster order: the same arguments but the stream, the
+ *  same refusals but the one for a missing device, the same bytes.  ffhip_me_search_host_counts() reports its blocks and costs. */
+int ffhip_me_search_bilat_frames_host(int method, const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride,
+                                      size_t frame_pitch, int nframes, int mb_size, int search_param, const int16_t *prev1,
+                                      const int16_t *prev2, int16_t *mv_out, uint32_t *cost_out);
+/** TEST HOOK of the host build, not part of the interface a caller should build on (it may change or go without notice): one cost of
+ *  the rule above on host arrays, cost(x, y) of block (bx, by) of the pair (cur, ref) with the predictor (pred_x, pred_y), written to
+ *  *cost.  It exists so that tests can pin the placement of the two windows apart from a search.  FFHIP_EINVAL with a text: what the
+ *  pair face refuses of one pair's geometry, a NULL cost, a block outside the picture, a predictor component beyond +-32768, (x, y)
+ *  outside the block's window. */
+int ffhip_me_search_bilat_cost_host(const uint8_t *cur, const uint8_t *ref, int width, int height, ptrdiff_t stride, int mb_size,
+                                    int search_param, int bx, int by, int x, int y, int pred_x, int pred_y, uint32_t *cost);
+/**
+ * The bilateral search of whole sequences in one launch: ffhip_me_search_pred_sequence_dev()'s arguments without cost_kind and
+ * direction.  Pair k of a sequence is A = picture k, B = picture k + 1.  Outputs are pair-major, as there.
+ * DEFINITION: the bytes of mv_out and cost_out are those of the loop of calls of ffhip_me_search_bilat_batch_dev() —
+ *   for k in 0 .. np - 1:
+ *       prev1 = k >= 1 ? field step k - 1 : init1;   prev2 = k >= 2 ? field step k - 2 : (k == 1 ? init1 : init2)
+ *       ffhip_me_search_bilat_batch_dev(method, picture k, picture k + 1, ..., frame_pitch = seq_pitch, nframes = nseq, ..., prev1, prev2,
+ *                                       field step k, cost step k, stream)
+ * — the chaining of the existing sequence face, word for word.  Refusals: those of ffhip_me_search_pred_sequence_dev() (direction apart)
+ * and of the pair face above; "anything to search" is nframes > 1, nseq > 0 and at least one block.
+ */
+int ffhip_me_search_bilat_sequence_dev(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                       int nframes, size_t seq_pitch, int nseq, int mb_size, int search_param, const int16_t *init1,
+                                       const int16_t *init2, int16_t *mv_out, uint32_t *cost_out, void *stream);
+/** The same loop on host arrays (device-free): the same arguments but the stream, the same refusals but the one for a missing device,
+ *  the same bytes.  ffhip_me_search_host_counts() reports the blocks and costs of all its pairs. */
+int ffhip_me_search_bilat_sequence_host(int method, const uint8_t *frames, int width, int height, ptrdiff_t stride, size_t frame_pitch,
+                                        int nframes, size_t seq_pitch, int nseq, int mb_size, int search_param, const int16_t *init1,
+                                        const int16_t *init2, int16_t *mv_out, uint32_t *cost_out);
+
+/**
  * vf_minterpolate's motion-compensated interpolation of whole sequences in one launch: mi_mode=mci, me_mode=bidir, mc_mode=obmc — the
  * overlapped-block accumulation of bidirectional_obmc() and the per-pixel weighted average of set_frame_data() — and the filter's
  * scene-change fallback, the blend.  It consumes the fields of two ffhip_me_search_pred_sequence_dev() calls (direction 0 and 1), so
  * frame-rate conversion is search forward, search backward, interpolation on one stream with no host round trip.  Fusing search and
- * compensation into one launch, me_mode=bilat, mc_mode=aobmc, vsbmc and depths above 8 bits are not here: in this face the caller
+ * compensation into one launch, mc_mode=aobmc, vsbmc and depths above 8 bits are not here (me_mode=bilat has faces of its own:
+ * ffhip_me_search_bilat_sequence_dev() above, ffhip_me_interp_bilat_sequence_dev() below): in this face the caller
  * decides per job between MCI and BLEND (ffhip_me_scene_sequence_dev() and ffhip_me_interp_sequence_scd_dev() below take that decision
  * on the device), and the other modes stay on the CPU.
  *
@@ -3218,6 +3286,37 @@ int ffhip_me_interp_sequence_scd_host(const FFHipMePlanes *src, const FFHipMePla
                                       int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
                                       const int16_t *mv_fwd, const int16_t *mv_bwd, const FFHipMeInterpJob *jobs, int njobs,
                                       const uint8_t *scene /* host, or NULL */, int scene_action);
+
+/**
+ * The bilateral compensation (vf_minterpolate's me_mode=bilat with mc_mode=obmc: bilateral_obmc() for every block in raster order,
+ * then set_frame_data()): ffhip_me_interp_sequence_scd_dev()'s arguments with ONE field `mv` — the half-vectors of
+ * ffhip_me_search_bilat_sequence_dev(), pair-major — in place of mv_fwd / mv_bwd.  `scene` may be NULL; scene_action is as there.  Job
+ * records, the window table, BLEND, DUP, the plane layouts and the counters of ffhip_me_interp_host_counts() keep their meanings
+ * ([3] counts malformed blocks per job; entry [2] stays 0).  So a conversion under the filter's default mode is search, detection,
+ * interpolation: three calls on one stream.
+ *
+ * RESTATED FROM MEMORY, NOT CHECKED against libavfilter/vf_minterpolate.c, which was not at hand; this text is the definition the tests
+ * pin (kernels/me_interp_rules.h is its one implementation, tests/me_bilat_model.py the model written from it).  The list of luma pixel
+ * (x, y) is built over by = 0 .. b_h - 1, then bx = 0 .. b_w - 1.  h = mb / 2.
+ *   1. v is the block's relative vector.  If |v.x| or |v.y| exceeds mv_range, the block is malformed and contributes nothing.
+ *   2. sx = (bx << log2mb) - h, sy the same in y.  The vector does not shift the window.
+ *   3. x0 = clip(sx, 0, W - 1), x1 = clip(sx + 2 * mb, 0, W - 1); y0, y1 the same with H.  The pixel is covered iff x0 <= x < x1 and
+ *      y0 <= y < y1.
+ *   4. w = window[(x - sx) + (y - sy) * 2 * mb].  Skip when w is 0.
+ *   5. m = 2 * v.  The two entries, the empty-list fallback, the luma average and the chroma rule follow the rule of
+ *      ffhip_me_interp_sequence_dev() from its step 5 on, read with this m in place of its m.
+ * At most four blocks reach a pixel (windows of 2 * mb stand mb apart: two per axis), so the cap of 16 never binds.
+ * vsbmc, aobmc and the cluster pass that feeds them stay out.
+ * FFHIP_EINVAL: everything ffhip_me_interp_sequence_scd_dev() refuses, read with `mv` for the two fields, each text naming these faces.
+ */
+int ffhip_me_interp_bilat_sequence_dev(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                       int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                       const int16_t *mv /* device, pair-major */, const FFHipMeInterpJob *jobs, int njobs,
+                                       const uint8_t *scene /* device, or NULL */, int scene_action, void *stream);
+/** The same on the CPU (device-free): everything on the host, the same refusals but the one for a missing device, the same bytes. */
+int ffhip_me_interp_bilat_sequence_host(const FFHipMePlanes *src, const FFHipMePlanes *dst, int nplanes, int log2_chroma_w, int log2_chroma_h,
+                                        int width, int height, int nframes, int nseq, int mb_size, int mv_range, const uint8_t *window,
+                                        const int16_t *mv, const FFHipMeInterpJob *jobs, int njobs, const uint8_t *scene, int scene_action);
 
 /* ------------------------------------------------------------------------------------------ */
 /* libavutil: av_tx float MDCT                                                               */

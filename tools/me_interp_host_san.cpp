@@ -65,6 +65,11 @@ int ffhip_launch_me_interp_scd(const FFHipMePlanes *, const FFHipMePlanes *, int
 {
     return FFHIP_ENOSYS;
 }
+int ffhip_launch_me_interp_bilat(const FFHipMePlanes *, const FFHipMePlanes *, int, int, int, int, int, int, int, int, const uint8_t *, const int16_t *,
+                                 const FFHipMeInterpJob *, int, const uint8_t *, int, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
 int ffhip_launch_me_scene(const uint8_t *, int, int, int, ptrdiff_t, size_t, int, size_t, int, double, const double *, double *, uint64_t *, float *,
                           uint8_t *, ihipStream_t *)
 {

@@ -61,6 +61,11 @@ int ffhip_launch_me_interp(const FFHipMePlanes *, const FFHipMePlanes *, int, in
 {
     return FFHIP_ENOSYS;
 }
+int ffhip_launch_me_interp_bilat(const FFHipMePlanes *, const FFHipMePlanes *, int, int, int, int, int, int, int, int, const uint8_t *, const int16_t *,
+                                 const FFHipMeInterpJob *, int, const uint8_t *, int, ihipStream_t *)
+{
+    return FFHIP_ENOSYS;
+}
 int ffhip_launch_me_interp_scd(const FFHipMePlanes *, const FFHipMePlanes *, int, int, int, int, int, int, int, int, const uint8_t *, const int16_t *,
                                const int16_t *, const FFHipMeInterpJob *, int, const uint8_t *, int, ihipStream_t *)
 {
