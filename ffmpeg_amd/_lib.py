@@ -125,6 +125,7 @@ def lib():
         "ffhip_sws_uops_run_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "ffhip_membw_probe": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
         "ffhip_sws_up2_virtual_bank_host": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+        "ffhip_sws_up2_walk_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]),
         "ffhip_sws_upn_virtual_bank_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
         "ffhip_sws_up2rgb_hco_host": (C.c_int, [vp, C.c_int, vp, C.c_int, vp]),
         "ffhip_sws_down2_virtual_bank_host": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),

@@ -136,7 +136,11 @@ struct FFHipUp2Job {
     int ngroups;                        /* 8-byte destination groups per row: plane srcW / 4, pair srcW / 2 */
     const uint32_t *hfv;                /* device: virtual horizontal bank, 2 srcW x 2 dwords */
     const uint32_t *vfv;                /* device: virtual vertical bank, row y at dwords 2 (y + 1): (2 srcH + 18) x 2 dwords, 16-byte aligned */
-    int nfull, upj;                     /* full 64-lane column blocks per row; units per (pack of frames, strip) */
+    /* the geometry of a (pack of frames, strip), read through sws_up2_lane() below.  edge 0: nfull whole 64-lane column blocks per frame, then
+     * the blocks at the ragged right end of the rows, shared by the pack's frames lane block by lane block.  edge e = 16, 32 or 64 (ngroups % 64
+     * = 16, 32, 0; sws_up2_edge_lanes): the two ends of a row, e / 2 groups each, are e lanes of a wave that holds the ends of 64 / e frames; the
+     * nfull = (ngroups - e) / 64 whole blocks between them start at group e / 2 and never meet a row end.  upj: units per (pack, strip). */
+    int nfull, edge, upj;
     int nstrips, steps_per_strip, unit_begin;
     /* samples above 8 bits (k_sws_up2<., ., 1>; 0: bytes): depths 9..14 of the little-endian uint16 samples on either side, and
      * whether they sit in the high bits (P010 / P012).  Groups are then 16 destination bytes. */
@@ -152,15 +156,75 @@ struct FFHipUp2Job {
 };
 struct FFHipUp2Args {
     FFHipUp2Job job[3];
-    int njobs, units_per_pack, npacks, nframes, fshift; /* a pack = 1 << fshift frames; they share the ragged-end blocks (64 >> fshift lanes each) */
+    /* a pack = 1 << fshift frames: the frames that share the ragged-end blocks (64 >> fshift lanes each) of a job without the edge layout,
+     * and at least the 64 / e frames of one edge wave of every job with it (a job whose edge wave holds fewer has several per pack) */
+    int njobs, units_per_pack, npacks, nframes, fshift;
     int xcd;                                            /* XCD-contiguous unit order */
 };
+
+/* The geometry of a launch of k_sws_up2, one statement for the kernel, the planner and the CPU test (tests/test_up2_plan.py, through
+ * ffhip_sws_up2_walk_host).  Wave gw of the launch is unit u of pack gw / units_per_pack; the jobs' units follow one another, a job's
+ * strips likewise, and a strip has the job's upj units. */
+struct FFHipUp2Unit { int pack, job, strip, idx; };
+__host__ __device__ __forceinline__ FFHipUp2Unit sws_up2_unit(const FFHipUp2Args &A, uint32_t gw)
+{
+    FFHipUp2Unit w;
+    w.pack = (int)(gw / (uint32_t)A.units_per_pack);
+    const int u = (int)(gw - (uint32_t)w.pack * (uint32_t)A.units_per_pack);
+    w.job = 0;
+    if (A.njobs > 1 && u >= A.job[1].unit_begin) w.job = 1;
+    if (A.njobs > 2 && u >= A.job[2].unit_begin) w.job = 2;
+    const int local = u - A.job[w.job].unit_begin;
+    w.strip = local / A.job[w.job].upj;
+    w.idx = local - w.strip * A.job[w.job].upj;
+    return w;
+}
+/* the edge layout of a row of n groups: lanes of an edge wave per frame (the row's ends are cut off at 64, 128 or 256 destination bytes), or
+ * 0: the row keeps its whole blocks and the shared ragged end */
+__host__ __device__ __forceinline__ int sws_up2_edge_lanes(int n)
+{
+    const int r = n & 63;
+    return n < 16 ? 0 : r == 0 ? 64 : r == 32 ? 32 : r == 16 ? 16 : 0;
+}
+/* Lane `lane` of unit idx of a (pack, strip): frame frame0 + fsub of the pack (frame0 is the same for the whole wave), group `group` of the
+ * row (at or above ngroups: the lane idles), and whether the wave holds a row end (the same for the whole wave: computed from idx alone).  A
+ * wave that does not holds groups 1 .. ngroups - 2 only, so its lanes replicate no edge, take no end column's coefficients and read inside
+ * their row. */
+struct FFHipUp2Lane { int frame0, fsub, group, edge; };
+__host__ __device__ __forceinline__ FFHipUp2Lane sws_up2_lane(const FFHipUp2Job &J, int fshift, int idx, int lane)
+{
+    FFHipUp2Lane m;
+    const int nf = J.nfull << fshift, e = J.edge;
+    if (idx < nf) {                               /* a whole block of one frame */
+        m.frame0 = idx / J.nfull;
+        m.fsub = 0;
+        const int gbase = (e >> 1) + (idx - m.frame0 * J.nfull) * 64;
+        m.group = gbase + lane;
+        m.edge = !e && (gbase == 0 || gbase + 64 >= J.ngroups);
+    } else if (e) {                               /* both ends of the rows of 64 / e frames */
+        const int esh = e == 16 ? 4 : e == 32 ? 5 : 6, l = lane & (e - 1);
+        m.frame0 = (idx - nf) << (6 - esh);
+        m.fsub = lane >> esh;
+        m.group = l < (e >> 1) ? l : J.ngroups - e + l;
+        m.edge = 1;
+    } else {                                      /* a block of the ragged end: 64 >> fshift lanes of each of the pack's frames */
+        const int lpf = 64 >> fshift, gbase = J.nfull * 64 + (idx - nf) * lpf;
+        m.frame0 = 0;
+        m.fsub = lane >> (6 - fshift);
+        m.group = gbase + (lane & (lpf - 1));
+        m.edge = gbase == 0 || gbase + lpf >= J.ngroups;
+    }
+    return m;
+}
 #ifdef __cplusplus
 #include <vector>
 int  ffhip_up2_virtual_bank(const int16_t *filter, const int32_t *pos, int n_dst, int n_src, std::vector<uint32_t> *out);
 int  ffhip_up2_hco(const std::vector<uint32_t> &h, uint32_t out[16]);
 #endif
-void ffhip_up2_plan_job(FFHipUp2Job *j, int lanes_per_frame, int want_steps);
+/* a job's strips and its units per (pack, strip) from ngroups, its `edge` and the launch's fshift */
+void ffhip_up2_plan_job(FFHipUp2Job *j, int fshift, int want_steps);
+/* unit_begin of every job, units_per_pack and npacks; returns the launch's waves */
+long long ffhip_up2_plan_launch(FFHipUp2Args &A);
 int  ffhip_launch_up2(FFHipUp2Args &A, int depth, int var, hipStream_t stream);
 
 /*

@@ -27,11 +27,19 @@
  *
  * Per 16 output samples: 39 (horizontal, once per source row) + 2 x 20 (vertical) VALU instructions = 4.9 per sample.
  *
- * Geometry: a wave owns 64 lanes x 8 output bytes of a strip of rows and walks down the source rows.  When a row does
- * not fill a whole number of waves (3840 columns = 7.5 x 512) the column blocks at the ragged right end are shared by 2 or
- * 4 FRAMES of the batch (the same strip and columns of frames f, f+1: identical schedule, the frame pitch is part of the
- * lane offset), so no lane idles there; every other wave stays inside one frame — 512 contiguous bytes per store
- * instruction (measured with the arithmetic taken out: 256-byte pieces cost 7 % of the bandwidth).
+ * Geometry: a wave owns 64 lanes x 8 output bytes of a strip of rows and walks down the source rows.  The lanes of a wave
+ * may belong to 2 or 4 FRAMES of the batch (the same strip of frames f, f+1: identical schedule, the frame pitch is part
+ * of the lane offset), and that is where the rows' ends go.  A row of n groups with n % 64 = 0, 32 or 16 (3840 columns =
+ * 480 groups = 7 x 64 + 32) is cut at e / 2 = 32, 16 or 8 groups from either end: the 2 x e / 2 end groups of a frame are e
+ * lanes of an EDGE wave that holds the ends of 64 / e frames side by side, and the n - e groups between them are whole
+ * 64-lane blocks of one frame that start at group e / 2 — 512 contiguous bytes per store instruction (measured with the
+ * arithmetic taken out: 256-byte pieces cost 7 % of the bandwidth), no lane at a row end, loads inside the row by
+ * construction.  Only the edge waves run the row-end code (`border`: the replication and the end columns' own
+ * coefficients, + 40 VALU instructions a row on a plane's 81, + 70 on a pair's 84): one wave in 15 of a pack of two nv12
+ * 1080p frames, where the first block of either frame and the shared last block were three.  Any other n keeps the whole
+ * blocks from group 0 and the blocks at the ragged right end, shared by the 2 or 4 frames of a pack lane block by lane
+ * block so that no lane idles; its first and last blocks are the `border` waves.  sws_up2_unit() / sws_up2_lane()
+ * (sws_kernels.h) are that geometry, for the kernel, the planner and the CPU test alike.
  */
 #include <stdlib.h>
 #include <type_traits>
@@ -230,21 +238,19 @@ __device__ __forceinline__ void up_v8h(uint32_t (&w)[4], const uint32_t (&pa)[8]
  * seven (s[k], s[k+1]) pairs of a plane are its dwords and three v_alignbyte, a pair's come from v_perm as at 8 bits.
  */
 template <int PAIR, int D, int VAR, int HB = 0, int RC = 0, int SC = 0>
-__device__ __forceinline__ void up2_unit(const FFHipUp2Job &J, int frame0, int fshift, int gbase, int strip, int lane, int nframes)
+__device__ __forceinline__ void up2_unit(const FFHipUp2Job &J, int frame0, int fsub, int graw, bool border, int strip, int nframes)
 {
+    /* frame0 (the wave's first frame), border (the wave holds a row end) and strip are wave-uniform; fsub and graw are the lane's frame above
+     * frame0 and its group (sws_up2_lane) */
     /* measurement-only variants (wrong output; tools/sweep_sws.py): 16 never stores, 32 re-reads one source row (48 = both: the
      * arithmetic alone), 64 moves the bytes without arithmetic (the memory pattern alone) */
     constexpr bool DBG_NOST = VAR & 16, DBG_ROW0 = VAR & 32, DBG_COPY = VAR & 64;
     constexpr bool NTS = VAR & 1; /* measured variant: non-temporal stores */
-    const int lpf = 64 >> fshift;                 /* lanes per frame */
-    const int fsub = lane >> (6 - fshift);
-    const int gl = lane & (lpf - 1);
-    const int graw = gbase + gl, fraw = frame0 + fsub;
+    const int fraw = frame0 + fsub;
     const bool act = graw < J.ngroups && fraw < nframes;
     const int g = min(graw, J.ngroups - 1);
     const int fs = fraw < nframes ? fsub : 0;     /* idle lanes shadow valid ones */
     const bool lb = g == 0, rb = g == J.ngroups - 1;
-    const bool border = gbase == 0 || gbase + lpf >= J.ngroups; /* wave-uniform */
 
     const uint32_t soff = (uint32_t)fs * (uint32_t)J.sfp +
                           (uint32_t)(!HB ? (lb ? 0 : rb ? 4 * g - 8 : 4 * g - 4)
@@ -564,32 +570,21 @@ __global__ __launch_bounds__(256) void k_sws_up2(FFHipUp2Args A)
     const uint32_t gw = blk * 4u + (uint32_t)wave;
     if (gw >= (uint32_t)A.units_per_pack * (uint32_t)A.npacks)
         return;
-    const int pack = (int)(gw / (uint32_t)A.units_per_pack);
-    const int u = (int)(gw - (uint32_t)pack * (uint32_t)A.units_per_pack);
-    int j = 0;
-    if (A.njobs > 1 && u >= A.job[1].unit_begin) j = 1;
-    if (A.njobs > 2 && u >= A.job[2].unit_begin) j = 2;
-    const FFHipUp2Job &J = A.job[j];
-    const int local = u - J.unit_begin;
-    /* units of a (pack, strip): the full 64-lane column blocks of each of the pack's frames, then the blocks at the ragged
-     * right end of the rows, which the pack's frames share lane block by lane block */
-    const int strip = local / J.upj, idx = local - strip * J.upj;
-    const int nf = J.nfull << A.fshift;
-    int frame0 = pack << A.fshift, fsh = 0, gbase;
-    if (idx < nf) {
-        const int fsub = idx / J.nfull;
-        frame0 += fsub;
-        gbase = (idx - fsub * J.nfull) * 64;
-        if (frame0 >= A.nframes)
-            return;
-    } else {
-        fsh = A.fshift;
-        gbase = J.nfull * 64 + (idx - nf) * (64 >> fsh);
-    }
+    /* units of a (pack, strip): the whole 64-lane column blocks of each of the pack's frames, then the waves that hold the rows' ends — the two
+     * ends of the rows of 64 / e frames side by side or, for a row that is not 16, 32 or 64 groups more than whole blocks, the blocks at its
+     * ragged right end, which the pack's frames share lane block by lane block (sws_kernels.h) */
+    const FFHipUp2Unit w = sws_up2_unit(A, gw);
+    const FFHipUp2Job &J = A.job[w.job];
+    const FFHipUp2Lane m = sws_up2_lane(J, A.fshift, w.idx, lane);
+    /* the wave's first frame and whether it holds a row end come from the unit alone: SGPRs */
+    const int frame0 = (w.pack << A.fshift) + __builtin_amdgcn_readfirstlane(m.frame0);
+    const bool border = __builtin_amdgcn_readfirstlane(m.edge) != 0;
+    if (frame0 >= A.nframes) /* the batch ends before this wave's first frame */
+        return;
     if (J.pair)
-        up2_unit<1, D, VAR, HB, RC, SC>(J, frame0, fsh, gbase, strip, lane, A.nframes);
+        up2_unit<1, D, VAR, HB, RC, SC>(J, frame0, m.fsub, m.group, border, w.strip, A.nframes);
     else
-        up2_unit<0, D, VAR, HB, RC, SC>(J, frame0, fsh, gbase, strip, lane, A.nframes);
+        up2_unit<0, D, VAR, HB, RC, SC>(J, frame0, m.fsub, m.group, border, w.strip, A.nframes);
 }
 
 /* ================================================================================================== */
@@ -655,14 +650,19 @@ int ffhip_up2_hco(const std::vector<uint32_t> &v, uint32_t out[16])
 }
 
 /* strips of `want` steps (a multiple of 6: the row loop is unrolled six times), evened out over the plane */
-void ffhip_up2_plan_job(FFHipUp2Job *j, int lanes_per_frame, int want)
+void ffhip_up2_plan_job(FFHipUp2Job *j, int fshift, int want)
 {
     const int steps = j->srcH + 1;
     int n = cdiv(steps, want);
     int s = cdiv(cdiv(steps, n), 6) * 6;
     j->steps_per_strip = s;
     j->nstrips = cdiv(steps, s);
-    if (lanes_per_frame == 64) {
+    const int lanes_per_frame = 64 >> fshift;
+    if (j->edge) {
+        /* the whole blocks between the two ends of a row, then the pack's edge waves of 64 / edge frames (the pack holds one at least) */
+        j->nfull = (j->ngroups - j->edge) / 64;
+        j->upj = (j->nfull << fshift) + ((j->edge << fshift) >> 6);
+    } else if (lanes_per_frame == 64) {
         j->nfull = 0; /* one frame per wave throughout: every block is a "tail" block of 64 lanes */
         j->upj = cdiv(j->ngroups, 64);
     } else {
@@ -671,10 +671,8 @@ void ffhip_up2_plan_job(FFHipUp2Job *j, int lanes_per_frame, int want)
     }
 }
 
-int ffhip_launch_up2(FFHipUp2Args &A, int depth, int var, hipStream_t stream)
+long long ffhip_up2_plan_launch(FFHipUp2Args &A)
 {
-    if (A.nframes <= 0)
-        return 0;
     int u = 0;
     for (int i = 0; i < A.njobs; i++) {
         A.job[i].unit_begin = u;
@@ -682,7 +680,14 @@ int ffhip_launch_up2(FFHipUp2Args &A, int depth, int var, hipStream_t stream)
     }
     A.units_per_pack = u;
     A.npacks = (A.nframes + (1 << A.fshift) - 1) >> A.fshift;
-    const long long waves = (long long)u * A.npacks;
+    return (long long)u * A.npacks;
+}
+
+int ffhip_launch_up2(FFHipUp2Args &A, int depth, int var, hipStream_t stream)
+{
+    if (A.nframes <= 0)
+        return 0;
+    const long long waves = ffhip_up2_plan_launch(A);
     if (waves >= (1LL << 31)) {
         ffhip_set_error("ffhip_sws: batch too large for one launch (%lld waves)", waves);
         return FFHIP_EINVAL;

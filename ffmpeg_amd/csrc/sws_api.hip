@@ -1449,22 +1449,34 @@ template <class A> static void put_src(A &a, const SidePlanes &s)
     }
 }
 
+/* the lane offsets of a pack of 1 << fsft frames (frame pitches included) stay below 2^31 in every job */
+static bool up2_span_fits(const FFHipUp2Args &U, int fsft)
+{
+    for (int i = 0; i < U.njobs; i++) {
+        const FFHipUp2Job &j = U.job[i];
+        const unsigned long long span_s = (unsigned long long)((1 << fsft) - 1) * j.sfp + (unsigned long long)j.srcH * (size_t)(j.sstride < 0 ? -j.sstride : j.sstride);
+        const unsigned long long span_d = (unsigned long long)((1 << fsft) - 1) * j.dfp + 2ull * j.srcH * (size_t)(j.dstride < 0 ? -j.dstride : j.dstride);
+        if (span_s >= (1ull << 31) || span_d >= (1ull << 31))
+            return false;
+    }
+    return true;
+}
+
 /* frames per wave of the exact-2x kernel (1 << fshift): the split that wastes the fewest lanes at the right edge of the rows, among those
- * whose lane offsets (frame pitches included) stay below 2^31; -1 when none does */
-static int up2_fshift(const FFHipUp2Args &U, int nframes)
+ * whose lane offsets stay below 2^31; -1 when none does.  The waste is counted over the jobs of `mask` (the ones with a ragged end), the
+ * offsets over all of them. */
+static int up2_fshift(const FFHipUp2Args &U, int nframes, unsigned mask = 7)
 {
     int best = -1;
     double bestw = 1e30;
     for (int fsft = 0; fsft <= 2; fsft++) {
         const int lpf = 64 >> fsft;
-        bool fits = !(nframes < (1 << fsft) && fsft);
+        const bool fits = !(nframes < (1 << fsft) && fsft) && up2_span_fits(U, fsft);
         double w = 0;
         for (int i = 0; i < U.njobs; i++) {
             const FFHipUp2Job &j = U.job[i];
-            const unsigned long long span_s = (unsigned long long)((1 << fsft) - 1) * j.sfp + (unsigned long long)j.srcH * (size_t)(j.sstride < 0 ? -j.sstride : j.sstride);
-            const unsigned long long span_d = (unsigned long long)((1 << fsft) - 1) * j.dfp + 2ull * j.srcH * (size_t)(j.dstride < 0 ? -j.dstride : j.dstride);
-            if (span_s >= (1ull << 31) || span_d >= (1ull << 31))
-                fits = false;
+            if (!(mask >> i & 1))
+                continue;
             /* waves per frame and strip: the full blocks, plus this frame's share of the shared ragged-end blocks */
             const int nfull = fsft ? j.ngroups / 64 : 0;
             w += ((double)nfull + (double)cdiv(j.ngroups - nfull * 64, lpf) / (1 << fsft)) * j.srcH;
@@ -1475,6 +1487,76 @@ static int up2_fshift(const FFHipUp2Args &U, int nframes)
         }
     }
     return best;
+}
+
+/* The geometry of a launch of the exact-2x kernel: U.fshift and every job's `edge`; -1 when no split keeps the lane offsets in range.
+ * A job whose rows are 16, 32 or 64 groups more than whole blocks (sws_up2_edge_lanes) takes the edge layout: the ends of its rows in waves
+ * of 64 / e frames, so one wave in 15 of nv12 1080p runs the row-end code where three did.  The pack is the largest any job needs: an edge
+ * wave's frames, or what up2_fshift() picks for the jobs that keep their ragged end.  Where that pack's offsets do not fit, and under `forced`
+ * (a pack of 1 << forced frames) or !edge_ok (measure build: FFHIP_UP2_FSHIFT, FFHIP_UP2_EDGE=0), every job keeps the ragged end. */
+static int up2_layout(FFHipUp2Args &U, int nframes, int forced, bool edge_ok)
+{
+    for (int i = 0; i < U.njobs; i++)
+        U.job[i].edge = 0;
+    if (forced >= 0)
+        return U.fshift = forced;
+    int need = -1;
+    unsigned ragged = 0;
+    for (int i = 0; i < U.njobs && edge_ok; i++) {
+        const int e = sws_up2_edge_lanes(U.job[i].ngroups);
+        if (e)
+            need = std::max(need, e == 64 ? 0 : e == 32 ? 1 : 2);
+        else
+            ragged |= 1u << i;
+    }
+    if (need >= 0) {
+        const int fs = ragged ? up2_fshift(U, nframes, ragged) : 0;
+        if (fs >= 0 && up2_span_fits(U, std::max(need, fs))) {
+            for (int i = 0; i < U.njobs; i++)
+                U.job[i].edge = sws_up2_edge_lanes(U.job[i].ngroups);
+            return U.fshift = std::max(need, fs);
+        }
+    }
+    const int fs = up2_fshift(U, nframes);
+    U.fshift = fs < 0 ? 0 : fs;
+    return fs;
+}
+
+extern "C" int ffhip_sws_up2_walk_host(int ngroups, int src_h, int nframes, int want_steps, int fshift, int32_t *out, size_t out_ints, int32_t info[4])
+{
+    if (ngroups < 1 || src_h < 1 || nframes < 1 || want_steps < 1 || fshift > 2 || !info)
+        return FFHIP_EINVAL;
+    /* one plane job of tightly packed rows, planned as scale_batch() plans it */
+    FFHipUp2Args U;
+    memset(&U, 0, sizeof(U));
+    U.nframes = nframes;
+    U.njobs = 1;
+    FFHipUp2Job &j = U.job[0];
+    j.ngroups = ngroups; j.srcW = 4 * ngroups; j.srcH = src_h;
+    j.sstride = 4 * ngroups; j.dstride = 8 * ngroups;
+    j.sfp = (size_t)j.sstride * src_h; j.dfp = (size_t)j.dstride * 2 * src_h;
+    if (up2_layout(U, nframes, fshift < 0 ? -1 : fshift, true) < 0)
+        return FFHIP_EINVAL;
+    ffhip_up2_plan_job(&j, U.fshift, want_steps);
+    const long long waves = ffhip_up2_plan_launch(U);
+    info[0] = j.edge; info[1] = U.fshift; info[2] = j.upj; info[3] = j.nstrips;
+    if (waves >= (1LL << 24))
+        return FFHIP_EINVAL;
+    if (!out)
+        return (int)waves;
+    if (out_ints < (size_t)waves * 64 * 4)
+        return FFHIP_ENOMEM;
+    for (uint32_t gw = 0; gw < (uint32_t)waves; gw++) {
+        const FFHipUp2Unit w = sws_up2_unit(U, gw);
+        for (int lane = 0; lane < 64; lane++) {
+            const FFHipUp2Lane m = sws_up2_lane(U.job[w.job], U.fshift, w.idx, lane);
+            const int f = (w.pack << U.fshift) + m.frame0 + m.fsub;
+            int32_t *o = out + ((size_t)gw * 64 + lane) * 4;
+            o[0] = f < nframes && m.group < ngroups ? f : -1; /* what up2_unit() calls an active lane */
+            o[1] = w.strip; o[2] = m.group; o[3] = m.edge;
+        }
+    }
+    return (int)waves;
 }
 
 /* a context with a side above 8 bits: luma, then the two chroma channels (planes of their own or the halves of an interleaved pair) */
@@ -1549,11 +1631,10 @@ static int scale16(FFHipSwsContext *c, int nframes, const void *const src[4], co
         });
         /* frames per wave as at 8 bits; when no split keeps the lane offsets in range this side takes the next kernel (the 8-bit side
          * launches with fshift 0) */
-        const int fs = up2_fshift(U, nframes);
+        const int fs = up2_layout(U, nframes, -1, !knob_is("FFHIP_UP2_EDGE", '0') /* measure build: 0 keeps the shared ragged end */);
         if (fs >= 0) {
-            U.fshift = fs;
             for (int i = 0; i < U.njobs; i++)
-                ffhip_up2_plan_job(&U.job[i], 64 >> U.fshift, 60);
+                ffhip_up2_plan_job(&U.job[i], U.fshift, 60);
             const char *ev2 = FFHIP_KNOB("FFHIP_UP2_VAR"); /* measure build: rows in flight (FFHIP_UP2_DEPTH), 1 = non-temporal stores */
             /* six rows in flight (round 6, with the straight-line rows: p010 1080p -> 4K 0.615 -> 0.63, planar unchanged) */
             return ffhip_launch_up2(U, knob_is("FFHIP_UP2_DEPTH", '3') ? 3 : 6, ev2 ? atoi(ev2) : 0, stream);
@@ -2346,8 +2427,8 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
             U.xcd = ex ? atoi(ex) : 1;     /* measure build: 0 plain numbering, 1 an eighth per XCD (the product), 1 + k chunks of 2^k workgroups */
             /* frames per wave (up2_fshift); when no split keeps the lane offsets in range this side launches with fshift 0 (the 16-bit side
              * takes the next kernel) */
-            const int fs = up2_fshift(U, nframes);
-            U.fshift = ef && ef[0] >= '0' && ef[0] <= '2' ? ef[0] - '0' : fs < 0 ? 0 : fs;
+            /* measure build: FFHIP_UP2_FSHIFT fixes the pack and FFHIP_UP2_EDGE=0 the product's; either keeps every row's shared ragged end */
+            (void)up2_layout(U, nframes, ef && ef[0] >= '0' && ef[0] <= '2' ? ef[0] - '0' : -1, !knob_is("FFHIP_UP2_EDGE", '0'));
             bool jneg = false;
             for (int i = 0; i < U.njobs; i++)
                 jneg = jneg || U.job[i].sstride < 0 || U.job[i].dstride < 0;
@@ -2360,7 +2441,7 @@ static int scale_batch_dev(FFHipSwsContext *c, int nframes, const void *const sr
                 for (int w = 0; w < 4; w++) {
                     long long u = 0;
                     for (int i = 0; i < U.njobs; i++) {
-                        ffhip_up2_plan_job(&U.job[i], 64 >> U.fshift, es && atoi(es) > 0 ? atoi(es) : wants[w]);
+                        ffhip_up2_plan_job(&U.job[i], U.fshift, es && atoi(es) > 0 ? atoi(es) : wants[w]);
                         u += (long long)U.job[i].upj * U.job[i].nstrips;
                     }
                     if ((es && atoi(es) > 0) || u * ((nframes + (1 << U.fshift) - 1) >> U.fshift) >= 8192)

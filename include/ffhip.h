@@ -331,6 +331,14 @@ int              ffhip_sws_mfma_tiles_host(const int16_t *filter, const int32_t 
  *  int16 pairs.  Returns 1, or 0 when some tap of the bank does not sit on its regular window (the kernel is then not
  *  used).  Exposed for the CPU test-suite. */
 int              ffhip_sws_up2_virtual_bank_host(const int16_t *filter, const int32_t *pos, int n_dst, int n_src, uint32_t *out);
+/** The geometry of a launch of the exact-2x kernel (no device needed): plans one plane of `ngroups` 8-byte destination groups per row and
+ *  src_h source rows in a batch of nframes frames, strips of about want_steps rows, the way the scaler plans it, and walks the launch through
+ *  the inline functions the kernel itself calls.  fshift < 0: the product's choice — rows of ngroups % 64 = 0, 32 or 16 gather their two ends
+ *  into waves of 1, 2 or 4 frames; 0..2: packs of 1 << fshift frames that share the rows' ragged end.  out (or NULL): 4 int32 per (wave, lane) —
+ *  the frame (-1: the lane idles), the strip, the group in the row, whether the wave holds a row end.  info: the edge lanes per frame (0: ragged
+ *  end), fshift, units per (pack, strip), strips.  Returns the launch's waves, FFHIP_ENOMEM when out_ints < 256 x waves, or FFHIP_EINVAL.
+ *  Exposed for the CPU test-suite. */
+int              ffhip_sws_up2_walk_host(int ngroups, int src_h, int nframes, int want_steps, int fshift, int32_t *out, size_t out_ints, int32_t info[4]);
 /** The same at `ratio` 2 or 4 (round 5; sws_up2rgb.hip: a packed-RGB target has a chroma line per output line, so 4:2:0 chroma goes up
  *  four times vertically — output y on the regular window start ((y + 2) >> 2) - 2).  ratio 2 == the call above. */
 int              ffhip_sws_upn_virtual_bank_host(const int16_t *filter, const int32_t *pos, int n_dst, int n_src, int ratio, uint32_t *out);
