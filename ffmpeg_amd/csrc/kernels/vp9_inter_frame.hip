@@ -11,12 +11,13 @@
  *   3. after a barrier, stores the covered samples inside the decoded area to the plane, four at a time where a quad is covered.
  * What no record covers (intra blocks, the stride padding, anything outside the decoded area) is never written.
  *
- * Interpolation is vp9dsp_template.c's (the oracle's ffo_vp9_mc_bd): 8-tap passes clip((sum + 64) >> 7), the 2-D form through
- * pixel-type temporaries of rows -3 .. h + 3 (wave-private LDS), bilinear a + ((m (b - a) + 8) >> 4) over rows 0 .. h, full-sample
- * copies.  Every reference sample is fetched with its coordinates clamped to the reference's real size, which is what
- * emulated_edge_mc gives mc_luma_unscaled / mc_chroma_unscaled, so MVs may point anywhere.  A lane computes one sample at a time;
- * block sizes are powers of two, so a block's samples are spread over the wave by shifts.  Records are checked before they are used
- * (include/ffhip.h lists what is malformed); a malformed record or TU is skipped.
+ * Interpolation is vp9dsp_template.c's (the oracle's ffo_vp9_mc_bd) as vp9_mc_rules.h states it: 8-tap passes
+ * clip((sum + 64) >> 7), the 2-D form through pixel-type temporaries of rows -3 .. h + 3 (wave-private LDS), bilinear
+ * a + ((m (b - a) + 8) >> 4) over rows 0 .. h, full-sample copies.  Every reference sample is fetched with its coordinates
+ * clamped to the reference's real size, which is what emulated_edge_mc gives mc_luma_unscaled / mc_chroma_unscaled, so MVs may
+ * point anywhere.  A lane computes one sample at a time; block sizes are powers of two, so a block's samples are spread over the
+ * wave by shifts.  Records are checked before they are used (include/ffhip.h lists what is malformed); a malformed record or TU is
+ * skipped.
  *
  * ffhip_vp9_inter_frames_scaled_dev() runs the SCALED instantiation when a launch has a reference of another size: each reference
  * carries its own real size, scale and step (staged behind the frames in the same progress-pool slot), and a record of the SCALED
@@ -32,6 +33,7 @@
 #include "common.h"
 #include "h264_kernels.h"
 #include "vp9_itxfm_tile.h"
+#include "vp9_mc_rules.h"
 
 static_assert(sizeof(FFHipVp9InterPred) == 20, "FFHipVp9InterPred is a 20-byte record");
 static_assert(sizeof(FFHipVp9InterTU) == 12, "FFHipVp9InterTU is a 12-byte record");
@@ -49,22 +51,6 @@ static_assert(VIF_PICS * (sizeof(FFHipVp9InterPic) + sizeof(VifRefScale)) <= FFH
               "a scaled launch's frames and reference scales fit one slot");
 
 namespace {
-/* ff_vp9_subpel_filters (libavcodec/vp9dsp.c): [filter 0 smooth / 1 regular / 2 sharp][m in sixteenths][tap]; m = 0 is never used */
-__constant__ int8_t vif_taps[3][16][8] = {
-    { { 0 }, { -3, -1, 32, 64, 38, 1, -3, 0 }, { -2, -2, 29, 63, 41, 2, -3, 0 }, { -2, -2, 26, 63, 43, 4, -4, 0 },
-      { -2, -3, 24, 62, 46, 5, -4, 0 }, { -2, -3, 21, 60, 49, 7, -4, 0 }, { -1, -4, 18, 59, 51, 9, -4, 0 }, { -1, -4, 16, 57, 53, 12, -4, -1 },
-      { -1, -4, 14, 55, 55, 14, -4, -1 }, { -1, -4, 12, 53, 57, 16, -4, -1 }, { 0, -4, 9, 51, 59, 18, -4, -1 }, { 0, -4, 7, 49, 60, 21, -3, -2 },
-      { 0, -4, 5, 46, 62, 24, -3, -2 }, { 0, -4, 4, 43, 63, 26, -2, -2 }, { 0, -3, 2, 41, 63, 29, -2, -2 }, { 0, -3, 1, 38, 64, 32, -1, -3 } },
-    { { 0 }, { 0, 1, -5, 126, 8, -3, 1, 0 }, { -1, 3, -10, 122, 18, -6, 2, 0 }, { -1, 4, -13, 118, 27, -9, 3, -1 },
-      { -1, 4, -16, 112, 37, -11, 4, -1 }, { -1, 5, -18, 105, 48, -14, 4, -1 }, { -1, 5, -19, 97, 58, -16, 5, -1 }, { -1, 6, -19, 88, 68, -18, 5, -1 },
-      { -1, 6, -19, 78, 78, -19, 6, -1 }, { -1, 5, -18, 68, 88, -19, 6, -1 }, { -1, 5, -16, 58, 97, -19, 5, -1 }, { -1, 4, -14, 48, 105, -18, 5, -1 },
-      { -1, 4, -11, 37, 112, -16, 4, -1 }, { -1, 3, -9, 27, 118, -13, 4, -1 }, { 0, 2, -6, 18, 122, -10, 3, -1 }, { 0, 1, -3, 8, 126, -5, 1, 0 } },
-    { { 0 }, { -1, 3, -7, 127, 8, -3, 1, 0 }, { -2, 5, -13, 125, 17, -6, 3, -1 }, { -3, 7, -17, 121, 27, -10, 5, -2 },
-      { -4, 9, -20, 115, 37, -13, 6, -2 }, { -4, 10, -23, 108, 48, -16, 8, -3 }, { -4, 10, -24, 100, 59, -19, 9, -3 }, { -4, 11, -24, 90, 70, -21, 10, -4 },
-      { -4, 11, -23, 80, 80, -23, 11, -4 }, { -4, 10, -21, 70, 90, -24, 11, -4 }, { -3, 9, -19, 59, 100, -24, 10, -4 }, { -3, 8, -16, 48, 108, -23, 10, -4 },
-      { -2, 6, -13, 37, 115, -20, 9, -4 }, { -2, 5, -10, 27, 121, -17, 7, -3 }, { -1, 3, -6, 17, 125, -13, 5, -2 }, { 0, 1, -3, 8, 127, -7, 3, -1 } },
-};
-
 constexpr int TILE = 64;          /* the tile's row pitch: a superblock plane is at most 64 x 64 */
 constexpr int TROWS = 64 + 7;     /* rows of the 2-D form's horizontal pass */
 
@@ -82,33 +68,18 @@ __device__ __forceinline__ int vif_ref(const VifSrc &s, int x, int y)
     return reinterpret_cast<const PIX *>(s.base + (ptrdiff_t)cy * s.stride)[cx];
 }
 
-/* one pass of mc[!!mx][!!my] at phase m over taps at(k) = the sample k steps along the pass (k = -3 .. 4) */
-template <typename AT>
-__device__ __forceinline__ int vif_tap(int filter, int m, int maxv, AT at)
-{
-    if (filter == 3) {
-        const int a = at(0);
-        return a + ((m * (at(1) - a) + 8) >> 4);
-    }
-    const int8_t *f = vif_taps[filter][m];
-    int sum = 64;
-#pragma unroll
-    for (int t = 0; t < 8; t++)
-        sum += f[t] * at(t - 3);
-    return min(max(sum >> 7, 0), maxv);
-}
-
 /* put (AVG false) or avg (AVG true) of a w x h block at tile position (lx, ly); tmp: the wave's temporaries */
 template <typename PIX, bool AVG>
 __device__ __forceinline__ void vif_predict(uint16_t *tile, PIX *tmp, const VifSrc &s, int lx, int ly, int lgw, int h, int filter, int maxv,
                                             int lane)
 {
     const int w = 1 << lgw;
-    if (s.mx && s.my) { /* the horizontal pass over rows -3 .. h + 3 (bilinear: 0 .. h) into pixel temporaries */
+    if (s.mx && s.my) { /* the horizontal pass over rows -3 .. h + 3 (bilinear: 0 .. h) into pixel temporaries: vp9mc_before() and
+                         * vp9mc_rows() at a step of 16, written out (as the calls, the 16-bit kernels take one VGPR more) */
         const int r0 = filter == 3 ? 0 : -3, rows = filter == 3 ? h + 1 : h + 7;
         for (int i = lane; i < rows << lgw; i += 64) {
             const int r = i >> lgw, x = i & (w - 1), yy = s.yi + r + r0;
-            tmp[r * TILE + x] = (PIX)vif_tap(filter, s.mx, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x + k, yy); });
+            tmp[r * TILE + x] = (PIX)vp9mc_pass(filter, s.mx, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x + k, yy); });
         }
         ffhip_wave_sync();
     }
@@ -117,22 +88,22 @@ __device__ __forceinline__ void vif_predict(uint16_t *tile, PIX *tmp, const VifS
         int v;
         if (s.mx && s.my) {
             const PIX *t = tmp + (y + (filter == 3 ? 0 : 3)) * TILE + x;
-            v = vif_tap(filter, s.my, maxv, [&](int k) { return (int)t[k * TILE]; });
+            v = vp9mc_pass(filter, s.my, maxv, [&](int k) { return (int)t[k * TILE]; });
         } else if (s.mx) {
-            v = vif_tap(filter, s.mx, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x + k, s.yi + y); });
+            v = vp9mc_pass(filter, s.mx, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x + k, s.yi + y); });
         } else if (s.my) {
-            v = vif_tap(filter, s.my, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x, s.yi + y + k); });
+            v = vp9mc_pass(filter, s.my, maxv, [&](int k) { return vif_ref<PIX>(s, s.xi + x, s.yi + y + k); });
         } else {
             v = vif_ref<PIX>(s, s.xi + x, s.yi + y);
         }
         uint16_t &d = tile[(ly + y) * TILE + lx + x];
-        d = (uint16_t)(AVG ? (d + v + 1) >> 1 : v);
+        d = (uint16_t)(AVG ? vp9mc_avg(d, v) : v);
     }
     ffhip_wave_sync(); /* tmp is reused by the next pass; an avg pass reads what this lane's put wrote */
 }
 
 constexpr int SROWS = 32; /* output rows per strip of the scaled 2-D form */
-static_assert(((15 + (SROWS - 1) * 32) >> 4) + 8 <= TROWS, "a strip's horizontal pass fits the temporaries at any step up to 32");
+static_assert(vp9mc_rows(0, 15, SROWS, 32) <= TROWS, "a strip's horizontal pass fits the temporaries at any step up to 32");
 
 /* smc (vp9dsp_template.c, the oracle's ffo_vp9_smc_bd), put or avg of a w x h block at tile position (lx, ly) with steps dx, dy: the
  * horizontal pass over the rows a strip of output rows reads, into pixel temporaries, then the vertical pass.  Phase 0 is a copy */
@@ -140,22 +111,21 @@ template <typename PIX, bool AVG>
 __device__ __forceinline__ void vif_predict_scaled(uint16_t *tile, PIX *tmp, const VifSrc &s, int dx, int dy, int lx, int ly, int lgw, int h,
                                                    int filter, int maxv, int lane)
 {
-    const int w = 1 << lgw, before = filter == 3 ? 0 : 3, extra = filter == 3 ? 2 : 8;
-    auto tap = [&](int m, auto at) { return m ? vif_tap(filter, m, maxv, at) : at(0); };
+    const int w = 1 << lgw, before = vp9mc_before(filter);
     for (int y0 = 0; y0 < h; y0 += SROWS) {
-        const int sh = min(h - y0, SROWS), p0 = s.my + y0 * dy, m0 = p0 & 15;
-        const int ry = s.yi + (p0 >> 4) - before, rows = ((m0 + (sh - 1) * dy) >> 4) + extra;
+        const int sh = min(h - y0, SROWS), p0 = vp9mc_pos(s.my, y0, dy), m0 = vp9mc_frac(p0);
+        const int ry = s.yi + vp9mc_whole(p0) - before, rows = vp9mc_rows(filter, m0, sh, dy);
         for (int i = lane; i < rows << lgw; i += 64) {
-            const int r = i >> lgw, x = i & (w - 1), pos = s.mx + x * dx, xx = s.xi + (pos >> 4);
-            tmp[r * TILE + x] = (PIX)tap(pos & 15, [&](int k) { return vif_ref<PIX>(s, xx + k, ry + r); });
+            const int r = i >> lgw, x = i & (w - 1), pos = vp9mc_pos(s.mx, x, dx), xx = s.xi + vp9mc_whole(pos);
+            tmp[r * TILE + x] = (PIX)vp9mc_pass0(filter, vp9mc_frac(pos), maxv, [&](int k) { return vif_ref<PIX>(s, xx + k, ry + r); });
         }
         ffhip_wave_sync();
         for (int i = lane; i < sh << lgw; i += 64) {
-            const int y = i >> lgw, x = i & (w - 1), pos = m0 + y * dy;
-            const PIX *t = tmp + ((pos >> 4) + before) * TILE + x;
-            const int v = tap(pos & 15, [&](int k) { return (int)t[k * TILE]; });
+            const int y = i >> lgw, x = i & (w - 1), pos = vp9mc_pos(m0, y, dy);
+            const PIX *t = tmp + (vp9mc_whole(pos) + before) * TILE + x;
+            const int v = vp9mc_pass0(filter, vp9mc_frac(pos), maxv, [&](int k) { return (int)t[k * TILE]; });
             uint16_t &d = tile[(ly + y0 + y) * TILE + lx + x];
-            d = (uint16_t)(AVG ? (d + v + 1) >> 1 : v);
+            d = (uint16_t)(AVG ? vp9mc_avg(d, v) : v);
         }
         ffhip_wave_sync(); /* the next strip or pass reuses tmp */
     }
