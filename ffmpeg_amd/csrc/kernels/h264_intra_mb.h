@@ -20,13 +20,16 @@
  *   - the host emulation (oracle/emul_h264_intra.cpp, test infrastructure): a phase = for (lane = 0..63) body(lane) — it pins
  *     this logic against the oracle's restatement of hl_decode_mb() on the CPU, where there is no GPU to run the kernel.
  *
- * The prediction rules are the per-sample rules over the block's edge line that h264_pred.hip uses (h264pred_template.c).
+ * The prediction rules — the directional rules over a block's edge line, which neighbours a block mode reads, the plane predictor and
+ * the DCs — are h264_pred_rules.h's, shared with h264_pred.hip.  The tables below (imb_p4_entry, imb_p4_tab, imb_p8_edge_tab, imb_p8_tab)
+ * are those directional rules solved for the tile's layout, checked against them by tests/h264_pred_rules_check.cpp.
  */
 #ifndef FFHIP_H264_INTRA_MB_H
 #define FFHIP_H264_INTRA_MB_H
 #include <stdint.h>
 
 #include "ffhip.h"
+#include "h264_pred_rules.h"
 #include "h264_tx_rules.h"
 
 #if defined(__HIPCC__)
@@ -36,119 +39,6 @@
 #define IMB_FN static inline
 #define IMB_MEM inline
 #endif
-
-/* ---- prediction rules over the edge line e[]: left column bottom-up, corner, row above, top-right ---- */
-IMB_FN int hp_a2(int a, int b) { return (a + b + 1) >> 1; }
-IMB_FN int hp_a3(int a, int b, int c) { return (a + 2 * b + c + 2) >> 2; }
-
-/* neighbours a pred4x4 / pred8x8l mode reads: bit0 left, bit1 top, bit2 corner, bit3 top-right (h264pred.h:35-48 order) */
-IMB_FN unsigned hp_need(int mode)
-{
-    /* 12 nibbles, mode 0 in the low one: V=2 H=1 DC=3 DDL=a DDR=7 VR=7 HD=7 VL=a HU=1 LEFT_DC=1 TOP_DC=2 DC_128=0 */
-    return (unsigned)(0x0211a777a312ull >> (4 * mode)) & 15u;
-}
-
-/* the edge line as a callable e(k) (an array in LDS, or the tile read in place) */
-struct HpArr {
-    const int *p;
-    IMB_MEM int operator()(int k) const { return p[k]; }
-};
-
-template <int N, class E>
-IMB_FN int hp_dir_sample_e(int mode, const E &e, int x, int y, int dc)
-{
-    auto T = [&](int k) { return e(N + 1 + k); };
-    switch (mode) {
-    case 0: return T(x);
-    case 1: return e(N - 1 - y);
-    case 3: {
-        const int i = x + y;
-        return i < 2 * N - 2 ? hp_a3(T(i), T(i + 1), T(i + 2)) : (T(2 * N - 2) + 3 * T(2 * N - 1) + 2) >> 2;
-    }
-    case 4: {
-        const int i = N - 1 - y + x;
-        return hp_a3(e(i), e(i + 1), e(i + 2));
-    }
-    case 5: {
-        const int d = 2 * x - y, h = d >> 1;
-        if (d < 0)
-            return hp_a3(e(N + d), e(N + d + 1), e(N + d + 2));
-        return (d & 1) ? hp_a3(e(N + h), e(N + h + 1), e(N + h + 2)) : hp_a2(e(N + h), e(N + h + 1));
-    }
-    case 6: {
-        const int d = 2 * y - x, h = d >> 1;
-        if (d < 0)
-            return hp_a3(e(N - d - 2), e(N - d - 1), e(N - d));
-        return (d & 1) ? hp_a3(e(N - h), e(N - h - 1), e(N - h - 2)) : hp_a2(e(N - h), e(N - h - 1));
-    }
-    case 7: {
-        const int i = (y >> 1) + x;
-        return (y & 1) ? hp_a3(T(i), T(i + 1), T(i + 2)) : hp_a2(T(i), T(i + 1));
-    }
-    case 8: {
-        const int i = 2 * y + x, j = N - 1 - (i >> 1);
-        if (i >= 2 * N - 2)
-            return e(0);
-        if (i == 2 * N - 3)
-            return (e(1) + 3 * e(0) + 2) >> 2;
-        return (i & 1) ? hp_a3(e(j), e(j - 1), e(j - 2)) : hp_a2(e(j), e(j - 1));
-    }
-    default: return dc;
-    }
-}
-
-template <int N>
-IMB_FN int hp_dir_sample(int mode, const int *e, int x, int y, int dc)
-{
-    return hp_dir_sample_e<N>(mode, HpArr{ e }, x, y, dc);
-}
-
-/* the DC of modes 2 (both sides), 9 (LEFT_DC), 10 (TOP_DC); 128 otherwise */
-template <int N, class E>
-IMB_FN int hp_dir_dc_e(int mode, const E &e, int mid = 128 /* 1 << (bit_depth - 1) */)
-{
-    if (mode != 2 && mode != 9 && mode != 10)
-        return mid;
-    int sl = 0, st = 0;
-    for (int i = 0; i < N; i++) {
-        sl += mode != 10 ? e(i) : 0;
-        st += mode != 9 ? e(N + 1 + i) : 0;
-    }
-    return mode == 2 ? (sl + st + N) >> (N == 8 ? 4 : 3) : ((mode == 9 ? sl : st) + N / 2) >> (N == 8 ? 3 : 2);
-}
-
-template <int N>
-IMB_FN int hp_dir_dc(int mode, const int *e)
-{
-    return hp_dir_dc_e<N>(mode, HpArr{ e });
-}
-
-/* PREDICT_8x8_LOAD_LEFT / _TOP / _TOPRIGHT / _TOPLEFT (h264pred_template.c:822-856): entry j of the low-pass filtered line from
- * the raw line w(0..24); entries the mode does not read are 0 */
-template <class W>
-IMB_FN int hp_filter8_e(const W &w, int j, unsigned need, bool tl, bool tr)
-{
-    if (j < 8) {
-        if (!(need & 1))
-            return 0;
-        return j == 7 ? hp_a3(tl ? w(8) : w(7), w(7), w(6)) : j == 0 ? (w(1) + 3 * w(0) + 2) >> 2 : hp_a3(w(j + 1), w(j), w(j - 1));
-    }
-    if (j == 8)
-        return (need & 4) ? hp_a3(w(7), w(8), w(9)) : 0;
-    if (j < 17) {
-        if (!(need & 2))
-            return 0;
-        return j == 9 ? hp_a3(tl ? w(8) : w(9), w(9), w(10)) : j == 16 ? hp_a3(tr ? w(17) : w(16), w(16), w(15)) : hp_a3(w(j - 1), w(j), w(j + 1));
-    }
-    if (!(need & 8))
-        return 0;
-    return !tr ? w(16) : j == 24 ? (w(23) + 3 * w(24) + 2) >> 2 : hp_a3(w(j - 1), w(j), w(j + 1));
-}
-
-IMB_FN int hp_filter8(const int *w, int j, unsigned need, bool tl, bool tr)
-{
-    return hp_filter8_e(HpArr{ w }, j, need, tl, tr);
-}
 
 /* ---- the tile ---- */
 /* the tile's coefficient type under the name the host emulation takes it by (oracle/emul_h264_intra.cpp, emul_h264_mbaff.cpp: the
@@ -292,58 +182,6 @@ IMB_FN void imb_resid4_col(const CF *b, int dc, bool dconly, int x, int out[4], 
         out[y] = h264tx_bfly4(y, r[0], r[1], r[2], r[3]) >> 6;
 }
 
-/* pred8x8 (N = 8, with the one-sided "mad cow" DC variants) / pred16x16 (N = 16) sample (x, y); t / l index the tile's row above
- * and left column through TOP(i) / LEFT(i), i = -1 the corner (h264pred_template.c:389-820; modes h264pred.h:67-82) */
-template <int N, typename PIX = uint8_t, class Top, class Left>
-IMB_FN int imb_pred_blk(int mode, int x, int y, Top TOP, Left LEFT, int maxv = 255)
-{
-    const int mid = (maxv + 1) >> 1;
-    constexpr int H2 = N / 2;
-    if (mode == 1)
-        return LEFT(y);
-    if (mode == 2)
-        return TOP(x);
-    if (mode == 3) {
-        int H = 0, V = 0;
-        for (int i = 1; i <= H2; i++) {
-            H += i * (TOP(H2 - 1 + i) - TOP(H2 - 1 - i));
-            V += i * (LEFT(H2 - 1 + i) - (i == H2 ? TOP(-1) : LEFT(H2 - 1 - i)));
-        }
-        H = N == 16 ? (5 * H + 32) >> 6 : (17 * H + 16) >> 5;
-        V = N == 16 ? (5 * V + 32) >> 6 : (17 * V + 16) >> 5;
-        const int a = 16 * (LEFT(N - 1) + TOP(N - 1) + 1) - (H2 - 1) * (V + H);
-        return imb_clip<PIX>((a + y * V + x * H) >> 5, maxv);
-    }
-    if (N == 16) {
-        int sl = 0, st = 0;
-        for (int i = 0; i < 16; i++) {
-            sl += (mode == 0 || mode == 4) ? LEFT(i) : 0;
-            st += (mode == 0 || mode == 5) ? TOP(i) : 0;
-        }
-        return mode == 0 ? (sl + st + 16) >> 5 : mode == 4 ? (sl + 8) >> 4 : mode == 5 ? (st + 8) >> 4 : mid;
-    }
-    const bool ut = mode == 0 || mode == 5 || mode == 7 || mode == 8, ul = mode == 0 || mode == 4 || mode >= 7;
-    int t0 = 0, t1 = 0, l0 = 0, l1 = 0;
-    for (int i = 0; i < 4; i++) {
-        t0 += ut ? TOP(i) : 0;
-        t1 += ut ? TOP(4 + i) : 0;
-        l0 += ul ? LEFT(i) : 0;
-        l1 += (ul && mode != 7) ? LEFT(4 + i) : 0;
-    }
-    int q0 = mid, q1 = mid, q2 = mid, q3 = mid;
-    switch (mode) {
-    case 0: q0 = (t0 + l0 + 4) >> 3; q1 = (t1 + 2) >> 2; q2 = (l1 + 2) >> 2; q3 = (t1 + l1 + 4) >> 3; break;
-    case 4: q0 = q1 = (l0 + 2) >> 2; q2 = q3 = (l1 + 2) >> 2; break;
-    case 5: q0 = q2 = (t0 + 2) >> 2; q1 = q3 = (t1 + 2) >> 2; break;
-    case 7: q0 = (t0 + l0 + 4) >> 3; q2 = (t0 + 2) >> 2; q1 = q3 = (t1 + 2) >> 2; break;
-    case 8: q0 = (t0 + 2) >> 2; q1 = (t1 + 2) >> 2; q2 = (l1 + 2) >> 2; q3 = (t1 + l1 + 4) >> 3; break;
-    case 9: q0 = q1 = (l0 + 2) >> 2; break;
-    case 10: q2 = q3 = (l1 + 2) >> 2; break;
-    default: break;
-    }
-    return (y >> 2) ? ((x >> 2) ? q3 : q2) : ((x >> 2) ? q1 : q0);
-}
-
 /* ---- pred4x4 as a table: every directional rule is (w0 e[i0] + w1 e[i1] + w2 e[i2] + 2) >> 2 with weights (1, 2, 1), (2, 2, 0) or
  * (4, 0, 0) — hp_a3, hp_a2, a copy — over the edge line.  imb_p4_entry() is hp_dir_sample_e<4> solved for (i0, i1, i2, kind): bits 0-3,
  * 4-7, 8-11 the three indices, bits 12-13 the kind (0 a3, 1 a2, 2 copy): the switch yields three indices, the edge reads and the
@@ -482,9 +320,9 @@ IMB_FN uint32_t imb_tab(int idx)
     return idx < IMB_P4_TAB ? imb_p4_tab(idx) : idx < IMB_P4_TAB + IMB_P8_EDGE_TAB ? imb_p8_edge_tab(idx - IMB_P4_TAB) : imb_p8_tab(idx - IMB_P4_TAB - IMB_P8_EDGE_TAB);
 }
 
-/* The same rules, split for a lane that produces the four samples (x0 .. x0 + 3, y): everything the rule reads is read ONCE, before
- * the lane writes (the compiler cannot hoist tile reads over tile writes itself: imb_pred_blk per sample re-read the whole edge — 64
- * byte reads for a DC, 64 for a plane — four times). */
+/* The block rules of h264_pred_rules.h, split for a lane that produces four samples: everything the rule reads is read ONCE, before
+ * the lane writes (the compiler cannot hoist tile reads over tile writes itself: evaluated per sample, the whole edge was re-read —
+ * 64 byte reads for a DC, 64 for a plane — four times). */
 struct ImbPred {
     int s[4], dc, a, H, V; /* s[j]: sample j's value under the horizontal / vertical rules */
 };
@@ -517,11 +355,34 @@ struct ImbPred {
 #define IMB_UNIFORM(v) (v)
 #endif
 
+/* the DC of a 16x16 block, or of cell (cx, r) of an 8-wide one: the sums of the neighbours the mode reads (the tile holds the others
+ * too), then the header's rule */
+template <int W, class Top, class Left>
+IMB_FN int imb_pred_dc(int mode, int cx, int r, Top TOP, Left LEFT, int mid)
+{
+    const bool ut = hp_blk_top(mode), ul = hp_blk_left(mode);
+    if (W == 16) {
+        int sl = 0, st = 0;
+        for (int i = 0; i < 16; i++) {
+            sl += ul ? LEFT(i) : 0;
+            st += ut ? TOP(i) : 0;
+        }
+        return hp_dc16(mode, sl, st, mid);
+    }
+    int t0 = 0, t1 = 0, l0 = 0, lr = 0;
+    for (int i = 0; i < 4; i++) {
+        t0 += ut ? TOP(i) : 0;
+        t1 += ut ? TOP(4 + i) : 0;
+        l0 += ul ? LEFT(i) : 0;
+        lr += (ul && hp_blk_lrows(mode, 8) > 4) ? LEFT(4 * r + i) : 0; /* the column's other rows, where the mode reads more than four */
+    }
+    return hp_cell_dc(mode, r, cx, t0, t1, l0, lr, mid);
+}
+
 /* the four samples are (x0 + j, y) of a row, or with COL (x0, y + j) of a column (y a multiple of 4) */
 template <int N, bool COL, class Top, class Left>
 IMB_FN ImbPred imb_pred_quad(int mode, int x0, int y, Top TOP, Left LEFT, int mid)
 {
-    constexpr int H2 = N / 2;
     ImbPred P;
     P.dc = P.a = P.H = P.V = 0;
     P.s[0] = P.s[1] = P.s[2] = P.s[3] = 0;
@@ -542,42 +403,12 @@ IMB_FN ImbPred imb_pred_quad(int mode, int x0, int y, Top TOP, Left LEFT, int mi
                 P.s[j] = TOP(x0 + j);
         }
     } else if (mode == 3) {
-        int H = 0, V = 0;
-        for (int i = 1; i <= H2; i++) {
-            H += i * (TOP(H2 - 1 + i) - TOP(H2 - 1 - i));
-            V += i * (LEFT(H2 - 1 + i) - (i == H2 ? TOP(-1) : LEFT(H2 - 1 - i)));
-        }
-        P.H = N == 16 ? (5 * H + 32) >> 6 : (17 * H + 16) >> 5;
-        P.V = N == 16 ? (5 * V + 32) >> 6 : (17 * V + 16) >> 5;
-        P.a = 16 * (LEFT(N - 1) + TOP(N - 1) + 1) - (H2 - 1) * (P.V + P.H);
-    } else if (N == 16) {
-        int sl = 0, st = 0;
-        for (int i = 0; i < 16; i++) {
-            sl += (mode == 0 || mode == 4) ? LEFT(i) : 0;
-            st += (mode == 0 || mode == 5) ? TOP(i) : 0;
-        }
-        P.dc = mode == 0 ? (sl + st + 16) >> 5 : mode == 4 ? (sl + 8) >> 4 : mode == 5 ? (st + 8) >> 4 : mid;
+        const HpPlane p = hp_plane<N, N>(TOP, LEFT);
+        P.a = p.a;
+        P.H = p.H;
+        P.V = p.V;
     } else {
-        const bool ut = mode == 0 || mode == 5 || mode == 7 || mode == 8, ul = mode == 0 || mode == 4 || mode >= 7;
-        int t0 = 0, t1 = 0, l0 = 0, l1 = 0;
-        for (int i = 0; i < 4; i++) {
-            t0 += ut ? TOP(i) : 0;
-            t1 += ut ? TOP(4 + i) : 0;
-            l0 += ul ? LEFT(i) : 0;
-            l1 += (ul && mode != 7) ? LEFT(4 + i) : 0;
-        }
-        int q0 = mid, q1 = mid, q2 = mid, q3 = mid;
-        switch (mode) {
-        case 0: q0 = (t0 + l0 + 4) >> 3; q1 = (t1 + 2) >> 2; q2 = (l1 + 2) >> 2; q3 = (t1 + l1 + 4) >> 3; break;
-        case 4: q0 = q1 = (l0 + 2) >> 2; q2 = q3 = (l1 + 2) >> 2; break;
-        case 5: q0 = q2 = (t0 + 2) >> 2; q1 = q3 = (t1 + 2) >> 2; break;
-        case 7: q0 = (t0 + l0 + 4) >> 3; q2 = (t0 + 2) >> 2; q1 = q3 = (t1 + 2) >> 2; break;
-        case 8: q0 = (t0 + 2) >> 2; q1 = (t1 + 2) >> 2; q2 = (l1 + 2) >> 2; q3 = (t1 + l1 + 4) >> 3; break;
-        case 9: q0 = q1 = (l0 + 2) >> 2; break;
-        case 10: q2 = q3 = (l1 + 2) >> 2; break;
-        default: break;
-        }
-        P.dc = (y >> 2) ? ((x0 >> 2) ? q3 : q2) : ((x0 >> 2) ? q1 : q0);
+        P.dc = imb_pred_dc<N>(mode, x0 >> 2, y >> 2, TOP, LEFT, mid);
     }
     return P;
 }
@@ -585,7 +416,7 @@ IMB_FN ImbPred imb_pred_quad(int mode, int x0, int y, Top TOP, Left LEFT, int mi
 template <typename PIX>
 IMB_FN int imb_pred_px(int mode, const ImbPred &P, int j, int x, int y, int maxv)
 {
-    return (mode == 1 || mode == 2) ? P.s[j] : mode == 3 ? imb_clip<PIX>((P.a + y * P.V + x * P.H) >> 5, maxv) : P.dc;
+    return (mode == 1 || mode == 2) ? P.s[j] : mode == 3 ? imb_clip<PIX>(hp_plane_raw(HpPlane{ P.a, P.H, P.V }, x, y), maxv) : P.dc;
 }
 
 /*
@@ -883,7 +714,6 @@ struct ImbTileC422 {
 template <typename PIX, class Top, class Left>
 IMB_FN void imb_pred8x16_col(int mode, int k, int xc, int y0, Top TOP, Left LEFT, int maxv, int out[4])
 {
-    const int mid = (maxv + 1) >> 1;
     if (mode == 1) {
         for (int j = 0; j < 4; j++)
             out[j] = LEFT(y0 + j);
@@ -893,46 +723,14 @@ IMB_FN void imb_pred8x16_col(int mode, int k, int xc, int y0, Top TOP, Left LEFT
         out[0] = out[1] = out[2] = out[3] = TOP(xc);
         return;
     }
-    if (mode == 3) { /* pred8x16_plane (h264pred_template.c:781-817) */
-        int H = 0, V = 0;
-        for (int i = 1; i <= 4; i++)
-            H += i * (TOP(3 + i) - TOP(3 - i));
-        for (int i = 1; i <= 8; i++)
-            V += i * (LEFT(7 + i) - (i == 8 ? TOP(-1) : LEFT(7 - i)));
-        H = (17 * H + 16) >> 5;
-        V = (5 * V + 32) >> 6;
-        const int a = 16 * (LEFT(15) + TOP(7) + 1) - 7 * V - 3 * H;
+    if (mode == 3) {
+        const HpPlane P = hp_plane<8, 16>(TOP, LEFT);
         for (int j = 0; j < 4; j++)
-            out[j] = imb_clip<PIX>((a + (y0 + j) * V + xc * H) >> 5, maxv);
+            out[j] = imb_clip<PIX>(hp_plane_raw(P, xc, y0 + j), maxv);
         return;
     }
-    /* the DC family: one value per 4 x 4 cell (r = cell row 0..3, cx = cell column) */
-    const int r = k >> 1, cx = k & 1;
-    const bool use_t = mode == 0 || mode == 5 || mode == 7 || mode == 8, use_l = mode == 0 || mode == 4 || mode >= 7;
-    int t0 = 0, t1 = 0, l0 = 0, lr = 0;
-    for (int i = 0; i < 4; i++) {
-        t0 += use_t ? TOP(i) : 0;
-        t1 += use_t ? TOP(4 + i) : 0;
-        l0 += use_l ? LEFT(i) : 0;
-        lr += (use_l && mode != 7) ? LEFT(4 * r + i) : 0;
-    }
-    int v = mid;
-    switch (mode) {
-    case 0: case 8: /* pred8x16_dc (:650-695); 8 = mad_cow_dc_0lt: cell 0 from the top alone */
-        v = cx == 0 ? (r == 0 ? (mode == 0 ? (t0 + l0 + 4) >> 3 : (t0 + 2) >> 2) : (lr + 2) >> 2)
-                    : (r == 0 ? (t1 + 2) >> 2 : (t1 + lr + 4) >> 3);
-        break;
-    case 4: case 9: case 10: /* left_dc (:567-571); 9 = _l00: the cells of rows 4..7 stay mid; 10 = _0l0: those of rows 0..3 (:725-749) */
-        v = ((mode == 9 && r == 1) || (mode == 10 && r == 0)) ? mid : (lr + 2) >> 2;
-        break;
-    case 5: case 7: /* top_dc (:599-603); 7 = _l0t: cell 0 is pred4x4_dc */
-        v = cx == 0 ? (t0 + 2) >> 2 : (t1 + 2) >> 2;
-        if (mode == 7 && k == 0)
-            v = (t0 + l0 + 4) >> 3;
-        break;
-    default: break; /* 6: DC_128 */
-    }
-    out[0] = out[1] = out[2] = out[3] = v;
+    /* the DC family: one value per 4 x 4 cell (cell row k >> 1 = 0..3, cell column k & 1) */
+    out[0] = out[1] = out[2] = out[3] = imb_pred_dc<8>(mode, k & 1, k >> 1, TOP, LEFT, (maxv + 1) >> 1);
 }
 
 template <typename PIX, class X>

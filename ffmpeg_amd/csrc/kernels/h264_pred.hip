@@ -16,13 +16,14 @@
 #include <type_traits>
 
 #include "common.h"
-#include "h264_intra_mb.h"
 #include "h264_kernels.h"
+#include "h264_pred_rules.h"
 
 static_assert(sizeof(FFHipH264Pred) == 12, "FFHipH264Pred is a 12-byte record");
 
-/* hp_a2 / hp_a3 / hp_need / hp_dir_sample: the per-sample rules over the edge line, shared with the picture pipeline's intra
- * reconstruction (h264_intra_mb.h) */
+/* The arithmetic — the per-sample rules over the edge line and its low-pass filter, which neighbours a mode reads, the plane
+ * predictor, the DCs — is h264_pred_rules.h's, shared with the picture pipeline's intra reconstruction (h264_intra_mb.h); the kernels
+ * here stage the neighbours, say which thread computes what, and store */
 
 __device__ __forceinline__ void hp_store4(uint16_t *d, const int *v) /* 16-bit samples: two dwords when aligned */
 {
@@ -84,29 +85,15 @@ __global__ __launch_bounds__(256) void k_h264_pred_dir(uint8_t *plane, ptrdiff_t
     __syncthreads();
     const int *e = raw[r];
     if (L8) {
-        /* PREDICT_8x8_LOAD_LEFT / _TOP / _TOPRIGHT / _TOPLEFT (h264pred_template.c:822-856) */
-        const int *w = raw[r];
-        for (int j = it; j < LINE; j += ITEMS) {
-            int v = 0;
-            if (j < 8) {
-                if (need & 1)
-                    v = j == 7 ? hp_a3(tl ? w[8] : w[7], w[7], w[6]) : j == 0 ? (w[1] + 3 * w[0] + 2) >> 2 : hp_a3(w[j + 1], w[j], w[j - 1]);
-            } else if (j == 8) {
-                if (need & 4)
-                    v = hp_a3(w[7], w[8], w[9]);
-            } else if (j < 17) {
-                if (need & 2)
-                    v = j == 9 ? hp_a3(tl ? w[8] : w[9], w[9], w[10]) : j == 16 ? hp_a3(tr ? w[17] : w[16], w[16], w[15]) : hp_a3(w[j - 1], w[j], w[j + 1]);
-            } else if (need & 8) {
-                v = !tr ? w[16] : j == 24 ? (w[23] + 3 * w[24] + 2) >> 2 : hp_a3(w[j - 1], w[j], w[j + 1]);
-            }
-            flt[r][j] = v;
-        }
+        for (int j = it; j < LINE; j += ITEMS)
+            flt[r][j] = hp_filter8(raw[r], j, need, tl, tr);
         __syncthreads();
         e = flt[r];
     }
     if (!valid)
         return;
+    /* hp_dir_dc_e's value over a line that holds 0 wherever the mode does not read, so both sides are summed without its per-mode
+     * masks (the tile readers need those): through hp_dir_dc_e the two kernels measured 1.5 - 2 % slower (profiles/h264_pred_rules.txt) */
     int dc = 1 << (bd - 1); /* DC_128_PRED at the depth */
     if (mode == 2 || mode == 9 || mode == 10) {
         int sl = 0, st = 0;
@@ -131,41 +118,32 @@ __global__ __launch_bounds__(256) void k_h264_pred_blk(uint8_t *plane, ptrdiff_t
 {
     const ptrdiff_t stride = stride_b / (ptrdiff_t)sizeof(P);
     const int mid = 1 << (bd - 1), maxv = (1 << bd) - 1;
-    constexpr int ITEMS = N * N / 4, RPB = 256 / ITEMS, QW = N / 4, H2 = N / 2;
+    constexpr int ITEMS = N * N / 4, RPB = 256 / ITEMS, QW = N / 4;
     __shared__ int L[RPB][N], T[RPB][N + 1]; /* T[0] is the corner */
-    __shared__ int PP[RPB][4];
+    __shared__ int PP[RPB][4];               /* the plane's (a, H, V), the 16x16 DC, or the DCs of cells [2 * row + column] */
     const int r = threadIdx.x / ITEMS, it = threadIdx.x % ITEMS, b = blockIdx.x * RPB + r;
     const bool valid = b < n;
     FFHipH264Pred k = {};
     if (valid)
         k = blocks[b];
     const int mode = k.mode;
-    /* modes: 0 DC 1 HOR 2 VERT 3 PLANE 4 LEFT_DC 5 TOP_DC 6 DC_128; pred8x8 also 7 L0T 8 0LT 9 L00 10 0L0 (h264pred.h:67-82) */
-    const bool use_t = valid && (mode == 0 || mode == 2 || mode == 3 || mode == 5 || mode == 7 || mode == 8);
-    const bool use_l = valid && (mode == 0 || mode == 1 || mode == 3 || mode == 4 || mode >= 7);
-    const int lrows = mode == 7 ? 4 : N; /* L0T: pred4x4_dc on the first quadrant reads four rows of the left column */
+    const unsigned need = valid ? hp_blk_need(mode) : 0u;
+    const int lrows = hp_blk_lrows(mode, N);
     P *src = reinterpret_cast<P *>(plane + k.offset);
     if (it < N) {
-        L[r][it] = use_l && it < lrows ? src[(ptrdiff_t)it * stride - 1] : 0;
-        T[r][it + 1] = use_t ? src[it - stride] : 0;
+        L[r][it] = (need & 1) && it < lrows ? src[(ptrdiff_t)it * stride - 1] : 0;
+        T[r][it + 1] = (need & 2) ? src[it - stride] : 0;
     } else if (it == N) {
-        T[r][0] = valid && mode == 3 ? src[-stride - 1] : 0;
+        T[r][0] = (need & 4) ? src[-stride - 1] : 0;
     }
     __syncthreads();
     if (it == 0 && valid) {
         const int *l = L[r], *t = T[r] + 1;
         if (mode == 3) {
-            int H = 0, V = 0;
-#pragma unroll
-            for (int i = 1; i <= H2; i++) {
-                H += i * (t[H2 - 1 + i] - t[H2 - 1 - i]);
-                V += i * (l[H2 - 1 + i] - (i == H2 ? t[-1] : l[H2 - 1 - i]));
-            }
-            H = N == 16 ? (5 * H + 32) >> 6 : (17 * H + 16) >> 5;
-            V = N == 16 ? (5 * V + 32) >> 6 : (17 * V + 16) >> 5;
-            PP[r][0] = 16 * (l[N - 1] + t[N - 1] + 1) - (H2 - 1) * (V + H);
-            PP[r][1] = H;
-            PP[r][2] = V;
+            const HpPlane p = hp_plane<N, N>([&](int i) { return t[i]; }, [&](int i) { return i < 0 ? t[-1] : l[i]; });
+            PP[r][0] = p.a;
+            PP[r][1] = p.H;
+            PP[r][2] = p.V;
         } else if (N == 16) {
             int sl = 0, st = 0;
 #pragma unroll
@@ -173,8 +151,11 @@ __global__ __launch_bounds__(256) void k_h264_pred_blk(uint8_t *plane, ptrdiff_t
                 sl += l[i];
                 st += t[i];
             }
-            PP[r][0] = mode == 0 ? (sl + st + 16) >> 5 : mode == 4 ? (sl + 8) >> 4 : mode == 5 ? (st + 8) >> 4 : mid;
+            PP[r][0] = hp_dc16(mode, sl, st, mid);
         } else {
+            /* hp_cell_dc's rule for cells (0, 0), (0, 1), (1, 0), (1, 1) solved per mode, the kernel's own lines: one thread fills the
+             * four cells behind ONE switch.  Through hp_cell_dc, a cell per thread, the kernel measured 7 % slower; four calls in this
+             * thread are four switches (profiles/h264_pred_rules.txt).  tests/test_gpu_h264_pred.py holds these lines to the oracle */
             const int t0 = t[0] + t[1] + t[2] + t[3], t1 = t[4] + t[5] + t[6] + t[7];
             const int l0 = l[0] + l[1] + l[2] + l[3], l1 = l[4] + l[5] + l[6] + l[7];
             int q0 = mid, q1 = mid, q2 = mid, q3 = mid;
@@ -204,7 +185,7 @@ __global__ __launch_bounds__(256) void k_h264_pred_blk(uint8_t *plane, ptrdiff_t
         else if (mode == 2)
             v[j] = T[r][x + 1];
         else if (mode == 3)
-            v[j] = min(max((PP[r][0] + y * PP[r][2] + x * PP[r][1]) >> 5, 0), maxv);
+            v[j] = hp_plane_sample(HpPlane{ PP[r][0], PP[r][1], PP[r][2] }, x, y, maxv);
         else
             v[j] = N == 16 ? PP[r][0] : PP[r][2 * (y >> 2) + (x >> 2)];
     }
@@ -231,34 +212,25 @@ __global__ __launch_bounds__(256) void k_h264_pred_8x16(uint8_t *plane, ptrdiff_
     if (valid)
         k = blocks[b];
     const int mode = k.mode;
-    const bool use_t = valid && (mode == 0 || mode == 2 || mode == 3 || mode == 5 || mode == 7 || mode == 8);
-    const bool use_l = valid && (mode == 0 || mode == 1 || mode == 3 || mode == 4 || mode >= 7);
-    const int lrows = mode == 7 ? 4 : 16; /* L0T: pred4x4_dc on the first 4x4 reads four rows of the left column */
+    const unsigned need = valid ? hp_blk_need(mode) : 0u;
+    const int lrows = hp_blk_lrows(mode, 16);
     P *src = reinterpret_cast<P *>(plane + k.offset);
     if (it < 16)
-        L[r][it] = use_l && it < lrows ? src[(ptrdiff_t)it * stride - 1] : 0;
+        L[r][it] = (need & 1) && it < lrows ? src[(ptrdiff_t)it * stride - 1] : 0;
     else if (it < 24)
-        T[r][it - 15] = use_t ? src[(it - 16) - stride] : 0;
+        T[r][it - 15] = (need & 2) ? src[(it - 16) - stride] : 0;
     else if (it == 24)
-        T[r][0] = valid && mode == 3 ? src[-stride - 1] : 0;
+        T[r][0] = (need & 4) ? src[-stride - 1] : 0;
     __syncthreads();
     if (it == 0 && valid) {
         const int *l = L[r], *t = T[r] + 1;
         if (mode == 3) {
-            /* H over the top row as for 8x8, V over the 16 left rows: k (l[7 + k] - l[7 - k]), k = 1..8, l[-1] = the corner */
-            int H = 0, V = 0;
-#pragma unroll
-            for (int i = 1; i <= 4; i++)
-                H += i * (t[3 + i] - t[3 - i]);
-#pragma unroll
-            for (int i = 1; i <= 8; i++)
-                V += i * (l[7 + i] - (i == 8 ? t[-1] : l[7 - i]));
-            H = (17 * H + 16) >> 5;
-            V = (5 * V + 32) >> 6;
-            PP[r][0] = 16 * (l[15] + t[7] + 1) - 7 * V - 3 * H;
-            PP[r][1] = H;
-            PP[r][2] = V;
+            const HpPlane p = hp_plane<8, 16>([&](int i) { return t[i]; }, [&](int i) { return i < 0 ? t[-1] : l[i]; });
+            PP[r][0] = p.a;
+            PP[r][1] = p.H;
+            PP[r][2] = p.V;
         } else {
+            /* hp_cell_dc's rule for the eight cells solved per mode, the kernel's own lines, as in k_h264_pred_blk<8> and for its reason */
             const int t0 = t[0] + t[1] + t[2] + t[3], t1 = t[4] + t[5] + t[6] + t[7];
             int lq[4];
 #pragma unroll
@@ -317,7 +289,7 @@ __global__ __launch_bounds__(256) void k_h264_pred_8x16(uint8_t *plane, ptrdiff_
         else if (mode == 2)
             v[j] = T[r][x + 1];
         else if (mode == 3)
-            v[j] = min(max((PP[r][0] + y * PP[r][2] + x * PP[r][1]) >> 5, 0), maxv);
+            v[j] = hp_plane_sample(HpPlane{ PP[r][0], PP[r][1], PP[r][2] }, x, y, maxv);
         else
             v[j] = PP[r][2 * (y >> 2) + (x >> 2)];
     }
@@ -342,13 +314,9 @@ __global__ __launch_bounds__(256) void k_h264_pred_add(uint8_t *plane, ptrdiff_t
     unsigned v;
     if (FILTER) {
         const bool tl = k.flags & FFHIP_H264_PRED_TOPLEFT, tr = k.flags & FFHIP_H264_PRED_TOPRIGHT;
-        const int c = edge[i * across];
-        if (i == 0)
-            v = hp_a3(tl ? edge[-across] : c, c, edge[across]);
-        else if (i == 7)
-            v = vert ? hp_a3(tr ? edge[8 * across] : c, c, edge[6 * across]) : (edge[6 * across] + 3 * c + 2) >> 2;
-        else
-            v = hp_a3(edge[(i - 1) * across], c, edge[(i + 1) * across]);
+        /* the block's raw edge line read in place: column i of VERT is entry 9 + i of it, row i of HOR entry 7 - i */
+        auto w = [&](int j) { return (int)edge[(vert ? j - 9 : 7 - j) * across]; };
+        v = hp_filter8_e(w, vert ? 9 + i : 7 - i, vert ? 2u : 1u, tl, tr);
     } else {
         v = edge[i * across];
     }

@@ -122,19 +122,19 @@ __device__ __forceinline__ int v8r_codec_form(int mode, int x, int y, const T &t
 }
 
 /* pred16x16[] (N 16: H.264's DC forms) / pred8x8[] (N 8: the RV40 DC forms VP8 installs) of slot `eff` (FFHIP_VP8_PRED_*) for the
- * N x N block whose sample (0, 0) is at T: both DC families are (sum + n / 2) / n over the n samples of the sides taken */
+ * N x N block whose sample (0, 0) is at T: both DC families are hp_sides_dc (h264_pred_rules.h) over the sides the slot takes */
 template <int N>
 __device__ __forceinline__ int v8r_blk_dc(int eff, const uint8_t *T, int pitch)
 {
+    const bool left = eff == FFHIP_VP8_PRED_DC || eff == FFHIP_VP8_PRED_LEFT_DC, top = eff == FFHIP_VP8_PRED_DC || eff == FFHIP_VP8_PRED_TOP_DC;
     int sl = 0, st = 0;
-    if (eff == FFHIP_VP8_PRED_DC || eff == FFHIP_VP8_PRED_LEFT_DC)
+    if (left)
         for (int i = 0; i < N; i++)
             sl += T[i * pitch - 1];
-    if (eff == FFHIP_VP8_PRED_DC || eff == FFHIP_VP8_PRED_TOP_DC)
+    if (top)
         for (int i = 0; i < N; i++)
             st += T[i - pitch];
-    constexpr int LG = N == 16 ? 4 : 3;
-    return eff == FFHIP_VP8_PRED_DC ? (sl + st + N) >> (LG + 1) : eff == FFHIP_VP8_PRED_DC_128 ? 128 : (sl + st + N / 2) >> LG;
+    return hp_sides_dc<N>(left, top, sl, st, 128);
 }
 template <int N>
 __device__ __forceinline__ int v8r_blk_sample(int eff, int dc, const uint8_t *T, int pitch, int x, int y)

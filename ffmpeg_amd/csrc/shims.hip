@@ -27,6 +27,7 @@
 
 #include "kernels/common.h"
 #include "kernels/h264_kernels.h"
+#include "kernels/h264_pred_rules.h"
 #include "kernels/me_kernels.h"
 
 #include "kernels/shim_arena.h"
@@ -1033,23 +1034,17 @@ static bool h264_pred_host(int bd, int kind, int mode, int n, unsigned need, int
 template <int BD, int F = 0> struct PredFb { static FFHipH264PredContext t; };
 template <int BD, int F> FFHipH264PredContext PredFb<BD, F>::t;
 #define g_fb_pred PredFb<BD>::t
-static constexpr unsigned hp_need4(int mode) { return (unsigned)(0x0211a777a312ull >> (4 * mode)) & 15u; } /* as kernels/h264_pred.hip */
-/* pred8x8 / pred16x16: 0 DC 1 HOR 2 VERT 3 PLANE 4 LEFT_DC 5 TOP_DC 6 DC_128 7 L0T 8 0LT 9 L00 10 0L0 */
-static constexpr unsigned hp_need_blk(int mode)
-{
-    return (mode == 0 || mode == 1 || mode == 3 || mode == 4 || mode >= 7 ? 1u : 0u) |
-           (mode == 0 || mode == 2 || mode == 3 || mode == 5 || mode == 7 || mode == 8 ? 2u : 0u) | (mode == 3 ? 4u : 0u);
-}
+/* what a mode reads is what its kernel loads: hp_need / hp_blk_need / hp_blk_lrows of kernels/h264_pred_rules.h */
 template <int BD, int MODE>
 static void s_pred4x4(uint8_t *src, const uint8_t *topright, ptrdiff_t stride)
 {
-    if (!h264_pred_host(BD, FFHIP_H264_PRED4x4, MODE, 4, hp_need4(MODE), 4, src, stride, topright, 0, 0, nullptr))
+    if (!h264_pred_host(BD, FFHIP_H264_PRED4x4, MODE, 4, hp_need(MODE), 4, src, stride, topright, 0, 0, nullptr))
         SHIM_FB(g_fb_pred, pred4x4[MODE], src, topright, stride);
 }
 template <int BD, int MODE>
 static void s_pred8x8l(uint8_t *src, int has_topleft, int has_topright, ptrdiff_t stride)
 {
-    constexpr unsigned need = hp_need4(MODE);
+    const unsigned need = hp_need(MODE);
     /* the corner is also read by the edge filter when has_topleft (PREDICT_8x8_LOAD_LEFT / _TOP) */
     if (!h264_pred_host(BD, FFHIP_H264_PRED8x8L, MODE, 8, need | ((has_topleft && (need & 3)) ? 4u : 0u), 8, src, stride, nullptr, has_topleft,
                         has_topright, nullptr))
@@ -1058,19 +1053,19 @@ static void s_pred8x8l(uint8_t *src, int has_topleft, int has_topright, ptrdiff_
 template <int BD, int MODE>
 static void s_pred8x8(uint8_t *src, ptrdiff_t stride)
 {
-    if (!h264_pred_host(BD, FFHIP_H264_PRED8x8, MODE, 8, hp_need_blk(MODE), MODE == 7 ? 4 : 8, src, stride, nullptr, 0, 0, nullptr))
+    if (!h264_pred_host(BD, FFHIP_H264_PRED8x8, MODE, 8, hp_blk_need(MODE), hp_blk_lrows(MODE, 8), src, stride, nullptr, 0, 0, nullptr))
         SHIM_FB(g_fb_pred, pred8x8[MODE], src, stride);
 }
 template <int BD, int MODE> /* pred8x8[MODE] at chroma_format_idc >= 2 */
 static void s_pred8x16(uint8_t *src, ptrdiff_t stride)
 {
-    if (!h264_pred_host(BD, FFHIP_H264_PRED8x16, MODE, 8, hp_need_blk(MODE), MODE == 7 ? 4 : 16, src, stride, nullptr, 0, 0, nullptr, 16))
+    if (!h264_pred_host(BD, FFHIP_H264_PRED8x16, MODE, 8, hp_blk_need(MODE), hp_blk_lrows(MODE, 16), src, stride, nullptr, 0, 0, nullptr, 16))
         SHIM_FB((PredFb<BD, 1>::t), pred8x8[MODE], src, stride);
 }
 template <int BD, int MODE>
 static void s_pred16x16(uint8_t *src, ptrdiff_t stride)
 {
-    if (!h264_pred_host(BD, FFHIP_H264_PRED16x16, MODE, 16, hp_need_blk(MODE), 16, src, stride, nullptr, 0, 0, nullptr))
+    if (!h264_pred_host(BD, FFHIP_H264_PRED16x16, MODE, 16, hp_blk_need(MODE), hp_blk_lrows(MODE, 16), src, stride, nullptr, 0, 0, nullptr))
         SHIM_FB(g_fb_pred, pred16x16[MODE], src, stride);
 }
 template <int BD, int KIND, int N, int MODE>
@@ -1172,7 +1167,7 @@ static void s_predv4(uint8_t *src, const uint8_t *topright, ptrdiff_t stride)
 template <int CI, int IDX, int MODE>
 static void s_predv4_plain(uint8_t *src, const uint8_t *topright, ptrdiff_t stride)
 {
-    if (!h264_pred_host(8, FFHIP_H264_PRED4x4, MODE, 4, hp_need4(MODE), 4, src, stride, topright, 0, 0, nullptr))
+    if (!h264_pred_host(8, FFHIP_H264_PRED4x4, MODE, 4, hp_need(MODE), 4, src, stride, topright, 0, 0, nullptr))
         SHIM_FB(PredFbCodec<CI>::t, pred4x4[IDX], src, topright, stride);
 }
 template <int CI, int IDX, int V, unsigned NEED>

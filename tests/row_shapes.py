@@ -28,11 +28,11 @@ INTRA_LDS = 64 * 1024 # the LDS a workgroup of k_h264_intra_frame may take, h264
 # __launch_bounds__(256, 2), h264_intra.hip:86, asks the compiler to keep two workgroups a CU achievable and caps nothing, and no test
 # pins the register count.  The bound that does hold is h264_intra()'s resident_bound (waves and LDS: 8 a CU at the narrow widths).
 INTRA_WG_PER_CU = 2
-# sizeof(ImbTileT<PIX>), ffmpeg_amd/csrc/kernels/h264_intra_mb.h:159-166: y[17 * 32] + c[2][9 * 16] samples, t8[4][64] + dcq[16] + edge[32] ints,
+# sizeof(ImbTileT<PIX>), ffmpeg_amd/csrc/kernels/h264_intra_mb.h:49-56: y[17 * 32] + c[2][9 * 16] samples, t8[4][64] + dcq[16] + edge[32] ints,
 # zero[16] coefficients (int16_t at 8 bits, int32_t above: H264Coef, h264_tx_rules.h:23-24)
 IMB_TILE = {1: 17 * 32 + 2 * 9 * 16 + 4 * (4 * 64 + 16 + 32) + 2 * 16, 2: 2 * (17 * 32 + 2 * 9 * 16) + 4 * (4 * 64 + 16 + 32) + 4 * 16}
 IMB_REC = 108         # sizeof(FFHipH264IntraMB), include/ffhip.h:819-837
-IMB_TABS = 2 * 12 * 16 + 4 * 32 + 9 * 64    # IMB_P4_TAB + IMB_P8_EDGE_TAB + IMB_P8_TAB, h264_intra_mb.h:396, :420, :421, :479
+IMB_TABS = 2 * 12 * 16 + 4 * 32 + 9 * 64    # IMB_P4_TAB + IMB_P8_EDGE_TAB + IMB_P8_TAB, h264_intra_mb.h:234, :258, :259, :317
 VP9_LF_PICS = 32      # FFHIP_VP9_LF_PICS, h264_kernels.h:135
 CU_LDS = 160 * 1024   # the LDS of one CU of gfx950
 CU_WAVES = 32         # the waves one CU holds at most (8 a SIMD)
