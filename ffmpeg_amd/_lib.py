@@ -123,6 +123,7 @@ def lib():
         "ffhip_sws_uops_set_fallback": (None, [vp, vp, vp]),
         "ffhip_sws_uops_func": (None, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
         "ffhip_sws_uops_run_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "ffhip_sws_uops_launch_shape_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "ffhip_membw_probe": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
         "ffhip_sws_up2_virtual_bank_host": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "ffhip_sws_up2_walk_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]),

@@ -807,31 +807,40 @@ int geometry(FFHipSwsUOps *p, const FFHipSwsOpExec *e, int bx_start, int y_start
     return 0;
 }
 
+/* The grid of a launch and the lines a thread walks (the kernel's `rr` loop strides by 4 * grid y): one statement for launch() and
+ * the CPU test (ffhip_sws_uops_launch_shape_host).  `rows_knob`: FFHIP_UOPS_ROWS of the measure build, 0 = none. */
+struct LaunchShape { unsigned gx, gy, gz; int rows; };
+LaunchShape launch_shape(int V, int npx, int ny, int nframes, int rows_knob)
+{
+    const int groups = cdiv(npx, V);
+    /* lines per thread: a wave that converts 256 pixels and retires is mostly launch and address set-up; 8 lines per thread keeps
+     * >= 4 workgroups per CU in flight on pictures from SD up, smaller jobs fall back to fewer lines */
+    int rows = rows_knob > 0 ? rows_knob : 8;
+    while (rows > 1 && (long)cdiv(groups, 64) * cdiv(ny, 4 * rows) * nframes < 2048)
+        rows >>= 1;
+    unsigned gy = cdiv(ny, 4 * rows);
+    if (gy > 16384)
+        gy = 16384;
+    return { (unsigned)cdiv(groups, 64), gy, (unsigned)nframes, rows };
+}
+
 int launch(FFHipSwsUOps *p, KArgs &a, int nframes, hipStream_t st)
 {
     for (int i = 0; i < MAXDATA; i++)
         a.data[i] = p->data[i];
     if (a.npx <= 0 || a.ny <= 0 || nframes <= 0)
         return 0;
-    const int groups = cdiv(a.npx, p->plan.V);
-    /* lines per thread: a wave that converts 256 pixels and retires is mostly launch and address set-up; 8 lines per thread keeps
-     * >= 4 workgroups per CU in flight on pictures from SD up, smaller jobs fall back to fewer lines */
     static const int rows_env = FFHIP_KNOB("FFHIP_UOPS_ROWS") ? atoi(FFHIP_KNOB("FFHIP_UOPS_ROWS")) : 0;
-    int rows = rows_env > 0 ? rows_env : 8;
-    while (rows > 1 && (long)cdiv(groups, 64) * cdiv(a.ny, 4 * rows) * nframes < 2048)
-        rows >>= 1;
-    unsigned gy = cdiv(a.ny, 4 * rows);
-    if (gy > 16384)
-        gy = 16384;
+    const LaunchShape s = launch_shape(p->plan.V, a.npx, a.ny, nframes, rows_env);
     size_t sz = sizeof a;
     void *cfg[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END };
-    HIP_TRY(hipModuleLaunchKernel(p->prog->fn[p->device], cdiv(groups, 64), gy, nframes, 64, 4, 1, 0, st, nullptr, cfg));
+    HIP_TRY(hipModuleLaunchKernel(p->prog->fn[p->device], s.gx, s.gy, s.gz, 64, 4, 1, 0, st, nullptr, cfg));
     return 0;
 }
 
 /* the device copy of a table with this content (under p->tab_mutex).  A new content gets a NEW allocation — tables in use by
  * launches in flight on any stream are never touched; past 32 distinct tables the device is drained once and the set restarts. */
-int table(FFHipSwsUOps *p, const int32_t *src, size_t n, hipStream_t st, int32_t **dev)
+int table(FFHipSwsUOps *p, const int32_t *src, size_t n, int32_t **dev)
 {
     for (auto &t : p->tabs)
         if (t->host.size() == n && !memcmp(t->host.data(), src, n * sizeof(int32_t))) {
@@ -847,7 +856,9 @@ int table(FFHipSwsUOps *p, const int32_t *src, size_t n, hipStream_t st, int32_t
     std::unique_ptr<DevTable> t(new DevTable);
     t->host.assign(src, src + n);
     HIP_TRY(hipMalloc(&t->dev, (n ? n : 1) * sizeof(int32_t)));
-    const hipError_t e = hipMemcpyAsync(t->dev, t->host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    /* complete before it is published: a later call with the same content finds the table by its host copy and launches on ITS
+     * stream, which nothing orders after a copy queued on this call's stream.  Once per distinct content, not once per launch */
+    const hipError_t e = hipMemcpy(t->dev, t->host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(t->dev);
         ffhip_set_error("sws uops: table upload failed: %s", hipGetErrorString(e));
@@ -877,13 +888,13 @@ extern "C" int ffhip_sws_uops_run_dev(FFHipSwsUOps *p, const FFHipSwsOpExec *e, 
     std::lock_guard<std::mutex> lk(p->tab_mutex);
     if (!rowtab.empty()) {
         int32_t *d = nullptr;
-        if ((r = table(p, rowtab.data(), rowtab.size(), st, &d)) < 0)
+        if ((r = table(p, rowtab.data(), rowtab.size(), &d)) < 0)
             return r;
         a.rowtab = d;
     }
     if (p->plan.fh_size) {
         int32_t *d = nullptr;
-        if ((r = table(p, e->in_offset_x, (size_t)a.x0 + a.npx, st, &d)) < 0)
+        if ((r = table(p, e->in_offset_x, (size_t)a.x0 + a.npx, &d)) < 0)
             return r;
         a.offx = d;
     }
@@ -894,6 +905,18 @@ extern "C" int ffhip_sws_uops_run_dev(FFHipSwsUOps *p, const FFHipSwsOpExec *e, 
         a.out_pitch[i] = out_frame_pitch ? out_frame_pitch[i] : 0;
     }
     return launch(p, a, nframes, st);
+}
+
+extern "C" int ffhip_sws_uops_launch_shape_host(int V, int npx, int ny, int nframes, int32_t out[4])
+{
+    if (V < 1 || npx < 1 || ny < 1 || nframes < 1 || !out)
+        return FFHIP_EINVAL;
+    const LaunchShape s = launch_shape(V, npx, ny, nframes, 0);
+    out[0] = (int32_t)s.gx;
+    out[1] = (int32_t)s.gy;
+    out[2] = (int32_t)s.gz;
+    out[3] = s.rows;
+    return 0;
 }
 
 /* ---- SwsOpFunc on host memory ------------------------------------------------------------------------------------------------ */

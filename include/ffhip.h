@@ -3517,6 +3517,10 @@ void ffhip_sws_uops_func(const FFHipSwsOpExec *exec, const void *priv, int bx_st
  *  Asynchronous on `stream`. */
 int  ffhip_sws_uops_run_dev(FFHipSwsUOps *p, const FFHipSwsOpExec *exec, int bx_start, int y_start, int bx_end, int y_end,
                             int nframes, const ptrdiff_t *in_frame_pitch, const ptrdiff_t *out_frame_pitch, void *stream);
+/** The shape both faces launch a call of `npx` pixels x `ny` lines x `nframes` pictures with, for a list whose threads own `V`
+ *  pixels (4; 8 for 1-bit lists): out = grid x, y, z and the lines per thread (a power of two in 1..8; a thread walks the lines
+ *  4 x grid y apart).  No device needed.  Returns 0 or FFHIP_EINVAL.  Exposed for the CPU test-suite. */
+int  ffhip_sws_uops_launch_shape_host(int V, int npx, int ny, int nframes, int32_t out[4]);
 
 #ifdef __cplusplus
 }

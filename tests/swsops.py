@@ -421,3 +421,189 @@ def run_golden(func, handle, block, lst, size, src, dst_shapes, pad=64):
     return [a[:, :s[1]] for a, s in zip(dp, dst_shapes)], dp
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# a picture reached rectangle by rectangle: what a threaded sws_scale_frame (slices) and a caller with column ranges hand a backend
+# ---------------------------------------------------------------------------------------------------------------------------------
+FILL = 0x5A        # what destinations hold before a call; whatever no rectangle covers must still hold it afterwards
+
+
+def rect_exec(lst, src_addrs, src_strides, dst_addrs, dst_strides, w, h, block, x0, x1, y0):
+    """the SwsOpExec of the columns [x0, x1) from line y0 on, of a w x h picture: plain_exec() of the whole picture with the
+    pointers and bumps moved the way op_pass_setup and the dispatcher move them for a slice (ops_dispatch.c:207-290, 403-436).
+    The call is then func(e, handle, x0 // block, y0, x1 // block, y1); x0 and x1 are whole blocks."""
+    assert x0 % block == 0 and x1 % block == 0 and 0 <= x0 < x1, (x0, x1, block)
+    e = plain_exec(lst, src_addrs, src_strides, dst_addrs, dst_strides, w, h, block)
+    rd = lst.read
+    _, bi = rw_geometry(rd)
+    _, bo = rw_geometry(lst.write)
+    npx = x1 - x0
+    dy = y0
+    if rd.uop == READ_PLANAR_FV:                 # in_bump_y stays the whole picture's: it is indexed by the absolute line
+        o = np.ctypeslib.as_array(rd.data.kernel.contents.offsets, (rd.data.kernel.contents.dst_size,))
+        dy = int(o[y0]) - int(o[0])
+    for i in range(4):
+        if e.in_[i] and not (rd.uop == READ_PALETTE and i == 1):
+            if rd.uop == READ_PLANAR_FH:         # in_offset_x stays the whole picture's: it is indexed by the absolute column
+                e.in_[i] += y0 * e.in_stride[i]
+                e.in_bump[i] = e.in_stride[i]
+            else:
+                e.in_[i] += dy * e.in_stride[i] + (x0 * bi >> 3)
+                e.in_bump[i] = e.in_stride[i] - (npx * bi >> 3)
+        if e.out[i]:
+            e.out[i] += y0 * e.out_stride[i] + (x0 * bo >> 3)
+            e.out_bump[i] = e.out_stride[i] - (npx * bo >> 3)
+    return e
+
+
+def tilings(w, h, block):
+    """two tilings of a w x h picture, as lists of (x0, x1, y0, y1): x cuts {0, block, 3 blocks, an odd block near the middle, w},
+    y cuts {0, 1, 3, h} and {0, 2, h - 1, h}.  With 1-pixel blocks the columns 1, 3 and the odd middle one start a rectangle off
+    the 4-pixel vector of a thread; with 2-pixel blocks (4-bit lists) the columns 2 and 6 do; with 8-pixel blocks (1-bit lists: the
+    x cuts are multiples of 8) the block IS the vector and no rectangle can."""
+    assert w % block == 0
+    nb = w // block
+    xs = sorted({0, block, 3 * block, (nb // 2 | 1) * block, w})
+    assert xs[-1] == w and len(xs) == 5, (w, block)
+    out = []
+    for ys in ((0, 1, 3, h), (0, 2, h - 1, h)):
+        ys = sorted({y for y in ys if 0 <= y <= h})
+        out.append([(x0, x1, y0, y1) for y0, y1 in zip(ys, ys[1:]) for x0, x1 in zip(xs, xs[1:])])
+    return out
+
+
+class HandList:
+    """a list put together in the test (UOpList's face)"""
+
+    def __init__(self, uops):
+        self.n = len(uops)
+        self.uops = (UOp * self.n)(*uops)
+
+    read = UOpList.read
+    write = UOpList.write
+
+
+class Buf:
+    """`frames` pictures of one plane behind one another in one flat byte buffer: `lines` lines of `rows` payload bytes, `pitch`
+    apart, the first `off` bytes into the buffer, `tail` bytes after the last.  Flat so that it can live on the host or, copied,
+    on the device, and so that every byte that is not payload can be checked."""
+
+    def __init__(self, rows, lines, frames=1, off=0, pitch=None, fill=0, tail=64):
+        self.rows, self.lines, self.frames, self.off, self.fill = rows, lines, frames, off, fill
+        self.pitch = pitch if pitch is not None else rows + 64
+        assert self.pitch >= rows
+        self.fpitch = lines * self.pitch
+        self.flat = np.full(off + frames * self.fpitch + tail, fill, np.uint8)
+
+    def view(self, flat=None):
+        f = self.flat if flat is None else flat
+        return f[self.off:self.off + self.frames * self.fpitch].reshape(self.frames, self.lines, self.pitch)
+
+    def payload(self, frame=0, flat=None):
+        return self.view(flat)[frame][:, :self.rows]
+
+    def outside_kept(self, flat=None, but=None):
+        """every byte that is not payload still holds the fill.  `but`: a (frames, lines, rows) mask of payload bytes that must
+        hold it as well (what no call has covered yet)"""
+        f = self.flat if flat is None else flat
+        m = np.ones(f.size, bool)
+        self.view(m)[:, :, :self.rows] = False if but is None else but
+        return bool((f[m] == self.fill).all())
+
+
+def same_bytes(a, b, f32):
+    """byte-exact; floats bit for bit with the NaNs as one value (as Case.compare)"""
+    if not f32:
+        return np.array_equal(a, b)
+    x, y = np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)
+    return a.shape == b.shape and bool(((x == y) | (np.isnan(x.view(np.float32)) & np.isnan(y.view(np.float32)))).all())
+
+
+def random_rows(rng, lst, shape, rng_max=0):
+    """source bytes of a plane: every bit pattern for integer planes (below `rng_max` + 1 where the list wants a range), numbers
+    in [0, 1) for float planes"""
+    if lst.read.type == F32:
+        return rng.random((shape[0], shape[1] // 4)).astype(np.float32).view(np.uint8)
+    return rng.integers(0, (rng_max or 255) + 1, shape, dtype=np.uint8)
+
+
+class RectCase:
+    """a list, the size of its destination picture, its source planes and the destination planes it must produce"""
+
+    def __init__(self, name, lst, w, h, src, want, rng_max=0):
+        self.name, self.lst, self.w, self.h, self.src, self.want, self.rng_max = name, lst, w, h, src, want, rng_max
+        self.f32 = lst.write.type == F32
+
+    def bufs(self, frames=1, dst_fill=FILL, src_off=0, dst_off=0, tight=False):
+        """(source Bufs with picture 0 filled in, destination Bufs holding the fill).  `tight`: line pitches of row bytes + 7 rounded
+        up to the element, the least a caller may choose"""
+        es, ed = SIZE[self.lst.read.type], SIZE[self.lst.write.type]
+        tp = lambda rows, el: (rows + 7 + el - 1) // el * el if tight else None      # noqa: E731
+        sb = [Buf(a.shape[1], a.shape[0], frames, src_off * es, tp(a.shape[1], es)) for a in self.src]
+        db = [Buf(a.shape[1], a.shape[0], frames, dst_off * ed, tp(a.shape[1], ed), fill=dst_fill) for a in self.want]
+        for b, a in zip(sb, self.src):
+            b.payload(0)[:] = a
+        return sb, db
+
+    def randomise(self, rng, sb, frames):
+        for b in sb:
+            for f in frames:
+                b.payload(f)[:] = random_rows(rng, self.lst, (b.lines, b.rows), self.rng_max)
+
+
+def run_rects(call, case, block, sb, s_addrs, db, d_addrs, rects):
+    """one call per rectangle: call(exec, bx_start, y_start, bx_end, y_end)"""
+    for x0, x1, y0, y1 in rects:
+        e = rect_exec(case.lst, s_addrs, [b.pitch for b in sb], d_addrs, [b.pitch for b in db], case.w, case.h, block, x0, x1, y0)
+        call(e, x0 // block, y0, x1 // block, y1)
+
+
+def oracle_into(g, case, sb, db, frames):
+    """the oracle's whole-picture answer for pictures `frames` of the source Bufs, written into the same pictures of `db`"""
+    h = C.c_void_p()
+    assert g("compile")(case.lst.uops, case.lst.n, C.byref(h)) == 0, case.name
+    bs = g("block_size")(h)
+    for f in frames:
+        e = plain_exec(case.lst, [b.flat.ctypes.data + b.off + f * b.fpitch for b in sb], [b.pitch for b in sb],
+                       [b.flat.ctypes.data + b.off + f * b.fpitch for b in db], [b.pitch for b in db], case.w, case.h, bs)
+        g("func")(C.byref(e), h, 0, 0, (case.w + bs - 1) // bs, case.h)
+    g("free")(C.byref(h))
+
+
+def oracle_pictures(g, case, sb, frames):
+    """-> {frame: [destination planes]}"""
+    db = [Buf(a.shape[1], a.shape[0], sb[0].frames) for a in case.want]
+    oracle_into(g, case, sb, db, frames)
+    assert all(b.outside_kept() for b in db), case.name
+    return {f: [b.payload(f).copy() for b in db] for f in frames}
+
+
+HAND_W, HAND_H = 88, 9      # whole 8-pixel blocks; 44 2-pixel blocks, so that the tiling's columns 2, 6 and 46 are off a thread's 4 pixels
+
+_rect_cases = {}
+
+
+def rect_cases(path, g):
+    """the committed lists of real conversions (expectation: backend_c's committed output) and three hand-built lists for the 4-bit
+    and 1-bit accesses the fixture lacks (expectation: the oracle `g` on the whole picture).  Built once; nobody writes into them.
+    Pixel values are 0..15 / 0..15 / 0..1 as in checkasm's check_write: for the packed reads that is every byte pattern."""
+    if path in _rect_cases:
+        return _rect_cases[path]
+    out = [RectCase("%s %dx%d-%dx%d" % ((name,) + size), lst, size[2], size[3], src, dst) for name, size, lst, src, dst in golden_cases(path)]
+    rng = np.random.default_rng(4100)
+    w, h = HAND_W, HAND_H
+    for name, uops, rows_in, rows_out, rng_max in (
+            ("hand nibble-read", [_mk(U8, READ_NIBBLE, 1), _mk(U8, WRITE_PLANAR, 1)], w // 2, w, 0),
+            ("hand nibble-write", [_mk(U8, READ_PLANAR, 1), _mk(U8, WRITE_NIBBLE, 1)], w, w // 2, 15),
+            ("hand bit-read", [_mk(U8, READ_BIT, 1), _mk(U8, WRITE_PLANAR, 1)], w // 8, w, 0)):
+        lst = HandList(uops)
+        case = RectCase(name, lst, w, h, [random_rows(rng, lst, (h, rows_in), rng_max)], [np.zeros((h, rows_out), np.uint8)], rng_max)
+        sb, _ = case.bufs()
+        case.want = oracle_pictures(g, case, sb, [0])[0]
+        out.append(case)
+    for c in out:
+        for a in c.src + c.want:
+            a.setflags(write=False)
+    _rect_cases[path] = out
+    return out
+
+

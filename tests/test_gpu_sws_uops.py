@@ -88,8 +88,10 @@ def test_every_micro_op_instance():
 
 
 def test_ragged_ranges_and_misaligned_planes():
-    """sub-ranges of a line (bx_start > 0, widths that are not whole vectors) and planes at odd byte addresses: the vector loads of
-    the generated kernels must not assume alignment, and nothing outside the blocks may be written"""
+    """sub-ranges of a line (bx_start > 0, widths that are not whole vectors) and host planes at odd byte addresses: the host face's
+    staging takes planes at any host address (it copies every plane into its arena, so the kernels see aligned slots whatever `off`
+    is), and nothing below the planes or outside the blocks is written.  What the generated vector loads and stores make of
+    unaligned DEVICE planes is test_gpu_sws_uops_rects.py::test_device_planes_at_any_address"""
     L, g = _lib()
     O, go = _oracle()
     rng = np.random.default_rng(77)
@@ -118,17 +120,19 @@ PAIRS = [("yuv444p", "rgb24"), ("rgb24", "yuv444p"), ("rgb24", "bgra"), ("gbrp",
          ("rgb24", "gbrpf32le"), ("x2rgb10le", "rgb24"), ("gray16le", "gray")]
 
 
-@pytest.mark.parametrize("sf,df", PAIRS)
-def test_graph_with_libffhip_as_backend(sf, df):
+@pytest.mark.parametrize("sf,df,threads", [(sf, df, t) for t in (1, 4) for sf, df in PAIRS],
+                         ids=["%s-%s" % (sf, df) + ("-threads%d" % t if t > 1 else "") for t in (1, 4) for sf, df in PAIRS])
+def test_graph_with_libffhip_as_backend(sf, df, threads):
     """sws_scale_frame() of the reference with backend_hip bound to libffhip == with backend_c: the reference generates, optimises,
-    splits and translates the op list, its dispatcher (ops_dispatch.c:403-500) calls ffhip_sws_uops_func with host pointers."""
+    splits and translates the op list, its dispatcher (ops_dispatch.c:403-500) calls ffhip_sws_uops_func with host pointers.  With 4
+    threads the dispatcher cuts the picture into slices and the calls arrive with y_start > 0, from several threads at once."""
     from test_sws_uops_cpu import graph_parity, SIZES
     if not ffi.have_ref():
         pytest.skip("the reference's graph: oracle/_ref/libffref.so not built (test_golden_lists_host_and_device runs its lists)")
     L, g = _lib()
     R = S.declare_ref(ffi.ref())
     before = L.ffhip_shim_fallbacks()
-    took = graph_parity(R, L, "ffhip_sws_uops_", sf, df, SIZES + [(320, 180, 640, 352), (1920, 16, 960, 8)])
+    took = graph_parity(R, L, "ffhip_sws_uops_", sf, df, SIZES + [(320, 180, 640, 352), (1920, 16, 960, 8)], threads=threads)
     assert took > 0
     assert L.ffhip_shim_fallbacks() == before, "the host face answered through backend_c"
 

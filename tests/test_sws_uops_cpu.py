@@ -77,8 +77,9 @@ def convert_pair(R, sf, df, size, backends, rng_seed, slack=0, **kw):
     return r, out
 
 
-def graph_parity(R, L, prefix, sf, df, sizes):
-    """sws_scale_frame() with backend_hip bound to L == with backend_c; returns the number of lists the bound backend compiled"""
+def graph_parity(R, L, prefix, sf, df, sizes, threads=1):
+    """sws_scale_frame() with backend_hip bound to L == with backend_c; returns the number of lists the bound backend compiled.
+    `threads`: of the run with the bound backend (its dispatcher then calls slice by slice); backend_c's answer is the 1-thread one"""
     took = 0
     for size in sizes:
         for kw in ({}, {"scaler": 1}):          # default scaler (bicubic), bilinear
@@ -95,7 +96,7 @@ def graph_parity(R, L, prefix, sf, df, sizes):
             S.bind(R, L, prefix)
             R.ffref_sws_hip_count(-1)
             try:
-                rh, got = convert_pair(R, sf, df, size, S.BACKEND_HIP | S.BACKEND_MEMCPY, 7, **kw)
+                rh, got = convert_pair(R, sf, df, size, S.BACKEND_HIP | S.BACKEND_MEMCPY, 7, threads=threads, **kw)
             finally:
                 S.unbind(R)
             assert rh >= 0, (sf, df, size, rh)
