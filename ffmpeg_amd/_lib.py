@@ -355,6 +355,8 @@ def lib():
         "ffhip_h264_bs_mvf_record_size": (C.c_int, []),
         "ffhip_h264_bs_slice_record_size": (C.c_int, []),
         "ffhip_h264_inter_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_h264_inter_pictures_fmt_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_h264_inter_pictures_fmt_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "ffhip_h264_inter_plan_pictures_host": (C.c_int, [C.c_int, C.c_int, C.c_int, vp]),
         "ffhip_h264_inter_slice_record_size": (C.c_int, []),
         "ffhip_h264_inter_ref_record_size": (C.c_int, []),
@@ -363,6 +365,8 @@ def lib():
         "ffhip_h264_inter_plan_pic_record_size": (C.c_int, []),
         "ffhip_h264_residual_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_h264_residual_pictures_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "ffhip_h264_residual_pictures_fmt_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_h264_residual_pictures_fmt_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "ffhip_h264_res_mb_record_size": (C.c_int, []),
         "ffhip_h264_res_pic_record_size": (C.c_int, []),
         "ffhip_hevc_residual_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp]),

@@ -1,7 +1,7 @@
 /*
- * h264_inter_pic.hip — H.264 inter prediction of whole pictures in one launch (ffhip_h264_inter_pictures_dev): the predicted
- * samples of every inter macroblock from the macroblock records, the 4x4 motion field and the slice table the edge-parameter face
- * (h264_bs_pic.hip) takes, both lists and the weighting combined in registers, every sample written once.
+ * h264_inter_pic.hip — H.264 inter prediction of whole pictures in one launch (ffhip_h264_inter_pictures_dev and its _fmt face): the
+ * predicted samples of every inter macroblock from the macroblock records, the 4x4 motion field and the slice table the
+ * edge-parameter face (h264_bs_pic.hip) takes, both lists and the weighting combined in registers, every sample written once.
  *
  * One workgroup of 4 waves per (picture, macroblock); an intra macroblock's workgroup exits at once.  Wave q takes the 8x8 quadrant q
  * as four 4x4 blocks of 16 lanes, a lane per luma sample.  Nothing is shared between waves, so there is no workgroup barrier:
@@ -12,6 +12,13 @@
  *   3. average / weight / biweight in registers;
  *   4. the samples go through a wave-private LDS tile and leave as whole rows of a block: one 4-sample store per luma row and one
  *      2-sample store per chroma row.  Nothing goes to HBM between the lists.
+ * The chroma format is a template parameter FMT:
+ *   FMT 1  4:2:0 and monochrome, as above;
+ *   FMT 2  4:2:2: a block's 2x4 Cb plus 2x4 Cr samples are exactly its 16 lanes, so every lane is a chroma lane (lane j: plane j >> 3,
+ *          sample (j & 1, (j >> 1) & 3)); the chroma tile has 16 entries per block and leaves as four 2-sample rows per plane;
+ *   FMT 3  4:4:4: steps 2 to 4 run once per plane on the plane's reference and destination, with the chroma values of the plan for
+ *          Cb and Cr; the plan and the vectors stay resolved once in registers, and the window's reuse by the next plane lies behind the
+ *          same ffhip_wave_sync() pairs as its reuse by the next list.
  * The interpolation and the weighting are h264_mc_rules.h's per-sample statements, which h264_hbd.hip's kernels run too; the source
  * coordinates are clamped as FFHIP_MC_EMU records are.
  */
@@ -34,7 +41,6 @@ static_assert(H4I_PICS * sizeof(FFHipH264InterPic) <= FFHIP_PROGRESS_SLOT_INTS *
 namespace {
 constexpr int WIN = 9;              /* a 4x4 block's window: 2 samples before, 3 after */
 constexpr int WIN_PITCH = 84;       /* uint16_t entries per block window (81 used) */
-constexpr int WAVE_LDS = 4 * WIN_PITCH + 64 + 32; /* four windows, the luma tile, the chroma tile */
 
 /* a lane's sample in its block's LDS window */
 struct WinSrc {
@@ -53,9 +59,13 @@ struct ClampSrc {
     }
 };
 
-template <typename P>
-__global__ __launch_bounds__(256) void k_h264_inter_pic(const FFHipH264InterPic *pics, int mb_w, int mb_h, int bd, int chroma)
+/* 8 waves per SIMD asked for by name: left to itself the 4:2:2 form takes 65 VGPRs, one past the step (with it 63, no scratch) */
+template <typename P, int FMT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void k_h264_inter_pic(const FFHipH264InterPic *pics, int mb_w, int mb_h, int bd, int chroma)
 {
+    constexpr int CT = FMT == 2 ? 16 : 8;                   /* chroma tile entries per block */
+    constexpr int WAVE_LDS = 4 * WIN_PITCH + 64 + 4 * CT;   /* four windows, the luma tile, the chroma tile */
     __shared__ uint16_t lds[4 * WAVE_LDS];
     const FFHipH264InterPic &Pc = pics[blockIdx.z];
     const int mx = blockIdx.x, my = blockIdx.y;
@@ -67,89 +77,88 @@ __global__ __launch_bounds__(256) void k_h264_inter_pic(const FFHipH264InterPic 
     const FFHipH264MvField f = Pc.mvf[(ptrdiff_t)by * Pc.mvf_stride + bx];
     const FFHipH264InterBlockPlan plan = h264inter_plan(&m, &f, Pc.slices, Pc.nslices, Pc.nrefs);
     const bool live = plan.mode != FFHIP_H264_INTER_SKIP, bi = plan.mode >= FFHIP_H264_INTER_BI_AVG;
-    const bool has_c = chroma && Pc.dst[1], clane = has_c && j < 8;
-    const int cpl = (j >> 2) & 1, cxs = j & 1, cys = (j >> 1) & 1;      /* a chroma lane's plane (0 Cb, 1 Cr) and sample of the 2x2 block */
+    const bool has_c = chroma && Pc.dst[1], clane = FMT != 3 && has_c && (FMT == 2 || j < 8);
+    /* a chroma lane's plane (0 Cb, 1 Cr) and sample of the block's 2x2 (2x4 at 4:2:2) chroma block */
+    const int cpl = FMT == 2 ? j >> 3 : (j >> 2) & 1, cxs = j & 1, cys = FMT == 2 ? (j >> 1) & 3 : (j >> 1) & 1;
     uint16_t *win = lds + q * WAVE_LDS + k * WIN_PITCH, *ytile = lds + q * WAVE_LDS + 4 * WIN_PITCH, *ctile = ytile + 64;
     const int pw = mb_w * 16, ph = mb_h * 16, maxv = (1 << bd) - 1;
-    int pl[2] = { 0, 0 }, pc[2] = { 0, 0 };
+    const int nplanes = FMT == 3 && has_c ? 3 : 1;          /* the planes that take the luma path */
 
+#pragma unroll 1
+    for (int p = 0; p < nplanes; p++) {
+        int pl[2] = { 0, 0 }, pc[2] = { 0, 0 };
 #pragma unroll
-    for (int n = 0; n < 2; n++) {
-        const bool on = live && (n == 0 || bi);
-        const int L = bi ? n : plan.list;
-        const int mvx = L ? f.mv[1][0] : f.mv[0][0], mvy = L ? f.mv[1][1] : f.mv[0][1], fx = mvx & 3, fy = mvy & 3;
-        const FFHipH264InterRef &R = Pc.ref[on ? (n ? plan.slot[1] : plan.slot[0]) : 0];
-        if (on) {
-            /* the window's origin is 2 left of / above the block's source position */
-            const int ox = bx * 4 + (mvx >> 2) - 2, oy = by * 4 + (mvy >> 2) - 2;
-            const uint8_t *base = R.base[0];
-            const ptrdiff_t s = R.stride[0];
-            for (int i = j; i < WIN * WIN; i += 16) {
-                const int r = i / WIN, c = i - r * WIN;
-                if ((!fy && (r < 2 || r > 5)) || (!fx && (c < 2 || c > 5)))
-                    continue;
-                const int yy = min(max(oy + r, 0), ph - 1), xx = min(max(ox + c, 0), pw - 1);
-                win[i] = reinterpret_cast<const P *>(base + (ptrdiff_t)yy * s)[xx];
+        for (int n = 0; n < 2; n++) {
+            const bool on = live && (n == 0 || bi);
+            const int L = bi ? n : plan.list;
+            const int mvx = L ? f.mv[1][0] : f.mv[0][0], mvy = L ? f.mv[1][1] : f.mv[0][1], fx = mvx & 3, fy = mvy & 3;
+            const FFHipH264InterRef &R = Pc.ref[on ? (n ? plan.slot[1] : plan.slot[0]) : 0];
+            if (on) {
+                /* the window's origin is 2 left of / above the block's source position */
+                const int ox = bx * 4 + (mvx >> 2) - 2, oy = by * 4 + (mvy >> 2) - 2;
+                const uint8_t *base = FMT == 3 ? R.base[p] : R.base[0];
+                const ptrdiff_t s = FMT == 3 ? R.stride[p] : R.stride[0];
+                for (int i = j; i < WIN * WIN; i += 16) {
+                    const int r = i / WIN, c = i - r * WIN;
+                    if ((!fy && (r < 2 || r > 5)) || (!fx && (c < 2 || c > 5)))
+                        continue;
+                    const int yy = min(max(oy + r, 0), ph - 1), xx = min(max(ox + c, 0), pw - 1);
+                    win[i] = reinterpret_cast<const P *>(base + (ptrdiff_t)yy * s)[xx];
+                }
             }
+            ffhip_wave_sync();
+            if (on) {
+                const WinSrc S = { win + (y4 + 2) * WIN + x4 + 2 };
+                H264MC_LUMA(pl[n], S, fx, fy, maxv);
+                if (clane) {
+                    const H264InterChroma C = h264inter_chroma(FMT, bx, by, mvx, mvy, R.chroma_dy, mb_w, mb_h);
+                    const ClampSrc<P> Sc = { R.base[1 + cpl], R.stride[1 + cpl], C.sx + cxs, C.sy + cys, C.cw, C.ch };
+                    pc[n] = h264mc_chroma(Sc, C.ax, C.ay);
+                }
+            }
+            ffhip_wave_sync(); /* list 1's window, or the next plane's, overwrites list 0's */
         }
+
+        /* ---- 3. the lists combined ---- */
+        const int yv = h264inter_combine(&plan, FMT == 3 ? p : 0, pl[0], pl[1], bd);
+
+        /* ---- 4. whole rows of a block ---- */
+        ytile[lane] = (uint16_t)yv;
+        if (FMT != 3 && (FMT == 2 || j < 8))
+            ctile[k * CT + j] = (uint16_t)h264inter_combine(&plan, 1 + cpl, pc[0], pc[1], bd);
         ffhip_wave_sync();
-        if (on) {
-            const WinSrc S = { win + (y4 + 2) * WIN + x4 + 2 };
-            H264MC_LUMA(pl[n], S, fx, fy, maxv);
-            if (clane) {
-                const int cx = mvx, cy = mvy + R.chroma_dy, ax = cx & 7, ay = cy & 7;
-                const ClampSrc<P> Sc = { R.base[1 + cpl], R.stride[1 + cpl], bx * 2 + cxs + (cx >> 3), by * 2 + cys + (cy >> 3), pw >> 1, ph >> 1 };
-                pc[n] = h264mc_chroma(Sc, ax, ay);
-            }
+        if (!live)
+            continue;
+        if (x4 == 0) { /* lanes j = 0, 4, 8, 12: row y4 of the block, 4 samples; dst base and stride are multiples of 4 samples */
+            const uint16_t *r = ytile + k * 16 + y4 * 4;
+            uint8_t *d = (FMT == 3 ? Pc.dst[p] : Pc.dst[0]) + (ptrdiff_t)(by * 4 + y4) * (FMT == 3 ? Pc.dst_stride[p] : Pc.dst_stride[0]) +
+                         (size_t)bx * 4 * sizeof(P);
+            if (sizeof(P) == 1)
+                *reinterpret_cast<uint32_t *>(d) = pack4(r[0], r[1], r[2], r[3]);
+            else
+                *reinterpret_cast<uint2 *>(d) = make_uint2((uint32_t)r[0] | (uint32_t)r[1] << 16, (uint32_t)r[2] | (uint32_t)r[3] << 16);
+        } else if (FMT != 3 && has_c && (x4 == 1 || (FMT == 2 && x4 == 2))) {
+            /* 4:2:0: lanes j = 1, 5, 9, 13: chroma row (y4 & 1) of plane (y4 >> 1); 4:2:2: lanes with x4 = 1 / 2: row y4 of Cb / Cr; 2 samples */
+            const int c = FMT == 2 ? x4 - 1 : y4 >> 1, row = FMT == 2 ? y4 : y4 & 1, rows = FMT == 2 ? 4 : 2;
+            const uint16_t *r = ctile + k * CT + (c * rows + row) * 2;
+            uint8_t *d = Pc.dst[1 + c] + (ptrdiff_t)(by * rows + row) * Pc.dst_stride[1 + c] + (size_t)bx * 2 * sizeof(P);
+            if (sizeof(P) == 1)
+                *reinterpret_cast<uint16_t *>(d) = (uint16_t)(r[0] | r[1] << 8);
+            else
+                *reinterpret_cast<uint32_t *>(d) = (uint32_t)r[0] | (uint32_t)r[1] << 16;
         }
-        ffhip_wave_sync(); /* list 1's window overwrites list 0's */
     }
+}
 
-    /* ---- 3. the lists combined ---- */
-    const int cw0 = cpl ? plan.chroma_weight[1][0] : plan.chroma_weight[0][0], cw1 = cpl ? plan.chroma_weight[1][1] : plan.chroma_weight[0][1];
-    const int co = cpl ? plan.chroma_offset[1] : plan.chroma_offset[0];
-    int yv = pl[0], cv = pc[0];
-    switch (plan.mode) {
-    case FFHIP_H264_INTER_UNI_W:
-        yv = h264mc_weight(pl[0], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_offset);
-        if (plan.chroma_weighted)
-            cv = h264mc_weight(pc[0], bd, plan.chroma_log2_denom, cw0, co);
-        break;
-    case FFHIP_H264_INTER_BI_AVG:
-        yv = h264mc_avg(pl[0], pl[1]);
-        cv = h264mc_avg(pc[0], pc[1]);
-        break;
-    case FFHIP_H264_INTER_BI_W:
-        yv = h264mc_biweight(pl[0], pl[1], bd, plan.luma_log2_denom, plan.luma_weight[0], plan.luma_weight[1], plan.luma_offset);
-        cv = h264mc_biweight(pc[0], pc[1], bd, plan.chroma_log2_denom, cw0, cw1, co);
-        break;
-    default:
-        break;
-    }
-
-    /* ---- 4. whole rows of a block ---- */
-    ytile[lane] = (uint16_t)yv;
-    if (j < 8)
-        ctile[k * 8 + j] = (uint16_t)cv;
-    ffhip_wave_sync();
-    if (!live)
-        return;
-    if (x4 == 0) { /* lanes j = 0, 4, 8, 12: luma row y4 of the block, 4 samples; dst base and stride are multiples of 4 samples */
-        const uint16_t *r = ytile + k * 16 + y4 * 4;
-        uint8_t *d = Pc.dst[0] + (ptrdiff_t)(by * 4 + y4) * Pc.dst_stride[0] + (size_t)bx * 4 * sizeof(P);
-        if (sizeof(P) == 1)
-            *reinterpret_cast<uint32_t *>(d) = pack4(r[0], r[1], r[2], r[3]);
-        else
-            *reinterpret_cast<uint2 *>(d) = make_uint2((uint32_t)r[0] | (uint32_t)r[1] << 16, (uint32_t)r[2] | (uint32_t)r[3] << 16);
-    } else if (has_c && x4 == 1) { /* lanes j = 1, 5, 9, 13: chroma row (y4 & 1) of plane (y4 >> 1), 2 samples */
-        const int c = y4 >> 1, row = y4 & 1;
-        const uint16_t *r = ctile + k * 8 + c * 4 + row * 2;
-        uint8_t *d = Pc.dst[1 + c] + (ptrdiff_t)(by * 2 + row) * Pc.dst_stride[1 + c] + (size_t)bx * 2 * sizeof(P);
-        if (sizeof(P) == 1)
-            *reinterpret_cast<uint16_t *>(d) = (uint16_t)(r[0] | r[1] << 8);
-        else
-            *reinterpret_cast<uint32_t *>(d) = (uint32_t)r[0] | (uint32_t)r[1] << 16;
-    }
+template <typename P>
+void launch(int fmt, dim3 grid, hipStream_t stream, const FFHipH264InterPic *dpics, int mb_w, int mb_h, int bd)
+{
+    if (fmt == 3)
+        hipLaunchKernelGGL((k_h264_inter_pic<P, 3>), grid, dim3(256), 0, stream, dpics, mb_w, mb_h, bd, 1);
+    else if (fmt == 2)
+        hipLaunchKernelGGL((k_h264_inter_pic<P, 2>), grid, dim3(256), 0, stream, dpics, mb_w, mb_h, bd, 1);
+    else
+        hipLaunchKernelGGL((k_h264_inter_pic<P, 1>), grid, dim3(256), 0, stream, dpics, mb_w, mb_h, bd, fmt);
 }
 } // namespace
 
@@ -161,9 +170,9 @@ int ffhip_launch_h264_inter_pictures(int bd, int chroma_format_idc, int mb_w, in
                                                   [&](FFHipH264InterPic *dpics) {
             const dim3 grid(mb_w, mb_h, n); /* at most 4096 x 4096 x 16 */
             if (bd > 8)
-                hipLaunchKernelGGL(k_h264_inter_pic<uint16_t>, grid, dim3(256), 0, stream, dpics, mb_w, mb_h, bd, chroma_format_idc);
+                launch<uint16_t>(chroma_format_idc, grid, stream, dpics, mb_w, mb_h, bd);
             else
-                hipLaunchKernelGGL(k_h264_inter_pic<uint8_t>, grid, dim3(256), 0, stream, dpics, mb_w, mb_h, bd, chroma_format_idc);
+                launch<uint8_t>(chroma_format_idc, grid, stream, dpics, mb_w, mb_h, bd);
         });
         if (r < 0)
             return r;

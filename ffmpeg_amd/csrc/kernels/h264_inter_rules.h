@@ -1,7 +1,9 @@
 /*
  * h264_inter_rules.h — how the lists of one 4x4 block combine in H.264 inter prediction (rules 1, 2 and 5 to 8 of
- * ffhip_h264_inter_pictures_dev as include/ffhip.h states them), once: shared by the kernel of h264_inter_pic.hip and by the
- * device-free face ffhip_h264_inter_plan_pictures_host() (shims_h264_inter.hip), which runs it on the host.  Restated from memory of
+ * ffhip_h264_inter_pictures_dev as include/ffhip.h states them), where a block's chroma samples lie and come from at each chroma
+ * format (rule 4, 4a / 4b of the _fmt faces: h264inter_chroma) and what a mode makes of the lists' samples on a plane
+ * (h264inter_combine), once: shared by the kernel of h264_inter_pic.hip and by the device-free faces
+ * ffhip_h264_inter_plan_pictures_host() and ffhip_h264_inter_pictures_fmt_host() (shims_h264_inter.hip), which run it on the host.  Restated from memory of
  * the reference's h264_mb.c (mc_part and what it calls) and from H.264 8.4.2.2 / 8.4.2.3, not checked against its source.  One plain
  * function of the macroblock record, the block's motion record and the slice table; it reads nothing else.  What a mode does to the
  * samples (weight / biweight_h264_pixels) is h264_mc_rules.h's.
@@ -12,6 +14,7 @@
 #include <stdint.h>
 
 #include "ffhip.h"
+#include "h264_mc_rules.h"
 
 #if defined(__HIPCC__)
 #define H264INTER_FN __host__ __device__ __forceinline__
@@ -94,6 +97,55 @@ H264INTER_FN FFHipH264InterBlockPlan h264inter_plan(const FFHipH264BsMb *m, cons
         }
     }
     return p;
+}
+
+/* Rule 4 by format (chroma_format_idc 1 or 2; at 3 Cb and Cr are luma planes): the chroma block of the 4x4 luma block (bx, by), in
+ * samples of a chroma plane, for the vector (mvx, mvy) of one list.  w x h samples at (x, y); sample (i, k) of it is h264chroma's put
+ * with the fractions (ax, ay) at the source position (sx + i, sy + k), each source coordinate clamped to [0, cw) x [0, ch). */
+struct H264InterChroma { int w, h, x, y, sx, sy, ax, ay, cw, ch; };
+H264INTER_FN H264InterChroma h264inter_chroma(int chroma_format_idc, int bx, int by, int mvx, int mvy, int chroma_dy, int mb_w, int mb_h)
+{
+    H264InterChroma c;
+    c.w = 2;
+    c.x = 2 * bx;
+    c.sx = c.x + (mvx >> 3);
+    c.ax = mvx & 7;
+    c.cw = 8 * mb_w;
+    if (chroma_format_idc == 2) {       /* mc_dir_part with ysh = 2; chroma_dy is 4:2:0's alone */
+        c.h = 4;
+        c.y = 4 * by;
+        c.sy = c.y + (mvy >> 2);
+        c.ay = (mvy * 2) & 7;          /* (my << 1) & 7 */
+        c.ch = 16 * mb_h;
+    } else {
+        const int cy = mvy + chroma_dy;
+        c.h = 2;
+        c.y = 2 * by;
+        c.sy = c.y + (cy >> 3);
+        c.ay = cy & 7;
+        c.ch = 8 * mb_h;
+    }
+    return c;
+}
+
+/* Rules 5 to 9 on a sample of plane pl (0 luma; 1 Cb, 2 Cr: the chroma values, at every format): p0 the sample of list 0 or of the
+ * one list, p1 that of list 1 */
+H264INTER_FN int h264inter_combine(const FFHipH264InterBlockPlan *p, int pl, int p0, int p1, int bd)
+{
+    const int c = pl == 2;
+    const int ld = pl ? p->chroma_log2_denom : p->luma_log2_denom;
+    const int w0 = pl ? p->chroma_weight[c][0] : p->luma_weight[0], w1 = pl ? p->chroma_weight[c][1] : p->luma_weight[1];
+    const int o = pl ? p->chroma_offset[c] : p->luma_offset;
+    switch (p->mode) {
+    case FFHIP_H264_INTER_UNI_W:
+        return pl && !p->chroma_weighted ? p0 : h264mc_weight(p0, bd, ld, w0, o);
+    case FFHIP_H264_INTER_BI_AVG:
+        return h264mc_avg(p0, p1);
+    case FFHIP_H264_INTER_BI_W:
+        return h264mc_biweight(p0, p1, bd, ld, w0, w1, o);
+    default:
+        return p0;
+    }
 }
 
 #endif /* FFHIP_H264_INTER_RULES_H */

@@ -127,10 +127,12 @@ int ffhip_launch_hevc_boundary_strengths_pictures(int width, int height, int log
 /* H.264 deblocking edge parameters of whole pictures (h264_bs_pic.hip), arguments validated by ffhip_h264_edge_params_pictures_dev() */
 int ffhip_launch_h264_edge_params_pictures(int mb_w, int mb_h, int field, int qp_bd_offset, int npics, const FFHipH264BsPic *pics,
                                            hipStream_t stream);
-/* H.264 inter prediction of whole pictures (h264_inter_pic.hip), arguments validated by ffhip_h264_inter_pictures_dev() */
+/* H.264 inter prediction of whole pictures (h264_inter_pic.hip), chroma_format_idc 0 .. 3; arguments validated by
+ * ffhip_h264_inter_pictures_dev() / _fmt_dev() */
 int ffhip_launch_h264_inter_pictures(int bd, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264InterPic *pics,
                                      hipStream_t stream);
-/* H.264 residuals of whole pictures (h264_res_pic.hip), arguments validated by ffhip_h264_residual_pictures_dev() */
+/* H.264 residuals of whole pictures (h264_res_pic.hip), chroma_format_idc 0 .. 3; arguments validated by
+ * ffhip_h264_residual_pictures_dev() / _fmt_dev() */
 int ffhip_launch_h264_residual_pictures(int bd, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264ResPic *pics,
                                         hipStream_t stream);
 /* HEVC residuals of whole pictures (hevc_res_pic.hip),arguments validated by ffhip_hevc_residual_pictures_dev() */

@@ -1,10 +1,16 @@
 /*
- * h264_res_pic.hip — the residual of every inter macroblock of whole H.264 pictures in one launch (ffhip_h264_residual_pictures_dev):
+ * h264_res_pic.hip — the residual of every inter macroblock of whole H.264 pictures in one launch (ffhip_h264_residual_pictures_dev,
+ * ffhip_h264_residual_pictures_fmt_dev):
  * idct_add16 / idct8_add4, chroma_dc_dequant_idct and idct_add8 of all planes from the macroblock array of the inter and the
  * edge-parameter faces plus one FFHipH264ResMb per macroblock, with no list sorted by transform size on the host.
  *
  * 32 lanes per macroblock, 8 macroblocks per workgroup of 4 waves, macroblocks in raster order along blockIdx.x.  Lane r of a
- * macroblock: r < 16 is luma block r of the decoder's order, 16 .. 19 the Cb blocks, 20 .. 23 the Cr blocks, 24 .. 31 idle.  Every lane
+ * macroblock: r < 16 is luma block r of the decoder's order, 16 .. 19 the Cb blocks, 20 .. 23 the Cr blocks, 24 .. 31 idle.  The chroma
+ * format is a template parameter FMT.  FMT 2 (4:2:2): 16 luma + 8 Cb + 8 Cr blocks are exactly the 32 lanes (16 .. 23 Cb, 24 .. 31 Cr);
+ * the eight DCs of a plane meet among the plane's eight lanes, two quads of one DPP row, by quad_perm and row_half_mirror.  FMT 3
+ * (4:4:4): the 16 luma lanes walk the three planes one after the other, each with the plane's own bits, which keeps the registers of
+ * the 8x8 quad path where they are; lanes 16 .. 31 stay idle (a macroblock's planes on separate lanes would need a second set of 16
+ * coefficients per lane or a third of the macroblocks per workgroup).  Every lane
  * reads the two records of its macroblock (32 lanes on the same words: one request) and resolves them with h264res_plan(); a lane
  * whose block is not coded leaves before it touches a coefficient.  Luma and chroma 4x4 blocks run through one code path, a lane per
  * block from end to end: the coefficients come in 16-byte loads (2 per block at 8 bits, 4 above), both passes run in registers, and
@@ -74,6 +80,8 @@ __device__ __forceinline__ int quad_xor1(int v) { return __builtin_amdgcn_mov_dp
 __device__ __forceinline__ int quad_xor2(int v) { return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true); }   /* quad_perm [2,3,0,1] */
 template <int N>
 __device__ __forceinline__ int quad_lane(int v) { return __builtin_amdgcn_mov_dpp(v, N * 0x55, 0xf, 0xf, true); }  /* quad_perm [N,N,N,N] */
+/* the value of lane (lane ^ 7) of an aligned group of eight lanes (row_half_mirror); every lane of the group must be active */
+__device__ __forceinline__ int oct_mirror(int v) { return __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, true); }
 
 /* the 4 x 4 transpose over a quad: w[p] of lane q becomes w[q] of lane p */
 __device__ __forceinline__ void quad_transpose(int &w0, int &w1, int &w2, int &w3, int q)
@@ -158,37 +166,62 @@ __device__ __forceinline__ void idct8_add_quad(const CF *c, uint8_t *dst, ptrdif
         add_row4(at + k * stride, PIX(), d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3], maxv);
 }
 
-template <typename PIX, typename CF>
+template <typename PIX, typename CF, int FMT>
 __global__ __launch_bounds__(32 * H4R_MBS) void k_h264_res_pic(const FFHipH264ResPic *pics, int mb_w, int nmb, int bd, int chroma)
 {
     const FFHipH264ResPic &P = pics[blockIdx.z];
     const int r = threadIdx.x & 31;
     const int m = (int)blockIdx.x * H4R_MBS + ((int)threadIdx.x >> 5);      /* nmb <= 4096 * 4096 */
-    if (m >= nmb || r >= 24)
+    if (m >= nmb || r >= (FMT == 2 ? 32 : FMT == 3 ? 16 : 24))
         return;
     const FFHipH264BsMb mb = P.mb[m];
     if (mb.flags & 1)
         return;
     const FFHipH264ResMb R = P.res[m];
-    const H264ResPlan plan = h264res_plan(mb, R, chroma && P.dst[1], P.ncoeffs);
+    const H264ResPlan plan = h264res_plan(mb, R, chroma && P.dst[1], P.ncoeffs, FMT);
     if (!plan.need)
         return;
     const int mx = m % mb_w, my = m / mb_w, maxv = (1 << bd) - 1;
+    if constexpr (FMT == 3) {   /* rule 15: three luma planes, one after the other on the 16 luma lanes */
+        const int np = plan.need == 768 ? 3 : 1, j = r & 3;
+#pragma unroll 1
+        for (int pl = 0; pl < np; pl++) {
+            const CF *c = reinterpret_cast<const CF *>(P.coeffs) + plan.off + 256 * pl + 16 * r;
+            const ptrdiff_t s = P.dst_stride[pl];
+            uint8_t *dst = P.dst[pl] + (ptrdiff_t)(my * 16 + 4 * h264res_y4(r)) * s + (size_t)(mx * 16 + 4 * h264res_x4(r)) * sizeof(PIX);
+            if (plan.t8) {      /* uniform over the quad */
+                if (h264res_luma8_on(plan, r >> 2, pl))
+                    idct8_add_quad<PIX, CF>(c - 16 * j, dst - (ptrdiff_t)(4 * h264res_y4(j)) * s - (size_t)(4 * h264res_x4(j)) * sizeof(PIX), s, j, maxv);
+                continue;
+            }
+            if (!h264res_luma4_on(plan, r, pl))
+                continue;
+            int v[16];
+            load_coefs(c, v);
+            h264res_luma<CF, 16>(v);
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                add_row4(dst + k * s, PIX(), v[k], v[4 + k], v[8 + k], v[12 + k], maxv);
+        }
+        return;
+    }
+    constexpr int NC = FMT == 2 ? 8 : 4;                                    /* 4x4 blocks of a chroma plane */
     const bool luma = r < 16;
-    const int pl = luma ? 0 : 1 + ((r - 16) >> 2), j = r & 3;               /* the plane; a chroma lane's block x + 2 * y */
+    const int pl = luma ? 0 : 1 + ((r - 16) >> (FMT == 2 ? 3 : 2)), j = r & (NC - 1);         /* the plane; a chroma lane's block x + 2 * y */
     /* the lane's 4x4 block: its coefficients, its top-left sample */
     const CF *c = reinterpret_cast<const CF *>(P.coeffs) + plan.off + (luma ? 16 * r : 256 * pl + 16 * j);
-    const int bx = luma ? mx * 16 + 4 * h264res_x4(r) : mx * 8 + 4 * (j & 1), by = luma ? my * 16 + 4 * h264res_y4(r) : my * 8 + 4 * (j >> 1);
+    const int bx = luma ? mx * 16 + 4 * h264res_x4(r) : mx * 8 + 4 * (j & 1), by = luma ? my * 16 + 4 * h264res_y4(r) : my * (2 * NC) + 4 * (j >> 1);
     const ptrdiff_t s = pl == 0 ? P.dst_stride[0] : pl == 1 ? P.dst_stride[1] : P.dst_stride[2];
     uint8_t *dst = (pl == 0 ? P.dst[0] : pl == 1 ? P.dst[1] : P.dst[2]) + (ptrdiff_t)by * s + (size_t)bx * sizeof(PIX);
     if (luma && plan.t8) {  /* lanes 4k .. 4k + 3 share 8x8 block k, whose coefficients and top-left sample are lane 4k's */
+        const int q = r & 3;
         if (h264res_luma8_on(plan, r >> 2))
-            idct8_add_quad<PIX, CF>(c - 16 * j, dst - (ptrdiff_t)(4 * h264res_y4(j)) * s - (size_t)(4 * h264res_x4(j)) * sizeof(PIX), s, j, maxv);
+            idct8_add_quad<PIX, CF>(c - 16 * q, dst - (ptrdiff_t)(4 * h264res_y4(q)) * s - (size_t)(4 * h264res_x4(q)) * sizeof(PIX), s, q, maxv);
         return;
     }
     /* luma and chroma 4x4 blocks take one path: rules 4, 6 and 7 */
     const bool dc_on = !luma && ((plan.chroma_dc >> (pl - 1)) & 1);
-    const bool ac_on = luma ? h264res_luma4_on(plan, r) : (plan.chroma >> (4 * (pl - 1) + j)) & 1;
+    const bool ac_on = luma ? h264res_luma4_on(plan, r) : h264res_chroma_on(plan, pl - 1, j);
     if (!dc_on && !ac_on)
         return;
     int v[16];
@@ -198,10 +231,30 @@ __global__ __launch_bounds__(32 * H4R_MBS) void k_h264_res_pic(const FFHipH264Re
         const uint4 w = *reinterpret_cast<const uint4 *>(c);
         v[0] = sizeof(CF) == 2 ? (int)(int16_t)(w.x & 0xFFFF) : (int)w.x;
     }
-    if (dc_on) {    /* uniform over the plane's four lanes, which are all here */
-        int dc[4] = { quad_lane<0>(v[0]), quad_lane<1>(v[0]), quad_lane<2>(v[0]), quad_lane<3>(v[0]) };
-        h264tx_chroma_dc<CF>(dc, pl == 1 ? R.qmul[0] : R.qmul[1]);
-        v[0] = j == 0 ? dc[0] : j == 1 ? dc[1] : j == 2 ? dc[2] : dc[3];
+    if (dc_on) {    /* uniform over the plane's lanes, which are all here */
+        const int qm = pl == 1 ? R.qmul[0] : R.qmul[1];
+        if constexpr (FMT == 2) {   /* rule 14: the plane's eight lanes, quads 0 (blocks 0 .. 3) and 1 (blocks 4 .. 7) */
+            const int o = oct_mirror(v[0]);     /* block 7 - j's */
+            const int mine[4] = { quad_lane<0>(v[0]), quad_lane<1>(v[0]), quad_lane<2>(v[0]), quad_lane<3>(v[0]) };
+            const int other[4] = { quad_lane<3>(o), quad_lane<2>(o), quad_lane<1>(o), quad_lane<0>(o) };   /* the other quad's, in its order */
+            const bool hi = j & 4;
+            int dc[8];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                dc[i] = hi ? other[i] : mine[i];
+                dc[4 + i] = hi ? mine[i] : other[i];
+            }
+            h264tx_chroma422_dc<CF>(dc, qm);
+            int d = dc[0];
+#pragma unroll
+            for (int i = 1; i < 8; i++)
+                d = j == i ? dc[i] : d;
+            v[0] = d;
+        } else {
+            int dc[4] = { quad_lane<0>(v[0]), quad_lane<1>(v[0]), quad_lane<2>(v[0]), quad_lane<3>(v[0]) };
+            h264tx_chroma_dc<CF>(dc, qm);
+            v[0] = j == 0 ? dc[0] : j == 1 ? dc[1] : j == 2 ? dc[2] : dc[3];
+        }
     }
     if (luma ? h264tx_flat(v) : !ac_on) {  /* rule 9: the *_dc_add form */
         const int d = h264tx_dc(v[0]);
@@ -215,6 +268,17 @@ __global__ __launch_bounds__(32 * H4R_MBS) void k_h264_res_pic(const FFHipH264Re
     for (int k = 0; k < 4; k++)
         add_row4(dst + k * s, PIX(), v[k], v[4 + k], v[8 + k], v[12 + k], maxv);
 }
+
+template <typename PIX, typename CF>
+void launch(int fmt, dim3 grid, hipStream_t stream, const FFHipH264ResPic *dpics, int mb_w, int nmb, int bd)
+{
+    if (fmt == 3)
+        hipLaunchKernelGGL((k_h264_res_pic<PIX, CF, 3>), grid, dim3(32 * H4R_MBS), 0, stream, dpics, mb_w, nmb, bd, 1);
+    else if (fmt == 2)
+        hipLaunchKernelGGL((k_h264_res_pic<PIX, CF, 2>), grid, dim3(32 * H4R_MBS), 0, stream, dpics, mb_w, nmb, bd, 1);
+    else
+        hipLaunchKernelGGL((k_h264_res_pic<PIX, CF, 1>), grid, dim3(32 * H4R_MBS), 0, stream, dpics, mb_w, nmb, bd, fmt);
+}
 } // namespace
 
 int ffhip_launch_h264_residual_pictures(int bd, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264ResPic *pics, hipStream_t stream)
@@ -226,9 +290,9 @@ int ffhip_launch_h264_residual_pictures(int bd, int chroma_format_idc, int mb_w,
                                                   [&](FFHipH264ResPic *dpics) {
             const dim3 grid((nmb + H4R_MBS - 1) / H4R_MBS, 1, n);   /* at most 2^21 x 1 x 16 */
             if (bd > 8)
-                hipLaunchKernelGGL((k_h264_res_pic<uint16_t, int32_t>), grid, dim3(32 * H4R_MBS), 0, stream, dpics, mb_w, nmb, bd, chroma_format_idc);
+                launch<uint16_t, int32_t>(chroma_format_idc, grid, stream, dpics, mb_w, nmb, bd);
             else
-                hipLaunchKernelGGL((k_h264_res_pic<uint8_t, int16_t>), grid, dim3(32 * H4R_MBS), 0, stream, dpics, mb_w, nmb, bd, chroma_format_idc);
+                launch<uint8_t, int16_t>(chroma_format_idc, grid, stream, dpics, mb_w, nmb, bd);
         });
         if (r < 0)
             return r;

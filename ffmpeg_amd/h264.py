@@ -203,10 +203,12 @@ class InterPlanPic(C.Structure):
                 ("nslices", C.c_int32), ("nrefs", C.c_int32), ("pad", C.c_int32)]
 
 
-def inter_pics(pics):
-    """the FFHipH264InterPic array of inter_pictures()'s dicts (the pointers are taken as they are: the caller keeps the tensors)"""
+def inter_pics(pics, ptr=None):
+    """the FFHipH264InterPic array of inter_pictures()'s dicts (the pointers are taken as they are: the caller keeps the tensors);
+    ptr: an entry's address (default: a tensor's data_ptr(); ints are taken as they are)"""
     arr = (InterPic * max(len(pics), 1))()
-    ptr = lambda t: None if t is None else t if isinstance(t, int) else t.data_ptr()
+    at = ptr or (lambda t: t.data_ptr())
+    ptr = lambda t: None if t is None else t if isinstance(t, int) else at(t)
     for i, m in enumerate(pics):
         a = arr[i]
         for p, (t, s) in enumerate(zip(m["dst"], m["dst_stride"])):
@@ -231,6 +233,22 @@ def inter_pictures(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1, stream=No
                                                                _stream(stream)), "ffhip_h264_inter_pictures_dev")
 
 
+def inter_pictures_fmt(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1, stream=None):
+    """ffhip_h264_inter_pictures_fmt_dev: inter_pictures() at chroma_format_idc 0 .. 3 (4:2:2: chroma planes of 8 mb_w x 16 mb_h samples,
+    4:4:4: of 16 mb_w x 16 mb_h); at 0 and 1 the bytes of inter_pictures().  Asynchronous on `stream`."""
+    arr = inter_pics(pics)
+    return _lib.check(_lib.lib().ffhip_h264_inter_pictures_fmt_dev(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p),
+                                                                   _stream(stream)), "ffhip_h264_inter_pictures_fmt_dev")
+
+
+def inter_pictures_fmt_host(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1):
+    """ffhip_h264_inter_pictures_fmt_host (device-free): as inter_pictures_fmt() with numpy arrays (or addresses) throughout; the
+    destination planes are written in place."""
+    arr = inter_pics(pics, lambda a: a.ctypes.data)
+    return _lib.check(_lib.lib().ffhip_h264_inter_pictures_fmt_host(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p)),
+                      "ffhip_h264_inter_pictures_fmt_host")
+
+
 def inter_plan_host(pics, mb_w, mb_h):
     """ffhip_h264_inter_plan_pictures_host (device-free): pics[i] is a dict with the numpy arrays mb, mvf, slices, plans (INTER_PLAN_DTYPE,
     16 * mb_w * mb_h records, written in place) and the ints mvf_stride, nslices, nrefs."""
@@ -246,7 +264,12 @@ def inter_plan_host(pics, mb_w, mb_h):
 #: FFHipH264ResMb (include/ffhip.h): one macroblock of residual_pictures(), parallel to BS_MB_DTYPE.  coeff_offset in coefficients (a
 #: multiple of 16); chroma: bit j Cb block j, bit 4 + j Cr block j; chroma_dc: bit 0 Cb, bit 1 Cr; qmul: Cb, Cr.
 RES_MB_DTYPE = np.dtype([("coeff_offset", np.int32), ("chroma", np.uint8), ("chroma_dc", np.uint8), ("pad", np.uint8, 2), ("qmul", np.int32, 2)])
-assert RES_MB_DTYPE.itemsize == 16
+#: the same 16 bytes with the names the _fmt faces read: chroma_lo422 (4:2:2: bit j - 4 Cb block j = 4..7, bit 4 + (j - 4) Cr) is
+#: pad[0], nnz444 (4:4:4: the low 16 bits are the non-zero bits of Cb, Cr in BS_MB_DTYPE.nnz's layout) shares qmul's bytes.
+RES_MB_FMT_DTYPE = np.dtype({"names": ["coeff_offset", "chroma", "chroma_dc", "chroma_lo422", "pad", "qmul", "nnz444"],
+                             "formats": [np.int32, np.uint8, np.uint8, np.uint8, np.uint8, (np.int32, 2), (np.uint32, 2)],
+                             "offsets": [0, 4, 5, 6, 7, 8, 8], "itemsize": 16})
+assert RES_MB_DTYPE.itemsize == 16 and RES_MB_FMT_DTYPE.itemsize == 16
 RES_PICS_PER_LAUNCH = 16
 
 
@@ -283,6 +306,21 @@ def residual_pictures_host(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1):
     arr = res_pics(pics, lambda a: a.ctypes.data)
     return _lib.check(_lib.lib().ffhip_h264_residual_pictures_host(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p)),
                       "ffhip_h264_residual_pictures_host")
+
+
+def residual_pictures_fmt(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1, stream=None):
+    """ffhip_h264_residual_pictures_fmt_dev: residual_pictures() at chroma_format_idc 0 .. 3; res holds RES_MB_FMT_DTYPE records (the
+    bytes of RES_MB_DTYPE).  At 0 and 1 the bytes of residual_pictures().  Asynchronous on `stream`."""
+    arr = res_pics(pics, lambda t: t.data_ptr())
+    return _lib.check(_lib.lib().ffhip_h264_residual_pictures_fmt_dev(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p),
+                                                                      _stream(stream)), "ffhip_h264_residual_pictures_fmt_dev")
+
+
+def residual_pictures_fmt_host(pics, mb_w, mb_h, bit_depth=8, chroma_format_idc=1):
+    """ffhip_h264_residual_pictures_fmt_host (device-free): as residual_pictures_fmt() with numpy arrays; the planes are written in place."""
+    arr = res_pics(pics, lambda a: a.ctypes.data)
+    return _lib.check(_lib.lib().ffhip_h264_residual_pictures_fmt_host(bit_depth, chroma_format_idc, mb_w, mb_h, len(pics), C.cast(arr, C.c_void_p)),
+                      "ffhip_h264_residual_pictures_fmt_host")
 
 
 class Picture:

@@ -715,7 +715,8 @@ int ffhip_h264_bs_slice_record_size(void);
  *     weights); offsets in 8-bit units, scaled by the depth inside as the batch faces take them.
  * 10. Every sample of every well-formed block of a non-intra macroblock is written exactly once; nothing else is: not intra
  *     macroblocks, not the stride padding, no input.
- * Out of scope: the residual (ffhip_h264_residual_pictures_dev below follows on the same stream), 4:2:2 / 4:4:4, MBAFF.
+ * Out of scope: the residual (ffhip_h264_residual_pictures_dev below follows on the same stream), MBAFF; 4:2:2 / 4:4:4 are the _fmt
+ * faces' (after the residual faces below).
  */
 typedef struct FFHipH264InterSlice {       /* what mc_part() reads from the slice, 2888 bytes */
     uint8_t  ref[2][32];                   /* [list][ref_idx] -> slot: index into FFHipH264InterPic.ref */
@@ -823,14 +824,20 @@ int ffhip_h264_inter_plan_pic_record_size(void);
  * 11. results clip to (1 << bit_depth) - 1.
  * 12. m.slice and m.qp are not looked at: a caller whose inter call dropped a macroblock as malformed drops it here too (nnz 0, no
  *     chroma bits).
- * Out of scope: the lossless bypass, MBAFF, luma DC (intra 16x16), I_PCM, 4:2:2 / 4:4:4.
+ * Out of scope: the lossless bypass, MBAFF, luma DC (intra 16x16), I_PCM; 4:2:2 / 4:4:4 are the _fmt faces' below.
  */
 typedef struct FFHipH264ResMb {            /* one macroblock, 16 bytes; parallel to FFHipH264BsMb */
     int32_t coeff_offset;                  /* in coefficients into FFHipH264ResPic.coeffs; a multiple of 16 */
     uint8_t chroma;                        /* bit j: Cb 4x4 block j has coefficients; bit 4 + j: Cr block j (j = x + 2*y) */
     uint8_t chroma_dc;                     /* bit 0: Cb DC coded (chroma_dc_dequant_idct runs on it); bit 1: Cr */
-    uint8_t pad[2];
-    int32_t qmul[2];                       /* Cb, Cr: the decoder's dequant4_coeff[4 + c][chroma qp][0] */
+    uint8_t chroma_lo422;                  /* read at chroma_format_idc 2 alone (the _fmt faces): bit j - 4: Cb block j = 4..7 of the
+                                              8 x 16 chroma, bit 4 + (j - 4): Cr block j; without effect at any other format */
+    uint8_t pad;
+    union {
+        int32_t qmul[2];                   /* Cb, Cr: the decoder's dequant4_coeff[4 + c][chroma qp][0]; 4:2:2: [1 + c][chroma_qp[c] + 3][0] */
+        uint32_t nnz444[2];                /* chroma_format_idc 3 alone (no chroma DC there): the low 16 bits are the non-zero bits of
+                                              Cb, Cr in FFHipH264BsMb.nnz's layout */
+    };
 } FFHipH264ResMb;
 typedef struct FFHipH264ResPic {           /* _dev: device pointers, _host: host pointers; 80 bytes */
     uint8_t *dst[3];                       /* as FFHipH264InterPic: Cb and Cr both NULL = monochrome */
@@ -854,6 +861,56 @@ int ffhip_h264_residual_pictures_dev(int bit_depth, int chroma_format_idc, int m
 /** The same rules compiled for the CPU, on host arrays (device-free): the same arguments, refusals but FFHIP_ENOSYS without a
  *  device, and bytes.  The _dev face never calls it. */
 int ffhip_h264_residual_pictures_host(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264ResPic *pics);
+
+/**
+ * The two faces above at every chroma format: chroma_format_idc 0 .. 3.  The existing four entry points keep their behaviour; for
+ * chroma_format_idc 0 and 1 the _fmt faces give their bytes and return values (the same launcher, the same kernel instantiation).
+ * The records are the same; the chroma planes are 8*mb_w x 8*mb_h at 4:2:0, 8*mb_w x 16*mb_h at 4:2:2 and 16*mb_w x 16*mb_h at 4:4:4,
+ * and that size is the one of the stride minimum, of the spans and of the row-overlap rule.  Cb and Cr both NULL: luma only, at
+ * every format.
+ *
+ * ffhip_h264_inter_pictures_fmt_dev: rules 1, 2, 3 and 5 to 10 of ffhip_h264_inter_pictures_dev; rule 4 by format, for the 4x4 luma
+ * block at (bx, by) in 4x4 units:
+ *  4a. chroma_format_idc 1: rule 4 as it stands (the block's 2x2 chroma block at (2*bx, 2*by)).
+ *  4b. chroma_format_idc 2: the block owns the chroma block 2 wide x 4 tall at (2*bx, 4*by) of each chroma plane.  Per list
+ *      cx = mvx, cy = mvy; origin the sample's position plus (cx >> 3, cy >> 2); h264chroma's put with the fractions
+ *      (cx & 7, (cy << 1) & 7) (mc_dir_part with ysh = 2); coordinates clamped to 8*mb_w x 16*mb_h.  ref.chroma_dy is not read: the
+ *      reference applies it at 4:2:0 alone.  The lists combine by rules 5 to 9 with the chroma values.
+ *  4c. chroma_format_idc 3: Cb and Cr have luma's geometry: every sample of plane 1 + c is rule 3 (h264qpel with the luma vector and
+ *      the luma clamps) on ref.base[1 + c] / ref.stride[1 + c], and the lists combine by rules 5 to 9 with the CHROMA values
+ *      (chroma_weight, chroma_log2_denom, use_weight_chroma under rule 8), which the reference hands to the luma-width weight
+ *      functions.  ref.chroma_dy is not read.
+ * FFHIP_EINVAL for a chroma_format_idc outside 0 .. 3 and for everything ffhip_h264_inter_pictures_dev refuses, with the format's
+ * plane sizes; FFHIP_ENOSYS without a device (after the argument checks).
+ */
+int ffhip_h264_inter_pictures_fmt_dev(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics,
+                                      const FFHipH264InterPic *pics /* host array */, void *stream);
+/** The same rules compiled for the CPU (device-free): every pointer of the records is a host pointer; the same arguments, refusals
+ *  but FFHIP_ENOSYS, and bytes, at chroma_format_idc 0 .. 3.  The _dev face never calls it. */
+int ffhip_h264_inter_pictures_fmt_host(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264InterPic *pics);
+/**
+ * ffhip_h264_residual_pictures_fmt_dev: rules 1 to 12 of ffhip_h264_residual_pictures_dev, and by format:
+ * 13. chroma_format_idc 0 / 1: r.chroma_lo422 is not read.
+ * 14. chroma_format_idc 2: a chroma plane has eight 4x4 blocks j = x + 2*y (x 0..1, y 0..3) at (4x, 4y) of the macroblock's 8 x 16
+ *     chroma; Cb block j lies at 256 + 16*j, Cr block j at 512 + 16*j (sl->mb at 4:2:2).  The bits of blocks 0..3 are r.chroma's, those
+ *     of blocks 4..7 r.chroma_lo422's (bit j - 4 Cb, bit 4 + (j - 4) Cr).  need (rule 2) is 768 where the picture has chroma planes and
+ *     r.chroma | r.chroma_lo422 | r.chroma_dc is non-zero.  With the plane's chroma_dc bit the eight first coefficients go through
+ *     chroma422_dc_dequant_idct with r.qmul[c] in the reference's unsigned arithmetic, truncated to the coefficient type, and all
+ *     eight blocks are added by rule 6; without it rule 7 runs over the eight blocks.
+ * 15. chroma_format_idc 3: plane p (0, 1, 2) is a luma plane whose coefficients lie at 256*p + the luma layout; rules 4, 5 and 9 run
+ *     per plane with the plane's own bits: m.nnz for plane 0, the low 16 bits of r.nnz444[0] / [1] for planes 1 / 2, in m.nnz's layout
+ *     and under its contract (with the 8x8 flag the four bits of an 8x8 block are equal).  The 8x8 flag of m.flags holds for all three
+ *     planes.  r.chroma, r.chroma_dc and r.chroma_lo422 are not read.  need is 768 where the picture has chroma planes and
+ *     (nnz444[0] | nnz444[1]) & 0xFFFF is non-zero, else 256 if m.nnz is non-zero, else 0; without chroma planes nnz444 is ignored.
+ * FFHIP_EINVAL for a chroma_format_idc outside 0 .. 3 and for everything ffhip_h264_residual_pictures_dev refuses, with the format's
+ * plane sizes; FFHIP_ENOSYS without a device (after the argument checks).
+ * Out of scope at every format: the edge-parameter chroma tables of 4:2:2 / 4:4:4 (the caller builds those FFHipH264Edge tables),
+ * MBAFF, the lossless bypass, luma DC / I_PCM.
+ */
+int ffhip_h264_residual_pictures_fmt_dev(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics,
+                                         const FFHipH264ResPic *pics /* host array */, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free).  The _dev face never calls it. */
+int ffhip_h264_residual_pictures_fmt_host(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics, const FFHipH264ResPic *pics);
 /** sizeof(FFHipH264ResMb), sizeof(FFHipH264ResPic), for bindings that mirror the records (no device needed). */
 int ffhip_h264_res_mb_record_size(void);
 int ffhip_h264_res_pic_record_size(void);
