@@ -354,6 +354,10 @@ def lib():
         "ffhip_h264_bs_mb_record_size": (C.c_int, []),
         "ffhip_h264_bs_mvf_record_size": (C.c_int, []),
         "ffhip_h264_bs_slice_record_size": (C.c_int, []),
+        "ffhip_h264_edge_params_pictures_fmt_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "ffhip_h264_edge_params_pictures_fmt_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "ffhip_h264_deblock_pictures_fmt_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_ssize_t, C.c_int, vp, vp]),
+        "ffhip_h264_lf_pic_record_size": (C.c_int, []),
         "ffhip_h264_inter_pictures_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_h264_inter_pictures_fmt_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "ffhip_h264_inter_pictures_fmt_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),

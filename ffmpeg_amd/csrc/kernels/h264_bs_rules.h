@@ -126,14 +126,16 @@ H264BS_FN int h264bs_check_mv(const H264BsBlk &p, const H264BsBlk &q, bool two_l
 
 /* Rules 1 and 2 of edge e of direction dir of macroblock q: the bS of group g in byte g, 0 for a skipped edge.  p: the macroblock
  * across edge 0 (anything at the border), q itself otherwise.  blk(x, y): the resolved block x, y of q in 4x4 blocks, -1 being the
- * last column / row of the macroblock to the left / above; called for blocks inside the picture only. */
+ * last column / row of the macroblock to the left / above; called for blocks inside the picture only.
+ * c422h: the edge is a chroma edge of the horizontal direction of a 4:2:2 picture (rule 6): the 8x8-transform clause of rule 1 does
+ * not hold for it, everything else does. */
 template <class Blk>
-H264BS_FN uint32_t h264bs_edge_bs(const H264BsMb &p, const H264BsMb &q, bool border, int dir, int e, int field, Blk &&blk)
+H264BS_FN uint32_t h264bs_edge_bs(const H264BsMb &p, const H264BsMb &q, bool border, int dir, int e, int field, Blk &&blk, bool c422h = false)
 {
     if (!(q.b & H264BS_SLICE_OK))
         return 0;
     const unsigned idc = (q.b >> H264BS_IDC_SHIFT) & 3;
-    if (idc == 1 || ((e & 1) && (q.b & H264BS_T8X8)))
+    if (idc == 1 || (!c422h && (e & 1) && (q.b & H264BS_T8X8)))
         return 0;
     if (!e && (border || (idc == 2 && (p.a & 0xFFFF) != (q.a & 0xFFFF))))
         return 0;
@@ -164,7 +166,9 @@ H264BS_FN int h264bs_edge_qp(const H264BsMb &p, const H264BsMb &q, int e, const 
 
 H264BS_FN int h264bs_clip51(int v) { return v < 0 ? 0 : v > 51 ? 51 : v; }
 
-/* rules 3 .. 5: the record of an edge as three little-endian dwords (offset; kind, alpha, beta, pad; tc0[4]) */
+/* rules 3 .. 5: the record of an edge as three little-endian dwords (offset; kind, alpha, beta, pad; tc0[4]).  chroma chooses the
+ * kinds and the tc0 convention, not the plane: true for the Cb / Cr records of 4:2:0 and 4:2:2 (*_CHROMA kinds, tc0' + 1, 0 at bS 0),
+ * false for luma and for the Cb / Cr records of 4:4:4 (rule 7: the luma kinds, tc0', -1 at bS 0), whose qp is the plane's all the same. */
 H264BS_FN void h264bs_pack(bool chroma, int dir, uint32_t bs, int qp, const H264BsMb &q, int qp_bd_offset, uint32_t out[3])
 {
     const uint32_t kind = (chroma ? FFHIP_H264_LF_V_CHROMA : FFHIP_H264_LF_V_LUMA) + (dir ? 0 : 1);

@@ -124,8 +124,9 @@ int ffhip_launch_hevc_loop_filter_pictures(int bd, int chroma_format_idc, int wi
                                            const FFHipHevcLfPic *pics, hipStream_t stream);
 /* HEVC deblocking boundary strengths of whole pictures (hevc_bs_pic.hip), arguments validated by ffhip_hevc_boundary_strengths_pictures_dev() */
 int ffhip_launch_hevc_boundary_strengths_pictures(int width, int height, int log2_ctb, int npics, const FFHipHevcBsPic *pics, hipStream_t stream);
-/* H.264 deblocking edge parameters of whole pictures (h264_bs_pic.hip), arguments validated by ffhip_h264_edge_params_pictures_dev() */
-int ffhip_launch_h264_edge_params_pictures(int mb_w, int mb_h, int field, int qp_bd_offset, int npics, const FFHipH264BsPic *pics,
+/* H.264 deblocking edge parameters of whole pictures (h264_bs_pic.hip), arguments validated by ffhip_h264_edge_params_pictures_dev() /
+ * _fmt_dev(); fmt: the format of the chroma tables, 1 .. 3 (monochrome: 1 with NULL cb / cr) */
+int ffhip_launch_h264_edge_params_pictures(int fmt, int mb_w, int mb_h, int field, int qp_bd_offset, int npics, const FFHipH264BsPic *pics,
                                            hipStream_t stream);
 /* H.264 inter prediction of whole pictures (h264_inter_pic.hip), chroma_format_idc 0 .. 3; arguments validated by
  * ffhip_h264_inter_pictures_dev() / _fmt_dev() */

@@ -170,6 +170,55 @@ def edge_params_pictures_host(pics, mb_w, mb_h, field=0, qp_bd_offset=0):
                       "ffhip_h264_edge_params_pictures_host")
 
 
+#: records of a macroblock in the cb / cr tables of edge_params_pictures_fmt(), by chroma_format_idc
+EDGE_CHROMA_RECORDS = (0, 4, 6, 8)
+
+
+def edge_params_pictures_fmt(pics, mb_w, mb_h, field=0, qp_bd_offset=0, chroma_format_idc=1, stream=None):
+    """ffhip_h264_edge_params_pictures_fmt_dev: edge_params_pictures() at chroma_format_idc 0 .. 3.  cb / cr hold
+    EDGE_CHROMA_RECORDS[chroma_format_idc] records per macroblock: 4:2:2 six ([mb * 6 + k]: the vertical edges x = 0, 4, then the
+    horizontal y = 0, 4, 8, 12), 4:4:4 eight in luma's layout and conventions; at 0 chroma_qp / cb / cr are ignored, at 1 the bytes are
+    edge_params_pictures()'s.  The tables are what deblock_pictures_fmt() takes.  Asynchronous on `stream`."""
+    arr = _bs_pics(pics, lambda t: t.data_ptr())
+    return _lib.check(_lib.lib().ffhip_h264_edge_params_pictures_fmt_dev(chroma_format_idc, mb_w, mb_h, field, qp_bd_offset, len(pics),
+                                                                         C.cast(arr, C.c_void_p), _stream(stream)),
+                      "ffhip_h264_edge_params_pictures_fmt_dev")
+
+
+def edge_params_pictures_fmt_host(pics, mb_w, mb_h, field=0, qp_bd_offset=0, chroma_format_idc=1):
+    """ffhip_h264_edge_params_pictures_fmt_host (device-free): as edge_params_pictures_fmt() with numpy arrays; luma / cb / cr are
+    written in place."""
+    arr = _bs_pics(pics, lambda a: a.ctypes.data)
+    return _lib.check(_lib.lib().ffhip_h264_edge_params_pictures_fmt_host(chroma_format_idc, mb_w, mb_h, field, qp_bd_offset, len(pics),
+                                                                          C.cast(arr, C.c_void_p)), "ffhip_h264_edge_params_pictures_fmt_host")
+
+
+class LfPic(C.Structure):
+    """FFHipH264LfPic"""
+    _fields_ = [("plane", C.c_void_p * 3), ("edges", C.c_void_p * 3)]
+
+
+def lf_pics(pics):
+    """the FFHipH264LfPic array of deblock_pictures_fmt()'s dicts (the caller keeps the tensors)"""
+    arr = (LfPic * max(len(pics), 1))()
+    ptr = lambda t: None if t is None else t if isinstance(t, int) else t.data_ptr()
+    for i, m in enumerate(pics):
+        for p in range(3):
+            arr[i].plane[p] = ptr(m["planes"][p]) if p < len(m["planes"]) else None
+            arr[i].edges[p] = ptr(m["edges"][p]) if p < len(m["edges"]) else None
+    return arr
+
+
+def deblock_pictures_fmt(pics, mb_w, mb_h, stride_y, stride_c, bit_depth=8, chroma_format_idc=1, stream=None):
+    """ffhip_h264_deblock_pictures_fmt_dev: frame-order deblocking of npics = len(pics) whole pictures at chroma_format_idc 0 .. 3.
+    pics[i]: a dict with planes (up to three device tensors or addresses) and edges (their tables, the luma / cb / cr of
+    edge_params_pictures_fmt(); None: the plane is not filtered).  stride_y / stride_c in bytes.  Asynchronous on `stream`."""
+    arr = lf_pics(pics)
+    return _lib.check(_lib.lib().ffhip_h264_deblock_pictures_fmt_dev(bit_depth, chroma_format_idc, mb_w, mb_h, stride_y, stride_c, len(pics),
+                                                                     C.cast(arr, C.c_void_p), _stream(stream)),
+                      "ffhip_h264_deblock_pictures_fmt_dev")
+
+
 #: FFHipH264InterSlice (include/ffhip.h): what the inter face reads from a slice.  ref[list][ref_idx] -> slot of InterPic.ref;
 #: luma_weight[ref_idx][list][weight, offset]; chroma_weight[ref_idx][list][Cb, Cr][weight, offset]; implicit_weight[ref_idx0][ref_idx1].
 INTER_SLICE_DTYPE = np.dtype([("ref", np.uint8, (2, 32)), ("num_ref", np.uint8, 2), ("use_weight", np.uint8), ("use_weight_chroma", np.uint8),

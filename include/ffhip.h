@@ -633,7 +633,7 @@ int ffhip_h264_deblock_frames_dev_hbd(int bit_depth, int chroma, uint8_t *plane,
  *  5. offset and pad are 0.  Every record of every table is written exactly once, nothing else is, and no input is written; malformed
  *     input has the result defined above and never causes an access outside the maps.
  * The records are in the 8-bit units the deblock faces scale by depth.
- * Out of scope: MBAFF, 4:2:2 / 4:4:4 chroma tables.
+ * Out of scope: MBAFF.  The 4:2:2 / 4:4:4 chroma tables are ffhip_h264_edge_params_pictures_fmt_dev's below (rules 6 and 7).
  */
 typedef struct FFHipH264MvField {  /* one 4x4 luma block, 12 bytes, grid w4 = 4*mb_w by h4 = 4*mb_h */
     int16_t mv[2][2];              /* [list][x, y], quarter samples */
@@ -682,6 +682,61 @@ int ffhip_h264_edge_params_pictures_host(int mb_w, int mb_h, int field, int qp_b
 int ffhip_h264_bs_mb_record_size(void);
 int ffhip_h264_bs_mvf_record_size(void);
 int ffhip_h264_bs_slice_record_size(void);
+
+/**
+ * ffhip_h264_edge_params_pictures_fmt_dev: rules 1 to 5 above with the same records, and by chroma_format_idc:
+ * chroma_format_idc 0: no chroma tables: chroma_qp / cb / cr are not read, and nothing is written through them.
+ * chroma_format_idc 1: the face above, its bytes and return values.
+ *  6. chroma_format_idc 2 (4:2:2, chroma macroblocks of 8 x 16 samples): cb / cr hold SIX records per macroblock, [mb*6 + k], the
+ *     layout of ffhip_h264_picture_deblock_mb() and of ffhip_h264_deblock_pictures_fmt_dev below.
+ *     - k = 0, 1: the vertical edges x = 0, 4: luma edges 0 and 2 of dir 0 with rule 1's skips and rule 2's four bS; tc0[g] belongs to
+ *       the 4-line group g (h_loop_filter_chroma422 filters 16 lines with one tc0 per 4 lines).
+ *     - k = 2 .. 5: the horizontal edges y = 0, 4, 8, 12: luma edges e = k - 2 of dir 1; tc0[g] covers two columns, as at 4:2:0.  The
+ *       "e odd and q has the 8x8 transform" clause of rule 1 does NOT hold for these four records: the luma record of such an edge is
+ *       the skipped record, the chroma record carries the bS rule 2 gives the edge (intra 3, a non-zero bit 2, otherwise motion
+ *       decides).  Every other skip of rule 1 holds.
+ *     - qp, indexA / indexB, tc0 = tc0' + 1 (0 at bS 0), the *_CHROMA / *_CHROMA_INTRA kinds and the skipped record as in rule 4.
+ *  7. chroma_format_idc 3 (4:4:4): cb / cr hold EIGHT records per macroblock in the luma layout [(mb*2 + dir)*4 + e], with the LUMA
+ *     kinds and the luma tc0 convention (tc0' without the + 1, -1 at bS 0, a skipped record's tc0 {-1,-1,-1,-1}).  Every skip of rule 1
+ *     holds for all three planes, the 8x8-transform one included; bS is the luma edge's; qp from chroma_qp[c] as in rule 4 (the average
+ *     of the two looked-up values on e = 0, q's otherwise).  The tables ffhip_h264_deblock_frames_dev / _dev_hbd(chroma = 0),
+ *     ffhip_h264_deblock_pictures_fmt_dev and ffhip_h264_picture_deblock_mb() take for planes 1 and 2 of a 4:4:4 picture.
+ * Rule 5 holds at every format.  Rule 6 restates filter_mb_dir() of libavcodec/h264_loopfilter.c ("if (!deblock_edge && (!chroma422 ||
+ * dir == 0)) continue;", chroma filtered at 4 * edge * uvlinesize on every edge of dir 1); restated, NOT checked against the source,
+ * which the build does not have.
+ * FFHIP_EINVAL for a chroma_format_idc outside 0 .. 3 and for everything the face above refuses, the overlap spans computed with the
+ * format's table sizes (mb_w * mb_h * 4, 6 or 8 records in cb / cr; at 0 cb, cr and chroma_qp are not looked at); FFHIP_ENOSYS without
+ * a device (after the argument checks).  Out of scope: MBAFF.
+ */
+int ffhip_h264_edge_params_pictures_fmt_dev(int chroma_format_idc, int mb_w, int mb_h, int field, int qp_bd_offset, int npics,
+                                            const FFHipH264BsPic *pics /* host array */, void *stream);
+/** The same rules compiled for the CPU, on host arrays (device-free): the same arguments, refusals but FFHIP_ENOSYS, and bytes.
+ *  The _dev face never calls it. */
+int ffhip_h264_edge_params_pictures_fmt_host(int chroma_format_idc, int mb_w, int mb_h, int field, int qp_bd_offset, int npics,
+                                             const FFHipH264BsPic *pics);
+
+/**
+ * Frame-order deblocking of npics whole pictures of mb_w x mb_h macroblocks at chroma_format_idc 0 .. 3 and bit_depth 8, 9, 10, 12 or
+ * 14, from the tables of ffhip_h264_edge_params_pictures_fmt_dev (or a caller's own in the same layouts).  No kernel of its own: plane 0
+ * at every format, and all three planes at 4:4:4, go through the luma filter of ffhip_h264_deblock_frames_dev / _dev_hbd; Cb / Cr of
+ * 4:2:0 through the chroma filter of ffhip_h264_deblock_frames_chroma_dev / _dev_hbd(chroma = 1), whose bytes they are; Cb / Cr of
+ * 4:2:2 (8 x 16 samples a macroblock, six records each: rule 6 above) through the 4:2:2 frame-order filter the picture object's flush
+ * uses, the chroma planes of all pictures side by side.  At format 0 plane[1], plane[2] and their tables are ignored.  A NULL edges[p]
+ * skips plane p.  stride_y: plane 0; stride_c: planes 1 and 2; both in bytes.  Samples above 8 bits are uint16_t.
+ * Asynchronous on `stream`; the planes are complete for work queued behind the call on `stream`.
+ * The face inherits the launchers' limits: at 8 bits every plane, stride and edge table 4-byte aligned; above 8 bits 16-byte aligned,
+ * but for the 4:2:2 chroma planes and stride_c (8 bytes) and their tables (4 bytes); mb_w and mb_h 1 .. 4096, which is within the
+ * progress pool's 8191 macroblock rows.  FFHIP_EINVAL with a text for another bit_depth, format or size, npics <= 0 or NULL pics, a
+ * table without its plane, or a misaligned plane, stride or table; FFHIP_ENOSYS without a device (after the argument checks).
+ */
+typedef struct FFHipH264LfPic {
+    uint8_t *plane[3];              /* device pointers */
+    const FFHipH264Edge *edges[3];  /* device pointers; NULL: the plane is not filtered */
+} FFHipH264LfPic;
+int ffhip_h264_deblock_pictures_fmt_dev(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, ptrdiff_t stride_y, ptrdiff_t stride_c,
+                                        int npics, const FFHipH264LfPic *pics /* host array */, void *stream);
+/** sizeof(FFHipH264LfPic), for bindings that mirror the record (no device needed). */
+int ffhip_h264_lf_pic_record_size(void);
 
 /**
  * The inter prediction of whole H.264 pictures in one launch, from the same two arrays the edge-parameter face above takes (mb, mvf)
@@ -904,8 +959,9 @@ int ffhip_h264_inter_pictures_fmt_host(int bit_depth, int chroma_format_idc, int
  *     (nnz444[0] | nnz444[1]) & 0xFFFF is non-zero, else 256 if m.nnz is non-zero, else 0; without chroma planes nnz444 is ignored.
  * FFHIP_EINVAL for a chroma_format_idc outside 0 .. 3 and for everything ffhip_h264_residual_pictures_dev refuses, with the format's
  * plane sizes; FFHIP_ENOSYS without a device (after the argument checks).
- * Out of scope at every format: the edge-parameter chroma tables of 4:2:2 / 4:4:4 (the caller builds those FFHipH264Edge tables),
- * MBAFF, the lossless bypass, luma DC / I_PCM.
+ * Out of scope at every format: MBAFF, the lossless bypass, luma DC / I_PCM.  The FFHipH264Edge tables of every format are
+ * ffhip_h264_edge_params_pictures_fmt_dev's and the filter ffhip_h264_deblock_pictures_fmt_dev's (above), behind this face and
+ * ffhip_h264_inter_pictures_fmt_dev on the same stream.
  */
 int ffhip_h264_residual_pictures_fmt_dev(int bit_depth, int chroma_format_idc, int mb_w, int mb_h, int npics,
                                          const FFHipH264ResPic *pics /* host array */, void *stream);

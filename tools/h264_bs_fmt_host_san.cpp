@@ -1,12 +1,14 @@
 /*
- * tools/h264_bs_host_san.cpp — a stand-alone host program over ffhip_h264_edge_params_pictures_host() for AddressSanitizer and
- * UBSan: random and malformed pictures (slice indices, ref_idx and qp out of range, num_ref 33) in heap blocks exactly as large as the
- * geometry says, so a read or write outside a map is an error the sanitizer reports.  CPU only: nothing here touches a device.
+ * tools/h264_bs_fmt_host_san.cpp — a stand-alone host program over ffhip_h264_edge_params_pictures_fmt_host() for AddressSanitizer and
+ * UBSan: at chroma_format_idc 0 .. 3, a 1 x 1 picture and random and malformed pictures (slice indices, ref_idx and qp out of range,
+ * num_ref 33) in heap blocks exactly as large as the geometry and the format say (cb / cr: 4, 6 or 8 records a macroblock), so a read
+ * or write outside a map is an error the sanitizer reports.  At format 0 cb / cr / chroma_qp point at four-byte blocks: touching them
+ * at all is an error.  CPU only: nothing here touches a device.
  *
  * Build and run from the repository root (the face's file and this one, nothing else of the library):
  *   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
  *         --offload-arch=gfx950 -Iinclude -Iffmpeg_amd/csrc -Iffmpeg_amd/csrc/host ffmpeg_amd/csrc/shims_h264_bs.hip \
- *         tools/h264_bs_host_san.cpp -o h264_bs_host_san && ./h264_bs_host_san
+ *         tools/h264_bs_fmt_host_san.cpp -o h264_bs_fmt_host_san && ./h264_bs_fmt_host_san
  * Prints a checksum of the tables per case and "ok"; the sanitizer aborts on the first finding.
  */
 #include <stdarg.h>
@@ -14,8 +16,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-
-#include <vector>
 
 #include "ffhip.h"
 
@@ -32,7 +32,7 @@ int ffhip_have_device(void) { return 0; }
 struct ihipStream_t;
 int ffhip_launch_h264_edge_params_pictures(int, int, int, int, int, int, const FFHipH264BsPic *, ihipStream_t *) { return FFHIP_ENOSYS; }
 
-static uint32_t rnd_state = 12345;
+static uint32_t rnd_state = 777;
 static uint32_t rnd(void)
 {
     rnd_state = rnd_state * 1664525u + 1013904223u;
@@ -45,17 +45,22 @@ static T *block(size_t n)
     return static_cast<T *>(malloc(n * sizeof(T) ? n * sizeof(T) : 1));
 }
 
-static int run(int mb_w, int mb_h, int field, int bd_off, int nslices, int pad, bool chroma, bool malformed)
+static int run(int fmt, int mb_w, int mb_h, int field, int bd_off, int nslices, int pad, bool malformed)
 {
-    const size_t nmb = (size_t)mb_w * mb_h;
+    const size_t nmb = (size_t)mb_w * mb_h, per = fmt == 3 ? 8 : fmt == 2 ? 6 : 4;
     const int w4 = 4 * mb_w, h4 = 4 * mb_h, stride = w4 + pad;
     /* the last row of the motion field ends with the picture, not with the stride */
     const size_t nmvf = (size_t)(h4 - 1) * stride + w4;
     FFHipH264BsMb *mb = block<FFHipH264BsMb>(nmb);
     FFHipH264MvField *mvf = block<FFHipH264MvField>(nmvf);
     FFHipH264BsSlice *slices = block<FFHipH264BsSlice>(nslices);
-    uint8_t *cqp = block<uint8_t>(176);
-    FFHipH264Edge *luma = block<FFHipH264Edge>(nmb * 8), *cb = block<FFHipH264Edge>(nmb * 4), *cr = block<FFHipH264Edge>(nmb * 4);
+    /* format 0: four-byte blocks that nothing may touch (the face does not even look at their alignment) */
+    uint8_t *cqp = block<uint8_t>(fmt ? 176 : 4);
+    FFHipH264Edge *luma = block<FFHipH264Edge>(nmb * 8);
+    FFHipH264Edge *cb = fmt ? block<FFHipH264Edge>(nmb * per) : (FFHipH264Edge *)block<uint8_t>(4);
+    FFHipH264Edge *cr = fmt ? block<FFHipH264Edge>(nmb * per) : (FFHipH264Edge *)block<uint8_t>(4);
+    if (!fmt)
+        memset(cqp, 0x5A, 4), memset(cb, 0x5A, 4), memset(cr, 0x5A, 4);
     for (size_t i = 0; i < nmb; i++) {
         mb[i].slice = (uint16_t)(malformed && rnd() % 8 == 0 ? rnd() : (i * nslices) / nmb);
         mb[i].nnz = (uint16_t)(rnd() & rnd() & rnd());
@@ -85,23 +90,25 @@ static int run(int mb_w, int mb_h, int field, int bd_off, int nslices, int pad, 
     }
     if (malformed)
         slices[0].num_ref[0] = 33;
-    for (int i = 0; i < 176; i++)
+    for (int i = 0; fmt && i < 176; i++)
         cqp[i] = (uint8_t)(malformed ? rnd() : i % 88);
     FFHipH264BsPic pic;
     memset(&pic, 0, sizeof(pic));
     pic.mb = mb; pic.mvf = mvf; pic.slices = slices; pic.luma = luma;
-    if (chroma) {
-        pic.chroma_qp = cqp; pic.cb = cb; pic.cr = cr;
-    }
+    pic.chroma_qp = cqp; pic.cb = cb; pic.cr = cr;
     pic.mvf_stride = stride; pic.nslices = nslices;
-    const int r = ffhip_h264_edge_params_pictures_host(mb_w, mb_h, field, bd_off, 1, &pic);
+    int r = ffhip_h264_edge_params_pictures_fmt_host(fmt, mb_w, mb_h, field, bd_off, 1, &pic);
     uint32_t sum = 0;
     const uint8_t *tabs[3] = { (const uint8_t *)luma, (const uint8_t *)cb, (const uint8_t *)cr };
-    for (int t = 0; t < (chroma ? 3 : 1); t++)
-        for (size_t i = 0; i < nmb * (t ? 4 : 8) * sizeof(FFHipH264Edge); i++)
+    for (int t = 0; t < (fmt ? 3 : 1); t++)
+        for (size_t i = 0; i < nmb * (t ? per : 8) * sizeof(FFHipH264Edge); i++)
             sum = sum * 31 + tabs[t][i];
-    printf("%d x %d field %d bd_off %d slices %d pad %d chroma %d malformed %d: rc %d checksum %08x\n", mb_w, mb_h, field, bd_off, nslices, pad,
-           (int)chroma, (int)malformed, r, sum);
+    if (!fmt)
+        for (int i = 0; i < 4; i++)
+            if (cqp[i] != 0x5A || ((uint8_t *)cb)[i] != 0x5A || ((uint8_t *)cr)[i] != 0x5A)
+                r = -1;
+    printf("format %d, %d x %d field %d bd_off %d slices %d pad %d malformed %d: rc %d checksum %08x\n", fmt, mb_w, mb_h, field, bd_off, nslices,
+           pad, (int)malformed, r, sum);
     free(mb); free(mvf); free(slices); free(cqp); free(luma); free(cb); free(cr);
     return r;
 }
@@ -110,12 +117,18 @@ int main(void)
 {
     int bad = 0;
     const int bd[5] = { 0, 6, 12, 24, 36 };
-    for (int k = 0; k < 20; k++) {
-        const int mb_w = 1 + (int)(rnd() % 11), mb_h = 1 + (int)(rnd() % 9);
-        bad |= run(mb_w, mb_h, k & 1, bd[k % 5], 1 + (int)(rnd() % 4), (int)(rnd() % 4), (k & 2) != 0, k >= 6) != 0;
+    for (int fmt = 0; fmt < 4; fmt++) {
+        bad |= run(fmt, 1, 1, 0, 0, 1, 0, false) != 0;
+        bad |= run(fmt, 1, 1, 1, 12, 1, 2, true) != 0;
+        for (int k = 0; k < 10; k++) {
+            const int mb_w = 1 + (int)(rnd() % 11), mb_h = 1 + (int)(rnd() % 9);
+            bad |= run(fmt, mb_w, mb_h, k & 1, bd[k % 5], 1 + (int)(rnd() % 4), (int)(rnd() % 4), k >= 2) != 0;
+        }
+        bad |= run(fmt, 9, 7, 0, 0, 3, 2, true) != 0;
+        bad |= run(fmt, 120, 68, 1, 12, 4, 3, true) != 0;
     }
-    bad |= run(120, 68, 0, 0, 4, 0, true, false) != 0;
-    bad |= run(120, 68, 1, 12, 4, 3, true, true) != 0;
+    /* a call that the checks refuse must not touch anything either */
+    bad |= ffhip_h264_edge_params_pictures_fmt_host(4, 1, 1, 0, 0, 1, nullptr) != FFHIP_EINVAL;
     puts(bad ? "FAILED" : "ok");
     return bad;
 }
